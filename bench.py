@@ -6,7 +6,10 @@ random-init with the Paraformer-large architecture (no network for the ModelScop
 = one pass of the hot path (PCM resident in HBM -> fbank/LFR/CMVN -> 50-layer SAN-M encoder ->
 CIF predictor -> 16-layer decoder -> log-softmax/argmax -> token ids back on the host) over one batch.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K headline steps and prints one JSON line; --dump-outputs writes what the last
+timed step returned as DIR/<name>.npy; --full adds everything else (back-to-back and host-buffer timings, the roofline,
+the C3 / C4 / C5 blocks, the CPU baseline and the cross-checks between them).
 N > 1 is launched by the driver through torch.distributed.run, one rank per GPU; utterance batches
 are sharded over ranks as independent replicas (no data-path collective), the only
 communication is the timing barrier / max-over-ranks.
@@ -293,6 +296,18 @@ def cpu_baseline(man, blob, utts, seconds_per_utt):
                       f"batch 1 per call, numpy/OpenBLAS fp32 CPU restatement (not onnxruntime); wall {wall:.1f} s"}
 
 
+def dump_outputs(dirname, res, max_tokens):
+    """What the timed path's caller received in the last timed step (forward_resident's dict), as float64 .npy files:
+    ids [batch, max_tokens] padded with -1, and token_num / n_fires / n_frames [batch]."""
+    os.makedirs(dirname, exist_ok=True)
+    ids = np.full((len(res["ids"]), max_tokens), -1.0, np.float64)
+    for b, x in enumerate(res["ids"]):
+        ids[b, :len(x)] = x
+    np.save(os.path.join(dirname, "ids.npy"), ids)
+    for k in ("token_num", "n_fires", "n_frames"):
+        np.save(os.path.join(dirname, k + ".npy"), np.asarray(res[k], np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -300,13 +315,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--seconds", type=int, default=SECONDS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
-    ap.add_argument("--no-streaming", action="store_true", help="skip the C3 streaming block (rank 0, N = 1 only)")
-    ap.add_argument("--no-c4c5", action="store_true", help="skip the C4 (hotword + timestamp) and C5 (long audio) blocks (rank 0, N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: back-to-back and host-buffer timings, the roofline, "
+                         "the C3 / C4 / C5 blocks and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not bracket kernels with HIP events")
+    ap.add_argument("--no-streaming", action="store_true", help="with --full: skip the C3 streaming block (rank 0, N = 1 only)")
+    ap.add_argument("--no-c4c5", action="store_true", help="with --full: skip the C4 (hotword + timestamp) and C5 (long audio) blocks (rank 0, N = 1 only)")
     ap.add_argument("--in-flight", type=int, default=3,
                     help="batches in flight per GPU in the timed region behind `value` (execution contexts of the one handle, one caller "
-                         "thread each); 1 = back to back.  The back-to-back figures and the roofline are always measured too")
+                         "thread each); 1 = back to back.  With --full the back-to-back figures and the roofline are measured too")
     args = ap.parse_args()
 
     import torch
@@ -354,13 +374,18 @@ def main():
     # the ONE handle (pfhip_set_inflight: one weight set, n workspaces), n_fly caller threads, PCM resident in HBM.
     n_fly = max(1, args.in_flight)
     last_of_thread = [None] * n_fly
+    last_step = [None]              # the result of the step that finished last, whichever thread ran it
+    last_lock = threading.Lock()
 
     def run_thread(i, k, host):
         for _ in range(k):
             if host:
-                last_of_thread[i] = model.forward_ids(utts, max_tokens=max_tokens)
+                r = model.forward_ids(utts, max_tokens=max_tokens)
             else:
-                last_of_thread[i] = model.forward_resident(d_pcm.data_ptr(), sample_off, n_samples, max_tokens)
+                r = model.forward_resident(d_pcm.data_ptr(), sample_off, n_samples, max_tokens)
+            last_of_thread[i] = r
+            with last_lock:
+                last_step[0] = r
 
     def steps_in_flight(k, host=False):
         share = [k // n_fly + (1 if i < k % n_fly else 0) for i in range(n_fly)]
@@ -372,34 +397,35 @@ def main():
 
     for _ in range(args.warmup):
         res = step()
-    # HIP events around the launches of the dominant kernel class only (the fp32 GEMM): bracketing all ~1000
-    # launches of a step costs ~6 % of the step, bracketing the 284 GEMMs ~1 %
-    model.profile_enable(0 if args.no_profile else GEMM_ONLY_MASK)
-    model.profile_read(reset=True)
-    # the driver's contract: exactly K steps bracketed by barrier + synchronize on both sides, MAX over ranks below
-    if dist is not None:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        res = step()
-    torch.cuda.synchronize()
-    if dist is not None:
-        dist.barrier()
-        torch.cuda.synchronize()       # the NCCL/RCCL barrier is enqueued on the stream: wait for it too
-    dt = time.perf_counter() - t0
-    prof = model.profile_read(reset=True)
-    model.profile_enable(0)
-    # a second, untimed pass with every class bracketed gives the per-class breakdown
-    prof_all = None
-    if not args.no_profile:
-        model.profile_enable(1)
-        step()
-        prof_all = model.profile_read(reset=True)
+    if args.full:
+        # HIP events around the launches of the dominant kernel class only (the fp32 GEMM): bracketing all ~1000
+        # launches of a step costs ~6 % of the step, bracketing the 284 GEMMs ~1 %
+        model.profile_enable(0 if args.no_profile else GEMM_ONLY_MASK)
+        model.profile_read(reset=True)
+        # the driver's contract: exactly K steps bracketed by barrier + synchronize on both sides, MAX over ranks below
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            res = step()
+        torch.cuda.synchronize()
+        if dist is not None:
+            dist.barrier()
+            torch.cuda.synchronize()       # the NCCL/RCCL barrier is enqueued on the stream: wait for it too
+        dt = time.perf_counter() - t0
+        prof = model.profile_read(reset=True)
         model.profile_enable(0)
-    dt = max_over_ranks(dt, dist, torch.device("cuda", local_rank))
-    dt_seq = dt
-    # the same K steps, n_fly of them in flight on the one handle: this timed region is the one behind `value`
+        # a second, untimed pass with every class bracketed gives the per-class breakdown
+        prof_all = None
+        if not args.no_profile:
+            model.profile_enable(1)
+            step()
+            prof_all = model.profile_read(reset=True)
+            model.profile_enable(0)
+        dt = max_over_ranks(dt, dist, torch.device("cuda", local_rank))
+        dt_seq = dt
+    # the K steps, n_fly of them in flight on the one handle: this timed region is the one behind `value`
     # (every rank runs the same sequence of collectives: nothing below raises between two barriers)
     try:
         if n_fly > 1:
@@ -418,42 +444,46 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
     dt = max_over_ranks(time.perf_counter() - t0, dist, torch.device("cuda", local_rank))
-    for got in last_of_thread:        # every context, under concurrency, returns what the back-to-back run returned
-        assert got is None or all(list(a) == list(b) for a, b in zip(got["ids"], res["ids"]))
+    res_timed = last_step[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res_timed, max_tokens)
     slots = model.inflight_stats()
-    # the same K steps on the reference's own boundary: host float** buffers in (Model::Forward(float** din, ...), H2D inside
-    # the timed region where paraformer-torch.cpp:355-358 has it), ids out — reported beside `value`, never as `value`:
-    # in flight on the one handle (n_fly caller threads, as the server's decoder threads), then back to back from one thread
-    steps_in_flight(min(max(args.warmup, 1), 2) * n_fly, host=True)
-    if dist is not None:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    steps_in_flight(args.steps, host=True)
-    torch.cuda.synchronize()
-    if dist is not None:
-        dist.barrier()
+    if args.full:
+        for got in last_of_thread:        # every context, under concurrency, returns what the back-to-back run returned
+            assert got is None or all(list(a) == list(b) for a, b in zip(got["ids"], res["ids"]))
+        # the same K steps on the reference's own boundary: host float** buffers in (Model::Forward(float** din, ...), H2D inside
+        # the timed region where paraformer-torch.cpp:355-358 has it), ids out — reported beside `value`, never as `value`:
+        # in flight on the one handle (n_fly caller threads, as the server's decoder threads), then back to back from one thread
+        steps_in_flight(min(max(args.warmup, 1), 2) * n_fly, host=True)
+        if dist is not None:
+            dist.barrier()
         torch.cuda.synchronize()
-    dt_host_fly = max_over_ranks(time.perf_counter() - t0, dist, torch.device("cuda", local_rank))
-    for got in last_of_thread:
-        assert got is None or all(list(a) == list(b) for a, b in zip(got["ids"], res["ids"]))
-    if dist is not None:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        res_h = model.forward_ids(utts, max_tokens=max_tokens)
-    torch.cuda.synchronize()
-    if dist is not None:
-        dist.barrier()
+        t0 = time.perf_counter()
+        steps_in_flight(args.steps, host=True)
         torch.cuda.synchronize()
-    dt_host = max_over_ranks(time.perf_counter() - t0, dist, torch.device("cuda", local_rank))
-    assert all(list(a) == list(b) for a, b in zip(res_h["ids"], res["ids"]))
+        if dist is not None:
+            dist.barrier()
+            torch.cuda.synchronize()
+        dt_host_fly = max_over_ranks(time.perf_counter() - t0, dist, torch.device("cuda", local_rank))
+        for got in last_of_thread:
+            assert got is None or all(list(a) == list(b) for a, b in zip(got["ids"], res["ids"]))
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            res_h = model.forward_ids(utts, max_tokens=max_tokens)
+        torch.cuda.synchronize()
+        if dist is not None:
+            dist.barrier()
+            torch.cuda.synchronize()
+        dt_host = max_over_ranks(time.perf_counter() - t0, dist, torch.device("cuda", local_rank))
+        assert all(list(a) == list(b) for a, b in zip(res_h["ids"], res["ids"]))
 
     x3 = os.environ.get("PFHIP_GEMM_X3", "1") != "0" and os.environ.get("PFHIP_GEMM_X6", "1") != "0"
     audio_per_step = world * args.batch * args.seconds
     value = audio_per_step * args.steps / dt
-    tokens = int(sum(len(x) for x in res["ids"]))
+    tokens = int(sum(len(x) for x in res_timed["ids"]))
 
     if rank == 0:
         out = {
@@ -465,31 +495,34 @@ def main():
                       "fp32 accumulate; error vs fp64 = the fp32 MFMA chain's)" if x3 else
                       "f32 (operands split exactly into 3 bf16 planes, 6 products on the BF16 matrix cores, fp32 accumulate)"),
             "data": "synthetic",
-            "value_host_buffers_in_flight": audio_per_step * args.steps / dt_host_fly,
-            "ms_per_step_host_buffers_in_flight": 1e3 * dt_host_fly / args.steps,
-            "value_host_buffers": audio_per_step * args.steps / dt_host, "ms_per_step_host_buffers": 1e3 * dt_host / args.steps,
-            "value_host_buffers_router": audio_per_step * args.steps / dt_host_fly,
-            "host_buffers_note": "same steps through pfhip_offline_forward(float** host pcm): the 61 MB H2D copy of the batch is "
-                                 "inside the timed region (the reference's Model::Forward boundary); `value` has the PCM resident in HBM. "
-                                 "`value_host_buffers_in_flight`: in_flight caller threads on the ONE handle (the unchanged server's decoder "
-                                 "threads on one shared model); `value_host_buffers`: one thread, back to back; "
-                                 "`value_host_buffers_router`: round-2 key, now the same number as `value_host_buffers_in_flight`",
-            "value_one_in_flight": audio_per_step * args.steps / dt_seq, "ms_per_step_one_in_flight": 1e3 * dt_seq / args.steps,
-            "in_flight_note": f"`value` / `ms_per_step`: the K steps from {n_fly} caller threads on ONE handle whose {n_fly} execution "
-                              "contexts (workspace + stream each) share one weight set (pfhip_set_inflight) — the reference serves with "
-                              "concurrent decoder threads on one shared session; `*_one_in_flight`: the same K steps back to back on "
-                              "context 0 — the round-over-round comparable figure, the timed region the roofline's HIP events bracket "
-                              "(with several batches in flight a launch's event-to-event time is not its own) and the command behind "
-                              "profiles/ (`--in-flight 1`)",
-            "slots": slots,
-            "config": {"workload": f"Paraformer-large offline, batch={args.batch} x {args.seconds} s synthetic 16 kHz "
-                                   f"utterances per GPU (BASELINE.json configs[1])",
-                       "in_flight": n_fly,
-                       "batch_per_gpu": args.batch, "utt_seconds": args.seconds, "lfr_frames_per_utt": int(res["n_frames"][0]),
-                       "tokens_per_batch": tokens, "weights": "random-init Paraformer-large (seed 1234), fp32",
-                       "parallelism": f"replicas x{world} (no collective)", "rtf": 1.0 / value},
         }
-        if not args.no_profile:
+        if args.full:
+            out.update({
+                "value_host_buffers_in_flight": audio_per_step * args.steps / dt_host_fly,
+                "ms_per_step_host_buffers_in_flight": 1e3 * dt_host_fly / args.steps,
+                "value_host_buffers": audio_per_step * args.steps / dt_host, "ms_per_step_host_buffers": 1e3 * dt_host / args.steps,
+                "value_host_buffers_router": audio_per_step * args.steps / dt_host_fly,
+                "host_buffers_note": "same steps through pfhip_offline_forward(float** host pcm): the 61 MB H2D copy of the batch is "
+                                     "inside the timed region (the reference's Model::Forward boundary); `value` has the PCM resident in HBM. "
+                                     "`value_host_buffers_in_flight`: in_flight caller threads on the ONE handle (the unchanged server's decoder "
+                                     "threads on one shared model); `value_host_buffers`: one thread, back to back; "
+                                     "`value_host_buffers_router`: round-2 key, now the same number as `value_host_buffers_in_flight`",
+                "value_one_in_flight": audio_per_step * args.steps / dt_seq, "ms_per_step_one_in_flight": 1e3 * dt_seq / args.steps,
+            })
+        out["in_flight_note"] = (f"`value` / `ms_per_step`: the K steps from {n_fly} caller threads on ONE handle whose {n_fly} execution "
+                                 "contexts (workspace + stream each) share one weight set (pfhip_set_inflight) — the reference serves with "
+                                 "concurrent decoder threads on one shared session; `*_one_in_flight` (--full): the same K steps back to back "
+                                 "on context 0 — the round-over-round comparable figure, the timed region the roofline's HIP events bracket "
+                                 "(with several batches in flight a launch's event-to-event time is not its own) and the command behind "
+                                 "profiles/ (`--in-flight 1`)")
+        out["slots"] = slots
+        out["config"] = {"workload": f"Paraformer-large offline, batch={args.batch} x {args.seconds} s synthetic 16 kHz "
+                                     f"utterances per GPU (BASELINE.json configs[1])",
+                         "in_flight": n_fly,
+                         "batch_per_gpu": args.batch, "utt_seconds": args.seconds, "lfr_frames_per_utt": int(res_timed["n_frames"][0]),
+                         "tokens_per_batch": tokens, "weights": "random-init Paraformer-large (seed 1234), fp32",
+                         "parallelism": f"replicas x{world} (no collective)", "rtf": 1.0 / value}
+        if args.full and not args.no_profile:
             g = prof["gemm"]
             traffic, traffic_source = pmc_traffic()
             ach = g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
@@ -516,14 +549,14 @@ def main():
                 "per_class_tflops_untimed_pass": {k: (v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["ms"] > 0 else 0.0)
                                                   for k, v in prof_all.items() if v["flops"] > 0},
             }
-        if world == 1 and not args.no_streaming:
+        if args.full and world == 1 and not args.no_streaming:
             out["streaming"] = streaming_block(pkg, model, int(blob.nbytes), np.random.default_rng(SEED_PCM + 7))
-        if world == 1 and not args.no_streaming:
+        if args.full and world == 1 and not args.no_streaming:
             try:
                 out["c3_2pass"] = c3_2pass_block(pkg, weights, man, blob)
             except Exception as e:
                 out["c3_2pass"] = {"error": str(e)}
-        if world == 1 and not args.no_c4c5:
+        if args.full and world == 1 and not args.no_c4c5:
             try:
                 out["c5"] = c5_block(pkg, weights, model)
             except Exception as e:
@@ -532,7 +565,7 @@ def main():
                 out["c4"] = c4_block(pkg, weights, utts, args.seconds, n_fly)
             except Exception as e:
                 out["c4"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             workers = min(16, os.cpu_count() or 1)
             out["cpu_baseline"] = cpu_baseline(man, blob, utts[:workers], args.seconds)
             out["cpu_baseline"]["host_cpus"] = os.cpu_count()

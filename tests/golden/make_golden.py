@@ -51,7 +51,18 @@ def main():
     # (5) full-scale clipping: a +-32767 square wave (largest magnitudes the front end can see)
     sq = np.where((np.arange(4000) // 37) % 2 == 0, 32767, -32768).astype(np.int16)
     np.savez_compressed(os.path.join(HERE, "fbank_fullscale.npz"), pcm=sq, fbank=ref_fbank(sq.astype(np.float32) / 32768))
+    write_random()
     print("golden fixtures written")
+
+
+def write_random():
+    """(6) seeded float noise of 400, 1234 and 16000 samples (one frame, a partial hop, one second): w_<n> in, fbank_<n> out."""
+    rng = np.random.default_rng(7)
+    out = {}
+    for n in (400, 1234, 16000):
+        w = (rng.standard_normal(n) * 0.2).clip(-1, 1).astype(np.float32)
+        out[f"w_{n}"], out[f"fbank_{n}"] = w, ref_fbank(w)
+    np.savez_compressed(os.path.join(HERE, "fbank_random.npz"), **out)
 
 
 if __name__ == "__main__":

@@ -130,8 +130,53 @@ def cases():
     return out
 
 
+def random_plans(seed=77, trials=60):
+    """Seeded random plans: yields (sil, waveform, calls, params) per trial; the same sequence on every machine."""
+    rng = np.random.default_rng(seed)
+    pattern = (0.5 * rng.standard_normal(160)).astype(np.float32)
+    for trial in range(trials):
+        runs = [(int(rng.integers(5, 400)), bool(k % 2 == int(trial % 2))) for k in range(int(rng.integers(1, 9)))]
+        sil = scores(rng, runs, noise=float(rng.uniform(0.01, 0.2)), flip=float(rng.uniform(0, 0.1)))
+        T = len(sil)
+        amp = (10.0 ** rng.uniform(-5, 0, T + 2)).astype(np.float32)
+        amp[rng.random(T + 2) < 0.05] = 0.0
+        online = bool(trial % 3 != 0)
+        sizes = [int(v) for v in rng.integers(1, 200, 4)] if trial % 4 else [T]
+        calls = chunks(T, sizes, online, final_empty=bool(trial % 5 == 0 and online))
+        params = (int(rng.choice([200, 500, 800, 1500])), int(rng.choice([1000, 6000, 15000, 60000])), float(rng.choice([0.5, 0.8, 0.9])))
+        yield sil, waveform(amp, pattern), calls, params
+
+
+def ref_plan(lib, sil, w, calls, params):
+    """One plan through a fresh reference detector: int32 [S, 3] as run_plan returns it."""
+    h = lib.e2evad_ref_create()
+
+    def feed(s, wv, fin, on, tail, mx, thr):
+        s = np.ascontiguousarray(s, np.float32)
+        wv = np.ascontiguousarray(wv, np.float32)
+        pairs = np.zeros((len(s) + 8, 2), np.int32)
+        n = lib.e2evad_ref_feed(h, s.ctypes.data, len(s), wv.ctypes.data, len(wv), int(fin), int(on), tail, mx, thr, 16000,
+                                pairs.ctypes.data, len(s) + 8)
+        assert n <= len(s) + 8
+        return [list(map(int, p)) for p in pairs[:n]]
+    try:
+        return run_plan(feed, sil, w, calls, params)
+    finally:
+        lib.e2evad_ref_destroy(h)
+
+
+def write_random_plans(lib):
+    """e2evad_random_plans.npz: the reference's segments for every plan of random_plans(), concatenated
+    (segs int32 [S, 3]; counts int32 [trials] = segments per plan, in order)."""
+    segs = [ref_plan(lib, *p) for p in random_plans()]
+    np.savez_compressed(os.path.join(HERE, "e2evad_random_plans.npz"), segs=np.concatenate(segs).astype(np.int32),
+                        counts=np.asarray([len(s) for s in segs], np.int32))
+    print(f"e2evad_random_plans: {len(segs)} plans, {sum(len(s) for s in segs)} segments")
+
+
 def main():
     lib = load_ref()
+    write_random_plans(lib)
     for name, c in cases().items():
         h = lib.e2evad_ref_create()
 

@@ -1,7 +1,7 @@
 """CPU: pins the oracle's front end against the reference's golden data.
 (i) committed vectors produced by the reference's own knf sources (tests/golden/make_golden.py),
 (ii) the knf known-answer test third_party/kaldi-native-fbank/.../csrc/test-rfft.cc:32-50,
-(iii) live comparison with oracle/_ref/libknf_ref.so when it has been built,
+(iii) seeded noise against stored reference frames, and against the live oracle/_ref/libknf_ref.so where it has been built,
 (iv) hand-derived known answers for LfrCmvn / LoadCmvn / GetPosEmb."""
 import ctypes
 import math
@@ -50,18 +50,23 @@ def test_num_frames_snip_edges():
 
 
 def test_live_reference_build_if_present():
+    """Seeded noise against the reference's fbank of it (tests/golden/fbank_random.npz); where oracle/_ref/libknf_ref.so has
+    been built, the live reference must still return exactly the stored frames."""
+    g = np.load(os.path.join(GOLD, "fbank_random.npz"))
     so = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libknf_ref.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built on this machine")
-    lib = ctypes.CDLL(so)
-    lib.knf_ref_fbank.restype = ctypes.c_int
-    lib.knf_ref_fbank.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-    rng = np.random.default_rng(7)
+    lib = None
+    if os.path.exists(so):
+        lib = ctypes.CDLL(so)
+        lib.knf_ref_fbank.restype = ctypes.c_int
+        lib.knf_ref_fbank.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     for n in (400, 1234, 16000):
-        w = (rng.standard_normal(n) * 0.2).clip(-1, 1).astype(np.float32)
-        nf = lib.knf_ref_fbank(w.ctypes.data, n, 80, None, 0)
-        ref = np.empty((nf, 80), np.float32)
-        lib.knf_ref_fbank(w.ctypes.data, n, 80, ref.ctypes.data, nf)
+        w, ref = g[f"w_{n}"], g[f"fbank_{n}"]
+        assert len(w) == n
+        if lib is not None:
+            nf = lib.knf_ref_fbank(w.ctypes.data, n, 80, None, 0)
+            live = np.empty((nf, 80), np.float32)
+            lib.knf_ref_fbank(w.ctypes.data, n, 80, live.ctypes.data, nf)
+            assert np.array_equal(live, ref)
         got = fe.fbank(w)
         assert got.shape == ref.shape and np.abs(got - ref).max() <= FBANK_TOL
 

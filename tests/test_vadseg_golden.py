@@ -3,8 +3,8 @@
 tests/golden/vadseg_*.npz were produced by `funasr::E2EVadModel` itself (onnxruntime/src/e2e-vad.h, compiled in place into
 oracle/_ref/libe2evad_ref.so; generator tests/golden/make_vadseg_golden.py).  Both the oracle restatement
 (oracle/e2e_vad.py) and the product's C++ detector (csrc/host/vad_segmenter.cpp through pfhip_vadseg_feed) must reproduce
-every call's segments bit-exactly (integers).  Where the compiled reference is present it is also driven directly on
-random plans (it travels to the GPU box with the snapshot but these are CPU tests)."""
+every call's segments bit-exactly (integers).  The reference's segments for 60 seeded random plans are stored as well
+(tests/golden/e2evad_random_plans.npz); where the compiled reference is present it is also driven directly on those plans."""
 import glob
 import importlib.util
 import os
@@ -60,34 +60,18 @@ def test_known_consequences_of_the_goldens():
     assert c["segs"].tolist() == [[1, 280, -1]]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libe2evad_ref.so not built (make -C oracle)")
 def test_random_plans_against_the_compiled_reference(pkg):
-    lib = G.load_ref()
-    rng = np.random.default_rng(77)
-    pattern = (0.5 * rng.standard_normal(160)).astype(np.float32)
-    for trial in range(60):
-        runs = [(int(rng.integers(5, 400)), bool(k % 2 == int(trial % 2))) for k in range(int(rng.integers(1, 9)))]
-        sil = G.scores(rng, runs, noise=float(rng.uniform(0.01, 0.2)), flip=float(rng.uniform(0, 0.1)))
-        T = len(sil)
-        amp = (10.0 ** rng.uniform(-5, 0, T + 2)).astype(np.float32)
-        amp[rng.random(T + 2) < 0.05] = 0.0
-        online = bool(trial % 3 != 0)
-        sizes = [int(v) for v in rng.integers(1, 200, 4)] if trial % 4 else [T]
-        calls = G.chunks(T, sizes, online, final_empty=bool(trial % 5 == 0 and online))
-        params = (int(rng.choice([200, 500, 800, 1500])), int(rng.choice([1000, 6000, 15000, 60000])), float(rng.choice([0.5, 0.8, 0.9])))
-        w = G.waveform(amp, pattern)
-        h = lib.e2evad_ref_create()
-
-        def ref_feed(s, wv, fin, on, tail, mx, thr):
-            s = np.ascontiguousarray(s, np.float32)
-            wv = np.ascontiguousarray(wv, np.float32)
-            pairs = np.zeros((len(s) + 8, 2), np.int32)
-            n = lib.e2evad_ref_feed(h, s.ctypes.data, len(s), wv.ctypes.data, len(wv), int(fin), int(on), tail, mx, thr, 16000,
-                                    pairs.ctypes.data, len(s) + 8)
-            return [list(map(int, p)) for p in pairs[:n]]
-
-        want = G.run_plan(ref_feed, sil, w, calls, params).tolist()
-        lib.e2evad_ref_destroy(h)
+    """60 seeded random plans (G.random_plans) against the segments the compiled reference returned for them
+    (tests/golden/e2evad_random_plans.npz); where the compiled reference is present it must still return exactly those."""
+    c = np.load(os.path.join(HERE, "golden", "e2evad_random_plans.npz"))
+    ends = np.cumsum(c["counts"])
+    plans = list(G.random_plans())
+    assert len(plans) == len(ends) and ends[-1] == len(c["segs"])
+    lib = G.load_ref() if os.path.exists(REF_SO) else None
+    for trial, (sil, w, calls, params) in enumerate(plans):
+        want = c["segs"][ends[trial] - c["counts"][trial]:ends[trial]].tolist()
+        if lib is not None:
+            assert G.ref_plan(lib, sil, w, calls, params).tolist() == want, ("reference", trial)
         mo, mp = E.E2EVadModel(), pkg.E2EVadModelHost()
         assert G.run_plan(lambda *a: mo(*a), sil, w, calls, params).tolist() == want, ("oracle", trial)
         assert G.run_plan(lambda *a: mp(*a), sil, w, calls, params).tolist() == want, ("product", trial)
