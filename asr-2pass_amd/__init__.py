@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "pfhip_container_manifest", "pfhip_container_from_cache", "pfhip_container_free", "pfhip_onnx_summary", "pfhip_vad_create_from_files", "pfhip_punc_create_from_files", "pfhip_create_group", "pfhip_group_size", "pfhip_group_stats", "pfhip_destroy",
     "pfhip_sample_rate", "pfhip_vocab_size", "pfhip_feat_dim", "pfhip_d_model",
     "pfhip_offline_forward", "pfhip_offline_enqueue", "pfhip_offline_fetch", "pfhip_offline_forward_resident",
+    "pfhip_resample_len", "pfhip_resample", "pfhip_offline_forward_rate",
     "pfhip_set_batching", "pfhip_set_inflight", "pfhip_warm_up", "pfhip_get_inflight", "pfhip_inflight_stats", "pfhip_is_contextual", "pfhip_has_timestamp_head", "pfhip_hotword_embed", "pfhip_set_hotwords",
     "pfhip_extract_feats", "pfhip_get_tensor", "pfhip_debug_poke", "pfhip_profile_enable", "pfhip_profile_read",
     "pfhip_stream_create", "pfhip_stream_destroy", "pfhip_stream_reset", "pfhip_stream_forward", "pfhip_stream_last_path", "pfhip_stream_forward_batch", "pfhip_set_stream_batching",
@@ -113,6 +114,13 @@ def load_lib() -> ctypes.CDLL:
     lib.pfhip_offline_enqueue.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci), ci, vp]
     lib.pfhip_offline_fetch.argtypes = [vp, ctypes.POINTER(_Out)]
     lib.pfhip_offline_forward_resident.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci), ci, ctypes.POINTER(_Out)]
+    lib.pfhip_resample_len.restype = ctypes.c_int64
+    lib.pfhip_resample_len.argtypes = [ci, ci, ctypes.c_int64]
+    lib.pfhip_resample.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci),
+                                   ctypes.POINTER(ci)]
+    lib.pfhip_offline_forward_rate.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, vp, ci, ctypes.POINTER(_Out)]
+    lib.pfhip_op_resample_table.argtypes = [ci, ci, vp, vp, vp, ctypes.c_size_t, ctypes.POINTER(ci), ctypes.POINTER(ci),
+                                            ctypes.POINTER(ci)]
     lib.pfhip_extract_feats.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, vp, ctypes.c_size_t, vp]
     lib.pfhip_get_tensor.argtypes = [vp, ctypes.c_char_p, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     lib.pfhip_set_batching.argtypes = [vp, ci, ci]
@@ -189,6 +197,27 @@ def read_model_files(kind, model, second=None, hotword=None, cmvn=None, config=N
         return man, blob, bool(lib.pfhip_container_from_cache(h))
     finally:
         lib.pfhip_container_free(h)
+
+
+def resample_len(fs_in, n, fs_out=16000):
+    """pfhip_resample_len: samples that n samples at fs_in become at fs_out (Audio::WavResample, flush); -1 if unsupported."""
+    return int(load_lib().pfhip_resample_len(int(fs_in), int(fs_out), int(n)))
+
+
+def resample_table(fs_in, fs_out=16000):
+    """pfhip_op_resample_table (host only): (P, first_index int32 [Q], ntaps int32 [Q], weights float32 [Q, K])."""
+    lib = load_lib()
+    q, k, p = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if lib.pfhip_op_resample_table(int(fs_in), int(fs_out), None, None, None, 0, ctypes.byref(q), ctypes.byref(k), ctypes.byref(p)):
+        raise PfhipError(f"unsupported rate pair {fs_in} -> {fs_out}")
+    first = np.zeros(q.value, np.int32)
+    nt = np.zeros(q.value, np.int32)
+    w = np.zeros((q.value, k.value), np.float32)
+    rc = lib.pfhip_op_resample_table(int(fs_in), int(fs_out), first.ctypes.data, nt.ctypes.data, w.ctypes.data, w.size,
+                                     ctypes.byref(q), ctypes.byref(k), ctypes.byref(p))
+    if rc:
+        raise PfhipError(f"pfhip_op_resample_table: {rc}")
+    return p.value, first, nt, w
 
 
 def onnx_summary(path):
@@ -345,17 +374,43 @@ class ParaformerHip:
         _check(self._lib, self._lib.pfhip_hotword_embed(self._h, mat.ctypes.data, ln.ctypes.data, len(rows), out.ctypes.data))
         return out
 
-    def forward_ids(self, din: Sequence[np.ndarray], want_logp=False, max_tokens=None, hw_emb=None, want_timestamps=False):
+    def resample(self, din: Sequence[np.ndarray], sample_rate: int):
+        """pfhip_resample: Audio::WavResample of each utterance from sample_rate to the model's rate, on the GPU."""
+        B = len(din)
+        if B == 0:
+            raise PfhipError("empty batch")
+        fs_out = self.GetAsrSampleRate()
+        bufs = [np.ascontiguousarray(x, dtype=np.float32) for x in din]
+        n_out = [resample_len(sample_rate, b.shape[0], fs_out) for b in bufs]
+        if min(n_out) < 0:
+            raise PfhipError(f"unsupported sample rate {sample_rate}")
+        outs = [np.zeros(max(n, 1), np.float32) for n in n_out]
+        lens = (ctypes.c_int * B)(*[int(b.shape[0]) for b in bufs])
+        ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
+        optrs = (ctypes.c_void_p * B)(*[o.ctypes.data for o in outs])
+        caps = (ctypes.c_int * B)(*[o.shape[0] for o in outs])
+        got = (ctypes.c_int * B)()
+        _check(self._lib, self._lib.pfhip_resample(self._h, ptrs, lens, B, int(sample_rate), optrs, caps, got))
+        return [o[:got[b]] for b, o in enumerate(outs)]
+
+    def forward_ids(self, din: Sequence[np.ndarray], want_logp=False, max_tokens=None, hw_emb=None, want_timestamps=False,
+                    sample_rate=None):
         """Batched forward.  Returns dict(token_num, n_fires, n_frames, ids=list of int arrays,
-        logp=list of [n_fires, V] arrays or None[, us_alphas, us_peaks = lists of [3*T_b] arrays])."""
+        logp=list of [n_fires, V] arrays or None[, us_alphas, us_peaks = lists of [3*T_b] arrays]).
+        sample_rate: the rate of din when it is not the model's (pfhip_offline_forward_rate resamples on the GPU first)."""
         B = len(din)
         if B == 0:
             raise PfhipError("empty batch")
         bufs = [np.ascontiguousarray(x, dtype=np.float32) for x in din]
         lens = (ctypes.c_int * B)(*[int(b.shape[0]) for b in bufs])
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
+        n_model = [int(b.shape[0]) for b in bufs]
+        if sample_rate is not None:
+            n_model = [resample_len(sample_rate, n, self.GetAsrSampleRate()) for n in n_model]
+            if min(n_model) < 0:
+                raise PfhipError(f"unsupported sample rate {sample_rate}")
         if max_tokens is None:
-            max_tokens = max(1, max(int(b.shape[0]) for b in bufs) // 960 + 2)   # <= T+1 fires per utterance
+            max_tokens = max(1, max(n_model) // 960 + 2)   # <= T+1 fires per utterance
         V = self.vocab_size
         ids = np.zeros((B, max_tokens), np.int32)
         tn = np.zeros(B, np.int32)
@@ -370,7 +425,7 @@ class ParaformerHip:
         out.logp = logp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if want_logp else None
         out.max_tokens = max_tokens
         if want_timestamps:
-            max_us = 3 * max(1, max(int(b.shape[0]) for b in bufs) // 960 + 2)
+            max_us = 3 * max(1, max(n_model) // 960 + 2)
             usa = np.zeros((B, max_us), np.float32)
             usp = np.zeros((B, max_us), np.float32)
             usl = np.zeros(B, np.int32)
@@ -379,8 +434,12 @@ class ParaformerHip:
             out.us_len = usl.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
             out.max_us = max_us
         hw = np.ascontiguousarray(hw_emb, dtype=np.float32) if hw_emb is not None else None
-        _check(self._lib, self._lib.pfhip_offline_forward(self._h, ptrs, lens, B, hw.ctypes.data if hw is not None else None,
-                                                          int(hw.shape[0]) if hw is not None else 0, ctypes.byref(out)))
+        hw_ptr, n_hw = (hw.ctypes.data, int(hw.shape[0])) if hw is not None else (None, 0)
+        if sample_rate is None:
+            _check(self._lib, self._lib.pfhip_offline_forward(self._h, ptrs, lens, B, hw_ptr, n_hw, ctypes.byref(out)))
+        else:
+            _check(self._lib, self._lib.pfhip_offline_forward_rate(self._h, ptrs, lens, B, int(sample_rate), hw_ptr, n_hw,
+                                                                   ctypes.byref(out)))
         res = dict(token_num=tn, n_fires=nf, n_frames=fr,
                    ids=[ids[b, :min(tn[b], nf[b])].copy() for b in range(B)],
                    logp=[logp[b, :nf[b]].copy() for b in range(B)] if want_logp else None)

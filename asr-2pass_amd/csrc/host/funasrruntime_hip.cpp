@@ -1,6 +1,7 @@
 #include "funasrruntime_hip.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -144,6 +145,28 @@ FUNASR_HANDLE FunOfflineInit(std::map<std::string, std::string>& model_path, int
   return os.release();
 }
 
+// Audio::LoadPcmwav / LoadPcmwavOnline (audio.cpp:787-857): s16 LE -> f32 / 32768, then Audio::WavResample (:259-284) when the
+// caller's rate is not the model's — on the GPU (pfhip_resample), a fresh resampler with flush per buffer as the reference builds
+// one per call.  False for a rate the resampler refuses.
+static bool LoadPcm(pfhip_model* m, const char* buf, int n_len, int sampling_rate, std::vector<float>& out) {
+  const int n = n_len / 2;
+  std::vector<float> pcm((size_t)n);
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(buf);
+  for (int i = 0; i < n; ++i) pcm[i] = (float)(int16_t)((b[2 * i + 1] << 8) | b[2 * i]) / 32768.f;
+  const int fs_out = pfhip_sample_rate(m);
+  if (sampling_rate == fs_out) { out.swap(pcm); return true; }
+  const int64_t n_out = pfhip_resample_len(sampling_rate, fs_out, n);
+  if (n_out < 0 || n_out > INT32_MAX) return false;
+  out.assign((size_t)std::max<int64_t>(n_out, 1), 0.f);
+  const float* in[1] = {pcm.data()};
+  float* dst[1] = {out.data()};
+  const int cap = (int)out.size();
+  int got = 0;
+  if (pfhip_resample(m, in, &n, 1, sampling_rate, dst, &cap, &got) != PFHIP_OK) return false;
+  out.resize((size_t)got);
+  return true;
+}
+
 FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, int n_len, FUNASR_MODE mode, QM_CALLBACK fn_callback,
                                     const std::vector<std::vector<float>>& hw_emb, int sampling_rate, std::string wav_format,
                                     bool itn, int vad_tail_sil, int vad_max_len, FUNASR_DEC_HANDLE dec_handle) {
@@ -151,14 +174,17 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   OfflineStreamHip* os = static_cast<OfflineStreamHip*>(handle);
   if (!os || !sz_buf) return nullptr;
   if (wav_format != "pcm" && wav_format != "PCM") return nullptr;      // the reference decodes other containers with ffmpeg
-  if (sampling_rate != os->asr.GetAsrSampleRate()) return nullptr;     // resampling (audio.cpp:230-260) is caller-side here
-  // Audio::LoadPcmwav (audio.cpp:787-819): s16 LE -> f32 / 32768
-  const int n = n_len / 2;
-  std::vector<float> pcm((size_t)n);
-  const int16_t* s16 = reinterpret_cast<const int16_t*>(sz_buf);
-  for (int i = 0; i < n; ++i) pcm[i] = (float)s16[i] / 32768.f;
+  // Audio::LoadPcmwav (audio.cpp:787-819); from here on samples, segments and stamps are at the model's rate (GetTimeLen
+  // divides by dest_sample_rate, audio.cpp:254-257)
+  std::vector<float> pcm;
+  if (!LoadPcm(os->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
+    std::fprintf(stderr, "FunOfflineInferBuffer: %s\n", pfhip_last_error());
+    return nullptr;
+  }
+  const int n = (int)pcm.size();
+  const int model_rate = os->asr.GetAsrSampleRate();
   auto res = std::make_unique<RecogResult>();
-  res->snippet_time = (float)n / (float)sampling_rate;
+  res->snippet_time = (float)n / (float)model_rate;
   if (n == 0) return res.release();
   std::vector<int> index_vector = {0};
   res->segs.assign(1, {0, n});
@@ -194,7 +220,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   std::string cur_stamp = "[";
   for (size_t idx = 0; idx < msgs.size(); ++idx) {                                     // funasrruntime.cpp:291-312
     if (msgs[idx].empty()) continue;
-    const float t0 = (float)res->segs[idx].first / (float)sampling_rate;               // msg_stimes
+    const float t0 = (float)res->segs[idx].first / (float)model_rate;                  // msg_stimes
     const size_t bar = msgs[idx].find(" | ");
     res->msg += msgs[idx].substr(0, bar);
     if (bar != std::string::npos) {                 // "<text> | b0, e0,b1, e1": seconds relative to the segment
@@ -320,9 +346,17 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
   TpassOnlineStreamHip* os = static_cast<TpassOnlineStreamHip*>(online_handle);
   if (!ts || !os || !sz_buf) return nullptr;
   if (wav_format != "pcm" && wav_format != "PCM") return nullptr;                  // funasrruntime.cpp:523-531
-  if (sampling_rate != 16000) return nullptr;
   if (ts->punc_online && punc_cache.size() < 2) return nullptr;                    // [0]: online text, [1]: 2nd-pass text
-  if (!os->audio.LoadPcmwavOnline(sz_buf, n_len)) return nullptr;
+  if (sampling_rate == 16000) {
+    if (!os->audio.LoadPcmwavOnline(sz_buf, n_len)) return nullptr;
+  } else {                  // LoadPcmwavOnline with WavResample of THIS buffer alone (audio.cpp:821-857): no state across calls
+    std::vector<float> pcm;
+    if (!LoadPcm(ts->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
+      std::fprintf(stderr, "FunTpassInferBuffer: %s\n", pfhip_last_error());
+      return nullptr;
+    }
+    os->audio.LoadSamplesOnline(pcm.data(), (int)pcm.size());
+  }
   auto res = std::make_unique<RecogResult>();
   res->snippet_time = os->audio.GetTimeLen();
   // FsmnVadOnline::Infer (fsmn-vad-online.cpp:135-151) as the VAD of Audio::Split

@@ -15,20 +15,21 @@
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s model_dir vad_dir|- pcm_s16_file [batch] [threads] [repeat] [punc_dir]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s model_dir vad_dir|- pcm_s16_file [batch] [threads] [repeat] [punc_dir|-] [audio_fs]\n", argv[0]);
     return 2;
   }
   std::map<std::string, std::string> paths;
   paths[MODEL_DIR] = argv[1];
   if (std::string(argv[2]) != "-") paths[VAD_DIR] = argv[2];
-  if (argc > 7) paths[PUNC_DIR] = argv[7];
+  if (argc > 7 && std::string(argv[7]) != "-") paths[PUNC_DIR] = argv[7];
+  const int audio_fs = argc > 8 ? std::atoi(argv[8]) : 16000;      // the client's --audio-fs (funasr-wss-client.cpp:194,240,366)
   const int batch = argc > 4 ? std::atoi(argv[4]) : 32, threads = argc > 5 ? std::atoi(argv[5]) : 1, repeat = argc > 6 ? std::atoi(argv[6]) : 1;
   std::ifstream f(argv[3], std::ios::binary);
   std::vector<char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
   FUNASR_HANDLE h = FunOfflineInit(paths, threads, true, batch);
   const std::vector<std::vector<float>> no_hw;
   {
-    FUNASR_RESULT r = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, 16000, "pcm");
+    FUNASR_RESULT r = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, audio_fs, "pcm");
     if (!r) { std::fprintf(stderr, "inference failed\n"); return 1; }
     const auto& segs = FunASRGetSegments(r);
     const auto& ids = FunASRGetSegmentIds(r);
@@ -47,7 +48,7 @@ int main(int argc, char** argv) {
     for (int t = 0; t < threads; ++t)
       pool.emplace_back([&] {
         for (int k = 0; k < repeat; ++k) {
-          FUNASR_RESULT q = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, 16000, "pcm");
+          FUNASR_RESULT q = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, audio_fs, "pcm");
           if (!q || want_text != FunASRGetResult(q, 0) || want_stamp != FunASRGetStamp(q)) ++mismatches;      // re-entrancy check
           FunASRFreeResult(q);
         }

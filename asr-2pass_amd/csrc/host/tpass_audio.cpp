@@ -24,6 +24,12 @@ bool TpassAudio::LoadPcmwavOnline(const char* buf, int n_buf_len) {
   return true;
 }
 
+void TpassAudio::LoadSamplesOnline(const float* x, int n) {
+  speech_data_.assign(x, x + n);
+  all_samples_.insert(all_samples_.end(), speech_data_.begin(), speech_data_.end());
+  frame_queue_.push_back(n);
+}
+
 TpassFrame TpassAudio::MakeFrame(int start, int n, bool is_final, int gs, int ge) const {
   TpassFrame f;
   f.is_final = is_final; f.global_start = gs; f.global_end = ge;

@@ -26,6 +26,8 @@ class TpassAudio {
   using VadInfer = std::function<std::vector<std::vector<int>>(std::vector<float>& waves, bool input_finished)>;
   explicit TpassAudio(int sample_rate = 16000) : dest_sample_rate_(sample_rate) { ResetIndex(); }
   bool LoadPcmwavOnline(const char* buf, int n_buf_len);
+  // the same for samples already converted (and resampled to dest_sample_rate by the caller)
+  void LoadSamplesOnline(const float* x, int n);
   void Split(const VadInfer& vad, int chunk_len, bool input_finished, AsrType asr_mode);
   bool FetchChunck(TpassFrame& out);
   bool FetchTpass(TpassFrame& out);

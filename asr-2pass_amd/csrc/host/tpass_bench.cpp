@@ -19,7 +19,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s offline_dir online_dir vad_dir punc_dir|- pcm_s16_file [connections] [mode]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s offline_dir online_dir vad_dir punc_dir|- pcm_s16_file [connections] [mode] [audio_fs]\n", argv[0]);
     return 2;
   }
   std::map<std::string, std::string> paths;
@@ -27,16 +27,18 @@ int main(int argc, char** argv) {
   if (std::string(argv[4]) != "-") paths[PUNC_DIR] = argv[4];
   const int n_conn = argc > 6 ? std::atoi(argv[6]) : 64;
   const ASR_TYPE mode = argc > 7 ? (ASR_TYPE)std::atoi(argv[7]) : ASR_TWO_PASS;
+  const int audio_fs = argc > 8 ? std::atoi(argv[8]) : 16000;     // rate of the file; each message is 600 ms of it
+  const int msg = audio_fs * 6 / 10 * 2;                           // bytes per message (19200 at 16 kHz)
   std::ifstream f(argv[5], std::ios::binary);
   std::vector<char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-  if (buf.size() < 19200) { std::fprintf(stderr, "pcm file too short\n"); return 2; }
+  if ((int)buf.size() < msg) { std::fprintf(stderr, "pcm file too short\n"); return 2; }
   FUNASR_HANDLE h = FunTpassInit(paths, n_conn);
   if (!h) return 1;
   {  // warm-up: one connection over the first 3 s
     FUNASR_HANDLE oh = FunTpassOnlineInit(h, {5, 10, 5});
     std::vector<std::vector<std::string>> pc(2);
-    for (int off = 0; off < 5 * 19200 && off + 19200 <= (int)buf.size(); off += 19200) {
-      FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, 19200, pc, off + 19200 >= 5 * 19200, 16000, "pcm", mode);
+    for (int off = 0; off < 5 * msg && off + msg <= (int)buf.size(); off += msg) {
+      FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, msg, pc, off + msg >= 5 * msg, audio_fs, "pcm", mode);
       if (r) FunASRFreeResult(r);
     }
     FunTpassOnlineUninit(oh);
@@ -60,10 +62,10 @@ int main(int argc, char** argv) {
         cv.notify_all();
         cv.wait(lk, [&] { return go; });
       }
-      for (int off = 0; off < n_bytes; off += 19200) {
-        const int nb = std::min(19200, n_bytes - off);
+      for (int off = 0; off < n_bytes; off += msg) {
+        const int nb = std::min(msg, n_bytes - off);
         const auto t0 = std::chrono::steady_clock::now();
-        FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, nb, punc_cache, off + 19200 >= n_bytes, 16000, "pcm", mode);
+        FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, nb, punc_cache, off + msg >= n_bytes, audio_fs, "pcm", mode);
         const double call_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         worst[c] = std::max(worst[c], call_s);
         lat[c].push_back((float)(call_s * 1e3));
@@ -85,7 +87,7 @@ int main(int argc, char** argv) {
   cv.notify_all();
   for (auto& th : pool) th.join();
   const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  const double audio = (double)n_conn * (double)(n_bytes / 2) / 16000.0;
+  const double audio = (double)n_conn * (double)(n_bytes / 2) / (double)audio_fs;
   double mx = 0;
   for (double w : worst) mx = std::max(mx, w);
   std::vector<float> all;
@@ -95,7 +97,7 @@ int main(int argc, char** argv) {
   std::printf("{\"connections\": %d, \"audio_s\": %.1f, \"wall_s\": %.3f, \"xrt\": %.1f, \"calls\": %ld, \"failures\": %ld, "
               "\"ms_per_round\": %.2f, \"p50_call_ms\": %.2f, \"p99_call_ms\": %.2f, \"worst_call_ms\": %.1f, \"tpass_results\": %ld, "
               "\"online_bytes\": %ld, \"tpass_bytes\": %ld}\n",
-              n_conn, audio, dt, audio / dt, calls.load(), failures.load(), dt / ((n_bytes + 19199) / 19200) * 1e3, pct(0.5), pct(0.99), mx * 1e3,
+              n_conn, audio, dt, audio / dt, calls.load(), failures.load(), dt / ((n_bytes + msg - 1) / msg) * 1e3, pct(0.5), pct(0.99), mx * 1e3,
               tpass_results.load(), online_chars.load(), tpass_chars.load());
   FunTpassUninit(h);
   return failures.load() ? 1 : 0;

@@ -9,8 +9,10 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -102,6 +104,28 @@ inline void free_lin(Lin& l) { if (l.w) (void)hipFree(l.w); if (l.b) (void)hipFr
 
 struct ProfRec { int cls; hipEvent_t e0, e1; };
 
+// ---- resampling ahead of the front end (resample.cpp / resample.hip) -------------------------------------------------
+// The polyphase plan of one rate pair on the host: Q output phases per unit of P input samples, per phase its first input
+// index, tap count and weight row ([Q][K], rows zero-padded past ntap).
+struct ResamplePlan {
+  int P = 0, Q = 0, K = 0;
+  std::vector<int32_t> first, ntap;
+  std::vector<float> w;
+};
+// both rates in [1000, 192000] Hz and lcm(fs_in, fs_out) within int32; otherwise false and a message in *why
+bool resample_supported(int fs_in, int fs_out, std::string* why);
+int64_t resample_out_len(int fs_in, int fs_out, int64_t n_in);     // flush-mode output count, -1 for an unsupported pair
+void build_resample_plan(int fs_in, int fs_out, ResamplePlan* p);
+// Device images of the plans, uploaded once per (device, rate pair) and kept until the cache dies; safe for concurrent callers.
+class ResampleCache {
+ public:
+  ~ResampleCache();
+  pfhip_status get(int device, int fs_in, int fs_out, pfhip::ResampleTable* out);
+ private:
+  std::mutex mu;
+  std::map<std::tuple<int, int, int>, pfhip::ResampleTable> plans;
+};
+
 }  // namespace pfhip_detail
 
 using pfhip_detail::Buf;
@@ -174,6 +198,9 @@ struct pfhip_model {
   Buf pcm, meta, feats, x0, x, y, qkv, mem, ctx, hbuf, enc, alphas, counts;
   Buf emb, xd, yd, hd, hd2, td, t2, qd, ctxd, logits, logp, ids, dmeta, cat, hw, hwkv;
   Buf sseg;                     // StreamSeg descriptors of a streaming batch
+  Buf rs_in;                    // audio at the caller's rate, resampled into `pcm` (pfhip_offline_forward_rate, pfhip_resample)
+  // resampling plans of this device (on the weight owner; contexts use their owner's)
+  std::unique_ptr<pfhip_detail::ResampleCache> rs_cache{new pfhip_detail::ResampleCache};
   Buf kvside;                   // [dec_layers][Mp][2d]: every decoder layer's K/V projection of the encoder output (side stream)
   Buf lnstats2;                 // the decoder's second hand-off (FFN1 -> ffn_norm -> FFN2): [ML][dec_ffn / 128][2]
   Buf lnstats;                  // per-row LayerNorm statistics handed from a producing GEMM's epilogue to the consumer [M][4][2]

@@ -299,4 +299,14 @@ void launch_lfr_cmvn_online_batch(const VadLfrOp* ops, int n_ops, int max_rows, 
                                   const float* istd, float* out, int ldo, hipStream_t s);
 void launch_softmax_rows(const float* x, int ldx, int M, int N, float* y, float* col0, hipStream_t s);
 
+// ---- resampling ahead of the front end (resample.hip; plan: resample.cpp) ----------------------
+// The device image of one rate pair's polyphase plan (Kaldi LinearResample, onnxruntime/src/resample.cpp:104-153):
+// per output phase ph < Q its first input index first[ph], its tap count ntap[ph] <= K and its weight row w[ph * K ..].
+// Output sample s of an utterance reads inputs first[s % Q] + (s / Q) * P + j, j < ntap[s % Q].
+struct ResampleTable { const int* first; const int* ntap; const float* w; int P, Q, K; };
+// Packed batch: utterance b reads n_in[b] samples at in + in_off[b] and writes n_out[b] samples at out + out_off[b]
+// (host arrays; n_out from the flush-mode count).  Bitwise the reference's serial fp32 dot product per output.
+void launch_resample(const float* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
+                     int B, const ResampleTable& t, hipStream_t s);
+
 }  // namespace pfhip

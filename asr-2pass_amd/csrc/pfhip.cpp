@@ -1335,6 +1335,40 @@ pfhip_status stage_pcm(pfhip_model* m, const float* const* pcm, const int* n_sam
   return PFHIP_OK;
 }
 
+// The batch at the caller's rate fs_in: staged into rs_in, resampled on `s` into `pcm` at the model's rate, packed as stage_pcm
+// packs it.  off / n_out receive the model-rate layout.
+pfhip_status stage_resampled(pfhip_model* m, const float* const* pcm, const int* n_samples, int B, int fs_in, hipStream_t s,
+                             std::vector<int64_t>& off, std::vector<int>& n_out) {
+  pfhip::ResampleTable t;
+  pfhip_status st = (m->weights_of ? m->weights_of : m)->rs_cache->get(m->device, fs_in, m->cfg.sample_rate, &t);
+  if (st) return st;
+  std::vector<int64_t> in_off(B);
+  off.assign(B, 0);
+  n_out.assign(B, 0);
+  int64_t tin = 0, tout = 0;
+  for (int b = 0; b < B; ++b) {
+    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    const int64_t no = pfhip_detail::resample_out_len(fs_in, m->cfg.sample_rate, n_samples[b]);
+    if (no < 0 || no > INT32_MAX) return fail(PFHIP_ERR_ARG, "resampled utterance too long");
+    in_off[b] = tin;
+    tin += (n_samples[b] + 3) & ~3;
+    n_out[b] = (int)no;
+    off[b] = tout;
+    tout += (no + 3) & ~3;
+  }
+  HIP_TRY(m->rs_in.ensure((size_t)std::max<int64_t>(tin, 4) * 4));
+  HIP_TRY(m->pcm.ensure((size_t)std::max<int64_t>(tout, 4) * 4));
+  for (int b = 0; b < B; ++b)
+    if (n_samples[b])
+      HIP_TRY(hipMemcpyAsync(m->rs_in.f() + in_off[b], pcm[b], (size_t)n_samples[b] * 4, hipMemcpyHostToDevice, s));
+  {
+    Scope sc(m, s, K_FBANK, 0.0, 4.0 * (double)(tin + tout));
+    pfhip::launch_resample(m->rs_in.f(), in_off.data(), n_samples, m->pcm.f(), off.data(), n_out.data(), B, t, s);
+  }
+  HIP_TRY(hipGetLastError());
+  return PFHIP_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1449,7 +1483,7 @@ void pfhip_destroy(pfhip_model* m) {
   for (Buf* b : {&m->pcm, &m->meta, &m->feats, &m->x0, &m->x, &m->y, &m->qkv, &m->mem, &m->ctx, &m->hbuf, &m->enc,
                  &m->alphas, &m->counts, &m->emb, &m->xd, &m->yd, &m->hd, &m->hd2, &m->td, &m->t2, &m->qd, &m->ctxd,
                  &m->logits, &m->logp, &m->ids, &m->dmeta, &m->cat, &m->hw, &m->hwkv, &m->ts_up, &m->ts_gx, &m->ts_y, &m->ts_hx, &m->ts_a2,
-                 &m->ts_alphas, &m->ts_peaks, &m->ts_meta, &m->sseg, &m->fbk, &m->d_ops, &m->kvall, &m->lnstats, &m->lnstats2, &m->kvside, &m->ts_cst, &m->ctxP, &m->xP, &m->hP, &m->encP, &m->xdP, &m->kvP})
+                 &m->ts_alphas, &m->ts_peaks, &m->ts_meta, &m->sseg, &m->rs_in, &m->fbk, &m->d_ops, &m->kvall, &m->lnstats, &m->lnstats2, &m->kvside, &m->ts_cst, &m->ctxP, &m->xP, &m->hP, &m->encP, &m->xdP, &m->kvP})
     b->release();
   if (!m->weights_of) {          // a context borrows these
 #define X(f) if (m->f) (void)hipFree((void*)m->f);
@@ -1497,8 +1531,9 @@ pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out) {
   return fetch_locked(m, out, m->prof_stream ? m->prof_stream : m->own_stream);
 }
 
+// fs_in: the rate of `pcm` when it is not the model's (resampled into the slot's PCM workspace first), else 0
 static pfhip_status forward_direct(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch,
-                                   const float* hw_emb, int n_hotwords, pfhip_out* out) {
+                                   const float* hw_emb, int n_hotwords, pfhip_out* out, int fs_in = 0) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
@@ -1509,9 +1544,10 @@ static pfhip_status forward_direct(pfhip_model* m, const float* const* pcm, cons
     if (hs) return hs;
   }
   std::vector<int64_t> off;
-  pfhip_status st = stage_pcm(m, pcm, n_samples, batch, s, off);
+  std::vector<int> n_rs;
+  pfhip_status st = fs_in ? stage_resampled(m, pcm, n_samples, batch, fs_in, s, off, n_rs) : stage_pcm(m, pcm, n_samples, batch, s, off);
   if (st) return st;
-  st = enqueue_locked(m, m->pcm.f(), off.data(), n_samples, batch, s, false);
+  st = enqueue_locked(m, m->pcm.f(), off.data(), fs_in ? n_rs.data() : n_samples, batch, s, false);
   if (st) return st;
   st = head_locked(m, s, out->logp != nullptr);
   if (st) return st;
@@ -1697,6 +1733,66 @@ pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pc
     if (!st) st = fetch_locked(m, out, s);
   }
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
+  release_slot(head, m);
+  return st;
+}
+
+// pfhip_offline_forward at the caller's rate: resampled on the device into the slot's PCM workspace, then the same forward
+pfhip_status pfhip_offline_forward_rate(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                        const float* hw_emb, int n_hotwords, pfhip_out* out) {
+  if (head && sample_rate == head->cfg.sample_rate) return pfhip_offline_forward(head, pcm, n_samples, batch, hw_emb, n_hotwords, out);
+  g_err.clear();
+  if (!head || !pcm || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  for (int i = 0; i < batch; ++i)
+    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+  std::string why;
+  if (!pfhip_detail::resample_supported(sample_rate, head->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
+  pfhip_model* m = acquire_slot(head);                  // not merged with other callers: one rate pair per packed batch
+  tl_last_replica = m;
+  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw_emb, n_hotwords, out, sample_rate);
+  ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
+  release_slot(head, m);
+  return st;
+}
+
+pfhip_status pfhip_resample(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int fs_in, float* const* out,
+                            const int* cap, int* n_out) {
+  g_err.clear();
+  if (!head || !pcm || !n_samples || batch <= 0 || !out || !cap || !n_out) return fail(PFHIP_ERR_ARG, "bad argument");
+  const int fs_out = head->cfg.sample_rate;
+  std::string why;
+  if (!pfhip_detail::resample_supported(fs_in, fs_out, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
+  bool short_cap = false;
+  for (int b = 0; b < batch; ++b) {
+    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    const int64_t no = pfhip_detail::resample_out_len(fs_in, fs_out, n_samples[b]);
+    if (no > INT32_MAX) return fail(PFHIP_ERR_ARG, "resampled utterance too long");
+    n_out[b] = (int)no;
+    if (no > 0 && (cap[b] < no || !out[b])) short_cap = true;
+  }
+  if (short_cap) return fail(PFHIP_ERR_CAPACITY, "output buffer smaller than the resampled length (n_out holds it)");
+  if (fs_in == fs_out) {        // identity: a copy, no kernel (the reference skips WavResample, audio.cpp:808-810)
+    for (int b = 0; b < batch; ++b)
+      if (n_samples[b]) std::memcpy(out[b], pcm[b], (size_t)n_samples[b] * 4);
+    return PFHIP_OK;
+  }
+  pfhip_model* m = acquire_slot(head);
+  pfhip_status st;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    st = [&]() -> pfhip_status {
+      HIP_TRY(hipSetDevice(m->device));
+      hipStream_t s = m->own_stream;
+      std::vector<int64_t> off;
+      std::vector<int> n_rs;
+      const pfhip_status ss = stage_resampled(m, pcm, n_samples, batch, fs_in, s, off, n_rs);
+      if (ss) return ss;
+      for (int b = 0; b < batch; ++b)
+        if (n_rs[b]) HIP_TRY(hipMemcpyAsync(out[b], m->pcm.f() + off[b], (size_t)n_rs[b] * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      return PFHIP_OK;
+    }();
+  }
   release_slot(head, m);
   return st;
 }

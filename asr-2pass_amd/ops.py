@@ -34,6 +34,7 @@ def _lib():
         lib.pfhip_op_attention_hd.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _ci, _vp]
         lib.pfhip_op_cif.argtypes = [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp]
         lib.pfhip_op_logsoftmax_argmax.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
+        lib.pfhip_op_resample.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]
         _bound = True
     return lib
 
@@ -143,6 +144,25 @@ def fsmn(v, w, off, length, res=None):
     _ck(_lib().pfhip_op_fsmn(_p(v), v.stride(0), _p(w), _p(res), res.stride(0) if res is not None else 0, _p(out),
                              out.stride(0), _p(off), _p(length), B, int(length.max().item()), v.shape[1], _stream()), "fsmn")
     return out
+
+
+def resample(x, in_off, n_in, fs_in, fs_out=16000):
+    """Audio::WavResample on a packed batch (resample.hip): utterance b is x[in_off[b] : in_off[b] + n_in[b]] (float32 at fs_in).
+    Returns (y, out_off, n_out): the utterances at fs_out packed back to back; offsets and counts are host int lists."""
+    import numpy as np
+    from . import resample_len
+    n_in = [int(v) for v in n_in]
+    n_out = [resample_len(fs_in, v, fs_out) for v in n_in]
+    if any(v < 0 for v in n_out):
+        raise PfhipError(f"unsupported rate pair {fs_in} -> {fs_out}")
+    out_off = np.zeros(len(n_in), np.int64)
+    out_off[1:] = np.cumsum(n_out[:-1]) if len(n_in) > 1 else out_off[1:]
+    y = torch.empty(max(sum(n_out), 1), dtype=torch.float32, device=x.device)
+    io = np.ascontiguousarray(in_off, np.int64)
+    ni = np.ascontiguousarray(n_in, np.int32)
+    _ck(_lib().pfhip_op_resample(_p(x), ctypes.c_void_p(io.ctypes.data), ctypes.c_void_p(ni.ctypes.data), len(n_in), fs_in, fs_out,
+                                 _p(y), ctypes.c_void_p(out_off.ctypes.data), _stream()), "resample")
+    return y, [int(v) for v in out_off], n_out
 
 
 def attention(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, head_dim=128):

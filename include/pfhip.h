@@ -168,6 +168,29 @@ pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out);
 pfhip_status pfhip_offline_forward_resident(pfhip_model* m, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
                                             int batch, pfhip_out* out);
 
+/* ---- audio at other sample rates --------------------------------------------------------------------
+ * Replaces Audio::WavResample (onnxruntime/src/audio.cpp:259-284), which Audio::LoadPcmwav / LoadPcmwavOnline (:787-857) run
+ * when the caller's rate differs from the model's (dest_sample_rate): Kaldi's LinearResample (onnxruntime/src/resample.cpp) with
+ * cutoff 0.99 * 0.5 * min(fs_in, fs_out), 6 zero crossings, a fresh resampler per call and flush = true.  Outputs are bitwise
+ * the reference's.  Rates: 1000 <= fs <= 192000 Hz with lcm(fs_in, fs_out) <= INT32_MAX (the reference's int32 tick
+ * arithmetic); any other pair is PFHIP_ERR_UNSUPPORTED.  The output rate is always the model's (pfhip_sample_rate).
+ *
+ * Host only (no device): the number of samples n_in samples at fs_in become at fs_out (LinearResample::GetNumOutputSamples with
+ * flush, resample.cpp:220-265), -1 for an unsupported pair.  fs_in == fs_out gives n_in. */
+int64_t pfhip_resample_len(int fs_in, int fs_out, int64_t n_in);
+/* Host buffers in and out: pcm[b] (n_samples[b] floats at fs_in) -> out[b] (room for cap[b] floats; n_out[b] receives the
+ * count, also on PFHIP_ERR_CAPACITY).  H2D, the kernel and D2H on one of the handle's execution slots; re-entrant.
+ * fs_in == the model's rate is a plain copy (no kernel), as the reference skips WavResample. */
+pfhip_status pfhip_resample(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, int fs_in, float* const* out,
+                            const int* cap, int* n_out);
+/* pfhip_offline_forward for audio at sample_rate (the server's `audio_fs`, websocket-server.cpp:361-398): the audio is copied to
+ * the device at its own rate and resampled there into the execution slot's PCM workspace, then the forward runs as
+ * pfhip_offline_forward_resident does, without a host round trip.  Results are those of pfhip_offline_forward on the output of
+ * pfhip_resample.  sample_rate == pfhip_sample_rate(m) is exactly pfhip_offline_forward.  Calls at another rate are not merged
+ * with other callers (pfhip_set_batching; as for contextual models).  Hotwords and the timestamp outputs are as there. */
+pfhip_status pfhip_offline_forward_rate(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                        const float* hw_emb, int n_hotwords, pfhip_out* out);
+
 /* ---- hotwords (contextual model) ---------------------------------------------------------------
  *   pfhip_hotword_embed <-> the `hw_m_session->Run` on model_eb.onnx + the per-hotword row selection inside
  *                           Paraformer::CompileHotwordEmbedding (paraformer.cpp:656-685): ids i32 [H,10] (0-padded, last row

@@ -106,6 +106,18 @@ int pfhip_op_fused_att_out(const float* Q, int ldq, const float* K, int ldk, con
                            const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* fsmn_v,
                            int ldfv, const float* fsmn_w, int N, void* stream);
 
+/* Resampling ahead of the front end (Audio::WavResample, onnxruntime/src/audio.cpp:259-284; plan of resample.cpp:104-153).
+ * Host only: the polyphase plan of a rate pair.  *n_phases = Q output samples per unit, *in_unit = P input samples per unit,
+ * *taps = K, the longest weight row.  With first_index [Q], ntaps [Q] or weights [Q * K] (row ph zero-padded past ntaps[ph])
+ * non-NULL and cap_floats >= Q * K they are filled.  Output sample s reads inputs first_index[s % Q] + (s / Q) * P + j. */
+int pfhip_op_resample_table(int fs_in, int fs_out, int32_t* first_index, int32_t* ntaps, float* weights, size_t cap_floats,
+                            int* n_phases, int* taps, int* in_unit);
+/* The kernel on a packed batch (resample.hip): utterance b reads n_in[b] samples at d_in + in_off[b] and writes
+ * pfhip_resample_len(fs_in, fs_out, n_in[b]) samples at d_out + out_off[b].  in_off / n_in / out_off are HOST arrays.
+ * fs_in == fs_out is a device copy.  Unsupported pairs return hipErrorInvalidValue. */
+int pfhip_op_resample(const float* d_in, const int64_t* in_off, const int* n_in, int batch, int fs_in, int fs_out, float* d_out,
+                      const int64_t* out_off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
