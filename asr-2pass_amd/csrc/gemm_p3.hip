@@ -127,7 +127,8 @@ __device__ __forceinline__ void tile_row_stats(const float4& v, int grow, int M,
   const float q = half_wave_sum((a * a + b * b) + (c * c + d * d));
   if (c4 == 0 && grow < M) *reinterpret_cast<float2*>(stats + ((size_t)grow * tiles_n + tn) * 2) = make_float2(mean, q);
 }
-// (a row whose rms leaves [2^-8, 2^12] raises the forward's range flag: gemm_x3.hip, kernels.h LaunchCtx)
+// (a row whose centred std leaves [2^-8, 2^11] or whose |mean| / std exceeds kLnOffsetMax raises the forward's range flag: gemm_x3.hip,
+// kernels.h LaunchCtx)
 __device__ __forceinline__ float2 ln_row_stats(const float* __restrict__ stats, int tiles, float eps, int row, int* range_flag) {
   const float* sp = stats + (size_t)row * tiles * 2;
   float msum = 0.f, m2 = 0.f;
@@ -135,7 +136,7 @@ __device__ __forceinline__ float2 ln_row_stats(const float* __restrict__ stats, 
   const float mean = msum / (float)tiles;
   for (int t = 0; t < tiles; ++t) { const float dm = sp[2 * t] - mean; m2 += sp[2 * t + 1] + (float)kPN * dm * dm; }
   const float rstd = 1.0f / sqrtf(m2 / (float)(tiles * kPN) + eps);
-  if (range_flag && !(rstd > kLnRstdMin && rstd < kLnRstdMax)) atomicOr(range_flag, 2);
+  if (range_flag && ln_row_out_of_domain(mean, rstd)) atomicOr(range_flag, 2);
   return make_float2(mean, rstd);
 }
 // The same for T tiles (4: d_model = 512; 16: the decoder's LayerNorm over the 2048 hidden channels) from the row's 8 T bytes fetched as
@@ -162,7 +163,7 @@ __device__ __forceinline__ float2 ln_row_stats_raw(const LnRaw<T>& r, float eps,
     { const float dm = r.v[i].z - mean; m2 += r.v[i].w + (float)kPN * dm * dm; }
   }
   const float rstd = 1.0f / sqrtf(m2 / (float)(T * kPN) + eps);
-  if (range_flag && !(rstd > kLnRstdMin && rstd < kLnRstdMax)) atomicOr(range_flag, 2);
+  if (range_flag && ln_row_out_of_domain(mean, rstd)) atomicOr(range_flag, 2);
   return make_float2(mean, rstd);
 }
 

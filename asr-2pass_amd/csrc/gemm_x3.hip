@@ -159,9 +159,10 @@ __device__ __forceinline__ void tile_row_stats(const float4& v, int grow, int M,
 
 // the consumer's half.  Row statistics merged from the producer's per-tile pairs (Chan: n = 128 per tile) — one thread per row,
 // at kernel start, parked in registers under the K-loop and published through LDS for the epilogue passes ...
-// A row whose rms lies outside [2^-8, 2^12] (or is not finite) is outside the domain the two fp16 planes of the raw residual
-// stream cover at fp32 grade: the forward's range flag is raised (kernels.h LaunchCtx) and the host redoes the batch on the
-// bf16 three-plane kernels.
+// A row whose centred standard deviation lies outside [2^-8, 2^11], whose offset |mean| / std exceeds kLnOffsetMax (the fold below
+// cancels: kernels.h) or whose statistics are not finite is outside the domain the fold on two fp16 planes of the raw residual
+// stream covers at fp32 grade: the forward's range flag is raised (kernels.h LaunchCtx) and the host redoes the batch unfolded on
+// the bf16 three-plane kernels.
 __device__ __forceinline__ float2 ln_row_stats(const float* __restrict__ stats, int tiles, float eps, int row, int* range_flag) {
   const float* sp = stats + (size_t)row * tiles * 2;
   float msum = 0.f, m2 = 0.f;
@@ -169,7 +170,7 @@ __device__ __forceinline__ float2 ln_row_stats(const float* __restrict__ stats, 
   const float mean = msum / (float)tiles;
   for (int t = 0; t < tiles; ++t) { const float dm = sp[2 * t] - mean; m2 += sp[2 * t + 1] + (float)kBN * dm * dm; }
   const float rstd = 1.0f / sqrtf(m2 / (float)(tiles * kBN) + eps);
-  if (range_flag && !(rstd > kLnRstdMin && rstd < kLnRstdMax)) atomicOr(range_flag, 2);
+  if (range_flag && ln_row_out_of_domain(mean, rstd)) atomicOr(range_flag, 2);
   return make_float2(mean, rstd);
 }
 // ... where v (four columns of x W'^T) becomes rstd * (v - mean * colsum)
@@ -426,8 +427,8 @@ __global__ __launch_bounds__(512, 4) void gemm_f32_f16x3_128_kernel(
   //     LN(x) W^T = rstd_i * (x W'^T - mean_i * colsum(W')_n) + (bias + W beta)_n,
   // so the K-loop is the plain one and the normalisation is two FMAs per output element in the epilogue (mean_i / rstd_i merged
   // from the per-tile pairs the producing GEMM left, Chan's formula; colsum and the folded bias prepared at load).  The
-  // subtraction amplifies the accumulation error by about sqrt(mean^2 + var) / std of the row — a small factor for a residual
-  // stream — where normalising on load did not, but on-load cost the 4-waves-per-SIMD loop 4 % (8 VALU ops per K-step).
+  // subtraction amplifies the accumulation error by about sqrt(mean^2 + var) / std of the row — bounded by the range guard's
+  // offset limit (kLnOffsetMax) — where normalising on load did not, but on-load cost the 4-waves-per-SIMD loop 4 % (8 VALU ops per K-step).
   float2 ln_mr = make_float2(0.f, 1.f);
   if (LN && tid < kSM) ln_mr = ln_row_stats(ln_stats, ln_tiles, ln_eps, min(m0 + tid, M - 1), range_flag);
   float4 xa, xw, ya, yw;

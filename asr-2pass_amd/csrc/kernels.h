@@ -43,17 +43,31 @@ void launch_embed(const float* feats, int D, float* x0, int ldx, const int* row_
 // ---- the fp16 two-plane domain guard ---------------------------------------------------------------------------------------
 // The default large-GEMM / attention forms stage their operands as two fp16 planes (gemm_x3.hip header): |a| >= 65504 overflows,
 // rows whose magnitude is far below 1 lose relative precision (absolute error 2^-25 per element).  A forward runs with a
-// per-thread launch context: `range_flag` (device word) is raised by the LayerNorm-folding kernels when a row's rms leaves
-// [2^-8, 2^11] (bit 1: no element of such a row of <= 512 values can reach 65504), by the LayerNorm kernel and by the head when
-// a row is not finite (bit 0: the check sits on the residual stream because ReLU swallows NaN); `exact` routes every split-operand launch of
-// the calling thread to the bf16 three-plane kernels (gemm_x6.hip / attention_x6.hip: fp32's exponent range, exact split) and
-// keeps the encoder off the plane images.  The reference computes in plain fp32 (onnxruntime/src/paraformer.cpp:496-541).
+// per-thread launch context: `range_flag` (device word) is raised (bit 1) by the LayerNorm-folding kernels when a row's CENTRED
+// standard deviation leaves [2^-8, 2^11] (1 / rstd, what the window below is applied to — not the rms: the offset is judged apart)
+// or when its offset |mean| / std exceeds kLnOffsetMax; by the LayerNorm kernel and by the head when a row is not finite (bit 0:
+// the check sits on the residual stream because ReLU swallows NaN).  Inside both limits |x| <= |mean| + sqrt(512) std <=
+// (4 + 22.7) * 2048 < 65504: no element of such a row of <= 512 values overflows a plane.  `exact` routes every split-operand
+// launch of the calling thread to the bf16 three-plane kernels (gemm_x6.hip / attention_x6.hip: fp32's exponent range, exact
+// split), keeps the encoder off the plane images and — the fold cancels in fp32 accumulation as well — the forward off the
+// LayerNorm fold (launch_layernorm + GEMM).  The reference computes in plain fp32 (onnxruntime/src/paraformer.cpp:496-541).
 struct LaunchCtx {
   bool exact = false;
   int* range_flag = nullptr;
 };
 LaunchCtx& launch_ctx();                      // thread-local (gemm.hip)
 constexpr float kLnRstdMin = 1.0f / 2048.0f, kLnRstdMax = 256.0f;
+// The fold rstd * (x W'^T - mean * colsum) subtracts two terms of size |mean| to leave one of size std: it loses |mean| / std of
+// the accumulation's precision on rows the window above cannot see.  Measured against fp64 (DESIGN.md section 2, table "stated
+// domain of the fold"; tests/test_gpu_ln_fold.py::test_fold_stated_domain): at |mean| / std = 4 every form is within the GEMM bound
+// 3e-5 (1.0e-5 .. 1.4e-5), at 16 none is (3.9e-5 .. 5.3e-5, more than 4 x the unfolded fp32 path).  4 is the largest offset of
+// that sweep at which all forms hold, so it is the limit.
+constexpr float kLnOffsetMax = 4.0f;
+// whether a row with these merged statistics is outside the domain of the fold (NaN / Inf statistics are)
+__host__ __device__ inline bool ln_row_out_of_domain(float mean, float rstd) {
+  const float off = mean * rstd;
+  return !(rstd > kLnRstdMin && rstd < kLnRstdMax) || !(off * off <= kLnOffsetMax * kLnOffsetMax);
+}
 
 // ---- dense ops --------------------------------------------------------------------------------
 // C[M,N] = A[M,K] * W[N,K]^T (+bias[N]) (+R1[M,N]) (+R2[M,N]) (ReLU)   — fp32 MFMA 32x32x2.

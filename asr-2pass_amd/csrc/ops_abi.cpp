@@ -78,6 +78,23 @@ int pfhip_op_gemm_f32_scaled(const float* A, int lda, const float* W, int ldw, f
   return (int)hipGetLastError();
 }
 float pfhip_op_best_w_scale(float max_abs) { return pfhip::best_w_scale(max_abs); }
+int pfhip_op_set_launch_ctx(int* range_flag, int exact) {
+  pfhip::launch_ctx().range_flag = range_flag;
+  pfhip::launch_ctx().exact = exact != 0;
+  return 0;
+}
+int pfhip_op_gemm_f32_ln(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1,
+                         const float* R2, int ldr2, int M, int N, int K, int relu, const float* ln_stats, int ln_tiles,
+                         const float* ln_colsum, float* stats_out, float w_scale, void* stream) {
+  // the kernels clamp operand rows to M - 1 / N - 1 and bounds-check every store; what they assume beyond that is checked here
+  if (M <= 0 || N <= 0 || K < pfhip::kTileK || K % pfhip::kTileK || !A || !W || !C || lda < K || ldw < K || ldc < N || (R1 && ldr1 < N) ||
+      (R2 && ldr2 < N) || (lda | ldw | ldc | ldr1 | ldr2) % 4 || !(w_scale > 0.f) || (ln_stats && (!ln_colsum || ln_tiles <= 0 || N % 4)) || (!ln_stats && ln_colsum) ||
+      (stats_out && N % 128))
+    return (int)hipErrorInvalidValue;
+  pfhip::launch_gemm_f32_x6_ln(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu != 0, ln_stats, ln_tiles, ln_colsum, stats_out,
+                               S(stream), w_scale);
+  return (int)hipGetLastError();
+}
 
 size_t pfhip_op_plane_image_bytes(int rows, int K) { return pfhip::plane_image_bytes(rows, K); }
 int pfhip_op_split_planes(const float* X, int ld, int rows_valid, int rows, int K, float scale, void* hi, void* lo, void* stream) {
@@ -93,7 +110,8 @@ int pfhip_op_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh,
   const int mp = (M + 127) / 128 * 128;
   if (M <= 0 || N <= 0 || K < 16 || K % 16 || N % 128 || rows_a % 128 || rows_w % 128 || rows_a < mp || rows_w < N || !Ah || !Al || !Wh ||
       !Wl || (!C && !Ph) || (Ph && (!Pl || rows_p % 128 || rows_p < mp)) || (C && ldc < N) || (R1 && ldr1 < N) || !(w_scale > 0.f) ||
-      (ln_stats && (!ln_colsum || ln_tiles <= 0)) || (tile_rows != 0 && tile_rows != 64 && tile_rows != 128 && tile_rows != 256))
+      (ln_stats && (!ln_colsum || ln_tiles <= 0)) || (stats_out && !C) /* the statistics come out of the fp32 epilogue */ ||
+      (tile_rows != 0 && tile_rows != 64 && tile_rows != 128 && tile_rows != 256))
     return (int)hipErrorInvalidValue;
   pfhip::launch_gemm_p3(Ah, Al, rows_a, Wh, Wl, rows_w, w_scale, C, ldc, Ph, Pl, rows_p, bias, R1, ldr1, M, N, K, relu != 0, ln_stats, ln_tiles,
                         ln_colsum, stats_out, 4, S(stream), tile_rows);

@@ -694,7 +694,9 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   // residual stream (out-projection, FFN2: N = 512 = four column tiles) leaves per-row statistics of each tile in its
   // epilogue; the GEMM that reads it (FFN1, the next layer's QKV) normalises its operand rows while staging them, with
   // gamma / beta folded into its weights (build_model).  One [M, 512] write + read and one launch per LayerNorm less.
-  const bool fuse_ln = m->d_lnw_qkv != nullptr && pfhip::gemm_x6_ln_ok(M);
+  // (not on the exact kernels: the fold's cancellation is a property of fp32 accumulation, not of the planes — kernels.h kLnOffsetMax —
+  // and the exact forward is what a batch flagged for its offset is redone on)
+  const bool fuse_ln = m->d_lnw_qkv != nullptr && pfhip::gemm_x6_ln_ok(M) && !pfhip::launch_ctx().exact;
   const bool mem_in_x = pfhip::attention_fsmn_is_fused(m->maxT);
   if (fuse_ln) HIP_TRY(m->lnstats.ensure((size_t)Mp * 4 * 2 * 4));
   auto gemm_ln = [&](const float* A, const float* Wd, int N, float* Cd, int ldc, const float* bias, const float* R1, const float* R2,
@@ -918,7 +920,7 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   // The decoder's FFN LayerNorms fold the same way (rows >= 4096): norm1 into FFN1 — its input is the residual stream the
   // previous layer's output projection wrote (statistics from that epilogue; the first layer's input comes from the CIF, so it
   // keeps its LayerNorm launch) — and the 2048-wide ffn_norm into FFN2 (FFN1's epilogue leaves 16 pairs per row, after its ReLU).
-  const bool fuse_dec = m->d_dlnw1 != nullptr && pfhip::gemm_x6_ln_ok(ML);
+  const bool fuse_dec = m->d_dlnw1 != nullptr && pfhip::gemm_x6_ln_ok(ML) && !pfhip::launch_ctx().exact;
   const int ftiles = c.dec_ffn / pfhip::kTileN;
   if (fuse_dec) {
     HIP_TRY(m->lnstats.ensure((size_t)std::max(Mp, MLp) * 4 * 2 * 4));
@@ -1214,8 +1216,9 @@ pfhip_status read_range_flag(pfhip_model* m, hipStream_t s, bool sync) {
 
 pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s);
 // The guard of the fp16 two-plane domain (kernels.h LaunchCtx): a forward whose range flag came back raised — a LayerNorm-folded
-// row outside [2^-8, 2^12] rms, or a log-prob row that is not finite — is redone ONCE, inside the same context, on the exact
-// kernels (bf16 three-plane GEMMs and attention, fp32 operands instead of plane images), and counted
+// row whose centred std is outside [2^-8, 2^11] or whose |mean| / std exceeds kLnOffsetMax, or a log-prob row that is not finite — is
+// redone ONCE, inside the same context, on the exact kernels (bf16 three-plane GEMMs and attention, fp32 operands instead of plane
+// images, LayerNorm kernels instead of the fold), and counted
 // (pfhip_debug_poke "range_fallbacks").  The reference computes in plain fp32 (paraformer.cpp:496-541).
 pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s) {
   pfhip_status st = fetch_once(m, out, s);

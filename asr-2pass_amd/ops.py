@@ -94,6 +94,39 @@ def gemm_f32(A, W, bias=None, R1=None, R2=None, relu=False, M=None, N=None, guar
     return out
 
 
+def set_launch_ctx(range_flag=None, exact=False):
+    """The launch context of this thread's later operator calls: range_flag = an int32 device tensor of one word that the
+    LayerNorm-folding kernels OR into (the caller zeroes and reads it; keep it alive until the context is reset), exact = the
+    bf16 three-plane kernels.  set_launch_ctx() restores the default."""
+    lib = _lib()
+    lib.pfhip_op_set_launch_ctx.argtypes = [_vp, _ci]
+    if range_flag is not None and (range_flag.dtype != torch.int32 or range_flag.numel() < 1):
+        raise PfhipError("range_flag must be an int32 device tensor")
+    _ck(lib.pfhip_op_set_launch_ctx(_p(range_flag), 1 if exact else 0), "set_launch_ctx")
+
+
+def gemm_f32_ln(A, W, M=None, N=None, bias=None, R1=None, R2=None, relu=False, ln_stats=None, ln_tiles=0, ln_colsum=None, stats_out=None,
+                w_scale=1.0, out=None):
+    """The in-loop-split GEMM of the product path (csrc/gemm_x3.hip; gemm_x6.hip under set_launch_ctx(exact=True)) with the
+    LayerNorm hand-off: ln_stats / ln_tiles / ln_colsum fold a LayerNorm of A in (W / bias from fold_layernorm), stats_out
+    [rows, N / 128, 2] receives the per-tile (mean, M2) pairs of the result."""
+    lib = _lib()
+    K = A.shape[1]
+    M = A.shape[0] if M is None else M
+    N = W.shape[0] if N is None else N
+    if out is None:
+        out = torch.empty((round_up(M, 128), N), dtype=torch.float32, device=A.device)
+    if w_scale == "auto":
+        w_scale = best_w_scale(float(W.abs().max()))
+    lib.pfhip_op_gemm_f32_ln.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp,
+                                         ctypes.c_float, _vp]
+    _ck(lib.pfhip_op_gemm_f32_ln(_p(A), A.stride(0), _p(W), W.stride(0), _p(out), out.stride(0), _p(bias), _p(R1),
+                                 R1.stride(0) if R1 is not None else 0, _p(R2), R2.stride(0) if R2 is not None else 0, M, N, K,
+                                 1 if relu else 0, _p(ln_stats), ln_tiles, _p(ln_colsum), _p(stats_out), float(w_scale), _stream()),
+        "gemm_f32_ln")
+    return out
+
+
 def fused_ln_gemm(X, W, M, N, g=None, b=None, D=None, bias=None, R1=None, R2=None, fsmn_v=None, fsmn_w=None, relu=False, out=None,
                   eps=1e-12):
     """One streaming window: LN (if g) -> GEMM (+bias +R1 +R2 +FSMN memory of fsmn_v, ReLU) in one launch (M <= 32)."""

@@ -28,6 +28,18 @@ int pfhip_op_gemm_f32_scaled(const float* A, int lda, const float* W, int ldw, f
                              const float* R1, int ldr1, const float* R2, int ldr2, int M, int N, int K, int relu,
                              int guard, int kind, float w_scale, void* stream);
 float pfhip_op_best_w_scale(float max_abs);
+/* The launch context of the calling thread's later operator calls (csrc/kernels.h LaunchCtx): range_flag = a device word the
+ * LayerNorm-folding kernels OR into when a row leaves the fp16 two-plane domain (one word per launch, not per row; the caller
+ * clears and reads it), exact != 0 = every split-operand launch on the bf16 three-plane kernels.  (NULL, 0) restores the default. */
+int pfhip_op_set_launch_ctx(int* range_flag, int exact);
+/* The product path's in-loop-split GEMM with the LayerNorm hand-off (launch_gemm_f32_x6_ln: gemm_x3.hip by default, gemm_x6.hip under
+ * `exact`; tile height by grid size as the model's launches): fp32 A [M, K], W [N, K], K % 32 == 0, row strides % 4 == 0.
+ * ln_stats != NULL: LayerNormalization folded in — A is the raw row, W / bias the gamma / beta-folded ones, ln_colsum[n] =
+ * sum_k W'[n][k], ln_stats [M][ln_tiles][2] the (mean, sum of squared deviations) pairs per 128 columns of A; eps = 1e-12.
+ * stats_out != NULL (N % 128 == 0): the same pairs of the result, [M][N / 128][2]. */
+int pfhip_op_gemm_f32_ln(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1,
+                         const float* R2, int ldr2, int M, int N, int K, int relu, const float* ln_stats, int ln_tiles,
+                         const float* ln_colsum, float* stats_out, float w_scale, void* stream);
 /* Pre-split operands (csrc/gemm_p3.hip): plane images — two fp16 planes of an fp32 matrix, [K/16][rows][16] with the 16-byte halves
  * of a row swapped where row bit 3 is set; rows a multiple of 128 — and the GEMM that consumes and produces them:
  * C = A W^T (x 1 / w_scale, LayerNorm-fold finish, +bias, +R1, ReLU) as fp32 (C != NULL) and / or as plane images (Ph / Pl != NULL).

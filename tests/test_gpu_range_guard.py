@@ -134,3 +134,44 @@ def test_a_raised_flag_redoes_the_batch_once_with_the_same_results(pkg, base):
     check(model, W, utts, picks=(3,))
     assert model.debug_poke("range_fallbacks") == 1                                                   # one forward only
     model.close()
+
+
+def residual_row_std(W, pcm):
+    """(min, max) over the encoder layers and rows of the standard deviation of the residual stream the folded LayerNorms read
+    (oracle, unmodified weights)."""
+    from oracle import frontend
+    x = P.embed(frontend.extract_feats(pcm, W["cmvn.mean"], W["cmvn.istd"]), W.cfg["d_model"])
+    lo, hi = np.inf, 0.0
+    for i in range(W.cfg["enc_layers"]):
+        x = P.encoder_layer(x, W, f"enc.{i}.", W.cfg["n_head"])
+        sd = x.astype(np.float64).std(1)
+        lo, hi = min(lo, float(sd.min())), max(hi, float(sd.max()))
+    return lo, hi
+
+
+@pytest.mark.parametrize("n_utts,seconds", [(8, 30), (6, 22)])
+@pytest.mark.parametrize("above", [False, True])
+def test_common_offset_of_the_residual_stream(pkg, base, n_utts, seconds, above):
+    """Layer 0's output-projection and FFN2 biases carry a common offset c: every later LayerNorm removes it exactly, so the oracle
+    of the UNMODIFIED weights is the reference — but the folded GEMMs subtract mean * colsum from x W'^T, both of size c, and lose
+    c / std of their precision with every element far inside fp16's range (kernels.h kLnOffsetMax = 4).
+    Below the limit (2 c = the smallest row std of the stream: |mean| / std <= 1 on every row): the file's tolerances, no fallback.
+    Above it (c = 16 x the largest row std: |mean| / std >= 16): the same tolerances, through the fallback — the batch is redone
+    unfolded on the exact kernels.  8 x 30 s runs on plane-image operands, 6 x 22 s on the in-loop split."""
+    need_gpu()
+    cfg, (man, blob0) = base
+    W0 = P.Weights(man, blob0)
+    utts = utterances(n_utts, seconds, 8)
+    lo, hi = residual_row_std(W0, utts[0])
+    c = np.float32(16.0 * hi if above else 0.5 * lo)
+    blob = blob0.copy()
+    for name in ("enc.0.out.b", "enc.0.ffn2.b"):
+        view(man, blob, name)[...] += c
+    model = pkg.ParaformerHip().InitAsr((man, blob))
+    assert model.debug_poke("always_exact") == 0
+    worst = check(model, W0, utts, picks=(0, n_utts - 1))
+    print(f"common offset c = {float(c):.3g} (row std {lo:.3g} .. {hi:.3g}): log-prob max abs err {worst:.2e}, "
+          f"fallbacks {model.debug_poke('range_fallbacks')}")
+    assert model.debug_poke("plane_forwards") == (1 if n_utts == 8 else 0)
+    assert (model.debug_poke("range_fallbacks") >= 1) if above else (model.debug_poke("range_fallbacks") == 0)
+    model.close()
