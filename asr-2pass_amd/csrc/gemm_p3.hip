@@ -1083,6 +1083,290 @@ __global__ __launch_bounds__(kPThreads, 3) void gemm_p3_128r3_kernel(
   }
 }
 
+// ---- the 256 x 256 tile: one persistent workgroup of EIGHT waves per CU, half the LDS fill per MFMA ------------------------------
+// The loops above are bound by the rate a CU takes operands into its LDS; this tile moves 32 KB per 192 MFMAs (0.5 x the bytes per MFMA of
+// the 128 x 128 tile, 0.75 x its fragment reads).  Waves 2 (M) x 4 (N), each 128 x 64 = 4 x 2 MFMA tiles held in 128 accumulator
+// registers; 24 MFMAs, 12 fragment reads and 4 DMA pieces per wave and K-step; ring of THREE 32-KB stages.
+//   * The K-steps of all the tiles a workgroup walks (tile b, b + G, b + 2 G ... of a grid of G) form ONE sequence: step s multiplies
+//     the fragments it holds, reads the fragments of step s + 1 from stage (s + 1) % 3 and issues the DMA of step s + 3 into stage s % 3,
+//     whichever tile that step belongs to.  `s_waitcnt vmcnt(4)` + the raw barrier at the end of step s retire the DMA of step s + 2 one
+//     full step (>= 1536 matrix cycles per SIMD) after its issue and one step before it is read; no `vmcnt(0)` and no __syncthreads()
+//     while a DMA is in flight.  The loop of the next tile therefore starts on operands that arrived while this tile's epilogue ran.
+//   * The 256 x 256 fp32 tile does not fit LDS: it leaves in eight slabs of 32 rows through a 33-KB image beside the ring.  Global
+//     stores are fire-and-forget (they only make the next `vmcnt(4)` wait for them too).
+//   * Served forms: LayerNorm fold with fp32 C (OUT 1: QKV') or with plane images of C (OUT 2: FFN1'); no residual, no row statistics
+//     out.  Per accumulator the products stay a_hi w_lo, a_lo w_hi, a_hi w_hi with K-steps ascending and the epilogue is the arithmetic
+//     of the 128-row kernel in its order: bit-identical results.
+constexpr int kWM = 256, kWN = 256, kWThreads = 512;
+constexpr int kWPlane = kWM * kPRowB;                   // 8,192 B: one plane of one operand of one stage
+constexpr int kWStage = 4 * kWPlane;                    // A hi | A lo | W hi | W lo = 32,768 B
+constexpr int kWRing = 3;
+constexpr int kWSlab = 32;                              // rows of the C tile that leave together
+constexpr int kWCs = kWN + 4;                           // padded slab row stride (floats)
+constexpr int kWSlabOff = kWRing * kWStage;             // 98,304
+constexpr int kWMrOff = kWSlabOff + kWSlab * kWCs * 4;  // 131,584: (mean, rstd) of the tile's 256 rows
+constexpr int kWColOff = kWMrOff + kWM * 8;             // 133,632: bias | LayerNorm column sums of the tile's 256 columns
+constexpr int kWLds = kWColOff + 2 * kWN * 4;           // 135,680 B of the CU's 160 KB
+template <bool LN, int OUT>
+__global__ __launch_bounds__(kWThreads) void gemm_p3_256x256_kernel(
+    const unsigned char* __restrict__ Ah, const unsigned char* __restrict__ Al, int rows_a, const unsigned char* __restrict__ Wh,
+    const unsigned char* __restrict__ Wl, int rows_w, float* C, int ldc, unsigned char* __restrict__ Ph, unsigned char* __restrict__ Pl,
+    int rows_p, const float* __restrict__ bias, int M, int N, int K, int tiles_n, int n_tiles, int gw, int relu,
+    const float* __restrict__ ln_stats, int ln_tiles, float ln_eps, const float* __restrict__ ln_colsum, float inv_scale, int* range_flag) {
+  static_assert(OUT == 1 || OUT == 2, "fp32 C or plane images of C");
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave >> 2, wc = wave & 3;                 // 2 x 4 waves of 128 x 64
+  const int r = lane & 31, h = lane >> 5;
+  const int G = gridDim.x;
+  const int nk = K / kPK;
+  const int p_rows = min(rows_p, (M + kPM - 1) / kPM * kPM);      // the plane rows the 128-row kernel's grid writes
+#ifdef PFHIP_P3_STAMPS      // dev build (tools/p3_stamps.py): s_memtime along the life of workgroup 0 and of a mid-grid one, into the C rows of
+                            // their FIRST tile (one row per wave, 128 stamps in the tile's own columns); that tile's results are not stored
+  const bool stamp_wg = C != nullptr && (blockIdx.x == 0 || (int)blockIdx.x == G / 2);
+  const bool stamping = stamp_wg && lane == 0;
+  int n_stamp = 0;
+  unsigned long long* stamp_row = nullptr;
+#define PFHIP_WSTAMP { asm volatile("s_nop 0" ::: "memory"); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (stamping && n_stamp < 128) stamp_row[n_stamp] = t_; ++n_stamp; }
+#else
+#define PFHIP_WSTAMP
+#endif
+
+  // DMA map: per K-step 32 pieces of 1 KB; wave w moves rows 32 w .. 32 w + 31 of A hi, A lo, W hi and W lo.  A row panel that reaches
+  // past the A image (padded row count an odd multiple of 128) is clamped into it: those tile rows are computed on repeated data and
+  // never stored.  The DMA cursor (d_tile, d_ks) runs three steps ahead of the MFMAs, across tile boundaries; behind the last
+  // K-step of the workgroup's last tile it stays there (three redundant copies into stages nobody reads again).
+  const size_t ka = (size_t)rows_a * kPRowB, kw = (size_t)rows_w * kPRowB;      // bytes per K-step of an image
+  size_t off_a, off_w;      // wave-uniform byte offsets of the cursor into the A and W images; the lane adds its 16 bytes
+  const unsigned lane16 = lane * 16;
+  int d_tile = blockIdx.x, d_ks = 0;
+  auto dma_tile = [&](int t) {
+    int tm_, tn_;
+    tile_of_block_p3(t, n_tiles, tiles_n, gw, tm_, tn_);
+    off_a = (size_t)min(tm_ * kWM + 32 * wave, rows_a - 32) * kPRowB;
+    off_w = (size_t)(tn_ * kWN + 32 * wave) * kPRowB;
+  };
+  auto dma_advance = [&] {
+    if (d_ks + 1 < nk) { ++d_ks; off_a += ka; off_w += kw; }
+    else if (d_tile + G < n_tiles) { d_tile += G; d_ks = 0; dma_tile(d_tile); }
+  };
+  dma_tile(d_tile);
+  const int lds_c = wave * 1024;
+#define PFHIP_WDMA1(src, st, region)                                                                                  \
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src),                              \
+                                   (__attribute__((address_space(3))) void*)(lds + (st) + (region) * kWPlane + lds_c), 16, 0, 0);
+#define gah (Ah + off_a + lane16)
+#define gal (Al + off_a + lane16)
+#define gwh (Wh + off_w + lane16)
+#define gwl (Wl + off_w + lane16)
+#define PFHIP_WDMA(st) PFHIP_WDMA1(gah, st, 0) PFHIP_WDMA1(gal, st, 1) PFHIP_WDMA1(gwh, st, 2) PFHIP_WDMA1(gwl, st, 3)
+
+  // fragment addresses (row R of the tile, 8-k piece h, swizzled like the image): rows R and R + 32 share bit 3
+  const int ra = wr * 128 + r, rb = wc * 64 + r;
+  const int a_fr = ra * kPRowB + ((h ^ ((ra >> 3) & 1)) << 4);
+  const int w_fr = 2 * kWPlane + rb * kPRowB + ((h ^ ((rb >> 3) & 1)) << 4);
+
+  float* const slab = reinterpret_cast<float*>(lds + kWSlabOff);
+  float2* const s_mr = reinterpret_cast<float2*>(lds + kWMrOff);
+  float* const s_col = reinterpret_cast<float*>(lds + kWColOff);
+  int tile = blockIdx.x, tm, tn;
+  tile_of_block_p3(tile, n_tiles, tiles_n, gw, tm, tn);
+  LnRaw<4> ls4;      // the row's statistics (d_model = 512: four tiles), requested a loop or an epilogue ahead of their use
+  if (LN && tid < kWM && ln_tiles == 4) ln_raw_load(ls4, ln_stats, min(tm * kWM + tid, M - 1));
+
+  f32x16 acc[4][2];
+  half8 fa[2][4], fb[2][2], ga_[2][4], gb_[2][2];          // [plane][MFMA tile]
+#define PFHIP_SB __builtin_amdgcn_sched_barrier(0)
+#define PFHIP_M(i, j, A_, B_) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A_, B_, acc[i][j], 0, 0, 0); PFHIP_SB;
+#define PFHIP_RA(G_, st, p, i) G_[p][i] = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(lds + (st) + (p) * kWPlane + a_fr + (i) * 32 * kPRowB)); PFHIP_SB;
+#define PFHIP_RB(G_, st, p, j) G_[p][j] = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(lds + (st) + (p) * kWPlane + w_fr + (j) * 32 * kPRowB)); PFHIP_SB;
+#define PFHIP_WBAR asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); PFHIP_SB;
+  // step: fragments FA / FB hold this K-step (stage st_c); read the next step's from stage st_n into GA / GB; DMA the step three
+  // ahead into st_c, one piece behind every sixth MFMA.  Per accumulator: a_hi w_lo, a_lo w_hi, a_hi w_hi.
+#define PFHIP_WSTEP(FA, FB, GA, GB)                                                                                   \
+  {                                                                                                                   \
+    PFHIP_M(0, 0, FA[0][0], FB[1][0]) PFHIP_RA(GA, st_n, 0, 0)                                                        \
+    PFHIP_WDMA1(gah, st_c, 0) PFHIP_SB;                                                                               \
+    PFHIP_M(0, 1, FA[0][0], FB[1][1]) PFHIP_RB(GB, st_n, 0, 0)                                                        \
+    PFHIP_M(1, 0, FA[0][1], FB[1][0]) PFHIP_RA(GA, st_n, 0, 1)                                                        \
+    PFHIP_M(1, 1, FA[0][1], FB[1][1]) PFHIP_RB(GB, st_n, 0, 1)                                                        \
+    PFHIP_M(2, 0, FA[0][2], FB[1][0]) PFHIP_RA(GA, st_n, 0, 2)                                                        \
+    PFHIP_M(2, 1, FA[0][2], FB[1][1]) PFHIP_RA(GA, st_n, 0, 3)                                                        \
+    PFHIP_M(3, 0, FA[0][3], FB[1][0]) PFHIP_RA(GA, st_n, 1, 0)                                                        \
+    PFHIP_WDMA1(gal, st_c, 1) PFHIP_SB;                                                                               \
+    PFHIP_M(3, 1, FA[0][3], FB[1][1]) PFHIP_RB(GB, st_n, 1, 0)                                                        \
+    PFHIP_M(0, 0, FA[1][0], FB[0][0]) PFHIP_RA(GA, st_n, 1, 1)                                                        \
+    PFHIP_M(0, 1, FA[1][0], FB[0][1]) PFHIP_RB(GB, st_n, 1, 1)                                                        \
+    PFHIP_M(1, 0, FA[1][1], FB[0][0]) PFHIP_RA(GA, st_n, 1, 2)                                                        \
+    PFHIP_M(1, 1, FA[1][1], FB[0][1]) PFHIP_RA(GA, st_n, 1, 3)                                                        \
+    PFHIP_M(2, 0, FA[1][2], FB[0][0])                                                                                 \
+    PFHIP_WDMA1(gwh, st_c, 2) PFHIP_SB;                                                                               \
+    PFHIP_M(2, 1, FA[1][2], FB[0][1])                                                                                 \
+    PFHIP_M(3, 0, FA[1][3], FB[0][0])                                                                                 \
+    PFHIP_M(3, 1, FA[1][3], FB[0][1])                                                                                 \
+    PFHIP_M(0, 0, FA[0][0], FB[0][0])                                                                                 \
+    PFHIP_M(0, 1, FA[0][0], FB[0][1])                                                                                 \
+    PFHIP_M(1, 0, FA[0][1], FB[0][0])                                                                                 \
+    PFHIP_WDMA1(gwl, st_c, 3) PFHIP_SB;                                                                               \
+    PFHIP_M(1, 1, FA[0][1], FB[0][1])                                                                                 \
+    PFHIP_M(2, 0, FA[0][2], FB[0][0])                                                                                 \
+    PFHIP_M(2, 1, FA[0][2], FB[0][1])                                                                                 \
+    PFHIP_M(3, 0, FA[0][3], FB[0][0])                                                                                 \
+    PFHIP_M(3, 1, FA[0][3], FB[0][1])                                                                                 \
+    dma_advance();                                                                                                    \
+    { const int t_ = st_c; st_c = st_n; st_n = st_x; st_x = t_; }                                                     \
+    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");                                          \
+    PFHIP_SB;                                                                                                         \
+  }
+
+  int st_c = 0, st_n = kWStage, st_x = 2 * kWStage;
+  PFHIP_WDMA(0) dma_advance();
+  PFHIP_WDMA(kWStage) dma_advance();
+  PFHIP_WDMA(2 * kWStage) dma_advance();
+
+  for (;;) {
+    const int m0 = tm * kWM, n0 = tn * kWN;
+#ifdef PFHIP_P3_STAMPS
+    if (tile == (int)blockIdx.x && C) stamp_row = reinterpret_cast<unsigned long long*>(C + (size_t)min(m0 + wave, M - 1) * ldc + n0);
+    PFHIP_WSTAMP
+#endif
+    if (LN && tid < kWM) s_mr[tid] = ln_tiles == 4 ? ln_row_stats_raw(ls4, ln_eps, range_flag) : ln_row_stats(ln_stats, ln_tiles, ln_eps, min(m0 + tid, M - 1), range_flag);
+    if (wave == 4) *reinterpret_cast<float4*>(s_col + 4 * lane) = bias ? *reinterpret_cast<const float4*>(bias + n0 + 4 * lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (wave == 5) *reinterpret_cast<float4*>(s_col + kWN + 4 * lane) = LN ? *reinterpret_cast<const float4*>(ln_colsum + n0 + 4 * lane) : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tile == (int)blockIdx.x) {
+      asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");        // K-steps 0 and 1 have landed, for every wave
+      PFHIP_SB;
+      PFHIP_RA(fa, 0, 0, 0) PFHIP_RA(fa, 0, 0, 1) PFHIP_RA(fa, 0, 0, 2) PFHIP_RA(fa, 0, 0, 3)
+      PFHIP_RA(fa, 0, 1, 0) PFHIP_RA(fa, 0, 1, 1) PFHIP_RA(fa, 0, 1, 2) PFHIP_RA(fa, 0, 1, 3)
+      PFHIP_RB(fb, 0, 0, 0) PFHIP_RB(fb, 0, 0, 1) PFHIP_RB(fb, 0, 1, 0) PFHIP_RB(fb, 0, 1, 1)
+      PFHIP_WBAR                                                            // stage 0 is free for the DMA of step 3
+    }
+    PFHIP_WSTAMP
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) { acc[i][0][e] = 0.f; acc[i][1][e] = 0.f; }
+    // the tile's K-steps, two per trip (the fragment sets alternate); behind an odd count the live set moves back into fa / fb
+    for (int k = nk;;) {
+      PFHIP_WSTEP(fa, fb, ga_, gb_)
+      PFHIP_WSTAMP
+      if (--k == 0) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) fa[p][i] = ga_[p][i];
+          fb[p][0] = gb_[p][0]; fb[p][1] = gb_[p][1];
+        }
+        break;
+      }
+      PFHIP_WSTEP(ga_, gb_, fa, fb)
+      PFHIP_WSTAMP
+      if (--k == 0) break;
+    }
+
+    // ---- epilogue: eight slabs of 32 rows; the ring already holds (or is receiving) the first K-steps of the next tile ----------------
+    const int next = tile + G;
+    int tm_n = tm, tn_n = tn;
+    if (next < n_tiles) {
+      tile_of_block_p3(next, n_tiles, tiles_n, gw, tm_n, tn_n);
+      if (LN && tid < kWM && ln_tiles == 4) ln_raw_load(ls4, ln_stats, min(tm_n * kWM + tid, M - 1));
+    }
+#ifdef PFHIP_P3_STAMPS
+    const bool do_store = !(stamp_wg && tile == (int)blockIdx.x);      // its C rows hold the stamps
+#else
+    const bool do_store = true;
+#endif
+    // OUT 1: thread = 4 columns (64 lanes x 16 B = the tile's 1 KB of a row); OUT 2: thread = (row, 16-column group pj = K-step of the consumer)
+    float4 e_bv = make_float4(0.f, 0.f, 0.f, 0.f), e_cs = e_bv;
+    const int pj = 2 * wave + h;
+    if (OUT == 1) {
+      e_bv = *reinterpret_cast<const float4*>(s_col + 4 * lane);
+      e_cs = *reinterpret_cast<const float4*>(s_col + kWN + 4 * lane);
+    }
+#pragma unroll
+    for (int sh = 0; sh < kWM / kWSlab; ++sh) {
+      if (wr == (sh >> 2)) {      // the four waves that hold these rows: accumulator row (e & 3) + 8 (e >> 2) + 4 h, column r
+        float* cw = slab + (4 * h) * kWCs + wc * 64 + r;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int ro = ((e & 3) + 8 * (e >> 2)) * kWCs;
+          cw[ro] = acc[sh & 3][0][e];
+          cw[ro + 32] = acc[sh & 3][1][e];
+        }
+      }
+      PFHIP_WBAR
+      if (OUT == 1) {      // fp32 rows: one wave = one full 1-KB row piece, eight rows per pass
+#pragma unroll
+        for (int pass = 0; pass < kWSlab / 8; ++pass) {
+          const int row = pass * 8 + wave, grow = m0 + kWSlab * sh + row;
+          float4 v = *reinterpret_cast<const float4*>(slab + row * kWCs + 4 * lane);
+          v.x *= inv_scale; v.y *= inv_scale; v.z *= inv_scale; v.w *= inv_scale;
+          if (LN) {
+            const float2 mr = s_mr[kWSlab * sh + row];
+            v.x = mr.y * (v.x - mr.x * e_cs.x); v.y = mr.y * (v.y - mr.x * e_cs.y); v.z = mr.y * (v.z - mr.x * e_cs.z); v.w = mr.y * (v.w - mr.x * e_cs.w);
+          }
+          v.x += e_bv.x + 0.f; v.y += e_bv.y + 0.f; v.z += e_bv.z + 0.f; v.w += e_bv.w + 0.f;      // (+ the residual the other forms add)
+          if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+          if (do_store && grow < M) *reinterpret_cast<float4*>(C + (size_t)grow * ldc + n0 + 4 * lane) = v;
+        }
+      } else {             // plane images of C: 32 lanes = the slab's rows of one K-step of the consumer = 1 KB per plane, contiguous
+        const int row = r, grow = m0 + kWSlab * sh + row;
+        const float2 mr = LN ? s_mr[kWSlab * sh + row] : make_float2(0.f, 1.f);
+        const int ksp = (n0 >> 4) + pj;
+#pragma unroll
+        for (int pc = 0; pc < 2; ++pc) {      // the two 8-column pieces of the group, one after the other (registers)
+          float v[8];
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const float4 t = *reinterpret_cast<const float4*>(slab + row * kWCs + 16 * pj + 8 * pc + 4 * c);
+            const float4 b4 = *reinterpret_cast<const float4*>(s_col + 16 * pj + 8 * pc + 4 * c);
+            const float4 s4 = *reinterpret_cast<const float4*>(s_col + kWN + 16 * pj + 8 * pc + 4 * c);
+            const float tt[4] = {t.x, t.y, t.z, t.w}, bb[4] = {b4.x, b4.y, b4.z, b4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              float x = tt[e] * inv_scale;
+              if (LN) x = mr.y * (x - mr.x * ss[e]);
+              x += bb[e];
+              if (relu) x = fmaxf(x, 0.f);
+              v[4 * c + e] = x;
+            }
+          }
+          uint4 hh, ll;
+          split8(v, hh, ll);
+          if (do_store && grow < p_rows) {
+            const size_t off = image_off(ksp, grow, pc, rows_p);
+            *reinterpret_cast<uint4*>(Ph + off) = hh;
+            *reinterpret_cast<uint4*>(Pl + off) = ll;
+          }
+        }
+      }
+      PFHIP_WBAR                                              // the next slab overwrites the image
+      PFHIP_WSTAMP
+    }
+    if (next >= n_tiles) break;
+    tile = next; tm = tm_n; tn = tn_n;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the redundant DMAs behind the last K-step
+#ifdef PFHIP_P3_STAMPS
+  if (stamping && n_stamp < 127) { stamp_row[n_stamp] = __builtin_amdgcn_s_memtime(); stamp_row[127] = (unsigned long long)n_stamp; }
+#endif
+#undef PFHIP_WSTEP
+#undef PFHIP_WBAR
+#undef PFHIP_M
+#undef PFHIP_RA
+#undef PFHIP_RB
+#undef PFHIP_SB
+#undef PFHIP_WDMA
+#undef PFHIP_WDMA1
+#undef gah
+#undef gal
+#undef gwh
+#undef gwl
+#undef PFHIP_WSTAMP
+}
+
 template <auto kern, int threads = kPThreads, class... Args>
 void launch_with_lds(int n_tiles, int lds_bytes, hipStream_t s, Args... args) {
   static std::atomic<unsigned long long> attr_done{0};      // > 64 KB of dynamic LDS needs the opt-in once per kernel and device
@@ -1106,14 +1390,66 @@ void launch_split_planes(const float* X, int ld, int rows_valid, int rows, int K
                      static_cast<unsigned char*>(hi), static_cast<unsigned char*>(lo));
 }
 
+// ---- dispatch of the 256 x 256 tile ----------------------------------------------------------------------------------------------------
+namespace {
+std::atomic<long> g_wide_launches{0};
+int cu_count() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  int n = cus[dev & 63].load(std::memory_order_relaxed);
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev & 63].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+}  // namespace
+long gemm_p3_wide_launches() { return g_wide_launches.load(std::memory_order_relaxed); }
+bool gemm_p3_wide_serves(bool c, bool planes, bool r1, bool ln, bool stats_out, int row_planes_from, int N, int K) {
+  return ln && c != planes && !r1 && !stats_out && row_planes_from <= 0 && N > 0 && N % kWN == 0 && K >= kPK && K % kPK == 0;
+}
+
 #ifndef PFHIP_P3_LDS_PAD
 #define PFHIP_P3_LDS_PAD 0      // timing-only builds: extra LDS per workgroup of the 128-row kernel (32768: ONE workgroup per CU)
 #endif
 void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, const void* Wl, int rows_w, float w_scale, float* C, int ldc,
                     void* Ph, void* Pl, int rows_p, const float* bias, const float* R1, int ldr1, int M, int N, int K, bool relu,
                     const float* ln_stats, int ln_tiles, const float* ln_colsum, float* stats_out, int gw, hipStream_t s, int tile_rows,
-                    int row_planes_from) {
+                    int row_planes_from, int tile_cols) {
   if (M <= 0 || N <= 0) return;
+  // The 256 x 256 tile (one persistent eight-wave workgroup per CU): the LayerNorm-folded forms with one output (FFN1', QKV') where its
+  // tiles fill at least 85 % of the CU slots of their rounds (the rule of the 256 x 128 tile), there is more than one round (the
+  // overlap of a tile's epilogue with the next tile's first DMAs is what the single workgroup per CU lives on; one-round grids such as
+  // the decoder's 7015-row FFN1' have not been measured and stay where they were) and K >= 256, d_model = 512 statistics.  Measured
+  // (tools/p3_probe.py, 16000 rows, three alternated pairs): FFN1' 104.6 - 106.2 us against 121.9 - 124.4 on the parent's 128r3 kernel;
+  // QKV' forced onto this tile (378 tiles: 74 % of two rounds) 99.2 - 100.6 against 94.9 - 99.1: not taken, and the rule leaves it out.  PFHIP_P3_WIDE=0 keeps the 128-column kernels (read per launch: tests and A/B runs switch it);
+  // tile_cols = 256 forces it for any form it serves.
+  {
+    const bool serves = gemm_p3_wide_serves(C != nullptr, Ph != nullptr, R1 != nullptr, ln_stats != nullptr, stats_out != nullptr, row_planes_from, N, K);
+    const int nw = ((M + kWM - 1) / kWM) * (N / kWN), cus = cu_count(), rounds = (nw + cus - 1) / cus;
+    const char* e = getenv("PFHIP_P3_WIDE");
+    const bool w_env = !(e && e[0] == '0');
+    static const int half_lim = [] { const char* h = getenv("PFHIP_P3_HALF_TILES"); return h && *h ? atoi(h) : 400; }();
+    const bool by_rule = tile_cols == 0 && tile_rows == 0 && w_env && serves && ln_tiles == 4 && K >= 256 && rows_a >= kWM && nw > cus &&
+                         ((M + kPM - 1) / kPM) * ((N + kPN - 1) / kPN) > half_lim && 100 * nw >= 85 * cus * rounds;
+    if (serves && (tile_cols == kWN || by_rule)) {
+      const int grid = (nw + rounds - 1) / rounds;      // every workgroup walks `rounds` tiles where that divides (504 tiles: 252 x 2)
+      const float inv = 1.0f / w_scale;
+      const unsigned char *ah = static_cast<const unsigned char*>(Ah), *al = static_cast<const unsigned char*>(Al);
+      const unsigned char *wh = static_cast<const unsigned char*>(Wh), *wl = static_cast<const unsigned char*>(Wl);
+      const int tn = N / kWN, g = std::max(1, std::min(gw, tn));
+      g_wide_launches.fetch_add(1, std::memory_order_relaxed);
+      if (C)
+        launch_with_lds<gemm_p3_256x256_kernel<true, 1>, kWThreads>(grid, kWLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, nullptr, nullptr, rows_p, bias,
+                                                                    M, N, K, tn, nw, g, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, inv, launch_ctx().range_flag);
+      else
+        launch_with_lds<gemm_p3_256x256_kernel<true, 2>, kWThreads>(grid, kWLds, s, ah, al, rows_a, wh, wl, rows_w, nullptr, 0, static_cast<unsigned char*>(Ph),
+                                                                    static_cast<unsigned char*>(Pl), rows_p, bias, M, N, K, tn, nw, g, relu ? 1 : 0, ln_stats,
+                                                                    ln_tiles, 1e-12f, ln_colsum, inv, launch_ctx().range_flag);
+      return;
+    }
+  }
   const int tiles_n = (N + kPN - 1) / kPN;
   // 64-row tiles (three workgroups per CU) when 128-row tiles would leave most of a round of 512 slots empty
   static const int half_env = [] { const char* e = getenv("PFHIP_P3_HALF_TILES"); return e && *e ? atoi(e) : 400; }();

@@ -108,7 +108,12 @@ void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, 
                     void* Ph, void* Pl, int rows_p, const float* bias, const float* R1, int ldr1, int M, int N, int K, bool relu,
                     const float* ln_stats, int ln_tiles, const float* ln_colsum, float* stats_out, int gw, hipStream_t s,
                     int tile_rows = 0,       // 0: 64-row tiles when 128-row tiles would fill less than a round; 64 / 128 force one
-                    int row_planes_from = 0);
+                    int row_planes_from = 0,
+                    int tile_cols = 0);      // 256: the 256 x 256 tile, for the forms gemm_p3_wide_serves() names (tile_rows 0)
+// whether the 256 x 256 tile has this form (LayerNorm fold, fp32 C or plane images of C but not both, no residual, no statistics out,
+// N % 256 == 0), and how many launches of this process it has served (tests, probes)
+bool gemm_p3_wide_serves(bool c, bool planes, bool r1, bool ln, bool stats_out, int row_planes_from, int N, int K);
+long gemm_p3_wide_launches();
 // row_planes_from = c > 0 (the encoder's QKV projection, C given): columns < c leave as fp32 rows of C, columns >= c as ROW-MAJOR fp16
 // planes Ph / Pl [M][rows_p] (rows_p = elements per plane row; column n at element n - c) — the K | V operand of attention_p3.hip.
 // c % 128 == 0; 128- and 64-row tiles only.

@@ -117,6 +117,25 @@ int pfhip_op_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh,
                         ln_colsum, stats_out, 4, S(stream), tile_rows);
   return (int)hipGetLastError();
 }
+// The same with a tile-width selector: tile_cols 0 = as pfhip_op_gemm_p3, 256 = the 256 x 256 tile (tile_rows must be 0), refused for the
+// forms and shapes that kernel does not serve.
+int pfhip_op_gemm_p3_cols(const void* Ah, const void* Al, int rows_a, const void* Wh, const void* Wl, int rows_w, float w_scale, float* C, int ldc,
+                          void* Ph, void* Pl, int rows_p, const float* bias, const float* R1, int ldr1, int M, int N, int K, int relu,
+                          const float* ln_stats, int ln_tiles, const float* ln_colsum, float* stats_out, int tile_rows, int tile_cols, void* stream) {
+  if (tile_cols == 0)
+    return pfhip_op_gemm_p3(Ah, Al, rows_a, Wh, Wl, rows_w, w_scale, C, ldc, Ph, Pl, rows_p, bias, R1, ldr1, M, N, K, relu, ln_stats, ln_tiles, ln_colsum,
+                            stats_out, tile_rows, stream);
+  const int mp = (M + 127) / 128 * 128;
+  if (tile_cols != 256 || tile_rows != 0 || M <= 0 || N <= 0 || K < 16 || K % 16 || N % 256 || rows_a % 128 || rows_w % 128 || rows_a < mp ||
+      rows_w < N || !Ah || !Al || !Wh || !Wl || (Ph && (!Pl || rows_p % 128 || rows_p < mp)) || (C && ldc < N) || !(w_scale > 0.f) ||
+      (ln_stats && (!ln_colsum || ln_tiles <= 0)) ||
+      !pfhip::gemm_p3_wide_serves(C != nullptr, Ph != nullptr, R1 != nullptr, ln_stats != nullptr, stats_out != nullptr, 0, N, K))
+    return (int)hipErrorInvalidValue;
+  pfhip::launch_gemm_p3(Ah, Al, rows_a, Wh, Wl, rows_w, w_scale, C, ldc, Ph, Pl, rows_p, bias, nullptr, 0, M, N, K, relu != 0, ln_stats, ln_tiles,
+                        ln_colsum, nullptr, 4, S(stream), 0, 0, 256);
+  return (int)hipGetLastError();
+}
+long pfhip_op_gemm_p3_wide_launches(void) { return pfhip::gemm_p3_wide_launches(); }
 
 int pfhip_op_layernorm(const float* x, int ldx, float* y, int ldy, const float* g, const float* b, int M, int D,
                        int Dout, float eps, void* stream) {

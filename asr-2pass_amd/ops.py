@@ -293,9 +293,9 @@ def planes_to_float(hi, lo, rows, K):
 
 
 def gemm_p3(A_img, W_img, M, N, K, w_scale=1.0, bias=None, R1=None, relu=False, want_c=True, want_planes=False, ln_stats=None,
-            ln_tiles=0, ln_colsum=None, stats_out=None, out=None, out_planes=None, tile_rows=0):
+            ln_tiles=0, ln_colsum=None, stats_out=None, out=None, out_planes=None, tile_rows=0, tile_cols=0):
     """A_img / W_img: (hi, lo, rows) from split_planes.  Returns (C or None, (hi, lo, rows) of C or None).  out / out_planes: reuse
-    buffers of an earlier call (timing loops)."""
+    buffers of an earlier call (timing loops).  tile_cols=256 forces the 256 x 256 tile (RuntimeError for a form it does not serve)."""
     lib = _lib()
     ah, al, ra = A_img
     wh, wl, rw = W_img
@@ -309,10 +309,22 @@ def gemm_p3(A_img, W_img, M, N, K, w_scale=1.0, bias=None, R1=None, relu=False, 
         P = (torch.zeros(nb, dtype=torch.uint8, device=ah.device), torch.zeros(nb, dtype=torch.uint8, device=ah.device), Mp)
     lib.pfhip_op_gemm_p3.argtypes = [_vp, _vp, _ci, _vp, _vp, _ci, ctypes.c_float, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _ci,
                                      _vp, _ci, _vp, _vp, _ci, _vp]
-    _ck(lib.pfhip_op_gemm_p3(_p(ah), _p(al), ra, _p(wh), _p(wl), rw, float(w_scale), _p(C), N if want_c else 0, _p(P[0]) if P else None,
-                             _p(P[1]) if P else None, Mp, _p(bias), _p(R1), R1.stride(0) if R1 is not None else 0, M, N, K,
-                             1 if relu else 0, _p(ln_stats), ln_tiles, _p(ln_colsum), _p(stats_out), tile_rows, _stream()), "gemm_p3")
+    args = (_p(ah), _p(al), ra, _p(wh), _p(wl), rw, float(w_scale), _p(C), N if want_c else 0, _p(P[0]) if P else None,
+            _p(P[1]) if P else None, Mp, _p(bias), _p(R1), R1.stride(0) if R1 is not None else 0, M, N, K,
+            1 if relu else 0, _p(ln_stats), ln_tiles, _p(ln_colsum), _p(stats_out), tile_rows)
+    if tile_cols:
+        lib.pfhip_op_gemm_p3_cols.argtypes = lib.pfhip_op_gemm_p3.argtypes[:-1] + [_ci, _vp]
+        _ck(lib.pfhip_op_gemm_p3_cols(*args, tile_cols, _stream()), "gemm_p3")
+    else:
+        _ck(lib.pfhip_op_gemm_p3(*args, _stream()), "gemm_p3")
     return C, P
+
+
+def gemm_p3_wide_launches():
+    """Launches of this process that the 256 x 256 tile of gemm_p3 has served."""
+    lib = _lib()
+    lib.pfhip_op_gemm_p3_wide_launches.restype = ctypes.c_long
+    return int(lib.pfhip_op_gemm_p3_wide_launches())
 
 
 # ---- K | V as row-major planes (csrc/attention_p3.hip) ------------------------------------------------------------------------------

@@ -49,6 +49,15 @@ int pfhip_op_split_planes(const float* X, int ld, int rows_valid, int rows, int 
 int pfhip_op_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, const void* Wl, int rows_w, float w_scale, float* C, int ldc,
                      void* Ph, void* Pl, int rows_p, const float* bias, const float* R1, int ldr1, int M, int N, int K, int relu,
                      const float* ln_stats, int ln_tiles, const float* ln_colsum, float* stats_out, int tile_rows, void* stream);
+/* The same with a tile-width selector.  tile_cols: 0 = as pfhip_op_gemm_p3; 256 = the 256 x 256 tile (one persistent workgroup per CU;
+ * bit-identical results), which serves the LayerNorm-folded forms with ONE output (C or the plane images, not both), no residual, no
+ * stats_out, N % 256 == 0, tile_rows 0 — anything else is refused with hipErrorInvalidValue and launches nothing. */
+int pfhip_op_gemm_p3_cols(const void* Ah, const void* Al, int rows_a, const void* Wh, const void* Wl, int rows_w, float w_scale, float* C, int ldc,
+                          void* Ph, void* Pl, int rows_p, const float* bias, const float* R1, int ldr1, int M, int N, int K, int relu,
+                          const float* ln_stats, int ln_tiles, const float* ln_colsum, float* stats_out, int tile_rows, int tile_cols,
+                          void* stream);
+/* How many pfhip_op_gemm_p3* / model launches of this process the 256 x 256 tile has served (tests of the default dispatch, probes). */
+long pfhip_op_gemm_p3_wide_launches(void);
 /* LayerNormalization over the last axis. */
 int pfhip_op_layernorm(const float* x, int ldx, float* y, int ldy, const float* g, const float* b, int M, int D,
                        int Dout, float eps, void* stream);
