@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "pfhip_offline_forward", "pfhip_offline_enqueue", "pfhip_offline_fetch", "pfhip_offline_forward_resident",
     "pfhip_resample_len", "pfhip_resample", "pfhip_offline_forward_rate",
     "pfhip_set_batching", "pfhip_set_inflight", "pfhip_warm_up", "pfhip_get_inflight", "pfhip_inflight_stats", "pfhip_is_contextual", "pfhip_has_timestamp_head", "pfhip_hotword_embed", "pfhip_set_hotwords",
+    "pfhip_offline_forward_hwsets", "pfhip_set_hotword_bank_bytes", "pfhip_set_hotword_merging", "pfhip_hotword_bank_stats",
     "pfhip_extract_feats", "pfhip_get_tensor", "pfhip_debug_poke", "pfhip_profile_enable", "pfhip_profile_read",
     "pfhip_stream_create", "pfhip_stream_destroy", "pfhip_stream_reset", "pfhip_stream_forward", "pfhip_stream_last_path", "pfhip_stream_forward_batch", "pfhip_set_stream_batching",
     "pfhip_stream_set_debug", "pfhip_stream_get_tensor",
@@ -64,6 +65,11 @@ class _Out(ctypes.Structure):
 class _SlotStats(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("context", ctypes.c_int32), ("forwards", ctypes.c_int64),
                 ("calls", ctypes.c_int64), ("utterances", ctypes.c_int64)]
+
+
+class _HwBankStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("hits", "misses", "evictions", "refused", "bytes_in_use", "bytes_capacity", "sets_resident",
+                                              "forwards", "per_call_forwards", "sets_in_forwards", "max_sets_in_forward")]
 
 
 class _Profile(ctypes.Structure):
@@ -131,6 +137,12 @@ def load_lib() -> ctypes.CDLL:
     lib.pfhip_is_contextual.argtypes = [vp]
     lib.pfhip_hotword_embed.argtypes = [vp, vp, vp, ci, vp]
     lib.pfhip_set_hotwords.argtypes = [vp, vp, ci]
+    if hasattr(lib, "pfhip_offline_forward_hwsets"):          # (an older build loaded through PFHIP_LIB for A/B timing has none of these)
+        lib.pfhip_offline_forward_hwsets.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci,
+                                                     ctypes.POINTER(ci), ctypes.POINTER(_Out)]
+        lib.pfhip_set_hotword_bank_bytes.argtypes = [vp, ctypes.c_int64]
+        lib.pfhip_set_hotword_merging.argtypes = [vp, ci]
+        lib.pfhip_hotword_bank_stats.argtypes = [vp, ctypes.POINTER(_HwBankStats)]
     lib.pfhip_stream_create.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(vp)]
     lib.pfhip_stream_destroy.argtypes = [vp]
     lib.pfhip_stream_destroy.restype = None
@@ -337,6 +349,21 @@ class ParaformerHip:
         return [dict(device=a.device, context=a.context, forwards=a.forwards, calls=a.calls, utterances=a.utterances)
                 for a in arr[:n.value]]
 
+    def set_hotword_merging(self, on=True):
+        """Contextual callers join the merge queue of set_batching, each with its own hotword sets (pfhip_set_hotword_merging)."""
+        _check(self._lib, self._lib.pfhip_set_hotword_merging(self._h, int(bool(on))))
+
+    def set_hotword_bank_bytes(self, nbytes):
+        """Bound of the per-device bank of projected hotword sets (pfhip_set_hotword_bank_bytes); call while nothing is in flight."""
+        _check(self._lib, self._lib.pfhip_set_hotword_bank_bytes(self._h, int(nbytes)))
+
+    def hotword_bank_stats(self):
+        """dict of the pfhip_hwbank_stats fields: hits, misses, evictions, refused, bytes_in_use, bytes_capacity, sets_resident,
+        forwards, per_call_forwards, sets_in_forwards, max_sets_in_forward (pfhip_hotword_bank_stats)."""
+        st = _HwBankStats()
+        _check(self._lib, self._lib.pfhip_hotword_bank_stats(self._h, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _HwBankStats._fields_}
+
     def StartUtterance(self):  # paraformer.cpp:297-307: stateless
         pass
 
@@ -394,9 +421,11 @@ class ParaformerHip:
         return [o[:got[b]] for b, o in enumerate(outs)]
 
     def forward_ids(self, din: Sequence[np.ndarray], want_logp=False, max_tokens=None, hw_emb=None, want_timestamps=False,
-                    sample_rate=None):
+                    sample_rate=None, hw_sets=None, set_of_utt=None):
         """Batched forward.  Returns dict(token_num, n_fires, n_frames, ids=list of int arrays,
         logp=list of [n_fires, V] arrays or None[, us_alphas, us_peaks = lists of [3*T_b] arrays]).
+        hw_emb: one hotword set [H, d] for the whole batch.  hw_sets + set_of_utt: a list of sets ([H_k, d] each) and, per
+        utterance, the index of the set it attends to (pfhip_offline_forward_hwsets); not together with hw_emb or sample_rate.
         sample_rate: the rate of din when it is not the model's (pfhip_offline_forward_rate resamples on the GPU first)."""
         B = len(din)
         if B == 0:
@@ -435,7 +464,15 @@ class ParaformerHip:
             out.max_us = max_us
         hw = np.ascontiguousarray(hw_emb, dtype=np.float32) if hw_emb is not None else None
         hw_ptr, n_hw = (hw.ctypes.data, int(hw.shape[0])) if hw is not None else (None, 0)
-        if sample_rate is None:
+        if hw_sets is not None:
+            if hw_emb is not None or sample_rate is not None or set_of_utt is None or len(set_of_utt) != B:
+                raise PfhipError("hw_sets needs set_of_utt [batch] and excludes hw_emb / sample_rate")
+            sets = [np.ascontiguousarray(h, dtype=np.float32) for h in hw_sets]
+            sptr = (ctypes.c_void_p * max(len(sets), 1))(*[h.ctypes.data if h.size else None for h in sets])
+            sn = (ctypes.c_int * max(len(sets), 1))(*[int(h.shape[0]) for h in sets])
+            sof = (ctypes.c_int * B)(*[int(k) for k in set_of_utt])
+            _check(self._lib, self._lib.pfhip_offline_forward_hwsets(self._h, ptrs, lens, B, sptr, sn, len(sets), sof, ctypes.byref(out)))
+        elif sample_rate is None:
             _check(self._lib, self._lib.pfhip_offline_forward(self._h, ptrs, lens, B, hw_ptr, n_hw, ctypes.byref(out)))
         else:
             _check(self._lib, self._lib.pfhip_offline_forward_rate(self._h, ptrs, lens, B, int(sample_rate), hw_ptr, n_hw,

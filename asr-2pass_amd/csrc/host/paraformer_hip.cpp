@@ -107,6 +107,9 @@ void ParaformerHip::LoadOffline(const std::string& am_model, const std::string& 
     std::fprintf(stderr, "ParaformerHip::InitAsr: %s (one forward at a time)\n", pfhip_last_error());
   const int wait_us = Knob("PFHIP_OFFLINE_WAIT_US", 3000);     // 0 = no merging
   if (wait_us > 0) pfhip_set_batching(handle_, wait_us, Knob("PFHIP_OFFLINE_MAX", 96));   // 96 merged utterances: +16 % over 32 on the long-audio flow
+  // contextual model: every connection brings its own hotword list to each Forward (websocket-server.cpp:316-359); the callers are
+  // merged all the same, each utterance of the packed forward attends to its caller's set (pfhip_set_hotword_merging)
+  if (wait_us > 0 && pfhip_is_contextual(handle_) && Knob("PFHIP_HOTWORD_MERGE", 1) != 0) pfhip_set_hotword_merging(handle_, 1);
   delete vocab;
   vocab = LoadVocab(token_file);                                // paraformer.cpp:47-48
   // ParaformerTorch::WarmUp (paraformer-torch.cpp:59,477-520): a dummy forward inside InitAsr.  Here through every execution
@@ -256,7 +259,9 @@ std::vector<std::string> ParaformerHip::Forward(float** din, int* len, bool inpu
     usp.resize((size_t)batch_in * max_us);
     out.us_alphas = usa.data(); out.us_peaks = usp.data(); out.us_len = usl.data(); out.max_us = max_us;
   }
-  // hw_emb [H][d] as the reference passes it (paraformer.cpp:515-531); plain models ignore it
+  // hw_emb [H][d] as the reference passes it (paraformer.cpp:515-531); plain models ignore it.  It is THIS caller's set: in a
+  // merged forward every caller's utterances attend to their own, and the device's hotword bank finds the connection's projected
+  // rows again by content, so the same list sent with every VAD segment is uploaded and projected once
   std::vector<float> hw;
   int n_hw = 0;
   if (pfhip_is_contextual(handle_)) {

@@ -11,12 +11,17 @@
 // turn an argmax at a near-tie.  `mismatches` counts requests that differ by more than ONE substituted token (or in length, or
 // in their time stamps with equal tokens) — these fail the run; `near_tie_flips` counts requests with exactly one substituted
 // token, reported for the caller to bound.
-//   serve_threads <model_dir> <vad_dir|-> [decoder_threads=16] [requests=64] [min_s=3] [max_s=12] [model_thread_num=1]
+//   serve_threads <model_dir> <vad_dir|-> [decoder_threads=16] [requests=64] [min_s=3] [max_s=12] [model_thread_num=1] [hotword_file]
+// hotword_file (contextual model): one hotword list per line, the hotwords separated by blanks as a client sends them; each line is
+// compiled once (CompileHotwordEmbedding, as a connection does at its first message, websocket-server.cpp:316-359) and request r is
+// served with list r % lines, alone and from the decoder threads, so concurrent callers carry different lists into the merge
+// queue.  The hotword bank's counters join the JSON line.  Without the file: no hotwords, as before.
 #include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -48,6 +53,7 @@ int main(int argc, char** argv) {
   const int threads = argc > 3 ? std::atoi(argv[3]) : 16, requests = argc > 4 ? std::atoi(argv[4]) : 64;
   const double min_s = argc > 5 ? std::atof(argv[5]) : 3.0, max_s = argc > 6 ? std::atof(argv[6]) : 12.0;
   const int model_thread_num = argc > 7 ? std::atoi(argv[7]) : 1;
+  const std::string hotword_file = argc > 8 ? argv[8] : "";
   FUNASR_HANDLE h = FunOfflineInit(paths, model_thread_num, true, 32);
   pfhip_model* am = FunOfflineGetAsrHandle(h);
   // synthetic s16 requests: a tone + noise, distinct pitch / length / noise per request
@@ -67,8 +73,18 @@ int main(int argc, char** argv) {
     }
   }
   const std::vector<std::vector<float>> no_hw;
+  std::vector<std::vector<std::vector<float>>> hw_lists;      // per-connection hotword lists, compiled
+  if (!hotword_file.empty()) {
+    if (!pfhip_is_contextual(am)) { std::fprintf(stderr, "hotword lists need a contextual model\n"); return 2; }
+    std::ifstream f(hotword_file);
+    for (std::string line; std::getline(f, line);)
+      if (!line.empty()) hw_lists.push_back(CompileHotwordEmbedding(h, line));
+    if (hw_lists.empty()) { std::fprintf(stderr, "no hotword list in %s\n", hotword_file.c_str()); return 2; }
+  }
+  const int hotword_lists = (int)hw_lists.size();
   auto infer = [&](int r, std::string& text, std::string& stamp, std::vector<int>& all_ids) {
-    FUNASR_RESULT q = FunOfflineInferBuffer(h, req[r].data(), (int)req[r].size(), RASR_NONE, nullptr, no_hw, 16000, "pcm");
+    const std::vector<std::vector<float>>& hw = hw_lists.empty() ? no_hw : hw_lists[(size_t)r % hw_lists.size()];
+    FUNASR_RESULT q = FunOfflineInferBuffer(h, req[r].data(), (int)req[r].size(), RASR_NONE, nullptr, hw, 16000, "pcm");
     if (!q) return false;
     text = FunASRGetResult(q, 0);
     stamp = FunASRGetStamp(q);
@@ -129,12 +145,18 @@ int main(int argc, char** argv) {
   const Totals b = read_stats(am);
   size_t tokens = 0;
   for (const std::vector<int>& v : want_ids) tokens += v.size();
+  pfhip_hwbank_stats hb{};
+  (void)pfhip_hotword_bank_stats(am, &hb);
   std::printf("{\"decoder_threads\": %d, \"model_thread_num\": %d, \"requests\": %d, \"audio_s\": %.1f, \"inflight\": %d, \"slots\": %d, "
               "\"slots_used\": %d, \"separate\": {\"forwards\": %lld, \"calls\": %lld, \"utterances\": %lld, \"wall_s\": %.4f}, "
               "\"concurrent\": {\"forwards\": %lld, \"calls\": %lld, \"utterances\": %lld, \"wall_s\": %.4f}, "
-              "\"mismatches\": %d, \"near_tie_flips\": %d, \"failures\": %d, \"id_chars\": %zu}\n",
+              "\"mismatches\": %d, \"near_tie_flips\": %d, \"failures\": %d, \"id_chars\": %zu, \"hotword_lists\": %d, "
+              "\"bank\": {\"hits\": %lld, \"misses\": %lld, \"evictions\": %lld, \"bytes_in_use\": %lld, \"forwards\": %lld, "
+              "\"sets_in_forwards\": %lld, \"max_sets_in_forward\": %lld}}\n",
               threads, model_thread_num, requests, audio_s, pfhip_get_inflight(am), b.slots, b.used, a.forwards - z.forwards, a.calls - z.calls, a.utts - z.utts, dt_seq,
-              b.forwards - a.forwards, b.calls - a.calls, b.utts - a.utts, dt_par, mismatches.load(), flips.load(), failures.load(), tokens);
+              b.forwards - a.forwards, b.calls - a.calls, b.utts - a.utts, dt_par, mismatches.load(), flips.load(), failures.load(), tokens, hotword_lists,
+              (long long)hb.hits, (long long)hb.misses, (long long)hb.evictions, (long long)hb.bytes_in_use, (long long)hb.forwards,
+              (long long)hb.sets_in_forwards, (long long)hb.max_sets_in_forward);
   FunOfflineUninit(h);
   return mismatches.load() || failures.load() ? 3 : 0;
 }

@@ -18,6 +18,7 @@
 
 #include "../../include/pfhip.h"
 #include "kernels.h"
+#include "hotword_bank.h"
 #include "merge_queue.h"
 
 namespace pfhip_detail {
@@ -136,6 +137,22 @@ using pfhip_detail::Tensor;
 struct BatchReq;
 struct StreamReq;
 
+namespace pfhip_detail {
+// The hotword bank of one device (on the weight owner; its contexts share it as they share the weights): the bias decoder's
+// projected K/V rows [rows][2d] of many hotword sets in one arena, addressed by row offset, so that one attention launch takes one
+// K base and one V base plus per-utterance offsets / counts.  hotword_bank.h keeps the books; `mu` covers them AND the enqueue of a
+// miss's upload + projection + ready event, so that whoever finds the entry afterwards finds its event recorded.
+struct HwBankDev {
+  std::mutex mu;
+  HotwordBank bank;
+  float* arena = nullptr;
+  bool configured = false;
+  int64_t bound_bytes = -1;           // -1: PFHIP_HOTWORD_BANK_MB (default 64) at first use
+  int default_id = -1;                // the entry of the pfhip_set_hotwords set, pinned for as long as it is the default
+  int64_t forwards = 0, sets_total = 0, sets_max = 0, percall_forwards = 0;
+};
+}  // namespace pfhip_detail
+
 struct pfhip_model {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -215,7 +232,12 @@ struct pfhip_model {
   bool ts_persistent = false;              // the last timestamp head ran the persistent kernel: its error word is read with the results
   int blstm_fallbacks = 0;         // timestamp requests served by the per-step recurrence after a barrier time-out
   float out2_b = 0.f;
-  int n_hw = 0;                  // hotword embeddings resident in `hw` ([n_hw, d])
+  // hotwords of the forward being run (resolve_hotwords_locked): per utterance the first row and the row count of its set's
+  // K/V rows under fw_hwkv — the device's bank arena, or this context's `hwkv` when a set did not fit the bank — and the bank
+  // entries this forward has pinned
+  std::vector<int> fw_hw_off, fw_hw_len, fw_pins;
+  const float* fw_hwkv = nullptr;
+  std::unique_ptr<pfhip_detail::HwBankDev> hwbank{new pfhip_detail::HwBankDev};      // on the weight owner
   void* h_meta = nullptr; size_t h_meta_cap = 0;     // pinned
   int* h_counts = nullptr;                            // pinned [2*B]
   size_t h_counts_cap = 0;
@@ -264,7 +286,10 @@ struct pfhip_model {
   int ctx_index = 0;
   int ctx_limit = 1;                        // on the head: contexts per device that take calls (pfhip_set_inflight)
   std::vector<pfhip_model*> slots;          // on the head: every execution slot of the handle, device-major round order; guarded by bq.mu
-  std::vector<float> hw_host;               // on the head: the resident hotword set (pfhip_set_hotwords), for contexts created later
+  // on the head: the default hotword set (pfhip_set_hotwords) of calls that bring none (pfhip_offline_enqueue,
+  // pfhip_offline_forward_resident); guarded by bq.mu
+  std::shared_ptr<const std::vector<float>> hw_default;
+  bool hw_merge = false;                    // on the head: contextual callers join the merge queue (pfhip_set_hotword_merging)
 
   // per weight matrix (device pointer of its first element): the power-of-two scale the fp16 two-plane GEMM stages it with
   // (kernels.h best_w_scale), fixed at load from its largest magnitude; contexts copy the table

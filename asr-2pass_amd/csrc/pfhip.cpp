@@ -855,8 +855,11 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   }
   m->ML = ML;
   if (ML == 0) { HIP_TRY(hipGetLastError()); return PFHIP_OK; }
-  if (c.contextual && m->n_hw <= 0)       // the reference logs "hw_emb is null" and returns empty results (paraformer.cpp:516-520)
-    return fail(PFHIP_ERR_ARG, "contextual model needs hotword embeddings (pfhip_set_hotwords / hw_emb)");
+  if (c.contextual) {       // the reference logs "hw_emb is null" and returns empty results (paraformer.cpp:516-520)
+    bool have = m->fw_hwkv != nullptr && (int)m->fw_hw_len.size() == B;
+    for (int b = 0; have && b < B; ++b) have = m->fw_hw_len[b] > 0;
+    if (!have) return fail(PFHIP_ERR_ARG, "contextual model needs hotword embeddings (pfhip_set_hotwords / hw_emb)");
+  }
   const int MLp = round_up(ML, pfhip::kTileM);
 
   // ---- decoder-side metadata + workspace -------------------------------------------------------------
@@ -869,7 +872,9 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
     int* dm = m->dmeta.i();
     std::memcpy(hm, m->tok_off.data(), 4 * B); m->m_tok_off = dm;
     std::memcpy(hm + B, m->n_fires.data(), 4 * B); m->m_tok_len = dm + B;
-    for (int b = 0; b < B; ++b) { hm[2 * B + b] = 0; hm[3 * B + b] = m->n_hw; }      // every utterance sees the same hotwords
+    // every utterance attends to its own hotword set: first row and row count of the set's K/V rows (resolve_hotwords_locked);
+    // utterances that share a set share an offset
+    for (int b = 0; b < B; ++b) { hm[2 * B + b] = c.contextual ? m->fw_hw_off[b] : 0; hm[3 * B + b] = c.contextual ? m->fw_hw_len[b] : 0; }
     m->m_hw_off = dm + 2 * B; m->m_hw_len = dm + 3 * B;
     m->m_src_row = dm + 4 * B;
     for (int b = 0; b < B; ++b)
@@ -1064,11 +1069,13 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
     gemm(m, s, m->ctxd.f(), d, m->W(p + "out.w").d, d, d, d, cat, 2 * d, m->W(p + "out.b").d, nullptr, 0, nullptr, 0, ML, false);
     lnorm(m, s, xd, d, m->yd.f(), d, "bias.dec.norm3", ML, d, d);
     gemm(m, s, m->yd.f(), d, m->W("bias.dec.q.w").d, d, d, d, m->qd.f(), d, m->W("bias.dec.q.b").d, nullptr, 0, nullptr, 0, ML, false);
-    // the hotword K/V projection lives in its own buffer, sized by the hotword count and filled once per hotword set
-    // (set_hotwords_locked) — the audio-side kv workspace only holds Mp rows
-    const float* hwkv = m->hwkv.f();
+    // the hotword K/V projections live in the device's hotword bank, filled once per hotword set and kept across calls
+    // (resolve_hotwords_locked) — the audio-side kv workspace only holds Mp rows
+    const float* hwkv = m->fw_hwkv;
     {
-      Scope sc(m, s, K_ATTN, 4.0 * ML * (double)m->n_hw * d, 8.0 * ML * d);
+      double hw_pairs = 0;
+      for (int b = 0; b < B; ++b) hw_pairs += (double)m->n_fires[b] * m->fw_hw_len[b];
+      Scope sc(m, s, K_ATTN, 4.0 * hw_pairs * d, 8.0 * ML * d);
       pfhip::launch_attention(m->qd.f(), d, hwkv, 2 * d, hwkv + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len,
                               m->m_hw_off, m->m_hw_len, B, c.n_head, m->maxL, att_scale, s);
     }
@@ -1307,19 +1314,187 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s) {
   return PFHIP_OK;
 }
 
-pfhip_status set_hotwords_locked(pfhip_model* m, const float* hw_emb, int H, hipStream_t s) {
+// ---- hotword bank (internal.h HwBankDev, hotword_bank.h) ----------------------------------------------------------------
+pfhip_model* bank_owner(pfhip_model* m) { return m->weights_of ? m->weights_of : m; }
+
+// sizes the arena at first use; the bank mutex is held
+void ensure_bank_locked(pfhip_model* owner) {
+  HwBankDev& D = *owner->hwbank;
+  if (D.configured) return;
+  if (D.bound_bytes < 0) {
+    const char* e = getenv("PFHIP_HOTWORD_BANK_MB");
+    const long mb = e && *e ? atol(e) : 64;
+    D.bound_bytes = (int64_t)std::max(0L, mb) << 20;
+  }
+  // Slabs are whole GEMM row tiles: the projection of an H-row set may write round_up(H, kTileM) rows (gemm pads M to the tile),
+  // all of them inside the set's own slab; the attention kernels clamp their key rows to the segment they are given
+  const int d = owner->cfg.d_model;
+  const int64_t gran_bytes = (int64_t)pfhip::kTileM * 2 * d * 4;
+  int granules = (int)std::min<int64_t>(D.bound_bytes / gran_bytes, INT32_MAX / pfhip::kTileM);
+  if (granules > 0 && hipMalloc((void**)&D.arena, (size_t)granules * gran_bytes) != hipSuccess) {
+    (void)hipGetLastError();          // no room for the arena: every set is served from the per-call buffers
+    D.arena = nullptr;
+    granules = 0;
+  }
+  D.bank.configure(pfhip::kTileM, d, granules);
+  D.default_id = -1;
+  D.configured = true;
+}
+
+// K/V projection of the bias decoder's cross-attention for one hotword set: [H, d] host rows -> staging rows of `m->hw` ->
+// dst [round_up(H, 128), 2d].  Enqueued on `s`, nothing waits.
+pfhip_status project_hotwords(pfhip_model* m, const float* host, int H, int stage_row, float* dst, hipStream_t s) {
   const int d = m->cfg.d_model;
-  if (!m->cfg.contextual) return fail(PFHIP_ERR_UNSUPPORTED, "model has no bias decoder (use_hotword == false)");
-  HIP_TRY(m->hw.ensure((size_t)round_up(H, pfhip::kTileM) * d * 4));
-  HIP_TRY(hipMemcpyAsync(m->hw.p, hw_emb, (size_t)H * d * 4, hipMemcpyHostToDevice, s));
-  // K/V projection of the bias decoder's cross-attention: constant per hotword set, [round_up(H,128), 2d]
-  HIP_TRY(m->hwkv.ensure((size_t)round_up(H, pfhip::kTileM) * 2 * d * 4));
-  gemm(m, s, m->hw.f(), d, m->W("bias.dec.kv.w").d, 2 * d, d, d, m->hwkv.f(), 2 * d, m->W("bias.dec.kv.b").d, nullptr, 0, nullptr, 0,
-       H, false);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s));
-  m->n_hw = H;
+  float* A = m->hw.f() + (size_t)stage_row * d;
+  HIP_TRY(hipMemcpyAsync(A, host, (size_t)H * d * 4, hipMemcpyHostToDevice, s));
+  gemm(m, s, A, d, m->W("bias.dec.kv.w").d, 2 * d, d, d, dst, 2 * d, m->W("bias.dec.kv.b").d, nullptr, 0, nullptr, 0, H, false);
   return PFHIP_OK;
+}
+
+// a bank miss: the entry's rows go up and are projected straight into its slab; the event tells other streams when.  Bank mutex held.
+pfhip_status fill_slab_locked(pfhip_model* m, HwBankDev& D, int id, int stage_row, hipStream_t s) {
+  HotwordBank::Entry& e = D.bank.entry(id);
+  pfhip_status st = project_hotwords(m, e.host.data(), e.H, stage_row, D.arena + (size_t)D.bank.row_off(id) * 2 * m->cfg.d_model, s);
+  if (st) return st;
+  if (!e.ready) {
+    hipEvent_t ev;
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    e.ready = ev;
+  }
+  HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(e.ready), s));
+  e.ready_on = s;
+  return PFHIP_OK;
+}
+
+void release_hotwords(pfhip_model* m) {
+  if (m->fw_pins.empty()) return;
+  HwBankDev& D = *bank_owner(m)->hwbank;
+  std::lock_guard<std::mutex> l(D.mu);
+  for (int id : m->fw_pins) D.bank.release(id);
+  m->fw_pins.clear();
+}
+struct HotwordPins {          // a forward's pins end with it, whichever way it ends (after its last synchronise)
+  pfhip_model* m;
+  ~HotwordPins() { release_hotwords(m); }
+};
+
+// Before a contextual forward: every utterance gets the first row and the row count of ITS hotword set (set_of_utt, nullptr = all
+// set 0).  Sets the device's bank holds are found by content and cost nothing; missing ones are uploaded and projected into
+// their slabs on `s` — all of a call's misses through one staging buffer, no synchronise.  The entries stay pinned until
+// release_hotwords.  A call with a set the bank cannot take (larger than its bound, or no room beside pinned slabs) projects
+// its sets into this context's own buffers, as every call did before the bank.
+pfhip_status resolve_hotwords_locked(pfhip_model* m, const float* const* emb, const int* H, int n_sets, const int* set_of_utt, int B,
+                                     hipStream_t s) {
+  m->fw_hw_off.assign((size_t)B, 0);
+  m->fw_hw_len.assign((size_t)B, 0);
+  m->fw_hwkv = nullptr;
+  if (!m->cfg.contextual) return PFHIP_OK;          // plain models ignore hw_emb (paraformer.cpp:515: use_hotword == false)
+  if (n_sets <= 0 || !emb || !H) return fail(PFHIP_ERR_ARG, "hw_emb is null");          // paraformer.cpp:516-520
+  std::vector<char> used((size_t)n_sets, 0);
+  for (int b = 0; b < B; ++b) {
+    const int k = set_of_utt ? set_of_utt[b] : 0;
+    if (k < 0 || k >= n_sets) return fail(PFHIP_ERR_ARG, "set_of_utt names no hotword set");
+    used[(size_t)k] = 1;
+  }
+  for (int k = 0; k < n_sets; ++k)
+    if (used[(size_t)k] && (!emb[k] || H[k] <= 0)) return fail(PFHIP_ERR_ARG, "hw_emb is null");
+  const int d = m->cfg.d_model;
+  HwBankDev& D = *bank_owner(m)->hwbank;
+  std::vector<int> row((size_t)n_sets, 0);
+  bool per_call = false;
+  {
+    std::lock_guard<std::mutex> l(D.mu);
+    ensure_bank_locked(bank_owner(m));
+    std::vector<int> ids((size_t)n_sets, -1), stage((size_t)n_sets, -1);
+    int stage_rows = 0;
+    for (int k = 0; k < n_sets && !per_call; ++k) {
+      if (!used[(size_t)k]) continue;
+      bool hit = false;
+      ids[(size_t)k] = D.bank.acquire(emb[k], H[k], &hit);
+      if (ids[(size_t)k] < 0) { per_call = true; break; }
+      m->fw_pins.push_back(ids[(size_t)k]);
+      if (!hit) { stage[(size_t)k] = stage_rows; stage_rows += round_up(H[k], pfhip::kTileM); }
+    }
+    if (per_call) {
+      // the hits are let go; a set that was just entered keeps its pin and has its slab filled below, for whoever finds it later
+      m->fw_pins.clear();
+      for (size_t k = 0; k < ids.size(); ++k) {
+        if (ids[k] < 0) continue;
+        if (stage[k] >= 0) m->fw_pins.push_back(ids[k]);
+        else D.bank.release(ids[k]);
+      }
+    }
+    // an upload that fails leaves no entry behind that claims rows it does not hold
+    auto give_up = [&](int from_k, pfhip_status st) {
+      for (int k = from_k; k < n_sets; ++k)
+        if (stage[(size_t)k] >= 0) {
+          m->fw_pins.erase(std::find(m->fw_pins.begin(), m->fw_pins.end(), ids[(size_t)k]));
+          D.bank.discard(ids[(size_t)k]);
+        }
+      return st;
+    };
+    if (stage_rows && m->hw.ensure((size_t)stage_rows * d * 4) != hipSuccess)
+      return give_up(0, fail(PFHIP_ERR_HIP, "hipMalloc of the hotword staging buffer failed"));
+    std::vector<int> distinct;
+    for (int k = 0; k < n_sets; ++k) {
+      if (ids[(size_t)k] < 0) continue;
+      const int id = ids[(size_t)k];
+      HotwordBank::Entry& e = D.bank.entry(id);
+      if (stage[(size_t)k] >= 0) {
+        const pfhip_status st = fill_slab_locked(m, D, id, stage[(size_t)k], s);
+        if (st) return give_up(k, st);
+      } else if (!per_call && !e.settled && e.ready && e.ready_on != s) {
+        HIP_TRY(hipStreamWaitEvent(s, static_cast<hipEvent_t>(e.ready), 0));      // filled on another context's stream
+      }
+      row[(size_t)k] = D.bank.row_off(id);
+      if (std::find(distinct.begin(), distinct.end(), id) == distinct.end()) distinct.push_back(id);
+    }
+    if (!per_call) {
+      ++D.forwards;
+      D.sets_total += (int64_t)distinct.size();
+      D.sets_max = std::max<int64_t>(D.sets_max, (int64_t)distinct.size());
+      m->fw_hwkv = D.arena;
+    }
+  }
+  if (per_call) {
+    int rows = 0, n_used = 0;
+    for (int k = 0; k < n_sets; ++k)
+      if (used[(size_t)k]) { row[(size_t)k] = rows; rows += round_up(H[k], pfhip::kTileM); ++n_used; }
+    HIP_TRY(m->hw.ensure((size_t)rows * d * 4));
+    HIP_TRY(m->hwkv.ensure((size_t)rows * 2 * d * 4));
+    for (int k = 0; k < n_sets; ++k) {
+      if (!used[(size_t)k]) continue;
+      const pfhip_status st = project_hotwords(m, emb[k], H[k], row[(size_t)k], m->hwkv.f() + (size_t)row[(size_t)k] * 2 * d, s);
+      if (st) return st;
+    }
+    m->fw_hwkv = m->hwkv.f();
+    std::lock_guard<std::mutex> l(D.mu);
+    ++D.forwards; ++D.percall_forwards;
+    D.sets_total += n_used;
+    D.sets_max = std::max<int64_t>(D.sets_max, n_used);
+  }
+  for (int b = 0; b < B; ++b) {
+    const int k = set_of_utt ? set_of_utt[b] : 0;
+    m->fw_hw_off[(size_t)b] = row[(size_t)k];
+    m->fw_hw_len[(size_t)b] = H[k];
+  }
+  HIP_TRY(hipGetLastError());
+  return PFHIP_OK;
+}
+
+// the default set (pfhip_set_hotwords) for calls that bring none
+std::shared_ptr<const std::vector<float>> default_hotwords(pfhip_model* m) {
+  pfhip_model* head = m->group_head ? m->group_head : m;
+  std::lock_guard<std::mutex> l(head->bq.mu);
+  return head->hw_default;
+}
+pfhip_status resolve_default_hotwords_locked(pfhip_model* m, int B, hipStream_t s) {
+  if (!m->cfg.contextual) return resolve_hotwords_locked(m, nullptr, nullptr, 0, nullptr, B, s);
+  const std::shared_ptr<const std::vector<float>> hw = default_hotwords(m);
+  if (!hw || hw->empty()) return fail(PFHIP_ERR_ARG, "hw_emb is null");
+  const float* e = hw->data();
+  const int H = (int)(hw->size() / (size_t)m->cfg.d_model);
+  return resolve_hotwords_locked(m, &e, &H, 1, nullptr, B, s);
 }
 
 pfhip_status stage_pcm(pfhip_model* m, const float* const* pcm, const int* n_samples, int B, hipStream_t s,
@@ -1488,6 +1663,12 @@ void pfhip_destroy(pfhip_model* m) {
                  &m->logits, &m->logp, &m->ids, &m->dmeta, &m->cat, &m->hw, &m->hwkv, &m->ts_up, &m->ts_gx, &m->ts_y, &m->ts_hx, &m->ts_a2,
                  &m->ts_alphas, &m->ts_peaks, &m->ts_meta, &m->sseg, &m->rs_in, &m->fbk, &m->d_ops, &m->kvall, &m->lnstats, &m->lnstats2, &m->kvside, &m->ts_cst, &m->ctxP, &m->xP, &m->hP, &m->encP, &m->xdP, &m->kvP})
     b->release();
+  if (m->hwbank) {               // the device's hotword bank (unused on a context)
+    HwBankDev& D = *m->hwbank;
+    for (size_t i = 0; i < D.bank.id_count(); ++i)
+      if (D.bank.entry((int)i).ready) (void)hipEventDestroy(static_cast<hipEvent_t>(D.bank.entry((int)i).ready));
+    if (D.arena) (void)hipFree(D.arena);
+  }
   if (!m->weights_of) {          // a context borrows these
 #define X(f) if (m->f) (void)hipFree((void*)m->f);
     PFHIP_WEIGHT_PTRS(X)
@@ -1521,7 +1702,12 @@ pfhip_status pfhip_offline_enqueue(pfhip_model* m, const float* d_pcm, const int
   std::lock_guard<std::mutex> lk(m->mu);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->own_stream;
   m->prof_stream = s;
-  pfhip_status st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
+  HIP_TRY(hipSetDevice(m->device));
+  // the default hotword set: its bank entry stays pinned for as long as it is the default, so this forward's own pins can go at once
+  HotwordPins pins{m};
+  pfhip_status st = resolve_default_hotwords_locked(m, batch, s);
+  if (st) return st;
+  st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
   if (st) return st;
   return head_locked(m, s, false);
 }
@@ -1535,15 +1721,18 @@ pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out) {
 }
 
 // fs_in: the rate of `pcm` when it is not the model's (resampled into the slot's PCM workspace first), else 0
+// hotword sets of a call: n_sets sets (emb[k]: [n[k], d]) and, per utterance, which one it attends to (of_utt == nullptr: all set 0)
+struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
+
 static pfhip_status forward_direct(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch,
-                                   const float* hw_emb, int n_hotwords, pfhip_out* out, int fs_in = 0) {
+                                   const HwSets& hw, pfhip_out* out, int fs_in = 0) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
   m->prof_stream = s;
-  if (m->cfg.contextual) {          // plain models ignore hw_emb (paraformer.cpp:515: use_hotword == false)
-    if (!hw_emb || n_hotwords <= 0) return fail(PFHIP_ERR_ARG, "hw_emb is null");          // paraformer.cpp:516-520
-    pfhip_status hs = set_hotwords_locked(m, hw_emb, n_hotwords, s);
+  HotwordPins pins{m};              // held until the results (a range-guard re-run included) are back
+  {
+    const pfhip_status hs = resolve_hotwords_locked(m, hw.emb, hw.n, hw.n_sets, hw.of_utt, batch, s);
     if (hs) return hs;
   }
   std::vector<int64_t> off;
@@ -1608,13 +1797,38 @@ static void release_slot(pfhip_model* head, pfhip_model* slot) {
 // the same sums in another order, 1e-6 apart in the log-probabilities).
 struct BatchReq : pfhip_detail::MergeReqBase {
   const float* const* pcm; const int* n; int batch; pfhip_out* out;
+  HwSets hw{nullptr, nullptr, 0, nullptr};          // the caller's hotword sets (contextual models)
   pfhip_status st = PFHIP_OK; std::string err;
 };
 
 // one packed forward on `m` for everybody in `take`
-static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& take) {
+static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
   std::vector<const float*> ptrs; std::vector<int> lens;
   bool want_logp = false, want_us = false; int max_tok = 1, utts = 0;
+  // Contextual model: the callers' hotword sets, deduplicated (one connection sends the same list with each of its segments; the
+  // bank then matches by content), and for every packed utterance the index of its set.  A caller without hotwords fails alone
+  // with the reference's "hw_emb is null" (paraformer.cpp:516-520); its company is served.
+  std::vector<BatchReq*> take;
+  std::vector<const float*> set_emb; std::vector<int> set_n, set_of;
+  for (BatchReq* r : all_taken) {
+    if (m->cfg.contextual) {
+      bool ok = r->hw.n_sets > 0 && r->hw.emb && r->hw.n;
+      for (int i = 0; ok && i < r->batch; ++i) {
+        const int k = r->hw.of_utt ? r->hw.of_utt[i] : 0;
+        ok = k >= 0 && k < r->hw.n_sets && r->hw.emb[k] && r->hw.n[k] > 0;
+      }
+      if (!ok) { r->st = PFHIP_ERR_ARG; r->err = "hw_emb is null"; continue; }
+      for (int i = 0; i < r->batch; ++i) {
+        const int k = r->hw.of_utt ? r->hw.of_utt[i] : 0;
+        size_t j = 0;
+        while (j < set_emb.size() && !(set_emb[j] == r->hw.emb[k] && set_n[j] == r->hw.n[k])) ++j;
+        if (j == set_emb.size()) { set_emb.push_back(r->hw.emb[k]); set_n.push_back(r->hw.n[k]); }
+        set_of.push_back((int)j);
+      }
+    }
+    take.push_back(r);
+  }
+  if (take.empty()) return;
   for (BatchReq* r : take) {
     for (int i = 0; i < r->batch; ++i) { ptrs.push_back(r->pcm[i]); lens.push_back(r->n[i]); max_tok = std::max(max_tok, r->n[i] / 960 + 2); }
     want_logp = want_logp || r->out->logp != nullptr;
@@ -1632,7 +1846,8 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& tak
     usa.resize((size_t)utts * max_us); usp.resize((size_t)utts * max_us); usl.resize(utts);
     all.us_alphas = usa.data(); all.us_peaks = usp.data(); all.us_len = usl.data(); all.max_us = max_us;
   }
-  pfhip_status st = forward_direct(m, ptrs.data(), lens.data(), utts, nullptr, 0, &all);
+  const HwSets sets{set_emb.data(), set_n.data(), (int)set_emb.size(), set_of.data()};
+  pfhip_status st = forward_direct(m, ptrs.data(), lens.data(), utts, sets, &all);
   const std::string err = g_err;
   int u0 = 0;
   for (BatchReq* r : take) {
@@ -1662,9 +1877,9 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& tak
 namespace { thread_local pfhip_model* tl_last_replica = nullptr; }      // where this thread's last offline forward ran (debug getters)
 
 static pfhip_status forward_batched(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
-                                    pfhip_out* out) {
+                                    const HwSets& hw, pfhip_out* out) {
   BatchReq me;
-  me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out;
+  me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out; me.hw = hw;
   int wait_us, max_utts;
   { std::lock_guard<std::mutex> l(head->bq.mu); wait_us = head->batch_wait_us; max_utts = head->batch_max_utts; }
   pfhip_model* ran_on = nullptr;
@@ -1700,22 +1915,44 @@ static pfhip_status forward_batched(pfhip_model* head, const float* const* pcm, 
   return me.st;
 }
 
-pfhip_status pfhip_offline_forward(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
-                                   const float* hw_emb, int n_hotwords, pfhip_out* out) {
+static pfhip_status offline_forward_sets(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, const HwSets& hw,
+                                         pfhip_out* out) {
   g_err.clear();
   if (!head || !pcm || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
   for (int i = 0; i < batch; ++i)
     if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
-  // merged with whoever else is calling (plain and timestamp models; hotwords are per connection, so contextual calls are not)
+  // merged with whoever else is calling: plain and timestamp models always; contextual models — every caller with its own hotword
+  // sets, each utterance attending to its own set in the packed forward — where pfhip_set_hotword_merging is on
   bool merge;
-  { std::lock_guard<std::mutex> l(head->bq.mu); merge = head->batch_wait_us > 0 && batch < head->batch_max_utts; }
-  if (merge && !head->cfg.contextual) return forward_batched(head, pcm, n_samples, batch, out);
+  {
+    std::lock_guard<std::mutex> l(head->bq.mu);
+    merge = head->batch_wait_us > 0 && batch < head->batch_max_utts && (!head->cfg.contextual || head->hw_merge);
+  }
+  if (merge) return forward_batched(head, pcm, n_samples, batch, hw, out);
   pfhip_model* m = acquire_slot(head);                  // the least-loaded execution slot (context / GPU)
   tl_last_replica = m;
-  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw_emb, n_hotwords, out);
+  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out);
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
   return st;
+}
+
+pfhip_status pfhip_offline_forward(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
+                                   const float* hw_emb, int n_hotwords, pfhip_out* out) {
+  // one set for all: the one-set case of pfhip_offline_forward_hwsets
+  const HwSets hw{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
+  return offline_forward_sets(head, pcm, n_samples, batch, hw, out);
+}
+
+pfhip_status pfhip_offline_forward_hwsets(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
+                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                          pfhip_out* out) {
+  if (head && head->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
+    g_err.clear();
+    return fail(PFHIP_ERR_ARG, "bad argument");
+  }
+  const HwSets hw{hw_emb, n_hotwords, n_sets < 0 ? 0 : n_sets, set_of_utt};
+  return offline_forward_sets(head, pcm, n_samples, batch, hw, out);
 }
 
 // pfhip_offline_forward with the PCM already in HBM: same routing over the execution slots, no H2D of the audio
@@ -1723,7 +1960,7 @@ pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pc
                                             int batch, pfhip_out* out) {
   g_err.clear();
   if (!head || !d_pcm || !sample_off || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (head->cfg.contextual && head->n_hw <= 0) return fail(PFHIP_ERR_ARG, "hw_emb is null");
+  if (head->cfg.contextual && !default_hotwords(head)) return fail(PFHIP_ERR_ARG, "hw_emb is null");
   pfhip_model* m = acquire_slot(head);
   tl_last_replica = m;
   pfhip_status st;
@@ -1731,7 +1968,10 @@ pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pc
     std::lock_guard<std::mutex> lk(m->mu);
     hipStream_t s = m->own_stream;
     m->prof_stream = s;
-    st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
+    HotwordPins pins{m};
+    st = hipSetDevice(m->device) == hipSuccess ? PFHIP_OK : fail(PFHIP_ERR_HIP, "hipSetDevice");
+    if (!st) st = resolve_default_hotwords_locked(m, batch, s);
+    if (!st) st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
     if (!st) st = head_locked(m, s, out->logp != nullptr);
     if (!st) st = fetch_locked(m, out, s);
   }
@@ -1752,7 +1992,8 @@ pfhip_status pfhip_offline_forward_rate(pfhip_model* head, const float* const* p
   if (!pfhip_detail::resample_supported(sample_rate, head->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
   pfhip_model* m = acquire_slot(head);                  // not merged with other callers: one rate pair per packed batch
   tl_last_replica = m;
-  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw_emb, n_hotwords, out, sample_rate);
+  const HwSets hw{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
+  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out, sample_rate);
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
   return st;
@@ -1822,8 +2063,6 @@ pfhip_status pfhip_set_inflight(pfhip_model* head, int n) {
   if (head->group_head || head->weights_of) return fail(PFHIP_ERR_ARG, "not the handle pfhip_create returned");
   std::vector<pfhip_model*> devs{head};
   for (pfhip_model* r : head->replicas) devs.push_back(r);
-  std::vector<float> hw;
-  { std::lock_guard<std::mutex> l(head->bq.mu); hw = head->hw_host; }
   for (pfhip_model* d : devs) {
     while ((int)d->contexts.size() + 1 < n) {
       pfhip_model* cx = nullptr;
@@ -1831,11 +2070,6 @@ pfhip_status pfhip_set_inflight(pfhip_model* head, int n) {
       if (st) return st;
       cx->group_head = head;
       cx->ctx_index = (int)d->contexts.size() + 1;
-      if (!hw.empty()) {
-        std::lock_guard<std::mutex> lk(cx->mu);
-        st = set_hotwords_locked(cx, hw.data(), (int)(hw.size() / (size_t)head->cfg.d_model), cx->own_stream);
-        if (st) { pfhip_destroy(cx); return st; }
-      }
       std::lock_guard<std::mutex> l(head->bq.mu);
       d->contexts.push_back(cx);
     }
@@ -1871,28 +2105,111 @@ pfhip_status pfhip_inflight_stats(pfhip_model* head, pfhip_slot_stats* out, int 
   return PFHIP_OK;
 }
 
+// The default set becomes (or stays) a pinned entry of the device's bank: filled on the owner's stream and waited for, the previous
+// default let go.  owner->mu is held.  A set the bank cannot take stays a host copy and is projected per call.
+static pfhip_status pin_default_hotwords(pfhip_model* owner, const float* hw_emb, int H) {
+  HIP_TRY(hipSetDevice(owner->device));
+  HIP_TRY(hipDeviceSynchronize());            // a forward enqueued with the previous default (pfhip_offline_enqueue) has finished
+  HwBankDev& D = *owner->hwbank;
+  std::lock_guard<std::mutex> l(D.mu);
+  ensure_bank_locked(owner);
+  const int old = D.default_id;
+  D.default_id = -1;
+  if (hw_emb && H > 0) {
+    bool hit = false;
+    const int id = D.bank.acquire(hw_emb, H, &hit);
+    if (id >= 0 && !hit) {
+      HIP_TRY(owner->hw.ensure((size_t)round_up(H, pfhip::kTileM) * owner->cfg.d_model * 4));
+      const pfhip_status st = fill_slab_locked(owner, D, id, 0, owner->own_stream);
+      if (st) return st;
+      HIP_TRY(hipStreamSynchronize(owner->own_stream));
+      D.bank.entry(id).settled = true;          // complete: nobody needs to wait for its event
+    }
+    D.default_id = id;
+  }
+  if (old >= 0) D.bank.release(old);
+  return PFHIP_OK;
+}
+
+static std::vector<pfhip_model*> device_owners(pfhip_model* head) {
+  std::lock_guard<std::mutex> l(head->bq.mu);
+  std::vector<pfhip_model*> devs{head};
+  for (pfhip_model* r : head->replicas) devs.push_back(r);
+  return devs;
+}
+
 pfhip_status pfhip_set_hotwords(pfhip_model* m, const float* hw_emb, int n_hotwords) {
   g_err.clear();
   if (!m || !hw_emb || n_hotwords <= 0) return fail(PFHIP_ERR_ARG, "bad argument");
-  // every context of every device, also those pfhip_set_inflight has taken off the slot list (they come back with a larger n)
-  std::vector<pfhip_model*> every;
-  {
-    std::lock_guard<std::mutex> l(m->bq.mu);
-    std::vector<pfhip_model*> devs{m};
-    for (pfhip_model* r : m->replicas) devs.push_back(r);
-    for (pfhip_model* d : devs) {
-      every.push_back(d);
-      for (pfhip_model* cx : d->contexts) every.push_back(cx);
-    }
-  }
-  for (pfhip_model* r : every) {
+  if (!m->cfg.contextual) return fail(PFHIP_ERR_UNSUPPORTED, "model has no bias decoder (use_hotword == false)");
+  if (m->group_head || m->weights_of) return fail(PFHIP_ERR_ARG, "not the handle pfhip_create returned");
+  for (pfhip_model* r : device_owners(m)) {          // one bank per device, shared by its contexts
     std::lock_guard<std::mutex> lk(r->mu);
-    HIP_TRY(hipSetDevice(r->device));
-    pfhip_status st = set_hotwords_locked(r, hw_emb, n_hotwords, r->own_stream);
+    const pfhip_status st = pin_default_hotwords(r, hw_emb, n_hotwords);
     if (st) return st;
   }
+  auto copy = std::make_shared<const std::vector<float>>(hw_emb, hw_emb + (size_t)n_hotwords * m->cfg.d_model);
   std::lock_guard<std::mutex> l(m->bq.mu);
-  m->hw_host.assign(hw_emb, hw_emb + (size_t)n_hotwords * m->cfg.d_model);
+  m->hw_default = std::move(copy);
+  return PFHIP_OK;
+}
+
+pfhip_status pfhip_set_hotword_merging(pfhip_model* m, int on) {
+  g_err.clear();
+  if (!m) return fail(PFHIP_ERR_ARG, "null model");
+  std::lock_guard<std::mutex> l(m->bq.mu);
+  m->hw_merge = on != 0;
+  return PFHIP_OK;
+}
+
+pfhip_status pfhip_set_hotword_bank_bytes(pfhip_model* m, int64_t bytes) {
+  g_err.clear();
+  if (!m || bytes < 0) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (m->group_head || m->weights_of) return fail(PFHIP_ERR_ARG, "not the handle pfhip_create returned");
+  const std::shared_ptr<const std::vector<float>> def = default_hotwords(m);
+  for (pfhip_model* r : device_owners(m)) {
+    std::lock_guard<std::mutex> lk(r->mu);
+    HIP_TRY(hipSetDevice(r->device));
+    HwBankDev& D = *r->hwbank;
+    {
+      std::lock_guard<std::mutex> l(D.mu);
+      for (size_t i = 0; i < D.bank.id_count(); ++i) {
+        const HotwordBank::Entry& e = D.bank.entry((int)i);
+        if (e.live && e.pins > ((int)i == D.default_id ? 1 : 0))
+          return fail(PFHIP_ERR_ARG, "hotword bank in use: set its bound while no forward is in flight");
+      }
+      HIP_TRY(hipDeviceSynchronize());
+      if (D.arena) HIP_TRY(hipFree(D.arena));
+      D.arena = nullptr;
+      D.bound_bytes = bytes;
+      D.configured = false;
+      ensure_bank_locked(r);
+    }
+    if (def && !def->empty()) {
+      const pfhip_status st = pin_default_hotwords(r, def->data(), (int)(def->size() / (size_t)m->cfg.d_model));
+      if (st) return st;
+    }
+  }
+  return PFHIP_OK;
+}
+
+pfhip_status pfhip_hotword_bank_stats(pfhip_model* m, pfhip_hwbank_stats* out) {
+  g_err.clear();
+  if (!m || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  *out = pfhip_hwbank_stats{};
+  const int64_t row_bytes = (int64_t)2 * m->cfg.d_model * 4;
+  for (pfhip_model* r : device_owners(m)) {
+    HwBankDev& D = *r->hwbank;
+    std::lock_guard<std::mutex> l(D.mu);
+    out->hits += D.bank.hits; out->misses += D.bank.misses; out->evictions += D.bank.evictions;
+    out->refused += D.bank.refused;
+    out->bytes_in_use += (int64_t)D.bank.used_granules() * D.bank.granule_rows() * row_bytes;
+    out->bytes_capacity += (int64_t)D.bank.capacity_granules() * D.bank.granule_rows() * row_bytes;
+    out->sets_resident += D.bank.live_entries();
+    out->forwards += D.forwards; out->per_call_forwards += D.percall_forwards;
+    out->sets_in_forwards += D.sets_total;
+    out->max_sets_in_forward = std::max(out->max_sets_in_forward, D.sets_max);
+  }
   return PFHIP_OK;
 }
 
@@ -1916,7 +2233,9 @@ pfhip_status pfhip_warm_up(pfhip_model* m, int batch, int n_samples) {
   for (pfhip_model* r : all_slots(m)) {
     pfhip_out out{};
     out.token_ids = ids.data(); out.token_num = tn.data(); out.n_fires = nf.data(); out.n_frames = fr.data(); out.max_tokens = max_tok;
-    const pfhip_status st = forward_direct(r, ptrs.data(), lens.data(), batch, hw.empty() ? nullptr : hw.data(), hw.empty() ? 0 : 1, &out);
+    const float* hwp = hw.empty() ? nullptr : hw.data();
+    const int one = 1;
+    const pfhip_status st = forward_direct(r, ptrs.data(), lens.data(), batch, HwSets{&hwp, &one, hw.empty() ? 0 : 1, nullptr}, &out);
     if (st) return st;
   }
   return PFHIP_OK;

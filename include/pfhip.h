@@ -124,8 +124,8 @@ pfhip_status pfhip_offline_forward(pfhip_model* m, const float* const* pcm, cons
  * idle slot and runs the batch it gathered while the next caller already gathers the next one.  A caller that finds nothing in
  * flight runs at once (a lone caller never waits); while every slot is busy the gathering is free; only with an idle slot AND
  * other batches executing does a leader wait — at most wait_us — for company.  Results are identical to separate calls.
- * 0 switches it off (default).  Contextual models are not merged (hotwords are per connection); calls with at least
- * max_utterances utterances go straight to the least-loaded slot. */
+ * 0 switches it off (default).  Contextual models are merged where pfhip_set_hotword_merging is on (every caller keeps its own
+ * hotword sets in the packed forward); calls with at least max_utterances utterances go straight to the least-loaded slot. */
 pfhip_status pfhip_set_batching(pfhip_model* m, int wait_us, int max_utterances);
 
 /* Execution contexts: how many offline forwards of this handle may be in flight per device.  The reference shares ONE
@@ -187,7 +187,7 @@ pfhip_status pfhip_resample(pfhip_model* m, const float* const* pcm, const int* 
  * the device at its own rate and resampled there into the execution slot's PCM workspace, then the forward runs as
  * pfhip_offline_forward_resident does, without a host round trip.  Results are those of pfhip_offline_forward on the output of
  * pfhip_resample.  sample_rate == pfhip_sample_rate(m) is exactly pfhip_offline_forward.  Calls at another rate are not merged
- * with other callers (pfhip_set_batching; as for contextual models).  Hotwords and the timestamp outputs are as there. */
+ * with other callers (pfhip_set_batching).  Hotwords (through the bank, below) and the timestamp outputs are as there. */
 pfhip_status pfhip_offline_forward_rate(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
                                         const float* hw_emb, int n_hotwords, pfhip_out* out);
 
@@ -205,6 +205,39 @@ int pfhip_has_timestamp_head(const pfhip_model* m);
 pfhip_status pfhip_hotword_embed(pfhip_model* m, const int32_t* hotword_matrix, const int32_t* lengths, int n_hotwords,
                                  float* out);
 pfhip_status pfhip_set_hotwords(pfhip_model* m, const float* hw_emb, int n_hotwords);
+
+/* ---- per-utterance hotword sets, kept projected on the device ---------------------------------------
+ * Replaces the one `hw_emb` that Model::Forward hands to the session for the whole batch (paraformer.cpp:515-531) where callers
+ * with different lists share a batch: every websocket connection of the reference's server brings its own hotword list
+ * (websocket-server.cpp:316-359) to each Forward it makes.  n_sets sets (hw_emb[k]: [n_hotwords[k], d] floats) and, per utterance,
+ * the index of the set it attends to in the bias decoder (set_of_utt [batch]).  pfhip_offline_forward(..., hw_emb, n_hotwords, ...)
+ * is the one-set case.  A contextual model with no set for an utterance is "hw_emb is null" (:516-520); plain models ignore sets.
+ *
+ * The bias decoder's projected K/V rows of the sets (bias.dec.kv.*, [H, 2d]) are kept in a per-device bank shared by the
+ * execution contexts and found again by content (hash + byte compare): a set seen before costs no upload, no GEMM and no
+ * synchronise; missing sets are uploaded and projected on the forward's own stream.  The bank is bounded in bytes
+ * (pfhip_set_hotword_bank_bytes; default PFHIP_HOTWORD_BANK_MB = 64 per device), evicts least recently used sets, never one a
+ * forward in flight uses; a call with a set that cannot be banked projects its sets into per-call buffers.  Set the bound while
+ * no forward is in flight (PFHIP_ERR_ARG otherwise); 0 banks nothing.  The pfhip_set_hotwords set is a bank entry that stays. */
+pfhip_status pfhip_offline_forward_hwsets(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch,
+                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                          pfhip_out* out);
+pfhip_status pfhip_set_hotword_bank_bytes(pfhip_model* m, int64_t bytes);
+/* Contextual callers in the merge queue (pfhip_set_batching): on != 0 lets concurrent pfhip_offline_forward[_hwsets] callers of a
+ * contextual model share packed forwards, each utterance attending to its caller's set; a caller without hotwords fails alone.
+ * Off (default), every contextual call is a forward of its own, bit-identical to a lone call; merged, results are those of
+ * separate calls as far as pfhip_set_batching states it for plain models.  The C++ adapters switch it on
+ * (PFHIP_HOTWORD_MERGE=0 keeps it off). */
+pfhip_status pfhip_set_hotword_merging(pfhip_model* m, int on);
+/* Totals over the devices of the handle.  hits / misses / evictions: sets found resident, uploaded, dropped for room; refused:
+ * sets the bank could not take; forwards: contextual forwards, per_call_forwards of them from per-call buffers;
+ * sets_in_forwards / forwards = distinct sets per packed forward, max_sets_in_forward its maximum. */
+typedef struct {
+  int64_t hits, misses, evictions, refused;
+  int64_t bytes_in_use, bytes_capacity, sets_resident;
+  int64_t forwards, per_call_forwards, sets_in_forwards, max_sets_in_forward;
+} pfhip_hwbank_stats;
+pfhip_status pfhip_hotword_bank_stats(pfhip_model* m, pfhip_hwbank_stats* out);
 
 /* ---- front end only ----------------------------------------------------------------------------
  * Replaces Paraformer::FbankKaldi + LfrCmvn (paraformer.cpp:309-323, 421-461) on their own:
