@@ -26,7 +26,7 @@ KCLASS_NAMES = ["gemm", "attention", "layernorm", "fsmn", "fbank", "cif", "head"
 ABI_SYMBOLS = [
     "pfhip_last_error", "pfhip_create", "pfhip_create_from_memory", "pfhip_create_from_files", "pfhip_read_model_files", "pfhip_container_blob",
     "pfhip_container_manifest", "pfhip_container_from_cache", "pfhip_container_free", "pfhip_onnx_summary", "pfhip_vad_create_from_files", "pfhip_punc_create_from_files", "pfhip_create_group", "pfhip_group_size", "pfhip_group_stats", "pfhip_destroy",
-    "pfhip_sample_rate", "pfhip_vocab_size", "pfhip_feat_dim", "pfhip_d_model",
+    "pfhip_sample_rate", "pfhip_vocab_size", "pfhip_feat_dim", "pfhip_d_model", "pfhip_head_dim",
     "pfhip_offline_forward", "pfhip_offline_enqueue", "pfhip_offline_fetch", "pfhip_offline_forward_resident",
     "pfhip_resample_len", "pfhip_resample", "pfhip_offline_forward_rate",
     "pfhip_set_batching", "pfhip_set_inflight", "pfhip_warm_up", "pfhip_get_inflight", "pfhip_inflight_stats", "pfhip_is_contextual", "pfhip_has_timestamp_head", "pfhip_hotword_embed", "pfhip_set_hotwords",
@@ -114,7 +114,7 @@ def load_lib() -> ctypes.CDLL:
     lib.pfhip_create_group.argtypes = [vp, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ci), ci, ctypes.POINTER(vp)]
     lib.pfhip_group_size.argtypes = [vp]
     lib.pfhip_group_stats.argtypes = [vp, vp, vp, vp, vp, ci]
-    for f in ("pfhip_sample_rate", "pfhip_vocab_size", "pfhip_feat_dim", "pfhip_d_model"):
+    for f in ("pfhip_sample_rate", "pfhip_vocab_size", "pfhip_feat_dim", "pfhip_d_model", "pfhip_head_dim"):
         getattr(lib, f).argtypes = [vp]
     lib.pfhip_offline_forward.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, vp, ci, ctypes.POINTER(_Out)]
     lib.pfhip_offline_enqueue.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ci), ci, vp]

@@ -60,6 +60,9 @@ def config_from_yaml(y):
                noise_threshold=float(pred.get("noise_threshold", cfg["noise_threshold"])),
                n_mels=int(fe.get("n_mels", cfg["n_mels"])), lfr_m=int(fe.get("lfr_m", cfg["lfr_m"])),
                lfr_n=int(fe.get("lfr_n", cfg["lfr_n"])))
+    # the decoder's own head count, only where config.yaml states one that differs (decoder_conf.attention_heads)
+    if int(dec.get("attention_heads", cfg["n_head"])) != cfg["n_head"]:
+        cfg["dec_n_head"] = int(dec["attention_heads"])
     return cfg
 
 

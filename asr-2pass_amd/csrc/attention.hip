@@ -18,6 +18,7 @@
 #include "kernels.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 namespace pfhip {
@@ -29,7 +30,10 @@ constexpr int kQW = 32;            // query rows per wave
 constexpr int kQB = 128;           // query rows per block
 constexpr int kKT = 32;            // keys per tile
 
-// HD = head dimension: 128 (Paraformer SAN-M / cross-attention) or 32 (CT-Transformer, 256 / 8 heads)
+// HD = head dimension: 128 (Paraformer SAN-M / cross-attention), 80 (the small Paraformer: 320 / 4 heads) or 32 (CT-Transformer,
+// 256 / 8 heads).  80 is no multiple of the 32-wide tiles: the K/V tile is staged by 240 of the 256 threads (12 rows x 20 float4 per
+// pass, three passes), the output has two full d-tiles and one of 16 live rows (the V column of its dead lanes is clamped to the
+// head's last one and their accumulator rows are never stored), and a wave stores three 320-B rows per pass.
 template <int HD>
 __global__ __launch_bounds__(256, 2) void attention_kernel(
     const float* __restrict__ Q, int ldq, const float* __restrict__ K, int ldk,
@@ -41,10 +45,12 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
   constexpr int kKVBuf = kKT * kKS + kKT * HD;       // floats per (K,V) buffer
   constexpr int kLdsFloats = (2 * kKVBuf > 4 * kQW * kKS) ? 2 * kKVBuf : 4 * kQW * kKS;
   constexpr int NKB = HD / 8;                        // MFMA k-blocks of the QK^T product
-  constexpr int ND = HD / 32;                        // 32-wide d tiles of the output
-  constexpr int NP = HD / 32;                        // staging passes (256 threads move 1024 floats per pass)
+  constexpr int ND = (HD + 31) / 32;                 // 32-wide d tiles of the output (the last one partly live when HD % 32)
   constexpr int C4 = HD / 4;                         // float4 chunks per row
-  constexpr int RPP = 256 / C4;                      // rows per staging pass
+  constexpr int RPP = 256 / C4;                      // rows per staging pass (RPP * C4 of the 256 threads move a float4 each)
+  constexpr int NP = (kKT + RPP - 1) / RPP;          // staging passes
+  constexpr bool kRagged = (256 % C4) != 0 || (kKT % RPP) != 0;      // some (thread, pass) pairs have no row (HD = 80)
+  static_assert(HD % 8 == 0 && ND <= 4 && NP <= 4 && NKB >= 2 * NP, "staging / tiling slots");
   __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
 
   // grid = (head, utterance, query block): consecutive workgroups go to consecutive XCDs, so with the query block as the
@@ -82,7 +88,9 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
   //      arrays to scratch and waits for the loads right where they are issued) -------------------------
   const int lrow = tid / C4, lc4 = tid % C4;   // RPP rows x C4 float4 per pass, NP passes
   float4 rk0, rk1, rk2, rk3, rv0, rv1, rv2, rv3;
-  rk1 = rk2 = rk3 = rv1 = rv2 = rv3 = make_float4(0.f, 0.f, 0.f, 0.f);
+  rk0 = rv0 = rk1 = rk2 = rk3 = rv1 = rv2 = rv3 = make_float4(0.f, 0.f, 0.f, 0.f);
+  // whether this thread has a row in staging pass i
+#define PFHIP_STAGE_LIVE(i) (!kRagged || (lrow < RPP && lrow + RPP * (i) < kKT))
   const float* Kh = K + kbase * ldk + head * kHeadDim + 4 * lc4;
   const float* Vh = V + kbase * ldv + head * kHeadDim + 4 * lc4;
   // one row group (RPP keys) of the next K or V tile -> staging registers / staging registers -> LDS
@@ -90,18 +98,18 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
   do {                                                                                  \
     int key_ = (kt) * kKT + lrow + RPP * (i);                                           \
     key_ = key_ < Lk ? key_ : Lk - 1;                                                   \
-    RK = *reinterpret_cast<const float4*>(Kh + (size_t)key_ * ldk);                     \
+    if (PFHIP_STAGE_LIVE(i)) RK = *reinterpret_cast<const float4*>(Kh + (size_t)key_ * ldk); \
   } while (0)
 #define PFHIP_V_LOAD(RV, i, kt)                                                         \
   do {                                                                                  \
     int key_ = (kt) * kKT + lrow + RPP * (i);                                           \
     key_ = key_ < Lk ? key_ : Lk - 1;                                                   \
-    RV = *reinterpret_cast<const float4*>(Vh + (size_t)key_ * ldv);                     \
+    if (PFHIP_STAGE_LIVE(i)) RV = *reinterpret_cast<const float4*>(Vh + (size_t)key_ * ldv); \
   } while (0)
 #define PFHIP_K_STORE(RK, i, buf) \
-  *reinterpret_cast<float4*>(lds + (buf) * kKVBuf + (lrow + RPP * (i)) * kKS + 4 * lc4) = RK
+  do { if (PFHIP_STAGE_LIVE(i)) *reinterpret_cast<float4*>(lds + (buf) * kKVBuf + (lrow + RPP * (i)) * kKS + 4 * lc4) = RK; } while (0)
 #define PFHIP_V_STORE(RV, i, buf) \
-  *reinterpret_cast<float4*>(lds + (buf) * kKVBuf + kKT * kKS + (lrow + RPP * (i)) * kHeadDim + 4 * lc4) = RV
+  do { if (PFHIP_STAGE_LIVE(i)) *reinterpret_cast<float4*>(lds + (buf) * kKVBuf + kKT * kKS + (lrow + RPP * (i)) * kHeadDim + 4 * lc4) = RV; } while (0)
 
   f32x16 oacc0, oacc1, oacc2, oacc3;
 #pragma unroll
@@ -110,15 +118,13 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 
   const int nkt = (Lk + kKT - 1) / kKT;
   PFHIP_K_LOAD(rk0, 0, 0); PFHIP_V_LOAD(rv0, 0, 0);
-  if (NP > 1) {
-    PFHIP_K_LOAD(rk1, 1, 0); PFHIP_V_LOAD(rv1, 1, 0); PFHIP_K_LOAD(rk2, 2, 0); PFHIP_V_LOAD(rv2, 2, 0);
-    PFHIP_K_LOAD(rk3, 3, 0); PFHIP_V_LOAD(rv3, 3, 0);
-  }
+  if (NP > 1) { PFHIP_K_LOAD(rk1, 1, 0); PFHIP_V_LOAD(rv1, 1, 0); }
+  if (NP > 2) { PFHIP_K_LOAD(rk2, 2, 0); PFHIP_V_LOAD(rv2, 2, 0); }
+  if (NP > 3) { PFHIP_K_LOAD(rk3, 3, 0); PFHIP_V_LOAD(rv3, 3, 0); }
   PFHIP_K_STORE(rk0, 0, 0); PFHIP_V_STORE(rv0, 0, 0);
-  if (NP > 1) {
-    PFHIP_K_STORE(rk1, 1, 0); PFHIP_V_STORE(rv1, 1, 0); PFHIP_K_STORE(rk2, 2, 0); PFHIP_V_STORE(rv2, 2, 0);
-    PFHIP_K_STORE(rk3, 3, 0); PFHIP_V_STORE(rv3, 3, 0);
-  }
+  if (NP > 1) { PFHIP_K_STORE(rk1, 1, 0); PFHIP_V_STORE(rv1, 1, 0); }
+  if (NP > 2) { PFHIP_K_STORE(rk2, 2, 0); PFHIP_V_STORE(rv2, 2, 0); }
+  if (NP > 3) { PFHIP_K_STORE(rk3, 3, 0); PFHIP_V_STORE(rv3, 3, 0); }
   __syncthreads();
 
   // Memory instructions are issued singly between MFMA groups (the next tile's 2*NP global loads under the QK^T
@@ -145,8 +151,12 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
       if (NP > 1) {
         if (kb == 2) PFHIP_K_LOAD(rk1, 1, ktn);
         if (kb == 3) PFHIP_V_LOAD(rv1, 1, ktn);
+      }
+      if (NP > 2) {
         if (kb == 4) PFHIP_K_LOAD(rk2, 2, ktn);
         if (kb == 5) PFHIP_V_LOAD(rv2, 2, ktn);
+      }
+      if (NP > 3) {
         if (kb == 6) PFHIP_K_LOAD(rk3, 3, ktn);
         if (kb == 7) PFHIP_V_LOAD(rv3, 3, ktn);
       }
@@ -196,39 +206,49 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         oacc0[e] *= alpha;
-        if (ND > 1) { oacc1[e] *= alpha; oacc2[e] *= alpha; oacc3[e] *= alpha; }
+        if (ND > 1) oacc1[e] *= alpha;
+        if (ND > 2) oacc2[e] *= alpha;
+        if (ND > 3) oacc3[e] *= alpha;
       }
     }
 
     // O^T[d][q] += sum_key V[key][d] * P^T[key][q]; V values of step e+1 are read under the 4 MFMAs of e
     const float* vp = vs + (4 * h) * kHeadDim + r;
+    // column of this lane in d-tile 2 / 3, relative to r: lanes past the head's last column re-read it (their rows of O^T are dropped)
+    const int c2 = HD % 32 == 0 ? 64 : (64 + r < HD ? 64 + r : HD - 1) - r, c3 = HD % 32 == 0 ? 96 : (96 + r < HD ? 96 + r : HD - 1) - r;
     float va0 = vp[0], va1 = 0.f, va2 = 0.f, va3 = 0.f;
-    if (ND > 1) { va1 = vp[32]; va2 = vp[64]; va3 = vp[96]; }
+    if (ND > 1) va1 = vp[32];
+    if (ND > 2) va2 = vp[c2];
+    if (ND > 3) va3 = vp[c3];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int en = e < 15 ? e + 1 : e;
       const float* vrow = vp + ((en & 3) + 8 * (en >> 2)) * kHeadDim;
       const float vn0 = vrow[0];
       float vn1 = 0.f, vn2 = 0.f, vn3 = 0.f;
-      if (ND > 1) { vn1 = vrow[32]; vn2 = vrow[64]; vn3 = vrow[96]; }
+      if (ND > 1) vn1 = vrow[32];
+      if (ND > 2) vn2 = vrow[c2];
+      if (ND > 3) vn3 = vrow[c3];
       if (e == 0) PFHIP_K_STORE(rk0, 0, cur ^ 1);
       if (e == 1) PFHIP_V_STORE(rv0, 0, cur ^ 1);
       if (NP > 1) {
         if (e == 2) PFHIP_K_STORE(rk1, 1, cur ^ 1);
         if (e == 3) PFHIP_V_STORE(rv1, 1, cur ^ 1);
+      }
+      if (NP > 2) {
         if (e == 4) PFHIP_K_STORE(rk2, 2, cur ^ 1);
         if (e == 5) PFHIP_V_STORE(rv2, 2, cur ^ 1);
+      }
+      if (NP > 3) {
         if (e == 6) PFHIP_K_STORE(rk3, 3, cur ^ 1);
         if (e == 7) PFHIP_V_STORE(rv3, 3, cur ^ 1);
       }
       __builtin_amdgcn_sched_barrier(0);
       const float pb = sacc[e];
       oacc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(va0, pb, oacc0, 0, 0, 0);
-      if (ND > 1) {
-        oacc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(va1, pb, oacc1, 0, 0, 0);
-        oacc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(va2, pb, oacc2, 0, 0, 0);
-        oacc3 = __builtin_amdgcn_mfma_f32_32x32x2f32(va3, pb, oacc3, 0, 0, 0);
-      }
+      if (ND > 1) oacc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(va1, pb, oacc1, 0, 0, 0);
+      if (ND > 2) oacc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(va2, pb, oacc2, 0, 0, 0);
+      if (ND > 3) oacc3 = __builtin_amdgcn_mfma_f32_32x32x2f32(va3, pb, oacc3, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       va0 = vn0; va1 = vn1; va2 = vn2; va3 = vn3;
     }
@@ -238,6 +258,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 #undef PFHIP_V_LOAD
 #undef PFHIP_K_STORE
 #undef PFHIP_V_STORE
+#undef PFHIP_STAGE_LIVE
 
   // ---- normalise, transpose through LDS, store full rows ------------------------------------------
   const float inv_l = 1.0f / l_run;
@@ -248,20 +269,23 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
     o4.x = OACC[4 * g + 0] * inv_l; o4.y = OACC[4 * g + 1] * inv_l;                      \
     o4.z = OACC[4 * g + 2] * inv_l; o4.w = OACC[4 * g + 3] * inv_l;                      \
     /* registers 4g..4g+3 are d = dt*32 + 8g + 4h + (0..3) of query column r */          \
-    *reinterpret_cast<float4*>(os + r * kKS + (dt) * 32 + 8 * g + 4 * h) = o4;           \
+    if ((dt) * 32 + 8 * g + 8 <= HD)                                                     \
+      *reinterpret_cast<float4*>(os + r * kKS + (dt) * 32 + 8 * g + 4 * h) = o4;         \
   }
   PFHIP_O_STORE(oacc0, 0)
-  if (ND > 1) { PFHIP_O_STORE(oacc1, 1) PFHIP_O_STORE(oacc2, 2) PFHIP_O_STORE(oacc3, 3) }
+  if (ND > 1) { PFHIP_O_STORE(oacc1, 1) }
+  if (ND > 2) { PFHIP_O_STORE(oacc2, 2) }
+  if (ND > 3) { PFHIP_O_STORE(oacc3, 3) }
 #undef PFHIP_O_STORE
   __syncthreads();
   // each wave stores its own 32 x HD tile as full rows: C4 lanes x float4 per row, 64/C4 rows per pass
   {
     constexpr int RW = 64 / C4;
 #pragma unroll
-    for (int pass = 0; pass < kQW / RW; ++pass) {
+    for (int pass = 0; pass < (kQW + RW - 1) / RW; ++pass) {
       const int row = pass * RW + lane / C4, cc = lane % C4;
       const int qrow = q0 + wave * kQW + row;
-      if (qrow < Lq) {
+      if (lane < RW * C4 && row < kQW && qrow < Lq) {
         const float4 o4 = *reinterpret_cast<const float4*>(os + row * kKS + 4 * cc);
         *reinterpret_cast<float4*>(O + (qbase + qrow) * ldo + head * kHeadDim + 4 * cc) = o4;
       }
@@ -271,23 +295,33 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 
 }  // namespace
 
+// One launch of the fp32-MFMA kernel for the head widths it is built for; any other width is a programming error (the ABI and
+// pfhip_create refuse it before a launch is reached)
+static void launch_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                                 const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, const int* q_kv_limit, int B, int H,
+                                 int max_q_len, float scale, int head_dim, hipStream_t s) {
+  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(256);
+#define PFHIP_ATT(HD_)                                                                                                      \
+  hipLaunchKernelGGL(attention_kernel<HD_>, grid, block, 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, \
+                     q_kv_limit, scale)
+  if (head_dim == 32) PFHIP_ATT(32);
+  else if (head_dim == 80) PFHIP_ATT(80);
+  else if (head_dim == 128) PFHIP_ATT(128);
+  else { fprintf(stderr, "pfhip: no attention kernel for head width %d\n", head_dim); abort(); }
+#undef PFHIP_ATT
+}
+
 void launch_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
                       float* O, int ldo, const int* q_off, const int* q_len, const int* kv_off,
-                      const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s) {
-  launch_attention_hd(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, kHeadDim, s);
+                      const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s, int head_dim) {
+  launch_attention_hd(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, head_dim, s);
 }
 
 void launch_attention_masked(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                              const int* q_off, const int* q_len, const int* kv_off, const int* kv_len,
                              const int* q_kv_limit, int B, int H, int max_q_len, float scale, int head_dim, hipStream_t s) {
   if (B <= 0 || max_q_len <= 0) return;
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(256);
-  if (head_dim == 32)
-    hipLaunchKernelGGL(attention_kernel<32>, grid, block, 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
-                       kv_len, q_kv_limit, scale);
-  else
-    hipLaunchKernelGGL(attention_kernel<128>, grid, block, 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
-                       kv_len, q_kv_limit, scale);
+  launch_attention_f32(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, q_kv_limit, B, H, max_q_len, scale, head_dim, s);
 }
 
 // the split-operand attention: two fp16 planes / three products (attention_x3.hip, default) or three bf16 planes / six products
@@ -309,24 +343,25 @@ static bool att_x6_on() {
   return x6;
 }
 
-bool attention_fsmn_is_fused(int max_len) {
+// d_k = 80 has no fused memory block and no plane-image output: its encoder layers take launch_fsmn + the attention launch
+bool attention_fsmn_is_fused(int max_len, int head_dim) {
   static const bool fuse = [] { const char* e = getenv("PFHIP_ATT_FSMN"); return !(e && e[0] == '0'); }();
-  return fuse && att_x6_on() && max_len > 64;
+  return fuse && att_x6_on() && max_len > 64 && head_dim == kHeadDim;
 }
 
-bool attention_planes_ok(int max_len) { return attention_fsmn_is_fused(max_len) && att_x3_on(); }
+bool attention_planes_ok(int max_len, int head_dim) { return attention_fsmn_is_fused(max_len, head_dim) && att_x3_on(); }
 
 void launch_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                            const int* off, const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem,
-                           int ldmem, hipStream_t s, bool mem_accumulate, void* planes_hi, void* planes_lo, int plane_rows) {
+                           int ldmem, hipStream_t s, bool mem_accumulate, void* planes_hi, void* planes_lo, int plane_rows, int head_dim) {
   if (B <= 0 || max_len <= 0) return;
-  if (attention_fsmn_is_fused(max_len)) {
+  if (attention_fsmn_is_fused(max_len, head_dim)) {
     launch_attention_split(Q, ldq, K, ldk, V, ldv, O, ldo, off, len, off, len, B, H, max_len, scale, s, fsmn_w, mem, ldmem, mem_accumulate,
                            planes_hi, planes_lo, plane_rows);
     return;
   }
-  launch_fsmn(V, ldv, fsmn_w, nullptr, 0, mem, ldmem, off, len, B, max_len, H * kHeadDim, s);
-  launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, off, len, off, len, B, H, max_len, scale, s);
+  launch_fsmn(V, ldv, fsmn_w, nullptr, 0, mem, ldmem, off, len, B, max_len, H * head_dim, s);
+  launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, off, len, off, len, B, H, max_len, scale, s, head_dim);
 }
 
 void launch_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
@@ -335,18 +370,17 @@ void launch_attention_hd(const float* Q, int ldq, const float* K, int ldk, const
   if (B <= 0 || max_q_len <= 0) return;
   // d_k = 128 without per-query limits (encoder self-attention, decoder cross-attention): both products on the BF16 matrix
   // cores with the exact three-way split (attention_x6.hip) — 1.5 x this file's fp32-MFMA kernel.  PFHIP_ATT_X6=0 keeps fp32.
-  static const bool x6 = [] { const char* e = getenv("PFHIP_ATT_X6"); return !(e && e[0] == '0'); }();
-  if (x6 && head_dim == 128 && max_q_len > 64) {      // streaming windows (20 queries) would leave 7 of its 8 waves idle
+  if (att_x6_on() && head_dim == 128 && max_q_len > 64) {      // streaming windows (20 queries) would leave 7 of its 8 waves idle
     launch_attention_split(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, s);
     return;
   }
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(256);
-  if (head_dim == 32)
-    hipLaunchKernelGGL(attention_kernel<32>, grid, block, 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
-                       kv_len, static_cast<const int*>(nullptr), scale);
-  else
-    hipLaunchKernelGGL(attention_kernel<128>, grid, block, 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
-                       kv_len, static_cast<const int*>(nullptr), scale);
+  // d_k = 80 (the small Paraformer): the same switch at 64 queries onto the fp16 two-plane kernel of attention_h80.hip; the exact
+  // re-run of the range guard (launch_ctx().exact: no fp16 planes) and PFHIP_ATT_X6=0 / PFHIP_ATT_X3=0 keep this file's fp32 kernel
+  if (att_x6_on() && att_x3_on() && head_dim == 80 && max_q_len > 64) {
+    launch_attention_h80(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, s);
+    return;
+  }
+  launch_attention_f32(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, nullptr, B, H, max_q_len, scale, head_dim, s);
 }
 
 }  // namespace pfhip

@@ -66,6 +66,7 @@ struct Tensor {
 
 struct Config {
   int d_model = 512, n_head = 4, ffn = 2048, enc_layers = 50, dec_layers = 16, dec_ffn = 2048;
+  int dec_n_head = 0;          // decoder_conf.attention_heads when it differs from the encoder's; pfhip_create resolves 0 to n_head
   int kernel = 11, vocab = 8404, n_mels = 80, lfr_m = 7, lfr_n = 6, pred_residual = 0, contextual = 0, timestamp = 0;
   float smooth_factor2 = 0.25f, noise_threshold2 = 0.01f;      // CifPredictorV3 timestamp head
   float cif_threshold = 1.0f, tail_threshold = 0.45f, smooth_factor = 1.0f, noise_threshold = 0.0f;
@@ -336,7 +337,10 @@ inline void gemm(pfhip_model* m, hipStream_t s, const float* A, int lda, const f
           float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
           int M, bool relu) {
   Scope sc(m, s, K_GEMM, 2.0 * M * (double)N * Ktrue, 4.0 * ((double)M * Ktrue + (double)N * Ktrue + (double)M * N));
-  launch_gemm_f32(A, lda, Wd, K, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, /*guard=*/false, s, m->w_scale_of(Wd));
+  // N that is no multiple of the column tile AND a C too narrow for the tile's pad columns (d_model 320: N = 320 / 960 with ldc = N):
+  // the bounds-checked epilogue.  The model's other shapes (N % 128 == 0, or the vocabulary with ldc = vocab_pad) keep the unguarded one.
+  const bool guard = N % pfhip::kTileN != 0 && ldc < (N + pfhip::kTileN - 1) / pfhip::kTileN * pfhip::kTileN;
+  launch_gemm_f32(A, lda, Wd, K, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, guard, s, m->w_scale_of(Wd));
 }
 // pinned staging, grown on demand (callers have no copy in flight from the old block: every forward ends with a sync)
 inline pfhip_status ensure_h_meta(pfhip_model* m, size_t bytes) {

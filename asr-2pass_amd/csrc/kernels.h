@@ -9,7 +9,9 @@ namespace pfhip {
 constexpr int kTileM = 128;      // GEMM block tile rows   (activation buffers are allocated in multiples)
 constexpr int kTileN = 128;      // GEMM block tile cols   (weights are repacked/padded to multiples)
 constexpr int kTileK = 32;       // GEMM k-step            (K is padded to multiples)
-constexpr int kHeadDim = 128;    // attention kernel is specialised for d_k = 128
+constexpr int kHeadDim = 128;    // the attention kernels' default head width (Paraformer-large); see head_dim_supported
+constexpr int kHeadDimSmall = 80; // the small Paraformer: d_model 320 / 4 heads
+inline bool head_dim_supported(int hd) { return hd == kHeadDim || hd == kHeadDimSmall; }      // what a Paraformer may be built with
 constexpr int kMelW = 32;        // max taps per mel triangle (80 bins @ 512-pt FFT need <= 19)
 
 // ---- front end (SURVEY §8a rows a2,a3) -------------------------------------------------------
@@ -154,9 +156,10 @@ void launch_fsmn_shift(const float* v, int ldv, const float* w, const float* res
 // utterance's own keys.  q segments (q_off,q_len), kv segments (kv_off,kv_len), all device arrays.
 void launch_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
                       float* O, int ldo, const int* q_off, const int* q_len, const int* kv_off,
-                      const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s);
+                      const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s, int head_dim = kHeadDim);
 
-// Same kernel with the head dimension chosen at run time: 128 or 32 (CT-Transformer: 256 / 8 heads).
+// Same kernel with the head dimension chosen at run time: 128, 80 (the small Paraformer: 320 / 4 heads) or 32 (CT-Transformer:
+// 256 / 8 heads).  d_k = 80 with more than 64 queries per utterance runs attention_h80.hip unless the launch context is exact.
 void launch_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                          int max_q_len, float scale, int head_dim, hipStream_t s);
@@ -175,18 +178,23 @@ void launch_attention_x3(const float* Q, int ldq, const float* K, int ldk, const
                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
                          float scale, hipStream_t s, const float* fsmn_w = nullptr, float* mem = nullptr, int ldmem = 0,
                          bool mem_accumulate = false, void* planes_hi = nullptr, void* planes_lo = nullptr, int plane_rows = 0);
+// d_k = 80 in the same arithmetic class (attention_h80.hip): two fp16 planes, three products per block on v_mfma_f32_32x32x16_f16,
+// fp32 accumulation, online softmax; V^T padded to 96 rows in LDS.  fp32 rows out; no fused memory block, no plane images.
+void launch_attention_h80(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
+                          float scale, hipStream_t s);
 // Encoder-layer pair: FSMN memory of V (into mem) + self-attention (into O).  One launch where the BF16 attention kernel runs
 // (d_k = 128, more than 64 queries per utterance), otherwise launch_fsmn + launch_attention.  C = V's channel count (H * 128).
 void launch_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                            const int* off, const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem,
                            int ldmem, hipStream_t s, bool mem_accumulate = false, void* planes_hi = nullptr, void* planes_lo = nullptr,
-                           int plane_rows = 0);
+                           int plane_rows = 0, int head_dim = kHeadDim);
 // whether launch_attention_fsmn can write the context as fp16 plane images (gemm_p3.hip's A operand) instead of fp32 rows: the
 // fused launch on attention_x3.hip only.  With planes_hi set, O is not written.
-bool attention_planes_ok(int max_len);
+bool attention_planes_ok(int max_len, int head_dim = kHeadDim);
 // whether launch_attention_fsmn will be the single fused launch (then, and only then, mem_accumulate is honoured: the caller may
 // pass the residual stream as `mem` and drop the memory term from the output projection)
-bool attention_fsmn_is_fused(int max_len);
+bool attention_fsmn_is_fused(int max_len, int head_dim = kHeadDim);      // never at d_k = 80
 void launch_attention_masked(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                              const int* q_off, const int* q_len, const int* kv_off, const int* kv_len,
                              const int* q_kv_limit, int B, int H, int max_q_len, float scale, int head_dim, hipStream_t s);
@@ -281,12 +289,13 @@ void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const 
                           const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K, bool relu, hipStream_t s);
 // Attention of ONE window (Lq, Lk <= 32 rows starting at the given pointers; d_k = 128; H heads): one small workgroup per head,
 // operands requested at kernel start (stream_fused.hip).  Returns false for shapes it does not take.
+// head_dim: 128 or 80 (any other: false).
 bool launch_window_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
-                             int H, float scale, hipStream_t s);
+                             int H, float scale, hipStream_t s, int head_dim = kHeadDim);
 bool launch_window_attention_segments(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                                       const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                                       int max_q_len, int max_kv_len, float scale, hipStream_t s, const float* fsmn_w = nullptr,
-                                      float* mem = nullptr, int ldmem = 0);
+                                      float* mem = nullptr, int ldmem = 0, int head_dim = kHeadDim);
 // The window's attention AND the projection of its context by W [N, 512] (+bias, +R1, + the FSMN memory of fsmn_v) in one launch:
 // every workgroup redoes the attention and keeps the context in LDS (stream_fused.hip).  H = 4 heads of 128, Lq <= 20, Lk <= 32.
 bool launch_fused_att_out(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int Lq, int Lk, int H, float scale,

@@ -1406,6 +1406,7 @@ void load_asr(const std::string& model, const std::string& second, const std::st
   c.kernel = (int)enc.number("kernel_size", c.kernel);
   c.dec_layers = (int)dec.number("att_layer_num", dec.number("num_blocks", c.dec_layers));
   c.dec_ffn = (int)dec.number("linear_units", c.dec_ffn);
+  const int dec_n_head = (int)dec.number("attention_heads", c.n_head);      // the decoder's own, where config.yaml states one
   c.cif_threshold = pred.number("threshold", c.cif_threshold);
   c.tail_threshold = pred.number("tail_threshold", c.tail_threshold);
   c.smooth_factor = pred.number("smooth_factor", c.smooth_factor);
@@ -1443,6 +1444,7 @@ void load_asr(const std::string& model, const std::string& second, const std::st
                    ", \"smooth_factor\": " + num(c.smooth_factor) + ", \"noise_threshold\": " + num(c.noise_threshold) +
                    ", \"pred_residual\": 0, \"contextual\": " + std::to_string(c.contextual) + ", \"timestamp\": " + std::to_string(c.timestamp) +
                    ", \"fs\": " + std::to_string(c.fs);
+  if (dec_n_head != c.n_head) cj += ", \"dec_n_head\": " + std::to_string(dec_n_head);
   if (c.timestamp) {
     if (c.has_sf2) cj += ", \"smooth_factor2\": " + num(c.smooth_factor2);
     if (c.has_nt2) cj += ", \"noise_threshold2\": " + num(c.noise_threshold2);

@@ -63,6 +63,12 @@ int pfhip_op_window_attention(const float* Q, int ldq, const float* K, int ldk, 
   if (!pfhip::launch_window_attention(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, H, scale, S(stream))) return (int)hipErrorInvalidValue;
   return done();
 }
+int pfhip_op_window_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
+                                 int H, float scale, int head_dim, void* stream) {
+  if (head_dim != 128 && head_dim != 80) return (int)hipErrorInvalidValue;      // before anything is launched
+  if (!pfhip::launch_window_attention(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, H, scale, S(stream), head_dim)) return (int)hipErrorInvalidValue;
+  return done();
+}
 int pfhip_op_fused_att_out(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int Lq, int Lk, int H, float scale,
                            const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* fsmn_v,
                            int ldfv, const float* fsmn_w, int N, void* stream) {
@@ -158,7 +164,7 @@ int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const f
 int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                           const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                           int max_q_len, float scale, int head_dim, void* stream) {
-  if (head_dim != 32 && head_dim != 128) return (int)hipErrorInvalidValue;
+  if (head_dim != 32 && head_dim != 80 && head_dim != 128) return (int)hipErrorInvalidValue;      // before anything is launched
   pfhip::launch_attention_hd(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, head_dim,
                              S(stream));
   return done();

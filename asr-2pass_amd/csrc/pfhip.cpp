@@ -130,6 +130,7 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   Config& c = m->cfg;
   c.d_model = (int)jc->number("d_model", c.d_model);
   c.n_head = (int)jc->number("n_head", c.n_head);
+  c.dec_n_head = (int)jc->number("dec_n_head", c.n_head);       // written by the loaders only where decoder_conf differs
   c.ffn = (int)jc->number("ffn", c.ffn);
   c.enc_layers = (int)jc->number("enc_layers", c.enc_layers);
   c.dec_layers = (int)jc->number("dec_layers", c.dec_layers);
@@ -154,9 +155,15 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   c.noise_threshold = (float)jc->number("noise_threshold", c.noise_threshold);
 
   // what the gfx950 kernels are specialised for
-  if (c.d_model % 128 || c.d_model / c.n_head != pfhip::kHeadDim)
-    return fail(PFHIP_ERR_UNSUPPORTED, "attention kernel needs d_model/n_head == 128");
+  if (c.d_model <= 0 || c.n_head <= 0 || c.d_model % 64 || c.d_model % c.n_head || !pfhip::head_dim_supported(c.d_model / c.n_head))
+    return fail(PFHIP_ERR_UNSUPPORTED, "attention kernel needs d_model/n_head == 128 or 80 (and d_model a multiple of 64)");
+  if (c.dec_n_head <= 0 || c.d_model % c.dec_n_head || !pfhip::head_dim_supported(c.d_model / c.dec_n_head))
+    return fail(PFHIP_ERR_UNSUPPORTED, "decoder attention needs d_model/dec_n_head == 128 or 80");
   if (c.d_model > 1024) return fail(PFHIP_ERR_UNSUPPORTED, "d_model > 1024");
+  // the hotword decoder, the timestamp head and its BLSTM are built for head width 128 only
+  if ((c.d_model / c.n_head != pfhip::kHeadDim || c.d_model / c.dec_n_head != pfhip::kHeadDim) && (c.contextual || c.timestamp))
+    return fail(PFHIP_ERR_UNSUPPORTED, "contextual (hotword) and timestamp models need head width d_model/n_head == 128; this model has " +
+                                           std::to_string(c.d_model / c.n_head));
   if (c.kernel != 11) return fail(PFHIP_ERR_UNSUPPORTED, "FSMN kernel size must be 11");
   if (c.n_mels != 80 || c.lfr_m != 7 || c.lfr_n != 6) return fail(PFHIP_ERR_UNSUPPORTED, "front end needs 80 mels, LFR 7/6");
   if (c.ffn % 128 || c.dec_ffn % 128 || c.ffn > 2048 || c.dec_ffn > 2048)
@@ -686,7 +693,8 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
     Scope sc(m, s, K_OTHER, 0, 4.0 * M * (FD + FP));
     pfhip::launch_embed(m->feats.f(), FD, m->x0.f(), FP, m->m_row_pos, M, m->d_inv_ts, sqrtf((float)d), s);
   }
-  const float att_scale = 1.0f / sqrtf((float)pfhip::kHeadDim);
+  const int hd = d / c.n_head;                    // 128, or 80 (the small Paraformer)
+  const float att_scale = 1.0f / sqrtf((float)hd);
   double attn_pairs = 0;
   for (int b = 0; b < B; ++b) attn_pairs += (double)m->T[b] * m->T[b];
   float* x = m->x.f();
@@ -697,7 +705,7 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   // (not on the exact kernels: the fold's cancellation is a property of fp32 accumulation, not of the planes — kernels.h kLnOffsetMax —
   // and the exact forward is what a batch flagged for its offset is redone on)
   const bool fuse_ln = m->d_lnw_qkv != nullptr && pfhip::gemm_x6_ln_ok(M) && !pfhip::launch_ctx().exact;
-  const bool mem_in_x = pfhip::attention_fsmn_is_fused(m->maxT);
+  const bool mem_in_x = pfhip::attention_fsmn_is_fused(m->maxT, hd);
   if (fuse_ln) HIP_TRY(m->lnstats.ensure((size_t)Mp * 4 * 2 * 4));
   auto gemm_ln = [&](const float* A, const float* Wd, int N, float* Cd, int ldc, const float* bias, const float* R1, const float* R2,
                      bool relu, const float* ln_colsum, bool stats_out, int K) {
@@ -716,7 +724,7 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   // switch, PFHIP_PLANES=0 at load removes the path)
   static const int planes_min_rows = [] { const char* e = getenv("PFHIP_PLANES_MIN_ROWS"); return e && *e ? atoi(e) : 3500; }();
   const bool planes = fuse_ln && mem_in_x && m->wp_layer_bytes != 0 && M >= planes_min_rows && pfhip::gemm_f16_planes_form() &&
-                      pfhip::attention_planes_ok(m->maxT);
+                      pfhip::attention_planes_ok(m->maxT, hd);
   if (planes) {
     ++m->plane_forwards;
     const size_t pd = pfhip::plane_image_bytes(Mp, d), pf = pfhip::plane_image_bytes(Mp, c.ffn);
@@ -794,7 +802,7 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
       else
       pfhip::launch_attention_fsmn(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, m->m_row_off,
                                    m->m_len, B, c.n_head, m->maxT, att_scale, m->W(p + "fsmn.w").d, mem_in_x ? x : m->mem.f(), d, s,
-                                   mem_in_x && !first, planes ? ctxP.hi : nullptr, planes ? ctxP.lo : nullptr, Mp);
+                                   mem_in_x && !first, planes ? ctxP.hi : nullptr, planes ? ctxP.lo : nullptr, Mp, hd);
     }
     if (planes) {
       // x = ctx Wo^T + b + (x + memory): fp32 for the residual stream, plane images for FFN1, row statistics for its LayerNorm
@@ -922,6 +930,8 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   }
   double cross_pairs = 0;
   for (int b = 0; b < B; ++b) cross_pairs += (double)m->n_fires[b] * m->T[b];
+  const int hdd = d / c.dec_n_head;               // the decoder's head width (decoder_conf.attention_heads)
+  const float att_scale_d = 1.0f / sqrtf((float)hdd);
   // The decoder's FFN LayerNorms fold the same way (rows >= 4096): norm1 into FFN1 — its input is the residual stream the
   // previous layer's output projection wrote (statistics from that epilogue; the first layer's input comes from the CIF, so it
   // keeps its LayerNorm launch) — and the 2048-wide ffn_norm into FFN2 (FFN1's epilogue leaves 16 pairs per row, after its ReLU).
@@ -946,7 +956,7 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   // the q projections (their input comes from the FSMN kernel), a contextual model's last layer and the vocabulary projection stay
   // on the in-loop-split kernels.
   static const int dec_planes_min_rows = [] { const char* e = getenv("PFHIP_DEC_PLANES_MIN_ROWS"); return e && *e ? atoi(e) : 3500; }();
-  const bool dec_planes = planes && fuse_dec && m->dwp_layer_bytes != 0 && ML >= dec_planes_min_rows && pfhip::attention_planes_ok(m->maxL) &&
+  const bool dec_planes = planes && fuse_dec && m->dwp_layer_bytes != 0 && ML >= dec_planes_min_rows && pfhip::attention_planes_ok(m->maxL, hdd) &&
                           pfhip::gemm_f16_planes_form();
   Img encP{nullptr, nullptr}, xdP{nullptr, nullptr}, hdP{nullptr, nullptr}, ctxdP{nullptr, nullptr};
   bool xd_has_planes = false;
@@ -1038,10 +1048,10 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
       Scope sc(m, s, K_ATTN, 4.0 * cross_pairs * d, 8.0 * ML * d + 8.0 * M * d);
       if (dec_planes && plain_layer)     // the context leaves as plane images for the output projection; no fp32 context is written
         pfhip::launch_attention_x3(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len, m->m_row_off, m->m_len,
-                                   B, c.n_head, m->maxL, att_scale, s, nullptr, nullptr, 0, false, ctxdP.hi, ctxdP.lo, MLp);
+                                   B, c.dec_n_head, m->maxL, att_scale_d, s, nullptr, nullptr, 0, false, ctxdP.hi, ctxdP.lo, MLp);
       else
         pfhip::launch_attention(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len,
-                                m->m_row_off, m->m_len, B, c.n_head, m->maxL, att_scale, s);
+                                m->m_row_off, m->m_len, B, c.dec_n_head, m->maxL, att_scale_d, s, hdd);
     }
     xd_has_stats = false;
     xd_has_planes = false;
@@ -1077,7 +1087,7 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
       for (int b = 0; b < B; ++b) hw_pairs += (double)m->n_fires[b] * m->fw_hw_len[b];
       Scope sc(m, s, K_ATTN, 4.0 * hw_pairs * d, 8.0 * ML * d);
       pfhip::launch_attention(m->qd.f(), d, hwkv, 2 * d, hwkv + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len,
-                              m->m_hw_off, m->m_hw_len, B, c.n_head, m->maxL, att_scale, s);
+                              m->m_hw_off, m->m_hw_len, B, c.dec_n_head, m->maxL, att_scale_d, s);
     }
     gemm(m, s, m->ctxd.f(), d, m->W("bias.dec.out.w").d, d, d, d, cat + d, 2 * d, m->W("bias.dec.out.b").d, nullptr, 0, nullptr,
          0, ML, false);
@@ -1693,6 +1703,7 @@ int pfhip_sample_rate(const pfhip_model* m) { return m ? m->cfg.sample_rate : 0;
 int pfhip_vocab_size(const pfhip_model* m) { return m ? m->cfg.vocab : 0; }
 int pfhip_feat_dim(const pfhip_model* m) { return m ? m->feat_dim : 0; }
 int pfhip_d_model(const pfhip_model* m) { return m ? m->cfg.d_model : 0; }
+int pfhip_head_dim(const pfhip_model* m) { return m && m->cfg.n_head > 0 ? m->cfg.d_model / m->cfg.n_head : 0; }
 
 pfhip_status pfhip_offline_enqueue(pfhip_model* m, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
                                    int batch, void* stream) {

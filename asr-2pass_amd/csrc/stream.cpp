@@ -200,7 +200,10 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
                              const std::vector<std::vector<int32_t>*>& outs, bool want_logp, Recorder& rec) {
   const Config& c = m->cfg;
   const int d = c.d_model, FD = m->feat_dim, FP = m->feat_pad, B = (int)ss.size();
-  const float att_scale = 1.0f / sqrtf((float)pfhip::kHeadDim);
+  const int hd = d / c.n_head;                    // 128, or 80 (the small Paraformer)
+  const float att_scale = 1.0f / sqrtf((float)hd);
+  const int hdd = d / c.dec_n_head;               // the decoder's (decoder_conf.attention_heads)
+  const float att_scale_d = 1.0f / sqrtf((float)hdd);
   if (B == 0) return flush(m, rec, st);
   std::vector<pfhip::StreamSeg> segs(B);
   int M = 0;
@@ -296,13 +299,13 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
                 nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, 3 * d, Kp, false);
       // attention + output projection + FSMN memory + residual as one launch (every workgroup redoes the attention) is opt-in:
       // measured slower than the two launches (stream_fused.hip, launch_fused_att_out)
-      if (!att_out_on || !pfhip::launch_fused_att_out(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, M, M, c.n_head, att_scale,
+      if (!att_out_on || hd != pfhip::kHeadDim || !pfhip::launch_fused_att_out(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, M, M, c.n_head, att_scale,
                                        m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, first ? nullptr : x, d, m->qkv.f() + 2 * d,
                                        3 * d, m->W(p + "fsmn.w").d, d, st)) {
         if (!pfhip::launch_window_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, M, M,
-                                            c.n_head, att_scale, st))
+                                            c.n_head, att_scale, st, hd))
           pfhip::launch_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
-                                  d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st);
+                                  d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st, hd);
         if (!gemv1(m->ctx.f(), d, m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, nullptr, first ? nullptr : x, d, m->qkv.f() + 2 * d,
                    3 * d, m->W(p + "fsmn.w").d, M, d, d, false))
           ln_gemm(m->ctx.f(), d, 0, "", m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, first ? nullptr : x, d, nullptr, 0,
@@ -334,10 +337,10 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     // written by the same launch
     if (!pfhip::launch_window_attention_segments(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
                                                  d_len, d_off, d_len, B, c.n_head, maxn, maxn, att_scale, st, m->W(p + "fsmn.w").d,
-                                                 m->mem.f(), d)) {
+                                                 m->mem.f(), d, hd)) {
       pfhip::launch_fsmn(m->qkv.f() + 2 * d, 3 * d, m->W(p + "fsmn.w").d, nullptr, 0, m->mem.f(), d, d_off, d_len, B, maxn, d, st);
       pfhip::launch_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
-                              d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st);
+                              d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st, hd);
     }
     if (fuse_ln_s) {
       pfhip::launch_gemm_f32_x6_ln(m->ctx.f(), d, m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, m->mem.f(), d, first ? nullptr : x, d, M,
@@ -466,12 +469,12 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
         ln_gemm(xd, d, d, p + "norm3", m->W(p + "q.w").d, d, m->qd.f(), d, m->W(p + "q.b").d, nullptr, 0, nullptr, 0, nullptr, 0,
                 nullptr, ML, d, d, false);
       const float* kvl = m->kvall.f() + (size_t)i * 2 * d;
-      if (att_out_on && pfhip::launch_fused_att_out(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, ML, M, c.n_head, att_scale, m->W(p + "out.w").d, d, xd, d,
+      if (att_out_on && hdd == pfhip::kHeadDim && pfhip::launch_fused_att_out(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, ML, M, c.dec_n_head, att_scale_d, m->W(p + "out.w").d, d, xd, d,
                                       m->W(p + "out.b").d, xd, d, nullptr, 0, nullptr, d, st))
         continue;
-      if (!pfhip::launch_window_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, ML, M, c.n_head, att_scale, st))
+      if (!pfhip::launch_window_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, ML, M, c.dec_n_head, att_scale_d, st, hdd))
         pfhip::launch_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off, d_len, B,
-                                c.n_head, maxN, att_scale, st);
+                                c.dec_n_head, maxN, att_scale_d, st, hdd);
       if (!gemv1(m->ctxd.f(), d, m->W(p + "out.w").d, d, xd, d, m->W(p + "out.b").d, nullptr, xd, d, nullptr, 0, nullptr, ML, d, d, false))
         ln_gemm(m->ctxd.f(), d, 0, "", m->W(p + "out.w").d, d, xd, d, m->W(p + "out.b").d, xd, d, nullptr, 0, nullptr, 0, nullptr,
                 ML, d, d, false);
@@ -482,9 +485,9 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     gemm(m, st, m->enc.f(), d, m->W(p + "kv.w").d, 2 * d, d, d, kvbuf, 2 * d, m->W(p + "kv.b").d, nullptr, 0, nullptr, 0, M,
          false);
     if (!pfhip::launch_window_attention_segments(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off,
-                                                 d_len, B, c.n_head, maxN, maxn, att_scale, st))
+                                                 d_len, B, c.dec_n_head, maxN, maxn, att_scale_d, st, nullptr, nullptr, 0, hdd))
       pfhip::launch_attention(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off, d_len, B,
-                              c.n_head, maxN, att_scale, st);
+                              c.dec_n_head, maxN, att_scale_d, st, hdd);
     gemm(m, st, m->ctxd.f(), d, m->W(p + "out.w").d, d, d, d, xd, d, m->W(p + "out.b").d, xd, d, nullptr, 0, ML, false);
   }
   dec_ffn("dec3.", c.dec_layers, xd, m->td.f());

@@ -428,13 +428,14 @@ __global__ __launch_bounds__(1024) void fused_gemv1t_kernel(
 
 // ---- attention over ONE window ----------------------------------------------------------------------------------------------
 // O[q, h*128:(h+1)*128] = softmax(scale * Q_h K_h^T) V_h for Lq <= 32 queries and Lk <= 32 keys (the encoder's self-attention over a
-// 20-row window; the decoder's few tokens against it), d_k = 128.  The general kernel (attention.hip) is built for hundreds of
+// 20-row window; the decoder's few tokens against it), d_k = HD = 128 or 80.  The general kernel (attention.hip) is built for hundreds of
 // keys — query blocks, K/V tiles through LDS, online softmax — and takes 8.6 us here; this one is one workgroup per head, four
 // waves: every operand is requested at kernel start (Q / K fragments of the wave's 32-wide slice of d, the V rows of its 32-wide
 // slice of the output), scores = four partial 32 x 32 tiles on the fp32 MFMA summed through LDS, one softmax pass with 32 lanes per
 // query, P V as ceil(Lk / 2) MFMAs per wave.  Same arithmetic type as the general kernel (fp32 MFMA = fmaf chains, exp2).
 // Grid (head, window): with segment arrays (device: row offsets and lengths per window, as launch_attention takes them) a round of
 // connections is one launch of H x B small workgroups.
+template <int HD>
 __global__ __launch_bounds__(256) void window_attention_kernel(const float* __restrict__ Q, int ldq, const float* __restrict__ K, int ldk,
                                                                const float* __restrict__ V, int ldv, float* __restrict__ O, int ldo,
                                                                int Lq, int Lk, float scale_log2e, const int* __restrict__ q_off,
@@ -455,18 +456,23 @@ __global__ __launch_bounds__(256) void window_attention_kernel(const float* __re
   const int r = lane & 31, hh = lane >> 5;
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
   float4 qf[4], kf[4];
-  const float* qp = Q + (size_t)(r < Lq ? r : 0) * ldq + h * 128 + w * 32 + 4 * hh;
-  const float* kp = K + (size_t)(r < Lk ? r : 0) * ldk + h * 128 + w * 32 + 4 * hh;
+  // HD = 80: wave w still owns the 32-wide slice [32 w, 32 w + 32) of the head; the part of it at or past column HD (half of wave
+  // 2's slice, all of wave 3's) is fed as zeros and never stored, so the four partial score tiles sum as they do at HD = 128
+  const int dbase = w * 32 + 4 * hh;
+  const bool clive = HD == 128 || w * 32 + r < HD;                 // this lane's V / output column exists
+  const float* qp = Q + (size_t)(r < Lq ? r : 0) * ldq + h * HD + dbase;
+  const float* kp = K + (size_t)(r < Lk ? r : 0) * ldk + h * HD + dbase;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    qf[u] = r < Lq ? *reinterpret_cast<const float4*>(qp + 8 * u) : zero4;
-    kf[u] = r < Lk ? *reinterpret_cast<const float4*>(kp + 8 * u) : zero4;
+    const bool dlive = HD % 32 == 0 || dbase + 8 * u < HD;
+    qf[u] = r < Lq && dlive ? *reinterpret_cast<const float4*>(qp + 8 * u) : zero4;
+    kf[u] = r < Lk && dlive ? *reinterpret_cast<const float4*>(kp + 8 * u) : zero4;
   }
   float vf[16];
 #pragma unroll
   for (int st = 0; st < 16; ++st) {
     const int key = 2 * st + hh;
-    vf[st] = key < Lk ? V[(size_t)key * ldv + h * 128 + w * 32 + r] : 0.f;
+    vf[st] = key < Lk && clive ? V[(size_t)key * ldv + h * HD + w * 32 + r] : 0.f;
   }
   f32x16 acc;
 #pragma unroll
@@ -484,8 +490,8 @@ __global__ __launch_bounds__(256) void window_attention_kernel(const float* __re
   // SAN-M memory block of the window (self-attention only: the V rows are the window's own): mem[t][c] = v[t][c] + sum_j
   // w[c][j] v[t + j - 5][c], rows outside [0, Lk) zero — launch_fsmn's operation order.  This lane holds column c = h*128 + w*32 + r
   // of the rows with its parity (vf[st] = row 2 st + hh); the other parity comes from lane ^ 32.
-  if (fsmn_w) {
-    const int c = h * 128 + w * 32 + r;
+  if (fsmn_w && clive) {
+    const int c = h * HD + w * 32 + r;
     float wk[11];
 #pragma unroll
     for (int j = 0; j < 11; ++j) wk[j] = fsmn_w[(size_t)c * 11 + j];
@@ -541,7 +547,7 @@ __global__ __launch_bounds__(256) void window_attention_kernel(const float* __re
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int q = (e & 3) + 8 * (e >> 2) + 4 * hh;
-    if (q < Lq) O[(size_t)q * ldo + h * 128 + w * 32 + r] = o2[e];
+    if (q < Lq && clive) O[(size_t)q * ldo + h * HD + w * 32 + r] = o2[e];
   }
 }
 
@@ -787,24 +793,33 @@ bool launch_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, f
 // window_attention_kernel: false when the shape is outside what it takes (the caller uses launch_attention).
 // PFHIP_STREAM_WATT=0 turns it off.
 bool launch_window_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
-                             int H, float scale, hipStream_t s) {
+                             int H, float scale, hipStream_t s, int head_dim) {
   static const bool on = [] { const char* e = getenv("PFHIP_STREAM_WATT"); return !(e && e[0] == '0'); }();
-  if (!on || Lq < 1 || Lq > 32 || Lk < 1 || Lk > 32 || H < 1) return false;
-  hipLaunchKernelGGL(window_attention_kernel, dim3(H), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk,
-                     scale * 1.4426950408889634f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+  if (!on || Lq < 1 || Lq > 32 || Lk < 1 || Lk > 32 || H < 1 || (head_dim != 128 && head_dim != 80)) return false;
+  if (head_dim == 80)
+    hipLaunchKernelGGL(window_attention_kernel<80>, dim3(H), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk,
+                       scale * 1.4426950408889634f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+  else
+    hipLaunchKernelGGL(window_attention_kernel<128>, dim3(H), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk,
+                       scale * 1.4426950408889634f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
   return true;
 }
 // B windows in one launch: segment arrays on the device, max_q_len / max_kv_len their host-side maxima (both <= 32 or false).
-// fsmn_w != nullptr (self-attention: q segments == kv segments, V = H * 128 channels wide): the launch also writes the encoder
+// fsmn_w != nullptr (self-attention: q segments == kv segments, V = H * head_dim channels wide): the launch also writes the encoder
 // layer's FSMN memory of V into mem (what launch_fsmn computes) — one launch per layer less in a round of connections.
 bool launch_window_attention_segments(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                                       const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                                       int max_q_len, int max_kv_len, float scale, hipStream_t s, const float* fsmn_w, float* mem,
-                                      int ldmem) {
+                                      int ldmem, int head_dim) {
   static const bool on = [] { const char* e = getenv("PFHIP_STREAM_WATT"); return !(e && e[0] == '0'); }();
-  if (!on || B < 1 || H < 1 || max_q_len < 1 || max_q_len > 32 || max_kv_len < 1 || max_kv_len > 32) return false;
-  hipLaunchKernelGGL(window_attention_kernel, dim3(H, B), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, 0, 0,
-                     scale * 1.4426950408889634f, q_off, q_len, kv_off, kv_len, fsmn_w, mem, ldmem);
+  if (!on || B < 1 || H < 1 || max_q_len < 1 || max_q_len > 32 || max_kv_len < 1 || max_kv_len > 32 || (head_dim != 128 && head_dim != 80))
+    return false;
+  if (head_dim == 80)
+    hipLaunchKernelGGL(window_attention_kernel<80>, dim3(H, B), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, 0, 0,
+                       scale * 1.4426950408889634f, q_off, q_len, kv_off, kv_len, fsmn_w, mem, ldmem);
+  else
+    hipLaunchKernelGGL(window_attention_kernel<128>, dim3(H, B), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, 0, 0,
+                       scale * 1.4426950408889634f, q_off, q_len, kv_off, kv_len, fsmn_w, mem, ldmem);
   return true;
 }
 

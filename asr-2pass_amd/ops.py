@@ -26,6 +26,7 @@ def _lib():
                                                _ci, _ci, _ci, _ci, _vp]
         lib.pfhip_op_fused_gemv_1trip.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _cf, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp]
         lib.pfhip_op_window_attention.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _cf, _vp]
+        lib.pfhip_op_window_attention_hd.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _cf, _ci, _vp]
         lib.pfhip_op_fused_att_out.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _cf, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp,
                                                _ci, _vp]
         lib.pfhip_op_layernorm.argtypes = [_vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _cf, _vp]
@@ -224,11 +225,15 @@ def attention_planes(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale):
     return hi, lo, rows
 
 
-def window_attention(Q, K, V, Lq, Lk, n_head, scale):
-    """One streaming window: softmax(scale Q_h K_h^T) V_h for rows [0, Lq) x [0, Lk), d_k = 128."""
-    O = torch.zeros((Q.shape[0], n_head * 128), dtype=torch.float32, device=Q.device)
-    _ck(_lib().pfhip_op_window_attention(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0), Lq, Lk, n_head,
-                                         scale, _stream()), "window_attention")
+def window_attention(Q, K, V, Lq, Lk, n_head, scale, head_dim=128):
+    """One streaming window: softmax(scale Q_h K_h^T) V_h for rows [0, Lq) x [0, Lk), d_k = head_dim (128 or 80)."""
+    O = torch.zeros((Q.shape[0], n_head * head_dim), dtype=torch.float32, device=Q.device)
+    if head_dim == 128:
+        _ck(_lib().pfhip_op_window_attention(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0), Lq, Lk,
+                                             n_head, scale, _stream()), "window_attention")
+    else:
+        _ck(_lib().pfhip_op_window_attention_hd(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0), Lq, Lk,
+                                                n_head, scale, head_dim, _stream()), "window_attention")
     return O
 
 

@@ -28,8 +28,24 @@ PARAFORMER_LARGE = dict(
 )
 
 
+# The small online Paraformer the reference's 2-pass launch scripts stream with (websocket/run_server_2pass.sh:27-28).  Widths from
+# public FunASR knowledge: d_model 320, 4 heads (d_k = 80), FFN 1280 in encoder and decoder.  No file in this repository confirms
+# them, and the layer counts below are upstream hypotheses too; the real config.yaml decides at load.
+PARAFORMER_SMALL = dict(PARAFORMER_LARGE, d_model=320, n_head=4, ffn=1280, dec_ffn=1280,
+                        enc_layers=50, dec_layers=16)      # layer counts: hypotheses (upstream's small model is not available offline)
+
+
+def small_config_320(**over):
+    """The small Paraformer's widths (320 / 4 heads of 80 / 1280 / 1280) with few layers and a small ragged vocabulary, so the CPU
+    oracle finishes in seconds."""
+    cfg = dict(PARAFORMER_SMALL)
+    cfg.update(enc_layers=3, dec_layers=2, vocab=1003)
+    cfg.update(over)
+    return cfg
+
+
 def small_config(**over):
-    """Same widths as Paraformer-large (kernels are specialised for d_model 512 / d_k 128) but few
+    """Same widths as Paraformer-large (the default kernels are specialised for d_model 512 / d_k 128) but few
     layers and a small ragged vocabulary, so the CPU oracle finishes in seconds."""
     cfg = dict(PARAFORMER_LARGE)
     cfg.update(enc_layers=3, dec_layers=2, vocab=1003)

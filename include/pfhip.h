@@ -81,6 +81,10 @@ int pfhip_sample_rate(const pfhip_model* m);
 int pfhip_vocab_size(const pfhip_model* m);
 int pfhip_feat_dim(const pfhip_model* m);   /* lfr_m * n_mels (560) */
 int pfhip_d_model(const pfhip_model* m);
+/* d_model / attention_heads: 128 (Paraformer-large) or 80 (the small online Paraformer).  The reference never fixes this width — it
+ * sizes its caches from encoder_conf.output_size as config.yaml states it (paraformer.cpp:225) — so a host that sizes buffers per
+ * head asks here. */
+int pfhip_head_dim(const pfhip_model* m);
 
 /* ---- offline forward --------------------------------------------------------------------------
  * Replaces the body of Paraformer::Forward / ParaformerTorch::Forward between `float** din` and the

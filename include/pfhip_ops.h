@@ -68,7 +68,8 @@ int pfhip_op_fsmn(const float* v, int ldv, const float* w, const float* res, int
 int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                        const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                        int max_q_len, float scale, void* stream);
-/* Same, head dimension 32 or 128 chosen at run time (CT-Transformer: 256 / 8 heads). */
+/* Same, head dimension 32, 80 or 128 chosen at run time (CT-Transformer: 256 / 8 heads; the small Paraformer: 320 / 4 heads).
+ * hipErrorInvalidValue for any other width, before anything is launched. */
 int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                           const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                           int max_q_len, float scale, int head_dim, void* stream);
@@ -120,6 +121,9 @@ int pfhip_op_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, 
  * onnxruntime/src/paraformer-online.cpp:426-515).  hipErrorInvalidValue for other shapes (callers use pfhip_op_attention). */
 int pfhip_op_window_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
                               int H, float scale, void* stream);
+/* The same with the head width chosen at run time: 128 or 80 (hipErrorInvalidValue for any other, before anything is launched). */
+int pfhip_op_window_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
+                                 int H, float scale, int head_dim, void* stream);
 
 /* The window's MatMul-Softmax-MatMul AND the MatMul/Gemm that projects its context (W [N, 512]; +bias, +residual Add, + the SAN-M
  * FSMN memory of fsmn_v over the Lq rows) in ONE launch: H = 4 heads of 128, Lq <= 20, Lk <= 32.  hipErrorInvalidValue otherwise. */
