@@ -16,6 +16,7 @@
 // Keys >= kv_len are masked to -inf; tile rows past the segment end are clamped to the last valid
 // row, so no out-of-segment memory is read.
 #include "kernels.h"
+#include "launch_common.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -327,7 +328,7 @@ void launch_attention_masked(const float* Q, int ldq, const float* K, int ldk, c
 // the split-operand attention: two fp16 planes / three products (attention_x3.hip, default) or three bf16 planes / six products
 // (attention_x6.hip, PFHIP_ATT_X3=0)
 static bool att_x3_on() {
-  static const bool x3 = [] { const char* e = getenv("PFHIP_ATT_X3"); return !(e && e[0] == '0'); }();
+  static const bool x3 = env_on("PFHIP_ATT_X3");
   return x3 && !launch_ctx().exact;
 }
 static void launch_attention_split(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
@@ -339,13 +340,13 @@ static void launch_attention_split(const float* Q, int ldq, const float* K, int 
 }
 
 static bool att_x6_on() {
-  static const bool x6 = [] { const char* e = getenv("PFHIP_ATT_X6"); return !(e && e[0] == '0'); }();
+  static const bool x6 = env_on("PFHIP_ATT_X6");
   return x6;
 }
 
 // d_k = 80 has no fused memory block and no plane-image output: its encoder layers take launch_fsmn + the attention launch
 bool attention_fsmn_is_fused(int max_len, int head_dim) {
-  static const bool fuse = [] { const char* e = getenv("PFHIP_ATT_FSMN"); return !(e && e[0] == '0'); }();
+  static const bool fuse = env_on("PFHIP_ATT_FSMN");
   return fuse && att_x6_on() && max_len > 64 && head_dim == kHeadDim;
 }
 

@@ -19,18 +19,15 @@
 // A V^T-plane row is 32 keys = 16 dwords padded to 18 (72 B), the stride attention_x3.hip uses: ds_read_b64 in groups of 32 lanes,
 // 18 r mod 64 distinct even numbers for r < 32.
 #include "kernels.h"
+#include "launch_common.h"
+#include "split_common.h"
 
 #include <math.h>
-
-#include <atomic>
 
 namespace pfhip {
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
-using float2v = __attribute__((ext_vector_type(2))) float;
 
 constexpr int kHD = 80, kHDP = 96, kQW = 32, kNW = 8, kQB = kNW * kQW, kKT = 32;
 constexpr int kKSteps = kHD / 16;                // 5 k-steps of the QK^T product
@@ -47,30 +44,7 @@ constexpr int kKChunks = kKT * (kHD / 4);        // 640 float4 of a K tile: thre
 constexpr int kVThreads = (kHD / 2) * (kKT / 4); // 320 threads take a 4-key x 2-d patch of the V tile each
 static_assert(kKChunks == kNW * 64 + 128 && kVThreads == 5 * 64, "staging roles are whole waves");
 
-// x - (float)h for the low / high half of a packed fp16 pair, one instruction each (see gemm_x3.hip)
-__device__ __forceinline__ float sub_lo(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float sub_hi(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ unsigned hi_pair(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b)); }
-__device__ __forceinline__ unsigned lo_pair(float a, float b) {
-  const float2v r = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(r, half2v));
-}
-// 8 fp32 values -> their two fp16 planes, packed as MFMA operands
-__device__ __forceinline__ void split8(const float (&v)[8], half8& p0, half8& p1) {
-  uint4 a, b;
-  a.x = hi_pair(v[0], v[1]); a.y = hi_pair(v[2], v[3]); a.z = hi_pair(v[4], v[5]); a.w = hi_pair(v[6], v[7]);
-  b.x = lo_pair(sub_lo(v[0], a.x), sub_hi(v[1], a.x)); b.y = lo_pair(sub_lo(v[2], a.y), sub_hi(v[3], a.y));
-  b.z = lo_pair(sub_lo(v[4], a.z), sub_hi(v[5], a.z)); b.w = lo_pair(sub_lo(v[6], a.w), sub_hi(v[7], a.w));
-  p0 = __builtin_bit_cast(half8, a); p1 = __builtin_bit_cast(half8, b);
-}
+// the fp16 two-plane primitives (sub_lo / sub_hi, hi_pair / lo_pair, split8): split_common.h
 // 4 values -> 8 bytes of the high plane at base and of the low plane at base + plane_bytes
 __device__ __forceinline__ void store4(float a, float c, float e, float g, unsigned char* base, int plane_bytes) {
   const unsigned h0 = hi_pair(a, c), h1 = hi_pair(e, g);
@@ -292,16 +266,8 @@ void launch_attention_h80(const float* Q, int ldq, const float* K, int ldk, cons
                           const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
                           float scale, hipStream_t s) {
   if (B <= 0 || max_q_len <= 0) return;
-  static std::atomic<unsigned long long> attr_done{0};      // > 64 KB of dynamic LDS needs the opt-in once per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_h80_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsBytes);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(512);
-  hipLaunchKernelGGL(attention_h80_kernel, grid, block, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
+  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB);
+  launch_with_lds<attention_h80_kernel>(grid, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
                      kv_len, scale);
 }
 

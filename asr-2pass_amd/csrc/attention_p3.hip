@@ -19,18 +19,15 @@
 // SAN-M memory block folded in front (reading V as hi + lo: the 22-23-bit value the products see) — is attention_x3.hip's, so the
 // context equals that kernel's bit for bit on the same K / V planes.
 #include "kernels.h"
+#include "launch_common.h"
+#include "split_common.h"
 
 #include <math.h>
-
-#include <atomic>
 
 namespace pfhip {
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
-using float2v = __attribute__((ext_vector_type(2))) float;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef PFHIP_ATTP_ABLATE
@@ -45,28 +42,7 @@ constexpr int kLdsBytes = kNW * kQW * kOS * 4;   // 135,168: the output transpos
 constexpr int kRing = 4;                         // tile buffers: the DMA runs three tiles ahead of the MFMAs
 static_assert(kLdsBytes >= kRing * kBuf, "K/V buffers must fit");
 
-__device__ __forceinline__ float sub_lo(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float sub_hi(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ unsigned hi_pair(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b)); }
-__device__ __forceinline__ unsigned lo_pair(float a, float b) {
-  const float2v r = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(r, half2v));
-}
-__device__ __forceinline__ void split8(const float (&v)[8], half8& p0, half8& p1) {
-  uint4 a, b;
-  a.x = hi_pair(v[0], v[1]); a.y = hi_pair(v[2], v[3]); a.z = hi_pair(v[4], v[5]); a.w = hi_pair(v[6], v[7]);
-  b.x = lo_pair(sub_lo(v[0], a.x), sub_hi(v[1], a.x)); b.y = lo_pair(sub_lo(v[2], a.y), sub_hi(v[3], a.y));
-  b.z = lo_pair(sub_lo(v[4], a.z), sub_hi(v[5], a.z)); b.w = lo_pair(sub_lo(v[6], a.w), sub_hi(v[7], a.w));
-  p0 = __builtin_bit_cast(half8, a); p1 = __builtin_bit_cast(half8, b);
-}
+// the fp16 two-plane primitives (sub_lo / sub_hi, hi_pair / lo_pair, split8): split_common.h
 // byte offset of 16-byte chunk `ch` of key row `row` inside a plane of a tile
 __device__ __forceinline__ int tile_off(int row, int ch) { return kRowB * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 // hi + lo of two packed fp16 pairs -> the fp32 values (exact: the planes do not overlap)
@@ -596,15 +572,8 @@ void launch_attention_p3(const float* Q, int ldq, const void* kv_hi, const void*
                          const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s,
                          const float* fsmn_w, float* mem, int ldmem, bool mem_accumulate, void* planes_hi, void* planes_lo, int plane_rows) {
   if (B <= 0 || max_q_len <= 0) return;
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_p3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(512);
-  hipLaunchKernelGGL(attention_p3_kernel, grid, block, kLdsBytes, s, Q, ldq, static_cast<const unsigned char*>(kv_hi),
+  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB);
+  launch_with_lds<attention_p3_kernel>(grid, kLdsBytes, s, Q, ldq, static_cast<const unsigned char*>(kv_hi),
                      static_cast<const unsigned char*>(kv_lo), ldkv, v_col, O, ldo, q_off, q_len, kv_off, kv_len, scale, fsmn_w, mem, ldmem,
                      mem_accumulate ? 1 : 0, static_cast<unsigned char*>(planes_hi), static_cast<unsigned char*>(planes_lo), plane_rows);
 }

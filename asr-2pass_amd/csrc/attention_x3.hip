@@ -18,18 +18,15 @@
 // Output: fp32 rows, or — the encoder on large batches — the context as the two fp16 plane images that the output projection
 // (gemm_p3.hip) stages by LDS-DMA; then no fp32 context is written at all.
 #include "kernels.h"
+#include "launch_common.h"
+#include "split_common.h"
 
 #include <math.h>
-
-#include <atomic>
 
 namespace pfhip {
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
-using float2v = __attribute__((ext_vector_type(2))) float;
 
 // Timing-only builds (tools/x3_variant.sh <name> "-DPFHIP_ATT_ABLATE=n" attention_x3.hip; results are WRONG for n != 0):
 //   1 no FSMN prologue   2 no tile barrier   3 no softmax arithmetic   4 V fragments of one address only   5 no staging of the next tile
@@ -50,31 +47,7 @@ constexpr int kOS = kHD + 4;                     // floats per row of the output
 constexpr int kLdsBytes = kNW * kQW * kOS * 4;    // 135,168: the output transpose tile (>= 2 * kBuf = 71,680)
 static_assert(kLdsBytes >= 2 * kBuf, "K/V buffers must fit");
 
-// x - (float)h for the low / high half of a packed fp16 pair, one instruction each (see gemm_x3.hip)
-__device__ __forceinline__ float sub_lo(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float sub_hi(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ unsigned hi_pair(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b)); }
-__device__ __forceinline__ unsigned lo_pair(float a, float b) {
-  const float2v r = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(r, half2v));
-}
-
-// 8 fp32 values -> their two fp16 planes, packed as MFMA operands
-__device__ __forceinline__ void split8(const float (&v)[8], half8& p0, half8& p1) {
-  uint4 a, b;
-  a.x = hi_pair(v[0], v[1]); a.y = hi_pair(v[2], v[3]); a.z = hi_pair(v[4], v[5]); a.w = hi_pair(v[6], v[7]);
-  b.x = lo_pair(sub_lo(v[0], a.x), sub_hi(v[1], a.x)); b.y = lo_pair(sub_lo(v[2], a.y), sub_hi(v[3], a.y));
-  b.z = lo_pair(sub_lo(v[4], a.z), sub_hi(v[5], a.z)); b.w = lo_pair(sub_lo(v[6], a.w), sub_hi(v[7], a.w));
-  p0 = __builtin_bit_cast(half8, a); p1 = __builtin_bit_cast(half8, b);
-}
+// the fp16 two-plane primitives (sub_lo / sub_hi, hi_pair / lo_pair, split8): split_common.h
 
 __global__ __launch_bounds__(512, 1) void attention_x3_kernel(
     const float* __restrict__ Q, int ldq, const float* __restrict__ K, int ldk, const float* __restrict__ V, int ldv,
@@ -407,16 +380,8 @@ void launch_attention_x3(const float* Q, int ldq, const float* K, int ldk, const
                          float scale, hipStream_t s, const float* fsmn_w, float* mem, int ldmem, bool mem_accumulate, void* planes_hi,
                          void* planes_lo, int plane_rows) {
   if (B <= 0 || max_q_len <= 0) return;
-  static std::atomic<unsigned long long> attr_done{0};      // > 64 KB of dynamic LDS needs the opt-in once per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsBytes);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(512);
-  hipLaunchKernelGGL(attention_x3_kernel, grid, block, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
+  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB);
+  launch_with_lds<attention_x3_kernel>(grid, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
                      kv_len, scale, fsmn_w, mem, ldmem, mem_accumulate ? 1 : 0, static_cast<unsigned char*>(planes_hi),
                      static_cast<unsigned char*>(planes_lo), plane_rows);
 }

@@ -12,10 +12,9 @@
 // K / V tiles are split while they are staged (global fp32 -> registers -> bf16 planes in LDS; V transposed on the way by
 // loading 4 keys x 4 d per thread), double-buffered, one barrier per tile.
 #include "kernels.h"
+#include "launch_common.h"
 
 #include <math.h>
-
-#include <atomic>
 
 namespace pfhip {
 namespace {
@@ -392,16 +391,8 @@ void launch_attention_x6(const float* Q, int ldq, const float* K, int ldk, const
                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
                          float scale, hipStream_t s, const float* fsmn_w, float* mem, int ldmem, bool mem_accumulate) {
   if (B <= 0 || max_q_len <= 0) return;
-  static std::atomic<unsigned long long> attr_done{0};      // > 64 KB of dynamic LDS needs the opt-in once per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x6_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsBytes);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(512);
-  hipLaunchKernelGGL(attention_x6_kernel, grid, block, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
+  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB);
+  launch_with_lds<attention_x6_kernel>(grid, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
                      kv_len, scale, fsmn_w, mem, ldmem, mem_accumulate ? 1 : 0);
 }
 

@@ -19,6 +19,8 @@
 // ~25 % of the kernel.  The tile is instead transposed through the (now idle) LDS and written as
 // full 512-byte rows with 16-byte accesses; bias / residual / ReLU are applied on the row pass.
 #include "kernels.h"
+#include "launch_common.h"
+#include "split_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -34,25 +36,7 @@ constexpr int kCs = kTileN + 4;                // padded C-tile row stride (floa
 constexpr int kLdsFloats = 4 * kStage;         // 73,728 B: A0 A1 B0 B1; the C tile (128 x 132) reuses it
 static_assert(kTileM * kCs <= kLdsFloats, "C tile must fit the operand buffers");
 
-// XCD-aware tile order (cdna_hip_programming.md T1, bijective form): blocks that share an XCD (equal blockIdx % 8) walk a
-// contiguous run of a linear tile order.  That order is column-GROUP major: group g = column tiles [g*gw, (g+1)*gw), inside
-// a group row panel by row panel, n fastest — so the gw weight tiles of a group (<= 2 MiB, the host picks gw) stay in the
-// XCD's 4 MB L2 while its row panels stream through, instead of the whole weight matrix being re-fetched for every
-// handful of row panels.  Same time, 35-70 % less L2->fabric traffic on the wide GEMMs (tools/probe/gemm_sched.hip + PMC).
-__device__ __forceinline__ void tile_of_block(int bid, int n_tiles, int tiles_n, int gw, int& tm, int& tn) {
-  {
-    const int q = n_tiles >> 3, r = n_tiles & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int tiles_m = n_tiles / tiles_n, full = tiles_n / gw, span = tiles_m * gw;
-  if (bid < full * span) {
-    const int g = bid / span, j = bid - g * span;
-    tm = j / gw; tn = g * gw + (j - tm * gw);
-  } else {                                        // the last, narrower group
-    const int j = bid - full * span, w = tiles_n - full * gw;
-    tm = j / w; tn = full * gw + (j - tm * w);
-  }
-}
+// XCD-aware, column-group-major tile order: tile_of_block, split_common.h
 
 template <bool GUARD, bool HAS_BIAS, bool HAS_R1, bool HAS_R2, bool RELU>
 __global__ __launch_bounds__(256, 2) void gemm_f32_mfma_kernel(
@@ -721,8 +705,12 @@ LaunchCtx& launch_ctx() {
   static thread_local LaunchCtx ctx;
   return ctx;
 }
+static bool x6_enabled() {
+  static const bool on = env_on("PFHIP_GEMM_X6");
+  return on;
+}
 static bool x3_enabled() {
-  static const bool on = [] { const char* e = getenv("PFHIP_GEMM_X3"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("PFHIP_GEMM_X3");
   return on && !launch_ctx().exact;
 }
 static void launch_split_gemm(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
@@ -749,7 +737,7 @@ void launch_gemm_f32_kind(const float* A, int lda, const float* W, int ldw, floa
   // gemm_x6.hip) — 1.3-1.6 x the fp32 MFMA kernels, results at least as close to fp64 as the fp32 chain.  Its 128 x 128 tile
   // (two blocks per CU) wins on the K = 512 shapes and on every under-filled grid; the 256 x 128 tile on long-K launches that
   // fill the chip (FFN2 at full batch: 201 vs 194 TF).  PFHIP_GEMM_X6=0 turns the path off.
-  static const bool x6_on = [] { const char* e = getenv("PFHIP_GEMM_X6"); return !(e && e[0] == '0'); }();
+  const bool x6_on = x6_enabled();
   const int tiles256 = ((M + 255) / 256) * ((N + kTileN - 1) / kTileN);
   // (tools/gemm_small_probe.py: between 48 and 128 tiles of 128 x 128 the half-height BF16-split kernel beats both the fp32-MFMA
   // 64-row kernel and the 128 x 128 BF16-split kernel by 15-25 % — 1-5 utterances of 30 s, rounds of 25-128 streaming connections)
@@ -785,14 +773,10 @@ void launch_gemm_f32_kind(const float* A, int lda, const float* W, int ldw, floa
   else launch_variant<false>(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, s);
 }
 
-static bool x6_enabled() {
-  static const bool on = [] { const char* e = getenv("PFHIP_GEMM_X6"); return !(e && e[0] == '0'); }();
-  return on;
-}
 // whether the large GEMMs run the fp16 two-plane form (gemm_x3.hip / gemm_p3.hip) — PFHIP_GEMM_X3=0 asks for the bf16 three-plane one
 bool gemm_f16_planes_form() { return x6_enabled() && x3_enabled(); }
 bool gemm_x6_ln_ok(int M) {
-  static const bool ln_on = [] { const char* e = getenv("PFHIP_GEMM_LN"); return !(e && e[0] == '0'); }();
+  static const bool ln_on = env_on("PFHIP_GEMM_LN");
   // from the batch size at which the N = 512 launches (four column tiles per row panel) go to the BF16-split kernels at all
   return ln_on && x6_enabled() && ((M + kTileM - 1) / kTileM) * 4 >= 48;
 }

@@ -24,18 +24,16 @@
 // In the model (pfhip.cpp, batches of 3500+ rows): QKV' <LN, fp32>, out-projection <fp32 + planes + statistics> on the planes the
 // attention writes, FFN1' <LN, planes>, FFN2 <fp32 + planes + statistics>.
 #include "kernels.h"
+#include "launch_common.h"
+#include "split_common.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <atomic>
 
 namespace pfhip {
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
-using float2v = __attribute__((ext_vector_type(2))) float;
 
 constexpr int kPM = 128, kPN = 128, kPK = 16;
 constexpr int kPRowB = 32;                              // bytes of one (row, K-step) of one plane
@@ -46,27 +44,7 @@ constexpr int kPCs = kPN + 4;                           // padded C-tile row str
 constexpr int kPLds = kPM * kPCs * 4 + kPM * 8;         // 68,608 B: the C tile + row statistics (> 4 stages = 65,536 B)
 static_assert(kPRing * kPStage <= kPLds, "the ring must fit");
 
-__device__ __forceinline__ float sub_lo(float x, unsigned h) {      // x - (float)low half of h: one instruction, exact
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float sub_hi(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-// eight consecutive values -> 16 bytes of the hi plane and 16 bytes of the lo plane (hi = rtz, lo = rn(x - hi))
-__device__ __forceinline__ void split8(const float (&v)[8], uint4& hi, uint4& lo) {
-  unsigned* hp = &hi.x;
-  unsigned* lp = &lo.x;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hp[i] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v[2 * i], v[2 * i + 1]));
-    const float2v r = {sub_lo(v[2 * i], hp[i]), sub_hi(v[2 * i + 1], hp[i])};
-    lp[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, half2v));
-  }
-}
+// (sub_lo / sub_hi / split8, tile_of_block, the row statistics hand-off with its range guard, ln_row_stats_raw: split_common.h)
 // byte offset of (row, 8-k piece) inside a plane image with `rows` rows per K-step
 __device__ __forceinline__ size_t image_off(int kstep, int row, int piece, int rows) {
   return ((size_t)kstep * rows + row) * kPRowB + (size_t)((piece ^ ((row >> 3) & 1)) << 4);
@@ -95,76 +73,6 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   const size_t off = image_off(pc >> 1, row, pc & 1, rows);
   *reinterpret_cast<uint4*>(hi + off) = h;
   *reinterpret_cast<uint4*>(lo + off) = l;
-}
-
-__device__ __forceinline__ void tile_of_block_p3(int bid, int n_tiles, int tiles_n, int gw, int& tm, int& tn) {
-  {
-    const int q = n_tiles >> 3, r = n_tiles & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int tiles_m = n_tiles / tiles_n, full = tiles_n / gw, span = tiles_m * gw;
-  if (bid < full * span) {
-    const int g = bid / span, j = bid - g * span;
-    tm = j / gw; tn = g * gw + (j - tm * gw);
-  } else {
-    const int j = bid - full * span, w = tiles_n - full * gw;
-    tm = j / w; tn = full * gw + (j - tm * w);
-  }
-}
-
-__device__ __forceinline__ float half_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-  v += __shfl_xor(v, 16);
-  return v;
-}
-__device__ __forceinline__ void tile_row_stats(const float4& v, int grow, int M, int tn, int tiles_n, int c4, float* __restrict__ stats) {
-  const float sum = half_wave_sum((v.x + v.y) + (v.z + v.w));
-  const float mean = sum * (1.0f / kPN);
-  const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
-  const float q = half_wave_sum((a * a + b * b) + (c * c + d * d));
-  if (c4 == 0 && grow < M) *reinterpret_cast<float2*>(stats + ((size_t)grow * tiles_n + tn) * 2) = make_float2(mean, q);
-}
-// (a row whose centred std leaves [2^-8, 2^11] or whose |mean| / std exceeds kLnOffsetMax raises the forward's range flag: gemm_x3.hip,
-// kernels.h LaunchCtx)
-__device__ __forceinline__ float2 ln_row_stats(const float* __restrict__ stats, int tiles, float eps, int row, int* range_flag) {
-  const float* sp = stats + (size_t)row * tiles * 2;
-  float msum = 0.f, m2 = 0.f;
-  for (int t = 0; t < tiles; ++t) msum += sp[2 * t];
-  const float mean = msum / (float)tiles;
-  for (int t = 0; t < tiles; ++t) { const float dm = sp[2 * t] - mean; m2 += sp[2 * t + 1] + (float)kPN * dm * dm; }
-  const float rstd = 1.0f / sqrtf(m2 / (float)(tiles * kPN) + eps);
-  if (range_flag && ln_row_out_of_domain(mean, rstd)) atomicOr(range_flag, 2);
-  return make_float2(mean, rstd);
-}
-// The same for T tiles (4: d_model = 512; 16: the decoder's LayerNorm over the 2048 hidden channels) from the row's 8 T bytes fetched as
-// T / 2 16-byte loads — requested at kernel entry and first used behind the prologue's DMA issue.  The loop above fetches one value per
-// trip with a wait in each: 2 T dependent round trips, 4,000 cycles (T = 4) in front of the first DMA of a 56,000-cycle workgroup
-// (in-kernel stamps, tools/p3_stamps.py).  Same operations in the same order: bit-identical.
-template <int T>
-struct LnRaw { float4 v[T / 2]; };
-template <int T>
-__device__ __forceinline__ void ln_raw_load(LnRaw<T>& r, const float* __restrict__ stats, int row) {
-  const float4* sp = reinterpret_cast<const float4*>(stats + (size_t)row * T * 2);
-#pragma unroll
-  for (int i = 0; i < T / 2; ++i) r.v[i] = sp[i];
-}
-template <int T>
-__device__ __forceinline__ float2 ln_row_stats_raw(const LnRaw<T>& r, float eps, int* range_flag) {
-  float msum = 0.f, m2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < T / 2; ++i) { msum += r.v[i].x; msum += r.v[i].z; }
-  const float mean = msum / (float)T;
-#pragma unroll
-  for (int i = 0; i < T / 2; ++i) {
-    { const float dm = r.v[i].x - mean; m2 += r.v[i].y + (float)kPN * dm * dm; }
-    { const float dm = r.v[i].z - mean; m2 += r.v[i].w + (float)kPN * dm * dm; }
-  }
-  const float rstd = 1.0f / sqrtf(m2 / (float)(T * kPN) + eps);
-  if (range_flag && ln_row_out_of_domain(mean, rstd)) atomicOr(range_flag, 2);
-  return make_float2(mean, rstd);
 }
 
 // Epilogue of a tile that leaves as ROW-MAJOR planes (OUT & 4: the K | V columns of the QKV projection, read by attention_p3.hip): thread =
@@ -217,7 +125,7 @@ __global__ __launch_bounds__(kPThreads, 2) void gemm_p3_128_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_p3(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kPM, n0 = tn * kPN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -540,7 +448,7 @@ __global__ __launch_bounds__(kQThreads, 2) void gemm_p3_256_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_p3(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kQM, n0 = tn * kPN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;                 // 4 x 2 waves of 64 x 64
@@ -831,7 +739,7 @@ __global__ __launch_bounds__(kPThreads, 3) void gemm_p3_64_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_p3(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kHM, n0 = tn * kPN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -956,7 +864,7 @@ __global__ __launch_bounds__(kPThreads, 3) void gemm_p3_128r3_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_p3(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kPM, n0 = tn * kPN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -1144,7 +1052,7 @@ __global__ __launch_bounds__(kWThreads) void gemm_p3_256x256_kernel(
   int d_tile = blockIdx.x, d_ks = 0;
   auto dma_tile = [&](int t) {
     int tm_, tn_;
-    tile_of_block_p3(t, n_tiles, tiles_n, gw, tm_, tn_);
+    tile_of_block(t, n_tiles, tiles_n, gw, tm_, tn_);
     off_a = (size_t)min(tm_ * kWM + 32 * wave, rows_a - 32) * kPRowB;
     off_w = (size_t)(tn_ * kWN + 32 * wave) * kPRowB;
   };
@@ -1172,7 +1080,7 @@ __global__ __launch_bounds__(kWThreads) void gemm_p3_256x256_kernel(
   float2* const s_mr = reinterpret_cast<float2*>(lds + kWMrOff);
   float* const s_col = reinterpret_cast<float*>(lds + kWColOff);
   int tile = blockIdx.x, tm, tn;
-  tile_of_block_p3(tile, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(tile, n_tiles, tiles_n, gw, tm, tn);
   LnRaw<4> ls4;      // the row's statistics (d_model = 512: four tiles), requested a loop or an epilogue ahead of their use
   if (LN && tid < kWM && ln_tiles == 4) ln_raw_load(ls4, ln_stats, min(tm * kWM + tid, M - 1));
 
@@ -1270,7 +1178,7 @@ __global__ __launch_bounds__(kWThreads) void gemm_p3_256x256_kernel(
     const int next = tile + G;
     int tm_n = tm, tn_n = tn;
     if (next < n_tiles) {
-      tile_of_block_p3(next, n_tiles, tiles_n, gw, tm_n, tn_n);
+      tile_of_block(next, n_tiles, tiles_n, gw, tm_n, tn_n);
       if (LN && tid < kWM && ln_tiles == 4) ln_raw_load(ls4, ln_stats, min(tm_n * kWM + tid, M - 1));
     }
 #ifdef PFHIP_P3_STAMPS
@@ -1367,18 +1275,6 @@ __global__ __launch_bounds__(kWThreads) void gemm_p3_256x256_kernel(
 #undef PFHIP_WSTAMP
 }
 
-template <auto kern, int threads = kPThreads, class... Args>
-void launch_with_lds(int n_tiles, int lds_bytes, hipStream_t s, Args... args) {
-  static std::atomic<unsigned long long> attr_done{0};      // > 64 KB of dynamic LDS needs the opt-in once per kernel and device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(threads), lds_bytes, s, args...);
-}
-
 }  // namespace
 
 size_t plane_image_bytes(int rows, int K) { return (size_t)((rows + 127) / 128 * 128) * (size_t)K * 2; }
@@ -1404,6 +1300,16 @@ int cu_count() {
   }
   return n;
 }
+// PFHIP_P3_HALF_TILES: the tile count of 128-row tiles up to which the 64-row tile is taken (and above which the 256 x 256 tile may be)
+int half_tiles_limit() {
+  static const int lim = env_int("PFHIP_P3_HALF_TILES", 400);
+  return lim;
+}
+// PFHIP_P3_TILE256, first character: '0' keeps the 128-row kernel, '2' takes the 256-row tile wherever it fills the chip (0 when unset)
+char tile256_knob() {
+  static const char c = [] { const char* e = getenv("PFHIP_P3_TILE256"); return e ? e[0] : '\0'; }();
+  return c;
+}
 }  // namespace
 long gemm_p3_wide_launches() { return g_wide_launches.load(std::memory_order_relaxed); }
 bool gemm_p3_wide_serves(bool c, bool planes, bool r1, bool ln, bool stats_out, int row_planes_from, int N, int K) {
@@ -1428,9 +1334,8 @@ void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, 
   {
     const bool serves = gemm_p3_wide_serves(C != nullptr, Ph != nullptr, R1 != nullptr, ln_stats != nullptr, stats_out != nullptr, row_planes_from, N, K);
     const int nw = ((M + kWM - 1) / kWM) * (N / kWN), cus = cu_count(), rounds = (nw + cus - 1) / cus;
-    const char* e = getenv("PFHIP_P3_WIDE");
-    const bool w_env = !(e && e[0] == '0');
-    static const int half_lim = [] { const char* h = getenv("PFHIP_P3_HALF_TILES"); return h && *h ? atoi(h) : 400; }();
+    const bool w_env = env_on("PFHIP_P3_WIDE");
+    const int half_lim = half_tiles_limit();
     const bool by_rule = tile_cols == 0 && tile_rows == 0 && w_env && serves && ln_tiles == 4 && K >= 256 && rows_a >= kWM && nw > cus &&
                          ((M + kPM - 1) / kPM) * ((N + kPN - 1) / kPN) > half_lim && 100 * nw >= 85 * cus * rounds;
     if (serves && (tile_cols == kWN || by_rule)) {
@@ -1452,17 +1357,17 @@ void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, 
   }
   const int tiles_n = (N + kPN - 1) / kPN;
   // 64-row tiles (three workgroups per CU) when 128-row tiles would leave most of a round of 512 slots empty
-  static const int half_env = [] { const char* e = getenv("PFHIP_P3_HALF_TILES"); return e && *e ? atoi(e) : 400; }();
+  const int half_env = half_tiles_limit();
   const bool half = tile_rows == kHM || (tile_rows != kPM && tile_rows != kQM && ((M + kPM - 1) / kPM) * tiles_n <= half_env);
   // 256-row tiles (one eight-wave workgroup per CU) where they fill the chip: at least 85 % of the CU slots of their rounds
   // (32 x 30 s: 252 / 756 / 1008 tiles for N = 512 / 1536 / 2048); PFHIP_P3_TILE256=0 keeps the 128-row kernel
-  static const bool q_env = [] { const char* e = getenv("PFHIP_P3_TILE256"); return !(e && e[0] == '0'); }();
+  const bool q_env = tile256_knob() != '0';
   const int nq = ((M + kQM - 1) / kQM) * tiles_n;
   // Measured (tools/p3_probe.py, 16000 rows, two runs, 256-row tile against 128-row tile): FFN2 (K = 2048) 108.4 / 108.6 against
   // 110.7 / 111.3 us, QKV 98.0 / 96.3 against 97.9 / 100.3, FFN1 129.7 / 129.8 against 126.6 / 127.3, out-projection 51.8 / 50.3
   // against 47.5 / 47.1: what the loop gains from 0.75 x the bytes the single workgroup loses in its epilogue, which no second
   // workgroup covers.  Taken where the loop is long (K >= 1024); PFHIP_P3_TILE256=2 takes it wherever it fills the chip.
-  static const bool q_all = [] { const char* e = getenv("PFHIP_P3_TILE256"); return e && e[0] == '2'; }();
+  const bool q_all = tile256_knob() == '2';
   const bool quad = row_planes_from <= 0 && (tile_rows == kQM || (tile_rows == 0 && q_env && !half && rows_a >= kQM && (K >= 1024 || q_all) &&
                                          100 * nq >= 85 * 256 * ((nq + 255) / 256)));
   // the three-stage 128-row kernel (three workgroups per CU) for grids of more than two rounds of its 768 slots.  Measured
@@ -1470,11 +1375,11 @@ void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, 
   // kernel, QKV' (1500 tiles) 100.2 / 99.0 against 98.3 / 96.3, out-projection (500) level — a third workgroup per CU does not lift the
   // loop (it is the CU's operand path that is busy), it only smooths the rounds of a long grid.  PFHIP_P3_R3=0 / 1:
   // never / wherever the 128-row tile is taken.
-  const int r3_env = [] { const char* e = getenv("PFHIP_P3_R3"); return e && *e ? atoi(e) : -1; }();      // (read per launch: tests switch it)
+  const int r3_env = env_int("PFHIP_P3_R3", -1);      // (read per launch: tests switch it)
   const bool ring3 = !quad && !half && (r3_env == 1 || (r3_env != 0 && ((M + kPM - 1) / kPM) * tiles_n > 1536));
   const int tmr = quad ? kQM : (half ? kHM : kPM);
   const int n_tiles = ((M + tmr - 1) / tmr) * tiles_n;
-  static const int gw_env = [] { const char* e = getenv("PFHIP_P3_GW"); return e && *e ? atoi(e) : 0; }();      // experiments
+  static const int gw_env = env_int("PFHIP_P3_GW", 0);      // experiments
 
   if (gw_env > 0) gw = gw_env;
   gw = std::max(1, std::min(gw, tiles_n));
@@ -1489,23 +1394,23 @@ void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, 
       launch_with_lds<gemm_p3_256_kernel<LNF, OUTM>, kQThreads>(n_tiles, kQLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
                                                     M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
     else if (half)                                                                                                              \
-      launch_with_lds<gemm_p3_64_kernel<LNF, OUTM>>(n_tiles, kHLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
+      launch_with_lds<gemm_p3_64_kernel<LNF, OUTM>, kPThreads>(n_tiles, kHLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
                                                     M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
     else if (ring3)                                                                                                             \
-      launch_with_lds<gemm_p3_128r3_kernel<LNF, OUTM>>(n_tiles, kP3Lds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
+      launch_with_lds<gemm_p3_128r3_kernel<LNF, OUTM>, kPThreads>(n_tiles, kP3Lds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
                                                      M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
     else                                                                                                                        \
-      launch_with_lds<gemm_p3_128_kernel<LNF, OUTM>>(n_tiles, kPLds + PFHIP_P3_LDS_PAD, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
+      launch_with_lds<gemm_p3_128_kernel<LNF, OUTM>, kPThreads>(n_tiles, kPLds + PFHIP_P3_LDS_PAD, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
                                                      M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
   }
   if (row_planes_from > 0) {      // the QKV projection: fp32 Q | row-major K, V planes (C and Ph both given)
 #define PFHIP_P3S(LNF)                                                                                                          \
   {                                                                                                                             \
     if (half)                                                                                                                   \
-      launch_with_lds<gemm_p3_64_kernel<LNF, 5>>(n_tiles, kHLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
+      launch_with_lds<gemm_p3_64_kernel<LNF, 5>, kPThreads>(n_tiles, kHLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
                                                  M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
     else                                                                                                                        \
-      launch_with_lds<gemm_p3_128_kernel<LNF, 5>>(n_tiles, kPLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
+      launch_with_lds<gemm_p3_128_kernel<LNF, 5>, kPThreads>(n_tiles, kPLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
                                                   M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
   }
     if (ln_stats) PFHIP_P3S(true) else PFHIP_P3S(false)

@@ -2,9 +2,7 @@
 //
 // gemm_x6.hip splits an fp32 operand EXACTLY into three bf16 planes (8 + 8 + 8 significand bits) and needs six bf16 MFMAs per
 // 32x32x16 block (ceiling 2.5 PF / 6 = 417 TFLOP/s).  fp16 has 11 significand bits, so TWO planes carry 22-23 of fp32's 24:
-//     x * S = x1 + x2 + e,   x1 = fp16_rtz(x * S),   x2 = fp16_rtz(x * S - x1)   (the subtraction is exact in fp32),
-//     |e| <= max(2^-22 |x1|, 2^-24)     (S a power of two; the second bound is fp16's subnormal spacing — the matrix cores keep
-//                                        subnormal fp16 operands, tools/probe/f16_split_probe.hip)
+//     x * S = x1 + x2 + e,   |e| <= max(2^-22 |x1|, 2^-24)     (the split and its error bound: split_common.h)
 // and a * b = a1 b1 + (a1 b2 + a2 b1) + [a2 b2 ~ 2^-22 |ab|, dropped]: THREE `v_mfma_f32_32x32x16_f16` per block, fp32
 // accumulation in the matrix core, a ceiling of 2.5 PF / 3 = 833 TFLOP/s of fp32-equivalent work.  The representation error of
 // the operands (rms ~2^-24 relative, unbiased to first order across a row) is BELOW the rounding an fp32 accumulation chain of
@@ -28,6 +26,8 @@
 // operands split while staged, LDS double-buffered, one hand-made barrier per K-step; LayerNorm folded in through the row
 // statistics hand-off) with two planes instead of three: per K-step and wave 12 / 6 / 3 MFMAs, 8 / 6 / 4 fragment reads.
 #include "kernels.h"
+#include "launch_common.h"
+#include "split_common.h"
 
 // Timing-only ablations of the K-step (tools/x3_ablate.sh builds one library per value; results are WRONG for any value but 0):
 //   1 no s_barrier   2 no split / LDS writes   3 no fragment reads   4 no global loads   5 MFMAs only (2 + 3 + 4, barrier kept)
@@ -46,15 +46,11 @@
 #define PFHIP_X3_DO_LOAD (PFHIP_X3_ABLATE != 4 && PFHIP_X3_ABLATE != 5)
 
 #include <algorithm>
-#include <atomic>
 
 namespace pfhip {
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
-using float2v = __attribute__((ext_vector_type(2))) float;
 
 constexpr int kBM = 256, kBN = 128, kBK = 16;
 constexpr int kRowB = 48;                                   // bytes per operand row in LDS (16 bf16 + pad)
@@ -65,18 +61,6 @@ constexpr int kRing = 3;                                    // LDS stages: the o
 constexpr int kLdsBytes = kRing * kStageB;                  // 110,592 B
 static_assert(128 * kCs * 4 <= kLdsBytes, "half C tile must fit the operand buffers");
 
-// x - (float)h for the low / high half of a packed fp16 pair, ONE instruction each (v_fma_mix_f32 reads an fp16 source in
-// place: fma(h, -1.0, x)); exact, because h has at most 11 of x's 24 significant bits and the same exponent or the one below
-__device__ __forceinline__ float sub_lo(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float sub_hi(float x, unsigned h) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
-  return r;
-}
 // two fp16 planes of v (* scale) for four consecutive k: hi = rtz(x), lo = rn(x - hi); the round-toward-zero conversion of hi
 // saturates instead of producing Inf.  8 vector instructions per float4 (12 scaled) against 22 for the three bf16 planes of gemm_x6.hip.
 template <bool SC>
@@ -118,66 +102,7 @@ __device__ __forceinline__ void split_lo(unsigned char* dst, const SplitTmp& t) 
                                               __builtin_bit_cast(unsigned, __builtin_convertvector(r23, half2v)));
 }
 
-// XCD-aware, column-group-major tile order (same scheme as gemm.hip's tile_of_block)
-__device__ __forceinline__ void tile_of_block_x3(int bid, int n_tiles, int tiles_n, int gw, int& tm, int& tn) {
-  {
-    const int q = n_tiles >> 3, r = n_tiles & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int tiles_m = n_tiles / tiles_n, full = tiles_n / gw, span = tiles_m * gw;
-  if (bid < full * span) {
-    const int g = bid / span, j = bid - g * span;
-    tm = j / gw; tn = g * gw + (j - tm * gw);
-  } else {
-    const int j = bid - full * span, w = tiles_n - full * gw;
-    tm = j / w; tn = full * gw + (j - tm * w);
-  }
-}
-
-// LayerNorm statistics of the rows this tile just finished, for the GEMM that consumes them (LN-on-load below): the 32 lanes
-// that hold one row's 128 columns reduce (mean of the tile's columns, M2 = sum of squared deviations from THAT mean) and lane 0
-// writes the pair to stats[row][tile column][2].  The consumer merges the tiles_n pairs of a row with Chan's formula — as
-// accurate as a two-pass LayerNorm, no atomics, no ordering between tiles.
-// sum over the 32 lanes of a half wave, result in every lane: four DPP steps inside the 16-lane rows (quad swaps, half-row
-// mirror, row mirror — vector-ALU speed) and ONE cross-row shuffle; five ds_bpermute round trips per sum cost the epilogue
-// ~2 us per tile
-__device__ __forceinline__ float half_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-  v += __shfl_xor(v, 16);
-  return v;
-}
-__device__ __forceinline__ void tile_row_stats(const float4& v, int grow, int M, int tn, int tiles_n, int c4, float* __restrict__ stats) {
-  const float sum = half_wave_sum((v.x + v.y) + (v.z + v.w));
-  const float mean = sum * (1.0f / kBN);
-  const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
-  const float q = half_wave_sum((a * a + b * b) + (c * c + d * d));
-  if (c4 == 0 && grow < M) *reinterpret_cast<float2*>(stats + ((size_t)grow * tiles_n + tn) * 2) = make_float2(mean, q);
-}
-
-// the consumer's half.  Row statistics merged from the producer's per-tile pairs (Chan: n = 128 per tile) — one thread per row,
-// at kernel start, parked in registers under the K-loop and published through LDS for the epilogue passes ...
-// A row whose centred standard deviation lies outside [2^-8, 2^11], whose offset |mean| / std exceeds kLnOffsetMax (the fold below
-// cancels: kernels.h) or whose statistics are not finite is outside the domain the fold on two fp16 planes of the raw residual
-// stream covers at fp32 grade: the forward's range flag is raised (kernels.h LaunchCtx) and the host redoes the batch unfolded on
-// the bf16 three-plane kernels.
-__device__ __forceinline__ float2 ln_row_stats(const float* __restrict__ stats, int tiles, float eps, int row, int* range_flag) {
-  const float* sp = stats + (size_t)row * tiles * 2;
-  float msum = 0.f, m2 = 0.f;
-  for (int t = 0; t < tiles; ++t) msum += sp[2 * t];
-  const float mean = msum / (float)tiles;
-  for (int t = 0; t < tiles; ++t) { const float dm = sp[2 * t] - mean; m2 += sp[2 * t + 1] + (float)kBN * dm * dm; }
-  const float rstd = 1.0f / sqrtf(m2 / (float)(tiles * kBN) + eps);
-  if (range_flag && ln_row_out_of_domain(mean, rstd)) atomicOr(range_flag, 2);
-  return make_float2(mean, rstd);
-}
-// ... where v (four columns of x W'^T) becomes rstd * (v - mean * colsum)
-__device__ __forceinline__ void ln_finish(float4& v, const float4& cs, float2 mr) {
-  v.x = mr.y * (v.x - mr.x * cs.x); v.y = mr.y * (v.y - mr.x * cs.y);
-  v.z = mr.y * (v.z - mr.x * cs.z); v.w = mr.y * (v.w - mr.x * cs.w);
-}
+// tile order, row statistics hand-off (tile_row_stats / ln_row_stats / ln_finish): split_common.h
 
 template <bool SC>
 __global__ __launch_bounds__(512, 1) void gemm_f32_f16x3_kernel(
@@ -187,7 +112,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f32_f16x3_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_x3(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kBM, n0 = tn * kBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -409,7 +334,7 @@ __global__ __launch_bounds__(512, 4) void gemm_f32_f16x3_128_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_x3(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kSM, n0 = tn * kBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
@@ -612,7 +537,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_f16x3_64_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_x3(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kHM, n0 = tn * kBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
@@ -778,21 +703,6 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_f16x3_64_kernel(
   }
 }
 
-}  // namespace
-
-namespace {
-template <auto kern, class... Args>
-void launch_with_lds(int n_tiles, int lds_bytes, hipStream_t s, Args... args) {
-  // > 64 KB of dynamic LDS needs the opt-in once per kernel (= per instantiation of this function) and device
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(512), lds_bytes, s, args...);
-}
 }  // namespace
 
 void launch_gemm_f32_f16x3(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,

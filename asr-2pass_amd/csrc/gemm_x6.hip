@@ -25,9 +25,10 @@
 // what is left.  Per K-step a wave issues 12 ds_read_b128 for 24 MFMAs.
 // Epilogue as in gemm.hip: accumulators transposed through LDS (two 128-row halves), rows written with 16-byte accesses.
 #include "kernels.h"
+#include "launch_common.h"
+#include "split_common.h"
 
 #include <algorithm>
-#include <atomic>
 
 namespace pfhip {
 namespace {
@@ -50,60 +51,8 @@ __device__ __forceinline__ float rest(float x) {                           // x 
   return x - __uint_as_float(__float_as_uint(x) & 0xFFFF0000u);
 }
 
-// XCD-aware, column-group-major tile order (same scheme as gemm.hip's tile_of_block)
-__device__ __forceinline__ void tile_of_block_x6(int bid, int n_tiles, int tiles_n, int gw, int& tm, int& tn) {
-  {
-    const int q = n_tiles >> 3, r = n_tiles & 7, xcd = bid & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int tiles_m = n_tiles / tiles_n, full = tiles_n / gw, span = tiles_m * gw;
-  if (bid < full * span) {
-    const int g = bid / span, j = bid - g * span;
-    tm = j / gw; tn = g * gw + (j - tm * gw);
-  } else {
-    const int j = bid - full * span, w = tiles_n - full * gw;
-    tm = j / w; tn = full * gw + (j - tm * w);
-  }
-}
-
-// LayerNorm statistics of the rows this tile just finished, for the GEMM that consumes them (LN-on-load below): the 32 lanes
-// that hold one row's 128 columns reduce (mean of the tile's columns, M2 = sum of squared deviations from THAT mean) and lane 0
-// writes the pair to stats[row][tile column][2].  The consumer merges the tiles_n pairs of a row with Chan's formula — as
-// accurate as a two-pass LayerNorm, no atomics, no ordering between tiles.
-// sum over the 32 lanes of a half wave, result in every lane: four DPP steps inside the 16-lane rows (quad swaps, half-row
-// mirror, row mirror — vector-ALU speed) and ONE cross-row shuffle; five ds_bpermute round trips per sum cost the epilogue
-// ~2 us per tile
-__device__ __forceinline__ float half_wave_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));   // row_mirror
-  v += __shfl_xor(v, 16);
-  return v;
-}
-__device__ __forceinline__ void tile_row_stats(const float4& v, int grow, int M, int tn, int tiles_n, int c4, float* __restrict__ stats) {
-  const float sum = half_wave_sum((v.x + v.y) + (v.z + v.w));
-  const float mean = sum * (1.0f / kBN);
-  const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
-  const float q = half_wave_sum((a * a + b * b) + (c * c + d * d));
-  if (c4 == 0 && grow < M) *reinterpret_cast<float2*>(stats + ((size_t)grow * tiles_n + tn) * 2) = make_float2(mean, q);
-}
-
-// the consumer's half.  Row statistics merged from the producer's per-tile pairs (Chan: n = 128 per tile) — one thread per row,
-// at kernel start, parked in registers under the K-loop and published through LDS for the epilogue passes ...
-__device__ __forceinline__ float2 ln_row_stats(const float* __restrict__ stats, int tiles, float eps, int row) {
-  const float* sp = stats + (size_t)row * tiles * 2;
-  float msum = 0.f, m2 = 0.f;
-  for (int t = 0; t < tiles; ++t) msum += sp[2 * t];
-  const float mean = msum / (float)tiles;
-  for (int t = 0; t < tiles; ++t) { const float dm = sp[2 * t] - mean; m2 += sp[2 * t + 1] + (float)kBN * dm * dm; }
-  return make_float2(mean, 1.0f / sqrtf(m2 / (float)(tiles * kBN) + eps));
-}
-// ... where v (four columns of x W'^T) becomes rstd * (v - mean * colsum)
-__device__ __forceinline__ void ln_finish(float4& v, const float4& cs, float2 mr) {
-  v.x = mr.y * (v.x - mr.x * cs.x); v.y = mr.y * (v.y - mr.x * cs.y);
-  v.z = mr.y * (v.z - mr.x * cs.z); v.w = mr.y * (v.w - mr.x * cs.w);
-}
+// tile order, row statistics hand-off (tile_row_stats / ln_row_stats / ln_finish): split_common.h; the bf16 split is exact over
+// fp32's whole range, so these kernels pass no range flag to ln_row_stats
 
 __global__ __launch_bounds__(512, 1) void gemm_f32_bf16x6_kernel(
     const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw, float* C, int ldc,
@@ -112,7 +61,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f32_bf16x6_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_x6(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kBM, n0 = tn * kBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -307,7 +256,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_bf16x6_128_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_x6(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kSM, n0 = tn * kBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
@@ -328,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_bf16x6_128_kernel(
   // subtraction amplifies the accumulation error by about sqrt(mean^2 + var) / std of the row — a small factor for a residual
   // stream — where normalising on load did not, but on-load cost the 4-waves-per-SIMD loop 4 % (8 VALU ops per K-step).
   float2 ln_mr = make_float2(0.f, 1.f);
-  if (LN && tid < kSM) ln_mr = ln_row_stats(ln_stats, ln_tiles, ln_eps, min(m0 + tid, M - 1));
+  if (LN && tid < kSM) ln_mr = ln_row_stats(ln_stats, ln_tiles, ln_eps, min(m0 + tid, M - 1), nullptr);
   float4 xa, xw, ya, yw;
 #define PFHIP_LOAD_RAW(RA, RW, k0)                            \
   RA = *reinterpret_cast<const float4*>(Ag + (k0));           \
@@ -493,7 +442,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_bf16x6_64_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   int tm, tn;
-  tile_of_block_x6(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
+  tile_of_block(blockIdx.x, n_tiles, tiles_n, gw, tm, tn);
   const int m0 = tm * kHM, n0 = tn * kBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
@@ -509,7 +458,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_bf16x6_64_kernel(
   const int w_fr = 3 * kHPlaneA + (wc * 32 + r) * kRowB + 16 * h;
 
   float2 ln_mr = make_float2(0.f, 1.f);
-  if (LN && tid < kHM) ln_mr = ln_row_stats(ln_stats, ln_tiles, ln_eps, min(m0 + tid, M - 1));
+  if (LN && tid < kHM) ln_mr = ln_row_stats(ln_stats, ln_tiles, ln_eps, min(m0 + tid, M - 1), nullptr);
   float4 xa = make_float4(0.f, 0.f, 0.f, 0.f), xw, ya = xa, yw;
 #define PFHIP_LOAD_RAW(RA, RW, k0)                                           \
   if (stage_a) RA = *reinterpret_cast<const float4*>(Ag + (k0));             \
@@ -643,31 +592,14 @@ void launch_gemm_f32_bf16x6(const float* A, int lda, const float* W, int ldw, fl
                             const float* ln_stats, int ln_tiles, float* stats_out, bool half_tile, const float* ln_colsum) {
   if (M <= 0 || N <= 0) return;
   if (ln_stats) small_tile = true;              // LayerNorm-on-load lives in the 128 / 64-row kernels (its consumers have K = 512)
-  // > 64 KB of dynamic LDS needs the opt-in once per device
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_bf16x6_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_bf16x6_128_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kSLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_bf16x6_128_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kSLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_bf16x6_64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kHLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f32_bf16x6_64_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kHLdsBytes);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
   if (small_tile && half_tile) {
     const int tiles_m = (M + kHM - 1) / kHM, tiles_n = (N + kBN - 1) / kBN, n_tiles = tiles_m * tiles_n;
     gw = std::max(1, std::min(gw, tiles_n));
     if (ln_stats)
-      hipLaunchKernelGGL(gemm_f32_bf16x6_64_kernel<true>, dim3(n_tiles), dim3(512), kHLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
+      launch_with_lds<gemm_f32_bf16x6_64_kernel<true>>(n_tiles, kHLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
                          R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
     else
-      hipLaunchKernelGGL(gemm_f32_bf16x6_64_kernel<false>, dim3(n_tiles), dim3(512), kHLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
+      launch_with_lds<gemm_f32_bf16x6_64_kernel<false>>(n_tiles, kHLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
                          R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
     return;
   }
@@ -675,16 +607,16 @@ void launch_gemm_f32_bf16x6(const float* A, int lda, const float* W, int ldw, fl
     const int tiles_m = (M + kSM - 1) / kSM, tiles_n = (N + kBN - 1) / kBN, n_tiles = tiles_m * tiles_n;
     gw = std::max(1, std::min(gw, tiles_n));
     if (ln_stats)
-      hipLaunchKernelGGL(gemm_f32_bf16x6_128_kernel<true>, dim3(n_tiles), dim3(512), kSLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
+      launch_with_lds<gemm_f32_bf16x6_128_kernel<true>>(n_tiles, kSLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
                          R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
     else
-      hipLaunchKernelGGL(gemm_f32_bf16x6_128_kernel<false>, dim3(n_tiles), dim3(512), kSLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
+      launch_with_lds<gemm_f32_bf16x6_128_kernel<false>>(n_tiles, kSLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
                          R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
     return;
   }
   const int tiles_m = (M + kBM - 1) / kBM, tiles_n = (N + kBN - 1) / kBN, n_tiles = tiles_m * tiles_n;
   gw = std::max(1, std::min(gw, tiles_n));
-  hipLaunchKernelGGL(gemm_f32_bf16x6_kernel, dim3(n_tiles), dim3(512), kLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2,
+  launch_with_lds<gemm_f32_bf16x6_kernel>(n_tiles, kLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2,
                      ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, stats_out);
 }
 

@@ -26,6 +26,7 @@
 #include <thread>
 
 #include "internal.h"
+#include "launch_common.h"
 
 using namespace pfhip_detail;
 
@@ -267,9 +268,9 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   float* x = m->x.f();
   // One connection, one window: the latency path.  Launch count, not bytes or flops, sets its time (stream_fused.hip), so
   // row-wise operators are folded into the GEMMs that consume them.  PFHIP_STREAM_FUSED=0 keeps the general path.
-  static const bool fused_on = [] { const char* e = getenv("PFHIP_STREAM_FUSED"); return !(e && e[0] == '0'); }();
+  static const bool fused_on = pfhip::env_on("PFHIP_STREAM_FUSED");
   const bool lean = fused_on && B == 1 && M <= 32;
-  static const bool att_out_on = [] { const char* e = getenv("PFHIP_STREAM_ATT_OUT"); return e && e[0] == '1'; }();
+  static const bool att_out_on = pfhip::env_is1("PFHIP_STREAM_ATT_OUT");
   auto ln_gemm = [&](const float* X, int ldx, int D, const std::string& norm, const float* Wd, int ldw, float* Cd, int ldc,
                      const float* bias, const float* R1, int ldr1, const float* R2, int ldr2, const float* fv, int ldv,
                      const float* fw, int rows, int N, int K, bool relu) {
@@ -376,7 +377,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   pfhip::launch_cif_stream(m->enc.f(), d, m->alphas.f(), d_segs, B, c.cif_threshold, c.tail_threshold, m->emb.f(), kMaxTok,
                            m->counts.i(), d, st);
   HIP_TRY(hipMemcpyAsync(m->h_counts, m->counts.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-  static const bool timing = [] { const char* e = getenv("PFHIP_STREAM_TIMING"); return e && e[0] == '1'; }();
+  static const bool timing = pfhip::env_is1("PFHIP_STREAM_TIMING");
   const auto t_sync0 = std::chrono::steady_clock::now();
   HIP_TRY(hipStreamSynchronize(st));
   if (timing) {

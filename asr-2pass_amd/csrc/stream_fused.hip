@@ -16,6 +16,7 @@
 //       and window_attention_kernel for the 20 x 20 attention between them.
 // All kernels take M <= 32 rows (one window of the [5,10,5] chunking is 20).
 #include "kernels.h"
+#include "launch_common.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -718,7 +719,7 @@ void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const 
   // (N = 512 at K = 2048: 2 columns -> 256 workgroups and ONE k-block per wave instead of two: three dependent round trips to L2
   // per lane instead of six)
   const int cw = N <= 640 ? (K >= 1024 ? 2 : 4) : (N <= 4096 ? 8 : 32);
-  static const bool use_mfma = [] { const char* e = getenv("PFHIP_STREAM_FUSED_MFMA"); return e && e[0] == '1'; }();
+  static const bool use_mfma = env_is1("PFHIP_STREAM_FUSED_MFMA");
   if (!use_mfma && K % 64 == 0 && N <= 4096) {
     if (g) {
       if (cw == 2) launch_gemv<true, 2>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
@@ -753,7 +754,7 @@ void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const 
 bool launch_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, float* C, int ldc, const float* bias, const float* ln_colsum,
                              float eps, const float* R1, int ldr1, const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K,
                              bool relu, hipStream_t s) {
-  static const bool on = [] { const char* e = getenv("PFHIP_STREAM_1TRIP"); return !(e && e[0] == '0'); }();
+  static const bool on = env_on("PFHIP_STREAM_1TRIP");
   if (!on || M <= 0 || M > 20 || N <= 0 || (fsmn_v && ln_colsum)) return false;
   // patch width as in launch_fused_ln_gemm; rows over 4 lane groups; a wave per k-block: K = waves * KS * 4 NF
   static const int cpl = [] { const char* e = getenv("PFHIP_1T_CPL"); return e ? atoi(e) : 2; }();     // columns per lane (measured: 2 beats 1 and 4 on every window shape)
@@ -792,10 +793,13 @@ bool launch_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, f
 
 // window_attention_kernel: false when the shape is outside what it takes (the caller uses launch_attention).
 // PFHIP_STREAM_WATT=0 turns it off.
+static bool window_attention_on() {
+  static const bool on = env_on("PFHIP_STREAM_WATT");
+  return on;
+}
 bool launch_window_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
                              int H, float scale, hipStream_t s, int head_dim) {
-  static const bool on = [] { const char* e = getenv("PFHIP_STREAM_WATT"); return !(e && e[0] == '0'); }();
-  if (!on || Lq < 1 || Lq > 32 || Lk < 1 || Lk > 32 || H < 1 || (head_dim != 128 && head_dim != 80)) return false;
+  if (!window_attention_on() || Lq < 1 || Lq > 32 || Lk < 1 || Lk > 32 || H < 1 || (head_dim != 128 && head_dim != 80)) return false;
   if (head_dim == 80)
     hipLaunchKernelGGL(window_attention_kernel<80>, dim3(H), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk,
                        scale * 1.4426950408889634f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
@@ -811,8 +815,7 @@ bool launch_window_attention_segments(const float* Q, int ldq, const float* K, i
                                       const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                                       int max_q_len, int max_kv_len, float scale, hipStream_t s, const float* fsmn_w, float* mem,
                                       int ldmem, int head_dim) {
-  static const bool on = [] { const char* e = getenv("PFHIP_STREAM_WATT"); return !(e && e[0] == '0'); }();
-  if (!on || B < 1 || H < 1 || max_q_len < 1 || max_q_len > 32 || max_kv_len < 1 || max_kv_len > 32 || (head_dim != 128 && head_dim != 80))
+  if (!window_attention_on() || B < 1 || H < 1 || max_q_len < 1 || max_q_len > 32 || max_kv_len < 1 || max_kv_len > 32 || (head_dim != 128 && head_dim != 80))
     return false;
   if (head_dim == 80)
     hipLaunchKernelGGL(window_attention_kernel<80>, dim3(H, B), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, 0, 0,

@@ -732,3 +732,33 @@ def test_fused_attention_and_projection(ops, Lq, Lk, fsmn):
     assert not out[Lq:].any()
     with pytest.raises(Exception):
         ops.fused_att_out(t[:, :d], t[:, d:2 * d], t[:, 2 * d:], 21, 20, H, 1.0, dev(W))
+
+
+def _integer_epilogue_case(M, N, K, seed):
+    """Integer-valued operands for test_split_gemm_epilogue_exact_on_integers and the int64 reference of
+    relu(A W^T + bias + R1 + R2).  |A W^T| <= 16 K <= 1024 and the three addends are <= 64 each: every partial sum is an integer
+    far below 2^24 (exact in the fp32 accumulator) and every operand has at most 3 significant bits (one fp16 / bf16 plane)."""
+    rng = np.random.default_rng(seed)
+    A = rng.integers(-4, 5, (M, K))
+    W = rng.integers(-4, 5, (N, K))
+    bias, R1, R2 = rng.integers(-64, 65, N), rng.integers(-64, 65, (M, N)), rng.integers(-64, 65, (M, N))
+    ref = np.maximum(A @ W.T + bias[None, :] + R1 + R2, 0)
+    # the reference itself is exactly representable: the same expression in float32 numpy gives the same integers
+    f = lambda x: x.astype(np.float32)
+    ref32 = np.maximum(f(A) @ f(W).T + f(bias)[None, :] + f(R1) + f(R2), np.float32(0))
+    assert ref32.dtype == np.float32 and np.array_equal(ref32.astype(np.int64), ref)
+    return f(A), f(W), f(bias), f(R1), f(R2), f(ref)
+
+
+@pytest.mark.parametrize("kind", [4, 5, 7, 8, 9, 10])
+def test_split_gemm_epilogue_exact_on_integers(ops, kind):
+    """Every split form (bf16 six-product: kinds 4 / 5 / 7 = 256 / 128 / 64-row tile; fp16 three-product: 8 / 9 / 10) through the whole
+    row epilogue at once — bias with a ragged last float4 group, R1, R2 and ReLU — on integers, where the result is exact: one
+    and two row tiles of every tile height, one and two K-steps of the 32-deep kernel.  No tolerance."""
+    for (M, N, K) in ((67, 130, 32), (129, 258, 64)):
+        A, W, bias, R1, R2, ref = _integer_epilogue_case(M, N, K, 1000 * kind + M)
+        pad_cols = lambda x: np.pad(x, ((0, 0), (0, -x.shape[1] % 128)))
+        dR1, dR2 = dev(pad_rows(pad_cols(R1))), dev(pad_rows(pad_cols(R2)))
+        C = ops.gemm_f32(dev(pad_rows(A)), dev(pad_rows(W)), bias=dev(np.pad(bias, (0, -N % 128))), R1=dR1, R2=dR2, relu=True, M=M, N=N,
+                         guard=True, kind=kind, w_scale=1.0 if kind >= 8 else None).cpu().numpy()[:M, :N]
+        assert np.array_equal(C, ref), (kind, M, N, K, int((C != ref).sum()), float(np.abs(C - ref).max()))
