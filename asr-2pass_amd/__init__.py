@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "pfhip_resample_len", "pfhip_resample", "pfhip_offline_forward_rate",
     "pfhip_set_batching", "pfhip_set_inflight", "pfhip_warm_up", "pfhip_get_inflight", "pfhip_inflight_stats", "pfhip_is_contextual", "pfhip_has_timestamp_head", "pfhip_hotword_embed", "pfhip_set_hotwords",
     "pfhip_offline_forward_hwsets", "pfhip_set_hotword_bank_bytes", "pfhip_set_hotword_merging", "pfhip_hotword_bank_stats",
+    "pfhip_offline_forward_nbest", "pfhip_set_nbest", "pfhip_offline_fetch_nbest",
     "pfhip_extract_feats", "pfhip_get_tensor", "pfhip_debug_poke", "pfhip_profile_enable", "pfhip_profile_read",
     "pfhip_stream_create", "pfhip_stream_destroy", "pfhip_stream_reset", "pfhip_stream_forward", "pfhip_stream_last_path", "pfhip_stream_forward_batch", "pfhip_set_stream_batching",
     "pfhip_stream_set_debug", "pfhip_stream_get_tensor",
@@ -60,6 +61,10 @@ class _Out(ctypes.Structure):
         ("us_len", ctypes.POINTER(ctypes.c_int32)),
         ("max_us", ctypes.c_int32),
     ]
+
+
+class _Nbest(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("ids", ctypes.POINTER(ctypes.c_int32)), ("logp", ctypes.POINTER(ctypes.c_float))]
 
 
 class _SlotStats(ctypes.Structure):
@@ -143,6 +148,11 @@ def load_lib() -> ctypes.CDLL:
         lib.pfhip_set_hotword_bank_bytes.argtypes = [vp, ctypes.c_int64]
         lib.pfhip_set_hotword_merging.argtypes = [vp, ci]
         lib.pfhip_hotword_bank_stats.argtypes = [vp, ctypes.POINTER(_HwBankStats)]
+    if hasattr(lib, "pfhip_offline_forward_nbest"):
+        lib.pfhip_offline_forward_nbest.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci,
+                                                    ctypes.POINTER(ci), ctypes.POINTER(_Out), ctypes.POINTER(_Nbest)]
+        lib.pfhip_set_nbest.argtypes = [vp, ci]
+        lib.pfhip_offline_fetch_nbest.argtypes = [vp, ctypes.POINTER(_Nbest)]
     lib.pfhip_stream_create.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(vp)]
     lib.pfhip_stream_destroy.argtypes = [vp]
     lib.pfhip_stream_destroy.restype = None
@@ -421,12 +431,14 @@ class ParaformerHip:
         return [o[:got[b]] for b, o in enumerate(outs)]
 
     def forward_ids(self, din: Sequence[np.ndarray], want_logp=False, max_tokens=None, hw_emb=None, want_timestamps=False,
-                    sample_rate=None, hw_sets=None, set_of_utt=None):
+                    sample_rate=None, hw_sets=None, set_of_utt=None, nbest=None, nbest_fill=0):
         """Batched forward.  Returns dict(token_num, n_fires, n_frames, ids=list of int arrays,
         logp=list of [n_fires, V] arrays or None[, us_alphas, us_peaks = lists of [3*T_b] arrays]).
         hw_emb: one hotword set [H, d] for the whole batch.  hw_sets + set_of_utt: a list of sets ([H_k, d] each) and, per
         utterance, the index of the set it attends to (pfhip_offline_forward_hwsets); not together with hw_emb or sample_rate.
-        sample_rate: the rate of din when it is not the model's (pfhip_offline_forward_rate resamples on the GPU first)."""
+        sample_rate: the rate of din when it is not the model's (pfhip_offline_forward_rate resamples on the GPU first).
+        nbest=k (1..8): also nbest_ids / nbest_logp [batch, max_tokens, k], the k best columns of every token row and their
+        log-probabilities (pfhip_offline_forward_nbest; rows >= n_fires keep nbest_fill); not together with sample_rate."""
         B = len(din)
         if B == 0:
             raise PfhipError("empty batch")
@@ -464,7 +476,20 @@ class ParaformerHip:
             out.max_us = max_us
         hw = np.ascontiguousarray(hw_emb, dtype=np.float32) if hw_emb is not None else None
         hw_ptr, n_hw = (hw.ctypes.data, int(hw.shape[0])) if hw is not None else (None, 0)
-        if hw_sets is not None:
+        if nbest is not None:
+            if sample_rate is not None or (hw_sets is not None and (hw_emb is not None or set_of_utt is None or len(set_of_utt) != B)):
+                raise PfhipError("nbest excludes sample_rate; hw_sets needs set_of_utt [batch] and excludes hw_emb")
+            k = int(nbest)
+            nb_ids = np.full((B, max_tokens, max(k, 1)), nbest_fill, np.int32)
+            nb_logp = np.full((B, max_tokens, max(k, 1)), nbest_fill, np.float32)
+            nb = _Nbest(k, nb_ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nb_logp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+            sets = [np.ascontiguousarray(h, dtype=np.float32) for h in hw_sets] if hw_sets is not None else ([hw] if hw is not None else [])
+            sptr = (ctypes.c_void_p * max(len(sets), 1))(*[h.ctypes.data if h.size else None for h in sets])
+            sn = (ctypes.c_int * max(len(sets), 1))(*[int(h.shape[0]) for h in sets])
+            sof = (ctypes.c_int * B)(*[int(j) for j in (set_of_utt if hw_sets is not None else [0] * B)])
+            _check(self._lib, self._lib.pfhip_offline_forward_nbest(self._h, ptrs, lens, B, sptr, sn, len(sets), sof, ctypes.byref(out),
+                                                                    ctypes.byref(nb)))
+        elif hw_sets is not None:
             if hw_emb is not None or sample_rate is not None or set_of_utt is None or len(set_of_utt) != B:
                 raise PfhipError("hw_sets needs set_of_utt [batch] and excludes hw_emb / sample_rate")
             sets = [np.ascontiguousarray(h, dtype=np.float32) for h in hw_sets]
@@ -483,6 +508,8 @@ class ParaformerHip:
         if want_timestamps:
             res["us_alphas"] = [usa[b, :usl[b]].copy() for b in range(B)]
             res["us_peaks"] = [usp[b, :usl[b]].copy() for b in range(B)]
+        if nbest is not None:
+            res["nbest_ids"], res["nbest_logp"] = nb_ids, nb_logp
         return res
 
     def Forward(self, din, len_=None, input_finished=True, hw_emb=None, decoder_handle=None, batch_in=1):
@@ -546,6 +573,18 @@ class ParaformerHip:
         out.max_tokens = max_tokens
         _check(self._lib, self._lib.pfhip_offline_fetch(self._h, ctypes.byref(out)))
         return dict(token_num=tn, n_fires=nf, n_frames=fr, ids=[ids[b, :min(tn[b], nf[b])].copy() for b in range(B)])
+
+    def set_nbest(self, k):
+        """pfhip_set_nbest: k candidates per token row for the following enqueue_device calls (0 = off)."""
+        _check(self._lib, self._lib.pfhip_set_nbest(self._h, int(k)))
+
+    def fetch_nbest(self, B: int, max_tokens: int, k: int, fill=0):
+        """pfhip_offline_fetch_nbest after fetch(B, max_tokens): (nbest_ids, nbest_logp) [B, max_tokens, k]."""
+        nb_ids = np.full((B, max_tokens, max(int(k), 1)), fill, np.int32)
+        nb_logp = np.full((B, max_tokens, max(int(k), 1)), fill, np.float32)
+        nb = _Nbest(int(k), nb_ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nb_logp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+        _check(self._lib, self._lib.pfhip_offline_fetch_nbest(self._h, ctypes.byref(nb)))
+        return nb_ids, nb_logp
 
     def forward_resident(self, d_pcm_ptr: int, sample_off: np.ndarray, n_samples: np.ndarray, max_tokens: int):
         """pfhip_offline_forward_resident: PCM already in HBM, routed over the handle's execution contexts like Forward."""

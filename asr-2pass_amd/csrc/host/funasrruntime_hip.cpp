@@ -31,6 +31,7 @@ struct RecogResult {               // funasr::FUNASR_RECOG_RESULT (com-define.h)
   std::vector<std::vector<int>> seg_ids;
   std::vector<std::pair<int, int>> segs;
   std::vector<int> online_ids;       // ids the streaming chunks of this call emitted (inspection)
+  std::vector<float> confidence;     // FunASRGetTokenConfidence (FunOfflineSetNbest)
 };
 
 bool ReadAll(const std::string& path, std::vector<char>& out) {
@@ -195,7 +196,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
     }
   }
   std::vector<std::string> msgs(index_vector.size());
-  std::vector<std::vector<float>> spans(index_vector.size());
+  std::vector<std::vector<float>> spans(index_vector.size()), conf(index_vector.size());
   res->seg_ids.assign(index_vector.size(), {});
   size_t head = 0, msg_idx = 0;
   std::vector<int> batch;
@@ -214,12 +215,14 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
       msgs[seg] = msg_batch[k];
       res->seg_ids[seg] = os->asr.LastTokenIds()[k];
       if (k < os->asr.LastTimestamps().size()) spans[seg] = os->asr.LastTimestamps()[k];
+      if (k < os->asr.LastTokenConfidence().size()) conf[seg] = os->asr.LastTokenConfidence()[k];
     }
     if (fn_callback) fn_callback(++step, (int)index_vector.size());
   }
   std::string cur_stamp = "[";
   for (size_t idx = 0; idx < msgs.size(); ++idx) {                                     // funasrruntime.cpp:291-312
     if (msgs[idx].empty()) continue;
+    res->confidence.insert(res->confidence.end(), conf[idx].begin(), conf[idx].end());       // in the order the text is assembled
     const float t0 = (float)res->segs[idx].first / (float)model_rate;                  // msg_stimes
     const size_t bar = msgs[idx].find(" | ");
     res->msg += msgs[idx].substr(0, bar);
@@ -263,6 +266,8 @@ void FunOfflineUninit(FUNASR_HANDLE handle) { delete static_cast<OfflineStreamHi
 const std::vector<std::vector<int>>& FunASRGetSegmentIds(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->seg_ids; }
 const std::vector<std::pair<int, int>>& FunASRGetSegments(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->segs; }
 const std::vector<int>& FunASRGetOnlineIds(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_ids; }
+void FunOfflineSetNbest(FUNASR_HANDLE handle, int k) { if (handle) static_cast<OfflineStreamHip*>(handle)->asr.SetNbest(k); }
+const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->confidence; }
 pfhip_model* FunOfflineGetAsrHandle(FUNASR_HANDLE handle) { return handle ? static_cast<OfflineStreamHip*>(handle)->asr.Handle() : nullptr; }
 
 

@@ -95,6 +95,14 @@ const std::vector<std::vector<int>>& FunASRGetSegmentIds(FUNASR_RESULT result);
 const std::vector<std::pair<int, int>>& FunASRGetSegments(FUNASR_RESULT result);
 // ... the ids the streaming chunks of one FunTpassInferBuffer call emitted
 const std::vector<int>& FunASRGetOnlineIds(FUNASR_RESULT result);
+// Extensions without a counterpart in funasrruntime.h (the reference's GreedySearch keeps only the arg-max, paraformer.cpp:386-395):
+// FunOfflineSetNbest(h, k), k = 1..8, makes every following FunOfflineInferBuffer on the handle ask the head for the k best
+// candidates per token (ParaformerHip::SetNbest; 0 = off, the default: the adapter then calls exactly what it always called).
+// FunASRGetTokenConfidence: exp(log-probability of the greedy token) for every token the text of the result was made from -- ids
+// that Vector2StringV2 drops are dropped here too -- the VAD segments concatenated in time order as the text is; empty when the
+// result was made without FunOfflineSetNbest.
+void FunOfflineSetNbest(FUNASR_HANDLE handle, int k);
+const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result);
 // ... and the C-ABI handle of the offline acoustic model behind a FunOfflineInit handle (pfhip_inflight_stats in the harnesses)
 struct pfhip_model;
 pfhip_model* FunOfflineGetAsrHandle(FUNASR_HANDLE handle);

@@ -2,6 +2,7 @@
 
 #include "postprocess.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -15,6 +16,8 @@ namespace {
 // per calling thread
 thread_local std::vector<std::vector<int>> tl_last_ids;
 thread_local std::vector<std::vector<float>> tl_last_spans;
+thread_local std::vector<std::vector<int>> tl_last_nbest_ids;
+thread_local std::vector<std::vector<float>> tl_last_nbest_logp, tl_last_conf;
 // (Vocab::Vector2StringV2 updates a member, `last_is_complete_english_`, vocab.h:22, and the reference calls it unguarded from
 // every decoder thread; the stand-alone HostVocab keeps that flag in an atomic, the in-tree build uses the reference's own
 // class as the reference does.  No lock is taken around the text step.)
@@ -232,6 +235,9 @@ std::vector<std::string> ParaformerHip::Forward(float** din, int* len, bool inpu
   std::vector<std::string> results(batch_in > 0 ? batch_in : 0);
   tl_last_ids.assign(results.size(), {});
   tl_last_spans.assign(results.size(), {});
+  tl_last_nbest_ids.assign(nbest_k_ ? results.size() : 0, {});
+  tl_last_nbest_logp.assign(nbest_k_ ? results.size() : 0, {});
+  tl_last_conf.assign(nbest_k_ ? results.size() : 0, {});
   if (batch_in <= 0 || !handle_) return results;
   // paraformer.cpp:563: the LM decides between GreedySearch and the decoder that came with the call
   Decoder* decoder = has_lm_ ? static_cast<Decoder*>(wfst_decoder) : nullptr;
@@ -272,7 +278,20 @@ std::vector<std::string> ParaformerHip::Forward(float** din, int* len, bool inpu
       ++n_hw;
     }
   }
-  const pfhip_status st = pfhip_offline_forward(handle_, din, len, batch_in, n_hw ? hw.data() : nullptr, n_hw, &out);
+  // SetNbest: the same forward plus the k best columns of every token row (this caller's one hotword set as set 0)
+  const int nk = nbest_k_;
+  std::vector<int32_t> nb_ids((size_t)(nk ? batch_in : 0) * max_tokens * nk);
+  std::vector<float> nb_logp(nb_ids.size());
+  pfhip_status st;
+  if (nk) {
+    const pfhip_nbest nb{nk, nb_ids.data(), nb_logp.data()};
+    const float* sets[1] = {hw.data()};
+    const int set_rows[1] = {n_hw};
+    const std::vector<int> set_of_utt((size_t)batch_in, 0);
+    st = pfhip_offline_forward_nbest(handle_, din, len, batch_in, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(), &out, &nb);
+  } else {
+    st = pfhip_offline_forward(handle_, din, len, batch_in, n_hw ? hw.data() : nullptr, n_hw, &out);
+  }
   if (st != PFHIP_OK) {
     std::fprintf(stderr, "ParaformerHip::Forward: %s\n", pfhip_last_error());
     return results;                                // "" per item, as paraformer.cpp:582-588
@@ -280,6 +299,13 @@ std::vector<std::string> ParaformerHip::Forward(float** din, int* len, bool inpu
   for (int i = 0; i < batch_in; ++i) {
     const int n = tn[i] < nf[i] ? tn[i] : nf[i];
     tl_last_ids[i].assign(ids.begin() + (size_t)i * max_tokens, ids.begin() + (size_t)i * max_tokens + n);
+    if (nk) {
+      const size_t row0 = (size_t)i * max_tokens * nk;
+      tl_last_nbest_ids[i].assign(nb_ids.begin() + row0, nb_ids.begin() + row0 + (size_t)n * nk);
+      tl_last_nbest_logp[i].assign(nb_logp.begin() + row0, nb_logp.begin() + row0 + (size_t)n * nk);
+      for (int t = 0; t < n; ++t)
+        if (InText(tl_last_ids[i][t])) tl_last_conf[i].push_back(std::exp(nb_logp[row0 + (size_t)t * nk]));
+    }
     if (decoder && fr[i] > 0) {                   // no feature frame: "" before any decoding (paraformer.cpp:477-480)
       // BeamSearch + FinalizeDecode (paraformer.cpp:410-419, 563-579; per item as paraformer-torch.cpp:431-466): `n` rows of V
       // log-probabilities, of which WfstDecoder::Search feeds the first n - 1 to the lattice decoder (wfst-decoder.cpp:27-58)
@@ -359,6 +385,18 @@ std::vector<std::vector<float>> ParaformerHip::CompileHotwordEmbedding(std::stri
 namespace funasr {
 const std::vector<std::vector<int>>& ParaformerHip::LastTokenIds() const { return tl_last_ids; }
 const std::vector<std::vector<float>>& ParaformerHip::LastTimestamps() const { return tl_last_spans; }
+const std::vector<std::vector<int>>& ParaformerHip::LastNbestIds() const { return tl_last_nbest_ids; }
+const std::vector<std::vector<float>>& ParaformerHip::LastNbestLogp() const { return tl_last_nbest_logp; }
+const std::vector<std::vector<float>>& ParaformerHip::LastTokenConfidence() const { return tl_last_conf; }
+
+// vocab.cpp:181 (Vector2StringV2) and util.cpp:733-735 (PostProcess) skip the same three tokens; without a token file the ids are
+// the text and every one is kept
+bool ParaformerHip::InText(int id) const {
+  if (!vocab) return true;
+  if (id < 0 || id >= vocab->Size()) return false;
+  const std::string w = vocab->Id2String(id);
+  return !(w == "<s>" || w == "</s>" || w == "<unk>");
+}
 }  // namespace funasr
 
 namespace funasr {

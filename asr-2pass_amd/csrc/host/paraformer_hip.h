@@ -173,6 +173,17 @@ class ParaformerHip : public ParaformerHipBase
   // timestamp models: (begin_s, end_s, is_sil) per span of the last Forward, what TimestampOnnx produced
   // (paraformer.cpp:545-562 + util.cpp:838-963); empty for plain models
   const std::vector<std::vector<float>>& LastTimestamps() const;
+  // N-best candidates (an extension; GreedySearch keeps only the arg-max, paraformer.cpp:386-395).  SetNbest(k), k = 1..8: every
+  // following Forward also asks the head for the k best columns of each token row (pfhip_offline_forward_nbest); 0 (default):
+  // Forward calls exactly what it calls without this.  Not a virtual: funasr::Model's table is untouched.
+  void SetNbest(int k) { nbest_k_ = k < 0 ? 0 : (k > 8 ? 8 : k); }
+  int GetNbest() const { return nbest_k_; }
+  // of the last Forward of the calling thread, per utterance: the candidates' ids and log-probabilities [tokens][k] (row-major,
+  // candidate 0 = the greedy id), and exp(candidate 0's log-probability) for every id the text was made from (ids that
+  // Vector2StringV2 / PostProcess drop -- <s>, </s>, <unk> -- are dropped here too).  Empty without SetNbest.
+  const std::vector<std::vector<int>>& LastNbestIds() const;
+  const std::vector<std::vector<float>>& LastNbestLogp() const;
+  const std::vector<std::vector<float>>& LastTokenConfidence() const;
   void SetDevice(int device) { device_ = device; }
   // the C-ABI handles underneath — the offline model and, after a 2-pass / online InitAsr, the online model that
   // ParaformerOnlineHip streams are created from (the reference's encoder_session_ / decoder_session_) — and the text mappings
@@ -198,6 +209,8 @@ class ParaformerHip : public ParaformerHipBase
   int device_ = 0;
   int batch_size_ = 1;
   bool has_lm_ = false;
+  int nbest_k_ = 0;                        // SetNbest
+  bool InText(int id) const;               // whether Vector2StringV2 / PostProcess keep the token of this id
   HipVocab* vocab = nullptr;               // tokens.json (paraformer.cpp:47-48)
   pfhip_host::SegDictHost* seg_dict_ = nullptr;
 };

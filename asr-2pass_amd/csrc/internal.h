@@ -247,6 +247,10 @@ struct pfhip_model {
   int B = 0, M = 0, ML = 0, maxT = 0, maxL = 0;
   std::vector<int> T, row_off, n_fires, token_num, tok_off;
   bool have_logp = false;
+  // N-best candidates (topk.hip): k of the forward being run (0 = the arg-max kernel alone, as ever), the [token rows, k] id and
+  // value buffers the head fills, the k the device-pointer form asks for (pfhip_set_nbest) and the max_tokens of its last fetch
+  int nbest_k = 0, nbest_enqueue_k = 0, nbest_fetch_max_tokens = 0;
+  Buf nb_ids, nb_logp;
   // device views into meta / dmeta
   int *m_frame_off = nullptr, *m_nframes = nullptr, *m_row_off = nullptr, *m_len = nullptr,
       *m_row_pos = nullptr, *m_row_len = nullptr;

@@ -248,6 +248,12 @@ void launch_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, i
 // range_flag (may be null): bit 0 is raised when a row's log-sum-exp is not finite (NaN / Inf reached the logits).
 void launch_logsoftmax_argmax(const float* logits, int ldl, int ML, int V, float* logp, int32_t* ids,
                               hipStream_t s, int* range_flag = nullptr);
+// The same head with the k best columns of every row (topk.hip; 1 <= k <= kTopkMax <= V): topk_ids / topk_logp [ML][k], larger logit
+// first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry of its column bit for bit.  The
+// log-sum-exp is formed with logp null as well.  false (nothing launched) when the arguments are outside that.
+constexpr int kTopkMax = 8;
+bool launch_logsoftmax_topk(const float* logits, int ldl, int ML, int V, int k, float* logp, int32_t* ids, int32_t* topk_ids,
+                            float* topk_logp, hipStream_t s, int* range_flag = nullptr);
 
 // ---- chunk-streaming pieces ----------------------------------------------
 // OnlineLfrCmvn + x*sqrt(d) + GetPosEmb (paraformer-online.cpp:196-238, 549-555, 240-268) for `n_rows`

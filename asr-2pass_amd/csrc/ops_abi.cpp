@@ -218,5 +218,11 @@ int pfhip_op_logsoftmax_argmax(const float* logits, int ldl, int ML, int V, floa
   pfhip::launch_logsoftmax_argmax(logits, ldl, ML, V, logp, ids, S(stream));
   return done();
 }
+int pfhip_op_logsoftmax_topk(const float* logits, int ldl, int M, int V, int k, float* logp, int32_t* ids, int32_t* topk_ids,
+                             float* topk_logp, void* stream) {
+  // the launcher checks k, V >= k, ldl >= V and the buffers before it launches anything
+  if (!pfhip::launch_logsoftmax_topk(logits, ldl, M, V, k, logp, ids, topk_ids, topk_logp, S(stream))) return (int)hipErrorInvalidValue;
+  return done();
+}
 
 }  // extern "C"

@@ -901,6 +901,7 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   HIP_TRY(m->ctxd.ensure((size_t)MLp * d * 4));
   HIP_TRY(m->logits.ensure((size_t)MLp * m->vocab_pad * 4));
   HIP_TRY(m->ids.ensure((size_t)MLp * 4));
+  if (m->nbest_k) { HIP_TRY(m->nb_ids.ensure((size_t)MLp * m->nbest_k * 4)); HIP_TRY(m->nb_logp.ensure((size_t)MLp * m->nbest_k * 4)); }
   {
     Scope sc(m, s, K_OTHER, 0, 8.0 * ML * d);
     pfhip::launch_compact(stage, m->emb.f(), m->m_src_row, ML, d, s);
@@ -1211,7 +1212,16 @@ pfhip_status head_locked(pfhip_model* m, hipStream_t s, bool want_logp) {
   if (m->ML == 0) return PFHIP_OK;
   const int V = m->cfg.vocab;
   if (want_logp) HIP_TRY(m->logp.ensure((size_t)m->ML * V * 4));
-  {
+  if (m->nbest_k) {      // candidates asked for: the sibling kernel (topk.hip), which reads the row a second time for its log-sum-exp
+    const int k = m->nbest_k;
+    HIP_TRY(m->nb_ids.ensure((size_t)m->ML * k * 4));
+    HIP_TRY(m->nb_logp.ensure((size_t)m->ML * k * 4));
+    Scope sc(m, s, K_HEAD, 0, 4.0 * m->ML * V * (want_logp ? 3 : 2));
+    if (!pfhip::launch_logsoftmax_topk(m->logits.f(), m->vocab_pad, m->ML, V, k, want_logp ? m->logp.f() : nullptr,
+                                       static_cast<int32_t*>(m->ids.p), static_cast<int32_t*>(m->nb_ids.p), m->nb_logp.f(), s,
+                                       m->d_range_flag))
+      return fail(PFHIP_ERR_ARG, "nbest k outside 1..8 or larger than the vocabulary");
+  } else {
     Scope sc(m, s, K_HEAD, 0, 4.0 * m->ML * V * (want_logp ? 3 : 2));
     pfhip::launch_logsoftmax_argmax(m->logits.f(), m->vocab_pad, m->ML, V, want_logp ? m->logp.f() : nullptr,
                                     static_cast<int32_t*>(m->ids.p), s, m->d_range_flag);
@@ -1232,14 +1242,16 @@ pfhip_status read_range_flag(pfhip_model* m, hipStream_t s, bool sync) {
   return PFHIP_OK;
 }
 
-pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s);
+pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb);
 // The guard of the fp16 two-plane domain (kernels.h LaunchCtx): a forward whose range flag came back raised — a LayerNorm-folded
 // row whose centred std is outside [2^-8, 2^11] or whose |mean| / std exceeds kLnOffsetMax, or a log-prob row that is not finite — is
 // redone ONCE, inside the same context, on the exact kernels (bf16 three-plane GEMMs and attention, fp32 operands instead of plane
 // images, LayerNorm kernels instead of the fold), and counted
 // (pfhip_debug_poke "range_fallbacks").  The reference computes in plain fp32 (paraformer.cpp:496-541).
-pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s) {
-  pfhip_status st = fetch_once(m, out, s);
+// nb (may be null): the caller's candidate buffers, nb->k <= m->nbest_k; the exact re-run's head produces the candidates again
+// (head_locked reads m->nbest_k), so what comes back belongs to the forward whose token_ids come back
+pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb = nullptr) {
+  pfhip_status st = fetch_once(m, out, s, nb);
   if (st || !m->range_hit || m->exact_rerun || m->always_exact || !m->last_pcm || m->last_feats_only) return st;
   ++m->range_fallbacks;
   m->exact_rerun = true;
@@ -1247,13 +1259,36 @@ pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s) {
   const std::vector<int> ns = m->last_n;
   st = enqueue_locked(m, m->last_pcm, off.data(), ns.data(), (int)ns.size(), s, false);
   if (!st) st = head_locked(m, s, out->logp != nullptr);
-  if (!st) st = fetch_once(m, out, s);
+  if (!st) st = fetch_once(m, out, s, nb);
   m->exact_rerun = false;
   return st;
 }
 
-pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s) {
+// the first nb->k of the m->nbest_k candidates of every token row, utterance b at row b * max_tokens of the caller's buffers; staged
+// on the host like the ids (tok rows x k x 8 bytes)
+struct NbestStage {
+  std::vector<int32_t> ids; std::vector<float> logp;
+  pfhip_status start(pfhip_model* m, hipStream_t s) {
+    ids.resize((size_t)m->ML * m->nbest_k); logp.resize(ids.size());
+    HIP_TRY(hipMemcpyAsync(ids.data(), m->nb_ids.p, ids.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(logp.data(), m->nb_logp.p, logp.size() * 4, hipMemcpyDeviceToHost, s));
+    return PFHIP_OK;
+  }
+  void scatter(const pfhip_model* m, const pfhip_nbest* nb, int max_tokens) const {      // after the synchronise
+    const int kc = m->nbest_k, k = nb->k;
+    for (int b = 0; b < m->B; ++b)
+      for (int t = 0; t < m->n_fires[b]; ++t) {
+        const size_t src = ((size_t)m->tok_off[b] + t) * kc, dst = ((size_t)b * max_tokens + t) * k;
+        std::memcpy(nb->ids + dst, ids.data() + src, 4 * (size_t)k);
+        std::memcpy(nb->logp + dst, logp.data() + src, 4 * (size_t)k);
+      }
+  }
+};
+
+pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb) {
   if (!out) return fail(PFHIP_ERR_ARG, "null out");
+  if (nb && (nb->k < 1 || nb->k > m->nbest_k || !nb->ids || !nb->logp)) return fail(PFHIP_ERR_ARG, "bad nbest argument");
+  m->nbest_fetch_max_tokens = out->max_tokens;
   ForwardCtx fc(m);
   const int B = m->B;
   for (int b = 0; b < B; ++b) {
@@ -1295,7 +1330,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s) {
     }
     return PFHIP_OK;
   }
-  if ((out->token_ids || out->logp) && out->max_tokens < m->maxL)
+  if ((out->token_ids || out->logp || nb) && out->max_tokens < m->maxL)
     return fail(PFHIP_ERR_CAPACITY, "max_tokens smaller than the longest token sequence");
   if (out->logp && !m->have_logp) {
     pfhip_status st = head_locked(m, s, true);
@@ -1306,6 +1341,8 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s) {
     ids.resize(m->ML);
     HIP_TRY(hipMemcpyAsync(ids.data(), m->ids.p, (size_t)m->ML * 4, hipMemcpyDeviceToHost, s));
   }
+  NbestStage nbs;
+  if (nb) { const pfhip_status ns = nbs.start(m, s); if (ns) return ns; }
   const int V = m->cfg.vocab;
   if (out->logp) {
     for (int b = 0; b < B; ++b)
@@ -1322,6 +1359,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s) {
   if (out->token_ids)
     for (int b = 0; b < B; ++b)
       std::memcpy(out->token_ids + (size_t)b * out->max_tokens, ids.data() + m->tok_off[b], 4 * (size_t)m->n_fires[b]);
+  if (nb) nbs.scatter(m, nb, out->max_tokens);
   return PFHIP_OK;
 }
 
@@ -1672,7 +1710,7 @@ void pfhip_destroy(pfhip_model* m) {
   for (Buf* b : {&m->pcm, &m->meta, &m->feats, &m->x0, &m->x, &m->y, &m->qkv, &m->mem, &m->ctx, &m->hbuf, &m->enc,
                  &m->alphas, &m->counts, &m->emb, &m->xd, &m->yd, &m->hd, &m->hd2, &m->td, &m->t2, &m->qd, &m->ctxd,
                  &m->logits, &m->logp, &m->ids, &m->dmeta, &m->cat, &m->hw, &m->hwkv, &m->ts_up, &m->ts_gx, &m->ts_y, &m->ts_hx, &m->ts_a2,
-                 &m->ts_alphas, &m->ts_peaks, &m->ts_meta, &m->sseg, &m->rs_in, &m->fbk, &m->d_ops, &m->kvall, &m->lnstats, &m->lnstats2, &m->kvside, &m->ts_cst, &m->ctxP, &m->xP, &m->hP, &m->encP, &m->xdP, &m->kvP})
+                 &m->ts_alphas, &m->ts_peaks, &m->ts_meta, &m->sseg, &m->rs_in, &m->fbk, &m->d_ops, &m->kvall, &m->lnstats, &m->lnstats2, &m->kvside, &m->ts_cst, &m->ctxP, &m->xP, &m->hP, &m->encP, &m->xdP, &m->kvP, &m->nb_ids, &m->nb_logp})
     b->release();
   if (m->hwbank) {               // the device's hotword bank (unused on a context)
     HwBankDev& D = *m->hwbank;
@@ -1719,6 +1757,7 @@ pfhip_status pfhip_offline_enqueue(pfhip_model* m, const float* d_pcm, const int
   HotwordPins pins{m};
   pfhip_status st = resolve_default_hotwords_locked(m, batch, s);
   if (st) return st;
+  m->nbest_k = m->nbest_enqueue_k;         // pfhip_set_nbest
   st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
   if (st) return st;
   return head_locked(m, s, false);
@@ -1737,11 +1776,13 @@ pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out) {
 struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
 
 static pfhip_status forward_direct(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch,
-                                   const HwSets& hw, pfhip_out* out, int fs_in = 0) {
+                                   const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_nbest* nb = nullptr) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
   m->prof_stream = s;
+  if (nb && nb->k > m->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k larger than the vocabulary");      // before any launch
+  m->nbest_k = nb ? nb->k : 0;
   HotwordPins pins{m};              // held until the results (a range-guard re-run included) are back
   {
     const pfhip_status hs = resolve_hotwords_locked(m, hw.emb, hw.n, hw.n_sets, hw.of_utt, batch, s);
@@ -1755,7 +1796,7 @@ static pfhip_status forward_direct(pfhip_model* m, const float* const* pcm, cons
   if (st) return st;
   st = head_locked(m, s, out->logp != nullptr);
   if (st) return st;
-  return fetch_locked(m, out, s);
+  return fetch_locked(m, out, s, nb);
 }
 
 // ---- execution slots -----------------------------------------------------------------------------------------------
@@ -1810,6 +1851,7 @@ static void release_slot(pfhip_model* head, pfhip_model* slot) {
 struct BatchReq : pfhip_detail::MergeReqBase {
   const float* const* pcm; const int* n; int batch; pfhip_out* out;
   HwSets hw{nullptr, nullptr, 0, nullptr};          // the caller's hotword sets (contextual models)
+  const pfhip_nbest* nb = nullptr;                  // the caller's candidate buffers (pfhip_offline_forward_nbest), or none
   pfhip_status st = PFHIP_OK; std::string err;
 };
 
@@ -1817,6 +1859,7 @@ struct BatchReq : pfhip_detail::MergeReqBase {
 static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
   std::vector<const float*> ptrs; std::vector<int> lens;
   bool want_logp = false, want_us = false; int max_tok = 1, utts = 0;
+  int kmax = 0;      // the packed forward computes the largest k among its callers; the order makes every prefix a caller's own answer
   // Contextual model: the callers' hotword sets, deduplicated (one connection sends the same list with each of its segments; the
   // bank then matches by content), and for every packed utterance the index of its set.  A caller without hotwords fails alone
   // with the reference's "hw_emb is null" (paraformer.cpp:516-520); its company is served.
@@ -1844,6 +1887,7 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
   for (BatchReq* r : take) {
     for (int i = 0; i < r->batch; ++i) { ptrs.push_back(r->pcm[i]); lens.push_back(r->n[i]); max_tok = std::max(max_tok, r->n[i] / 960 + 2); }
     want_logp = want_logp || r->out->logp != nullptr;
+    if (r->nb) kmax = std::max(kmax, (int)r->nb->k);
     want_us = want_us || r->out->us_alphas || r->out->us_peaks || r->out->us_len;
     utts += r->batch;
   }
@@ -1858,8 +1902,11 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
     usa.resize((size_t)utts * max_us); usp.resize((size_t)utts * max_us); usl.resize(utts);
     all.us_alphas = usa.data(); all.us_peaks = usp.data(); all.us_len = usl.data(); all.max_us = max_us;
   }
+  std::vector<int32_t> nbi; std::vector<float> nbl;
+  if (kmax) { nbi.resize((size_t)utts * max_tok * kmax); nbl.resize(nbi.size()); }
+  const pfhip_nbest nb_all{kmax, nbi.data(), nbl.data()};
   const HwSets sets{set_emb.data(), set_n.data(), (int)set_emb.size(), set_of.data()};
-  pfhip_status st = forward_direct(m, ptrs.data(), lens.data(), utts, sets, &all);
+  pfhip_status st = forward_direct(m, ptrs.data(), lens.data(), utts, sets, &all, 0, kmax ? &nb_all : nullptr);
   const std::string err = g_err;
   int u0 = 0;
   for (BatchReq* r : take) {
@@ -1870,11 +1917,17 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
       if (o->token_num) o->token_num[i] = tn[u];
       if (o->n_fires) o->n_fires[i] = nf[u];
       if (o->n_frames) o->n_frames[i] = fr[u];
-      if ((o->token_ids || o->logp) && o->max_tokens < nf[u]) {
+      if ((o->token_ids || o->logp || r->nb) && o->max_tokens < nf[u]) {
         r->st = PFHIP_ERR_CAPACITY; r->err = "max_tokens smaller than the longest token sequence"; break;
       }
       if (o->token_ids) std::memcpy(o->token_ids + (size_t)i * o->max_tokens, ids.data() + (size_t)u * max_tok, 4 * (size_t)nf[u]);
       if (o->logp) std::memcpy(o->logp + (size_t)i * o->max_tokens * V, logp.data() + (size_t)u * max_tok * V, 4 * (size_t)nf[u] * V);
+      if (r->nb)
+        for (int t = 0; t < nf[u]; ++t) {
+          const size_t src = ((size_t)u * max_tok + t) * kmax, dst = ((size_t)i * o->max_tokens + t) * r->nb->k;
+          std::memcpy(r->nb->ids + dst, nbi.data() + src, 4 * (size_t)r->nb->k);
+          std::memcpy(r->nb->logp + dst, nbl.data() + src, 4 * (size_t)r->nb->k);
+        }
       if (o->us_alphas || o->us_peaks || o->us_len) {
         if (o->us_len) o->us_len[i] = usl[u];
         if ((o->us_alphas || o->us_peaks) && o->max_us < usl[u]) { r->st = PFHIP_ERR_CAPACITY; r->err = "max_us smaller than 3 x frames"; break; }
@@ -1889,9 +1942,9 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
 namespace { thread_local pfhip_model* tl_last_replica = nullptr; }      // where this thread's last offline forward ran (debug getters)
 
 static pfhip_status forward_batched(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
-                                    const HwSets& hw, pfhip_out* out) {
+                                    const HwSets& hw, pfhip_out* out, const pfhip_nbest* nb) {
   BatchReq me;
-  me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out; me.hw = hw;
+  me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out; me.hw = hw; me.nb = nb;
   int wait_us, max_utts;
   { std::lock_guard<std::mutex> l(head->bq.mu); wait_us = head->batch_wait_us; max_utts = head->batch_max_utts; }
   pfhip_model* ran_on = nullptr;
@@ -1928,9 +1981,11 @@ static pfhip_status forward_batched(pfhip_model* head, const float* const* pcm, 
 }
 
 static pfhip_status offline_forward_sets(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, const HwSets& hw,
-                                         pfhip_out* out) {
+                                         pfhip_out* out, const pfhip_nbest* nb = nullptr) {
   g_err.clear();
   if (!head || !pcm || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (nb && (nb->k < 1 || nb->k > pfhip::kTopkMax || nb->k > head->cfg.vocab || !nb->ids || !nb->logp))
+    return fail(PFHIP_ERR_ARG, "nbest: k outside 1..8 (or above the vocabulary) or a null buffer");
   for (int i = 0; i < batch; ++i)
     if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
   // merged with whoever else is calling: plain and timestamp models always; contextual models — every caller with its own hotword
@@ -1940,10 +1995,10 @@ static pfhip_status offline_forward_sets(pfhip_model* head, const float* const* 
     std::lock_guard<std::mutex> l(head->bq.mu);
     merge = head->batch_wait_us > 0 && batch < head->batch_max_utts && (!head->cfg.contextual || head->hw_merge);
   }
-  if (merge) return forward_batched(head, pcm, n_samples, batch, hw, out);
+  if (merge) return forward_batched(head, pcm, n_samples, batch, hw, out, nb);
   pfhip_model* m = acquire_slot(head);                  // the least-loaded execution slot (context / GPU)
   tl_last_replica = m;
-  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out);
+  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out, 0, nb);
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
   return st;
@@ -1967,6 +2022,47 @@ pfhip_status pfhip_offline_forward_hwsets(pfhip_model* head, const float* const*
   return offline_forward_sets(head, pcm, n_samples, batch, hw, out);
 }
 
+// pfhip_offline_forward_hwsets plus the k best candidates of every token row (an extension: GreedySearch, paraformer.cpp:386-395,
+// keeps only the arg-max); nb == nullptr is pfhip_offline_forward_hwsets itself
+pfhip_status pfhip_offline_forward_nbest(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
+                                         const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                         pfhip_out* out, const pfhip_nbest* nb) {
+  if (head && head->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
+    g_err.clear();
+    return fail(PFHIP_ERR_ARG, "bad argument");
+  }
+  const HwSets hw{hw_emb, n_hotwords, n_sets < 0 ? 0 : n_sets, set_of_utt};
+  return offline_forward_sets(head, pcm, n_samples, batch, hw, out, nb);
+}
+
+// device-pointer form: k candidates for the following pfhip_offline_enqueue calls of this handle (context 0); 0 = off
+pfhip_status pfhip_set_nbest(pfhip_model* m, int k) {
+  g_err.clear();
+  if (!m || k < 0 || k > pfhip::kTopkMax || k > m->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k outside 0..8 (or above the vocabulary)");
+  std::lock_guard<std::mutex> lk(m->mu);
+  m->nbest_enqueue_k = k;
+  return PFHIP_OK;
+}
+
+// the candidates of the forward pfhip_offline_fetch just returned (a range-guard re-run included: its head filled the buffers again)
+pfhip_status pfhip_offline_fetch_nbest(pfhip_model* m, const pfhip_nbest* nb) {
+  g_err.clear();
+  if (!m || !nb) return fail(PFHIP_ERR_ARG, "bad argument");
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (nb->k < 1 || nb->k > m->nbest_k || !nb->ids || !nb->logp)
+    return fail(PFHIP_ERR_ARG, "nbest: the last forward computed fewer candidates than asked for (pfhip_set_nbest), or a null buffer");
+  if (m->ML == 0) return PFHIP_OK;
+  if (m->nbest_fetch_max_tokens < m->maxL) return fail(PFHIP_ERR_CAPACITY, "pfhip_offline_fetch first: its max_tokens lays out the rows");
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t s = m->prof_stream ? m->prof_stream : m->own_stream;
+  NbestStage nbs;
+  const pfhip_status st = nbs.start(m, s);
+  if (st) return st;
+  HIP_TRY(hipStreamSynchronize(s));
+  nbs.scatter(m, nb, m->nbest_fetch_max_tokens);
+  return PFHIP_OK;
+}
+
 // pfhip_offline_forward with the PCM already in HBM: same routing over the execution slots, no H2D of the audio
 pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
                                             int batch, pfhip_out* out) {
@@ -1982,6 +2078,7 @@ pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pc
     m->prof_stream = s;
     HotwordPins pins{m};
     st = hipSetDevice(m->device) == hipSuccess ? PFHIP_OK : fail(PFHIP_ERR_HIP, "hipSetDevice");
+    m->nbest_k = 0;
     if (!st) st = resolve_default_hotwords_locked(m, batch, s);
     if (!st) st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
     if (!st) st = head_locked(m, s, out->logp != nullptr);
@@ -2343,7 +2440,11 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   else if (nm == "logp") {
     if (m->ML && !m->have_logp) { pfhip_status st = head_locked(m, s, true); if (st) return st; }
     src = m->logp.p; n = (size_t)m->ML * m->cfg.vocab;
-  } else return fail(PFHIP_ERR_ARG, "unknown tensor name " + nm);
+  }
+  // the last forward's candidates [token rows][k] (k as it was computed); the ids are int32 words in the float buffer
+  else if (nm == "nbest_ids" && m->nbest_k) { src = m->nb_ids.p; n = (size_t)m->ML * m->nbest_k; }
+  else if (nm == "nbest_logp" && m->nbest_k) { src = m->nb_logp.p; n = (size_t)m->ML * m->nbest_k; }
+  else return fail(PFHIP_ERR_ARG, "unknown tensor name " + nm);
   if (n > cap_floats) return fail(PFHIP_ERR_CAPACITY, "dst too small");
   if (n) HIP_TRY(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

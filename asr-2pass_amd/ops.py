@@ -35,6 +35,7 @@ def _lib():
         lib.pfhip_op_attention_hd.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _ci, _vp]
         lib.pfhip_op_cif.argtypes = [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp]
         lib.pfhip_op_logsoftmax_argmax.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
+        lib.pfhip_op_logsoftmax_topk.argtypes = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
         lib.pfhip_op_resample.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]
         _bound = True
     return lib
@@ -266,6 +267,21 @@ def logsoftmax_argmax(logits, V=None, want_logp=True):
     ids = torch.empty(ML, dtype=torch.int32, device=logits.device)
     _ck(_lib().pfhip_op_logsoftmax_argmax(_p(logits), logits.stride(0), ML, V, _p(logp), _p(ids), _stream()), "logsoftmax")
     return logp, ids
+
+
+def logsoftmax_topk(logits, k, V=None, want_logp=True):
+    """The head with the k best columns per row (csrc/topk.hip): (logp or None, ids, topk_ids [ML, k], topk_logp [ML, k]).
+    Raises PfhipError (hipErrorInvalidValue = 1, nothing launched) for k outside 1..8 or V < k."""
+    ML = logits.shape[0]
+    V = logits.shape[1] if V is None else V
+    logp = torch.empty((ML, V), dtype=torch.float32, device=logits.device) if want_logp else None
+    ids = torch.empty(ML, dtype=torch.int32, device=logits.device)
+    kk = max(int(k), 1)
+    topk_ids = torch.empty((ML, kk), dtype=torch.int32, device=logits.device)
+    topk_logp = torch.empty((ML, kk), dtype=torch.float32, device=logits.device)
+    _ck(_lib().pfhip_op_logsoftmax_topk(_p(logits), logits.stride(0), ML, V, int(k), _p(logp), _p(ids), _p(topk_ids), _p(topk_logp),
+                                        _stream()), "logsoftmax_topk")
+    return logp, ids, topk_ids, topk_logp
 
 
 # ---- pre-split operands (csrc/gemm_p3.hip) ------------------------------------------------------------------------------------

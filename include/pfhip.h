@@ -243,6 +243,32 @@ typedef struct {
 } pfhip_hwbank_stats;
 pfhip_status pfhip_hotword_bank_stats(pfhip_model* m, pfhip_hwbank_stats* out);
 
+/* ---- N-best candidates and token confidence (extension) --------------------------------------------
+ * The reference has no counterpart: GreedySearch keeps only the arg-max of each row (paraformer.cpp:386-395), and the only other
+ * way to a token's probability is the whole logp matrix.  Here the head also selects, per token row, the k best columns and their
+ * log-probabilities (topk.hip): larger logit first, equal logits smaller column first (FindMax's rule, util.cpp:63-74), so
+ * ids[.., 0] == token_ids[..], any prefix is the answer for a smaller k, and a value equals the logp entry of its column bit for bit
+ * where both are asked for.  exp(logp[.., 0]) is the token's confidence.  Off (no nb / k = 0), the forward is exactly what it was. */
+typedef struct {
+  int32_t k;        /* 1..8 candidates per token row */
+  int32_t* ids;     /* [batch * max_tokens * k], row-major per utterance like token_ids; rows >= n_fires untouched */
+  float* logp;      /* same shape: log-probabilities, descending; ids[.., 0] == token_ids[..] */
+} pfhip_nbest;
+/* pfhip_offline_forward_hwsets plus the candidates (n_sets = 0: a plain model's call; nb == NULL: exactly
+ * pfhip_offline_forward_hwsets).  max_tokens is out's.  Same route through the merge queue (pfhip_set_batching): callers with
+ * different k share a packed forward that computes the largest, each receives its own first k, and a caller without nb receives
+ * what it always did.  After a range-guard re-run the candidates are the re-run's, like token_ids.  PFHIP_ERR_ARG for k outside
+ * 1..8, a NULL buffer, or a vocabulary smaller than k. */
+pfhip_status pfhip_offline_forward_nbest(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch,
+                                         const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                         pfhip_out* out, const pfhip_nbest* nb);
+/* Device-pointer form: k candidates for every following pfhip_offline_enqueue of this handle (context 0), 0 = off (default).
+ * GreedySearch's arg-max stays what pfhip_offline_fetch returns; the candidates stay in the device workspace beside it. */
+pfhip_status pfhip_set_nbest(pfhip_model* m, int k);
+/* After pfhip_offline_fetch (whose max_tokens lays out the rows here as well): the candidates of that forward, the first nb->k
+ * of the k it computed.  PFHIP_ERR_ARG when the last enqueue computed none (no pfhip_set_nbest) or fewer than nb->k. */
+pfhip_status pfhip_offline_fetch_nbest(pfhip_model* m, const pfhip_nbest* nb);
+
 /* ---- front end only ----------------------------------------------------------------------------
  * Replaces Paraformer::FbankKaldi + LfrCmvn (paraformer.cpp:309-323, 421-461) on their own:
  * feats_out gets sum(n_frames)*feat_dim floats, utterances back to back; n_frames_out [batch]. */

@@ -101,6 +101,12 @@ int pfhip_op_cif(const float* hidden, int ldh, const float* alphas, const int* r
                  float threshold, float tail, float* stage, int* n_fires, int* token_num, void* stream);
 /* LogSoftmax + ArgMax (GreedySearch/FindMax, onnxruntime/src/paraformer.cpp:386-395, util.cpp:63-74). */
 int pfhip_op_logsoftmax_argmax(const float* logits, int ldl, int ML, int V, float* logp, int32_t* ids, void* stream);
+/* The same head with the k best columns of every row (topk.hip; beyond GreedySearch, which keeps only the arg-max): topk_ids /
+ * topk_logp [M][k], larger logit first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry
+ * of its column bit for bit.  logp may be NULL (the log-sum-exp is formed all the same).  hipErrorInvalidValue, before anything is
+ * launched, for k outside 1..8, V < k, ldl < V, M < 0 or a NULL buffer other than logp. */
+int pfhip_op_logsoftmax_topk(const float* logits, int ldl, int M, int V, int k, float* logp, int32_t* ids, int32_t* topk_ids,
+                             float* topk_logp, void* stream);
 
 /* One streaming window (M <= 32 rows): LayerNormalization (g != NULL; width D <= K) -> MatMul/Gemm (+bias, +residual Adds, Relu)
  * (+ the SAN-M FSMN memory of fsmn_v over the M rows, k = 11) in ONE launch — stream_fused.hip. */
