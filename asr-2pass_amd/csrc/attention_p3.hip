@@ -176,6 +176,7 @@ __global__ __launch_bounds__(512, 1) void attention_p3_kernel(
 
   PFHIP_STAMP2
   // ---- SAN-M memory block (attention_x3.hip / rowops.hip fsmn_kernel, same operation order) on v = hi + lo ------------------------
+  // (one of three copies — attention_x3.hip, attention_x6.hip, attention_p3.hip: a shared force-inlined form compiles differently)
   if (fsmn_w && PFHIP_ATTP_ABLATE != 1) {
     constexpr int kTaps = 11, kStrip = 16;
     const int cg = tid & 31, strip = tid >> 5;

@@ -72,6 +72,7 @@ __global__ __launch_bounds__(512, 1) void attention_x3_kernel(
   // encoder layer less.  With mem_accumulate the memory is added straight into the residual stream (mem = x): the output
   // projection that follows — bandwidth-bound at N = K = 512: 128 MB of operand, two residuals and result per 8.4 GFLOP — then
   // reads one residual instead of two; the 33 MB move into this kernel, which has bandwidth to spare.
+  // (one of three copies — attention_x3.hip, attention_x6.hip, attention_p3.hip: a shared force-inlined form compiles differently)
   if (fsmn_w && !kAbNoFsmn) {
     constexpr int kTaps = 11, kStrip = 16;
     const int cg = tid & 31, strip = tid >> 5;

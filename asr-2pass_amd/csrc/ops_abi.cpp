@@ -169,6 +169,15 @@ int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, cons
                              S(stream));
   return done();
 }
+int pfhip_op_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, const int* off,
+                            const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem, int ldmem,
+                            int mem_accumulate, int head_dim, void* stream) {
+  if ((head_dim != 80 && head_dim != 128) || !fsmn_w || !mem || !O || H <= 0 || ldmem < H * head_dim) return (int)hipErrorInvalidValue;
+  pfhip::launch_attention_fsmn(Q, ldq, K, ldk, V, ldv, O, ldo, off, len, B, H, max_len, scale, fsmn_w, mem, ldmem, S(stream), mem_accumulate != 0,
+                               nullptr, nullptr, 0, head_dim);
+  return done();
+}
+int pfhip_op_attention_fsmn_is_fused(int max_len, int head_dim) { return pfhip::attention_fsmn_is_fused(max_len, head_dim) ? 1 : 0; }
 int pfhip_op_attention_planes(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, void* planes_hi, void* planes_lo,
                               int plane_rows, const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                               int max_q_len, int total_q_rows, float scale, void* stream) {

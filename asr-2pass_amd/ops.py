@@ -209,6 +209,25 @@ def attention(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, head_dim=128
     return O
 
 
+def attention_fsmn_is_fused(max_len, head_dim=128):
+    """Whether attention_fsmn runs as the one fused launch (only then is mem_accumulate honoured)."""
+    lib = _lib()
+    lib.pfhip_op_attention_fsmn_is_fused.argtypes = [_ci, _ci]
+    return bool(lib.pfhip_op_attention_fsmn_is_fused(int(max_len), int(head_dim)))
+
+
+def attention_fsmn(Q, K, V, off, length, n_head, scale, fsmn_w, mem, mem_accumulate=False, head_dim=128):
+    """Self-attention and the SAN-M memory block of V in the encoder layer's launch: returns the context (fp32 rows); the memory goes
+    into `mem` (added to it when mem_accumulate and the launch is fused)."""
+    lib = _lib()
+    O = torch.zeros((Q.shape[0], n_head * head_dim), dtype=torch.float32, device=Q.device)
+    lib.pfhip_op_attention_fsmn.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _cf, _vp, _vp, _ci, _ci, _ci, _vp]
+    _ck(lib.pfhip_op_attention_fsmn(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0), _p(off), _p(length),
+                                    off.numel(), n_head, int(length.max().item()), float(scale), _p(fsmn_w), _p(mem), mem.stride(0),
+                                    1 if mem_accumulate else 0, head_dim, _stream()), "attention_fsmn")
+    return O
+
+
 def attention_planes(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale):
     """attention (d_k = 128) with the context as fp16 plane images: returns (hi, lo, rows) as split_planes does."""
     lib = _lib()

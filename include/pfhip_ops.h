@@ -73,6 +73,15 @@ int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const f
 int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                           const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                           int max_q_len, float scale, int head_dim, void* stream);
+/* The encoder layer's pair on one set of self-attention segments (off / len): the SAN-M memory block of V into mem (pfhip_op_fsmn
+ * without a residual) and the attention block's context into O as fp32 rows.  ONE launch — the memory block runs in front of the
+ * attention kernel's key loop — where pfhip_op_attention_fsmn_is_fused(max_len, head_dim) says so; then, and only then,
+ * mem_accumulate adds the memory into mem instead of overwriting it.  Otherwise pfhip_op_fsmn followed by pfhip_op_attention_hd.
+ * head_dim 80 or 128. */
+int pfhip_op_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, const int* off,
+                            const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem, int ldmem,
+                            int mem_accumulate, int head_dim, void* stream);
+int pfhip_op_attention_fsmn_is_fused(int max_len, int head_dim);
 /* The same block (d_k = 128, attention_x3.hip) with the context written as the two fp16 plane images that pfhip_op_gemm_p3 takes as
  * its A operand ([K / 16][plane_rows][16] per plane, K = H * 128; row = q_off[b] + t) instead of fp32 rows: the encoder's
  * attention -> output-projection hand-off on large batches.  total_q_rows = the number of rows the offsets span (<= plane_rows,

@@ -146,6 +146,49 @@ def test_attention_rescale_branch(ops):
     _attn_case(ops, [40], [200], 13, spike=True)
 
 
+def test_attention_self_with_fused_memory_block(ops):
+    """The encoder layer's fused launch (attention_x3.hip; attention_x6.hip under PFHIP_ATT_X3=0; fsmn + attention under PFHIP_ATT_X6=0):
+    the SAN-M memory of V equals the stand-alone fsmn kernel's bit for bit (same operation order; one rounding apart when it is added
+    into the residual stream), the context equals the plain attention launch's bit for bit, rows behind the last utterance are untouched.
+    Lengths: 1 (inside a launch whose longest segment exceeds 64), 65 (the shortest fused launch), 257 (past the 256-query workgroup and
+    a 16-row strip), 300 (partial last key tile, strips that end mid-strip)."""
+    rng = np.random.default_rng(41)
+    H, dk, pad, sentinel = 2, 128, 128, -7.5
+    D = H * dk
+    lens = [1, 65, 257, 300]
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+    M = sum(lens)
+    Q = rng.standard_normal((M, D)).astype(np.float32)
+    K = rng.standard_normal((M, D)).astype(np.float32)
+    V = rng.standard_normal((M, D)).astype(np.float32)
+    X = rng.standard_normal((M, D)).astype(np.float32)
+    w = (rng.standard_normal((D, 11)) / 3).astype(np.float32)
+    dl, doff = dev(np.asarray(lens, np.int32)), dev(off)
+    O = ops.attention(dev(Q), dev(K), dev(V), doff, dl, doff, dl, H, dk ** -0.5).cpu().numpy()
+    for b, (o, L) in enumerate(zip(off, lens)):
+        ref = P.mha(Q[o:o + L].astype(np.float64), K[o:o + L].astype(np.float64), V[o:o + L].astype(np.float64), H)
+        assert np.abs(O[o:o + L] - ref).max() < 2e-5, (b, np.abs(O[o:o + L] - ref).max())
+    fused = ops.attention_fsmn_is_fused(max(lens), dk)
+    for acc in (False, True):
+        if acc and not fused:      # the unfused pair ignores the flag
+            continue
+        mem0 = np.full((M + pad, D), sentinel, np.float32)
+        mem0[:M] = X
+        mem = dev(mem0)
+        ctx = ops.attention_fsmn(dev(Q), dev(K), dev(V), doff, dl, H, dk ** -0.5, dev(w), mem, mem_accumulate=acc).cpu().numpy()
+        got_mem = mem.cpu().numpy()
+        want = ops.fsmn(dev(V), dev(w), doff, dl, res=dev(X) if acc else None).cpu().numpy()
+        if acc:      # x + (v + conv) against (v + conv) + x: one rounding apart
+            assert np.abs(got_mem[:M] - want).max() < 1e-5
+        else:
+            assert np.array_equal(got_mem[:M], want)
+        for o, L in zip(off, lens):
+            ref = P.fsmn(V[o:o + L].astype(np.float64), w.astype(np.float64)) + (X[o:o + L] if acc else 0)
+            assert np.abs(got_mem[o:o + L] - ref).max() < 1e-5
+        assert np.array_equal(ctx, O)      # the memory block does not disturb the attention
+        assert np.all(got_mem[M:] == sentinel)
+
+
 def test_attention_context_as_plane_images(ops):
     """attention_x3.hip writing the context as the fp16 plane images gemm_p3.hip stages by DMA: the decoded planes equal the fp32
     output of the same launch to the planes' 22 bits, rows of other utterances and pad rows untouched, and the images feed the
