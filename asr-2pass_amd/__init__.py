@@ -41,7 +41,28 @@ ABI_SYMBOLS = [
     "pfhip_timestamp_onnx", "pfhip_post_process",
     "pfhip_punc_create_from_memory", "pfhip_punc_destroy", "pfhip_punc_num_classes", "pfhip_punc_infer",
     "pfhip_punc_infer_online", "pfhip_punc_infer_batch", "pfhip_set_punc_batching", "pfhip_punc_add_punc",
+    # 16-bit PCM in: the same calls on int16 samples (s means s / 32768), bit-identical to their f32 siblings
+    "pfhip_offline_forward_s16", "pfhip_offline_forward_hwsets_s16", "pfhip_offline_forward_rate_s16", "pfhip_offline_enqueue_s16",
+    "pfhip_offline_forward_resident_s16", "pfhip_vad_forward_sil_s16", "pfhip_stream_forward_s16", "pfhip_stream_forward_batch_s16",
+    "pfhip_vad_stream_infer_s16", "pfhip_vad_stream_infer_batch_s16",
 ]
+
+
+def _pcm_buffers(din):
+    """The utterances of a call as contiguous arrays of ONE sample format, and whether that format is 16-bit PCM: int16 when every
+    array is np.int16 (the *_s16 entry points take them as they are), float32 otherwise (int16 arrays among floats become
+    s / 32768, which is what the s16 entry points mean by them)."""
+    arrs = [np.asarray(x) for x in din]
+    if arrs and all(a.dtype == np.int16 for a in arrs):
+        return [np.ascontiguousarray(a) for a in arrs], True
+    return [_pcm_f32(a) for a in arrs], False
+
+
+def _pcm_f32(x):
+    x = np.asarray(x)
+    if x.dtype == np.int16:
+        return np.ascontiguousarray(x.astype(np.float32) / np.float32(32768.0))
+    return np.ascontiguousarray(x, dtype=np.float32)
 
 
 class PfhipError(RuntimeError):
@@ -195,6 +216,11 @@ def load_lib() -> ctypes.CDLL:
     lib.pfhip_debug_poke.argtypes = [vp, ctypes.c_char_p, ci]
     lib.pfhip_profile_enable.argtypes = [vp, ci]
     lib.pfhip_profile_read.argtypes = [vp, ctypes.POINTER(_Profile), ci]
+    # 16-bit PCM in: the argument lists of the f32 siblings
+    for f in ("pfhip_offline_forward", "pfhip_offline_forward_hwsets", "pfhip_offline_forward_rate", "pfhip_offline_enqueue",
+              "pfhip_offline_forward_resident", "pfhip_vad_forward_sil", "pfhip_stream_forward", "pfhip_stream_forward_batch",
+              "pfhip_vad_stream_infer", "pfhip_vad_stream_infer_batch"):
+        getattr(lib, f + "_s16").argtypes = getattr(lib, f).argtypes
     _lib = lib
     return lib
 
@@ -417,7 +443,7 @@ class ParaformerHip:
         if B == 0:
             raise PfhipError("empty batch")
         fs_out = self.GetAsrSampleRate()
-        bufs = [np.ascontiguousarray(x, dtype=np.float32) for x in din]
+        bufs = [_pcm_f32(x) for x in din]
         n_out = [resample_len(sample_rate, b.shape[0], fs_out) for b in bufs]
         if min(n_out) < 0:
             raise PfhipError(f"unsupported sample rate {sample_rate}")
@@ -442,7 +468,9 @@ class ParaformerHip:
         B = len(din)
         if B == 0:
             raise PfhipError("empty batch")
-        bufs = [np.ascontiguousarray(x, dtype=np.float32) for x in din]
+        # np.int16 utterances go to the *_s16 entry points as they are (the candidates call has no s16 form: floats there)
+        bufs, s16 = _pcm_buffers(din) if nbest is None else ([_pcm_f32(x) for x in din], False)
+        sfx = "_s16" if s16 else ""
         lens = (ctypes.c_int * B)(*[int(b.shape[0]) for b in bufs])
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
         n_model = [int(b.shape[0]) for b in bufs]
@@ -496,12 +524,13 @@ class ParaformerHip:
             sptr = (ctypes.c_void_p * max(len(sets), 1))(*[h.ctypes.data if h.size else None for h in sets])
             sn = (ctypes.c_int * max(len(sets), 1))(*[int(h.shape[0]) for h in sets])
             sof = (ctypes.c_int * B)(*[int(k) for k in set_of_utt])
-            _check(self._lib, self._lib.pfhip_offline_forward_hwsets(self._h, ptrs, lens, B, sptr, sn, len(sets), sof, ctypes.byref(out)))
+            _check(self._lib, getattr(self._lib, "pfhip_offline_forward_hwsets" + sfx)(self._h, ptrs, lens, B, sptr, sn, len(sets), sof,
+                                                                                       ctypes.byref(out)))
         elif sample_rate is None:
-            _check(self._lib, self._lib.pfhip_offline_forward(self._h, ptrs, lens, B, hw_ptr, n_hw, ctypes.byref(out)))
+            _check(self._lib, getattr(self._lib, "pfhip_offline_forward" + sfx)(self._h, ptrs, lens, B, hw_ptr, n_hw, ctypes.byref(out)))
         else:
-            _check(self._lib, self._lib.pfhip_offline_forward_rate(self._h, ptrs, lens, B, int(sample_rate), hw_ptr, n_hw,
-                                                                   ctypes.byref(out)))
+            _check(self._lib, getattr(self._lib, "pfhip_offline_forward_rate" + sfx)(self._h, ptrs, lens, B, int(sample_rate), hw_ptr, n_hw,
+                                                                                     ctypes.byref(out)))
         res = dict(token_num=tn, n_fires=nf, n_frames=fr,
                    ids=[ids[b, :min(tn[b], nf[b])].copy() for b in range(B)],
                    logp=[logp[b, :nf[b]].copy() for b in range(B)] if want_logp else None)
@@ -530,7 +559,7 @@ class ParaformerHip:
     def extract_feats(self, din: Sequence[np.ndarray]):
         """FbankKaldi + LfrCmvn (paraformer.cpp:309-323, 421-461) on the GPU; list of [T_b, 560]."""
         B = len(din)
-        bufs = [np.ascontiguousarray(x, dtype=np.float32) for x in din]
+        bufs = [_pcm_f32(x) for x in din]
         lens = (ctypes.c_int * B)(*[int(b.shape[0]) for b in bufs])
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
         fd = self._lib.pfhip_feat_dim(self._h)
@@ -551,11 +580,12 @@ class ParaformerHip:
         return buf[:n.value]
 
     # -- device-resident form (bench.py) -------------------------------------------------------------
-    def enqueue_device(self, d_pcm_ptr: int, sample_off: np.ndarray, n_samples: np.ndarray, stream: int = 0):
+    def enqueue_device(self, d_pcm_ptr: int, sample_off: np.ndarray, n_samples: np.ndarray, stream: int = 0, s16: bool = False):
+        """s16: the device buffer holds int16 samples (pfhip_offline_enqueue_s16; sample_off in samples, any alignment)."""
         B = len(n_samples)
         so = np.ascontiguousarray(sample_off, np.int64)
         ns = np.ascontiguousarray(n_samples, np.int32)
-        _check(self._lib, self._lib.pfhip_offline_enqueue(
+        _check(self._lib, (self._lib.pfhip_offline_enqueue_s16 if s16 else self._lib.pfhip_offline_enqueue)(
             self._h, ctypes.c_void_p(d_pcm_ptr), so.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
             ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, ctypes.c_void_p(stream) if stream else None))
 
@@ -586,8 +616,9 @@ class ParaformerHip:
         _check(self._lib, self._lib.pfhip_offline_fetch_nbest(self._h, ctypes.byref(nb)))
         return nb_ids, nb_logp
 
-    def forward_resident(self, d_pcm_ptr: int, sample_off: np.ndarray, n_samples: np.ndarray, max_tokens: int):
-        """pfhip_offline_forward_resident: PCM already in HBM, routed over the handle's execution contexts like Forward."""
+    def forward_resident(self, d_pcm_ptr: int, sample_off: np.ndarray, n_samples: np.ndarray, max_tokens: int, s16: bool = False):
+        """pfhip_offline_forward_resident: PCM already in HBM, routed over the handle's execution contexts like Forward.
+        s16: the device buffer holds int16 samples (pfhip_offline_forward_resident_s16)."""
         B = len(n_samples)
         so = np.ascontiguousarray(sample_off, np.int64)
         ns = np.ascontiguousarray(n_samples, np.int32)
@@ -602,7 +633,7 @@ class ParaformerHip:
         out.n_frames = fr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         out.logp = None
         out.max_tokens = max_tokens
-        _check(self._lib, self._lib.pfhip_offline_forward_resident(
+        _check(self._lib, (self._lib.pfhip_offline_forward_resident_s16 if s16 else self._lib.pfhip_offline_forward_resident)(
             self._h, ctypes.c_void_p(d_pcm_ptr), so.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
             ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, ctypes.byref(out)))
         return dict(token_num=tn, n_fires=nf, n_frames=fr, ids=[ids[b, :min(tn[b], nf[b])].copy() for b in range(B)])
@@ -659,10 +690,10 @@ class ParaformerOnlineHip:
         return int(self._lib.pfhip_stream_last_path(self._h))
 
     def Forward(self, din, len_=None, input_finished=False, cap=256):
-        x = np.ascontiguousarray(din if len_ is None else np.asarray(din)[:len_], dtype=np.float32)
+        (x,), s16 = _pcm_buffers([din if len_ is None else np.asarray(din)[:len_]])
         ids = np.zeros(max(cap, 1), np.int32)
         n = ctypes.c_int(0)
-        _check(self._lib, self._lib.pfhip_stream_forward(self._h, x.ctypes.data if x.size else None, int(x.size),
+        _check(self._lib, (self._lib.pfhip_stream_forward_s16 if s16 else self._lib.pfhip_stream_forward)(self._h, x.ctypes.data if x.size else None, int(x.size),
                                                          1 if input_finished else 0, ids.ctypes.data, int(cap), ctypes.byref(n)))
         return [int(v) for v in ids[:n.value]]
 
@@ -676,7 +707,7 @@ class ParaformerOnlineHip:
         if B == 0:
             return []
         lib = streams[0]._lib
-        bufs = [np.ascontiguousarray(x, dtype=np.float32) for x in dins]
+        bufs, s16 = _pcm_buffers(dins)
         hs = (ctypes.c_void_p * B)(*[s._h for s in streams])
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data if b.size else None for b in bufs])
         lens = (ctypes.c_int * B)(*[int(b.size) for b in bufs])
@@ -685,7 +716,7 @@ class ParaformerOnlineHip:
         idp = (ctypes.c_void_p * B)(*[ids[i].ctypes.data for i in range(B)])
         ccaps = (ctypes.c_int * B)(*([256] * B if caps is None else [int(c) for c in caps]))
         nt = (ctypes.c_int * B)()
-        st = lib.pfhip_stream_forward_batch(hs, B, ptrs, lens, fin, idp, ccaps, nt)
+        st = (lib.pfhip_stream_forward_batch_s16 if s16 else lib.pfhip_stream_forward_batch)(hs, B, ptrs, lens, fin, idp, ccaps, nt)
         if caps is not None:
             return st, [[int(v) for v in ids[i, :min(nt[i], ccaps[i])]] for i in range(B)], [int(v) for v in nt]
         _check(lib, st)
@@ -733,17 +764,17 @@ class FsmnVadHip:
         _check(self._lib, self._lib.pfhip_set_vad_stream_batching(self._h, int(wait_us), int(max_streams)))
 
     def ForwardSil(self, waves, is_final=False):
-        """Frame-wise silence posterior only (what E2EVadModel reads)."""
-        x = np.ascontiguousarray(waves, dtype=np.float32)
+        """Frame-wise silence posterior only (what E2EVadModel reads).  np.int16 waves go to pfhip_vad_forward_sil_s16."""
+        (x,), s16 = _pcm_buffers([waves])
         cap = max(0, (x.size - 400) // 160 + 1) + 1
         sil = np.zeros(cap, np.float32)
         n = ctypes.c_int(0)
-        _check(self._lib, self._lib.pfhip_vad_forward_sil(self._h, x.ctypes.data if x.size else None, int(x.size),
+        _check(self._lib, (self._lib.pfhip_vad_forward_sil_s16 if s16 else self._lib.pfhip_vad_forward_sil)(self._h, x.ctypes.data if x.size else None, int(x.size),
                                                           1 if is_final else 0, sil.ctypes.data, cap, ctypes.byref(n)))
         return sil[:n.value]
 
     def Forward(self, waves, is_final=False):
-        x = np.ascontiguousarray(waves, dtype=np.float32)
+        x = _pcm_f32(waves)
         C = self._lib.pfhip_vad_num_classes(self._h)
         cap = (max(0, (x.size - 400) // 160 + 1) + 1) * C
         probs = np.zeros(cap, np.float32)
@@ -850,12 +881,12 @@ class FsmnVadOnlineHip:
         self.vad_silence_duration_, self.vad_max_len_ = vad_tail_sil, vad_max_len
 
     def InferScores(self, waves, input_finished=False):
-        x = np.ascontiguousarray(waves, dtype=np.float32)
+        (x,), s16 = _pcm_buffers([waves])
         cap = x.size // 160 + 16
         sil = np.zeros(cap, np.float32)
         wv = np.zeros(x.size + 2048, np.float32)
         nf, nw = ctypes.c_int(0), ctypes.c_int(0)
-        _check(self._lib, self._lib.pfhip_vad_stream_infer(self._h, x.ctypes.data if x.size else None, int(x.size),
+        _check(self._lib, (self._lib.pfhip_vad_stream_infer_s16 if s16 else self._lib.pfhip_vad_stream_infer)(self._h, x.ctypes.data if x.size else None, int(x.size),
                                                            1 if input_finished else 0, sil.ctypes.data, cap, ctypes.byref(nf),
                                                            wv.ctypes.data, wv.size, ctypes.byref(nw)))
         return sil[:nf.value].copy(), wv[:nw.value].copy()
@@ -865,7 +896,7 @@ class FsmnVadOnlineHip:
         """InferScores of several connections (of one FsmnVadHip) as one device pass; returns [(sil, waveform), ...]."""
         n = len(streams)
         lib = streams[0]._lib
-        xs = [np.ascontiguousarray(w, dtype=np.float32) for w in waves]
+        xs, s16 = _pcm_buffers(waves)
         sils = [np.zeros(x.size // 160 + 16, np.float32) for x in xs]
         wvs = [np.zeros(x.size + 2048, np.float32) for x in xs]
         P = ctypes.c_void_p * n
@@ -878,7 +909,8 @@ class FsmnVadOnlineHip:
         pw = P(*[a.ctypes.data for a in wvs])
         wcaps = (ctypes.c_size_t * n)(*[a.size for a in wvs])
         nf, nw = (ctypes.c_int * n)(), (ctypes.c_int * n)()
-        _check(lib, lib.pfhip_vad_stream_infer_batch(h, n, px, ns, fin, ps, caps, nf, pw, wcaps, nw))
+        _check(lib, (lib.pfhip_vad_stream_infer_batch_s16 if s16 else lib.pfhip_vad_stream_infer_batch)(h, n, px, ns, fin, ps, caps, nf, pw,
+                                                                                                       wcaps, nw))
         return [(sils[i][:nf[i]].copy(), wvs[i][:nw[i]].copy()) for i in range(n)]
 
     def Infer(self, waves, input_finished=False):

@@ -17,7 +17,7 @@
 // it will transform, the neighbour of the pre-emphasis comes over DPP (row_shr / row_ror inside the 16-lane row).
 //
 // Built with -ffp-contract=off so that a*b+c sequences round exactly like the reference's scalar code.
-// HBM-bound: 4*S bytes in, 4*560*T out per utterance; the 400-sample windows overlap
+// HBM-bound: 4*S bytes in (2*S from 16-bit PCM), 4*560*T out per utterance; the 400-sample windows overlap
 // 240/400, the re-reads are served by L2.
 #include "kernels.h"
 
@@ -27,8 +27,11 @@ namespace pfhip {
 
 namespace {
 
+// Sample: float (samples in [-1, 1), scaled by 32768 on load as the reference does) or int16_t (16-bit PCM as it arrives: the
+// sample s stands for s / 32768.f, and s / 32768.f * 32768.f == (float)s exactly, so the s16 form loads (float)s with no multiply)
+template <typename Sample>
 struct FbankParams {
-  const float* pcm;
+  const Sample* pcm;
   const int64_t* sample_off;
   const int* frame_off;
   const int* nframes;
@@ -102,7 +105,15 @@ __device__ __forceinline__ float row_ror1(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xF, 0xF, false));
 }
 
-__global__ __launch_bounds__(256) void fbank_lfr_cmvn_kernel(FbankParams p) {
+__device__ __forceinline__ float load_x32768(const float* x, int i) { return x[i] * 32768.f; }
+// Written as 2-byte loads and never cast to a wider type: a packed s16 utterance may start at an odd sample offset, so the address
+// is only known to be 2-byte aligned.  The compiler is free to fetch x[i] and x[i + 1] with one 4-byte load at that address (it does
+// for most pairs, splitting the halves afterwards) because gfx950 global loads need no natural alignment; it reads no byte the
+// source does not name, so nothing outside the frame's 400 samples is touched.
+__device__ __forceinline__ float load_x32768(const int16_t* x, int i) { return (float)x[i]; }
+
+template <typename Sample>
+__global__ __launch_bounds__(256) void fbank_lfr_cmvn_kernel(FbankParams<Sample> p) {
   __shared__ double ex[4][4][256];        // [wave][frame of the wave][256 doubles]: 32 KB, four workgroups per CU.  Exchanges move
                                           // the real parts, then the imaginary parts, through the same 2 KB of a frame.
 
@@ -125,7 +136,7 @@ __global__ __launch_bounds__(256) void fbank_lfr_cmvn_kernel(FbankParams p) {
   }
   const int f = gg - p.frame_off[b];
   const int F = p.nframes[b];
-  const float* x = p.pcm + p.sample_off[b] + (int64_t)f * kFrameShift;
+  const Sample* x = p.pcm + p.sample_off[b] + (int64_t)f * kFrameShift;
 
   // ---- window extraction (samples 32 n1 + 2 l and + 1), x32768, DC removal ------------------------------------------------------
   float ze[13], zo[13];
@@ -134,8 +145,8 @@ __global__ __launch_bounds__(256) void fbank_lfr_cmvn_kernel(FbankParams p) {
   for (int n1 = 0; n1 < 13; ++n1) {
     const int i = 32 * n1 + 2 * l;
     const bool ok = i < kFrameLen;                 // i is even and the frame length is even: i + 1 is valid with i
-    ze[n1] = ok ? x[i] * 32768.f : 0.f;
-    zo[n1] = ok ? x[i + 1] * 32768.f : 0.f;
+    ze[n1] = ok ? load_x32768(x, i) : 0.f;
+    zo[n1] = ok ? load_x32768(x, i + 1) : 0.f;
     s += ze[n1];
     s += zo[n1];
   }
@@ -282,27 +293,44 @@ __global__ __launch_bounds__(256) void fbank_lfr_cmvn_kernel(FbankParams p) {
 
 }  // namespace
 
+namespace {
+template <typename Sample>
+void launch_fbank(const Sample* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, const int* row_off, int B,
+                  int total_frames, FbankTables tb, float* feats, float* fb_out, hipStream_t s) {
+  if (total_frames <= 0) return;
+  FbankParams<Sample> p{pcm, sample_off, frame_off, nframes, row_off, B, total_frames, tb, feats, fb_out};
+  const int blocks = (total_frames + kFramesPerBlock - 1) / kFramesPerBlock;
+  hipLaunchKernelGGL(fbank_lfr_cmvn_kernel<Sample>, dim3(blocks), dim3(256), 0, s, p);
+}
+}  // namespace
+
 void launch_fbank_lfr_cmvn(const float* pcm, const int64_t* sample_off, const int* frame_off,
                            const int* nframes, const int* row_off, int B, int total_frames,
                            FbankTables tb, float* feats, hipStream_t s) {
-  if (total_frames <= 0) return;
-  FbankParams p{pcm, sample_off, frame_off, nframes, row_off, B, total_frames, tb, feats, nullptr};
-  const int blocks = (total_frames + kFramesPerBlock - 1) / kFramesPerBlock;
-  hipLaunchKernelGGL(fbank_lfr_cmvn_kernel, dim3(blocks), dim3(256), 0, s, p);
+  launch_fbank(pcm, sample_off, frame_off, nframes, row_off, B, total_frames, tb, feats, nullptr, s);
+}
+void launch_fbank_lfr_cmvn(const int16_t* pcm, const int64_t* sample_off, const int* frame_off,
+                           const int* nframes, const int* row_off, int B, int total_frames,
+                           FbankTables tb, float* feats, hipStream_t s) {
+  launch_fbank(pcm, sample_off, frame_off, nframes, row_off, B, total_frames, tb, feats, nullptr, s);
 }
 
 void launch_fbank_frames(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes,
                          int total_frames, FbankTables tb, float* fb_out, hipStream_t s) {
-  if (total_frames <= 0) return;
-  FbankParams p{pcm, sample_off, frame_off, nframes, nullptr, 1, total_frames, tb, nullptr, fb_out};
-  hipLaunchKernelGGL(fbank_lfr_cmvn_kernel, dim3((total_frames + kFramesPerBlock - 1) / kFramesPerBlock), dim3(256), 0, s, p);
+  launch_fbank(pcm, sample_off, frame_off, nframes, nullptr, 1, total_frames, tb, nullptr, fb_out, s);
+}
+void launch_fbank_frames(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes,
+                         int total_frames, FbankTables tb, float* fb_out, hipStream_t s) {
+  launch_fbank(pcm, sample_off, frame_off, nframes, nullptr, 1, total_frames, tb, nullptr, fb_out, s);
 }
 
 void launch_fbank_frames_batch(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
                                int total_frames, FbankTables tb, float* fb_out, hipStream_t s) {
-  if (total_frames <= 0) return;
-  FbankParams p{pcm, sample_off, frame_off, nframes, nullptr, B, total_frames, tb, nullptr, fb_out};
-  hipLaunchKernelGGL(fbank_lfr_cmvn_kernel, dim3((total_frames + kFramesPerBlock - 1) / kFramesPerBlock), dim3(256), 0, s, p);
+  launch_fbank(pcm, sample_off, frame_off, nframes, nullptr, B, total_frames, tb, nullptr, fb_out, s);
+}
+void launch_fbank_frames_batch(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                               int total_frames, FbankTables tb, float* fb_out, hipStream_t s) {
+  launch_fbank(pcm, sample_off, frame_off, nframes, nullptr, B, total_frames, tb, nullptr, fb_out, s);
 }
 
 // ---- embed: x*sqrt(d_model) + sinusoidal PE (paraformer-online.cpp:549-555, 240-268) ----------

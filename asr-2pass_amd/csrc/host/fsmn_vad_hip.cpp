@@ -71,6 +71,13 @@ void FsmnVadHip::Reset() {
 }
 
 std::vector<std::vector<int>> FsmnVadHip::Infer(std::vector<float>& waves, bool input_finished) {
+  return InferAny(nullptr, waves, input_finished);
+}
+std::vector<std::vector<int>> FsmnVadHip::InferPcm16(const int16_t* pcm16, std::vector<float>& waves, bool input_finished) {
+  return InferAny(pcm16, waves, input_finished);
+}
+
+std::vector<std::vector<int>> FsmnVadHip::InferAny(const int16_t* pcm16, std::vector<float>& waves, bool input_finished) {
   const int n = (int)waves.size();
   const int max_frames = n >= 400 ? (n - 400) / 160 + 1 : 0;
   if (max_frames <= 0) return {};                           // no full window: no features (:245-247)
@@ -78,7 +85,9 @@ std::vector<std::vector<int>> FsmnVadHip::Infer(std::vector<float>& waves, bool 
   int T = 0;
   {
     std::lock_guard<std::mutex> lk(mu_);
-    if (pfhip_vad_forward_sil(handle_, waves.data(), n, input_finished ? 1 : 0, sil.data(), sil.size(), &T) != PFHIP_OK) {
+    const pfhip_status fs = pcm16 ? pfhip_vad_forward_sil_s16(handle_, pcm16, n, input_finished ? 1 : 0, sil.data(), sil.size(), &T)
+                                  : pfhip_vad_forward_sil(handle_, waves.data(), n, input_finished ? 1 : 0, sil.data(), sil.size(), &T);
+    if (fs != PFHIP_OK) {
       std::fprintf(stderr, "FsmnVadHip::Infer: %s\n", pfhip_last_error());
       return {};
     }
@@ -112,11 +121,21 @@ void FsmnVadOnlineHip::Reset() {
 }
 
 std::vector<std::vector<int>> FsmnVadOnlineHip::Infer(std::vector<float>& waves, bool input_finished) {
-  if (!ok()) return {};
-  std::vector<float> sil(waves.size() / 160 + 16), wv(waves.size() + 4096);
+  return InferAny(waves.data(), nullptr, (int)waves.size(), input_finished);
+}
+std::vector<std::vector<int>> FsmnVadOnlineHip::InferPcm16(const int16_t* pcm16, int n, bool input_finished) {
+  return InferAny(nullptr, pcm16, n, input_finished);
+}
+
+std::vector<std::vector<int>> FsmnVadOnlineHip::InferAny(const float* f32, const int16_t* pcm16, int n, bool input_finished) {
+  if (!ok() || n < 0) return {};
+  std::vector<float> sil((size_t)n / 160 + 16), wv((size_t)n + 4096);
   int nf = 0, nw = 0;
-  if (pfhip_vad_stream_infer(stream_, waves.data(), (int)waves.size(), input_finished ? 1 : 0, sil.data(), sil.size(), &nf, wv.data(),
-                             wv.size(), &nw) != PFHIP_OK) {
+  const pfhip_status is = pcm16 ? pfhip_vad_stream_infer_s16(stream_, pcm16, n, input_finished ? 1 : 0, sil.data(), sil.size(), &nf,
+                                                             wv.data(), wv.size(), &nw)
+                                : pfhip_vad_stream_infer(stream_, f32, n, input_finished ? 1 : 0, sil.data(), sil.size(), &nf, wv.data(),
+                                                         wv.size(), &nw);
+  if (is != PFHIP_OK) {
     std::fprintf(stderr, "FsmnVadOnlineHip::Infer: %s\n", pfhip_last_error());
     return {};
   }

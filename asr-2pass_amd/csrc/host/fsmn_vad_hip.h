@@ -44,6 +44,10 @@ class FsmnVadHip : public VadModelHipBase {
   // fsmn-vad.cpp:240-256: scores of the whole buffer, a FRESH detector run with is_final = true, online = false.
   // The network caches carry over between calls unless input_finished (Forward, :129-134); Reset() zeroes them.
   std::vector<std::vector<int>> Infer(std::vector<float>& waves, bool input_finished = true) override;
+  // The same on 16-bit PCM as it arrives (not a virtual: funasr::VadModel's table is untouched): the device scores `pcm16`
+  // (pfhip_vad_forward_sil_s16, bit for bit the scores of Infer); `waves` are the same waves.size() samples / 32768, which only the
+  // detector's decibel track reads on the host.
+  std::vector<std::vector<int>> InferPcm16(const int16_t* pcm16, std::vector<float>& waves, bool input_finished = true);
   int GetVadSampleRate() override { return 16000; }
   void SetConfig(int vad_tail_sil, int vad_max_len) override { vad_silence_duration_ = vad_tail_sil; vad_max_len_ = vad_max_len; }
   void Reset();
@@ -53,6 +57,7 @@ class FsmnVadHip : public VadModelHipBase {
   float vad_speech_noise_thres_ = 0.9f;
 
  private:
+  std::vector<std::vector<int>> InferAny(const int16_t* pcm16, std::vector<float>& waves, bool input_finished);
   pfhip_vad* handle_ = nullptr;
   std::mutex mu_;                        // the offline object keeps per-file caches: one file at a time
   int device_ = 0;
@@ -64,12 +69,15 @@ class FsmnVadOnlineHip : public VadModelHipBase {
   ~FsmnVadOnlineHip() override;
   void InitVad(const std::string&, const std::string&, const std::string&, int) override {}     // fsmn-vad-online.h:31
   std::vector<std::vector<int>> Infer(std::vector<float>& waves, bool input_finished = true) override;
+  // the same on the n 16-bit samples of a message as they arrive (pfhip_vad_stream_infer_s16 hands the detector its float waveform)
+  std::vector<std::vector<int>> InferPcm16(const int16_t* pcm16, int n, bool input_finished = true);
   int GetVadSampleRate() override { return 16000; }
   void SetConfig(int vad_tail_sil, int vad_max_len) override { vad_silence_duration_ = vad_tail_sil; vad_max_len_ = vad_max_len; }
   void Reset();                                               // Reset + ResetCache + a fresh detector (:160-163)
   bool ok() const { return stream_ != nullptr && scorer_ != nullptr; }
 
  private:
+  std::vector<std::vector<int>> InferAny(const float* f32, const int16_t* pcm16, int n, bool input_finished);
   pfhip_vad_stream* stream_ = nullptr;
   pfhip_vadseg* scorer_ = nullptr;
   int vad_silence_duration_, vad_max_len_;

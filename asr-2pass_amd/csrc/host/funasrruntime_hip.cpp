@@ -48,7 +48,8 @@ constexpr int kSegSample = 16;      // samples per ms at 16 kHz (audio.cpp: seg_
 
 // Audio::CutSplit (audio.cpp:1172-1240): the FSMN-VAD scores the whole buffer in one pass (it is causal: the reference's
 // 1-s slices carry the same cache state), the end-point detector runs on the host, segments come back in ms.
-bool CutSplit(OfflineStreamHip* os, std::vector<float>& pcm, int vad_tail_sil, int vad_max_len,
+// pcm16 (may be null): the same samples as 16-bit PCM; the device then scores those and `pcm` only feeds the decibel track.
+bool CutSplit(OfflineStreamHip* os, std::vector<float>& pcm, const int16_t* pcm16, int vad_tail_sil, int vad_max_len,
               std::vector<std::pair<int, int>>& frames, std::vector<int>& index_vector) {
   frames.clear();
   index_vector.clear();
@@ -58,7 +59,7 @@ bool CutSplit(OfflineStreamHip* os, std::vector<float>& pcm, int vad_tail_sil, i
     std::lock_guard<std::mutex> lk(os->vad_mu);
     os->vad->Reset();
     os->vad->SetConfig(vad_tail_sil, vad_max_len);
-    segs = os->vad->Infer(pcm, true);
+    segs = pcm16 ? os->vad->InferPcm16(pcm16, pcm, true) : os->vad->Infer(pcm, true);
   }
   for (const std::vector<int>& sg : segs) frames.emplace_back(sg[0] * kSegSample, std::min(sg[1] * kSegSample, n));
   index_vector.resize(frames.size());
@@ -149,6 +150,18 @@ FUNASR_HANDLE FunOfflineInit(std::map<std::string, std::string>& model_path, int
 // Audio::LoadPcmwav / LoadPcmwavOnline (audio.cpp:787-857): s16 LE -> f32 / 32768, then Audio::WavResample (:259-284) when the
 // caller's rate is not the model's — on the GPU (pfhip_resample), a fresh resampler with flush per buffer as the reference builds
 // one per call.  False for a rate the resampler refuses.
+// The 16-bit samples of a little-endian s16 buffer, host-endian and 2-byte aligned: the caller's own bytes where they already are
+// that (every supported host is little-endian), else a copy in `store`.
+static const int16_t* Pcm16View(const char* buf, int n, std::vector<int16_t>& store) {
+  const uint16_t probe = 1;
+  const bool little = *reinterpret_cast<const uint8_t*>(&probe) == 1;
+  if (little && (reinterpret_cast<uintptr_t>(buf) & 1) == 0) return reinterpret_cast<const int16_t*>(buf);
+  store.resize((size_t)n);
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(buf);
+  for (int i = 0; i < n; ++i) store[i] = (int16_t)((b[2 * i + 1] << 8) | b[2 * i]);
+  return store.data();
+}
+
 static bool LoadPcm(pfhip_model* m, const char* buf, int n_len, int sampling_rate, std::vector<float>& out) {
   const int n = n_len / 2;
   std::vector<float> pcm((size_t)n);
@@ -176,21 +189,46 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   if (!os || !sz_buf) return nullptr;
   if (wav_format != "pcm" && wav_format != "PCM") return nullptr;      // the reference decodes other containers with ffmpeg
   // Audio::LoadPcmwav (audio.cpp:787-819); from here on samples, segments and stamps are at the model's rate (GetTimeLen
-  // divides by dest_sample_rate, audio.cpp:254-257)
-  std::vector<float> pcm;
-  if (!LoadPcm(os->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
-    std::fprintf(stderr, "FunOfflineInferBuffer: %s\n", pfhip_last_error());
-    return nullptr;
-  }
-  const int n = (int)pcm.size();
+  // divides by dest_sample_rate, audio.cpp:254-257).
+  // The acoustic model (and the VAD network) take the caller's 16-bit samples as they are:
+  //   * at the model's rate, every segment is a range of the caller's buffer (ParaformerHip::ForwardPcm16); the host float copy is
+  //     made only for the end-point detector's decibel track, i.e. only with a VAD;
+  //   * at another rate WITHOUT a VAD the one segment is the whole buffer: it goes to the device as s16 and is resampled there
+  //     (pfhip_offline_forward_rate_s16), no float copy at all;
+  //   * at another rate WITH a VAD the segments are ranges of the RESAMPLED waveform, which the detector needs on the host anyway:
+  //     that path stays on floats (LoadPcm).
+  // N-best candidates have no s16 form in the C ABI: with FunOfflineSetNbest the float path is kept as well.
   const int model_rate = os->asr.GetAsrSampleRate();
+  const int n_in = n_len / 2;
+  const bool same_rate = sampling_rate == model_rate;
+  const bool use16 = os->asr.GetNbest() == 0 && (same_rate || !os->vad);
+  std::vector<int16_t> store16;
+  const int16_t* pcm16 = use16 ? Pcm16View(sz_buf, n_in, store16) : nullptr;
+  std::vector<float> pcm;
+  int n;
+  if (use16 && !same_rate) {                         // whole buffer, resampled on the device
+    const int64_t n_rs = pfhip_resample_len(sampling_rate, model_rate, n_in);
+    if (n_rs < 0 || n_rs > INT32_MAX) {
+      std::fprintf(stderr, "FunOfflineInferBuffer: unsupported sample rate %d\n", sampling_rate);
+      return nullptr;
+    }
+    n = (int)n_rs;
+  } else if (use16 && !os->vad) {
+    n = n_in;
+  } else {
+    if (!LoadPcm(os->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
+      std::fprintf(stderr, "FunOfflineInferBuffer: %s\n", pfhip_last_error());
+      return nullptr;
+    }
+    n = (int)pcm.size();
+  }
   auto res = std::make_unique<RecogResult>();
   res->snippet_time = (float)n / (float)model_rate;
   if (n == 0) return res.release();
   std::vector<int> index_vector = {0};
   res->segs.assign(1, {0, n});
   if (os->vad) {
-    if (!CutSplit(os, pcm, vad_tail_sil, vad_max_len, res->segs, index_vector)) {
+    if (!CutSplit(os, pcm, pcm16, vad_tail_sil, vad_max_len, res->segs, index_vector)) {
       std::fprintf(stderr, "FunOfflineInferBuffer: %s\n", pfhip_last_error());
       return res.release();
     }
@@ -204,12 +242,16 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   int step = 0;
   while (FetchDynamic(res->segs, index_vector, head, batch_size, batch) > 0) {
     std::vector<float*> buff(batch.size());
+    std::vector<const int16_t*> buff16(batch.size());
     std::vector<int> len(batch.size());
     for (size_t k = 0; k < batch.size(); ++k) {
-      buff[k] = pcm.data() + res->segs[batch[k]].first;
-      len[k] = res->segs[batch[k]].second - res->segs[batch[k]].first;
+      if (pcm16) buff16[k] = pcm16 + (same_rate ? res->segs[batch[k]].first : 0);
+      else buff[k] = pcm.data() + res->segs[batch[k]].first;
+      len[k] = same_rate || !pcm16 ? res->segs[batch[k]].second - res->segs[batch[k]].first : n_in;
     }
-    const std::vector<std::string> msg_batch = os->asr.Forward(buff.data(), len.data(), true, hw_emb, nullptr, (int)batch.size());
+    const std::vector<std::string> msg_batch =
+        pcm16 ? os->asr.ForwardPcm16(buff16.data(), len.data(), true, hw_emb, nullptr, (int)batch.size(), same_rate ? 0 : sampling_rate)
+              : os->asr.Forward(buff.data(), len.data(), true, hw_emb, nullptr, (int)batch.size());
     for (size_t k = 0; k < batch.size(); ++k, ++msg_idx) {        // funasrruntime.cpp:270-279
       const int seg = index_vector[msg_idx];
       msgs[seg] = msg_batch[k];
@@ -366,11 +408,20 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
   res->snippet_time = os->audio.GetTimeLen();
   // FsmnVadOnline::Infer (fsmn-vad-online.cpp:135-151) as the VAD of Audio::Split
   os->vad_online->SetConfig(vad_tail_sil, vad_max_len);
-  auto vad_infer = [&](std::vector<float>& waves, bool fin) { return os->vad_online->Infer(waves, fin); };
+  // at 16 kHz the message's own 16-bit samples go to the VAD network (Split hands the callable exactly this message's samples as
+  // floats; the detector gets its float waveform back from the device call), to the streaming model and to the offline model
+  std::vector<int16_t> store16;
+  const int16_t* msg16 = sampling_rate == 16000 ? Pcm16View(sz_buf, n_len / 2, store16) : nullptr;
+  auto vad_infer = [&](std::vector<float>& waves, bool fin) {
+    if (msg16 && (int)waves.size() == n_len / 2) return os->vad_online->InferPcm16(msg16, n_len / 2, fin);
+    return os->vad_online->Infer(waves, fin);
+  };
   os->audio.Split(vad_infer, os->asr_online->chunk_len, input_finished, (pfhip_host::AsrType)mode);
   pfhip_host::TpassFrame frame;
   while (os->audio.FetchChunck(frame)) {                                            // funasrruntime.cpp:538-566
-    const std::string msg = os->asr_online->Forward(frame.data.data(), (int)frame.data.size(), frame.is_final);      // :540
+    const std::string msg = frame.pcm16.size() == frame.data.size() && !frame.data.empty()
+                                ? os->asr_online->ForwardPcm16(frame.pcm16.data(), (int)frame.pcm16.size(), frame.is_final)
+                                : os->asr_online->Forward(frame.data.data(), (int)frame.data.size(), frame.is_final);      // :540
     res->online_ids.insert(res->online_ids.end(), os->asr_online->LastTokenIds().begin(), os->asr_online->LastTokenIds().end());
     if (mode == ASR_ONLINE) {
       os->asr_online->online_res += msg;
@@ -388,7 +439,10 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
   while (os->audio.FetchTpass(frame)) {                                             // funasrruntime.cpp:570-639
     float* buff[1] = {frame.data.data()};
     int len[1] = {(int)frame.data.size()};
-    const std::vector<std::string> msgs = ts->asr.Forward(buff, len, true, hw_emb, nullptr, 1);
+    const int16_t* buff16[1] = {frame.pcm16.data()};
+    const std::vector<std::string> msgs = frame.pcm16.size() == frame.data.size() && !frame.data.empty() && ts->asr.GetNbest() == 0
+                                              ? ts->asr.ForwardPcm16(buff16, len, true, hw_emb, nullptr, 1)
+                                              : ts->asr.Forward(buff, len, true, hw_emb, nullptr, 1);
     std::string msg = msgs.empty() ? "" : msgs[0];
     if (msg.empty()) continue;
     const size_t bar = msg.find(" | ");

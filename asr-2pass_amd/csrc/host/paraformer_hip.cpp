@@ -2,6 +2,7 @@
 
 #include "postprocess.h"
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -232,6 +233,41 @@ std::string ParaformerHip::IdsToString(const std::vector<int>& ids) {
 std::vector<std::string> ParaformerHip::Forward(float** din, int* len, bool input_finished,
                                                 const std::vector<std::vector<float>>& hw_emb, void* wfst_decoder,
                                                 int batch_in) {
+  return ForwardAny(reinterpret_cast<const void* const*>(din), false, len, input_finished, hw_emb, wfst_decoder, batch_in, 0);
+}
+
+std::vector<std::string> ParaformerHip::ForwardPcm16(const int16_t* const* din, const int* len, bool input_finished,
+                                                     const std::vector<std::vector<float>>& hw_emb, void* wfst_decoder, int batch_in,
+                                                     int sample_rate) {
+  if (sample_rate == GetAsrSampleRate()) sample_rate = 0;
+  if (nbest_k_ && sample_rate) {      // neither the candidates call nor the resampling call has the other's form
+    std::fprintf(stderr, "ParaformerHip::ForwardPcm16: SetNbest and a sample rate other than the model's exclude each other\n");
+    const size_t n_res = batch_in > 0 ? (size_t)batch_in : 0;
+    tl_last_ids.assign(n_res, {});
+    tl_last_spans.assign(n_res, {});
+    tl_last_nbest_ids.assign(n_res, {});
+    tl_last_nbest_logp.assign(n_res, {});
+    tl_last_conf.assign(n_res, {});
+    return std::vector<std::string>(n_res);      // "" per item, as every failed Forward
+  }
+  if (nbest_k_ && batch_in > 0 && din && len) {      // pfhip_offline_forward_nbest takes floats only
+    std::vector<std::vector<float>> f((size_t)batch_in);
+    std::vector<const void*> ptrs((size_t)batch_in);
+    for (int i = 0; i < batch_in; ++i) {
+      f[i].resize((size_t)(len[i] > 0 ? len[i] : 0));
+      for (size_t j = 0; j < f[i].size(); ++j) f[i][j] = (float)din[i][j] / 32768.f;
+      ptrs[i] = f[i].data();
+    }
+    return ForwardAny(ptrs.data(), false, len, input_finished, hw_emb, wfst_decoder, batch_in, 0);
+  }
+  return ForwardAny(reinterpret_cast<const void* const*>(din), true, len, input_finished, hw_emb, wfst_decoder, batch_in, sample_rate);
+}
+
+std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, bool s16, const int* len, bool input_finished,
+                                                   const std::vector<std::vector<float>>& hw_emb, void* wfst_decoder, int batch_in,
+                                                   int sample_rate) {
+  const float* const* din = reinterpret_cast<const float* const*>(din_any);
+  const int16_t* const* din16 = reinterpret_cast<const int16_t* const*>(din_any);
   std::vector<std::string> results(batch_in > 0 ? batch_in : 0);
   tl_last_ids.assign(results.size(), {});
   tl_last_spans.assign(results.size(), {});
@@ -243,6 +279,14 @@ std::vector<std::string> ParaformerHip::Forward(float** din, int* len, bool inpu
   Decoder* decoder = has_lm_ ? static_cast<Decoder*>(wfst_decoder) : nullptr;
   int max_len = 0;
   for (int i = 0; i < batch_in; ++i) max_len = len[i] > max_len ? len[i] : max_len;
+  if (sample_rate) {                              // the model sees the resampled length
+    const int64_t n_rs = pfhip_resample_len(sample_rate, GetAsrSampleRate(), max_len);
+    if (n_rs < 0 || n_rs > INT_MAX) {
+      std::fprintf(stderr, "ParaformerHip::Forward: unsupported sample rate %d\n", sample_rate);
+      return results;
+    }
+    max_len = (int)n_rs;
+  }
   const int max_tokens = max_len / 960 + 2;       // at most T+1 CIF fires, T = ceil(frames/6)
   const int V = pfhip_vocab_size(handle_);
   std::vector<int32_t> ids((size_t)batch_in * max_tokens), tn(batch_in), nf(batch_in), usl(batch_in), fr(batch_in);
@@ -279,11 +323,15 @@ std::vector<std::string> ParaformerHip::Forward(float** din, int* len, bool inpu
     }
   }
   // SetNbest: the same forward plus the k best columns of every token row (this caller's one hotword set as set 0)
-  const int nk = nbest_k_;
+  const int nk = s16 ? 0 : nbest_k_;              // (ForwardPcm16 converts and comes here as floats when candidates are on)
   std::vector<int32_t> nb_ids((size_t)(nk ? batch_in : 0) * max_tokens * nk);
   std::vector<float> nb_logp(nb_ids.size());
   pfhip_status st;
-  if (nk) {
+  if (s16 && sample_rate) {
+    st = pfhip_offline_forward_rate_s16(handle_, din16, len, batch_in, sample_rate, n_hw ? hw.data() : nullptr, n_hw, &out);
+  } else if (s16) {
+    st = pfhip_offline_forward_s16(handle_, din16, len, batch_in, n_hw ? hw.data() : nullptr, n_hw, &out);
+  } else if (nk) {
     const pfhip_nbest nb{nk, nb_ids.data(), nb_logp.data()};
     const float* sets[1] = {hw.data()};
     const int set_rows[1] = {n_hw};
@@ -427,14 +475,25 @@ void ParaformerOnlineHip::Reset() {
 std::string ParaformerOnlineHip::Forward(float* din, int len, bool input_finished, const std::vector<std::vector<float>>& hw_emb,
                                          void* wfst_decoder) {
   (void)hw_emb; (void)wfst_decoder;                              // unused by ParaformerOnline::Forward too
+  return ForwardAny(din, nullptr, len, input_finished);
+}
+std::string ParaformerOnlineHip::ForwardPcm16(const int16_t* din, int len, bool input_finished) {
+  return ForwardAny(nullptr, din, len, input_finished);
+}
+
+std::string ParaformerOnlineHip::ForwardAny(const float* din, const int16_t* din16, int len, bool input_finished) {
   last_ids_.clear();
-  if (!stream_ || len < 0 || (len > 0 && !din)) return "";       // (an empty final frame flushes the look-back cache, :532-540)
+  if (!stream_ || len < 0 || (len > 0 && !din && !din16)) return "";       // (an empty final frame flushes the look-back cache, :532-540)
   std::vector<int32_t> ids(256);
   int n_ids = 0;
-  pfhip_status st = pfhip_stream_forward(stream_, din, len, input_finished ? 1 : 0, ids.data(), (int)ids.size(), &n_ids);
+  auto call = [&]() {
+    return din16 ? pfhip_stream_forward_s16(stream_, din16, len, input_finished ? 1 : 0, ids.data(), (int)ids.size(), &n_ids)
+                 : pfhip_stream_forward(stream_, din, len, input_finished ? 1 : 0, ids.data(), (int)ids.size(), &n_ids);
+  };
+  pfhip_status st = call();
   if (st == PFHIP_ERR_CAPACITY) {                                // *n_tokens = what it needed; the chunk was not consumed
     ids.resize((size_t)n_ids + 16);
-    st = pfhip_stream_forward(stream_, din, len, input_finished ? 1 : 0, ids.data(), (int)ids.size(), &n_ids);
+    st = call();
   }
   if (st != PFHIP_OK) {
     std::fprintf(stderr, "ParaformerOnlineHip::Forward: %s\n", pfhip_last_error());

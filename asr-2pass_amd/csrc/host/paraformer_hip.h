@@ -129,6 +129,16 @@ class ParaformerHip : public ParaformerHipBase
   std::vector<std::string> Forward(float** din, int* len, bool input_finished,
                                    const std::vector<std::vector<float>>& hw_emb = {{0.0}}, void* wfst_decoder = nullptr,
                                    int batch_in = 1) override;
+  // The same Forward on 16-bit PCM as the server receives it (the samples Audio::LoadPcmwav, audio.cpp:787-819, divides by 32768
+  // on the host): the caller's buffers go to the device as they are (pfhip_offline_forward_s16 — half the bytes, no float copy) and
+  // every result is bit for bit that of Forward on din[i][j] / 32768.f.  sample_rate != 0 and != GetAsrSampleRate(): the audio is
+  // at that rate and is resampled on the device first (pfhip_offline_forward_rate_s16, Audio::WavResample).  With SetNbest the
+  // candidates call has no s16 form: the samples are converted here and take the float path; SetNbest together with another
+  // sample rate is refused ("" per item and a message, like a failed Forward: resample first with pfhip_resample).  Not a virtual: the
+  // funasr::Model::Forward(float**) seam and its table are untouched.
+  std::vector<std::string> ForwardPcm16(const int16_t* const* din, const int* len, bool input_finished,
+                                        const std::vector<std::vector<float>>& hw_emb = {{0.0}}, void* wfst_decoder = nullptr,
+                                        int batch_in = 1, int sample_rate = 0);
   // offline-stream.cpp:60-72 / paraformer.cpp:243-261: called before InitAsr with <MODEL_DIR>/model_eb.onnx (or
   // model_eb.torchscript); marks the model contextual (use_hotword) and remembers the file, whose tensors (bias_embed,
   // bias_encoder) are read together with the acoustic model's.  InitSegDict reads the "word<TAB>pieces" file Latin hotwords are
@@ -196,6 +206,9 @@ class ParaformerHip : public ParaformerHipBase
   std::string language = "zh-cn";          // paraformer.h:97
 
  private:
+  // Forward / ForwardPcm16: din[i] points at len[i] floats, or (s16) 16-bit samples at sample_rate (0 = the model's)
+  std::vector<std::string> ForwardAny(const void* const* din, bool s16, const int* len, bool input_finished,
+                                      const std::vector<std::vector<float>>& hw_emb, void* wfst_decoder, int batch_in, int sample_rate);
   std::string IdsToString(const std::vector<int>& ids);
   void LoadOffline(const std::string& am_model, const std::string& am_cmvn, const std::string& am_config, const std::string& token_file);
   void LoadOnline(const std::string& en_model, const std::string& de_model, const std::string& am_cmvn, const std::string& am_config,
@@ -230,6 +243,8 @@ class ParaformerOnlineHip : public ParaformerHipBase {
 #ifdef PFHIP_WITH_FUNASR
   using Model::Forward;
 #endif
+  // the same on 16-bit PCM as Audio::LoadPcmwavOnline reads it (audio.cpp:821-857): pfhip_stream_forward_s16
+  std::string ForwardPcm16(const int16_t* din, int len, bool input_finished);
   void StartUtterance() override {}
   void EndUtterance() override {}
   void Reset() override;                                   // Reset + ResetCache (:386-395)
@@ -242,6 +257,7 @@ class ParaformerOnlineHip : public ParaformerHipBase {
   int chunk_len = 9600;
 
  private:
+  std::string ForwardAny(const float* f32, const int16_t* s16, int len, bool input_finished);
   ParaformerHip* offline_handle_ = nullptr;
   pfhip_stream* stream_ = nullptr;
   std::vector<int> last_ids_;

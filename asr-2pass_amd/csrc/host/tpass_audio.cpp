@@ -9,15 +9,20 @@ namespace { constexpr int kSegSample = 16; }      // samples per ms at 16 kHz
 void TpassAudio::ResetIndex() {
   speech_start_ = -1; speech_end_ = 0; speech_offline_start_ = -1; offset_ = 0;
   all_samples_.clear();
+  all_pcm16_.clear();
+  pcm16_ok_ = true;
 }
 
 bool TpassAudio::LoadPcmwavOnline(const char* buf, int n_buf_len) {
   const int n = n_buf_len / 2;
   speech_data_.resize((size_t)n);
   const uint8_t* b = reinterpret_cast<const uint8_t*>(buf);
+  const size_t at16 = all_pcm16_.size();
+  if (pcm16_ok_) all_pcm16_.resize(at16 + (size_t)n);
   for (int i = 0; i < n; ++i) {
     const int16_t val = (int16_t)((b[2 * i + 1] << 8) | b[2 * i]);
-    speech_data_[i] = (float)val / 32768.0f;
+    speech_data_[i] = (float)val / 32768.0f;      // the end-point detector's decibel track and the 2-s cache read floats
+    if (pcm16_ok_) all_pcm16_[at16 + (size_t)i] = val;
   }
   all_samples_.insert(all_samples_.end(), speech_data_.begin(), speech_data_.end());
   frame_queue_.push_back(n);
@@ -26,6 +31,8 @@ bool TpassAudio::LoadPcmwavOnline(const char* buf, int n_buf_len) {
 
 void TpassAudio::LoadSamplesOnline(const float* x, int n) {
   speech_data_.assign(x, x + n);
+  pcm16_ok_ = false;                             // resampled floats have no 16-bit form
+  all_pcm16_.clear();
   all_samples_.insert(all_samples_.end(), speech_data_.begin(), speech_data_.end());
   frame_queue_.push_back(n);
 }
@@ -34,8 +41,13 @@ TpassFrame TpassAudio::MakeFrame(int start, int n, bool is_final, int gs, int ge
   TpassFrame f;
   f.is_final = is_final; f.global_start = gs; f.global_end = ge;
   const long a = (long)start - offset_;
-  if (n > 0 && a >= 0 && a + n <= (long)all_samples_.size()) f.data.assign(all_samples_.begin() + a, all_samples_.begin() + a + n);
-  else if (n > 0) f.data.assign((size_t)n, 0.f);      // outside the 2-s cache (the reference would read out of bounds)
+  if (n > 0 && a >= 0 && a + n <= (long)all_samples_.size()) {
+    f.data.assign(all_samples_.begin() + a, all_samples_.begin() + a + n);
+    if (pcm16_ok_) f.pcm16.assign(all_pcm16_.begin() + a, all_pcm16_.begin() + a + n);
+  } else if (n > 0) {
+    f.data.assign((size_t)n, 0.f);      // outside the 2-s cache (the reference would read out of bounds)
+    if (pcm16_ok_) f.pcm16.assign((size_t)n, 0);
+  }
   return f;
 }
 
@@ -96,6 +108,7 @@ void TpassAudio::Split(const VadInfer& vad, int chunk_len, bool input_finished, 
     if ((int)all_samples_.size() > vector_cache) {
       const int erase = (int)all_samples_.size() - vector_cache;
       all_samples_.erase(all_samples_.begin(), all_samples_.begin() + erase);
+      if (pcm16_ok_) all_pcm16_.erase(all_pcm16_.begin(), all_pcm16_.begin() + erase);
       offset_ += erase;
     }
   } else {
@@ -103,6 +116,7 @@ void TpassAudio::Split(const VadInfer& vad, int chunk_len, bool input_finished, 
     if (offline_start - offset_ > vector_cache) {
       const int erase = offline_start - offset_ - vector_cache;
       all_samples_.erase(all_samples_.begin(), all_samples_.begin() + erase);
+      if (pcm16_ok_) all_pcm16_.erase(all_pcm16_.begin(), all_pcm16_.begin() + erase);
       offset_ += erase;
     }
   }

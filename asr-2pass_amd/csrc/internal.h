@@ -30,6 +30,30 @@ inline pfhip_status fail(pfhip_status st, const std::string& msg) {
   return st;
 }
 
+// The sample formats audio arrives in.  f32: samples in [-1, 1) as Model::Forward gets them.  s16: 16-bit PCM as the server receives
+// it; the sample s stands for the float s / 32768.f (audio.cpp:787-857 divide exactly so), which is exact, and so is the x 32768 the
+// front end applies again (paraformer.cpp:312-314) — the s16 kernels therefore give bit for bit what the f32 kernels give.
+// PcmView: one buffer (host or device); HostPcm: a call's array of per-utterance host buffers, all of one format.
+struct PcmView {
+  const void* p; bool s16;
+  const float* f32() const { return static_cast<const float*>(p); }
+  const int16_t* i16() const { return static_cast<const int16_t*>(p); }
+  size_t sample_bytes() const { return s16 ? 2 : 4; }
+};
+struct HostPcm {
+  const void* const* p; bool s16;
+  HostPcm(const float* const* f) : p(reinterpret_cast<const void* const*>(f)), s16(false) {}
+  HostPcm(const int16_t* const* i) : p(reinterpret_cast<const void* const*>(i)), s16(true) {}
+  HostPcm(const void* const* v, bool is_s16) : p(v), s16(is_s16) {}
+  size_t sample_bytes() const { return s16 ? 2 : 4; }
+};
+// n samples of `src` as floats: a copy, or s / 32768.f (the streaming families convert during the one copy they make anyway)
+inline void pcm_to_f32(float* dst, PcmView src, size_t n) {
+  if (!src.s16) { if (n) std::memcpy(dst, src.p, n * 4); return; }
+  const int16_t* s = src.i16();
+  for (size_t i = 0; i < n; ++i) dst[i] = (float)s[i] / 32768.f;
+}
+
 #define HIP_TRY(expr)                                                                        \
   do {                                                                                       \
     hipError_t e__ = (expr);                                                                 \
@@ -189,7 +213,7 @@ struct pfhip_model {
   int range_hit = 0, debug_range_flag = 0;
   bool exact_rerun = false, last_feats_only = false;
   long long range_fallbacks = 0;
-  const float* last_pcm = nullptr;
+  pfhip_detail::PcmView last_pcm{nullptr, false};               // the device buffer AND its sample format
   std::vector<int64_t> last_off;
   std::vector<int> last_n;
   int plane_forwards = 0;                                       // forwards of this context that took the plane path (debug read-out)
@@ -262,6 +286,7 @@ struct pfhip_model {
   // slot while the next one already gathers the next batch (merge_queue.h PoolQueue)
   pfhip_detail::PoolQueue<BatchReq, pfhip_model> bq;
   int batch_wait_us = 0, batch_max_utts = 32;
+  long long format_splits = 0;              // on the head, under bq.mu: picks that left callers of the other sample format queued
   // the same for streaming calls: concurrent pfhip_stream_forward callers (one thread per connection) are merged
   pfhip_detail::MergeQueue<StreamReq> sq;
   int stream_wait_us = 0, stream_max = 128;

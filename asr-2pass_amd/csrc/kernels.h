@@ -29,13 +29,26 @@ struct FbankTables {
 void launch_fbank_lfr_cmvn(const float* pcm, const int64_t* sample_off, const int* frame_off,
                            const int* nframes, const int* row_off, int B, int total_frames,
                            FbankTables tb, float* feats, hipStream_t s);
+// The same three launchers (this one and the two below) from 16-bit PCM: the sample s stands for s / 32768.f, which the float form
+// multiplies by 32768 again (paraformer.cpp:312-314), so the kernel loads (float)s and every result is bit for bit that of the float
+// form fed s / 32768.f.  sample_off counts samples: an utterance may start at an odd one (2-byte alignment is all that is assumed;
+// the compiled kernel may fetch two neighbouring samples with one unaligned 4-byte load, which gfx950 global loads allow).
+void launch_fbank_lfr_cmvn(const int16_t* pcm, const int64_t* sample_off, const int* frame_off,
+                           const int* nframes, const int* row_off, int B, int total_frames,
+                           FbankTables tb, float* feats, hipStream_t s);
 
 // Streaming form (ParaformerOnline::FbankKaldi, paraformer-online.cpp:119-145): one utterance, raw
 // log-mel frames [total_frames, 80] out, no LFR/CMVN.  sample_off/frame_off/nframes: 1/2/1 entries.
 void launch_fbank_frames(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes,
                          int total_frames, FbankTables tb, float* fb_out, hipStream_t s);
+void launch_fbank_frames(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes,
+                         int total_frames, FbankTables tb, float* fb_out, hipStream_t s);
 // the same for B utterances back to back in `pcm` (frame_off has B + 1 entries); frames land back to back in fb_out
 void launch_fbank_frames_batch(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                               int total_frames, FbankTables tb, float* fb_out, hipStream_t s);
+// (no caller today: both streaming families convert to f32 while the host copies the samples into its staging buffer, so no test
+// reaches this overload; it is the launcher a staging buffer of shorts would use)
+void launch_fbank_frames_batch(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
                                int total_frames, FbankTables tb, float* fb_out, hipStream_t s);
 
 // x0[row][0..D) = feats*scale + PE(row_pos[row]+1); columns D..ldx are zeroed.
@@ -341,6 +354,10 @@ struct ResampleTable { const int* first; const int* ntap; const float* w; int P,
 // Packed batch: utterance b reads n_in[b] samples at in + in_off[b] and writes n_out[b] samples at out + out_off[b]
 // (host arrays; n_out from the flush-mode count).  Bitwise the reference's serial fp32 dot product per output.
 void launch_resample(const float* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
+                     int B, const ResampleTable& t, hipStream_t s);
+// 16-bit PCM in (offsets in samples, 2-byte alignment assumed): every sample is converted (float)s * (1.f / 32768.f) on load, the tap
+// loop and its order are the same, the output stays f32 — bit for bit launch_resample of s / 32768.f.
+void launch_resample(const int16_t* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
                      int B, const ResampleTable& t, hipStream_t s);
 
 }  // namespace pfhip

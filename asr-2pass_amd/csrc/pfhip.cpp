@@ -583,9 +583,10 @@ struct ForwardCtx {
   ~ForwardCtx() { pfhip::launch_ctx() = saved; }
 };
 
-pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sample_off, const int* n_samples, int B, hipStream_t s,
+// d_pcm: the packed device buffer in either sample format (internal.h PcmView); sample_off counts samples of that format
+pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples, int B, hipStream_t s,
                           bool feats_only);
-pfhip_status enqueue_locked(pfhip_model* m, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
+pfhip_status enqueue_locked(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                             int B, hipStream_t s, bool feats_only) {
   m->d_range_flag = nullptr;                          // until the metadata upload places it
   const pfhip::LaunchCtx saved = pfhip::launch_ctx();
@@ -595,7 +596,7 @@ pfhip_status enqueue_locked(pfhip_model* m, const float* d_pcm, const int64_t* s
   return st;
 }
 
-pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
+pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                           int B, hipStream_t s, bool feats_only) {
   const Config& c = m->cfg;
   const int d = c.d_model, FD = m->feat_dim, FP = m->feat_pad;
@@ -680,12 +681,16 @@ pfhip_status enqueue_body(pfhip_model* m, const float* d_pcm, const int64_t* sam
   // ---- a2+a3: fbank -> LFR -> CMVN -----------------------------------------------------------------------
   {
     double in_bytes = 0;
-    for (int b = 0; b < B; ++b) in_bytes += 4.0 * n_samples[b];
+    for (int b = 0; b < B; ++b) in_bytes += (double)d_pcm.sample_bytes() * n_samples[b];
     Scope sc(m, s, K_FBANK, 0, in_bytes + 4.0 * FD * M);
     pfhip::FbankTables tb{m->d_window, m->d_tw, m->d_mel_off, m->d_mel_size, m->d_mel_w,
                           m->W("cmvn.mean").d, m->W("cmvn.istd").d};
-    pfhip::launch_fbank_lfr_cmvn(d_pcm, m->m_sample_off, m->m_frame_off, m->m_nframes, m->m_row_off, B,
-                                 total_frames, tb, m->feats.f(), s);
+    if (d_pcm.s16)
+      pfhip::launch_fbank_lfr_cmvn(d_pcm.i16(), m->m_sample_off, m->m_frame_off, m->m_nframes, m->m_row_off, B,
+                                   total_frames, tb, m->feats.f(), s);
+    else
+      pfhip::launch_fbank_lfr_cmvn(d_pcm.f32(), m->m_sample_off, m->m_frame_off, m->m_nframes, m->m_row_off, B,
+                                   total_frames, tb, m->feats.f(), s);
   }
   if (feats_only) { HIP_TRY(hipGetLastError()); return PFHIP_OK; }
 
@@ -1252,12 +1257,12 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
 // (head_locked reads m->nbest_k), so what comes back belongs to the forward whose token_ids come back
 pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb = nullptr) {
   pfhip_status st = fetch_once(m, out, s, nb);
-  if (st || !m->range_hit || m->exact_rerun || m->always_exact || !m->last_pcm || m->last_feats_only) return st;
+  if (st || !m->range_hit || m->exact_rerun || m->always_exact || !m->last_pcm.p || m->last_feats_only) return st;
   ++m->range_fallbacks;
   m->exact_rerun = true;
   const std::vector<int64_t> off = m->last_off;
   const std::vector<int> ns = m->last_n;
-  st = enqueue_locked(m, m->last_pcm, off.data(), ns.data(), (int)ns.size(), s, false);
+  st = enqueue_locked(m, m->last_pcm, off.data(), ns.data(), (int)ns.size(), s, false);      // the saved view: pointer and format
   if (!st) st = head_locked(m, s, out->logp != nullptr);
   if (!st) st = fetch_once(m, out, s, nb);
   m->exact_rerun = false;
@@ -1546,25 +1551,29 @@ pfhip_status resolve_default_hotwords_locked(pfhip_model* m, int B, hipStream_t 
   return resolve_hotwords_locked(m, &e, &H, 1, nullptr, B, s);
 }
 
-pfhip_status stage_pcm(pfhip_model* m, const float* const* pcm, const int* n_samples, int B, hipStream_t s,
+// The batch packed into the slot's PCM workspace in the caller's own format: `off` counts samples, the workspace is indexed in floats
+// or in shorts accordingly (one buffer; 16-bit PCM takes half of what the same batch takes as floats).
+pfhip_status stage_pcm(pfhip_model* m, HostPcm pcm, const int* n_samples, int B, hipStream_t s,
                        std::vector<int64_t>& off) {
   off.assign(B, 0);
   int64_t tot = 0;
   for (int b = 0; b < B; ++b) {
-    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
     off[b] = tot;
     tot += (n_samples[b] + 3) & ~3;
   }
-  HIP_TRY(m->pcm.ensure((size_t)std::max<int64_t>(tot, 4) * 4));
+  const size_t es = pcm.sample_bytes();
+  HIP_TRY(m->pcm.ensure((size_t)std::max<int64_t>(tot, 4) * es));
   for (int b = 0; b < B; ++b)
     if (n_samples[b])
-      HIP_TRY(hipMemcpyAsync(m->pcm.f() + off[b], pcm[b], (size_t)n_samples[b] * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(static_cast<char*>(m->pcm.p) + (size_t)off[b] * es, pcm.p[b], (size_t)n_samples[b] * es, hipMemcpyHostToDevice, s));
   return PFHIP_OK;
 }
 
 // The batch at the caller's rate fs_in: staged into rs_in, resampled on `s` into `pcm` at the model's rate, packed as stage_pcm
-// packs it.  off / n_out receive the model-rate layout.
-pfhip_status stage_resampled(pfhip_model* m, const float* const* pcm, const int* n_samples, int B, int fs_in, hipStream_t s,
+// packs it.  off / n_out receive the model-rate layout.  16-bit PCM is staged as it is and converted by the kernel's loads; what
+// lands in `pcm` is f32 either way.
+pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, int B, int fs_in, hipStream_t s,
                              std::vector<int64_t>& off, std::vector<int>& n_out) {
   pfhip::ResampleTable t;
   pfhip_status st = (m->weights_of ? m->weights_of : m)->rs_cache->get(m->device, fs_in, m->cfg.sample_rate, &t);
@@ -1574,7 +1583,7 @@ pfhip_status stage_resampled(pfhip_model* m, const float* const* pcm, const int*
   n_out.assign(B, 0);
   int64_t tin = 0, tout = 0;
   for (int b = 0; b < B; ++b) {
-    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
     const int64_t no = pfhip_detail::resample_out_len(fs_in, m->cfg.sample_rate, n_samples[b]);
     if (no < 0 || no > INT32_MAX) return fail(PFHIP_ERR_ARG, "resampled utterance too long");
     in_off[b] = tin;
@@ -1583,14 +1592,18 @@ pfhip_status stage_resampled(pfhip_model* m, const float* const* pcm, const int*
     off[b] = tout;
     tout += (no + 3) & ~3;
   }
-  HIP_TRY(m->rs_in.ensure((size_t)std::max<int64_t>(tin, 4) * 4));
+  const size_t es = pcm.sample_bytes();
+  HIP_TRY(m->rs_in.ensure((size_t)std::max<int64_t>(tin, 4) * es));
   HIP_TRY(m->pcm.ensure((size_t)std::max<int64_t>(tout, 4) * 4));
   for (int b = 0; b < B; ++b)
     if (n_samples[b])
-      HIP_TRY(hipMemcpyAsync(m->rs_in.f() + in_off[b], pcm[b], (size_t)n_samples[b] * 4, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(static_cast<char*>(m->rs_in.p) + (size_t)in_off[b] * es, pcm.p[b], (size_t)n_samples[b] * es, hipMemcpyHostToDevice, s));
   {
-    Scope sc(m, s, K_FBANK, 0.0, 4.0 * (double)(tin + tout));
-    pfhip::launch_resample(m->rs_in.f(), in_off.data(), n_samples, m->pcm.f(), off.data(), n_out.data(), B, t, s);
+    Scope sc(m, s, K_FBANK, 0.0, (double)es * (double)tin + 4.0 * (double)tout);
+    if (pcm.s16)
+      pfhip::launch_resample(static_cast<const int16_t*>(m->rs_in.p), in_off.data(), n_samples, m->pcm.f(), off.data(), n_out.data(), B, t, s);
+    else
+      pfhip::launch_resample(m->rs_in.f(), in_off.data(), n_samples, m->pcm.f(), off.data(), n_out.data(), B, t, s);
   }
   HIP_TRY(hipGetLastError());
   return PFHIP_OK;
@@ -1744,11 +1757,11 @@ int pfhip_feat_dim(const pfhip_model* m) { return m ? m->feat_dim : 0; }
 int pfhip_d_model(const pfhip_model* m) { return m ? m->cfg.d_model : 0; }
 int pfhip_head_dim(const pfhip_model* m) { return m && m->cfg.n_head > 0 ? m->cfg.d_model / m->cfg.n_head : 0; }
 
-pfhip_status pfhip_offline_enqueue(pfhip_model* m, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
-                                   int batch, void* stream) {
+static pfhip_status offline_enqueue(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
+                                    int batch, void* stream) {
   g_err.clear();
   if (!m || !sample_off || !n_samples || batch <= 0) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (!d_pcm) return fail(PFHIP_ERR_ARG, "null device pcm");
+  if (!d_pcm.p) return fail(PFHIP_ERR_ARG, "null device pcm");
   std::lock_guard<std::mutex> lk(m->mu);
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : m->own_stream;
   m->prof_stream = s;
@@ -1761,6 +1774,15 @@ pfhip_status pfhip_offline_enqueue(pfhip_model* m, const float* d_pcm, const int
   st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
   if (st) return st;
   return head_locked(m, s, false);
+}
+pfhip_status pfhip_offline_enqueue(pfhip_model* m, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
+                                   int batch, void* stream) {
+  return offline_enqueue(m, PcmView{d_pcm, false}, sample_off, n_samples, batch, stream);
+}
+// the same from a device buffer of 16-bit PCM (what Audio::LoadPcmwav, audio.cpp:787-819, would have divided by 32768 on the host)
+pfhip_status pfhip_offline_enqueue_s16(pfhip_model* m, const int16_t* d_pcm, const int64_t* sample_off, const int* n_samples,
+                                       int batch, void* stream) {
+  return offline_enqueue(m, PcmView{d_pcm, true}, sample_off, n_samples, batch, stream);
 }
 
 pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out) {
@@ -1775,7 +1797,7 @@ pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out) {
 // hotword sets of a call: n_sets sets (emb[k]: [n[k], d]) and, per utterance, which one it attends to (of_utt == nullptr: all set 0)
 struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
 
-static pfhip_status forward_direct(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch,
+static pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch,
                                    const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_nbest* nb = nullptr) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
@@ -1792,7 +1814,8 @@ static pfhip_status forward_direct(pfhip_model* m, const float* const* pcm, cons
   std::vector<int> n_rs;
   pfhip_status st = fs_in ? stage_resampled(m, pcm, n_samples, batch, fs_in, s, off, n_rs) : stage_pcm(m, pcm, n_samples, batch, s, off);
   if (st) return st;
-  st = enqueue_locked(m, m->pcm.f(), off.data(), fs_in ? n_rs.data() : n_samples, batch, s, false);
+  // the workspace holds the caller's format, except after resampling (always f32 out)
+  st = enqueue_locked(m, PcmView{m->pcm.p, pcm.s16 && !fs_in}, off.data(), fs_in ? n_rs.data() : n_samples, batch, s, false);
   if (st) return st;
   st = head_locked(m, s, out->logp != nullptr);
   if (st) return st;
@@ -1849,15 +1872,15 @@ static void release_slot(pfhip_model* head, pfhip_model* slot) {
 // tests/test_gpu_forward.py::test_batch_composition_invariance — a merged forward may run another kernel family than a lone one,
 // the same sums in another order, 1e-6 apart in the log-probabilities).
 struct BatchReq : pfhip_detail::MergeReqBase {
-  const float* const* pcm; const int* n; int batch; pfhip_out* out;
+  HostPcm pcm{static_cast<const float* const*>(nullptr)}; const int* n; int batch; pfhip_out* out;
   HwSets hw{nullptr, nullptr, 0, nullptr};          // the caller's hotword sets (contextual models)
   const pfhip_nbest* nb = nullptr;                  // the caller's candidate buffers (pfhip_offline_forward_nbest), or none
   pfhip_status st = PFHIP_OK; std::string err;
 };
 
-// one packed forward on `m` for everybody in `take`
+// one packed forward on `m` for everybody in `take` (all of one sample format: forward_batched's pick splits the queue by format)
 static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
-  std::vector<const float*> ptrs; std::vector<int> lens;
+  std::vector<const void*> ptrs; std::vector<int> lens;
   bool want_logp = false, want_us = false; int max_tok = 1, utts = 0;
   int kmax = 0;      // the packed forward computes the largest k among its callers; the order makes every prefix a caller's own answer
   // Contextual model: the callers' hotword sets, deduplicated (one connection sends the same list with each of its segments; the
@@ -1885,7 +1908,7 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
   }
   if (take.empty()) return;
   for (BatchReq* r : take) {
-    for (int i = 0; i < r->batch; ++i) { ptrs.push_back(r->pcm[i]); lens.push_back(r->n[i]); max_tok = std::max(max_tok, r->n[i] / 960 + 2); }
+    for (int i = 0; i < r->batch; ++i) { ptrs.push_back(r->pcm.p[i]); lens.push_back(r->n[i]); max_tok = std::max(max_tok, r->n[i] / 960 + 2); }
     want_logp = want_logp || r->out->logp != nullptr;
     if (r->nb) kmax = std::max(kmax, (int)r->nb->k);
     want_us = want_us || r->out->us_alphas || r->out->us_peaks || r->out->us_len;
@@ -1906,7 +1929,7 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
   if (kmax) { nbi.resize((size_t)utts * max_tok * kmax); nbl.resize(nbi.size()); }
   const pfhip_nbest nb_all{kmax, nbi.data(), nbl.data()};
   const HwSets sets{set_emb.data(), set_n.data(), (int)set_emb.size(), set_of.data()};
-  pfhip_status st = forward_direct(m, ptrs.data(), lens.data(), utts, sets, &all, 0, kmax ? &nb_all : nullptr);
+  pfhip_status st = forward_direct(m, HostPcm(ptrs.data(), take.front()->pcm.s16), lens.data(), utts, sets, &all, 0, kmax ? &nb_all : nullptr);
   const std::string err = g_err;
   int u0 = 0;
   for (BatchReq* r : take) {
@@ -1941,7 +1964,10 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
 
 namespace { thread_local pfhip_model* tl_last_replica = nullptr; }      // where this thread's last offline forward ran (debug getters)
 
-static pfhip_status forward_batched(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
+// Callers of both sample formats share the queue; a packed forward holds ONE format, the leader's: pick takes the queued callers of
+// that format (in order) and leaves the others, in order, for the next leader.  Nothing is converted on the host, every caller gets
+// the results of a forward in its own format, which are those of the other format bit for bit.
+static pfhip_status forward_batched(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch,
                                     const HwSets& hw, pfhip_out* out, const pfhip_nbest* nb) {
   BatchReq me;
   me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out; me.hw = hw; me.nb = nb;
@@ -1962,11 +1988,19 @@ static pfhip_status forward_batched(pfhip_model* head, const float* const* pcm, 
       [&](const std::deque<BatchReq*>& q) { int u = 0; for (BatchReq* r : q) u += r->batch; return u >= max_utts; },
       [&](std::deque<BatchReq*>& q, std::vector<BatchReq*>& take) {
         int utts = 0;
+        const bool s16 = q.front()->pcm.s16;
+        std::deque<BatchReq*> other;                      // callers of the other sample format: they stay queued, in order
         while (!q.empty() && (take.empty() || utts + q.front()->batch <= max_utts)) {
-          utts += q.front()->batch;
-          take.push_back(q.front());
+          if (q.front()->pcm.s16 == s16) {
+            utts += q.front()->batch;
+            take.push_back(q.front());
+          } else {
+            other.push_back(q.front());
+          }
           q.pop_front();
         }
+        for (auto it = other.rbegin(); it != other.rend(); ++it) q.push_front(*it);
+        if (!other.empty()) ++head->format_splits;        // (pfhip_debug_poke "format_splits")
       },
       [&](pfhip_model* r, std::vector<BatchReq*>& take) {
         ran_on = r;
@@ -1980,14 +2014,14 @@ static pfhip_status forward_batched(pfhip_model* head, const float* const* pcm, 
   return me.st;
 }
 
-static pfhip_status offline_forward_sets(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, const HwSets& hw,
+static pfhip_status offline_forward_sets(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const HwSets& hw,
                                          pfhip_out* out, const pfhip_nbest* nb = nullptr) {
   g_err.clear();
-  if (!head || !pcm || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!head || !pcm.p || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
   if (nb && (nb->k < 1 || nb->k > pfhip::kTopkMax || nb->k > head->cfg.vocab || !nb->ids || !nb->logp))
     return fail(PFHIP_ERR_ARG, "nbest: k outside 1..8 (or above the vocabulary) or a null buffer");
   for (int i = 0; i < batch; ++i)
-    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm.p[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
   // merged with whoever else is calling: plain and timestamp models always; contextual models — every caller with its own hotword
   // sets, each utterance attending to its own set in the packed forward — where pfhip_set_hotword_merging is on
   bool merge;
@@ -2010,16 +2044,32 @@ pfhip_status pfhip_offline_forward(pfhip_model* head, const float* const* pcm, c
   const HwSets hw{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
   return offline_forward_sets(head, pcm, n_samples, batch, hw, out);
 }
+// pfhip_offline_forward from 16-bit PCM: the bytes Audio::LoadPcmwav (audio.cpp:787-819) reads, without its host-side / 32768
+pfhip_status pfhip_offline_forward_s16(pfhip_model* head, const int16_t* const* pcm, const int* n_samples, int batch,
+                                       const float* hw_emb, int n_hotwords, pfhip_out* out) {
+  const HwSets hw{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
+  return offline_forward_sets(head, pcm, n_samples, batch, hw, out);
+}
 
-pfhip_status pfhip_offline_forward_hwsets(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
-                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
-                                          pfhip_out* out) {
+static pfhip_status offline_forward_hwsets(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch,
+                                           const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                           pfhip_out* out) {
   if (head && head->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
     g_err.clear();
     return fail(PFHIP_ERR_ARG, "bad argument");
   }
   const HwSets hw{hw_emb, n_hotwords, n_sets < 0 ? 0 : n_sets, set_of_utt};
   return offline_forward_sets(head, pcm, n_samples, batch, hw, out);
+}
+pfhip_status pfhip_offline_forward_hwsets(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
+                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                          pfhip_out* out) {
+  return offline_forward_hwsets(head, pcm, n_samples, batch, hw_emb, n_hotwords, n_sets, set_of_utt, out);
+}
+pfhip_status pfhip_offline_forward_hwsets_s16(pfhip_model* head, const int16_t* const* pcm, const int* n_samples, int batch,
+                                              const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                              pfhip_out* out) {
+  return offline_forward_hwsets(head, pcm, n_samples, batch, hw_emb, n_hotwords, n_sets, set_of_utt, out);
 }
 
 // pfhip_offline_forward_hwsets plus the k best candidates of every token row (an extension: GreedySearch, paraformer.cpp:386-395,
@@ -2064,10 +2114,10 @@ pfhip_status pfhip_offline_fetch_nbest(pfhip_model* m, const pfhip_nbest* nb) {
 }
 
 // pfhip_offline_forward with the PCM already in HBM: same routing over the execution slots, no H2D of the audio
-pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
-                                            int batch, pfhip_out* out) {
+static pfhip_status offline_forward_resident(pfhip_model* head, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
+                                             int batch, pfhip_out* out) {
   g_err.clear();
-  if (!head || !d_pcm || !sample_off || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!head || !d_pcm.p || !sample_off || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
   if (head->cfg.contextual && !default_hotwords(head)) return fail(PFHIP_ERR_ARG, "hw_emb is null");
   pfhip_model* m = acquire_slot(head);
   tl_last_replica = m;
@@ -2088,15 +2138,26 @@ pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pc
   release_slot(head, m);
   return st;
 }
+pfhip_status pfhip_offline_forward_resident(pfhip_model* head, const float* d_pcm, const int64_t* sample_off, const int* n_samples,
+                                            int batch, pfhip_out* out) {
+  return offline_forward_resident(head, PcmView{d_pcm, false}, sample_off, n_samples, batch, out);
+}
+pfhip_status pfhip_offline_forward_resident_s16(pfhip_model* head, const int16_t* d_pcm, const int64_t* sample_off,
+                                                const int* n_samples, int batch, pfhip_out* out) {
+  return offline_forward_resident(head, PcmView{d_pcm, true}, sample_off, n_samples, batch, out);
+}
 
 // pfhip_offline_forward at the caller's rate: resampled on the device into the slot's PCM workspace, then the same forward
-pfhip_status pfhip_offline_forward_rate(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
-                                        const float* hw_emb, int n_hotwords, pfhip_out* out) {
-  if (head && sample_rate == head->cfg.sample_rate) return pfhip_offline_forward(head, pcm, n_samples, batch, hw_emb, n_hotwords, out);
+static pfhip_status offline_forward_rate(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, int sample_rate,
+                                         const float* hw_emb, int n_hotwords, pfhip_out* out) {
+  if (head && sample_rate == head->cfg.sample_rate) {
+    const HwSets same{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
+    return offline_forward_sets(head, pcm, n_samples, batch, same, out);
+  }
   g_err.clear();
-  if (!head || !pcm || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!head || !pcm.p || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
   for (int i = 0; i < batch; ++i)
-    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm.p[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
   std::string why;
   if (!pfhip_detail::resample_supported(sample_rate, head->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
   pfhip_model* m = acquire_slot(head);                  // not merged with other callers: one rate pair per packed batch
@@ -2106,6 +2167,15 @@ pfhip_status pfhip_offline_forward_rate(pfhip_model* head, const float* const* p
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
   return st;
+}
+pfhip_status pfhip_offline_forward_rate(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                        const float* hw_emb, int n_hotwords, pfhip_out* out) {
+  return offline_forward_rate(head, pcm, n_samples, batch, sample_rate, hw_emb, n_hotwords, out);
+}
+// 16-bit PCM at the caller's rate (Audio::LoadPcmwav + WavResample, audio.cpp:787-819, 259-284): converted by the resampler's loads
+pfhip_status pfhip_offline_forward_rate_s16(pfhip_model* head, const int16_t* const* pcm, const int* n_samples, int batch,
+                                            int sample_rate, const float* hw_emb, int n_hotwords, pfhip_out* out) {
+  return offline_forward_rate(head, pcm, n_samples, batch, sample_rate, hw_emb, n_hotwords, out);
 }
 
 pfhip_status pfhip_resample(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int fs_in, float* const* out,
@@ -2406,7 +2476,7 @@ pfhip_status pfhip_extract_feats(pfhip_model* m, const float* const* pcm, const 
   std::vector<int64_t> off;
   pfhip_status st = stage_pcm(m, pcm, n_samples, batch, s, off);
   if (st) return st;
-  st = enqueue_locked(m, m->pcm.f(), off.data(), n_samples, batch, s, true);
+  st = enqueue_locked(m, PcmView{m->pcm.p, false}, off.data(), n_samples, batch, s, true);
   if (st) return st;
   if (n_frames_out) for (int b = 0; b < batch; ++b) n_frames_out[b] = m->T[b];
   const size_t n = (size_t)m->M * m->feat_dim;
@@ -2470,6 +2540,10 @@ pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value) {
   if (std::string(what) == "dec_plane_forwards") return (pfhip_status)m->dec_plane_forwards; // ... whose decoder took the plane path too
   if (std::string(what) == "static_bound") return (pfhip_status)std::min(m->static_bound, 2.0e9);      // read-out: the load-time activation bound
   if (std::string(what) == "always_exact") return (pfhip_status)(m->always_exact ? 1 : 0);
+  if (std::string(what) == "format_splits") {         // read-out: merged batches cut short because callers of both sample formats were queued
+    std::lock_guard<std::mutex> ql(m->bq.mu);
+    return (pfhip_status)m->format_splits;
+  }
   if (std::string(what) == "range_flag") { m->debug_range_flag = value; return PFHIP_OK; }    // the next forward starts with its range flag raised
   if (std::string(what) == "range_fallbacks") {       // read-out: forwards redone on the exact kernels, over every context of the handle
     long long n = m->range_fallbacks;

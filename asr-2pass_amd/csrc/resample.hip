@@ -11,7 +11,12 @@
 // window its span reads into LDS (16-byte loads where the window is 16-byte aligned in HBM), then each lane computes
 // outputs from LDS with its phase's weight row, read from the plan table (a few KB to 1.5 MB: L2-resident), and stores
 // them coalesced.  Outputs whose window is not wholly staged (utterance edges) read HBM directly.
+//
+// 16-bit PCM in: the same kernel with every load converted (float)s * (1.f / 32768.f) — exactly s / 32768.f — so the staged window
+// and the tap loop hold the floats the f32 form would have read.  s16 windows are staged sample by sample, never through a wider
+// cast (an utterance may start at an odd sample of a packed buffer: 2-byte alignment is all that is assumed).
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -31,8 +36,11 @@ struct ResampleBatch {
   int nb;
   int span;                                  // output samples per workgroup (multiple of kThreads)
   int lds;                                   // staged floats per workgroup (0: no staging, every read from HBM)
-  int vec;                                   // input base pointer is 16-byte aligned: stage with float4 loads
+  int vec;                                   // input base pointer is 16-byte aligned: stage with float4 loads (f32 input only)
 };
+
+__device__ __forceinline__ float load_sample(const float* in, int64_t e) { return in[e]; }
+__device__ __forceinline__ float load_sample(const int16_t* in, int64_t e) { return (float)in[e] * (1.f / 32768.f); }
 
 __device__ __forceinline__ int64_t first_in(const ResampleTable& t, int s, int* ph) {
   const int unit = s / t.Q;
@@ -40,7 +48,8 @@ __device__ __forceinline__ int64_t first_in(const ResampleTable& t, int s, int* 
   return (int64_t)t.first[*ph] + (int64_t)unit * t.P;
 }
 
-__global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restrict__ in, float* __restrict__ out,
+template <typename Sample>
+__global__ __launch_bounds__(kThreads) void resample_kernel(const Sample* __restrict__ in, float* __restrict__ out,
                                                             const ResampleBatch a, const ResampleTable t) {
   extern __shared__ float4 win_raw[];                // 16-byte aligned for the float4 staging stores
   float* win = reinterpret_cast<float*>(win_raw);
@@ -51,7 +60,7 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restr
   const int n = a.n_in[b];
   const int cnt = min(a.span, a.n_out[b] - s0);
   const int64_t base = a.in_off[b];
-  const float* x = in + base;
+  const Sample* x = in + base;
   float* y = out + a.out_off[b] + s0;
 
   // input window [lo, hi) of this span, clamped to the utterance; staged as LDS[e - g0] for global element e = base + idx
@@ -63,16 +72,20 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restr
   const bool staged = hi > lo && g1 - g0 <= a.lds;
   if (staged) {
     const int64_t e0 = base + lo, e1 = base + hi;    // elements that may be read (inside this utterance)
-    if (a.vec) {
-      // 16-byte groups wholly inside [e0, e1); the partial groups at both ends element by element
-      const int64_t v0 = (e0 + 3) & ~(int64_t)3, v1 = e1 & ~(int64_t)3;
-      for (int64_t e = v0 + 4 * (int64_t)threadIdx.x; e < v1; e += 4 * kThreads)
-        *reinterpret_cast<float4*>(win + (e - g0)) = *reinterpret_cast<const float4*>(in + e);
-      const int64_t h1 = min(v0, e1);
-      for (int64_t e = e0 + threadIdx.x; e < h1; e += kThreads) win[e - g0] = in[e];
-      for (int64_t e = max(v1, h1) + threadIdx.x; e < e1; e += kThreads) win[e - g0] = in[e];
+    if constexpr (std::is_same<Sample, float>::value) {
+      if (a.vec) {
+        // 16-byte groups wholly inside [e0, e1); the partial groups at both ends element by element
+        const int64_t v0 = (e0 + 3) & ~(int64_t)3, v1 = e1 & ~(int64_t)3;
+        for (int64_t e = v0 + 4 * (int64_t)threadIdx.x; e < v1; e += 4 * kThreads)
+          *reinterpret_cast<float4*>(win + (e - g0)) = *reinterpret_cast<const float4*>(in + e);
+        const int64_t h1 = min(v0, e1);
+        for (int64_t e = e0 + threadIdx.x; e < h1; e += kThreads) win[e - g0] = in[e];
+        for (int64_t e = max(v1, h1) + threadIdx.x; e < e1; e += kThreads) win[e - g0] = in[e];
+      } else {
+        for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) win[e - g0] = in[e];
+      }
     } else {
-      for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) win[e - g0] = in[e];
+      for (int64_t e = e0 + threadIdx.x; e < e1; e += kThreads) win[e - g0] = load_sample(in, e);
     }
   }
   __syncthreads();
@@ -96,7 +109,8 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restr
         if (idx < 0 || idx >= n) continue;           // skipped, not added as zero (resample.cpp:187-205)
         float v;
         if (idx >= wlo && idx < whi) v = win[idx - sh];
-        else v = x[idx];
+        else if constexpr (std::is_same<Sample, float>::value) v = x[idx];
+        else v = load_sample(x, idx);
         acc = __fadd_rn(acc, __fmul_rn(w[j], v));
       }
     }
@@ -106,8 +120,10 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const float* __restr
 
 }  // namespace
 
-void launch_resample(const float* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
-                     int B, const ResampleTable& t, hipStream_t s) {
+namespace {
+template <typename Sample>
+void launch_resample_any(const Sample* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
+                         int B, const ResampleTable& t, hipStream_t s) {
   // span: 4 outputs per lane, fewer when the staged window would not fit (strong downsampling to a low rate)
   int span = 4 * kThreads;
   auto window = [&](int sp) { return (int)(((int64_t)(sp - 1) * t.P + t.Q - 1) / t.Q) + t.K + 2 + 8; };
@@ -118,7 +134,7 @@ void launch_resample(const float* in, const int64_t* in_off, const int* n_in, fl
     a.nb = std::min(kMaxUtts, B - u0);
     a.span = span;
     a.lds = lds;
-    a.vec = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    a.vec = std::is_same<Sample, float>::value && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
     int blocks = 0;
     for (int i = 0; i < a.nb; ++i) {
       a.in_off[i] = in_off[u0 + i];
@@ -130,8 +146,18 @@ void launch_resample(const float* in, const int64_t* in_off, const int* n_in, fl
     }
     a.blk_off[a.nb] = blocks;
     if (blocks == 0) continue;
-    hipLaunchKernelGGL(resample_kernel, dim3(blocks), dim3(kThreads), (size_t)lds * sizeof(float), s, in, out, a, t);
+    hipLaunchKernelGGL(resample_kernel<Sample>, dim3(blocks), dim3(kThreads), (size_t)lds * sizeof(float), s, in, out, a, t);
   }
+}
+}  // namespace
+
+void launch_resample(const float* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
+                     int B, const ResampleTable& t, hipStream_t s) {
+  launch_resample_any(in, in_off, n_in, out, out_off, n_out, B, t, s);
+}
+void launch_resample(const int16_t* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
+                     int B, const ResampleTable& t, hipStream_t s) {
+  launch_resample_any(in, in_off, n_in, out, out_off, n_out, B, t, s);
 }
 
 }  // namespace pfhip

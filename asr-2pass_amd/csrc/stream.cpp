@@ -569,14 +569,21 @@ pfhip_status online_lfr_cmvn(pfhip_stream* s, int T, bool input_finished, Record
 }
 
 // ExtractFeats (:147-194) + x*sqrt(d) + GetPosEmb (:549-555): leaves `*n_rows` finished LFR rows in s->rows.
-pfhip_status extract_feats(pfhip_stream* s, const float* pcm, int len, bool input_finished, Recorder& rec, int* n_rows) {
+// 16-bit PCM is converted (s / 32768.f, exact) by the one copy into `waves` that this function makes of every sample anyway: the
+// splice cache, the staging buffer and the fbank launch stay f32, so the s16 entry points are the f32 ones bit for bit.
+pfhip_status extract_feats(pfhip_stream* s, PcmView pcm, int len, bool input_finished, Recorder& rec, int* n_rows) {
   pfhip_model* m = s->m;
   *n_rows = 0;
   const int fl = 400, fs = 160, lfr_m = m->cfg.lfr_m;
   // FbankKaldi (:119-145): prepend input_cache_, keep what follows the last frame shift for the next call
   std::vector<float>& waves = s->waves;            // lives until the flush of this call has copied it
   waves.assign(s->input_cache.begin(), s->input_cache.end());
-  waves.insert(waves.end(), pcm, pcm + len);
+  if (pcm.s16) {
+    waves.resize(s->input_cache.size() + (size_t)len);
+    pcm_to_f32(waves.data() + s->input_cache.size(), pcm, (size_t)len);
+  } else {
+    waves.insert(waves.end(), pcm.f32(), pcm.f32() + len);
+  }
   const int total = (int)waves.size();
   int frame_number = (total - fl) / fs + 1;
   if (!(frame_number >= 1 && total >= fl)) frame_number = 0;            // paraformer-online.h:25-31
@@ -681,7 +688,7 @@ namespace {
 // the reference calls ForwardChunk, so that the chunks of many connections can run as one packed forward.
 struct Call {
   pfhip_stream* s;
-  const float* pcm;
+  PcmView pcm;
   int n_samples;
   bool fin;
   std::vector<int32_t> out;
@@ -763,7 +770,7 @@ pfhip_status forward_calls(pfhip_model* m, std::vector<Call>& calls, hipStream_t
 // (n_tokens = the count it needed) and the others still receive their ids; only a failure of the shared forward itself
 // fails everybody, and then every stream of the batch is re-initialised (Reset + InitCache) so that its caches do not
 // keep a half-advanced chunk.  Returns the first non-OK status.
-pfhip_status forward_batch_each(pfhip_stream* const* streams, int n_streams, const float* const* pcm, const int* n_samples,
+pfhip_status forward_batch_each(pfhip_stream* const* streams, int n_streams, const PcmView* pcm, const int* n_samples,
                                 const int* input_finished, int32_t* const* token_ids, const int* cap, int* n_tokens,
                                 pfhip_status* each, std::string* each_err) {
   auto all = [&](pfhip_status st) {
@@ -779,7 +786,7 @@ pfhip_status forward_batch_each(pfhip_stream* const* streams, int n_streams, con
     pfhip_stream* s = streams[i];
     if (!s || s->m != m) return all(fail(PFHIP_ERR_ARG, "streams of one batch must belong to one model"));
     for (int j = 0; j < i; ++j) if (streams[j] == s) return all(fail(PFHIP_ERR_ARG, "a stream appears twice in one batch"));
-    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return all(fail(PFHIP_ERR_ARG, "bad pcm buffer"));
+    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i].p)) return all(fail(PFHIP_ERR_ARG, "bad pcm buffer"));
     if (n_samples[i] > kMaxSamples) return all(fail(PFHIP_ERR_ARG, "more than 32000 samples in one streaming call"));
     calls[i].s = s; calls[i].pcm = pcm[i]; calls[i].n_samples = n_samples[i]; calls[i].fin = input_finished[i] != 0;
     n_tokens[i] = 0;
@@ -812,15 +819,10 @@ pfhip_status forward_batch_each(pfhip_stream* const* streams, int n_streams, con
   if (first) last_error() = first_err;
   return first;
 }
-}  // namespace
 
-extern "C" {
-
-pfhip_status pfhip_stream_forward_batch(pfhip_stream* const* streams, int n_streams, const float* const* pcm, const int* n_samples,
-                                        const int* input_finished, int32_t* const* token_ids, const int* cap, int* n_tokens) {
-  last_error().clear();
-  if (!streams || n_streams <= 0 || !pcm || !n_samples || !input_finished || !token_ids || !cap || !n_tokens)
-    return fail(PFHIP_ERR_ARG, "bad argument");
+// pfhip_stream_forward_batch on per-connection PCM views (either sample format, connection by connection)
+pfhip_status stream_forward_batch(pfhip_stream* const* streams, int n_streams, const PcmView* pcm, const int* n_samples,
+                                  const int* input_finished, int32_t* const* token_ids, const int* cap, int* n_tokens) {
   // streams of a replica group (pfhip_create_group) may sit on different devices: one sub-batch per replica, run concurrently
   std::vector<pfhip_model*> models;
   for (int i = 0; i < n_streams; ++i) {
@@ -840,7 +842,7 @@ pfhip_status pfhip_stream_forward_batch(pfhip_stream* const* streams, int n_stre
   for (Part& p : parts)
     pool.emplace_back([&, pp = &p] {
       const size_t n = pp->idx.size();
-      std::vector<pfhip_stream*> ss(n); std::vector<const float*> pc(n); std::vector<int> ns(n), fin(n), cp(n), nt(n); std::vector<int32_t*> ids(n);
+      std::vector<pfhip_stream*> ss(n); std::vector<PcmView> pc(n); std::vector<int> ns(n), fin(n), cp(n), nt(n); std::vector<int32_t*> ids(n);
       for (size_t k = 0; k < n; ++k) {
         const int i = pp->idx[k];
         ss[k] = streams[i]; pc[k] = pcm[i]; ns[k] = n_samples[i]; fin[k] = input_finished[i]; cp[k] = cap[i]; ids[k] = token_ids[i];
@@ -856,6 +858,31 @@ pfhip_status pfhip_stream_forward_batch(pfhip_stream* const* streams, int n_stre
   return PFHIP_OK;
 }
 
+template <typename Sample>
+pfhip_status stream_forward_batch_of(pfhip_stream* const* streams, int n_streams, const Sample* const* pcm, const int* n_samples,
+                                     const int* input_finished, int32_t* const* token_ids, const int* cap, int* n_tokens) {
+  last_error().clear();
+  if (!streams || n_streams <= 0 || !pcm || !n_samples || !input_finished || !token_ids || !cap || !n_tokens)
+    return fail(PFHIP_ERR_ARG, "bad argument");
+  std::vector<PcmView> views((size_t)n_streams);
+  for (int i = 0; i < n_streams; ++i) views[i] = PcmView{pcm[i], sizeof(Sample) == 2};
+  return stream_forward_batch(streams, n_streams, views.data(), n_samples, input_finished, token_ids, cap, n_tokens);
+}
+}  // namespace
+
+extern "C" {
+
+pfhip_status pfhip_stream_forward_batch(pfhip_stream* const* streams, int n_streams, const float* const* pcm, const int* n_samples,
+                                        const int* input_finished, int32_t* const* token_ids, const int* cap, int* n_tokens) {
+  return stream_forward_batch_of(streams, n_streams, pcm, n_samples, input_finished, token_ids, cap, n_tokens);
+}
+// the same on 16-bit PCM (the bytes Audio::LoadPcmwavOnline, audio.cpp:821-857, divides by 32768 on the host)
+pfhip_status pfhip_stream_forward_batch_s16(pfhip_stream* const* streams, int n_streams, const int16_t* const* pcm,
+                                            const int* n_samples, const int* input_finished, int32_t* const* token_ids,
+                                            const int* cap, int* n_tokens) {
+  return stream_forward_batch_of(streams, n_streams, pcm, n_samples, input_finished, token_ids, cap, n_tokens);
+}
+
 }  // extern "C"
 
 // ---- cross-connection batching behind the per-connection call --------------------------------------------------------
@@ -864,7 +891,7 @@ pfhip_status pfhip_stream_forward_batch(pfhip_stream* const* streams, int n_stre
 // streams of one model are merged like the offline callers (pfhip_set_batching): the first to arrive leads, waits up to
 // wait_us for others, runs ONE batched forward (forward_calls) and hands every caller its ids.
 struct StreamReq : pfhip_detail::MergeReqBase {
-  pfhip_stream* s; const float* pcm; int n; int fin; int32_t* ids; int cap; int* n_out;
+  pfhip_stream* s; pfhip_detail::PcmView pcm; int n; int fin; int32_t* ids; int cap; int* n_out;      // f32 and s16 callers merge freely
   pfhip_status st = PFHIP_OK; std::string err;
 };
 
@@ -873,7 +900,7 @@ namespace {
 void run_requests(const std::vector<StreamReq*>& reqs) {
   const int n = (int)reqs.size();
   std::vector<pfhip_stream*> ss(n);
-  std::vector<const float*> pcm(n);
+  std::vector<PcmView> pcm(n);
   std::vector<int> ns(n), fin(n), cap(n), nt(n);
   std::vector<int32_t*> ids(n);
   for (int i = 0; i < n; ++i) { ss[i] = reqs[i]->s; pcm[i] = reqs[i]->pcm; ns[i] = reqs[i]->n; fin[i] = reqs[i]->fin; ids[i] = reqs[i]->ids; cap[i] = reqs[i]->cap; }
@@ -913,6 +940,22 @@ pfhip_status stream_forward_queued(pfhip_model* m, StreamReq& me) {
   return me.st;
 }
 
+pfhip_status stream_forward_one(pfhip_stream* s, PcmView pcm, int n_samples, int input_finished, int32_t* token_ids, int cap,
+                                int* n_tokens) {
+  if (!s || !n_tokens) { last_error().clear(); return fail(PFHIP_ERR_ARG, "bad argument"); }
+  if (s->m->stream_wait_us > 0 && !s->debug) {
+    last_error().clear();
+    if (n_samples < 0 || (n_samples > 0 && !pcm.p) || n_samples > kMaxSamples) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    StreamReq me;
+    me.s = s; me.pcm = pcm; me.n = n_samples; me.fin = input_finished; me.ids = token_ids; me.cap = cap; me.n_out = n_tokens;
+    *n_tokens = 0;
+    return stream_forward_queued(s->m, me);
+  }
+  last_error().clear();
+  int32_t* ids[1] = {token_ids};
+  return stream_forward_batch(&s, 1, &pcm, &n_samples, &input_finished, ids, &cap, n_tokens);
+}
+
 }  // namespace
 
 extern "C" {
@@ -931,18 +974,11 @@ pfhip_status pfhip_set_stream_batching(pfhip_model* m, int wait_us, int max_stre
 
 pfhip_status pfhip_stream_forward(pfhip_stream* s, const float* pcm, int n_samples, int input_finished,
                                   int32_t* token_ids, int cap, int* n_tokens) {
-  if (!s || !n_tokens) { last_error().clear(); return fail(PFHIP_ERR_ARG, "bad argument"); }
-  if (s->m->stream_wait_us > 0 && !s->debug) {
-    last_error().clear();
-    if (n_samples < 0 || (n_samples > 0 && !pcm) || n_samples > kMaxSamples) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
-    StreamReq me;
-    me.s = s; me.pcm = pcm; me.n = n_samples; me.fin = input_finished; me.ids = token_ids; me.cap = cap; me.n_out = n_tokens;
-    *n_tokens = 0;
-    return stream_forward_queued(s->m, me);
-  }
-  int32_t* ids[1] = {token_ids};
-  const float* p[1] = {pcm};
-  return pfhip_stream_forward_batch(&s, 1, p, &n_samples, &input_finished, ids, &cap, n_tokens);
+  return stream_forward_one(s, PcmView{pcm, false}, n_samples, input_finished, token_ids, cap, n_tokens);
+}
+pfhip_status pfhip_stream_forward_s16(pfhip_stream* s, const int16_t* pcm, int n_samples, int input_finished,
+                                      int32_t* token_ids, int cap, int* n_tokens) {
+  return stream_forward_one(s, PcmView{pcm, true}, n_samples, input_finished, token_ids, cap, n_tokens);
 }
 
 pfhip_status pfhip_stream_set_debug(pfhip_stream* s, int on) {

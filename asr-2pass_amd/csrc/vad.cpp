@@ -200,23 +200,29 @@ static pfhip_status vad_workspace(pfhip_vad* v, int T) {
   return PFHIP_OK;
 }
 
-static pfhip_status vad_forward_impl(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* probs,
+static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, int is_final, float* probs,
                                      size_t cap_floats, int* n_frames, bool sil_only);
 
 pfhip_status pfhip_vad_forward(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* probs,
                                size_t cap_floats, int* n_frames) {
-  return vad_forward_impl(v, pcm, n_samples, is_final, probs, cap_floats, n_frames, false);
+  return vad_forward_impl(v, PcmView{pcm, false}, n_samples, is_final, probs, cap_floats, n_frames, false);
 }
 
 pfhip_status pfhip_vad_forward_sil(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* sil_prob,
                                    size_t cap_floats, int* n_frames) {
-  return vad_forward_impl(v, pcm, n_samples, is_final, sil_prob, cap_floats, n_frames, true);
+  return vad_forward_impl(v, PcmView{pcm, false}, n_samples, is_final, sil_prob, cap_floats, n_frames, true);
+}
+// the same from 16-bit PCM (the bytes Audio::LoadPcmwav, audio.cpp:787-819, divides by 32768 on the host): copied as they are,
+// converted by the fbank kernel's loads
+pfhip_status pfhip_vad_forward_sil_s16(pfhip_vad* v, const int16_t* pcm, int n_samples, int is_final, float* sil_prob,
+                                       size_t cap_floats, int* n_frames) {
+  return vad_forward_impl(v, PcmView{pcm, true}, n_samples, is_final, sil_prob, cap_floats, n_frames, true);
 }
 
-static pfhip_status vad_forward_impl(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* probs,
+static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, int is_final, float* probs,
                                      size_t cap_floats, int* n_frames, bool sil_only) {
   last_error().clear();
-  if (!v || n_samples < 0 || (n_samples > 0 && !pcm) || !n_frames) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!v || n_samples < 0 || (n_samples > 0 && !pcm.p) || !n_frames) return fail(PFHIP_ERR_ARG, "bad argument");
   std::lock_guard<std::mutex> lk(v->mu);
   HIP_TRY(hipSetDevice(v->device));
   hipStream_t s = v->stream;
@@ -226,7 +232,7 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, const float* pcm, int n_sampl
   if (T == 0) return PFHIP_OK;                                // fsmn-vad.cpp:245-247
   if ((size_t)T * (sil_only ? 1 : v->n_out) > cap_floats && probs) return fail(PFHIP_ERR_CAPACITY, "probs buffer too small");
   const int Tp = round_up(T, 128);
-  HIP_TRY(v->pcm.ensure((size_t)n_samples * 4));
+  HIP_TRY(v->pcm.ensure((size_t)n_samples * pcm.sample_bytes()));      // the one workspace, in floats or in shorts
   HIP_TRY(v->fb.ensure((size_t)F * 80 * 4));
   HIP_TRY(v->feats.ensure((size_t)Tp * v->in1.Kp * 4));
   HIP_TRY(v->a.ensure((size_t)Tp * 256 * 4));
@@ -237,7 +243,7 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, const float* pcm, int n_sampl
   HIP_TRY(v->sil.ensure((size_t)T * 4));
   if (v->in1.Np > 256 || v->in2.Np > 256 || v->out1.Np > 256 || v->out2.Np > 256 || v->proj > 128)
     return fail(PFHIP_ERR_UNSUPPORTED, "FSMN-VAD layer wider than the workspace");
-  HIP_TRY(hipMemcpyAsync(v->pcm.p, pcm, (size_t)n_samples * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(v->pcm.p, pcm.p, (size_t)n_samples * pcm.sample_bytes(), hipMemcpyHostToDevice, s));
   {
     int64_t* h64 = reinterpret_cast<int64_t*>(v->h_pin);
     h64[0] = 0;
@@ -246,8 +252,12 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, const float* pcm, int n_sampl
     HIP_TRY(hipMemcpyAsync(v->meta.p, v->h_pin, 32, hipMemcpyHostToDevice, s));
   }
   pfhip::FbankTables tb{v->ft.d_window, v->ft.d_tw, v->ft.d_mel_off, v->ft.d_mel_size, v->ft.d_mel_w, v->d_mean, v->d_istd};
-  pfhip::launch_fbank_frames(v->pcm.f(), reinterpret_cast<int64_t*>(v->meta.p), v->meta.i() + 2, v->meta.i() + 4, F, tb,
-                             v->fb.f(), s);
+  if (pcm.s16)
+    pfhip::launch_fbank_frames(static_cast<const int16_t*>(v->pcm.p), reinterpret_cast<int64_t*>(v->meta.p), v->meta.i() + 2,
+                               v->meta.i() + 4, F, tb, v->fb.f(), s);
+  else
+    pfhip::launch_fbank_frames(v->pcm.f(), reinterpret_cast<int64_t*>(v->meta.p), v->meta.i() + 2, v->meta.i() + 4, F, tb,
+                               v->fb.f(), s);
   pfhip::launch_lfr_cmvn(v->fb.f(), F, T, v->lfr_m, v->lfr_n, v->n_mels, v->d_mean, v->d_istd, v->feats.f(), v->in1.Kp, s);
   {
     pfhip::VadSeg* hs = reinterpret_cast<pfhip::VadSeg*>(v->h_pin + 16);
@@ -341,7 +351,7 @@ namespace {
 // One connection's share of a (batched) FsmnVadOnline::Infer: the host part of ExtractFeats runs first and leaves a plan,
 // the device work of all connections is then issued as a handful of batched launches.
 struct VadCall {
-  pfhip_vad_stream* vs; const float* pcm; int n_samples; bool fin;
+  pfhip_vad_stream* vs; PcmView pcm; int n_samples; bool fin;
   float* sil_prob; size_t cap_floats; int* n_frames; float* waves_out; size_t waves_cap; int* n_waves;
   // plan.  buf = this call's slice of the pinned sample staging: [reserve_waveforms_ | input_cache_ | new samples]
   float* buf = nullptr;
@@ -354,7 +364,8 @@ struct VadCall {
 };
 
 // ExtractFeats (:40-88) on counters and sample ranges only; the one copy of the samples made here is the one into the
-// staging buffer the device reads
+// staging buffer the device reads.  16-bit PCM becomes s / 32768.f (exact) during that copy: the caches, the waveform handed to the
+// scorer (waves_out, whose decibel track needs floats) and the fbank launch stay f32 — bit for bit the f32 entry points.
 pfhip_status vad_plan(VadCall& c) {
   pfhip_vad_stream* vs = c.vs;
   pfhip_vad* v = vs->v;
@@ -362,7 +373,7 @@ pfhip_status vad_plan(VadCall& c) {
   const size_t r0 = vs->reserve.size(), ic = vs->input_cache.size();
   if (r0) std::memcpy(c.buf, vs->reserve.data(), r0 * 4);
   if (ic) std::memcpy(c.buf + r0, vs->input_cache.data(), ic * 4);
-  if (c.n_samples) std::memcpy(c.buf + r0 + ic, c.pcm, (size_t)c.n_samples * 4);
+  pcm_to_f32(c.buf + r0 + ic, c.pcm, (size_t)c.n_samples);
   c.used = r0 + ic + (size_t)c.n_samples;
   const float* W = c.buf + r0;                              // `waves` = input_cache_ ++ new samples (:43-44)
   const int total = (int)(ic + (size_t)c.n_samples);
@@ -533,14 +544,12 @@ pfhip_status vad_execute(pfhip_vad* v, std::vector<VadCall>& calls) {
   return PFHIP_OK;
 }
 
-}  // namespace
 
-extern "C" {
-
-pfhip_status pfhip_vad_stream_infer_batch(pfhip_vad_stream* const* streams, int n_streams, const float* const* pcm,
-                                          const int* n_samples, const int* input_finished, float* const* sil_prob,
-                                          const size_t* cap_floats, int* n_frames, float* const* waves_out,
-                                          const size_t* waves_cap, int* n_waves) {
+// pfhip_vad_stream_infer_batch on per-connection PCM views (either sample format, connection by connection)
+pfhip_status vad_stream_infer_batch(pfhip_vad_stream* const* streams, int n_streams, const PcmView* pcm,
+                                    const int* n_samples, const int* input_finished, float* const* sil_prob,
+                                    const size_t* cap_floats, int* n_frames, float* const* waves_out,
+                                    const size_t* waves_cap, int* n_waves) {
   last_error().clear();
   if (!streams || n_streams <= 0 || !pcm || !n_samples || !input_finished || !sil_prob || !cap_floats || !n_frames || !waves_out ||
       !waves_cap || !n_waves)
@@ -551,7 +560,7 @@ pfhip_status pfhip_vad_stream_infer_batch(pfhip_vad_stream* const* streams, int 
   for (int i = 0; i < n_streams; ++i) {
     if (!streams[i] || streams[i]->v != v) return fail(PFHIP_ERR_ARG, "streams of one batch must belong to one VAD model");
     for (int j = 0; j < i; ++j) if (streams[j] == streams[i]) return fail(PFHIP_ERR_ARG, "a stream appears twice in one batch");
-    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i].p)) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
     if (n_samples[i] > kVadMaxSamples) return fail(PFHIP_ERR_ARG, "more than 64000 samples in one online VAD call");
     calls[i].vs = streams[i]; calls[i].pcm = pcm[i]; calls[i].n_samples = n_samples[i]; calls[i].fin = input_finished[i] != 0;
     calls[i].sil_prob = sil_prob[i]; calls[i].cap_floats = cap_floats[i]; calls[i].n_frames = &n_frames[i];
@@ -561,6 +570,38 @@ pfhip_status pfhip_vad_stream_infer_batch(pfhip_vad_stream* const* streams, int 
   std::lock_guard<std::mutex> lk(v->mu);
   HIP_TRY(hipSetDevice(v->device));
   return vad_execute(v, calls);
+}
+
+template <typename Sample>
+pfhip_status vad_stream_infer_batch_of(pfhip_vad_stream* const* streams, int n_streams, const Sample* const* pcm,
+                                       const int* n_samples, const int* input_finished, float* const* sil_prob,
+                                       const size_t* cap_floats, int* n_frames, float* const* waves_out,
+                                       const size_t* waves_cap, int* n_waves) {
+  std::vector<PcmView> views;
+  if (pcm && n_streams > 0)
+    for (int i = 0; i < n_streams; ++i) views.push_back(PcmView{pcm[i], sizeof(Sample) == 2});
+  return vad_stream_infer_batch(streams, n_streams, views.empty() ? nullptr : views.data(), n_samples, input_finished, sil_prob,
+                                cap_floats, n_frames, waves_out, waves_cap, n_waves);
+}
+
+}  // namespace
+
+extern "C" {
+
+pfhip_status pfhip_vad_stream_infer_batch(pfhip_vad_stream* const* streams, int n_streams, const float* const* pcm,
+                                          const int* n_samples, const int* input_finished, float* const* sil_prob,
+                                          const size_t* cap_floats, int* n_frames, float* const* waves_out,
+                                          const size_t* waves_cap, int* n_waves) {
+  return vad_stream_infer_batch_of(streams, n_streams, pcm, n_samples, input_finished, sil_prob, cap_floats, n_frames, waves_out,
+                                   waves_cap, n_waves);
+}
+// the same on 16-bit PCM (the bytes Audio::LoadPcmwavOnline, audio.cpp:821-857, divides by 32768 on the host); waves_out stays f32
+pfhip_status pfhip_vad_stream_infer_batch_s16(pfhip_vad_stream* const* streams, int n_streams, const int16_t* const* pcm,
+                                              const int* n_samples, const int* input_finished, float* const* sil_prob,
+                                              const size_t* cap_floats, int* n_frames, float* const* waves_out,
+                                              const size_t* waves_cap, int* n_waves) {
+  return vad_stream_infer_batch_of(streams, n_streams, pcm, n_samples, input_finished, sil_prob, cap_floats, n_frames, waves_out,
+                                   waves_cap, n_waves);
 }
 
 pfhip_status pfhip_set_vad_stream_batching(pfhip_vad* v, int wait_us, int max_streams) {
@@ -577,7 +618,8 @@ pfhip_status pfhip_set_vad_stream_batching(pfhip_vad* v, int wait_us, int max_st
 // One FsmnVadOnline::Infer per websocket handler thread (funasrruntime.cpp:516-532): with wait_us > 0 the first caller to
 // arrive leads, waits up to wait_us for the others and runs ONE pfhip_vad_stream_infer_batch for all of them.
 struct VadReq : pfhip_detail::MergeReqBase {
-  pfhip_vad_stream* vs; const float* pcm; int n; int fin; float* sil; size_t cap; int* nf; float* wo; size_t wcap; int* nw;
+  pfhip_vad_stream* vs; pfhip_detail::PcmView pcm;      // f32 and s16 callers merge freely
+  int n; int fin; float* sil; size_t cap; int* nf; float* wo; size_t wcap; int* nw;
   pfhip_status st = PFHIP_OK; std::string err;
 };
 
@@ -586,7 +628,7 @@ namespace {
 void vad_run_requests(const std::vector<VadReq*>& reqs) {
   const int n = (int)reqs.size();
   std::vector<pfhip_vad_stream*> ss(n);
-  std::vector<const float*> pcm(n);
+  std::vector<PcmView> pcm(n);
   std::vector<int> ns(n), fin(n), nf(n), nw(n);
   std::vector<float*> sil(n), wo(n);
   std::vector<size_t> cap(n), wcap(n);
@@ -594,7 +636,7 @@ void vad_run_requests(const std::vector<VadReq*>& reqs) {
     const VadReq& r = *reqs[i];
     ss[i] = r.vs; pcm[i] = r.pcm; ns[i] = r.n; fin[i] = r.fin; sil[i] = r.sil; cap[i] = r.cap; wo[i] = r.wo; wcap[i] = r.wcap;
   }
-  const pfhip_status st = pfhip_vad_stream_infer_batch(ss.data(), n, pcm.data(), ns.data(), fin.data(), sil.data(), cap.data(),
+  const pfhip_status st = vad_stream_infer_batch(ss.data(), n, pcm.data(), ns.data(), fin.data(), sil.data(), cap.data(),
                                                        nf.data(), wo.data(), wcap.data(), nw.data());
   const std::string err = pfhip_detail::last_error();
   for (int i = 0; i < n; ++i) { *reqs[i]->nf = nf[i]; *reqs[i]->nw = nw[i]; reqs[i]->st = st; reqs[i]->err = err; }
@@ -622,12 +664,8 @@ pfhip_status vad_infer_queued(pfhip_vad* v, VadReq& me) {
   return me.st;
 }
 
-}  // namespace
-
-extern "C" {
-
-pfhip_status pfhip_vad_stream_infer(pfhip_vad_stream* vs, const float* pcm, int n_samples, int input_finished, float* sil_prob,
-                                    size_t cap_floats, int* n_frames, float* waves_out, size_t waves_cap, int* n_waves) {
+pfhip_status vad_stream_infer_one(pfhip_vad_stream* vs, PcmView pcm, int n_samples, int input_finished, float* sil_prob,
+                                  size_t cap_floats, int* n_frames, float* waves_out, size_t waves_cap, int* n_waves) {
   if (!vs || !n_frames || !n_waves) { last_error().clear(); return fail(PFHIP_ERR_ARG, "bad argument"); }
   pfhip_vad* v = vs->v;
   bool queued;
@@ -638,10 +676,24 @@ pfhip_status pfhip_vad_stream_infer(pfhip_vad_stream* vs, const float* pcm, int 
     me.wo = waves_out; me.wcap = waves_cap; me.nw = n_waves;
     return vad_infer_queued(v, me);
   }
-  const float* p[1] = {pcm};
   float* sp[1] = {sil_prob};
   float* wo[1] = {waves_out};
-  return pfhip_vad_stream_infer_batch(&vs, 1, p, &n_samples, &input_finished, sp, &cap_floats, n_frames, wo, &waves_cap, n_waves);
+  return vad_stream_infer_batch(&vs, 1, &pcm, &n_samples, &input_finished, sp, &cap_floats, n_frames, wo, &waves_cap, n_waves);
+}
+
+}  // namespace
+
+extern "C" {
+
+pfhip_status pfhip_vad_stream_infer(pfhip_vad_stream* vs, const float* pcm, int n_samples, int input_finished, float* sil_prob,
+                                    size_t cap_floats, int* n_frames, float* waves_out, size_t waves_cap, int* n_waves) {
+  return vad_stream_infer_one(vs, PcmView{pcm, false}, n_samples, input_finished, sil_prob, cap_floats, n_frames, waves_out,
+                              waves_cap, n_waves);
+}
+pfhip_status pfhip_vad_stream_infer_s16(pfhip_vad_stream* vs, const int16_t* pcm, int n_samples, int input_finished, float* sil_prob,
+                                        size_t cap_floats, int* n_frames, float* waves_out, size_t waves_cap, int* n_waves) {
+  return vad_stream_infer_one(vs, PcmView{pcm, true}, n_samples, input_finished, sil_prob, cap_floats, n_frames, waves_out,
+                              waves_cap, n_waves);
 }
 
 }  // extern "C"

@@ -37,11 +37,14 @@ def merge_online_segments(vad_segments: Sequence[Sequence[int]]) -> List[Tuple[i
 def cut_split(pcm: np.ndarray, vad, segmenter, vad_tail_sil=800, vad_max_len=60000, speech_noise_thres=0.9):
     """Returns (frames, index_vector): frames = [(start_sample, end_sample)] in time order, index_vector = their
     order by increasing length (audio.cpp:1226-1239), i.e. the order they are queued for FetchDynamic."""
-    sil = vad.ForwardSil(pcm, is_final=True)
+    sil = vad.ForwardSil(pcm, is_final=True)          # np.int16 audio goes to the device as it is
     if sil.size == 0:
         return [], []
     n_used = 400 + 160 * (sil.size - 1)
-    segs = segmenter(sil, pcm[:max(n_used, 0)], True, False, vad_tail_sil, vad_max_len, speech_noise_thres)
+    wave = pcm[:max(n_used, 0)]
+    if np.asarray(wave).dtype == np.int16:            # the end-point detector's decibel track reads floats
+        wave = np.asarray(wave).astype(np.float32) / np.float32(32768.0)
+    segs = segmenter(sil, wave, True, False, vad_tail_sil, vad_max_len, speech_noise_thres)
     frames = [(s * SEG_SAMPLE, min(e * SEG_SAMPLE, len(pcm))) for s, e in segs]
     index_vector = sorted(range(len(frames)), key=lambda i: (frames[i][1] - frames[i][0], i))     # stable like std::sort on ties? see note
     return frames, index_vector
@@ -72,7 +75,8 @@ def fetch_dynamic(queue: List[Tuple[int, int]], batch_size: int):
 
 def infer_buffer(pcm: np.ndarray, asr, vad, segmenter, batch_size=32, vad_tail_sil=800, vad_max_len=60000,
                  speech_noise_thres=0.9):
-    """FunOfflineInferBuffer for one file: returns (token ids per segment in TIME order, segments in samples)."""
+    """FunOfflineInferBuffer for one file: returns (token ids per segment in TIME order, segments in samples).
+    pcm: float32 in [-1, 1), or np.int16 as the server receives it (the VAD and the acoustic model then take the s16 entry points)."""
     frames, index_vector = cut_split(pcm, vad, segmenter, vad_tail_sil, vad_max_len, speech_noise_thres)
     queue = [frames[i] for i in index_vector]
     msgs = []

@@ -195,6 +195,37 @@ pfhip_status pfhip_resample(pfhip_model* m, const float* const* pcm, const int* 
 pfhip_status pfhip_offline_forward_rate(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
                                         const float* hw_emb, int n_hotwords, pfhip_out* out);
 
+/* ---- 16-bit PCM in ----------------------------------------------------------------------------------
+ * Replaces the host loops of Audio::LoadPcmwav (onnxruntime/src/audio.cpp:787-819) and Audio::LoadPcmwavOnline (:821-857), which
+ * turn the little-endian s16 bytes a client sends into floats, `speech_data[i] = (float)speech_buff[i] / scale` with scale 32768,
+ * before Model::Forward sees them.  Every *_s16 entry point takes those samples as they arrive (host-endian int16_t; the
+ * supported hosts are little-endian) and means by the sample s the float s / 32768.f.  That division is exact, and so is the
+ * x 32768 the front end applies again (paraformer.cpp:312-314): the fbank kernel's s16 form loads (float)s with no multiply, the
+ * resampler's converts on load, and every output — feats, log-probs, ids, token_num, us_alphas / us_peaks, N-best, VAD scores —
+ * is bit for bit that of the f32 sibling fed s / 32768.f.  Half the bytes cross to the device, and no float copy is made on the host.
+ * Arguments other than `pcm` are those of the sibling; sample offsets and counts are in samples.  A device buffer of packed s16
+ * (pfhip_offline_enqueue_s16, pfhip_offline_forward_resident_s16) needs 2-byte alignment only: an utterance may start at an odd sample.
+ * pfhip_offline_fetch / pfhip_offline_fetch_nbest serve both enqueue forms; a range-guard re-run reads the buffer in the format it was
+ * enqueued in.
+ * Merged callers (pfhip_set_batching, pfhip_set_hotword_merging): f32 and s16 callers share the queue, and a packed forward holds ONE
+ * format — the leader takes the queued callers of its own format and leaves the others, in order, for the next leader — so results
+ * stay those of separate calls and nothing is converted on the host.  The two streaming families (pfhip_stream_forward*_s16,
+ * pfhip_vad_stream_infer*_s16) convert during the one copy the host makes of every sample anyway (the splice caches and the waveform
+ * handed to the end-point detector are floats); their merged rounds (pfhip_set_stream_batching, pfhip_set_vad_stream_batching) mix
+ * the two formats freely.  pfhip_vad_stream_infer*_s16 still return waves_out as floats: pfhip_vadseg_feed's decibel track reads it. */
+pfhip_status pfhip_offline_forward_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch,
+                                       const float* hw_emb, int n_hotwords, pfhip_out* out);
+pfhip_status pfhip_offline_forward_hwsets_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch,
+                                              const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                              pfhip_out* out);
+/* Audio::LoadPcmwav + WavResample (audio.cpp:787-819, 259-284): s16 at sample_rate, resampled on the device */
+pfhip_status pfhip_offline_forward_rate_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch,
+                                            int sample_rate, const float* hw_emb, int n_hotwords, pfhip_out* out);
+pfhip_status pfhip_offline_enqueue_s16(pfhip_model* m, const int16_t* d_pcm, const int64_t* sample_off, const int* n_samples,
+                                       int batch, void* stream);
+pfhip_status pfhip_offline_forward_resident_s16(pfhip_model* m, const int16_t* d_pcm, const int64_t* sample_off,
+                                                const int* n_samples, int batch, pfhip_out* out);
+
 /* ---- hotwords (contextual model) ---------------------------------------------------------------
  *   pfhip_hotword_embed <-> the `hw_m_session->Run` on model_eb.onnx + the per-hotword row selection inside
  *                           Paraformer::CompileHotwordEmbedding (paraformer.cpp:656-685): ids i32 [H,10] (0-padded, last row
@@ -295,6 +326,9 @@ void pfhip_stream_destroy(pfhip_stream* s);
 pfhip_status pfhip_stream_reset(pfhip_stream* s);
 pfhip_status pfhip_stream_forward(pfhip_stream* s, const float* pcm, int n_samples, int input_finished,
                                   int32_t* token_ids, int cap, int* n_tokens);
+/* From 16-bit PCM as Audio::LoadPcmwavOnline reads it (audio.cpp:821-857); see "16-bit PCM in" above. */
+pfhip_status pfhip_stream_forward_s16(pfhip_stream* s, const int16_t* pcm, int n_samples, int input_finished,
+                                      int32_t* token_ids, int cap, int* n_tokens);
 /* Which branch of ParaformerOnline::Forward the stream's last call took: 0 not a final call (or no feature row), 1 the short
  * final call that flushes the look-back cache (:532-540), 2 a final call whose rows fit one last chunk (:557-559; the only one
  * whose non-empty text the reference ends with a blank, :585-587), 3 first chunk + last chunk (:560-579). */
@@ -311,6 +345,9 @@ int pfhip_stream_last_path(const pfhip_stream* s);
 pfhip_status pfhip_stream_forward_batch(pfhip_stream* const* streams, int n_streams, const float* const* pcm,
                                         const int* n_samples, const int* input_finished, int32_t* const* token_ids,
                                         const int* cap, int* n_tokens);
+pfhip_status pfhip_stream_forward_batch_s16(pfhip_stream* const* streams, int n_streams, const int16_t* const* pcm,
+                                            const int* n_samples, const int* input_finished, int32_t* const* token_ids,
+                                            const int* cap, int* n_tokens);      /* audio.cpp:821-857 */
 /* Cross-connection batching behind the per-connection call: with wait_us > 0, concurrent pfhip_stream_forward callers on
  * different streams of model m (the 2-pass server's one-strand-per-connection threads, websocket-server-2pass.cpp:266-297)
  * are merged into one pfhip_stream_forward_batch of up to max_streams connections; the first caller waits at most wait_us.
@@ -345,6 +382,9 @@ pfhip_status pfhip_vad_forward(pfhip_vad* v, const float* pcm, int n_samples, in
  * detector reads (e2e-vad.h:103,607-609): T floats instead of T x 248. */
 pfhip_status pfhip_vad_forward_sil(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* sil_prob,
                                    size_t cap_floats, int* n_frames);
+/* From 16-bit PCM as Audio::LoadPcmwav reads it (audio.cpp:787-819); see "16-bit PCM in" above. */
+pfhip_status pfhip_vad_forward_sil_s16(pfhip_vad* v, const int16_t* pcm, int n_samples, int is_final, float* sil_prob,
+                                       size_t cap_floats, int* n_frames);
 
 /* ---- online FSMN-VAD: one pfhip_vad_stream per connection = one `funasr::FsmnVadOnline` --------------------------------
  * (onnxruntime/src/fsmn-vad-online.cpp; built on the offline handle like FsmnVadOnline(FsmnVad*), :206-219).
@@ -362,6 +402,10 @@ pfhip_status pfhip_vad_stream_reset(pfhip_vad_stream* vs);
 pfhip_status pfhip_vad_stream_infer(pfhip_vad_stream* vs, const float* pcm, int n_samples, int input_finished, float* sil_prob,
                                     size_t cap_floats, int* n_frames, float* waves_out, size_t waves_cap, int* n_waves);
 
+/* From 16-bit PCM as Audio::LoadPcmwavOnline reads it (audio.cpp:821-857); waves_out stays f32. */
+pfhip_status pfhip_vad_stream_infer_s16(pfhip_vad_stream* vs, const int16_t* pcm, int n_samples, int input_finished, float* sil_prob,
+                                        size_t cap_floats, int* n_frames, float* waves_out, size_t waves_cap, int* n_waves);
+
 /* The same call for n_streams connections of ONE pfhip_vad at once (arrays of the per-connection arguments above): the 2-pass
  * server's websocket handlers each call FsmnVadOnline::Infer per 600 ms message (websocket-server-2pass.cpp:85-117 ->
  * funasrruntime.cpp:516-532); issued together they share every launch (fbank, OnlineLfrCmvn rows, the 11 GEMMs, the FSMN
@@ -371,6 +415,11 @@ pfhip_status pfhip_vad_stream_infer_batch(pfhip_vad_stream* const* streams, int 
                                           const int* n_samples, const int* input_finished, float* const* sil_prob,
                                           const size_t* cap_floats, int* n_frames, float* const* waves_out,
                                           const size_t* waves_cap, int* n_waves);
+
+pfhip_status pfhip_vad_stream_infer_batch_s16(pfhip_vad_stream* const* streams, int n_streams, const int16_t* const* pcm,
+                                              const int* n_samples, const int* input_finished, float* const* sil_prob,
+                                              const size_t* cap_floats, int* n_frames, float* const* waves_out,
+                                              const size_t* waves_cap, int* n_waves);      /* audio.cpp:821-857 */
 
 /* Merge concurrent pfhip_vad_stream_infer callers (one thread per connection, as the reference's websocket handlers are) into
  * batched passes: wait_us > 0 and max_streams > 1 make the first caller wait up to wait_us for others.  Default: off. */
@@ -480,7 +529,8 @@ pfhip_status pfhip_group_stats(pfhip_model* m, int* devices, int64_t* calls, int
 /* Test hook, not part of the serving path: "blstm_flag" (value != 0) raises the timestamp head's error word for the next
  * timestamp request only — as a step-barrier time-out of the persistent BLSTM kernel would — which then has to be served by the
  * per-step recurrence; "blstm_fallbacks" returns (as the status value) how many requests were served that way; "plane_forwards"
- * how many forwards of this context ran the encoder on plane-image operands (gemm_p3.hip: batches of PFHIP_PLANES_MIN_ROWS+ rows). */
+ * how many forwards of this context ran the encoder on plane-image operands (gemm_p3.hip: batches of PFHIP_PLANES_MIN_ROWS+ rows);
+ * "format_splits" how many merged batches (pfhip_set_batching) were cut short because f32 and s16 callers were queued together. */
 pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value);
 pfhip_status pfhip_profile_enable(pfhip_model* m, int on);
 pfhip_status pfhip_profile_read(pfhip_model* m, pfhip_profile* out, int reset);
