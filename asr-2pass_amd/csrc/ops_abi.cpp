@@ -3,9 +3,28 @@
 
 #include "kernels.h"
 
+#include <vector>
+
 namespace {
 inline hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
 inline int done() { return (int)hipGetLastError(); }
+// The entries of kernels that read device descriptors (StreamSeg, VadSeg) take plain host arrays: the descriptors are built here,
+// uploaded with a synchronous copy, and freed after the stream has drained.  Test entries: the sync costs nothing that matters.
+template <class Seg, class Launch>
+int with_device_segs(const std::vector<Seg>& host, hipStream_t s, Launch launch) {
+  Seg* d = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), host.size() * sizeof(Seg));
+  if (e != hipSuccess) return (int)e;
+  e = hipMemcpy(d, host.data(), host.size() * sizeof(Seg), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch(d);
+    e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = e2;
+  }
+  (void)hipFree(d);
+  return (int)e;
+}
 }  // namespace
 
 extern "C" {
@@ -231,6 +250,93 @@ int pfhip_op_logsoftmax_topk(const float* logits, int ldl, int M, int V, int k, 
                              float* topk_logp, void* stream) {
   // the launcher checks k, V >= k, ldl >= V and the buffers before it launches anything
   if (!pfhip::launch_logsoftmax_topk(logits, ldl, M, V, k, logp, ids, topk_ids, topk_logp, S(stream))) return (int)hipErrorInvalidValue;
+  return done();
+}
+
+// ---- the scan, cache and row kernels (tests only: the descriptor-taking ones upload their descriptors synchronously) ----------------
+int pfhip_op_cif_stream(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
+                        const int* pre, const int* suf, float* carry, long long carry_stride, int B, int D, float threshold,
+                        float tail, float* emb, int emb_rows, int* n_fire, void* stream) {
+  if (B <= 0 || D <= 0 || D > 1024 || lde < D || emb_rows < 0 || carry_stride < D + 1 || !enc || !alphas || !row_off || !n || !is_last ||
+      !pre || !suf || !carry || !emb || !n_fire)
+    return (int)hipErrorInvalidValue;
+  std::vector<pfhip::StreamSeg> segs((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    if (row_off[b] < 0 || n[b] < 0) return (int)hipErrorInvalidValue;
+    pfhip::StreamSeg sg{};
+    sg.carry = carry + (size_t)b * carry_stride;
+    sg.row_off = row_off[b]; sg.n = n[b];
+    sg.is_last = is_last[b]; sg.pre = pre[b]; sg.suf = suf[b];
+    segs[b] = sg;
+  }
+  return with_device_segs(segs, S(stream), [&](const pfhip::StreamSeg* d) {
+    pfhip::launch_cif_stream(enc, lde, alphas, d, B, threshold, tail, emb, emb_rows, n_fire, D, S(stream));
+  });
+}
+int pfhip_op_fsmn_cached(const float* t2, const float* w, const float* res, float* out, const int* tok_off, const int* n_tok, float* dcache,
+                         long long dcache_stride, int B, int layer, int C, void* stream) {
+  if (B <= 0 || C <= 0 || C % 4 || layer < 0 || dcache_stride < (long long)(layer + 1) * 10 * C || dcache_stride % 4 || !t2 || !w || !res ||
+      !out || !tok_off || !n_tok || !dcache)
+    return (int)hipErrorInvalidValue;
+  std::vector<pfhip::StreamSeg> segs((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    if (tok_off[b] < 0) return (int)hipErrorInvalidValue;
+    pfhip::StreamSeg sg{};
+    sg.dcache = dcache + (size_t)b * dcache_stride;
+    sg.tok_off = tok_off[b]; sg.n_tok = n_tok[b];
+    segs[b] = sg;
+  }
+  return with_device_segs(segs, S(stream), [&](const pfhip::StreamSeg* d) {
+    pfhip::launch_fsmn_cached(t2, w, res, out, d, B, layer, C, S(stream));
+  });
+}
+int pfhip_op_fsmn_causal20(const float* p, int ldp, const float* w, const int* row_off, const int* T, const int* final,
+                           const float* cache_in, float* cache_out, long long cache_stride, int B, int layer, float* out, int ldo, int C,
+                           void* stream) {
+  if (B <= 0 || C <= 0 || C % 4 || ldp % 4 || ldo % 4 || ldp < C || ldo < C || layer < 0 || cache_stride < (long long)(layer + 1) * 19 * C ||
+      cache_stride % 4 || !p || !w || !row_off || !T || !final || !cache_in || !cache_out || cache_in == cache_out || !out)
+    return (int)hipErrorInvalidValue;
+  std::vector<pfhip::VadSeg> segs((size_t)B);
+  int max_T = 0;
+  for (int b = 0; b < B; ++b) {
+    if (row_off[b] < 0 || T[b] < 0) return (int)hipErrorInvalidValue;
+    segs[b] = pfhip::VadSeg{cache_in + (size_t)b * cache_stride, final[b] ? nullptr : cache_out + (size_t)b * cache_stride, row_off[b], T[b]};
+    if (T[b] > max_T) max_T = T[b];
+  }
+  return with_device_segs(segs, S(stream), [&](const pfhip::VadSeg* d) {
+    pfhip::launch_fsmn_causal20(p, ldp, w, d, B, max_T, layer, out, ldo, C, S(stream));
+  });
+}
+int pfhip_op_softmax_rows(const float* x, int ldx, int M, int N, float* y, float* col0, void* stream) {
+  if (M < 0 || N <= 0 || ldx < N || !x || !y) return (int)hipErrorInvalidValue;
+  pfhip::launch_softmax_rows(x, ldx, M, N, y, col0, S(stream));
+  return done();
+}
+int pfhip_op_im2col3(const float* h, int ldh, float* col, int ldc, const int* row_pos, const int* row_len, int M, int D, void* stream) {
+  if (M < 0 || D <= 0 || D % 4 || ldh % 4 || ldc % 4 || ldh < D || ldc < 3 * D || !h || !col || !row_pos || !row_len) return (int)hipErrorInvalidValue;
+  pfhip::launch_im2col3(h, ldh, col, ldc, row_pos, row_len, M, D, S(stream));
+  return done();
+}
+int pfhip_op_alpha(const float* o, int ldo, const float* w, const float* b, float smooth, float noise, float* alphas, int M, int D,
+                   void* stream) {
+  if (M < 0 || D <= 0 || D % 4 || ldo % 4 || ldo < D || !o || !w || !b || !alphas) return (int)hipErrorInvalidValue;
+  pfhip::launch_alpha(o, ldo, w, b, smooth, noise, alphas, M, D, S(stream));
+  return done();
+}
+int pfhip_op_alpha2(const float* y, int ldy, const float* w, float b, float smooth, float noise, float* a2, int rows, int D, void* stream) {
+  if (rows < 0 || D <= 0 || D % 4 || ldy % 4 || ldy < D || !y || !w || !a2) return (int)hipErrorInvalidValue;
+  pfhip::launch_alpha2(y, ldy, w, b, smooth, noise, a2, rows, D, S(stream));
+  return done();
+}
+int pfhip_op_us_cif(const float* a2, const int* off, const int* len, const int* token_num, int B, int max_len, float threshold,
+                    float* us_alphas, float* us_peaks, void* stream) {
+  if (B < 0 || max_len < 0 || !a2 || !off || !len || !token_num || !us_alphas || !us_peaks) return (int)hipErrorInvalidValue;
+  pfhip::launch_us_cif(a2, off, len, token_num, B, max_len, threshold, us_alphas, us_peaks, S(stream));
+  return done();
+}
+int pfhip_op_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, int t, float* sel, int H, int D, void* stream) {
+  if (H < 0 || D <= 0 || !G || !c || !h || !lens || !sel) return (int)hipErrorInvalidValue;
+  pfhip::launch_lstm_cell(G, c, h, lens, t, sel, H, D, S(stream));
   return done();
 }
 

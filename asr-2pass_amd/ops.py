@@ -420,3 +420,96 @@ def attention_kvplanes(Q, kv, v_col, q_off, q_len, kv_off, kv_len, n_head, scale
                                         Q.shape[0], float(scale), _p(fsmn_w), _p(mem), mem.stride(0) if mem is not None else 0,
                                         1 if mem_accumulate else 0, _stream()), "attention_kvplanes")
     return P if want_planes else O
+
+
+# ---- the scan, cache and row kernels (csrc/stream.hip, vad.hip, rowops.hip, blstm.hip) ------------------------------------------------
+def _hi(values):
+    """A host int32 array for an entry that takes per-connection HOST arrays: (keep-alive array, pointer)."""
+    import numpy as np
+    a = np.ascontiguousarray(values, np.int32)
+    return a, ctypes.c_void_p(a.ctypes.data)
+
+
+_ll = ctypes.c_longlong
+
+
+def cif_stream(enc, alphas, row_off, n, is_last, pre, suf, carry, D, threshold, tail, emb, n_fire):
+    """CifSearch for B connections in one launch.  row_off / n / is_last / pre / suf: host int sequences; carry [B, >= D + 1]
+    (hidden, then the integrate scalar; replaced in place); emb [B, emb_rows, D] and n_fire [B] int32 are written."""
+    B = len(n)
+    lib = _lib()
+    lib.pfhip_op_cif_stream.argtypes = [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ci, _ci, _cf, _cf, _vp, _ci, _vp, _vp]
+    ro, n_, il, pr, su = _hi(row_off), _hi(n), _hi(is_last), _hi(pre), _hi(suf)
+    _ck(lib.pfhip_op_cif_stream(_p(enc), enc.stride(0), _p(alphas), ro[1], n_[1], il[1], pr[1], su[1], _p(carry), carry.stride(0), B, D,
+                                float(threshold), float(tail), _p(emb), emb.shape[1], _p(n_fire), _stream()), "cif_stream")
+
+
+def fsmn_cached(t2, w, res, out, tok_off, n_tok, dcache, layer):
+    """The streaming decoder's cached FSMN for B connections: out (may be res) = res + t2 + conv over [cache; t2];
+    dcache [B, layers, 10, C] is advanced in place.  tok_off / n_tok: host int sequences."""
+    lib = _lib()
+    lib.pfhip_op_fsmn_cached.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ci, _ci, _ci, _vp]
+    to, nt = _hi(tok_off), _hi(n_tok)
+    _ck(lib.pfhip_op_fsmn_cached(_p(t2), _p(w), _p(res), _p(out), to[1], nt[1], _p(dcache), dcache.stride(0), len(n_tok), layer,
+                                 t2.shape[1], _stream()), "fsmn_cached")
+
+
+def fsmn_causal20(p, w, row_off, T, final, cache_in, cache_out, layer, C, out):
+    """The FSMN-VAD memory block (left order 20) for B connections: out rows = p + causal conv over [cache_in; p]; cache_out
+    [B, layers, 19, C] receives the last 19 rows of [cache_in; p] where final[b] == 0.  row_off / T / final: host int sequences."""
+    lib = _lib()
+    lib.pfhip_op_fsmn_causal20.argtypes = [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ci, _ci, _vp, _ci, _ci, _vp]
+    ro, tt, fi = _hi(row_off), _hi(T), _hi(final)
+    _ck(lib.pfhip_op_fsmn_causal20(_p(p), p.stride(0), _p(w), ro[1], tt[1], fi[1], _p(cache_in), _p(cache_out), cache_in.stride(0), len(T),
+                                   layer, _p(out), out.stride(0), C, _stream()), "fsmn_causal20")
+
+
+def softmax_rows(x, M, N, y, col0=None):
+    """y [>= M, N] = softmax over columns [0, N) of x's rows; col0 [>= M] (optional) = y[:, 0]."""
+    lib = _lib()
+    lib.pfhip_op_softmax_rows.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
+    _ck(lib.pfhip_op_softmax_rows(_p(x), x.stride(0), M, N, _p(y), _p(col0), _stream()), "softmax_rows")
+
+
+def im2col3(h, row_pos, row_len, D, ldc=None, out=None):
+    """col [M, 3 D] = [h[row - 1] | h[row] | h[row + 1]] with zeros outside the row's utterance (row_pos / row_len: int32 device)."""
+    M = row_pos.numel()
+    col = out if out is not None else torch.empty((M, 3 * D if ldc is None else ldc), dtype=torch.float32, device=h.device)
+    lib = _lib()
+    lib.pfhip_op_im2col3.argtypes = [_vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _vp]
+    _ck(lib.pfhip_op_im2col3(_p(h), h.stride(0), _p(col), col.stride(0), _p(row_pos), _p(row_len), M, D, _stream()), "im2col3")
+    return col
+
+
+def alpha(o, w, b, smooth, noise, M, D):
+    lib = _lib()
+    lib.pfhip_op_alpha.argtypes = [_vp, _ci, _vp, _vp, _cf, _cf, _vp, _ci, _ci, _vp]
+    a = torch.empty(M, dtype=torch.float32, device=o.device)
+    _ck(lib.pfhip_op_alpha(_p(o), o.stride(0), _p(w), _p(b), float(smooth), float(noise), _p(a), M, D, _stream()), "alpha")
+    return a
+
+
+def alpha2(y, w, b, smooth, noise, M, D):
+    lib = _lib()
+    lib.pfhip_op_alpha2.argtypes = [_vp, _ci, _vp, _cf, _cf, _cf, _vp, _ci, _ci, _vp]
+    a = torch.empty(M, dtype=torch.float32, device=y.device)
+    _ck(lib.pfhip_op_alpha2(_p(y), y.stride(0), _p(w), float(b), float(smooth), float(noise), _p(a), M, D, _stream()), "alpha2")
+    return a
+
+
+def us_cif(a2, off, length, token_num, threshold):
+    """(us_alphas, us_peaks) of the timestamp head for the utterances (off, length, token_num: int32 device tensors)."""
+    lib = _lib()
+    lib.pfhip_op_us_cif.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _cf, _vp, _vp, _vp]
+    us_alphas, us_peaks = torch.zeros_like(a2), torch.zeros_like(a2)
+    _ck(lib.pfhip_op_us_cif(_p(a2), _p(off), _p(length), _p(token_num), off.numel(), int(length.max().item()), float(threshold),
+                            _p(us_alphas), _p(us_peaks), _stream()), "us_cif")
+    return us_alphas, us_peaks
+
+
+def lstm_cell(G, c, h, lens, t, sel):
+    """One LSTM step in place on c, h [H, D] from pre-activations G [H, 4 D]; sel rows with lens - 1 == t receive h."""
+    H, D = c.shape
+    lib = _lib()
+    lib.pfhip_op_lstm_cell.argtypes = [_vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _vp]
+    _ck(lib.pfhip_op_lstm_cell(_p(G), _p(c), _p(h), _p(lens), int(t), _p(sel), H, D, _stream()), "lstm_cell")

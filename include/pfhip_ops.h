@@ -158,6 +158,47 @@ int pfhip_op_resample_table(int fs_in, int fs_out, int32_t* first_index, int32_t
 int pfhip_op_resample(const float* d_in, const int64_t* in_off, const int* n_in, int batch, int fs_in, int fs_out, float* d_out,
                       const int64_t* out_off, void* stream);
 
+/* ---- The scan, cache and row kernels, one entry each, for operator tests (no model path calls these entries).
+ * Where a kernel reads per-connection device descriptors (csrc/kernels.h StreamSeg / VadSeg), the entry takes plain HOST arrays of
+ * B entries plus a base pointer and a stride (in floats) for the per-connection state, builds the descriptors, uploads them with a
+ * synchronous copy and returns after the stream has drained.  Every entry returns hipErrorInvalidValue, before anything is
+ * launched, for what its kernel assumes: channel counts and row strides that are not multiples of 4, a NULL buffer. */
+/* CifSearch (onnxruntime/src/paraformer-online.cpp:270-345) for B connections: connection b integrates its carry, rows
+ * [row_off[b], row_off[b] + n[b]) of enc / alphas (alphas outside [pre[b], suf[b]) count as 0) and, with is_last[b], the tail slot.
+ * Its fires land in emb[b * emb_rows ..] (D floats a row; fires past emb_rows are counted, not stored), their count in n_fire[b];
+ * its carry (hidden [D], then the integrate scalar) lives at carry + b * carry_stride and is replaced.  D <= 1024. */
+int pfhip_op_cif_stream(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
+                        const int* pre, const int* suf, float* carry, long long carry_stride, int B, int D, float threshold,
+                        float tail, float* emb, int emb_rows, int* n_fire, void* stream);
+/* The streaming decoder's FSMN with its 10-frame cache (paraformer-online.cpp:374, 500): connection b's tokens are rows
+ * [tok_off[b], tok_off[b] + n_tok[b]) of t2 / res / out (row stride C; out may alias res), its caches [layers][10][C] live at
+ * dcache + b * dcache_stride; out = res + t2 + conv over [cache; t2], and the layer's cache becomes the last 10 rows of [cache; t2]
+ * (untouched where n_tok[b] == 0). */
+int pfhip_op_fsmn_cached(const float* t2, const float* w, const float* res, float* out, const int* tok_off, const int* n_tok, float* dcache,
+                         long long dcache_stride, int B, int layer, int C, void* stream);
+/* The FSMN-VAD memory block, left order 20 (fsmn-vad.cpp:129-134): connection b's rows are [row_off[b], row_off[b] + T[b]) of p / out,
+ * its caches [layers][19][C] at cache_in / cache_out + b * cache_stride; out = p + causal conv over [cache_in; p], cache_out = the
+ * last 19 rows of [cache_in; p] — not written where final[b] != 0.  cache_out must not be cache_in. */
+int pfhip_op_fsmn_causal20(const float* p, int ldp, const float* w, const int* row_off, const int* T, const int* final,
+                           const float* cache_in, float* cache_out, long long cache_stride, int B, int layer, float* out, int ldo, int C,
+                           void* stream);
+/* Softmax over columns [0, N) of every row; y [M][N] packed, col0 (may be NULL) [M] = y[:, 0]. */
+int pfhip_op_softmax_rows(const float* x, int ldx, int M, int N, float* y, float* col0, void* stream);
+/* The predictor's Conv1d k = 3 operand: col[row] = [h[row - 1] | h[row] | h[row + 1]], zeros where row_pos[row] -/+ 1 leaves
+ * [0, row_len[row]) (device arrays: the local index and the utterance length of every packed row). */
+int pfhip_op_im2col3(const float* h, int ldh, float* col, int ldc, const int* row_pos, const int* row_len, int M, int D, void* stream);
+/* alphas[row] = relu(sigmoid(o[row] . w + b[0]) * smooth - noise): CifPredictorV2's head; alpha2 the timestamp head's (b by value). */
+int pfhip_op_alpha(const float* o, int ldo, const float* w, const float* b, float smooth, float noise, float* alphas, int M, int D,
+                   void* stream);
+int pfhip_op_alpha2(const float* y, int ldy, const float* w, float b, float smooth, float noise, float* a2, int rows, int D, void* stream);
+/* Timestamp head, per utterance b (frames [off[b], off[b] + len[b]); device arrays; len[b] <= max_len): us_alphas = a2 rescaled to
+ * sum to token_num[b], us_peaks = cif_wo_hidden(us_alphas, threshold). */
+int pfhip_op_us_cif(const float* a2, const int* off, const int* len, const int* token_num, int B, int max_len, float threshold,
+                    float* us_alphas, float* us_peaks, void* stream);
+/* One LSTM step of the hotword embedder on pre-activations G [H][4 D] (gates i, f, g, o): c, h [H][D] updated in place; rows with
+ * lens[j] - 1 == t also copy h into sel[j]. */
+int pfhip_op_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, int t, float* sel, int H, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,41 @@ def decoder_chunk(emb, enc, caches, W):
     return (z - lse).astype(F32), new_caches
 
 
+def cif_search(hidden, alphas, hidden_cache, alphas_cache, chunk_size, is_last_chunk, encoder_size, tail_alphas, cif_threshold):
+    """ParaformerOnline::CifSearch (paraformer-online.cpp:270-345) as a function of its state: returns (list_frame, the new
+    hidden_cache_, the new alphas_cache_).  The method below calls it; the operator tests call it directly."""
+    hidden = [h for h in hidden]
+    alphas = np.asarray(alphas, F32).copy()
+    alphas[:chunk_size[0]] = 0.0
+    chunk_size_suf = chunk_size[0] + chunk_size[1]
+    alphas[chunk_size_suf:] = 0.0
+    alphas = list(alphas)
+    if len(hidden_cache) > 0:
+        hidden = list(hidden_cache) + hidden
+        alphas = list(alphas_cache) + alphas
+    if is_last_chunk:
+        hidden.append(np.zeros(encoder_size, F32))
+        alphas.append(tail_alphas)
+    thr = cif_threshold
+    integrate = F32(0.0)
+    frames = np.zeros(encoder_size, F32)
+    list_frame = []
+    for i in range(len(alphas)):
+        alpha = F32(alphas[i])
+        if F32(alpha + integrate) < thr:
+            integrate = F32(integrate + alpha)
+            frames = (frames + alpha * hidden[i]).astype(F32)
+        else:
+            frames = (frames + F32(thr - integrate) * hidden[i]).astype(F32)
+            list_frame.append(frames.copy())
+            integrate = F32(integrate + alpha)
+            integrate = F32(integrate - thr)
+            frames = (integrate * hidden[i]).astype(F32)
+    if integrate > 0.0:
+        return list_frame, [(frames / integrate).astype(F32)], [integrate]
+    return list_frame, [frames.copy()], [integrate]
+
+
 class ParaformerOnline:
     """State and methods named after the reference class (paraformer-online.h)."""
 
@@ -217,39 +252,9 @@ class ParaformerOnline:
 
     # :270-345
     def CifSearch(self, hidden, alphas):
-        hidden = [h for h in hidden]
-        alphas = np.asarray(alphas, F32).copy()
-        alphas[:self.chunk_size[0]] = 0.0
-        chunk_size_suf = self.chunk_size[0] + self.chunk_size[1]
-        alphas[chunk_size_suf:] = 0.0
-        alphas = list(alphas)
-        if len(self.hidden_cache_) > 0:
-            hidden = list(self.hidden_cache_) + hidden
-            alphas = list(self.alphas_cache_) + alphas
-            self.hidden_cache_, self.alphas_cache_ = [], []
-        if self.is_last_chunk:
-            hidden.append(np.zeros(self.encoder_size, F32))
-            alphas.append(self.tail_alphas)
-        thr = self.cif_threshold
-        integrate = F32(0.0)
-        frames = np.zeros(self.encoder_size, F32)
-        list_frame = []
-        for i in range(len(alphas)):
-            alpha = F32(alphas[i])
-            if F32(alpha + integrate) < thr:
-                integrate = F32(integrate + alpha)
-                frames = (frames + alpha * hidden[i]).astype(F32)
-            else:
-                frames = (frames + F32(thr - integrate) * hidden[i]).astype(F32)
-                list_frame.append(frames.copy())
-                integrate = F32(integrate + alpha)
-                integrate = F32(integrate - thr)
-                frames = (integrate * hidden[i]).astype(F32)
-        self.alphas_cache_ = [integrate]
-        if integrate > 0.0:
-            self.hidden_cache_ = [(frames / integrate).astype(F32)]
-        else:
-            self.hidden_cache_ = [frames.copy()]
+        list_frame, self.hidden_cache_, self.alphas_cache_ = cif_search(
+            hidden, alphas, self.hidden_cache_, self.alphas_cache_, self.chunk_size, self.is_last_chunk, self.encoder_size,
+            self.tail_alphas, self.cif_threshold)
         return list_frame
 
     # :415-523

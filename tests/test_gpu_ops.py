@@ -251,21 +251,25 @@ def test_cif_bit_exact_against_oracle(ops):
     lens = [1, 5, 83, 500, 0, 9]
     off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
     M = sum(lens)
-    hidden = rng.standard_normal((M, 512)).astype(np.float32)
-    alphas = rng.uniform(0, 0.7, M).astype(np.float32)
-    stage, nf, tn = ops.cif(dev(hidden), dev(alphas), dev(off), dev(np.asarray(lens, np.int32)), 1.0, 0.45)
-    stage, nf, tn = stage.cpu().numpy(), nf.cpu().numpy(), tn.cpu().numpy()
-    for b, (o, L) in enumerate(zip(off, lens)):
-        if L == 0:
-            assert nf[b] == 0 and tn[b] == 0
-            continue
-        h = np.concatenate([hidden[o:o + L], np.zeros((1, 512), np.float32)])
-        a = np.concatenate([alphas[o:o + L], np.asarray([0.45], np.float32)])
-        emb, _ = P.cif(h, a, 1.0)
-        assert nf[b] == emb.shape[0]
-        assert tn[b] == int(np.floor(np.cumsum(a, dtype=np.float32)[-1]))
-        # same operations in the same order with contraction off: bit-exact
-        assert np.array_equal(stage[o + b:o + b + nf[b]], emb)
+    # D = 320 / 512: cif_kernel<1>; D = 516: cif_kernel<2> with four channels in its second slot
+    for D in (320, 512, 516):
+        hidden = rng.standard_normal((M, D)).astype(np.float32)
+        # the second set: multiples of 1/16 in [0, 1], whose running sums are exact in fp32, so that alpha + integrate == threshold
+        # happens (uniform alphas never meet the threshold) and an alpha of 1.0 fires on its own frame
+        for alphas in (rng.uniform(0, 0.7, M).astype(np.float32), (rng.integers(0, 17, M) / 16.0).astype(np.float32)):
+            stage, nf, tn = ops.cif(dev(hidden), dev(alphas), dev(off), dev(np.asarray(lens, np.int32)), 1.0, 0.45)
+            stage, nf, tn = stage.cpu().numpy(), nf.cpu().numpy(), tn.cpu().numpy()
+            for b, (o, L) in enumerate(zip(off, lens)):
+                if L == 0:
+                    assert nf[b] == 0 and tn[b] == 0
+                    continue
+                h = np.concatenate([hidden[o:o + L], np.zeros((1, D), np.float32)])
+                a = np.concatenate([alphas[o:o + L], np.asarray([0.45], np.float32)])
+                emb, _ = P.cif(h, a, 1.0)
+                assert nf[b] == emb.shape[0]
+                assert tn[b] == int(np.floor(np.cumsum(a, dtype=np.float32)[-1]))
+                # same operations in the same order with contraction off: bit-exact
+                assert np.array_equal(stage[o + b:o + b + nf[b]], emb)
 
 
 def test_logsoftmax_argmax_first_max_wins(ops):
