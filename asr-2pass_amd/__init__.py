@@ -45,6 +45,9 @@ ABI_SYMBOLS = [
     "pfhip_offline_forward_s16", "pfhip_offline_forward_hwsets_s16", "pfhip_offline_forward_rate_s16", "pfhip_offline_enqueue_s16",
     "pfhip_offline_forward_resident_s16", "pfhip_vad_forward_sil_s16", "pfhip_stream_forward_s16", "pfhip_stream_forward_batch_s16",
     "pfhip_vad_stream_infer_s16", "pfhip_vad_stream_infer_batch_s16",
+    # VAD: the decibel track on the device, files in company
+    "pfhip_vad_forward_sil_energy", "pfhip_vad_forward_sil_energy_s16", "pfhip_vad_forward_sil_batch", "pfhip_vad_forward_sil_batch_s16",
+    "pfhip_set_vad_batching", "pfhip_vad_batch_stats", "pfhip_vadseg_feed_energy",
 ]
 
 
@@ -203,6 +206,11 @@ def load_lib() -> ctypes.CDLL:
     lib.pfhip_vadseg_destroy.restype = None
     lib.pfhip_vadseg_reset.argtypes = [vp]
     lib.pfhip_vadseg_feed.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, ctypes.c_float, ci, vp, ci, ctypes.POINTER(ci)]
+    lib.pfhip_vadseg_feed_energy.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ctypes.c_float, ci, vp, ci, ctypes.POINTER(ci)]
+    lib.pfhip_vad_forward_sil_energy.argtypes = [vp, vp, ci, ci, vp, ctypes.c_size_t, ctypes.POINTER(ci), vp, ctypes.c_size_t, ctypes.POINTER(ci)]
+    lib.pfhip_vad_forward_sil_batch.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.pfhip_set_vad_batching.argtypes = [vp, ci, ci]
+    lib.pfhip_vad_batch_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ci)]
     lib.pfhip_timestamp_onnx.argtypes = [vp, vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, ci, ctypes.POINTER(ci)]
     lib.pfhip_punc_create_from_memory.argtypes = [vp, ctypes.c_size_t, ctypes.c_char_p, ci, ctypes.POINTER(vp)]
     lib.pfhip_punc_destroy.argtypes = [vp]
@@ -219,7 +227,7 @@ def load_lib() -> ctypes.CDLL:
     # 16-bit PCM in: the argument lists of the f32 siblings
     for f in ("pfhip_offline_forward", "pfhip_offline_forward_hwsets", "pfhip_offline_forward_rate", "pfhip_offline_enqueue",
               "pfhip_offline_forward_resident", "pfhip_vad_forward_sil", "pfhip_stream_forward", "pfhip_stream_forward_batch",
-              "pfhip_vad_stream_infer", "pfhip_vad_stream_infer_batch"):
+              "pfhip_vad_stream_infer", "pfhip_vad_stream_infer_batch", "pfhip_vad_forward_sil_energy", "pfhip_vad_forward_sil_batch"):
         getattr(lib, f + "_s16").argtypes = getattr(lib, f).argtypes
     _lib = lib
     return lib
@@ -773,6 +781,47 @@ class FsmnVadHip:
                                                           1 if is_final else 0, sil.ctypes.data, cap, ctypes.byref(n)))
         return sil[:n.value]
 
+    def ForwardSilEnergy(self, waves, is_final=False):
+        """ForwardSil plus the frame energies (sum of squares of every 25-ms frame) of these samples, computed on the device:
+        (sil [T], energy [F]).  Feed both to E2EVadModelHost.feed_energy; np.int16 waves go to the s16 entry point as they are."""
+        (x,), s16 = _pcm_buffers([waves])
+        cap = max(0, (x.size - 400) // 160 + 1) + 1
+        sil, eng = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+        n, ne = ctypes.c_int(0), ctypes.c_int(0)
+        fn = self._lib.pfhip_vad_forward_sil_energy_s16 if s16 else self._lib.pfhip_vad_forward_sil_energy
+        _check(self._lib, fn(self._h, x.ctypes.data if x.size else None, int(x.size), 1 if is_final else 0, sil.ctypes.data, cap,
+                             ctypes.byref(n), eng.ctypes.data, cap, ctypes.byref(ne)))
+        return sil[:n.value], eng[:ne.value]
+
+    def ForwardSilBatch(self, files):
+        """Several COMPLETE files in one device pass, each scored like ForwardSilEnergy(x, is_final=True) on a fresh object (the
+        handle's carried caches are not touched): [(sil, energy), ...].  All np.int16 -> the s16 entry point."""
+        xs, s16 = _pcm_buffers(files)
+        n = len(xs)
+        if n == 0:
+            return []
+        caps = [max(0, (x.size - 400) // 160 + 1) + 1 for x in xs]
+        sil = [np.zeros(c, np.float32) for c in caps]
+        eng = [np.zeros(c, np.float32) for c in caps]
+        ptrs = lambda arrs: (ctypes.c_void_p * n)(*[a.ctypes.data if a.size else None for a in arrs])
+        ns = (ctypes.c_int * n)(*[int(x.size) for x in xs])
+        cp = (ctypes.c_size_t * n)(*caps)
+        nf, ne = (ctypes.c_int * n)(), (ctypes.c_int * n)()
+        fn = self._lib.pfhip_vad_forward_sil_batch_s16 if s16 else self._lib.pfhip_vad_forward_sil_batch
+        _check(self._lib, fn(self._h, ptrs(xs), ns, n, ptrs(sil), cp, nf, ptrs(eng), cp, ne))
+        return [(sil[i][:nf[i]], eng[i][:ne[i]]) for i in range(n)]
+
+    def set_batching(self, wait_us, max_files=32):
+        """Merge concurrent ForwardSilEnergy(is_final=True) callers on a handle without carried state into ForwardSilBatch passes
+        (pfhip_set_vad_batching); 0 = off."""
+        _check(self._lib, self._lib.pfhip_set_vad_batching(self._h, int(wait_us), int(max_files)))
+
+    def batch_stats(self):
+        """Packed passes so far: {"passes", "files", "max_files"}."""
+        p, f, m = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_int(0)
+        _check(self._lib, self._lib.pfhip_vad_batch_stats(self._h, ctypes.byref(p), ctypes.byref(f), ctypes.byref(m)))
+        return {"passes": p.value, "files": f.value, "max_files": m.value}
+
     def Forward(self, waves, is_final=False):
         x = _pcm_f32(waves)
         C = self._lib.pfhip_vad_num_classes(self._h)
@@ -957,6 +1006,22 @@ class E2EVadModelHost:
                                                       int(online), int(max_end_sil), int(max_single_segment_time),
                                                       float(speech_noise_thres), int(sample_rate), segs.ctypes.data, cap,
                                                       ctypes.byref(n)))
+        return [[int(a), int(b)] for a, b in segs[:n.value]]
+
+    def feed_energy(self, score_sil, energy, n_samples, is_final=False, online=False, max_end_sil=800, max_single_segment_time=15000,
+                    speech_noise_thres=0.8, sample_rate=16000):
+        """The same call with the frame energies of the n_samples new samples (FsmnVadHip.ForwardSilEnergy, ops.frame_energy) in
+        place of the waveform (pfhip_vadseg_feed_energy): same segments, no samples on the host."""
+        sc = np.ascontiguousarray(score_sil, dtype=np.float32)
+        en = np.ascontiguousarray(energy, dtype=np.float32)
+        cap = sc.size + 8
+        segs = np.zeros((cap, 2), np.int32)
+        n = ctypes.c_int(0)
+        _check(self._lib, self._lib.pfhip_vadseg_feed_energy(self._h, sc.ctypes.data if sc.size else None, int(sc.size),
+                                                             en.ctypes.data if en.size else None, int(en.size), int(n_samples),
+                                                             int(is_final), int(online), int(max_end_sil), int(max_single_segment_time),
+                                                             float(speech_noise_thres), int(sample_rate), segs.ctypes.data, cap,
+                                                             ctypes.byref(n)))
         return [[int(a), int(b)] for a, b in segs[:n.value]]
 
 

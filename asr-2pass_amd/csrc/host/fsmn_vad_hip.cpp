@@ -63,42 +63,55 @@ void FsmnVadHip::InitVad(const std::string& vad_model, const std::string& vad_cm
   vad_silence_duration_ = (int)ManifestNumber(man, "max_end_silence_time", 800);             // model_conf (fsmn-vad.cpp:36-38)
   vad_max_len_ = (int)ManifestNumber(man, "max_single_segment_time", 60000);
   vad_speech_noise_thres_ = (float)ManifestNumber(man, "speech_noise_thres", 0.9);
+  // the decoder threads' files are scored in company (pfhip_set_vad_batching; a lone caller never waits).  PFHIP_VAD_MERGE=0 keeps
+  // every file alone; PFHIP_VAD_FILE_WAIT_US / PFHIP_VAD_FILE_MAX size the merge.
+  auto knob = [](const char* name, int dflt) { const char* e = std::getenv(name); return e && *e ? std::atoi(e) : dflt; };
+  const int wait_us = knob("PFHIP_VAD_FILE_WAIT_US", 2000), max_files = knob("PFHIP_VAD_FILE_MAX", 32);
+  if (knob("PFHIP_VAD_MERGE", 1) != 0 && wait_us > 0 && max_files > 1 && pfhip_set_vad_batching(handle_, wait_us, max_files) != PFHIP_OK)
+    std::fprintf(stderr, "FsmnVadHip::InitVad: %s (one file at a time)\n", pfhip_last_error());
 }
 
-void FsmnVadHip::Reset() {
-  std::lock_guard<std::mutex> lk(mu_);
-  (void)pfhip_vad_reset(handle_);
-}
+void FsmnVadHip::Reset() { (void)pfhip_vad_reset(handle_); }
 
 std::vector<std::vector<int>> FsmnVadHip::Infer(std::vector<float>& waves, bool input_finished) {
-  return InferAny(nullptr, waves, input_finished);
+  return InferAny(waves.data(), nullptr, (int)waves.size(), input_finished, vad_silence_duration_, vad_max_len_);
 }
 std::vector<std::vector<int>> FsmnVadHip::InferPcm16(const int16_t* pcm16, std::vector<float>& waves, bool input_finished) {
-  return InferAny(pcm16, waves, input_finished);
+  return InferAny(nullptr, pcm16, (int)waves.size(), input_finished, vad_silence_duration_, vad_max_len_);
+}
+std::vector<std::vector<int>> FsmnVadHip::InferPcm16(const int16_t* pcm16, int n, bool input_finished) {
+  return InferAny(nullptr, pcm16, n, input_finished, vad_silence_duration_, vad_max_len_);
+}
+std::vector<std::vector<int>> FsmnVadHip::InferFile(const float* f32, const int16_t* pcm16, int n, int vad_tail_sil, int vad_max_len) {
+  return InferAny(f32, pcm16, n, true, vad_tail_sil, vad_max_len);
 }
 
-std::vector<std::vector<int>> FsmnVadHip::InferAny(const int16_t* pcm16, std::vector<float>& waves, bool input_finished) {
-  const int n = (int)waves.size();
+// The device returns the silence posteriors AND the frame energies of the detector's decibel track (pfhip_vad_forward_sil_energy),
+// so the host reads no sample: 16-bit input needs no float copy.  No lock here: the C ABI serialises device passes itself, and a
+// final call on a handle without carried caches may be scored in company with other threads' files.
+std::vector<std::vector<int>> FsmnVadHip::InferAny(const float* f32, const int16_t* pcm16, int n, bool input_finished, int tail_sil,
+                                                   int max_len) {
   const int max_frames = n >= 400 ? (n - 400) / 160 + 1 : 0;
   if (max_frames <= 0) return {};                           // no full window: no features (:245-247)
-  std::vector<float> sil((size_t)max_frames + 8);
-  int T = 0;
-  {
-    std::lock_guard<std::mutex> lk(mu_);
-    const pfhip_status fs = pcm16 ? pfhip_vad_forward_sil_s16(handle_, pcm16, n, input_finished ? 1 : 0, sil.data(), sil.size(), &T)
-                                  : pfhip_vad_forward_sil(handle_, waves.data(), n, input_finished ? 1 : 0, sil.data(), sil.size(), &T);
-    if (fs != PFHIP_OK) {
-      std::fprintf(stderr, "FsmnVadHip::Infer: %s\n", pfhip_last_error());
-      return {};
-    }
+  std::vector<float> sil((size_t)max_frames + 8), energy((size_t)max_frames + 8);
+  int T = 0, F = 0;
+  const pfhip_status fs =
+      pcm16 ? pfhip_vad_forward_sil_energy_s16(handle_, pcm16, n, input_finished ? 1 : 0, sil.data(), sil.size(), &T, energy.data(),
+                                               energy.size(), &F)
+            : pfhip_vad_forward_sil_energy(handle_, f32, n, input_finished ? 1 : 0, sil.data(), sil.size(), &T, energy.data(),
+                                           energy.size(), &F);
+  if (fs != PFHIP_OK) {
+    std::fprintf(stderr, "FsmnVadHip::Infer: %s\n", pfhip_last_error());
+    return {};
   }
   if (T <= 0) return {};
   pfhip_vadseg* seg = nullptr;
   if (pfhip_vadseg_create(&seg) != PFHIP_OK) return {};
   std::vector<int32_t> pairs((size_t)2 * (T / 2 + 8));
   int n_seg = 0;
-  const pfhip_status st = pfhip_vadseg_feed(seg, sil.data(), T, waves.data(), std::min(400 + 160 * (T - 1), n), 1, 0, vad_silence_duration_,
-                                            vad_max_len_, vad_speech_noise_thres_, 16000, pairs.data(), (int)pairs.size() / 2, &n_seg);
+  // the detector gets the samples of the T scored frames, as before: 400 + 160 (T - 1) of them, i.e. T energies
+  const pfhip_status st = pfhip_vadseg_feed_energy(seg, sil.data(), T, energy.data(), T, std::min(400 + 160 * (T - 1), n), 1, 0, tail_sil,
+                                                   max_len, vad_speech_noise_thres_, 16000, pairs.data(), (int)pairs.size() / 2, &n_seg);
   pfhip_vadseg_destroy(seg);
   if (st != PFHIP_OK) return {};
   return Pairs(pairs, n_seg);

@@ -1,7 +1,8 @@
 // Host side of the VAD path in the reference's own language: `FsmnVadHip` / `FsmnVadOnlineHip`, the siblings of
 // `funasr::FsmnVad` / `funasr::FsmnVadOnline` behind `class funasr::VadModel` (onnxruntime/include/vad-model.h:10-19).
-// Infer = device forward (pfhip_vad_forward_sil / pfhip_vad_stream_infer) + the end-point detector on the host
-// (pfhip_vadseg_feed), exactly the split of fsmn-vad.cpp:240-256 and fsmn-vad-online.cpp:135-151.
+// Infer = device forward (pfhip_vad_forward_sil_energy / pfhip_vad_stream_infer) + the end-point detector on the host
+// (pfhip_vadseg_feed_energy / pfhip_vadseg_feed), exactly the split of fsmn-vad.cpp:240-256 and fsmn-vad-online.cpp:135-151; the
+// offline object's detector reads the frame energies the device returns, not the samples.
 //
 // Built stand-alone against the small interface below; inside the reference tree define PFHIP_WITH_FUNASR to derive from
 // the real funasr::VadModel.
@@ -44,10 +45,15 @@ class FsmnVadHip : public VadModelHipBase {
   // fsmn-vad.cpp:240-256: scores of the whole buffer, a FRESH detector run with is_final = true, online = false.
   // The network caches carry over between calls unless input_finished (Forward, :129-134); Reset() zeroes them.
   std::vector<std::vector<int>> Infer(std::vector<float>& waves, bool input_finished = true) override;
-  // The same on 16-bit PCM as it arrives (not a virtual: funasr::VadModel's table is untouched): the device scores `pcm16`
-  // (pfhip_vad_forward_sil_s16, bit for bit the scores of Infer); `waves` are the same waves.size() samples / 32768, which only the
-  // detector's decibel track reads on the host.
+  // The same on 16-bit PCM as it arrives (not a virtual: funasr::VadModel's table is untouched): the device scores the n samples
+  // of `pcm16` (pfhip_vad_forward_sil_energy_s16, bit for bit the scores and energies of Infer on pcm16 / 32768) and no float copy
+  // exists.  The form with `waves` is kept for callers that have one: only its size is read.
+  std::vector<std::vector<int>> InferPcm16(const int16_t* pcm16, int n, bool input_finished = true);
   std::vector<std::vector<int>> InferPcm16(const int16_t* pcm16, std::vector<float>& waves, bool input_finished = true);
+  // One COMPLETE file (input_finished = true) with the call's own configuration instead of SetConfig's: nothing of the object is
+  // written, so decoder threads may call it at once — their files are then scored in company (pfhip_set_vad_batching, switched on
+  // by InitVad unless PFHIP_VAD_MERGE=0).  Exactly one of f32 / pcm16 is given.
+  std::vector<std::vector<int>> InferFile(const float* f32, const int16_t* pcm16, int n, int vad_tail_sil, int vad_max_len);
   int GetVadSampleRate() override { return 16000; }
   void SetConfig(int vad_tail_sil, int vad_max_len) override { vad_silence_duration_ = vad_tail_sil; vad_max_len_ = vad_max_len; }
   void Reset();
@@ -57,9 +63,8 @@ class FsmnVadHip : public VadModelHipBase {
   float vad_speech_noise_thres_ = 0.9f;
 
  private:
-  std::vector<std::vector<int>> InferAny(const int16_t* pcm16, std::vector<float>& waves, bool input_finished);
+  std::vector<std::vector<int>> InferAny(const float* f32, const int16_t* pcm16, int n, bool input_finished, int tail_sil, int max_len);
   pfhip_vad* handle_ = nullptr;
-  std::mutex mu_;                        // the offline object keeps per-file caches: one file at a time
   int device_ = 0;
 };
 

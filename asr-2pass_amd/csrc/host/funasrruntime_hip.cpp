@@ -20,8 +20,7 @@ namespace {
 
 struct OfflineStreamHip {
   funasr::ParaformerHip asr;
-  std::unique_ptr<funasr::FsmnVadHip> vad;
-  std::mutex vad_mu;            // FsmnVad keeps per-file caches: one file at a time, like the reference's per-call Reset
+  std::unique_ptr<funasr::FsmnVadHip> vad;      // complete files only (InferFile): no per-file state, no lock
   std::unique_ptr<funasr::PuncModelHipBase> punc;      // OfflineStream::punc_handle (offline-stream.cpp:105-129)
 };
 
@@ -48,19 +47,15 @@ constexpr int kSegSample = 16;      // samples per ms at 16 kHz (audio.cpp: seg_
 
 // Audio::CutSplit (audio.cpp:1172-1240): the FSMN-VAD scores the whole buffer in one pass (it is causal: the reference's
 // 1-s slices carry the same cache state), the end-point detector runs on the host, segments come back in ms.
-// pcm16 (may be null): the same samples as 16-bit PCM; the device then scores those and `pcm` only feeds the decibel track.
-bool CutSplit(OfflineStreamHip* os, std::vector<float>& pcm, const int16_t* pcm16, int vad_tail_sil, int vad_max_len,
+// The n samples come as floats (pcm) or as 16-bit PCM (pcm16), never both: the detector's decibel track is computed on the device
+// from whichever was sent there, so 16-bit input is not converted on the host.  Nothing is shared between calls — the configuration
+// travels with the call, the detector is the call's own, every file is scored against fresh caches — so the decoder threads run
+// this at once and the VAD handle scores their files in company.
+bool CutSplit(OfflineStreamHip* os, const float* pcm, const int16_t* pcm16, int n, int vad_tail_sil, int vad_max_len,
               std::vector<std::pair<int, int>>& frames, std::vector<int>& index_vector) {
   frames.clear();
   index_vector.clear();
-  const int n = (int)pcm.size();
-  std::vector<std::vector<int>> segs;
-  {
-    std::lock_guard<std::mutex> lk(os->vad_mu);
-    os->vad->Reset();
-    os->vad->SetConfig(vad_tail_sil, vad_max_len);
-    segs = pcm16 ? os->vad->InferPcm16(pcm16, pcm, true) : os->vad->Infer(pcm, true);
-  }
+  const std::vector<std::vector<int>> segs = os->vad->InferFile(pcm16 ? nullptr : pcm, pcm16, n, vad_tail_sil, vad_max_len);
   for (const std::vector<int>& sg : segs) frames.emplace_back(sg[0] * kSegSample, std::min(sg[1] * kSegSample, n));
   index_vector.resize(frames.size());
   std::iota(index_vector.begin(), index_vector.end(), 0);
@@ -191,12 +186,12 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   // Audio::LoadPcmwav (audio.cpp:787-819); from here on samples, segments and stamps are at the model's rate (GetTimeLen
   // divides by dest_sample_rate, audio.cpp:254-257).
   // The acoustic model (and the VAD network) take the caller's 16-bit samples as they are:
-  //   * at the model's rate, every segment is a range of the caller's buffer (ParaformerHip::ForwardPcm16); the host float copy is
-  //     made only for the end-point detector's decibel track, i.e. only with a VAD;
+  //   * at the model's rate, every segment is a range of the caller's buffer (ParaformerHip::ForwardPcm16) and no float copy of the
+  //     file is made, with or without a VAD: the end-point detector's decibel track comes back from the device as frame energies;
   //   * at another rate WITHOUT a VAD the one segment is the whole buffer: it goes to the device as s16 and is resampled there
   //     (pfhip_offline_forward_rate_s16), no float copy at all;
-  //   * at another rate WITH a VAD the segments are ranges of the RESAMPLED waveform, which the detector needs on the host anyway:
-  //     that path stays on floats (LoadPcm).
+  //   * at another rate WITH a VAD the segments are ranges of the RESAMPLED waveform, which is on the host as floats (LoadPcm):
+  //     that path stays on floats, and its VAD takes the energy form as well.
   // N-best candidates have no s16 form in the C ABI: with FunOfflineSetNbest the float path is kept as well.
   const int model_rate = os->asr.GetAsrSampleRate();
   const int n_in = n_len / 2;
@@ -213,7 +208,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
       return nullptr;
     }
     n = (int)n_rs;
-  } else if (use16 && !os->vad) {
+  } else if (use16) {
     n = n_in;
   } else {
     if (!LoadPcm(os->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
@@ -228,7 +223,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   std::vector<int> index_vector = {0};
   res->segs.assign(1, {0, n});
   if (os->vad) {
-    if (!CutSplit(os, pcm, pcm16, vad_tail_sil, vad_max_len, res->segs, index_vector)) {
+    if (!CutSplit(os, pcm.data(), pcm16, n, vad_tail_sil, vad_max_len, res->segs, index_vector)) {
       std::fprintf(stderr, "FunOfflineInferBuffer: %s\n", pfhip_last_error());
       return res.release();
     }

@@ -52,12 +52,24 @@ int VadSegmenter::StartLatencyFrames() const {        // LatencyFrmNumAtStartPoi
 // ComputeDecibel (:433-449): 10*log10(sum x^2 + 1e-6) over 25-ms frames at 10-ms shift
 void VadSegmenter::AppendDecibel(const float* w, int n) {
   const int flen = frame_length_ms_ * sample_rate_ / 1000, fshift = frame_in_ms_ * sample_rate_ / 1000;
-  if (buf_all_ == 0) { buf_all_ = n; buf_size_ = n; } else { buf_all_ += n; }
+  AccountSamples(n);
   for (int off = 0; off + flen - 1 < n; off += fshift) {
     float s = 0.0f;
     for (int i = 0; i < flen; ++i) s += w[off + i] * w[off + i];
-    db_.push_back((float)(10 * std::log10(s + 0.000001)));
+    db_.push_back(Decibel(s));
   }
+}
+
+// the same track from the sums themselves (computed on the device, bit for bit the loop above): only the logarithm is left here
+void VadSegmenter::AppendEnergy(const float* e, int n_energy, int n_samples) {
+  AccountSamples(n_samples);
+  for (int f = 0; f < n_energy; ++f) db_.push_back(Decibel(e[f]));
+}
+
+int VadSegmenter::EnergyFrames(int n_samples, int sample_rate) const {
+  const int flen = frame_length_ms_ * sample_rate / 1000, fshift = frame_in_ms_ * sample_rate / 1000;
+  if (flen < 1 || fshift < 1) return -1;
+  return n_samples < flen ? 0 : 1 + (n_samples - flen) / fshift;
 }
 
 // GetFrameState (:591-640)
@@ -200,11 +212,28 @@ void VadSegmenter::Step(Frame f, int idx, bool last) {
 std::vector<VadSegment> VadSegmenter::Feed(const float* sil_prob, int T, const float* waveform, int n_samples,
                                            bool is_final, bool online, int max_end_sil, int max_single_segment_time,
                                            float speech_noise_thres, int sample_rate) {
+  SetOptions(max_end_sil, max_single_segment_time, speech_noise_thres, sample_rate);
+  AppendDecibel(waveform, n_samples);
+  return Detect(sil_prob, T, is_final, online);
+}
+
+std::vector<VadSegment> VadSegmenter::FeedEnergy(const float* sil_prob, int T, const float* energy, int n_energy, int n_samples,
+                                                 bool is_final, bool online, int max_end_sil, int max_single_segment_time,
+                                                 float speech_noise_thres, int sample_rate) {
+  SetOptions(max_end_sil, max_single_segment_time, speech_noise_thres, sample_rate);
+  AppendEnergy(energy, n_energy, n_samples);
+  return Detect(sil_prob, T, is_final, online);
+}
+
+void VadSegmenter::SetOptions(int max_end_sil, int max_single_segment_time, float speech_noise_thres, int sample_rate) {
   max_end_sil_thresh_ = max_end_sil - speech_to_sil_time_thres_;
   max_single_segment_time_ = max_single_segment_time;
   speech_noise_thres_ = speech_noise_thres;
   sample_rate_ = sample_rate;
-  AppendDecibel(waveform, n_samples);
+}
+
+// what follows the decibel track in E2EVadModel::operator() (:303-362)
+std::vector<VadSegment> VadSegmenter::Detect(const float* sil_prob, int T, bool is_final, bool online) {
   nn_eval_block_size_ = T;                                   // ComputeScores (:451-455)
   frm_cnt_ += T;
   sil_.assign(sil_prob, sil_prob + T);

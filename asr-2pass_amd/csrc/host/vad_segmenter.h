@@ -5,6 +5,7 @@
 // the network is the silence posterior (class 0, e2e-vad.h:103,607-609), so the device hands over [T] floats
 // instead of the [T, 248] score matrix.
 #pragma once
+#include <cmath>
 #include <vector>
 
 namespace pfhip_host {
@@ -19,6 +20,14 @@ class VadSegmenter {
   std::vector<VadSegment> Feed(const float* sil_prob, int T, const float* waveform, int n_samples, bool is_final,
                                bool online, int max_end_sil = 800, int max_single_segment_time = 15000,
                                float speech_noise_thres = 0.8f, int sample_rate = 16000);
+  // The same call with the frame energies sum x^2 of the n_samples new samples (n_energy = EnergyFrames(n_samples, sample_rate)
+  // values, e.g. from pfhip_vad_forward_sil_energy) in place of the samples: the decibel track is (float)(10 * log10(e + 1e-6)) as
+  // in ComputeDecibel, the sample accounting runs on n_samples.  Same segments as Feed on the waveform.
+  std::vector<VadSegment> FeedEnergy(const float* sil_prob, int T, const float* energy, int n_energy, int n_samples, bool is_final,
+                                     bool online, int max_end_sil = 800, int max_single_segment_time = 15000,
+                                     float speech_noise_thres = 0.8f, int sample_rate = 16000);
+  // frames of the decibel track in n_samples new samples at sample_rate (25-ms windows, 10-ms shift); -1 for a rate without one
+  int EnergyFrames(int n_samples, int sample_rate) const;
   void ResetAll();
 
  private:
@@ -55,6 +64,11 @@ class VadSegmenter {
   void ResetDetection();
   int StartLatencyFrames() const;
   void AppendDecibel(const float* w, int n);
+  void AppendEnergy(const float* e, int n_energy, int n_samples);
+  void AccountSamples(int n) { if (buf_all_ == 0) { buf_all_ = n; buf_size_ = n; } else { buf_all_ += n; } }
+  static float Decibel(float s) { return (float)(10 * std::log10(s + 0.000001)); }
+  void SetOptions(int max_end_sil, int max_single_segment_time, float speech_noise_thres, int sample_rate);
+  std::vector<VadSegment> Detect(const float* sil_prob, int T, bool is_final, bool online);
   Frame Classify(int t);
   void Step(Frame f, int idx, bool last);
   void DropUntil(int frame);

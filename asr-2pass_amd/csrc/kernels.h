@@ -46,8 +46,8 @@ void launch_fbank_frames(const int16_t* pcm, const int64_t* sample_off, const in
 // the same for B utterances back to back in `pcm` (frame_off has B + 1 entries); frames land back to back in fb_out
 void launch_fbank_frames_batch(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
                                int total_frames, FbankTables tb, float* fb_out, hipStream_t s);
-// (no caller today: both streaming families convert to f32 while the host copies the samples into its staging buffer, so no test
-// reaches this overload; it is the launcher a staging buffer of shorts would use)
+// the s16 form serves the packed offline VAD pass (pfhip_vad_forward_sil_batch_s16, vad.cpp), whose staging buffer holds the files'
+// shorts as they arrived; both streaming families convert to f32 while the host copies the samples into their staging buffers
 void launch_fbank_frames_batch(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
                                int total_frames, FbankTables tb, float* fb_out, hipStream_t s);
 
@@ -345,6 +345,20 @@ void launch_fsmn_causal20(const float* p, int ldp, const float* w, const VadSeg*
 void launch_lfr_cmvn_online_batch(const VadLfrOp* ops, int n_ops, int max_rows, int m, int n, int n_mels, const float* mean,
                                   const float* istd, float* out, int ldo, hipStream_t s);
 void launch_softmax_rows(const float* x, int ldx, int M, int N, float* y, float* col0, hipStream_t s);
+// The offline LfrCmvn (fsmn-vad.cpp:198-238) for B files whose fbank frames lie back to back in fb (frame_off[b], nframes[b]): every
+// file is padded at its own edges, its T_b = ceil(nframes[b] / n) rows go to rows row_off[b].. of out; max_T = the largest T_b.  Row
+// for row what launch_lfr_cmvn writes for the file alone.
+void launch_lfr_cmvn_packed(const float* fb, const int* frame_off, const int* nframes, const int* row_off, int B, int max_T, int m, int n,
+                            int n_mels, const float* mean, const float* istd, float* out, int ldo, hipStream_t s);
+// Frame energies of the end-point detector's decibel track (vad_energy.hip): B utterances packed in pcm as for
+// launch_fbank_frames_batch (sample_off int64, frame_off [B + 1], nframes [B], device arrays; nframes[b] = n < flen ? 0 :
+// 1 + (n - flen) / fshift); e[frame_off[b] + f] = sum_{i < flen} x[f * fshift + i]^2 in one fp32 accumulator, i ascending, products
+// rounded before they are added: bit for bit VadSegmenter::AppendDecibel's sum.  s16: x = (float)s * (1 / 32768), exact; an utterance
+// may start at an odd sample.  false (nothing launched) when 63 * fshift + flen samples do not fit 64 KB of LDS.
+bool launch_frame_energy(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B, int total_frames,
+                         int flen, int fshift, float* e, hipStream_t s);
+bool launch_frame_energy(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B, int total_frames,
+                         int flen, int fshift, float* e, hipStream_t s);
 
 // ---- resampling ahead of the front end (resample.hip; plan: resample.cpp) ----------------------
 // The device image of one rate pair's polyphase plan (Kaldi LinearResample, onnxruntime/src/resample.cpp:104-153):

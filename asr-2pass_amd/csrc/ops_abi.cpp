@@ -312,6 +312,18 @@ int pfhip_op_softmax_rows(const float* x, int ldx, int M, int N, float* y, float
   pfhip::launch_softmax_rows(x, ldx, M, N, y, col0, S(stream));
   return done();
 }
+int pfhip_op_frame_energy(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B, int total_frames,
+                          int flen, int fshift, float* e, void* stream) {
+  if (B < 0 || total_frames < 0 || !sample_off || !frame_off || !nframes || (total_frames && (!pcm || !e))) return (int)hipErrorInvalidValue;
+  if (!pfhip::launch_frame_energy(pcm, sample_off, frame_off, nframes, B, total_frames, flen, fshift, e, S(stream))) return (int)hipErrorInvalidValue;
+  return done();
+}
+int pfhip_op_frame_energy_s16(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                              int total_frames, int flen, int fshift, float* e, void* stream) {
+  if (B < 0 || total_frames < 0 || !sample_off || !frame_off || !nframes || (total_frames && (!pcm || !e))) return (int)hipErrorInvalidValue;
+  if (!pfhip::launch_frame_energy(pcm, sample_off, frame_off, nframes, B, total_frames, flen, fshift, e, S(stream))) return (int)hipErrorInvalidValue;
+  return done();
+}
 int pfhip_op_im2col3(const float* h, int ldh, float* col, int ldc, const int* row_pos, const int* row_len, int M, int D, void* stream) {
   if (M < 0 || D <= 0 || D % 4 || ldh % 4 || ldc % 4 || ldh < D || ldc < 3 * D || !h || !col || !row_pos || !row_len) return (int)hipErrorInvalidValue;
   pfhip::launch_im2col3(h, ldh, col, ldc, row_pos, row_len, M, D, S(stream));

@@ -35,6 +35,13 @@ struct pfhip_vad {
   pfhip_detail::MergeQueue<struct VadReq> mq;
   int q_wait_us = 0, q_max = 1;
   std::atomic<int> live_streams{0};
+  // the offline forward in company (pfhip_vad_forward_sil_batch, pfhip_set_vad_batching): frame energies, the zero block that stands
+  // for a fresh file's caches, whether non-final calls have left state in cache[] since the last reset, the callers' queue
+  Buf eng, zcache;
+  std::atomic<bool> carried{false};
+  pfhip_detail::MergeQueue<struct VadFileReq> fq;
+  int fq_wait_us = 0, fq_max = 1;                 // guarded by fq.mu
+  long long fq_passes = 0, fq_files = 0; int fq_max_seen = 0;      // guarded by mu: packed passes, their files, the fullest pass
   float* h_wave(size_t n) {
     if (n > h_wave_cap) {
       if (h_wave_buf) (void)hipHostFree(h_wave_buf);
@@ -144,7 +151,7 @@ void pfhip_vad_destroy(pfhip_vad* v) {
   if (!v) return;
   (void)hipSetDevice(v->device);
   (void)hipDeviceSynchronize();
-  for (Buf* b : {&v->pcm, &v->fb, &v->feats, &v->a, &v->b, &v->p, &v->f, &v->probs, &v->meta, &v->cache[0], &v->cache[1], &v->segs, &v->fbk, &v->ops, &v->sil}) b->release();
+  for (Buf* b : {&v->pcm, &v->fb, &v->feats, &v->a, &v->b, &v->p, &v->f, &v->probs, &v->meta, &v->cache[0], &v->cache[1], &v->segs, &v->fbk, &v->ops, &v->sil, &v->eng, &v->zcache}) b->release();
   auto fl = [](Lin& l) { free_lin(l); };
   fl(v->in1); fl(v->in2); fl(v->out1); fl(v->out2);
   for (auto& l : v->blk_linear) fl(l);
@@ -166,6 +173,7 @@ pfhip_status pfhip_vad_reset(pfhip_vad* v) {
   HIP_TRY(hipSetDevice(v->device));
   for (int i = 0; i < 2; ++i) HIP_TRY(hipMemsetAsync(v->cache[i].p, 0, (size_t)v->layers * 19 * v->proj * 4, v->stream));
   HIP_TRY(hipStreamSynchronize(v->stream));
+  v->carried = false;
   return PFHIP_OK;
 }
 
@@ -201,7 +209,8 @@ static pfhip_status vad_workspace(pfhip_vad* v, int T) {
 }
 
 static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, int is_final, float* probs,
-                                     size_t cap_floats, int* n_frames, bool sil_only);
+                                     size_t cap_floats, int* n_frames, bool sil_only, float* energy = nullptr, size_t cap_energy = 0,
+                                     int* n_energy = nullptr);
 
 pfhip_status pfhip_vad_forward(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* probs,
                                size_t cap_floats, int* n_frames) {
@@ -219,8 +228,11 @@ pfhip_status pfhip_vad_forward_sil_s16(pfhip_vad* v, const int16_t* pcm, int n_s
   return vad_forward_impl(v, PcmView{pcm, true}, n_samples, is_final, sil_prob, cap_floats, n_frames, true);
 }
 
+// n_energy != nullptr: the call also returns the frame energies of its samples (one per fbank frame), computed from the PCM the
+// fbank kernel has just read; the launches that produce the scores are the same with and without.
 static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, int is_final, float* probs,
-                                     size_t cap_floats, int* n_frames, bool sil_only) {
+                                     size_t cap_floats, int* n_frames, bool sil_only, float* energy, size_t cap_energy,
+                                     int* n_energy) {
   last_error().clear();
   if (!v || n_samples < 0 || (n_samples > 0 && !pcm.p) || !n_frames) return fail(PFHIP_ERR_ARG, "bad argument");
   std::lock_guard<std::mutex> lk(v->mu);
@@ -229,8 +241,11 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, i
   const int F = n_samples < 400 ? 0 : 1 + (n_samples - 400) / 160;
   const int T = (F + v->lfr_n - 1) / v->lfr_n;               // fsmn-vad.cpp:202
   *n_frames = T;
+  if (n_energy) *n_energy = F;
   if (T == 0) return PFHIP_OK;                                // fsmn-vad.cpp:245-247
   if ((size_t)T * (sil_only ? 1 : v->n_out) > cap_floats && probs) return fail(PFHIP_ERR_CAPACITY, "probs buffer too small");
+  if (n_energy && energy && (size_t)F > cap_energy) return fail(PFHIP_ERR_CAPACITY, "energy buffer too small (n_energy holds the count)");
+  if (n_energy) HIP_TRY(v->eng.ensure((size_t)F * 4));
   const int Tp = round_up(T, 128);
   HIP_TRY(v->pcm.ensure((size_t)n_samples * pcm.sample_bytes()));      // the one workspace, in floats or in shorts
   HIP_TRY(v->fb.ensure((size_t)F * 80 * 4));
@@ -266,7 +281,15 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, i
     HIP_TRY(hipMemcpyAsync(v->segs.p, hs, sizeof(pfhip::VadSeg), hipMemcpyHostToDevice, s));
     vad_network(v, s, T, static_cast<const pfhip::VadSeg*>(v->segs.p), 1, T);
   }
-  if (!is_final) v->cache_cur ^= 1;                             // fsmn-vad.cpp:129-134: caches kept only if not final
+  if (!is_final) { v->cache_cur ^= 1; v->carried = true; }      // fsmn-vad.cpp:129-134: caches kept only if not final
+  if (n_energy) {
+    const int64_t* so = reinterpret_cast<int64_t*>(v->meta.p);
+    const bool ok = pcm.s16 ? pfhip::launch_frame_energy(static_cast<const int16_t*>(v->pcm.p), so, v->meta.i() + 2, v->meta.i() + 4, 1, F,
+                                                         400, 160, v->eng.f(), s)
+                            : pfhip::launch_frame_energy(v->pcm.f(), so, v->meta.i() + 2, v->meta.i() + 4, 1, F, 400, 160, v->eng.f(), s);
+    if (!ok) return fail(PFHIP_ERR_UNSUPPORTED, "frame energy launch refused");
+    if (energy) HIP_TRY(hipMemcpyAsync(energy, v->eng.p, (size_t)F * 4, hipMemcpyDeviceToHost, s));
+  }
   if (probs && !sil_only) HIP_TRY(hipMemcpyAsync(probs, v->probs.p, (size_t)T * v->n_out * 4, hipMemcpyDeviceToHost, s));
   if (probs && sil_only)        // column 0 of the [T, n_out] score matrix
     HIP_TRY(hipMemcpyAsync(probs, v->sil.p, (size_t)T * 4, hipMemcpyDeviceToHost, s));
@@ -275,6 +298,217 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, i
   return PFHIP_OK;
 }
 
+
+}  // extern "C"
+
+// ---- complete files in company ----------------------------------------------------------------------------------------------
+// One caller's file of a packed pass.  Every file is scored as an is_final call on a fresh object: zeroed caches in, nothing
+// carried out (fsmn-vad.cpp:129-134), so the handle's own caches are neither read nor written.
+struct VadFileReq : pfhip_detail::MergeReqBase {
+  pfhip_detail::PcmView pcm; int n;
+  float* sil; size_t cap; int* nf; float* energy; size_t cap_e; int* ne;
+  pfhip_status st = PFHIP_OK; std::string err;
+};
+
+namespace {
+
+// All files of one sample format.  Status per file (a file whose buffers are too small gets its counts and nothing else, the
+// others are served); a failure of the shared pass fails every file.  Returns the first non-OK status.
+pfhip_status vad_forward_files(pfhip_vad* v, const std::vector<VadFileReq*>& files) {
+  last_error().clear();
+  const int B = (int)files.size();
+  const bool s16 = B > 0 && files[0]->pcm.s16;
+  const size_t sb = s16 ? 2 : 4;
+  auto fail_all = [&](pfhip_status st) {
+    for (VadFileReq* r : files) { r->st = st; r->err = last_error(); }
+    return st;
+  };
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (hipSetDevice(v->device) != hipSuccess) return fail_all(fail(PFHIP_ERR_HIP, "hipSetDevice failed"));
+  hipStream_t s = v->stream;
+  // ---- plan: the files that have frames (and room for their results) take samples, frames and rows, back to back ----------------
+  struct Plan { VadFileReq* r; int F, T; size_t so; int fo, ro; };
+  std::vector<Plan> plan;
+  size_t n_samp = 0;
+  int n_fr = 0, n_row = 0, max_T = 0;
+  pfhip_status first = PFHIP_OK;
+  std::string first_err;
+  for (VadFileReq* r : files) {
+    const int F = r->n < 400 ? 0 : 1 + (r->n - 400) / 160;
+    const int T = (F + v->lfr_n - 1) / v->lfr_n;
+    *r->nf = T; *r->ne = F;
+    r->st = PFHIP_OK; r->err.clear();
+    if (T == 0) continue;
+    if ((r->sil && (size_t)T > r->cap) || (r->energy && (size_t)F > r->cap_e)) {
+      r->st = fail(PFHIP_ERR_CAPACITY, "sil_prob or energy buffer too small (n_frames / n_energy hold the counts)");
+      r->err = last_error();
+      if (!first) { first = r->st; first_err = r->err; }
+      continue;
+    }
+    plan.push_back(Plan{r, F, T, n_samp, n_fr, n_row});
+    n_samp += (size_t)r->n; n_fr += F; n_row += T; max_T = std::max(max_T, T);
+  }
+  const int U = (int)plan.size();
+  if (U > 0) {
+    auto run = [&]() -> pfhip_status {
+      const size_t cache_bytes = (size_t)v->layers * 19 * v->proj * 4;
+      if (!v->zcache.p) {
+        HIP_TRY(v->zcache.ensure(cache_bytes));
+        HIP_TRY(hipMemsetAsync(v->zcache.p, 0, cache_bytes, s));
+      }
+      HIP_TRY(v->pcm.ensure(n_samp * sb + 16));
+      HIP_TRY(v->fbk.ensure((size_t)n_fr * 80 * 4));
+      HIP_TRY(v->eng.ensure((size_t)n_fr * 4));
+      pfhip_status ws = vad_workspace(v, n_row);
+      if (ws) return ws;
+      // control block: sample_off [U] int64 | frame_off [U + 1] | nframes [U] | row_off [U] | VadSeg [U]; then the results
+      const size_t o_fo = (size_t)U * 8, o_nf = o_fo + (size_t)(U + 1) * 4, o_ro = o_nf + (size_t)U * 4;
+      const size_t o_seg = (o_ro + (size_t)U * 4 + 15) & ~(size_t)15;
+      const size_t ctl = (o_seg + (size_t)U * sizeof(pfhip::VadSeg) + 63) & ~(size_t)63;
+      float* hp_f = v->h_wave(ctl / 4 + (size_t)n_row + (size_t)n_fr + 16);
+      if (!hp_f) return fail(PFHIP_ERR_HIP, "pinned staging allocation failed");
+      char* hp = reinterpret_cast<char*>(hp_f);
+      float* h_sil = reinterpret_cast<float*>(hp + ctl);
+      float* h_eng = h_sil + n_row;
+      HIP_TRY(v->ops.ensure(ctl));
+      char* dp = static_cast<char*>(v->ops.p);
+      int64_t* h_so = reinterpret_cast<int64_t*>(hp);
+      int* h_fo = reinterpret_cast<int*>(hp + o_fo);
+      int* h_nf = reinterpret_cast<int*>(hp + o_nf);
+      int* h_ro = reinterpret_cast<int*>(hp + o_ro);
+      pfhip::VadSeg* h_seg = reinterpret_cast<pfhip::VadSeg*>(hp + o_seg);
+      for (int u = 0; u < U; ++u) {
+        const Plan& pl = plan[u];
+        h_so[u] = (int64_t)pl.so; h_fo[u] = pl.fo; h_nf[u] = pl.F; h_ro[u] = pl.ro;
+        h_seg[u] = pfhip::VadSeg{v->zcache.f(), nullptr, pl.ro, pl.T};
+        // the caller's samples go to the device as they are: no host copy, no conversion
+        HIP_TRY(hipMemcpyAsync(static_cast<char*>(v->pcm.p) + pl.so * sb, pl.r->pcm.p, (size_t)pl.r->n * sb, hipMemcpyHostToDevice, s));
+      }
+      h_fo[U] = n_fr;
+      HIP_TRY(hipMemcpyAsync(dp, hp, ctl, hipMemcpyHostToDevice, s));
+      const int64_t* d_so = reinterpret_cast<const int64_t*>(dp);
+      const int *d_fo = reinterpret_cast<const int*>(dp + o_fo), *d_nf = reinterpret_cast<const int*>(dp + o_nf),
+                *d_ro = reinterpret_cast<const int*>(dp + o_ro);
+      pfhip::FbankTables tb{v->ft.d_window, v->ft.d_tw, v->ft.d_mel_off, v->ft.d_mel_size, v->ft.d_mel_w, v->d_mean, v->d_istd};
+      bool ok;
+      if (s16) {
+        const int16_t* d_pcm = static_cast<const int16_t*>(v->pcm.p);
+        pfhip::launch_fbank_frames_batch(d_pcm, d_so, d_fo, d_nf, U, n_fr, tb, v->fbk.f(), s);
+        ok = pfhip::launch_frame_energy(d_pcm, d_so, d_fo, d_nf, U, n_fr, 400, 160, v->eng.f(), s);
+      } else {
+        pfhip::launch_fbank_frames_batch(v->pcm.f(), d_so, d_fo, d_nf, U, n_fr, tb, v->fbk.f(), s);
+        ok = pfhip::launch_frame_energy(v->pcm.f(), d_so, d_fo, d_nf, U, n_fr, 400, 160, v->eng.f(), s);
+      }
+      if (!ok) return fail(PFHIP_ERR_UNSUPPORTED, "frame energy launch refused");
+      pfhip::launch_lfr_cmvn_packed(v->fbk.f(), d_fo, d_nf, d_ro, U, max_T, v->lfr_m, v->lfr_n, v->n_mels, v->d_mean, v->d_istd,
+                                    v->feats.f(), v->in1.Kp, s);
+      vad_network(v, s, n_row, reinterpret_cast<const pfhip::VadSeg*>(dp + o_seg), U, max_T);
+      HIP_TRY(hipMemcpyAsync(h_sil, v->sil.p, (size_t)n_row * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_eng, v->eng.p, (size_t)n_fr * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(hipGetLastError());
+      for (const Plan& pl : plan) {
+        if (pl.r->sil) std::memcpy(pl.r->sil, h_sil + pl.ro, (size_t)pl.T * 4);
+        if (pl.r->energy) std::memcpy(pl.r->energy, h_eng + pl.fo, (size_t)pl.F * 4);
+      }
+      return PFHIP_OK;
+    };
+    const pfhip_status st = run();
+    if (st) return fail_all(st);
+    ++v->fq_passes; v->fq_files += U; v->fq_max_seen = std::max(v->fq_max_seen, U);
+  }
+  if (first) last_error() = first_err;
+  return first;
+}
+
+template <typename Sample>
+pfhip_status vad_forward_sil_batch_of(pfhip_vad* v, const Sample* const* pcm, const int* n_samples, int n_files, float* const* sil_prob,
+                                      const size_t* cap_floats, int* n_frames, float* const* energy, const size_t* cap_energy,
+                                      int* n_energy) {
+  last_error().clear();
+  if (!v || n_files <= 0 || !pcm || !n_samples || !sil_prob || !cap_floats || !n_frames || !energy || !cap_energy || !n_energy)
+    return fail(PFHIP_ERR_ARG, "bad argument");
+  std::vector<VadFileReq> reqs((size_t)n_files);
+  std::vector<VadFileReq*> ptrs((size_t)n_files);
+  for (int i = 0; i < n_files; ++i) {
+    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    VadFileReq& r = reqs[i];
+    r.pcm = PcmView{pcm[i], sizeof(Sample) == 2}; r.n = n_samples[i];
+    r.sil = sil_prob[i]; r.cap = cap_floats[i]; r.nf = &n_frames[i];
+    r.energy = energy[i]; r.cap_e = cap_energy[i]; r.ne = &n_energy[i];
+    ptrs[i] = &r;
+  }
+  return vad_forward_files(v, ptrs);
+}
+
+// pfhip_vad_forward_sil_energy[_s16]: a final call on a handle without carried caches IS a fresh file, so with
+// pfhip_set_vad_batching on it joins the callers' queue and is scored in company; every other call runs alone as ever.
+pfhip_status vad_forward_sil_energy_one(pfhip_vad* v, PcmView pcm, int n_samples, int is_final, float* sil_prob, size_t cap_floats,
+                                        int* n_frames, float* energy, size_t cap_energy, int* n_energy) {
+  if (!v || !n_frames || !n_energy || n_samples < 0 || (n_samples > 0 && !pcm.p)) { last_error().clear(); return fail(PFHIP_ERR_ARG, "bad argument"); }
+  int wait_us, cap;
+  { std::lock_guard<std::mutex> ql(v->fq.mu); wait_us = v->fq_wait_us; cap = v->fq_max; }
+  if (!(is_final && wait_us > 0 && cap > 1 && !v->carried.load()))
+    return vad_forward_impl(v, pcm, n_samples, is_final, sil_prob, cap_floats, n_frames, true, energy, cap_energy, n_energy);
+  VadFileReq me;
+  me.pcm = pcm; me.n = n_samples; me.sil = sil_prob; me.cap = cap_floats; me.nf = n_frames;
+  me.energy = energy; me.cap_e = cap_energy; me.ne = n_energy;
+  v->fq.submit(
+      me, wait_us, [&](const std::deque<VadFileReq*>& q) { return (int)q.size() >= cap; },
+      [&](std::deque<VadFileReq*>& q, std::vector<VadFileReq*>& take) {      // one sample format per pass: the leader's
+        const bool s16 = q.front()->pcm.s16;
+        std::deque<VadFileReq*> later;
+        while (!q.empty()) {
+          VadFileReq* r = q.front();
+          q.pop_front();
+          if ((int)take.size() < cap && r->pcm.s16 == s16) take.push_back(r); else later.push_back(r);
+        }
+        q.swap(later);
+      },
+      [&](std::vector<VadFileReq*>& take) { (void)vad_forward_files(v, take); }, /*fresh_no_wait=*/true);
+  last_error() = me.err;
+  return me.st;
+}
+
+}  // namespace
+
+extern "C" {
+
+pfhip_status pfhip_vad_forward_sil_energy(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* sil_prob,
+                                          size_t cap_floats, int* n_frames, float* energy, size_t cap_energy, int* n_energy) {
+  return vad_forward_sil_energy_one(v, PcmView{pcm, false}, n_samples, is_final, sil_prob, cap_floats, n_frames, energy, cap_energy, n_energy);
+}
+pfhip_status pfhip_vad_forward_sil_energy_s16(pfhip_vad* v, const int16_t* pcm, int n_samples, int is_final, float* sil_prob,
+                                              size_t cap_floats, int* n_frames, float* energy, size_t cap_energy, int* n_energy) {
+  return vad_forward_sil_energy_one(v, PcmView{pcm, true}, n_samples, is_final, sil_prob, cap_floats, n_frames, energy, cap_energy, n_energy);
+}
+pfhip_status pfhip_vad_forward_sil_batch(pfhip_vad* v, const float* const* pcm, const int* n_samples, int n_files, float* const* sil_prob,
+                                         const size_t* cap_floats, int* n_frames, float* const* energy, const size_t* cap_energy,
+                                         int* n_energy) {
+  return vad_forward_sil_batch_of(v, pcm, n_samples, n_files, sil_prob, cap_floats, n_frames, energy, cap_energy, n_energy);
+}
+pfhip_status pfhip_vad_forward_sil_batch_s16(pfhip_vad* v, const int16_t* const* pcm, const int* n_samples, int n_files,
+                                             float* const* sil_prob, const size_t* cap_floats, int* n_frames, float* const* energy,
+                                             const size_t* cap_energy, int* n_energy) {
+  return vad_forward_sil_batch_of(v, pcm, n_samples, n_files, sil_prob, cap_floats, n_frames, energy, cap_energy, n_energy);
+}
+pfhip_status pfhip_set_vad_batching(pfhip_vad* v, int wait_us, int max_files) {
+  last_error().clear();
+  if (!v || wait_us < 0 || max_files < 1) return fail(PFHIP_ERR_ARG, "bad argument");
+  std::lock_guard<std::mutex> ql(v->fq.mu);
+  v->fq_wait_us = wait_us;
+  v->fq_max = max_files;
+  return PFHIP_OK;
+}
+pfhip_status pfhip_vad_batch_stats(pfhip_vad* v, long long* passes, long long* files, int* max_files) {
+  last_error().clear();
+  if (!v) return fail(PFHIP_ERR_ARG, "null handle");
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (passes) *passes = v->fq_passes;
+  if (files) *files = v->fq_files;
+  if (max_files) *max_files = v->fq_max_seen;
+  return PFHIP_OK;
+}
 
 // ---- FsmnVadOnline (onnxruntime/src/fsmn-vad-online.cpp): one object per connection -----------------------------------
 // The online feature front end keeps three caches between calls: input_cache_ (samples after the last frame shift,

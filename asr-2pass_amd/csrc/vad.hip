@@ -128,6 +128,38 @@ void launch_lfr_cmvn_online(const float* fb, int F, int T, int m, int n, int n_m
   hipLaunchKernelGGL(lfr_cmvn_kernel, dim3(T), dim3(128), 0, s, fb, F, T, m, n, n_mels, mean, istd, out, ldo, 0);
 }
 
+// LfrCmvn of several files packed back to back: every file is padded at its OWN edges (fsmn-vad.cpp:198-238), row i of file b is
+// row row_off[b] + i of out.  blockIdx.y = file, blockIdx.x = row of the file.
+__global__ __launch_bounds__(128) void lfr_cmvn_packed_kernel(const float* __restrict__ fb, const int* __restrict__ frame_off,
+                                                              const int* __restrict__ nframes, const int* __restrict__ row_off, int m,
+                                                              int n, int n_mels, const float* __restrict__ mean,
+                                                              const float* __restrict__ istd, float* __restrict__ out, int ldo) {
+  const int b = blockIdx.y;
+  const int F = nframes[b];
+  const int T = (F + n - 1) / n;
+  const int i = blockIdx.x;
+  if (i >= T) return;
+  const float* f0 = fb + (size_t)frame_off[b] * n_mels;
+  const int D = m * n_mels, lp = (m - 1) / 2;
+  for (int c = threadIdx.x; c < ldo; c += blockDim.x) {
+    float v = 0.f;
+    if (c < D) {
+      const int j = c / n_mels, bin = c - j * n_mels;
+      int f = i * n + j - lp;
+      f = f < 0 ? 0 : (f > F - 1 ? F - 1 : f);
+      v = (f0[(size_t)f * n_mels + bin] + mean[c]) * istd[c];
+    }
+    out[(size_t)(row_off[b] + i) * ldo + c] = v;
+  }
+}
+
+void launch_lfr_cmvn_packed(const float* fb, const int* frame_off, const int* nframes, const int* row_off, int B, int max_T, int m, int n,
+                            int n_mels, const float* mean, const float* istd, float* out, int ldo, hipStream_t s) {
+  if (B <= 0 || max_T <= 0) return;
+  hipLaunchKernelGGL(lfr_cmvn_packed_kernel, dim3(max_T, B), dim3(128), 0, s, fb, frame_off, nframes, row_off, m, n, n_mels, mean, istd,
+                     out, ldo);
+}
+
 void launch_fsmn_causal20(const float* p, int ldp, const float* w, const VadSeg* segs, int B, int max_T, int layer, float* out,
                           int ldo, int C, hipStream_t s) {
   if (B <= 0 || max_T <= 0) return;

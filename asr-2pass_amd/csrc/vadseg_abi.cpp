@@ -22,6 +22,15 @@ pfhip_status pfhip_vadseg_reset(pfhip_vadseg* s) {
   s->seg.ResetAll();
   return PFHIP_OK;
 }
+namespace {
+pfhip_status put_segments(const std::vector<pfhip_host::VadSegment>& segs, int32_t* segments, int cap_pairs, int* n_segments) {
+  *n_segments = (int)segs.size();
+  if ((int)segs.size() > cap_pairs) return pfhip_detail::fail(PFHIP_ERR_CAPACITY, "segment buffer too small");
+  for (size_t i = 0; i < segs.size(); ++i) { segments[2 * i] = segs[i].start_ms; segments[2 * i + 1] = segs[i].end_ms; }
+  return PFHIP_OK;
+}
+}  // namespace
+
 pfhip_status pfhip_vadseg_feed(pfhip_vadseg* s, const float* sil_prob, int n_frames, const float* waveform, int n_samples,
                                int is_final, int online, int max_end_sil, int max_single_segment_time,
                                float speech_noise_thres, int sample_rate, int32_t* segments, int cap_pairs,
@@ -31,12 +40,23 @@ pfhip_status pfhip_vadseg_feed(pfhip_vadseg* s, const float* sil_prob, int n_fra
   // every scored frame needs its 25-ms energy window (e2e-vad.h:433-449 / :593)
   const int have = n_samples >= 400 ? (n_samples - 400) / 160 + 1 : 0;
   if (have < n_frames) return pfhip_detail::fail(PFHIP_ERR_ARG, "waveform shorter than the scored frames");
-  const auto segs = s->seg.Feed(sil_prob, n_frames, waveform, n_samples, is_final != 0, online != 0, max_end_sil,
-                                max_single_segment_time, speech_noise_thres, sample_rate);
-  *n_segments = (int)segs.size();
-  if ((int)segs.size() > cap_pairs) return pfhip_detail::fail(PFHIP_ERR_CAPACITY, "segment buffer too small");
-  for (size_t i = 0; i < segs.size(); ++i) { segments[2 * i] = segs[i].start_ms; segments[2 * i + 1] = segs[i].end_ms; }
-  return PFHIP_OK;
+  return put_segments(s->seg.Feed(sil_prob, n_frames, waveform, n_samples, is_final != 0, online != 0, max_end_sil,
+                                  max_single_segment_time, speech_noise_thres, sample_rate),
+                      segments, cap_pairs, n_segments);
+}
+
+pfhip_status pfhip_vadseg_feed_energy(pfhip_vadseg* s, const float* sil_prob, int n_frames, const float* energy, int n_energy,
+                                      int n_samples, int is_final, int online, int max_end_sil, int max_single_segment_time,
+                                      float speech_noise_thres, int sample_rate, int32_t* segments, int cap_pairs,
+                                      int* n_segments) {
+  if (!s || n_frames < 0 || n_samples < 0 || n_energy < 0 || (n_frames && !sil_prob) || (n_energy && !energy) || !n_segments)
+    return pfhip_detail::fail(PFHIP_ERR_ARG, "bad argument");
+  if (n_energy != s->seg.EnergyFrames(n_samples, sample_rate))
+    return pfhip_detail::fail(PFHIP_ERR_ARG, "n_energy is not the frame count of n_samples at this sample rate");
+  if (n_energy < n_frames) return pfhip_detail::fail(PFHIP_ERR_ARG, "fewer energies than scored frames");
+  return put_segments(s->seg.FeedEnergy(sil_prob, n_frames, energy, n_energy, n_samples, is_final != 0, online != 0, max_end_sil,
+                                        max_single_segment_time, speech_noise_thres, sample_rate),
+                      segments, cap_pairs, n_segments);
 }
 
 pfhip_status pfhip_timestamp_onnx(float* us_alphas, const float* us_cif_peak, int n_frames3, int n_chars, float begin_time_ms,

@@ -513,3 +513,26 @@ def lstm_cell(G, c, h, lens, t, sel):
     lib = _lib()
     lib.pfhip_op_lstm_cell.argtypes = [_vp, _vp, _vp, _vp, _ci, _vp, _ci, _ci, _vp]
     _ck(lib.pfhip_op_lstm_cell(_p(G), _p(c), _p(h), _p(lens), int(t), _p(sel), H, D, _stream()), "lstm_cell")
+
+
+def frame_energy(pcm, sample_off, n_samples, flen=400, fshift=160):
+    """Frame energies sum x^2 (25-ms windows at a 10-ms shift by default) of the utterances packed in `pcm`, a float32 or int16 device
+    tensor (int16 means s / 32768): utterance b is n_samples[b] samples from sample_off[b] (host int sequences).  Returns
+    (e, frame_off): e float32 [total frames] on the device, utterance b's frames at e[frame_off[b]:frame_off[b + 1]]."""
+    lib = _lib()
+    lib.pfhip_op_frame_energy.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
+    lib.pfhip_op_frame_energy_s16.argtypes = lib.pfhip_op_frame_energy.argtypes
+    nf = [0 if n < flen else 1 + (n - flen) // fshift for n in n_samples]
+    fo = [0]
+    for f in nf:
+        fo.append(fo[-1] + f)
+    dev = pcm.device
+    d_so = torch.tensor(list(sample_off), dtype=torch.int64, device=dev)
+    d_fo = torch.tensor(fo, dtype=torch.int32, device=dev)
+    d_nf = torch.tensor(nf, dtype=torch.int32, device=dev)
+    e = torch.empty(max(fo[-1], 1), dtype=torch.float32, device=dev)
+    if pcm.dtype not in (torch.float32, torch.int16):
+        raise PfhipError("frame_energy takes float32 or int16 samples")
+    fn = lib.pfhip_op_frame_energy_s16 if pcm.dtype == torch.int16 else lib.pfhip_op_frame_energy
+    _ck(fn(_p(pcm), _p(d_so), _p(d_fo), _p(d_nf), len(nf), fo[-1], int(flen), int(fshift), _p(e), _stream()), "frame_energy")
+    return e[:fo[-1]], fo

@@ -8,7 +8,8 @@
 
 MI355X-first differences (results identical, see tests/test_gpu_pipeline.py): the FSMN-VAD network scores the WHOLE
 file in one pass instead of 600 one-second Runs per 10 minutes (it is causal, the caches would carry the same state),
-only the silence posterior column leaves the GPU, and batches are packed (no padding rows) so `max_acc` bounds memory,
+only the silence posterior column and the frame energies of the end-point detector's decibel track leave the GPU
+(int16 audio is never converted on the host), and batches are packed (no padding rows) so `max_acc` bounds memory,
 not wasted compute.  Host logic only; all arithmetic is in libpfhip.so.
 """
 from __future__ import annotations
@@ -37,14 +38,11 @@ def merge_online_segments(vad_segments: Sequence[Sequence[int]]) -> List[Tuple[i
 def cut_split(pcm: np.ndarray, vad, segmenter, vad_tail_sil=800, vad_max_len=60000, speech_noise_thres=0.9):
     """Returns (frames, index_vector): frames = [(start_sample, end_sample)] in time order, index_vector = their
     order by increasing length (audio.cpp:1226-1239), i.e. the order they are queued for FetchDynamic."""
-    sil = vad.ForwardSil(pcm, is_final=True)          # np.int16 audio goes to the device as it is
-    if sil.size == 0:
+    sil, energy = vad.ForwardSilEnergy(pcm, is_final=True)      # np.int16 audio goes to the device as it is and stays there:
+    if sil.size == 0:                                           # the detector's decibel track comes back as frame energies
         return [], []
     n_used = 400 + 160 * (sil.size - 1)
-    wave = pcm[:max(n_used, 0)]
-    if np.asarray(wave).dtype == np.int16:            # the end-point detector's decibel track reads floats
-        wave = np.asarray(wave).astype(np.float32) / np.float32(32768.0)
-    segs = segmenter(sil, wave, True, False, vad_tail_sil, vad_max_len, speech_noise_thres)
+    segs = segmenter.feed_energy(sil, energy[:sil.size], n_used, True, False, vad_tail_sil, vad_max_len, speech_noise_thres)
     frames = [(s * SEG_SAMPLE, min(e * SEG_SAMPLE, len(pcm))) for s, e in segs]
     index_vector = sorted(range(len(frames)), key=lambda i: (frames[i][1] - frames[i][0], i))     # stable like std::sort on ties? see note
     return frames, index_vector

@@ -386,6 +386,43 @@ pfhip_status pfhip_vad_forward_sil(pfhip_vad* v, const float* pcm, int n_samples
 pfhip_status pfhip_vad_forward_sil_s16(pfhip_vad* v, const int16_t* pcm, int n_samples, int is_final, float* sil_prob,
                                        size_t cap_floats, int* n_frames);
 
+/* ---- the decibel track on the device, files in company -----------------------------------------------------------------------
+ * The end-point detector reads, beside the silence posterior, the energy of every 25-ms frame (E2EVadModel::ComputeDecibel,
+ * e2e-vad.h:437-452).  pfhip_vad_forward_sil_energy[_s16] is pfhip_vad_forward_sil[_s16] that also returns those energies,
+ * computed on the device from the PCM the forward has copied there anyway: energy[f] = sum_{i < 400} x[160 f + i]^2 for the
+ * *n_energy = (n_samples < 400 ? 0 : 1 + (n_samples - 400) / 160) frames of THIS call's samples — one fp32 accumulator, i ascending,
+ * products rounded to fp32: bit for bit the host loop, for s16 input that of s / 32768.f.  Hand them to pfhip_vadseg_feed_energy,
+ * which takes the logarithm on the host (the device's log10 is not glibc's).  sil_prob, *n_frames, is_final and the caches are
+ * exactly those of pfhip_vad_forward_sil (same launches, bit-identical scores).  energy may be NULL (count only); cap_energy <
+ * *n_energy -> PFHIP_ERR_CAPACITY with *n_energy holding the count. */
+pfhip_status pfhip_vad_forward_sil_energy(pfhip_vad* v, const float* pcm, int n_samples, int is_final, float* sil_prob,
+                                          size_t cap_floats, int* n_frames, float* energy, size_t cap_energy, int* n_energy);
+pfhip_status pfhip_vad_forward_sil_energy_s16(pfhip_vad* v, const int16_t* pcm, int n_samples, int is_final, float* sil_prob,
+                                              size_t cap_floats, int* n_frames, float* energy, size_t cap_energy, int* n_energy);
+/* n_files COMPLETE files in one pass: every file is scored as an is_final = 1 call on a fresh object — zeroed caches in, nothing
+ * carried out (fsmn-vad.cpp:129-134) — so the handle's own carried caches are neither read nor written.  Arrays of the per-file
+ * arguments above.  The files' samples go to one device buffer as they are (no host copy, no conversion); one fbank launch, one
+ * LFR/CMVN that pads every file at its own edges, one network pass over the packed rows, one energy launch, one synchronise.  A file
+ * shorter than one window has n_frames = n_energy = 0.  Errors are per file where they can be: a file whose sil_prob or energy
+ * buffer is too small receives its counts and nothing else, the others are served, the call returns PFHIP_ERR_CAPACITY.
+ * Numerics: energies are exact (bitwise those of separate calls).  The silence posteriors are those of separate calls up to the
+ * GEMM dispatch: the GEMM kernel is picked from the row count, so a file's rows may run on another kernel in company than alone —
+ * as one file scored whole and in 1-s slices already may.  Both are within the VAD tolerance against the reference (2e-5). */
+pfhip_status pfhip_vad_forward_sil_batch(pfhip_vad* v, const float* const* pcm, const int* n_samples, int n_files, float* const* sil_prob,
+                                         const size_t* cap_floats, int* n_frames, float* const* energy, const size_t* cap_energy,
+                                         int* n_energy);
+pfhip_status pfhip_vad_forward_sil_batch_s16(pfhip_vad* v, const int16_t* const* pcm, const int* n_samples, int n_files,
+                                             float* const* sil_prob, const size_t* cap_floats, int* n_frames, float* const* energy,
+                                             const size_t* cap_energy, int* n_energy);
+/* Merge concurrent pfhip_vad_forward_sil_energy[_s16] callers (one decoder thread per file) into pfhip_vad_forward_sil_batch passes
+ * of up to max_files files: only calls with is_final = 1 on a handle that carries no state (no non-final call since create /
+ * pfhip_vad_reset) are merged, every other call runs alone as before.  A caller that finds the handle idle runs at once (a lone
+ * caller never waits); one that arrives while a pass runs leads the next pass and waits up to wait_us for company.  A pass holds
+ * ONE sample format, the leader's; callers of the other format form the next pass.  wait_us = 0 or max_files = 1: off (default).
+ * pfhip_vad_batch_stats: packed passes so far (merged or called directly), the files they scored, the most files in one pass. */
+pfhip_status pfhip_set_vad_batching(pfhip_vad* v, int wait_us, int max_files);
+pfhip_status pfhip_vad_batch_stats(pfhip_vad* v, long long* passes, long long* files, int* max_files);
+
 /* ---- online FSMN-VAD: one pfhip_vad_stream per connection = one `funasr::FsmnVadOnline` --------------------------------
  * (onnxruntime/src/fsmn-vad-online.cpp; built on the offline handle like FsmnVadOnline(FsmnVad*), :206-219).
  *   pfhip_vad_stream_infer <-> FsmnVadOnline::Infer up to the scorer (:135-147): ExtractFeats with input_cache_ /
@@ -439,6 +476,16 @@ pfhip_status pfhip_vadseg_feed(pfhip_vadseg* s, const float* sil_prob, int n_fra
                                int n_samples, int is_final, int online, int max_end_sil, int max_single_segment_time,
                                float speech_noise_thres, int sample_rate, int32_t* segments, int cap_pairs,
                                int* n_segments);
+
+/* The same call on frame energies instead of samples (pfhip_vad_forward_sil_energy, pfhip_op_frame_energy): energy[n_energy] are
+ * the sums of squares of the 25-ms frames of the n_samples new samples; the decibel track is (float)(10 * log10(e + 0.000001)) in
+ * double arithmetic, the expression of ComputeDecibel, and the sample accounting runs on n_samples — the segments are exactly those
+ * of pfhip_vadseg_feed on the waveform.  n_energy must be the frame count of n_samples at sample_rate (n < 25 ms ? 0 :
+ * 1 + (n - 25 ms) / 10 ms): anything else is PFHIP_ERR_ARG.  Online and offline modes. */
+pfhip_status pfhip_vadseg_feed_energy(pfhip_vadseg* s, const float* sil_prob, int n_frames, const float* energy, int n_energy,
+                                      int n_samples, int is_final, int online, int max_end_sil, int max_single_segment_time,
+                                      float speech_noise_thres, int sample_rate, int32_t* segments, int cap_pairs,
+                                      int* n_segments);
 
 /* ---- token time stamps (host logic) ------------------------------------------------------------------
  * `funasr::TimestampOnnx` (onnxruntime/src/util.cpp:838-963) restated on the host: us_alphas / us_cif_peak [3T] of the

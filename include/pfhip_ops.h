@@ -184,6 +184,15 @@ int pfhip_op_fsmn_causal20(const float* p, int ldp, const float* w, const int* r
                            void* stream);
 /* Softmax over columns [0, N) of every row; y [M][N] packed, col0 (may be NULL) [M] = y[:, 0]. */
 int pfhip_op_softmax_rows(const float* x, int ldx, int M, int N, float* y, float* col0, void* stream);
+/* Frame energies of the end-point detector's decibel track (E2EVadModel::ComputeDecibel, e2e-vad.h:437-452): B utterances packed in
+ * pcm; DEVICE arrays sample_off [B] (int64, in samples), frame_off [B + 1] (prefix sums of nframes) and nframes [B] with
+ * nframes[b] = n_b < flen ? 0 : 1 + (n_b - flen) / fshift.  e[frame_off[b] + f] = sum_{i < flen} x[f * fshift + i]^2, one fp32
+ * accumulator, i ascending, each product rounded to fp32 first: bit for bit the host loop.  s16: x = (float)s / 32768 (exact); an
+ * utterance may start at an odd sample.  hipErrorInvalidValue when 63 * fshift + flen samples exceed 64 KB of LDS. */
+int pfhip_op_frame_energy(const float* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B, int total_frames,
+                          int flen, int fshift, float* e, void* stream);
+int pfhip_op_frame_energy_s16(const int16_t* pcm, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                              int total_frames, int flen, int fshift, float* e, void* stream);
 /* The predictor's Conv1d k = 3 operand: col[row] = [h[row - 1] | h[row] | h[row + 1]], zeros where row_pos[row] -/+ 1 leaves
  * [0, row_len[row]) (device arrays: the local index and the utterance length of every packed row). */
 int pfhip_op_im2col3(const float* h, int ldh, float* col, int ldc, const int* row_pos, const int* row_len, int M, int D, void* stream);

@@ -38,6 +38,9 @@ import threading
 workers = int(sys.argv[3]) if len(sys.argv) > 3 else n_files
 MAXU = int(os.environ.get('MAXU', '96'))
 asr.set_batching(int(os.environ.get('WAIT_US', '3000')) if workers > 1 else 0, MAXU)
+ENERGY = os.environ.get("VAD_ENERGY", "1") != "0"      # 0: ForwardSil + the detector on the waveform, the flow before the energy form
+if ENERGY and workers > 1 and os.environ.get("PFHIP_VAD_MERGE", "1") != "0":
+    vad.set_batching(int(os.environ.get("PFHIP_VAD_FILE_WAIT_US", "2000")), 32)
 stats = dict(vad=0.0, seg=0.0, asr=0.0, nseg=0, ntok=0)
 lock = threading.Lock()
 nxt = [0]
@@ -50,9 +53,14 @@ def worker():
             return
         f = files[i]
         a = time.perf_counter()
-        sil = vad.ForwardSil(f, is_final=True)
-        b = time.perf_counter()
-        segs = seg_objs[threading.get_ident()](sil, f[:400 + 160 * (len(sil) - 1)], True, False, 800, 60000, 0.9)
+        if ENERGY:      # the decibel track comes back from the device: the host detector reads no sample
+            sil, eng = vad.ForwardSilEnergy(f, is_final=True)
+            b = time.perf_counter()
+            segs = seg_objs[threading.get_ident()].feed_energy(sil, eng[:len(sil)], 400 + 160 * (len(sil) - 1), True, False, 800, 60000, 0.9)
+        else:
+            sil = vad.ForwardSil(f, is_final=True)
+            b = time.perf_counter()
+            segs = seg_objs[threading.get_ident()](sil, f[:400 + 160 * (len(sil) - 1)], True, False, 800, 60000, 0.9)
         c = time.perf_counter()
         frames = [(s * 16, min(e * 16, len(f))) for s, e in segs]
         order = sorted(range(len(frames)), key=lambda k: (frames[k][1] - frames[k][0], k))
