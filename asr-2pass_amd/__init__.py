@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     # VAD: the decibel track on the device, files in company
     "pfhip_vad_forward_sil_energy", "pfhip_vad_forward_sil_energy_s16", "pfhip_vad_forward_sil_batch", "pfhip_vad_forward_sil_batch_s16",
     "pfhip_set_vad_batching", "pfhip_vad_batch_stats", "pfhip_vadseg_feed_energy",
+    # streaming: candidates, confidences and fire frames per token; the candidates call on 16-bit PCM
+    "pfhip_stream_set_detail", "pfhip_stream_last_detail", "pfhip_offline_forward_nbest_s16",
 ]
 
 
@@ -89,6 +91,11 @@ class _Out(ctypes.Structure):
 
 class _Nbest(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("ids", ctypes.POINTER(ctypes.c_int32)), ("logp", ctypes.POINTER(ctypes.c_float))]
+
+
+class _StreamDetail(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("ids", ctypes.POINTER(ctypes.c_int32)), ("logp", ctypes.POINTER(ctypes.c_float)),
+                ("fire_frame", ctypes.POINTER(ctypes.c_int32)), ("cap", ctypes.c_int32)]
 
 
 class _SlotStats(ctypes.Structure):
@@ -177,6 +184,10 @@ def load_lib() -> ctypes.CDLL:
                                                     ctypes.POINTER(ci), ctypes.POINTER(_Out), ctypes.POINTER(_Nbest)]
         lib.pfhip_set_nbest.argtypes = [vp, ci]
         lib.pfhip_offline_fetch_nbest.argtypes = [vp, ctypes.POINTER(_Nbest)]
+    if hasattr(lib, "pfhip_stream_set_detail"):
+        lib.pfhip_offline_forward_nbest_s16.argtypes = lib.pfhip_offline_forward_nbest.argtypes
+        lib.pfhip_stream_set_detail.argtypes = [vp, ci, ci]
+        lib.pfhip_stream_last_detail.argtypes = [vp, ctypes.POINTER(_StreamDetail), ctypes.POINTER(ci)]
     lib.pfhip_stream_create.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(vp)]
     lib.pfhip_stream_destroy.argtypes = [vp]
     lib.pfhip_stream_destroy.restype = None
@@ -235,7 +246,9 @@ def load_lib() -> ctypes.CDLL:
 
 def _check(lib, st):
     if st != 0:
-        raise PfhipError(f"pfhip status {st}: {lib.pfhip_last_error().decode()}")
+        e = PfhipError(f"pfhip status {st}: {lib.pfhip_last_error().decode()}")
+        e.status = int(st)
+        raise e
 
 
 def read_model_files(kind, model, second=None, hotword=None, cmvn=None, config=None):
@@ -465,19 +478,20 @@ class ParaformerHip:
         return [o[:got[b]] for b, o in enumerate(outs)]
 
     def forward_ids(self, din: Sequence[np.ndarray], want_logp=False, max_tokens=None, hw_emb=None, want_timestamps=False,
-                    sample_rate=None, hw_sets=None, set_of_utt=None, nbest=None, nbest_fill=0):
+                    sample_rate=None, hw_sets=None, set_of_utt=None, nbest=None, nbest_fill=0, nbest_s16=False):
         """Batched forward.  Returns dict(token_num, n_fires, n_frames, ids=list of int arrays,
         logp=list of [n_fires, V] arrays or None[, us_alphas, us_peaks = lists of [3*T_b] arrays]).
         hw_emb: one hotword set [H, d] for the whole batch.  hw_sets + set_of_utt: a list of sets ([H_k, d] each) and, per
         utterance, the index of the set it attends to (pfhip_offline_forward_hwsets); not together with hw_emb or sample_rate.
         sample_rate: the rate of din when it is not the model's (pfhip_offline_forward_rate resamples on the GPU first).
         nbest=k (1..8): also nbest_ids / nbest_logp [batch, max_tokens, k], the k best columns of every token row and their
-        log-probabilities (pfhip_offline_forward_nbest; rows >= n_fires keep nbest_fill); not together with sample_rate."""
+        log-probabilities (pfhip_offline_forward_nbest; rows >= n_fires keep nbest_fill); not together with sample_rate.
+        nbest_s16: np.int16 utterances go to pfhip_offline_forward_nbest_s16 as they are instead of being converted here."""
         B = len(din)
         if B == 0:
             raise PfhipError("empty batch")
-        # np.int16 utterances go to the *_s16 entry points as they are (the candidates call has no s16 form: floats there)
-        bufs, s16 = _pcm_buffers(din) if nbest is None else ([_pcm_f32(x) for x in din], False)
+        # np.int16 utterances go to the *_s16 entry points as they are (with nbest only where nbest_s16 asks for it: floats otherwise)
+        bufs, s16 = _pcm_buffers(din) if nbest is None or nbest_s16 else ([_pcm_f32(x) for x in din], False)
         sfx = "_s16" if s16 else ""
         lens = (ctypes.c_int * B)(*[int(b.shape[0]) for b in bufs])
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
@@ -523,8 +537,8 @@ class ParaformerHip:
             sptr = (ctypes.c_void_p * max(len(sets), 1))(*[h.ctypes.data if h.size else None for h in sets])
             sn = (ctypes.c_int * max(len(sets), 1))(*[int(h.shape[0]) for h in sets])
             sof = (ctypes.c_int * B)(*[int(j) for j in (set_of_utt if hw_sets is not None else [0] * B)])
-            _check(self._lib, self._lib.pfhip_offline_forward_nbest(self._h, ptrs, lens, B, sptr, sn, len(sets), sof, ctypes.byref(out),
-                                                                    ctypes.byref(nb)))
+            _check(self._lib, getattr(self._lib, "pfhip_offline_forward_nbest" + sfx)(self._h, ptrs, lens, B, sptr, sn, len(sets), sof,
+                                                                                      ctypes.byref(out), ctypes.byref(nb)))
         elif hw_sets is not None:
             if hw_emb is not None or sample_rate is not None or set_of_utt is None or len(set_of_utt) != B:
                 raise PfhipError("hw_sets needs set_of_utt [batch] and excludes hw_emb / sample_rate")
@@ -661,6 +675,9 @@ class ParaformerHip:
                 for i in range(PFHIP_NUM_KCLASS)}
 
 
+FIRE_ROW_MS = 60           # one LFR row: lfr_n (6) frame shifts of 10 ms
+
+
 class ParaformerOnlineHip:
     """Host-side mirror of `funasr::ParaformerOnline` (onnxruntime/src/paraformer-online.cpp): one object per
     connection, built from the (online) model handle like `ParaformerOnline(Model* offline_handle, chunk_size)`
@@ -691,6 +708,37 @@ class ParaformerOnlineHip:
 
     def set_debug(self, on=True):
         _check(self._lib, self._lib.pfhip_stream_set_debug(self._h, 1 if on else 0))
+
+    def set_detail(self, k=0, fires=False):
+        """pfhip_stream_set_detail: k = 0..8 candidates per token and, with fires, the row each token fired in, for the following
+        calls (an extension; 0 / False = off, the default: the calls then launch what they always launched)."""
+        _check(self._lib, self._lib.pfhip_stream_set_detail(self._h, int(k), 1 if fires else 0))
+        self._detail = (int(k), bool(fires))
+
+    def last_detail(self, k=None, fires=None, cap=256):
+        """The detail of the last Forward / forward_batch call of this stream (pfhip_stream_last_detail), parallel to the ids it
+        returned: dict(n, ids [n, k] int32, logp [n, k] float32 descending (exp(logp[:, 0]) = the token's confidence),
+        fire_frame [n] int32 or None, fire_ms = fire_frame * lfr_n * 10: the fired row's position to within the 25-ms analysis
+        window and the 60-ms row).  k / fires default to what set_detail asked for.  A PfhipError carries .status and, where the
+        library reported it, .n_tokens (the count a too small cap needed)."""
+        dk, df = getattr(self, "_detail", (0, False))
+        k = dk if k is None else int(k)
+        fires = df if fires is None else bool(fires)
+        ids = np.zeros((max(cap, 1), max(k, 1)), np.int32)
+        logp = np.zeros((max(cap, 1), max(k, 1)), np.float32)
+        ff = np.zeros(max(cap, 1), np.int32)
+        d = _StreamDetail(k, ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if k else None,
+                          logp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if k else None,
+                          ff.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if fires else None, int(cap))
+        n = ctypes.c_int(-1)
+        try:
+            _check(self._lib, self._lib.pfhip_stream_last_detail(self._h, ctypes.byref(d), ctypes.byref(n)))
+        except PfhipError as e:
+            e.n_tokens = n.value
+            raise
+        fire = ff[:n.value].copy() if fires else None
+        return dict(n=n.value, ids=ids[:n.value, :k].copy(), logp=logp[:n.value, :k].copy(), fire_frame=fire,
+                    fire_ms=None if fire is None else fire * FIRE_ROW_MS)
 
     def last_path(self):
         """Which branch of ParaformerOnline::Forward the last call took (pfhip_stream_last_path): 2 = the one whose non-empty

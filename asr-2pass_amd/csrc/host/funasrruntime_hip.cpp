@@ -30,7 +30,9 @@ struct RecogResult {               // funasr::FUNASR_RECOG_RESULT (com-define.h)
   std::vector<std::vector<int>> seg_ids;
   std::vector<std::pair<int, int>> segs;
   std::vector<int> online_ids;       // ids the streaming chunks of this call emitted (inspection)
-  std::vector<float> confidence;     // FunASRGetTokenConfidence (FunOfflineSetNbest)
+  std::vector<float> confidence;     // FunASRGetTokenConfidence (FunOfflineSetNbest / FunTpassSetNbest: the second-pass text)
+  std::vector<float> online_conf;    // FunASRGetOnlineConfidence, FunASRGetOnlineFireMs: parallel to online_ids (FunTpassSetNbest)
+  std::vector<int> online_fire_ms;
 };
 
 bool ReadAll(const std::string& path, std::vector<char>& out) {
@@ -192,11 +194,12 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   //     (pfhip_offline_forward_rate_s16), no float copy at all;
   //   * at another rate WITH a VAD the segments are ranges of the RESAMPLED waveform, which is on the host as floats (LoadPcm):
   //     that path stays on floats, and its VAD takes the energy form as well.
-  // N-best candidates have no s16 form in the C ABI: with FunOfflineSetNbest the float path is kept as well.
+  // FunOfflineSetNbest changes none of this: the candidates call takes 16-bit samples too (pfhip_offline_forward_nbest_s16).
   const int model_rate = os->asr.GetAsrSampleRate();
   const int n_in = n_len / 2;
   const bool same_rate = sampling_rate == model_rate;
-  const bool use16 = os->asr.GetNbest() == 0 && (same_rate || !os->vad);
+  // (candidates and device-side resampling exclude each other: that one combination stays on resampled floats)
+  const bool use16 = same_rate || (!os->vad && os->asr.GetNbest() == 0);
   std::vector<int16_t> store16;
   const int16_t* pcm16 = use16 ? Pcm16View(sz_buf, n_in, store16) : nullptr;
   std::vector<float> pcm;
@@ -305,6 +308,8 @@ const std::vector<std::pair<int, int>>& FunASRGetSegments(FUNASR_RESULT result) 
 const std::vector<int>& FunASRGetOnlineIds(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_ids; }
 void FunOfflineSetNbest(FUNASR_HANDLE handle, int k) { if (handle) static_cast<OfflineStreamHip*>(handle)->asr.SetNbest(k); }
 const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->confidence; }
+const std::vector<float>& FunASRGetOnlineConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_conf; }
+const std::vector<int>& FunASRGetOnlineFireMs(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_fire_ms; }
 pfhip_model* FunOfflineGetAsrHandle(FUNASR_HANDLE handle) { return handle ? static_cast<OfflineStreamHip*>(handle)->asr.Handle() : nullptr; }
 
 
@@ -313,6 +318,7 @@ namespace {
 
 struct TpassStreamHip {               // funasr::TpassStream (tpass-stream.cpp): the shared models
   funasr::ParaformerHip asr;          // ONE object holds the offline session and the online encoder / decoder (paraformer.cpp:134-154)
+  int detail_k = 0;                   // FunTpassSetNbest: for the streams of later FunTpassOnlineInit calls
   std::unique_ptr<funasr::FsmnVadHip> vad;
   std::unique_ptr<funasr::PuncModelHipBase> punc_online;      // TpassStream::punc_online_handle (tpass-stream.cpp:100-135)
 };
@@ -376,7 +382,15 @@ FUNASR_HANDLE FunTpassOnlineInit(FUNASR_HANDLE tpass_handle, std::vector<int> ch
     std::fprintf(stderr, "FunTpassOnlineInit: %s\n", pfhip_last_error());
     return nullptr;
   }
+  if (ts->detail_k > 0) os->asr_online->SetDetail(ts->detail_k, true);      // FunTpassSetNbest
   return os.release();
+}
+
+void FunTpassSetNbest(FUNASR_HANDLE tpass_handle, int k) {
+  TpassStreamHip* ts = static_cast<TpassStreamHip*>(tpass_handle);
+  if (!ts) return;
+  ts->asr.SetNbest(k);
+  ts->detail_k = ts->asr.GetNbest();
 }
 
 FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_handle, const char* sz_buf, int n_len,
@@ -418,6 +432,8 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
                                 ? os->asr_online->ForwardPcm16(frame.pcm16.data(), (int)frame.pcm16.size(), frame.is_final)
                                 : os->asr_online->Forward(frame.data.data(), (int)frame.data.size(), frame.is_final);      // :540
     res->online_ids.insert(res->online_ids.end(), os->asr_online->LastTokenIds().begin(), os->asr_online->LastTokenIds().end());
+    res->online_conf.insert(res->online_conf.end(), os->asr_online->LastTokenConfidence().begin(), os->asr_online->LastTokenConfidence().end());
+    for (int f : os->asr_online->LastFireFrames()) res->online_fire_ms.push_back(funasr::ParaformerOnlineHip::FireFrameMs(f));
     if (mode == ASR_ONLINE) {
       os->asr_online->online_res += msg;
       if (frame.is_final) {                                                         // funasrruntime.cpp:543-556
@@ -435,11 +451,13 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
     float* buff[1] = {frame.data.data()};
     int len[1] = {(int)frame.data.size()};
     const int16_t* buff16[1] = {frame.pcm16.data()};
-    const std::vector<std::string> msgs = frame.pcm16.size() == frame.data.size() && !frame.data.empty() && ts->asr.GetNbest() == 0
+    const std::vector<std::string> msgs = frame.pcm16.size() == frame.data.size() && !frame.data.empty()
                                               ? ts->asr.ForwardPcm16(buff16, len, true, hw_emb, nullptr, 1)
                                               : ts->asr.Forward(buff, len, true, hw_emb, nullptr, 1);
     std::string msg = msgs.empty() ? "" : msgs[0];
     if (msg.empty()) continue;
+    if (!ts->asr.LastTokenConfidence().empty())                                     // FunTpassSetNbest: as FunOfflineInferBuffer
+      res->confidence.insert(res->confidence.end(), ts->asr.LastTokenConfidence()[0].begin(), ts->asr.LastTokenConfidence()[0].end());
     const size_t bar = msg.find(" | ");
     if (bar != std::string::npos) {
       std::vector<float> v;

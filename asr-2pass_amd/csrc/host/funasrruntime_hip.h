@@ -103,6 +103,16 @@ const std::vector<int>& FunASRGetOnlineIds(FUNASR_RESULT result);
 // result was made without FunOfflineSetNbest.
 void FunOfflineSetNbest(FUNASR_HANDLE handle, int k);
 const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result);
+// The same for the 2-pass handle: FunTpassSetNbest(tpass_handle, k) applies SetNbest(k) to the second-pass model -- so that
+// FunASRGetTokenConfidence covers the tpass text of a FunTpassInferBuffer result as it covers the offline text -- and
+// ParaformerOnlineHip::SetDetail(k, true) to every stream made by a LATER FunTpassOnlineInit (0 = off, the default).
+// FunASRGetOnlineConfidence / FunASRGetOnlineFireMs are parallel to FunASRGetOnlineIds (one entry per id, nothing dropped):
+// exp(log-probability) of each streamed token and the time of the LFR row it fired in, in ms from the first sample the
+// connection's stream saw since its last final chunk (fire frame * 60: the row's position to within the 25-ms analysis window and
+// the 60-ms row).  Empty without FunTpassSetNbest.
+void FunTpassSetNbest(FUNASR_HANDLE tpass_handle, int k);
+const std::vector<float>& FunASRGetOnlineConfidence(FUNASR_RESULT result);
+const std::vector<int>& FunASRGetOnlineFireMs(FUNASR_RESULT result);
 // ... and the C-ABI handle of the offline acoustic model behind a FunOfflineInit handle (pfhip_inflight_stats in the harnesses)
 struct pfhip_model;
 pfhip_model* FunOfflineGetAsrHandle(FUNASR_HANDLE handle);

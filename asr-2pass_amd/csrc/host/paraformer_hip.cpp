@@ -250,16 +250,6 @@ std::vector<std::string> ParaformerHip::ForwardPcm16(const int16_t* const* din, 
     tl_last_conf.assign(n_res, {});
     return std::vector<std::string>(n_res);      // "" per item, as every failed Forward
   }
-  if (nbest_k_ && batch_in > 0 && din && len) {      // pfhip_offline_forward_nbest takes floats only
-    std::vector<std::vector<float>> f((size_t)batch_in);
-    std::vector<const void*> ptrs((size_t)batch_in);
-    for (int i = 0; i < batch_in; ++i) {
-      f[i].resize((size_t)(len[i] > 0 ? len[i] : 0));
-      for (size_t j = 0; j < f[i].size(); ++j) f[i][j] = (float)din[i][j] / 32768.f;
-      ptrs[i] = f[i].data();
-    }
-    return ForwardAny(ptrs.data(), false, len, input_finished, hw_emb, wfst_decoder, batch_in, 0);
-  }
   return ForwardAny(reinterpret_cast<const void* const*>(din), true, len, input_finished, hw_emb, wfst_decoder, batch_in, sample_rate);
 }
 
@@ -323,20 +313,21 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
     }
   }
   // SetNbest: the same forward plus the k best columns of every token row (this caller's one hotword set as set 0)
-  const int nk = s16 ? 0 : nbest_k_;              // (ForwardPcm16 converts and comes here as floats when candidates are on)
+  const int nk = nbest_k_;                        // (ForwardPcm16 refuses it together with another sample rate)
   std::vector<int32_t> nb_ids((size_t)(nk ? batch_in : 0) * max_tokens * nk);
   std::vector<float> nb_logp(nb_ids.size());
   pfhip_status st;
-  if (s16 && sample_rate) {
-    st = pfhip_offline_forward_rate_s16(handle_, din16, len, batch_in, sample_rate, n_hw ? hw.data() : nullptr, n_hw, &out);
-  } else if (s16) {
-    st = pfhip_offline_forward_s16(handle_, din16, len, batch_in, n_hw ? hw.data() : nullptr, n_hw, &out);
-  } else if (nk) {
+  if (nk) {
     const pfhip_nbest nb{nk, nb_ids.data(), nb_logp.data()};
     const float* sets[1] = {hw.data()};
     const int set_rows[1] = {n_hw};
     const std::vector<int> set_of_utt((size_t)batch_in, 0);
-    st = pfhip_offline_forward_nbest(handle_, din, len, batch_in, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(), &out, &nb);
+    st = s16 ? pfhip_offline_forward_nbest_s16(handle_, din16, len, batch_in, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(), &out, &nb)
+             : pfhip_offline_forward_nbest(handle_, din, len, batch_in, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(), &out, &nb);
+  } else if (s16 && sample_rate) {
+    st = pfhip_offline_forward_rate_s16(handle_, din16, len, batch_in, sample_rate, n_hw ? hw.data() : nullptr, n_hw, &out);
+  } else if (s16) {
+    st = pfhip_offline_forward_s16(handle_, din16, len, batch_in, n_hw ? hw.data() : nullptr, n_hw, &out);
   } else {
     st = pfhip_offline_forward(handle_, din, len, batch_in, n_hw ? hw.data() : nullptr, n_hw, &out);
   }
@@ -464,6 +455,16 @@ ParaformerOnlineHip::ParaformerOnlineHip(ParaformerHipBase* offline_handle, std:
   chunk_len = chunk_size[1] * 10 * 6 * (offline_handle_->GetAsrSampleRate() / 1000);
 }
 
+void ParaformerOnlineHip::SetDetail(int k, bool fires) {
+  if (!stream_) return;
+  if (pfhip_stream_set_detail(stream_, k, fires ? 1 : 0) != PFHIP_OK) {
+    std::fprintf(stderr, "ParaformerOnlineHip::SetDetail: %s\n", pfhip_last_error());
+    return;
+  }
+  detail_k_ = k;
+  detail_fires_ = fires;
+}
+
 ParaformerOnlineHip::~ParaformerOnlineHip() {
   if (stream_) pfhip_stream_destroy(stream_);
 }
@@ -483,6 +484,7 @@ std::string ParaformerOnlineHip::ForwardPcm16(const int16_t* din, int len, bool 
 
 std::string ParaformerOnlineHip::ForwardAny(const float* din, const int16_t* din16, int len, bool input_finished) {
   last_ids_.clear();
+  last_nbest_ids_.clear(); last_nbest_logp_.clear(); last_conf_.clear(); last_fire_frames_.clear();
   if (!stream_ || len < 0 || (len > 0 && !din && !din16)) return "";       // (an empty final frame flushes the look-back cache, :532-540)
   std::vector<int32_t> ids(256);
   int n_ids = 0;
@@ -500,6 +502,21 @@ std::string ParaformerOnlineHip::ForwardAny(const float* din, const int16_t* din
     return "";
   }
   last_ids_.assign(ids.begin(), ids.begin() + n_ids);
+  if ((detail_k_ || detail_fires_) && n_ids > 0) {           // SetDetail: what the same call kept beside its ids
+    std::vector<int32_t> cid((size_t)n_ids * detail_k_), fire(detail_fires_ ? (size_t)n_ids : 0);
+    std::vector<float> clp(cid.size());
+    const pfhip_stream_detail d{detail_k_, detail_k_ ? cid.data() : nullptr, detail_k_ ? clp.data() : nullptr,
+                                detail_fires_ ? fire.data() : nullptr, n_ids};
+    int n_det = 0;
+    if (pfhip_stream_last_detail(stream_, &d, &n_det) == PFHIP_OK && n_det == n_ids) {
+      last_nbest_ids_.assign(cid.begin(), cid.end());
+      last_nbest_logp_ = clp;
+      for (int j = 0; detail_k_ && j < n_ids; ++j) last_conf_.push_back(std::exp(clp[(size_t)j * detail_k_]));
+      last_fire_frames_.assign(fire.begin(), fire.end());
+    } else {
+      std::fprintf(stderr, "ParaformerOnlineHip::Forward: no detail: %s\n", pfhip_last_error());
+    }
+  }
   std::string result = offline_handle_->OnlineTokensToString(last_ids_);
   if (!result.empty() && pfhip_stream_last_path(stream_) == 2) result.push_back(' ');      // paraformer-online.cpp:585-587
   return result;

@@ -132,8 +132,8 @@ class ParaformerHip : public ParaformerHipBase
   // The same Forward on 16-bit PCM as the server receives it (the samples Audio::LoadPcmwav, audio.cpp:787-819, divides by 32768
   // on the host): the caller's buffers go to the device as they are (pfhip_offline_forward_s16 — half the bytes, no float copy) and
   // every result is bit for bit that of Forward on din[i][j] / 32768.f.  sample_rate != 0 and != GetAsrSampleRate(): the audio is
-  // at that rate and is resampled on the device first (pfhip_offline_forward_rate_s16, Audio::WavResample).  With SetNbest the
-  // candidates call has no s16 form: the samples are converted here and take the float path; SetNbest together with another
+  // at that rate and is resampled on the device first (pfhip_offline_forward_rate_s16, Audio::WavResample).  With SetNbest the bytes go
+  // to pfhip_offline_forward_nbest_s16 in the same way; SetNbest together with another
   // sample rate is refused ("" per item and a message, like a failed Forward: resample first with pfhip_resample).  Not a virtual: the
   // funasr::Model::Forward(float**) seam and its table are untouched.
   std::vector<std::string> ForwardPcm16(const int16_t* const* din, const int* len, bool input_finished,
@@ -252,6 +252,21 @@ class ParaformerOnlineHip : public ParaformerHipBase {
   int GetAsrSampleRate() override { return offline_handle_ ? offline_handle_->GetAsrSampleRate() : 16000; }
   bool ok() const { return stream_ != nullptr; }
   const std::vector<int>& LastTokenIds() const { return last_ids_; }
+  // Candidates, confidences and fire frames per token (an extension; OnlineGreedySearch keeps only the arg-max,
+  // paraformer.cpp:362-371, and the reference's streaming result carries no time).  SetDetail(k, fires), k = 0..8: every following
+  // Forward also keeps the k best columns of each token row and, with fires, the LFR row each token fired in
+  // (pfhip_stream_set_detail); (0, false), the default: Forward calls exactly what it calls without this.
+  void SetDetail(int k, bool fires);
+  // of the last Forward, parallel to LastTokenIds() (one entry per id, nothing dropped): candidates [tokens][k] row-major
+  // (candidate 0 = the id), exp(candidate 0's log-probability), and the fired row counted from the stream's first row since
+  // creation, Reset or its last final call.  Empty where SetDetail did not ask.
+  const std::vector<int>& LastNbestIds() const { return last_nbest_ids_; }
+  const std::vector<float>& LastNbestLogp() const { return last_nbest_logp_; }
+  const std::vector<float>& LastTokenConfidence() const { return last_conf_; }
+  const std::vector<int>& LastFireFrames() const { return last_fire_frames_; }
+  // fire frame -> milliseconds from the stream's first sample: fire_frame * lfr_n (6) * 10 ms, the row's position to within the
+  // 25-ms analysis window and the 60-ms row
+  static int FireFrameMs(int fire_frame) { return fire_frame * 6 * 10; }
   // 2pass (paraformer-online.h:131-133)
   std::string online_res;
   int chunk_len = 9600;
@@ -261,6 +276,10 @@ class ParaformerOnlineHip : public ParaformerHipBase {
   ParaformerHip* offline_handle_ = nullptr;
   pfhip_stream* stream_ = nullptr;
   std::vector<int> last_ids_;
+  int detail_k_ = 0;                       // SetDetail
+  bool detail_fires_ = false;
+  std::vector<int> last_nbest_ids_, last_fire_frames_;
+  std::vector<float> last_nbest_logp_, last_conf_;
 };
 
 }  // namespace funasr

@@ -1,8 +1,10 @@
 // Harness over the 2-pass handle API (funasrruntime_hip.h), one connection fed like the websocket server feeds it
 // (websocket/bin/websocket-server-2pass.cpp:135-148: 9600-sample pieces, the last one with input_finished):
-//   tpass_infer <offline_model_dir> <online_model_dir> <vad_dir> <pcm_s16_file> [step_samples=9600] [mode=2] [punc_dir|-] [audio_fs=16000]
+//   tpass_infer <offline_model_dir> <online_model_dir> <vad_dir> <pcm_s16_file> [step_samples=9600] [mode=2] [punc_dir|-] [audio_fs=16000] [nbest=0]
 //   (step_samples counts samples at audio_fs, as the reference server forwards each message with its audio_fs)
 // One line per call: "call <j> | online <text> | tpass <text> | stamp <stamp>".
+// nbest = 1..8 (FunTpassSetNbest, an extension) appends two fields to every line: " | online_detail <confidence>@<fire ms> ..." with one
+// entry per streamed token id of the call, and " | tpass_conf <confidence> ..." for the tokens of the second-pass text.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -12,7 +14,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    std::fprintf(stderr, "usage: %s offline_dir online_dir vad_dir pcm_s16_file [step] [mode] [punc_dir|-] [audio_fs]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s offline_dir online_dir vad_dir pcm_s16_file [step] [mode] [punc_dir|-] [audio_fs] [nbest]\n", argv[0]);
     return 2;
   }
   std::map<std::string, std::string> paths;
@@ -24,6 +26,8 @@ int main(int argc, char** argv) {
   std::ifstream f(argv[4], std::ios::binary);
   std::vector<char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
   FUNASR_HANDLE h = FunTpassInit(paths, 1);
+  const int nbest = argc > 9 ? std::atoi(argv[9]) : 0;
+  if (h && nbest > 0) FunTpassSetNbest(h, nbest);                  // before the connection's stream is made
   FUNASR_HANDLE oh = FunTpassOnlineInit(h, {5, 10, 5});
   if (!h || !oh) return 1;
   std::vector<std::vector<std::string>> punc_cache(2);
@@ -34,7 +38,16 @@ int main(int argc, char** argv) {
     const bool last = off + step_bytes >= n_bytes;
     FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, nb, punc_cache, last, audio_fs, "pcm", mode);
     if (!r) { std::fprintf(stderr, "inference failed\n"); return 1; }
-    std::printf("call %d | online %s | tpass %s | stamp %s\n", j, FunASRGetResult(r, 0), FunASRGetTpassResult(r, 0), FunASRGetStamp(r));
+    std::printf("call %d | online %s | tpass %s | stamp %s", j, FunASRGetResult(r, 0), FunASRGetTpassResult(r, 0), FunASRGetStamp(r));
+    if (nbest > 0) {
+      const std::vector<float>& conf = FunASRGetOnlineConfidence(r);
+      const std::vector<int>& ms = FunASRGetOnlineFireMs(r);
+      std::printf(" | online_detail");
+      for (size_t t = 0; t < conf.size() && t < ms.size(); ++t) std::printf(" %.9g@%d", conf[t], ms[t]);
+      std::printf(" | tpass_conf");
+      for (float c : FunASRGetTokenConfidence(r)) std::printf(" %.9g", c);
+    }
+    std::printf("\n");
     FunASRFreeResult(r);
   }
   FunTpassOnlineUninit(oh);

@@ -293,9 +293,11 @@ struct StreamSeg {
   int pad_;
 };
 // CifSearch (paraformer-online.cpp:270-345) for B connections at once; stream b's fires land in emb_all[b * emb_rows ..],
-// their count in n_fire[b] (counts above emb_rows are reported but not stored: the caller checks).
+// their count in n_fire[b] (counts above emb_rows are reported but not stored: the caller checks).  fire_step (may be null: the
+// kernel and launch as ever) [B * emb_rows]: the scan step in which stored token j of stream b fired, at [b * emb_rows + j]
+// (0 = the carry slot, 1..n = window rows 0..n-1, n + 1 = the tail slot); slots of tokens that did not fire are left alone.
 void launch_cif_stream(const float* enc, int lde, const float* alphas, const StreamSeg* segs, int B, float threshold, float tail,
-                       float* emb_all, int emb_rows, int* n_fire, int D, hipStream_t s);
+                       float* emb_all, int emb_rows, int* n_fire, int D, hipStream_t s, int* fire_step = nullptr);
 // Decoder FSMN with the 10-frame cache (paraformer-online.cpp:374, 500) for the packed tokens of B connections.
 void launch_fsmn_cached(const float* t2, const float* w, const float* res, float* out, const StreamSeg* segs, int B, int layer,
                         int C, hipStream_t s);

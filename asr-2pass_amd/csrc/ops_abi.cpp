@@ -254,9 +254,9 @@ int pfhip_op_logsoftmax_topk(const float* logits, int ldl, int M, int V, int k, 
 }
 
 // ---- the scan, cache and row kernels (tests only: the descriptor-taking ones upload their descriptors synchronously) ----------------
-int pfhip_op_cif_stream(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
+static int cif_stream_op(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
                         const int* pre, const int* suf, float* carry, long long carry_stride, int B, int D, float threshold,
-                        float tail, float* emb, int emb_rows, int* n_fire, void* stream) {
+                        float tail, float* emb, int emb_rows, int* n_fire, int* fire_step, void* stream) {
   if (B <= 0 || D <= 0 || D > 1024 || lde < D || emb_rows < 0 || carry_stride < D + 1 || !enc || !alphas || !row_off || !n || !is_last ||
       !pre || !suf || !carry || !emb || !n_fire)
     return (int)hipErrorInvalidValue;
@@ -270,8 +270,21 @@ int pfhip_op_cif_stream(const float* enc, int lde, const float* alphas, const in
     segs[b] = sg;
   }
   return with_device_segs(segs, S(stream), [&](const pfhip::StreamSeg* d) {
-    pfhip::launch_cif_stream(enc, lde, alphas, d, B, threshold, tail, emb, emb_rows, n_fire, D, S(stream));
+    pfhip::launch_cif_stream(enc, lde, alphas, d, B, threshold, tail, emb, emb_rows, n_fire, D, S(stream), fire_step);
   });
+}
+int pfhip_op_cif_stream(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
+                        const int* pre, const int* suf, float* carry, long long carry_stride, int B, int D, float threshold,
+                        float tail, float* emb, int emb_rows, int* n_fire, void* stream) {
+  return cif_stream_op(enc, lde, alphas, row_off, n, is_last, pre, suf, carry, carry_stride, B, D, threshold, tail, emb, emb_rows, n_fire,
+                       nullptr, stream);
+}
+int pfhip_op_cif_stream_fires(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
+                              const int* pre, const int* suf, float* carry, long long carry_stride, int B, int D, float threshold,
+                              float tail, float* emb, int emb_rows, int* n_fire, int* fire_step, void* stream) {
+  if (!fire_step) return (int)hipErrorInvalidValue;
+  return cif_stream_op(enc, lde, alphas, row_off, n, is_last, pre, suf, carry, carry_stride, B, D, threshold, tail, emb, emb_rows, n_fire,
+                       fire_step, stream);
 }
 int pfhip_op_fsmn_cached(const float* t2, const float* w, const float* res, float* out, const int* tok_off, const int* n_tok, float* dcache,
                          long long dcache_stride, int B, int layer, int C, void* stream) {

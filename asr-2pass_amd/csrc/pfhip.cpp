@@ -2074,15 +2074,25 @@ pfhip_status pfhip_offline_forward_hwsets_s16(pfhip_model* head, const int16_t* 
 
 // pfhip_offline_forward_hwsets plus the k best candidates of every token row (an extension: GreedySearch, paraformer.cpp:386-395,
 // keeps only the arg-max); nb == nullptr is pfhip_offline_forward_hwsets itself
-pfhip_status pfhip_offline_forward_nbest(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
-                                         const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
-                                         pfhip_out* out, const pfhip_nbest* nb) {
+static pfhip_status offline_forward_nbest(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch,
+                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                          pfhip_out* out, const pfhip_nbest* nb) {
   if (head && head->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
     g_err.clear();
     return fail(PFHIP_ERR_ARG, "bad argument");
   }
   const HwSets hw{hw_emb, n_hotwords, n_sets < 0 ? 0 : n_sets, set_of_utt};
   return offline_forward_sets(head, pcm, n_samples, batch, hw, out, nb);
+}
+pfhip_status pfhip_offline_forward_nbest(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
+                                         const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                         pfhip_out* out, const pfhip_nbest* nb) {
+  return offline_forward_nbest(head, pcm, n_samples, batch, hw_emb, n_hotwords, n_sets, set_of_utt, out, nb);
+}
+pfhip_status pfhip_offline_forward_nbest_s16(pfhip_model* head, const int16_t* const* pcm, const int* n_samples, int batch,
+                                             const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                             pfhip_out* out, const pfhip_nbest* nb) {
+  return offline_forward_nbest(head, pcm, n_samples, batch, hw_emb, n_hotwords, n_sets, set_of_utt, out, nb);
 }
 
 // device-pointer form: k candidates for the following pfhip_offline_enqueue calls of this handle (context 0); 0 = off

@@ -50,6 +50,21 @@ struct pfhip_stream {
   int last_n = 0, last_fires = 0, last_row_off = 0, last_tok_off = 0, last_slot = 0;
   bool last_has_logp = false;
   bool debug = false;
+  // pfhip_stream_set_detail: candidates per token (0 = off) and fire frames for this stream's following calls
+  int nbest_k = 0;
+  bool want_fires = false;
+  // which emitted LFR row (counted like start_idx, InitCache's zero rows negative) each row of feats_cache_ / of the window in
+  // `chunk` is a copy of: AddOverlapChunk's bookkeeping (:397-413) on indices
+  std::vector<int> featc_idx, win_idx;
+  // the detail of the last call (pfhip_stream_last_detail), on the host: [det_n, det_k] candidates, [det_n] fire frames
+  int det_n = 0, det_k = 0;
+  bool det_fires = false;
+  std::vector<int32_t> det_ids, det_fire;
+  std::vector<float> det_logp;
+  void clear_detail(int k, bool fires) {
+    det_n = 0; det_k = k; det_fires = fires;
+    det_ids.clear(); det_logp.clear(); det_fire.clear();
+  }
 };
 
 namespace {
@@ -78,6 +93,8 @@ pfhip_status init_cache(pfhip_stream* s, hipStream_t st) {
   s->is_first_chunk = true;
   s->is_last_chunk = false;
   s->n_featc = s->chunk_size[0] + s->chunk_size[2];
+  s->featc_idx.resize((size_t)s->n_featc);
+  for (int i = 0; i < s->n_featc; ++i) s->featc_idx[i] = i - s->n_featc;     // the zero rows: before row 0
   HIP_TRY(hipMemsetAsync(s->carry.p, 0, (size_t)(m->cfg.d_model + 4) * 4, st));
   HIP_TRY(hipMemsetAsync(s->featc.p, 0, (size_t)16 * m->feat_dim * 4, st));
   HIP_TRY(hipMemsetAsync(s->dcache.p, 0, (size_t)std::max(1, m->cfg.dec_layers) * 10 * m->cfg.d_model * 4, st));
@@ -208,9 +225,13 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   if (B == 0) return flush(m, rec, st);
   std::vector<pfhip::StreamSeg> segs(B);
   int M = 0;
+  int kmax = 0;                  // pfhip_stream_set_detail: the largest k of the batch (0: the arg-max head as ever) ...
+  bool any_fires = false;        // ... and whether any stream wants to know where its tokens fired (false: the CIF kernel as ever)
   for (int b = 0; b < B; ++b) {
     pfhip_stream* s = ss[b];
     const int n = s->win_n;
+    kmax = std::max(kmax, s->nbest_k);
+    any_fires = any_fires || s->want_fires;
     s->last_n = n; s->last_fires = 0; s->last_has_logp = false; s->last_row_off = M; s->last_tok_off = 0; s->last_slot = b;
     if (n <= 0 || n > 128) return fail(PFHIP_ERR_ARG, "stream window out of range");
     segs[b] = pfhip::StreamSeg{s->carry.f(), s->dcache.f(), M, n, s->is_last_chunk ? 1 : 0, s->chunk_size[0],
@@ -229,7 +250,9 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   HIP_TRY(m->enc.ensure((size_t)Mp * d * 4));
   HIP_TRY(m->alphas.ensure((size_t)Mp * 4));
   HIP_TRY(m->emb.ensure((size_t)B * kMaxTok * d * 4));
-  HIP_TRY(m->counts.ensure((size_t)2 * B * 4));
+  // with fire frames the B * kMaxTok steps follow the B counts, so that one copy brings both back
+  const size_t n_counts = any_fires ? (size_t)B * (1 + kMaxTok) : (size_t)B;
+  HIP_TRY(m->counts.ensure(std::max((size_t)2 * B, n_counts) * 4));
   // device metadata: off[B] len[B] tok_off[B] tok_len[B] row_pos[M] row_len[M] src_row[B*kMaxTok]; segs in their own buffer
   const size_t n_meta = 4 * (size_t)B + 2 * (size_t)M + (size_t)B * kMaxTok;
   HIP_TRY(m->dmeta.ensure(n_meta * 4));
@@ -238,7 +261,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     const size_t half = ((n_meta * 4 + 15) & ~(size_t)15) + (size_t)B * sizeof(pfhip::StreamSeg) + 64;
     pfhip_status ps = ensure_h_meta(m, 2 * half);
     if (ps) return ps;
-    ps = ensure_h_counts(m, (size_t)2 * B * 4);
+    ps = ensure_h_counts(m, std::max((size_t)2 * B, n_counts) * 4);
     if (ps) return ps;
   }
   int* hm = static_cast<int*>(m->h_meta);
@@ -375,8 +398,8 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
                       m->alphas.f(), M, d, st);
   // ---- CifSearch (:270-345), one block per connection ---------------------------------------------------
   pfhip::launch_cif_stream(m->enc.f(), d, m->alphas.f(), d_segs, B, c.cif_threshold, c.tail_threshold, m->emb.f(), kMaxTok,
-                           m->counts.i(), d, st);
-  HIP_TRY(hipMemcpyAsync(m->h_counts, m->counts.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+                           m->counts.i(), d, st, any_fires ? m->counts.i() + B : nullptr);
+  HIP_TRY(hipMemcpyAsync(m->h_counts, m->counts.p, n_counts * 4, hipMemcpyDeviceToHost, st));
   static const bool timing = pfhip::env_is1("PFHIP_STREAM_TIMING");
   const auto t_sync0 = std::chrono::steady_clock::now();
   HIP_TRY(hipStreamSynchronize(st));
@@ -398,6 +421,15 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     segs[b].tok_off = ML; segs[b].n_tok = N;
     ML += N;
     maxN = std::max(maxN, N);
+    if (ss[b]->want_fires) {       // step -> window row -> the emitted row it is a copy of (h_counts is overwritten by the next forward)
+      const std::vector<int>& wi = ss[b]->win_idx;
+      const int* steps = m->h_counts + B + (size_t)b * kMaxTok;
+      for (int k = 0; k < N; ++k) {
+        // 0 = the carry slot (the window's first row), 1..n = rows 0..n-1, n + 1 = the tail slot (the window's last row)
+        const int row = std::min(std::max(steps[k] - 1, 0), (int)wi.size() - 1);
+        ss[b]->det_fire.push_back(wi.empty() ? 0 : std::max(wi[(size_t)row], 0));
+      }
+    }
   }
   if (ML <= 0) { HIP_TRY(hipGetLastError()); return PFHIP_OK; }          // :472 decoder only if CIF fired
   const int MLp = round_up(ML, pfhip::kTileM);
@@ -410,7 +442,8 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   HIP_TRY(m->qd.ensure((size_t)MLp * d * 4));
   HIP_TRY(m->ctxd.ensure((size_t)MLp * d * 4));
   HIP_TRY(m->logits.ensure((size_t)MLp * m->vocab_pad * 4));
-  HIP_TRY(m->ids.ensure((size_t)MLp * 4));
+  // ids [ML], then with candidates their ids [ML, kmax] and values [ML, kmax]: one buffer, one copy back
+  HIP_TRY(m->ids.ensure((size_t)MLp * 4 * (1 + 2 * kmax)));
   if (want_logp) HIP_TRY(m->logp.ensure((size_t)MLp * c.vocab * 4));
   // second half of the pinned staging buffer (the first half may still be read by the copies above)
   {
@@ -500,21 +533,37 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     gemm(m, st, m->yd.f(), d, m->W("dec.out.w").d, c.vocab, d, d, m->logits.f(), m->vocab_pad, m->d_vocab_bias, nullptr, 0,
          nullptr, 0, ML, false);
   }
-  pfhip::launch_logsoftmax_argmax(m->logits.f(), m->vocab_pad, ML, c.vocab, want_logp ? m->logp.f() : nullptr,
-                                  static_cast<int32_t*>(m->ids.p), st);
-  std::vector<int32_t> ids(ML);
-  HIP_TRY(hipMemcpyAsync(ids.data(), m->ids.p, (size_t)ML * 4, hipMemcpyDeviceToHost, st));
+  int32_t* d_ids = static_cast<int32_t*>(m->ids.p);
+  if (kmax > 0) {      // the sibling head (topk.hip): candidate 0 and `ids` are the arg-max kernel's bit for bit
+    if (!pfhip::launch_logsoftmax_topk(m->logits.f(), m->vocab_pad, ML, c.vocab, kmax, want_logp ? m->logp.f() : nullptr, d_ids,
+                                       d_ids + ML, reinterpret_cast<float*>(d_ids + (size_t)ML * (1 + kmax)), st))
+      return fail(PFHIP_ERR_ARG, "stream nbest k outside 1..8 or larger than the vocabulary");
+  } else {
+    pfhip::launch_logsoftmax_argmax(m->logits.f(), m->vocab_pad, ML, c.vocab, want_logp ? m->logp.f() : nullptr, d_ids, st);
+  }
+  std::vector<int32_t> ids((size_t)ML * (1 + 2 * kmax));
+  HIP_TRY(hipMemcpyAsync(ids.data(), m->ids.p, ids.size() * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   for (int b = 0; b < B; ++b) {
     ss[b]->last_has_logp = want_logp;
     for (int k = 0; k < segs[b].n_tok; ++k) outs[b]->push_back(ids[segs[b].tok_off + k]);        // OnlineGreedySearch paraformer.cpp:362-371
+    const int ks = ss[b]->nbest_k;                                   // this stream's own first k of the batch's kmax
+    if (ks <= 0) continue;
+    const int32_t* cid = ids.data() + ML;
+    const float* cv = reinterpret_cast<const float*>(ids.data() + (size_t)ML * (1 + kmax));
+    for (int k = 0; k < segs[b].n_tok; ++k) {
+      const size_t row = (size_t)(segs[b].tok_off + k) * kmax;
+      ss[b]->det_ids.insert(ss[b]->det_ids.end(), cid + row, cid + row + ks);
+      ss[b]->det_logp.insert(ss[b]->det_logp.end(), cv + row, cv + row + ks);
+    }
   }
   return PFHIP_OK;
 }
 
 // window = feats_cache_ ++ rows[r0, r0+nr) (AddOverlapChunk :397-413); returns the window length in *n_out
-pfhip_status add_overlap_chunk(pfhip_stream* s, int r0, int nr, bool input_finished, Recorder& rec, int* n_out) {
+// idx0: which emitted row rows[r0] is (pfhip_stream::win_idx)
+pfhip_status add_overlap_chunk(pfhip_stream* s, int r0, int nr, int idx0, bool input_finished, Recorder& rec, int* n_out) {
   pfhip_model* m = s->m;
   const int FD = m->feat_dim, FP = m->feat_pad;
   const int nc = s->n_featc;
@@ -529,6 +578,9 @@ pfhip_status add_overlap_chunk(pfhip_stream* s, int r0, int nr, bool input_finis
     keep = s->chunk_size[0] + s->chunk_size[2];
   }
   if (keep > n) return fail(PFHIP_ERR_ARG, "stream window shorter than the look-back cache");
+  s->win_idx = s->featc_idx;
+  for (int i = 0; i < nr; ++i) s->win_idx.push_back(idx0 + i);
+  s->featc_idx.assign(s->win_idx.end() - keep, s->win_idx.end());
   // new feats_cache_ = last `keep` rows of the (unpadded) window; chunk has stride FP, featc FD
   rec.copy(Recorder::kFeatc, s->featc.f(), FD, s->chunk.f() + (size_t)(n - keep) * FP, FP, keep, FD);
   s->n_featc = keep;
@@ -537,6 +589,7 @@ pfhip_status add_overlap_chunk(pfhip_stream* s, int r0, int nr, bool input_finis
     if (total > n) {                                          // zero rows up to 20 (:402-408)
       rec.copy(Recorder::kZeroPad, s->chunk.f() + (size_t)n * FP, FP, nullptr, 0, total - n, 0);
       n = total;
+      s->win_idx.resize((size_t)n, s->win_idx.back());       // the zero rows lie past `suf`: no token fires there
     }
   }
   *n_out = n;
@@ -674,9 +727,41 @@ pfhip_status pfhip_stream_reset(pfhip_stream* s) {
   std::lock_guard<std::mutex> lk(s->m->mu);
   HIP_TRY(hipSetDevice(s->m->device));
   reset_cache(s);
+  s->clear_detail(0, false);
   pfhip_status st = init_cache(s, s->m->own_stream);
   if (st) return st;
   HIP_TRY(hipStreamSynchronize(s->m->own_stream));
+  return PFHIP_OK;
+}
+
+pfhip_status pfhip_stream_set_detail(pfhip_stream* s, int nbest_k, int fire_frames) {
+  last_error().clear();
+  if (!s) return fail(PFHIP_ERR_ARG, "null stream");
+  if (nbest_k < 0 || nbest_k > pfhip::kTopkMax || nbest_k > s->m->cfg.vocab)
+    return fail(PFHIP_ERR_ARG, "stream detail: k outside 0..8 (or above the vocabulary)");
+  std::lock_guard<std::mutex> lk(s->m->mu);
+  s->nbest_k = nbest_k;
+  s->want_fires = fire_frames != 0;
+  return PFHIP_OK;
+}
+
+pfhip_status pfhip_stream_last_detail(pfhip_stream* s, const pfhip_stream_detail* d, int* n_tokens) {
+  last_error().clear();
+  if (!s || !d || !n_tokens) return fail(PFHIP_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> lk(s->m->mu);
+  if (d->k < 0 || d->k > s->det_k) return fail(PFHIP_ERR_ARG, "stream detail: the last call computed fewer candidates than asked for (pfhip_stream_set_detail)");
+  if (d->k > 0 && (!d->ids || !d->logp)) return fail(PFHIP_ERR_ARG, "stream detail: k > 0 with a null buffer");
+  if (d->fire_frame && !s->det_fires) return fail(PFHIP_ERR_ARG, "stream detail: fire frames were off in the last call (pfhip_stream_set_detail)");
+  *n_tokens = s->det_n;
+  if (d->cap < s->det_n) return fail(PFHIP_ERR_CAPACITY, "stream detail: cap too small (n_tokens holds the count needed)");
+  const int k = d->k, kc = s->det_k;
+  for (int j = 0; j < s->det_n; ++j) {
+    for (int i = 0; i < k; ++i) {
+      d->ids[(size_t)j * k + i] = s->det_ids[(size_t)j * kc + i];
+      d->logp[(size_t)j * k + i] = s->det_logp[(size_t)j * kc + i];
+    }
+    if (d->fire_frame) d->fire_frame[j] = s->det_fire[(size_t)j];
+  }
   return PFHIP_OK;
 }
 
@@ -708,6 +793,7 @@ pfhip_status prepare_first(Call& c, Recorder& rec) {
     s->is_last_chunk = true;
     s->last_path = 1;
     s->win_n = s->n_featc;
+    s->win_idx = s->featc_idx;
     rec.copy(Recorder::kWindow, s->chunk.f(), m->feat_pad, s->featc.f(), m->feat_dim, s->win_n, m->feat_dim);
     c.has_window = true;
     c.reinit = true;
@@ -722,7 +808,7 @@ pfhip_status prepare_first(Call& c, Recorder& rec) {
     else { c.second = true; s->last_path = 3; }                                     // (:560-579) first chunk + last chunk
     c.reinit = true;
   }
-  rc = add_overlap_chunk(s, 0, c.nr, c.fin, rec, &s->win_n);
+  rc = add_overlap_chunk(s, 0, c.nr, s->start_idx - c.nr, c.fin, rec, &s->win_n);       // start_idx already counts this call's rows
   if (rc) return rc;
   c.has_window = true;
   return PFHIP_OK;
@@ -733,13 +819,14 @@ pfhip_status prepare_second(Call& c, Recorder& rec) {
   pfhip_stream* s = c.s;
   s->is_last_chunk = true;
   const int k = c.nr + s->chunk_size[2] - s->chunk_size[1];
-  return add_overlap_chunk(s, c.nr - k, k, c.fin, rec, &s->win_n);
+  return add_overlap_chunk(s, c.nr - k, k, s->start_idx - k, c.fin, rec, &s->win_n);      // the last k rows again, under their numbers
 }
 
 pfhip_status forward_calls(pfhip_model* m, std::vector<Call>& calls, hipStream_t st) {
   bool want_logp = false;
   Recorder rec;
   for (Call& c : calls) {
+    c.s->clear_detail(c.s->nbest_k, c.s->want_fires);
     pfhip_status rc = prepare_first(c, rec);
     if (rc) return rc;
     want_logp = want_logp || c.s->debug;
@@ -798,7 +885,7 @@ pfhip_status forward_batch_each(pfhip_stream* const* streams, int n_streams, con
   pfhip_status rc = forward_calls(m, calls, st);
   if (rc) {
     const std::string why = last_error();
-    for (Call& c : calls) { reset_cache(c.s); (void)init_cache(c.s, st); }
+    for (Call& c : calls) { reset_cache(c.s); (void)init_cache(c.s, st); c.s->clear_detail(0, false); }
     (void)hipStreamSynchronize(st);
     last_error() = why + " (every stream of the batch was reset)";
     return all(rc);
@@ -807,6 +894,7 @@ pfhip_status forward_batch_each(pfhip_stream* const* streams, int n_streams, con
   std::string first_err;
   for (int i = 0; i < n_streams; ++i) {
     n_tokens[i] = (int)calls[i].out.size();
+    calls[i].s->det_n = n_tokens[i];                       // kept when token_ids is too small, like n_tokens
     pfhip_status si = PFHIP_OK;
     if ((int)calls[i].out.size() > cap[i]) {
       si = fail(PFHIP_ERR_CAPACITY, "token_ids too small (n_tokens holds the count needed; the chunk's ids are lost)");

@@ -76,12 +76,17 @@ __global__ __launch_bounds__(256) void rows_copy_batch_kernel(const RowsCopyOp* 
     op.dst[(size_t)r * op.ldd + c] = (op.src && c < op.ncols) ? op.src[(size_t)r * op.lds + c] : 0.f;
 }
 
-template <int NC>
+// FIRES: the sibling that also records in which step i of the scan each stored token fired (fire_step[b * emb_rows + j]; i = 0 the
+// carry slot, 1..n window rows 0..n-1, n + 1 the tail slot).  One lane stores it; the arithmetic is the same statements, so emb, the
+// carry and n_fire are the default instantiation's bit for bit.  The pointer is a parameter of the sibling alone (FS = int*), so the
+// default instantiation keeps its signature and kernel arguments.
+template <int NC, bool FIRES = false, typename... FS>
 __global__ __launch_bounds__(512) void cif_stream_kernel(const float* __restrict__ enc_all, int lde,
                                                          const float* __restrict__ alphas_all,
                                                          const StreamSeg* __restrict__ segs, float thr, float tail,
                                                          float* __restrict__ emb_all, int emb_rows,
-                                                         int* __restrict__ n_fire_all, int D) {
+                                                         int* __restrict__ n_fire_all, int D, FS... fire_step_all) {
+  static_assert(sizeof...(FS) == (FIRES ? 1 : 0), "the fire-step pointer belongs to the FIRES instantiation only");
   const StreamSeg sg = segs[blockIdx.x];
   const float* enc = enc_all + (size_t)sg.row_off * lde;
   const float* alphas = alphas_all + sg.row_off;
@@ -123,6 +128,10 @@ __global__ __launch_bounds__(512) void cif_stream_kernel(const float* __restrict
         frames[c] += w * hv[c];
         const int ch = threadIdx.x + c * 512;
         if (ch < D && nf < emb_rows) emb[(size_t)nf * D + ch] = frames[c];
+      }
+      if constexpr (FIRES) {
+        int* fire_step = (fire_step_all, ...) + (size_t)blockIdx.x * emb_rows;
+        if (threadIdx.x == 0 && nf < emb_rows) fire_step[nf] = i;
       }
       ++nf;
       integrate += alpha;
@@ -214,8 +223,17 @@ void launch_rows_copy_batch(const RowsCopyOp* ops, int n_ops, int max_rows, hipS
 }
 
 void launch_cif_stream(const float* enc, int lde, const float* alphas, const StreamSeg* segs, int B, float threshold, float tail,
-                       float* emb_all, int emb_rows, int* n_fire, int D, hipStream_t s) {
+                       float* emb_all, int emb_rows, int* n_fire, int D, hipStream_t s, int* fire_step) {
   if (B <= 0) return;
+  if (fire_step) {
+    if (D <= 512)
+      hipLaunchKernelGGL((cif_stream_kernel<1, true, int*>), dim3(B), dim3(512), 0, s, enc, lde, alphas, segs, threshold, tail, emb_all,
+                         emb_rows, n_fire, D, fire_step);
+    else
+      hipLaunchKernelGGL((cif_stream_kernel<2, true, int*>), dim3(B), dim3(512), 0, s, enc, lde, alphas, segs, threshold, tail, emb_all,
+                         emb_rows, n_fire, D, fire_step);
+    return;
+  }
   if (D <= 512)
     hipLaunchKernelGGL(cif_stream_kernel<1>, dim3(B), dim3(512), 0, s, enc, lde, alphas, segs, threshold, tail, emb_all, emb_rows,
                        n_fire, D);

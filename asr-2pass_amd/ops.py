@@ -444,6 +444,18 @@ def cif_stream(enc, alphas, row_off, n, is_last, pre, suf, carry, D, threshold, 
                                 float(threshold), float(tail), _p(emb), emb.shape[1], _p(n_fire), _stream()), "cif_stream")
 
 
+def cif_stream_fires(enc, alphas, row_off, n, is_last, pre, suf, carry, D, threshold, tail, emb, n_fire, fire_step):
+    """cif_stream by the sibling kernel that also writes fire_step [B, emb_rows] int32: the scan step in which each stored token
+    fired (0 = the carry slot, 1..n = window rows 0..n-1, n + 1 = the tail slot).  Slots past the stored fires are left alone."""
+    B = len(n)
+    lib = _lib()
+    lib.pfhip_op_cif_stream_fires.argtypes = [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _ci, _ci, _cf, _cf, _vp, _ci, _vp, _vp, _vp]
+    ro, n_, il, pr, su = _hi(row_off), _hi(n), _hi(is_last), _hi(pre), _hi(suf)
+    _ck(lib.pfhip_op_cif_stream_fires(_p(enc), enc.stride(0), _p(alphas), ro[1], n_[1], il[1], pr[1], su[1], _p(carry), carry.stride(0), B,
+                                      D, float(threshold), float(tail), _p(emb), emb.shape[1], _p(n_fire), _p(fire_step), _stream()),
+        "cif_stream_fires")
+
+
 def fsmn_cached(t2, w, res, out, tok_off, n_tok, dcache, layer):
     """The streaming decoder's cached FSMN for B connections: out (may be res) = res + t2 + conv over [cache; t2];
     dcache [B, layers, 10, C] is advanced in place.  tok_off / n_tok: host int sequences."""

@@ -293,6 +293,12 @@ typedef struct {
 pfhip_status pfhip_offline_forward_nbest(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch,
                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
                                          pfhip_out* out, const pfhip_nbest* nb);
+/* The same from 16-bit PCM (what pfhip_offline_forward_hwsets_s16 is to pfhip_offline_forward_hwsets; see "16-bit PCM in" above):
+ * token ids, candidates and values are those of the f32 call fed s / 32768.f bit for bit; callers of both formats share the
+ * merge queue as those of the other offline calls do (a packed forward holds one format). */
+pfhip_status pfhip_offline_forward_nbest_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch,
+                                             const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                             pfhip_out* out, const pfhip_nbest* nb);
 /* Device-pointer form: k candidates for every following pfhip_offline_enqueue of this handle (context 0), 0 = off (default).
  * GreedySearch's arg-max stays what pfhip_offline_fetch returns; the candidates stay in the device workspace beside it. */
 pfhip_status pfhip_set_nbest(pfhip_model* m, int k);
@@ -359,6 +365,28 @@ pfhip_status pfhip_set_stream_batching(pfhip_model* m, int wait_us, int max_stre
 pfhip_status pfhip_stream_set_debug(pfhip_stream* s, int on);
 pfhip_status pfhip_stream_get_tensor(pfhip_stream* s, const char* name, float* dst, size_t cap_floats,
                                      size_t* n_out);
+/* N-best candidates, confidences and fire frames per streamed token (an extension: OnlineGreedySearch, paraformer.cpp:362-371,
+ * keeps only the arg-max, and the reference's streaming result carries no time).  Per stream, and through every forward entry
+ * point above, batched or merged: the packed forward's head computes the largest k of its streams (topk.hip, as offline) and
+ * each stream keeps its own first k; the CIF scan records the step in which each token fired and the host turns it into
+ * fire_frame: the index, among the LFR rows this stream's front end has emitted since creation, reset or its last final call
+ * (first row = 0; one row = lfr_n * 10 ms), of the row the token fired in.  Rows that a two-window final call (:560-579)
+ * feeds again keep their numbers, so within that one call fire_frame can step back.  A token fired by the tail slot of a last
+ * chunk gets the window's last row.  With k = 0 and fire frames off (default) every call launches what it always launched.
+ * k = 0..8 candidates per token (0 = off), fire_frames != 0: also where each token fired.  Applies to the stream's following calls. */
+pfhip_status pfhip_stream_set_detail(pfhip_stream* s, int nbest_k, int fire_frames);
+typedef struct {
+  int32_t k;            /* <= the stream's k; 0 with ids/logp NULL = fire frames only */
+  int32_t* ids;         /* [cap * k] row-major, ids[j*k] == the j-th token id the call returned */
+  float* logp;          /* [cap * k] descending; bit for bit the logp entry of its column */
+  int32_t* fire_frame;  /* [cap] or NULL */
+  int32_t cap;          /* token rows the buffers hold */
+} pfhip_stream_detail;
+/* The detail of the stream's LAST forward (any entry point, batched or merged); valid until its next forward or reset.
+ * n_tokens receives the count (the call's n_tokens, also where its token_ids was too small).  PFHIP_ERR_ARG for a k above
+ * what the last call computed or fire frames that were off; PFHIP_ERR_CAPACITY (n_tokens = the count needed) when cap is too
+ * small.  A failed shared forward and pfhip_stream_reset leave no detail. */
+pfhip_status pfhip_stream_last_detail(pfhip_stream* s, const pfhip_stream_detail* d, int* n_tokens);
 
 /* ---- FSMN-VAD forward ---------------------------------------------------------------------------
  *   pfhip_vad_create_from_memory <-> FsmnVad::InitVad (ReadModel + LoadCmvn + InitCache, fsmn-vad.cpp:12-70, 258-263)

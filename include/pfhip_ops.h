@@ -170,6 +170,13 @@ int pfhip_op_resample(const float* d_in, const int64_t* in_off, const int* n_in,
 int pfhip_op_cif_stream(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
                         const int* pre, const int* suf, float* carry, long long carry_stride, int B, int D, float threshold,
                         float tail, float* emb, int emb_rows, int* n_fire, void* stream);
+/* The same scan by the sibling instantiation that also records where each token fired: fire_step[b * emb_rows + j] = the step of
+ * the scan in which stored token j of connection b fired (0 = the carry slot, 1..n[b] = window rows 0..n[b]-1, n[b] + 1 = the tail
+ * slot).  Slots past the stored fires are not written.  emb, n_fire and the carry are pfhip_op_cif_stream's bit for bit.  Refuses
+ * what pfhip_op_cif_stream refuses, and a NULL fire_step. */
+int pfhip_op_cif_stream_fires(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,
+                              const int* pre, const int* suf, float* carry, long long carry_stride, int B, int D, float threshold,
+                              float tail, float* emb, int emb_rows, int* n_fire, int* fire_step, void* stream);
 /* The streaming decoder's FSMN with its 10-frame cache (paraformer-online.cpp:374, 500): connection b's tokens are rows
  * [tok_off[b], tok_off[b] + n_tok[b]) of t2 / res / out (row stride C; out may alias res), its caches [layers][10][C] live at
  * dcache + b * dcache_stride; out = res + t2 + conv over [cache; t2], and the layer's cache becomes the last 10 rows of [cache; t2]
