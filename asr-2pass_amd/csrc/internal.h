@@ -13,11 +13,11 @@
 #include <mutex>
 #include <string>
 #include <tuple>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/pfhip.h"
 #include "kernels.h"
+#include "weights.h"
 #include "hotword_bank.h"
 #include "merge_queue.h"
 
@@ -67,6 +67,12 @@ std::atomic<uint64_t>& buf_epoch();          // pfhip.cpp
 struct Buf {
   void* p = nullptr;
   size_t cap = 0;
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+  ~Buf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     buf_epoch().fetch_add(1);
@@ -81,34 +87,33 @@ struct Buf {
   int* i() const { return static_cast<int*>(p); }
 };
 
-struct Tensor {
-  const float* d = nullptr;   // device
-  const float* h = nullptr;   // host (only valid during create)
-  std::vector<int> shape;
-  size_t n = 0;
+// Pinned host staging, grown on demand to twice the request (callers have no copy in flight from the old block: every forward ends
+// with a sync); freed by its destructor.
+struct PinBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { if (p) (void)hipHostFree(p); }
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    if (p) { hipError_t e = hipHostFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
+    hipError_t e = hipHostMalloc(&p, bytes * 2, hipHostMallocDefault);
+    if (e == hipSuccess) cap = bytes * 2;
+    return e;
+  }
+  int* i() const { return static_cast<int*>(p); }
 };
 
-struct Config {
-  int d_model = 512, n_head = 4, ffn = 2048, enc_layers = 50, dec_layers = 16, dec_ffn = 2048;
-  int dec_n_head = 0;          // decoder_conf.attention_heads when it differs from the encoder's; pfhip_create resolves 0 to n_head
-  int kernel = 11, vocab = 8404, n_mels = 80, lfr_m = 7, lfr_n = 6, pred_residual = 0, contextual = 0, timestamp = 0;
-  float smooth_factor2 = 0.25f, noise_threshold2 = 0.01f;      // CifPredictorV3 timestamp head
-  float cif_threshold = 1.0f, tail_threshold = 0.45f, smooth_factor = 1.0f, noise_threshold = 0.0f;
-  int sample_rate = 16000;
-};
-
-struct FrontendTables {
-  float* d_window = nullptr; double* d_tw = nullptr; int* d_mel_off = nullptr; int* d_mel_size = nullptr;
-  float* d_mel_w = nullptr;
-};
 pfhip_status build_frontend_tables(int n_mels, int sample_rate, FrontendTables* ft);   // pfhip.cpp
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // A linear layer repacked for the GEMM kernels: W zero-padded to [ceil(N/128)*128][ceil(K/32)*32], bias to the
 // padded N, so pad outputs are exact zeros (odd widths: FSMN-VAD 140/250/248, punctuation head 6).
-struct Lin { float* w = nullptr; float* b = nullptr; int N = 0, K = 0, Np = 0, Kp = 0; float ws = 1.0f; };
-inline pfhip_status pack_linear(const float* w, const float* bias, int N, int K, Lin* out) {
+struct PackedLin { DevMem w, b; int N = 0, K = 0, Np = 0, Kp = 0; float ws = 1.0f; };
+inline pfhip_status pack_linear(const float* w, const float* bias, int N, int K, PackedLin* out) {
   out->N = N; out->K = K; out->Np = round_up(N, 128); out->Kp = round_up(K, 32);
   std::vector<float> pw((size_t)out->Np * out->Kp, 0.f), pb((size_t)out->Np, 0.f);
   for (int n = 0; n < N; ++n) std::memcpy(&pw[(size_t)n * out->Kp], w + (size_t)n * K, sizeof(float) * K);
@@ -116,17 +121,14 @@ inline pfhip_status pack_linear(const float* w, const float* bias, int N, int K,
   float mx = 0.f;
   for (float v : pw) mx = std::max(mx, std::fabs(v));
   out->ws = pfhip::best_w_scale(mx);
-  HIP_TRY(hipMalloc((void**)&out->w, pw.size() * 4));
-  HIP_TRY(hipMemcpy(out->w, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&out->b, pb.size() * 4));
-  HIP_TRY(hipMemcpy(out->b, pb.data(), pb.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(out->w.upload(pw));
+  HIP_TRY(out->b.upload(pb));
   return PFHIP_OK;
 }
-inline void lin_gemm(hipStream_t s, const Lin& l, const float* A, int lda, float* C, int ldc, const float* R1, int ldr1,
+inline void lin_gemm(hipStream_t s, const PackedLin& l, const float* A, int lda, float* C, int ldc, const float* R1, int ldr1,
                      const float* R2, int ldr2, int M, bool relu) {
-  pfhip::launch_gemm_f32(A, lda, l.w, l.Kp, C, ldc, l.b, R1, ldr1, R2, ldr2, M, l.Np, l.Kp, relu, false, s, l.ws);
+  pfhip::launch_gemm_f32(A, lda, l.w.f(), l.Kp, C, ldc, l.b.f(), R1, ldr1, R2, ldr2, M, l.Np, l.Kp, relu, false, s, l.ws);
 }
-inline void free_lin(Lin& l) { if (l.w) (void)hipFree(l.w); if (l.b) (void)hipFree(l.b); l.w = l.b = nullptr; }
 
 struct ProfRec { int cls; hipEvent_t e0, e1; };
 
@@ -145,19 +147,20 @@ void build_resample_plan(int fs_in, int fs_out, ResamplePlan* p);
 // Device images of the plans, uploaded once per (device, rate pair) and kept until the cache dies; safe for concurrent callers.
 class ResampleCache {
  public:
-  ~ResampleCache();
   pfhip_status get(int device, int fs_in, int fs_out, pfhip::ResampleTable* out);
  private:
+  struct Plan { DevMem first, ntap, w; pfhip::ResampleTable t; };
   std::mutex mu;
-  std::map<std::tuple<int, int, int>, pfhip::ResampleTable> plans;
+  std::map<std::tuple<int, int, int>, Plan> plans;
 };
 
 }  // namespace pfhip_detail
 
 using pfhip_detail::Buf;
 using pfhip_detail::Config;
+using pfhip_detail::ModelWeights;
+using pfhip_detail::PinBuf;
 using pfhip_detail::ProfRec;
-using pfhip_detail::Tensor;
 
 struct BatchReq;
 struct StreamReq;
@@ -186,30 +189,12 @@ struct pfhip_model {
   hipEvent_t ev_enc_ready = nullptr;
   std::vector<hipEvent_t> ev_kv;
   std::mutex mu;
-  Config cfg;
-  int feat_dim = 560, feat_pad = 576, vocab_pad = 8448;
-
-  float* d_blob = nullptr;
-  std::map<std::string, Tensor> t;
-  float* d_w0qkv = nullptr;     // enc.0.qkv.w K-padded to feat_pad
-  float* d_predconv = nullptr;  // [d][3*d] im2col order
-  float* d_vocab_bias = nullptr;  // dec.out.b padded to vocab_pad
-  float* d_kv_all_w = nullptr;    // the decoder layers' kv.w stacked [layers * 2d][d] (+ bias): one launch projects a streaming window for all layers
-  float* d_kv_all_b = nullptr;
-  // LayerNorm folded into its consumer GEMM (gemm_x6.hip LN-on-load): per encoder layer W * gamma (per input column) and
-  // bias + W beta, for qkv (layers >= 1) and ffn1; [layers][N][d] / [layers][N]
-  float* d_lnw_qkv = nullptr; float* d_lnb_qkv = nullptr; float* d_lnw_ffn1 = nullptr; float* d_lnb_ffn1 = nullptr;
-  float* d_lns_qkv = nullptr; float* d_lns_ffn1 = nullptr;      // column sums of the folded weights [layers][N]
-  // fp16 plane images (gemm_p3.hip) of the encoder's four large weights per layer, scale baked in: [layer] { qkv' | out | ffn1' |
-  // ffn2 }, each image hi plane then lo plane.  wp_layer_bytes = 0: not built (the fp32 path serves every batch size).
-  unsigned char* d_wplanes = nullptr;
-  size_t wp_layer_bytes = 0, wp_off_out = 0, wp_off_ffn1 = 0, wp_off_ffn2 = 0;
+  // everything that is read-only after load, shared by the weight owner and its contexts (weights.h); the last of them frees it
+  std::shared_ptr<const ModelWeights> weights;
   // guard of the fp16 two-plane domain (pfhip.cpp fetch_locked): the forward's flag word (inside `meta`, cleared by the metadata
   // upload), its pinned host mirror, what a re-run on the exact kernels needs, and the count of such re-runs
-  double static_bound = 0.0;          // load-time bound on |Linear(LayerNorm(x))| over the model's layers
-  bool always_exact = false;          // that bound reaches fp16's range: every forward runs the exact kernels
   int* d_range_flag = nullptr;
-  int* h_flag = nullptr;
+  PinBuf h_flag;
   int range_hit = 0, debug_range_flag = 0;
   bool exact_rerun = false, last_feats_only = false;
   long long range_fallbacks = 0;
@@ -221,20 +206,7 @@ struct pfhip_model {
   Buf kvP;                                                      // K | V of an encoder layer as row-major fp16 planes (attention_p3.hip)
   int kvplane_forwards = 0;                                     // forwards whose encoder attention took K | V as planes (debug read-out)
   Buf encP, xdP;                                                // decoder on plane operands: images of the encoder output and of the token-side residual stream
-  // fp16 plane images of the decoder's large weights per layer (dec3 = the last entry: FFN only): [layer] { ffn1' | ffn2' | kv | out }
-  unsigned char* d_dwplanes = nullptr;
-  size_t dwp_layer_bytes = 0, dwp_off_ffn2 = 0, dwp_off_kv = 0, dwp_off_out = 0;
   int dec_plane_forwards = 0;                                   // forwards whose decoder took the plane path (debug read-out)
-  // the same for the decoder's FFN: ffn1 with norm1, ffn2 with ffn_norm; [dec_layers + 1] entries (the last one is dec3)
-  float* d_dlnw1 = nullptr; float* d_dlnb1 = nullptr; float* d_dlns1 = nullptr;
-  float* d_dlnw2 = nullptr; float* d_dlnb2 = nullptr; float* d_dlns2 = nullptr;
-  float* d_dlnw3 = nullptr; float* d_dlnb3 = nullptr; float* d_dlns3 = nullptr;     // norm3 -> q projection (streaming latency path)
-  // timestamp head repacks: ConvTranspose1d as [3d][d] + tiled bias, both LSTM directions' input weights [8d][d] + summed
-  // biases, recurrent weights [2][4d][d]
-  float* d_up_w = nullptr; float* d_up_b = nullptr; float* d_wih = nullptr; float* d_bih = nullptr; float* d_whh = nullptr;
-  // front-end tables
-  float* d_window = nullptr; double* d_tw = nullptr; int* d_mel_off = nullptr; int* d_mel_size = nullptr;
-  float* d_mel_w = nullptr; float* d_inv_ts = nullptr;
 
   // workspace
   Buf pcm, meta, feats, x0, x, y, qkv, mem, ctx, hbuf, enc, alphas, counts;
@@ -248,7 +220,7 @@ struct pfhip_model {
   Buf lnstats;                  // per-row LayerNorm statistics handed from a producing GEMM's epilogue to the consumer [M][4][2]
   Buf kvall;                    // one window's K/V projections of every decoder layer [32][layers * 2d]
   Buf fbk, d_ops;               // streaming batch: fbank frames of all connections, operation descriptors
-  void* h_ops = nullptr; size_t h_ops_cap = 0;       // pinned staging of the same (+ the batch's PCM)
+  PinBuf h_ops;                 // pinned staging of the same (+ the batch's PCM)
   Buf ts_up, ts_gx, ts_y, ts_hx, ts_a2, ts_alphas, ts_peaks, ts_meta, ts_cst;
   bool have_ts = false;
   int debug_blstm_flag = 0;        // pfhip_debug_poke
@@ -256,16 +228,13 @@ struct pfhip_model {
   hipEvent_t ev_ts_in = nullptr, ev_ts_out = nullptr;
   bool ts_persistent = false;              // the last timestamp head ran the persistent kernel: its error word is read with the results
   int blstm_fallbacks = 0;         // timestamp requests served by the per-step recurrence after a barrier time-out
-  float out2_b = 0.f;
   // hotwords of the forward being run (resolve_hotwords_locked): per utterance the first row and the row count of its set's
   // K/V rows under fw_hwkv — the device's bank arena, or this context's `hwkv` when a set did not fit the bank — and the bank
   // entries this forward has pinned
   std::vector<int> fw_hw_off, fw_hw_len, fw_pins;
   const float* fw_hwkv = nullptr;
   std::unique_ptr<pfhip_detail::HwBankDev> hwbank{new pfhip_detail::HwBankDev};      // on the weight owner
-  void* h_meta = nullptr; size_t h_meta_cap = 0;     // pinned
-  int* h_counts = nullptr;                            // pinned [2*B]
-  size_t h_counts_cap = 0;
+  PinBuf h_meta, h_counts;      // pinned: the metadata uploads (two halves), the token counts [2*B]
 
   // state of the last forward
   int B = 0, M = 0, ML = 0, maxT = 0, maxL = 0;
@@ -308,9 +277,9 @@ struct pfhip_model {
   std::atomic<int> inflight{0};
   std::atomic<int64_t> served_calls{0}, served_utts{0}, served_forwards{0};
   std::atomic<unsigned> rr{0};
-  // Execution contexts (pfhip_set_inflight / PFHIP_INFLIGHT): further pfhip_model objects on THIS device that borrow every
-  // weight pointer of `weights_of` (the blob, the repacks, the LayerNorm-folded copies, the front-end tables) and own only a
-  // workspace, streams and events — the reference's one shared Ort::Session under many decoder threads (paraformer.cpp:35-41,541).
+  // Execution contexts (pfhip_set_inflight / PFHIP_INFLIGHT): further pfhip_model objects on THIS device that share the
+  // `weights` of `weights_of` and own only a workspace, streams and events — the reference's one shared Ort::Session under many
+  // decoder threads (paraformer.cpp:35-41,541).
   std::vector<pfhip_model*> contexts;       // on a device replica: its extra contexts (the replica itself is context 0)
   pfhip_model* weights_of = nullptr;        // on a context: whose weights it borrows
   int ctx_index = 0;
@@ -321,12 +290,8 @@ struct pfhip_model {
   std::shared_ptr<const std::vector<float>> hw_default;
   bool hw_merge = false;                    // on the head: contextual callers join the merge queue (pfhip_set_hotword_merging)
 
-  // per weight matrix (device pointer of its first element): the power-of-two scale the fp16 two-plane GEMM stages it with
-  // (kernels.h best_w_scale), fixed at load from its largest magnitude; contexts copy the table
-  std::unordered_map<const void*, float> wscale;
-  float w_scale_of(const void* w) const { auto it = wscale.find(w); return it == wscale.end() ? 1.0f : it->second; }
-
-  const Tensor& W(const std::string& n) const { return t.at(n); }
+  // sets the device, waits for it, destroys contexts / replicas, events and streams; the members then free what they own
+  ~pfhip_model();
 };
 
 namespace pfhip_detail {
@@ -362,37 +327,18 @@ struct Scope {
 
 enum { K_GEMM = 0, K_ATTN = 1, K_LN = 2, K_FSMN = 3, K_FBANK = 4, K_CIF = 5, K_HEAD = 6, K_OTHER = 7 };
 
-inline void gemm(pfhip_model* m, hipStream_t s, const float* A, int lda, const float* Wd, int N, int K, int Ktrue,
-          float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
-          int M, bool relu) {
+// C = A L.w^T + L.b (+ R1 + R2)
+inline void gemm(pfhip_model* m, hipStream_t s, const float* A, int lda, const Linear& L, int N, int K, int Ktrue,
+          float* C, int ldc, const float* R1, int ldr1, const float* R2, int ldr2, int M, bool relu) {
   Scope sc(m, s, K_GEMM, 2.0 * M * (double)N * Ktrue, 4.0 * ((double)M * Ktrue + (double)N * Ktrue + (double)M * N));
   // N that is no multiple of the column tile AND a C too narrow for the tile's pad columns (d_model 320: N = 320 / 960 with ldc = N):
   // the bounds-checked epilogue.  The model's other shapes (N % 128 == 0, or the vocabulary with ldc = vocab_pad) keep the unguarded one.
   const bool guard = N % pfhip::kTileN != 0 && ldc < (N + pfhip::kTileN - 1) / pfhip::kTileN * pfhip::kTileN;
-  launch_gemm_f32(A, lda, Wd, K, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, guard, s, m->w_scale_of(Wd));
+  launch_gemm_f32(A, lda, L.w, K, C, ldc, L.b, R1, ldr1, R2, ldr2, M, N, K, relu, guard, s, L.scale);
 }
-// pinned staging, grown on demand (callers have no copy in flight from the old block: every forward ends with a sync)
-inline pfhip_status ensure_h_meta(pfhip_model* m, size_t bytes) {
-  if (bytes <= m->h_meta_cap) return PFHIP_OK;
-  if (m->h_meta) HIP_TRY(hipHostFree(m->h_meta));
-  m->h_meta = nullptr; m->h_meta_cap = 0;
-  HIP_TRY(hipHostMalloc(&m->h_meta, bytes * 2, hipHostMallocDefault));
-  m->h_meta_cap = bytes * 2;
-  return PFHIP_OK;
-}
-inline pfhip_status ensure_h_counts(pfhip_model* m, size_t bytes) {
-  if (bytes <= m->h_counts_cap) return PFHIP_OK;
-  if (m->h_counts) HIP_TRY(hipHostFree(m->h_counts));
-  m->h_counts = nullptr; m->h_counts_cap = 0;
-  HIP_TRY(hipHostMalloc((void**)&m->h_counts, bytes * 2, hipHostMallocDefault));
-  m->h_counts_cap = bytes * 2;
-  return PFHIP_OK;
-}
-inline void lnorm(pfhip_model* m, hipStream_t s, const float* x, int ldx, float* y, int ldy, const std::string& name,
-           int M, int D, int Dout) {
+inline void lnorm(pfhip_model* m, hipStream_t s, const float* x, int ldx, float* y, int ldy, const Norm& n, int M, int D, int Dout) {
   Scope sc(m, s, K_LN, 8.0 * M * D, 8.0 * M * D);
-  pfhip::launch_layernorm(x, ldx, y, ldy, m->W(name + ".g").d, m->W(name + ".b").d, M, D, Dout, 1e-12f, s);
+  pfhip::launch_layernorm(x, ldx, y, ldy, n.g, n.b, M, D, Dout, 1e-12f, s);
 }
-
 
 }  // namespace pfhip_detail

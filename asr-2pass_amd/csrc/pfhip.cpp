@@ -20,6 +20,7 @@
 #include <mutex>
 #include <sstream>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "internal.h"
@@ -76,13 +77,6 @@ void build_mel(int num_bins, float sample_freq, std::vector<int>& off, std::vect
   }
 }
 
-template <typename T>
-pfhip_status upload(T** dst, const std::vector<T>& v) {
-  HIP_TRY(hipMalloc((void**)dst, std::max<size_t>(v.size(), 1) * sizeof(T)));
-  HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return PFHIP_OK;
-}
-
 }  // namespace
 
 namespace pfhip_detail {
@@ -98,10 +92,11 @@ pfhip_status build_frontend_tables(int n_mels, int sample_rate, FrontendTables* 
   build_mel(n_mels, (float)sample_rate, moff, msz, mw);
   for (int b = 0; b < n_mels; ++b)
     if (msz[b] > pfhip::kMelW) return fail(PFHIP_ERR_UNSUPPORTED, "mel triangle wider than kMelW");
-  pfhip_status st;
-  if ((st = upload(&ft->d_window, win)) || (st = upload(&ft->d_tw, tw)) || (st = upload(&ft->d_mel_off, moff)) ||
-      (st = upload(&ft->d_mel_size, msz)) || (st = upload(&ft->d_mel_w, mw)))
-    return st;
+  HIP_TRY(ft->window.upload(win));
+  HIP_TRY(ft->tw.upload(tw));
+  HIP_TRY(ft->mel_off.upload(moff));
+  HIP_TRY(ft->mel_size.upload(msz));
+  HIP_TRY(ft->mel_w.upload(mw));
   return PFHIP_OK;
 }
 }  // namespace pfhip_detail
@@ -110,6 +105,14 @@ namespace {
 using namespace pfhip_detail;
 
 pfhip_status create_streams(pfhip_model* m);
+
+// a tensor of the blob as the builder sees it: by name, with its host copy.  Nothing of this outlives build_model.
+struct Tensor {
+  const float* d = nullptr;   // device
+  const float* h = nullptr;   // host
+  std::vector<int> shape;
+  size_t n = 0;
+};
 
 pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manifest_json, int device,
                          pfhip_model** out) {
@@ -126,9 +129,11 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   const pfhip::JValue* jt = man.get("tensors");
   if (!jc || !jt || jt->kind != pfhip::JValue::OBJ) return fail(PFHIP_ERR_FORMAT, "manifest needs config and tensors");
 
+  // a return before the end gives everything back: `w` frees its allocations, `m` its streams (after it has waited for the device)
+  std::shared_ptr<ModelWeights> w = std::make_shared<ModelWeights>();
   std::unique_ptr<pfhip_model> m(new pfhip_model);
   m->device = device;
-  Config& c = m->cfg;
+  Config& c = w->cfg;
   c.d_model = (int)jc->number("d_model", c.d_model);
   c.n_head = (int)jc->number("n_head", c.n_head);
   c.dec_n_head = (int)jc->number("dec_n_head", c.n_head);       // written by the loaders only where decoder_conf differs
@@ -170,16 +175,17 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   if (c.ffn % 128 || c.dec_ffn % 128 || c.ffn > 2048 || c.dec_ffn > 2048)
     return fail(PFHIP_ERR_UNSUPPORTED, "ffn width must be a multiple of 128 and <= 2048");
   if (c.enc_layers < 1 || c.dec_layers < 0) return fail(PFHIP_ERR_FORMAT, "bad layer counts");
-  m->feat_dim = c.n_mels * c.lfr_m;
-  m->feat_pad = round_up(m->feat_dim, pfhip::kTileK);
-  m->vocab_pad = round_up(c.vocab, pfhip::kTileN);
+  w->feat_dim = c.n_mels * c.lfr_m;
+  w->feat_pad = round_up(w->feat_dim, pfhip::kTileK);
+  w->vocab_pad = round_up(c.vocab, pfhip::kTileN);
 
   // ---- weights: upload the blob once; GEMM N-padding reads run into the slack at the end ----------
   const size_t slack = (size_t)pfhip::kTileN * 2048 * sizeof(float);
-  HIP_TRY(hipMalloc((void**)&m->d_blob, blob_bytes + slack));
-  HIP_TRY(hipMemset(m->d_blob, 0, blob_bytes + slack));
-  HIP_TRY(hipMemcpy(m->d_blob, blob, blob_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(w->blob.alloc(blob_bytes + slack));
+  HIP_TRY(hipMemset(w->blob.p, 0, blob_bytes + slack));
+  HIP_TRY(hipMemcpy(w->blob.p, blob, blob_bytes, hipMemcpyHostToDevice));
   const float* hb = static_cast<const float*>(blob);
+  std::map<std::string, Tensor> t;
   for (const auto& kv : jt->obj) {
     const pfhip::JValue* sh = kv.second.get("shape");
     const pfhip::JValue* of = kv.second.get("offset");
@@ -189,30 +195,34 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
     for (const auto& d : sh->arr) { tt.shape.push_back((int)d.num); tt.n *= (size_t)d.num; }
     const size_t off = (size_t)of->num;
     if (off % 16 || off + tt.n * 4 > blob_bytes) return fail(PFHIP_ERR_FORMAT, "tensor " + kv.first + ": out of blob");
-    tt.d = m->d_blob + off / 4;
+    tt.d = w->blob.f() + off / 4;
     tt.h = hb + off / 4;
-    m->t.emplace(kv.first, std::move(tt));
+    t.emplace(kv.first, std::move(tt));
   }
-  // fp16 two-plane GEMM (gemm_x3.hip): one power-of-two scale per weight matrix, from its largest magnitude
+  auto T = [&](const std::string& n) -> const Tensor& { return t.at(n); };
+  // fp16 two-plane GEMM (gemm_x3.hip): one power-of-two scale per weight matrix (device pointer of its first element), from its
+  // largest magnitude; a matrix nothing was registered for is staged with 1.0
+  std::unordered_map<const void*, float> wscale;
   auto reg_scale = [&](const void* dptr, const float* host, size_t n) {
     float mx = 0.f;
     for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(host[i]));
-    m->wscale[dptr] = pfhip::best_w_scale(mx);
+    wscale[dptr] = pfhip::best_w_scale(mx);
   };
-  for (const auto& kv : m->t)
+  auto scale_of = [&](const void* p) { auto it = wscale.find(p); return it == wscale.end() ? 1.0f : it->second; };
+  for (const auto& kv : t)
     if (kv.second.shape.size() >= 2) reg_scale(kv.second.d, kv.second.h, kv.second.n);
   // required tensors / shapes
   auto need = [&](const std::string& n, std::vector<int> shape) -> bool {
-    auto it = m->t.find(n);
-    if (it == m->t.end()) { g_err = "missing tensor " + n; return false; }
+    auto it = t.find(n);
+    if (it == t.end()) { g_err = "missing tensor " + n; return false; }
     if (it->second.shape != shape) { g_err = "tensor " + n + " has unexpected shape"; return false; }
     return true;
   };
   const int d = c.d_model;
-  bool ok = need("cmvn.mean", {m->feat_dim}) && need("cmvn.istd", {m->feat_dim});
+  bool ok = need("cmvn.mean", {w->feat_dim}) && need("cmvn.istd", {w->feat_dim});
   for (int i = 0; ok && i < c.enc_layers; ++i) {
     const std::string p = "enc." + std::to_string(i) + ".";
-    const int in = i == 0 ? m->feat_dim : d;
+    const int in = i == 0 ? w->feat_dim : d;
     ok = need(p + "norm1.g", {in}) && need(p + "norm1.b", {in}) && need(p + "qkv.w", {3 * d, in}) &&
          need(p + "qkv.b", {3 * d}) && need(p + "fsmn.w", {d, c.kernel}) && need(p + "out.w", {d, d}) &&
          need(p + "out.b", {d}) && need(p + "norm2.g", {d}) && need(p + "norm2.b", {d}) &&
@@ -252,284 +262,318 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
 
   // ---- repacks ---------------------------------------------------------------------------------------
   {
-    const Tensor& w0 = m->W("enc.0.qkv.w");
-    std::vector<float> p((size_t)3 * d * m->feat_pad, 0.f);
+    const Tensor& w0 = T("enc.0.qkv.w");
+    std::vector<float> p((size_t)3 * d * w->feat_pad, 0.f);
     for (int n = 0; n < 3 * d; ++n)
-      std::memcpy(&p[(size_t)n * m->feat_pad], w0.h + (size_t)n * m->feat_dim, sizeof(float) * m->feat_dim);
-    pfhip_status st = upload(&m->d_w0qkv, p);
-    if (st) return st;
-    reg_scale(m->d_w0qkv, p.data(), p.size());
-    const Tensor& cw = m->W("pred.conv.w");
+      std::memcpy(&p[(size_t)n * w->feat_pad], w0.h + (size_t)n * w->feat_dim, sizeof(float) * w->feat_dim);
+    HIP_TRY(w->w0qkv.upload(p));
+    reg_scale(w->w0qkv.p, p.data(), p.size());
+    const Tensor& cw = T("pred.conv.w");
     std::vector<float> q((size_t)d * 3 * d);
     for (int n = 0; n < d; ++n)
       for (int ci = 0; ci < d; ++ci)
         for (int j = 0; j < 3; ++j) q[(size_t)n * 3 * d + (size_t)j * d + ci] = cw.h[((size_t)n * d + ci) * 3 + j];
-    st = upload(&m->d_predconv, q);
-    if (st) return st;
-    reg_scale(m->d_predconv, q.data(), q.size());
-    {
-      // The static half of the fp16-domain guard (kernels.h LaunchCtx).  Everything the two-plane kernels multiply besides the
-      // residual stream is the output of a Linear on a LayerNorm-ed row (q, k, v, the FFN hidden layer, the decoder's q / k / v,
-      // the logits' input) or an average of such rows (attention context, CIF embeddings), and a LayerNorm-ed row has norm
-      // sqrt(K) before gamma:   |LN(x) w_n + b_n| <= sqrt(K) * ||w_n o gamma||_2 + |b_n + w_n . beta|   for ANY input.
-      // A model whose bound reaches 32768 (no trained model's does: weights of norm ~1 give a few hundred) runs on the exact
-      // kernels altogether; the residual stream itself is checked per forward.
-      double worst = 0.0;
-      auto ln_linear = [&](const std::string& wn, const std::string& bn, const std::string& ln) {
-        if (!m->t.count(wn) || !m->t.count(ln + ".g")) return;
-        const Tensor& w = m->W(wn);
-        const float* bb = !bn.empty() && m->t.count(bn) ? m->W(bn).h : nullptr;
-        const float* g = m->W(ln + ".g").h; const float* be = m->W(ln + ".b").h;
-        const int N = w.shape[0], K = w.shape[1];
-        for (int n = 0; n < N; ++n) {
-          double ss = 0.0, dot = bb ? bb[n] : 0.0;
-          for (int k = 0; k < K; ++k) {
-            const double wg = (double)w.h[(size_t)n * K + k] * (double)g[k];
-            ss += wg * wg;
-            dot += (double)w.h[(size_t)n * K + k] * (double)be[k];
-          }
-          worst = std::max(worst, std::sqrt((double)K) * std::sqrt(ss) + std::fabs(dot));
+    HIP_TRY(w->predconv.upload(q));
+    reg_scale(w->predconv.p, q.data(), q.size());
+  }
+  {
+    // The static half of the fp16-domain guard (kernels.h LaunchCtx).  Everything the two-plane kernels multiply besides the
+    // residual stream is the output of a Linear on a LayerNorm-ed row (q, k, v, the FFN hidden layer, the decoder's q / k / v,
+    // the logits' input) or an average of such rows (attention context, CIF embeddings), and a LayerNorm-ed row has norm
+    // sqrt(K) before gamma:   |LN(x) w_n + b_n| <= sqrt(K) * ||w_n o gamma||_2 + |b_n + w_n . beta|   for ANY input.
+    // A model whose bound reaches 32768 (no trained model's does: weights of norm ~1 give a few hundred) runs on the exact
+    // kernels altogether; the residual stream itself is checked per forward.
+    double worst = 0.0;
+    auto ln_linear = [&](const std::string& wn, const std::string& bn, const std::string& ln) {
+      if (!t.count(wn) || !t.count(ln + ".g")) return;
+      const Tensor& wt = T(wn);
+      const float* bb = !bn.empty() && t.count(bn) ? T(bn).h : nullptr;
+      const float* g = T(ln + ".g").h; const float* be = T(ln + ".b").h;
+      const int N = wt.shape[0], K = wt.shape[1];
+      for (int n = 0; n < N; ++n) {
+        double ss = 0.0, dot = bb ? bb[n] : 0.0;
+        for (int k = 0; k < K; ++k) {
+          const double wg = (double)wt.h[(size_t)n * K + k] * (double)g[k];
+          ss += wg * wg;
+          dot += (double)wt.h[(size_t)n * K + k] * (double)be[k];
         }
-      };
-      for (int i = 0; i < c.enc_layers; ++i) {
-        const std::string ep = "enc." + std::to_string(i) + ".";
-        ln_linear(ep + "qkv.w", ep + "qkv.b", ep + "norm1");
-        ln_linear(ep + "ffn1.w", ep + "ffn1.b", ep + "norm2");
+        worst = std::max(worst, std::sqrt((double)K) * std::sqrt(ss) + std::fabs(dot));
       }
-      {
-        const float* g = m->W("enc.after_norm.g").h; const float* be = m->W("enc.after_norm.b").h;
-        double gm = 0.0, bm = 0.0;
-        for (int k = 0; k < d; ++k) { gm = std::max(gm, (double)std::fabs(g[k])); bm = std::max(bm, (double)std::fabs(be[k])); }
-        worst = std::max(worst, std::sqrt((double)d) * gm + bm);                 // |enc| (keys / values source, CIF embeddings)
-      }
-      for (int i = 0; i < c.dec_layers; ++i) {
-        const std::string dp = "dec." + std::to_string(i) + ".";
-        ln_linear(dp + "ffn1.w", dp + "ffn1.b", dp + "norm1");
-        ln_linear(dp + "ffn2.w", "", dp + "ffn_norm");
-        ln_linear(dp + "q.w", dp + "q.b", dp + "norm3");
-        ln_linear(dp + "kv.w", dp + "kv.b", "enc.after_norm");
-      }
-      ln_linear("dec3.ffn1.w", "dec3.ffn1.b", "dec3.norm1");
-      ln_linear("dec3.ffn2.w", "", "dec3.ffn_norm");
-      ln_linear("dec.out.w", "dec.out.b", "dec.after_norm");
-      if (c.contextual) ln_linear("bias.dec.q.w", "bias.dec.q.b", "bias.dec.norm3");
-      m->static_bound = worst;
-      m->always_exact = !(worst < 32768.0);
+    };
+    for (int i = 0; i < c.enc_layers; ++i) {
+      const std::string ep = "enc." + std::to_string(i) + ".";
+      ln_linear(ep + "qkv.w", ep + "qkv.b", ep + "norm1");
+      ln_linear(ep + "ffn1.w", ep + "ffn1.b", ep + "norm2");
     }
-    if (d == 4 * pfhip::kTileN) {   // LN-on-load needs the residual stream to be exactly four 128-column tiles wide
-      // W' = W * gamma[k], b' = b + W beta: LayerNorm's affine part folded into the GEMM that consumes it (offline path,
-      // large batches: enqueue_locked).  Products in double, rounded once.
-      auto foldk = [&](const std::string& wn, const std::string& bn, const std::string& ln, int N, int K, float* dw, float* db, float* ds) {
-        const float* w = m->W(wn).h; const float* bb = bn.empty() ? nullptr : m->W(bn).h;
-        const float* g = m->W(ln + ".g").h; const float* be = m->W(ln + ".b").h;
-        for (int n = 0; n < N; ++n) {
-          double acc = bb ? bb[n] : 0.0, cs = 0.0;
-          for (int k = 0; k < K; ++k) {
-            const float wf = (float)((double)w[(size_t)n * K + k] * (double)g[k]);
-            dw[(size_t)n * K + k] = wf;
-            cs += (double)wf;                         // column sum of the weights AS STORED: what the matrix cores will multiply
-            acc += (double)w[(size_t)n * K + k] * (double)be[k];
-          }
-          db[n] = (float)acc;
-          ds[n] = (float)cs;
+    {
+      const float* g = T("enc.after_norm.g").h; const float* be = T("enc.after_norm.b").h;
+      double gm = 0.0, bm = 0.0;
+      for (int k = 0; k < d; ++k) { gm = std::max(gm, (double)std::fabs(g[k])); bm = std::max(bm, (double)std::fabs(be[k])); }
+      worst = std::max(worst, std::sqrt((double)d) * gm + bm);                 // |enc| (keys / values source, CIF embeddings)
+    }
+    for (int i = 0; i < c.dec_layers; ++i) {
+      const std::string dp = "dec." + std::to_string(i) + ".";
+      ln_linear(dp + "ffn1.w", dp + "ffn1.b", dp + "norm1");
+      ln_linear(dp + "ffn2.w", "", dp + "ffn_norm");
+      ln_linear(dp + "q.w", dp + "q.b", dp + "norm3");
+      ln_linear(dp + "kv.w", dp + "kv.b", "enc.after_norm");
+    }
+    ln_linear("dec3.ffn1.w", "dec3.ffn1.b", "dec3.norm1");
+    ln_linear("dec3.ffn2.w", "", "dec3.ffn_norm");
+    ln_linear("dec.out.w", "dec.out.b", "dec.after_norm");
+    if (c.contextual) ln_linear("bias.dec.q.w", "bias.dec.q.b", "bias.dec.norm3");
+    w->static_bound = worst;
+    w->always_exact = !(worst < 32768.0);
+  }
+
+  // ---- the typed tables: what is read straight from the blob -------------------------------------------
+  auto lin = [&](const std::string& wn, const std::string& bn) {
+    const float* wd = T(wn).d;
+    return Linear{wd, bn.empty() ? nullptr : T(bn).d, scale_of(wd)};
+  };
+  auto norm = [&](const std::string& p) { return Norm{T(p + ".g").d, T(p + ".b").d}; };
+  auto dec_ffn = [&](const std::string& p) {
+    DecFfn f;
+    f.norm1 = norm(p + "norm1"); f.ffn_norm = norm(p + "ffn_norm");
+    f.ffn1 = lin(p + "ffn1.w", p + "ffn1.b"); f.ffn2 = lin(p + "ffn2.w", "");
+    return f;
+  };
+  w->cmvn_mean = T("cmvn.mean").d; w->cmvn_istd = T("cmvn.istd").d;
+  w->enc.resize((size_t)c.enc_layers);
+  for (int i = 0; i < c.enc_layers; ++i) {
+    const std::string p = "enc." + std::to_string(i) + ".";
+    EncLayer& L = w->enc[(size_t)i];
+    L.norm1 = norm(p + "norm1"); L.norm2 = norm(p + "norm2");
+    L.qkv = lin(p + "qkv.w", p + "qkv.b"); L.out = lin(p + "out.w", p + "out.b");
+    L.ffn1 = lin(p + "ffn1.w", p + "ffn1.b"); L.ffn2 = lin(p + "ffn2.w", p + "ffn2.b");
+    L.fsmn_w = T(p + "fsmn.w").d;
+  }
+  w->enc[0].qkv.w = w->w0qkv.f(); w->enc[0].qkv.scale = scale_of(w->w0qkv.p);
+  w->enc_after = norm("enc.after_norm");
+  w->pred.conv = Linear{w->predconv.f(), T("pred.conv.b").d, scale_of(w->predconv.p)};
+  w->pred.out_w = T("pred.out.w").d; w->pred.out_b = T("pred.out.b").d;
+  w->dec.resize((size_t)c.dec_layers);
+  for (int i = 0; i < c.dec_layers; ++i) {
+    const std::string p = "dec." + std::to_string(i) + ".";
+    DecLayer& L = w->dec[(size_t)i];
+    L.ffn = dec_ffn(p);
+    L.norm2 = norm(p + "norm2"); L.norm3 = norm(p + "norm3");
+    L.fsmn_w = T(p + "fsmn.w").d;
+    L.q = lin(p + "q.w", p + "q.b"); L.kv = lin(p + "kv.w", p + "kv.b"); L.out = lin(p + "out.w", p + "out.b");
+  }
+  w->dec3 = dec_ffn("dec3.");
+  w->dec_after = norm("dec.after_norm");
+  if (c.contextual) {
+    Contextual& b = w->bias;
+    b.embed_w = T("bias.embed.w").d;
+    b.lstm_ih = lin("bias.lstm.w_ih", "bias.lstm.b_ih"); b.lstm_hh = lin("bias.lstm.w_hh", "bias.lstm.b_hh");
+    b.norm3 = norm("bias.dec.norm3");
+    b.q = lin("bias.dec.q.w", "bias.dec.q.b"); b.kv = lin("bias.dec.kv.w", "bias.dec.kv.b"); b.out = lin("bias.dec.out.w", "bias.dec.out.b");
+    b.merge = lin("bias.out.w", "");
+  }
+
+  if (d == 4 * pfhip::kTileN) {   // LN-on-load needs the residual stream to be exactly four 128-column tiles wide
+    // W' = W * gamma[k], b' = b + W beta: LayerNorm's affine part folded into the GEMM that consumes it (offline path,
+    // large batches: forward_encoder).  Products in double, rounded once.
+    auto foldk = [&](const std::string& wn, const std::string& bn, const std::string& ln, int N, int K, float* dw, float* db, float* ds) {
+      const float* wh = T(wn).h; const float* bb = bn.empty() ? nullptr : T(bn).h;
+      const float* g = T(ln + ".g").h; const float* be = T(ln + ".b").h;
+      for (int n = 0; n < N; ++n) {
+        double acc = bb ? bb[n] : 0.0, cs = 0.0;
+        for (int k = 0; k < K; ++k) {
+          const float wf = (float)((double)wh[(size_t)n * K + k] * (double)g[k]);
+          dw[(size_t)n * K + k] = wf;
+          cs += (double)wf;                         // column sum of the weights AS STORED: what the matrix cores will multiply
+          acc += (double)wh[(size_t)n * K + k] * (double)be[k];
         }
-      };
-      auto fold = [&](const std::string& wn, const std::string& bn, const std::string& ln, int N, float* dw, float* db, float* ds) {
-        foldk(wn, bn, ln, N, d, dw, db, ds);
-      };
-      const int L = c.enc_layers;
+        db[n] = (float)acc;
+        ds[n] = (float)cs;
+      }
+    };
+    // entry i of a stack of folded weights [i][N][K] / [i][N]
+    auto folded = [&](const DevMem& fw, const DevMem& fb, const DevMem& fs, int i, int N, int K) {
+      const float* wd = fw.f() + (size_t)i * N * K;
+      return FoldLin{Linear{wd, fb.f() + (size_t)i * N, scale_of(wd)}, fs.f() + (size_t)i * N, Planes{}};
+    };
+    // a plane image [rows][cols] of `src` (scale baked in) at `at`, hi plane then lo plane; returns the image's bytes
+    auto split = [&](const Linear& src, int rows, int cols, const unsigned char* at, Planes* img) {
+      const size_t half = pfhip::plane_image_bytes(rows, cols);
+      unsigned char* hi = const_cast<unsigned char*>(at);
+      pfhip::launch_split_planes(src.w, cols, rows, rows, cols, src.scale, hi, hi + half, nullptr);
+      *img = Planes{hi, hi + half, src.scale};
+      return 2 * half;
+    };
+    const int L = c.enc_layers;
+    {
       std::vector<float> wq((size_t)L * 3 * d * d + (size_t)pfhip::kTileN * d, 0.f), bq((size_t)L * 3 * d + pfhip::kTileN, 0.f);
       std::vector<float> wf((size_t)L * c.ffn * d + (size_t)pfhip::kTileN * d, 0.f), bf((size_t)L * c.ffn + pfhip::kTileN, 0.f);
       std::vector<float> sq(bq.size(), 0.f), sf(bf.size(), 0.f);
       for (int i = 0; i < L; ++i) {
         const std::string ep = "enc." + std::to_string(i) + ".";
-        if (i > 0) fold(ep + "qkv.w", ep + "qkv.b", ep + "norm1", 3 * d, &wq[(size_t)i * 3 * d * d], &bq[(size_t)i * 3 * d], &sq[(size_t)i * 3 * d]);
-        fold(ep + "ffn1.w", ep + "ffn1.b", ep + "norm2", c.ffn, &wf[(size_t)i * c.ffn * d], &bf[(size_t)i * c.ffn], &sf[(size_t)i * c.ffn]);
+        if (i > 0) foldk(ep + "qkv.w", ep + "qkv.b", ep + "norm1", 3 * d, d, &wq[(size_t)i * 3 * d * d], &bq[(size_t)i * 3 * d], &sq[(size_t)i * 3 * d]);
+        foldk(ep + "ffn1.w", ep + "ffn1.b", ep + "norm2", c.ffn, d, &wf[(size_t)i * c.ffn * d], &bf[(size_t)i * c.ffn], &sf[(size_t)i * c.ffn]);
       }
-      st = upload(&m->d_lnw_qkv, wq);
-      if (!st) st = upload(&m->d_lnb_qkv, bq);
-      if (!st) st = upload(&m->d_lnw_ffn1, wf);
-      if (!st) st = upload(&m->d_lnb_ffn1, bf);
-      if (!st) st = upload(&m->d_lns_qkv, sq);
-      if (!st) st = upload(&m->d_lns_ffn1, sf);
-      if (st) return st;
+      HIP_TRY(w->lnw_qkv.upload(wq)); HIP_TRY(w->lnb_qkv.upload(bq));
+      HIP_TRY(w->lnw_ffn1.upload(wf)); HIP_TRY(w->lnb_ffn1.upload(bf));
+      HIP_TRY(w->lns_qkv.upload(sq)); HIP_TRY(w->lns_ffn1.upload(sf));
       for (int i = 0; i < L; ++i) {
-        reg_scale(m->d_lnw_qkv + (size_t)i * 3 * d * d, &wq[(size_t)i * 3 * d * d], (size_t)3 * d * d);
-        reg_scale(m->d_lnw_ffn1 + (size_t)i * c.ffn * d, &wf[(size_t)i * c.ffn * d], (size_t)c.ffn * d);
+        reg_scale(w->lnw_qkv.f() + (size_t)i * 3 * d * d, &wq[(size_t)i * 3 * d * d], (size_t)3 * d * d);
+        reg_scale(w->lnw_ffn1.f() + (size_t)i * c.ffn * d, &wf[(size_t)i * c.ffn * d], (size_t)c.ffn * d);
+        if (i > 0) w->enc[(size_t)i].qkv_f = folded(w->lnw_qkv, w->lnb_qkv, w->lns_qkv, i, 3 * d, d);
+        w->enc[(size_t)i].ffn1_f = folded(w->lnw_ffn1, w->lnb_ffn1, w->lns_ffn1, i, c.ffn, d);
       }
-      // The same four weights of every layer once more as fp16 plane images, pre-multiplied by their scale (gemm_p3.hip): on large
-      // batches the encoder's GEMMs stage both operands by LDS-DMA — the activations arrive as plane images from the kernel that
-      // produced them (enqueue_locked).  Same bytes as the fp32 copies (0.6 GB for Paraformer-large); PFHIP_PLANES=0 skips them.
-      static const bool planes_on = pfhip::env_on("PFHIP_PLANES");
-      if (planes_on && c.ffn % pfhip::kTileN == 0) {
-        const size_t iq = 2 * pfhip::plane_image_bytes(3 * d, d), io = 2 * pfhip::plane_image_bytes(d, d);
-        const size_t i1 = 2 * pfhip::plane_image_bytes(c.ffn, d), i2 = 2 * pfhip::plane_image_bytes(d, c.ffn);
-        m->wp_off_out = iq; m->wp_off_ffn1 = iq + io; m->wp_off_ffn2 = iq + io + i1;
-        const size_t per_layer = iq + io + i1 + i2;
-        if (hipMalloc((void**)&m->d_wplanes, per_layer * (size_t)L) != hipSuccess) {
-          // no room for the images (+70 % on the weight set): the fp32-operand kernels serve every batch size, nothing is lost
-          (void)hipGetLastError();
-          m->d_wplanes = nullptr;
+      w->enc_folded = true;
+    }
+    // The same four weights of every layer once more as fp16 plane images, pre-multiplied by their scale (gemm_p3.hip): on large
+    // batches the encoder's GEMMs stage both operands by LDS-DMA — the activations arrive as plane images from the kernel that
+    // produced them (forward_encoder).  Same bytes as the fp32 copies (0.6 GB for Paraformer-large); PFHIP_PLANES=0 skips them.
+    static const bool planes_on = pfhip::env_on("PFHIP_PLANES");
+    if (planes_on && c.ffn % pfhip::kTileN == 0) {
+      const size_t per_layer = 2 * (pfhip::plane_image_bytes(3 * d, d) + pfhip::plane_image_bytes(d, d) + pfhip::plane_image_bytes(c.ffn, d) +
+                                    pfhip::plane_image_bytes(d, c.ffn));
+      // no room for the images (+70 % on the weight set): the fp32-operand kernels serve every batch size, nothing is lost
+      if (w->wplanes.alloc(per_layer * (size_t)L) != hipSuccess) (void)hipGetLastError();
+      for (int i = 0; i < L && w->wplanes.p; ++i) {
+        EncLayer& E = w->enc[(size_t)i];
+        const unsigned char* at = w->wplanes.as<unsigned char>() + per_layer * (size_t)i;
+        if (i > 0) split(E.qkv_f.folded, 3 * d, d, at, &E.qkv_f.img);
+        at += 2 * pfhip::plane_image_bytes(3 * d, d);
+        at += split(E.out, d, d, at, &E.out_img);
+        at += split(E.ffn1_f.folded, c.ffn, d, at, &E.ffn1_f.img);
+        split(E.ffn2, d, c.ffn, at, &E.ffn2_img);
+      }
+      if (w->wplanes.p) {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        w->enc_planes = true;
+      }
+    }
+    if (c.dec_ffn % pfhip::kTileN == 0) {          // decoder FFNs: layers 0..dec_layers-1 and dec3 (the last entry)
+      const int DL = c.dec_layers + 1, f = c.dec_ffn;
+      std::vector<float> w1((size_t)DL * f * d + (size_t)pfhip::kTileN * d, 0.f), b1((size_t)DL * f + pfhip::kTileN, 0.f), s1(b1.size(), 0.f);
+      std::vector<float> w2((size_t)DL * d * f + (size_t)pfhip::kTileN * f, 0.f), b2((size_t)DL * d + pfhip::kTileN, 0.f), s2(b2.size(), 0.f);
+      std::vector<float> w3((size_t)DL * d * d + (size_t)pfhip::kTileN * d, 0.f), b3((size_t)DL * d + pfhip::kTileN, 0.f), s3(b3.size(), 0.f);
+      for (int i = 0; i < DL; ++i) {
+        const std::string dp = i < c.dec_layers ? "dec." + std::to_string(i) + "." : std::string("dec3.");
+        foldk(dp + "ffn1.w", dp + "ffn1.b", dp + "norm1", f, d, &w1[(size_t)i * f * d], &b1[(size_t)i * f], &s1[(size_t)i * f]);
+        foldk(dp + "ffn2.w", "", dp + "ffn_norm", d, f, &w2[(size_t)i * d * f], &b2[(size_t)i * d], &s2[(size_t)i * d]);
+        if (i < c.dec_layers) foldk(dp + "q.w", dp + "q.b", dp + "norm3", d, d, &w3[(size_t)i * d * d], &b3[(size_t)i * d], &s3[(size_t)i * d]);
+      }
+      HIP_TRY(w->dlnw3.upload(w3)); HIP_TRY(w->dlnb3.upload(b3)); HIP_TRY(w->dlns3.upload(s3));
+      HIP_TRY(w->dlnw1.upload(w1)); HIP_TRY(w->dlnb1.upload(b1)); HIP_TRY(w->dlns1.upload(s1));
+      HIP_TRY(w->dlnw2.upload(w2)); HIP_TRY(w->dlnb2.upload(b2)); HIP_TRY(w->dlns2.upload(s2));
+      for (int i = 0; i < DL; ++i) {
+        reg_scale(w->dlnw1.f() + (size_t)i * f * d, &w1[(size_t)i * f * d], (size_t)f * d);
+        reg_scale(w->dlnw2.f() + (size_t)i * d * f, &w2[(size_t)i * d * f], (size_t)d * f);
+        reg_scale(w->dlnw3.f() + (size_t)i * d * d, &w3[(size_t)i * d * d], (size_t)d * d);
+        DecFfn& F = i < c.dec_layers ? w->dec[(size_t)i].ffn : w->dec3;
+        F.ffn1_f = folded(w->dlnw1, w->dlnb1, w->dlns1, i, f, d);
+        F.ffn2_f = folded(w->dlnw2, w->dlnb2, w->dlns2, i, d, f);
+        if (i < c.dec_layers) w->dec[(size_t)i].q_f = folded(w->dlnw3, w->dlnb3, w->dlns3, i, d, d);
+      }
+      w->dec_folded = true;
+      // The decoder's large weights as plane images too (gemm_p3.hip; +0.2 GB for Paraformer-large): FFN1' / FFN2' with
+      // their LayerNorms folded in, the K/V projection of the encoder output and the output projection of the cross-attention
+      if (w->enc_planes) {
+        const size_t per = 2 * (pfhip::plane_image_bytes(f, d) + pfhip::plane_image_bytes(d, f) + pfhip::plane_image_bytes(2 * d, d) +
+                                pfhip::plane_image_bytes(d, d));
+        if (w->dwplanes.alloc(per * (size_t)DL) != hipSuccess) (void)hipGetLastError();
+        for (int i = 0; i < DL && w->dwplanes.p; ++i) {
+          DecFfn& F = i < c.dec_layers ? w->dec[(size_t)i].ffn : w->dec3;
+          const unsigned char* at = w->dwplanes.as<unsigned char>() + per * (size_t)i;
+          at += split(F.ffn1_f.folded, f, d, at, &F.ffn1_f.img);
+          at += split(F.ffn2_f.folded, d, f, at, &F.ffn2_f.img);
+          if (i < c.dec_layers) {
+            at += split(w->dec[(size_t)i].kv, 2 * d, d, at, &w->dec[(size_t)i].kv_img);
+            split(w->dec[(size_t)i].out, d, d, at, &w->dec[(size_t)i].out_img);
+          }
         }
-        for (int i = 0; i < L && m->d_wplanes; ++i) {
-          const std::string ep = "enc." + std::to_string(i) + ".";
-          unsigned char* base = m->d_wplanes + per_layer * (size_t)i;
-          const float* wqkv = m->d_lnw_qkv + (size_t)i * 3 * d * d;
-          const float* wff1 = m->d_lnw_ffn1 + (size_t)i * c.ffn * d;
-          const float* wout = m->W(ep + "out.w").d;
-          const float* wff2 = m->W(ep + "ffn2.w").d;
-          if (i > 0) pfhip::launch_split_planes(wqkv, d, 3 * d, 3 * d, d, m->w_scale_of(wqkv), base, base + iq / 2, nullptr);
-          pfhip::launch_split_planes(wout, d, d, d, d, m->w_scale_of(wout), base + m->wp_off_out, base + m->wp_off_out + io / 2, nullptr);
-          pfhip::launch_split_planes(wff1, d, c.ffn, c.ffn, d, m->w_scale_of(wff1), base + m->wp_off_ffn1, base + m->wp_off_ffn1 + i1 / 2, nullptr);
-          pfhip::launch_split_planes(wff2, c.ffn, d, d, c.ffn, m->w_scale_of(wff2), base + m->wp_off_ffn2, base + m->wp_off_ffn2 + i2 / 2, nullptr);
-        }
-        if (m->d_wplanes) {
+        if (w->dwplanes.p) {
           HIP_TRY(hipGetLastError());
           HIP_TRY(hipDeviceSynchronize());
-          m->wp_layer_bytes = per_layer;
+          w->dec_planes = true;
         }
       }
-      if (!st && c.dec_ffn % pfhip::kTileN == 0) {          // decoder FFNs: layers 0..dec_layers-1 and dec3 (the last entry)
-        const int DL = c.dec_layers + 1, f = c.dec_ffn;
-        std::vector<float> w1((size_t)DL * f * d + (size_t)pfhip::kTileN * d, 0.f), b1((size_t)DL * f + pfhip::kTileN, 0.f), s1(b1.size(), 0.f);
-        std::vector<float> w2((size_t)DL * d * f + (size_t)pfhip::kTileN * f, 0.f), b2((size_t)DL * d + pfhip::kTileN, 0.f), s2(b2.size(), 0.f);
-        std::vector<float> w3((size_t)DL * d * d + (size_t)pfhip::kTileN * d, 0.f), b3((size_t)DL * d + pfhip::kTileN, 0.f), s3(b3.size(), 0.f);
-        for (int i = 0; i < DL; ++i) {
-          const std::string dp = i < c.dec_layers ? "dec." + std::to_string(i) + "." : std::string("dec3.");
-          foldk(dp + "ffn1.w", dp + "ffn1.b", dp + "norm1", f, d, &w1[(size_t)i * f * d], &b1[(size_t)i * f], &s1[(size_t)i * f]);
-          foldk(dp + "ffn2.w", "", dp + "ffn_norm", d, f, &w2[(size_t)i * d * f], &b2[(size_t)i * d], &s2[(size_t)i * d]);
-          if (i < c.dec_layers) foldk(dp + "q.w", dp + "q.b", dp + "norm3", d, d, &w3[(size_t)i * d * d], &b3[(size_t)i * d], &s3[(size_t)i * d]);
-        }
-        st = upload(&m->d_dlnw3, w3);
-        if (!st) st = upload(&m->d_dlnb3, b3);
-        if (!st) st = upload(&m->d_dlns3, s3);
-        if (st) return st;
-        st = upload(&m->d_dlnw1, w1);
-        if (!st) st = upload(&m->d_dlnb1, b1);
-        if (!st) st = upload(&m->d_dlns1, s1);
-        if (!st) st = upload(&m->d_dlnw2, w2);
-        if (!st) st = upload(&m->d_dlnb2, b2);
-        if (!st) st = upload(&m->d_dlns2, s2);
-        if (st) return st;
-        for (int i = 0; i < DL; ++i) {
-          reg_scale(m->d_dlnw1 + (size_t)i * f * d, &w1[(size_t)i * f * d], (size_t)f * d);
-          reg_scale(m->d_dlnw2 + (size_t)i * d * f, &w2[(size_t)i * d * f], (size_t)d * f);
-          reg_scale(m->d_dlnw3 + (size_t)i * d * d, &w3[(size_t)i * d * d], (size_t)d * d);
-        }
-        // Round 4: the decoder's large weights as plane images too (gemm_p3.hip; +0.2 GB for Paraformer-large): FFN1' / FFN2' with
-        // their LayerNorms folded in, the K/V projection of the encoder output and the output projection of the cross-attention
-        if (m->wp_layer_bytes != 0) {
-          const size_t j1 = 2 * pfhip::plane_image_bytes(f, d), j2 = 2 * pfhip::plane_image_bytes(d, f);
-          const size_t jk = 2 * pfhip::plane_image_bytes(2 * d, d), jo = 2 * pfhip::plane_image_bytes(d, d);
-          m->dwp_off_ffn2 = j1; m->dwp_off_kv = j1 + j2; m->dwp_off_out = j1 + j2 + jk;
-          const size_t per = j1 + j2 + jk + jo;
-          if (hipMalloc((void**)&m->d_dwplanes, per * (size_t)DL) != hipSuccess) { (void)hipGetLastError(); m->d_dwplanes = nullptr; }
-          for (int i = 0; i < DL && m->d_dwplanes; ++i) {
-            unsigned char* base = m->d_dwplanes + per * (size_t)i;
-            const float* wf1 = m->d_dlnw1 + (size_t)i * f * d;
-            const float* wf2 = m->d_dlnw2 + (size_t)i * d * f;
-            pfhip::launch_split_planes(wf1, d, f, f, d, m->w_scale_of(wf1), base, base + j1 / 2, nullptr);
-            pfhip::launch_split_planes(wf2, f, d, d, f, m->w_scale_of(wf2), base + m->dwp_off_ffn2, base + m->dwp_off_ffn2 + j2 / 2, nullptr);
-            if (i < c.dec_layers) {
-              const std::string dp = "dec." + std::to_string(i) + ".";
-              const float* wkv = m->W(dp + "kv.w").d;
-              const float* wo = m->W(dp + "out.w").d;
-              pfhip::launch_split_planes(wkv, d, 2 * d, 2 * d, d, m->w_scale_of(wkv), base + m->dwp_off_kv, base + m->dwp_off_kv + jk / 2, nullptr);
-              pfhip::launch_split_planes(wo, d, d, d, d, m->w_scale_of(wo), base + m->dwp_off_out, base + m->dwp_off_out + jo / 2, nullptr);
-            }
-          }
-          if (m->d_dwplanes) {
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipDeviceSynchronize());
-            m->dwp_layer_bytes = per;
-          }
-        }
-      }
-      if (st) return st;
     }
-    if (c.dec_layers > 0) {     // streaming latency path: all layers' K/V projections of a window in one launch (stream.cpp)
-      std::vector<float> kw((size_t)c.dec_layers * 2 * d * d + (size_t)pfhip::kTileN * d, 0.f), kb((size_t)c.dec_layers * 2 * d + pfhip::kTileN, 0.f);
-      for (int i = 0; i < c.dec_layers; ++i) {
-        const std::string dp = "dec." + std::to_string(i) + ".";
-        std::memcpy(&kw[(size_t)i * 2 * d * d], m->W(dp + "kv.w").h, sizeof(float) * 2 * d * d);
-        std::memcpy(&kb[(size_t)i * 2 * d], m->W(dp + "kv.b").h, sizeof(float) * 2 * d);
-      }
-      st = upload(&m->d_kv_all_w, kw);
-      if (!st) st = upload(&m->d_kv_all_b, kb);
-      if (st) return st;
-      reg_scale(m->d_kv_all_w, kw.data(), kw.size());
+  }
+  if (c.dec_layers > 0) {     // streaming latency path: all layers' K/V projections of a window in one launch (stream.cpp)
+    std::vector<float> kw((size_t)c.dec_layers * 2 * d * d + (size_t)pfhip::kTileN * d, 0.f), kb((size_t)c.dec_layers * 2 * d + pfhip::kTileN, 0.f);
+    for (int i = 0; i < c.dec_layers; ++i) {
+      const std::string dp = "dec." + std::to_string(i) + ".";
+      std::memcpy(&kw[(size_t)i * 2 * d * d], T(dp + "kv.w").h, sizeof(float) * 2 * d * d);
+      std::memcpy(&kb[(size_t)i * 2 * d], T(dp + "kv.b").h, sizeof(float) * 2 * d);
     }
-    std::vector<float> vb((size_t)m->vocab_pad, 0.f);
-    std::memcpy(vb.data(), m->W("dec.out.b").h, sizeof(float) * c.vocab);
-    st = upload(&m->d_vocab_bias, vb);
-    if (st) return st;
+    HIP_TRY(w->kv_all_w.upload(kw));
+    HIP_TRY(w->kv_all_b.upload(kb));
+    reg_scale(w->kv_all_w.p, kw.data(), kw.size());
+    w->kv_all = Linear{w->kv_all_w.f(), w->kv_all_b.f(), scale_of(w->kv_all_w.p)};
+  }
+  {
+    std::vector<float> vb((size_t)w->vocab_pad, 0.f);
+    std::memcpy(vb.data(), T("dec.out.b").h, sizeof(float) * c.vocab);
+    HIP_TRY(w->vocab_bias.upload(vb));
+    w->dec_out = Linear{T("dec.out.w").d, w->vocab_bias.f(), scale_of(T("dec.out.w").d)};
   }
   if (c.timestamp) {
     // ConvTranspose1d(d, d, k = stride = 3): out[3t + j][co] = b[co] + sum_ci x[t][ci] * w[ci][co][j]  ==  one GEMM with
     // the weight laid out [j*d + co][ci]; its [T, 3d] result IS the [3T, d] upsampled sequence.
-    const Tensor& uw = m->W("pred.up.w");
+    const Tensor& uw = T("pred.up.w");
     std::vector<float> w2((size_t)3 * d * d), b2((size_t)3 * d);
     for (int ci = 0; ci < d; ++ci)
       for (int co = 0; co < d; ++co)
         for (int j = 0; j < 3; ++j) w2[((size_t)j * d + co) * d + ci] = uw.h[((size_t)ci * d + co) * 3 + j];
-    for (int j = 0; j < 3; ++j) std::memcpy(&b2[(size_t)j * d], m->W("pred.up.b").h, sizeof(float) * d);
-    pfhip_status st = upload(&m->d_up_w, w2);
-    if (!st) st = upload(&m->d_up_b, b2);
-    if (st) return st;
-    reg_scale(m->d_up_w, w2.data(), w2.size());
+    for (int j = 0; j < 3; ++j) std::memcpy(&b2[(size_t)j * d], T("pred.up.b").h, sizeof(float) * d);
+    HIP_TRY(w->up_w.upload(w2));
+    HIP_TRY(w->up_b.upload(b2));
+    reg_scale(w->up_w.p, w2.data(), w2.size());
     // both directions' input projections in one GEMM (N = 8d), b_ih + b_hh folded; recurrent weights [2][4d][d]
     std::vector<float> wih((size_t)8 * d * d), bih((size_t)8 * d), whh((size_t)8 * d * d);
     int dir = 0;
     for (const char* sfx : {"", "_r"}) {
-      std::memcpy(&wih[(size_t)dir * 4 * d * d], m->W(std::string("pred.blstm.w_ih") + sfx).h, sizeof(float) * 4 * d * d);
-      std::memcpy(&whh[(size_t)dir * 4 * d * d], m->W(std::string("pred.blstm.w_hh") + sfx).h, sizeof(float) * 4 * d * d);
-      const float* bi = m->W(std::string("pred.blstm.b_ih") + sfx).h;
-      const float* bh = m->W(std::string("pred.blstm.b_hh") + sfx).h;
+      std::memcpy(&wih[(size_t)dir * 4 * d * d], T(std::string("pred.blstm.w_ih") + sfx).h, sizeof(float) * 4 * d * d);
+      std::memcpy(&whh[(size_t)dir * 4 * d * d], T(std::string("pred.blstm.w_hh") + sfx).h, sizeof(float) * 4 * d * d);
+      const float* bi = T(std::string("pred.blstm.b_ih") + sfx).h;
+      const float* bh = T(std::string("pred.blstm.b_hh") + sfx).h;
       for (int k = 0; k < 4 * d; ++k) bih[(size_t)dir * 4 * d + k] = bi[k] + bh[k];
       ++dir;
     }
-    if (!st) st = upload(&m->d_wih, wih);
-    if (!st) st = upload(&m->d_bih, bih);
-    if (!st) st = upload(&m->d_whh, whh);
-    if (st) return st;
-    reg_scale(m->d_wih, wih.data(), wih.size());
-    m->out2_b = m->W("pred.out2.b").h[0];
+    HIP_TRY(w->wih.upload(wih));
+    HIP_TRY(w->bih.upload(bih));
+    HIP_TRY(w->whh.upload(whh));
+    reg_scale(w->wih.p, wih.data(), wih.size());
+    TimestampHead& ts = w->ts;
+    ts.up = Linear{w->up_w.f(), w->up_b.f(), scale_of(w->up_w.p)};
+    ts.ih = Linear{w->wih.f(), w->bih.f(), scale_of(w->wih.p)};
+    ts.whh = w->whh.f();
+    ts.out2_w = T("pred.out2.w").d;
+    ts.out2_b = T("pred.out2.b").h[0];
   }
   // ---- front-end tables ------------------------------------------------------------------------------
   {
-    pfhip_detail::FrontendTables ft;
-    pfhip_status st = pfhip_detail::build_frontend_tables(c.n_mels, c.sample_rate, &ft);
+    pfhip_status st = pfhip_detail::build_frontend_tables(c.n_mels, c.sample_rate, &w->ft);
     if (st) return st;
-    m->d_window = ft.d_window; m->d_tw = ft.d_tw; m->d_mel_off = ft.d_mel_off; m->d_mel_size = ft.d_mel_size;
-    m->d_mel_w = ft.d_mel_w;
-    const int half = m->feat_dim / 2;
+    const int half = w->feat_dim / 2;
     std::vector<float> inv(half);
     // paraformer-online.cpp:247-252: float scale, exp() in double of a float argument, stored to float
-    const float scale = m->feat_dim == 560 ? -0.0330119726594128f : (float)(-std::log(10000.0) / (half - 1));
+    const float scale = w->feat_dim == 560 ? -0.0330119726594128f : (float)(-std::log(10000.0) / (half - 1));
     for (int i = 0; i < half; ++i) inv[i] = (float)exp((double)(i * scale));
-    if ((st = upload(&m->d_inv_ts, inv))) return st;
+    HIP_TRY(w->inv_ts_mem.upload(inv));
+    w->inv_ts = w->inv_ts_mem.f();
   }
+  m->weights = std::move(w);
   {
     pfhip_status st = create_streams(m.get());
     if (st) return st;
   }
-  for (auto& kv : m->t) kv.second.h = nullptr;
   *out = m.release();
   return PFHIP_OK;
 }
-
-// every device pointer of a model that is read-only after build_model: what an execution context borrows and only the owner frees
-#define PFHIP_WEIGHT_PTRS(X)                                                                                                  \
-  X(d_blob) X(d_w0qkv) X(d_predconv) X(d_vocab_bias) X(d_kv_all_w) X(d_kv_all_b) X(d_lnw_qkv) X(d_lnb_qkv) X(d_lnw_ffn1)     \
-  X(d_lnb_ffn1) X(d_lns_qkv) X(d_lns_ffn1) X(d_dlnw1) X(d_dlnb1) X(d_dlns1) X(d_dlnw2) X(d_dlnb2) X(d_dlns2) X(d_dlnw3)        \
-  X(d_dlnb3) X(d_dlns3) X(d_up_w) X(d_up_b) X(d_wih) X(d_bih) X(d_whh) X(d_window) X(d_tw) X(d_mel_off) X(d_mel_size)         \
-  X(d_mel_w) X(d_inv_ts) X(d_wplanes) X(d_dwplanes)
 
 pfhip_status create_streams(pfhip_model* m) {
   HIP_TRY(hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking));
   HIP_TRY(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreateWithFlags(&m->ev_enc_ready, hipEventDisableTiming));
-  m->ev_kv.resize((size_t)m->cfg.dec_layers, nullptr);
+  m->ev_kv.resize((size_t)m->weights->cfg.dec_layers, nullptr);
   for (auto& e : m->ev_kv) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   return PFHIP_OK;
 }
@@ -541,25 +585,41 @@ pfhip_status build_context(pfhip_model* owner, pfhip_model** out) {
   HIP_TRY(hipSetDevice(owner->device));
   std::unique_ptr<pfhip_model> m(new pfhip_model);
   m->device = owner->device;
-  m->cfg = owner->cfg;
-  m->feat_dim = owner->feat_dim; m->feat_pad = owner->feat_pad; m->vocab_pad = owner->vocab_pad;
-  m->t = owner->t;
-  m->wscale = owner->wscale;
-  m->out2_b = owner->out2_b;
-  m->static_bound = owner->static_bound; m->always_exact = owner->always_exact;
-  m->wp_layer_bytes = owner->wp_layer_bytes; m->wp_off_out = owner->wp_off_out; m->wp_off_ffn1 = owner->wp_off_ffn1;
-  m->wp_off_ffn2 = owner->wp_off_ffn2;
-  m->dwp_layer_bytes = owner->dwp_layer_bytes; m->dwp_off_ffn2 = owner->dwp_off_ffn2; m->dwp_off_kv = owner->dwp_off_kv;
-  m->dwp_off_out = owner->dwp_off_out;
-#define X(f) m->f = owner->f;
-  PFHIP_WEIGHT_PTRS(X)
-#undef X
+  m->weights = owner->weights;
   m->weights_of = owner;
   pfhip_status st = create_streams(m.get());
-  if (st) { pfhip_destroy(m.release()); return st; }
+  if (st) return st;
   *out = m.release();
   return PFHIP_OK;
 }
+
+}  // namespace
+
+// Everything pfhip_destroy does: the device is set and idle before any member gives its memory back; the workspace, the pinned
+// staging, the hotword bank's book-keeping and the (shared) weights are then freed by their own destructors.
+pfhip_model::~pfhip_model() {
+  for (pfhip_model* r : replicas) delete r;
+  for (pfhip_model* cx : contexts) delete cx;
+  (void)hipSetDevice(device);
+  (void)hipDeviceSynchronize();
+  if (hwbank) {               // the device's hotword bank (unused on a context)
+    HwBankDev& D = *hwbank;
+    for (size_t i = 0; i < D.bank.id_count(); ++i)
+      if (D.bank.entry((int)i).ready) (void)hipEventDestroy(static_cast<hipEvent_t>(D.bank.entry((int)i).ready));
+    if (D.arena) (void)hipFree(D.arena);
+  }
+  for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+  if (own_stream) (void)hipStreamDestroy(own_stream);
+  if (side_stream) (void)hipStreamDestroy(side_stream);
+  if (ev_enc_ready) (void)hipEventDestroy(ev_enc_ready);
+  if (ev_ts_in) (void)hipEventDestroy(ev_ts_in);
+  if (ev_ts_out) (void)hipEventDestroy(ev_ts_out);
+  if (blstm_stream) (void)hipStreamDestroy(blstm_stream);
+  for (hipEvent_t e : ev_kv) if (e) (void)hipEventDestroy(e);
+}
+
+namespace {
+using namespace pfhip_detail;
 
 pfhip_status read_file(const char* path, std::vector<char>& out) {
   std::ifstream f(path, std::ios::binary | std::ios::ate);
@@ -577,29 +637,45 @@ pfhip_status read_file(const char* path, std::vector<char>& out) {
 struct ForwardCtx {
   pfhip::LaunchCtx saved;
   explicit ForwardCtx(pfhip_model* m) : saved(pfhip::launch_ctx()) {
-    pfhip::launch_ctx().exact = m->exact_rerun || m->always_exact;
+    pfhip::launch_ctx().exact = m->exact_rerun || m->weights->always_exact;
     pfhip::launch_ctx().range_flag = m->d_range_flag;
   }
   ~ForwardCtx() { pfhip::launch_ctx() = saved; }
 };
 
+// The offline forward is enqueued in three parts, cut where its data already lives in pfhip_model: front end + encoder (up to `enc`),
+// predictor + CIF + the token-count sync (n_fires, ML), decoder + vocabulary projection (`logits`).  What crosses the cuts besides
+// that state are the path decisions:
+struct ForwardPaths {
+  bool planes = false;          // the encoder ran on plane-image operands (the decoder may only then)
+};
+// activation plane images: hi plane then lo plane in one workspace buffer
+struct Img { unsigned char* hi; unsigned char* lo; };
+Img img_of(const Buf& b, size_t plane_bytes) { return {static_cast<unsigned char*>(b.p), static_cast<unsigned char*>(b.p) + plane_bytes}; }
+
 // d_pcm: the packed device buffer in either sample format (internal.h PcmView); sample_off counts samples of that format
-pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples, int B, hipStream_t s,
-                          bool feats_only);
+pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples, int B, hipStream_t s,
+                             bool feats_only, ForwardPaths* paths);
+pfhip_status forward_cif(pfhip_model* m, hipStream_t s);
+pfhip_status forward_decoder(pfhip_model* m, hipStream_t s, const ForwardPaths& paths);
+
 pfhip_status enqueue_locked(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                             int B, hipStream_t s, bool feats_only) {
   m->d_range_flag = nullptr;                          // until the metadata upload places it
-  const pfhip::LaunchCtx saved = pfhip::launch_ctx();
-  pfhip::launch_ctx().exact = m->exact_rerun || m->always_exact;
-  const pfhip_status st = enqueue_body(m, d_pcm, sample_off, n_samples, B, s, feats_only);
-  pfhip::launch_ctx() = saved;
-  return st;
+  ForwardCtx fc(m);
+  ForwardPaths paths;
+  pfhip_status st = forward_encoder(m, d_pcm, sample_off, n_samples, B, s, feats_only, &paths);
+  if (st || feats_only || m->M == 0) return st;
+  st = forward_cif(m, s);
+  if (st || m->ML == 0) return st;
+  return forward_decoder(m, s, paths);
 }
 
-pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
-                          int B, hipStream_t s, bool feats_only) {
-  const Config& c = m->cfg;
-  const int d = c.d_model, FD = m->feat_dim, FP = m->feat_pad;
+pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
+                             int B, hipStream_t s, bool feats_only, ForwardPaths* paths) {
+  const ModelWeights& w = *m->weights;
+  const Config& c = w.cfg;
+  const int d = c.d_model, FD = w.feat_dim, FP = w.feat_pad;
   HIP_TRY(hipSetDevice(m->device));
   m->B = B; m->M = 0; m->ML = 0; m->maxT = 0; m->maxL = 0; m->have_logp = false; m->have_ts = false;
   m->T.assign(B, 0); m->row_off.assign(B, 0); m->n_fires.assign(B, 0); m->token_num.assign(B, 0); m->tok_off.assign(B, 0);
@@ -619,15 +695,10 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
 
   // ---- metadata: one pinned staging buffer, one H2D copy ---------------------------------------------
   const size_t n_ints = (size_t)2 * B /*sample_off as int64*/ + (B + 1) + 3 * (size_t)B + 2 * (size_t)M + 8;
-  if (n_ints * 4 > m->h_meta_cap) {
-    if (m->h_meta) HIP_TRY(hipHostFree(m->h_meta));
-    m->h_meta = nullptr; m->h_meta_cap = 0;
-    HIP_TRY(hipHostMalloc(&m->h_meta, n_ints * 4 * 2, hipHostMallocDefault));
-    m->h_meta_cap = n_ints * 4 * 2;
-  }
+  HIP_TRY(m->h_meta.ensure(n_ints * 4));
   HIP_TRY(m->meta.ensure(n_ints * 4));
   {
-    int* hm = static_cast<int*>(m->h_meta);
+    int* hm = m->h_meta.i();
     int* dm = m->meta.i();
     size_t o = 0;
     std::memcpy(hm + o, sample_off, sizeof(int64_t) * B); m->m_sample_off = reinterpret_cast<int64_t*>(dm + o); o += 2 * (size_t)B;
@@ -670,12 +741,7 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     HIP_TRY(m->enc.ensure((size_t)Mp * d * 4));
     HIP_TRY(m->alphas.ensure((size_t)Mp * 4));
     HIP_TRY(m->counts.ensure((size_t)2 * B * 4));
-    if ((size_t)2 * B * 4 > m->h_counts_cap) {
-      if (m->h_counts) HIP_TRY(hipHostFree(m->h_counts));
-      m->h_counts = nullptr; m->h_counts_cap = 0;
-      HIP_TRY(hipHostMalloc((void**)&m->h_counts, (size_t)2 * B * 4 * 2, hipHostMallocDefault));
-      m->h_counts_cap = (size_t)2 * B * 4 * 2;
-    }
+    HIP_TRY(m->h_counts.ensure((size_t)2 * B * 4));
   }
 
   // ---- a2+a3: fbank -> LFR -> CMVN -----------------------------------------------------------------------
@@ -683,8 +749,7 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     double in_bytes = 0;
     for (int b = 0; b < B; ++b) in_bytes += (double)d_pcm.sample_bytes() * n_samples[b];
     Scope sc(m, s, K_FBANK, 0, in_bytes + 4.0 * FD * M);
-    pfhip::FbankTables tb{m->d_window, m->d_tw, m->d_mel_off, m->d_mel_size, m->d_mel_w,
-                          m->W("cmvn.mean").d, m->W("cmvn.istd").d};
+    const pfhip::FbankTables tb = w.ft.fbank(w.cmvn_mean, w.cmvn_istd);
     if (d_pcm.s16)
       pfhip::launch_fbank_lfr_cmvn(d_pcm.i16(), m->m_sample_off, m->m_frame_off, m->m_nframes, m->m_row_off, B,
                                    total_frames, tb, m->feats.f(), s);
@@ -697,7 +762,7 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
   // ---- a4: encoder -------------------------------------------------------------------------------------------
   {
     Scope sc(m, s, K_OTHER, 0, 4.0 * M * (FD + FP));
-    pfhip::launch_embed(m->feats.f(), FD, m->x0.f(), FP, m->m_row_pos, M, m->d_inv_ts, sqrtf((float)d), s);
+    pfhip::launch_embed(m->feats.f(), FD, m->x0.f(), FP, m->m_row_pos, M, w.inv_ts, sqrtf((float)d), s);
   }
   const int hd = d / c.n_head;                    // 128, or 80 (the small Paraformer)
   const float att_scale = 1.0f / sqrtf((float)hd);
@@ -710,36 +775,34 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
   // gamma / beta folded into its weights (build_model).  One [M, 512] write + read and one launch per LayerNorm less.
   // (not on the exact kernels: the fold's cancellation is a property of fp32 accumulation, not of the planes — kernels.h kLnOffsetMax —
   // and the exact forward is what a batch flagged for its offset is redone on)
-  const bool fuse_ln = m->d_lnw_qkv != nullptr && pfhip::gemm_x6_ln_ok(M) && !pfhip::launch_ctx().exact;
+  const bool fuse_ln = w.enc_folded && pfhip::gemm_x6_ln_ok(M) && !pfhip::launch_ctx().exact;
   const bool mem_in_x = pfhip::attention_fsmn_is_fused(m->maxT, hd);
   if (fuse_ln) HIP_TRY(m->lnstats.ensure((size_t)Mp * 4 * 2 * 4));
-  auto gemm_ln = [&](const float* A, const float* Wd, int N, float* Cd, int ldc, const float* bias, const float* R1, const float* R2,
+  auto gemm_ln = [&](const float* A, const Linear& W, int N, float* Cd, int ldc, const float* R1, const float* R2,
                      bool relu, const float* ln_colsum, bool stats_out, int K) {
     Scope sc(m, s, K_GEMM, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    pfhip::launch_gemm_f32_x6_ln(A, K, Wd, K, Cd, ldc, bias, R1, d, R2, d, M, N, K, relu, ln_colsum ? m->lnstats.f() : nullptr, 4,
-                                 ln_colsum, stats_out ? m->lnstats.f() : nullptr, s, m->w_scale_of(Wd));
+    pfhip::launch_gemm_f32_x6_ln(A, K, W.w, K, Cd, ldc, W.b, R1, d, R2, d, M, N, K, relu, ln_colsum ? m->lnstats.f() : nullptr, 4,
+                                 ln_colsum, stats_out ? m->lnstats.f() : nullptr, s, W.scale);
   };
   // Large batches, second step: the four big GEMMs of a layer take BOTH operands as fp16 plane images staged by LDS-DMA
   // (gemm_p3.hip) — weights split once at load, activations written as planes by the kernel that produces them (the attention's
   // context, the residual stream out of the output projection and FFN2, FFN1's hidden activation).  The fp32 residual stream and
   // the QKV rows stay fp32 (residual adds, the attention's own staging).  Same arithmetic as the in-loop split of gemm_x3.hip.
-  struct Img { unsigned char* hi; unsigned char* lo; };
   Img ctxP{nullptr, nullptr}, xP{nullptr, nullptr}, hP{nullptr, nullptr};
   // Below ~3500 rows the fp32-operand kernels stay: measured with the 64-row tile of gemm_p3.hip, 16 x 30 s = 8000 rows 16.95 ms
   // against 17.60, 8 x 30 s = 4000 rows 12.01 against 12.17, 4 x 30 s = 2000 rows 10.08 against 9.94 (PFHIP_PLANES_MIN_ROWS moves the
   // switch, PFHIP_PLANES=0 at load removes the path)
   static const int planes_min_rows = pfhip::env_int("PFHIP_PLANES_MIN_ROWS", 3500);
-  const bool planes = fuse_ln && mem_in_x && m->wp_layer_bytes != 0 && M >= planes_min_rows && pfhip::gemm_f16_planes_form() &&
+  const bool planes = fuse_ln && mem_in_x && w.enc_planes && M >= planes_min_rows && pfhip::gemm_f16_planes_form() &&
                       pfhip::attention_planes_ok(m->maxT, hd);
+  paths->planes = planes;
   if (planes) {
     ++m->plane_forwards;
     const size_t pd = pfhip::plane_image_bytes(Mp, d), pf = pfhip::plane_image_bytes(Mp, c.ffn);
     HIP_TRY(m->ctxP.ensure(2 * pd));
     HIP_TRY(m->xP.ensure(2 * pd));
     HIP_TRY(m->hP.ensure(2 * pf));
-    ctxP = {static_cast<unsigned char*>(m->ctxP.p), static_cast<unsigned char*>(m->ctxP.p) + pd};
-    xP = {static_cast<unsigned char*>(m->xP.p), static_cast<unsigned char*>(m->xP.p) + pd};
-    hP = {static_cast<unsigned char*>(m->hP.p), static_cast<unsigned char*>(m->hP.p) + pf};
+    ctxP = img_of(m->ctxP, pd); xP = img_of(m->xP, pd); hP = img_of(m->hP, pf);
   }
   // Third step (round 4, opt-in: PFHIP_KV_PLANES=1): layers 1.. hand K and V to the attention as row-major fp16 planes written by the
   // QKV projection's epilogue (the bytes of the fp32 columns they replace) and staged without the in-loop split (attention_p3.hip); Q
@@ -752,50 +815,35 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     ++m->kvplane_forwards;
     const size_t pk = (size_t)Mp * 2 * d * 2;
     HIP_TRY(m->kvP.ensure(2 * pk));
-    kvP = {static_cast<unsigned char*>(m->kvP.p), static_cast<unsigned char*>(m->kvP.p) + pk};
+    kvP = img_of(m->kvP, pk);
   }
-  struct WImg { const unsigned char* hi; const unsigned char* lo; float scale; };
-  auto wimg = [&](int layer, int which) -> WImg {          // 0 qkv', 1 out, 2 ffn1', 3 ffn2
-    const unsigned char* base = m->d_wplanes + m->wp_layer_bytes * (size_t)layer;
-    const std::string ep = "enc." + std::to_string(layer) + ".";
-    switch (which) {
-      case 0: return {base, base + pfhip::plane_image_bytes(3 * d, d), m->w_scale_of(m->d_lnw_qkv + (size_t)layer * 3 * d * d)};
-      case 1: return {base + m->wp_off_out, base + m->wp_off_out + pfhip::plane_image_bytes(d, d), m->w_scale_of(m->W(ep + "out.w").d)};
-      case 2: return {base + m->wp_off_ffn1, base + m->wp_off_ffn1 + pfhip::plane_image_bytes(c.ffn, d),
-                      m->w_scale_of(m->d_lnw_ffn1 + (size_t)layer * c.ffn * d)};
-      default: return {base + m->wp_off_ffn2, base + m->wp_off_ffn2 + pfhip::plane_image_bytes(d, c.ffn), m->w_scale_of(m->W(ep + "ffn2.w").d)};
-    }
-  };
   // C (fp32, may be null) and / or plane images of C; LayerNorm folded in when ln_colsum is given (statistics in lnstats)
-  auto gemm_pl = [&](const Img& A, const WImg& W, int N, int K, float* Cd, int ldc, const Img* P, const float* bias, const float* R1, bool relu,
+  auto gemm_pl = [&](const Img& A, const Planes& W, int N, int K, float* Cd, int ldc, const Img* P, const float* bias, const float* R1, bool relu,
                      const float* ln_colsum, bool stats_out) {
     Scope sc(m, s, K_GEMM, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
     pfhip::launch_gemm_p3(A.hi, A.lo, Mp, W.hi, W.lo, N, W.scale, Cd, ldc, P ? P->hi : nullptr, P ? P->lo : nullptr, Mp, bias, R1, d, M, N, K, relu,
                           ln_colsum ? m->lnstats.f() : nullptr, 4, ln_colsum, stats_out ? m->lnstats.f() : nullptr, 4, s);
   };
   for (int i = 0; i < c.enc_layers; ++i) {
-    const std::string p = "enc." + std::to_string(i) + ".";
+    const EncLayer& L = w.enc[(size_t)i];
     const bool first = i == 0;
     const float* xin = first ? m->x0.f() : x;
     const int ldin = first ? FP : d, Din = first ? FD : d, Kp = first ? FP : d;
     if (kv_planes && !first) {
       // LayerNorm(x) Wqkv'^T on the plane images of x: Q as fp32 rows of qkv, K | V as row-major planes
       Scope sc(m, s, K_GEMM, 2.0 * M * (double)(3 * d) * d, 4.0 * ((double)M * d + 3.0 * d * d + (double)M * 3 * d));
-      const WImg W = wimg(i, 0);
+      const Planes& W = L.qkv_f.img;
       pfhip::launch_gemm_p3(xP.hi, xP.lo, Mp, W.hi, W.lo, 3 * d, W.scale, m->qkv.f(), 3 * d, kvP.hi, kvP.lo, 2 * d,
-                            m->d_lnb_qkv + (size_t)i * 3 * d, nullptr, 0, M, 3 * d, d, false, m->lnstats.f(), 4, m->d_lns_qkv + (size_t)i * 3 * d,
+                            L.qkv_f.folded.b, nullptr, 0, M, 3 * d, d, false, m->lnstats.f(), 4, L.qkv_f.colsum,
                             nullptr, 4, s, 0, d);
     } else if (planes && !first) {
       // LayerNorm(x) Wqkv'^T on the plane images of x that the previous layer's FFN2 left
-      gemm_pl(xP, wimg(i, 0), 3 * d, d, m->qkv.f(), 3 * d, nullptr, m->d_lnb_qkv + (size_t)i * 3 * d, nullptr, false,
-              m->d_lns_qkv + (size_t)i * 3 * d, false);
+      gemm_pl(xP, L.qkv_f.img, 3 * d, d, m->qkv.f(), 3 * d, nullptr, L.qkv_f.folded.b, nullptr, false, L.qkv_f.colsum, false);
     } else if (fuse_ln && !first) {
-      gemm_ln(x, m->d_lnw_qkv + (size_t)i * 3 * d * d, 3 * d, m->qkv.f(), 3 * d, m->d_lnb_qkv + (size_t)i * 3 * d, nullptr, nullptr, false,
-              m->d_lns_qkv + (size_t)i * 3 * d, false, d);
+      gemm_ln(x, L.qkv_f.folded, 3 * d, m->qkv.f(), 3 * d, nullptr, nullptr, false, L.qkv_f.colsum, false, d);
     } else {
-      lnorm(m, s, xin, ldin, m->y.f(), Kp, p + "norm1", M, Din, Kp);
-      gemm(m, s, m->y.f(), Kp, first ? m->d_w0qkv : m->W(p + "qkv.w").d, 3 * d, Kp, Din, m->qkv.f(), 3 * d,
-           m->W(p + "qkv.b").d, nullptr, 0, nullptr, 0, M, false);
+      lnorm(m, s, xin, ldin, m->y.f(), Kp, L.norm1, M, Din, Kp);
+      gemm(m, s, m->y.f(), Kp, L.qkv, 3 * d, Kp, Din, m->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, M, false);
     }
     {
       // FSMN memory of V + self-attention: one launch where the BF16 attention kernel runs (attention_x6.hip), else two
@@ -804,52 +852,51 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
       // has no residual), so the bandwidth-bound output projection reads ONE residual
       if (kv_planes && !first)
         pfhip::launch_attention_p3(m->qkv.f(), 3 * d, kvP.hi, kvP.lo, 2 * d, d, nullptr, 0, m->m_row_off, m->m_len, m->m_row_off, m->m_len, B,
-                                   c.n_head, m->maxT, att_scale, s, m->W(p + "fsmn.w").d, x, d, true, ctxP.hi, ctxP.lo, Mp);
+                                   c.n_head, m->maxT, att_scale, s, L.fsmn_w, x, d, true, ctxP.hi, ctxP.lo, Mp);
       else
       pfhip::launch_attention_fsmn(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, m->m_row_off,
-                                   m->m_len, B, c.n_head, m->maxT, att_scale, m->W(p + "fsmn.w").d, mem_in_x ? x : m->mem.f(), d, s,
+                                   m->m_len, B, c.n_head, m->maxT, att_scale, L.fsmn_w, mem_in_x ? x : m->mem.f(), d, s,
                                    mem_in_x && !first, planes ? ctxP.hi : nullptr, planes ? ctxP.lo : nullptr, Mp, hd);
     }
+    const bool more = i + 1 < c.enc_layers;
     if (planes) {
       // x = ctx Wo^T + b + (x + memory): fp32 for the residual stream, plane images for FFN1, row statistics for its LayerNorm
-      gemm_pl(ctxP, wimg(i, 1), d, d, x, d, &xP, m->W(p + "out.b").d, x, false, nullptr, true);
-      gemm_pl(xP, wimg(i, 2), c.ffn, d, nullptr, 0, &hP, m->d_lnb_ffn1 + (size_t)i * c.ffn, nullptr, true, m->d_lns_ffn1 + (size_t)i * c.ffn, false);
-      const bool more = i + 1 < c.enc_layers;
-      gemm_pl(hP, wimg(i, 3), d, c.ffn, x, d, more ? &xP : nullptr, m->W(p + "ffn2.b").d, x, false, nullptr, more);
+      gemm_pl(ctxP, L.out_img, d, d, x, d, &xP, L.out.b, x, false, nullptr, true);
+      gemm_pl(xP, L.ffn1_f.img, c.ffn, d, nullptr, 0, &hP, L.ffn1_f.folded.b, nullptr, true, L.ffn1_f.colsum, false);
+      gemm_pl(hP, L.ffn2_img, d, c.ffn, x, d, more ? &xP : nullptr, L.ffn2.b, x, false, nullptr, more);
       continue;
     }
     // x = (first ? 0 : x) + ctx*Wo + b + fsmn_memory
     if (fuse_ln) {
-      gemm_ln(m->ctx.f(), m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, mem_in_x ? x : m->mem.f(), mem_in_x || first ? nullptr : x, false,
-              nullptr, true, d);
-      gemm_ln(x, m->d_lnw_ffn1 + (size_t)i * c.ffn * d, c.ffn, m->hbuf.f(), c.ffn, m->d_lnb_ffn1 + (size_t)i * c.ffn, nullptr, nullptr, true,
-              m->d_lns_ffn1 + (size_t)i * c.ffn, false, d);
-      gemm_ln(m->hbuf.f(), m->W(p + "ffn2.w").d, d, x, d, m->W(p + "ffn2.b").d, x, nullptr, false, nullptr, i + 1 < c.enc_layers, c.ffn);
+      gemm_ln(m->ctx.f(), L.out, d, x, d, mem_in_x ? x : m->mem.f(), mem_in_x || first ? nullptr : x, false, nullptr, true, d);
+      gemm_ln(x, L.ffn1_f.folded, c.ffn, m->hbuf.f(), c.ffn, nullptr, nullptr, true, L.ffn1_f.colsum, false, d);
+      gemm_ln(m->hbuf.f(), L.ffn2, d, x, d, x, nullptr, false, nullptr, more, c.ffn);
       continue;
     }
-    gemm(m, s, m->ctx.f(), d, m->W(p + "out.w").d, d, d, d, x, d, m->W(p + "out.b").d, mem_in_x ? x : m->mem.f(), d,
-         mem_in_x || first ? nullptr : x, d, M, false);
-    lnorm(m, s, x, d, m->y.f(), d, p + "norm2", M, d, d);
-    gemm(m, s, m->y.f(), d, m->W(p + "ffn1.w").d, c.ffn, d, d, m->hbuf.f(), c.ffn, m->W(p + "ffn1.b").d, nullptr, 0,
-         nullptr, 0, M, true);
-    gemm(m, s, m->hbuf.f(), c.ffn, m->W(p + "ffn2.w").d, d, c.ffn, c.ffn, x, d, m->W(p + "ffn2.b").d, x, d, nullptr, 0,
-         M, false);
+    gemm(m, s, m->ctx.f(), d, L.out, d, d, d, x, d, mem_in_x ? x : m->mem.f(), d, mem_in_x || first ? nullptr : x, d, M, false);
+    lnorm(m, s, x, d, m->y.f(), d, L.norm2, M, d, d);
+    gemm(m, s, m->y.f(), d, L.ffn1, c.ffn, d, d, m->hbuf.f(), c.ffn, nullptr, 0, nullptr, 0, M, true);
+    gemm(m, s, m->hbuf.f(), c.ffn, L.ffn2, d, c.ffn, c.ffn, x, d, x, d, nullptr, 0, M, false);
   }
-  lnorm(m, s, x, d, m->enc.f(), d, "enc.after_norm", M, d, d);
+  lnorm(m, s, x, d, m->enc.f(), d, w.enc_after, M, d, d);
+  return PFHIP_OK;
+}
 
-  // ---- predictor + CIF ------------------------------------------------------------------------------------
+// ---- predictor + CIF: alphas, the fired embeddings staged in `hbuf`, and the one host sync for the token counts ------------
+pfhip_status forward_cif(pfhip_model* m, hipStream_t s) {
+  const ModelWeights& w = *m->weights;
+  const Config& c = w.cfg;
+  const int d = c.d_model, B = m->B, M = m->M;
   float* col = m->qkv.f();          // [Mp, 3d] reused
   float* po = m->ctx.f();           // [Mp, d] reused
   {
     Scope sc(m, s, K_OTHER, 0, 16.0 * M * d);
     pfhip::launch_im2col3(m->enc.f(), d, col, 3 * d, m->m_row_pos, m->m_row_len, M, d, s);
   }
-  gemm(m, s, col, 3 * d, m->d_predconv, d, 3 * d, 3 * d, po, d, m->W("pred.conv.b").d,
-       c.pred_residual ? m->enc.f() : nullptr, d, nullptr, 0, M, true);
+  gemm(m, s, col, 3 * d, w.pred.conv, d, 3 * d, 3 * d, po, d, c.pred_residual ? m->enc.f() : nullptr, d, nullptr, 0, M, true);
   {
     Scope sc(m, s, K_OTHER, 2.0 * M * d, 4.0 * M * d);
-    pfhip::launch_alpha(po, d, m->W("pred.out.w").d, m->W("pred.out.b").d, c.smooth_factor, c.noise_threshold,
-                        m->alphas.f(), M, d, s);
+    pfhip::launch_alpha(po, d, w.pred.out_w, w.pred.out_b, c.smooth_factor, c.noise_threshold, m->alphas.f(), M, d, s);
   }
   float* stage = m->hbuf.f();       // [(M+B), d] reused
   {
@@ -857,18 +904,28 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     pfhip::launch_cif(m->enc.f(), d, m->alphas.f(), m->m_row_off, m->m_len, B, d, c.cif_threshold, c.tail_threshold,
                       stage, m->counts.i(), m->counts.i() + B, s);
   }
-  HIP_TRY(hipMemcpyAsync(m->h_counts, m->counts.p, (size_t)2 * B * 4, hipMemcpyDeviceToHost, s));
+  const int* h_counts = m->h_counts.i();
+  HIP_TRY(hipMemcpyAsync(m->h_counts.p, m->counts.p, (size_t)2 * B * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));      // the one host sync: token counts size the decoder launch
   int ML = 0;
   for (int b = 0; b < B; ++b) {
-    m->n_fires[b] = m->h_counts[b];
-    m->token_num[b] = m->h_counts[B + b];
+    m->n_fires[b] = h_counts[b];
+    m->token_num[b] = h_counts[B + b];
     m->tok_off[b] = ML;
     ML += m->n_fires[b];
     m->maxL = std::max(m->maxL, m->n_fires[b]);
   }
   m->ML = ML;
-  if (ML == 0) { HIP_TRY(hipGetLastError()); return PFHIP_OK; }
+  if (ML == 0) HIP_TRY(hipGetLastError());
+  return PFHIP_OK;
+}
+
+// ---- decoder over the ML fired tokens + vocabulary projection ----------------------------------------------------------------
+pfhip_status forward_decoder(pfhip_model* m, hipStream_t s, const ForwardPaths& paths) {
+  const ModelWeights& w = *m->weights;
+  const Config& c = w.cfg;
+  const int d = c.d_model, B = m->B, M = m->M, ML = m->ML;
+  const int Mp = round_up(M, pfhip::kTileM);
   if (c.contextual) {       // the reference logs "hw_emb is null" and returns empty results (paraformer.cpp:516-520)
     bool have = m->fw_hwkv != nullptr && (int)m->fw_hw_len.size() == B;
     for (int b = 0; have && b < B; ++b) have = m->fw_hw_len[b] > 0;
@@ -881,8 +938,8 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     const size_t n = 4 * (size_t)B + ML;
     HIP_TRY(m->dmeta.ensure(n * 4));
     // second half of the pinned staging buffer: never overwritten while an earlier copy may be in flight
-    if (m->h_meta_cap / 2 + n * 4 > m->h_meta_cap) return fail(PFHIP_ERR_CAPACITY, "internal: metadata staging too small");
-    int* hm = reinterpret_cast<int*>(static_cast<char*>(m->h_meta) + m->h_meta_cap / 2);
+    if (m->h_meta.cap / 2 + n * 4 > m->h_meta.cap) return fail(PFHIP_ERR_CAPACITY, "internal: metadata staging too small");
+    int* hm = reinterpret_cast<int*>(static_cast<char*>(m->h_meta.p) + m->h_meta.cap / 2);
     int* dm = m->dmeta.i();
     std::memcpy(hm, m->tok_off.data(), 4 * B); m->m_tok_off = dm;
     std::memcpy(hm + B, m->n_fires.data(), 4 * B); m->m_tok_len = dm + B;
@@ -904,16 +961,15 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
   HIP_TRY(m->t2.ensure((size_t)MLp * d * 4));
   HIP_TRY(m->qd.ensure((size_t)MLp * d * 4));
   HIP_TRY(m->ctxd.ensure((size_t)MLp * d * 4));
-  HIP_TRY(m->logits.ensure((size_t)MLp * m->vocab_pad * 4));
+  HIP_TRY(m->logits.ensure((size_t)MLp * w.vocab_pad * 4));
   HIP_TRY(m->ids.ensure((size_t)MLp * 4));
   if (m->nbest_k) { HIP_TRY(m->nb_ids.ensure((size_t)MLp * m->nbest_k * 4)); HIP_TRY(m->nb_logp.ensure((size_t)MLp * m->nbest_k * 4)); }
   {
     Scope sc(m, s, K_OTHER, 0, 8.0 * ML * d);
-    pfhip::launch_compact(stage, m->emb.f(), m->m_src_row, ML, d, s);
+    pfhip::launch_compact(m->hbuf.f(), m->emb.f(), m->m_src_row, ML, d, s);      // the CIF's staging rows [(M+B), d]
     HIP_TRY(hipMemcpyAsync(m->xd.p, m->emb.p, (size_t)ML * d * 4, hipMemcpyDeviceToDevice, s));
   }
 
-  // ---- decoder ----------------------------------------------------------------------------------------------
   float* xd = m->xd.f();
   float* kvbuf = m->qkv.f();        // [Mp, 2d] reused
   // Large batches: the K/V projections of the encoder output (16 x [M, 512] x [512, 1024]: 1000 tiles each, they fill the
@@ -929,8 +985,7 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     HIP_TRY(hipEventRecord(m->ev_enc_ready, s));
     HIP_TRY(hipStreamWaitEvent(m->side_stream, m->ev_enc_ready, 0));
     for (int i = 0; i < c.dec_layers; ++i) {
-      const std::string p = "dec." + std::to_string(i) + ".";
-      gemm(m, m->side_stream, m->enc.f(), d, m->W(p + "kv.w").d, 2 * d, d, d, m->kvside.f() + (size_t)i * Mp * 2 * d, 2 * d, m->W(p + "kv.b").d,
+      gemm(m, m->side_stream, m->enc.f(), d, w.dec[(size_t)i].kv, 2 * d, d, d, m->kvside.f() + (size_t)i * Mp * 2 * d, 2 * d,
            nullptr, 0, nullptr, 0, M, false);
       HIP_TRY(hipEventRecord(m->ev_kv[(size_t)i], m->side_stream));
     }
@@ -942,20 +997,19 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
   // The decoder's FFN LayerNorms fold the same way (rows >= 4096): norm1 into FFN1 — its input is the residual stream the
   // previous layer's output projection wrote (statistics from that epilogue; the first layer's input comes from the CIF, so it
   // keeps its LayerNorm launch) — and the 2048-wide ffn_norm into FFN2 (FFN1's epilogue leaves 16 pairs per row, after its ReLU).
-  const bool fuse_dec = m->d_dlnw1 != nullptr && pfhip::gemm_x6_ln_ok(ML) && !pfhip::launch_ctx().exact;
+  const bool fuse_dec = w.dec_folded && pfhip::gemm_x6_ln_ok(ML) && !pfhip::launch_ctx().exact;
   const int ftiles = c.dec_ffn / pfhip::kTileN;
   if (fuse_dec) {
     HIP_TRY(m->lnstats.ensure((size_t)std::max(Mp, MLp) * 4 * 2 * 4));
     HIP_TRY(m->lnstats2.ensure((size_t)MLp * ftiles * 2 * 4));
   }
-  auto x6ln = [&](const float* A, int K, const float* Wd, int N, float* Cd, const float* bias, const float* R1, bool relu,
+  auto x6ln = [&](const float* A, int K, const Linear& W, int N, float* Cd, const float* R1, bool relu,
                   const float* st_in, int tiles_in, const float* colsum, float* st_out) {
     Scope sc(m, s, K_GEMM, 2.0 * ML * (double)N * K, 4.0 * ((double)ML * K + (double)N * K + (double)ML * N));
-    pfhip::launch_gemm_f32_x6_ln(A, K, Wd, K, Cd, N, bias, R1, d, nullptr, 0, ML, N, K, relu, st_in, tiles_in, colsum, st_out, s,
-                                 m->w_scale_of(Wd));
+    pfhip::launch_gemm_f32_x6_ln(A, K, W.w, K, Cd, N, W.b, R1, d, nullptr, 0, ML, N, K, relu, st_in, tiles_in, colsum, st_out, s, W.scale);
   };
   bool xd_has_stats = false;          // lnstats holds the row statistics of the current xd
-  // Round 4: from 3500 token rows on (and only where the encoder ran on plane images: same arithmetic form) the decoder's large
+  // From 3500 token rows on (and only where the encoder ran on plane images: same arithmetic form) the decoder's large
   // GEMMs take plane-image operands as well (gemm_p3.hip): the K/V projection reads the images of the encoder output (one split
   // launch per forward), the cross-attention writes its context as images, the output projection leaves the token-side residual
   // stream as fp32 + images + row statistics, FFN1' (norm1 folded) reads those and leaves the hidden activation as fp32 + images +
@@ -963,7 +1017,7 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
   // the q projections (their input comes from the FSMN kernel), a contextual model's last layer and the vocabulary projection stay
   // on the in-loop-split kernels.
   static const int dec_planes_min_rows = pfhip::env_int("PFHIP_DEC_PLANES_MIN_ROWS", 3500);
-  const bool dec_planes = planes && fuse_dec && m->dwp_layer_bytes != 0 && ML >= dec_planes_min_rows && pfhip::attention_planes_ok(m->maxL, hdd) &&
+  const bool dec_planes = paths.planes && fuse_dec && w.dec_planes && ML >= dec_planes_min_rows && pfhip::attention_planes_ok(m->maxL, hdd) &&
                           pfhip::gemm_f16_planes_form();
   Img encP{nullptr, nullptr}, xdP{nullptr, nullptr}, hdP{nullptr, nullptr}, ctxdP{nullptr, nullptr};
   bool xd_has_planes = false;
@@ -974,82 +1028,62 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     HIP_TRY(m->xdP.ensure(2 * pdd));
     HIP_TRY(m->ctxP.ensure(2 * pdd));
     HIP_TRY(m->hP.ensure(2 * pff));
-    encP = {static_cast<unsigned char*>(m->encP.p), static_cast<unsigned char*>(m->encP.p) + pe};
-    xdP = {static_cast<unsigned char*>(m->xdP.p), static_cast<unsigned char*>(m->xdP.p) + pdd};
-    ctxdP = {static_cast<unsigned char*>(m->ctxP.p), static_cast<unsigned char*>(m->ctxP.p) + pdd};
-    hdP = {static_cast<unsigned char*>(m->hP.p), static_cast<unsigned char*>(m->hP.p) + pff};
+    encP = img_of(m->encP, pe); xdP = img_of(m->xdP, pdd); ctxdP = img_of(m->ctxP, pdd); hdP = img_of(m->hP, pff);
     Scope sc(m, s, K_OTHER, 0, 8.0 * M * d);
     pfhip::launch_split_planes(m->enc.f(), d, M, Mp, d, 1.0f, encP.hi, encP.lo, s);
   }
-  auto dwimg = [&](int layer, int which) -> WImg {         // 0 ffn1', 1 ffn2', 2 kv, 3 out
-    const unsigned char* base = m->d_dwplanes + m->dwp_layer_bytes * (size_t)layer;
-    const std::string dp = "dec." + std::to_string(layer) + ".";
-    switch (which) {
-      case 0: return {base, base + pfhip::plane_image_bytes(c.dec_ffn, d), m->w_scale_of(m->d_dlnw1 + (size_t)layer * c.dec_ffn * d)};
-      case 1: return {base + m->dwp_off_ffn2, base + m->dwp_off_ffn2 + pfhip::plane_image_bytes(d, c.dec_ffn),
-                      m->w_scale_of(m->d_dlnw2 + (size_t)layer * d * c.dec_ffn)};
-      case 2: return {base + m->dwp_off_kv, base + m->dwp_off_kv + pfhip::plane_image_bytes(2 * d, d), m->w_scale_of(m->W(dp + "kv.w").d)};
-      default: return {base + m->dwp_off_out, base + m->dwp_off_out + pfhip::plane_image_bytes(d, d), m->w_scale_of(m->W(dp + "out.w").d)};
-    }
-  };
   // one gemm_p3 launch over `rows` rows: A image with rows_a rows per K-step, result as fp32 (Cd) and / or images (P, MLp rows)
-  auto dgemm_pl = [&](const Img& A, int rows_a, const WImg& W, int rows, int N, int K, float* Cd, int ldc, const Img* P, const float* bias,
+  auto dgemm_pl = [&](const Img& A, int rows_a, const Planes& W, int rows, int N, int K, float* Cd, int ldc, const Img* P, const float* bias,
                       const float* R1, bool relu, const float* st_in, int tiles_in, const float* colsum, float* st_out) {
     Scope sc(m, s, K_GEMM, 2.0 * rows * (double)N * K, 4.0 * ((double)rows * K + (double)N * K + (double)rows * N));
     pfhip::launch_gemm_p3(A.hi, A.lo, rows_a, W.hi, W.lo, N, W.scale, Cd, ldc, P ? P->hi : nullptr, P ? P->lo : nullptr, MLp, bias, R1, d, rows, N, K,
                           relu, st_in, tiles_in, colsum, st_out, 4, s);
   };
-  auto dec_ffn = [&](const std::string& p, int li, const float* xin, float* out) {
+  auto dec_ffn = [&](const DecFfn& F, const float* xin, float* out) {
     if (dec_planes && xd_has_planes && xd_has_stats) {
       // FFN1' on the images of the residual stream: hidden activation as fp32 (row statistics ride on that pass) + images
-      dgemm_pl(xdP, MLp, dwimg(li, 0), ML, c.dec_ffn, d, m->hd.f(), c.dec_ffn, &hdP, m->d_dlnb1 + (size_t)li * c.dec_ffn, nullptr, true,
-               m->lnstats.f(), 4, m->d_dlns1 + (size_t)li * c.dec_ffn, m->lnstats2.f());
-      dgemm_pl(hdP, MLp, dwimg(li, 1), ML, d, c.dec_ffn, out, d, nullptr, m->d_dlnb2 + (size_t)li * d, nullptr, false, m->lnstats2.f(), ftiles,
-               m->d_dlns2 + (size_t)li * d, nullptr);
+      dgemm_pl(xdP, MLp, F.ffn1_f.img, ML, c.dec_ffn, d, m->hd.f(), c.dec_ffn, &hdP, F.ffn1_f.folded.b, nullptr, true,
+               m->lnstats.f(), 4, F.ffn1_f.colsum, m->lnstats2.f());
+      dgemm_pl(hdP, MLp, F.ffn2_f.img, ML, d, c.dec_ffn, out, d, nullptr, F.ffn2_f.folded.b, nullptr, false, m->lnstats2.f(), ftiles,
+               F.ffn2_f.colsum, nullptr);
       return;
     }
     if (fuse_dec) {
       if (xd_has_stats) {
-        x6ln(xin, d, m->d_dlnw1 + (size_t)li * c.dec_ffn * d, c.dec_ffn, m->hd.f(), m->d_dlnb1 + (size_t)li * c.dec_ffn, nullptr, true,
-             m->lnstats.f(), 4, m->d_dlns1 + (size_t)li * c.dec_ffn, m->lnstats2.f());
+        x6ln(xin, d, F.ffn1_f.folded, c.dec_ffn, m->hd.f(), nullptr, true, m->lnstats.f(), 4, F.ffn1_f.colsum, m->lnstats2.f());
       } else {
-        lnorm(m, s, xin, d, m->yd.f(), d, p + "norm1", ML, d, d);
-        x6ln(m->yd.f(), d, m->W(p + "ffn1.w").d, c.dec_ffn, m->hd.f(), m->W(p + "ffn1.b").d, nullptr, true, nullptr, 0, nullptr,
-             m->lnstats2.f());
+        lnorm(m, s, xin, d, m->yd.f(), d, F.norm1, ML, d, d);
+        x6ln(m->yd.f(), d, F.ffn1, c.dec_ffn, m->hd.f(), nullptr, true, nullptr, 0, nullptr, m->lnstats2.f());
       }
-      x6ln(m->hd.f(), c.dec_ffn, m->d_dlnw2 + (size_t)li * d * c.dec_ffn, d, out, m->d_dlnb2 + (size_t)li * d, nullptr, false, m->lnstats2.f(),
-           ftiles, m->d_dlns2 + (size_t)li * d, nullptr);
+      x6ln(m->hd.f(), c.dec_ffn, F.ffn2_f.folded, d, out, nullptr, false, m->lnstats2.f(), ftiles, F.ffn2_f.colsum, nullptr);
       return;
     }
-    lnorm(m, s, xin, d, m->yd.f(), d, p + "norm1", ML, d, d);
-    gemm(m, s, m->yd.f(), d, m->W(p + "ffn1.w").d, c.dec_ffn, d, d, m->hd.f(), c.dec_ffn, m->W(p + "ffn1.b").d, nullptr,
-         0, nullptr, 0, ML, true);
-    lnorm(m, s, m->hd.f(), c.dec_ffn, m->hd2.f(), c.dec_ffn, p + "ffn_norm", ML, c.dec_ffn, c.dec_ffn);
-    gemm(m, s, m->hd2.f(), c.dec_ffn, m->W(p + "ffn2.w").d, d, c.dec_ffn, c.dec_ffn, out, d, nullptr, nullptr, 0, nullptr,
-         0, ML, false);
+    lnorm(m, s, xin, d, m->yd.f(), d, F.norm1, ML, d, d);
+    gemm(m, s, m->yd.f(), d, F.ffn1, c.dec_ffn, d, d, m->hd.f(), c.dec_ffn, nullptr, 0, nullptr, 0, ML, true);
+    lnorm(m, s, m->hd.f(), c.dec_ffn, m->hd2.f(), c.dec_ffn, F.ffn_norm, ML, c.dec_ffn, c.dec_ffn);
+    gemm(m, s, m->hd2.f(), c.dec_ffn, F.ffn2, d, c.dec_ffn, c.dec_ffn, out, d, nullptr, 0, nullptr, 0, ML, false);
   };
   for (int i = 0; i < c.dec_layers; ++i) {
-    const std::string p = "dec." + std::to_string(i) + ".";
-    dec_ffn(p, i, xd, m->td.f());
-    lnorm(m, s, m->td.f(), d, m->t2.f(), d, p + "norm2", ML, d, d);
+    const DecLayer& L = w.dec[(size_t)i];
+    dec_ffn(L.ffn, xd, m->td.f());
+    lnorm(m, s, m->td.f(), d, m->t2.f(), d, L.norm2, ML, d, d);
     {
       Scope sc(m, s, K_FSMN, 2.0 * 11 * ML * d, 12.0 * ML * d);
-      pfhip::launch_fsmn(m->t2.f(), d, m->W(p + "fsmn.w").d, xd, d, xd, d, m->m_tok_off, m->m_tok_len, B, m->maxL, d, s);
+      pfhip::launch_fsmn(m->t2.f(), d, L.fsmn_w, xd, d, xd, d, m->m_tok_off, m->m_tok_len, B, m->maxL, d, s);
     }
-    lnorm(m, s, xd, d, m->yd.f(), d, p + "norm3", ML, d, d);
-    gemm(m, s, m->yd.f(), d, m->W(p + "q.w").d, d, d, d, m->qd.f(), d, m->W(p + "q.b").d, nullptr, 0, nullptr, 0, ML, false);
+    lnorm(m, s, xd, d, m->yd.f(), d, L.norm3, ML, d, d);
+    gemm(m, s, m->yd.f(), d, L.q, d, d, d, m->qd.f(), d, nullptr, 0, nullptr, 0, ML, false);
     const bool plain_layer = !(c.contextual && i == c.dec_layers - 1);
     if (side_kv) {
       kvbuf = m->kvside.f() + (size_t)i * Mp * 2 * d;
       HIP_TRY(hipStreamWaitEvent(s, m->ev_kv[(size_t)i], 0));
     } else if (dec_planes) {
       Scope sc(m, s, K_GEMM, 2.0 * M * 2.0 * d * d, 4.0 * ((double)M * d + 2.0 * d * d + 2.0 * M * d));
-      const WImg W = dwimg(i, 2);
-      pfhip::launch_gemm_p3(encP.hi, encP.lo, Mp, W.hi, W.lo, 2 * d, W.scale, kvbuf, 2 * d, nullptr, nullptr, Mp, m->W(p + "kv.b").d, nullptr, 0, M,
+      const Planes& W = L.kv_img;
+      pfhip::launch_gemm_p3(encP.hi, encP.lo, Mp, W.hi, W.lo, 2 * d, W.scale, kvbuf, 2 * d, nullptr, nullptr, Mp, L.kv.b, nullptr, 0, M,
                             2 * d, d, false, nullptr, 0, nullptr, nullptr, 4, s);
     } else {
-      gemm(m, s, m->enc.f(), d, m->W(p + "kv.w").d, 2 * d, d, d, kvbuf, 2 * d, m->W(p + "kv.b").d, nullptr, 0, nullptr, 0, M,
-           false);
+      gemm(m, s, m->enc.f(), d, L.kv, 2 * d, d, d, kvbuf, 2 * d, nullptr, 0, nullptr, 0, M, false);
     }
     {
       Scope sc(m, s, K_ATTN, 4.0 * cross_pairs * d, 8.0 * ML * d + 8.0 * M * d);
@@ -1064,17 +1098,17 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     xd_has_planes = false;
     if (dec_planes && plain_layer) {
       // xd = ctx Wo^T + b + xd: fp32 for the residual adds, images + row statistics for the next FFN1'
-      dgemm_pl(ctxdP, MLp, dwimg(i, 3), ML, d, d, xd, d, &xdP, m->W(p + "out.b").d, xd, false, nullptr, 0, nullptr, m->lnstats.f());
+      dgemm_pl(ctxdP, MLp, L.out_img, ML, d, d, xd, d, &xdP, L.out.b, xd, false, nullptr, 0, nullptr, m->lnstats.f());
       xd_has_stats = true;
       xd_has_planes = true;
       continue;
     }
-    if (!(c.contextual && i == c.dec_layers - 1)) {
+    if (plain_layer) {
       if (fuse_dec) {          // the output projection also leaves the statistics the next norm1 needs
-        x6ln(m->ctxd.f(), d, m->W(p + "out.w").d, d, xd, m->W(p + "out.b").d, xd, false, nullptr, 0, nullptr, m->lnstats.f());
+        x6ln(m->ctxd.f(), d, L.out, d, xd, xd, false, nullptr, 0, nullptr, m->lnstats.f());
         xd_has_stats = true;
       } else {
-        gemm(m, s, m->ctxd.f(), d, m->W(p + "out.w").d, d, d, d, xd, d, m->W(p + "out.b").d, xd, d, nullptr, 0, ML, false);
+        gemm(m, s, m->ctxd.f(), d, L.out, d, d, d, xd, d, xd, d, nullptr, 0, ML, false);
       }
       continue;
     }
@@ -1083,9 +1117,9 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
     //      embeddings; xd holds x_self_attn, cat = [x_src_attn | cx] with row stride 2d.
     HIP_TRY(m->cat.ensure((size_t)MLp * 2 * d * 4));
     float* cat = m->cat.f();
-    gemm(m, s, m->ctxd.f(), d, m->W(p + "out.w").d, d, d, d, cat, 2 * d, m->W(p + "out.b").d, nullptr, 0, nullptr, 0, ML, false);
-    lnorm(m, s, xd, d, m->yd.f(), d, "bias.dec.norm3", ML, d, d);
-    gemm(m, s, m->yd.f(), d, m->W("bias.dec.q.w").d, d, d, d, m->qd.f(), d, m->W("bias.dec.q.b").d, nullptr, 0, nullptr, 0, ML, false);
+    gemm(m, s, m->ctxd.f(), d, L.out, d, d, d, cat, 2 * d, nullptr, 0, nullptr, 0, ML, false);
+    lnorm(m, s, xd, d, m->yd.f(), d, w.bias.norm3, ML, d, d);
+    gemm(m, s, m->yd.f(), d, w.bias.q, d, d, d, m->qd.f(), d, nullptr, 0, nullptr, 0, ML, false);
     // the hotword K/V projections live in the device's hotword bank, filled once per hotword set and kept across calls
     // (resolve_hotwords_locked) — the audio-side kv workspace only holds Mp rows
     const float* hwkv = m->fw_hwkv;
@@ -1096,14 +1130,12 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
       pfhip::launch_attention(m->qd.f(), d, hwkv, 2 * d, hwkv + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len,
                               m->m_hw_off, m->m_hw_len, B, c.dec_n_head, m->maxL, att_scale_d, s);
     }
-    gemm(m, s, m->ctxd.f(), d, m->W("bias.dec.out.w").d, d, d, d, cat + d, 2 * d, m->W("bias.dec.out.b").d, nullptr, 0, nullptr,
-         0, ML, false);
-    gemm(m, s, cat, 2 * d, m->W("bias.out.w").d, d, 2 * d, 2 * d, xd, d, nullptr, xd, d, nullptr, 0, ML, false);
+    gemm(m, s, m->ctxd.f(), d, w.bias.out, d, d, d, cat + d, 2 * d, nullptr, 0, nullptr, 0, ML, false);
+    gemm(m, s, cat, 2 * d, w.bias.merge, d, 2 * d, 2 * d, xd, d, xd, d, nullptr, 0, ML, false);
   }
-  dec_ffn("dec3.", c.dec_layers, xd, m->td.f());
-  lnorm(m, s, m->td.f(), d, m->yd.f(), d, "dec.after_norm", ML, d, d);
-  gemm(m, s, m->yd.f(), d, m->W("dec.out.w").d, c.vocab, d, d, m->logits.f(), m->vocab_pad, m->d_vocab_bias, nullptr, 0,
-       nullptr, 0, ML, false);
+  dec_ffn(w.dec3, xd, m->td.f());
+  lnorm(m, s, m->td.f(), d, m->yd.f(), d, w.dec_after, ML, d, d);
+  gemm(m, s, m->yd.f(), d, w.dec_out, c.vocab, d, d, m->logits.f(), w.vocab_pad, nullptr, 0, nullptr, 0, ML, false);
   HIP_TRY(hipGetLastError());
   return PFHIP_OK;
 }
@@ -1111,7 +1143,8 @@ pfhip_status enqueue_body(pfhip_model* m, PcmView d_pcm, const int64_t* sample_o
 // ---- a6 producer: CifPredictorV3.get_upsample_timestmap on the encoder output of the batch just run -------------------
 pfhip_status ts_head_locked(pfhip_model* m, hipStream_t s, bool stepwise_only = false) {
   ForwardCtx fc(m);
-  const Config& c = m->cfg;
+  const Config& c = m->weights->cfg;
+  const TimestampHead& ts = m->weights->ts;
   if (!c.timestamp) return fail(PFHIP_ERR_UNSUPPORTED, "model has no timestamp head (us_alphas / us_cif_peak outputs)");
   if (m->have_ts) return PFHIP_OK;
   const int d = c.d_model, B = m->B, M = m->M;
@@ -1149,9 +1182,9 @@ pfhip_status ts_head_locked(pfhip_model* m, hipStream_t s, bool stepwise_only = 
   const int* d_len = d_off + B;
   const int* d_tok = d_off + 2 * B;
   // ConvTranspose1d: [M, d] x [3d, d]^T -> [M, 3d] == [3M, d]
-  gemm(m, s, m->enc.f(), d, m->d_up_w, 3 * d, d, d, m->ts_up.f(), 3 * d, m->d_up_b, nullptr, 0, nullptr, 0, M, false);
+  gemm(m, s, m->enc.f(), d, ts.up, 3 * d, d, d, m->ts_up.f(), 3 * d, nullptr, 0, nullptr, 0, M, false);
   // input projections of both directions: [3M, d] x [8d, d]^T -> [3M, 8d]
-  gemm(m, s, m->ts_up.f(), d, m->d_wih, 8 * d, d, d, m->ts_gx.f(), 8 * d, m->d_bih, nullptr, 0, nullptr, 0, R, false);
+  gemm(m, s, m->ts_up.f(), d, ts.ih, 8 * d, d, d, m->ts_gx.f(), 8 * d, nullptr, 0, nullptr, 0, R, false);
   {
     Scope sc(m, s, K_OTHER, 2.0 * R * 8 * d * d, 4.0 * R * 10 * d);
     // The recurrence advances up to 32 utterances together.  First the persistent kernel (one launch, 9 us per step); if its
@@ -1165,10 +1198,10 @@ pfhip_status ts_head_locked(pfhip_model* m, hipStream_t s, bool stepwise_only = 
         int lmax = 0;
         for (int b = b0; b < b0 + nb; ++b) lmax = std::max(lmax, 3 * m->T[b]);
         if (stepwise)
-          HIP_TRY(pfhip::launch_blstm_stepwise(m->ts_gx.f(), m->d_whh, m->ts_y.f(), m->ts_hx.f(), m->ts_cst.f(), d_off + b0, d_len + b0, nb,
+          HIP_TRY(pfhip::launch_blstm_stepwise(m->ts_gx.f(), ts.whh, m->ts_y.f(), m->ts_hx.f(), m->ts_cst.f(), d_off + b0, d_len + b0, nb,
                                                lmax, rs));
         else
-          HIP_TRY(pfhip::launch_blstm(m->ts_gx.f(), m->d_whh, m->ts_y.f(), m->ts_hx.f(), d_off + b0, d_len + b0, nb, lmax, rs));
+          HIP_TRY(pfhip::launch_blstm(m->ts_gx.f(), ts.whh, m->ts_y.f(), m->ts_hx.f(), d_off + b0, d_len + b0, nb, lmax, rs));
       }
       return PFHIP_OK;
     };
@@ -1203,7 +1236,7 @@ pfhip_status ts_head_locked(pfhip_model* m, hipStream_t s, bool stepwise_only = 
       pfhip_status st = recurrence(true, s);
       if (st) return st;
     }
-    pfhip::launch_alpha2(m->ts_y.f(), 2 * d, m->W("pred.out2.w").d, m->out2_b, c.smooth_factor2, c.noise_threshold2,
+    pfhip::launch_alpha2(m->ts_y.f(), 2 * d, ts.out2_w, ts.out2_b, c.smooth_factor2, c.noise_threshold2,
                          m->ts_a2.f(), R, 2 * d, s);
     pfhip::launch_us_cif(m->ts_a2.f(), d_off, d_len, d_tok, B, maxL, c.cif_threshold - 1e-4f, m->ts_alphas.f(),
                          m->ts_peaks.f(), s);
@@ -1215,20 +1248,20 @@ pfhip_status ts_head_locked(pfhip_model* m, hipStream_t s, bool stepwise_only = 
 
 pfhip_status head_locked(pfhip_model* m, hipStream_t s, bool want_logp) {
   if (m->ML == 0) return PFHIP_OK;
-  const int V = m->cfg.vocab;
+  const int V = m->weights->cfg.vocab;
   if (want_logp) HIP_TRY(m->logp.ensure((size_t)m->ML * V * 4));
   if (m->nbest_k) {      // candidates asked for: the sibling kernel (topk.hip), which reads the row a second time for its log-sum-exp
     const int k = m->nbest_k;
     HIP_TRY(m->nb_ids.ensure((size_t)m->ML * k * 4));
     HIP_TRY(m->nb_logp.ensure((size_t)m->ML * k * 4));
     Scope sc(m, s, K_HEAD, 0, 4.0 * m->ML * V * (want_logp ? 3 : 2));
-    if (!pfhip::launch_logsoftmax_topk(m->logits.f(), m->vocab_pad, m->ML, V, k, want_logp ? m->logp.f() : nullptr,
+    if (!pfhip::launch_logsoftmax_topk(m->logits.f(), m->weights->vocab_pad, m->ML, V, k, want_logp ? m->logp.f() : nullptr,
                                        static_cast<int32_t*>(m->ids.p), static_cast<int32_t*>(m->nb_ids.p), m->nb_logp.f(), s,
                                        m->d_range_flag))
       return fail(PFHIP_ERR_ARG, "nbest k outside 1..8 or larger than the vocabulary");
   } else {
     Scope sc(m, s, K_HEAD, 0, 4.0 * m->ML * V * (want_logp ? 3 : 2));
-    pfhip::launch_logsoftmax_argmax(m->logits.f(), m->vocab_pad, m->ML, V, want_logp ? m->logp.f() : nullptr,
+    pfhip::launch_logsoftmax_argmax(m->logits.f(), m->weights->vocab_pad, m->ML, V, want_logp ? m->logp.f() : nullptr,
                                     static_cast<int32_t*>(m->ids.p), s, m->d_range_flag);
   }
   m->have_logp = want_logp;
@@ -1240,9 +1273,9 @@ pfhip_status head_locked(pfhip_model* m, hipStream_t s, bool want_logp) {
 pfhip_status read_range_flag(pfhip_model* m, hipStream_t s, bool sync) {
   m->range_hit = 0;
   if (!m->d_range_flag) return PFHIP_OK;
-  if (!m->h_flag) HIP_TRY(hipHostMalloc((void**)&m->h_flag, 64, hipHostMallocDefault));
-  *m->h_flag = 0;
-  HIP_TRY(hipMemcpyAsync(m->h_flag, m->d_range_flag, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(m->h_flag.ensure(32));
+  *m->h_flag.i() = 0;
+  HIP_TRY(hipMemcpyAsync(m->h_flag.p, m->d_range_flag, 4, hipMemcpyDeviceToHost, s));
   if (sync) HIP_TRY(hipStreamSynchronize(s));
   return PFHIP_OK;
 }
@@ -1257,7 +1290,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
 // (head_locked reads m->nbest_k), so what comes back belongs to the forward whose token_ids come back
 pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb = nullptr) {
   pfhip_status st = fetch_once(m, out, s, nb);
-  if (st || !m->range_hit || m->exact_rerun || m->always_exact || !m->last_pcm.p || m->last_feats_only) return st;
+  if (st || !m->range_hit || m->exact_rerun || m->weights->always_exact || !m->last_pcm.p || m->last_feats_only) return st;
   ++m->range_fallbacks;
   m->exact_rerun = true;
   const std::vector<int64_t> off = m->last_off;
@@ -1331,7 +1364,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
     if (m->M > 0) {
       const pfhip_status rs = read_range_flag(m, s, true);
       if (rs) return rs;
-      m->range_hit = *m->h_flag;
+      m->range_hit = *m->h_flag.i();
     }
     return PFHIP_OK;
   }
@@ -1348,7 +1381,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
   }
   NbestStage nbs;
   if (nb) { const pfhip_status ns = nbs.start(m, s); if (ns) return ns; }
-  const int V = m->cfg.vocab;
+  const int V = m->weights->cfg.vocab;
   if (out->logp) {
     for (int b = 0; b < B; ++b)
       if (m->n_fires[b])
@@ -1360,7 +1393,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
     if (rs) return rs;
   }
   HIP_TRY(hipStreamSynchronize(s));
-  m->range_hit = m->h_flag ? *m->h_flag : 0;
+  m->range_hit = m->h_flag.p ? *m->h_flag.i() : 0;
   if (out->token_ids)
     for (int b = 0; b < B; ++b)
       std::memcpy(out->token_ids + (size_t)b * out->max_tokens, ids.data() + m->tok_off[b], 4 * (size_t)m->n_fires[b]);
@@ -1382,7 +1415,7 @@ void ensure_bank_locked(pfhip_model* owner) {
   }
   // Slabs are whole GEMM row tiles: the projection of an H-row set may write round_up(H, kTileM) rows (gemm pads M to the tile),
   // all of them inside the set's own slab; the attention kernels clamp their key rows to the segment they are given
-  const int d = owner->cfg.d_model;
+  const int d = owner->weights->cfg.d_model;
   const int64_t gran_bytes = (int64_t)pfhip::kTileM * 2 * d * 4;
   int granules = (int)std::min<int64_t>(D.bound_bytes / gran_bytes, INT32_MAX / pfhip::kTileM);
   if (granules > 0 && hipMalloc((void**)&D.arena, (size_t)granules * gran_bytes) != hipSuccess) {
@@ -1398,17 +1431,17 @@ void ensure_bank_locked(pfhip_model* owner) {
 // K/V projection of the bias decoder's cross-attention for one hotword set: [H, d] host rows -> staging rows of `m->hw` ->
 // dst [round_up(H, 128), 2d].  Enqueued on `s`, nothing waits.
 pfhip_status project_hotwords(pfhip_model* m, const float* host, int H, int stage_row, float* dst, hipStream_t s) {
-  const int d = m->cfg.d_model;
+  const int d = m->weights->cfg.d_model;
   float* A = m->hw.f() + (size_t)stage_row * d;
   HIP_TRY(hipMemcpyAsync(A, host, (size_t)H * d * 4, hipMemcpyHostToDevice, s));
-  gemm(m, s, A, d, m->W("bias.dec.kv.w").d, 2 * d, d, d, dst, 2 * d, m->W("bias.dec.kv.b").d, nullptr, 0, nullptr, 0, H, false);
+  gemm(m, s, A, d, m->weights->bias.kv, 2 * d, d, d, dst, 2 * d, nullptr, 0, nullptr, 0, H, false);
   return PFHIP_OK;
 }
 
 // a bank miss: the entry's rows go up and are projected straight into its slab; the event tells other streams when.  Bank mutex held.
 pfhip_status fill_slab_locked(pfhip_model* m, HwBankDev& D, int id, int stage_row, hipStream_t s) {
   HotwordBank::Entry& e = D.bank.entry(id);
-  pfhip_status st = project_hotwords(m, e.host.data(), e.H, stage_row, D.arena + (size_t)D.bank.row_off(id) * 2 * m->cfg.d_model, s);
+  pfhip_status st = project_hotwords(m, e.host.data(), e.H, stage_row, D.arena + (size_t)D.bank.row_off(id) * 2 * m->weights->cfg.d_model, s);
   if (st) return st;
   if (!e.ready) {
     hipEvent_t ev;
@@ -1442,7 +1475,7 @@ pfhip_status resolve_hotwords_locked(pfhip_model* m, const float* const* emb, co
   m->fw_hw_off.assign((size_t)B, 0);
   m->fw_hw_len.assign((size_t)B, 0);
   m->fw_hwkv = nullptr;
-  if (!m->cfg.contextual) return PFHIP_OK;          // plain models ignore hw_emb (paraformer.cpp:515: use_hotword == false)
+  if (!m->weights->cfg.contextual) return PFHIP_OK;          // plain models ignore hw_emb (paraformer.cpp:515: use_hotword == false)
   if (n_sets <= 0 || !emb || !H) return fail(PFHIP_ERR_ARG, "hw_emb is null");          // paraformer.cpp:516-520
   std::vector<char> used((size_t)n_sets, 0);
   for (int b = 0; b < B; ++b) {
@@ -1452,7 +1485,7 @@ pfhip_status resolve_hotwords_locked(pfhip_model* m, const float* const* emb, co
   }
   for (int k = 0; k < n_sets; ++k)
     if (used[(size_t)k] && (!emb[k] || H[k] <= 0)) return fail(PFHIP_ERR_ARG, "hw_emb is null");
-  const int d = m->cfg.d_model;
+  const int d = m->weights->cfg.d_model;
   HwBankDev& D = *bank_owner(m)->hwbank;
   std::vector<int> row((size_t)n_sets, 0);
   bool per_call = false;
@@ -1543,11 +1576,11 @@ std::shared_ptr<const std::vector<float>> default_hotwords(pfhip_model* m) {
   return head->hw_default;
 }
 pfhip_status resolve_default_hotwords_locked(pfhip_model* m, int B, hipStream_t s) {
-  if (!m->cfg.contextual) return resolve_hotwords_locked(m, nullptr, nullptr, 0, nullptr, B, s);
+  if (!m->weights->cfg.contextual) return resolve_hotwords_locked(m, nullptr, nullptr, 0, nullptr, B, s);
   const std::shared_ptr<const std::vector<float>> hw = default_hotwords(m);
   if (!hw || hw->empty()) return fail(PFHIP_ERR_ARG, "hw_emb is null");
   const float* e = hw->data();
-  const int H = (int)(hw->size() / (size_t)m->cfg.d_model);
+  const int H = (int)(hw->size() / (size_t)m->weights->cfg.d_model);
   return resolve_hotwords_locked(m, &e, &H, 1, nullptr, B, s);
 }
 
@@ -1576,7 +1609,7 @@ pfhip_status stage_pcm(pfhip_model* m, HostPcm pcm, const int* n_samples, int B,
 pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, int B, int fs_in, hipStream_t s,
                              std::vector<int64_t>& off, std::vector<int>& n_out) {
   pfhip::ResampleTable t;
-  pfhip_status st = (m->weights_of ? m->weights_of : m)->rs_cache->get(m->device, fs_in, m->cfg.sample_rate, &t);
+  pfhip_status st = (m->weights_of ? m->weights_of : m)->rs_cache->get(m->device, fs_in, m->weights->cfg.sample_rate, &t);
   if (st) return st;
   std::vector<int64_t> in_off(B);
   off.assign(B, 0);
@@ -1584,7 +1617,7 @@ pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, 
   int64_t tin = 0, tout = 0;
   for (int b = 0; b < B; ++b) {
     if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
-    const int64_t no = pfhip_detail::resample_out_len(fs_in, m->cfg.sample_rate, n_samples[b]);
+    const int64_t no = pfhip_detail::resample_out_len(fs_in, m->weights->cfg.sample_rate, n_samples[b]);
     if (no < 0 || no > INT32_MAX) return fail(PFHIP_ERR_ARG, "resampled utterance too long");
     in_off[b] = tin;
     tin += (n_samples[b] + 3) & ~3;
@@ -1712,50 +1745,13 @@ pfhip_status pfhip_create(const char* weight_blob_path, const char* manifest_jso
   return pfhip_create_from_memory(blob.data(), blob.size(), man.data(), device, out);
 }
 
-void pfhip_destroy(pfhip_model* m) {
-  if (!m) return;
-  for (pfhip_model* r : m->replicas) pfhip_destroy(r);
-  m->replicas.clear();
-  for (pfhip_model* cx : m->contexts) pfhip_destroy(cx);
-  m->contexts.clear();
-  (void)hipSetDevice(m->device);
-  (void)hipDeviceSynchronize();
-  for (Buf* b : {&m->pcm, &m->meta, &m->feats, &m->x0, &m->x, &m->y, &m->qkv, &m->mem, &m->ctx, &m->hbuf, &m->enc,
-                 &m->alphas, &m->counts, &m->emb, &m->xd, &m->yd, &m->hd, &m->hd2, &m->td, &m->t2, &m->qd, &m->ctxd,
-                 &m->logits, &m->logp, &m->ids, &m->dmeta, &m->cat, &m->hw, &m->hwkv, &m->ts_up, &m->ts_gx, &m->ts_y, &m->ts_hx, &m->ts_a2,
-                 &m->ts_alphas, &m->ts_peaks, &m->ts_meta, &m->sseg, &m->rs_in, &m->fbk, &m->d_ops, &m->kvall, &m->lnstats, &m->lnstats2, &m->kvside, &m->ts_cst, &m->ctxP, &m->xP, &m->hP, &m->encP, &m->xdP, &m->kvP, &m->nb_ids, &m->nb_logp})
-    b->release();
-  if (m->hwbank) {               // the device's hotword bank (unused on a context)
-    HwBankDev& D = *m->hwbank;
-    for (size_t i = 0; i < D.bank.id_count(); ++i)
-      if (D.bank.entry((int)i).ready) (void)hipEventDestroy(static_cast<hipEvent_t>(D.bank.entry((int)i).ready));
-    if (D.arena) (void)hipFree(D.arena);
-  }
-  if (!m->weights_of) {          // a context borrows these
-#define X(f) if (m->f) (void)hipFree((void*)m->f);
-    PFHIP_WEIGHT_PTRS(X)
-#undef X
-  }
-  if (m->h_meta) (void)hipHostFree(m->h_meta);
-  if (m->h_ops) (void)hipHostFree(m->h_ops);
-  if (m->h_counts) (void)hipHostFree(m->h_counts);
-  if (m->h_flag) (void)hipHostFree(m->h_flag);
-  for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
-  if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
-  if (m->side_stream) (void)hipStreamDestroy(m->side_stream);
-  if (m->ev_enc_ready) (void)hipEventDestroy(m->ev_enc_ready);
-  if (m->ev_ts_in) (void)hipEventDestroy(m->ev_ts_in);
-  if (m->ev_ts_out) (void)hipEventDestroy(m->ev_ts_out);
-  if (m->blstm_stream) (void)hipStreamDestroy(m->blstm_stream);
-  for (hipEvent_t e : m->ev_kv) if (e) (void)hipEventDestroy(e);
-  delete m;
-}
+void pfhip_destroy(pfhip_model* m) { delete m; }
 
-int pfhip_sample_rate(const pfhip_model* m) { return m ? m->cfg.sample_rate : 0; }
-int pfhip_vocab_size(const pfhip_model* m) { return m ? m->cfg.vocab : 0; }
-int pfhip_feat_dim(const pfhip_model* m) { return m ? m->feat_dim : 0; }
-int pfhip_d_model(const pfhip_model* m) { return m ? m->cfg.d_model : 0; }
-int pfhip_head_dim(const pfhip_model* m) { return m && m->cfg.n_head > 0 ? m->cfg.d_model / m->cfg.n_head : 0; }
+int pfhip_sample_rate(const pfhip_model* m) { return m ? m->weights->cfg.sample_rate : 0; }
+int pfhip_vocab_size(const pfhip_model* m) { return m ? m->weights->cfg.vocab : 0; }
+int pfhip_feat_dim(const pfhip_model* m) { return m ? m->weights->feat_dim : 0; }
+int pfhip_d_model(const pfhip_model* m) { return m ? m->weights->cfg.d_model : 0; }
+int pfhip_head_dim(const pfhip_model* m) { return m && m->weights->cfg.n_head > 0 ? m->weights->cfg.d_model / m->weights->cfg.n_head : 0; }
 
 static pfhip_status offline_enqueue(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                                     int batch, void* stream) {
@@ -1803,7 +1799,7 @@ static pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sam
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
   m->prof_stream = s;
-  if (nb && nb->k > m->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k larger than the vocabulary");      // before any launch
+  if (nb && nb->k > m->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k larger than the vocabulary");      // before any launch
   m->nbest_k = nb ? nb->k : 0;
   HotwordPins pins{m};              // held until the results (a range-guard re-run included) are back
   {
@@ -1889,7 +1885,7 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
   std::vector<BatchReq*> take;
   std::vector<const float*> set_emb; std::vector<int> set_n, set_of;
   for (BatchReq* r : all_taken) {
-    if (m->cfg.contextual) {
+    if (m->weights->cfg.contextual) {
       bool ok = r->hw.n_sets > 0 && r->hw.emb && r->hw.n;
       for (int i = 0; ok && i < r->batch; ++i) {
         const int k = r->hw.of_utt ? r->hw.of_utt[i] : 0;
@@ -1914,7 +1910,7 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
     want_us = want_us || r->out->us_alphas || r->out->us_peaks || r->out->us_len;
     utts += r->batch;
   }
-  const int V = m->cfg.vocab, max_us = 3 * max_tok;
+  const int V = m->weights->cfg.vocab, max_us = 3 * max_tok;
   std::vector<int32_t> ids((size_t)utts * max_tok), tn(utts), nf(utts), fr(utts), usl;
   std::vector<float> logp, usa, usp;
   if (want_logp) logp.resize((size_t)utts * max_tok * V);
@@ -2018,7 +2014,7 @@ static pfhip_status offline_forward_sets(pfhip_model* head, HostPcm pcm, const i
                                          pfhip_out* out, const pfhip_nbest* nb = nullptr) {
   g_err.clear();
   if (!head || !pcm.p || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (nb && (nb->k < 1 || nb->k > pfhip::kTopkMax || nb->k > head->cfg.vocab || !nb->ids || !nb->logp))
+  if (nb && (nb->k < 1 || nb->k > pfhip::kTopkMax || nb->k > head->weights->cfg.vocab || !nb->ids || !nb->logp))
     return fail(PFHIP_ERR_ARG, "nbest: k outside 1..8 (or above the vocabulary) or a null buffer");
   for (int i = 0; i < batch; ++i)
     if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm.p[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
@@ -2027,7 +2023,7 @@ static pfhip_status offline_forward_sets(pfhip_model* head, HostPcm pcm, const i
   bool merge;
   {
     std::lock_guard<std::mutex> l(head->bq.mu);
-    merge = head->batch_wait_us > 0 && batch < head->batch_max_utts && (!head->cfg.contextual || head->hw_merge);
+    merge = head->batch_wait_us > 0 && batch < head->batch_max_utts && (!head->weights->cfg.contextual || head->hw_merge);
   }
   if (merge) return forward_batched(head, pcm, n_samples, batch, hw, out, nb);
   pfhip_model* m = acquire_slot(head);                  // the least-loaded execution slot (context / GPU)
@@ -2054,7 +2050,7 @@ pfhip_status pfhip_offline_forward_s16(pfhip_model* head, const int16_t* const* 
 static pfhip_status offline_forward_hwsets(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch,
                                            const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
                                            pfhip_out* out) {
-  if (head && head->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
+  if (head && head->weights->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
     g_err.clear();
     return fail(PFHIP_ERR_ARG, "bad argument");
   }
@@ -2077,7 +2073,7 @@ pfhip_status pfhip_offline_forward_hwsets_s16(pfhip_model* head, const int16_t* 
 static pfhip_status offline_forward_nbest(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch,
                                           const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
                                           pfhip_out* out, const pfhip_nbest* nb) {
-  if (head && head->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
+  if (head && head->weights->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
     g_err.clear();
     return fail(PFHIP_ERR_ARG, "bad argument");
   }
@@ -2098,7 +2094,7 @@ pfhip_status pfhip_offline_forward_nbest_s16(pfhip_model* head, const int16_t* c
 // device-pointer form: k candidates for the following pfhip_offline_enqueue calls of this handle (context 0); 0 = off
 pfhip_status pfhip_set_nbest(pfhip_model* m, int k) {
   g_err.clear();
-  if (!m || k < 0 || k > pfhip::kTopkMax || k > m->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k outside 0..8 (or above the vocabulary)");
+  if (!m || k < 0 || k > pfhip::kTopkMax || k > m->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k outside 0..8 (or above the vocabulary)");
   std::lock_guard<std::mutex> lk(m->mu);
   m->nbest_enqueue_k = k;
   return PFHIP_OK;
@@ -2128,7 +2124,7 @@ static pfhip_status offline_forward_resident(pfhip_model* head, PcmView d_pcm, c
                                              int batch, pfhip_out* out) {
   g_err.clear();
   if (!head || !d_pcm.p || !sample_off || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (head->cfg.contextual && !default_hotwords(head)) return fail(PFHIP_ERR_ARG, "hw_emb is null");
+  if (head->weights->cfg.contextual && !default_hotwords(head)) return fail(PFHIP_ERR_ARG, "hw_emb is null");
   pfhip_model* m = acquire_slot(head);
   tl_last_replica = m;
   pfhip_status st;
@@ -2160,7 +2156,7 @@ pfhip_status pfhip_offline_forward_resident_s16(pfhip_model* head, const int16_t
 // pfhip_offline_forward at the caller's rate: resampled on the device into the slot's PCM workspace, then the same forward
 static pfhip_status offline_forward_rate(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, int sample_rate,
                                          const float* hw_emb, int n_hotwords, pfhip_out* out) {
-  if (head && sample_rate == head->cfg.sample_rate) {
+  if (head && sample_rate == head->weights->cfg.sample_rate) {
     const HwSets same{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
     return offline_forward_sets(head, pcm, n_samples, batch, same, out);
   }
@@ -2169,7 +2165,7 @@ static pfhip_status offline_forward_rate(pfhip_model* head, HostPcm pcm, const i
   for (int i = 0; i < batch; ++i)
     if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm.p[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
   std::string why;
-  if (!pfhip_detail::resample_supported(sample_rate, head->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
+  if (!pfhip_detail::resample_supported(sample_rate, head->weights->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
   pfhip_model* m = acquire_slot(head);                  // not merged with other callers: one rate pair per packed batch
   tl_last_replica = m;
   const HwSets hw{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
@@ -2192,7 +2188,7 @@ pfhip_status pfhip_resample(pfhip_model* head, const float* const* pcm, const in
                             const int* cap, int* n_out) {
   g_err.clear();
   if (!head || !pcm || !n_samples || batch <= 0 || !out || !cap || !n_out) return fail(PFHIP_ERR_ARG, "bad argument");
-  const int fs_out = head->cfg.sample_rate;
+  const int fs_out = head->weights->cfg.sample_rate;
   std::string why;
   if (!pfhip_detail::resample_supported(fs_in, fs_out, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
   bool short_cap = false;
@@ -2308,7 +2304,7 @@ static pfhip_status pin_default_hotwords(pfhip_model* owner, const float* hw_emb
     bool hit = false;
     const int id = D.bank.acquire(hw_emb, H, &hit);
     if (id >= 0 && !hit) {
-      HIP_TRY(owner->hw.ensure((size_t)round_up(H, pfhip::kTileM) * owner->cfg.d_model * 4));
+      HIP_TRY(owner->hw.ensure((size_t)round_up(H, pfhip::kTileM) * owner->weights->cfg.d_model * 4));
       const pfhip_status st = fill_slab_locked(owner, D, id, 0, owner->own_stream);
       if (st) return st;
       HIP_TRY(hipStreamSynchronize(owner->own_stream));
@@ -2330,14 +2326,14 @@ static std::vector<pfhip_model*> device_owners(pfhip_model* head) {
 pfhip_status pfhip_set_hotwords(pfhip_model* m, const float* hw_emb, int n_hotwords) {
   g_err.clear();
   if (!m || !hw_emb || n_hotwords <= 0) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (!m->cfg.contextual) return fail(PFHIP_ERR_UNSUPPORTED, "model has no bias decoder (use_hotword == false)");
+  if (!m->weights->cfg.contextual) return fail(PFHIP_ERR_UNSUPPORTED, "model has no bias decoder (use_hotword == false)");
   if (m->group_head || m->weights_of) return fail(PFHIP_ERR_ARG, "not the handle pfhip_create returned");
   for (pfhip_model* r : device_owners(m)) {          // one bank per device, shared by its contexts
     std::lock_guard<std::mutex> lk(r->mu);
     const pfhip_status st = pin_default_hotwords(r, hw_emb, n_hotwords);
     if (st) return st;
   }
-  auto copy = std::make_shared<const std::vector<float>>(hw_emb, hw_emb + (size_t)n_hotwords * m->cfg.d_model);
+  auto copy = std::make_shared<const std::vector<float>>(hw_emb, hw_emb + (size_t)n_hotwords * m->weights->cfg.d_model);
   std::lock_guard<std::mutex> l(m->bq.mu);
   m->hw_default = std::move(copy);
   return PFHIP_OK;
@@ -2375,7 +2371,7 @@ pfhip_status pfhip_set_hotword_bank_bytes(pfhip_model* m, int64_t bytes) {
       ensure_bank_locked(r);
     }
     if (def && !def->empty()) {
-      const pfhip_status st = pin_default_hotwords(r, def->data(), (int)(def->size() / (size_t)m->cfg.d_model));
+      const pfhip_status st = pin_default_hotwords(r, def->data(), (int)(def->size() / (size_t)m->weights->cfg.d_model));
       if (st) return st;
     }
   }
@@ -2386,7 +2382,7 @@ pfhip_status pfhip_hotword_bank_stats(pfhip_model* m, pfhip_hwbank_stats* out) {
   g_err.clear();
   if (!m || !out) return fail(PFHIP_ERR_ARG, "bad argument");
   *out = pfhip_hwbank_stats{};
-  const int64_t row_bytes = (int64_t)2 * m->cfg.d_model * 4;
+  const int64_t row_bytes = (int64_t)2 * m->weights->cfg.d_model * 4;
   for (pfhip_model* r : device_owners(m)) {
     HwBankDev& D = *r->hwbank;
     std::lock_guard<std::mutex> l(D.mu);
@@ -2418,7 +2414,7 @@ pfhip_status pfhip_warm_up(pfhip_model* m, int batch, int n_samples) {
   std::vector<int> lens((size_t)batch, n_samples);
   const int max_tok = n_samples / 960 + 2;
   std::vector<int32_t> ids((size_t)batch * max_tok), tn(batch), nf(batch), fr(batch);
-  std::vector<float> hw(m->cfg.contextual ? (size_t)m->cfg.d_model : 0, 0.f);
+  std::vector<float> hw(m->weights->cfg.contextual ? (size_t)m->weights->cfg.d_model : 0, 0.f);
   for (pfhip_model* r : all_slots(m)) {
     pfhip_out out{};
     out.token_ids = ids.data(); out.token_num = tn.data(); out.n_fires = nf.data(); out.n_frames = fr.data(); out.max_tokens = max_tok;
@@ -2430,8 +2426,8 @@ pfhip_status pfhip_warm_up(pfhip_model* m, int batch, int n_samples) {
   return PFHIP_OK;
 }
 
-int pfhip_is_contextual(const pfhip_model* m) { return m ? m->cfg.contextual : 0; }
-int pfhip_has_timestamp_head(const pfhip_model* m) { return m ? m->cfg.timestamp : 0; }
+int pfhip_is_contextual(const pfhip_model* m) { return m ? m->weights->cfg.contextual : 0; }
+int pfhip_has_timestamp_head(const pfhip_model* m) { return m ? m->weights->cfg.timestamp : 0; }
 
 // model_eb.onnx Run + row selection (paraformer.cpp:656-685): Embedding -> 1-layer LSTM over the 10 padded positions,
 // output of hotword j taken at step lengths[j]-1.
@@ -2439,19 +2435,19 @@ pfhip_status pfhip_hotword_embed(pfhip_model* m, const int32_t* hotword_matrix, 
                                  float* out) {
   g_err.clear();
   if (!m || !hotword_matrix || !lengths || n_hotwords <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (!m->cfg.contextual) return fail(PFHIP_ERR_UNSUPPORTED, "model has no hotword embedder (use_hotword == false)");
-  const int H = n_hotwords, L = 10, d = m->cfg.d_model;
+  if (!m->weights->cfg.contextual) return fail(PFHIP_ERR_UNSUPPORTED, "model has no hotword embedder (use_hotword == false)");
+  const int H = n_hotwords, L = 10, d = m->weights->cfg.d_model;
   for (int j = 0; j < H; ++j) {
     if (lengths[j] < 1 || lengths[j] > L) return fail(PFHIP_ERR_ARG, "hotword length outside 1..10");
     for (int t = 0; t < L; ++t)
-      if (hotword_matrix[j * L + t] < 0 || hotword_matrix[j * L + t] >= m->cfg.vocab) return fail(PFHIP_ERR_ARG, "hotword id outside the vocabulary");
+      if (hotword_matrix[j * L + t] < 0 || hotword_matrix[j * L + t] >= m->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "hotword id outside the vocabulary");
   }
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
   const int R = L * H, Rp = round_up(R, pfhip::kTileM), Hp = round_up(H, pfhip::kTileM);
+  const Contextual& bias = m->weights->bias;
   Buf ids, lens, X, GX, G, hc;
-  struct Free { Buf* b[6]; ~Free() { for (Buf* x : b) x->release(); } } fr{{&ids, &lens, &X, &GX, &G, &hc}};
   HIP_TRY(ids.ensure((size_t)R * 4)); HIP_TRY(lens.ensure((size_t)H * 4));
   HIP_TRY(X.ensure((size_t)Rp * d * 4)); HIP_TRY(GX.ensure((size_t)(Rp + pfhip::kTileM) * 4 * d * 4)); HIP_TRY(G.ensure((size_t)Hp * 4 * d * 4));
   HIP_TRY(hc.ensure((size_t)3 * Hp * d * 4));
@@ -2462,11 +2458,10 @@ pfhip_status pfhip_hotword_embed(pfhip_model* m, const int32_t* hotword_matrix, 
   HIP_TRY(hipMemcpyAsync(lens.p, lengths, (size_t)H * 4, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(hc.p, 0, (size_t)3 * Hp * d * 4, s));
   float* h = hc.f(); float* cst = h + (size_t)Hp * d; float* sel = cst + (size_t)Hp * d;
-  pfhip::launch_gather_rows(static_cast<const int32_t*>(ids.p), m->W("bias.embed.w").d, d, X.f(), R, s);
-  gemm(m, s, X.f(), d, m->W("bias.lstm.w_ih").d, 4 * d, d, d, GX.f(), 4 * d, m->W("bias.lstm.b_ih").d, nullptr, 0, nullptr, 0, R, false);
+  pfhip::launch_gather_rows(static_cast<const int32_t*>(ids.p), bias.embed_w, d, X.f(), R, s);
+  gemm(m, s, X.f(), d, bias.lstm_ih, 4 * d, d, d, GX.f(), 4 * d, nullptr, 0, nullptr, 0, R, false);
   for (int t = 0; t < L; ++t) {
-    gemm(m, s, h, d, m->W("bias.lstm.w_hh").d, 4 * d, d, d, G.f(), 4 * d, m->W("bias.lstm.b_hh").d, GX.f() + (size_t)t * H * 4 * d,
-         4 * d, nullptr, 0, H, false);
+    gemm(m, s, h, d, bias.lstm_hh, 4 * d, d, d, G.f(), 4 * d, GX.f() + (size_t)t * H * 4 * d, 4 * d, nullptr, 0, H, false);
     pfhip::launch_lstm_cell(G.f(), cst, h, static_cast<const int32_t*>(lens.p), t, sel, H, d, s);
   }
   HIP_TRY(hipMemcpyAsync(out, sel, (size_t)H * d * 4, hipMemcpyDeviceToHost, s));
@@ -2489,7 +2484,7 @@ pfhip_status pfhip_extract_feats(pfhip_model* m, const float* const* pcm, const 
   st = enqueue_locked(m, PcmView{m->pcm.p, false}, off.data(), n_samples, batch, s, true);
   if (st) return st;
   if (n_frames_out) for (int b = 0; b < batch; ++b) n_frames_out[b] = m->T[b];
-  const size_t n = (size_t)m->M * m->feat_dim;
+  const size_t n = (size_t)m->M * m->weights->feat_dim;
   if (feats_out) {
     if (n > feats_cap_floats) return fail(PFHIP_ERR_CAPACITY, "feats_out too small");
     if (n) HIP_TRY(hipMemcpyAsync(feats_out, m->feats.p, n * 4, hipMemcpyDeviceToHost, s));
@@ -2509,8 +2504,8 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   const std::string nm(name);
   const void* src = nullptr;
   size_t n = 0;
-  const int d = m->cfg.d_model;
-  if (nm == "feats") { src = m->feats.p; n = (size_t)m->M * m->feat_dim; }
+  const int d = m->weights->cfg.d_model;
+  if (nm == "feats") { src = m->feats.p; n = (size_t)m->M * m->weights->feat_dim; }
   else if (nm == "enc") { src = m->enc.p; n = (size_t)m->M * d; }
   else if (nm == "alphas") { src = m->alphas.p; n = (size_t)m->M; }
   else if (nm == "emb") { src = m->emb.p; n = (size_t)m->ML * d; }
@@ -2519,7 +2514,7 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   else if (nm == "ts_y" && m->have_ts) { src = m->ts_y.p; n = (size_t)3 * m->M * 2 * d; }
   else if (nm == "logp") {
     if (m->ML && !m->have_logp) { pfhip_status st = head_locked(m, s, true); if (st) return st; }
-    src = m->logp.p; n = (size_t)m->ML * m->cfg.vocab;
+    src = m->logp.p; n = (size_t)m->ML * m->weights->cfg.vocab;
   }
   // the last forward's candidates [token rows][k] (k as it was computed); the ids are int32 words in the float buffer
   else if (nm == "nbest_ids" && m->nbest_k) { src = m->nb_ids.p; n = (size_t)m->ML * m->nbest_k; }
@@ -2548,8 +2543,8 @@ pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value) {
   if (std::string(what) == "plane_forwards") return (pfhip_status)m->plane_forwards;        // read-out: forwards on plane-image operands
   if (std::string(what) == "kvplane_forwards") return (pfhip_status)m->kvplane_forwards;     // ... whose attention took K | V as planes
   if (std::string(what) == "dec_plane_forwards") return (pfhip_status)m->dec_plane_forwards; // ... whose decoder took the plane path too
-  if (std::string(what) == "static_bound") return (pfhip_status)std::min(m->static_bound, 2.0e9);      // read-out: the load-time activation bound
-  if (std::string(what) == "always_exact") return (pfhip_status)(m->always_exact ? 1 : 0);
+  if (std::string(what) == "static_bound") return (pfhip_status)std::min(m->weights->static_bound, 2.0e9);      // read-out: the load-time activation bound
+  if (std::string(what) == "always_exact") return (pfhip_status)(m->weights->always_exact ? 1 : 0);
   if (std::string(what) == "format_splits") {         // read-out: merged batches cut short because callers of both sample formats were queued
     std::lock_guard<std::mutex> ql(m->bq.mu);
     return (pfhip_status)m->format_splits;

@@ -29,11 +29,11 @@ struct pfhip_punc {
   int vocab = 0, d = 256, n_head = 8, ffn = 1024, layers = 4, n_punc = 6, sanm_shift = 0;
   float* d_table = nullptr;
   float* d_inv_ts = nullptr;
-  struct Layer { float *n1g, *n1b, *n2g, *n2b, *fsmn; Lin qkv, out, ffn1, ffn2; };
+  struct Layer { float *n1g, *n1b, *n2g, *n2b, *fsmn; PackedLin qkv, out, ffn1, ffn2; };
   std::vector<Layer> L;
   float *an_g = nullptr, *an_b = nullptr;
-  Lin head;
-  std::vector<float*> owned;
+  PackedLin head;
+  std::vector<DevMem> owned;      // the vectors and tables behind the raw pointers above
   Buf ids, x, y, qkv, mem, ctx, h, logits, punc, meta, lim;
   int* h_pin = nullptr;
   // pinned staging for one (batched) call: [ids | pos | lim | off | len] in, punctuation ids out
@@ -50,6 +50,14 @@ struct pfhip_punc {
   // merging of concurrent callers (pfhip_set_punc_batching)
   pfhip_detail::MergeQueue<PuncReq> mq;
   int q_wait_us = 0, q_max = 1;
+  // the device set and idle before any member gives its memory back (a create that returns early comes through here too)
+  ~pfhip_punc() {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();
+    if (h_pin) (void)hipHostFree(h_pin);
+    if (h_stage) (void)hipHostFree(h_stage);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 extern "C" {
@@ -101,9 +109,10 @@ pfhip_status pfhip_punc_create_from_memory(const void* blob, size_t blob_bytes, 
     return true;
   };
   auto dev_copy = [&](const float* src, size_t n, float** dst) -> pfhip_status {
-    HIP_TRY(hipMalloc((void**)dst, n * 4));
-    HIP_TRY(hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
-    p->owned.push_back(*dst);
+    DevMem mem;
+    HIP_TRY(mem.upload(src, n * 4));
+    *dst = mem.f();
+    p->owned.push_back(std::move(mem));
     return PFHIP_OK;
   };
   auto vec = [&](const std::string& name, int n, float** dst) -> pfhip_status {
@@ -111,7 +120,7 @@ pfhip_status pfhip_punc_create_from_memory(const void* blob, size_t blob_bytes, 
     if (!get(name, {n}, &src)) return PFHIP_ERR_FORMAT;
     return dev_copy(src, n, dst);
   };
-  auto lin = [&](const std::string& name, int N, int K, Lin* l) -> pfhip_status {
+  auto lin = [&](const std::string& name, int N, int K, PackedLin* l) -> pfhip_status {
     const float *w = nullptr, *b = nullptr;
     if (!get(name + ".w", {N, K}, &w) || !get(name + ".b", {N}, &b)) return PFHIP_ERR_FORMAT;
     return pack_linear(w, b, N, K, l);
@@ -151,19 +160,7 @@ pfhip_status pfhip_punc_create_from_memory(const void* blob, size_t blob_bytes, 
   return PFHIP_OK;
 }
 
-void pfhip_punc_destroy(pfhip_punc* p) {
-  if (!p) return;
-  (void)hipSetDevice(p->device);
-  (void)hipDeviceSynchronize();
-  for (Buf* b : {&p->ids, &p->x, &p->y, &p->qkv, &p->mem, &p->ctx, &p->h, &p->logits, &p->punc, &p->meta, &p->lim}) b->release();
-  for (auto& l : p->L) { free_lin(l.qkv); free_lin(l.out); free_lin(l.ffn1); free_lin(l.ffn2); }
-  free_lin(p->head);
-  for (float* q : p->owned) (void)hipFree(q);
-  if (p->h_pin) (void)hipHostFree(p->h_pin);
-  if (p->h_stage) (void)hipHostFree(p->h_stage);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
-}
+void pfhip_punc_destroy(pfhip_punc* p) { delete p; }
 
 int pfhip_punc_num_classes(const pfhip_punc* p) { return p ? p->n_punc : 0; }
 

@@ -103,34 +103,23 @@ void build_resample_plan(int fs_in, int fs_out, ResamplePlan* p) {
   for (int i = 0; i < p->Q; ++i) std::copy(rows[i].begin(), rows[i].end(), p->w.begin() + (size_t)i * p->K);
 }
 
-ResampleCache::~ResampleCache() {
-  for (auto& kv : plans) {
-    (void)hipFree(const_cast<int*>(kv.second.first));
-    (void)hipFree(const_cast<int*>(kv.second.ntap));
-    (void)hipFree(const_cast<float*>(kv.second.w));
-  }
-}
-
 pfhip_status ResampleCache::get(int device, int fs_in, int fs_out, pfhip::ResampleTable* out) {
   std::string why;
   if (!resample_supported(fs_in, fs_out, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
   std::lock_guard<std::mutex> lk(mu);
   const auto key = std::make_tuple(device, fs_in, fs_out);
   auto it = plans.find(key);
-  if (it != plans.end()) { *out = it->second; return PFHIP_OK; }
+  if (it != plans.end()) { *out = it->second.t; return PFHIP_OK; }
   ResamplePlan p;
   build_resample_plan(fs_in, fs_out, &p);
-  int* d_first = nullptr; int* d_ntap = nullptr; float* d_w = nullptr;
+  Plan dev;
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipMalloc((void**)&d_first, p.first.size() * 4));
-  HIP_TRY(hipMalloc((void**)&d_ntap, p.ntap.size() * 4));
-  HIP_TRY(hipMalloc((void**)&d_w, std::max<size_t>(p.w.size(), 1) * 4));
-  HIP_TRY(hipMemcpy(d_first, p.first.data(), p.first.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_ntap, p.ntap.data(), p.ntap.size() * 4, hipMemcpyHostToDevice));
-  if (!p.w.empty()) HIP_TRY(hipMemcpy(d_w, p.w.data(), p.w.size() * 4, hipMemcpyHostToDevice));
-  const pfhip::ResampleTable t{d_first, d_ntap, d_w, p.P, p.Q, p.K};
-  plans.emplace(key, t);
-  *out = t;
+  HIP_TRY(dev.first.upload(p.first));
+  HIP_TRY(dev.ntap.upload(p.ntap));
+  HIP_TRY(dev.w.upload(p.w));
+  dev.t = pfhip::ResampleTable{dev.first.as<int>(), dev.ntap.as<int>(), dev.w.f(), p.P, p.Q, p.K};
+  *out = dev.t;
+  plans.emplace(key, std::move(dev));
   return PFHIP_OK;
 }
 

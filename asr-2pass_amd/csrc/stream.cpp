@@ -76,13 +76,13 @@ constexpr int kMaxTok = 72;
 
 pfhip_status stream_alloc(pfhip_stream* s) {
   pfhip_model* m = s->m;
-  const int d = m->cfg.d_model, FD = m->feat_dim, FP = m->feat_pad;
+  const int d = m->weights->cfg.d_model, FD = m->weights->feat_dim, FP = m->weights->feat_pad;
   for (int i = 0; i < 2; ++i) HIP_TRY(s->fb[i].ensure((size_t)kMaxFrames * 80 * 4));
   HIP_TRY(s->rows.ensure((size_t)kMaxRows * FD * 4));
   HIP_TRY(s->featc.ensure((size_t)16 * FD * 4));
   HIP_TRY(s->chunk.ensure((size_t)128 * FP * 4));
   HIP_TRY(s->carry.ensure((size_t)(d + 4) * 4));
-  HIP_TRY(s->dcache.ensure((size_t)std::max(1, m->cfg.dec_layers) * 10 * d * 4));
+  HIP_TRY(s->dcache.ensure((size_t)std::max(1, m->weights->cfg.dec_layers) * 10 * d * 4));
   return PFHIP_OK;
 }
 
@@ -95,9 +95,9 @@ pfhip_status init_cache(pfhip_stream* s, hipStream_t st) {
   s->n_featc = s->chunk_size[0] + s->chunk_size[2];
   s->featc_idx.resize((size_t)s->n_featc);
   for (int i = 0; i < s->n_featc; ++i) s->featc_idx[i] = i - s->n_featc;     // the zero rows: before row 0
-  HIP_TRY(hipMemsetAsync(s->carry.p, 0, (size_t)(m->cfg.d_model + 4) * 4, st));
-  HIP_TRY(hipMemsetAsync(s->featc.p, 0, (size_t)16 * m->feat_dim * 4, st));
-  HIP_TRY(hipMemsetAsync(s->dcache.p, 0, (size_t)std::max(1, m->cfg.dec_layers) * 10 * m->cfg.d_model * 4, st));
+  HIP_TRY(hipMemsetAsync(s->carry.p, 0, (size_t)(m->weights->cfg.d_model + 4) * 4, st));
+  HIP_TRY(hipMemsetAsync(s->featc.p, 0, (size_t)16 * m->weights->feat_dim * 4, st));
+  HIP_TRY(hipMemsetAsync(s->dcache.p, 0, (size_t)std::max(1, m->weights->cfg.dec_layers) * 10 * m->weights->cfg.d_model * 4, st));
   return PFHIP_OK;
 }
 
@@ -131,7 +131,8 @@ struct Recorder {
 
 pfhip_status flush(pfhip_model* m, Recorder& r, hipStream_t st) {
   if (r.empty()) return PFHIP_OK;
-  const Config& c = m->cfg;
+  const ModelWeights& w = *m->weights;
+  const Config& c = w.cfg;
   // ---- fbank of all new audio in one launch: PCM staged back to back, frames into a batch buffer -----------------
   const int U = (int)r.pcm_src.size();
   size_t total_samples = 0;
@@ -143,14 +144,9 @@ pfhip_status flush(pfhip_model* m, Recorder& r, hipStream_t st) {
   const size_t meta_bytes = ((size_t)U * 8 + (size_t)(U + 1) * 4 + (size_t)U * 4 + 63) & ~(size_t)63;
   const size_t ops_bytes = n_ops * sizeof(pfhip::RowsCopyOp) + 64;
   const size_t pin_bytes = meta_bytes + ops_bytes + total_samples * 4 + 256;
-  if (pin_bytes > m->h_ops_cap) {
-    if (m->h_ops) HIP_TRY(hipHostFree(m->h_ops));
-    m->h_ops = nullptr; m->h_ops_cap = 0;
-    HIP_TRY(hipHostMalloc(&m->h_ops, pin_bytes * 2, hipHostMallocDefault));
-    m->h_ops_cap = pin_bytes * 2;
-  }
+  HIP_TRY(m->h_ops.ensure(pin_bytes));
   HIP_TRY(m->d_ops.ensure(meta_bytes + ops_bytes));
-  char* hp = static_cast<char*>(m->h_ops);
+  char* hp = static_cast<char*>(m->h_ops.p);
   char* dp = static_cast<char*>(m->d_ops.p);
   if (U > 0) {
     HIP_TRY(m->pcm.ensure((total_samples + 1024) * 4));
@@ -169,7 +165,7 @@ pfhip_status flush(pfhip_model* m, Recorder& r, hipStream_t st) {
     h_foff[U] = fo;
     HIP_TRY(hipMemcpyAsync(m->pcm.p, h_pcm, total_samples * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dp, hp, meta_bytes, hipMemcpyHostToDevice, st));
-    pfhip::FbankTables tb{m->d_window, m->d_tw, m->d_mel_off, m->d_mel_size, m->d_mel_w, m->W("cmvn.mean").d, m->W("cmvn.istd").d};
+    const pfhip::FbankTables tb = w.ft.fbank(w.cmvn_mean, w.cmvn_istd);
     pfhip::launch_fbank_frames_batch(m->pcm.f(), reinterpret_cast<const int64_t*>(dp), reinterpret_cast<const int*>(dp + (size_t)U * 8),
                                      reinterpret_cast<const int*>(dp + (size_t)U * 8 + (size_t)(U + 1) * 4), U, total_frames, tb,
                                      m->fbk.f(), st);
@@ -200,7 +196,7 @@ pfhip_status flush(pfhip_model* m, Recorder& r, hipStream_t st) {
     int mx = 0;
     for (const auto& o : r.lfr) mx = std::max(mx, o.n_rows);
     pfhip::launch_stream_lfr_batch(reinterpret_cast<const pfhip::StreamLfrOp*>(d_ops + lfr_off), (int)r.lfr.size(), mx,
-                                   m->W("cmvn.mean").d, m->W("cmvn.istd").d, sqrtf((float)c.d_model), m->d_inv_ts, m->feat_dim, st);
+                                   w.cmvn_mean, w.cmvn_istd, sqrtf((float)c.d_model), w.inv_ts, w.feat_dim, st);
   }
   run_copies(Recorder::kSpliceRotate);
   run_copies(Recorder::kWindow);
@@ -216,8 +212,9 @@ pfhip_status flush(pfhip_model* m, Recorder& r, hipStream_t st) {
 // buffer.  Appends each stream's ids to outs[b].
 pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& ss, hipStream_t st,
                              const std::vector<std::vector<int32_t>*>& outs, bool want_logp, Recorder& rec) {
-  const Config& c = m->cfg;
-  const int d = c.d_model, FD = m->feat_dim, FP = m->feat_pad, B = (int)ss.size();
+  const ModelWeights& w = *m->weights;
+  const Config& c = w.cfg;
+  const int d = c.d_model, FD = w.feat_dim, FP = w.feat_pad, B = (int)ss.size();
   const int hd = d / c.n_head;                    // 128, or 80 (the small Paraformer)
   const float att_scale = 1.0f / sqrtf((float)hd);
   const int hdd = d / c.dec_n_head;               // the decoder's (decoder_conf.attention_heads)
@@ -259,12 +256,10 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   HIP_TRY(m->sseg.ensure((size_t)B * sizeof(pfhip::StreamSeg)));
   {   // pinned staging: first half = this upload, second half = the post-CIF upload
     const size_t half = ((n_meta * 4 + 15) & ~(size_t)15) + (size_t)B * sizeof(pfhip::StreamSeg) + 64;
-    pfhip_status ps = ensure_h_meta(m, 2 * half);
-    if (ps) return ps;
-    ps = ensure_h_counts(m, std::max((size_t)2 * B, n_counts) * 4);
-    if (ps) return ps;
+    HIP_TRY(m->h_meta.ensure(2 * half));
+    HIP_TRY(m->h_counts.ensure(std::max((size_t)2 * B, n_counts) * 4));
   }
-  int* hm = static_cast<int*>(m->h_meta);
+  int* hm = m->h_meta.i();
   int* dm = m->dmeta.i();
   int* d_off = dm; int* d_len = dm + B; int* d_tok_off = dm + 2 * B; int* d_tok_len = dm + 3 * B;
   int* d_row_pos = dm + 4 * B; int* d_row_len = d_row_pos + M; int* d_src_row = d_row_len + M;
@@ -272,8 +267,8 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     hm[b] = segs[b].row_off; hm[B + b] = segs[b].n; hm[2 * B + b] = 0; hm[3 * B + b] = 0;
     for (int t = 0; t < segs[b].n; ++t) { hm[4 * B + segs[b].row_off + t] = t; hm[4 * B + M + segs[b].row_off + t] = segs[b].n; }
   }
-  pfhip::StreamSeg* h_segs = reinterpret_cast<pfhip::StreamSeg*>(static_cast<char*>(m->h_meta) + ((n_meta * 4 + 15) & ~(size_t)15));
-  if (((n_meta * 4 + 15) & ~(size_t)15) + (size_t)B * sizeof(pfhip::StreamSeg) > m->h_meta_cap)
+  pfhip::StreamSeg* h_segs = reinterpret_cast<pfhip::StreamSeg*>(static_cast<char*>(m->h_meta.p) + ((n_meta * 4 + 15) & ~(size_t)15));
+  if (((n_meta * 4 + 15) & ~(size_t)15) + (size_t)B * sizeof(pfhip::StreamSeg) > m->h_meta.cap)
     return fail(PFHIP_ERR_CAPACITY, "too many stream rows in one batch");
   std::memcpy(h_segs, segs.data(), (size_t)B * sizeof(pfhip::StreamSeg));
   HIP_TRY(hipMemcpyAsync(dm, hm, (4 * (size_t)B + 2 * (size_t)M) * 4, hipMemcpyHostToDevice, st));
@@ -294,112 +289,100 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   static const bool fused_on = pfhip::env_on("PFHIP_STREAM_FUSED");
   const bool lean = fused_on && B == 1 && M <= 32;
   static const bool att_out_on = pfhip::env_is1("PFHIP_STREAM_ATT_OUT");
-  auto ln_gemm = [&](const float* X, int ldx, int D, const std::string& norm, const float* Wd, int ldw, float* Cd, int ldc,
-                     const float* bias, const float* R1, int ldr1, const float* R2, int ldr2, const float* fv, int ldv,
+  // LayerNorm `nm` (null: none) of X, then L
+  auto ln_gemm = [&](const float* X, int ldx, int D, const Norm* nm, const Linear& L, int ldw, float* Cd, int ldc,
+                     const float* R1, int ldr1, const float* R2, int ldr2, const float* fv, int ldv,
                      const float* fw, int rows, int N, int K, bool relu) {
-    pfhip::launch_fused_ln_gemm(X, ldx, D, norm.empty() ? nullptr : m->W(norm + ".g").d, norm.empty() ? nullptr : m->W(norm + ".b").d,
-                                1e-12f, Wd, ldw, Cd, ldc, bias, R1, ldr1, R2, ldr2, fv, ldv, fw, rows, N, K, relu, st);
+    pfhip::launch_fused_ln_gemm(X, ldx, D, nm ? nm->g : nullptr, nm ? nm->b : nullptr, 1e-12f, L.w, ldw, Cd, ldc, L.b, R1, ldr1, R2, ldr2,
+                                fv, ldv, fw, rows, N, K, relu, st);
   };
   // one-trip form of the same launches where the shape allows (stream_fused.hip: every operand requested at once, LayerNorm
-  // applied algebraically on the gamma/beta-folded weights built at load); false -> the caller uses ln_gemm
-  auto gemv1 = [&](const float* X, int ldx, const float* Wd, int ldw, float* Cd, int ldc, const float* bias, const float* colsum,
+  // applied algebraically on the gamma/beta-folded weights built at load: colsum); false -> the caller uses ln_gemm
+  auto gemv1 = [&](const float* X, int ldx, const Linear& L, int ldw, float* Cd, int ldc, const float* colsum,
                    const float* R1, int ldr1, const float* fv, int ldv, const float* fw, int rows, int N, int K, bool relu) {
-    return Wd && pfhip::launch_fused_gemv_1trip(X, ldx, Wd, ldw, Cd, ldc, bias, colsum, 1e-12f, R1, ldr1, fv, ldv, fw, rows, N, K, relu, st);
+    return L.w && pfhip::launch_fused_gemv_1trip(X, ldx, L.w, ldw, Cd, ldc, L.b, colsum, 1e-12f, R1, ldr1, fv, ldv, fw, rows, N, K, relu, st);
   };
-  const bool fuse_ln_s = !lean && m->d_lnw_qkv != nullptr && pfhip::gemm_x6_ln_ok(M);
+  // the same on a LayerNorm-folded weight; false too where the fold was not built
+  auto gemv1_ln = [&](const float* X, int ldx, const FoldLin& F, int ldw, float* Cd, int ldc, int rows, int N, int K, bool relu) {
+    return gemv1(X, ldx, F.folded, ldw, Cd, ldc, F.colsum, nullptr, 0, nullptr, 0, nullptr, rows, N, K, relu);
+  };
+  const bool fuse_ln_s = !lean && w.enc_folded && pfhip::gemm_x6_ln_ok(M);
   if (fuse_ln_s) HIP_TRY(m->lnstats.ensure((size_t)(M + 256) * 4 * 2 * 4));
   // ---- streaming encoder session (:448): SAN-M stack on the windows as given (no scale/PE inside) --------
   for (int i = 0; i < c.enc_layers; ++i) {
-    const std::string p = "enc." + std::to_string(i) + ".";
+    const EncLayer& L = w.enc[(size_t)i];
     const bool first = i == 0;
     const float* xin = first ? m->x0.f() : x;
     const int ldin = first ? FP : d, Din = first ? FD : d, Kp = first ? FP : d;
     if (lean) {
       // 5 launches: LN1+QKV | attention | out-projection + FSMN memory + residual | LN2+FFN1 | FFN2 + residual
-      if (first || !m->d_lnw_qkv ||
-          !gemv1(x, d, m->d_lnw_qkv + (size_t)i * 3 * d * d, d, m->qkv.f(), 3 * d, m->d_lnb_qkv + (size_t)i * 3 * d,
-                 m->d_lns_qkv + (size_t)i * 3 * d, nullptr, 0, nullptr, 0, nullptr, M, 3 * d, d, false))
-        ln_gemm(xin, ldin, Din, p + "norm1", first ? m->d_w0qkv : m->W(p + "qkv.w").d, Kp, m->qkv.f(), 3 * d, m->W(p + "qkv.b").d,
-                nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, 3 * d, Kp, false);
+      if (!gemv1_ln(x, d, L.qkv_f, d, m->qkv.f(), 3 * d, M, 3 * d, d, false))      // (layer 0 has no folded qkv)
+        ln_gemm(xin, ldin, Din, &L.norm1, L.qkv, Kp, m->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, 3 * d, Kp, false);
       // attention + output projection + FSMN memory + residual as one launch (every workgroup redoes the attention) is opt-in:
       // measured slower than the two launches (stream_fused.hip, launch_fused_att_out)
       if (!att_out_on || hd != pfhip::kHeadDim || !pfhip::launch_fused_att_out(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, M, M, c.n_head, att_scale,
-                                       m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, first ? nullptr : x, d, m->qkv.f() + 2 * d,
-                                       3 * d, m->W(p + "fsmn.w").d, d, st)) {
+                                       L.out.w, d, x, d, L.out.b, first ? nullptr : x, d, m->qkv.f() + 2 * d,
+                                       3 * d, L.fsmn_w, d, st)) {
         if (!pfhip::launch_window_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, M, M,
                                             c.n_head, att_scale, st, hd))
           pfhip::launch_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
                                   d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st, hd);
-        if (!gemv1(m->ctx.f(), d, m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, nullptr, first ? nullptr : x, d, m->qkv.f() + 2 * d,
-                   3 * d, m->W(p + "fsmn.w").d, M, d, d, false))
-          ln_gemm(m->ctx.f(), d, 0, "", m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, first ? nullptr : x, d, nullptr, 0,
-                  m->qkv.f() + 2 * d, 3 * d, m->W(p + "fsmn.w").d, M, d, d, false);
+        if (!gemv1(m->ctx.f(), d, L.out, d, x, d, nullptr, first ? nullptr : x, d, m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, M, d, d, false))
+          ln_gemm(m->ctx.f(), d, 0, nullptr, L.out, d, x, d, first ? nullptr : x, d, nullptr, 0,
+                  m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, M, d, d, false);
       }
-      if (!m->d_lnw_ffn1 ||
-          !gemv1(x, d, m->d_lnw_ffn1 + (size_t)i * c.ffn * d, d, m->hbuf.f(), c.ffn, m->d_lnb_ffn1 + (size_t)i * c.ffn,
-                 m->d_lns_ffn1 + (size_t)i * c.ffn, nullptr, 0, nullptr, 0, nullptr, M, c.ffn, d, true))
-        ln_gemm(x, d, d, p + "norm2", m->W(p + "ffn1.w").d, d, m->hbuf.f(), c.ffn, m->W(p + "ffn1.b").d, nullptr, 0, nullptr, 0,
-                nullptr, 0, nullptr, M, c.ffn, d, true);
-      if (!gemv1(m->hbuf.f(), c.ffn, m->W(p + "ffn2.w").d, c.ffn, x, d, m->W(p + "ffn2.b").d, nullptr, x, d, nullptr, 0, nullptr, M, d,
-                 c.ffn, false))
-        ln_gemm(m->hbuf.f(), c.ffn, 0, "", m->W(p + "ffn2.w").d, c.ffn, x, d, m->W(p + "ffn2.b").d, x, d, nullptr, 0, nullptr, 0,
-                nullptr, M, d, c.ffn, false);
+      if (!gemv1_ln(x, d, L.ffn1_f, d, m->hbuf.f(), c.ffn, M, c.ffn, d, true))
+        ln_gemm(x, d, d, &L.norm2, L.ffn1, d, m->hbuf.f(), c.ffn, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, c.ffn, d, true);
+      if (!gemv1(m->hbuf.f(), c.ffn, L.ffn2, c.ffn, x, d, nullptr, x, d, nullptr, 0, nullptr, M, d, c.ffn, false))
+        ln_gemm(m->hbuf.f(), c.ffn, 0, nullptr, L.ffn2, c.ffn, x, d, x, d, nullptr, 0, nullptr, 0, nullptr, M, d, c.ffn, false);
       continue;
     }
     // rounds of many connections (>= 1536 rows): the two LayerNorms of a layer folded into the GEMMs around them, as offline
-    // (pfhip.cpp enqueue_locked: row statistics from the producing epilogue, algebraic normalisation in the consumer's)
+    // (pfhip.cpp forward_encoder: row statistics from the producing epilogue, algebraic normalisation in the consumer's)
     if (fuse_ln_s && !first)
-      pfhip::launch_gemm_f32_x6_ln(x, d, m->d_lnw_qkv + (size_t)i * 3 * d * d, d, m->qkv.f(), 3 * d, m->d_lnb_qkv + (size_t)i * 3 * d, nullptr, 0,
-                                   nullptr, 0, M, 3 * d, d, false, m->lnstats.f(), 4, m->d_lns_qkv + (size_t)i * 3 * d, nullptr, st,
-                                   m->w_scale_of(m->d_lnw_qkv + (size_t)i * 3 * d * d));
+      pfhip::launch_gemm_f32_x6_ln(x, d, L.qkv_f.folded.w, d, m->qkv.f(), 3 * d, L.qkv_f.folded.b, nullptr, 0,
+                                   nullptr, 0, M, 3 * d, d, false, m->lnstats.f(), 4, L.qkv_f.colsum, nullptr, st, L.qkv_f.folded.scale);
     else {
-      lnorm(m, st, xin, ldin, m->y.f(), Kp, p + "norm1", M, Din, Kp);
-      gemm(m, st, m->y.f(), Kp, first ? m->d_w0qkv : m->W(p + "qkv.w").d, 3 * d, Kp, Din, m->qkv.f(), 3 * d,
-           m->W(p + "qkv.b").d, nullptr, 0, nullptr, 0, M, false);
+      lnorm(m, st, xin, ldin, m->y.f(), Kp, L.norm1, M, Din, Kp);
+      gemm(m, st, m->y.f(), Kp, L.qkv, 3 * d, Kp, Din, m->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, M, false);
     }
     // windows of <= 32 rows: one small workgroup per (head, connection) instead of the long-sequence kernel, the FSMN memory of V
     // written by the same launch
     if (!pfhip::launch_window_attention_segments(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
-                                                 d_len, d_off, d_len, B, c.n_head, maxn, maxn, att_scale, st, m->W(p + "fsmn.w").d,
+                                                 d_len, d_off, d_len, B, c.n_head, maxn, maxn, att_scale, st, L.fsmn_w,
                                                  m->mem.f(), d, hd)) {
-      pfhip::launch_fsmn(m->qkv.f() + 2 * d, 3 * d, m->W(p + "fsmn.w").d, nullptr, 0, m->mem.f(), d, d_off, d_len, B, maxn, d, st);
+      pfhip::launch_fsmn(m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, nullptr, 0, m->mem.f(), d, d_off, d_len, B, maxn, d, st);
       pfhip::launch_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
                               d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st, hd);
     }
     if (fuse_ln_s) {
-      pfhip::launch_gemm_f32_x6_ln(m->ctx.f(), d, m->W(p + "out.w").d, d, x, d, m->W(p + "out.b").d, m->mem.f(), d, first ? nullptr : x, d, M,
-                                   d, d, false, nullptr, 4, nullptr, m->lnstats.f(), st, m->w_scale_of(m->W(p + "out.w").d));
-      pfhip::launch_gemm_f32_x6_ln(x, d, m->d_lnw_ffn1 + (size_t)i * c.ffn * d, d, m->hbuf.f(), c.ffn, m->d_lnb_ffn1 + (size_t)i * c.ffn,
-                                   nullptr, 0, nullptr, 0, M, c.ffn, d, true, m->lnstats.f(), 4, m->d_lns_ffn1 + (size_t)i * c.ffn, nullptr, st,
-                                   m->w_scale_of(m->d_lnw_ffn1 + (size_t)i * c.ffn * d));
-      pfhip::launch_gemm_f32_x6_ln(m->hbuf.f(), c.ffn, m->W(p + "ffn2.w").d, c.ffn, x, d, m->W(p + "ffn2.b").d, x, d, nullptr, 0, M, d, c.ffn,
-                                   false, nullptr, 4, nullptr, i + 1 < c.enc_layers ? m->lnstats.f() : nullptr, st,
-                                   m->w_scale_of(m->W(p + "ffn2.w").d));
+      pfhip::launch_gemm_f32_x6_ln(m->ctx.f(), d, L.out.w, d, x, d, L.out.b, m->mem.f(), d, first ? nullptr : x, d, M,
+                                   d, d, false, nullptr, 4, nullptr, m->lnstats.f(), st, L.out.scale);
+      pfhip::launch_gemm_f32_x6_ln(x, d, L.ffn1_f.folded.w, d, m->hbuf.f(), c.ffn, L.ffn1_f.folded.b,
+                                   nullptr, 0, nullptr, 0, M, c.ffn, d, true, m->lnstats.f(), 4, L.ffn1_f.colsum, nullptr, st,
+                                   L.ffn1_f.folded.scale);
+      pfhip::launch_gemm_f32_x6_ln(m->hbuf.f(), c.ffn, L.ffn2.w, c.ffn, x, d, L.ffn2.b, x, d, nullptr, 0, M, d, c.ffn,
+                                   false, nullptr, 4, nullptr, i + 1 < c.enc_layers ? m->lnstats.f() : nullptr, st, L.ffn2.scale);
       continue;
     }
-    gemm(m, st, m->ctx.f(), d, m->W(p + "out.w").d, d, d, d, x, d, m->W(p + "out.b").d, m->mem.f(), d,
-         first ? nullptr : x, d, M, false);
-    lnorm(m, st, x, d, m->y.f(), d, p + "norm2", M, d, d);
-    gemm(m, st, m->y.f(), d, m->W(p + "ffn1.w").d, c.ffn, d, d, m->hbuf.f(), c.ffn, m->W(p + "ffn1.b").d, nullptr, 0,
-         nullptr, 0, M, true);
-    gemm(m, st, m->hbuf.f(), c.ffn, m->W(p + "ffn2.w").d, d, c.ffn, c.ffn, x, d, m->W(p + "ffn2.b").d, x, d, nullptr, 0,
-         M, false);
+    gemm(m, st, m->ctx.f(), d, L.out, d, d, d, x, d, m->mem.f(), d, first ? nullptr : x, d, M, false);
+    lnorm(m, st, x, d, m->y.f(), d, L.norm2, M, d, d);
+    gemm(m, st, m->y.f(), d, L.ffn1, c.ffn, d, d, m->hbuf.f(), c.ffn, nullptr, 0, nullptr, 0, M, true);
+    gemm(m, st, m->hbuf.f(), c.ffn, L.ffn2, d, c.ffn, c.ffn, x, d, x, d, nullptr, 0, M, false);
   }
-  lnorm(m, st, x, d, m->enc.f(), d, "enc.after_norm", M, d, d);
+  lnorm(m, st, x, d, m->enc.f(), d, w.enc_after, M, d, d);
   // predictor alphas: conv1d k=3 over each window (zero padded at its ends) -> relu -> linear -> sigmoid
   float* col = m->qkv.f();
   float* po = m->ctx.f();
   pfhip::launch_im2col3(m->enc.f(), d, col, 3 * d, d_row_pos, d_row_len, M, d, st);
-  if (!lean || !gemv1(col, 3 * d, m->d_predconv, 3 * d, po, d, m->W("pred.conv.b").d, nullptr, c.pred_residual ? m->enc.f() : nullptr, d,
+  if (!lean || !gemv1(col, 3 * d, w.pred.conv, 3 * d, po, d, nullptr, c.pred_residual ? m->enc.f() : nullptr, d,
                       nullptr, 0, nullptr, M, d, 3 * d, true))
-    gemm(m, st, col, 3 * d, m->d_predconv, d, 3 * d, 3 * d, po, d, m->W("pred.conv.b").d,
-         c.pred_residual ? m->enc.f() : nullptr, d, nullptr, 0, M, true);
-  pfhip::launch_alpha(po, d, m->W("pred.out.w").d, m->W("pred.out.b").d, c.smooth_factor, c.noise_threshold,
-                      m->alphas.f(), M, d, st);
+    gemm(m, st, col, 3 * d, w.pred.conv, d, 3 * d, 3 * d, po, d, c.pred_residual ? m->enc.f() : nullptr, d, nullptr, 0, M, true);
+  pfhip::launch_alpha(po, d, w.pred.out_w, w.pred.out_b, c.smooth_factor, c.noise_threshold, m->alphas.f(), M, d, st);
   // ---- CifSearch (:270-345), one block per connection ---------------------------------------------------
   pfhip::launch_cif_stream(m->enc.f(), d, m->alphas.f(), d_segs, B, c.cif_threshold, c.tail_threshold, m->emb.f(), kMaxTok,
                            m->counts.i(), d, st, any_fires ? m->counts.i() + B : nullptr);
-  HIP_TRY(hipMemcpyAsync(m->h_counts, m->counts.p, n_counts * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(m->h_counts.p, m->counts.p, n_counts * 4, hipMemcpyDeviceToHost, st));
   static const bool timing = pfhip::env_is1("PFHIP_STREAM_TIMING");
   const auto t_sync0 = std::chrono::steady_clock::now();
   HIP_TRY(hipStreamSynchronize(st));
@@ -411,7 +394,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     (void)enq_us; (void)t_last;
     if (++n % 50 == 0) { std::fprintf(stderr, "[stream timing] encoder: avg wait in sync %.1f us over %d chunks\n", wait_us / n, n); }
   }
-  const int* fires = m->h_counts;
+  const int* fires = m->h_counts.i();
   int ML = 0, maxN = 0;
   for (int b = 0; b < B; ++b) {
     const int N = fires[b];
@@ -423,7 +406,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     maxN = std::max(maxN, N);
     if (ss[b]->want_fires) {       // step -> window row -> the emitted row it is a copy of (h_counts is overwritten by the next forward)
       const std::vector<int>& wi = ss[b]->win_idx;
-      const int* steps = m->h_counts + B + (size_t)b * kMaxTok;
+      const int* steps = m->h_counts.i() + B + (size_t)b * kMaxTok;
       for (int k = 0; k < N; ++k) {
         // 0 = the carry slot (the window's first row), 1..n = rows 0..n-1, n + 1 = the tail slot (the window's last row)
         const int row = std::min(std::max(steps[k] - 1, 0), (int)wi.size() - 1);
@@ -441,15 +424,15 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   HIP_TRY(m->t2.ensure((size_t)MLp * d * 4));
   HIP_TRY(m->qd.ensure((size_t)MLp * d * 4));
   HIP_TRY(m->ctxd.ensure((size_t)MLp * d * 4));
-  HIP_TRY(m->logits.ensure((size_t)MLp * m->vocab_pad * 4));
+  HIP_TRY(m->logits.ensure((size_t)MLp * w.vocab_pad * 4));
   // ids [ML], then with candidates their ids [ML, kmax] and values [ML, kmax]: one buffer, one copy back
   HIP_TRY(m->ids.ensure((size_t)MLp * 4 * (1 + 2 * kmax)));
   if (want_logp) HIP_TRY(m->logp.ensure((size_t)MLp * c.vocab * 4));
   // second half of the pinned staging buffer (the first half may still be read by the copies above)
   {
-    int* hm2 = reinterpret_cast<int*>(static_cast<char*>(m->h_meta) + m->h_meta_cap / 2);
+    int* hm2 = reinterpret_cast<int*>(static_cast<char*>(m->h_meta.p) + m->h_meta.cap / 2);
     const size_t need = (2 * (size_t)B + ML) * 4 + 16 + (size_t)B * sizeof(pfhip::StreamSeg);
-    if (m->h_meta_cap / 2 + need > m->h_meta_cap) return fail(PFHIP_ERR_CAPACITY, "too many stream tokens in one batch");
+    if (m->h_meta.cap / 2 + need > m->h_meta.cap) return fail(PFHIP_ERR_CAPACITY, "too many stream tokens in one batch");
     for (int b = 0; b < B; ++b) { hm2[b] = segs[b].tok_off; hm2[B + b] = segs[b].n_tok; }
     for (int b = 0; b < B; ++b)
       for (int k = 0; k < segs[b].n_tok; ++k) hm2[2 * B + segs[b].tok_off + k] = b * kMaxTok + k;
@@ -464,82 +447,69 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   float* kvbuf = m->qkv.f();
   pfhip::launch_compact(m->emb.f(), xd, d_src_row, ML, d, st);
   const bool lean_dec = lean && ML <= 32;
-  auto dec_ffn = [&](const std::string& p, int li, const float* xin, float* o) {
+  auto dec_ffn = [&](const DecFfn& F, const float* xin, float* o) {
     if (lean_dec) {          // LN1+FFN1 | ffn_norm+FFN2
       const int f = c.dec_ffn;
-      if (!m->d_dlnw1 || !gemv1(xin, d, m->d_dlnw1 + (size_t)li * f * d, d, m->hd.f(), f, m->d_dlnb1 + (size_t)li * f,
-                                m->d_dlns1 + (size_t)li * f, nullptr, 0, nullptr, 0, nullptr, ML, f, d, true))
-        ln_gemm(xin, d, d, p + "norm1", m->W(p + "ffn1.w").d, d, m->hd.f(), c.dec_ffn, m->W(p + "ffn1.b").d, nullptr, 0, nullptr, 0,
-                nullptr, 0, nullptr, ML, c.dec_ffn, d, true);
-      if (!m->d_dlnw2 || !gemv1(m->hd.f(), f, m->d_dlnw2 + (size_t)li * d * f, f, o, d, m->d_dlnb2 + (size_t)li * d,
-                                m->d_dlns2 + (size_t)li * d, nullptr, 0, nullptr, 0, nullptr, ML, d, f, false))
-        ln_gemm(m->hd.f(), c.dec_ffn, c.dec_ffn, p + "ffn_norm", m->W(p + "ffn2.w").d, c.dec_ffn, o, d, nullptr, nullptr, 0, nullptr, 0,
-                nullptr, 0, nullptr, ML, d, c.dec_ffn, false);
+      if (!gemv1_ln(xin, d, F.ffn1_f, d, m->hd.f(), f, ML, f, d, true))
+        ln_gemm(xin, d, d, &F.norm1, F.ffn1, d, m->hd.f(), f, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, ML, f, d, true);
+      if (!gemv1_ln(m->hd.f(), f, F.ffn2_f, f, o, d, ML, d, f, false))
+        ln_gemm(m->hd.f(), f, f, &F.ffn_norm, F.ffn2, f, o, d, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, ML, d, f, false);
       return;
     }
-    lnorm(m, st, xin, d, m->yd.f(), d, p + "norm1", ML, d, d);
-    gemm(m, st, m->yd.f(), d, m->W(p + "ffn1.w").d, c.dec_ffn, d, d, m->hd.f(), c.dec_ffn, m->W(p + "ffn1.b").d, nullptr,
-         0, nullptr, 0, ML, true);
-    lnorm(m, st, m->hd.f(), c.dec_ffn, m->hd2.f(), c.dec_ffn, p + "ffn_norm", ML, c.dec_ffn, c.dec_ffn);
-    gemm(m, st, m->hd2.f(), c.dec_ffn, m->W(p + "ffn2.w").d, d, c.dec_ffn, c.dec_ffn, o, d, nullptr, nullptr, 0, nullptr, 0,
-         ML, false);
+    lnorm(m, st, xin, d, m->yd.f(), d, F.norm1, ML, d, d);
+    gemm(m, st, m->yd.f(), d, F.ffn1, c.dec_ffn, d, d, m->hd.f(), c.dec_ffn, nullptr, 0, nullptr, 0, ML, true);
+    lnorm(m, st, m->hd.f(), c.dec_ffn, m->hd2.f(), c.dec_ffn, F.ffn_norm, ML, c.dec_ffn, c.dec_ffn);
+    gemm(m, st, m->hd2.f(), c.dec_ffn, F.ffn2, d, c.dec_ffn, c.dec_ffn, o, d, nullptr, 0, nullptr, 0, ML, false);
   };
   const int kv_ld = c.dec_layers * 2 * d;
   if (lean_dec) {            // the window is the same for every layer: all K/V projections in one launch
     HIP_TRY(m->kvall.ensure((size_t)32 * (kv_ld + pfhip::kTileN) * 4));
-    if (!gemv1(m->enc.f(), d, m->d_kv_all_w, d, m->kvall.f(), kv_ld, m->d_kv_all_b, nullptr, nullptr, 0, nullptr, 0, nullptr, M, kv_ld, d,
-               false))
-      ln_gemm(m->enc.f(), d, 0, "", m->d_kv_all_w, d, m->kvall.f(), kv_ld, m->d_kv_all_b, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M,
-              kv_ld, d, false);
+    if (!gemv1(m->enc.f(), d, w.kv_all, d, m->kvall.f(), kv_ld, nullptr, nullptr, 0, nullptr, 0, nullptr, M, kv_ld, d, false))
+      ln_gemm(m->enc.f(), d, 0, nullptr, w.kv_all, d, m->kvall.f(), kv_ld, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, kv_ld, d, false);
   }
   for (int i = 0; i < c.dec_layers; ++i) {
-    const std::string p = "dec." + std::to_string(i) + ".";
-    dec_ffn(p, i, xd, m->td.f());
-    lnorm(m, st, m->td.f(), d, m->t2.f(), d, p + "norm2", ML, d, d);
-    pfhip::launch_fsmn_cached(m->t2.f(), m->W(p + "fsmn.w").d, xd, xd, d_segs, B, i, d, st);
+    const DecLayer& L = w.dec[(size_t)i];
+    dec_ffn(L.ffn, xd, m->td.f());
+    lnorm(m, st, m->td.f(), d, m->t2.f(), d, L.norm2, ML, d, d);
+    pfhip::launch_fsmn_cached(m->t2.f(), L.fsmn_w, xd, xd, d_segs, B, i, d, st);
     if (lean_dec) {
-      if (!m->d_dlnw3 || !gemv1(xd, d, m->d_dlnw3 + (size_t)i * d * d, d, m->qd.f(), d, m->d_dlnb3 + (size_t)i * d,
-                                m->d_dlns3 + (size_t)i * d, nullptr, 0, nullptr, 0, nullptr, ML, d, d, false))
-        ln_gemm(xd, d, d, p + "norm3", m->W(p + "q.w").d, d, m->qd.f(), d, m->W(p + "q.b").d, nullptr, 0, nullptr, 0, nullptr, 0,
-                nullptr, ML, d, d, false);
+      if (!gemv1_ln(xd, d, L.q_f, d, m->qd.f(), d, ML, d, d, false))
+        ln_gemm(xd, d, d, &L.norm3, L.q, d, m->qd.f(), d, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, ML, d, d, false);
       const float* kvl = m->kvall.f() + (size_t)i * 2 * d;
-      if (att_out_on && hdd == pfhip::kHeadDim && pfhip::launch_fused_att_out(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, ML, M, c.dec_n_head, att_scale_d, m->W(p + "out.w").d, d, xd, d,
-                                      m->W(p + "out.b").d, xd, d, nullptr, 0, nullptr, d, st))
+      if (att_out_on && hdd == pfhip::kHeadDim && pfhip::launch_fused_att_out(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, ML, M, c.dec_n_head, att_scale_d, L.out.w, d, xd, d,
+                                      L.out.b, xd, d, nullptr, 0, nullptr, d, st))
         continue;
       if (!pfhip::launch_window_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, ML, M, c.dec_n_head, att_scale_d, st, hdd))
         pfhip::launch_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off, d_len, B,
                                 c.dec_n_head, maxN, att_scale_d, st, hdd);
-      if (!gemv1(m->ctxd.f(), d, m->W(p + "out.w").d, d, xd, d, m->W(p + "out.b").d, nullptr, xd, d, nullptr, 0, nullptr, ML, d, d, false))
-        ln_gemm(m->ctxd.f(), d, 0, "", m->W(p + "out.w").d, d, xd, d, m->W(p + "out.b").d, xd, d, nullptr, 0, nullptr, 0, nullptr,
-                ML, d, d, false);
+      if (!gemv1(m->ctxd.f(), d, L.out, d, xd, d, nullptr, xd, d, nullptr, 0, nullptr, ML, d, d, false))
+        ln_gemm(m->ctxd.f(), d, 0, nullptr, L.out, d, xd, d, xd, d, nullptr, 0, nullptr, 0, nullptr, ML, d, d, false);
       continue;
     }
-    lnorm(m, st, xd, d, m->yd.f(), d, p + "norm3", ML, d, d);
-    gemm(m, st, m->yd.f(), d, m->W(p + "q.w").d, d, d, d, m->qd.f(), d, m->W(p + "q.b").d, nullptr, 0, nullptr, 0, ML, false);
-    gemm(m, st, m->enc.f(), d, m->W(p + "kv.w").d, 2 * d, d, d, kvbuf, 2 * d, m->W(p + "kv.b").d, nullptr, 0, nullptr, 0, M,
-         false);
+    lnorm(m, st, xd, d, m->yd.f(), d, L.norm3, ML, d, d);
+    gemm(m, st, m->yd.f(), d, L.q, d, d, d, m->qd.f(), d, nullptr, 0, nullptr, 0, ML, false);
+    gemm(m, st, m->enc.f(), d, L.kv, 2 * d, d, d, kvbuf, 2 * d, nullptr, 0, nullptr, 0, M, false);
     if (!pfhip::launch_window_attention_segments(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off,
                                                  d_len, B, c.dec_n_head, maxN, maxn, att_scale_d, st, nullptr, nullptr, 0, hdd))
       pfhip::launch_attention(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off, d_len, B,
                               c.dec_n_head, maxN, att_scale_d, st, hdd);
-    gemm(m, st, m->ctxd.f(), d, m->W(p + "out.w").d, d, d, d, xd, d, m->W(p + "out.b").d, xd, d, nullptr, 0, ML, false);
+    gemm(m, st, m->ctxd.f(), d, L.out, d, d, d, xd, d, xd, d, nullptr, 0, ML, false);
   }
-  dec_ffn("dec3.", c.dec_layers, xd, m->td.f());
+  dec_ffn(w.dec3, xd, m->td.f());
   if (lean_dec) {
-    ln_gemm(m->td.f(), d, d, "dec.after_norm", m->W("dec.out.w").d, d, m->logits.f(), m->vocab_pad, m->d_vocab_bias, nullptr, 0,
+    ln_gemm(m->td.f(), d, d, &w.dec_after, w.dec_out, d, m->logits.f(), w.vocab_pad, nullptr, 0,
             nullptr, 0, nullptr, 0, nullptr, ML, c.vocab, d, false);
   } else {
-    lnorm(m, st, m->td.f(), d, m->yd.f(), d, "dec.after_norm", ML, d, d);
-    gemm(m, st, m->yd.f(), d, m->W("dec.out.w").d, c.vocab, d, d, m->logits.f(), m->vocab_pad, m->d_vocab_bias, nullptr, 0,
-         nullptr, 0, ML, false);
+    lnorm(m, st, m->td.f(), d, m->yd.f(), d, w.dec_after, ML, d, d);
+    gemm(m, st, m->yd.f(), d, w.dec_out, c.vocab, d, d, m->logits.f(), w.vocab_pad, nullptr, 0, nullptr, 0, ML, false);
   }
   int32_t* d_ids = static_cast<int32_t*>(m->ids.p);
   if (kmax > 0) {      // the sibling head (topk.hip): candidate 0 and `ids` are the arg-max kernel's bit for bit
-    if (!pfhip::launch_logsoftmax_topk(m->logits.f(), m->vocab_pad, ML, c.vocab, kmax, want_logp ? m->logp.f() : nullptr, d_ids,
+    if (!pfhip::launch_logsoftmax_topk(m->logits.f(), w.vocab_pad, ML, c.vocab, kmax, want_logp ? m->logp.f() : nullptr, d_ids,
                                        d_ids + ML, reinterpret_cast<float*>(d_ids + (size_t)ML * (1 + kmax)), st))
       return fail(PFHIP_ERR_ARG, "stream nbest k outside 1..8 or larger than the vocabulary");
   } else {
-    pfhip::launch_logsoftmax_argmax(m->logits.f(), m->vocab_pad, ML, c.vocab, want_logp ? m->logp.f() : nullptr, d_ids, st);
+    pfhip::launch_logsoftmax_argmax(m->logits.f(), w.vocab_pad, ML, c.vocab, want_logp ? m->logp.f() : nullptr, d_ids, st);
   }
   std::vector<int32_t> ids((size_t)ML * (1 + 2 * kmax));
   HIP_TRY(hipMemcpyAsync(ids.data(), m->ids.p, ids.size() * 4, hipMemcpyDeviceToHost, st));
@@ -565,7 +535,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
 // idx0: which emitted row rows[r0] is (pfhip_stream::win_idx)
 pfhip_status add_overlap_chunk(pfhip_stream* s, int r0, int nr, int idx0, bool input_finished, Recorder& rec, int* n_out) {
   pfhip_model* m = s->m;
-  const int FD = m->feat_dim, FP = m->feat_pad;
+  const int FD = m->weights->feat_dim, FP = m->weights->feat_pad;
   const int nc = s->n_featc;
   int n = nc + nr;
   if (n > 128) return fail(PFHIP_ERR_ARG, "stream window too long");
@@ -600,7 +570,7 @@ pfhip_status add_overlap_chunk(pfhip_stream* s, int r0, int nr, int idx0, bool i
 // s->rows and rotates the splice cache.
 pfhip_status online_lfr_cmvn(pfhip_stream* s, int T, bool input_finished, Recorder& rec, int* n_rows) {
   pfhip_model* m = s->m;
-  const int lfr_m = m->cfg.lfr_m, lfr_n = m->cfg.lfr_n;
+  const int lfr_m = m->weights->cfg.lfr_m, lfr_n = m->weights->cfg.lfr_n;
   const int T_lrf = (int)std::ceil((T - (lfr_m - 1) / 2) / (float)lfr_n);
   int splice = T_lrf, n_out = 0;
   for (int i = 0; i < T_lrf; ++i) {
@@ -627,7 +597,7 @@ pfhip_status online_lfr_cmvn(pfhip_stream* s, int T, bool input_finished, Record
 pfhip_status extract_feats(pfhip_stream* s, PcmView pcm, int len, bool input_finished, Recorder& rec, int* n_rows) {
   pfhip_model* m = s->m;
   *n_rows = 0;
-  const int fl = 400, fs = 160, lfr_m = m->cfg.lfr_m;
+  const int fl = 400, fs = 160, lfr_m = m->weights->cfg.lfr_m;
   // FbankKaldi (:119-145): prepend input_cache_, keep what follows the last frame shift for the next call
   std::vector<float>& waves = s->waves;            // lives until the flush of this call has copied it
   waves.assign(s->input_cache.begin(), s->input_cache.end());
@@ -712,11 +682,9 @@ void pfhip_stream_destroy(pfhip_stream* s) {
     std::lock_guard<std::mutex> lk(s->m->mu);
     (void)hipSetDevice(s->m->device);
     (void)hipStreamSynchronize(s->m->own_stream);
-    for (Buf* b : {&s->fb[0], &s->fb[1], &s->rows, &s->featc, &s->chunk, &s->carry, &s->dcache})
-      b->release();
+    --s->m->live_streams;
+    delete s;                 // its buffers go back under the model's lock, with the device set and the stream idle
   }
-  --s->m->live_streams;
-  delete s;
 }
 
 int pfhip_stream_last_path(const pfhip_stream* s) { return s ? s->last_path : 0; }
@@ -737,7 +705,7 @@ pfhip_status pfhip_stream_reset(pfhip_stream* s) {
 pfhip_status pfhip_stream_set_detail(pfhip_stream* s, int nbest_k, int fire_frames) {
   last_error().clear();
   if (!s) return fail(PFHIP_ERR_ARG, "null stream");
-  if (nbest_k < 0 || nbest_k > pfhip::kTopkMax || nbest_k > s->m->cfg.vocab)
+  if (nbest_k < 0 || nbest_k > pfhip::kTopkMax || nbest_k > s->m->weights->cfg.vocab)
     return fail(PFHIP_ERR_ARG, "stream detail: k outside 0..8 (or above the vocabulary)");
   std::lock_guard<std::mutex> lk(s->m->mu);
   s->nbest_k = nbest_k;
@@ -794,7 +762,7 @@ pfhip_status prepare_first(Call& c, Recorder& rec) {
     s->last_path = 1;
     s->win_n = s->n_featc;
     s->win_idx = s->featc_idx;
-    rec.copy(Recorder::kWindow, s->chunk.f(), m->feat_pad, s->featc.f(), m->feat_dim, s->win_n, m->feat_dim);
+    rec.copy(Recorder::kWindow, s->chunk.f(), m->weights->feat_pad, s->featc.f(), m->weights->feat_dim, s->win_n, m->weights->feat_dim);
     c.has_window = true;
     c.reinit = true;
     return PFHIP_OK;
@@ -1083,13 +1051,13 @@ pfhip_status pfhip_stream_get_tensor(pfhip_stream* s, const char* name, float* d
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = m->own_stream;
   const std::string nm(name);
-  const int d = m->cfg.d_model;
+  const int d = m->weights->cfg.d_model;
   // the last window of this stream, where the last batched forward left it in the model's packed workspace (valid
   // until the next forward on this model)
   if (nm == "chunk") {
-    const size_t n = (size_t)s->last_n * m->feat_dim;
+    const size_t n = (size_t)s->last_n * m->weights->feat_dim;
     if (n > cap_floats) return fail(PFHIP_ERR_CAPACITY, "dst too small");
-    if (n) HIP_TRY(hipMemcpy2DAsync(dst, (size_t)m->feat_dim * 4, s->chunk.p, (size_t)m->feat_pad * 4, (size_t)m->feat_dim * 4,
+    if (n) HIP_TRY(hipMemcpy2DAsync(dst, (size_t)m->weights->feat_dim * 4, s->chunk.p, (size_t)m->weights->feat_pad * 4, (size_t)m->weights->feat_dim * 4,
                                     s->last_n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n_out) *n_out = n;
@@ -1100,7 +1068,7 @@ pfhip_status pfhip_stream_get_tensor(pfhip_stream* s, const char* name, float* d
   if (nm == "emb") return copy_out(m->emb.f() + (size_t)s->last_slot * kMaxTok * d, (size_t)s->last_fires * d, dst, cap_floats, n_out, st);
   if (nm == "logp") {
     if (!s->last_has_logp && s->last_fires > 0) return fail(PFHIP_ERR_ARG, "enable pfhip_stream_set_debug before the call");
-    return copy_out(m->logp.f() + (size_t)s->last_tok_off * m->cfg.vocab, (size_t)s->last_fires * m->cfg.vocab, dst, cap_floats, n_out, st);
+    return copy_out(m->logp.f() + (size_t)s->last_tok_off * m->weights->cfg.vocab, (size_t)s->last_fires * m->weights->cfg.vocab, dst, cap_floats, n_out, st);
   }
   return fail(PFHIP_ERR_ARG, "unknown tensor name " + nm);
 }

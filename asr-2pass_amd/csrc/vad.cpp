@@ -22,10 +22,10 @@ struct pfhip_vad {
   std::mutex mu;
   int n_mels = 80, lfr_m = 5, lfr_n = 1, input_dim = 400, proj = 128, lorder = 20, layers = 4, n_out = 248, linear = 250;
   FrontendTables ft;
-  float *d_mean = nullptr, *d_istd = nullptr;
-  Lin in1, in2, out1, out2;
-  std::vector<Lin> blk_linear, blk_affine;
-  std::vector<float*> fsmn_w;
+  DevMem cmvn_mean, cmvn_istd;
+  PackedLin in1, in2, out1, out2;
+  std::vector<PackedLin> blk_linear, blk_affine;
+  std::vector<DevMem> fsmn_w;
   Buf pcm, fb, feats, a, b, p, f, probs, sil, meta, cache[2], segs, fbk, ops;
   int cache_cur = 0;
   int* h_pin = nullptr;
@@ -51,11 +51,19 @@ struct pfhip_vad {
     }
     return h_wave_buf;
   }
+  // the device set and idle before any member gives its memory back (a create that returns early comes through here too)
+  ~pfhip_vad() {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();
+    if (h_pin) (void)hipHostFree(h_pin);
+    if (h_wave_buf) (void)hipHostFree(h_wave_buf);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
 
-void lin_gemm(hipStream_t s, const Lin& l, const float* A, int lda, float* C, int ldc, int M, bool relu) {
+void lin_gemm(hipStream_t s, const PackedLin& l, const float* A, int lda, float* C, int ldc, int M, bool relu) {
   pfhip_detail::lin_gemm(s, l, A, lda, C, ldc, nullptr, 0, nullptr, 0, M, relu);
 }
 
@@ -109,7 +117,7 @@ pfhip_status pfhip_vad_create_from_memory(const void* blob, size_t blob_bytes, c
     *p = hb + off / 4;
     return true;
   };
-  auto lin = [&](const std::string& name, int N, int K, bool bias, Lin* l) -> pfhip_status {
+  auto lin = [&](const std::string& name, int N, int K, bool bias, PackedLin* l) -> pfhip_status {
     const float *w = nullptr, *b = nullptr;
     if (!get(name + ".w", {N, K}, &w)) return PFHIP_ERR_FORMAT;
     if (bias && !get(name + ".b", {N}, &b)) return PFHIP_ERR_FORMAT;
@@ -118,12 +126,10 @@ pfhip_status pfhip_vad_create_from_memory(const void* blob, size_t blob_bytes, c
   pfhip_status st;
   const float *mean = nullptr, *istd = nullptr;
   if (!get("cmvn.mean", {v->input_dim}, &mean) || !get("cmvn.istd", {v->input_dim}, &istd)) return PFHIP_ERR_FORMAT;
-  HIP_TRY(hipMalloc((void**)&v->d_mean, v->input_dim * 4));
-  HIP_TRY(hipMemcpy(v->d_mean, mean, v->input_dim * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc((void**)&v->d_istd, v->input_dim * 4));
-  HIP_TRY(hipMemcpy(v->d_istd, istd, v->input_dim * 4, hipMemcpyHostToDevice));
+  HIP_TRY(v->cmvn_mean.upload(mean, (size_t)v->input_dim * 4));
+  HIP_TRY(v->cmvn_istd.upload(istd, (size_t)v->input_dim * 4));
   if ((st = lin("in1", affine, v->input_dim, true, &v->in1)) || (st = lin("in2", v->linear, affine, true, &v->in2))) return st;
-  v->blk_linear.resize(v->layers); v->blk_affine.resize(v->layers); v->fsmn_w.assign(v->layers, nullptr);
+  v->blk_linear.resize(v->layers); v->blk_affine.resize(v->layers); v->fsmn_w.resize(v->layers);
   for (int i = 0; i < v->layers; ++i) {
     const std::string p = "blk." + std::to_string(i) + ".";
     if ((st = lin(p + "linear", v->proj, v->linear, false, &v->blk_linear[i])) ||
@@ -131,8 +137,7 @@ pfhip_status pfhip_vad_create_from_memory(const void* blob, size_t blob_bytes, c
       return st;
     const float* fw = nullptr;
     if (!get(p + "fsmn.w", {v->proj, v->lorder}, &fw)) return PFHIP_ERR_FORMAT;
-    HIP_TRY(hipMalloc((void**)&v->fsmn_w[i], (size_t)v->proj * v->lorder * 4));
-    HIP_TRY(hipMemcpy(v->fsmn_w[i], fw, (size_t)v->proj * v->lorder * 4, hipMemcpyHostToDevice));
+    HIP_TRY(v->fsmn_w[i].upload(fw, (size_t)v->proj * v->lorder * 4));
   }
   if ((st = lin("out1", out_affine, v->linear, true, &v->out1)) || (st = lin("out2", v->n_out, out_affine, true, &v->out2))) return st;
   if ((st = build_frontend_tables(v->n_mels, 16000, &v->ft))) return st;
@@ -147,24 +152,7 @@ pfhip_status pfhip_vad_create_from_memory(const void* blob, size_t blob_bytes, c
   return PFHIP_OK;
 }
 
-void pfhip_vad_destroy(pfhip_vad* v) {
-  if (!v) return;
-  (void)hipSetDevice(v->device);
-  (void)hipDeviceSynchronize();
-  for (Buf* b : {&v->pcm, &v->fb, &v->feats, &v->a, &v->b, &v->p, &v->f, &v->probs, &v->meta, &v->cache[0], &v->cache[1], &v->segs, &v->fbk, &v->ops, &v->sil, &v->eng, &v->zcache}) b->release();
-  auto fl = [](Lin& l) { free_lin(l); };
-  fl(v->in1); fl(v->in2); fl(v->out1); fl(v->out2);
-  for (auto& l : v->blk_linear) fl(l);
-  for (auto& l : v->blk_affine) fl(l);
-  for (float* p : v->fsmn_w) if (p) (void)hipFree(p);
-  for (void* p : {(void*)v->d_mean, (void*)v->d_istd, (void*)v->ft.d_window, (void*)v->ft.d_tw, (void*)v->ft.d_mel_off,
-                  (void*)v->ft.d_mel_size, (void*)v->ft.d_mel_w})
-    if (p) (void)hipFree(p);
-  if (v->h_pin) (void)hipHostFree(v->h_pin);
-  if (v->h_wave_buf) (void)hipHostFree(v->h_wave_buf);
-  if (v->stream) (void)hipStreamDestroy(v->stream);
-  delete v;
-}
+void pfhip_vad_destroy(pfhip_vad* v) { delete v; }
 
 pfhip_status pfhip_vad_reset(pfhip_vad* v) {
   last_error().clear();
@@ -186,7 +174,7 @@ static void vad_network(pfhip_vad* v, hipStream_t s, int T, const pfhip::VadSeg*
   lin_gemm(s, v->in2, v->a.f(), 256, v->b.f(), 256, T, true);
   for (int i = 0; i < v->layers; ++i) {
     lin_gemm(s, v->blk_linear[i], v->b.f(), 256, v->p.f(), 128, T, false);
-    pfhip::launch_fsmn_causal20(v->p.f(), 128, v->fsmn_w[i], d_segs, B, max_T, i, v->f.f(), 128, v->proj, s);
+    pfhip::launch_fsmn_causal20(v->p.f(), 128, v->fsmn_w[i].f(), d_segs, B, max_T, i, v->f.f(), 128, v->proj, s);
     lin_gemm(s, v->blk_affine[i], v->f.f(), 128, v->b.f(), 256, T, true);
   }
   lin_gemm(s, v->out1, v->b.f(), 256, v->a.f(), 256, T, false);
@@ -266,14 +254,14 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, i
     hm[0] = 0; hm[1] = F; hm[2] = F;
     HIP_TRY(hipMemcpyAsync(v->meta.p, v->h_pin, 32, hipMemcpyHostToDevice, s));
   }
-  pfhip::FbankTables tb{v->ft.d_window, v->ft.d_tw, v->ft.d_mel_off, v->ft.d_mel_size, v->ft.d_mel_w, v->d_mean, v->d_istd};
+  const pfhip::FbankTables tb = v->ft.fbank(v->cmvn_mean.f(), v->cmvn_istd.f());
   if (pcm.s16)
     pfhip::launch_fbank_frames(static_cast<const int16_t*>(v->pcm.p), reinterpret_cast<int64_t*>(v->meta.p), v->meta.i() + 2,
                                v->meta.i() + 4, F, tb, v->fb.f(), s);
   else
     pfhip::launch_fbank_frames(v->pcm.f(), reinterpret_cast<int64_t*>(v->meta.p), v->meta.i() + 2, v->meta.i() + 4, F, tb,
                                v->fb.f(), s);
-  pfhip::launch_lfr_cmvn(v->fb.f(), F, T, v->lfr_m, v->lfr_n, v->n_mels, v->d_mean, v->d_istd, v->feats.f(), v->in1.Kp, s);
+  pfhip::launch_lfr_cmvn(v->fb.f(), F, T, v->lfr_m, v->lfr_n, v->n_mels, v->cmvn_mean.f(), v->cmvn_istd.f(), v->feats.f(), v->in1.Kp, s);
   {
     pfhip::VadSeg* hs = reinterpret_cast<pfhip::VadSeg*>(v->h_pin + 16);
     *hs = pfhip::VadSeg{v->cache[v->cache_cur].f(), is_final ? nullptr : v->cache[v->cache_cur ^ 1].f(), 0, T};
@@ -389,7 +377,7 @@ pfhip_status vad_forward_files(pfhip_vad* v, const std::vector<VadFileReq*>& fil
       const int64_t* d_so = reinterpret_cast<const int64_t*>(dp);
       const int *d_fo = reinterpret_cast<const int*>(dp + o_fo), *d_nf = reinterpret_cast<const int*>(dp + o_nf),
                 *d_ro = reinterpret_cast<const int*>(dp + o_ro);
-      pfhip::FbankTables tb{v->ft.d_window, v->ft.d_tw, v->ft.d_mel_off, v->ft.d_mel_size, v->ft.d_mel_w, v->d_mean, v->d_istd};
+      const pfhip::FbankTables tb = v->ft.fbank(v->cmvn_mean.f(), v->cmvn_istd.f());
       bool ok;
       if (s16) {
         const int16_t* d_pcm = static_cast<const int16_t*>(v->pcm.p);
@@ -400,7 +388,7 @@ pfhip_status vad_forward_files(pfhip_vad* v, const std::vector<VadFileReq*>& fil
         ok = pfhip::launch_frame_energy(v->pcm.f(), d_so, d_fo, d_nf, U, n_fr, 400, 160, v->eng.f(), s);
       }
       if (!ok) return fail(PFHIP_ERR_UNSUPPORTED, "frame energy launch refused");
-      pfhip::launch_lfr_cmvn_packed(v->fbk.f(), d_fo, d_nf, d_ro, U, max_T, v->lfr_m, v->lfr_n, v->n_mels, v->d_mean, v->d_istd,
+      pfhip::launch_lfr_cmvn_packed(v->fbk.f(), d_fo, d_nf, d_ro, U, max_T, v->lfr_m, v->lfr_n, v->n_mels, v->cmvn_mean.f(), v->cmvn_istd.f(),
                                     v->feats.f(), v->in1.Kp, s);
       vad_network(v, s, n_row, reinterpret_cast<const pfhip::VadSeg*>(dp + o_seg), U, max_T);
       HIP_TRY(hipMemcpyAsync(h_sil, v->sil.p, (size_t)n_row * 4, hipMemcpyDeviceToHost, s));
@@ -559,10 +547,9 @@ void pfhip_vad_stream_destroy(pfhip_vad_stream* vs) {
     std::lock_guard<std::mutex> lk(vs->v->mu);
     (void)hipSetDevice(vs->v->device);
     (void)hipStreamSynchronize(vs->v->stream);
-    for (Buf* b : {&vs->fb[0], &vs->fb[1], &vs->cache[0], &vs->cache[1]}) b->release();
+    --vs->v->live_streams;
+    delete vs;                // its buffers go back under the handle's lock, with the device set and the stream idle
   }
-  --vs->v->live_streams;
-  delete vs;
 }
 
 // Reset() + ResetCache() (fsmn-vad-online.cpp:160-163, fsmn-vad-online.h:59-63)
@@ -709,7 +696,7 @@ pfhip_status vad_execute(pfhip_vad* v, std::vector<VadCall>& calls) {
     h_foff[U] = fo;
     HIP_TRY(hipMemcpyAsync(v->pcm.p, h_pcm, cap_samples * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(dp, hp, meta_bytes, hipMemcpyHostToDevice, s));
-    pfhip::FbankTables tb{v->ft.d_window, v->ft.d_tw, v->ft.d_mel_off, v->ft.d_mel_size, v->ft.d_mel_w, v->d_mean, v->d_istd};
+    const pfhip::FbankTables tb = v->ft.fbank(v->cmvn_mean.f(), v->cmvn_istd.f());
     pfhip::launch_fbank_frames_batch(v->pcm.f(), reinterpret_cast<const int64_t*>(dp), reinterpret_cast<const int*>(dp + (size_t)U * 8),
                                      reinterpret_cast<const int*>(dp + (size_t)U * 8 + (size_t)(U + 1) * 4), U, total_frames, tb,
                                      v->fbk.f(), s);
@@ -755,7 +742,7 @@ pfhip_status vad_execute(pfhip_vad* v, std::vector<VadCall>& calls) {
   pfhip::launch_rows_copy_batch(reinterpret_cast<const pfhip::RowsCopyOp*>(d_ops + o_fb), (int)to_fb.size(), max_rows(to_fb), s);
   pfhip::launch_rows_copy_batch(reinterpret_cast<const pfhip::RowsCopyOp*>(d_ops + o_fr), (int)fresh.size(), max_rows(fresh), s);
   pfhip::launch_lfr_cmvn_online_batch(reinterpret_cast<const pfhip::VadLfrOp*>(d_ops + o_lfr), (int)lfr.size(), max_T, m, n, v->n_mels,
-                                      v->d_mean, v->d_istd, v->feats.f(), v->in1.Kp, s);
+                                      v->cmvn_mean.f(), v->cmvn_istd.f(), v->feats.f(), v->in1.Kp, s);
   pfhip::launch_rows_copy_batch(reinterpret_cast<const pfhip::RowsCopyOp*>(d_ops + o_rot), (int)rotate.size(), max_rows(rotate), s);
   if (T > 0) {
     vad_network(v, s, T, reinterpret_cast<const pfhip::VadSeg*>(d_ops + o_seg), (int)segs.size(), max_T);

@@ -131,6 +131,29 @@ def test_errors_are_loud(pkg, weights_mod):
     m.close()
 
 
+def test_refused_load_gives_its_memory_back(pkg, weights_mod):
+    """A manifest that build_model refuses AFTER the blob went up (a tensor missing, a tensor of another shape) must leave no HBM
+    behind: everything the loader had allocated goes back through the destructors of what it was building.  Free memory after each
+    refused load is at least what it was before, minus the 8 MiB that test_gpu_contexts.py allows for "costs next to nothing"; the
+    blob is 80 MB, so a loader that drops it on the floor misses by ten times the allowance."""
+    cfg = weights_mod.small_config(enc_layers=5, dec_layers=1)
+    man, blob = weights_mod.synth_weights(cfg)
+    assert blob.nbytes >= 64 << 20
+    pkg.ParaformerHip().InitAsr((man, blob)).close()          # the runtime's one-time allocations fall outside the window
+    tensors, name = man["tensors"], "enc.4.ffn2.w"
+    missing = dict(man, tensors={k: v for k, v in tensors.items() if k != name})
+    reshaped = dict(man, tensors=dict(tensors, **{name: dict(tensors[name], shape=tensors[name]["shape"][::-1])}))
+    for bad, why in ((missing, "missing tensor"), (reshaped, "unexpected shape")):
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+        with pytest.raises(pkg.PfhipError, match=why):
+            pkg.ParaformerHip().InitAsr((bad, blob))
+        torch.cuda.synchronize()
+        free1 = torch.cuda.mem_get_info()[0]
+        print(f"refused load ({why}): blob {blob.nbytes >> 20} MiB, free before {free0 >> 20} MiB, after {free1 >> 20} MiB")
+        assert free1 >= free0 - (8 << 20), (why, free0 - free1, blob.nbytes)
+
+
 def test_full_size_properties(pkg, weights_mod):
     """BASELINE configs[1] shapes (full Paraformer-large, 30-s utterances) through size-independent
     properties: deterministic, batch-order equivariant, log-probs normalised, token_num == fires."""
