@@ -298,31 +298,16 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(
 
 // One launch of the fp32-MFMA kernel for the head widths it is built for; any other width is a programming error (the ABI and
 // pfhip_create refuse it before a launch is reached)
-static void launch_attention_f32(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                                 const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, const int* q_kv_limit, int B, int H,
-                                 int max_q_len, float scale, int head_dim, hipStream_t s) {
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB), block(256);
-#define PFHIP_ATT(HD_)                                                                                                      \
-  hipLaunchKernelGGL(attention_kernel<HD_>, grid, block, 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, \
-                     q_kv_limit, scale)
-  if (head_dim == 32) PFHIP_ATT(32);
-  else if (head_dim == 80) PFHIP_ATT(80);
-  else if (head_dim == 128) PFHIP_ATT(128);
-  else { fprintf(stderr, "pfhip: no attention kernel for head width %d\n", head_dim); abort(); }
+static void launch_attention_f32(const AttnOp& o, hipStream_t s) {
+  const dim3 grid(o.H, o.B, (o.max_q_len + kQB - 1) / kQB), block(256);
+#define PFHIP_ATT(HD_)                                                                                                              \
+  hipLaunchKernelGGL(attention_kernel<HD_>, grid, block, 0, s, o.Q, o.ldq, o.K, o.ldk, o.V, o.ldv, o.O, o.ldo, o.q_off, o.q_len, o.kv_off, \
+                     o.kv_len, o.q_kv_limit, o.scale)
+  if (o.head_dim == 32) PFHIP_ATT(32);
+  else if (o.head_dim == 80) PFHIP_ATT(80);
+  else if (o.head_dim == 128) PFHIP_ATT(128);
+  else { fprintf(stderr, "pfhip: no attention kernel for head width %d\n", o.head_dim); abort(); }
 #undef PFHIP_ATT
-}
-
-void launch_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
-                      float* O, int ldo, const int* q_off, const int* q_len, const int* kv_off,
-                      const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s, int head_dim) {
-  launch_attention_hd(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, head_dim, s);
-}
-
-void launch_attention_masked(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                             const int* q_off, const int* q_len, const int* kv_off, const int* kv_len,
-                             const int* q_kv_limit, int B, int H, int max_q_len, float scale, int head_dim, hipStream_t s) {
-  if (B <= 0 || max_q_len <= 0) return;
-  launch_attention_f32(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, q_kv_limit, B, H, max_q_len, scale, head_dim, s);
 }
 
 // the split-operand attention: two fp16 planes / three products (attention_x3.hip, default) or three bf16 planes / six products
@@ -331,12 +316,9 @@ static bool att_x3_on() {
   static const bool x3 = env_on("PFHIP_ATT_X3");
   return x3 && !launch_ctx().exact;
 }
-static void launch_attention_split(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                                   const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
-                                   float scale, hipStream_t s, const float* fsmn_w = nullptr, float* mem = nullptr, int ldmem = 0,
-                                   bool mem_accumulate = false, void* planes_hi = nullptr, void* planes_lo = nullptr, int plane_rows = 0) {
-  if (att_x3_on()) launch_attention_x3(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, s, fsmn_w, mem, ldmem, mem_accumulate, planes_hi, planes_lo, plane_rows);
-  else launch_attention_x6(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, s, fsmn_w, mem, ldmem, mem_accumulate);
+static void launch_attention_split(const AttnOp& op, hipStream_t s) {
+  if (att_x3_on()) launch_attention_x3(op, s);
+  else launch_attention_x6(op, s);
 }
 
 static bool att_x6_on() {
@@ -352,36 +334,35 @@ bool attention_fsmn_is_fused(int max_len, int head_dim) {
 
 bool attention_planes_ok(int max_len, int head_dim) { return attention_fsmn_is_fused(max_len, head_dim) && att_x3_on(); }
 
-void launch_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                           const int* off, const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem,
-                           int ldmem, hipStream_t s, bool mem_accumulate, void* planes_hi, void* planes_lo, int plane_rows, int head_dim) {
-  if (B <= 0 || max_len <= 0) return;
-  if (attention_fsmn_is_fused(max_len, head_dim)) {
-    launch_attention_split(Q, ldq, K, ldk, V, ldv, O, ldo, off, len, off, len, B, H, max_len, scale, s, fsmn_w, mem, ldmem, mem_accumulate,
-                           planes_hi, planes_lo, plane_rows);
+void launch_attention_fsmn(const AttnOp& op, hipStream_t s) {
+  if (op.B <= 0 || op.max_q_len <= 0) return;
+  if (attention_fsmn_is_fused(op.max_q_len, op.head_dim)) {
+    launch_attention_split(op, s);
     return;
   }
-  launch_fsmn(V, ldv, fsmn_w, nullptr, 0, mem, ldmem, off, len, B, max_len, H * head_dim, s);
-  launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, off, len, off, len, B, H, max_len, scale, s, head_dim);
+  launch_fsmn(op.V, op.ldv, op.fsmn_w, nullptr, 0, op.mem, op.ldmem, op.q_off, op.q_len, op.B, op.max_q_len, op.H * op.head_dim, s);
+  launch_attention(op, s);      // (which leaves the memory block and the plane images out: fp32 rows of context)
 }
 
-void launch_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                         const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
-                         int max_q_len, float scale, int head_dim, hipStream_t s) {
-  if (B <= 0 || max_q_len <= 0) return;
+void launch_attention(const AttnOp& full, hipStream_t s) {
+  if (full.B <= 0 || full.max_q_len <= 0) return;
+  AttnOp op = full;      // plain attention on every kernel this may take: no memory block, no plane images
+  op.fsmn_w = nullptr; op.mem = nullptr; op.ldmem = 0; op.mem_accumulate = false;
+  op.planes_hi = op.planes_lo = nullptr; op.plane_rows = 0;
+  const bool unmasked = op.q_kv_limit == nullptr;      // the per-query key limit lives in this file's fp32 kernel
   // d_k = 128 without per-query limits (encoder self-attention, decoder cross-attention): both products on the BF16 matrix
   // cores with the exact three-way split (attention_x6.hip) — 1.5 x this file's fp32-MFMA kernel.  PFHIP_ATT_X6=0 keeps fp32.
-  if (att_x6_on() && head_dim == 128 && max_q_len > 64) {      // streaming windows (20 queries) would leave 7 of its 8 waves idle
-    launch_attention_split(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, s);
+  if (unmasked && att_x6_on() && op.head_dim == 128 && op.max_q_len > 64) {      // streaming windows (20 queries) would leave 7 of its 8 waves idle
+    launch_attention_split(op, s);
     return;
   }
   // d_k = 80 (the small Paraformer): the same switch at 64 queries onto the fp16 two-plane kernel of attention_h80.hip; the exact
   // re-run of the range guard (launch_ctx().exact: no fp16 planes) and PFHIP_ATT_X6=0 / PFHIP_ATT_X3=0 keep this file's fp32 kernel
-  if (att_x6_on() && att_x3_on() && head_dim == 80 && max_q_len > 64) {
-    launch_attention_h80(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, s);
+  if (unmasked && att_x6_on() && att_x3_on() && op.head_dim == 80 && op.max_q_len > 64) {
+    launch_attention_h80(op, s);
     return;
   }
-  launch_attention_f32(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, nullptr, B, H, max_q_len, scale, head_dim, s);
+  launch_attention_f32(op, s);
 }
 
 }  // namespace pfhip

@@ -2,7 +2,7 @@
 // attention_x3.hip: Q, K, V and the probabilities are staged as two fp16 planes (hi = fp16_rtz(x), lo = fp16_rn(x - hi)), three
 // products per block on `v_mfma_f32_32x32x16_f16`, fp32 accumulation, flash-style online softmax, ragged segments through the same
 // q_off / q_len / kv_off / kv_len interface.  Used for launches of more than 64 queries per utterance outside the exact launch
-// context (attention.hip: launch_attention_hd); the fp32-MFMA attention_kernel<80> serves the rest.
+// context (attention.hip: launch_attention); the fp32-MFMA attention_kernel<80> serves the rest.
 //
 // One workgroup = 8 waves = 256 query rows of one (utterance, head); a wave keeps its 32 queries' Q planes in registers.  Per 32-key
 // tile:
@@ -262,13 +262,11 @@ __global__ __launch_bounds__(512, 1) void attention_h80_kernel(
 
 }  // namespace
 
-void launch_attention_h80(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
-                          float scale, hipStream_t s) {
-  if (B <= 0 || max_q_len <= 0) return;
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB);
-  launch_with_lds<attention_h80_kernel>(grid, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
-                     kv_len, scale);
+void launch_attention_h80(const AttnOp& o, hipStream_t s) {
+  if (o.B <= 0 || o.max_q_len <= 0) return;
+  const dim3 grid(o.H, o.B, (o.max_q_len + kQB - 1) / kQB);
+  launch_with_lds<attention_h80_kernel>(grid, kLdsBytes, s, o.Q, o.ldq, o.K, o.ldk, o.V, o.ldv, o.O, o.ldo, o.q_off, o.q_len, o.kv_off,
+                     o.kv_len, o.scale);
 }
 
 }  // namespace pfhip

@@ -388,13 +388,11 @@ __global__ __launch_bounds__(512, 1) void attention_x6_kernel(
 
 }  // namespace
 
-void launch_attention_x6(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                         const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
-                         float scale, hipStream_t s, const float* fsmn_w, float* mem, int ldmem, bool mem_accumulate) {
-  if (B <= 0 || max_q_len <= 0) return;
-  const dim3 grid(H, B, (max_q_len + kQB - 1) / kQB);
-  launch_with_lds<attention_x6_kernel>(grid, kLdsBytes, s, Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off,
-                     kv_len, scale, fsmn_w, mem, ldmem, mem_accumulate ? 1 : 0);
+void launch_attention_x6(const AttnOp& o, hipStream_t s) {
+  if (o.B <= 0 || o.max_q_len <= 0) return;
+  const dim3 grid(o.H, o.B, (o.max_q_len + kQB - 1) / kQB);
+  launch_with_lds<attention_x6_kernel>(grid, kLdsBytes, s, o.Q, o.ldq, o.K, o.ldk, o.V, o.ldv, o.O, o.ldo, o.q_off, o.q_len, o.kv_off,
+                     o.kv_len, o.scale, o.fsmn_w, o.mem, o.ldmem, o.mem_accumulate ? 1 : 0);
 }
 
 }  // namespace pfhip

@@ -607,71 +607,42 @@ inline int column_group_width(int M, int K, int tiles_n) {
   return est_grouped < est_all ? g : tiles_n;
 }
 
-template <bool GUARD>
-void launch_variant64(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias,
-                      const float* R1, int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu,
-                      hipStream_t s) {
-  const int tiles_m = (M + kTileM64 - 1) / kTileM64;
-  const int tiles_n = (N + kTileN - 1) / kTileN;
+template <bool GUARD, int TILE_M>
+void launch_variant(const GemmOp& o, hipStream_t s) {
+  const int tiles_m = (o.M + TILE_M - 1) / TILE_M;
+  const int tiles_n = (o.N + kTileN - 1) / kTileN;
   const int n_tiles = tiles_m * tiles_n;
   const dim3 grid(n_tiles), block(256);
-  const int gw = column_group_width(M, K, tiles_n);
-#define PFHIP_GEMM64(B_, R1_, R2_, RL_)                                                              \
-  hipLaunchKernelGGL((gemm_f32_mfma64_kernel<GUARD, B_, R1_, R2_, RL_>), grid, block, 0, s, A, lda, W, \
-                     ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw)
-  const int key = (bias ? 8 : 0) | (R1 ? 4 : 0) | (R2 ? 2 : 0) | (relu ? 1 : 0);
+  const int gw = column_group_width(o.M, o.K, tiles_n);
+  // one launch of the 128-row (gemm_f32_mfma_kernel) or the 64-row (gemm_f32_mfma64_kernel) tiled kernel
+#define PFHIP_GEMM(KERN, B_, R1_, R2_, RL_)                                                                       \
+  hipLaunchKernelGGL((KERN<GUARD, B_, R1_, R2_, RL_>), grid, block, 0, s, o.A, o.lda, o.W, o.ldw, o.C, o.ldc, o.bias, \
+                     o.R1, o.ldr1, o.R2, o.ldr2, o.M, o.N, o.K, tiles_n, n_tiles, gw)
+#define PFHIP_GEMM_TILE(...)                                                                      \
+  do {                                                                                            \
+    if constexpr (TILE_M == kTileM64) PFHIP_GEMM(gemm_f32_mfma64_kernel, __VA_ARGS__);            \
+    else PFHIP_GEMM(gemm_f32_mfma_kernel, __VA_ARGS__);                                           \
+  } while (0)
+  const int key = (o.bias ? 8 : 0) | (o.R1 ? 4 : 0) | (o.R2 ? 2 : 0) | (o.relu ? 1 : 0);
   switch (key) {
-    case 0: PFHIP_GEMM64(false, false, false, false); break;
-    case 1: PFHIP_GEMM64(false, false, false, true); break;
-    case 2: PFHIP_GEMM64(false, false, true, false); break;
-    case 3: PFHIP_GEMM64(false, false, true, true); break;
-    case 4: PFHIP_GEMM64(false, true, false, false); break;
-    case 5: PFHIP_GEMM64(false, true, false, true); break;
-    case 6: PFHIP_GEMM64(false, true, true, false); break;
-    case 7: PFHIP_GEMM64(false, true, true, true); break;
-    case 8: PFHIP_GEMM64(true, false, false, false); break;
-    case 9: PFHIP_GEMM64(true, false, false, true); break;
-    case 10: PFHIP_GEMM64(true, false, true, false); break;
-    case 11: PFHIP_GEMM64(true, false, true, true); break;
-    case 12: PFHIP_GEMM64(true, true, false, false); break;
-    case 13: PFHIP_GEMM64(true, true, false, true); break;
-    case 14: PFHIP_GEMM64(true, true, true, false); break;
-    default: PFHIP_GEMM64(true, true, true, true); break;
+    case 0: PFHIP_GEMM_TILE(false, false, false, false); break;   // decoder ffn2 (no bias)
+    case 1: PFHIP_GEMM_TILE(false, false, false, true); break;
+    case 2: PFHIP_GEMM_TILE(false, false, true, false); break;
+    case 3: PFHIP_GEMM_TILE(false, false, true, true); break;
+    case 4: PFHIP_GEMM_TILE(false, true, false, false); break;
+    case 5: PFHIP_GEMM_TILE(false, true, false, true); break;
+    case 6: PFHIP_GEMM_TILE(false, true, true, false); break;
+    case 7: PFHIP_GEMM_TILE(false, true, true, true); break;
+    case 8: PFHIP_GEMM_TILE(true, false, false, false); break;    // qkv, q, kv, vocab
+    case 9: PFHIP_GEMM_TILE(true, false, false, true); break;     // ffn1, predictor conv
+    case 10: PFHIP_GEMM_TILE(true, false, true, false); break;
+    case 11: PFHIP_GEMM_TILE(true, false, true, true); break;
+    case 12: PFHIP_GEMM_TILE(true, true, false, false); break;    // ffn2 + residual, first-layer out-proj
+    case 13: PFHIP_GEMM_TILE(true, true, false, true); break;     // predictor conv + residual
+    case 14: PFHIP_GEMM_TILE(true, true, true, false); break;     // out-proj + fsmn memory + residual
+    default: PFHIP_GEMM_TILE(true, true, true, true); break;
   }
-#undef PFHIP_GEMM64
-}
-
-template <bool GUARD>
-void launch_variant(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias,
-                    const float* R1, int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu,
-                    hipStream_t s) {
-  const int tiles_m = (M + kTileM - 1) / kTileM;
-  const int tiles_n = (N + kTileN - 1) / kTileN;
-  const int n_tiles = tiles_m * tiles_n;
-  const dim3 grid(n_tiles), block(256);
-  const int gw = column_group_width(M, K, tiles_n);
-#define PFHIP_GEMM(B_, R1_, R2_, RL_)                                                              \
-  hipLaunchKernelGGL((gemm_f32_mfma_kernel<GUARD, B_, R1_, R2_, RL_>), grid, block, 0, s, A, lda, W, \
-                     ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw)
-  const int key = (bias ? 8 : 0) | (R1 ? 4 : 0) | (R2 ? 2 : 0) | (relu ? 1 : 0);
-  switch (key) {
-    case 0: PFHIP_GEMM(false, false, false, false); break;   // decoder ffn2 (no bias)
-    case 1: PFHIP_GEMM(false, false, false, true); break;
-    case 2: PFHIP_GEMM(false, false, true, false); break;
-    case 3: PFHIP_GEMM(false, false, true, true); break;
-    case 4: PFHIP_GEMM(false, true, false, false); break;
-    case 5: PFHIP_GEMM(false, true, false, true); break;
-    case 6: PFHIP_GEMM(false, true, true, false); break;
-    case 7: PFHIP_GEMM(false, true, true, true); break;
-    case 8: PFHIP_GEMM(true, false, false, false); break;    // qkv, q, kv, vocab
-    case 9: PFHIP_GEMM(true, false, false, true); break;     // ffn1, predictor conv
-    case 10: PFHIP_GEMM(true, false, true, false); break;
-    case 11: PFHIP_GEMM(true, false, true, true); break;
-    case 12: PFHIP_GEMM(true, true, false, false); break;    // ffn2 + residual, first-layer out-proj
-    case 13: PFHIP_GEMM(true, true, false, true); break;     // predictor conv + residual
-    case 14: PFHIP_GEMM(true, true, true, false); break;     // out-proj + fsmn memory + residual
-    default: PFHIP_GEMM(true, true, true, true); break;
-  }
+#undef PFHIP_GEMM_TILE
 #undef PFHIP_GEMM
 }
 
@@ -713,64 +684,67 @@ static bool x3_enabled() {
   static const bool on = env_on("PFHIP_GEMM_X3");
   return on && !launch_ctx().exact;
 }
-static void launch_split_gemm(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                              int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, int gw, hipStream_t s, bool small_tile,
-                              const float* ln_stats, int ln_tiles, float* stats_out, bool half_tile, const float* ln_colsum, int form,
-                              float w_scale) {
-  if (form == 3 || (form == 0 && x3_enabled())) {
+static void launch_split_gemm(const GemmOp& op, SplitTile tile, SplitForm form, hipStream_t s) {
+  const int gw = column_group_width(op.M, op.K, (op.N + kTileN - 1) / kTileN);
+  if (form == SplitForm::F16x3 || (form == SplitForm::ByContext && x3_enabled())) {
     // PFHIP_X3_SW: override of the per-tensor weight scale the caller passes (log2)
     static const float sw_env = [] { const char* e = getenv("PFHIP_X3_SW"); return e ? ldexpf(1.f, atoi(e)) : 0.f; }();
-    launch_gemm_f32_f16x3(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, gw, s, small_tile, ln_stats, ln_tiles, stats_out,
-                          half_tile, ln_colsum, sw_env > 0.f ? sw_env : w_scale);
+    GemmOp scaled = op;
+    if (sw_env > 0.f) scaled.w_scale = sw_env;
+    launch_gemm_f32_f16x3(scaled, tile, gw, s);
     return;
   }
-  launch_gemm_f32_bf16x6(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, gw, s, small_tile, ln_stats, ln_tiles, stats_out,
-                         half_tile, ln_colsum);
+  launch_gemm_f32_bf16x6(op, tile, gw, s);
 }
 
-void launch_gemm_f32_kind(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                          int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, bool guard, int kind,
-                          hipStream_t s, float w_scale) {
+void launch_gemm(const GemmOp& op, GemmKernel kernel, bool guard, hipStream_t s) {
+  const int M = op.M, N = op.N, K = op.K;
   if (M <= 0 || N <= 0) return;
   const int tiles = ((M + kTileM - 1) / kTileM) * ((N + kTileN - 1) / kTileN);
   // Launches of at least half a round of tiles go to the BF16 matrix cores (exact three-way split, six MFMAs per block:
   // gemm_x6.hip) — 1.3-1.6 x the fp32 MFMA kernels, results at least as close to fp64 as the fp32 chain.  Its 128 x 128 tile
   // (two blocks per CU) wins on the K = 512 shapes and on every under-filled grid; the 256 x 128 tile on long-K launches that
   // fill the chip (FFN2 at full batch: 201 vs 194 TF).  PFHIP_GEMM_X6=0 turns the path off.
-  const bool x6_on = x6_enabled();
-  const int tiles256 = ((M + 255) / 256) * ((N + kTileN - 1) / kTileN);
   // (tools/gemm_small_probe.py: between 48 and 128 tiles of 128 x 128 the half-height BF16-split kernel beats both the fp32-MFMA
   // 64-row kernel and the 128 x 128 BF16-split kernel by 15-25 % — 1-5 utterances of 30 s, rounds of 25-128 streaming connections)
-  // kinds 4 / 5 / 7: the bf16 six-product form (256 x 128, 128 x 128, 64 x 128 tile); 8 / 9 / 10: the fp16 three-product form
-  if (kind == 4 || kind == 5 || kind == 7 || kind == 8 || kind == 9 || kind == 10 || (kind == 0 && x6_on && tiles >= 48)) {
-    const int form = kind == 0 ? 0 : (kind >= 8 ? 3 : 6);
-    if (kind >= 8) kind = kind == 8 ? 4 : (kind == 9 ? 5 : 7);
-    const bool small_tile = kind == 5 || kind == 7 || (kind == 0 && !(K >= 1024 && tiles256 >= 180));
-    // measured (tools/gemm_mid_probe.py, kinds 5 vs 7, N = 512): the half-height tile wins while its own grid still fits one
+  const bool by_size = kernel == GemmKernel::BySize;
+  const bool split = kernel == GemmKernel::SplitBySize || (by_size && x6_enabled() && tiles >= 48);
+  if (split) {
+    const int tiles256 = ((M + 255) / 256) * ((N + kTileN - 1) / kTileN);
+    // measured (tools/gemm_mid_probe.py, 128- vs 64-row tile, N = 512): the half-height tile wins while its own grid still fits one
     // workgroup per CU (<= 128 tiles of 128 x 128 = 256 half tiles: 19.0 vs 22.1 us at M = 4000, K = 512; 61 vs 66 at K = 2048);
     // at 160 tiles (316 half tiles: a second, mostly empty round) the taller tile is ahead again (23.2 vs 27.4, 72 vs 93 us at
     // M = 5000), as at 220 (28.3 vs 31.9 at M = 7015)
-    const bool half_tile = kind == 7 || (kind == 0 && small_tile && tiles <= 128);
-    launch_split_gemm(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu,
-                      column_group_width(M, K, (N + kTileN - 1) / kTileN), s, small_tile, nullptr, 0, nullptr, half_tile, nullptr, form,
-                      w_scale);
+    const SplitTile tile = K >= 1024 && tiles256 >= 180 ? SplitTile::Rows256 : (tiles <= 128 ? SplitTile::Rows64 : SplitTile::Rows128);
+    launch_split_gemm(op, tile, SplitForm::ByContext, s);
     return;
   }
-  const bool skinny = kind == 2 || (kind == 0 && tiles < kStreamingBelowTiles);
-  const bool half = kind == 3 || (kind == 0 && prefer_half_tile(tiles));
-  if (skinny) {   // always bounds-checked
+  if (kernel <= GemmKernel::Tiled64 && (op.ln_stats || op.ln_colsum || op.stats_out)) {      // a programming error, as a wrong head width is
+    fprintf(stderr, "pfhip: the LayerNorm fold and the row statistics need the split-operand GEMM kernels\n");
+    abort();
+  }
+  switch (kernel) {
+    case GemmKernel::Bf16_256: launch_split_gemm(op, SplitTile::Rows256, SplitForm::Bf16x6, s); return;
+    case GemmKernel::Bf16_128: launch_split_gemm(op, SplitTile::Rows128, SplitForm::Bf16x6, s); return;
+    case GemmKernel::Bf16_64: launch_split_gemm(op, SplitTile::Rows64, SplitForm::Bf16x6, s); return;
+    case GemmKernel::F16_256: launch_split_gemm(op, SplitTile::Rows256, SplitForm::F16x3, s); return;
+    case GemmKernel::F16_128: launch_split_gemm(op, SplitTile::Rows128, SplitForm::F16x3, s); return;
+    case GemmKernel::F16_64: launch_split_gemm(op, SplitTile::Rows64, SplitForm::F16x3, s); return;
+    default: break;
+  }
+  if (kernel == GemmKernel::Streaming || (by_size && tiles < kStreamingBelowTiles)) {   // always bounds-checked
     const dim3 grid((N + 31) / 32, (M + 31) / 32), block(1024);
-    hipLaunchKernelGGL(gemm_f32_skinny_kernel, grid, block, 0, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N,
-                       K, relu ? 1 : 0);
+    hipLaunchKernelGGL(gemm_f32_skinny_kernel, grid, block, 0, s, op.A, op.lda, op.W, op.ldw, op.C, op.ldc, op.bias, op.R1, op.ldr1, op.R2,
+                       op.ldr2, M, N, K, op.relu ? 1 : 0);
     return;
   }
-  if (half) {
-    if (guard) launch_variant64<true>(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, s);
-    else launch_variant64<false>(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, s);
+  if (kernel == GemmKernel::Tiled64 || (by_size && prefer_half_tile(tiles))) {
+    if (guard) launch_variant<true, kTileM64>(op, s);
+    else launch_variant<false, kTileM64>(op, s);
     return;
   }
-  if (guard) launch_variant<true>(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, s);
-  else launch_variant<false>(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, s);
+  if (guard) launch_variant<true, kTileM>(op, s);
+  else launch_variant<false, kTileM>(op, s);
 }
 
 // whether the large GEMMs run the fp16 two-plane form (gemm_x3.hip / gemm_p3.hip) — PFHIP_GEMM_X3=0 asks for the bf16 three-plane one
@@ -779,24 +753,6 @@ bool gemm_x6_ln_ok(int M) {
   static const bool ln_on = env_on("PFHIP_GEMM_LN");
   // from the batch size at which the N = 512 launches (four column tiles per row panel) go to the BF16-split kernels at all
   return ln_on && x6_enabled() && ((M + kTileM - 1) / kTileM) * 4 >= 48;
-}
-void launch_gemm_f32_x6_ln(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                           int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, const float* ln_stats, int ln_tiles,
-                           const float* ln_colsum, float* stats_out, hipStream_t s, float w_scale) {
-  if (M <= 0 || N <= 0) return;
-  const int tiles256 = ((M + 255) / 256) * ((N + kTileN - 1) / kTileN);
-  const bool small_tile = !(K >= 1024 && tiles256 >= 180);
-  const int tiles128 = ((M + kTileM - 1) / kTileM) * ((N + kTileN - 1) / kTileN);
-  const bool half_tile = small_tile && tiles128 <= 128;       // as the default dispatch: 64-row tiles where 128-row ones leave CUs idle
-  launch_split_gemm(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu,
-                    column_group_width(M, K, (N + kTileN - 1) / kTileN), s, small_tile, ln_stats, ln_tiles, stats_out, half_tile,
-                    ln_colsum, 0, w_scale);
-}
-
-void launch_gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, int ldc,
-                     const float* bias, const float* R1, int ldr1, const float* R2, int ldr2, int M,
-                     int N, int K, bool relu, bool guard, hipStream_t s, float w_scale) {
-  launch_gemm_f32_kind(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, guard, 0, s, w_scale);
 }
 
 }  // namespace pfhip

@@ -1319,11 +1319,15 @@ bool gemm_p3_wide_serves(bool c, bool planes, bool r1, bool ln, bool stats_out, 
 #ifndef PFHIP_P3_LDS_PAD
 #define PFHIP_P3_LDS_PAD 0      // timing-only builds: extra LDS per workgroup of the 128-row kernel (32768: ONE workgroup per CU)
 #endif
-void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, const void* Wl, int rows_w, float w_scale, float* C, int ldc,
-                    void* Ph, void* Pl, int rows_p, const float* bias, const float* R1, int ldr1, int M, int N, int K, bool relu,
-                    const float* ln_stats, int ln_tiles, const float* ln_colsum, float* stats_out, int gw, hipStream_t s, int tile_rows,
-                    int row_planes_from, int tile_cols) {
+void launch_gemm_p3(const PlaneGemmOp& o, hipStream_t s, int tile_rows, int tile_cols) {
+  const int M = o.M, N = o.N, K = o.K, rows_a = o.rows_a, row_planes_from = o.row_planes_from, rl = o.relu ? 1 : 0;
+  float* const C = o.C;
   if (M <= 0 || N <= 0) return;
+  constexpr int kGroupWidth = 4;      // column-group width of the tile order: what every caller has asked for
+  const float inv = 1.0f / o.w_scale;
+  const unsigned char *ah = static_cast<const unsigned char*>(o.Ah), *al = static_cast<const unsigned char*>(o.Al);
+  const unsigned char *wh = static_cast<const unsigned char*>(o.Wh), *wl = static_cast<const unsigned char*>(o.Wl);
+  unsigned char *ph = static_cast<unsigned char*>(o.Ph), *pl = static_cast<unsigned char*>(o.Pl);
   // The 256 x 256 tile (one persistent eight-wave workgroup per CU): the LayerNorm-folded forms with one output (FFN1', QKV') where its
   // tiles fill at least 85 % of the CU slots of their rounds (the rule of the 256 x 128 tile), there is more than one round (the
   // overlap of a tile's epilogue with the next tile's first DMAs is what the single workgroup per CU lives on; one-round grids such as
@@ -1332,26 +1336,22 @@ void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, 
   // QKV' forced onto this tile (378 tiles: 74 % of two rounds) 99.2 - 100.6 against 94.9 - 99.1: not taken, and the rule leaves it out.  PFHIP_P3_WIDE=0 keeps the 128-column kernels (read per launch: tests and A/B runs switch it);
   // tile_cols = 256 forces it for any form it serves.
   {
-    const bool serves = gemm_p3_wide_serves(C != nullptr, Ph != nullptr, R1 != nullptr, ln_stats != nullptr, stats_out != nullptr, row_planes_from, N, K);
+    const bool serves = gemm_p3_wide_serves(C != nullptr, o.Ph != nullptr, o.R1 != nullptr, o.ln_stats != nullptr, o.stats_out != nullptr, row_planes_from, N, K);
     const int nw = ((M + kWM - 1) / kWM) * (N / kWN), cus = cu_count(), rounds = (nw + cus - 1) / cus;
     const bool w_env = env_on("PFHIP_P3_WIDE");
     const int half_lim = half_tiles_limit();
-    const bool by_rule = tile_cols == 0 && tile_rows == 0 && w_env && serves && ln_tiles == 4 && K >= 256 && rows_a >= kWM && nw > cus &&
+    const bool by_rule = tile_cols == 0 && tile_rows == 0 && w_env && serves && o.ln_tiles == 4 && K >= 256 && rows_a >= kWM && nw > cus &&
                          ((M + kPM - 1) / kPM) * ((N + kPN - 1) / kPN) > half_lim && 100 * nw >= 85 * cus * rounds;
     if (serves && (tile_cols == kWN || by_rule)) {
       const int grid = (nw + rounds - 1) / rounds;      // every workgroup walks `rounds` tiles where that divides (504 tiles: 252 x 2)
-      const float inv = 1.0f / w_scale;
-      const unsigned char *ah = static_cast<const unsigned char*>(Ah), *al = static_cast<const unsigned char*>(Al);
-      const unsigned char *wh = static_cast<const unsigned char*>(Wh), *wl = static_cast<const unsigned char*>(Wl);
-      const int tn = N / kWN, g = std::max(1, std::min(gw, tn));
+      const int tn = N / kWN, g = std::max(1, std::min(kGroupWidth, tn));
       g_wide_launches.fetch_add(1, std::memory_order_relaxed);
       if (C)
-        launch_with_lds<gemm_p3_256x256_kernel<true, 1>, kWThreads>(grid, kWLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, nullptr, nullptr, rows_p, bias,
-                                                                    M, N, K, tn, nw, g, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, inv, launch_ctx().range_flag);
+        launch_with_lds<gemm_p3_256x256_kernel<true, 1>, kWThreads>(grid, kWLds, s, ah, al, rows_a, wh, wl, o.rows_w, C, o.ldc, nullptr, nullptr, o.rows_p, o.bias,
+                                                                    M, N, K, tn, nw, g, rl, o.ln_stats, o.ln_tiles, 1e-12f, o.ln_colsum, inv, launch_ctx().range_flag);
       else
-        launch_with_lds<gemm_p3_256x256_kernel<true, 2>, kWThreads>(grid, kWLds, s, ah, al, rows_a, wh, wl, rows_w, nullptr, 0, static_cast<unsigned char*>(Ph),
-                                                                    static_cast<unsigned char*>(Pl), rows_p, bias, M, N, K, tn, nw, g, relu ? 1 : 0, ln_stats,
-                                                                    ln_tiles, 1e-12f, ln_colsum, inv, launch_ctx().range_flag);
+        launch_with_lds<gemm_p3_256x256_kernel<true, 2>, kWThreads>(grid, kWLds, s, ah, al, rows_a, wh, wl, o.rows_w, nullptr, 0, ph, pl, o.rows_p, o.bias, M, N, K,
+                                                                    tn, nw, g, rl, o.ln_stats, o.ln_tiles, 1e-12f, o.ln_colsum, inv, launch_ctx().range_flag);
       return;
     }
   }
@@ -1380,49 +1380,34 @@ void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, 
   const int tmr = quad ? kQM : (half ? kHM : kPM);
   const int n_tiles = ((M + tmr - 1) / tmr) * tiles_n;
   static const int gw_env = env_int("PFHIP_P3_GW", 0);      // experiments
-
-  if (gw_env > 0) gw = gw_env;
-  gw = std::max(1, std::min(gw, tiles_n));
-  const int out = (C ? 1 : 0) | (Ph ? 2 : 0);
-  const float inv = 1.0f / w_scale;
-  const unsigned char *ah = static_cast<const unsigned char*>(Ah), *al = static_cast<const unsigned char*>(Al);
-  const unsigned char *wh = static_cast<const unsigned char*>(Wh), *wl = static_cast<const unsigned char*>(Wl);
-  unsigned char *ph = static_cast<unsigned char*>(Ph), *pl = static_cast<unsigned char*>(Pl);
-#define PFHIP_P3(LNF, OUTM)                                                                                                     \
-  {                                                                                                                             \
-    if (quad)                                                                                                                   \
-      launch_with_lds<gemm_p3_256_kernel<LNF, OUTM>, kQThreads>(n_tiles, kQLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
-                                                    M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
-    else if (half)                                                                                                              \
-      launch_with_lds<gemm_p3_64_kernel<LNF, OUTM>, kPThreads>(n_tiles, kHLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
-                                                    M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
-    else if (ring3)                                                                                                             \
-      launch_with_lds<gemm_p3_128r3_kernel<LNF, OUTM>, kPThreads>(n_tiles, kP3Lds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
-                                                     M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
-    else                                                                                                                        \
-      launch_with_lds<gemm_p3_128_kernel<LNF, OUTM>, kPThreads>(n_tiles, kPLds + PFHIP_P3_LDS_PAD, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
-                                                     M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
+  const int gw = std::max(1, std::min(gw_env > 0 ? gw_env : kGroupWidth, tiles_n));
+  const int out = (C ? 1 : 0) | (ph ? 2 : 0);
+  // one launch of a 128-column kernel (the variadic argument: its template arguments hold a comma)
+#define PFHIP_P3_GO(THREADS, LDS, ...)                                                                                                        \
+  launch_with_lds<__VA_ARGS__, THREADS>(n_tiles, LDS, s, ah, al, rows_a, wh, wl, o.rows_w, C, o.ldc, ph, pl, o.rows_p, o.bias, o.R1, o.ldr1, M, N, K, \
+                                        tiles_n, n_tiles, gw, rl, o.ln_stats, o.ln_tiles, 1e-12f, o.ln_colsum, o.stats_out, inv,              \
+                                        launch_ctx().range_flag, row_planes_from)
+#define PFHIP_P3(LNF, OUTM)                                                                              \
+  {                                                                                                      \
+    if (quad) PFHIP_P3_GO(kQThreads, kQLds, gemm_p3_256_kernel<LNF, OUTM>);                              \
+    else if (half) PFHIP_P3_GO(kPThreads, kHLds, gemm_p3_64_kernel<LNF, OUTM>);                          \
+    else if (ring3) PFHIP_P3_GO(kPThreads, kP3Lds, gemm_p3_128r3_kernel<LNF, OUTM>);                     \
+    else PFHIP_P3_GO(kPThreads, kPLds + PFHIP_P3_LDS_PAD, gemm_p3_128_kernel<LNF, OUTM>);                \
   }
   if (row_planes_from > 0) {      // the QKV projection: fp32 Q | row-major K, V planes (C and Ph both given)
-#define PFHIP_P3S(LNF)                                                                                                          \
-  {                                                                                                                             \
-    if (half)                                                                                                                   \
-      launch_with_lds<gemm_p3_64_kernel<LNF, 5>, kPThreads>(n_tiles, kHLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
-                                                 M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
-    else                                                                                                                        \
-      launch_with_lds<gemm_p3_128_kernel<LNF, 5>, kPThreads>(n_tiles, kPLds, s, ah, al, rows_a, wh, wl, rows_w, C, ldc, ph, pl, rows_p, bias, R1, ldr1, \
-                                                  M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, ln_colsum, stats_out, inv, launch_ctx().range_flag, row_planes_from); \
-  }
-    if (ln_stats) PFHIP_P3S(true) else PFHIP_P3S(false)
-#undef PFHIP_P3S
+    if (half && o.ln_stats) PFHIP_P3_GO(kPThreads, kHLds, gemm_p3_64_kernel<true, 5>);
+    else if (half) PFHIP_P3_GO(kPThreads, kHLds, gemm_p3_64_kernel<false, 5>);
+    else if (o.ln_stats) PFHIP_P3_GO(kPThreads, kPLds, gemm_p3_128_kernel<true, 5>);
+    else PFHIP_P3_GO(kPThreads, kPLds, gemm_p3_128_kernel<false, 5>);
     return;
   }
-  if (ln_stats) {
+  if (o.ln_stats) {
     if (out == 1) PFHIP_P3(true, 1) else if (out == 2) PFHIP_P3(true, 2) else PFHIP_P3(true, 3)
   } else {
     if (out == 1) PFHIP_P3(false, 1) else if (out == 2) PFHIP_P3(false, 2) else PFHIP_P3(false, 3)
   }
 #undef PFHIP_P3
+#undef PFHIP_P3_GO
 }
 
 }  // namespace pfhip

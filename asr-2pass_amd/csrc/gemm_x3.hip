@@ -705,36 +705,33 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_f16x3_64_kernel(
 
 }  // namespace
 
-void launch_gemm_f32_f16x3(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                           int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, int gw, hipStream_t s, bool small_tile,
-                           const float* ln_stats, int ln_tiles, float* stats_out, bool half_tile, const float* ln_colsum, float sw) {
-  if (M <= 0 || N <= 0) return;
-  if (ln_stats) small_tile = true;              // LayerNorm-on-load lives in the 128 / 64-row kernels (its consumers have K = 512)
-  const bool sc = sw != 1.0f;
-  const int rl = relu ? 1 : 0;
-  const float eps = 1e-12f;
-  const int tiles_n = (N + kBN - 1) / kBN;
+void launch_gemm_f32_f16x3(const GemmOp& o, SplitTile tile, int gw, hipStream_t s) {
+  if (o.M <= 0 || o.N <= 0) return;
+  if (o.ln_stats && tile == SplitTile::Rows256) tile = SplitTile::Rows128;   // LayerNorm-on-load lives in the 128 / 64-row kernels (its consumers have K = 512)
+  const float sw = o.w_scale;
+  const bool sc = sw != 1.0f, ln = o.ln_stats != nullptr;
+  const int rl = o.relu ? 1 : 0;
+  const int tm = tile == SplitTile::Rows64 ? kHM : (tile == SplitTile::Rows128 ? kSM : kBM);
+  const int tiles_n = (o.N + kBN - 1) / kBN, n_tiles = ((o.M + tm - 1) / tm) * tiles_n;
   gw = std::max(1, std::min(gw, tiles_n));
-#define PFHIP_X3_LAUNCH_LN(KERN, TM, LDS)                                                                                        \
-  {                                                                                                                              \
-    const int n_tiles = ((M + (TM) - 1) / (TM)) * tiles_n;                                                                       \
-    if (ln_stats && sc) launch_with_lds<KERN<true, true>>(n_tiles, LDS, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw, rl, ln_stats, ln_tiles, eps, stats_out, ln_colsum, sw, launch_ctx().range_flag);      \
-    else if (ln_stats) launch_with_lds<KERN<true, false>>(n_tiles, LDS, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw, rl, ln_stats, ln_tiles, eps, stats_out, ln_colsum, sw, launch_ctx().range_flag);       \
-    else if (sc) launch_with_lds<KERN<false, true>>(n_tiles, LDS, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw, rl, ln_stats, ln_tiles, eps, stats_out, ln_colsum, sw, launch_ctx().range_flag);            \
-    else launch_with_lds<KERN<false, false>>(n_tiles, LDS, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw, rl, ln_stats, ln_tiles, eps, stats_out, ln_colsum, sw, launch_ctx().range_flag);                    \
+  // the operands every kernel of this file starts with; the 128- and 64-row kernels add the LayerNorm fold and the range flag
+#define PFHIP_X3_HEAD o.A, o.lda, o.W, o.ldw, o.C, o.ldc, o.bias, o.R1, o.ldr1, o.R2, o.ldr2, o.M, o.N, o.K, tiles_n, n_tiles, gw, rl
+#define PFHIP_X3_LAUNCH_LN(LDS, ...) /* ... = the kernel: its template arguments hold a comma */                                              \
+  launch_with_lds<__VA_ARGS__>(n_tiles, LDS, s, PFHIP_X3_HEAD, o.ln_stats, o.ln_tiles, 1e-12f, o.stats_out, o.ln_colsum, sw, launch_ctx().range_flag)
+#define PFHIP_X3_LAUNCH_BY_FORM(KERN, LDS)                                     \
+  {                                                                            \
+    if (ln && sc) PFHIP_X3_LAUNCH_LN(LDS, KERN<true, true>);                   \
+    else if (ln) PFHIP_X3_LAUNCH_LN(LDS, KERN<true, false>);                   \
+    else if (sc) PFHIP_X3_LAUNCH_LN(LDS, KERN<false, true>);                   \
+    else PFHIP_X3_LAUNCH_LN(LDS, KERN<false, false>);                          \
   }
-  if (small_tile && half_tile) {
-    PFHIP_X3_LAUNCH_LN(gemm_f32_f16x3_64_kernel, kHM, kHLdsBytes)
-    return;
-  }
-  if (small_tile) {
-    PFHIP_X3_LAUNCH_LN(gemm_f32_f16x3_128_kernel, kSM, kSLdsBytes)
-    return;
-  }
+  if (tile == SplitTile::Rows64) PFHIP_X3_LAUNCH_BY_FORM(gemm_f32_f16x3_64_kernel, kHLdsBytes)
+  else if (tile == SplitTile::Rows128) PFHIP_X3_LAUNCH_BY_FORM(gemm_f32_f16x3_128_kernel, kSLdsBytes)
+  else if (sc) launch_with_lds<gemm_f32_f16x3_kernel<true>>(n_tiles, kLdsBytes, s, PFHIP_X3_HEAD, o.stats_out, sw);
+  else launch_with_lds<gemm_f32_f16x3_kernel<false>>(n_tiles, kLdsBytes, s, PFHIP_X3_HEAD, o.stats_out, sw);
+#undef PFHIP_X3_LAUNCH_BY_FORM
 #undef PFHIP_X3_LAUNCH_LN
-  const int n_tiles = ((M + kBM - 1) / kBM) * tiles_n;
-  if (sc) launch_with_lds<gemm_f32_f16x3_kernel<true>>(n_tiles, kLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw, rl, stats_out, sw);
-  else launch_with_lds<gemm_f32_f16x3_kernel<false>>(n_tiles, kLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, tiles_n, n_tiles, gw, rl, stats_out, sw);
+#undef PFHIP_X3_HEAD
 }
 
 }  // namespace pfhip

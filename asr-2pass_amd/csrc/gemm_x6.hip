@@ -587,37 +587,27 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_bf16x6_64_kernel(
 
 }  // namespace
 
-void launch_gemm_f32_bf16x6(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                            int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, int gw, hipStream_t s, bool small_tile,
-                            const float* ln_stats, int ln_tiles, float* stats_out, bool half_tile, const float* ln_colsum) {
-  if (M <= 0 || N <= 0) return;
-  if (ln_stats) small_tile = true;              // LayerNorm-on-load lives in the 128 / 64-row kernels (its consumers have K = 512)
-  if (small_tile && half_tile) {
-    const int tiles_m = (M + kHM - 1) / kHM, tiles_n = (N + kBN - 1) / kBN, n_tiles = tiles_m * tiles_n;
-    gw = std::max(1, std::min(gw, tiles_n));
-    if (ln_stats)
-      launch_with_lds<gemm_f32_bf16x6_64_kernel<true>>(n_tiles, kHLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
-                         R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
-    else
-      launch_with_lds<gemm_f32_bf16x6_64_kernel<false>>(n_tiles, kHLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
-                         R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
-    return;
-  }
-  if (small_tile) {
-    const int tiles_m = (M + kSM - 1) / kSM, tiles_n = (N + kBN - 1) / kBN, n_tiles = tiles_m * tiles_n;
-    gw = std::max(1, std::min(gw, tiles_n));
-    if (ln_stats)
-      launch_with_lds<gemm_f32_bf16x6_128_kernel<true>>(n_tiles, kSLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
-                         R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
-    else
-      launch_with_lds<gemm_f32_bf16x6_128_kernel<false>>(n_tiles, kSLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1,
-                         R2, ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, ln_stats, ln_tiles, 1e-12f, stats_out, ln_colsum);
-    return;
-  }
-  const int tiles_m = (M + kBM - 1) / kBM, tiles_n = (N + kBN - 1) / kBN, n_tiles = tiles_m * tiles_n;
+void launch_gemm_f32_bf16x6(const GemmOp& o, SplitTile tile, int gw, hipStream_t s) {
+  if (o.M <= 0 || o.N <= 0) return;
+  if (o.ln_stats && tile == SplitTile::Rows256) tile = SplitTile::Rows128;   // LayerNorm-on-load lives in the 128 / 64-row kernels (its consumers have K = 512)
+  const int tm = tile == SplitTile::Rows64 ? kHM : (tile == SplitTile::Rows128 ? kSM : kBM);
+  const int tiles_n = (o.N + kBN - 1) / kBN, n_tiles = ((o.M + tm - 1) / tm) * tiles_n, rl = o.relu ? 1 : 0;
   gw = std::max(1, std::min(gw, tiles_n));
-  launch_with_lds<gemm_f32_bf16x6_kernel>(n_tiles, kLdsBytes, s, A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2,
-                     ldr2, M, N, K, tiles_n, n_tiles, gw, relu ? 1 : 0, stats_out);
+  if (tile == SplitTile::Rows256) {
+    launch_with_lds<gemm_f32_bf16x6_kernel>(n_tiles, kLdsBytes, s, o.A, o.lda, o.W, o.ldw, o.C, o.ldc, o.bias, o.R1, o.ldr1, o.R2, o.ldr2, o.M, o.N,
+                                            o.K, tiles_n, n_tiles, gw, rl, o.stats_out);
+    return;
+  }
+  // the 128- and 64-row kernels share one parameter list
+#define PFHIP_X6_LAUNCH(KERN, LDS)                                                                                                      \
+  launch_with_lds<KERN>(n_tiles, LDS, s, o.A, o.lda, o.W, o.ldw, o.C, o.ldc, o.bias, o.R1, o.ldr1, o.R2, o.ldr2, o.M, o.N, o.K, tiles_n, \
+                        n_tiles, gw, rl, o.ln_stats, o.ln_tiles, 1e-12f, o.stats_out, o.ln_colsum)
+  const bool ln = o.ln_stats != nullptr;
+  if (tile == SplitTile::Rows64 && ln) PFHIP_X6_LAUNCH(gemm_f32_bf16x6_64_kernel<true>, kHLdsBytes);
+  else if (tile == SplitTile::Rows64) PFHIP_X6_LAUNCH(gemm_f32_bf16x6_64_kernel<false>, kHLdsBytes);
+  else if (ln) PFHIP_X6_LAUNCH(gemm_f32_bf16x6_128_kernel<true>, kSLdsBytes);
+  else PFHIP_X6_LAUNCH(gemm_f32_bf16x6_128_kernel<false>, kSLdsBytes);
+#undef PFHIP_X6_LAUNCH
 }
 
 }  // namespace pfhip

@@ -127,7 +127,9 @@ inline pfhip_status pack_linear(const float* w, const float* bias, int N, int K,
 }
 inline void lin_gemm(hipStream_t s, const PackedLin& l, const float* A, int lda, float* C, int ldc, const float* R1, int ldr1,
                      const float* R2, int ldr2, int M, bool relu) {
-  pfhip::launch_gemm_f32(A, lda, l.w.f(), l.Kp, C, ldc, l.b.f(), R1, ldr1, R2, ldr2, M, l.Np, l.Kp, relu, false, s, l.ws);
+  pfhip::launch_gemm({.A = A, .lda = lda, .W = l.w.f(), .ldw = l.Kp, .C = C, .ldc = ldc, .M = M, .N = l.Np, .K = l.Kp, .bias = l.b.f(),
+                      .R1 = R1, .ldr1 = ldr1, .R2 = R2, .ldr2 = ldr2, .relu = relu, .w_scale = l.ws},
+                     pfhip::GemmKernel::BySize, false, s);
 }
 
 struct ProfRec { int cls; hipEvent_t e0, e1; };
@@ -305,8 +307,6 @@ inline pfhip_model* route_stream(pfhip_model* m) {
 
 namespace pfhip_detail {
 
-using pfhip::launch_gemm_f32;
-
 struct Scope {
   pfhip_model* m; hipStream_t s; int cls; hipEvent_t e1 = nullptr;
   Scope(pfhip_model* m_, hipStream_t s_, int cls_, double flops, double bytes) : m(m_), s(s_), cls(cls_) {
@@ -334,7 +334,26 @@ inline void gemm(pfhip_model* m, hipStream_t s, const float* A, int lda, const L
   // N that is no multiple of the column tile AND a C too narrow for the tile's pad columns (d_model 320: N = 320 / 960 with ldc = N):
   // the bounds-checked epilogue.  The model's other shapes (N % 128 == 0, or the vocabulary with ldc = vocab_pad) keep the unguarded one.
   const bool guard = N % pfhip::kTileN != 0 && ldc < (N + pfhip::kTileN - 1) / pfhip::kTileN * pfhip::kTileN;
-  launch_gemm_f32(A, lda, L.w, K, C, ldc, L.b, R1, ldr1, R2, ldr2, M, N, K, relu, guard, s, L.scale);
+  pfhip::launch_gemm({.A = A, .lda = lda, .W = L.w, .ldw = K, .C = C, .ldc = ldc, .M = M, .N = N, .K = K, .bias = L.b, .R1 = R1, .ldr1 = ldr1,
+                      .R2 = R2, .ldr2 = ldr2, .relu = relu, .w_scale = L.scale},
+                     pfhip::GemmKernel::BySize, guard, s);
+}
+// A split-kernel GEMM (GemmKernel::SplitBySize) over M rows of the model's buffers.  op names A, C, ldc, N, K, the residuals
+// (row stride d), relu, ln_colsum (the LayerNorm fold: four statistics pairs per row read from lnstats) and stats_out; every
+// other field is filled here, over whatever the caller put there.
+inline void split_gemm(hipStream_t s, const Linear& W, pfhip::GemmOp op, int M, int d, const float* lnstats) {
+  op.lda = op.ldw = op.K; op.W = W.w; op.bias = W.b; op.w_scale = W.scale; op.M = M; op.ldr1 = op.ldr2 = d;
+  op.ln_stats = op.ln_colsum ? lnstats : nullptr; op.ln_tiles = 4;
+  pfhip::launch_gemm(op, pfhip::GemmKernel::SplitBySize, false, s);
+}
+// The matrices of an attention launch as the model lays them out; the caller adds segments, sizes, scale and what else it uses.
+// Self-attention: Q | K | V in the columns of one [rows, 3d] buffer, context [rows, d].
+inline pfhip::AttnOp qkv_attention(const float* qkv, int d, float* ctx) {
+  return {.Q = qkv, .ldq = 3 * d, .K = qkv + d, .ldk = 3 * d, .V = qkv + 2 * d, .ldv = 3 * d, .O = ctx, .ldo = d};
+}
+// Cross-attention: Q [rows, d], K | V in columns 0 and d of a buffer of row stride ldkv, context [rows, d].
+inline pfhip::AttnOp kv_attention(const float* q, int d, const float* kv, int ldkv, float* ctx) {
+  return {.Q = q, .ldq = d, .K = kv, .ldk = ldkv, .V = kv + d, .ldv = ldkv, .O = ctx, .ldo = d};
 }
 inline void lnorm(pfhip_model* m, hipStream_t s, const float* x, int ldx, float* y, int ldy, const Norm& n, int M, int D, int Dout) {
   Scope sc(m, s, K_LN, 8.0 * M * D, 8.0 * M * D);

@@ -85,33 +85,49 @@ __host__ __device__ inline bool ln_row_out_of_domain(float mean, float rstd) {
 }
 
 // ---- dense ops --------------------------------------------------------------------------------
-// C[M,N] = A[M,K] * W[N,K]^T (+bias[N]) (+R1[M,N]) (+R2[M,N]) (ReLU)   — fp32 MFMA 32x32x2.
-// A rows must be allocated up to a multiple of 128, K % 32 == 0, W readable for ceil(N/128)*128 rows.
-// guard == false (the product path): C/R1/R2 are allocated for ceil(M/128)*128 rows and
-// ceil(N/128)*128 columns and bias is readable to the padded N, so the epilogue has no bounds
-// branches (pad outputs are junk nobody reads).  guard == true bounds-checks every element.
-// C may alias R1 or R2 (in-place residual update).
-void launch_gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, int ldc,
-                     const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
-                     int M, int N, int K, bool relu, bool guard, hipStream_t s, float w_scale = 1.0f);
-// w_scale: power of two with max|W| * w_scale < 65504, used by the fp16 two-plane kernels (gemm_x3.hip) to stage W * w_scale
-// (best_w_scale below; 1 is always valid for |W| < 65504 and costs precision only for weights of very small magnitude)
+// Operands of C[M,N] = act(LNfold?(A[M,K]) W[N,K]^T + bias[N]) (+R1[M,N]) (+R2[M,N]); an absent field is nullptr / 0 / false / 1.
+// A rows must be allocated up to a multiple of 128, K % 32 == 0, W readable for ceil(N/128)*128 rows.  C may alias R1 or R2
+// (in-place residual update).
+struct GemmOp {
+  const float* A = nullptr; int lda = 0;
+  const float* W = nullptr; int ldw = 0;
+  float* C = nullptr; int ldc = 0;
+  int M = 0, N = 0, K = 0;
+  const float* bias = nullptr;
+  const float* R1 = nullptr; int ldr1 = 0;
+  const float* R2 = nullptr; int ldr2 = 0;
+  bool relu = false;
+  // power of two with max|W| * w_scale < 65504, used by the fp16 two-plane kernels (gemm_x3.hip) to stage W * w_scale
+  // (best_w_scale below; 1 is always valid for |W| < 65504 and costs precision only for weights of very small magnitude)
+  float w_scale = 1.0f;
+  // The two below are served by the split-operand kernels only (gemm_x6.hip / gemm_x3.hip: GemmKernel::SplitBySize or a forced one);
+  // launch_gemm aborts when they reach another kernel.
+  // ln_stats (with ln_tiles, ln_colsum): LayerNorm folded in — A is the raw residual stream x, W must be W * gamma, bias must be
+  // bias + W beta and ln_colsum[n] = sum_k W[n][k] gamma[k]; the epilogue forms rstd_i * (x W'^T - mean_i * colsum) + bias with the
+  // statistics merged from the ln_tiles pairs per row the producer left (eps 1e-12).
+  const float* ln_stats = nullptr; int ln_tiles = 0; const float* ln_colsum = nullptr;
+  // stats_out (N == tiles_n * 128 exactly): the epilogue also leaves per-row LayerNorm statistics of its 128-column tile at
+  // stats_out[row][tile column][2] = (mean of the tile's columns, sum of squared deviations from it).
+  float* stats_out = nullptr;
+};
+// Which kernel launch_gemm takes.  BySize: the measured rules of gemm.hip (fp32 MFMA 32x32x2 kernels below 48 tiles of 128 x 128,
+// the split-operand kernels from there).  The next nine force one kernel (dev / tests): the 128 x 128 tiled, the weight-streaming
+// and the 64 x 128 tiled fp32-MFMA kernels; the bf16 three-plane / six-product kernels (gemm_x6.hip) and the fp16 two-plane /
+// three-product kernels (gemm_x3.hip) on their 256 / 128 / 64 x 128 tiles.  SplitBySize — the product path of the LayerNorm fold
+// and of the row statistics: always the split-operand kernels, form by context and tile by the rules of BySize.
+enum class GemmKernel { BySize, Tiled128, Streaming, Tiled64, Bf16_256, Bf16_128, Bf16_64, F16_256, F16_128, F16_64, SplitBySize };
+enum class SplitTile { Rows256, Rows128, Rows64 };      // tile height of the split-operand kernels (128 columns)
+enum class SplitForm { ByContext, F16x3, Bf16x6 };      // ByContext: fp16 x3 unless PFHIP_GEMM_X3=0 or the launch context is exact
+// guard == false (the product path): C/R1/R2 are allocated for ceil(M/128)*128 rows and ceil(N/128)*128 columns and bias is
+// readable to the padded N, so the epilogue has no bounds branches (pad outputs are junk nobody reads).  guard == true
+// bounds-checks every element (the streaming and the split-operand kernels always do).
+void launch_gemm(const GemmOp& op, GemmKernel kernel, bool guard, hipStream_t s);
 float best_w_scale(float max_abs);
-// kind: 0 = pick by M, 1 = the 128 x 128 tiled kernel, 2 = the weight-streaming kernel (dev / tests)
-// fp32-grade GEMM on the BF16 matrix cores (three-way bf16 split of both operands, six MFMAs per block): gemm_x6.hip
-// stats_out (N == tiles_n * 128 exactly): the epilogue also leaves per-row LayerNorm statistics of its 128-column tile at
-// stats_out[row][tile column][2] = (mean of the tile's columns, sum of squared deviations from it).
-// ln_stats (with ln_tiles, ln_colsum): LayerNorm folded in — A is the raw residual stream x, W must be W * gamma, bias must be
-// bias + W beta and ln_colsum[n] = sum_k W[n][k] gamma[k]; the epilogue forms rstd_i * (x W'^T - mean_i * colsum) + bias with the
-// statistics merged from the ln_tiles pairs per row the producer left (eps 1e-12).
-void launch_gemm_f32_bf16x6(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                            int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, int gw, hipStream_t s, bool small_tile = false,
-                            const float* ln_stats = nullptr, int ln_tiles = 0, float* stats_out = nullptr, bool half_tile = false,
-                            const float* ln_colsum = nullptr);
-// the same tilings with TWO fp16 planes and THREE products per block (gemm_x3.hip); sw: the power-of-two weight scale
-void launch_gemm_f32_f16x3(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                           int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, int gw, hipStream_t s, bool small_tile,
-                           const float* ln_stats, int ln_tiles, float* stats_out, bool half_tile, const float* ln_colsum, float sw);
+// fp32-grade GEMM on the BF16 matrix cores (three-way bf16 split of both operands, six MFMAs per block): gemm_x6.hip.
+// gw: column-group width of the tile order.  With ln_stats the 256-row tile becomes the 128-row one.
+void launch_gemm_f32_bf16x6(const GemmOp& op, SplitTile tile, int gw, hipStream_t s);
+// the same tilings with TWO fp16 planes and THREE products per block (gemm_x3.hip); op.w_scale: the power-of-two weight scale
+void launch_gemm_f32_f16x3(const GemmOp& op, SplitTile tile, int gw, hipStream_t s);
 // ---- pre-split operands (gemm_p3.hip): the three-product fp16 scheme with the split taken out of the K-loop -------------------
 // Plane image of X[rows, K]: two arrays (hi, lo) of plane_image_bytes(rows, K) bytes each, laid out [K / 16][rows padded to 128][16]
 // fp16 with the 16-byte halves of a row swapped where row bit 3 is set.  launch_split_planes writes the images of an fp32 matrix
@@ -119,38 +135,37 @@ void launch_gemm_f32_f16x3(const float* A, int lda, const float* W, int ldw, flo
 // writes fp32 C (bias, LayerNorm-fold finish, residual R1, ReLU, row statistics) and / or the plane images of C (rows_p rows).
 size_t plane_image_bytes(int rows, int K);
 void launch_split_planes(const float* X, int ld, int rows_valid, int rows, int K, float scale, void* hi, void* lo, hipStream_t s);
-void launch_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh, const void* Wl, int rows_w, float w_scale, float* C, int ldc,
-                    void* Ph, void* Pl, int rows_p, const float* bias, const float* R1, int ldr1, int M, int N, int K, bool relu,
-                    const float* ln_stats, int ln_tiles, const float* ln_colsum, float* stats_out, int gw, hipStream_t s,
-                    int tile_rows = 0,       // 0: 64-row tiles when 128-row tiles would fill less than a round; 64 / 128 force one
-                    int row_planes_from = 0,
+struct PlaneGemmOp {
+  const void* Ah = nullptr; const void* Al = nullptr; int rows_a = 0;      // A images, rows per K-step
+  const void* Wh = nullptr; const void* Wl = nullptr; int rows_w = 0;      // W images
+  float w_scale = 1.0f;
+  float* C = nullptr; int ldc = 0;
+  void* Ph = nullptr; void* Pl = nullptr; int rows_p = 0;                  // images of C
+  // row_planes_from = c > 0 (the encoder's QKV projection, C given): columns < c leave as fp32 rows of C, columns >= c as ROW-MAJOR
+  // fp16 planes Ph / Pl [M][rows_p] (rows_p = elements per plane row; column n at element n - c) — the K | V operand of
+  // attention_p3.hip.  c % 128 == 0; 128- and 64-row tiles only.
+  int row_planes_from = 0;
+  int M = 0, N = 0, K = 0;
+  const float* bias = nullptr;
+  const float* R1 = nullptr; int ldr1 = 0;
+  bool relu = false;
+  const float* ln_stats = nullptr; int ln_tiles = 0; const float* ln_colsum = nullptr;      // as GemmOp's
+  float* stats_out = nullptr;
+};
+// The column-group width of the tile order is 4; PFHIP_P3_GW overrides it on the 128-column kernels only (not on the 256 x 256 tile).
+void launch_gemm_p3(const PlaneGemmOp& op, hipStream_t s,
+                    int tile_rows = 0,       // 0: 64-row tiles when 128-row tiles would fill less than a round; 64 / 128 / 256 force one
                     int tile_cols = 0);      // 256: the 256 x 256 tile, for the forms gemm_p3_wide_serves() names (tile_rows 0)
 // whether the 256 x 256 tile has this form (LayerNorm fold, fp32 C or plane images of C but not both, no residual, no statistics out,
 // N % 256 == 0), and how many launches of this process it has served (tests, probes)
 bool gemm_p3_wide_serves(bool c, bool planes, bool r1, bool ln, bool stats_out, int row_planes_from, int N, int K);
 long gemm_p3_wide_launches();
-// row_planes_from = c > 0 (the encoder's QKV projection, C given): columns < c leave as fp32 rows of C, columns >= c as ROW-MAJOR fp16
-// planes Ph / Pl [M][rows_p] (rows_p = elements per plane row; column n at element n - c) — the K | V operand of attention_p3.hip.
-// c % 128 == 0; 128- and 64-row tiles only.
 // Row-major planes of an fp32 matrix (tests, tools): hi / lo [rows][ldp] fp16, cols % 8 == 0.
 void launch_split_rows(const float* X, int ld, int rows, int cols, void* hi, void* lo, int ldp, hipStream_t s);
-// attention_x3.hip's fused attention on K / V given as row-major planes (row stride ldkv elements, K at column 0, V at column v_col of
-// each plane; head h in columns 128 h ..): tiles staged by LDS-DMA, V read through gfx950's transposing LDS read.  d_k = 128.
-void launch_attention_p3(const float* Q, int ldq, const void* kv_hi, const void* kv_lo, int ldkv, int v_col, float* O, int ldo, const int* q_off,
-                         const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s,
-                         const float* fsmn_w = nullptr, float* mem = nullptr, int ldmem = 0, bool mem_accumulate = false,
-                         void* planes_hi = nullptr, void* planes_lo = nullptr, int plane_rows = 0);
-// The product-path form of the two options above: the BF16-split kernels with the tile / column-group choice of launch_gemm_f32.
-// gemm_x6_ln_ok(M): whether launch_gemm_f32 would put the N = 512 launches of M rows on these kernels (both sides of a
-// statistics hand-off must).
+// gemm_x6_ln_ok(M): whether launch_gemm (BySize) would put the N = 512 launches of M rows on the split-operand kernels (both sides
+// of a statistics hand-off must).
 bool gemm_x6_ln_ok(int M);
 bool gemm_f16_planes_form();      // the large GEMMs are on the fp16 two-plane form (not PFHIP_GEMM_X3=0 / PFHIP_GEMM_X6=0)
-void launch_gemm_f32_x6_ln(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                           int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, const float* ln_stats, int ln_tiles,
-                           const float* ln_colsum, float* stats_out, hipStream_t s, float w_scale = 1.0f);
-void launch_gemm_f32_kind(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
-                          int ldr1, const float* R2, int ldr2, int M, int N, int K, bool relu, bool guard, int kind,
-                          hipStream_t s, float w_scale = 1.0f);
 
 // y[row][0..D) = LN(x[row][0..D)) * g + b; columns D..Dout zeroed.  D % 4 == 0, Dout <= 2048.
 void launch_layernorm(const float* x, int ldx, float* y, int ldy, const float* g, const float* b,
@@ -165,52 +180,55 @@ void launch_fsmn(const float* v, int ldv, const float* w, const float* res, int 
 void launch_fsmn_shift(const float* v, int ldv, const float* w, const float* res, int ldres, float* out,
                        int ldo, const int* off, const int* len, int B, int max_len, int C, int shift, hipStream_t s);
 
-// Multi-head attention, d_k = 128: O[q, h*128:(h+1)*128] = softmax(scale * Q_h K_h^T) V_h over the
-// utterance's own keys.  q segments (q_off,q_len), kv segments (kv_off,kv_len), all device arrays.
-void launch_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv,
-                      float* O, int ldo, const int* q_off, const int* q_len, const int* kv_off,
-                      const int* kv_len, int B, int H, int max_q_len, float scale, hipStream_t s, int head_dim = kHeadDim);
-
-// Same kernel with the head dimension chosen at run time: 128, 80 (the small Paraformer: 320 / 4 heads) or 32 (CT-Transformer:
-// 256 / 8 heads).  d_k = 80 with more than 64 queries per utterance runs attention_h80.hip unless the launch context is exact.
-void launch_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                         const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
-                         int max_q_len, float scale, int head_dim, hipStream_t s);
-
-// With a per-query key limit: query row i (packed index) only sees keys [0, min(kv_len, q_kv_limit[i])) — the
-// prefix mask CTTransformerOnline::VadMask builds (ct-transformer-online.cpp:225-240).
+// Operands of packed multi-head attention: O[q, h*hd:(h+1)*hd] = softmax(scale * Q_h K_h^T) V_h over the utterance's own keys.
+// q segments (q_off, q_len), kv segments (kv_off, kv_len), all device arrays.  An absent field is nullptr / 0 / false.
+struct AttnOp {
+  const float* Q = nullptr; int ldq = 0;
+  const float* K = nullptr; int ldk = 0;
+  const float* V = nullptr; int ldv = 0;
+  float* O = nullptr; int ldo = 0;
+  const int* q_off = nullptr; const int* q_len = nullptr;
+  const int* kv_off = nullptr; const int* kv_len = nullptr;
+  int B = 0, H = 0, max_q_len = 0;
+  float scale = 1.0f;
+  int head_dim = kHeadDim;
+  // With a per-query key limit: query row i (packed index) only sees keys [0, min(kv_len, q_kv_limit[i])) — the
+  // prefix mask CTTransformerOnline::VadMask builds (ct-transformer-online.cpp:225-240).  The fp32-MFMA kernel only.
+  const int* q_kv_limit = nullptr;
+  // fsmn_w != nullptr (self-attention only: q segments == kv segments; the split-operand kernels, launch_attention_fsmn): the kernel
+  // also writes the encoder layer's FSMN memory mem = V + depthwise conv k = 11 over time (what launch_fsmn computes, bit for bit)
+  // for its rows and its head's channels; mem_accumulate: mem += instead.
+  const float* fsmn_w = nullptr; float* mem = nullptr; int ldmem = 0; bool mem_accumulate = false;
+  // the context as fp16 plane images (gemm_p3.hip's A operand) instead of fp32 rows; with planes_hi set, O is not written
+  // (attention_x3.hip, attention_p3.hip)
+  void* planes_hi = nullptr; void* planes_lo = nullptr; int plane_rows = 0;
+  // attention_p3.hip: K / V given as row-major planes instead of K / V above (row stride ldkv elements, K at column 0, V at column
+  // v_col of each plane; head h in columns 128 h ..)
+  const void* kv_hi = nullptr; const void* kv_lo = nullptr; int ldkv = 0, v_col = 0;
+};
+// Plain attention (the fused memory block and the plane-image fields of op are not honoured on any kernel), kernel by head width: 128, 80 (the small Paraformer: 320 / 4 heads) or
+// 32 (CT-Transformer: 256 / 8 heads).  d_k = 128 with more than 64 queries per utterance runs the split-operand kernels, d_k = 80
+// with more than 64 attention_h80.hip unless the launch context is exact; q_kv_limit keeps the fp32-MFMA kernel.
+void launch_attention(const AttnOp& op, hipStream_t s);
 // both attention products on the BF16 matrix cores (exact three-way split, attention_x6.hip); d_k = 128, no per-query limits
-// fsmn_w != nullptr (self-attention only: q segments == kv segments): the kernel also writes the encoder layer's FSMN memory
-// mem = V + depthwise conv k = 11 over time (what launch_fsmn computes, bit for bit) for its rows and its head's channels
-void launch_attention_x6(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                         const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
-                         float scale, hipStream_t s, const float* fsmn_w = nullptr, float* mem = nullptr, int ldmem = 0,
-                         bool mem_accumulate = false);
+void launch_attention_x6(const AttnOp& op, hipStream_t s);
 // the same with two fp16 planes and three products per block (attention_x3.hip)
-void launch_attention_x3(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                         const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
-                         float scale, hipStream_t s, const float* fsmn_w = nullptr, float* mem = nullptr, int ldmem = 0,
-                         bool mem_accumulate = false, void* planes_hi = nullptr, void* planes_lo = nullptr, int plane_rows = 0);
+void launch_attention_x3(const AttnOp& op, hipStream_t s);
+// attention_x3.hip's fused attention on K / V given as row-major planes (op.kv_hi ..): tiles staged by LDS-DMA, V read through
+// gfx950's transposing LDS read.  d_k = 128.
+void launch_attention_p3(const AttnOp& op, hipStream_t s);
 // d_k = 80 in the same arithmetic class (attention_h80.hip): two fp16 planes, three products per block on v_mfma_f32_32x32x16_f16,
 // fp32 accumulation, online softmax; V^T padded to 96 rows in LDS.  fp32 rows out; no fused memory block, no plane images.
-void launch_attention_h80(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
-                          float scale, hipStream_t s);
-// Encoder-layer pair: FSMN memory of V (into mem) + self-attention (into O).  One launch where the BF16 attention kernel runs
-// (d_k = 128, more than 64 queries per utterance), otherwise launch_fsmn + launch_attention.  C = V's channel count (H * 128).
-void launch_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                           const int* off, const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem,
-                           int ldmem, hipStream_t s, bool mem_accumulate = false, void* planes_hi = nullptr, void* planes_lo = nullptr,
-                           int plane_rows = 0, int head_dim = kHeadDim);
+void launch_attention_h80(const AttnOp& op, hipStream_t s);
+// Encoder-layer pair: FSMN memory of V (into mem) + self-attention (into O) over the q segments.  One launch where the BF16
+// attention kernel runs (d_k = 128, more than 64 queries per utterance), otherwise launch_fsmn + launch_attention.
+void launch_attention_fsmn(const AttnOp& op, hipStream_t s);
 // whether launch_attention_fsmn can write the context as fp16 plane images (gemm_p3.hip's A operand) instead of fp32 rows: the
-// fused launch on attention_x3.hip only.  With planes_hi set, O is not written.
+// fused launch on attention_x3.hip only.
 bool attention_planes_ok(int max_len, int head_dim = kHeadDim);
 // whether launch_attention_fsmn will be the single fused launch (then, and only then, mem_accumulate is honoured: the caller may
 // pass the residual stream as `mem` and drop the memory term from the output projection)
 bool attention_fsmn_is_fused(int max_len, int head_dim = kHeadDim);      // never at d_k = 80
-void launch_attention_masked(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                             const int* q_off, const int* q_len, const int* kv_off, const int* kv_len,
-                             const int* q_kv_limit, int B, int H, int max_q_len, float scale, int head_dim, hipStream_t s);
 
 // ---- timestamp head (SURVEY §8a row a6 producer; blstm.hip) -------------------------------------------------------
 // Bidirectional LSTM, hidden 512, over packed sequences (off/len in frames, B <= 32): gx [rows, 4096] = input projections

@@ -25,6 +25,16 @@ int with_device_segs(const std::vector<Seg>& host, hipStream_t s, Launch launch)
   (void)hipFree(d);
   return (int)e;
 }
+// The ABI's integer `kind` (pfhip_ops.h) as the launchers' enum — the one place the numbers appear; false for 6 and outside 0..10
+constexpr int kKindBySize = 0;
+bool kernel_of_kind(int kind, pfhip::GemmKernel* kernel) {
+  using G = pfhip::GemmKernel;
+  static const G table[11] = {G::BySize,   G::Tiled128, G::Streaming, G::Tiled64, G::Bf16_256, G::Bf16_128,
+                              G::BySize /* 6: none */, G::Bf16_64,  G::F16_256,   G::F16_128, G::F16_64};
+  if (kind < 0 || kind > 10 || kind == 6) return false;
+  *kernel = table[kind];
+  return true;
+}
 }  // namespace
 
 extern "C" {
@@ -32,16 +42,12 @@ extern "C" {
 int pfhip_op_gemm_f32(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias,
                       const float* R1, int ldr1, const float* R2, int ldr2, int M, int N, int K, int relu,
                       int guard, void* stream) {
-  if (K % pfhip::kTileK) return (int)hipErrorInvalidValue;
-  pfhip::launch_gemm_f32(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu != 0, guard != 0, S(stream));
-  return done();
+  return pfhip_op_gemm_f32_scaled(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, guard, kKindBySize, 1.0f, stream);
 }
 int pfhip_op_gemm_f32_kind(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias,
                            const float* R1, int ldr1, const float* R2, int ldr2, int M, int N, int K, int relu,
                            int guard, int kind, void* stream) {
-  if (K % pfhip::kTileK || kind < 0 || kind > 10 || kind == 6) return (int)hipErrorInvalidValue;
-  pfhip::launch_gemm_f32_kind(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu != 0, guard != 0, kind, S(stream));
-  return done();
+  return pfhip_op_gemm_f32_scaled(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu, guard, kind, 1.0f, stream);
 }
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
                            float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
@@ -98,8 +104,11 @@ int pfhip_op_fused_att_out(const float* Q, int ldq, const float* K, int ldk, con
 int pfhip_op_gemm_f32_scaled(const float* A, int lda, const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1,
                              int ldr1, const float* R2, int ldr2, int M, int N, int K, int relu, int guard, int kind, float w_scale,
                              void* stream) {
-  if (K % pfhip::kTileK || kind < 0 || kind > 10 || kind == 6 || !(w_scale > 0.f)) return (int)hipErrorInvalidValue;
-  pfhip::launch_gemm_f32_kind(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu != 0, guard != 0, kind, S(stream), w_scale);
+  pfhip::GemmKernel kernel;
+  if (K % pfhip::kTileK || !kernel_of_kind(kind, &kernel) || !(w_scale > 0.f)) return (int)hipErrorInvalidValue;
+  pfhip::launch_gemm({.A = A, .lda = lda, .W = W, .ldw = ldw, .C = C, .ldc = ldc, .M = M, .N = N, .K = K, .bias = bias, .R1 = R1, .ldr1 = ldr1,
+                      .R2 = R2, .ldr2 = ldr2, .relu = relu != 0, .w_scale = w_scale},
+                     kernel, guard != 0, S(stream));
   return (int)hipGetLastError();
 }
 float pfhip_op_best_w_scale(float max_abs) { return pfhip::best_w_scale(max_abs); }
@@ -116,8 +125,10 @@ int pfhip_op_gemm_f32_ln(const float* A, int lda, const float* W, int ldw, float
       (R2 && ldr2 < N) || (lda | ldw | ldc | ldr1 | ldr2) % 4 || !(w_scale > 0.f) || (ln_stats && (!ln_colsum || ln_tiles <= 0 || N % 4)) || (!ln_stats && ln_colsum) ||
       (stats_out && N % 128))
     return (int)hipErrorInvalidValue;
-  pfhip::launch_gemm_f32_x6_ln(A, lda, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, M, N, K, relu != 0, ln_stats, ln_tiles, ln_colsum, stats_out,
-                               S(stream), w_scale);
+  pfhip::launch_gemm({.A = A, .lda = lda, .W = W, .ldw = ldw, .C = C, .ldc = ldc, .M = M, .N = N, .K = K, .bias = bias, .R1 = R1, .ldr1 = ldr1,
+                      .R2 = R2, .ldr2 = ldr2, .relu = relu != 0, .w_scale = w_scale, .ln_stats = ln_stats, .ln_tiles = ln_tiles,
+                      .ln_colsum = ln_colsum, .stats_out = stats_out},
+                     pfhip::GemmKernel::SplitBySize, false, S(stream));
   return (int)hipGetLastError();
 }
 
@@ -138,8 +149,10 @@ int pfhip_op_gemm_p3(const void* Ah, const void* Al, int rows_a, const void* Wh,
       (ln_stats && (!ln_colsum || ln_tiles <= 0)) || (stats_out && !C) /* the statistics come out of the fp32 epilogue */ ||
       (tile_rows != 0 && tile_rows != 64 && tile_rows != 128 && tile_rows != 256))
     return (int)hipErrorInvalidValue;
-  pfhip::launch_gemm_p3(Ah, Al, rows_a, Wh, Wl, rows_w, w_scale, C, ldc, Ph, Pl, rows_p, bias, R1, ldr1, M, N, K, relu != 0, ln_stats, ln_tiles,
-                        ln_colsum, stats_out, 4, S(stream), tile_rows);
+  pfhip::launch_gemm_p3({.Ah = Ah, .Al = Al, .rows_a = rows_a, .Wh = Wh, .Wl = Wl, .rows_w = rows_w, .w_scale = w_scale, .C = C, .ldc = ldc,
+                         .Ph = Ph, .Pl = Pl, .rows_p = rows_p, .M = M, .N = N, .K = K, .bias = bias, .R1 = R1, .ldr1 = ldr1,
+                         .relu = relu != 0, .ln_stats = ln_stats, .ln_tiles = ln_tiles, .ln_colsum = ln_colsum, .stats_out = stats_out},
+                        S(stream), tile_rows);
   return (int)hipGetLastError();
 }
 // The same with a tile-width selector: tile_cols 0 = as pfhip_op_gemm_p3, 256 = the 256 x 256 tile (tile_rows must be 0), refused for the
@@ -156,8 +169,10 @@ int pfhip_op_gemm_p3_cols(const void* Ah, const void* Al, int rows_a, const void
       (ln_stats && (!ln_colsum || ln_tiles <= 0)) ||
       !pfhip::gemm_p3_wide_serves(C != nullptr, Ph != nullptr, R1 != nullptr, ln_stats != nullptr, stats_out != nullptr, 0, N, K))
     return (int)hipErrorInvalidValue;
-  pfhip::launch_gemm_p3(Ah, Al, rows_a, Wh, Wl, rows_w, w_scale, C, ldc, Ph, Pl, rows_p, bias, nullptr, 0, M, N, K, relu != 0, ln_stats, ln_tiles,
-                        ln_colsum, nullptr, 4, S(stream), 0, 0, 256);
+  pfhip::launch_gemm_p3({.Ah = Ah, .Al = Al, .rows_a = rows_a, .Wh = Wh, .Wl = Wl, .rows_w = rows_w, .w_scale = w_scale, .C = C, .ldc = ldc,
+                         .Ph = Ph, .Pl = Pl, .rows_p = rows_p, .M = M, .N = N, .K = K, .bias = bias, .relu = relu != 0,
+                         .ln_stats = ln_stats, .ln_tiles = ln_tiles, .ln_colsum = ln_colsum},
+                        S(stream), 0, 256);
   return (int)hipGetLastError();
 }
 long pfhip_op_gemm_p3_wide_launches(void) { return pfhip::gemm_p3_wide_launches(); }
@@ -177,23 +192,25 @@ int pfhip_op_fsmn(const float* v, int ldv, const float* w, const float* res, int
 int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                        const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                        int max_q_len, float scale, void* stream) {
-  pfhip::launch_attention(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, S(stream));
-  return done();
+  return pfhip_op_attention_hd(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, pfhip::kHeadDim, stream);
 }
 int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                           const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                           int max_q_len, float scale, int head_dim, void* stream) {
   if (head_dim != 32 && head_dim != 80 && head_dim != 128) return (int)hipErrorInvalidValue;      // before anything is launched
-  pfhip::launch_attention_hd(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, head_dim,
-                             S(stream));
+  pfhip::launch_attention({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .O = O, .ldo = ldo, .q_off = q_off, .q_len = q_len, .kv_off = kv_off, .kv_len = kv_len, .B = B, .H = H,
+                           .max_q_len = max_q_len, .scale = scale, .head_dim = head_dim},
+                          S(stream));
   return done();
 }
 int pfhip_op_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, const int* off,
                             const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem, int ldmem,
                             int mem_accumulate, int head_dim, void* stream) {
   if ((head_dim != 80 && head_dim != 128) || !fsmn_w || !mem || !O || H <= 0 || ldmem < H * head_dim) return (int)hipErrorInvalidValue;
-  pfhip::launch_attention_fsmn(Q, ldq, K, ldk, V, ldv, O, ldo, off, len, B, H, max_len, scale, fsmn_w, mem, ldmem, S(stream), mem_accumulate != 0,
-                               nullptr, nullptr, 0, head_dim);
+  pfhip::launch_attention_fsmn({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .O = O, .ldo = ldo, .q_off = off, .q_len = len, .kv_off = off, .kv_len = len, .B = B, .H = H, .max_q_len = max_len,
+                                .scale = scale, .head_dim = head_dim, .fsmn_w = fsmn_w, .mem = mem, .ldmem = ldmem,
+                                .mem_accumulate = mem_accumulate != 0},
+                               S(stream));
   return done();
 }
 int pfhip_op_attention_fsmn_is_fused(int max_len, int head_dim) { return pfhip::attention_fsmn_is_fused(max_len, head_dim) ? 1 : 0; }
@@ -202,8 +219,10 @@ int pfhip_op_attention_planes(const float* Q, int ldq, const float* K, int ldk, 
                               int max_q_len, int total_q_rows, float scale, void* stream) {
   // the image must hold every query row the launch writes (rows are global: q_off[b] + t), in whole 128-row tiles
   if (!planes_hi || !planes_lo || plane_rows % 128 || total_q_rows > plane_rows || B <= 0 || H <= 0) return (int)hipErrorInvalidValue;
-  pfhip::launch_attention_x3(Q, ldq, K, ldk, V, ldv, nullptr, 0, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, S(stream), nullptr,
-                             nullptr, 0, false, planes_hi, planes_lo, plane_rows);
+  pfhip::launch_attention_x3({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .q_off = q_off, .q_len = q_len, .kv_off = kv_off,
+                              .kv_len = kv_len, .B = B, .H = H, .max_q_len = max_q_len, .scale = scale, .planes_hi = planes_hi,
+                              .planes_lo = planes_lo, .plane_rows = plane_rows},
+                             S(stream));
   return done();
 }
 int pfhip_op_split_rows(const float* X, int ld, int rows, int cols, void* hi, void* lo, int ldp, void* stream) {
@@ -219,8 +238,10 @@ int pfhip_op_gemm_p3_qkv(const void* Ah, const void* Al, int rows_a, const void*
       !Wl || !C || !kv_hi || !kv_lo || q_cols <= 0 || q_cols % 128 || q_cols >= N || ldc < q_cols || ldkv < N - q_cols || ldkv % 8 ||
       !(w_scale > 0.f) || (ln_stats && (!ln_colsum || ln_tiles <= 0)) || (tile_rows != 0 && tile_rows != 64 && tile_rows != 128))
     return (int)hipErrorInvalidValue;
-  pfhip::launch_gemm_p3(Ah, Al, rows_a, Wh, Wl, rows_w, w_scale, C, ldc, kv_hi, kv_lo, ldkv, bias, nullptr, 0, M, N, K, false, ln_stats, ln_tiles,
-                        ln_colsum, nullptr, 4, S(stream), tile_rows, q_cols);
+  pfhip::launch_gemm_p3({.Ah = Ah, .Al = Al, .rows_a = rows_a, .Wh = Wh, .Wl = Wl, .rows_w = rows_w, .w_scale = w_scale, .C = C, .ldc = ldc,
+                         .Ph = kv_hi, .Pl = kv_lo, .rows_p = ldkv, .row_planes_from = q_cols, .M = M, .N = N, .K = K,
+                         .bias = bias, .ln_stats = ln_stats, .ln_tiles = ln_tiles, .ln_colsum = ln_colsum},
+                        S(stream), tile_rows);
   return (int)hipGetLastError();
 }
 int pfhip_op_attention_kvplanes(const float* Q, int ldq, const void* kv_hi, const void* kv_lo, int ldkv, int v_col, int total_kv_rows, float* O,
@@ -232,8 +253,11 @@ int pfhip_op_attention_kvplanes(const float* Q, int ldq, const void* kv_hi, cons
       (!O && !planes_hi) || (planes_hi && (!planes_lo || plane_rows % 128 || total_q_rows > plane_rows)) || (O && ldo < H * 128) ||
       (fsmn_w && (!mem || ldmem < H * 128)))
     return (int)hipErrorInvalidValue;
-  pfhip::launch_attention_p3(Q, ldq, kv_hi, kv_lo, ldkv, v_col, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, scale, S(stream), fsmn_w,
-                             mem, ldmem, mem_accumulate != 0, planes_hi, planes_lo, plane_rows);
+  pfhip::launch_attention_p3({.Q = Q, .ldq = ldq, .O = O, .ldo = ldo, .q_off = q_off, .q_len = q_len, .kv_off = kv_off, .kv_len = kv_len, .B = B,
+                              .H = H, .max_q_len = max_q_len, .scale = scale, .fsmn_w = fsmn_w, .mem = mem, .ldmem = ldmem,
+                              .mem_accumulate = mem_accumulate != 0, .planes_hi = planes_hi, .planes_lo = planes_lo,
+                              .plane_rows = plane_rows, .kv_hi = kv_hi, .kv_lo = kv_lo, .ldkv = ldkv, .v_col = v_col},
+                             S(stream));
   return done();
 }
 int pfhip_op_cif(const float* hidden, int ldh, const float* alphas, const int* row_off, const int* len, int B, int D,

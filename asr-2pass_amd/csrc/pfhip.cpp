@@ -778,11 +778,10 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
   const bool fuse_ln = w.enc_folded && pfhip::gemm_x6_ln_ok(M) && !pfhip::launch_ctx().exact;
   const bool mem_in_x = pfhip::attention_fsmn_is_fused(m->maxT, hd);
   if (fuse_ln) HIP_TRY(m->lnstats.ensure((size_t)Mp * 4 * 2 * 4));
-  auto gemm_ln = [&](const float* A, const Linear& W, int N, float* Cd, int ldc, const float* R1, const float* R2,
-                     bool relu, const float* ln_colsum, bool stats_out, int K) {
+  auto gemm_ln = [&](const Linear& W, const pfhip::GemmOp& op) {      // split_gemm (internal.h) with its accounting
+    const int N = op.N, K = op.K;
     Scope sc(m, s, K_GEMM, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    pfhip::launch_gemm_f32_x6_ln(A, K, W.w, K, Cd, ldc, W.b, R1, d, R2, d, M, N, K, relu, ln_colsum ? m->lnstats.f() : nullptr, 4,
-                                 ln_colsum, stats_out ? m->lnstats.f() : nullptr, s, W.scale);
+    split_gemm(s, W, op, M, d, m->lnstats.f());
   };
   // Large batches, second step: the four big GEMMs of a layer take BOTH operands as fp16 plane images staged by LDS-DMA
   // (gemm_p3.hip) — weights split once at load, activations written as planes by the kernel that produces them (the attention's
@@ -817,13 +816,19 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
     HIP_TRY(m->kvP.ensure(2 * pk));
     kvP = img_of(m->kvP, pk);
   }
-  // C (fp32, may be null) and / or plane images of C; LayerNorm folded in when ln_colsum is given (statistics in lnstats)
-  auto gemm_pl = [&](const Img& A, const Planes& W, int N, int K, float* Cd, int ldc, const Img* P, const float* bias, const float* R1, bool relu,
-                     const float* ln_colsum, bool stats_out) {
+  // op names C (fp32) and / or the plane images of C, N, K, bias, R1, relu, ln_colsum (the fold: statistics read from lnstats) and
+  // stats_out; the operand images and the row counts are filled here
+  auto gemm_pl = [&](const Img& A, const Planes& W, pfhip::PlaneGemmOp op) {
+    const int N = op.N, K = op.K;
     Scope sc(m, s, K_GEMM, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    pfhip::launch_gemm_p3(A.hi, A.lo, Mp, W.hi, W.lo, N, W.scale, Cd, ldc, P ? P->hi : nullptr, P ? P->lo : nullptr, Mp, bias, R1, d, M, N, K, relu,
-                          ln_colsum ? m->lnstats.f() : nullptr, 4, ln_colsum, stats_out ? m->lnstats.f() : nullptr, 4, s);
+    op.Ah = A.hi; op.Al = A.lo; op.rows_a = op.rows_p = Mp; op.Wh = W.hi; op.Wl = W.lo; op.rows_w = N; op.w_scale = W.scale;
+    op.M = M; op.ldr1 = d; op.ln_stats = op.ln_colsum ? m->lnstats.f() : nullptr; op.ln_tiles = 4;
+    pfhip::launch_gemm_p3(op, s);
   };
+  // the layers' self-attention over one qkv buffer; a layer adds its memory block and, on the plane path, the images of its context
+  pfhip::AttnOp self_att = qkv_attention(m->qkv.f(), d, m->ctx.f());
+  self_att.q_off = self_att.kv_off = m->m_row_off; self_att.q_len = self_att.kv_len = m->m_len;
+  self_att.B = B; self_att.H = c.n_head; self_att.max_q_len = m->maxT; self_att.scale = att_scale; self_att.head_dim = hd;
   for (int i = 0; i < c.enc_layers; ++i) {
     const EncLayer& L = w.enc[(size_t)i];
     const bool first = i == 0;
@@ -833,14 +838,15 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
       // LayerNorm(x) Wqkv'^T on the plane images of x: Q as fp32 rows of qkv, K | V as row-major planes
       Scope sc(m, s, K_GEMM, 2.0 * M * (double)(3 * d) * d, 4.0 * ((double)M * d + 3.0 * d * d + (double)M * 3 * d));
       const Planes& W = L.qkv_f.img;
-      pfhip::launch_gemm_p3(xP.hi, xP.lo, Mp, W.hi, W.lo, 3 * d, W.scale, m->qkv.f(), 3 * d, kvP.hi, kvP.lo, 2 * d,
-                            L.qkv_f.folded.b, nullptr, 0, M, 3 * d, d, false, m->lnstats.f(), 4, L.qkv_f.colsum,
-                            nullptr, 4, s, 0, d);
+      pfhip::launch_gemm_p3({.Ah = xP.hi, .Al = xP.lo, .rows_a = Mp, .Wh = W.hi, .Wl = W.lo, .rows_w = 3 * d, .w_scale = W.scale, .C = m->qkv.f(),
+                             .ldc = 3 * d, .Ph = kvP.hi, .Pl = kvP.lo, .rows_p = 2 * d, .row_planes_from = d, .M = M, .N = 3 * d, .K = d,
+                             .bias = L.qkv_f.folded.b, .ln_stats = m->lnstats.f(), .ln_tiles = 4, .ln_colsum = L.qkv_f.colsum},
+                            s);
     } else if (planes && !first) {
       // LayerNorm(x) Wqkv'^T on the plane images of x that the previous layer's FFN2 left
-      gemm_pl(xP, L.qkv_f.img, 3 * d, d, m->qkv.f(), 3 * d, nullptr, L.qkv_f.folded.b, nullptr, false, L.qkv_f.colsum, false);
+      gemm_pl(xP, L.qkv_f.img, {.C = m->qkv.f(), .ldc = 3 * d, .N = 3 * d, .K = d, .bias = L.qkv_f.folded.b, .ln_colsum = L.qkv_f.colsum});
     } else if (fuse_ln && !first) {
-      gemm_ln(x, L.qkv_f.folded, 3 * d, m->qkv.f(), 3 * d, nullptr, nullptr, false, L.qkv_f.colsum, false, d);
+      gemm_ln(L.qkv_f.folded, {.A = x, .C = m->qkv.f(), .ldc = 3 * d, .N = 3 * d, .K = d, .ln_colsum = L.qkv_f.colsum});
     } else {
       lnorm(m, s, xin, ldin, m->y.f(), Kp, L.norm1, M, Din, Kp);
       gemm(m, s, m->y.f(), Kp, L.qkv, 3 * d, Kp, Din, m->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, M, false);
@@ -850,27 +856,33 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
       Scope sc(m, s, K_ATTN, 4.0 * attn_pairs * d + 2.0 * 11 * M * d, 24.0 * M * d);
       // fused launch: the FSMN memory goes straight into the residual stream (x += memory; x = memory in the first layer, which
       // has no residual), so the bandwidth-bound output projection reads ONE residual
-      if (kv_planes && !first)
-        pfhip::launch_attention_p3(m->qkv.f(), 3 * d, kvP.hi, kvP.lo, 2 * d, d, nullptr, 0, m->m_row_off, m->m_len, m->m_row_off, m->m_len, B,
-                                   c.n_head, m->maxT, att_scale, s, L.fsmn_w, x, d, true, ctxP.hi, ctxP.lo, Mp);
-      else
-      pfhip::launch_attention_fsmn(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, m->m_row_off,
-                                   m->m_len, B, c.n_head, m->maxT, att_scale, L.fsmn_w, mem_in_x ? x : m->mem.f(), d, s,
-                                   mem_in_x && !first, planes ? ctxP.hi : nullptr, planes ? ctxP.lo : nullptr, Mp, hd);
+      pfhip::AttnOp att = self_att;
+      att.fsmn_w = L.fsmn_w; att.mem = mem_in_x ? x : m->mem.f(); att.ldmem = d; att.mem_accumulate = mem_in_x && !first;
+      if (planes) { att.planes_hi = ctxP.hi; att.planes_lo = ctxP.lo; att.plane_rows = Mp; }
+      if (kv_planes && !first) {      // K | V from the planes the QKV projection wrote, no fp32 context (kv_planes implies planes, mem_in_x)
+        att.O = nullptr; att.ldo = 0;
+        att.kv_hi = kvP.hi; att.kv_lo = kvP.lo; att.ldkv = 2 * d; att.v_col = d;
+        pfhip::launch_attention_p3(att, s);
+      } else {
+        pfhip::launch_attention_fsmn(att, s);
+      }
     }
     const bool more = i + 1 < c.enc_layers;
     if (planes) {
       // x = ctx Wo^T + b + (x + memory): fp32 for the residual stream, plane images for FFN1, row statistics for its LayerNorm
-      gemm_pl(ctxP, L.out_img, d, d, x, d, &xP, L.out.b, x, false, nullptr, true);
-      gemm_pl(xP, L.ffn1_f.img, c.ffn, d, nullptr, 0, &hP, L.ffn1_f.folded.b, nullptr, true, L.ffn1_f.colsum, false);
-      gemm_pl(hP, L.ffn2_img, d, c.ffn, x, d, more ? &xP : nullptr, L.ffn2.b, x, false, nullptr, more);
+      gemm_pl(ctxP, L.out_img, {.C = x, .ldc = d, .Ph = xP.hi, .Pl = xP.lo, .N = d, .K = d, .bias = L.out.b, .R1 = x, .stats_out = m->lnstats.f()});
+      gemm_pl(xP, L.ffn1_f.img, {.Ph = hP.hi, .Pl = hP.lo, .N = c.ffn, .K = d, .bias = L.ffn1_f.folded.b, .relu = true, .ln_colsum = L.ffn1_f.colsum});
+      // (the last layer's output is read by the final LayerNorm only: neither images nor statistics)
+      gemm_pl(hP, L.ffn2_img, {.C = x, .ldc = d, .Ph = more ? xP.hi : nullptr, .Pl = more ? xP.lo : nullptr, .N = d, .K = c.ffn, .bias = L.ffn2.b,
+                               .R1 = x, .stats_out = more ? m->lnstats.f() : nullptr});
       continue;
     }
     // x = (first ? 0 : x) + ctx*Wo + b + fsmn_memory
     if (fuse_ln) {
-      gemm_ln(m->ctx.f(), L.out, d, x, d, mem_in_x ? x : m->mem.f(), mem_in_x || first ? nullptr : x, false, nullptr, true, d);
-      gemm_ln(x, L.ffn1_f.folded, c.ffn, m->hbuf.f(), c.ffn, nullptr, nullptr, true, L.ffn1_f.colsum, false, d);
-      gemm_ln(m->hbuf.f(), L.ffn2, d, x, d, x, nullptr, false, nullptr, more, c.ffn);
+      gemm_ln(L.out, {.A = m->ctx.f(), .C = x, .ldc = d, .N = d, .K = d, .R1 = mem_in_x ? x : m->mem.f(),
+                      .R2 = mem_in_x || first ? nullptr : x, .stats_out = m->lnstats.f()});
+      gemm_ln(L.ffn1_f.folded, {.A = x, .C = m->hbuf.f(), .ldc = c.ffn, .N = c.ffn, .K = d, .relu = true, .ln_colsum = L.ffn1_f.colsum});
+      gemm_ln(L.ffn2, {.A = m->hbuf.f(), .C = x, .ldc = d, .N = d, .K = c.ffn, .R1 = x, .stats_out = more ? m->lnstats.f() : nullptr});
       continue;
     }
     gemm(m, s, m->ctx.f(), d, L.out, d, d, d, x, d, mem_in_x ? x : m->mem.f(), d, mem_in_x || first ? nullptr : x, d, M, false);
@@ -1003,10 +1015,12 @@ pfhip_status forward_decoder(pfhip_model* m, hipStream_t s, const ForwardPaths& 
     HIP_TRY(m->lnstats.ensure((size_t)std::max(Mp, MLp) * 4 * 2 * 4));
     HIP_TRY(m->lnstats2.ensure((size_t)MLp * ftiles * 2 * 4));
   }
-  auto x6ln = [&](const float* A, int K, const Linear& W, int N, float* Cd, const float* R1, bool relu,
-                  const float* st_in, int tiles_in, const float* colsum, float* st_out) {
+  // op names A, C, N, K, R1, relu, the fold (ln_stats, ln_tiles, ln_colsum) and stats_out; the rest is filled here
+  auto x6ln = [&](const Linear& W, pfhip::GemmOp op) {
+    const int N = op.N, K = op.K;
     Scope sc(m, s, K_GEMM, 2.0 * ML * (double)N * K, 4.0 * ((double)ML * K + (double)N * K + (double)ML * N));
-    pfhip::launch_gemm_f32_x6_ln(A, K, W.w, K, Cd, N, W.b, R1, d, nullptr, 0, ML, N, K, relu, st_in, tiles_in, colsum, st_out, s, W.scale);
+    op.lda = op.ldw = K; op.W = W.w; op.bias = W.b; op.w_scale = W.scale; op.ldc = N; op.M = ML; op.ldr1 = d;
+    pfhip::launch_gemm(op, pfhip::GemmKernel::SplitBySize, false, s);
   };
   bool xd_has_stats = false;          // lnstats holds the row statistics of the current xd
   // From 3500 token rows on (and only where the encoder ran on plane images: same arithmetic form) the decoder's large
@@ -1032,36 +1046,48 @@ pfhip_status forward_decoder(pfhip_model* m, hipStream_t s, const ForwardPaths& 
     Scope sc(m, s, K_OTHER, 0, 8.0 * M * d);
     pfhip::launch_split_planes(m->enc.f(), d, M, Mp, d, 1.0f, encP.hi, encP.lo, s);
   }
-  // one gemm_p3 launch over `rows` rows: A image with rows_a rows per K-step, result as fp32 (Cd) and / or images (P, MLp rows)
-  auto dgemm_pl = [&](const Img& A, int rows_a, const Planes& W, int rows, int N, int K, float* Cd, int ldc, const Img* P, const float* bias,
-                      const float* R1, bool relu, const float* st_in, int tiles_in, const float* colsum, float* st_out) {
-    Scope sc(m, s, K_GEMM, 2.0 * rows * (double)N * K, 4.0 * ((double)rows * K + (double)N * K + (double)rows * N));
-    pfhip::launch_gemm_p3(A.hi, A.lo, rows_a, W.hi, W.lo, N, W.scale, Cd, ldc, P ? P->hi : nullptr, P ? P->lo : nullptr, MLp, bias, R1, d, rows, N, K,
-                          relu, st_in, tiles_in, colsum, st_out, 4, s);
+  // one gemm_p3 launch over the token rows: op names the result as fp32 (C) and / or images (Ph, Pl), N, K, bias, R1, relu, the fold
+  // and stats_out; the operand images (MLp rows per K-step) and the row counts are filled here
+  auto dgemm_pl = [&](const Img& A, const Planes& W, pfhip::PlaneGemmOp op) {
+    const int N = op.N, K = op.K;
+    Scope sc(m, s, K_GEMM, 2.0 * ML * (double)N * K, 4.0 * ((double)ML * K + (double)N * K + (double)ML * N));
+    op.Ah = A.hi; op.Al = A.lo; op.rows_a = op.rows_p = MLp; op.Wh = W.hi; op.Wl = W.lo; op.rows_w = N; op.w_scale = W.scale;
+    op.M = ML; op.ldr1 = d;
+    pfhip::launch_gemm_p3(op, s);
   };
   auto dec_ffn = [&](const DecFfn& F, const float* xin, float* out) {
     if (dec_planes && xd_has_planes && xd_has_stats) {
       // FFN1' on the images of the residual stream: hidden activation as fp32 (row statistics ride on that pass) + images
-      dgemm_pl(xdP, MLp, F.ffn1_f.img, ML, c.dec_ffn, d, m->hd.f(), c.dec_ffn, &hdP, F.ffn1_f.folded.b, nullptr, true,
-               m->lnstats.f(), 4, F.ffn1_f.colsum, m->lnstats2.f());
-      dgemm_pl(hdP, MLp, F.ffn2_f.img, ML, d, c.dec_ffn, out, d, nullptr, F.ffn2_f.folded.b, nullptr, false, m->lnstats2.f(), ftiles,
-               F.ffn2_f.colsum, nullptr);
+      dgemm_pl(xdP, F.ffn1_f.img, {.C = m->hd.f(), .ldc = c.dec_ffn, .Ph = hdP.hi, .Pl = hdP.lo, .N = c.dec_ffn, .K = d, .bias = F.ffn1_f.folded.b,
+                                   .relu = true, .ln_stats = m->lnstats.f(), .ln_tiles = 4, .ln_colsum = F.ffn1_f.colsum,
+                                   .stats_out = m->lnstats2.f()});
+      dgemm_pl(hdP, F.ffn2_f.img, {.C = out, .ldc = d, .N = d, .K = c.dec_ffn, .bias = F.ffn2_f.folded.b, .ln_stats = m->lnstats2.f(),
+                                   .ln_tiles = ftiles, .ln_colsum = F.ffn2_f.colsum});
       return;
     }
     if (fuse_dec) {
       if (xd_has_stats) {
-        x6ln(xin, d, F.ffn1_f.folded, c.dec_ffn, m->hd.f(), nullptr, true, m->lnstats.f(), 4, F.ffn1_f.colsum, m->lnstats2.f());
+        x6ln(F.ffn1_f.folded, {.A = xin, .C = m->hd.f(), .N = c.dec_ffn, .K = d, .relu = true, .ln_stats = m->lnstats.f(), .ln_tiles = 4,
+                               .ln_colsum = F.ffn1_f.colsum, .stats_out = m->lnstats2.f()});
       } else {
         lnorm(m, s, xin, d, m->yd.f(), d, F.norm1, ML, d, d);
-        x6ln(m->yd.f(), d, F.ffn1, c.dec_ffn, m->hd.f(), nullptr, true, nullptr, 0, nullptr, m->lnstats2.f());
+        x6ln(F.ffn1, {.A = m->yd.f(), .C = m->hd.f(), .N = c.dec_ffn, .K = d, .relu = true, .stats_out = m->lnstats2.f()});
       }
-      x6ln(m->hd.f(), c.dec_ffn, F.ffn2_f.folded, d, out, nullptr, false, m->lnstats2.f(), ftiles, F.ffn2_f.colsum, nullptr);
+      x6ln(F.ffn2_f.folded, {.A = m->hd.f(), .C = out, .N = d, .K = c.dec_ffn, .ln_stats = m->lnstats2.f(), .ln_tiles = ftiles,
+                             .ln_colsum = F.ffn2_f.colsum});
       return;
     }
     lnorm(m, s, xin, d, m->yd.f(), d, F.norm1, ML, d, d);
     gemm(m, s, m->yd.f(), d, F.ffn1, c.dec_ffn, d, d, m->hd.f(), c.dec_ffn, nullptr, 0, nullptr, 0, ML, true);
     lnorm(m, s, m->hd.f(), c.dec_ffn, m->hd2.f(), c.dec_ffn, F.ffn_norm, ML, c.dec_ffn, c.dec_ffn);
     gemm(m, s, m->hd2.f(), c.dec_ffn, F.ffn2, d, c.dec_ffn, c.dec_ffn, out, d, nullptr, 0, nullptr, 0, ML, false);
+  };
+  // the tokens' queries in qd against K | V [., 2d] of the given segments, context into ctxd
+  auto cross_att = [&](const float* kv, const int* kv_off, const int* kv_len) {
+    pfhip::AttnOp op = kv_attention(m->qd.f(), d, kv, 2 * d, m->ctxd.f());
+    op.q_off = m->m_tok_off; op.q_len = m->m_tok_len; op.kv_off = kv_off; op.kv_len = kv_len;
+    op.B = B; op.H = c.dec_n_head; op.max_q_len = m->maxL; op.scale = att_scale_d;
+    return op;
   };
   for (int i = 0; i < c.dec_layers; ++i) {
     const DecLayer& L = w.dec[(size_t)i];
@@ -1080,32 +1106,35 @@ pfhip_status forward_decoder(pfhip_model* m, hipStream_t s, const ForwardPaths& 
     } else if (dec_planes) {
       Scope sc(m, s, K_GEMM, 2.0 * M * 2.0 * d * d, 4.0 * ((double)M * d + 2.0 * d * d + 2.0 * M * d));
       const Planes& W = L.kv_img;
-      pfhip::launch_gemm_p3(encP.hi, encP.lo, Mp, W.hi, W.lo, 2 * d, W.scale, kvbuf, 2 * d, nullptr, nullptr, Mp, L.kv.b, nullptr, 0, M,
-                            2 * d, d, false, nullptr, 0, nullptr, nullptr, 4, s);
+      pfhip::launch_gemm_p3({.Ah = encP.hi, .Al = encP.lo, .rows_a = Mp, .Wh = W.hi, .Wl = W.lo, .rows_w = 2 * d, .w_scale = W.scale, .C = kvbuf,
+                             .ldc = 2 * d, .rows_p = Mp, .M = M, .N = 2 * d, .K = d, .bias = L.kv.b},
+                            s);
     } else {
       gemm(m, s, m->enc.f(), d, L.kv, 2 * d, d, d, kvbuf, 2 * d, nullptr, 0, nullptr, 0, M, false);
     }
     {
       Scope sc(m, s, K_ATTN, 4.0 * cross_pairs * d, 8.0 * ML * d + 8.0 * M * d);
-      if (dec_planes && plain_layer)     // the context leaves as plane images for the output projection; no fp32 context is written
-        pfhip::launch_attention_x3(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len, m->m_row_off, m->m_len,
-                                   B, c.dec_n_head, m->maxL, att_scale_d, s, nullptr, nullptr, 0, false, ctxdP.hi, ctxdP.lo, MLp);
-      else
-        pfhip::launch_attention(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len,
-                                m->m_row_off, m->m_len, B, c.dec_n_head, m->maxL, att_scale_d, s, hdd);
+      pfhip::AttnOp att = cross_att(kvbuf, m->m_row_off, m->m_len);
+      if (dec_planes && plain_layer) {     // the context leaves as plane images for the output projection; no fp32 context is written
+        att.planes_hi = ctxdP.hi; att.planes_lo = ctxdP.lo; att.plane_rows = MLp;
+        pfhip::launch_attention_x3(att, s);
+      } else {
+        att.head_dim = hdd;
+        pfhip::launch_attention(att, s);
+      }
     }
     xd_has_stats = false;
     xd_has_planes = false;
     if (dec_planes && plain_layer) {
       // xd = ctx Wo^T + b + xd: fp32 for the residual adds, images + row statistics for the next FFN1'
-      dgemm_pl(ctxdP, MLp, L.out_img, ML, d, d, xd, d, &xdP, L.out.b, xd, false, nullptr, 0, nullptr, m->lnstats.f());
+      dgemm_pl(ctxdP, L.out_img, {.C = xd, .ldc = d, .Ph = xdP.hi, .Pl = xdP.lo, .N = d, .K = d, .bias = L.out.b, .R1 = xd, .stats_out = m->lnstats.f()});
       xd_has_stats = true;
       xd_has_planes = true;
       continue;
     }
     if (plain_layer) {
       if (fuse_dec) {          // the output projection also leaves the statistics the next norm1 needs
-        x6ln(m->ctxd.f(), d, L.out, d, xd, xd, false, nullptr, 0, nullptr, m->lnstats.f());
+        x6ln(L.out, {.A = m->ctxd.f(), .C = xd, .N = d, .K = d, .R1 = xd, .stats_out = m->lnstats.f()});
         xd_has_stats = true;
       } else {
         gemm(m, s, m->ctxd.f(), d, L.out, d, d, d, xd, d, xd, d, nullptr, 0, ML, false);
@@ -1127,8 +1156,7 @@ pfhip_status forward_decoder(pfhip_model* m, hipStream_t s, const ForwardPaths& 
       double hw_pairs = 0;
       for (int b = 0; b < B; ++b) hw_pairs += (double)m->n_fires[b] * m->fw_hw_len[b];
       Scope sc(m, s, K_ATTN, 4.0 * hw_pairs * d, 8.0 * ML * d);
-      pfhip::launch_attention(m->qd.f(), d, hwkv, 2 * d, hwkv + d, 2 * d, m->ctxd.f(), d, m->m_tok_off, m->m_tok_len,
-                              m->m_hw_off, m->m_hw_len, B, c.dec_n_head, m->maxL, att_scale_d, s);
+      pfhip::launch_attention(cross_att(hwkv, m->m_hw_off, m->m_hw_len), s);
     }
     gemm(m, s, m->ctxd.f(), d, w.bias.out, d, d, d, cat + d, 2 * d, nullptr, 0, nullptr, 0, ML, false);
     gemm(m, s, cat, 2 * d, w.bias.merge, d, 2 * d, 2 * d, xd, d, xd, d, nullptr, 0, ML, false);

@@ -293,14 +293,17 @@ static pfhip_status punc_infer_packed(pfhip_punc* p, const int32_t* const* ids, 
   float* x = p->x.f();
   pfhip::launch_embed_gather(d_ids, p->d_table, p->vocab, d, x, d, total, p->d_inv_ts, sqrtf((float)d), B > 1 ? d_pos : nullptr, s);
   const float att_scale = 1.0f / sqrtf(32.f);
+  // every layer's attention: d_k = 32, with the VadMask prefix limits when the model is the online one
+  pfhip::AttnOp att = qkv_attention(p->qkv.f(), d, p->ctx.f());
+  att.q_off = att.kv_off = d_off; att.q_len = att.kv_len = d_len;
+  att.B = B; att.H = p->n_head; att.max_q_len = max_n; att.scale = att_scale; att.head_dim = 32; att.q_kv_limit = d_lim;
   for (int i = 0; i < p->layers; ++i) {
     const pfhip_punc::Layer& l = p->L[i];
     pfhip::launch_layernorm(x, d, p->y.f(), d, l.n1g, l.n1b, total, d, d, 1e-12f, s);
     lin_gemm(s, l.qkv, p->y.f(), d, p->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, total, false);
     pfhip::launch_fsmn_shift(p->qkv.f() + 2 * d, 3 * d, l.fsmn, nullptr, 0, p->mem.f(), d, d_off, d_len, B, max_n, d,
                              p->sanm_shift, s);
-    pfhip::launch_attention_masked(p->qkv.f(), 3 * d, p->qkv.f() + d, 3 * d, p->qkv.f() + 2 * d, 3 * d, p->ctx.f(), d, d_off,
-                                   d_len, d_off, d_len, d_lim, B, p->n_head, max_n, att_scale, 32, s);
+    pfhip::launch_attention(att, s);
     lin_gemm(s, l.out, p->ctx.f(), d, x, d, p->mem.f(), d, x, d, total, false);          // in_size == size: residual
     pfhip::launch_layernorm(x, d, p->y.f(), d, l.n2g, l.n2b, total, d, d, 1e-12f, s);
     lin_gemm(s, l.ffn1, p->y.f(), d, p->h.f(), p->ffn, nullptr, 0, nullptr, 0, total, true);

@@ -308,6 +308,11 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   };
   const bool fuse_ln_s = !lean && w.enc_folded && pfhip::gemm_x6_ln_ok(M);
   if (fuse_ln_s) HIP_TRY(m->lnstats.ensure((size_t)(M + 256) * 4 * 2 * 4));
+  auto gemm_ln = [&](const Linear& W, const pfhip::GemmOp& op) { split_gemm(st, W, op, M, d, m->lnstats.f()); };
+  // the windows' self-attention over the qkv buffer, for the shapes the window kernels do not take
+  pfhip::AttnOp self_att = qkv_attention(m->qkv.f(), d, m->ctx.f());
+  self_att.q_off = self_att.kv_off = d_off; self_att.q_len = self_att.kv_len = d_len;
+  self_att.B = B; self_att.H = c.n_head; self_att.max_q_len = maxn; self_att.scale = att_scale; self_att.head_dim = hd;
   // ---- streaming encoder session (:448): SAN-M stack on the windows as given (no scale/PE inside) --------
   for (int i = 0; i < c.enc_layers; ++i) {
     const EncLayer& L = w.enc[(size_t)i];
@@ -325,8 +330,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
                                        3 * d, L.fsmn_w, d, st)) {
         if (!pfhip::launch_window_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, M, M,
                                             c.n_head, att_scale, st, hd))
-          pfhip::launch_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
-                                  d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st, hd);
+          pfhip::launch_attention(self_att, st);
         if (!gemv1(m->ctx.f(), d, L.out, d, x, d, nullptr, first ? nullptr : x, d, m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, M, d, d, false))
           ln_gemm(m->ctx.f(), d, 0, nullptr, L.out, d, x, d, first ? nullptr : x, d, nullptr, 0,
                   m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, M, d, d, false);
@@ -340,8 +344,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     // rounds of many connections (>= 1536 rows): the two LayerNorms of a layer folded into the GEMMs around them, as offline
     // (pfhip.cpp forward_encoder: row statistics from the producing epilogue, algebraic normalisation in the consumer's)
     if (fuse_ln_s && !first)
-      pfhip::launch_gemm_f32_x6_ln(x, d, L.qkv_f.folded.w, d, m->qkv.f(), 3 * d, L.qkv_f.folded.b, nullptr, 0,
-                                   nullptr, 0, M, 3 * d, d, false, m->lnstats.f(), 4, L.qkv_f.colsum, nullptr, st, L.qkv_f.folded.scale);
+      gemm_ln(L.qkv_f.folded, {.A = x, .C = m->qkv.f(), .ldc = 3 * d, .N = 3 * d, .K = d, .ln_colsum = L.qkv_f.colsum});
     else {
       lnorm(m, st, xin, ldin, m->y.f(), Kp, L.norm1, M, Din, Kp);
       gemm(m, st, m->y.f(), Kp, L.qkv, 3 * d, Kp, Din, m->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, M, false);
@@ -352,17 +355,13 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
                                                  d_len, d_off, d_len, B, c.n_head, maxn, maxn, att_scale, st, L.fsmn_w,
                                                  m->mem.f(), d, hd)) {
       pfhip::launch_fsmn(m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, nullptr, 0, m->mem.f(), d, d_off, d_len, B, maxn, d, st);
-      pfhip::launch_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
-                              d_len, d_off, d_len, B, c.n_head, maxn, att_scale, st, hd);
+      pfhip::launch_attention(self_att, st);
     }
     if (fuse_ln_s) {
-      pfhip::launch_gemm_f32_x6_ln(m->ctx.f(), d, L.out.w, d, x, d, L.out.b, m->mem.f(), d, first ? nullptr : x, d, M,
-                                   d, d, false, nullptr, 4, nullptr, m->lnstats.f(), st, L.out.scale);
-      pfhip::launch_gemm_f32_x6_ln(x, d, L.ffn1_f.folded.w, d, m->hbuf.f(), c.ffn, L.ffn1_f.folded.b,
-                                   nullptr, 0, nullptr, 0, M, c.ffn, d, true, m->lnstats.f(), 4, L.ffn1_f.colsum, nullptr, st,
-                                   L.ffn1_f.folded.scale);
-      pfhip::launch_gemm_f32_x6_ln(m->hbuf.f(), c.ffn, L.ffn2.w, c.ffn, x, d, L.ffn2.b, x, d, nullptr, 0, M, d, c.ffn,
-                                   false, nullptr, 4, nullptr, i + 1 < c.enc_layers ? m->lnstats.f() : nullptr, st, L.ffn2.scale);
+      gemm_ln(L.out, {.A = m->ctx.f(), .C = x, .ldc = d, .N = d, .K = d, .R1 = m->mem.f(), .R2 = first ? nullptr : x, .stats_out = m->lnstats.f()});
+      gemm_ln(L.ffn1_f.folded, {.A = x, .C = m->hbuf.f(), .ldc = c.ffn, .N = c.ffn, .K = d, .relu = true, .ln_colsum = L.ffn1_f.colsum});
+      gemm_ln(L.ffn2, {.A = m->hbuf.f(), .C = x, .ldc = d, .N = d, .K = c.ffn, .R1 = x,
+                       .stats_out = i + 1 < c.enc_layers ? m->lnstats.f() : nullptr});
       continue;
     }
     gemm(m, st, m->ctx.f(), d, L.out, d, d, d, x, d, m->mem.f(), d, first ? nullptr : x, d, M, false);
@@ -467,6 +466,13 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     if (!gemv1(m->enc.f(), d, w.kv_all, d, m->kvall.f(), kv_ld, nullptr, nullptr, 0, nullptr, 0, nullptr, M, kv_ld, d, false))
       ln_gemm(m->enc.f(), d, 0, nullptr, w.kv_all, d, m->kvall.f(), kv_ld, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, kv_ld, d, false);
   }
+  // the tokens' queries in qd against each stream's window in K | V (row stride ldkv), for the shapes the window kernels do not take
+  auto cross_att = [&](const float* kv, int ldkv) {
+    pfhip::AttnOp op = kv_attention(m->qd.f(), d, kv, ldkv, m->ctxd.f());
+    op.q_off = d_tok_off; op.q_len = d_tok_len; op.kv_off = d_off; op.kv_len = d_len;
+    op.B = B; op.H = c.dec_n_head; op.max_q_len = maxN; op.scale = att_scale_d; op.head_dim = hdd;
+    return op;
+  };
   for (int i = 0; i < c.dec_layers; ++i) {
     const DecLayer& L = w.dec[(size_t)i];
     dec_ffn(L.ffn, xd, m->td.f());
@@ -480,8 +486,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
                                       L.out.b, xd, d, nullptr, 0, nullptr, d, st))
         continue;
       if (!pfhip::launch_window_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, ML, M, c.dec_n_head, att_scale_d, st, hdd))
-        pfhip::launch_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off, d_len, B,
-                                c.dec_n_head, maxN, att_scale_d, st, hdd);
+        pfhip::launch_attention(cross_att(kvl, kv_ld), st);
       if (!gemv1(m->ctxd.f(), d, L.out, d, xd, d, nullptr, xd, d, nullptr, 0, nullptr, ML, d, d, false))
         ln_gemm(m->ctxd.f(), d, 0, nullptr, L.out, d, xd, d, xd, d, nullptr, 0, nullptr, 0, nullptr, ML, d, d, false);
       continue;
@@ -491,8 +496,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     gemm(m, st, m->enc.f(), d, L.kv, 2 * d, d, d, kvbuf, 2 * d, nullptr, 0, nullptr, 0, M, false);
     if (!pfhip::launch_window_attention_segments(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off,
                                                  d_len, B, c.dec_n_head, maxN, maxn, att_scale_d, st, nullptr, nullptr, 0, hdd))
-      pfhip::launch_attention(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off, d_len, B,
-                              c.dec_n_head, maxN, att_scale_d, st, hdd);
+      pfhip::launch_attention(cross_att(kvbuf, 2 * d), st);
     gemm(m, st, m->ctxd.f(), d, L.out, d, d, d, xd, d, xd, d, nullptr, 0, ML, false);
   }
   dec_ffn(w.dec3, xd, m->td.f());

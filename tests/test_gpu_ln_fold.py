@@ -187,7 +187,7 @@ def test_fold_on_plane_operands_matches_fp64_layernorm(ops, monkeypatch, K, N):
 @pytest.mark.parametrize("exact", [False, True])
 @pytest.mark.parametrize("K,N", [(512, 512), (512, 1536), (2048, 512)])
 def test_fold_on_fp32_operands_matches_fp64_layernorm(ops, K, N, exact):
-    """launch_gemm_f32_x6_ln through pfhip_op_gemm_f32_ln: gemm_x3.hip (default) and gemm_x6.hip (exact).  Row counts on both sides
+    """launch_gemm (GemmKernel::SplitBySize) through pfhip_op_gemm_f32_ln: gemm_x3.hip (default) and gemm_x6.hip (exact).  Row counts on both sides
     of gemm_x6_ln_ok (1408 rows = 11 row panels: off; 1409: on), of the 64- / 128-row tile switch (128 tiles of 128 x 128) and ragged."""
     rng = np.random.default_rng(2000 + K + N)
     L = layer(ops, rng, N, K)
