@@ -50,6 +50,9 @@ ABI_SYMBOLS = [
     "pfhip_set_vad_batching", "pfhip_vad_batch_stats", "pfhip_vadseg_feed_energy",
     # streaming: candidates, confidences and fire frames per token; the candidates call on 16-bit PCM
     "pfhip_stream_set_detail", "pfhip_stream_last_detail", "pfhip_offline_forward_nbest_s16",
+    # offline: fire frames of the CIF scan per token, and token spans from them
+    "pfhip_offline_forward_detail", "pfhip_offline_forward_detail_s16", "pfhip_set_fire_frames", "pfhip_offline_fetch_fire_frames",
+    "pfhip_lfr_frame_ms", "pfhip_cif_timestamps",
 ]
 
 
@@ -91,6 +94,11 @@ class _Out(ctypes.Structure):
 
 class _Nbest(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("ids", ctypes.POINTER(ctypes.c_int32)), ("logp", ctypes.POINTER(ctypes.c_float))]
+
+
+class _Detail(ctypes.Structure):
+    _fields_ = [("nbest_k", ctypes.c_int32), ("nbest_ids", ctypes.POINTER(ctypes.c_int32)), ("nbest_logp", ctypes.POINTER(ctypes.c_float)),
+                ("fire_frame", ctypes.POINTER(ctypes.c_int32))]
 
 
 class _StreamDetail(ctypes.Structure):
@@ -188,6 +196,14 @@ def load_lib() -> ctypes.CDLL:
         lib.pfhip_offline_forward_nbest_s16.argtypes = lib.pfhip_offline_forward_nbest.argtypes
         lib.pfhip_stream_set_detail.argtypes = [vp, ci, ci]
         lib.pfhip_stream_last_detail.argtypes = [vp, ctypes.POINTER(_StreamDetail), ctypes.POINTER(ci)]
+    if hasattr(lib, "pfhip_offline_forward_detail"):
+        lib.pfhip_offline_forward_detail.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci),
+                                                     ci, ctypes.POINTER(ci), ctypes.POINTER(_Out), ctypes.POINTER(_Detail)]
+        lib.pfhip_offline_forward_detail_s16.argtypes = lib.pfhip_offline_forward_detail.argtypes
+        lib.pfhip_set_fire_frames.argtypes = [vp, ci]
+        lib.pfhip_offline_fetch_fire_frames.argtypes = [vp, vp]
+        lib.pfhip_lfr_frame_ms.argtypes = [vp]
+        lib.pfhip_cif_timestamps.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, ci, ctypes.POINTER(ci)]
     lib.pfhip_stream_create.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(vp)]
     lib.pfhip_stream_destroy.argtypes = [vp]
     lib.pfhip_stream_destroy.restype = None
@@ -478,7 +494,8 @@ class ParaformerHip:
         return [o[:got[b]] for b, o in enumerate(outs)]
 
     def forward_ids(self, din: Sequence[np.ndarray], want_logp=False, max_tokens=None, hw_emb=None, want_timestamps=False,
-                    sample_rate=None, hw_sets=None, set_of_utt=None, nbest=None, nbest_fill=0, nbest_s16=False):
+                    sample_rate=None, hw_sets=None, set_of_utt=None, nbest=None, nbest_fill=0, nbest_s16=False,
+                    want_fire_frames=False, fire_fill=-1):
         """Batched forward.  Returns dict(token_num, n_fires, n_frames, ids=list of int arrays,
         logp=list of [n_fires, V] arrays or None[, us_alphas, us_peaks = lists of [3*T_b] arrays]).
         hw_emb: one hotword set [H, d] for the whole batch.  hw_sets + set_of_utt: a list of sets ([H_k, d] each) and, per
@@ -486,7 +503,9 @@ class ParaformerHip:
         sample_rate: the rate of din when it is not the model's (pfhip_offline_forward_rate resamples on the GPU first).
         nbest=k (1..8): also nbest_ids / nbest_logp [batch, max_tokens, k], the k best columns of every token row and their
         log-probabilities (pfhip_offline_forward_nbest; rows >= n_fires keep nbest_fill); not together with sample_rate.
-        nbest_s16: np.int16 utterances go to pfhip_offline_forward_nbest_s16 as they are instead of being converted here."""
+        nbest_s16: np.int16 utterances go to pfhip_offline_forward_nbest_s16 as they are instead of being converted here.
+        want_fire_frames: also fire_frame [batch, max_tokens] int32, the LFR row each token row fired in (n_frames[b] = the tail slot;
+        rows >= n_fires keep fire_fill), through pfhip_offline_forward_detail — which takes nbest, hw_sets and sample_rate together."""
         B = len(din)
         if B == 0:
             raise PfhipError("empty batch")
@@ -526,7 +545,25 @@ class ParaformerHip:
             out.max_us = max_us
         hw = np.ascontiguousarray(hw_emb, dtype=np.float32) if hw_emb is not None else None
         hw_ptr, n_hw = (hw.ctypes.data, int(hw.shape[0])) if hw is not None else (None, 0)
-        if nbest is not None:
+        if want_fire_frames:
+            if hw_sets is not None and (hw_emb is not None or set_of_utt is None or len(set_of_utt) != B):
+                raise PfhipError("hw_sets needs set_of_utt [batch] and excludes hw_emb")
+            k = int(nbest) if nbest is not None else 0
+            fire = np.full((B, max_tokens), fire_fill, np.int32)
+            det = _Detail(k, None, None, fire.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+            if nbest is not None:
+                nb_ids = np.full((B, max_tokens, max(k, 1)), nbest_fill, np.int32)
+                nb_logp = np.full((B, max_tokens, max(k, 1)), nbest_fill, np.float32)
+                det.nbest_ids = nb_ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+                det.nbest_logp = nb_logp.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+            sets = [np.ascontiguousarray(h, dtype=np.float32) for h in hw_sets] if hw_sets is not None else ([hw] if hw is not None else [])
+            sptr = (ctypes.c_void_p * max(len(sets), 1))(*[h.ctypes.data if h.size else None for h in sets])
+            sn = (ctypes.c_int * max(len(sets), 1))(*[int(h.shape[0]) for h in sets])
+            sof = (ctypes.c_int * B)(*[int(j) for j in (set_of_utt if hw_sets is not None else [0] * B)])
+            _check(self._lib, getattr(self._lib, "pfhip_offline_forward_detail" + sfx)(
+                self._h, ptrs, lens, B, int(sample_rate) if sample_rate is not None else 0, sptr, sn, len(sets), sof, ctypes.byref(out),
+                ctypes.byref(det)))
+        elif nbest is not None:
             if sample_rate is not None or (hw_sets is not None and (hw_emb is not None or set_of_utt is None or len(set_of_utt) != B)):
                 raise PfhipError("nbest excludes sample_rate; hw_sets needs set_of_utt [batch] and excludes hw_emb")
             k = int(nbest)
@@ -561,6 +598,8 @@ class ParaformerHip:
             res["us_peaks"] = [usp[b, :usl[b]].copy() for b in range(B)]
         if nbest is not None:
             res["nbest_ids"], res["nbest_logp"] = nb_ids, nb_logp
+        if want_fire_frames:
+            res["fire_frame"] = fire
         return res
 
     def Forward(self, din, len_=None, input_finished=True, hw_emb=None, decoder_handle=None, batch_in=1):
@@ -637,6 +676,19 @@ class ParaformerHip:
         nb = _Nbest(int(k), nb_ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), nb_logp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
         _check(self._lib, self._lib.pfhip_offline_fetch_nbest(self._h, ctypes.byref(nb)))
         return nb_ids, nb_logp
+
+    def set_fire_frames(self, on=True):
+        """pfhip_set_fire_frames: fire frames for the following enqueue_device / forward_resident calls (False = off)."""
+        _check(self._lib, self._lib.pfhip_set_fire_frames(self._h, 1 if on else 0))
+
+    def fetch_fire_frames(self, B: int, max_tokens: int, fill=-1):
+        """pfhip_offline_fetch_fire_frames after fetch(B, max_tokens) or forward_resident(..., max_tokens): fire_frame [B, max_tokens]."""
+        fire = np.full((B, max_tokens), fill, np.int32)
+        _check(self._lib, self._lib.pfhip_offline_fetch_fire_frames(self._h, fire.ctypes.data))
+        return fire
+
+    def lfr_frame_ms(self):
+        return int(self._lib.pfhip_lfr_frame_ms(self._h))
 
     def forward_resident(self, d_pcm_ptr: int, sample_off: np.ndarray, n_samples: np.ndarray, max_tokens: int, s16: bool = False):
         """pfhip_offline_forward_resident: PCM already in HBM, routed over the handle's execution contexts like Forward.
@@ -1083,4 +1135,22 @@ def timestamp_onnx(us_alphas, us_cif_peak, n_chars, begin_time=0.0, total_offset
     n = ctypes.c_int(0)
     _check(lib, lib.pfhip_timestamp_onnx(a.ctypes.data, p.ctypes.data, int(p.size), int(n_chars), float(begin_time),
                                          float(total_offset), spans.ctypes.data, cap, ctypes.byref(n)))
+    return [(float(s[0]), float(s[1]), bool(s[2])) for s in spans[:n.value]]
+
+
+def cif_timestamps(fire_frame, n_chars, n_frames, frame_ms=60.0, begin_time=0.0, cap=None):
+    """pfhip_cif_timestamps: token spans from the fire frames of the CIF scan (an extension: the reference stamps only through its
+    timestamp head): [(begin_s, end_s, is_sil)].  cap: room for that many spans (default: enough)."""
+    lib = load_lib()
+    f = np.ascontiguousarray(fire_frame, dtype=np.int32)
+    cap = 2 * max(int(n_chars), 0) + 2 if cap is None else int(cap)
+    spans = np.zeros((max(cap, 1), 3), np.float32)
+    n = ctypes.c_int(0)
+    rc = lib.pfhip_cif_timestamps(f.ctypes.data if f.size else None, int(f.size), int(n_chars), int(n_frames), float(frame_ms),
+                                  float(begin_time), spans.ctypes.data, cap, ctypes.byref(n))
+    if rc == 5:      # PFHIP_ERR_CAPACITY: the count it needed travels with the error
+        err = PfhipError(f"pfhip status {rc}: {lib.pfhip_last_error().decode()}")
+        err.status, err.needed = rc, n.value
+        raise err
+    _check(lib, rc)
     return [(float(s[0]), float(s[1]), bool(s[2])) for s in spans[:n.value]]

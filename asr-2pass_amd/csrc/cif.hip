@@ -16,14 +16,15 @@ namespace {
 
 constexpr int kPf = 8;
 
-template <int NC>
-__global__ __launch_bounds__(512) void cif_kernel(const float* __restrict__ hidden, int ldh,
-                                                  const float* __restrict__ alphas,
-                                                  const int* __restrict__ row_off,
-                                                  const int* __restrict__ len, int D, float thr,
-                                                  float tail, float* __restrict__ stage,
-                                                  int* __restrict__ n_fires,
-                                                  int* __restrict__ token_num) {
+// The scan, shared by the two kernels below.  FIRES: also record in which step i of the scan each token fired (i = 0..T-1 an LFR
+// row, i = T the tail slot), laid out like the staged embeddings: utterance b, fire nf at fire_frame_all[row_off[b] + b + nf].  One
+// lane stores it, outside the per-channel loops; the fire / no-fire branch stays uniform across the block (every thread carries the
+// same integrate) and the arithmetic is the same statements in the same order, so stage, n_fires and token_num do not depend on FIRES.
+template <int NC, bool FIRES>
+__device__ __forceinline__ void cif_scan(const float* __restrict__ hidden, int ldh, const float* __restrict__ alphas,
+                                         const int* __restrict__ row_off, const int* __restrict__ len, int D, float thr, float tail,
+                                         float* __restrict__ stage, int* __restrict__ n_fires, int* __restrict__ token_num,
+                                         int* __restrict__ fire_frame_all) {
   const int b = blockIdx.x;
   const int T = len[b];
   if (T <= 0) {
@@ -70,6 +71,9 @@ __global__ __launch_bounds__(512) void cif_kernel(const float* __restrict__ hidd
           const int ch = threadIdx.x + c * 512;
           if (ch < D) out[(size_t)nf * D + ch] = frames[c];
         }
+        if constexpr (FIRES) {
+          if (threadIdx.x == 0) fire_frame_all[base + b + nf] = i0 + u;
+        }
         ++nf;
         integrate += alpha;
         integrate -= thr;
@@ -84,12 +88,43 @@ __global__ __launch_bounds__(512) void cif_kernel(const float* __restrict__ hidd
   }
 }
 
+// the default kernel: its signature and kernel arguments are what they always were
+template <int NC>
+__global__ __launch_bounds__(512) void cif_kernel(const float* __restrict__ hidden, int ldh,
+                                                  const float* __restrict__ alphas,
+                                                  const int* __restrict__ row_off,
+                                                  const int* __restrict__ len, int D, float thr,
+                                                  float tail, float* __restrict__ stage,
+                                                  int* __restrict__ n_fires,
+                                                  int* __restrict__ token_num) {
+  cif_scan<NC, false>(hidden, ldh, alphas, row_off, len, D, thr, tail, stage, n_fires, token_num, nullptr);
+}
+
+// the sibling that also writes fire_frame [sum len + B]
+template <int NC>
+__global__ __launch_bounds__(512) void cif_fires_kernel(const float* __restrict__ hidden, int ldh, const float* __restrict__ alphas,
+                                                        const int* __restrict__ row_off, const int* __restrict__ len, int D,
+                                                        float thr, float tail, float* __restrict__ stage,
+                                                        int* __restrict__ n_fires, int* __restrict__ token_num,
+                                                        int* __restrict__ fire_frame) {
+  cif_scan<NC, true>(hidden, ldh, alphas, row_off, len, D, thr, tail, stage, n_fires, token_num, fire_frame);
+}
+
 }  // namespace
 
 void launch_cif(const float* hidden, int ldh, const float* alphas, const int* row_off,
                 const int* len, int B, int D, float threshold, float tail, float* stage,
-                int* n_fires, int* token_num, hipStream_t s) {
+                int* n_fires, int* token_num, hipStream_t s, int* fire_frame) {
   if (B <= 0) return;
+  if (fire_frame) {
+    if (D <= 512)
+      hipLaunchKernelGGL(cif_fires_kernel<1>, dim3(B), dim3(512), 0, s, hidden, ldh, alphas, row_off, len, D, threshold, tail,
+                         stage, n_fires, token_num, fire_frame);
+    else
+      hipLaunchKernelGGL(cif_fires_kernel<2>, dim3(B), dim3(512), 0, s, hidden, ldh, alphas, row_off, len, D, threshold, tail,
+                         stage, n_fires, token_num, fire_frame);
+    return;
+  }
   if (D <= 512)
     hipLaunchKernelGGL(cif_kernel<1>, dim3(B), dim3(512), 0, s, hidden, ldh, alphas, row_off, len, D,
                        threshold, tail, stage, n_fires, token_num);

@@ -194,12 +194,12 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   //     (pfhip_offline_forward_rate_s16), no float copy at all;
   //   * at another rate WITH a VAD the segments are ranges of the RESAMPLED waveform, which is on the host as floats (LoadPcm):
   //     that path stays on floats, and its VAD takes the energy form as well.
-  // FunOfflineSetNbest changes none of this: the candidates call takes 16-bit samples too (pfhip_offline_forward_nbest_s16).
+  // FunOfflineSetNbest and FunOfflineSetCifStamps change none of this: their calls take 16-bit samples and a sample rate too
+  // (pfhip_offline_forward_nbest_s16, pfhip_offline_forward_detail_s16).
   const int model_rate = os->asr.GetAsrSampleRate();
   const int n_in = n_len / 2;
   const bool same_rate = sampling_rate == model_rate;
-  // (candidates and device-side resampling exclude each other: that one combination stays on resampled floats)
-  const bool use16 = same_rate || (!os->vad && os->asr.GetNbest() == 0);
+  const bool use16 = same_rate || !os->vad;
   std::vector<int16_t> store16;
   const int16_t* pcm16 = use16 ? Pcm16View(sz_buf, n_in, store16) : nullptr;
   std::vector<float> pcm;
@@ -307,6 +307,7 @@ const std::vector<std::vector<int>>& FunASRGetSegmentIds(FUNASR_RESULT result) {
 const std::vector<std::pair<int, int>>& FunASRGetSegments(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->segs; }
 const std::vector<int>& FunASRGetOnlineIds(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_ids; }
 void FunOfflineSetNbest(FUNASR_HANDLE handle, int k) { if (handle) static_cast<OfflineStreamHip*>(handle)->asr.SetNbest(k); }
+void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode) { if (handle) static_cast<OfflineStreamHip*>(handle)->asr.SetCifTimestamps(mode); }
 const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->confidence; }
 const std::vector<float>& FunASRGetOnlineConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_conf; }
 const std::vector<int>& FunASRGetOnlineFireMs(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_fire_ms; }
@@ -391,6 +392,10 @@ void FunTpassSetNbest(FUNASR_HANDLE tpass_handle, int k) {
   if (!ts) return;
   ts->asr.SetNbest(k);
   ts->detail_k = ts->asr.GetNbest();
+}
+
+void FunTpassSetCifStamps(FUNASR_HANDLE tpass_handle, int mode) {
+  if (tpass_handle) static_cast<TpassStreamHip*>(tpass_handle)->asr.SetCifTimestamps(mode);
 }
 
 FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_handle, const char* sz_buf, int n_len,

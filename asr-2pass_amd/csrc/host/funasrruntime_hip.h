@@ -113,6 +113,15 @@ const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result);
 void FunTpassSetNbest(FUNASR_HANDLE tpass_handle, int k);
 const std::vector<float>& FunASRGetOnlineConfidence(FUNASR_RESULT result);
 const std::vector<int>& FunASRGetOnlineFireMs(FUNASR_RESULT result);
+// Time stamps from the CIF scan for any Paraformer (an extension: the reference stamps only through the CifPredictorV3 head of its
+// 4-output graph, paraformer.cpp:545, and FunASRGetStamp is empty for every other model).  FunOfflineSetCifStamps(h, mode) applies
+// ParaformerHip::SetCifTimestamps(mode) to the handle's acoustic model for every following FunOfflineInferBuffer: 0 = off (default:
+// the adapter calls exactly what it always called), 1 = models without the head get stamps from the fire frames of the CIF scan, models
+// with the head keep the head's, 2 = every model gets the CIF rule's (the head is skipped).  The result's stamps come through
+// FunASRGetStamp in its usual "[[b,e],...]" form, one pair per character of the text, VAD segment offsets added; resolution is one
+// LFR row (60 ms), and they are not the head's stamps.  FunTpassSetCifStamps does the same for the offline pass of the 2-pass flow.
+void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode);
+void FunTpassSetCifStamps(FUNASR_HANDLE tpass_handle, int mode);
 // ... and the C-ABI handle of the offline acoustic model behind a FunOfflineInit handle (pfhip_inflight_stats in the harnesses)
 struct pfhip_model;
 pfhip_model* FunOfflineGetAsrHandle(FUNASR_HANDLE handle);

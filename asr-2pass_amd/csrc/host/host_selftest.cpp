@@ -23,12 +23,12 @@
 
 namespace {
 
-struct Req : pfhip_detail::MergeReqBase {
+struct Req : pfhip_impl::MergeReqBase {
   int thread = 0, value = 0, result = -1, batch = 0;
 };
 
 int run_mergequeue(int n_threads, int rounds) {
-  pfhip_detail::MergeQueue<Req> q;
+  pfhip_impl::MergeQueue<Req> q;
   std::atomic<long> execs{0}, served{0}, max_batch{0};
   std::atomic<int> errors{0};
   std::vector<std::thread> pool;

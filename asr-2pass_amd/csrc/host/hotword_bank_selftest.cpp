@@ -7,7 +7,7 @@
 
 #include "../hotword_bank.h"
 
-using pfhip_detail::HotwordBank;
+using pfhip_impl::HotwordBank;
 
 #define CHECK(cond)                                                                  \
   do {                                                                               \
@@ -43,8 +43,8 @@ int collision() {
   CHECK(e >= 0 && e != a && e != c && !hit);
   CHECK(b.hits == 2 && b.misses == 3 && b.evictions == 0);
   // the real hash separates H as well as content
-  CHECK(pfhip_detail::hotword_hash(A.data(), A.size(), 3) != pfhip_detail::hotword_hash(B.data(), B.size(), 3));
-  CHECK(pfhip_detail::hotword_hash(A.data(), A.size(), 3) != pfhip_detail::hotword_hash(A.data(), A.size(), 4));
+  CHECK(pfhip_impl::hotword_hash(A.data(), A.size(), 3) != pfhip_impl::hotword_hash(B.data(), B.size(), 3));
+  CHECK(pfhip_impl::hotword_hash(A.data(), A.size(), 3) != pfhip_impl::hotword_hash(A.data(), A.size(), 4));
   return 0;
 }
 

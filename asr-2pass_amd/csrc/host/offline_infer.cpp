@@ -1,6 +1,6 @@
 // Harness over the handle-API mirror (funasrruntime_hip.h) with the shape of the reference's offline client
 // (onnxruntime/bin/funasr-onnx-offline.cpp: FunOfflineInit -> FunOfflineInferBuffer per file -> FunASRGetResult):
-//   offline_infer <model_dir> <vad_dir|-> <pcm_s16_file> [batch=32] [threads=1] [repeat=1] [punc_dir|-] [audio_fs] [nbest=0]
+//   offline_infer <model_dir> <vad_dir|-> <pcm_s16_file> [batch=32] [threads=1] [repeat=1] [punc_dir|-] [audio_fs] [nbest=0] [cif_stamps=0]
 // Prints one line per VAD segment, time order: "seg <start_sample> <end_sample> : <ids...>", then timing; with threads > 1
 // every thread transcribes the same buffer through the shared handle (the server's decoder threads).
 #include <atomic>
@@ -15,7 +15,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s model_dir vad_dir|- pcm_s16_file [batch] [threads] [repeat] [punc_dir|-] [audio_fs] [nbest]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s model_dir vad_dir|- pcm_s16_file [batch] [threads] [repeat] [punc_dir|-] [audio_fs] [nbest] [cif_stamps]\n", argv[0]);
     return 2;
   }
   std::map<std::string, std::string> paths;
@@ -24,6 +24,7 @@ int main(int argc, char** argv) {
   if (argc > 7 && std::string(argv[7]) != "-") paths[PUNC_DIR] = argv[7];
   const int audio_fs = argc > 8 ? std::atoi(argv[8]) : 16000;      // the client's --audio-fs (funasr-wss-client.cpp:194,240,366)
   const int nbest = argc > 9 ? std::atoi(argv[9]) : 0;             // FunOfflineSetNbest for one extra pass (an extension)
+  const int cif_stamps = argc > 10 ? std::atoi(argv[10]) : 0;      // FunOfflineSetCifStamps mode for one extra pass (an extension)
   const int batch = argc > 4 ? std::atoi(argv[4]) : 32, threads = argc > 5 ? std::atoi(argv[5]) : 1, repeat = argc > 6 ? std::atoi(argv[6]) : 1;
   std::ifstream f(argv[3], std::ios::binary);
   std::vector<char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
@@ -50,6 +51,14 @@ int main(int argc, char** argv) {
       std::printf("\n");
       FunASRFreeResult(q);
       FunOfflineSetNbest(h, 0);
+    }
+    if (cif_stamps > 0) {  // the same buffer once more with stamps from the CIF scan: "cif_text <text>", "cif_stamp <stamps>"
+      FunOfflineSetCifStamps(h, cif_stamps);
+      FUNASR_RESULT q = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, audio_fs, "pcm");
+      if (!q) { std::fprintf(stderr, "inference failed\n"); return 1; }
+      std::printf("cif_text %s\ncif_stamp %s\n", FunASRGetResult(q, 0), FunASRGetStamp(q));
+      FunASRFreeResult(q);
+      FunOfflineSetCifStamps(h, 0);
     }
     const std::string want_text = FunASRGetResult(r, 0), want_stamp = FunASRGetStamp(r);
     std::atomic<int> mismatches{0};

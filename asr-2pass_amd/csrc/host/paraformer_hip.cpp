@@ -240,16 +240,6 @@ std::vector<std::string> ParaformerHip::ForwardPcm16(const int16_t* const* din, 
                                                      const std::vector<std::vector<float>>& hw_emb, void* wfst_decoder, int batch_in,
                                                      int sample_rate) {
   if (sample_rate == GetAsrSampleRate()) sample_rate = 0;
-  if (nbest_k_ && sample_rate) {      // neither the candidates call nor the resampling call has the other's form
-    std::fprintf(stderr, "ParaformerHip::ForwardPcm16: SetNbest and a sample rate other than the model's exclude each other\n");
-    const size_t n_res = batch_in > 0 ? (size_t)batch_in : 0;
-    tl_last_ids.assign(n_res, {});
-    tl_last_spans.assign(n_res, {});
-    tl_last_nbest_ids.assign(n_res, {});
-    tl_last_nbest_logp.assign(n_res, {});
-    tl_last_conf.assign(n_res, {});
-    return std::vector<std::string>(n_res);      // "" per item, as every failed Forward
-  }
   return ForwardAny(reinterpret_cast<const void* const*>(din), true, len, input_finished, hw_emb, wfst_decoder, batch_in, sample_rate);
 }
 
@@ -291,7 +281,13 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
     logp.resize((size_t)batch_in * max_tokens * V);
     out.logp = logp.data();
   }
-  const bool with_ts = pfhip_has_timestamp_head(handle_) != 0;      // the reference's outputTensor.size() == 4 (paraformer.cpp:545)
+  const bool has_head = pfhip_has_timestamp_head(handle_) != 0;     // the reference's outputTensor.size() == 4 (paraformer.cpp:545)
+  // SetCifTimestamps: spans from the CIF scan's fire frames, for models without the head (1) or for every model (2: the head is then
+  // skipped, all three us_* pointers NULL).  Never with an LM decoder: FinalizeDecode(true, ...) needs the head's traces
+  const bool cif_ts = !decoder && (cif_ts_mode_ == 2 || (cif_ts_mode_ == 1 && !has_head));
+  const bool with_ts = has_head && !cif_ts;
+  std::vector<int32_t> fire(cif_ts ? (size_t)batch_in * max_tokens : 0);
+  const float frame_ms = cif_ts ? (float)pfhip_lfr_frame_ms(handle_) : 0.f;
   const int max_us = 3 * max_tokens;
   std::vector<float> usa, usp;
   if (with_ts) {
@@ -313,11 +309,20 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
     }
   }
   // SetNbest: the same forward plus the k best columns of every token row (this caller's one hotword set as set 0)
-  const int nk = nbest_k_;                        // (ForwardPcm16 refuses it together with another sample rate)
+  const int nk = nbest_k_;
   std::vector<int32_t> nb_ids((size_t)(nk ? batch_in : 0) * max_tokens * nk);
   std::vector<float> nb_logp(nb_ids.size());
   pfhip_status st;
-  if (nk) {
+  if (cif_ts || (nk && sample_rate)) {            // one call carries the candidates, the fire frames and the rate of the audio
+    const pfhip_detail det{nk, nk ? nb_ids.data() : nullptr, nk ? nb_logp.data() : nullptr, cif_ts ? fire.data() : nullptr};
+    const float* sets[1] = {hw.data()};
+    const int set_rows[1] = {n_hw};
+    const std::vector<int> set_of_utt((size_t)batch_in, 0);
+    st = s16 ? pfhip_offline_forward_detail_s16(handle_, din16, len, batch_in, sample_rate, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(),
+                                                &out, &det)
+             : pfhip_offline_forward_detail(handle_, din, len, batch_in, sample_rate, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(), &out,
+                                            &det);
+  } else if (nk) {
     const pfhip_nbest nb{nk, nb_ids.data(), nb_logp.data()};
     const float* sets[1] = {hw.data()};
     const int set_rows[1] = {n_hw};
@@ -365,7 +370,7 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
       continue;
     }
     results[i] = IdsToString(tl_last_ids[i]);
-    if (with_ts && n > 0 && usl[i] > 0) {
+    if ((with_ts && n > 0 && usl[i] > 0) || (cif_ts && n > 0)) {
       // GreedySearch(..., is_stamp = true) -> TimestampOnnx over the characters of the hypothesis (paraformer.cpp:386-395)
       // char_list = all token_num hypotheses (Vocab::Vector2String keeps every id); TimestampOnnx drops a trailing "</s>"
       // (util.cpp:846-849) — id 2 in the FunASR vocabularies when no tokens.json is loaded
@@ -374,9 +379,12 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
       const int n_chars = n - (eos ? 1 : 0);
       std::vector<float> spans((size_t)3 * (2 * n + 2));
       int n_spans = 0;
+      // (CIF stamps: the same triplets from the fire frames of this utterance's first n token rows; the eos row's is the tail slot's)
       if (n_chars > 0 &&
-          pfhip_timestamp_onnx(usa.data() + (size_t)i * max_us, usp.data() + (size_t)i * max_us, usl[i], n_chars, 0.f, -1.5f,
-                               spans.data(), (int)spans.size() / 3, &n_spans) == PFHIP_OK)
+          (cif_ts ? pfhip_cif_timestamps(fire.data() + (size_t)i * max_tokens, n, n_chars, fr[i], frame_ms, 0.f, spans.data(),
+                                         (int)spans.size() / 3, &n_spans)
+                  : pfhip_timestamp_onnx(usa.data() + (size_t)i * max_us, usp.data() + (size_t)i * max_us, usl[i], n_chars, 0.f, -1.5f,
+                                         spans.data(), (int)spans.size() / 3, &n_spans)) == PFHIP_OK)
         tl_last_spans[i].assign(spans.begin(), spans.begin() + (size_t)3 * n_spans);
       if (vocab && n_spans > 0) {
         // time-stamp mode returns "<text> | <stamps>" (paraformer.cpp:398-406: Vector2String -> TimestampOnnx -> PostProcess)

@@ -133,9 +133,9 @@ class ParaformerHip : public ParaformerHipBase
   // on the host): the caller's buffers go to the device as they are (pfhip_offline_forward_s16 — half the bytes, no float copy) and
   // every result is bit for bit that of Forward on din[i][j] / 32768.f.  sample_rate != 0 and != GetAsrSampleRate(): the audio is
   // at that rate and is resampled on the device first (pfhip_offline_forward_rate_s16, Audio::WavResample).  With SetNbest the bytes go
-  // to pfhip_offline_forward_nbest_s16 in the same way; SetNbest together with another
-  // sample rate is refused ("" per item and a message, like a failed Forward: resample first with pfhip_resample).  Not a virtual: the
-  // funasr::Model::Forward(float**) seam and its table are untouched.
+  // to pfhip_offline_forward_nbest_s16 in the same way; SetNbest or SetCifTimestamps together with another sample rate go through
+  // pfhip_offline_forward_detail_s16, which carries all of them.  Not a virtual: the funasr::Model::Forward(float**) seam and its table
+  // are untouched.
   std::vector<std::string> ForwardPcm16(const int16_t* const* din, const int* len, bool input_finished,
                                         const std::vector<std::vector<float>>& hw_emb = {{0.0}}, void* wfst_decoder = nullptr,
                                         int batch_in = 1, int sample_rate = 0);
@@ -181,7 +181,7 @@ class ParaformerHip : public ParaformerHipBase
   // (of the calling thread: Forward is re-entrant)
   const std::vector<std::vector<int>>& LastTokenIds() const;
   // timestamp models: (begin_s, end_s, is_sil) per span of the last Forward, what TimestampOnnx produced
-  // (paraformer.cpp:545-562 + util.cpp:838-963); empty for plain models
+  // (paraformer.cpp:545-562 + util.cpp:838-963); empty for plain models (unless SetCifTimestamps makes them, below)
   const std::vector<std::vector<float>>& LastTimestamps() const;
   // N-best candidates (an extension; GreedySearch keeps only the arg-max, paraformer.cpp:386-395).  SetNbest(k), k = 1..8: every
   // following Forward also asks the head for the k best columns of each token row (pfhip_offline_forward_nbest); 0 (default):
@@ -194,6 +194,16 @@ class ParaformerHip : public ParaformerHipBase
   const std::vector<std::vector<int>>& LastNbestIds() const;
   const std::vector<std::vector<float>>& LastNbestLogp() const;
   const std::vector<std::vector<float>>& LastTokenConfidence() const;
+  // Time stamps from the CIF scan (an extension: the reference has no counterpart; its only source of stamps is the head of the
+  // 4-output graph, paraformer.cpp:545).  0 (default): Forward calls exactly what it calls without this.  1: models WITHOUT the head
+  // get (begin_s, end_s, is_sil) spans from the fire frames of the scan (pfhip_offline_forward_detail -> pfhip_cif_timestamps, one LFR
+  // row = 60 ms of resolution); models with the head are unchanged.  2: every model gets them; a model with the head is called with all
+  // three us_* pointers NULL, which skips the head.  From the spans on, the time-stamp code runs unchanged: the eos drop,
+  // LastTimestamps(), Vector2String -> PostProcess ("<text> | <stamps>").  These are not the head's stamps and not claimed to equal
+  // them.  With an LM decoder attached to the call, FinalizeDecode(true, us_alphas, us_peaks) needs the head's traces: no CIF stamps
+  // are made then, whatever the mode.  Not a virtual: funasr::Model's table is untouched.
+  void SetCifTimestamps(int mode) { cif_ts_mode_ = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
+  int GetCifTimestamps() const { return cif_ts_mode_; }
   void SetDevice(int device) { device_ = device; }
   // the C-ABI handles underneath — the offline model and, after a 2-pass / online InitAsr, the online model that
   // ParaformerOnlineHip streams are created from (the reference's encoder_session_ / decoder_session_) — and the text mappings
@@ -223,6 +233,7 @@ class ParaformerHip : public ParaformerHipBase
   int batch_size_ = 1;
   bool has_lm_ = false;
   int nbest_k_ = 0;                        // SetNbest
+  int cif_ts_mode_ = 0;                    // SetCifTimestamps
   bool InText(int id) const;               // whether Vector2StringV2 / PostProcess keep the token of this id
   HipVocab* vocab = nullptr;               // tokens.json (paraformer.cpp:47-48)
   pfhip_host::SegDictHost* seg_dict_ = nullptr;

@@ -1,5 +1,6 @@
 #include "timestamp.h"
 
+#include <cstddef>
 #include <numeric>
 
 namespace pfhip_host {
@@ -61,6 +62,40 @@ std::vector<TimeSpan> TimestampOnnx(std::vector<float>& us_alphas, const std::ve
     for (TimeSpan& t : spans) { t.begin_s += begin_time_ms / 1000.0; t.end_s += begin_time_ms / 1000.0; }
   }
   return spans;
+}
+
+std::vector<TimeSpan> CifTimestamps(const int* fire_frame, int n_chars, int n_frames, float frame_ms, float begin_time_ms) {
+  std::vector<TimeSpan> spans;
+  if (n_chars <= 0) return spans;
+  const double kMaxTokMs = 30.0 * 20.0, kStartEndMs = 5.0 * 20.0;      // MAX_TOKEN_DURATION, START_END_THRESHOLD x the head's 20-ms grid
+  const double ms = frame_ms, maxtok = kMaxTokMs / ms, t0 = begin_time_ms / 1000.0;
+  auto sec = [&](double frames) { return (float)(frames * ms / 1000.0 + t0); };
+  double prev = 0.0;
+  for (int k = 0; k < n_chars; ++k) {
+    // (a fire frame outside 0..n_frames cannot come from the scan; clamped so that spans stay inside the audio and ordered)
+    double e = (double)fire_frame[k] + 1.0;
+    if (e > n_frames) e = n_frames;
+    if (e < prev) e = prev;
+    const double b = e - maxtok > prev ? e - maxtok : prev;
+    if (b > prev) spans.push_back({sec(prev), sec(b), true});
+    spans.push_back({sec(b), sec(e), false});
+    prev = e;
+  }
+  if ((n_frames - prev) * ms > kStartEndMs) spans.push_back({sec(prev), sec(n_frames), true});
+  else spans.back().end_s = sec(n_frames);
+  return spans;
+}
+
+CifStampStatus CifTimestampSpans(const int* fire_frame, int n_fires, int n_chars, int n_frames, float frame_ms, float begin_time_ms,
+                                 float* spans, int cap, int* n_spans) {
+  if (!n_spans || n_fires < 0 || n_chars < 0 || n_frames < 0 || cap < 0 || n_chars > n_fires || !(frame_ms > 0.f) ||
+      !(begin_time_ms >= 0.f) || (n_chars && !fire_frame))
+    return kCifBadArg;
+  const std::vector<TimeSpan> r = CifTimestamps(fire_frame, n_chars, n_frames, frame_ms, begin_time_ms);
+  *n_spans = (int)r.size();
+  if ((int)r.size() > cap || (!r.empty() && !spans)) return kCifCapacity;
+  for (size_t i = 0; i < r.size(); ++i) { spans[3 * i] = r[i].begin_s; spans[3 * i + 1] = r[i].end_s; spans[3 * i + 2] = r[i].is_sil ? 1.f : 0.f; }
+  return kCifOk;
 }
 
 }  // namespace pfhip_host

@@ -1,10 +1,11 @@
 // Harness over the 2-pass handle API (funasrruntime_hip.h), one connection fed like the websocket server feeds it
 // (websocket/bin/websocket-server-2pass.cpp:135-148: 9600-sample pieces, the last one with input_finished):
-//   tpass_infer <offline_model_dir> <online_model_dir> <vad_dir> <pcm_s16_file> [step_samples=9600] [mode=2] [punc_dir|-] [audio_fs=16000] [nbest=0]
+//   tpass_infer <offline_model_dir> <online_model_dir> <vad_dir> <pcm_s16_file> [step_samples=9600] [mode=2] [punc_dir|-] [audio_fs=16000] [nbest=0] [cif_stamps=0]
 //   (step_samples counts samples at audio_fs, as the reference server forwards each message with its audio_fs)
 // One line per call: "call <j> | online <text> | tpass <text> | stamp <stamp>".
 // nbest = 1..8 (FunTpassSetNbest, an extension) appends two fields to every line: " | online_detail <confidence>@<fire ms> ..." with one
 // entry per streamed token id of the call, and " | tpass_conf <confidence> ..." for the tokens of the second-pass text.
+// cif_stamps = 1 | 2 (FunTpassSetCifStamps, an extension): the stamp field of the second pass comes from the CIF scan's fire frames.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -14,7 +15,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 5) {
-    std::fprintf(stderr, "usage: %s offline_dir online_dir vad_dir pcm_s16_file [step] [mode] [punc_dir|-] [audio_fs] [nbest]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s offline_dir online_dir vad_dir pcm_s16_file [step] [mode] [punc_dir|-] [audio_fs] [nbest] [cif_stamps]\n", argv[0]);
     return 2;
   }
   std::map<std::string, std::string> paths;
@@ -28,6 +29,7 @@ int main(int argc, char** argv) {
   FUNASR_HANDLE h = FunTpassInit(paths, 1);
   const int nbest = argc > 9 ? std::atoi(argv[9]) : 0;
   if (h && nbest > 0) FunTpassSetNbest(h, nbest);                  // before the connection's stream is made
+  if (h && argc > 10) FunTpassSetCifStamps(h, std::atoi(argv[10]));      // the offline pass stamps from the CIF scan (an extension)
   FUNASR_HANDLE oh = FunTpassOnlineInit(h, {5, 10, 5});
   if (!h || !oh) return 1;
   std::vector<std::vector<std::string>> punc_cache(2);

@@ -18,7 +18,7 @@
 #include <unordered_map>
 #include <vector>
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 
 // word-wise multiply-xorshift over the floats' bytes, H mixed in
 inline uint64_t hotword_hash(const float* emb, size_t n_floats, int H) {
@@ -179,4 +179,4 @@ class HotwordBank {
   std::map<int, int> free_;                   // first granule -> run length
 };
 
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl

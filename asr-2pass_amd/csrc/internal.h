@@ -21,7 +21,7 @@
 #include "hotword_bank.h"
 #include "merge_queue.h"
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 
 std::string& last_error();          // thread-local, defined in pfhip.cpp
 
@@ -58,7 +58,7 @@ inline void pcm_to_f32(float* dst, PcmView src, size_t n) {
   do {                                                                                       \
     hipError_t e__ = (expr);                                                                 \
     if (e__ != hipSuccess)                                                                   \
-      return pfhip_detail::fail(PFHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
+      return pfhip_impl::fail(PFHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
 // bumped whenever a workspace buffer is (re)allocated or freed: cached hipGraphs hold raw pointers
@@ -156,18 +156,18 @@ class ResampleCache {
   std::map<std::tuple<int, int, int>, Plan> plans;
 };
 
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl
 
-using pfhip_detail::Buf;
-using pfhip_detail::Config;
-using pfhip_detail::ModelWeights;
-using pfhip_detail::PinBuf;
-using pfhip_detail::ProfRec;
+using pfhip_impl::Buf;
+using pfhip_impl::Config;
+using pfhip_impl::ModelWeights;
+using pfhip_impl::PinBuf;
+using pfhip_impl::ProfRec;
 
 struct BatchReq;
 struct StreamReq;
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 // The hotword bank of one device (on the weight owner; its contexts share it as they share the weights): the bias decoder's
 // projected K/V rows [rows][2d] of many hotword sets in one arena, addressed by row offset, so that one attention launch takes one
 // K base and one V base plus per-utterance offsets / counts.  hotword_bank.h keeps the books; `mu` covers them AND the enqueue of a
@@ -181,9 +181,16 @@ struct HwBankDev {
   int default_id = -1;                // the entry of the pfhip_set_hotwords set, pinned for as long as it is the default
   int64_t forwards = 0, sets_total = 0, sets_max = 0, percall_forwards = 0;
 };
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl
+
+namespace pfhip_impl {
+// a number no other handle of the process ever had: what a thread's note of "my last forward ran there" is matched on (an address
+// can be that of a handle destroyed since)
+inline uint64_t next_model_uid() { static std::atomic<uint64_t> n{0}; return ++n; }
+}  // namespace pfhip_impl
 
 struct pfhip_model {
+  const uint64_t uid = pfhip_impl::next_model_uid();
   int device = 0;
   hipStream_t own_stream = nullptr;
   // decoder K/V projections of a large batch run beside the (under-filled) token-side launches: pfhip.cpp enqueue_locked
@@ -200,7 +207,7 @@ struct pfhip_model {
   int range_hit = 0, debug_range_flag = 0;
   bool exact_rerun = false, last_feats_only = false;
   long long range_fallbacks = 0;
-  pfhip_detail::PcmView last_pcm{nullptr, false};               // the device buffer AND its sample format
+  pfhip_impl::PcmView last_pcm{nullptr, false};               // the device buffer AND its sample format
   std::vector<int64_t> last_off;
   std::vector<int> last_n;
   int plane_forwards = 0;                                       // forwards of this context that took the plane path (debug read-out)
@@ -216,7 +223,7 @@ struct pfhip_model {
   Buf sseg;                     // StreamSeg descriptors of a streaming batch
   Buf rs_in;                    // audio at the caller's rate, resampled into `pcm` (pfhip_offline_forward_rate, pfhip_resample)
   // resampling plans of this device (on the weight owner; contexts use their owner's)
-  std::unique_ptr<pfhip_detail::ResampleCache> rs_cache{new pfhip_detail::ResampleCache};
+  std::unique_ptr<pfhip_impl::ResampleCache> rs_cache{new pfhip_impl::ResampleCache};
   Buf kvside;                   // [dec_layers][Mp][2d]: every decoder layer's K/V projection of the encoder output (side stream)
   Buf lnstats2;                 // the decoder's second hand-off (FFN1 -> ffn_norm -> FFN2): [ML][dec_ffn / 128][2]
   Buf lnstats;                  // per-row LayerNorm statistics handed from a producing GEMM's epilogue to the consumer [M][4][2]
@@ -235,7 +242,7 @@ struct pfhip_model {
   // entries this forward has pinned
   std::vector<int> fw_hw_off, fw_hw_len, fw_pins;
   const float* fw_hwkv = nullptr;
-  std::unique_ptr<pfhip_detail::HwBankDev> hwbank{new pfhip_detail::HwBankDev};      // on the weight owner
+  std::unique_ptr<pfhip_impl::HwBankDev> hwbank{new pfhip_impl::HwBankDev};      // on the weight owner
   PinBuf h_meta, h_counts;      // pinned: the metadata uploads (two halves), the token counts [2*B]
 
   // state of the last forward
@@ -246,6 +253,13 @@ struct pfhip_model {
   // value buffers the head fills, the k the device-pointer form asks for (pfhip_set_nbest) and the max_tokens of its last fetch
   int nbest_k = 0, nbest_enqueue_k = 0, nbest_fetch_max_tokens = 0;
   Buf nb_ids, nb_logp;
+  // Fire frames (cif.hip, the sibling kernel): whether the forward being run records them (a range-guard re-run reads it again), whether
+  // the last forward did, and what the device-pointer forms ask for (pfhip_set_fire_frames; read on the handle the caller holds).  They
+  // sit behind the token counts in `counts` — [2B | M + B], laid out like the CIF's staging rows: fire nf of utterance b at
+  // row_off[b] + b + nf — and cross to the pinned `h_counts` in the one copy forward_cif makes and synchronises on anyway
+  bool want_fires = false, have_fires = false;
+  std::atomic<int> fires_enqueue{0};
+  const int32_t* host_fires() const { return h_counts.i() + 2 * B; }
   // device views into meta / dmeta
   int *m_frame_off = nullptr, *m_nframes = nullptr, *m_row_off = nullptr, *m_len = nullptr,
       *m_row_pos = nullptr, *m_row_len = nullptr;
@@ -255,11 +269,11 @@ struct pfhip_model {
   // cross-request batching (pfhip_set_batching): callers queue at the handle they hold (ONE queue for every execution slot of
   // the handle: contexts on this device, replicas on other devices); the caller at the front leads a merged forward on an idle
   // slot while the next one already gathers the next batch (merge_queue.h PoolQueue)
-  pfhip_detail::PoolQueue<BatchReq, pfhip_model> bq;
+  pfhip_impl::PoolQueue<BatchReq, pfhip_model> bq;
   int batch_wait_us = 0, batch_max_utts = 32;
   long long format_splits = 0;              // on the head, under bq.mu: picks that left callers of the other sample format queued
   // the same for streaming calls: concurrent pfhip_stream_forward callers (one thread per connection) are merged
-  pfhip_detail::MergeQueue<StreamReq> sq;
+  pfhip_impl::MergeQueue<StreamReq> sq;
   int stream_wait_us = 0, stream_max = 128;
   std::atomic<int> live_streams{0};     // open pfhip_streams: a leader stops waiting once all of them have queued
 
@@ -296,16 +310,16 @@ struct pfhip_model {
   ~pfhip_model();
 };
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 inline pfhip_model* route_stream(pfhip_model* m) {
   pfhip_model* best = m;
   for (pfhip_model* r : m->replicas)
     if (r->live_streams.load() < best->live_streams.load()) best = r;
   return best;
 }
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 
 struct Scope {
   pfhip_model* m; hipStream_t s; int cls; hipEvent_t e1 = nullptr;
@@ -360,4 +374,4 @@ inline void lnorm(pfhip_model* m, hipStream_t s, const float* x, int ldx, float*
   pfhip::launch_layernorm(x, ldx, y, ldy, n.g, n.b, M, D, Dout, 1e-12f, s);
 }
 
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl

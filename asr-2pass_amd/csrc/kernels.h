@@ -259,9 +259,11 @@ void launch_alpha(const float* o, int ldo, const float* w, const float* b, float
 // CIF integrate-and-fire per utterance (paraformer-online.cpp:301-327) with the tail slot
 // (alpha = tail, hidden = 0) appended.  Writes fired frames to stage[(row_off[b]+b+n)][0..D),
 // n_fires[b], token_num[b] = floor(sequential fp32 sum of alphas incl. tail).
+// fire_frame (optional, [sum len + B] ints): the sibling kernel that also stores the step each token fired in, fire nf of
+// utterance b at row_off[b] + b + nf (0..len-1 an LFR row, len the tail slot); NULL launches exactly the default kernel
 void launch_cif(const float* hidden, int ldh, const float* alphas, const int* row_off,
                 const int* len, int B, int D, float threshold, float tail, float* stage,
-                int* n_fires, int* token_num, hipStream_t s);
+                int* n_fires, int* token_num, hipStream_t s, int* fire_frame = nullptr);
 // emb[tok_off[b]+n] = stage[row_off[b]+b+n]
 void launch_compact(const float* stage, float* emb, const int* tok_row_src, int ML, int D,
                     hipStream_t s);

@@ -11,7 +11,7 @@
 #include <mutex>
 #include <vector>
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 
 struct MergeReqBase {
   std::condition_variable cv;
@@ -128,4 +128,4 @@ struct PoolQueue {
   }
 };
 
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl

@@ -13,7 +13,7 @@ struct pfhip_container {
 };
 
 namespace {
-using pfhip_detail::fail;
+using pfhip_impl::fail;
 
 const char* nz(const char* s) { return s ? s : ""; }
 

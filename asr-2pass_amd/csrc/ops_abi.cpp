@@ -266,6 +266,12 @@ int pfhip_op_cif(const float* hidden, int ldh, const float* alphas, const int* r
   pfhip::launch_cif(hidden, ldh, alphas, row_off, len, B, D, threshold, tail, stage, n_fires, token_num, S(stream));
   return done();
 }
+int pfhip_op_cif_fires(const float* hidden, int ldh, const float* alphas, const int* row_off, const int* len, int B, int D,
+                       float threshold, float tail, float* stage, int* n_fires, int* token_num, int* fire_frame, void* stream) {
+  if (D > 1024 || !fire_frame) return (int)hipErrorInvalidValue;
+  pfhip::launch_cif(hidden, ldh, alphas, row_off, len, B, D, threshold, tail, stage, n_fires, token_num, S(stream), fire_frame);
+  return done();
+}
 int pfhip_op_logsoftmax_argmax(const float* logits, int ldl, int ML, int V, float* logp, int32_t* ids, void* stream) {
   pfhip::launch_logsoftmax_argmax(logits, ldl, ML, V, logp, ids, S(stream));
   return done();

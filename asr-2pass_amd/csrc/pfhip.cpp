@@ -18,6 +18,7 @@
 #include <fstream>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <sstream>
 #include <string>
 #include <unordered_map>
@@ -27,7 +28,7 @@
 #include "launch_common.h"
 #include "json_min.h"
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 std::atomic<uint64_t>& buf_epoch() {
   static std::atomic<uint64_t> e{1};
   return e;
@@ -36,11 +37,11 @@ std::string& last_error() {
   thread_local std::string e;
   return e;
 }
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl
 
 namespace {
-using namespace pfhip_detail;
-#define g_err (pfhip_detail::last_error())
+using namespace pfhip_impl;
+#define g_err (pfhip_impl::last_error())
 
 // ---- front-end tables, computed exactly like knf does on the host --------------------------------
 void build_mel(int num_bins, float sample_freq, std::vector<int>& off, std::vector<int>& size,
@@ -79,7 +80,7 @@ void build_mel(int num_bins, float sample_freq, std::vector<int>& off, std::vect
 
 }  // namespace
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 // knf tables exactly as the reference's host code computes them (feature-window.cc:33-42,
 // mel-computations.cc:107-196) + the FFT twiddles of the device kernel.
 pfhip_status build_frontend_tables(int n_mels, int sample_rate, FrontendTables* ft) {
@@ -99,10 +100,10 @@ pfhip_status build_frontend_tables(int n_mels, int sample_rate, FrontendTables* 
   HIP_TRY(ft->mel_w.upload(mw));
   return PFHIP_OK;
 }
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl
 
 namespace {
-using namespace pfhip_detail;
+using namespace pfhip_impl;
 
 pfhip_status create_streams(pfhip_model* m);
 
@@ -550,7 +551,7 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   }
   // ---- front-end tables ------------------------------------------------------------------------------
   {
-    pfhip_status st = pfhip_detail::build_frontend_tables(c.n_mels, c.sample_rate, &w->ft);
+    pfhip_status st = pfhip_impl::build_frontend_tables(c.n_mels, c.sample_rate, &w->ft);
     if (st) return st;
     const int half = w->feat_dim / 2;
     std::vector<float> inv(half);
@@ -619,7 +620,7 @@ pfhip_model::~pfhip_model() {
 }
 
 namespace {
-using namespace pfhip_detail;
+using namespace pfhip_impl;
 
 pfhip_status read_file(const char* path, std::vector<char>& out) {
   std::ifstream f(path, std::ios::binary | std::ios::ate);
@@ -727,6 +728,7 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
   m->last_off.assign(sample_off, sample_off + B);
   m->last_n.assign(n_samples, n_samples + B);
   m->last_feats_only = feats_only;
+  m->have_fires = false;
 
   // ---- workspace ---------------------------------------------------------------------------------------
   HIP_TRY(m->feats.ensure((size_t)Mp * FD * 4));
@@ -740,8 +742,9 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
     HIP_TRY(m->hbuf.ensure((size_t)(Mp + B + 128) * std::max(c.ffn, d) * 4));
     HIP_TRY(m->enc.ensure((size_t)Mp * d * 4));
     HIP_TRY(m->alphas.ensure((size_t)Mp * 4));
-    HIP_TRY(m->counts.ensure((size_t)2 * B * 4));
-    HIP_TRY(m->h_counts.ensure((size_t)2 * B * 4));
+    const size_t n_counts = (size_t)2 * B + (m->want_fires ? (size_t)M + B : 0);      // + the fire frames, where asked for
+    HIP_TRY(m->counts.ensure(n_counts * 4));
+    HIP_TRY(m->h_counts.ensure(n_counts * 4));
   }
 
   // ---- a2+a3: fbank -> LFR -> CMVN -----------------------------------------------------------------------
@@ -911,13 +914,16 @@ pfhip_status forward_cif(pfhip_model* m, hipStream_t s) {
     pfhip::launch_alpha(po, d, w.pred.out_w, w.pred.out_b, c.smooth_factor, c.noise_threshold, m->alphas.f(), M, d, s);
   }
   float* stage = m->hbuf.f();       // [(M+B), d] reused
+  // fire frames asked for: the sibling kernel, which also stores the step of every fire, behind the counts
+  int* fire = m->want_fires ? m->counts.i() + 2 * B : nullptr;
   {
     Scope sc(m, s, K_CIF, 2.0 * M * d, 4.0 * M * d);
     pfhip::launch_cif(m->enc.f(), d, m->alphas.f(), m->m_row_off, m->m_len, B, d, c.cif_threshold, c.tail_threshold,
-                      stage, m->counts.i(), m->counts.i() + B, s);
+                      stage, m->counts.i(), m->counts.i() + B, s, fire);
   }
+  m->have_fires = fire != nullptr;
   const int* h_counts = m->h_counts.i();
-  HIP_TRY(hipMemcpyAsync(m->h_counts.p, m->counts.p, (size_t)2 * B * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(m->h_counts.p, m->counts.p, ((size_t)2 * B + (fire ? (size_t)M + B : 0)) * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));      // the one host sync: token counts size the decoder launch
   int ML = 0;
   for (int b = 0; b < B; ++b) {
@@ -1308,16 +1314,17 @@ pfhip_status read_range_flag(pfhip_model* m, hipStream_t s, bool sync) {
   return PFHIP_OK;
 }
 
-pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb);
+pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_detail* dt);
 // The guard of the fp16 two-plane domain (kernels.h LaunchCtx): a forward whose range flag came back raised — a LayerNorm-folded
 // row whose centred std is outside [2^-8, 2^11] or whose |mean| / std exceeds kLnOffsetMax, or a log-prob row that is not finite — is
 // redone ONCE, inside the same context, on the exact kernels (bf16 three-plane GEMMs and attention, fp32 operands instead of plane
 // images, LayerNorm kernels instead of the fold), and counted
 // (pfhip_debug_poke "range_fallbacks").  The reference computes in plain fp32 (paraformer.cpp:496-541).
-// nb (may be null): the caller's candidate buffers, nb->k <= m->nbest_k; the exact re-run's head produces the candidates again
-// (head_locked reads m->nbest_k), so what comes back belongs to the forward whose token_ids come back
-pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb = nullptr) {
-  pfhip_status st = fetch_once(m, out, s, nb);
+// dt (may be null): the caller's candidate buffers, dt->nbest_k <= m->nbest_k, and / or its fire-frame buffer; the exact re-run's head
+// produces the candidates again (head_locked reads m->nbest_k) and its scan the fire frames (forward_cif reads m->want_fires), so what
+// comes back belongs to the forward whose token_ids come back
+pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_detail* dt = nullptr) {
+  pfhip_status st = fetch_once(m, out, s, dt);
   if (st || !m->range_hit || m->exact_rerun || m->weights->always_exact || !m->last_pcm.p || m->last_feats_only) return st;
   ++m->range_fallbacks;
   m->exact_rerun = true;
@@ -1325,12 +1332,12 @@ pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const p
   const std::vector<int> ns = m->last_n;
   st = enqueue_locked(m, m->last_pcm, off.data(), ns.data(), (int)ns.size(), s, false);      // the saved view: pointer and format
   if (!st) st = head_locked(m, s, out->logp != nullptr);
-  if (!st) st = fetch_once(m, out, s, nb);
+  if (!st) st = fetch_once(m, out, s, dt);
   m->exact_rerun = false;
   return st;
 }
 
-// the first nb->k of the m->nbest_k candidates of every token row, utterance b at row b * max_tokens of the caller's buffers; staged
+// the first k of the m->nbest_k candidates of every token row, utterance b at row b * max_tokens of the caller's buffers; staged
 // on the host like the ids (tok rows x k x 8 bytes)
 struct NbestStage {
   std::vector<int32_t> ids; std::vector<float> logp;
@@ -1340,20 +1347,29 @@ struct NbestStage {
     HIP_TRY(hipMemcpyAsync(logp.data(), m->nb_logp.p, logp.size() * 4, hipMemcpyDeviceToHost, s));
     return PFHIP_OK;
   }
-  void scatter(const pfhip_model* m, const pfhip_nbest* nb, int max_tokens) const {      // after the synchronise
-    const int kc = m->nbest_k, k = nb->k;
+  void scatter(const pfhip_model* m, int k, int32_t* dst_ids, float* dst_logp, int max_tokens) const {      // after the synchronise
+    const int kc = m->nbest_k;
     for (int b = 0; b < m->B; ++b)
       for (int t = 0; t < m->n_fires[b]; ++t) {
         const size_t src = ((size_t)m->tok_off[b] + t) * kc, dst = ((size_t)b * max_tokens + t) * k;
-        std::memcpy(nb->ids + dst, ids.data() + src, 4 * (size_t)k);
-        std::memcpy(nb->logp + dst, logp.data() + src, 4 * (size_t)k);
+        std::memcpy(dst_ids + dst, ids.data() + src, 4 * (size_t)k);
+        std::memcpy(dst_logp + dst, logp.data() + src, 4 * (size_t)k);
       }
   }
 };
+// the fire frames of the last forward (on the host since forward_cif's synchronise: pfhip_model::host_fires), utterance b at row
+// b * max_tokens of the caller's buffer
+void scatter_fires(const pfhip_model* m, int32_t* dst, int max_tokens) {
+  for (int b = 0; b < m->B; ++b)
+    if (m->n_fires[b]) std::memcpy(dst + (size_t)b * max_tokens, m->host_fires() + m->row_off[b] + b, 4 * (size_t)m->n_fires[b]);
+}
 
-pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_nbest* nb) {
+pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_detail* dt) {
   if (!out) return fail(PFHIP_ERR_ARG, "null out");
-  if (nb && (nb->k < 1 || nb->k > m->nbest_k || !nb->ids || !nb->logp)) return fail(PFHIP_ERR_ARG, "bad nbest argument");
+  const int nk = dt ? dt->nbest_k : 0;
+  int32_t* fire = dt ? dt->fire_frame : nullptr;
+  if (nk && (nk < 1 || nk > m->nbest_k || !dt->nbest_ids || !dt->nbest_logp)) return fail(PFHIP_ERR_ARG, "bad nbest argument");
+  if (fire && m->M > 0 && !m->have_fires) return fail(PFHIP_ERR_ARG, "the forward recorded no fire frames");
   m->nbest_fetch_max_tokens = out->max_tokens;
   ForwardCtx fc(m);
   const int B = m->B;
@@ -1396,7 +1412,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
     }
     return PFHIP_OK;
   }
-  if ((out->token_ids || out->logp || nb) && out->max_tokens < m->maxL)
+  if ((out->token_ids || out->logp || nk || fire) && out->max_tokens < m->maxL)
     return fail(PFHIP_ERR_CAPACITY, "max_tokens smaller than the longest token sequence");
   if (out->logp && !m->have_logp) {
     pfhip_status st = head_locked(m, s, true);
@@ -1408,7 +1424,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
     HIP_TRY(hipMemcpyAsync(ids.data(), m->ids.p, (size_t)m->ML * 4, hipMemcpyDeviceToHost, s));
   }
   NbestStage nbs;
-  if (nb) { const pfhip_status ns = nbs.start(m, s); if (ns) return ns; }
+  if (nk) { const pfhip_status ns = nbs.start(m, s); if (ns) return ns; }
   const int V = m->weights->cfg.vocab;
   if (out->logp) {
     for (int b = 0; b < B; ++b)
@@ -1425,7 +1441,8 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
   if (out->token_ids)
     for (int b = 0; b < B; ++b)
       std::memcpy(out->token_ids + (size_t)b * out->max_tokens, ids.data() + m->tok_off[b], 4 * (size_t)m->n_fires[b]);
-  if (nb) nbs.scatter(m, nb, out->max_tokens);
+  if (nk) nbs.scatter(m, nk, dt->nbest_ids, dt->nbest_logp, out->max_tokens);
+  if (fire) scatter_fires(m, fire, out->max_tokens);
   return PFHIP_OK;
 }
 
@@ -1645,7 +1662,7 @@ pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, 
   int64_t tin = 0, tout = 0;
   for (int b = 0; b < B; ++b) {
     if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
-    const int64_t no = pfhip_detail::resample_out_len(fs_in, m->weights->cfg.sample_rate, n_samples[b]);
+    const int64_t no = pfhip_impl::resample_out_len(fs_in, m->weights->cfg.sample_rate, n_samples[b]);
     if (no < 0 || no > INT32_MAX) return fail(PFHIP_ERR_ARG, "resampled utterance too long");
     in_off[b] = tin;
     tin += (n_samples[b] + 3) & ~3;
@@ -1781,6 +1798,34 @@ int pfhip_feat_dim(const pfhip_model* m) { return m ? m->weights->feat_dim : 0; 
 int pfhip_d_model(const pfhip_model* m) { return m ? m->weights->cfg.d_model : 0; }
 int pfhip_head_dim(const pfhip_model* m) { return m && m->weights->cfg.n_head > 0 ? m->weights->cfg.d_model / m->weights->cfg.n_head : 0; }
 
+// The fire frames of the calling thread's last pfhip_offline_fetch / pfhip_offline_forward_resident, for pfhip_offline_fetch_fire_frames:
+// copied out of the execution slot while its lock is still held, into storage the thread owns, already laid out by that call's batch and
+// max_tokens (per utterance its count and its frames).  On a shared handle another thread may take the slot the moment the lock is
+// gone; what this thread reads later is its own call's, and no slot state.  Matched on the handle's uid, not its address.
+namespace {
+struct ThreadFires {
+  uint64_t head_uid = 0;
+  bool recorded = false;            // the forward ran with fire frames on
+  bool laid_out = false;            // ... and the call's max_tokens had room for its longest token sequence
+  int max_tokens = 0;
+  std::vector<int32_t> n, frames;   // [B], [B * max_tokens]
+};
+thread_local ThreadFires tl_fires;
+// under m->mu, after a successful fetch_locked(m, out, ...)
+void keep_thread_fires(const pfhip_model* head, const pfhip_model* m, const pfhip_out* out) {
+  ThreadFires& t = tl_fires;
+  t.head_uid = head->uid;
+  t.recorded = m->want_fires;
+  t.max_tokens = out->max_tokens;
+  t.n.clear(); t.frames.clear();
+  t.laid_out = m->ML == 0 || out->max_tokens >= m->maxL;
+  if (!t.recorded || m->ML == 0 || !t.laid_out) return;
+  t.n.assign(m->n_fires.begin(), m->n_fires.begin() + m->B);
+  t.frames.assign((size_t)m->B * out->max_tokens, 0);
+  scatter_fires(m, t.frames.data(), out->max_tokens);
+}
+}  // namespace
+
 static pfhip_status offline_enqueue(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                                     int batch, void* stream) {
   g_err.clear();
@@ -1795,6 +1840,7 @@ static pfhip_status offline_enqueue(pfhip_model* m, PcmView d_pcm, const int64_t
   pfhip_status st = resolve_default_hotwords_locked(m, batch, s);
   if (st) return st;
   m->nbest_k = m->nbest_enqueue_k;         // pfhip_set_nbest
+  m->want_fires = m->fires_enqueue.load() != 0;      // pfhip_set_fire_frames
   st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
   if (st) return st;
   return head_locked(m, s, false);
@@ -1814,7 +1860,9 @@ pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out) {
   if (!m) return fail(PFHIP_ERR_ARG, "null model");
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
-  return fetch_locked(m, out, m->prof_stream ? m->prof_stream : m->own_stream);
+  const pfhip_status st = fetch_locked(m, out, m->prof_stream ? m->prof_stream : m->own_stream);
+  if (!st) keep_thread_fires(m, m, out);      // for pfhip_offline_fetch_fire_frames
+  return st;
 }
 
 // fs_in: the rate of `pcm` when it is not the model's (resampled into the slot's PCM workspace first), else 0
@@ -1822,13 +1870,14 @@ pfhip_status pfhip_offline_fetch(pfhip_model* m, pfhip_out* out) {
 struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
 
 static pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch,
-                                   const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_nbest* nb = nullptr) {
+                                   const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_detail* dt = nullptr) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
   m->prof_stream = s;
-  if (nb && nb->k > m->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k larger than the vocabulary");      // before any launch
-  m->nbest_k = nb ? nb->k : 0;
+  if (dt && dt->nbest_k > m->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k larger than the vocabulary");      // before any launch
+  m->nbest_k = dt ? dt->nbest_k : 0;
+  m->want_fires = dt && dt->fire_frame;
   HotwordPins pins{m};              // held until the results (a range-guard re-run included) are back
   {
     const pfhip_status hs = resolve_hotwords_locked(m, hw.emb, hw.n, hw.n_sets, hw.of_utt, batch, s);
@@ -1843,7 +1892,7 @@ static pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sam
   if (st) return st;
   st = head_locked(m, s, out->logp != nullptr);
   if (st) return st;
-  return fetch_locked(m, out, s, nb);
+  return fetch_locked(m, out, s, dt);
 }
 
 // ---- execution slots -----------------------------------------------------------------------------------------------
@@ -1895,10 +1944,10 @@ static void release_slot(pfhip_model* head, pfhip_model* slot) {
 // Results are those of separate calls up to the near-tie statement the tests make (packed layout, per-utterance masks:
 // tests/test_gpu_forward.py::test_batch_composition_invariance — a merged forward may run another kernel family than a lone one,
 // the same sums in another order, 1e-6 apart in the log-probabilities).
-struct BatchReq : pfhip_detail::MergeReqBase {
+struct BatchReq : pfhip_impl::MergeReqBase {
   HostPcm pcm{static_cast<const float* const*>(nullptr)}; const int* n; int batch; pfhip_out* out;
   HwSets hw{nullptr, nullptr, 0, nullptr};          // the caller's hotword sets (contextual models)
-  const pfhip_nbest* nb = nullptr;                  // the caller's candidate buffers (pfhip_offline_forward_nbest), or none
+  const pfhip_detail* dt = nullptr;                 // the caller's candidate / fire-frame buffers (pfhip_offline_forward_detail), or none
   pfhip_status st = PFHIP_OK; std::string err;
 };
 
@@ -1907,6 +1956,7 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
   std::vector<const void*> ptrs; std::vector<int> lens;
   bool want_logp = false, want_us = false; int max_tok = 1, utts = 0;
   int kmax = 0;      // the packed forward computes the largest k among its callers; the order makes every prefix a caller's own answer
+  bool want_fires = false;      // ... and records fire frames when any of them asks; each receives its own utterances' rows
   // Contextual model: the callers' hotword sets, deduplicated (one connection sends the same list with each of its segments; the
   // bank then matches by content), and for every packed utterance the index of its set.  A caller without hotwords fails alone
   // with the reference's "hw_emb is null" (paraformer.cpp:516-520); its company is served.
@@ -1934,7 +1984,7 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
   for (BatchReq* r : take) {
     for (int i = 0; i < r->batch; ++i) { ptrs.push_back(r->pcm.p[i]); lens.push_back(r->n[i]); max_tok = std::max(max_tok, r->n[i] / 960 + 2); }
     want_logp = want_logp || r->out->logp != nullptr;
-    if (r->nb) kmax = std::max(kmax, (int)r->nb->k);
+    if (r->dt) { kmax = std::max(kmax, (int)r->dt->nbest_k); want_fires = want_fires || r->dt->fire_frame; }
     want_us = want_us || r->out->us_alphas || r->out->us_peaks || r->out->us_len;
     utts += r->batch;
   }
@@ -1951,9 +2001,11 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
   }
   std::vector<int32_t> nbi; std::vector<float> nbl;
   if (kmax) { nbi.resize((size_t)utts * max_tok * kmax); nbl.resize(nbi.size()); }
-  const pfhip_nbest nb_all{kmax, nbi.data(), nbl.data()};
+  std::vector<int32_t> fire_all(want_fires ? (size_t)utts * max_tok : 0);
+  const pfhip_detail dt_all{kmax, kmax ? nbi.data() : nullptr, kmax ? nbl.data() : nullptr, want_fires ? fire_all.data() : nullptr};
   const HwSets sets{set_emb.data(), set_n.data(), (int)set_emb.size(), set_of.data()};
-  pfhip_status st = forward_direct(m, HostPcm(ptrs.data(), take.front()->pcm.s16), lens.data(), utts, sets, &all, 0, kmax ? &nb_all : nullptr);
+  pfhip_status st = forward_direct(m, HostPcm(ptrs.data(), take.front()->pcm.s16), lens.data(), utts, sets, &all, 0,
+                                   kmax || want_fires ? &dt_all : nullptr);
   const std::string err = g_err;
   int u0 = 0;
   for (BatchReq* r : take) {
@@ -1964,17 +2016,20 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
       if (o->token_num) o->token_num[i] = tn[u];
       if (o->n_fires) o->n_fires[i] = nf[u];
       if (o->n_frames) o->n_frames[i] = fr[u];
-      if ((o->token_ids || o->logp || r->nb) && o->max_tokens < nf[u]) {
+      const int rk = r->dt ? r->dt->nbest_k : 0;
+      int32_t* rfire = r->dt ? r->dt->fire_frame : nullptr;
+      if ((o->token_ids || o->logp || rk || rfire) && o->max_tokens < nf[u]) {
         r->st = PFHIP_ERR_CAPACITY; r->err = "max_tokens smaller than the longest token sequence"; break;
       }
       if (o->token_ids) std::memcpy(o->token_ids + (size_t)i * o->max_tokens, ids.data() + (size_t)u * max_tok, 4 * (size_t)nf[u]);
       if (o->logp) std::memcpy(o->logp + (size_t)i * o->max_tokens * V, logp.data() + (size_t)u * max_tok * V, 4 * (size_t)nf[u] * V);
-      if (r->nb)
+      if (rk)
         for (int t = 0; t < nf[u]; ++t) {
-          const size_t src = ((size_t)u * max_tok + t) * kmax, dst = ((size_t)i * o->max_tokens + t) * r->nb->k;
-          std::memcpy(r->nb->ids + dst, nbi.data() + src, 4 * (size_t)r->nb->k);
-          std::memcpy(r->nb->logp + dst, nbl.data() + src, 4 * (size_t)r->nb->k);
+          const size_t src = ((size_t)u * max_tok + t) * kmax, dst = ((size_t)i * o->max_tokens + t) * rk;
+          std::memcpy(r->dt->nbest_ids + dst, nbi.data() + src, 4 * (size_t)rk);
+          std::memcpy(r->dt->nbest_logp + dst, nbl.data() + src, 4 * (size_t)rk);
         }
+      if (rfire && nf[u]) std::memcpy(rfire + (size_t)i * o->max_tokens, fire_all.data() + (size_t)u * max_tok, 4 * (size_t)nf[u]);
       if (o->us_alphas || o->us_peaks || o->us_len) {
         if (o->us_len) o->us_len[i] = usl[u];
         if ((o->us_alphas || o->us_peaks) && o->max_us < usl[u]) { r->st = PFHIP_ERR_CAPACITY; r->err = "max_us smaller than 3 x frames"; break; }
@@ -1992,9 +2047,9 @@ namespace { thread_local pfhip_model* tl_last_replica = nullptr; }      // where
 // that format (in order) and leaves the others, in order, for the next leader.  Nothing is converted on the host, every caller gets
 // the results of a forward in its own format, which are those of the other format bit for bit.
 static pfhip_status forward_batched(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch,
-                                    const HwSets& hw, pfhip_out* out, const pfhip_nbest* nb) {
+                                    const HwSets& hw, pfhip_out* out, const pfhip_detail* dt) {
   BatchReq me;
-  me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out; me.hw = hw; me.nb = nb;
+  me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out; me.hw = hw; me.dt = dt;
   int wait_us, max_utts;
   { std::lock_guard<std::mutex> l(head->bq.mu); wait_us = head->batch_wait_us; max_utts = head->batch_max_utts; }
   pfhip_model* ran_on = nullptr;
@@ -2038,25 +2093,35 @@ static pfhip_status forward_batched(pfhip_model* head, HostPcm pcm, const int* n
   return me.st;
 }
 
+// dt: candidates and / or fire frames beside `out` (nbest_k = 0: no candidates), or null.  rate: the rate of `pcm`, none or the model's
+// own for audio at the model's rate; another rate is resampled on the device into the slot's PCM workspace and runs alone (one rate
+// pair per packed batch)
 static pfhip_status offline_forward_sets(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const HwSets& hw,
-                                         pfhip_out* out, const pfhip_nbest* nb = nullptr) {
+                                         pfhip_out* out, const pfhip_detail* dt = nullptr, std::optional<int> rate = std::nullopt) {
   g_err.clear();
   if (!head || !pcm.p || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (nb && (nb->k < 1 || nb->k > pfhip::kTopkMax || nb->k > head->weights->cfg.vocab || !nb->ids || !nb->logp))
+  if (dt && dt->nbest_k && (dt->nbest_k < 1 || dt->nbest_k > pfhip::kTopkMax || dt->nbest_k > head->weights->cfg.vocab || !dt->nbest_ids ||
+                            !dt->nbest_logp))
     return fail(PFHIP_ERR_ARG, "nbest: k outside 1..8 (or above the vocabulary) or a null buffer");
   for (int i = 0; i < batch; ++i)
     if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm.p[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+  const bool other_rate = rate && *rate != head->weights->cfg.sample_rate;
+  if (other_rate) {
+    std::string why;
+    if (!pfhip_impl::resample_supported(*rate, head->weights->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
+  }
+  const int fs_in = other_rate ? *rate : 0;      // forward_direct: 0 = no resampling
   // merged with whoever else is calling: plain and timestamp models always; contextual models — every caller with its own hotword
   // sets, each utterance attending to its own set in the packed forward — where pfhip_set_hotword_merging is on
   bool merge;
   {
     std::lock_guard<std::mutex> l(head->bq.mu);
-    merge = head->batch_wait_us > 0 && batch < head->batch_max_utts && (!head->weights->cfg.contextual || head->hw_merge);
+    merge = !fs_in && head->batch_wait_us > 0 && batch < head->batch_max_utts && (!head->weights->cfg.contextual || head->hw_merge);
   }
-  if (merge) return forward_batched(head, pcm, n_samples, batch, hw, out, nb);
+  if (merge) return forward_batched(head, pcm, n_samples, batch, hw, out, dt);
   pfhip_model* m = acquire_slot(head);                  // the least-loaded execution slot (context / GPU)
   tl_last_replica = m;
-  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out, 0, nb);
+  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out, fs_in, dt);
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
   return st;
@@ -2106,7 +2171,32 @@ static pfhip_status offline_forward_nbest(pfhip_model* head, HostPcm pcm, const 
     return fail(PFHIP_ERR_ARG, "bad argument");
   }
   const HwSets hw{hw_emb, n_hotwords, n_sets < 0 ? 0 : n_sets, set_of_utt};
-  return offline_forward_sets(head, pcm, n_samples, batch, hw, out, nb);
+  if (!nb) return offline_forward_sets(head, pcm, n_samples, batch, hw, out);
+  if (nb->k < 1) { g_err.clear(); return fail(PFHIP_ERR_ARG, "nbest: k outside 1..8 (or above the vocabulary) or a null buffer"); }
+  const pfhip_detail dt{nb->k, nb->ids, nb->logp, nullptr};
+  return offline_forward_sets(head, pcm, n_samples, batch, hw, out, &dt);
+}
+
+// the hwsets form with a pfhip_detail (candidates and / or fire frames) and the rate of the audio
+static pfhip_status offline_forward_detail(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, int sample_rate,
+                                           const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                           pfhip_out* out, const pfhip_detail* dt) {
+  if (head && head->weights->cfg.contextual && n_sets > 0 && (!hw_emb || !n_hotwords || !set_of_utt)) {
+    g_err.clear();
+    return fail(PFHIP_ERR_ARG, "bad argument");
+  }
+  const HwSets hw{hw_emb, n_hotwords, n_sets < 0 ? 0 : n_sets, set_of_utt};
+  return offline_forward_sets(head, pcm, n_samples, batch, hw, out, dt, sample_rate == 0 ? std::nullopt : std::optional<int>(sample_rate));      // 0 = the model's
+}
+pfhip_status pfhip_offline_forward_detail(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                          pfhip_out* out, const pfhip_detail* dt) {
+  return offline_forward_detail(head, pcm, n_samples, batch, sample_rate, hw_emb, n_hotwords, n_sets, set_of_utt, out, dt);
+}
+pfhip_status pfhip_offline_forward_detail_s16(pfhip_model* head, const int16_t* const* pcm, const int* n_samples, int batch,
+                                              int sample_rate, const float* const* hw_emb, const int* n_hotwords, int n_sets,
+                                              const int* set_of_utt, pfhip_out* out, const pfhip_detail* dt) {
+  return offline_forward_detail(head, pcm, n_samples, batch, sample_rate, hw_emb, n_hotwords, n_sets, set_of_utt, out, dt);
 }
 pfhip_status pfhip_offline_forward_nbest(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch,
                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
@@ -2143,9 +2233,33 @@ pfhip_status pfhip_offline_fetch_nbest(pfhip_model* m, const pfhip_nbest* nb) {
   const pfhip_status st = nbs.start(m, s);
   if (st) return st;
   HIP_TRY(hipStreamSynchronize(s));
-  nbs.scatter(m, nb, m->nbest_fetch_max_tokens);
+  nbs.scatter(m, nb->k, nb->ids, nb->logp, m->nbest_fetch_max_tokens);
   return PFHIP_OK;
 }
+
+// device-pointer forms: fire frames for the following pfhip_offline_enqueue / pfhip_offline_forward_resident calls of this handle
+pfhip_status pfhip_set_fire_frames(pfhip_model* m, int on) {
+  g_err.clear();
+  if (!m) return fail(PFHIP_ERR_ARG, "null model");
+  m->fires_enqueue.store(on != 0);
+  return PFHIP_OK;
+}
+
+// the fire frames of the calling thread's last pfhip_offline_fetch / pfhip_offline_forward_resident on this handle (a range-guard re-run
+// included: what was kept is what the call returned): from the thread's own copy, laid out by that call's max_tokens
+pfhip_status pfhip_offline_fetch_fire_frames(pfhip_model* m, int32_t* fire_frame) {
+  g_err.clear();
+  if (!m || !fire_frame) return fail(PFHIP_ERR_ARG, "bad argument");
+  const ThreadFires& t = tl_fires;
+  if (t.head_uid != m->uid) return fail(PFHIP_ERR_ARG, "this thread has fetched no forward of this handle (pfhip_offline_fetch first)");
+  if (!t.recorded) return fail(PFHIP_ERR_ARG, "the last forward recorded no fire frames (pfhip_set_fire_frames)");
+  if (!t.laid_out) return fail(PFHIP_ERR_CAPACITY, "that call's max_tokens was smaller than its longest token sequence");
+  for (size_t b = 0; b < t.n.size(); ++b)
+    if (t.n[b]) std::memcpy(fire_frame + b * t.max_tokens, t.frames.data() + b * t.max_tokens, 4 * (size_t)t.n[b]);
+  return PFHIP_OK;
+}
+
+int pfhip_lfr_frame_ms(const pfhip_model* m) { return m ? m->weights->cfg.lfr_n * 10 : 0; }      // 10-ms frame shift (paraformer.cpp:24-31)
 
 // pfhip_offline_forward with the PCM already in HBM: same routing over the execution slots, no H2D of the audio
 static pfhip_status offline_forward_resident(pfhip_model* head, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
@@ -2163,10 +2277,12 @@ static pfhip_status offline_forward_resident(pfhip_model* head, PcmView d_pcm, c
     HotwordPins pins{m};
     st = hipSetDevice(m->device) == hipSuccess ? PFHIP_OK : fail(PFHIP_ERR_HIP, "hipSetDevice");
     m->nbest_k = 0;
+    m->want_fires = head->fires_enqueue.load() != 0;      // pfhip_set_fire_frames, on the handle the caller holds
     if (!st) st = resolve_default_hotwords_locked(m, batch, s);
     if (!st) st = enqueue_locked(m, d_pcm, sample_off, n_samples, batch, s, false);
     if (!st) st = head_locked(m, s, out->logp != nullptr);
     if (!st) st = fetch_locked(m, out, s);
+    if (!st) keep_thread_fires(head, m, out);      // while the slot is still this call's: for pfhip_offline_fetch_fire_frames
   }
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
@@ -2184,23 +2300,8 @@ pfhip_status pfhip_offline_forward_resident_s16(pfhip_model* head, const int16_t
 // pfhip_offline_forward at the caller's rate: resampled on the device into the slot's PCM workspace, then the same forward
 static pfhip_status offline_forward_rate(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, int sample_rate,
                                          const float* hw_emb, int n_hotwords, pfhip_out* out) {
-  if (head && sample_rate == head->weights->cfg.sample_rate) {
-    const HwSets same{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
-    return offline_forward_sets(head, pcm, n_samples, batch, same, out);
-  }
-  g_err.clear();
-  if (!head || !pcm.p || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
-  for (int i = 0; i < batch; ++i)
-    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm.p[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
-  std::string why;
-  if (!pfhip_detail::resample_supported(sample_rate, head->weights->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
-  pfhip_model* m = acquire_slot(head);                  // not merged with other callers: one rate pair per packed batch
-  tl_last_replica = m;
   const HwSets hw{&hw_emb, &n_hotwords, hw_emb && n_hotwords > 0 ? 1 : 0, nullptr};
-  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out, sample_rate);
-  ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
-  release_slot(head, m);
-  return st;
+  return offline_forward_sets(head, pcm, n_samples, batch, hw, out, nullptr, sample_rate);
 }
 pfhip_status pfhip_offline_forward_rate(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
                                         const float* hw_emb, int n_hotwords, pfhip_out* out) {
@@ -2218,11 +2319,11 @@ pfhip_status pfhip_resample(pfhip_model* head, const float* const* pcm, const in
   if (!head || !pcm || !n_samples || batch <= 0 || !out || !cap || !n_out) return fail(PFHIP_ERR_ARG, "bad argument");
   const int fs_out = head->weights->cfg.sample_rate;
   std::string why;
-  if (!pfhip_detail::resample_supported(fs_in, fs_out, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
+  if (!pfhip_impl::resample_supported(fs_in, fs_out, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
   bool short_cap = false;
   for (int b = 0; b < batch; ++b) {
     if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
-    const int64_t no = pfhip_detail::resample_out_len(fs_in, fs_out, n_samples[b]);
+    const int64_t no = pfhip_impl::resample_out_len(fs_in, fs_out, n_samples[b]);
     if (no > INT32_MAX) return fail(PFHIP_ERR_ARG, "resampled utterance too long");
     n_out[b] = (int)no;
     if (no > 0 && (cap[b] < no || !out[b])) short_cap = true;
@@ -2547,6 +2648,13 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   // the last forward's candidates [token rows][k] (k as it was computed); the ids are int32 words in the float buffer
   else if (nm == "nbest_ids" && m->nbest_k) { src = m->nb_ids.p; n = (size_t)m->ML * m->nbest_k; }
   else if (nm == "nbest_logp" && m->nbest_k) { src = m->nb_logp.p; n = (size_t)m->ML * m->nbest_k; }
+  else if (nm == "fire_frame" && m->have_fires) {      // [token rows], compacted from the staged layout (on the host already) and converted: small integers
+    if ((size_t)m->ML > cap_floats) return fail(PFHIP_ERR_CAPACITY, "dst too small");
+    for (int b = 0; b < m->B && m->ML; ++b)
+      for (int t = 0; t < m->n_fires[b]; ++t) dst[m->tok_off[b] + t] = (float)m->host_fires()[(size_t)m->row_off[b] + b + t];
+    if (n_out) *n_out = (size_t)m->ML;
+    return PFHIP_OK;
+  }
   else return fail(PFHIP_ERR_ARG, "unknown tensor name " + nm);
   if (n > cap_floats) return fail(PFHIP_ERR_CAPACITY, "dst too small");
   if (n) HIP_TRY(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, s));

@@ -9,7 +9,7 @@
 #include "internal.h"
 #include "json_min.h"
 
-using namespace pfhip_detail;
+using namespace pfhip_impl;
 
 namespace pfhip {
 void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int D, float* out, int ldo, int N,
@@ -17,7 +17,7 @@ void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int 
 void launch_argmax_first(const float* logits, int ldl, int N, int ncls, int32_t* out, hipStream_t s);
 }
 
-struct PuncReq : pfhip_detail::MergeReqBase {
+struct PuncReq : pfhip_impl::MergeReqBase {
   const int32_t* ids; int n; int vad_pos; int32_t* out;
   pfhip_status st = PFHIP_OK; std::string err;
 };
@@ -48,7 +48,7 @@ struct pfhip_punc {
     return h_stage;
   }
   // merging of concurrent callers (pfhip_set_punc_batching)
-  pfhip_detail::MergeQueue<PuncReq> mq;
+  pfhip_impl::MergeQueue<PuncReq> mq;
   int q_wait_us = 0, q_max = 1;
   // the device set and idle before any member gives its memory back (a create that returns early comes through here too)
   ~pfhip_punc() {

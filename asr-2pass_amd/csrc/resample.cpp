@@ -12,7 +12,7 @@
 #include "internal.h"
 #include "../../include/pfhip_ops.h"
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 namespace {
 
 constexpr int kMinRate = 1000, kMaxRate = 192000, kZeros = 6;
@@ -123,17 +123,17 @@ pfhip_status ResampleCache::get(int device, int fs_in, int fs_out, pfhip::Resamp
   return PFHIP_OK;
 }
 
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl
 
 extern "C" {
 
-int64_t pfhip_resample_len(int fs_in, int fs_out, int64_t n_in) { return pfhip_detail::resample_out_len(fs_in, fs_out, n_in); }
+int64_t pfhip_resample_len(int fs_in, int fs_out, int64_t n_in) { return pfhip_impl::resample_out_len(fs_in, fs_out, n_in); }
 
 int pfhip_op_resample_table(int fs_in, int fs_out, int32_t* first_index, int32_t* ntaps, float* weights, size_t cap_floats,
                             int* n_phases, int* taps, int* in_unit) {
-  if (!pfhip_detail::resample_supported(fs_in, fs_out, nullptr)) return (int)hipErrorInvalidValue;
-  pfhip_detail::ResamplePlan p;
-  pfhip_detail::build_resample_plan(fs_in, fs_out, &p);
+  if (!pfhip_impl::resample_supported(fs_in, fs_out, nullptr)) return (int)hipErrorInvalidValue;
+  pfhip_impl::ResamplePlan p;
+  pfhip_impl::build_resample_plan(fs_in, fs_out, &p);
   if (n_phases) *n_phases = p.Q;
   if (taps) *taps = p.K;
   if (in_unit) *in_unit = p.P;
@@ -148,13 +148,13 @@ int pfhip_op_resample_table(int fs_in, int fs_out, int32_t* first_index, int32_t
 int pfhip_op_resample(const float* d_in, const int64_t* in_off, const int* n_in, int batch, int fs_in, int fs_out, float* d_out,
                       const int64_t* out_off, void* stream) {
   // process-wide plans for the operator entry (the handle API keeps its own per handle)
-  static pfhip_detail::ResampleCache* cache = new pfhip_detail::ResampleCache;
+  static pfhip_impl::ResampleCache* cache = new pfhip_impl::ResampleCache;
   if (batch < 0 || (batch > 0 && (!in_off || !n_in || !out_off))) return (int)hipErrorInvalidValue;
-  if (!pfhip_detail::resample_supported(fs_in, fs_out, nullptr)) return (int)hipErrorInvalidValue;
+  if (!pfhip_impl::resample_supported(fs_in, fs_out, nullptr)) return (int)hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::vector<int> n_out(batch);
   for (int b = 0; b < batch; ++b) {
-    const int64_t n = pfhip_detail::resample_out_len(fs_in, fs_out, n_in[b]);
+    const int64_t n = pfhip_impl::resample_out_len(fs_in, fs_out, n_in[b]);
     if (n < 0 || n > INT_MAX) return (int)hipErrorInvalidValue;
     n_out[b] = (int)n;
   }

@@ -28,7 +28,7 @@
 #include "internal.h"
 #include "launch_common.h"
 
-using namespace pfhip_detail;
+using namespace pfhip_impl;
 
 struct pfhip_stream {
   pfhip_model* m = nullptr;
@@ -661,7 +661,7 @@ extern "C" {
 pfhip_status pfhip_stream_create(pfhip_model* m, const int* chunk_size, pfhip_stream** out) {
   last_error().clear();
   if (!m || !out) return fail(PFHIP_ERR_ARG, "null argument");
-  m = pfhip_detail::route_stream(m);           // a group: the connection lives on the replica (GPU) with the fewest open streams
+  m = pfhip_impl::route_stream(m);           // a group: the connection lives on the replica (GPU) with the fewest open streams
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   std::unique_ptr<pfhip_stream> s(new pfhip_stream);
@@ -950,8 +950,8 @@ pfhip_status pfhip_stream_forward_batch_s16(pfhip_stream* const* streams, int n_
 // (websocket-server-2pass.cpp:266-297).  With pfhip_set_stream_batching(wait_us > 0) concurrent pfhip_stream_forward callers on
 // streams of one model are merged like the offline callers (pfhip_set_batching): the first to arrive leads, waits up to
 // wait_us for others, runs ONE batched forward (forward_calls) and hands every caller its ids.
-struct StreamReq : pfhip_detail::MergeReqBase {
-  pfhip_stream* s; pfhip_detail::PcmView pcm; int n; int fin; int32_t* ids; int cap; int* n_out;      // f32 and s16 callers merge freely
+struct StreamReq : pfhip_impl::MergeReqBase {
+  pfhip_stream* s; pfhip_impl::PcmView pcm; int n; int fin; int32_t* ids; int cap; int* n_out;      // f32 and s16 callers merge freely
   pfhip_status st = PFHIP_OK; std::string err;
 };
 
@@ -966,13 +966,13 @@ void run_requests(const std::vector<StreamReq*>& reqs) {
   for (int i = 0; i < n; ++i) { ss[i] = reqs[i]->s; pcm[i] = reqs[i]->pcm; ns[i] = reqs[i]->n; fin[i] = reqs[i]->fin; ids[i] = reqs[i]->ids; cap[i] = reqs[i]->cap; }
   std::vector<pfhip_status> each(n, PFHIP_OK);
   std::vector<std::string> err(n);
-  pfhip_detail::last_error().clear();
+  pfhip_impl::last_error().clear();
   const pfhip_status st = forward_batch_each(ss.data(), n, pcm.data(), ns.data(), fin.data(), ids.data(), cap.data(), nt.data(),
                                              each.data(), err.data());
   if (st && !each.empty() && each[0] == PFHIP_OK && err[0].empty()) {      // argument-level failure before `each` was filled
     bool any = false;
     for (int i = 0; i < n; ++i) any = any || each[i] != PFHIP_OK;
-    if (!any) for (int i = 0; i < n; ++i) { each[i] = st; err[i] = pfhip_detail::last_error(); }
+    if (!any) for (int i = 0; i < n; ++i) { each[i] = st; err[i] = pfhip_impl::last_error(); }
   }
   for (int i = 0; i < n; ++i) { *reqs[i]->n_out = nt[i]; reqs[i]->st = each[i]; reqs[i]->err = err[i]; }
 }
@@ -996,7 +996,7 @@ pfhip_status stream_forward_queued(pfhip_model* m, StreamReq& me) {
         for (auto it = later.rbegin(); it != later.rend(); ++it) q.push_front(*it);
       },
       [&](std::vector<StreamReq*>& take) { run_requests(take); });
-  if (me.st != PFHIP_OK) pfhip_detail::last_error() = me.err;
+  if (me.st != PFHIP_OK) pfhip_impl::last_error() = me.err;
   return me.st;
 }
 

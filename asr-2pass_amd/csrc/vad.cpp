@@ -14,7 +14,7 @@
 #include "internal.h"
 #include "json_min.h"
 
-using namespace pfhip_detail;
+using namespace pfhip_impl;
 
 struct pfhip_vad {
   int device = 0;
@@ -32,14 +32,14 @@ struct pfhip_vad {
   // pinned staging for the online path's PCM (grown on demand); h_wave(n) returns a buffer of at least n floats
   float* h_wave_buf = nullptr; size_t h_wave_cap = 0;
   // merging of concurrent pfhip_vad_stream_infer callers (pfhip_set_vad_stream_batching)
-  pfhip_detail::MergeQueue<struct VadReq> mq;
+  pfhip_impl::MergeQueue<struct VadReq> mq;
   int q_wait_us = 0, q_max = 1;
   std::atomic<int> live_streams{0};
   // the offline forward in company (pfhip_vad_forward_sil_batch, pfhip_set_vad_batching): frame energies, the zero block that stands
   // for a fresh file's caches, whether non-final calls have left state in cache[] since the last reset, the callers' queue
   Buf eng, zcache;
   std::atomic<bool> carried{false};
-  pfhip_detail::MergeQueue<struct VadFileReq> fq;
+  pfhip_impl::MergeQueue<struct VadFileReq> fq;
   int fq_wait_us = 0, fq_max = 1;                 // guarded by fq.mu
   long long fq_passes = 0, fq_files = 0; int fq_max_seen = 0;      // guarded by mu: packed passes, their files, the fullest pass
   float* h_wave(size_t n) {
@@ -64,7 +64,7 @@ struct pfhip_vad {
 namespace {
 
 void lin_gemm(hipStream_t s, const PackedLin& l, const float* A, int lda, float* C, int ldc, int M, bool relu) {
-  pfhip_detail::lin_gemm(s, l, A, lda, C, ldc, nullptr, 0, nullptr, 0, M, relu);
+  pfhip_impl::lin_gemm(s, l, A, lda, C, ldc, nullptr, 0, nullptr, 0, M, relu);
 }
 
 }  // namespace
@@ -292,8 +292,8 @@ static pfhip_status vad_forward_impl(pfhip_vad* v, PcmView pcm, int n_samples, i
 // ---- complete files in company ----------------------------------------------------------------------------------------------
 // One caller's file of a packed pass.  Every file is scored as an is_final call on a fresh object: zeroed caches in, nothing
 // carried out (fsmn-vad.cpp:129-134), so the handle's own caches are neither read nor written.
-struct VadFileReq : pfhip_detail::MergeReqBase {
-  pfhip_detail::PcmView pcm; int n;
+struct VadFileReq : pfhip_impl::MergeReqBase {
+  pfhip_impl::PcmView pcm; int n;
   float* sil; size_t cap; int* nf; float* energy; size_t cap_e; int* ne;
   pfhip_status st = PFHIP_OK; std::string err;
 };
@@ -838,8 +838,8 @@ pfhip_status pfhip_set_vad_stream_batching(pfhip_vad* v, int wait_us, int max_st
 
 // One FsmnVadOnline::Infer per websocket handler thread (funasrruntime.cpp:516-532): with wait_us > 0 the first caller to
 // arrive leads, waits up to wait_us for the others and runs ONE pfhip_vad_stream_infer_batch for all of them.
-struct VadReq : pfhip_detail::MergeReqBase {
-  pfhip_vad_stream* vs; pfhip_detail::PcmView pcm;      // f32 and s16 callers merge freely
+struct VadReq : pfhip_impl::MergeReqBase {
+  pfhip_vad_stream* vs; pfhip_impl::PcmView pcm;      // f32 and s16 callers merge freely
   int n; int fin; float* sil; size_t cap; int* nf; float* wo; size_t wcap; int* nw;
   pfhip_status st = PFHIP_OK; std::string err;
 };
@@ -859,7 +859,7 @@ void vad_run_requests(const std::vector<VadReq*>& reqs) {
   }
   const pfhip_status st = vad_stream_infer_batch(ss.data(), n, pcm.data(), ns.data(), fin.data(), sil.data(), cap.data(),
                                                        nf.data(), wo.data(), wcap.data(), nw.data());
-  const std::string err = pfhip_detail::last_error();
+  const std::string err = pfhip_impl::last_error();
   for (int i = 0; i < n; ++i) { *reqs[i]->nf = nf[i]; *reqs[i]->nw = nw[i]; reqs[i]->st = st; reqs[i]->err = err; }
 }
 
@@ -881,7 +881,7 @@ pfhip_status vad_infer_queued(pfhip_vad* v, VadReq& me) {
         for (auto it = later.rbegin(); it != later.rend(); ++it) q.push_front(*it);
       },
       [&](std::vector<VadReq*>& take) { vad_run_requests(take); });
-  if (me.st != PFHIP_OK) pfhip_detail::last_error() = me.err;
+  if (me.st != PFHIP_OK) pfhip_impl::last_error() = me.err;
   return me.st;
 }
 

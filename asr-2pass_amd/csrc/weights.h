@@ -10,7 +10,7 @@
 
 #include "kernels.h"
 
-namespace pfhip_detail {
+namespace pfhip_impl {
 
 // A device allocation made once at load (weights, tables): exact size, move-only, freed by its destructor.
 struct DevMem {
@@ -111,4 +111,4 @@ struct ModelWeights {
   DevMem up_w, up_b, wih, bih, whh;
 };
 
-}  // namespace pfhip_detail
+}  // namespace pfhip_impl

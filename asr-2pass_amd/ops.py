@@ -34,6 +34,7 @@ def _lib():
         lib.pfhip_op_attention.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _vp]
         lib.pfhip_op_attention_hd.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _ci, _vp]
         lib.pfhip_op_cif.argtypes = [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp]
+        lib.pfhip_op_cif_fires.argtypes = [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _vp]
         lib.pfhip_op_logsoftmax_argmax.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
         lib.pfhip_op_logsoftmax_topk.argtypes = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
         lib.pfhip_op_resample.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]
@@ -277,6 +278,24 @@ def cif(hidden, alphas, row_off, length, threshold, tail):
     _ck(_lib().pfhip_op_cif(_p(hidden), hidden.stride(0), _p(alphas), _p(row_off), _p(length), B, D, threshold, tail,
                             _p(stage), _p(n_fires), _p(token_num), _stream()), "cif")
     return stage, n_fires, token_num
+
+
+def cif_fires(hidden, alphas, row_off, length, threshold, tail, fire_frame=None):
+    """cif by the sibling kernel that also writes fire_frame [rows + B] int32, laid out like stage's rows: fire j of utterance b at
+    row_off[b] + b + j holds the scan step it happened in (0..len-1 = that row, len = the tail slot); slots past n_fires[b] keep
+    what the caller put there (fire_frame given) or -1."""
+    B = row_off.numel()
+    D = hidden.shape[1]
+    stage = torch.zeros((hidden.shape[0] + B, D), dtype=torch.float32, device=hidden.device)
+    n_fires = torch.zeros(B, dtype=torch.int32, device=hidden.device)
+    token_num = torch.zeros(B, dtype=torch.int32, device=hidden.device)
+    if fire_frame is None:
+        fire_frame = torch.full((hidden.shape[0] + B,), -1, dtype=torch.int32, device=hidden.device)
+    if fire_frame.dtype != torch.int32 or fire_frame.numel() < hidden.shape[0] + B or not fire_frame.is_contiguous():
+        raise PfhipError("cif_fires: fire_frame must be a contiguous int32 tensor of rows + B entries")
+    _ck(_lib().pfhip_op_cif_fires(_p(hidden), hidden.stride(0), _p(alphas), _p(row_off), _p(length), B, D, threshold, tail,
+                                  _p(stage), _p(n_fires), _p(token_num), _p(fire_frame), _stream()), "cif_fires")
+    return stage, n_fires, token_num, fire_frame
 
 
 def logsoftmax_argmax(logits, V=None, want_logp=True):

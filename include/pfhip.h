@@ -306,6 +306,54 @@ pfhip_status pfhip_set_nbest(pfhip_model* m, int k);
  * of the k it computed.  PFHIP_ERR_ARG when the last enqueue computed none (no pfhip_set_nbest) or fewer than nb->k. */
 pfhip_status pfhip_offline_fetch_nbest(pfhip_model* m, const pfhip_nbest* nb);
 
+/* ---- fire frames: where the CIF scan completed each token (extension) --------------------------------
+ * The reference has no counterpart: its only source of token times is the CifPredictorV3 head of the 4-output graph
+ * (paraformer.cpp:545, `outputTensor.size() == 4`); a model without that head returns text only.  Every forward, however, runs the
+ * CIF scan (cif.hip), which decides frame by frame where each token's integration completes — the acoustic boundary between two
+ * tokens.  With fire frames asked for, a sibling of the scan kernel stores the step of each fire: the same statements in the same
+ * order plus one store by one lane per token, so token ids, log-probs, token_num and n_fires are bit for bit those of the forward
+ * without.  Resolution is one LFR row (pfhip_lfr_frame_ms: lfr_n x 10 ms = 60 ms) against the head's 20 ms; these are not the head's
+ * stamps.  Off (the default), every entry point launches exactly what it launches without this section.
+ *
+ * pfhip_detail: what a forward may return beside pfhip_out (pfhip_out and pfhip_nbest keep their size).
+ *   nbest_k / nbest_ids / nbest_logp   the candidates, as pfhip_nbest's k / ids / logp; nbest_k = 0 with NULL buffers = none
+ *   fire_frame [batch * max_tokens]    or NULL.  fire_frame[b*max_tokens + j], j < n_fires[b]: the LFR row (0..n_frames[b]-1) token
+ *                                      row j fired in, or n_frames[b] where the offline tail slot fired it (the trailing "</s>" row
+ *                                      usually).  Non-decreasing in j.  Rows >= n_fires[b] are untouched. */
+typedef struct {
+  int32_t nbest_k;
+  int32_t* nbest_ids;
+  float* nbest_logp;
+  int32_t* fire_frame;
+} pfhip_detail;
+/* pfhip_offline_forward_nbest with a pfhip_detail (det == NULL: exactly pfhip_offline_forward_hwsets) and the rate of the audio:
+ * sample_rate = 0 or pfhip_sample_rate(m) is the model's own; any other rate is resampled on the device as pfhip_offline_forward_rate
+ * does (and, as there, not merged with other callers).  Candidates and fire frames take every route a forward can take: merged
+ * callers (pfhip_set_batching, pfhip_set_hotword_merging) each receive their own utterances' rows, whatever the others asked for;
+ * each execution context (pfhip_set_inflight) and replica owns its buffer; after a range-guard re-run they are the re-run's, like
+ * token_ids.  Timestamp-head models: leave out's three us_* pointers NULL to skip the head.  PFHIP_ERR_ARG for a bad nbest_k / a
+ * nbest buffer missing, PFHIP_ERR_CAPACITY where max_tokens is below the longest token sequence. */
+pfhip_status pfhip_offline_forward_detail(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                          const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                          pfhip_out* out, const pfhip_detail* det);
+/* The same from 16-bit PCM (see "16-bit PCM in" above): bit for bit the f32 call fed s / 32768.f. */
+pfhip_status pfhip_offline_forward_detail_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                              const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
+                                              pfhip_out* out, const pfhip_detail* det);
+/* Device-pointer forms: on != 0 makes every following pfhip_offline_enqueue[_s16] (context 0) and pfhip_offline_forward_resident[_s16]
+ * (whichever slot runs it) of this handle record fire frames; 0 = off (default). */
+pfhip_status pfhip_set_fire_frames(pfhip_model* m, int on);
+/* fire_frame [batch * max_tokens], as in pfhip_detail, of the CALLING THREAD's last pfhip_offline_fetch or
+ * pfhip_offline_forward_resident[_s16] on this handle, laid out by that call's batch and out->max_tokens (pfhip_offline_fetch comes
+ * first, as for pfhip_offline_fetch_nbest).  Those calls copy their fire frames into storage of the calling thread before they give
+ * the execution slot up, and this call reads only that copy: threads that share a handle (what the resident form is for) each get
+ * their own call's, whatever has run on the slot since, and a fetch made on another thread is not seen here.  PFHIP_ERR_ARG when
+ * this thread has fetched no forward of the handle or that forward recorded none (no pfhip_set_fire_frames), PFHIP_ERR_CAPACITY
+ * when that call's max_tokens was below its longest token sequence. */
+pfhip_status pfhip_offline_fetch_fire_frames(pfhip_model* m, int32_t* fire_frame);
+/* Milliseconds of audio one LFR row advances: lfr_n x the 10-ms frame shift (60 for the Paraformers).  0 for a NULL handle. */
+int pfhip_lfr_frame_ms(const pfhip_model* m);
+
 /* ---- front end only ----------------------------------------------------------------------------
  * Replaces Paraformer::FbankKaldi + LfrCmvn (paraformer.cpp:309-323, 421-461) on their own:
  * feats_out gets sum(n_frames)*feat_dim floats, utterances back to back; n_frames_out [batch]. */
@@ -525,6 +573,24 @@ pfhip_status pfhip_timestamp_onnx(float* us_alphas, const float* us_cif_peak, in
  * UTF-8) + their (begin_s, end_s) stamps -> "<text> | <b0>, <e0>,<b1>, <e1>..." exactly as Paraformer::GreedySearch returns
  * it in time-stamp mode; special tokens dropped, "@@" pieces merged, Latin words spaced.  *n_out = strlen (cap >= +1). */
 pfhip_status pfhip_post_process(const char* const* chars, const float* stamps, int n, char* out, int cap, int* n_out);
+/* Token spans from fire frames (extension; the reference has no counterpart: TimestampOnnx above, fed by the head of
+ * paraformer.cpp:545, is its only source of stamps).  fire_frame [n_fires] as pfhip_detail returns it for one utterance, n_chars
+ * <= n_fires the recognised tokens to stamp (without "</s>"), n_frames the utterance's LFR rows, frame_ms = pfhip_lfr_frame_ms.
+ * Writes (begin_s, end_s, is_sil) triplets exactly as pfhip_timestamp_onnx does, so pfhip_post_process takes them unchanged.
+ * The rule has no constants of its own; it uses TimestampOnnx's two (util.cpp:838-963) as times: MAX_TOKEN_DURATION = 30 x 20 ms =
+ * 600 ms and START_END_THRESHOLD = 5 x 20 ms = 100 ms.  In frames, with e[-1] = 0 and maxtok = 600 / frame_ms, for k = 0..n_chars-1:
+ *   e[k] = min(fire_frame[k] + 1, n_frames)        the token ends with the row it fired in
+ *   b[k] = max(e[k-1], e[k] - maxtok)              and is at most MAX_TOKEN_DURATION long
+ *   b[k] > e[k-1]: a <sil> span [e[k-1], b[k]] first; then the token [b[k], e[k]]
+ * after the last token: (n_frames - e[last]) * frame_ms > 100 -> a <sil> span [e[last], n_frames], else the last token ends at
+ * n_frames.  Seconds = frames * frame_ms / 1000 + begin_time_ms / 1000.  Resolution is one LFR row; two fires in one row give a
+ * zero-length token.  No real model has validated the rule against the head's stamps: it is not claimed to equal them.
+ * Known answer: n_frames = 40, frame_ms = 60, fire_frame = {4, 9, 30, 33, 40} (the fifth is the tail slot's "</s>"), n_chars = 4 ->
+ *   token [0.00, 0.30]  token [0.30, 0.60]  <sil> [0.60, 1.26]  token [1.26, 1.86]  token [1.86, 2.04]  <sil> [2.04, 2.40]
+ * PFHIP_ERR_ARG: n_chars > n_fires, a negative argument, frame_ms <= 0, a NULL pointer; PFHIP_ERR_CAPACITY: cap (in triplets) too
+ * small, *n_spans = the count needed; n_chars = 0: no spans. */
+pfhip_status pfhip_cif_timestamps(const int32_t* fire_frame, int n_fires, int n_chars, int n_frames, float frame_ms,
+                                  float begin_time_ms, float* spans, int cap, int* n_spans);
 
 /* ---- CT-Transformer punctuation forward ------------------------------------------------------------
  *   pfhip_punc_create_from_memory <-> CTTransformer::InitPunc session load (ct-transformer.cpp:14-37)
@@ -564,7 +630,8 @@ pfhip_status pfhip_punc_add_punc(pfhip_punc* p, const int32_t* ids, int n, int32
 
 /* ---- inspection (parity tests) -----------------------------------------------------------------
  * Copies a named intermediate of the LAST forward to host: "feats" [M,560], "enc" [M,d],
- * "alphas" [M] (without the tail slot), "emb" [sum fires, d], "logp" [sum fires, vocab].
+ * "alphas" [M] (without the tail slot), "emb" [sum fires, d], "logp" [sum fires, vocab],
+ * "fire_frame" [sum fires] (the fire frames of a forward that recorded them, as floats: the values are small integers).
  * Rows are utterance-major in batch order.  *n_out = floats written. */
 pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size_t cap_floats,
                               size_t* n_out);

@@ -108,6 +108,12 @@ int pfhip_op_attention_kvplanes(const float* Q, int ldq, const void* kv_hi, cons
 /* CIF integrate-and-fire (onnxruntime/src/paraformer-online.cpp:301-327) + tail slot. */
 int pfhip_op_cif(const float* hidden, int ldh, const float* alphas, const int* row_off, const int* len, int B, int D,
                  float threshold, float tail, float* stage, int* n_fires, int* token_num, void* stream);
+/* The same scan by the sibling kernel that also records where each token fired: fire_frame[row_off[b] + b + j] = the step of
+ * the scan in which fire j of utterance b happened (0..len[b]-1 = that LFR row, len[b] = the tail slot), laid out like stage's rows
+ * ([sum len + B] ints).  Slots past n_fires[b] are not written.  stage, n_fires and token_num are pfhip_op_cif's bit for bit.
+ * Refuses what pfhip_op_cif refuses, and a NULL fire_frame. */
+int pfhip_op_cif_fires(const float* hidden, int ldh, const float* alphas, const int* row_off, const int* len, int B, int D,
+                       float threshold, float tail, float* stage, int* n_fires, int* token_num, int* fire_frame, void* stream);
 /* LogSoftmax + ArgMax (GreedySearch/FindMax, onnxruntime/src/paraformer.cpp:386-395, util.cpp:63-74). */
 int pfhip_op_logsoftmax_argmax(const float* logits, int ldl, int ML, int V, float* logp, int32_t* ids, void* stream);
 /* The same head with the k best columns of every row (topk.hip; beyond GreedySearch, which keeps only the arg-max): topk_ids /
