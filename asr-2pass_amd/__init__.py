@@ -943,6 +943,11 @@ class CTTransformerHip:
         self._h = ctypes.c_void_p()
 
     def InitPunc(self, punc_model, punc_config=None, token_file=None, thread_num=1, device=0):
+        if isinstance(punc_model, (str, os.PathLike)):
+            # the strings the reference passes (`<dir>/model.onnx` and `<dir>/config.yaml`, offline-stream.cpp:111-117), read in libpfhip.so
+            enc = lambda p: None if p is None else os.fspath(p).encode()
+            _check(self._lib, self._lib.pfhip_punc_create_from_files(enc(punc_model), enc(punc_config), device, ctypes.byref(self._h)))
+            return self
         man, blob = punc_model
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         _check(self._lib, self._lib.pfhip_punc_create_from_memory(blob.ctypes.data, blob.nbytes, json.dumps(man).encode(),

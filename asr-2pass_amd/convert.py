@@ -221,11 +221,21 @@ def convert_vad(state, shift, rescale, cfg=None):
     return {"config": cfg, "tensors": tensors, "total_bytes": total}, blob
 
 
-def convert_punc(state, cfg=None):
+def convert_punc(state, cfg=None, declared=None):
+    """The widths are what the tensors have: d_model from embed.weight, ffn from the first feed-forward weight.  declared: the
+    encoder_conf of a config.yaml; its output_size / linear_units may be absent and may not contradict the tensors."""
     cfg = dict(Wt.CT_TRANSFORMER) if cfg is None else dict(cfg)
     nm = punc_name_map(cfg)
+    state = dict(state)
+    for k in list(state):
+        state.setdefault(_without_model_components(k), state[k])
     cfg["vocab"] = int(state[nm["embed.w"]].shape[0])
     cfg["n_punc"] = int(state[nm["out.w"]].shape[0])
+    cfg["d_model"] = int(state[nm["embed.w"]].shape[1])
+    cfg["ffn"] = int(state[nm["enc.0.ffn1.w"]].shape[0])
+    for key, have, tensor in (("output_size", cfg["d_model"], nm["embed.w"]), ("linear_units", cfg["ffn"], nm["enc.0.ffn1.w"])):
+        if declared and key in declared and int(declared[key]) != have:
+            raise ValueError(f"encoder_conf.{key} is {int(declared[key])} but {tensor} has {have}")
     tensors, blob, total = _fill(Wt.punc_tensor_specs(cfg), nm, state, {})
     return {"config": cfg, "tensors": tensors, "total_bytes": total}, blob
 
@@ -277,7 +287,22 @@ def convert_model_dir(kind, src, prefer="auto", quantized=False):
             raise FileNotFoundError(f"{src}: neither model.onnx nor model.pt")
         state, files = load_state_dict(pt), [pt]
     if kind == "punc":
-        man, blob = convert_punc(state)
+        cfg, enc, ypath = dict(Wt.CT_TRANSFORMER), {}, os.path.join(src, "config.yaml")
+        if os.path.exists(ypath):
+            with open(ypath, encoding="utf-8") as f:
+                y = yaml.safe_load(f) or {}
+            enc = y.get("encoder_conf") or {}
+            for dst, keys in (("n_head", ("attention_heads",)), ("layers", ("num_blocks",)), ("kernel", ("kernel_size",)),
+                              ("sanm_shift", ("sanm_shfit", "sanm_shift"))):      # (sic) the upstream key is misspelt
+                for k in keys:
+                    if k in enc:
+                        cfg[dst] = int(enc[k])
+                        break
+            pl = (y.get("model_conf") or {}).get("punc_list") or y.get("punc_list")
+            if pl:
+                cfg["punc_list"] = [str(p) for p in pl]
+            files = files + [ypath]
+        man, blob = convert_punc(state, cfg, enc)
         return man, blob, files
     mvn = next((os.path.join(src, n) for n in (("vad.mvn", "am.mvn") if kind == "vad" else ("am.mvn",)) if os.path.exists(os.path.join(src, n))), None)
     if mvn is None:

@@ -1517,9 +1517,7 @@ void load_punc(const std::string& model, const std::string& config, Container& o
   auto sect = [&](const YNode& from, const char* k) { const YNode* n = from.get(k); return n && n->kind == YNode::MAP ? *n : none; };
   const YNode enc = sect(y, "encoder_conf"), mc = sect(y, "model_conf");
   PuncConfig c;
-  c.d_model = (int)enc.number("output_size", c.d_model);
   c.n_head = (int)enc.number("attention_heads", c.n_head);
-  c.ffn = (int)enc.number("linear_units", c.ffn);
   c.layers = (int)enc.number("num_blocks", c.layers);
   c.kernel = (int)enc.number("kernel_size", c.kernel);
   c.sanm_shift = (int)enc.number("sanm_shfit", enc.number("sanm_shift", c.sanm_shift));      // (sic) the upstream key is misspelt
@@ -1533,6 +1531,16 @@ void load_punc(const std::string& model, const std::string& config, Container& o
   State state;
   add_file_state(onnx, state, keep, out);
   c.vocab = (int)dim_of(state, "embed.weight", 0, "the punctuation vocabulary");
+  // the widths are what the tensors have; encoder_conf may leave them out, and may not contradict them
+  c.d_model = (int)dim_of(state, "embed.weight", 1, "the punctuation model width");
+  c.ffn = (int)dim_of(state, "encoder.encoders0.0.feed_forward.w_1.weight", 0, "the punctuation feed-forward width");
+  auto declared = [&](const char* key, int have, const std::string& tensor) {
+    const int64_t want = (int64_t)enc.number(key, (double)have);
+    if (want != have)
+      bad(config + ": encoder_conf." + key + " is " + std::to_string(want) + " but " + tensor + " has " + std::to_string(have));
+  };
+  declared("output_size", c.d_model, "embed.weight");
+  declared("linear_units", c.ffn, "encoder.encoders0.0.feed_forward.w_1.weight");
   c.n_punc = (int)dim_of(state, "decoder.weight", 0, "the punctuation classes");
   out.sources.push_back(config);
   std::string cj = "{\"model\": \"ct_transformer\", \"vocab\": " + std::to_string(c.vocab) + ", \"d_model\": " + std::to_string(c.d_model) +

@@ -203,6 +203,18 @@ int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, cons
                           S(stream));
   return done();
 }
+int pfhip_op_attention_dk(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
+                          int max_q_len, float scale, int d_k, const int* q_kv_limit, void* stream) {
+  // before anything is launched: the kernel reads and writes H * d_k columns of every row
+  if (d_k < 1 || d_k > 64 || H < 1 || !Q || !K || !V || !O || !q_off || !q_len || !kv_off || !kv_len) return (int)hipErrorInvalidValue;
+  const long long w = (long long)H * d_k;
+  if (ldq < w || ldk < w || ldv < w || ldo < w) return (int)hipErrorInvalidValue;
+  pfhip::launch_attention_dk({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .O = O, .ldo = ldo, .q_off = q_off, .q_len = q_len, .kv_off = kv_off, .kv_len = kv_len, .B = B, .H = H,
+                              .max_q_len = max_q_len, .scale = scale, .head_dim = d_k, .q_kv_limit = q_kv_limit},
+                             S(stream));
+  return done();
+}
 int pfhip_op_attention_fsmn(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, const int* off,
                             const int* len, int B, int H, int max_len, float scale, const float* fsmn_w, float* mem, int ldmem,
                             int mem_accumulate, int head_dim, void* stream) {

@@ -1,9 +1,17 @@
 // CT-Transformer punctuation forward on MI355X — the C ABI's pfhip_punc_* family.
 // Replaces the `m_session->Run` + Argmax loop of CTTransformer::Infer (onnxruntime/src/ct-transformer.cpp:162-204):
 // token ids [N] -> logits [N, 6] -> punctuation id = first maximum over the first CANDIDATE_NUM-1 classes.
-// Same kernels as the ASR encoder (fp32 MFMA GEMMs, FSMN memory block, fused attention instantiated for
-// d_k = 32) plus an embedding gather fused with the x*sqrt(d) + sinusoidal PE step.  The 272727 x 256
-// embedding table (279 MB) stays in HBM; a call touches N rows of it.
+// Same kernels as the ASR encoder (fp32 MFMA GEMMs, FSMN memory block, fused attention) plus an embedding gather fused with
+// the x*sqrt(d) + sinusoidal PE step.  Any CT-Transformer with d_model % 4 == 0, d_model <= 1024, a head width
+// d_k = d_model / n_head in [1, 64], ffn % 128 == 0, ffn <= 2048: d_k = 32 (the 256 / 8 / 1024 x 4 model of
+// punc_ct-transformer_zh-cn-common-vocab272727) runs attention.hip's kernel, every other width attention_dk.hip's (the large model
+// of the reference's English deployment, recalled as 516 / 12 / 2048 x 12: d_k = 43).  The embedding table (272727 x 256 = 279 MB,
+// 471067 x 516 = 0.97 GB) stays in HBM; a call touches N rows of it.
+//
+// Leading dimensions.  The GEMMs run over the weights' padded shapes (internal.h lin_gemm: N = round_up(N, 128), K = round_up(K, 32)),
+// so they write round_up(d, 128) columns and read round_up(d, 32): the activations x, y, mem, ctx have the row stride
+// ld = round_up(d, 128) and qkv round_up(3 d, 128) (d and 3 d themselves at 256).  The pad columns [d, ld) of everything a GEMM reads
+// are zeros (see punc_infer_packed): a pad column meets zero weights, but junk * 0 is NaN when the junk is.
 #include <memory>
 
 #include "internal.h"
@@ -12,7 +20,7 @@
 using namespace pfhip_impl;
 
 namespace pfhip {
-void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int D, float* out, int ldo, int N,
+void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int D, int Dout, float* out, int ldo, int N,
                          const float* inv_ts, float scale, const int* pos_of_row, hipStream_t s);   // punc.hip
 void launch_argmax_first(const float* logits, int ldl, int N, int ncls, int32_t* out, hipStream_t s);
 }
@@ -34,6 +42,7 @@ struct pfhip_punc {
   float *an_g = nullptr, *an_b = nullptr;
   PackedLin head;
   std::vector<DevMem> owned;      // the vectors and tables behind the raw pointers above
+  int ld = 256, ldqkv = 768;      // row strides of x / y / mem / ctx and of qkv: round_up(d, 128), round_up(3 d, 128)
   Buf ids, x, y, qkv, mem, ctx, h, logits, punc, meta, lim;
   int* h_pin = nullptr;
   // pinned staging for one (batched) call: [ids | pos | lim | off | len] in, punctuation ids out
@@ -88,9 +97,15 @@ pfhip_status pfhip_punc_create_from_memory(const void* blob, size_t blob_bytes, 
   p->sanm_shift = (int)jc->number("sanm_shift", 0);
   if (p->sanm_shift != 0 && p->sanm_shift != 5) return fail(PFHIP_ERR_UNSUPPORTED, "sanm_shift must be 0 or 5");
   const int d = p->d;
-  if (p->vocab <= 0 || d % 128 || d > 512 || d / p->n_head != 32 || kernel != 11 || p->ffn % 128 || p->ffn > 2048 ||
-      p->n_punc < 2 || p->n_punc > 128)
-    return fail(PFHIP_ERR_UNSUPPORTED, "CT-Transformer kernels need d_model/n_head == 32, FSMN kernel 11");
+  if (p->vocab <= 0 || d < 4 || d % 4 || d > 1024 || p->n_head < 1 || d % p->n_head || d / p->n_head > 64 || kernel != 11 || p->ffn < 128 ||
+      p->ffn % 128 || p->ffn > 2048 || p->n_punc < 2 || p->n_punc > 128)
+    return fail(PFHIP_ERR_UNSUPPORTED,
+                "CT-Transformer kernels need d_model % 4 == 0, d_model <= 1024, d_model % n_head == 0, 1 <= d_model / n_head <= 64, "
+                "ffn % 128 == 0, ffn <= 2048, FSMN kernel 11, 2 <= n_punc <= 128 (got d_model " + std::to_string(d) + ", n_head " +
+                std::to_string(p->n_head) + ", ffn " + std::to_string(p->ffn) + ", kernel " + std::to_string(kernel) + ", n_punc " +
+                std::to_string(p->n_punc) + ")");
+  p->ld = round_up(d, 128);
+  p->ldqkv = round_up(3 * d, 128);
   const float* hb = static_cast<const float*>(blob);
   auto get = [&](const std::string& name, std::vector<int> shape, const float** ptr) -> bool {
     const pfhip::JValue* t = jt->get(name);
@@ -256,12 +271,24 @@ static pfhip_status punc_infer_packed(pfhip_punc* p, const int32_t* const* ids, 
   std::lock_guard<std::mutex> lk(p->mu);
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t s = p->stream;
-  const int d = p->d, Np = round_up(total, 128);
-  HIP_TRY(p->x.ensure((size_t)Np * d * 4));
-  HIP_TRY(p->y.ensure((size_t)Np * d * 4));
-  HIP_TRY(p->qkv.ensure((size_t)Np * 3 * d * 4));
-  HIP_TRY(p->mem.ensure((size_t)Np * d * 4));
-  HIP_TRY(p->ctx.ensure((size_t)Np * d * 4));
+  const int d = p->d, ld = p->ld, ldqkv = p->ldqkv, Np = round_up(total, 128);
+  // Pad columns [d, ld) of the GEMMs' A operands and residuals, zero by construction (nothing to do at ld == d):
+  //   x    the embedding gather zeroes them on every call; a GEMM epilogue then writes 0 (zero weights and bias) + mem's + x's own
+  //   y    every LayerNorm launch zeroes columns [d, Dout = ld)
+  //   ctx  the attention writes columns [0, d) only, and mem's producer (the FSMN block) likewise: a buffer that `ensure` has just
+  //   mem  (re)allocated is cleared whole, on the stream, ahead of its first use, and nothing ever writes its pad columns
+  // h needs none (ffn % 128 == 0: K is ffn itself); qkv's pad columns are written by its GEMM and read by nobody.
+  auto ensure_cleared = [&](Buf& b, size_t bytes) -> pfhip_status {
+    const bool grows = bytes > b.cap;
+    HIP_TRY(b.ensure(bytes));
+    if (grows && ld != d) HIP_TRY(hipMemsetAsync(b.p, 0, b.cap, s));
+    return PFHIP_OK;
+  };
+  HIP_TRY(p->x.ensure((size_t)Np * ld * 4));
+  HIP_TRY(p->y.ensure((size_t)Np * ld * 4));
+  HIP_TRY(p->qkv.ensure((size_t)Np * ldqkv * 4));
+  if (pfhip_status st = ensure_cleared(p->mem, (size_t)Np * ld * 4)) return st;
+  if (pfhip_status st = ensure_cleared(p->ctx, (size_t)Np * ld * 4)) return st;
   HIP_TRY(p->h.ensure((size_t)Np * p->ffn * 4));
   HIP_TRY(p->logits.ensure((size_t)Np * 128 * 4));
   HIP_TRY(p->punc.ensure((size_t)total * 4));
@@ -291,26 +318,29 @@ static pfhip_status punc_infer_packed(pfhip_punc* p, const int32_t* const* ids, 
   const int* d_off = d_ids + 3 * total;
   const int* d_len = d_off + B;
   float* x = p->x.f();
-  pfhip::launch_embed_gather(d_ids, p->d_table, p->vocab, d, x, d, total, p->d_inv_ts, sqrtf((float)d), B > 1 ? d_pos : nullptr, s);
-  const float att_scale = 1.0f / sqrtf(32.f);
-  // every layer's attention: d_k = 32, with the VadMask prefix limits when the model is the online one
-  pfhip::AttnOp att = qkv_attention(p->qkv.f(), d, p->ctx.f());
+  pfhip::launch_embed_gather(d_ids, p->d_table, p->vocab, d, ld, x, ld, total, p->d_inv_ts, sqrtf((float)d), B > 1 ? d_pos : nullptr, s);
+  // every layer's attention, with the VadMask prefix limits when the model is the online one: d_k = 32 on attention.hip's kernel,
+  // any other width on attention_dk.hip's
+  const int dk = d / p->n_head;
+  pfhip::AttnOp att{.Q = p->qkv.f(), .ldq = ldqkv, .K = p->qkv.f() + d, .ldk = ldqkv, .V = p->qkv.f() + 2 * d, .ldv = ldqkv,
+                    .O = p->ctx.f(), .ldo = ld};
   att.q_off = att.kv_off = d_off; att.q_len = att.kv_len = d_len;
-  att.B = B; att.H = p->n_head; att.max_q_len = max_n; att.scale = att_scale; att.head_dim = 32; att.q_kv_limit = d_lim;
+  att.B = B; att.H = p->n_head; att.max_q_len = max_n; att.scale = 1.0f / sqrtf((float)dk); att.head_dim = dk; att.q_kv_limit = d_lim;
   for (int i = 0; i < p->layers; ++i) {
     const pfhip_punc::Layer& l = p->L[i];
-    pfhip::launch_layernorm(x, d, p->y.f(), d, l.n1g, l.n1b, total, d, d, 1e-12f, s);
-    lin_gemm(s, l.qkv, p->y.f(), d, p->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, total, false);
-    pfhip::launch_fsmn_shift(p->qkv.f() + 2 * d, 3 * d, l.fsmn, nullptr, 0, p->mem.f(), d, d_off, d_len, B, max_n, d,
+    pfhip::launch_layernorm(x, ld, p->y.f(), ld, l.n1g, l.n1b, total, d, ld, 1e-12f, s);
+    lin_gemm(s, l.qkv, p->y.f(), ld, p->qkv.f(), ldqkv, nullptr, 0, nullptr, 0, total, false);
+    pfhip::launch_fsmn_shift(p->qkv.f() + 2 * d, ldqkv, l.fsmn, nullptr, 0, p->mem.f(), ld, d_off, d_len, B, max_n, d,
                              p->sanm_shift, s);
-    pfhip::launch_attention(att, s);
-    lin_gemm(s, l.out, p->ctx.f(), d, x, d, p->mem.f(), d, x, d, total, false);          // in_size == size: residual
-    pfhip::launch_layernorm(x, d, p->y.f(), d, l.n2g, l.n2b, total, d, d, 1e-12f, s);
-    lin_gemm(s, l.ffn1, p->y.f(), d, p->h.f(), p->ffn, nullptr, 0, nullptr, 0, total, true);
-    lin_gemm(s, l.ffn2, p->h.f(), p->ffn, x, d, x, d, nullptr, 0, total, false);
+    if (dk == 32) pfhip::launch_attention(att, s);
+    else pfhip::launch_attention_dk(att, s);
+    lin_gemm(s, l.out, p->ctx.f(), ld, x, ld, p->mem.f(), ld, x, ld, total, false);          // in_size == size: residual
+    pfhip::launch_layernorm(x, ld, p->y.f(), ld, l.n2g, l.n2b, total, d, ld, 1e-12f, s);
+    lin_gemm(s, l.ffn1, p->y.f(), ld, p->h.f(), p->ffn, nullptr, 0, nullptr, 0, total, true);
+    lin_gemm(s, l.ffn2, p->h.f(), p->ffn, x, ld, x, ld, nullptr, 0, total, false);
   }
-  pfhip::launch_layernorm(x, d, p->y.f(), d, p->an_g, p->an_b, total, d, d, 1e-12f, s);
-  lin_gemm(s, p->head, p->y.f(), d, p->logits.f(), 128, nullptr, 0, nullptr, 0, total, false);
+  pfhip::launch_layernorm(x, ld, p->y.f(), ld, p->an_g, p->an_b, total, d, ld, 1e-12f, s);
+  lin_gemm(s, p->head, p->y.f(), ld, p->logits.f(), 128, nullptr, 0, nullptr, 0, total, false);
   // Argmax(p, p + CANDIDATE_NUM - 1): first maximum over the first n_punc-1 classes (ct-transformer.cpp:193-196)
   pfhip::launch_argmax_first(p->logits.f(), 128, total, p->n_punc - 1, static_cast<int32_t*>(p->punc.p), s);
   HIP_TRY(hipMemcpyAsync(h_out, p->punc.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));

@@ -7,7 +7,7 @@
 namespace pfhip {
 namespace {
 __global__ __launch_bounds__(128) void embed_gather_kernel(const int32_t* __restrict__ ids,
-                                                           const float* __restrict__ table, int vocab, int D,
+                                                           const float* __restrict__ table, int vocab, int D, int Dout,
                                                            float* __restrict__ out, int ldo, int N,
                                                            const float* __restrict__ inv_ts, float scale,
                                                            const int* __restrict__ pos_of_row) {
@@ -23,6 +23,7 @@ __global__ __launch_bounds__(128) void embed_gather_kernel(const int32_t* __rest
     const float pe = c < half ? sinf(coe) : cosf(coe);
     out[(size_t)row * ldo + c] = table[(size_t)id * D + c] * scale + pe;
   }
+  for (int c = D + threadIdx.x; c < Dout; c += blockDim.x) out[(size_t)row * ldo + c] = 0.f;      // pad columns of a GEMM operand
 }
 __global__ __launch_bounds__(256) void argmax_first_kernel(const float* __restrict__ logits, int ldl, int N, int ncls,
                                                            int32_t* __restrict__ out) {
@@ -37,10 +38,11 @@ __global__ __launch_bounds__(256) void argmax_first_kernel(const float* __restri
 }
 }  // namespace
 
-void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int D, float* out, int ldo, int N,
+// out[row][0..D) = table[id] * scale + PE; columns D..Dout zeroed (Dout <= ldo)
+void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int D, int Dout, float* out, int ldo, int N,
                          const float* inv_ts, float scale, const int* pos_of_row, hipStream_t s) {
   if (N <= 0) return;
-  hipLaunchKernelGGL(embed_gather_kernel, dim3(N), dim3(128), 0, s, ids, table, vocab, D, out, ldo, N, inv_ts, scale, pos_of_row);
+  hipLaunchKernelGGL(embed_gather_kernel, dim3(N), dim3(128), 0, s, ids, table, vocab, D, Dout, out, ldo, N, inv_ts, scale, pos_of_row);
 }
 void launch_argmax_first(const float* logits, int ldl, int N, int ncls, int32_t* out, hipStream_t s) {
   if (N <= 0) return;

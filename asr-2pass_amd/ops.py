@@ -33,6 +33,7 @@ def _lib():
         lib.pfhip_op_fsmn.argtypes = [_vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp]
         lib.pfhip_op_attention.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _vp]
         lib.pfhip_op_attention_hd.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _ci, _vp]
+        lib.pfhip_op_attention_dk.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _ci, _vp, _vp]
         lib.pfhip_op_cif.argtypes = [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp]
         lib.pfhip_op_cif_fires.argtypes = [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _cf, _cf, _vp, _vp, _vp, _vp, _vp]
         lib.pfhip_op_logsoftmax_argmax.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
@@ -207,6 +208,18 @@ def attention(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, head_dim=128
     _ck(_lib().pfhip_op_attention_hd(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0),
                                      _p(q_off), _p(q_len), _p(kv_off), _p(kv_len), B, n_head, int(q_len.max().item()),
                                      scale, head_dim, _stream()), "attention")
+    return O
+
+
+def attention_dk(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, d_k, q_kv_limit=None, out=None):
+    """Attention for any head width 1 <= d_k <= 64 (attention_dk.hip), head h in columns [h * d_k, (h + 1) * d_k); q_kv_limit: per
+    packed query row the number of keys it may see.  out: a [rows, >= n_head * d_k] tensor to write into (only those columns of the
+    segments' rows are touched); otherwise a zero-filled [rows, n_head * d_k] one is made."""
+    lib = _lib()
+    O = torch.zeros((Q.shape[0], n_head * d_k), dtype=torch.float32, device=Q.device) if out is None else out
+    _ck(lib.pfhip_op_attention_dk(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0),
+                                  _p(q_off), _p(q_len), _p(kv_off), _p(kv_len), q_off.numel(), n_head, int(q_len.max().item()),
+                                  float(scale), int(d_k), _p(q_kv_limit), _stream()), "attention_dk")
     return O
 
 

@@ -597,7 +597,10 @@ pfhip_status pfhip_cif_timestamps(const int32_t* fire_frame, int n_fires, int n_
  *   pfhip_punc_infer              <-> CTTransformer::Infer (ct-transformer.cpp:162-204): ids [n] -> punctuation id
  *                                     per token = first maximum over the first CANDIDATE_NUM-1 classes; logits_out
  *                                     (optional) gets the [n, n_classes] scores.  Tokenisation and the 20-token
- *                                     mini-sentence bookkeeping of AddPunc (:39-155) stay on the host above this. */
+ *                                     mini-sentence bookkeeping of AddPunc (:39-155) stay on the host above this.
+ * Served: d_model % 4 == 0, d_model <= 1024, d_model % n_head == 0, 1 <= d_model / n_head <= 64, ffn % 128 == 0, ffn <= 2048,
+ * FSMN kernel 11, sanm_shift 0 or 5, 2 <= n_punc <= 128 (256 / 8 / 1024 x 4, the zh-cn model; 516 / 12 / 2048 x 12, the large
+ * cn-en model as recalled); anything else is PFHIP_ERR_UNSUPPORTED with the range and the values in pfhip_last_error. */
 typedef struct pfhip_punc pfhip_punc;
 pfhip_status pfhip_punc_create_from_memory(const void* blob, size_t blob_bytes, const char* manifest_json, int device,
                                            pfhip_punc** out);

@@ -73,6 +73,13 @@ int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const f
 int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                           const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                           int max_q_len, float scale, int head_dim, void* stream);
+/* The same block for any head width 1 <= d_k <= 64 (attention_dk.hip; the large CT-Transformer: 516 / 12 heads = 43), fp32, head h in
+ * columns [h * d_k, (h + 1) * d_k) of a row: no other column is read or written.  q_kv_limit: nullptr, or per packed query row the
+ * number of keys it may see (CTTransformerOnline::VadMask).  hipErrorInvalidValue, before anything is launched, for d_k < 1,
+ * d_k > 64, H < 1 or a leading dimension below H * d_k. */
+int pfhip_op_attention_dk(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                          const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
+                          int max_q_len, float scale, int d_k, const int* q_kv_limit, void* stream);
 /* The encoder layer's pair on one set of self-attention segments (off / len): the SAN-M memory block of V into mem (pfhip_op_fsmn
  * without a residual) and the attention block's context into O as fp32 rows.  ONE launch — the memory block runs in front of the
  * attention kernel's key loop — where pfhip_op_attention_fsmn_is_fused(max_len, head_dim) says so; then, and only then,
