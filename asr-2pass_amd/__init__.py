@@ -53,6 +53,8 @@ ABI_SYMBOLS = [
     # offline: fire frames of the CIF scan per token, and token spans from them
     "pfhip_offline_forward_detail", "pfhip_offline_forward_detail_s16", "pfhip_set_fire_frames", "pfhip_offline_fetch_fire_frames",
     "pfhip_lfr_frame_ms", "pfhip_cif_timestamps",
+    # SenseVoiceSmall, offline: CTC head over every frame, collapsed on the device
+    "pfhip_is_ctc", "pfhip_svs_lid", "pfhip_svs_forward", "pfhip_svs_forward_s16",
 ]
 
 
@@ -99,6 +101,13 @@ class _Nbest(ctypes.Structure):
 class _Detail(ctypes.Structure):
     _fields_ = [("nbest_k", ctypes.c_int32), ("nbest_ids", ctypes.POINTER(ctypes.c_int32)), ("nbest_logp", ctypes.POINTER(ctypes.c_float)),
                 ("fire_frame", ctypes.POINTER(ctypes.c_int32))]
+
+
+class _SvsOut(ctypes.Structure):
+    _fields_ = [("ids", ctypes.POINTER(ctypes.c_int32)), ("token_num", ctypes.POINTER(ctypes.c_int32)), ("max_tokens", ctypes.c_int),
+                ("tok_frame", ctypes.POINTER(ctypes.c_int32)), ("tok_logp", ctypes.POINTER(ctypes.c_float)),
+                ("frame_ids", ctypes.POINTER(ctypes.c_int32)), ("frame_logp", ctypes.POINTER(ctypes.c_float)),
+                ("frame_len", ctypes.POINTER(ctypes.c_int32)), ("logp", ctypes.POINTER(ctypes.c_float)), ("logp_cap_floats", ctypes.c_size_t)]
 
 
 class _StreamDetail(ctypes.Structure):
@@ -249,6 +258,12 @@ def load_lib() -> ctypes.CDLL:
     lib.pfhip_punc_infer_batch.argtypes = [vp, vp, vp, vp, ci, vp]
     lib.pfhip_set_punc_batching.argtypes = [vp, ci, ci]
     lib.pfhip_debug_poke.argtypes = [vp, ctypes.c_char_p, ci]
+    if hasattr(lib, "pfhip_svs_forward"):
+        lib.pfhip_is_ctc.argtypes = [vp]
+        lib.pfhip_svs_lid.argtypes = [ctypes.c_char_p]
+        lib.pfhip_svs_forward.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_SvsOut)]
+        lib.pfhip_svs_forward_s16.argtypes = lib.pfhip_svs_forward.argtypes
     lib.pfhip_profile_enable.argtypes = [vp, ci]
     lib.pfhip_profile_read.argtypes = [vp, ctypes.POINTER(_Profile), ci]
     # 16-bit PCM in: the argument lists of the f32 siblings
@@ -269,7 +284,7 @@ def _check(lib, st):
 
 def read_model_files(kind, model, second=None, hotword=None, cmvn=None, config=None):
     """The reference's own file contract (com-define.h:52-88) -> (manifest dict, float32 blob, from_cache) through the C++ reader
-    in libpfhip.so (pfhip_read_model_files); kind in {"asr", "vad", "punc"}.  No device needed."""
+    in libpfhip.so (pfhip_read_model_files); kind in {"asr", "sensevoice", "vad", "punc"}.  No device needed."""
     lib = load_lib()
     enc = lambda s: None if s is None else str(s).encode()
     h = ctypes.c_void_p()
@@ -835,6 +850,125 @@ class ParaformerOnlineHip:
         n = ctypes.c_size_t(0)
         _check(self._lib, self._lib.pfhip_stream_get_tensor(self._h, name.encode(), buf.ctypes.data, cap_floats, ctypes.byref(n)))
         return buf[:n.value]
+
+
+def svs_lid(svs_lang):
+    """pfhip_svs_lid: lid_map of the reference (sensevoice-small.h:121-129); an unknown string gives 0."""
+    return int(load_lib().pfhip_svs_lid(None if svs_lang is None else str(svs_lang).encode()))
+
+
+class SenseVoiceHip:
+    """Host-side mirror of the reference's SenseVoiceSmall (onnxruntime/src/sensevoice-small.cpp) for the offline path, beside
+    ParaformerHip: InitAsr on a (manifest, blob) container of kind "sensevoice" or a `<prefix>.bin/.json` pair, then forward() =
+    pfhip_svs_forward on a packed batch with per-utterance language and text normalisation.  Model widths and wiring are recalled
+    from upstream FunASR.  The text assembly of CTCSearch (:348-375) is host string handling above this."""
+
+    def __init__(self):
+        self._lib = load_lib()
+        self._h = ctypes.c_void_p()
+        self.cfg = None
+
+    def InitAsr(self, am_model, am_cmvn=None, am_config=None, device=0):
+        """am_model: a (manifest, blob) pair, the path prefix of `<prefix>.bin/.json`, or — with am_cmvn and am_config — the strings
+        the reference passes (`<dir>/model.onnx`, `am.mvn`, `config.yaml`): pfhip_create_from_files reads the reference's own files."""
+        self.close()
+        if isinstance(am_model, str) and am_cmvn and am_config:
+            enc = lambda s: str(s).encode()
+            _check(self._lib, self._lib.pfhip_create_from_files(enc(am_model), None, None, enc(am_cmvn), enc(am_config), device,
+                                                                ctypes.byref(self._h)))
+            self.cfg = read_model_files("sensevoice", am_model, None, None, am_cmvn, am_config)[0]["config"]
+        elif isinstance(am_model, (tuple, list)):
+            man, blob = am_model
+            blob = np.ascontiguousarray(blob, dtype=np.float32)
+            _check(self._lib, self._lib.pfhip_create_from_memory(blob.ctypes.data, blob.nbytes, json.dumps(man).encode(), device,
+                                                                 ctypes.byref(self._h)))
+            self.cfg = man["config"]
+        else:
+            _check(self._lib, self._lib.pfhip_create((am_model + ".bin").encode(), (am_model + ".json").encode(), device,
+                                                     ctypes.byref(self._h)))
+            with open(am_model + ".json") as f:
+                self.cfg = json.load(f)["config"]
+        if not self._lib.pfhip_is_ctc(self._h):
+            self.close()
+            raise PfhipError("not a SenseVoice container (config.kind != \"sensevoice\"): use ParaformerHip")
+        return self
+
+    def close(self):
+        if self._h:
+            self._lib.pfhip_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def GetAsrSampleRate(self):
+        return self._lib.pfhip_sample_rate(self._h)
+
+    def set_inflight(self, n):
+        _check(self._lib, self._lib.pfhip_set_inflight(self._h, int(n)))
+
+    def warm_up(self, batch, n_samples):
+        _check(self._lib, self._lib.pfhip_warm_up(self._h, int(batch), int(n_samples)))
+
+    def rows_of(self, n_samples):
+        """Rows of one utterance in the packed sequence: ceil(frames / lfr_n) + 4 prompt rows, or 0 without a frame."""
+        frames = 0 if n_samples < 400 else 1 + (n_samples - 400) // 160
+        T = -(-frames // int(self.cfg.get("lfr_n", 6)))
+        return T + 4 if T > 0 else 0
+
+    def forward(self, din, lang="auto", itn=True, lid=None, textnorm=None, want_logp=False):
+        """One packed forward.  lang / itn: a value for all utterances or one per utterance (svs_lang strings, booleans); lid /
+        textnorm override them with prompt ids.  Returns dict(token_num [B], ids / tok_frame / tok_logp: per-utterance arrays (the four
+        leading tag ids included), frame_len [B], frame_ids / frame_logp: per-utterance arrays over its rows, logp: per-utterance
+        [rows, vocab] arrays when want_logp)."""
+        bufs, s16 = _pcm_buffers(din)
+        B = len(bufs)
+        per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * B
+        lid = [svs_lid(x) for x in per(lang)] if lid is None else [int(x) for x in per(lid)]
+        textnorm = [14 if x else 15 for x in per(itn)] if textnorm is None else [int(x) for x in per(textnorm)]
+        ns = np.array([len(b) for b in bufs], np.int32)
+        rows = [self.rows_of(int(n)) for n in ns]
+        M, cap = int(sum(rows)), max(rows + [1])
+        V = int(self.cfg["vocab"])
+        ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data for b in bufs])
+        lid_a, tn_a = np.array(lid, np.int32), np.array(textnorm, np.int32)
+        ids = np.full((B, cap), -1, np.int32)
+        tok_frame = np.full((B, cap), -1, np.int32)
+        tok_logp = np.full((B, cap), np.nan, np.float32)
+        token_num = np.zeros(B, np.int32)
+        frame_len = np.zeros(B, np.int32)
+        frame_ids = np.full(max(M, 1), -1, np.int32)
+        frame_logp = np.full(max(M, 1), np.nan, np.float32)
+        logp = np.zeros((max(M, 1), V), np.float32) if want_logp else None
+        i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        out = _SvsOut(ids.ctypes.data_as(i32p), token_num.ctypes.data_as(i32p), cap, tok_frame.ctypes.data_as(i32p),
+                      tok_logp.ctypes.data_as(f32p), frame_ids.ctypes.data_as(i32p), frame_logp.ctypes.data_as(f32p),
+                      frame_len.ctypes.data_as(i32p), logp.ctypes.data_as(f32p) if want_logp else None, logp.size if want_logp else 0)
+        fn = self._lib.pfhip_svs_forward_s16 if s16 else self._lib.pfhip_svs_forward
+        _check(self._lib, fn(self._h, ptrs, ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, lid_a.ctypes.data_as(i32p),
+                             tn_a.ctypes.data_as(i32p), ctypes.byref(out)))
+        assert frame_len.tolist() == rows, (frame_len.tolist(), rows)
+        offs = np.concatenate([[0], np.cumsum(frame_len)]).astype(np.int64)
+        cut = lambda a: [a[offs[b]:offs[b + 1]] for b in range(B)]
+        res = dict(token_num=token_num, frame_len=frame_len, ids=[ids[b, :token_num[b]] for b in range(B)],
+                   tok_frame=[tok_frame[b, :token_num[b]] for b in range(B)], tok_logp=[tok_logp[b, :token_num[b]] for b in range(B)],
+                   frame_ids=cut(frame_ids), frame_logp=cut(frame_logp))
+        if want_logp:
+            res["logp"] = cut(logp)
+        return res
+
+    def get_tensor(self, name: str, cap_floats: int) -> np.ndarray:
+        buf = np.zeros(max(cap_floats, 1), np.float32)
+        n = ctypes.c_size_t(0)
+        _check(self._lib, self._lib.pfhip_get_tensor(self._h, name.encode(), buf.ctypes.data, cap_floats, ctypes.byref(n)))
+        return buf[:n.value]
+
+    def debug_poke(self, what, value=0):
+        """pfhip_debug_poke: "ctc_unfused", "ctc_unfused_forwards", "ctc_head_chunks", "range_flag", "range_fallbacks", "plane_forwards"."""
+        return int(self._lib.pfhip_debug_poke(self._h, what.encode(), int(value)))
 
 
 class FsmnVadHip:

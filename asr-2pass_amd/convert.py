@@ -66,6 +66,30 @@ def config_from_yaml(y):
     return cfg
 
 
+def sensevoice_name_map(cfg):
+    """container tensor name -> UPSTREAM SenseVoiceSmall state_dict key, as recalled from upstream FunASR (no SenseVoice file was
+    available): embed.weight, encoder.encoders0.0 / encoders.{0..} / after_norm as the Paraformer encoder, encoder.tp_encoders.{i} /
+    tp_norm, ctc.ctc_lo.  Sub-layer names are those of paraformer_name_map's encoder part."""
+    m = {"svs.embed.w": "embed.weight"}
+
+    def layer(p, src):
+        for dst, s in (("norm1.g", "norm1.weight"), ("norm1.b", "norm1.bias"), ("qkv.w", "self_attn.linear_q_k_v.weight"),
+                       ("qkv.b", "self_attn.linear_q_k_v.bias"), ("fsmn.w", "self_attn.fsmn_block.weight"),
+                       ("out.w", "self_attn.linear_out.weight"), ("out.b", "self_attn.linear_out.bias"), ("norm2.g", "norm2.weight"),
+                       ("norm2.b", "norm2.bias"), ("ffn1.w", "feed_forward.w_1.weight"), ("ffn1.b", "feed_forward.w_1.bias"),
+                       ("ffn2.w", "feed_forward.w_2.weight"), ("ffn2.b", "feed_forward.w_2.bias")):
+            m[p + dst] = src + "." + s
+
+    for i in range(cfg["enc_layers"]):
+        layer(f"enc.{i}.", "encoder.encoders0.0" if i == 0 else f"encoder.encoders.{i - 1}")
+    m["enc.after_norm.g"], m["enc.after_norm.b"] = "encoder.after_norm.weight", "encoder.after_norm.bias"
+    for i in range(cfg["tp_layers"]):
+        layer(f"tp.{i}.", f"encoder.tp_encoders.{i}")
+    m["tp.norm.g"], m["tp.norm.b"] = "encoder.tp_norm.weight", "encoder.tp_norm.bias"
+    m["ctc.w"], m["ctc.b"] = "ctc.ctc_lo.weight", "ctc.ctc_lo.bias"
+    return m
+
+
 def paraformer_name_map(cfg):
     """container tensor name -> UPSTREAM state_dict key (weight containers use .w/.b/.g, torch uses .weight/.bias)."""
     m = {}
@@ -215,6 +239,37 @@ def convert_paraformer(state, cfg, shift, rescale):
     return {"config": cfg, "tensors": tensors, "total_bytes": total}, blob
 
 
+def is_sensevoice(state):
+    """The kind, from the tensors that are there: a CTC head and no decoder (the C++ reader decides the same way)."""
+    keys = {_without_model_components(k) for k in state}
+    return "ctc.ctc_lo.weight" in keys and "decoder.output_layer.weight" not in keys
+
+
+def sensevoice_config_from_yaml(y):
+    """config.yaml of a SenseVoiceSmall directory -> container config; defaults = weights.SENSEVOICE_SMALL (recalled from upstream
+    FunASR: encoder_conf.tp_blocks counts the layers behind the encoder)."""
+    cfg = dict(Wt.SENSEVOICE_SMALL)
+    enc, fe = (y.get(k, {}) or {} for k in ("encoder_conf", "frontend_conf"))
+    cfg.update(d_model=int(enc.get("output_size", cfg["d_model"])), n_head=int(enc.get("attention_heads", cfg["n_head"])),
+               ffn=int(enc.get("linear_units", cfg["ffn"])), enc_layers=int(enc.get("num_blocks", cfg["enc_layers"])),
+               tp_layers=int(enc.get("tp_blocks", cfg["tp_layers"])), kernel=int(enc.get("kernel_size", cfg["kernel"])),
+               n_mels=int(fe.get("n_mels", cfg["n_mels"])), lfr_m=int(fe.get("lfr_m", cfg["lfr_m"])),
+               lfr_n=int(fe.get("lfr_n", cfg["lfr_n"])), fs=int(fe.get("fs", 16000)))
+    cfg["dec_ffn"] = cfg["ffn"]
+    return cfg
+
+
+def convert_sensevoice(state, cfg, shift, rescale):
+    cfg = dict(cfg)
+    state = dict(state)
+    for k in list(state):
+        state.setdefault(_without_model_components(k), state[k])
+    nm = sensevoice_name_map(cfg)
+    cfg["vocab"] = int(state[nm["ctc.w"]].shape[0])
+    tensors, blob, total = _fill(Wt.svs_tensor_specs(cfg), nm, state, {"cmvn.mean": shift, "cmvn.istd": rescale})
+    return {"config": cfg, "tensors": tensors, "total_bytes": total}, blob
+
+
 def convert_vad(state, shift, rescale, cfg=None):
     cfg = dict(Wt.FSMN_VAD) if cfg is None else dict(cfg)
     tensors, blob, total = _fill(Wt.vad_tensor_specs(cfg), vad_name_map(cfg), state, {"cmvn.mean": shift, "cmvn.istd": rescale})
@@ -273,7 +328,8 @@ def detect_heads(state):
 
 
 def convert_model_dir(kind, src, prefer="auto", quantized=False):
-    """kind in {asr, vad, punc}; src = a model directory as the reference's server receives it (--model-dir / --vad-dir /
+    """kind in {asr, sensevoice, vad, punc} ("asr" recognises a SenseVoiceSmall by its tensors, "sensevoice" takes nothing else);
+    src = a model directory as the reference's server receives it (--model-dir / --vad-dir /
     --punc-dir: model.onnx [+ decoder.onnx, model_eb.onnx], am.mvn / vad.mvn, config.yaml / vad.yaml / punc.yaml, tokens.json).
     prefer: "onnx", "pt" or "auto" (ONNX when present).  Returns (manifest, blob, source files)."""
     import os
@@ -312,6 +368,13 @@ def convert_model_dir(kind, src, prefer="auto", quantized=False):
         man, blob = convert_vad(state, shift, rescale)
         return man, blob, files + [mvn]
     ypath = os.path.join(src, "config.yaml")
+    if kind == "sensevoice" and not is_sensevoice(state):
+        raise ValueError(f"{src}: not a SenseVoice model (no ctc.ctc_lo, or a decoder)")
+    if is_sensevoice(state):
+        with open(ypath) as f:
+            cfg = sensevoice_config_from_yaml(yaml.safe_load(f))
+        man, blob = convert_sensevoice(state, cfg, shift, rescale)
+        return man, blob, files + [mvn, ypath]
     with open(ypath) as f:
         cfg = config_from_yaml(yaml.safe_load(f))
     cfg.update(detect_heads(state))

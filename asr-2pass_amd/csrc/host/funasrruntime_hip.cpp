@@ -14,12 +14,14 @@
 #include "ct_transformer_hip.h"
 #include "fsmn_vad_hip.h"
 #include "paraformer_hip.h"
+#include "sensevoice_hip.h"
 #include "tpass_audio.h"
 
 namespace {
 
 struct OfflineStreamHip {
   funasr::ParaformerHip asr;
+  std::unique_ptr<funasr::SenseVoiceSmallHip> svs;      // model type MODEL_SVS (offline-stream.cpp:50-56): `asr` stays unloaded
   std::unique_ptr<funasr::FsmnVadHip> vad;      // complete files only (InferFile): no per-file state, no lock
   std::unique_ptr<funasr::PuncModelHipBase> punc;      // OfflineStream::punc_handle (offline-stream.cpp:105-129)
 };
@@ -122,6 +124,14 @@ FUNASR_HANDLE FunOfflineInit(std::map<std::string, std::string>& model_path, int
   os->vad = MakeVad(model_path, thread_num);
   if (model_path.count(MODEL_DIR)) {
     const std::string dir = model_path[MODEL_DIR];
+    if (dir.find(MODEL_SVS) != std::string::npos) {                              // :50-56: the directory's name picks the model
+      os->svs.reset(new funasr::SenseVoiceSmallHip());
+      os->svs->SetBatchSize(batch_size);
+      std::string token_path = model_path.count(TOKEN_PATH_KEY) ? model_path[TOKEN_PATH_KEY] : PathAppend(dir, TOKEN_PATH);
+      if (!FileExists(token_path)) token_path.clear();
+      os->svs->InitAsr(PathAppend(dir, IsTrue(model_path, QUANTIZE) ? QUANT_MODEL_NAME : MODEL_NAME), PathAppend(dir, AM_CMVN_NAME),
+                       PathAppend(dir, AM_CONFIG_NAME), token_path, thread_num);   // :89, exits on failure
+    } else {
     os->asr.SetBatchSize(batch_size);                                            // :41 (before InitAsr)
     const std::string hw_cpu_model_path = PathAppend(dir, MODEL_EB_NAME), hw_gpu_model_path = PathAppend(dir, TORCH_MODEL_EB_NAME);
     const std::string seg_dict_path = PathAppend(dir, MODEL_SEG_DICT);
@@ -138,6 +148,7 @@ FUNASR_HANDLE FunOfflineInit(std::map<std::string, std::string>& model_path, int
     std::string token_path = model_path.count(TOKEN_PATH_KEY) ? model_path[TOKEN_PATH_KEY] : PathAppend(dir, TOKEN_PATH);
     if (!FileExists(token_path)) token_path.clear();                             // harness runs on synthetic models: ids as text
     os->asr.InitAsr(am_model_path, PathAppend(dir, AM_CMVN_NAME), PathAppend(dir, AM_CONFIG_NAME), token_path, thread_num);   // :89, exits on failure
+    }
   }
   if (model_path.count(PUNC_DIR) && !model_path[PUNC_DIR].empty())               // :105-129, always CTTransformer here
     os->punc.reset(funasr::CreatePuncModelHip(model_path[PUNC_DIR], thread_num, false, IsTrue(model_path, PUNC_QUANT)));
@@ -180,10 +191,12 @@ static bool LoadPcm(pfhip_model* m, const char* buf, int n_len, int sampling_rat
 
 FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, int n_len, FUNASR_MODE mode, QM_CALLBACK fn_callback,
                                     const std::vector<std::vector<float>>& hw_emb, int sampling_rate, std::string wav_format,
-                                    bool itn, int vad_tail_sil, int vad_max_len, FUNASR_DEC_HANDLE dec_handle) {
+                                    bool itn, int vad_tail_sil, int vad_max_len, FUNASR_DEC_HANDLE dec_handle, std::string svs_lang,
+                                    bool svs_itn) {
   (void)mode; (void)itn; (void)dec_handle;
   OfflineStreamHip* os = static_cast<OfflineStreamHip*>(handle);
   if (!os || !sz_buf) return nullptr;
+  funasr::SenseVoiceSmallHip* svs = os->svs.get();      // funasrruntime.cpp:265-266: the model type routes the Forward call
   if (wav_format != "pcm" && wav_format != "PCM") return nullptr;      // the reference decodes other containers with ffmpeg
   // Audio::LoadPcmwav (audio.cpp:787-819); from here on samples, segments and stamps are at the model's rate (GetTimeLen
   // divides by dest_sample_rate, audio.cpp:254-257).
@@ -196,10 +209,10 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   //     that path stays on floats, and its VAD takes the energy form as well.
   // FunOfflineSetNbest and FunOfflineSetCifStamps change none of this: their calls take 16-bit samples and a sample rate too
   // (pfhip_offline_forward_nbest_s16, pfhip_offline_forward_detail_s16).
-  const int model_rate = os->asr.GetAsrSampleRate();
+  const int model_rate = svs ? svs->GetAsrSampleRate() : os->asr.GetAsrSampleRate();
   const int n_in = n_len / 2;
   const bool same_rate = sampling_rate == model_rate;
-  const bool use16 = same_rate || !os->vad;
+  const bool use16 = same_rate || (!os->vad && !svs);      // SenseVoice has no call at another rate: resampled through LoadPcm
   std::vector<int16_t> store16;
   const int16_t* pcm16 = use16 ? Pcm16View(sz_buf, n_in, store16) : nullptr;
   std::vector<float> pcm;
@@ -214,7 +227,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   } else if (use16) {
     n = n_in;
   } else {
-    if (!LoadPcm(os->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
+    if (!LoadPcm(svs ? svs->Handle() : os->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
       std::fprintf(stderr, "FunOfflineInferBuffer: %s\n", pfhip_last_error());
       return nullptr;
     }
@@ -236,7 +249,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   res->seg_ids.assign(index_vector.size(), {});
   size_t head = 0, msg_idx = 0;
   std::vector<int> batch;
-  const int batch_size = os->asr.GetBatchSize();
+  const int batch_size = svs ? svs->GetBatchSize() : os->asr.GetBatchSize();
   int step = 0;
   while (FetchDynamic(res->segs, index_vector, head, batch_size, batch) > 0) {
     std::vector<float*> buff(batch.size());
@@ -248,12 +261,15 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
       len[k] = same_rate || !pcm16 ? res->segs[batch[k]].second - res->segs[batch[k]].first : n_in;
     }
     const std::vector<std::string> msg_batch =
+        svs ? (pcm16 ? svs->ForwardPcm16(buff16.data(), len.data(), true, svs_lang, svs_itn, nullptr, (int)batch.size())
+                     : svs->Forward(buff.data(), len.data(), true, svs_lang, svs_itn, nullptr, (int)batch.size())) :
         pcm16 ? os->asr.ForwardPcm16(buff16.data(), len.data(), true, hw_emb, nullptr, (int)batch.size(), same_rate ? 0 : sampling_rate)
               : os->asr.Forward(buff.data(), len.data(), true, hw_emb, nullptr, (int)batch.size());
     for (size_t k = 0; k < batch.size(); ++k, ++msg_idx) {        // funasrruntime.cpp:270-279
       const int seg = index_vector[msg_idx];
       msgs[seg] = msg_batch[k];
-      res->seg_ids[seg] = os->asr.LastTokenIds()[k];
+      res->seg_ids[seg] = svs ? svs->LastTokenIds()[k] : os->asr.LastTokenIds()[k];
+      if (svs) continue;                                          // no stamps; confidences stay with the adapter
       if (k < os->asr.LastTimestamps().size()) spans[seg] = os->asr.LastTimestamps()[k];
       if (k < os->asr.LastTokenConfidence().size()) conf[seg] = os->asr.LastTokenConfidence()[k];
     }

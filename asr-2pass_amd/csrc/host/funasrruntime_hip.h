@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#define MODEL_SVS "SenseVoiceSmall"    // com-define.h:41: a MODEL_DIR whose name contains it holds that model (offline-stream.cpp:50-56)
 #define MODEL_DIR "model-dir"          // com-define.h:14-28 keys of the model_path map
 #define OFFLINE_MODEL_DIR "model-dir"
 #define ONLINE_MODEL_DIR "online-model-dir"
@@ -56,6 +57,9 @@ typedef void (*QM_CALLBACK)(int cur_step, int n_total);
 // seg_dict, am.mvn, config.yaml, tokens.json); the constructor makes the calls of OfflineStream::OfflineStream
 // (offline-stream.cpp:4-129) on the HIP plug-ins.  A directory that holds a converted container (x.pfhip.{bin,json}) instead of
 // ONNX files works too.  A model that fails to load ends the process like the reference (paraformer.cpp:43-46).
+// A MODEL_DIR whose name contains MODEL_SVS gets SenseVoiceSmallHip instead of ParaformerHip, as offline-stream.cpp:50-56 picks the
+// model; FunOfflineInferBuffer then routes by model type as funasrruntime.cpp:265-266 does, with its two trailing parameters
+// svs_lang / svs_itn (funasrruntime.h:107), and ignores hw_emb for that model, as the reference does.
 FUNASR_HANDLE FunOfflineInit(std::map<std::string, std::string>& model_path, int thread_num, bool use_gpu = true,
                              int batch_size = 1);
 // sz_buf: n_len BYTES of little-endian int16 PCM (wav_format "pcm"/"PCM"; anything else returns nullptr: the
@@ -63,7 +67,8 @@ FUNASR_HANDLE FunOfflineInit(std::map<std::string, std::string>& model_path, int
 FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, int n_len, FUNASR_MODE mode,
                                     QM_CALLBACK fn_callback, const std::vector<std::vector<float>>& hw_emb,
                                     int sampling_rate = 16000, std::string wav_format = "pcm", bool itn = true,
-                                    int vad_tail_sil = 800, int vad_max_len = 60000, FUNASR_DEC_HANDLE dec_handle = nullptr);
+                                    int vad_tail_sil = 800, int vad_max_len = 60000, FUNASR_DEC_HANDLE dec_handle = nullptr,
+                                    std::string svs_lang = "auto", bool svs_itn = true);
 const std::vector<std::vector<float>> CompileHotwordEmbedding(FUNASR_HANDLE handle, std::string& hotwords, ASR_TYPE mode = ASR_OFFLINE);
 const char* FunASRGetResult(FUNASR_RESULT result, int n_index);
 const char* FunASRGetStamp(FUNASR_RESULT result);

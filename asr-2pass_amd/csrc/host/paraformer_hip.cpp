@@ -449,7 +449,7 @@ bool ParaformerHip::InText(int id) const {
 namespace funasr {
 
 ParaformerOnlineHip::ParaformerOnlineHip(ParaformerHipBase* offline_handle, std::vector<int> chunk_size, std::string model_type) {
-  (void)model_type;                                             // MODEL_PARA only (SenseVoice is out of scope)
+  (void)model_type;                                             // MODEL_PARA only (SenseVoice is served offline, sensevoice_hip.h; its 2-pass seam is out of scope)
   offline_handle_ = dynamic_cast<ParaformerHip*>(offline_handle);
   if (!offline_handle_ || !offline_handle_->OnlineHandle() || chunk_size.size() != 3) {
     std::fprintf(stderr, "ParaformerOnlineHip: the shared model holds no online encoder / decoder (InitAsr with en_model, de_model)\n");

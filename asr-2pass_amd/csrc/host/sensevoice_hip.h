@@ -1,0 +1,82 @@
+// `SenseVoiceSmallHip`, the sibling of `funasr::SenseVoiceSmall` (onnxruntime/src/sensevoice-small.{h,cpp}) behind the plug-in seam
+// `class funasr::Model` (model.h:12-46), offline: the model the reference builds when the model directory's name contains
+// MODEL_SVS (offline-stream.cpp:50-56).  Same two builds as paraformer_hip.h: inside the reference tree (-DPFHIP_WITH_FUNASR) it
+// derives from the real funasr::Model + funasr::WfstDecodable; stand-alone from the small interfaces of paraformer_hip.h.
+// Model widths and wiring underneath are recalled from upstream FunASR (no SenseVoice file was available).
+#pragma once
+#include <string>
+#include <vector>
+
+#include "paraformer_hip.h"
+
+namespace funasr {
+
+class SenseVoiceSmallHip : public ParaformerHipBase
+#ifdef PFHIP_WITH_FUNASR
+    , public WfstDecodable
+#endif
+{
+ public:
+  SenseVoiceSmallHip() {}
+  ~SenseVoiceSmallHip() override;
+
+  // SenseVoiceSmall::InitAsr (sensevoice-small.cpp:22-56), the five-argument form offline-stream.cpp:89 calls.  am_model:
+  // <dir>/model.onnx (or model_quant.onnx) with am.mvn and config.yaml, read by pfhip_read_model_files("sensevoice", ...) and cached
+  // beside the source, or a container x.pfhip.bin of kind "sensevoice".  Exits on failure like the reference's (:48-51).
+  void InitAsr(const std::string& am_model, const std::string& am_cmvn, const std::string& am_config, const std::string& token_file,
+               int thread_num) override;
+  using ParaformerHipBase::InitAsr;        // the online / 2-pass overloads stay visible (empty in the base: the 2-pass seam is out of scope)
+  // The overload of model.h:33-34 (sensevoice-small.cpp:575-690).  Returns batch_in strings; the reference refuses batch_in != 1
+  // (:577-580), here the utterances are packed, all with the call's svs_lang / svs_itn.  decoder_handle == nullptr: the text of
+  // CTCSearch (:323-377), made on the host from the ids the device collapsed.  With a decoder handle the full log-prob rows of every
+  // utterance are handed to `((Decoder*)decoder_handle)->Search(rows, n_rows, vocab)` — the search itself (CTCPrefixBeamSearch /
+  // BeamSearch, :651-662) is not part of this path — and, when input_finished, FinalizeDecode() gives the text.
+  // "" for an utterance without one full fbank window (:584-587) and for every item when the device call fails.
+  std::vector<std::string> Forward(float** din, int* len, bool input_finished, std::string svs_lang = "auto", bool svs_itn = false,
+                                   void* decoder_handle = nullptr, int batch_in = 1)
+#ifdef PFHIP_WITH_FUNASR
+      override
+#endif
+      ;
+  using ParaformerHipBase::Forward;        // the Paraformer overloads stay visible (and keep their empty defaults)
+  // the same on 16-bit PCM as the server receives it (pfhip_svs_forward_s16); not a virtual
+  std::vector<std::string> ForwardPcm16(const int16_t* const* din, const int* len, bool input_finished, std::string svs_lang = "auto",
+                                        bool svs_itn = false, void* decoder_handle = nullptr, int batch_in = 1);
+  void StartUtterance() override {}
+  void EndUtterance() override {}
+  void Reset() override {}
+  std::string Rescoring() override { return ""; }             // "Not Imp" in the reference too (:686-690)
+  std::string GetLang() override { return language; }
+  int GetAsrSampleRate() override { return asr_sample_rate_; }
+  void SetBatchSize(int batch_size) override { batch_size_ = batch_size; }
+  int GetBatchSize() override { return batch_size_; }
+#ifdef PFHIP_WITH_FUNASR
+  std::shared_ptr<fst::Fst<fst::StdArc>> GetLm() const override { return nullptr; }       // InitLm is out of scope for this model
+  Vocab* GetVocab() const override { return vocab; }
+  PhoneSet* GetPhoneSet() const override { return nullptr; }
+  Vocab* GetLmVocab() const override { return nullptr; }
+  Vocab* GetVocab() override { return vocab; }
+  PhoneSet* GetPhoneSet() override { return nullptr; }
+  Vocab* GetLmVocab() override { return nullptr; }
+#endif
+  // of the last Forward of the calling thread, per utterance: the kept ids (the four leading tags included), the row of the T + 4
+  // sequence each kept run starts at, and exp(log-prob of that frame's arg-max)
+  const std::vector<std::vector<int>>& LastTokenIds() const;
+  const std::vector<std::vector<int>>& LastTokenFrames() const;
+  const std::vector<std::vector<float>>& LastTokenConfidence() const;
+  void SetDevice(int device) { device_ = device; }
+  pfhip_model* Handle() const { return handle_; }
+  // CTCSearch's text step (:348-375) on kept ids; without a vocabulary the ids from the fifth on, space-separated
+  std::string TokensToString(const std::vector<int>& ids) const;
+
+  std::string language = "auto";
+
+ private:
+  std::vector<std::string> ForwardAny(const void* const* din, bool s16, const int* len, bool input_finished, const std::string& svs_lang,
+                                      bool svs_itn, void* decoder_handle, int batch_in);
+  pfhip_model* handle_ = nullptr;
+  HipVocab* vocab = nullptr;
+  int asr_sample_rate_ = 16000, device_ = 0, batch_size_ = 1;
+};
+
+}  // namespace funasr

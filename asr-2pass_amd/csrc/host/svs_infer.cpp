@@ -1,0 +1,129 @@
+// Harness over SenseVoiceSmallHip (sensevoice_hip.h), the shape of a decoder thread's call:
+//   svs_infer <am_model> <tokens.json|-> <svs_lang> <svs_itn 0|1> <pcm_s16_file>...
+//   svs_infer --decoder <am_model> <pcm_s16_file>...      the same packed call with a stub Decoder as decoder_handle (the shape of
+//                          decoder_handoff.cpp for Paraformer): prints what every Search call received — "search <i> rows <n> vocab <V> :
+//                          <arg-max of each row>" — the Start / End / Finalize calls it saw, and the strings Forward returned
+//   svs_infer --handle-api <model_dir> <svs_lang> <svs_itn 0|1> <pcm_s16_file>      FunOfflineInit -> FunOfflineInferBuffer on the
+//                          directory (its name decides the model type); prints "seg <start> <end> : <ids>" and "text [<text>]"
+// One packed ForwardPcm16 over all files, then Forward on the floats of the first file alone.  Prints per utterance
+// "utt <i> ids : ..." / "utt <i> frames : ..." / "utt <i> text [<text>]", then "alone ids : ..." for the float call.
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <iterator>
+#include <string>
+#include <vector>
+
+#include "funasrruntime_hip.h"
+#include "sensevoice_hip.h"
+
+namespace {
+std::string dir_file(const std::string& model, const char* name) {      // <dir of am_model>/<name>, as the factory builds its paths
+  const size_t slash = model.rfind('/');
+  return (slash == std::string::npos ? std::string() : model.substr(0, slash + 1)) + name;
+}
+std::vector<std::vector<int16_t>> read_pcm(int argc, char** argv, int first) {
+  std::vector<std::vector<int16_t>> pcm;
+  for (int i = first; i < argc; ++i) {
+    std::ifstream f(argv[i], std::ios::binary);
+    const std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    pcm.emplace_back(reinterpret_cast<const int16_t*>(raw.data()), reinterpret_cast<const int16_t*>(raw.data()) + raw.size() / 2);
+  }
+  return pcm;
+}
+// what a caller's search would be handed: records every call
+struct StubDecoder : funasr::Decoder {
+  int starts = 0, ends = 0, finals = 0, searches = 0;
+  void StartUtterance() override { ++starts; }
+  void EndUtterance() override { ++ends; }
+  std::string Search(float* in, int len, int64_t token_nums) override {
+    std::printf("search %d rows %d vocab %lld :", searches, len, (long long)token_nums);
+    for (int t = 0; t < len; ++t) {
+      const float* row = in + (size_t)t * token_nums;
+      int best = 0;
+      for (int64_t v = 1; v < token_nums; ++v) if (row[v] > row[best]) best = (int)v;
+      std::printf(" %d", best);
+    }
+    std::printf("\n");
+    return "partial" + std::to_string(searches++);
+  }
+  std::string FinalizeDecode(bool, std::vector<float>, std::vector<float>) override { return "final" + std::to_string(finals++); }
+};
+}  // namespace
+
+static int decoder_mode(int argc, char** argv) {
+  if (argc < 4) return 2;
+  const std::vector<std::vector<int16_t>> pcm = read_pcm(argc, argv, 3);
+  funasr::SenseVoiceSmallHip model;
+  model.InitAsr(argv[2], dir_file(argv[2], "am.mvn"), dir_file(argv[2], "config.yaml"), "", 1);
+  std::vector<const int16_t*> ptr;
+  std::vector<int> len;
+  for (const auto& p : pcm) { ptr.push_back(p.data()); len.push_back((int)p.size()); }
+  StubDecoder dec;
+  for (int finished = 0; finished < 2; ++finished) {
+    const std::vector<std::string> text = model.ForwardPcm16(ptr.data(), len.data(), finished != 0, "auto", false, &dec, (int)pcm.size());
+    for (size_t i = 0; i < text.size(); ++i) std::printf("finished %d utt %zu text [%s]\n", finished, i, text[i].c_str());
+  }
+  std::printf("calls starts %d ends %d finals %d searches %d\n", dec.starts, dec.ends, dec.finals, dec.searches);
+  return 0;
+}
+
+static int handle_api(int argc, char** argv) {
+  if (argc < 6) return 2;
+  std::map<std::string, std::string> paths;
+  paths[MODEL_DIR] = argv[2];
+  std::ifstream f(argv[5], std::ios::binary);
+  const std::vector<char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  FUNASR_HANDLE h = FunOfflineInit(paths, 1, false, 1);
+  const std::vector<std::vector<float>> no_hw;
+  FUNASR_RESULT r = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, 16000, "pcm", true, 800, 60000, nullptr,
+                                          argv[3], std::atoi(argv[4]) != 0);
+  if (!r) { std::fprintf(stderr, "inference failed\n"); return 1; }
+  const auto& segs = FunASRGetSegments(r);
+  const auto& ids = FunASRGetSegmentIds(r);
+  for (size_t i = 0; i < segs.size(); ++i) {
+    std::printf("seg %d %d :", segs[i].first, segs[i].second);
+    for (int id : ids[i]) std::printf(" %d", id);
+    std::printf("\n");
+  }
+  std::printf("handle text [%s]\n", FunASRGetResult(r, 0));
+  FunASRFreeResult(r);
+  FunOfflineUninit(h);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "--handle-api") return handle_api(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "--decoder") return decoder_mode(argc, argv);
+  if (argc < 6) {
+    std::fprintf(stderr, "usage: %s am_model tokens.json|- svs_lang svs_itn pcm_s16_file...\n", argv[0]);
+    return 2;
+  }
+  const std::string tokens = std::string(argv[2]) == "-" ? "" : argv[2], lang = argv[3];
+  const bool itn = std::atoi(argv[4]) != 0;
+  const std::vector<std::vector<int16_t>> pcm = read_pcm(argc, argv, 5);
+  funasr::SenseVoiceSmallHip model;
+  model.SetBatchSize((int)pcm.size());
+  model.InitAsr(argv[1], dir_file(argv[1], "am.mvn"), dir_file(argv[1], "config.yaml"), tokens, 1);
+  std::vector<const int16_t*> ptr;
+  std::vector<int> len;
+  for (const auto& p : pcm) { ptr.push_back(p.data()); len.push_back((int)p.size()); }
+  const std::vector<std::string> text = model.ForwardPcm16(ptr.data(), len.data(), true, lang, itn, nullptr, (int)pcm.size());
+  for (size_t i = 0; i < text.size(); ++i) {
+    std::printf("utt %zu ids :", i);
+    for (int id : model.LastTokenIds()[i]) std::printf(" %d", id);
+    std::printf("\nutt %zu frames :", i);
+    for (int fr : model.LastTokenFrames()[i]) std::printf(" %d", fr);
+    std::printf("\nutt %zu confidence_ok %d\nutt %zu text [%s]\n", i, (int)(model.LastTokenConfidence()[i].size() == model.LastTokenIds()[i].size()), i,
+                text[i].c_str());
+  }
+  std::vector<float> f32(pcm[0].size());
+  for (size_t i = 0; i < f32.size(); ++i) f32[i] = (float)pcm[0][i] / 32768.f;
+  float* one = f32.data();
+  int n = (int)f32.size();
+  const std::vector<std::string> alone = model.Forward(&one, &n, true, lang, itn, nullptr, 1);
+  std::printf("alone ids :");
+  for (int id : model.LastTokenIds()[0]) std::printf(" %d", id);
+  std::printf("\nalone text [%s]\n", alone[0].c_str());
+  return 0;
+}

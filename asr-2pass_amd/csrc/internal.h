@@ -260,6 +260,14 @@ struct pfhip_model {
   bool want_fires = false, have_fires = false;
   std::atomic<int> fires_enqueue{0};
   const int32_t* host_fires() const { return h_counts.i() + 2 * B; }
+  // SenseVoice (cfg.svs): the prompt ids of the forward being run [B][4] (a range-guard re-run reads them again), whether the caller
+  // wants full log-prob rows (the unfused head), the debug switch to the unfused head, the chunks the last unfused head ran, the
+  // results of the last forward on the host (h_counts: token_num [B] | ids, tok_frame, tok_logp [B][maxT] | frame ids, logp [M])
+  std::vector<int32_t> svs_prompt;
+  float* svs_logp_host = nullptr;
+  int debug_ctc_unfused = 0, svs_head_chunks = 0, svs_unfused_forwards = 0;
+  Buf svs_ws, svs_frame, svs_logits, svs_logp;
+  int *m_feat_off = nullptr, *m_prompt = nullptr;
   // device views into meta / dmeta
   int *m_frame_off = nullptr, *m_nframes = nullptr, *m_row_off = nullptr, *m_len = nullptr,
       *m_row_pos = nullptr, *m_row_len = nullptr;

@@ -285,6 +285,26 @@ void launch_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, i
 // range_flag (may be null): bit 0 is raised when a row's log-sum-exp is not finite (NaN / Inf reached the logits).
 void launch_logsoftmax_argmax(const float* logits, int ldl, int ML, int V, float* logp, int32_t* ids,
                               hipStream_t s, int* range_flag = nullptr);
+// ---- CTC head and collapse (ctc_head.hip) --------------------------------------------------------------------------------------
+// The head of a CTC model without its logits matrix: per row of X [M, K] (K % 32 == 0; exactly M rows are read) the arg-max over
+// x W^T + bias (W [V, K], exactly V rows; first maximum wins), logp_best = that logit - log-sum-exp of the row, and (lse non-null)
+// the log-sum-exp.  Arithmetic of gemm_x3.hip with the given power-of-two w_scale.  workspace: ctc_head_workspace_bytes(M, V) bytes
+// of per-tile (max, arg-max, sum exp) partials.  false (nothing launched) for what the kernels do not take.
+size_t ctc_head_workspace_bytes(int M, int V);
+bool launch_ctc_head(const float* X, int ldx, const float* W, int ldw, const float* bias, float w_scale, int M, int V, int K, int32_t* ids,
+                     float* logp_best, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s, int* range_flag = nullptr);
+// SenseVoice's four prompt rows: rows row_off[b] .. + 3 of feats (row stride ld) = rows prompt[4 b .. 4 b + 3] of E [16][D], for every
+// utterance with rows (len[b] >= 4; device arrays).  best[r] = logp[r][ids[r]].
+void launch_svs_prompt_rows(const float* E, int D, const int* prompt, const int* row_off, const int* len, int B, float* feats, int ld,
+                            hipStream_t s);
+void launch_gather_best(const float* logp, int ld, const int32_t* ids, int M, float* best, hipStream_t s);
+// CTC collapse per utterance b over frames [row_off[b], row_off[b] + len[b]) (device arrays): a frame is kept when its id is not
+// `blank` and differs from the previous frame's.  ids / tok_frame / tok_logp [B][max_tokens] (the two last may be null): the kept
+// id, its 0-based frame inside the utterance and a copy of frame_logp there; token_num[b] = the number kept, also beyond max_tokens
+// (tokens past max_tokens are counted, not stored).  ctc_collapse_chunk(): the frames one trip of the scan covers.
+int ctc_collapse_chunk();
+bool launch_ctc_collapse(const int32_t* frame_ids, const float* frame_logp, const int* row_off, const int* len, int B, int blank,
+                         int max_tokens, int32_t* ids, int32_t* tok_frame, float* tok_logp, int32_t* token_num, hipStream_t s);
 // The same head with the k best columns of every row (topk.hip; 1 <= k <= kTopkMax <= V): topk_ids / topk_logp [ML][k], larger logit
 // first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry of its column bit for bit.  The
 // log-sum-exp is formed with logp null as well.  false (nothing launched) when the arguments are outside that.

@@ -859,6 +859,8 @@ struct AsrConfig {      // weights.py PARAFORMER_LARGE
   double cif_threshold = 1.0, tail_threshold = 0.45, smooth_factor = 1.0, noise_threshold = 0.0, smooth_factor2 = 1.0, noise_threshold2 = 0.0;
   bool has_sf2 = false, has_nt2 = false;
   std::string lang;
+  // SenseVoiceSmall (weights.py SENSEVOICE_SMALL; recalled from upstream FunASR): encoder_conf.tp_blocks more layers behind the encoder
+  int tp_layers = 20, blank_id = 0;
 };
 
 // weights.py tensor_specs, same order
@@ -926,6 +928,30 @@ SpecList asr_specs(const AsrConfig& c) {
     s.lin("bias.dec.out", d, d);
     s.add("bias.out.w", {d, 2 * d});
   }
+  return s;
+}
+
+// weights.py svs_tensor_specs, same order
+SpecList svs_specs(const AsrConfig& c) {
+  SpecList s;
+  const int64_t d = c.d_model, f = c.ffn, k = c.kernel, feat = (int64_t)c.n_mels * c.lfr_m;
+  s.add("cmvn.mean", {feat});
+  s.add("cmvn.istd", {feat});
+  s.add("svs.embed.w", {16, feat});
+  auto layer = [&](const std::string& p, int64_t in_f) {
+    s.ln(p + "norm1", in_f);
+    s.lin(p + "qkv", 3 * d, in_f);
+    s.add(p + "fsmn.w", {d, k});
+    s.lin(p + "out", d, d);
+    s.ln(p + "norm2", d);
+    s.lin(p + "ffn1", f, d);
+    s.lin(p + "ffn2", d, f);
+  };
+  for (int i = 0; i < c.enc_layers; ++i) layer("enc." + std::to_string(i) + ".", i == 0 ? feat : d);
+  s.ln("enc.after_norm", d);
+  for (int i = 0; i < c.tp_layers; ++i) layer("tp." + std::to_string(i) + ".", d);
+  s.ln("tp.norm", d);
+  s.lin("ctc", c.vocab, d);
   return s;
 }
 
@@ -1003,6 +1029,29 @@ NameMap asr_name_map(const AsrConfig& c) {
     map_lin(m, "bias.dec.out", "decoder.bias_decoder.src_attn.linear_out");
     m["bias.out.w"] = "decoder.bias_output.weight";
   }
+  return m;
+}
+
+// convert.py sensevoice_name_map: container tensor -> UPSTREAM SenseVoiceSmall state_dict key (recalled from upstream FunASR; no
+// SenseVoice file was available)
+NameMap svs_name_map(const AsrConfig& c) {
+  NameMap m;
+  m["svs.embed.w"] = "embed.weight";
+  auto layer = [&](const std::string& p, const std::string& src) {
+    map_ln(m, p + "norm1", src + ".norm1");
+    map_lin(m, p + "qkv", src + ".self_attn.linear_q_k_v");
+    m[p + "fsmn.w"] = src + ".self_attn.fsmn_block.weight";
+    map_lin(m, p + "out", src + ".self_attn.linear_out");
+    map_ln(m, p + "norm2", src + ".norm2");
+    map_lin(m, p + "ffn1", src + ".feed_forward.w_1");
+    map_lin(m, p + "ffn2", src + ".feed_forward.w_2");
+  };
+  for (int i = 0; i < c.enc_layers; ++i)
+    layer("enc." + std::to_string(i) + ".", i == 0 ? "encoder.encoders0.0" : "encoder.encoders." + std::to_string(i - 1));
+  map_ln(m, "enc.after_norm", "encoder.after_norm");
+  for (int i = 0; i < c.tp_layers; ++i) layer("tp." + std::to_string(i) + ".", "encoder.tp_encoders." + std::to_string(i));
+  map_ln(m, "tp.norm", "encoder.tp_norm");
+  map_lin(m, "ctc", "ctc.ctc_lo");
   return m;
 }
 
@@ -1429,12 +1478,29 @@ void load_asr(const std::string& model, const std::string& second, const std::st
   // the heads that are there decide (config.yaml names the model class, the weights decide)
   c.contextual = has_key(state, "decoder.bias_output.weight") || has_key(state, "bias_embed.weight") ? 1 : 0;
   c.timestamp = has_key(state, "predictor.upsample_cnn.weight") ? 1 : 0;
-  c.vocab = (int)dim_of(state, "decoder.output_layer.weight", 0, "the vocabulary");
+  // the kind, from the initialisers: a CTC head and no decoder is SenseVoiceSmall (the reference goes by the directory's name,
+  // offline-stream.cpp:50-56; the weights decide here, as for the heads above)
+  const bool svs = has_key(state, "ctc.ctc_lo.weight") && !has_key(state, "decoder.output_layer.weight");
+  c.vocab = (int)dim_of(state, svs ? "ctc.ctc_lo.weight" : "decoder.output_layer.weight", 0, "the vocabulary");
 
   std::vector<float> shift, rescale;
   parse_am_mvn(slurp(cmvn), shift, rescale);
   out.sources.push_back(cmvn);
   out.sources.push_back(config);
+  if (svs) {
+    c.tp_layers = (int)enc.number("tp_blocks", c.tp_layers);
+    std::string sj = "{\"kind\": \"sensevoice\", \"d_model\": " + std::to_string(c.d_model) + ", \"n_head\": " + std::to_string(c.n_head) +
+                     ", \"ffn\": " + std::to_string(c.ffn) + ", \"enc_layers\": " + std::to_string(c.enc_layers) + ", \"tp_layers\": " +
+                     std::to_string(c.tp_layers) + ", \"dec_layers\": 0, \"dec_ffn\": " + std::to_string(c.ffn) + ", \"kernel\": " +
+                     std::to_string(c.kernel) + ", \"vocab\": " + std::to_string(c.vocab) + ", \"blank_id\": " + std::to_string(c.blank_id) +
+                     ", \"n_mels\": " + std::to_string(c.n_mels) + ", \"lfr_m\": " + std::to_string(c.lfr_m) + ", \"lfr_n\": " +
+                     std::to_string(c.lfr_n) + ", \"fs\": " + std::to_string(c.fs);
+    if (!c.lang.empty()) sj += ", \"lang\": \"" + json_escape(c.lang) + "\"";
+    sj += "}";
+    fill(svs_specs(c), svs_name_map(c), state, {{"cmvn.mean", shift}, {"cmvn.istd", rescale}}, sj, out);
+    finish(prefix, files, out);
+    return;
+  }
 
   std::string cj = "{\"d_model\": " + std::to_string(c.d_model) + ", \"n_head\": " + std::to_string(c.n_head) + ", \"ffn\": " + std::to_string(c.ffn) +
                    ", \"enc_layers\": " + std::to_string(c.enc_layers) + ", \"dec_layers\": " + std::to_string(c.dec_layers) +

@@ -21,9 +21,14 @@ pfhip_status read_files(const std::string& kind, const char* model, const char* 
                         const char* config, pfhip_files::Container& c) {
   try {
     if (kind == "asr") pfhip_files::load_asr(nz(model), nz(second), nz(hotword), nz(cmvn), nz(config), c);
+    else if (kind == "sensevoice") {      // the same reader (it tells the kinds apart by the initialisers), and nothing but that kind
+      pfhip_files::load_asr(nz(model), "", "", nz(cmvn), nz(config), c);
+      if (c.manifest.find("\"kind\": \"sensevoice\"") == std::string::npos)
+        return fail(PFHIP_ERR_FORMAT, std::string(nz(model)) + " is not a SenseVoice model (no ctc.ctc_lo, or a decoder): read it as \"asr\"");
+    }
     else if (kind == "vad") pfhip_files::load_vad(nz(model), nz(cmvn), nz(config), c);
     else if (kind == "punc") pfhip_files::load_punc(nz(model), nz(config), c);
-    else return fail(PFHIP_ERR_ARG, "kind must be asr, vad or punc");
+    else return fail(PFHIP_ERR_ARG, "kind must be asr, sensevoice, vad or punc");
   } catch (const pfhip_files::FormatError& e) {
     return fail(PFHIP_ERR_FORMAT, e.what());
   } catch (const std::exception& e) {

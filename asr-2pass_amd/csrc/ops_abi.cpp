@@ -294,6 +294,21 @@ int pfhip_op_logsoftmax_topk(const float* logits, int ldl, int M, int V, int k, 
   if (!pfhip::launch_logsoftmax_topk(logits, ldl, M, V, k, logp, ids, topk_ids, topk_logp, S(stream))) return (int)hipErrorInvalidValue;
   return done();
 }
+size_t pfhip_op_ctc_head_workspace_bytes(int M, int V) { return M > 0 && V > 0 ? pfhip::ctc_head_workspace_bytes(M, V) : 0; }
+int pfhip_op_ctc_head(const float* X, int ldx, const float* W, int ldw, const float* bias, float w_scale, int M, int V, int K,
+                      int32_t* ids, float* logp_best, float* lse, void* workspace, size_t workspace_bytes, void* stream) {
+  // the launcher checks shapes, strides, buffers and the workspace size before it launches anything
+  if (!pfhip::launch_ctc_head(X, ldx, W, ldw, bias, w_scale, M, V, K, ids, logp_best, lse, workspace, workspace_bytes, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+int pfhip_op_ctc_collapse(const int32_t* frame_ids, const float* frame_logp, const int* row_off, const int* len, int B, int blank,
+                          int max_tokens, int32_t* ids, int32_t* tok_frame, float* tok_logp, int32_t* token_num, void* stream) {
+  if (!pfhip::launch_ctc_collapse(frame_ids, frame_logp, row_off, len, B, blank, max_tokens, ids, tok_frame, tok_logp, token_num, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+int pfhip_op_ctc_collapse_chunk(void) { return pfhip::ctc_collapse_chunk(); }
 
 // ---- the scan, cache and row kernels (tests only: the descriptor-taking ones upload their descriptors synchronously) ----------------
 static int cif_stream_op(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,

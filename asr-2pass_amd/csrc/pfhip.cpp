@@ -160,6 +160,21 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   c.tail_threshold = (float)jc->number("tail_threshold", c.tail_threshold);
   c.smooth_factor = (float)jc->number("smooth_factor", c.smooth_factor);
   c.noise_threshold = (float)jc->number("noise_threshold", c.noise_threshold);
+  if (const pfhip::JValue* kind = jc->get("kind")) {      // containers without `kind` mean what they always meant
+    if (kind->str == "sensevoice") c.svs = 1;
+    else if (!kind->str.empty() && kind->str != "paraformer") return fail(PFHIP_ERR_FORMAT, "unknown container kind " + kind->str);
+  }
+  if (c.svs) {
+    c.tp_layers = (int)jc->number("tp_layers", 0);
+    c.blank_id = (int)jc->number("blank_id", 0);
+    if (c.dec_layers != 0 || c.contextual || c.timestamp) return fail(PFHIP_ERR_FORMAT, "a sensevoice container has no decoder, hotwords or timestamp head");
+    // (without a tp layer the forward would have no place for enc.after_norm: the hand-off is the first tp layer's)
+    if (c.tp_layers < 1 || c.blank_id < 0 || c.blank_id >= c.vocab) return fail(PFHIP_ERR_FORMAT, "a sensevoice container needs tp_layers >= 1 and blank_id inside the vocabulary");
+    c.dec_ffn = c.ffn;
+  }
+  const int n_layers = c.enc_layers + c.tp_layers;
+  // the weight prefix of layer i of that list
+  auto layer_prefix = [&](int i) { return i < c.enc_layers ? "enc." + std::to_string(i) + "." : "tp." + std::to_string(i - c.enc_layers) + "."; };
 
   // what the gfx950 kernels are specialised for
   if (c.d_model <= 0 || c.n_head <= 0 || c.d_model % 64 || c.d_model % c.n_head || !pfhip::head_dim_supported(c.d_model / c.n_head))
@@ -221,8 +236,8 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   };
   const int d = c.d_model;
   bool ok = need("cmvn.mean", {w->feat_dim}) && need("cmvn.istd", {w->feat_dim});
-  for (int i = 0; ok && i < c.enc_layers; ++i) {
-    const std::string p = "enc." + std::to_string(i) + ".";
+  for (int i = 0; ok && i < n_layers; ++i) {
+    const std::string p = layer_prefix(i);
     const int in = i == 0 ? w->feat_dim : d;
     ok = need(p + "norm1.g", {in}) && need(p + "norm1.b", {in}) && need(p + "qkv.w", {3 * d, in}) &&
          need(p + "qkv.b", {3 * d}) && need(p + "fsmn.w", {d, c.kernel}) && need(p + "out.w", {d, d}) &&
@@ -230,8 +245,12 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
          need(p + "ffn1.w", {c.ffn, d}) && need(p + "ffn1.b", {c.ffn}) && need(p + "ffn2.w", {d, c.ffn}) &&
          need(p + "ffn2.b", {d});
   }
-  ok = ok && need("enc.after_norm.g", {d}) && need("enc.after_norm.b", {d}) && need("pred.conv.w", {d, d, 3}) &&
-       need("pred.conv.b", {d}) && need("pred.out.w", {1, d}) && need("pred.out.b", {1});
+  ok = ok && need("enc.after_norm.g", {d}) && need("enc.after_norm.b", {d});
+  if (c.svs)
+    ok = ok && need("svs.embed.w", {16, w->feat_dim}) && need("tp.norm.g", {d}) && need("tp.norm.b", {d}) && need("ctc.w", {c.vocab, d}) &&
+         need("ctc.b", {c.vocab});
+  else
+    ok = ok && need("pred.conv.w", {d, d, 3}) && need("pred.conv.b", {d}) && need("pred.out.w", {1, d}) && need("pred.out.b", {1});
   auto need_ffn = [&](const std::string& p) {
     return need(p + "norm1.g", {d}) && need(p + "norm1.b", {d}) && need(p + "ffn1.w", {c.dec_ffn, d}) &&
            need(p + "ffn1.b", {c.dec_ffn}) && need(p + "ffn_norm.g", {c.dec_ffn}) &&
@@ -243,8 +262,9 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
          need(p + "norm3.g", {d}) && need(p + "norm3.b", {d}) && need(p + "q.w", {d, d}) && need(p + "q.b", {d}) &&
          need(p + "kv.w", {2 * d, d}) && need(p + "kv.b", {2 * d}) && need(p + "out.w", {d, d}) && need(p + "out.b", {d});
   }
-  ok = ok && need_ffn("dec3.") && need("dec.after_norm.g", {d}) && need("dec.after_norm.b", {d}) &&
-       need("dec.out.w", {c.vocab, d}) && need("dec.out.b", {c.vocab});
+  if (!c.svs)
+    ok = ok && need_ffn("dec3.") && need("dec.after_norm.g", {d}) && need("dec.after_norm.b", {d}) &&
+         need("dec.out.w", {c.vocab, d}) && need("dec.out.b", {c.vocab});
   if (ok && c.contextual) {      // contextual (hotword) model: bias embedder + bias decoder
     if (c.dec_layers < 1) return fail(PFHIP_ERR_FORMAT, "contextual model needs a decoder");
     ok = need("bias.embed.w", {c.vocab, d}) && need("bias.lstm.w_ih", {4 * d, d}) && need("bias.lstm.w_hh", {4 * d, d}) &&
@@ -269,6 +289,8 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
       std::memcpy(&p[(size_t)n * w->feat_pad], w0.h + (size_t)n * w->feat_dim, sizeof(float) * w->feat_dim);
     HIP_TRY(w->w0qkv.upload(p));
     reg_scale(w->w0qkv.p, p.data(), p.size());
+  }
+  if (!c.svs) {
     const Tensor& cw = T("pred.conv.w");
     std::vector<float> q((size_t)d * 3 * d);
     for (int n = 0; n < d; ++n)
@@ -301,8 +323,8 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
         worst = std::max(worst, std::sqrt((double)K) * std::sqrt(ss) + std::fabs(dot));
       }
     };
-    for (int i = 0; i < c.enc_layers; ++i) {
-      const std::string ep = "enc." + std::to_string(i) + ".";
+    for (int i = 0; i < n_layers; ++i) {
+      const std::string ep = layer_prefix(i);
       ln_linear(ep + "qkv.w", ep + "qkv.b", ep + "norm1");
       ln_linear(ep + "ffn1.w", ep + "ffn1.b", ep + "norm2");
     }
@@ -322,6 +344,7 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
     ln_linear("dec3.ffn1.w", "dec3.ffn1.b", "dec3.norm1");
     ln_linear("dec3.ffn2.w", "", "dec3.ffn_norm");
     ln_linear("dec.out.w", "dec.out.b", "dec.after_norm");
+    ln_linear("ctc.w", "ctc.b", "tp.norm");
     if (c.contextual) ln_linear("bias.dec.q.w", "bias.dec.q.b", "bias.dec.norm3");
     w->static_bound = worst;
     w->always_exact = !(worst < 32768.0);
@@ -340,9 +363,9 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
     return f;
   };
   w->cmvn_mean = T("cmvn.mean").d; w->cmvn_istd = T("cmvn.istd").d;
-  w->enc.resize((size_t)c.enc_layers);
-  for (int i = 0; i < c.enc_layers; ++i) {
-    const std::string p = "enc." + std::to_string(i) + ".";
+  w->enc.resize((size_t)n_layers);
+  for (int i = 0; i < n_layers; ++i) {
+    const std::string p = layer_prefix(i);
     EncLayer& L = w->enc[(size_t)i];
     L.norm1 = norm(p + "norm1"); L.norm2 = norm(p + "norm2");
     L.qkv = lin(p + "qkv.w", p + "qkv.b"); L.out = lin(p + "out.w", p + "out.b");
@@ -351,8 +374,13 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
   }
   w->enc[0].qkv.w = w->w0qkv.f(); w->enc[0].qkv.scale = scale_of(w->w0qkv.p);
   w->enc_after = norm("enc.after_norm");
-  w->pred.conv = Linear{w->predconv.f(), T("pred.conv.b").d, scale_of(w->predconv.p)};
-  w->pred.out_w = T("pred.out.w").d; w->pred.out_b = T("pred.out.b").d;
+  if (c.svs) {
+    w->tp_norm = norm("tp.norm");
+    w->svs_embed = T("svs.embed.w").d;
+  } else {
+    w->pred.conv = Linear{w->predconv.f(), T("pred.conv.b").d, scale_of(w->predconv.p)};
+    w->pred.out_w = T("pred.out.w").d; w->pred.out_b = T("pred.out.b").d;
+  }
   w->dec.resize((size_t)c.dec_layers);
   for (int i = 0; i < c.dec_layers; ++i) {
     const std::string p = "dec." + std::to_string(i) + ".";
@@ -362,8 +390,10 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
     L.fsmn_w = T(p + "fsmn.w").d;
     L.q = lin(p + "q.w", p + "q.b"); L.kv = lin(p + "kv.w", p + "kv.b"); L.out = lin(p + "out.w", p + "out.b");
   }
-  w->dec3 = dec_ffn("dec3.");
-  w->dec_after = norm("dec.after_norm");
+  if (!c.svs) {
+    w->dec3 = dec_ffn("dec3.");
+    w->dec_after = norm("dec.after_norm");
+  }
   if (c.contextual) {
     Contextual& b = w->bias;
     b.embed_w = T("bias.embed.w").d;
@@ -404,13 +434,13 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
       *img = Planes{hi, hi + half, src.scale};
       return 2 * half;
     };
-    const int L = c.enc_layers;
+    const int L = n_layers;
     {
       std::vector<float> wq((size_t)L * 3 * d * d + (size_t)pfhip::kTileN * d, 0.f), bq((size_t)L * 3 * d + pfhip::kTileN, 0.f);
       std::vector<float> wf((size_t)L * c.ffn * d + (size_t)pfhip::kTileN * d, 0.f), bf((size_t)L * c.ffn + pfhip::kTileN, 0.f);
       std::vector<float> sq(bq.size(), 0.f), sf(bf.size(), 0.f);
       for (int i = 0; i < L; ++i) {
-        const std::string ep = "enc." + std::to_string(i) + ".";
+        const std::string ep = layer_prefix(i);
         if (i > 0) foldk(ep + "qkv.w", ep + "qkv.b", ep + "norm1", 3 * d, d, &wq[(size_t)i * 3 * d * d], &bq[(size_t)i * 3 * d], &sq[(size_t)i * 3 * d]);
         foldk(ep + "ffn1.w", ep + "ffn1.b", ep + "norm2", c.ffn, d, &wf[(size_t)i * c.ffn * d], &bf[(size_t)i * c.ffn], &sf[(size_t)i * c.ffn]);
       }
@@ -449,7 +479,7 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
         w->enc_planes = true;
       }
     }
-    if (c.dec_ffn % pfhip::kTileN == 0) {          // decoder FFNs: layers 0..dec_layers-1 and dec3 (the last entry)
+    if (!c.svs && c.dec_ffn % pfhip::kTileN == 0) {          // decoder FFNs: layers 0..dec_layers-1 and dec3 (the last entry)
       const int DL = c.dec_layers + 1, f = c.dec_ffn;
       std::vector<float> w1((size_t)DL * f * d + (size_t)pfhip::kTileN * d, 0.f), b1((size_t)DL * f + pfhip::kTileN, 0.f), s1(b1.size(), 0.f);
       std::vector<float> w2((size_t)DL * d * f + (size_t)pfhip::kTileN * f, 0.f), b2((size_t)DL * d + pfhip::kTileN, 0.f), s2(b2.size(), 0.f);
@@ -510,10 +540,12 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
     w->kv_all = Linear{w->kv_all_w.f(), w->kv_all_b.f(), scale_of(w->kv_all_w.p)};
   }
   {
+    const char* head = c.svs ? "ctc" : "dec.out";
     std::vector<float> vb((size_t)w->vocab_pad, 0.f);
-    std::memcpy(vb.data(), T("dec.out.b").h, sizeof(float) * c.vocab);
+    std::memcpy(vb.data(), T(std::string(head) + ".b").h, sizeof(float) * c.vocab);
     HIP_TRY(w->vocab_bias.upload(vb));
-    w->dec_out = Linear{T("dec.out.w").d, w->vocab_bias.f(), scale_of(T("dec.out.w").d)};
+    const float* hw = T(std::string(head) + ".w").d;
+    (c.svs ? w->ctc : w->dec_out) = Linear{hw, w->vocab_bias.f(), scale_of(hw)};
   }
   if (c.timestamp) {
     // ConvTranspose1d(d, d, k = stride = 3): out[3t + j][co] = b[co] + sum_ci x[t][ci] * w[ci][co][j]  ==  one GEMM with
@@ -659,6 +691,8 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
                              bool feats_only, ForwardPaths* paths);
 pfhip_status forward_cif(pfhip_model* m, hipStream_t s);
 pfhip_status forward_decoder(pfhip_model* m, hipStream_t s, const ForwardPaths& paths);
+pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s);
+pfhip_status read_range_flag(pfhip_model* m, hipStream_t s, bool sync);
 
 pfhip_status enqueue_locked(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                             int B, hipStream_t s, bool feats_only) {
@@ -667,6 +701,7 @@ pfhip_status enqueue_locked(pfhip_model* m, PcmView d_pcm, const int64_t* sample
   ForwardPaths paths;
   pfhip_status st = forward_encoder(m, d_pcm, sample_off, n_samples, B, s, feats_only, &paths);
   if (st || feats_only || m->M == 0) return st;
+  if (m->weights->cfg.svs) return svs_head_locked(m, s);      // no CIF, no decoder, no second host sync
   st = forward_cif(m, s);
   if (st || m->ML == 0) return st;
   return forward_decoder(m, s, paths);
@@ -685,6 +720,9 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
     if (n_samples[b] < 0) return fail(PFHIP_ERR_ARG, "negative sample count");
     F[b] = n_samples[b] < 400 ? 0 : 1 + (n_samples[b] - 400) / 160;        // feature-window.cc:84-87
     m->T[b] = (F[b] + c.lfr_n - 1) / c.lfr_n;                               // paraformer.cpp:425
+    // SenseVoice: four prompt rows in front of the features (sensevoice-small.cpp:597-640); an utterance without frames has no rows at
+    // all, as the reference returns "" before it runs the graph (:584-587)
+    if (c.svs && !feats_only && m->T[b] > 0) m->T[b] += 4;
     m->row_off[b] = m->M;
     m->M += m->T[b];
     m->maxT = std::max(m->maxT, m->T[b]);
@@ -695,7 +733,9 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
   const int Mp = round_up(M, pfhip::kTileM);
 
   // ---- metadata: one pinned staging buffer, one H2D copy ---------------------------------------------
-  const size_t n_ints = (size_t)2 * B /*sample_off as int64*/ + (B + 1) + 3 * (size_t)B + 2 * (size_t)M + 8;
+  const bool svs = c.svs && !feats_only;
+  if (svs && (int)m->svs_prompt.size() != 4 * B) return fail(PFHIP_ERR_ARG, "a SenseVoice model is run through pfhip_svs_forward");
+  const size_t n_ints = (size_t)2 * B /*sample_off as int64*/ + (B + 1) + 3 * (size_t)B + 2 * (size_t)M + 8 + (svs ? 5 * (size_t)B : 0);
   HIP_TRY(m->h_meta.ensure(n_ints * 4));
   HIP_TRY(m->meta.ensure(n_ints * 4));
   {
@@ -707,6 +747,11 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
     std::memcpy(hm + o, F.data(), 4 * B); m->m_nframes = dm + o; o += B;
     std::memcpy(hm + o, m->row_off.data(), 4 * B); m->m_row_off = dm + o; o += B;
     std::memcpy(hm + o, m->T.data(), 4 * B); m->m_len = dm + o; o += B;
+    if (svs) {        // where the front end writes utterance b's features (behind its prompt rows), and the prompt ids
+      for (int b = 0; b < B; ++b) hm[o + b] = m->row_off[b] + 4;
+      m->m_feat_off = dm + o; o += B;
+      std::memcpy(hm + o, m->svs_prompt.data(), 4 * 4 * (size_t)B); m->m_prompt = dm + o; o += 4 * (size_t)B;
+    }
     if (o & 1) ++o;
     m->m_row_pos = dm + o;
     for (int b = 0; b < B; ++b) for (int t = 0; t < m->T[b]; ++t) hm[o + m->row_off[b] + t] = t;
@@ -753,12 +798,15 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
     for (int b = 0; b < B; ++b) in_bytes += (double)d_pcm.sample_bytes() * n_samples[b];
     Scope sc(m, s, K_FBANK, 0, in_bytes + 4.0 * FD * M);
     const pfhip::FbankTables tb = w.ft.fbank(w.cmvn_mean, w.cmvn_istd);
+    const int* feat_off = svs ? m->m_feat_off : m->m_row_off;
     if (d_pcm.s16)
-      pfhip::launch_fbank_lfr_cmvn(d_pcm.i16(), m->m_sample_off, m->m_frame_off, m->m_nframes, m->m_row_off, B,
+      pfhip::launch_fbank_lfr_cmvn(d_pcm.i16(), m->m_sample_off, m->m_frame_off, m->m_nframes, feat_off, B,
                                    total_frames, tb, m->feats.f(), s);
     else
-      pfhip::launch_fbank_lfr_cmvn(d_pcm.f32(), m->m_sample_off, m->m_frame_off, m->m_nframes, m->m_row_off, B,
+      pfhip::launch_fbank_lfr_cmvn(d_pcm.f32(), m->m_sample_off, m->m_frame_off, m->m_nframes, feat_off, B,
                                    total_frames, tb, m->feats.f(), s);
+    // E[lid], E[1], E[2], E[textnorm] into the four rows in front of them
+    if (svs) pfhip::launch_svs_prompt_rows(w.svs_embed, FD, m->m_prompt, m->m_row_off, m->m_len, B, m->feats.f(), FD, s);
   }
   if (feats_only) { HIP_TRY(hipGetLastError()); return PFHIP_OK; }
 
@@ -832,12 +880,23 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
   pfhip::AttnOp self_att = qkv_attention(m->qkv.f(), d, m->ctx.f());
   self_att.q_off = self_att.kv_off = m->m_row_off; self_att.q_len = self_att.kv_len = m->m_len;
   self_att.B = B; self_att.H = c.n_head; self_att.max_q_len = m->maxT; self_att.scale = att_scale; self_att.head_dim = hd;
-  for (int i = 0; i < c.enc_layers; ++i) {
+  // SenseVoice runs the loop on over its tp layers: after enc.after_norm the normalised rows ARE the residual stream (in `enc`; the
+  // last LayerNorm, tp.norm, writes back into `x`).  Two things set a layer apart: `first` — input of the feature width and no
+  // residual (enc.0 only) — and `no_stats` — no producer GEMM has left row statistics or plane images of its input, so its QKV
+  // takes LayerNorm + GEMM (enc.0, and tp.0 behind the LayerNorm kernel).  From its out-projection on such a layer is on whichever
+  // path the batch is on.
+  const int n_layers = svs ? c.enc_layers + c.tp_layers : c.enc_layers;
+  for (int i = 0; i < n_layers; ++i) {
     const EncLayer& L = w.enc[(size_t)i];
     const bool first = i == 0;
+    const bool no_stats = first || i == c.enc_layers;
+    if (i == c.enc_layers) {
+      lnorm(m, s, x, d, m->enc.f(), d, w.enc_after, M, d, d);
+      x = m->enc.f();
+    }
     const float* xin = first ? m->x0.f() : x;
     const int ldin = first ? FP : d, Din = first ? FD : d, Kp = first ? FP : d;
-    if (kv_planes && !first) {
+    if (kv_planes && !no_stats) {
       // LayerNorm(x) Wqkv'^T on the plane images of x: Q as fp32 rows of qkv, K | V as row-major planes
       Scope sc(m, s, K_GEMM, 2.0 * M * (double)(3 * d) * d, 4.0 * ((double)M * d + 3.0 * d * d + (double)M * 3 * d));
       const Planes& W = L.qkv_f.img;
@@ -845,10 +904,10 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
                              .ldc = 3 * d, .Ph = kvP.hi, .Pl = kvP.lo, .rows_p = 2 * d, .row_planes_from = d, .M = M, .N = 3 * d, .K = d,
                              .bias = L.qkv_f.folded.b, .ln_stats = m->lnstats.f(), .ln_tiles = 4, .ln_colsum = L.qkv_f.colsum},
                             s);
-    } else if (planes && !first) {
+    } else if (planes && !no_stats) {
       // LayerNorm(x) Wqkv'^T on the plane images of x that the previous layer's FFN2 left
       gemm_pl(xP, L.qkv_f.img, {.C = m->qkv.f(), .ldc = 3 * d, .N = 3 * d, .K = d, .bias = L.qkv_f.folded.b, .ln_colsum = L.qkv_f.colsum});
-    } else if (fuse_ln && !first) {
+    } else if (fuse_ln && !no_stats) {
       gemm_ln(L.qkv_f.folded, {.A = x, .C = m->qkv.f(), .ldc = 3 * d, .N = 3 * d, .K = d, .ln_colsum = L.qkv_f.colsum});
     } else {
       lnorm(m, s, xin, ldin, m->y.f(), Kp, L.norm1, M, Din, Kp);
@@ -862,7 +921,7 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
       pfhip::AttnOp att = self_att;
       att.fsmn_w = L.fsmn_w; att.mem = mem_in_x ? x : m->mem.f(); att.ldmem = d; att.mem_accumulate = mem_in_x && !first;
       if (planes) { att.planes_hi = ctxP.hi; att.planes_lo = ctxP.lo; att.plane_rows = Mp; }
-      if (kv_planes && !first) {      // K | V from the planes the QKV projection wrote, no fp32 context (kv_planes implies planes, mem_in_x)
+      if (kv_planes && !no_stats) {      // K | V from the planes the QKV projection wrote, no fp32 context (kv_planes implies planes, mem_in_x)
         att.O = nullptr; att.ldo = 0;
         att.kv_hi = kvP.hi; att.kv_lo = kvP.lo; att.ldkv = 2 * d; att.v_col = d;
         pfhip::launch_attention_p3(att, s);
@@ -870,7 +929,7 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
         pfhip::launch_attention_fsmn(att, s);
       }
     }
-    const bool more = i + 1 < c.enc_layers;
+    const bool more = i + 1 < n_layers && i + 1 != c.enc_layers;      // the next layer's QKV reads statistics / images
     if (planes) {
       // x = ctx Wo^T + b + (x + memory): fp32 for the residual stream, plane images for FFN1, row statistics for its LayerNorm
       gemm_pl(ctxP, L.out_img, {.C = x, .ldc = d, .Ph = xP.hi, .Pl = xP.lo, .N = d, .K = d, .bias = L.out.b, .R1 = x, .stats_out = m->lnstats.f()});
@@ -893,7 +952,80 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
     gemm(m, s, m->y.f(), d, L.ffn1, c.ffn, d, d, m->hbuf.f(), c.ffn, nullptr, 0, nullptr, 0, M, true);
     gemm(m, s, m->hbuf.f(), c.ffn, L.ffn2, d, c.ffn, c.ffn, x, d, x, d, nullptr, 0, M, false);
   }
-  lnorm(m, s, x, d, m->enc.f(), d, w.enc_after, M, d, d);
+  if (svs) lnorm(m, s, x, d, m->x.f(), d, w.tp_norm, M, d, d);      // x is `enc` here: the model's output rows are in m->x
+  else lnorm(m, s, x, d, m->enc.f(), d, w.enc_after, M, d, d);
+  return PFHIP_OK;
+}
+
+// ---- SenseVoice: CTC head over every row of `x` (after tp.norm), collapse, ONE device-to-host copy and the forward's one sync -----
+// Results on the host (h_counts): token_num [B] | ids, tok_frame, tok_logp [B][maxT] | frame ids [M] | frame log-probs [M].
+// The fused head (ctc_head.hip) keeps 12 bytes per row and 128-column tile.  The unfused head — the exact re-run of the range guard,
+// a caller who wants full log-prob rows, the debug switch — runs GEMM + launch_logsoftmax_argmax over chunks of kSvsChunkRows rows:
+// at vocabulary 25 055 its scratch is 2 x 2048 x 25 088 x 4 B = 411 MB (logits and log-probs of one chunk), never rows x vocabulary.
+constexpr int kSvsChunkRows = 2048;
+struct SvsHost { const int32_t *num, *ids, *frames, *fid; const float *logp, *flp; };
+SvsHost svs_host(const pfhip_model* m) {
+  const int32_t* h = m->h_counts.i();
+  const size_t bt = (size_t)m->B * m->maxT;
+  return {h, h + m->B, h + m->B + bt, h + m->B + 3 * bt, reinterpret_cast<const float*>(h + m->B + 2 * bt),
+          reinterpret_cast<const float*>(h + m->B + 3 * bt + m->M)};
+}
+pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
+  const ModelWeights& w = *m->weights;
+  const Config& c = w.cfg;
+  const int d = c.d_model, B = m->B, M = m->M, V = c.vocab, maxT = m->maxT;
+  const size_t bt = (size_t)B * maxT, n_words = (size_t)B + 3 * bt + 2 * (size_t)M;
+  HIP_TRY(m->counts.ensure(n_words * 4));
+  HIP_TRY(m->h_counts.ensure(n_words * 4));
+  int32_t* dn = m->counts.i();
+  int32_t *d_ids = dn + B, *d_frames = dn + B + bt, *d_fid = dn + B + 3 * bt;
+  float *d_logp = reinterpret_cast<float*>(dn + B + 2 * bt), *d_flp = reinterpret_cast<float*>(d_fid + M);
+  const float* X = m->x.f();
+  const bool unfused = pfhip::launch_ctx().exact || m->debug_ctc_unfused || m->svs_logp_host;
+  m->debug_ctc_unfused = 0;
+  m->svs_head_chunks = 0;
+  if (unfused) {
+    ++m->svs_unfused_forwards;
+    const int rows_max = std::min(kSvsChunkRows, round_up(M, pfhip::kTileM));
+    HIP_TRY(m->svs_logits.ensure((size_t)rows_max * w.vocab_pad * 4));
+    HIP_TRY(m->svs_logp.ensure((size_t)rows_max * V * 4));
+    for (int r0 = 0; r0 < M; r0 += kSvsChunkRows) {
+      const int rows = std::min(kSvsChunkRows, M - r0);
+      gemm(m, s, X + (size_t)r0 * d, d, w.ctc, V, d, d, m->svs_logits.f(), w.vocab_pad, nullptr, 0, nullptr, 0, rows, false);
+      {
+        Scope sc(m, s, K_HEAD, 0, 12.0 * rows * V);
+        pfhip::launch_logsoftmax_argmax(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_logp.f(), d_fid + r0, s, m->d_range_flag);
+        pfhip::launch_gather_best(m->svs_logp.f(), V, d_fid + r0, rows, d_flp + r0, s);
+      }
+      if (m->svs_logp_host)
+        HIP_TRY(hipMemcpyAsync(m->svs_logp_host + (size_t)r0 * V, m->svs_logp.p, (size_t)rows * V * 4, hipMemcpyDeviceToHost, s));
+      ++m->svs_head_chunks;
+    }
+  } else {
+    const size_t ws = pfhip::ctc_head_workspace_bytes(M, V);
+    HIP_TRY(m->svs_ws.ensure(ws));
+    Scope sc(m, s, K_GEMM, 2.0 * M * (double)V * d, 4.0 * ((double)M * d + (double)V * d) + 12.0 * M * (w.vocab_pad / pfhip::kTileN));
+    if (!pfhip::launch_ctc_head(X, d, w.ctc.w, d, w.ctc.b, w.ctc.scale, M, V, d, d_fid, d_flp, nullptr, m->svs_ws.p, ws, s, m->d_range_flag))
+      return fail(PFHIP_ERR_UNSUPPORTED, "CTC head: d_model must be a multiple of 32");
+  }
+  {
+    Scope sc(m, s, K_CIF, 0, 20.0 * M);
+    if (!pfhip::launch_ctc_collapse(d_fid, d_flp, m->m_row_off, m->m_len, B, c.blank_id, maxT, d_ids, d_frames, d_logp, dn, s))
+      return fail(PFHIP_ERR_ARG, "CTC collapse refused its arguments");
+  }
+  HIP_TRY(hipMemcpyAsync(m->h_counts.p, m->counts.p, n_words * 4, hipMemcpyDeviceToHost, s));
+  {
+    const pfhip_status rs = read_range_flag(m, s, false);
+    if (rs) return rs;
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  m->range_hit = m->h_flag.p ? *m->h_flag.i() : 0;
+  const SvsHost h = svs_host(m);
+  for (int b = 0; b < B; ++b) {
+    m->token_num[b] = h.num[b];
+    m->maxL = std::max(m->maxL, h.num[b]);
+  }
   return PFHIP_OK;
 }
 
@@ -1826,9 +1958,14 @@ void keep_thread_fires(const pfhip_model* head, const pfhip_model* m, const pfhi
 }
 }  // namespace
 
+// every Paraformer entry point on a SenseVoice handle
+static bool is_svs(const pfhip_model* m) { return m && m->weights->cfg.svs; }
+static pfhip_status refuse_svs() { return fail(PFHIP_ERR_UNSUPPORTED, "a SenseVoice (CTC) model is run through pfhip_svs_forward"); }
+
 static pfhip_status offline_enqueue(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                                     int batch, void* stream) {
   g_err.clear();
+  if (is_svs(m)) return refuse_svs();
   if (!m || !sample_off || !n_samples || batch <= 0) return fail(PFHIP_ERR_ARG, "bad argument");
   if (!d_pcm.p) return fail(PFHIP_ERR_ARG, "null device pcm");
   std::lock_guard<std::mutex> lk(m->mu);
@@ -2099,6 +2236,7 @@ static pfhip_status forward_batched(pfhip_model* head, HostPcm pcm, const int* n
 static pfhip_status offline_forward_sets(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const HwSets& hw,
                                          pfhip_out* out, const pfhip_detail* dt = nullptr, std::optional<int> rate = std::nullopt) {
   g_err.clear();
+  if (is_svs(head)) return refuse_svs();
   if (!head || !pcm.p || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
   if (dt && dt->nbest_k && (dt->nbest_k < 1 || dt->nbest_k > pfhip::kTopkMax || dt->nbest_k > head->weights->cfg.vocab || !dt->nbest_ids ||
                             !dt->nbest_logp))
@@ -2265,6 +2403,7 @@ int pfhip_lfr_frame_ms(const pfhip_model* m) { return m ? m->weights->cfg.lfr_n 
 static pfhip_status offline_forward_resident(pfhip_model* head, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
                                              int batch, pfhip_out* out) {
   g_err.clear();
+  if (is_svs(head)) return refuse_svs();
   if (!head || !d_pcm.p || !sample_off || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
   if (head->weights->cfg.contextual && !default_hotwords(head)) return fail(PFHIP_ERR_ARG, "hw_emb is null");
   pfhip_model* m = acquire_slot(head);
@@ -2358,6 +2497,7 @@ pfhip_status pfhip_resample(pfhip_model* head, const float* const* pcm, const in
 pfhip_status pfhip_set_batching(pfhip_model* m, int wait_us, int max_utterances) {
   g_err.clear();
   if (!m || wait_us < 0 || max_utterances < 1) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (is_svs(m)) return fail(PFHIP_ERR_UNSUPPORTED, "merging concurrent callers is not built for SenseVoice (CTC) models");
   std::lock_guard<std::mutex> ql(m->bq.mu);
   m->batch_wait_us = wait_us;
   m->batch_max_utts = max_utterances;
@@ -2527,6 +2667,97 @@ pfhip_status pfhip_hotword_bank_stats(pfhip_model* m, pfhip_hwbank_stats* out) {
   return PFHIP_OK;
 }
 
+// ---- SenseVoiceSmall, offline ------------------------------------------------------------------------------------------------
+int pfhip_is_ctc(const pfhip_model* m) { return is_svs(m) ? 1 : 0; }
+// lid_map (sensevoice-small.h:121-129), looked up as sensevoice-small.cpp:597-602 does: an unknown string keeps 0
+int pfhip_svs_lid(const char* svs_lang) {
+  static const struct { const char* name; int id; } kLid[] = {{"auto", 0}, {"zh", 3}, {"en", 4}, {"yue", 7}, {"ja", 11}, {"ko", 12}, {"nospeech", 13}};
+  if (svs_lang)
+    for (const auto& e : kLid)
+      if (std::strcmp(svs_lang, e.name) == 0) return e.id;
+  return 0;
+}
+
+// one packed forward on slot m, its range-guard re-run included, and the results into out
+static pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
+                                       const int32_t* textnorm, pfhip_svs_out* out) {
+  std::lock_guard<std::mutex> lk(m->mu);
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t s = m->own_stream;
+  m->prof_stream = s;
+  const int V = m->weights->cfg.vocab;
+  m->nbest_k = 0; m->want_fires = false;
+  m->svs_prompt.resize((size_t)4 * batch);
+  for (int b = 0; b < batch; ++b) {      // sensevoice-small.cpp:607-640: language, then the two fixed rows 1 and 2, then text normalisation
+    m->svs_prompt[4 * b] = lid[b]; m->svs_prompt[4 * b + 1] = 1; m->svs_prompt[4 * b + 2] = 2; m->svs_prompt[4 * b + 3] = textnorm[b];
+  }
+  std::vector<int64_t> off;
+  pfhip_status st = stage_pcm(m, pcm, n_samples, batch, s, off);
+  if (st) return st;
+  if (out->logp) {       // the row count is known on the host before anything is launched
+    size_t rows = 0;
+    for (int b = 0; b < batch; ++b) {
+      const int F = n_samples[b] < 400 ? 0 : 1 + (n_samples[b] - 400) / 160;
+      const int T = (F + m->weights->cfg.lfr_n - 1) / m->weights->cfg.lfr_n;
+      rows += T > 0 ? (size_t)T + 4 : 0;
+    }
+    if (rows * (size_t)V > out->logp_cap_floats) return fail(PFHIP_ERR_CAPACITY, "logp_cap_floats smaller than rows x vocabulary");
+  }
+  m->svs_logp_host = out->logp;
+  st = enqueue_locked(m, PcmView{m->pcm.p, pcm.s16}, off.data(), n_samples, batch, s, false);
+  if (!st && m->M > 0 && m->range_hit && !m->weights->always_exact) {      // the guard of the fp16 two-plane domain: redone once, exact
+    ++m->range_fallbacks;
+    m->exact_rerun = true;
+    st = enqueue_locked(m, PcmView{m->pcm.p, pcm.s16}, off.data(), n_samples, batch, s, false);
+    m->exact_rerun = false;
+  }
+  m->svs_logp_host = nullptr;
+  if (st) return st;
+  for (int b = 0; b < batch; ++b) {
+    if (out->token_num) out->token_num[b] = m->M ? m->token_num[b] : 0;
+    if (out->frame_len) out->frame_len[b] = m->T[b];
+  }
+  if (m->M == 0) return PFHIP_OK;
+  if ((out->ids || out->tok_frame || out->tok_logp) && out->max_tokens < m->maxL)
+    return fail(PFHIP_ERR_CAPACITY, "max_tokens smaller than the longest token sequence");
+  const SvsHost h = svs_host(m);
+  for (int b = 0; b < batch; ++b) {
+    const size_t n = (size_t)m->token_num[b], src = (size_t)b * m->maxT, dst = (size_t)b * out->max_tokens;
+    if (out->ids) std::memcpy(out->ids + dst, h.ids + src, n * 4);
+    if (out->tok_frame) std::memcpy(out->tok_frame + dst, h.frames + src, n * 4);
+    if (out->tok_logp) std::memcpy(out->tok_logp + dst, h.logp + src, n * 4);
+  }
+  if (out->frame_ids) std::memcpy(out->frame_ids, h.fid, (size_t)m->M * 4);
+  if (out->frame_logp) std::memcpy(out->frame_logp, h.flp, (size_t)m->M * 4);
+  return PFHIP_OK;
+}
+
+static pfhip_status svs_forward(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid, const int32_t* textnorm,
+                                pfhip_svs_out* out) {
+  g_err.clear();
+  if (!head || !pcm.p || !n_samples || batch <= 0 || !lid || !textnorm || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!is_svs(head)) return fail(PFHIP_ERR_UNSUPPORTED, "not a SenseVoice (CTC) model: a Paraformer is run through pfhip_offline_forward");
+  if (!head->replicas.empty()) return fail(PFHIP_ERR_UNSUPPORTED, "multi-device groups are not built for SenseVoice (CTC) models");
+  for (int b = 0; b < batch; ++b) {
+    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    if (lid[b] < 0 || lid[b] > 15 || textnorm[b] < 0 || textnorm[b] > 15) return fail(PFHIP_ERR_ARG, "lid / textnorm outside 0..15");
+  }
+  pfhip_model* m = acquire_slot(head);                  // the least-loaded execution context
+  tl_last_replica = m;
+  const pfhip_status st = svs_forward_direct(m, pcm, n_samples, batch, lid, textnorm, out);
+  ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
+  release_slot(head, m);
+  return st;
+}
+pfhip_status pfhip_svs_forward(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                               const int32_t* textnorm, pfhip_svs_out* out) {
+  return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out);
+}
+pfhip_status pfhip_svs_forward_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                   const int32_t* textnorm, pfhip_svs_out* out) {
+  return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out);
+}
+
 // One synthetic batch through every execution slot: the code objects are loaded, each context's workspace is sized for
 // `batch` utterances of `n_samples` samples and its streams have run once, so the first real request pays none of that.
 pfhip_status pfhip_warm_up(pfhip_model* m, int batch, int n_samples) {
@@ -2544,6 +2775,16 @@ pfhip_status pfhip_warm_up(pfhip_model* m, int batch, int n_samples) {
   const int max_tok = n_samples / 960 + 2;
   std::vector<int32_t> ids((size_t)batch * max_tok), tn(batch), nf(batch), fr(batch);
   std::vector<float> hw(m->weights->cfg.contextual ? (size_t)m->weights->cfg.d_model : 0, 0.f);
+  if (is_svs(m)) {
+    std::vector<int32_t> lid((size_t)batch, 0), tnorm((size_t)batch, 15), sids((size_t)batch * (max_tok * 2 + 8));
+    for (pfhip_model* r : all_slots(m)) {
+      pfhip_svs_out so{};
+      so.ids = sids.data(); so.token_num = tn.data(); so.max_tokens = max_tok * 2 + 8;
+      const pfhip_status st = svs_forward_direct(r, ptrs.data(), lens.data(), batch, lid.data(), tnorm.data(), &so);
+      if (st) return st;
+    }
+    return PFHIP_OK;
+  }
   for (pfhip_model* r : all_slots(m)) {
     pfhip_out out{};
     out.token_ids = ids.data(); out.token_num = tn.data(); out.n_fires = nf.data(); out.n_frames = fr.data(); out.max_tokens = max_tok;
@@ -2635,7 +2876,8 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   size_t n = 0;
   const int d = m->weights->cfg.d_model;
   if (nm == "feats") { src = m->feats.p; n = (size_t)m->M * m->weights->feat_dim; }
-  else if (nm == "enc") { src = m->enc.p; n = (size_t)m->M * d; }
+  else if (nm == "enc") { src = m->weights->cfg.svs ? m->x.p : m->enc.p; n = (size_t)m->M * d; }      // SenseVoice: the rows after tp.norm
+  else if (m->weights->cfg.svs) return fail(PFHIP_ERR_ARG, "a SenseVoice model has the tensors feats and enc, not " + nm);
   else if (nm == "alphas") { src = m->alphas.p; n = (size_t)m->M; }
   else if (nm == "emb") { src = m->emb.p; n = (size_t)m->ML * d; }
   else if (nm == "ts_up" && m->have_ts) { src = m->ts_up.p; n = (size_t)3 * m->M * d; }            // timestamp-head stages
@@ -2684,6 +2926,29 @@ pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value) {
   if (std::string(what) == "format_splits") {         // read-out: merged batches cut short because callers of both sample formats were queued
     std::lock_guard<std::mutex> ql(m->bq.mu);
     return (pfhip_status)m->format_splits;
+  }
+  // SenseVoice.  A forward runs on whichever execution context is least loaded, so the switch is set on every context of the handle
+  // (each one's next forward takes the unfused head once) and the counter is summed over them, as range_fallbacks is; the chunk
+  // count is that of the context which served the calling thread's last forward.
+  if (std::string(what) == "ctc_unfused" || std::string(what) == "ctc_unfused_forwards") {
+    const bool set = std::string(what) == "ctc_unfused";
+    long long n = 0;
+    auto visit = [&](pfhip_model* x, bool locked) {
+      std::unique_lock<std::mutex> xl(x->mu, std::defer_lock);
+      if (!locked) xl.lock();
+      if (set) x->debug_ctc_unfused = value;
+      n += x->svs_unfused_forwards;
+    };
+    visit(m, true);
+    for (pfhip_model* cx : m->contexts) visit(cx, false);
+    for (pfhip_model* r : m->replicas) { visit(r, false); for (pfhip_model* cx : r->contexts) visit(cx, false); }
+    return set ? PFHIP_OK : (pfhip_status)n;
+  }
+  if (std::string(what) == "ctc_head_chunks") {
+    // (looked up among this handle's contexts, never dereferenced before it is found there: the note may be of a handle since destroyed)
+    for (pfhip_model* cx : m->contexts)
+      if (cx == tl_last_replica) return (pfhip_status)cx->svs_head_chunks;
+    return (pfhip_status)m->svs_head_chunks;
   }
   if (std::string(what) == "range_flag") { m->debug_range_flag = value; return PFHIP_OK; }    // the next forward starts with its range flag raised
   if (std::string(what) == "range_fallbacks") {       // read-out: forwards redone on the exact kernels, over every context of the handle

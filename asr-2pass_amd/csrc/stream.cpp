@@ -661,6 +661,7 @@ extern "C" {
 pfhip_status pfhip_stream_create(pfhip_model* m, const int* chunk_size, pfhip_stream** out) {
   last_error().clear();
   if (!m || !out) return fail(PFHIP_ERR_ARG, "null argument");
+  if (m->weights->cfg.svs) return fail(PFHIP_ERR_UNSUPPORTED, "a SenseVoice (CTC) model is offline only: pfhip_svs_forward");
   m = pfhip_impl::route_stream(m);           // a group: the connection lives on the replica (GPU) with the fewest open streams
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));

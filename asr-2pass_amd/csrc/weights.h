@@ -38,6 +38,9 @@ struct Config {
   float smooth_factor2 = 0.25f, noise_threshold2 = 0.01f;      // CifPredictorV3 timestamp head
   float cif_threshold = 1.0f, tail_threshold = 0.45f, smooth_factor = 1.0f, noise_threshold = 0.0f;
   int sample_rate = 16000;
+  // config.kind == "sensevoice" (SenseVoiceSmall, sensevoice-small.cpp): the SAN-M encoder is followed by tp_layers more layers of
+  // the same kind, tp.norm and a CTC head over every row; no predictor, no decoder.  Widths and wiring recalled from upstream FunASR.
+  int svs = 0, tp_layers = 0, blank_id = 0;
 };
 
 struct FrontendTables {
@@ -92,8 +95,11 @@ struct ModelWeights {
   FrontendTables ft;
   const float* cmvn_mean = nullptr; const float* cmvn_istd = nullptr;
   const float* inv_ts = nullptr;                    // position-encoding timescales
-  std::vector<EncLayer> enc;
+  std::vector<EncLayer> enc;          // a SenseVoice container: enc.0 .. enc.{enc_layers-1}, then tp.0 .. tp.{tp_layers-1}
   Norm enc_after;
+  Norm tp_norm;                       // cfg.svs: after the last tp layer
+  const float* svs_embed = nullptr;   // cfg.svs: the prompt embedding [16][feat_dim]
+  Linear ctc;                         // cfg.svs: ctc.w [vocab][d], b: ctc.b padded to vocab_pad
   Predictor pred;
   std::vector<DecLayer> dec;
   DecFfn dec3;

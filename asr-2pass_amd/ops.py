@@ -39,6 +39,11 @@ def _lib():
         lib.pfhip_op_logsoftmax_argmax.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _vp]
         lib.pfhip_op_logsoftmax_topk.argtypes = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
         lib.pfhip_op_resample.argtypes = [_vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]
+        if hasattr(lib, "pfhip_op_ctc_head"):          # (an older build loaded through PFHIP_LIB for A/B timing has none of these)
+            lib.pfhip_op_ctc_head_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_ctc_head_workspace_bytes.argtypes = [_ci, _ci]
+            lib.pfhip_op_ctc_head.argtypes = [_vp, _ci, _vp, _ci, _vp, _cf, _ci, _ci, _ci, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+            lib.pfhip_op_ctc_collapse.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
         _bound = True
     return lib
 
@@ -333,6 +338,43 @@ def logsoftmax_topk(logits, k, V=None, want_logp=True):
     _ck(_lib().pfhip_op_logsoftmax_topk(_p(logits), logits.stride(0), ML, V, int(k), _p(logp), _p(ids), _p(topk_ids), _p(topk_logp),
                                         _stream()), "logsoftmax_topk")
     return logp, ids, topk_ids, topk_logp
+
+
+def ctc_head(X, W, bias, w_scale="auto", M=None, V=None, want_lse=True):
+    """The CTC head without the logits matrix (csrc/ctc_head.hip): (ids [M] int32, logp_best [M], lse [M] or None) of
+    X[:M] @ W[:V]^T + bias.  w_scale as gemm_f32 ("auto" = best_w_scale(max |W|))."""
+    M = X.shape[0] if M is None else M
+    V = W.shape[0] if V is None else V
+    K = X.shape[1]
+    if w_scale == "auto":
+        w_scale = best_w_scale(float(W[:V].abs().max()))
+    lib = _lib()
+    ids = torch.empty(M, dtype=torch.int32, device=X.device)
+    logp_best = torch.empty(M, dtype=torch.float32, device=X.device)
+    lse = torch.empty(M, dtype=torch.float32, device=X.device) if want_lse else None
+    nbytes = int(lib.pfhip_op_ctc_head_workspace_bytes(M, V))
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=X.device)
+    _ck(lib.pfhip_op_ctc_head(_p(X), X.stride(0), _p(W), W.stride(0), _p(bias), float(w_scale), M, V, K, _p(ids), _p(logp_best),
+                              _p(lse), _p(ws), nbytes, _stream()), "ctc_head")
+    return ids, logp_best, lse
+
+
+def ctc_collapse_chunk():
+    return int(_lib().pfhip_op_ctc_collapse_chunk())
+
+
+def ctc_collapse(frame_ids, frame_logp, row_off, length, max_tokens, blank=0, fill=-1):
+    """CTC collapse per utterance (csrc/ctc_head.hip): (ids, tok_frame, tok_logp [B, max_tokens], token_num [B]).  Slots past
+    token_num[b] keep `fill` (NaN for tok_logp)."""
+    B = row_off.numel()
+    dev = frame_ids.device
+    ids = torch.full((B, max_tokens), fill, dtype=torch.int32, device=dev)
+    tok_frame = torch.full((B, max_tokens), fill, dtype=torch.int32, device=dev)
+    tok_logp = torch.full((B, max_tokens), float("nan"), dtype=torch.float32, device=dev)
+    token_num = torch.full((B,), fill, dtype=torch.int32, device=dev)
+    _ck(_lib().pfhip_op_ctc_collapse(_p(frame_ids), _p(frame_logp), _p(row_off), _p(length), B, int(blank), int(max_tokens), _p(ids),
+                                     _p(tok_frame), _p(tok_logp), _p(token_num), _stream()), "ctc_collapse")
+    return ids, tok_frame, tok_logp, token_num
 
 
 # ---- pre-split operands (csrc/gemm_p3.hip) ------------------------------------------------------------------------------------

@@ -44,6 +44,77 @@ def small_config_320(**over):
     return cfg
 
 
+# SenseVoiceSmall, the model the reference builds when the model directory's name says so (offline-stream.cpp:50-56).  Every width
+# here is RECALLED from upstream FunASR, not read: no SenseVoice file was available when this was written.  d_model 512, 4 heads of 128,
+# FFN 2048, 50 encoder layers (encoders0 560 -> 512, then 49) + 20 tp_encoders, FSMN kernel 11, vocabulary 25055, a 16 x 560 prompt
+# embedding, blank id 0.  The real config.yaml decides at load.
+SENSEVOICE_SMALL = dict(kind="sensevoice", d_model=512, n_head=4, ffn=2048, enc_layers=50, tp_layers=20, dec_layers=0, dec_ffn=2048,
+                        kernel=11, vocab=25055, blank_id=0, n_mels=80, lfr_m=7, lfr_n=6)
+
+
+def small_config_svs(**over):
+    """SenseVoiceSmall's widths (512 / 4 heads of 128 / 2048) with 2 + 2 layers and a small ragged vocabulary."""
+    cfg = dict(SENSEVOICE_SMALL)
+    cfg.update(enc_layers=2, tp_layers=2, vocab=1003)
+    cfg.update(over)
+    return cfg
+
+
+def svs_tensor_specs(cfg):
+    """Ordered (name, shape, init) list of a "sensevoice" container: cmvn.*, svs.embed.w, enc.{i}.* / enc.after_norm.* as the
+    Paraformer encoder, tp.{i}.* with the encoder layer's sub-names, tp.norm.*, ctc.w / ctc.b."""
+    d, f, V, k = cfg["d_model"], cfg["ffn"], cfg["vocab"], cfg["kernel"]
+    feat = cfg["n_mels"] * cfg["lfr_m"]
+    specs = [("cmvn.mean", [feat], ("const", -8.0)), ("cmvn.istd", [feat], ("const", 0.3)),
+             ("svs.embed.w", [16, feat], ("normal", 1.0))]
+
+    def lin(name, out_f, in_f):
+        specs.append((name + ".w", [out_f, in_f], ("normal", 1.0 / math.sqrt(in_f))))
+        specs.append((name + ".b", [out_f], ("normal", 0.02)))
+
+    def ln(name, n):
+        specs.append((name + ".g", [n], ("const", 1.0)))
+        specs.append((name + ".b", [n], ("const", 0.0)))
+
+    def layer(p, in_f):
+        ln(p + "norm1", in_f)
+        lin(p + "qkv", 3 * d, in_f)
+        specs.append((p + "fsmn.w", [d, k], ("normal", 1.0 / math.sqrt(k))))
+        lin(p + "out", d, d)
+        ln(p + "norm2", d)
+        lin(p + "ffn1", f, d)
+        lin(p + "ffn2", d, f)
+
+    for i in range(cfg["enc_layers"]):
+        layer(f"enc.{i}.", feat if i == 0 else d)
+    ln("enc.after_norm", d)
+    for i in range(cfg["tp_layers"]):
+        layer(f"tp.{i}.", d)
+    ln("tp.norm", d)
+    lin("ctc", V, d)
+    return specs
+
+
+def synth_svs_weights(cfg=None, seed=1357):
+    """(manifest, blob) of a synthetic SenseVoice container, initialised as synth_weights does.  ctc.b[blank] gets +3.2: on
+    independent LayerNorm-ed rows and N(0, 1/sqrt(d)) weights that makes about half the frames blank and about a quarter of
+    neighbouring frames equal (numpy, 3 seeds x 4000 rows: blank share 0.48-0.49, repeats 0.23-0.24).  On the rows this synthetic
+    model itself produces — the frames of an utterance share most of their encoder row — the numpy restatement gives 0.15-0.19 blank
+    and about half of the other frames equal to their predecessor.  Without the bias random weights almost never give a blank and
+    the collapse is not exercised end to end."""
+    cfg = small_config_svs() if cfg is None else cfg
+    specs = svs_tensor_specs(cfg)
+    man, blob = synth_generic(cfg, specs, seed)
+    rng = np.random.default_rng(seed + 1)
+    for name, shape, init in specs:
+        if init[0] == "const" and (name.endswith(".g") or (name.endswith(".b") and "norm" in name)):
+            n = int(np.prod(shape))
+            o = man["tensors"][name]["offset"] // 4
+            blob[o:o + n] += rng.standard_normal(n, dtype=np.float32) * np.float32(0.05)
+    blob[man["tensors"]["ctc.b"]["offset"] // 4 + int(cfg.get("blank_id", 0))] += np.float32(3.2)
+    return man, blob
+
+
 def small_config(**over):
     """Same widths as Paraformer-large (the default kernels are specialised for d_model 512 / d_k 128) but few
     layers and a small ragged vocabulary, so the CPU oracle finishes in seconds."""

@@ -61,8 +61,11 @@ pfhip_status pfhip_create_from_memory(const void* blob, size_t blob_bytes, const
  * (PFHIP_MODEL_CACHE=0 switches the cache off; a read-only directory is not an error). */
 pfhip_status pfhip_create_from_files(const char* am_model, const char* second_model, const char* hw_model, const char* am_cmvn,
                                      const char* am_config, int device, pfhip_model** out);
-/* The file-reading step on its own (no device needed): kind = "asr" | "vad" | "punc".  The blob / manifest pointers stay
- * valid until pfhip_container_free. */
+/* The file-reading step on its own (no device needed): kind = "asr" | "sensevoice" | "vad" | "punc".  The blob / manifest pointers
+ * stay valid until pfhip_container_free.  "asr" (and pfhip_create_from_files) tells the acoustic models apart by their initialisers:
+ * ctc.ctc_lo.* present and no decoder.output_layer is SenseVoiceSmall (sensevoice-small.cpp:22-56 reads the same three files; the
+ * reference goes by the directory's name, offline-stream.cpp:50-56) and gives a container of config.kind "sensevoice", with
+ * encoder_conf.tp_blocks as tp_layers; "sensevoice" is the same reader and PFHIP_ERR_FORMAT for any other model. */
 typedef struct pfhip_container pfhip_container;
 pfhip_status pfhip_read_model_files(const char* kind, const char* model, const char* second, const char* hotword, const char* cmvn,
                                     const char* config, pfhip_container** out);
@@ -631,11 +634,48 @@ pfhip_status pfhip_set_punc_batching(pfhip_punc* p, int wait_us, int max_sequenc
  * string assembly stay on the host above this. */
 pfhip_status pfhip_punc_add_punc(pfhip_punc* p, const int32_t* ids, int n, int32_t* punc_out, int cap, int* n_out);
 
+/* ---- SenseVoiceSmall, offline (a container with config.kind == "sensevoice") --------------------
+ * The reference builds SenseVoiceSmall instead of Paraformer when the model directory's name says so (offline-stream.cpp:50-56) and
+ * runs it one utterance at a time (sensevoice-small.cpp:575-690 refuses batch_in != 1); here utterances are packed as everywhere.
+ * Model widths and wiring are recalled from upstream FunASR: no SenseVoice file was available when this was written.
+ *   pfhip_is_ctc          1 for such a handle.  Every Paraformer forward, pfhip_stream_create and pfhip_set_batching return
+ *                         PFHIP_ERR_UNSUPPORTED on it (merging concurrent callers is not built for this kind), and
+ *                         pfhip_svs_forward does on a Paraformer handle.
+ *   pfhip_svs_lid     <-> lid_map (sensevoice-small.h:121-129) with the look-up of sensevoice-small.cpp:597-602: "auto" 0, "zh" 3,
+ *                         "en" 4, "yue" 7, "ja" 11, "ko" 12, "nospeech" 13; any other string (or NULL) 0.
+ *   pfhip_svs_forward <-> SenseVoiceSmall::Forward (sensevoice-small.cpp:575-690): LfrCmvn features behind the four prompt rows
+ *                         embed[lid], embed[1], embed[2], embed[textnorm] (textnorm 14 = with ITN, 15 = without, :603-605), the graph,
+ *                         and the frame loop of CTCSearch (:331-347: arg-max per frame, first maximum wins; a frame is kept when
+ *                         its id is not the blank and differs from the previous frame's).  The text assembly of :348-375 stays on
+ *                         the host above this.  lid / textnorm are per utterance, each in 0..15 (PFHIP_ERR_ARG before any launch).
+ *                         An utterance of fewer than 400 samples has no rows at all, prompt rows included, and token_num 0 (the
+ *                         reference returns "" without running the graph, :584-587).
+ * pfhip_svs_out: ids / token_num as pfhip_out's token_ids / token_num — the kept ids [batch][max_tokens], the four leading tag ids
+ * (language, emotion, event, ITN) included; PFHIP_ERR_CAPACITY when max_tokens is below the longest kept sequence.  Optional, NULL to
+ * skip: tok_frame / tok_logp [batch][max_tokens] = the 0-based row (prompt rows counted) at which a kept run starts and that frame's
+ * log-prob; frame_ids / frame_logp packed [sum rows] with frame_len [batch] = rows per utterance (T + 4, or 0); logp = the full
+ * log-softmax rows [sum rows][vocab] for a host search (logp_cap_floats too small: PFHIP_ERR_CAPACITY) — asking for them takes the
+ * unfused head (GEMM + log-softmax over chunks of 2048 rows: at most 2 x 2048 x vocab floats of scratch, never rows x vocab). */
+int pfhip_is_ctc(const pfhip_model* m);
+int pfhip_svs_lid(const char* svs_lang);
+typedef struct pfhip_svs_out {
+  int32_t* ids; int32_t* token_num; int max_tokens;
+  int32_t* tok_frame; float* tok_logp;
+  int32_t* frame_ids; float* frame_logp;
+  int32_t* frame_len;
+  float* logp; size_t logp_cap_floats;
+} pfhip_svs_out;
+pfhip_status pfhip_svs_forward(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                               const int32_t* textnorm, pfhip_svs_out* out);
+pfhip_status pfhip_svs_forward_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                   const int32_t* textnorm, pfhip_svs_out* out);
+
 /* ---- inspection (parity tests) -----------------------------------------------------------------
  * Copies a named intermediate of the LAST forward to host: "feats" [M,560], "enc" [M,d],
  * "alphas" [M] (without the tail slot), "emb" [sum fires, d], "logp" [sum fires, vocab],
  * "fire_frame" [sum fires] (the fire frames of a forward that recorded them, as floats: the values are small integers).
- * Rows are utterance-major in batch order.  *n_out = floats written. */
+ * Rows are utterance-major in batch order.  *n_out = floats written.  A SenseVoice handle has "feats" [M,560] (prompt rows
+ * included, M = sum of T + 4) and "enc" [M,d] (the rows after tp.norm, which the CTC head reads). */
 pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size_t cap_floats,
                               size_t* n_out);
 
@@ -675,7 +715,10 @@ pfhip_status pfhip_group_stats(pfhip_model* m, int* devices, int64_t* calls, int
  * timestamp request only — as a step-barrier time-out of the persistent BLSTM kernel would — which then has to be served by the
  * per-step recurrence; "blstm_fallbacks" returns (as the status value) how many requests were served that way; "plane_forwards"
  * how many forwards of this context ran the encoder on plane-image operands (gemm_p3.hip: batches of PFHIP_PLANES_MIN_ROWS+ rows);
- * "format_splits" how many merged batches (pfhip_set_batching) were cut short because f32 and s16 callers were queued together. */
+ * "format_splits" how many merged batches (pfhip_set_batching) were cut short because f32 and s16 callers were queued together;
+ * "ctc_unfused" (value != 0) sends the next pfhip_svs_forward of EVERY execution context of the handle through the unfused CTC head
+ * (once each: with pfhip_set_inflight(1) that is the next forward); "ctc_unfused_forwards" returns how many forwards took that head,
+ * summed over the contexts; "ctc_head_chunks" how many row chunks the unfused head of the calling thread's last forward ran. */
 pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value);
 pfhip_status pfhip_profile_enable(pfhip_model* m, int on);
 pfhip_status pfhip_profile_read(pfhip_model* m, pfhip_profile* out, int reset);

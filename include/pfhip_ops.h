@@ -130,6 +130,25 @@ int pfhip_op_logsoftmax_argmax(const float* logits, int ldl, int ML, int V, floa
 int pfhip_op_logsoftmax_topk(const float* logits, int ldl, int M, int V, int k, float* logp, int32_t* ids, int32_t* topk_ids,
                              float* topk_logp, void* stream);
 
+/* The head of a CTC model (SenseVoiceSmall: the graph's ctc_lo MatMul + LogSoftmax and the per-frame arg-max of CTCSearch,
+ * onnxruntime/src/sensevoice-small.cpp:331-337) WITHOUT the logits matrix (ctc_head.hip): X [M, K] fp32 (exactly M rows, K % 32 == 0,
+ * row strides % 4 == 0), W [V, K] (exactly V rows), bias [V], w_scale as pfhip_op_gemm_f32_scaled.  ids [M] = arg-max column of
+ * x W^T + bias (first maximum wins, std::max_element), logp_best [M] = that logit - log sum exp of the row, lse [M] (may be NULL) =
+ * the log-sum-exp.  workspace: pfhip_op_ctc_head_workspace_bytes(M, V) bytes of device memory (per row and 128-column tile the
+ * triple max / arg-max / sum of exp).  hipErrorInvalidValue, before anything is launched, for any other shape, a NULL buffer or a
+ * short workspace. */
+size_t pfhip_op_ctc_head_workspace_bytes(int M, int V);
+int pfhip_op_ctc_head(const float* X, int ldx, const float* W, int ldw, const float* bias, float w_scale, int M, int V, int K,
+                      int32_t* ids, float* logp_best, float* lse, void* workspace, size_t workspace_bytes, void* stream);
+/* CTC collapse (CTCSearch's loop, sensevoice-small.cpp:340-347) for B utterances packed in frame_ids / frame_logp: utterance b owns
+ * frames [row_off[b], row_off[b] + len[b]) (DEVICE arrays); frame t is kept when frame_ids[t] != blank and != frame_ids[t - 1] (the
+ * first frame has no predecessor).  ids / tok_frame / tok_logp are [B][max_tokens]: the kept id, its 0-based frame in the utterance,
+ * and frame_logp of that frame bit for bit (tok_frame, tok_logp and, with tok_logp NULL, frame_logp may be NULL).  token_num [B] =
+ * the number of kept frames — the true count even above max_tokens, where the surplus is not stored.  A length of 0 gives 0. */
+int pfhip_op_ctc_collapse(const int32_t* frame_ids, const float* frame_logp, const int* row_off, const int* len, int B, int blank,
+                          int max_tokens, int32_t* ids, int32_t* tok_frame, float* tok_logp, int32_t* token_num, void* stream);
+/* The number of frames one trip of the collapse kernel's scan covers (tests place lengths on both sides of it). */
+int pfhip_op_ctc_collapse_chunk(void);
 /* One streaming window (M <= 32 rows): LayerNormalization (g != NULL; width D <= K) -> MatMul/Gemm (+bias, +residual Adds, Relu)
  * (+ the SAN-M FSMN memory of fsmn_v over the M rows, k = 11) in ONE launch — stream_fused.hip. */
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
