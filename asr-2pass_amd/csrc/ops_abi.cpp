@@ -94,6 +94,21 @@ int pfhip_op_window_attention_hd(const float* Q, int ldq, const float* K, int ld
   if (!pfhip::launch_window_attention(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, H, scale, S(stream), head_dim)) return (int)hipErrorInvalidValue;
   return done();
 }
+int pfhip_op_window_attention_segments(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                                       const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
+                                       int max_kv_len, float scale, const float* fsmn_w, float* mem, int ldmem, int head_dim, void* stream) {
+  // before anything is launched: the kernel reads float4s of H * head_dim columns of every Q / K row and stores as many of O / mem
+  if ((head_dim != 128 && head_dim != 80) || B < 1 || H < 1 || max_q_len < 1 || max_q_len > 32 || max_kv_len < 1 || max_kv_len > 32 ||
+      !Q || !K || !V || !O || !q_off || !q_len || !kv_off || !kv_len)
+    return (int)hipErrorInvalidValue;
+  const long long w = (long long)H * head_dim;
+  if ((ldq | ldk | ldv | ldo) % 4 || ldq < w || ldk < w || ldv < w || ldo < w || (fsmn_w && (!mem || ldmem < w || ldmem % 4)))
+    return (int)hipErrorInvalidValue;
+  if (!pfhip::launch_window_attention_segments(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, max_kv_len, scale,
+                                               S(stream), fsmn_w, mem, ldmem, head_dim))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
 int pfhip_op_fused_att_out(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int Lq, int Lk, int H, float scale,
                            const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* fsmn_v,
                            int ldfv, const float* fsmn_w, int N, void* stream) {
@@ -187,6 +202,29 @@ int pfhip_op_fsmn(const float* v, int ldv, const float* w, const float* res, int
                   const int* off, const int* len, int B, int max_len, int C, void* stream) {
   if (C % 4) return (int)hipErrorInvalidValue;
   pfhip::launch_fsmn(v, ldv, w, res, ldres, out, ldo, off, len, B, max_len, C, S(stream));
+  return done();
+}
+int pfhip_op_fsmn_shift(const float* v, int ldv, const float* w, const float* res, int ldres, float* out, int ldo,
+                        const int* off, const int* len, int B, int max_len, int C, int shift, void* stream) {
+  // before anything is launched: one float4 of four channels per thread and row
+  if ((shift != 0 && shift != 5) || C <= 0 || C % 4 || !v || !w || !out || !off || !len || (ldv | ldo) % 4 || ldv < C || ldo < C ||
+      (res && (ldres % 4 || ldres < C)))
+    return (int)hipErrorInvalidValue;
+  pfhip::launch_fsmn_shift(v, ldv, w, res, ldres, out, ldo, off, len, B, max_len, C, shift, S(stream));
+  return done();
+}
+int pfhip_op_attention_limit(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                             const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
+                             int max_q_len, float scale, int head_dim, const int* q_kv_limit, void* stream) {
+  // before anything is launched: the fp32-MFMA kernel reads and writes float4s of H * head_dim columns of every row
+  if ((head_dim != 32 && head_dim != 80 && head_dim != 128) || H < 1 || !Q || !K || !V || !O || !q_off || !q_len || !kv_off || !kv_len ||
+      !q_kv_limit)
+    return (int)hipErrorInvalidValue;
+  const long long w = (long long)H * head_dim;
+  if ((ldq | ldk | ldv | ldo) % 4 || ldq < w || ldk < w || ldv < w || ldo < w) return (int)hipErrorInvalidValue;
+  pfhip::launch_attention({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .O = O, .ldo = ldo, .q_off = q_off, .q_len = q_len, .kv_off = kv_off, .kv_len = kv_len, .B = B, .H = H,
+                           .max_q_len = max_q_len, .scale = scale, .head_dim = head_dim, .q_kv_limit = q_kv_limit},
+                          S(stream));
   return done();
 }
 int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,

@@ -188,6 +188,17 @@ def fsmn(v, w, off, length, res=None):
     return out
 
 
+def fsmn_shift(v, w, off, length, shift, res=None):
+    """fsmn with the taps shifted into the past by `shift` frames (0, or 5 = causal: the online CT-Transformer's layers)."""
+    lib = _lib()
+    lib.pfhip_op_fsmn_shift.argtypes = [_vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _ci, _vp]
+    out = torch.zeros((v.shape[0], v.shape[1]), dtype=torch.float32, device=v.device)
+    _ck(lib.pfhip_op_fsmn_shift(_p(v), v.stride(0), _p(w), _p(res), res.stride(0) if res is not None else 0, _p(out), out.stride(0),
+                                _p(off), _p(length), off.numel(), int(length.max().item()), v.shape[1], int(shift), _stream()),
+        "fsmn_shift")
+    return out
+
+
 def resample(x, in_off, n_in, fs_in, fs_out=16000):
     """Audio::WavResample on a packed batch (resample.hip): utterance b is x[in_off[b] : in_off[b] + n_in[b]] (float32 at fs_in).
     Returns (y, out_off, n_out): the utterances at fs_out packed back to back; offsets and counts are host int lists."""
@@ -213,6 +224,17 @@ def attention(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, head_dim=128
     _ck(_lib().pfhip_op_attention_hd(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0),
                                      _p(q_off), _p(q_len), _p(kv_off), _p(kv_len), B, n_head, int(q_len.max().item()),
                                      scale, head_dim, _stream()), "attention")
+    return O
+
+
+def attention_limit(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, q_kv_limit, head_dim=128):
+    """attention (head_dim 32, 80 or 128) with q_kv_limit: per packed query row the number of keys it may see (>= 1; int32 device)."""
+    lib = _lib()
+    lib.pfhip_op_attention_limit.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _ci, _vp, _vp]
+    O = torch.zeros((Q.shape[0], n_head * head_dim), dtype=torch.float32, device=Q.device)
+    _ck(lib.pfhip_op_attention_limit(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0), _p(q_off), _p(q_len),
+                                     _p(kv_off), _p(kv_len), q_off.numel(), n_head, int(q_len.max().item()), float(scale), int(head_dim),
+                                     _p(q_kv_limit), _stream()), "attention_limit")
     return O
 
 
@@ -273,6 +295,24 @@ def window_attention(Q, K, V, Lq, Lk, n_head, scale, head_dim=128):
     else:
         _ck(_lib().pfhip_op_window_attention_hd(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0), Lq, Lk,
                                                 n_head, scale, head_dim, _stream()), "window_attention")
+    return O
+
+
+def window_attention_segments(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, head_dim=128, fsmn_w=None, mem=None, out=None,
+                              max_q_len=None, max_kv_len=None):
+    """B streaming windows in one launch (segment arrays: int32 device tensors, every length <= 32), as a round of connections runs
+    them.  fsmn_w / mem: also the SAN-M memory block of V into mem (self-attention).  out: a [rows, >= n_head * head_dim] tensor to
+    write into (only the windows' rows and those columns are touched); otherwise a zero-filled one is made."""
+    lib = _lib()
+    lib.pfhip_op_window_attention_segments.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _cf,
+                                                       _vp, _vp, _ci, _ci, _vp]
+    O = torch.zeros((Q.shape[0], n_head * head_dim), dtype=torch.float32, device=Q.device) if out is None else out
+    mq = int(q_len.max().item()) if max_q_len is None else max_q_len
+    mk = int(kv_len.max().item()) if max_kv_len is None else max_kv_len
+    _ck(lib.pfhip_op_window_attention_segments(_p(Q), Q.stride(0), _p(K), K.stride(0), _p(V), V.stride(0), _p(O), O.stride(0), _p(q_off),
+                                               _p(q_len), _p(kv_off), _p(kv_len), q_off.numel(), n_head, mq, mk, float(scale), _p(fsmn_w),
+                                               _p(mem), mem.stride(0) if mem is not None else 0, int(head_dim), _stream()),
+        "window_attention_segments")
     return O
 
 

@@ -64,6 +64,11 @@ int pfhip_op_layernorm(const float* x, int ldx, float* y, int ldy, const float* 
 /* FSMN memory block: depthwise Conv1d k=11 over time + identity (+residual), per utterance segment. */
 int pfhip_op_fsmn(const float* v, int ldv, const float* w, const float* res, int ldres, float* out, int ldo,
                   const int* off, const int* len, int B, int max_len, int C, void* stream);
+/* The same with the window shifted into the past by `shift` frames (sanm_shfit; the online CT-Transformer's layers): taps over
+ * [t - 5 - shift, t + 5 - shift].  hipErrorInvalidValue, before anything is launched, for a shift other than 0 or 5 (5 = causal),
+ * C % 4 != 0, a NULL buffer (res may be NULL), a row stride below C or not a multiple of 4. */
+int pfhip_op_fsmn_shift(const float* v, int ldv, const float* w, const float* res, int ldres, float* out, int ldo,
+                        const int* off, const int* len, int B, int max_len, int C, int shift, void* stream);
 /* MatMul-Softmax-MatMul of one attention block, d_k = 128. */
 int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                        const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
@@ -73,6 +78,13 @@ int pfhip_op_attention(const float* Q, int ldq, const float* K, int ldk, const f
 int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                           const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                           int max_q_len, float scale, int head_dim, void* stream);
+/* pfhip_op_attention_hd with a per-query key limit, what the 256-wide online CT-Transformer launches in every layer (the masked branch
+ * of attention.hip's fp32-MFMA kernel at every segment length): q_kv_limit [packed query rows] = the number of keys the row may see
+ * (CTTransformerOnline::VadMask), >= 1 — the result of a row that may see no key is undefined.  hipErrorInvalidValue, before anything
+ * is launched, for a head width other than 32, 80 or 128, H < 1, a NULL buffer, a row stride below H * head_dim or not a multiple of 4. */
+int pfhip_op_attention_limit(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                             const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
+                             int max_q_len, float scale, int head_dim, const int* q_kv_limit, void* stream);
 /* The same block for any head width 1 <= d_k <= 64 (attention_dk.hip; the large CT-Transformer: 516 / 12 heads = 43), fp32, head h in
  * columns [h * d_k, (h + 1) * d_k) of a row: no other column is read or written.  q_kv_limit: nullptr, or per packed query row the
  * number of keys it may see (CTTransformerOnline::VadMask).  hipErrorInvalidValue, before anything is launched, for d_k < 1,
@@ -171,6 +183,16 @@ int pfhip_op_window_attention(const float* Q, int ldq, const float* K, int ldk, 
 /* The same with the head width chosen at run time: 128 or 80 (hipErrorInvalidValue for any other, before anything is launched). */
 int pfhip_op_window_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
                                  int H, float scale, int head_dim, void* stream);
+/* B such windows in ONE launch, as a round of streaming connections runs them (grid (H, B)): window b is rows [q_off[b], q_off[b] +
+ * q_len[b]) of Q / O against rows [kv_off[b], kv_off[b] + kv_len[b]) of K / V (DEVICE arrays; every length <= 32, max_q_len /
+ * max_kv_len their host-side maxima); a window with q_len[b] <= 0 or kv_len[b] <= 0 writes nothing.  fsmn_w != NULL (self-attention:
+ * q segments == kv segments): the launch also writes the SAN-M memory block of V (pfhip_op_fsmn without a residual, bit for bit) into
+ * mem.  Only columns [0, H * head_dim) of a row are read or written.  hipErrorInvalidValue, before anything is launched, for
+ * max_q_len or max_kv_len outside 1..32, a head width other than 80 or 128, B < 1, H < 1, a NULL buffer, fsmn_w without mem, a row
+ * stride (ldmem with fsmn_w) below H * head_dim or not a multiple of 4. */
+int pfhip_op_window_attention_segments(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
+                                       const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H, int max_q_len,
+                                       int max_kv_len, float scale, const float* fsmn_w, float* mem, int ldmem, int head_dim, void* stream);
 
 /* The window's MatMul-Softmax-MatMul AND the MatMul/Gemm that projects its context (W [N, 512]; +bias, +residual Add, + the SAN-M
  * FSMN memory of fsmn_v over the Lq rows) in ONE launch: H = 4 heads of 128, Lq <= 20, Lk <= 32.  hipErrorInvalidValue otherwise. */
