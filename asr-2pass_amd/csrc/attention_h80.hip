@@ -2,7 +2,7 @@
 // attention_x3.hip: Q, K, V and the probabilities are staged as two fp16 planes (hi = fp16_rtz(x), lo = fp16_rn(x - hi)), three
 // products per block on `v_mfma_f32_32x32x16_f16`, fp32 accumulation, flash-style online softmax, ragged segments through the same
 // q_off / q_len / kv_off / kv_len interface.  Used for launches of more than 64 queries per utterance outside the exact launch
-// context (attention.hip: launch_attention); the fp32-MFMA attention_kernel<80> serves the rest.
+// context (attention.hip: launch_attention); the fp32-MFMA attention_kernel<80, false> serves the rest.
 //
 // One workgroup = 8 waves = 256 query rows of one (utterance, head); a wave keeps its 32 queries' Q planes in registers.  Per 32-key
 // tile:

@@ -220,8 +220,8 @@ void launch_attention_p3(const AttnOp& op, hipStream_t s);
 // d_k = 80 in the same arithmetic class (attention_h80.hip): two fp16 planes, three products per block on v_mfma_f32_32x32x16_f16,
 // fp32 accumulation, online softmax; V^T padded to 96 rows in LDS.  fp32 rows out; no fused memory block, no plane images.
 void launch_attention_h80(const AttnOp& op, hipStream_t s);
-// Plain fp32 attention for any head width 1 <= op.head_dim <= 64 (attention_dk.hip; the large CT-Transformer: 516 / 12 = 43): the
-// arithmetic of launch_attention's fp32-MFMA kernel, q_kv_limit included, on heads that start at any multiple of 4 bytes.  Reads
+// Plain fp32 attention for any head width 1 <= op.head_dim <= 64 (the exact-width form of attention.hip's kernel; the large CT-Transformer: 516 / 12 = 43):
+// the arithmetic of launch_attention's fp32-MFMA kernel, q_kv_limit included, on heads that start at any multiple of 4 bytes.  Reads
 // and writes columns [h * head_dim, (h + 1) * head_dim) of a row and nothing else.  launch_attention does not route here.
 void launch_attention_dk(const AttnOp& op, hipStream_t s);
 // Encoder-layer pair: FSMN memory of V (into mem) + self-attention (into O) over the q segments.  One launch where the BF16

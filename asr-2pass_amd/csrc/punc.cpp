@@ -4,7 +4,7 @@
 // Same kernels as the ASR encoder (fp32 MFMA GEMMs, FSMN memory block, fused attention) plus an embedding gather fused with
 // the x*sqrt(d) + sinusoidal PE step.  Any CT-Transformer with d_model % 4 == 0, d_model <= 1024, a head width
 // d_k = d_model / n_head in [1, 64], ffn % 128 == 0, ffn <= 2048: d_k = 32 (the 256 / 8 / 1024 x 4 model of
-// punc_ct-transformer_zh-cn-common-vocab272727) runs attention.hip's kernel, every other width attention_dk.hip's (the large model
+// punc_ct-transformer_zh-cn-common-vocab272727) runs attention.hip's kernel in its aligned form, every other width in its exact-width form (the large model
 // of the reference's English deployment, recalled as 516 / 12 / 2048 x 12: d_k = 43).  The embedding table (272727 x 256 = 279 MB,
 // 471067 x 516 = 0.97 GB) stays in HBM; a call touches N rows of it.
 //
@@ -319,8 +319,8 @@ static pfhip_status punc_infer_packed(pfhip_punc* p, const int32_t* const* ids, 
   const int* d_len = d_off + B;
   float* x = p->x.f();
   pfhip::launch_embed_gather(d_ids, p->d_table, p->vocab, d, ld, x, ld, total, p->d_inv_ts, sqrtf((float)d), B > 1 ? d_pos : nullptr, s);
-  // every layer's attention, with the VadMask prefix limits when the model is the online one: d_k = 32 on attention.hip's kernel,
-  // any other width on attention_dk.hip's
+  // every layer's attention, with the VadMask prefix limits when the model is the online one: d_k = 32 on the aligned form of attention.hip's
+  // kernel, any other width on its exact-width form
   const int dk = d / p->n_head;
   pfhip::AttnOp att{.Q = p->qkv.f(), .ldq = ldqkv, .K = p->qkv.f() + d, .ldk = ldqkv, .V = p->qkv.f() + 2 * d, .ldv = ldqkv,
                     .O = p->ctx.f(), .ldo = ld};

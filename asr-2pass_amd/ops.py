@@ -239,8 +239,8 @@ def attention_limit(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, q_kv_l
 
 
 def attention_dk(Q, K, V, q_off, q_len, kv_off, kv_len, n_head, scale, d_k, q_kv_limit=None, out=None):
-    """Attention for any head width 1 <= d_k <= 64 (attention_dk.hip), head h in columns [h * d_k, (h + 1) * d_k); q_kv_limit: per
-    packed query row the number of keys it may see.  out: a [rows, >= n_head * d_k] tensor to write into (only those columns of the
+    """Attention for any head width 1 <= d_k <= 64 (the exact-width form of attention.hip's kernel), head h in columns
+    [h * d_k, (h + 1) * d_k); q_kv_limit: per packed query row the number of keys it may see.  out: a [rows, >= n_head * d_k] tensor to write into (only those columns of the
     segments' rows are touched); otherwise a zero-filled [rows, n_head * d_k] one is made."""
     lib = _lib()
     O = torch.zeros((Q.shape[0], n_head * d_k), dtype=torch.float32, device=Q.device) if out is None else out

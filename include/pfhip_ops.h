@@ -85,8 +85,8 @@ int pfhip_op_attention_hd(const float* Q, int ldq, const float* K, int ldk, cons
 int pfhip_op_attention_limit(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
                              const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
                              int max_q_len, float scale, int head_dim, const int* q_kv_limit, void* stream);
-/* The same block for any head width 1 <= d_k <= 64 (attention_dk.hip; the large CT-Transformer: 516 / 12 heads = 43), fp32, head h in
- * columns [h * d_k, (h + 1) * d_k) of a row: no other column is read or written.  q_kv_limit: nullptr, or per packed query row the
+/* The same block for any head width 1 <= d_k <= 64 (the exact-width form of attention.hip's kernel; the large CT-Transformer:
+ * 516 / 12 heads = 43), fp32, head h in columns [h * d_k, (h + 1) * d_k) of a row: no other column is read or written.  q_kv_limit: nullptr, or per packed query row the
  * number of keys it may see (CTTransformerOnline::VadMask).  hipErrorInvalidValue, before anything is launched, for d_k < 1,
  * d_k > 64, H < 1 or a leading dimension below H * d_k. */
 int pfhip_op_attention_dk(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,

@@ -1,5 +1,5 @@
-"""GPU: pfhip_op_attention_dk (attention_dk.hip) — fp32 fused attention for head widths that are not 32, 80 or 128 — against the
-fp64 product of oracle.paraformer.mha, as tests/test_gpu_punc.py::test_attention_head_dim_32_op holds the d_k = 32 form.
+"""GPU: pfhip_op_attention_dk (the exact-width form of attention.hip's kernel) — fp32 fused attention for head widths that are
+not 32, 80 or 128 — against the fp64 product of oracle.paraformer.mha, as tests/test_gpu_punc.py::test_attention_head_dim_32_op holds the d_k = 32 form.
 
 Q, K and V are column slices of one standard-normal [rows, 3 H d_k] matrix, so head h starts at column h * d_k of a row of
 3 H d_k floats: as unaligned as in the model (d_k = 43: 4 bytes).  One packed call holds segments of 1, 31, 32, 33, 100 and 129
@@ -110,6 +110,53 @@ def test_per_query_key_limit(ops, H, dk):
     assert err < TOL, (H, dk, err)
     assert np.abs(ref_masked[:VAD_POS - 1] - ref[o:o + VAD_POS - 1]).max() > 1e-3          # the mask matters
     assert (got[:o] == SENTINEL).all() and (got[o + L:] == SENTINEL).all() and (got[:, d:] == SENTINEL).all()
+
+
+def test_exact_width_form_equals_aligned_form_at_32(ops):
+    """d_k = 32 is served by both forms of the kernel: the same products in the same order, so the same bits.  The slices of a
+    [rows, 3 * 8 * 32] matrix are 16-byte aligned with a stride that is a multiple of 4, which the aligned form asks for."""
+    H, dk = 8, 32
+    qkv, _, _ = case(H, dk)
+    d = H * dk
+    t = dev(qkv)
+    off, ln = dev(OFF), dev(np.asarray(LENS, np.int32))
+    q, k, v = t[:, :d], t[:, d:2 * d], t[:, 2 * d:]
+    exact = ops.attention_dk(q, k, v, off, ln, off, ln, H, dk ** -0.5, dk)
+    aligned = ops.attention(q, k, v, off, ln, off, ln, H, dk ** -0.5, head_dim=dk)
+    print(f"exact-width against aligned form, d_k 32: max abs diff {float((exact - aligned).abs().max()):.3e}")
+    assert exact.shape == aligned.shape == (ROWS, d) and torch.equal(exact, aligned)
+
+
+def test_exact_width_form_equals_aligned_form_at_32_with_key_limits(ops):
+    """The same on the 100-row segment under the vad_pos = 37 limits of test_per_query_key_limit."""
+    H, dk = 8, 32
+    qkv, _, _ = case(H, dk)
+    d = H * dk
+    o, L = int(OFF[4]), LENS[4]
+    t = dev(qkv)
+    lim = np.full(ROWS, -1, np.int32)
+    lim[o:o + L] = [VAD_POS if i < VAD_POS - 1 else L for i in range(L)]
+    lim = dev(lim)
+    off, ln = dev(np.asarray([o], np.int32)), dev(np.asarray([L], np.int32))
+    q, k, v = t[:, :d], t[:, d:2 * d], t[:, 2 * d:]
+    exact = ops.attention_dk(q, k, v, off, ln, off, ln, H, dk ** -0.5, dk, q_kv_limit=lim)
+    aligned = ops.attention_limit(q, k, v, off, ln, off, ln, H, dk ** -0.5, lim, head_dim=dk)
+    print(f"exact-width against aligned form, d_k 32, key limits: max abs diff {float((exact - aligned).abs().max()):.3e}")
+    assert torch.equal(exact[o:o + L], aligned[o:o + L])
+    assert bool((exact[o:o + L] != 0).any())          # (both start from zeros: the segment was written)
+
+
+def test_empty_key_segment_writes_nothing(ops):
+    """kv_len = 0 in the exact-width form: the kernel returns before any load, and no element of the output is written."""
+    H, dk = 12, 43
+    qkv, _, _ = case(H, dk)
+    d = H * dk
+    t = dev(qkv)
+    off, q_len, kv_len = dev(np.asarray([0], np.int32)), dev(np.asarray([33], np.int32)), dev(np.asarray([0], np.int32))
+    O = sentinel_out(H, dk)
+    ops.attention_dk(t[:, :d], t[:, d:2 * d], t[:, 2 * d:], off, q_len, off, kv_len, H, dk ** -0.5, dk, out=O)
+    torch.cuda.synchronize()
+    assert bool((O == SENTINEL).all())
 
 
 def test_refusals_launch_nothing(ops, pkg):

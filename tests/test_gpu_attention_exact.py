@@ -4,7 +4,7 @@ softmax(QK^T)V in fp64 per segment, through the operator-level C ABI (include/pf
 
   exact, more than 64 queries in the longest segment   attention_x6.hip: three bf16 planes, six products, its own copy of the fused SAN-M
                                                        memory block, lazy rescale when a maximum outgrows the reference by 2^16
-  exact, up to 64 queries                              the fp32-MFMA attention_kernel<128> of attention.hip
+  exact, up to 64 queries                              the fp32-MFMA attention_kernel<128, false> of attention.hip
   default context, more than 64 queries                attention_x3.hip / attention_p3.hip (d_k = 128), attention_h80.hip (d_k = 80):
                                                        two fp16 planes, lazy rescale at 2^10
 

@@ -3,7 +3,7 @@ through the operator-level C ABI (include/pfhip_ops.h).
 
   pfhip_op_attention_hd(head_dim = 80)   more than 64 queries in the longest segment: attention_h80.hip (two fp16 planes, three
                                          products on v_mfma_f32_32x32x16_f16, V^T padded to 96 rows in LDS); up to 64 queries, or the
-                                         launch context set to exact: the fp32-MFMA attention_kernel<80> of attention.hip
+                                         launch context set to exact: the fp32-MFMA attention_kernel<80, false> of attention.hip
   pfhip_op_window_attention_hd(80)       one streaming window, stream_fused.hip window_attention_kernel<80>
 
 Tolerances are the ones tests/test_gpu_ops.py holds the d_k = 128 forms to (2e-5; 3e-4 for scores of magnitude ~500)."""
@@ -97,7 +97,7 @@ def large_range_inputs():
     return Q, K, V
 
 
-@pytest.mark.parametrize("n_q", [300, 40])            # attention_h80.hip (lazy rescale) / attention_kernel<80> (rescale per tile)
+@pytest.mark.parametrize("n_q", [300, 40])            # attention_h80.hip (lazy rescale) / attention_kernel<80, false> (rescale per tile)
 def test_rescale_branch_and_large_score_range(ops, n_q):
     Q, K, V = large_range_inputs()
     Q = Q[:n_q]

@@ -2,7 +2,7 @@
 """Wall time of the punctuation calls on the two CT-Transformer shapes ("The large CT-Transformer").
 
 Synthetic weights, vocabulary 5000: `small` = 256 / 8 / 1024 x 4 (d_k = 32, attention.hip's kernel), `large` = 516 / 12 / 2048 x 12
-(d_k = 43, attention_dk.hip's).  Three loads per model: Infer of 20 ids, Infer of 200 ids, pfhip_punc_infer_batch of 32 x 40 ids.
+(d_k = 43, its exact-width form).  Three loads per model: Infer of 20 ids, Infer of 200 ids, pfhip_punc_infer_batch of 32 x 40 ids.
 Per load, warm-up calls and then timed calls with the models alternating call by call, so that clock and thermal drift hit both
 alike.  Wall time per call includes the upload of the ids and the download of the punctuation ids.
 
