@@ -454,6 +454,16 @@ int pfhip_op_us_cif(const float* a2, const int* off, const int* len, const int* 
   pfhip::launch_us_cif(a2, off, len, token_num, B, max_len, threshold, us_alphas, us_peaks, S(stream));
   return done();
 }
+int pfhip_op_blstm_scratch_floats(void) { return pfhip::kBlstmScratchFloats; }
+int pfhip_op_blstm_flag_word(void) { return pfhip::kBlstmFlagWord; }
+int pfhip_op_blstm(const float* gx, const float* whh, float* y, const int* off, const int* len, int B, int Lmax, int stepwise, float* hx,
+                   float* cst, void* stream) {
+  if (B < 0 || B > 32 || Lmax < 0 || !gx || !whh || !y || !off || !len || !hx || (stepwise && !cst)) return (int)hipErrorInvalidValue;
+  if (B == 0 || Lmax == 0) return 0;
+  const hipError_t e = stepwise ? pfhip::launch_blstm_stepwise(gx, whh, y, hx, cst, off, len, B, Lmax, S(stream))
+                                : pfhip::launch_blstm(gx, whh, y, hx, off, len, B, Lmax, S(stream));
+  return (int)e;
+}
 int pfhip_op_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, int t, float* sel, int H, int D, void* stream) {
   if (H < 0 || D <= 0 || !G || !c || !h || !lens || !sel) return (int)hipErrorInvalidValue;
   pfhip::launch_lstm_cell(G, c, h, lens, t, sel, H, D, S(stream));

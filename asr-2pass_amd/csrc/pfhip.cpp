@@ -565,6 +565,14 @@ pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manife
     for (const char* sfx : {"", "_r"}) {
       std::memcpy(&wih[(size_t)dir * 4 * d * d], T(std::string("pred.blstm.w_ih") + sfx).h, sizeof(float) * 4 * d * d);
       std::memcpy(&whh[(size_t)dir * 4 * d * d], T(std::string("pred.blstm.w_hh") + sfx).h, sizeof(float) * 4 * d * d);
+      // blstm.hip stages W_hh times 2^10 as two fp16 planes: its header states |w| < 32 (beyond, the low plane loses bits, then
+      // the high plane overflows).  Refused here, where the weights are still named.
+      for (size_t k = 0; k < (size_t)4 * d * d; ++k) {
+        const float v = whh[(size_t)dir * 4 * d * d + k];
+        if (!(std::fabs(v) < 32.0f))
+          return fail(PFHIP_ERR_UNSUPPORTED, std::string("timestamp head: pred.blstm.w_hh") + sfx + " holds " + std::to_string(v) + " at element " +
+                                                 std::to_string(k) + "; the recurrence kernel takes |w_hh| < 32 (finite)");
+      }
       const float* bi = T(std::string("pred.blstm.b_ih") + sfx).h;
       const float* bh = T(std::string("pred.blstm.b_hh") + sfx).h;
       for (int k = 0; k < 4 * d; ++k) bih[(size_t)dir * 4 * d + k] = bi[k] + bh[k];

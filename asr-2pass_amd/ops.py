@@ -633,6 +633,40 @@ def us_cif(a2, off, length, token_num, threshold):
     return us_alphas, us_peaks
 
 
+def blstm_scratch():
+    """(floats of scratch pfhip_op_blstm takes, index of its error word): the layout csrc/kernels.h states, asked of the library."""
+    lib = _lib()
+    return int(lib.pfhip_op_blstm_scratch_floats()), int(lib.pfhip_op_blstm_flag_word())
+
+
+def blstm_entry(gx, whh, y, off, length, B, Lmax, stepwise, hx, cst):
+    """pfhip_op_blstm as it is, on the current stream, nothing allocated or checked here (any tensor may be None = NULL)."""
+    lib = _lib()
+    lib.pfhip_op_blstm.argtypes = [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]
+    _ck(lib.pfhip_op_blstm(_p(gx), _p(whh), _p(y), _p(off), _p(length), int(B), int(Lmax), int(bool(stepwise)), _p(hx), _p(cst), _stream()),
+        "blstm")
+
+
+def blstm(gx, whh, off, length, stepwise=False, Lmax=None, y=None):
+    """The timestamp head's BLSTM recurrence: gx [rows, 4096], whh [2, 2048, 512], off / length int32 device tensors of B <= 32
+    utterances.  stepwise=False runs the persistent kernel, True the one-launch-per-step form.  Runs on the current stream and
+    synchronises.  Returns (y [rows, 1024], flag, xcc_words): flag is the persistent kernel's error word (0 = served, 1 = the h
+    exchange timed out, 2 = a direction's blocks were not on one XCD), xcc_words the XCC id + 1 each direction noted (0 = never
+    written; the stepwise form writes neither).  A y that is passed in is written in place, rows outside utterances untouched."""
+    B = off.numel()
+    if Lmax is None:
+        Lmax = int(length.max().item()) if B else 0
+    if y is None:
+        y = torch.zeros((gx.shape[0], 1024), dtype=torch.float32, device=gx.device)
+    n_scratch, flag_word = blstm_scratch()
+    hx = torch.zeros(n_scratch, dtype=torch.float32, device=gx.device)
+    cst = torch.zeros(2 * 32 * 512, dtype=torch.float32, device=gx.device)
+    blstm_entry(gx, whh, y, off, length, B, Lmax, stepwise, hx, cst)
+    torch.cuda.current_stream().synchronize()
+    state = hx[flag_word:flag_word + 4].view(torch.int32).cpu().tolist()
+    return y, state[0], (state[2], state[3])
+
+
 def lstm_cell(G, c, h, lens, t, sel):
     """One LSTM step in place on c, h [H, D] from pre-activations G [H, 4 D]; sel rows with lens - 1 == t receive h."""
     H, D = c.shape

@@ -265,6 +265,19 @@ int pfhip_op_alpha2(const float* y, int ldy, const float* w, float b, float smoo
  * sum to token_num[b], us_peaks = cif_wo_hidden(us_alphas, threshold). */
 int pfhip_op_us_cif(const float* a2, const int* off, const int* len, const int* token_num, int B, int max_len, float threshold,
                     float* us_alphas, float* us_peaks, void* stream);
+/* The timestamp head's bidirectional LSTM recurrence (hidden 512) over B <= 32 packed utterances (frames [off[b], off[b] + len[b]);
+ * DEVICE arrays; len[b] <= Lmax): gx [rows, 4096] = input projections + biases (forward i,f,g,o | backward i,f,g,o), whh
+ * [2][2048][512] with |w| < 32, y [rows, 1024] = forward h | backward h; only rows inside an utterance are written.  stepwise == 0:
+ * the persistent kernel; stepwise != 0: one launch per step (bit-identical).  hx = pfhip_op_blstm_scratch_floats() floats that the
+ * caller zeroed once; after the stream has drained, word pfhip_op_blstm_flag_word() of hx is the persistent kernel's error word
+ * (0 = served; 1 = its h exchange timed out; 2 = the blocks of a direction were not on one XCD; y is then not valid) and the
+ * words flag + 2, flag + 3 hold the XCC id + 1 of the forward and the backward direction.  cst = 2 * 32 * 512 floats of cell
+ * state (stepwise only; may be NULL otherwise).  B = 0 or Lmax = 0 writes nothing.  hipErrorInvalidValue, before anything is
+ * launched, for B > 32, B < 0, Lmax < 0 or a NULL buffer. */
+int pfhip_op_blstm_scratch_floats(void);
+int pfhip_op_blstm_flag_word(void);
+int pfhip_op_blstm(const float* gx, const float* whh, float* y, const int* off, const int* len, int B, int Lmax, int stepwise, float* hx,
+                   float* cst, void* stream);
 /* One LSTM step of the hotword embedder on pre-activations G [H][4 D] (gates i, f, g, o): c, h [H][D] updated in place; rows with
  * lens[j] - 1 == t also copy h into sel[j]. */
 int pfhip_op_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, int t, float* sel, int H, int D, void* stream);
