@@ -371,6 +371,21 @@ bool launch_fused_att_out(const float* Q, int ldq, const float* K, int ldk, cons
 bool launch_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, float* C, int ldc, const float* bias, const float* ln_colsum,
                              float eps, const float* R1, int ldr1, const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K,
                              bool relu, hipStream_t s);
+// Which instantiation and launch geometry the two launchers above take for a shape: host arithmetic only (nothing is launched, no
+// device is needed), the environment knobs of this process included.  The launchers launch exactly what these return — the one
+// place the choice is made.
+struct Gemv1tRoute {        // fused_gemv1t_kernel<LN, FS, CW, CPL, 4, RPL, NF> on `waves` waves; ok == false: refused (all else 0)
+  bool ok, ln, fs;
+  int cw, cpl, rpl, nf, waves;
+};
+Gemv1tRoute fused_gemv_1trip_route(int M, int N, int K, bool has_ln, bool has_fsmn);
+enum LnGemmKernel { kLnGemmNone = 0, kLnGemmVector = 1, kLnGemmMatrix = 2 };      // none: M <= 0 or N <= 0, nothing to launch
+struct LnGemmRoute {        // fused_ln_gemv_kernel<LN, CW, MR> (vector) or fused_ln_gemm_kernel<LN, CW> (matrix: MR = 32, 16 waves)
+  LnGemmKernel kernel;      // k_blocks: the k-blocks the waves share (K / (256 / CW) in the vector form, K / 8 in the matrix form)
+  bool ln;
+  int cw, mr, waves, k_blocks;
+};
+LnGemmRoute fused_ln_gemm_route(int M, int N, int K, bool has_ln);
 
 // ---- FSMN-VAD pieces --------------------------------------------------------------
 // Generic LfrCmvn over raw fbank frames fb [F, n_mels] -> out [T = ceil(F/n), ldo] (columns >= m*n_mels zeroed).

@@ -35,6 +35,8 @@ bool kernel_of_kind(int kind, pfhip::GemmKernel* kernel) {
   *kernel = table[kind];
   return true;
 }
+// the rows and K that pfhip_op_fused_ln_gemm and its route entry take
+inline bool ln_gemm_shape_ok(int M, int K) { return M >= 1 && M <= 32 && K % 8 == 0; }
 }  // namespace
 
 extern "C" {
@@ -52,7 +54,7 @@ int pfhip_op_gemm_f32_kind(const float* A, int lda, const float* W, int ldw, flo
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
                            float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
                            const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K, int relu, void* stream) {
-  if (M < 1 || M > 32 || K % 8 || (g && (D % 4 || D > K || D > 2048))) return (int)hipErrorInvalidValue;
+  if (!ln_gemm_shape_ok(M, K) || (g && (D % 4 || D > K || D > 2048))) return (int)hipErrorInvalidValue;
   pfhip::launch_fused_ln_gemm(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu != 0,
                               S(stream));
   return done();
@@ -72,6 +74,21 @@ int pfhip_op_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, 
   if (!pfhip::launch_fused_gemv_1trip(X, ldx, W, ldw, C, ldc, bias, ln_colsum, eps, R1, ldr1, fsmn_v, ldv, fsmn_w, M, N, K, relu != 0, S(stream)))
     return (int)hipErrorInvalidValue;
   return done();
+}
+// what the two entries above would launch (kernels.h: the launchers' own choice; nothing is launched, no device is touched)
+int pfhip_op_fused_gemv_1trip_route(int M, int N, int K, int has_ln, int has_fsmn, int* out) {
+  if (!out) return (int)hipErrorInvalidValue;
+  const pfhip::Gemv1tRoute r = pfhip::fused_gemv_1trip_route(M, N, K, has_ln != 0, has_fsmn != 0);
+  const int v[8] = {r.ok, r.ln, r.fs, r.cw, r.cpl, r.rpl, r.nf, r.waves};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return 0;
+}
+int pfhip_op_fused_ln_gemm_route(int M, int N, int K, int has_ln, int* out) {
+  if (!out || !ln_gemm_shape_ok(M, K)) return (int)hipErrorInvalidValue;
+  const pfhip::LnGemmRoute r = pfhip::fused_ln_gemm_route(M, N, K, has_ln != 0);
+  const int v[6] = {(int)r.kernel, r.ln, r.cw, r.mr, r.waves, r.k_blocks};
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
+  return 0;
 }
 // dev hook (tools/fused_gemv_bench.py): the one-trip form over the same ring of weight copies
 int pfhip_dev_fused_gemv_1trip_bench(const float* X, int ldx, const float* W, int ldw, size_t w_stride_floats, int n_copies, float* C, int ldc,

@@ -696,53 +696,88 @@ __global__ __launch_bounds__(1024) void fused_att_out_kernel(
 
 }  // namespace
 
-template <bool LN, int CW>
-static void launch_gemv(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw, float* C,
-                        int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2, const float* fsmn_v, int ldv,
-                        const float* fsmn_w, int M, int N, int K, bool relu, hipStream_t s) {
-  constexpr int KI = 4 * (64 / CW);
-  // LayerNorm needs 32 threads per row for its statistics: all 16 waves; without it, one wave per k-block is enough
-  const int waves = g ? kWaves : std::max(1, std::min(kWaves, K / KI));
-  const dim3 grid((N + CW - 1) / CW), block(64 * waves);
-#define PFHIP_LAUNCH(MR_)                                                                                                            \
-  hipLaunchKernelGGL((fused_ln_gemv_kernel<LN, CW, MR_>), grid, block, 0, s, X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, \
-                     ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu ? 1 : 0)
-  if (M <= 8) PFHIP_LAUNCH(8); else if (M <= 16) PFHIP_LAUNCH(16); else if (M <= 24) PFHIP_LAUNCH(24); else PFHIP_LAUNCH(32);
-#undef PFHIP_LAUNCH
+// ---- routing: which instantiation a shape gets (kernels.h; the launchers below launch exactly what these return) -----------------
+LnGemmRoute fused_ln_gemm_route(int M, int N, int K, bool has_ln) {
+  LnGemmRoute r = {kLnGemmNone, false, 0, 0, 0, 0};
+  if (M <= 0 || N <= 0) return r;
+  r.ln = has_ln;
+  // patch width: at least ~128 workgroups per launch (N = 512 -> 4 columns, 1024-2048 -> 8, the vocabulary -> 32)
+  // (N = 512 at K = 2048: 2 columns -> 256 workgroups and ONE k-block per wave instead of two: three dependent round trips to L2
+  // per lane instead of six)
+  // The 2-column form walks K in k-blocks of 128: a K with 64 left over keeps 4 columns, whose k-block of 64 divides every K the
+  // vector form takes.
+  const int cw = N <= 640 ? (K >= 1024 && K % 128 == 0 ? 2 : 4) : (N <= 4096 ? 8 : 32);
+  static const bool use_mfma = env_is1("PFHIP_STREAM_FUSED_MFMA");
+  if (!use_mfma && K % 64 == 0 && N <= 4096) {
+    const int ki = 4 * (64 / cw);            // k per wave and iteration (fused_ln_gemv_kernel's KI)
+    r.kernel = kLnGemmVector;
+    r.cw = cw;
+    r.mr = M <= 8 ? 8 : M <= 16 ? 16 : M <= 24 ? 24 : 32;
+    r.k_blocks = K / ki;
+    // LayerNorm needs 32 threads per row for its statistics: all 16 waves; without it, one wave per k-block is enough — but never
+    // fewer threads than the MR x CW outputs the workgroup finishes, one each (K = 64: 1-2 k-blocks)
+    r.waves = has_ln ? kWaves : std::max((r.mr * cw + 63) / 64, std::min(kWaves, K / ki));
+    return r;
+  }
+  r.kernel = kLnGemmMatrix;
+  r.cw = cw == 2 ? 4 : cw;
+  r.mr = kRows;
+  r.waves = kWaves;
+  r.k_blocks = K >> 3;
+  return r;
+}
+
+// PFHIP_STREAM_1TRIP=0 turns the form off; PFHIP_1T_CPL = columns per lane (measured: 2 beats 1 and 4 on every window shape).
+Gemv1tRoute fused_gemv_1trip_route(int M, int N, int K, bool has_ln, bool has_fsmn) {
+  const Gemv1tRoute no = {false, false, false, 0, 0, 0, 0, 0};
+  static const bool on = env_on("PFHIP_STREAM_1TRIP");
+  if (!on || M <= 0 || M > 20 || N <= 0 || (has_fsmn && has_ln)) return no;
+  // patch width as in fused_ln_gemm_route; rows over 4 lane groups; a wave per k-block: K = waves * KS * 4 NF
+  static const int cpl = [] { const char* e = getenv("PFHIP_1T_CPL"); return e ? atoi(e) : 2; }();
+  const int cw = N <= 640 ? (K >= 2048 ? 2 : 4) : 8;
+  if (cpl > cw || (cpl != 1 && cpl != 2 && cpl != 4)) return no;
+  const int ks = 64 / (cw / cpl * 4);
+  int nf = K / (kWaves * ks * 4) >= 1 ? K / (kWaves * ks * 4) : 1;
+  // N = 512, K = 512 (4-column patches): 8 waves with twice the k per lane beat 16 (4.45-4.66 vs 4.85 us: half the partial sums)
+  if (cw == 4 && 2 * nf <= 4 && K % (ks * 4 * 2 * nf) == 0 && 64 * (K / (ks * 4 * 2 * nf)) >= 20 * cw) nf *= 2;
+  const int ki = ks * 4 * nf;
+  if (K % ki || K / ki > kWaves || N % cw || nf < 1 || nf > 4) return no;
+  if (64 * (K / ki) < (M <= 8 ? 8 : 20) * cw) return no;       // the lanes that finish the outputs must exist (tiny K)
+  return {true, has_ln, has_fsmn, cw, cpl, M <= 8 ? 2 : 5, nf, K / ki};
 }
 
 void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
                           float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
                           const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K, bool relu, hipStream_t s) {
-  if (M <= 0 || N <= 0) return;
-  // patch width: at least ~128 workgroups per launch (N = 512 -> 4 columns, 1024-2048 -> 8, the vocabulary -> 32)
-  // (N = 512 at K = 2048: 2 columns -> 256 workgroups and ONE k-block per wave instead of two: three dependent round trips to L2
-  // per lane instead of six)
-  const int cw = N <= 640 ? (K >= 1024 ? 2 : 4) : (N <= 4096 ? 8 : 32);
-  static const bool use_mfma = env_is1("PFHIP_STREAM_FUSED_MFMA");
-  if (!use_mfma && K % 64 == 0 && N <= 4096) {
-    if (g) {
-      if (cw == 2) launch_gemv<true, 2>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-      else if (cw == 4) launch_gemv<true, 4>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-      else if (cw == 8) launch_gemv<true, 8>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-      else launch_gemv<true, 32>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-    } else {
-      if (cw == 2) launch_gemv<false, 2>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-      else if (cw == 4) launch_gemv<false, 4>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-      else if (cw == 8) launch_gemv<false, 8>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-      else launch_gemv<false, 32>(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu, s);
-    }
+  const LnGemmRoute r = fused_ln_gemm_route(M, N, K, g != nullptr);
+  if (r.kernel == kLnGemmNone) return;
+  const dim3 grid((N + r.cw - 1) / r.cw), block(64 * r.waves);
+  if (r.kernel == kLnGemmVector) {
+#define PFHIP_LAUNCH(LN_, CW_, MR_)                                                                                                    \
+  hipLaunchKernelGGL((fused_ln_gemv_kernel<LN_, CW_, MR_>), grid, block, 0, s, X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, \
+                     ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu ? 1 : 0)
+#define PFHIP_PICK_MR(LN_, CW_)                                                                     \
+  do {                                                                                              \
+    if (r.mr == 8) PFHIP_LAUNCH(LN_, CW_, 8); else if (r.mr == 16) PFHIP_LAUNCH(LN_, CW_, 16);      \
+    else if (r.mr == 24) PFHIP_LAUNCH(LN_, CW_, 24); else PFHIP_LAUNCH(LN_, CW_, 32);               \
+  } while (0)
+#define PFHIP_PICK_CW(LN_)                                                                          \
+  do {                                                                                              \
+    if (r.cw == 2) PFHIP_PICK_MR(LN_, 2); else if (r.cw == 4) PFHIP_PICK_MR(LN_, 4); else PFHIP_PICK_MR(LN_, 8); \
+  } while (0)
+    if (r.ln) PFHIP_PICK_CW(true); else PFHIP_PICK_CW(false);
+#undef PFHIP_PICK_CW
+#undef PFHIP_PICK_MR
+#undef PFHIP_LAUNCH
     return;
   }
-  const int cwm = cw == 2 ? 4 : cw;
-  const dim3 grid((N + cwm - 1) / cwm), block(kThreads);
 #define PFHIP_LAUNCH(LN_, CW_)                                                                                                    \
   hipLaunchKernelGGL((fused_ln_gemm_kernel<LN_, CW_>), grid, block, 0, s, X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, \
                      ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu ? 1 : 0)
-  if (g) {
-    if (cwm == 4) PFHIP_LAUNCH(true, 4); else if (cwm == 8) PFHIP_LAUNCH(true, 8); else PFHIP_LAUNCH(true, 32);
+  if (r.ln) {
+    if (r.cw == 4) PFHIP_LAUNCH(true, 4); else if (r.cw == 8) PFHIP_LAUNCH(true, 8); else PFHIP_LAUNCH(true, 32);
   } else {
-    if (cwm == 4) PFHIP_LAUNCH(false, 4); else if (cwm == 8) PFHIP_LAUNCH(false, 8); else PFHIP_LAUNCH(false, 32);
+    if (r.cw == 4) PFHIP_LAUNCH(false, 4); else if (r.cw == 8) PFHIP_LAUNCH(false, 8); else PFHIP_LAUNCH(false, 32);
   }
 #undef PFHIP_LAUNCH
 }
@@ -750,39 +785,28 @@ void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const 
 
 // One-trip form (fused_gemv1t_kernel).  W / bias are the LayerNorm-folded ones when ln_colsum is given (the caller's LayerNorm is
 // over exactly the K operand columns).  False when the shape is outside what the kernel takes — the caller falls back to
-// launch_fused_ln_gemm with the plain weights.  PFHIP_STREAM_1TRIP=0 turns it off.
+// launch_fused_ln_gemm with the plain weights.
 bool launch_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, float* C, int ldc, const float* bias, const float* ln_colsum,
                              float eps, const float* R1, int ldr1, const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K,
                              bool relu, hipStream_t s) {
-  static const bool on = env_on("PFHIP_STREAM_1TRIP");
-  if (!on || M <= 0 || M > 20 || N <= 0 || (fsmn_v && ln_colsum)) return false;
-  // patch width as in launch_fused_ln_gemm; rows over 4 lane groups; a wave per k-block: K = waves * KS * 4 NF
-  static const int cpl = [] { const char* e = getenv("PFHIP_1T_CPL"); return e ? atoi(e) : 2; }();     // columns per lane (measured: 2 beats 1 and 4 on every window shape)
-  const int cw = N <= 640 ? (K >= 2048 ? 2 : 4) : 8;
-  if (cpl > cw || (cpl != 1 && cpl != 2 && cpl != 4)) return false;
-  const int ks = 64 / (cw / cpl * 4);
-  int nf = K / (kWaves * ks * 4) >= 1 ? K / (kWaves * ks * 4) : 1;
-  // N = 512, K = 512 (4-column patches): 8 waves with twice the k per lane beat 16 (4.45-4.66 vs 4.85 us: half the partial sums)
-  if (cw == 4 && 2 * nf <= 4 && K % (ks * 4 * 2 * nf) == 0 && 64 * (K / (ks * 4 * 2 * nf)) >= 20 * cw) nf *= 2;
-  const int ki = ks * 4 * nf;
-  if (K % ki || K / ki > kWaves || N % cw || nf < 1 || nf > 4) return false;
-  if (64 * (K / ki) < (M <= 8 ? 8 : 20) * cw) return false;       // the lanes that finish the outputs must exist (tiny K)
-  const dim3 grid(N / cw), block(64 * (K / ki));
+  const Gemv1tRoute r = fused_gemv_1trip_route(M, N, K, ln_colsum != nullptr, fsmn_v != nullptr);
+  if (!r.ok) return false;
+  const dim3 grid(N / r.cw), block(64 * r.waves);
 #define PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, RPL_, NF_)                                                                                      \
   hipLaunchKernelGGL((fused_gemv1t_kernel<LN_, FS_, CW_, CPL_, 4, RPL_, NF_>), grid, block, 0, s, X, ldx, W, ldw, C, ldc, bias, ln_colsum, eps, \
                      R1, ldr1, fsmn_v, ldv, fsmn_w, M, N, K, relu ? 1 : 0)
 #define PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, NF_)                                   \
-  do { if (M <= 8) PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, 2, NF_); else PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, 5, NF_); } while (0)
+  do { if (r.rpl == 2) PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, 2, NF_); else PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, 5, NF_); } while (0)
 #define PFHIP_PICK_NF(LN_, FS_, CW_, CPL_)                                        \
-  do { if (nf == 1) PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 1); else if (nf == 2) PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 2); else if (nf == 3) PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 3); else PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 4); } while (0)
+  do { if (r.nf == 1) PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 1); else if (r.nf == 2) PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 2); else if (r.nf == 3) PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 3); else PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, 4); } while (0)
 #define PFHIP_PICK_CW(LN_, FS_)                                                                       \
   do {                                                                                                \
-    if (cpl == 1) { if (cw == 2) PFHIP_PICK_NF(LN_, FS_, 2, 1); else if (cw == 4) PFHIP_PICK_NF(LN_, FS_, 4, 1); else PFHIP_PICK_NF(LN_, FS_, 8, 1); } \
-    else if (cpl == 2) { if (cw == 2) PFHIP_PICK_NF(LN_, FS_, 2, 2); else if (cw == 4) PFHIP_PICK_NF(LN_, FS_, 4, 2); else PFHIP_PICK_NF(LN_, FS_, 8, 2); } \
-    else { if (cw == 4) PFHIP_PICK_NF(LN_, FS_, 4, 4); else PFHIP_PICK_NF(LN_, FS_, 8, 4); }                                                              \
+    if (r.cpl == 1) { if (r.cw == 2) PFHIP_PICK_NF(LN_, FS_, 2, 1); else if (r.cw == 4) PFHIP_PICK_NF(LN_, FS_, 4, 1); else PFHIP_PICK_NF(LN_, FS_, 8, 1); } \
+    else if (r.cpl == 2) { if (r.cw == 2) PFHIP_PICK_NF(LN_, FS_, 2, 2); else if (r.cw == 4) PFHIP_PICK_NF(LN_, FS_, 4, 2); else PFHIP_PICK_NF(LN_, FS_, 8, 2); } \
+    else { if (r.cw == 4) PFHIP_PICK_NF(LN_, FS_, 4, 4); else PFHIP_PICK_NF(LN_, FS_, 8, 4); }                                                              \
   } while (0)
-  if (ln_colsum) PFHIP_PICK_CW(true, false);
-  else if (fsmn_v) PFHIP_PICK_CW(false, true);
+  if (r.ln) PFHIP_PICK_CW(true, false);
+  else if (r.fs) PFHIP_PICK_CW(false, true);
   else PFHIP_PICK_CW(false, false);
 #undef PFHIP_PICK_CW
 #undef PFHIP_PICK_NF

@@ -171,6 +171,27 @@ def fused_gemv_1trip(X, W, M, N, bias=None, ln_colsum=None, R1=None, fsmn_v=None
     return out
 
 
+def fused_gemv_1trip_route(M, N, K, ln=False, fsmn=False):
+    """What fused_gemv_1trip would launch for the shape (the launcher's own choice; nothing is launched, no device needed):
+    dict(ok, ln, fs, cw, cpl, rpl, nf, waves); ok False = the shape is refused."""
+    lib = _lib()
+    lib.pfhip_op_fused_gemv_1trip_route.argtypes = [_ci, _ci, _ci, _ci, _ci, ctypes.POINTER(_ci)]
+    out = (_ci * 8)()
+    _ck(lib.pfhip_op_fused_gemv_1trip_route(int(M), int(N), int(K), 1 if ln else 0, 1 if fsmn else 0, out), "fused_gemv_1trip_route")
+    ok, ln_, fs, cw, cpl, rpl, nf, waves = list(out)
+    return dict(ok=bool(ok), ln=bool(ln_), fs=bool(fs), cw=cw, cpl=cpl, rpl=rpl, nf=nf, waves=waves)
+
+
+def fused_ln_gemm_route(M, N, K, ln=False):
+    """What fused_ln_gemm would launch for the shape: dict(kernel = "vector" | "matrix", ln, cw, mr, waves, k_blocks)."""
+    lib = _lib()
+    lib.pfhip_op_fused_ln_gemm_route.argtypes = [_ci, _ci, _ci, _ci, ctypes.POINTER(_ci)]
+    out = (_ci * 6)()
+    _ck(lib.pfhip_op_fused_ln_gemm_route(int(M), int(N), int(K), 1 if ln else 0, out), "fused_ln_gemm_route")
+    kernel, ln_, cw, mr, waves, k_blocks = list(out)
+    return dict(kernel={1: "vector", 2: "matrix"}.get(kernel, "none"), ln=bool(ln_), cw=cw, mr=mr, waves=waves, k_blocks=k_blocks)
+
+
 def layernorm(x, g, b, D=None, Dout=None, eps=1e-12):
     M = x.shape[0]
     D = x.shape[1] if D is None else D

@@ -174,6 +174,13 @@ int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const
 int pfhip_op_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, float* C, int ldc, const float* bias,
                               const float* ln_colsum, float eps, const float* R1, int ldr1, const float* fsmn_v, int ldv,
                               const float* fsmn_w, int M, int N, int K, int relu, void* stream);
+/* Which kernel instantiation and launch geometry the two entries above take for a shape — the launchers' own choice, reported by the
+ * function they call; nothing is launched and no device is needed; the PFHIP_* knobs of this process count.
+ * pfhip_op_fused_gemv_1trip_route: out[8] = {ok, LN, FS, CW, CPL, RPL, NF, waves} (has_ln: ln_colsum given, has_fsmn: fsmn_v given;
+ * ok = 0: the shape is refused and the rest is 0).  pfhip_op_fused_ln_gemm_route: out[6] = {kernel (1 = vector form, 2 = matrix
+ * form), LN, CW, MR, waves, k_blocks}; hipErrorInvalidValue for the M and K that pfhip_op_fused_ln_gemm refuses, and for out == NULL. */
+int pfhip_op_fused_gemv_1trip_route(int M, int N, int K, int has_ln, int has_fsmn, int* out);
+int pfhip_op_fused_ln_gemm_route(int M, int N, int K, int has_ln, int* out);
 
 /* MatMul-Softmax-MatMul of ONE streaming window: Lq <= 32 queries against Lk <= 32 keys (rows 0.. of the given pointers), H heads of
  * d_k = 128 (the streaming encoder's self-attention over its 20-row window, the decoder's tokens against it:
