@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "pfhip_lfr_frame_ms", "pfhip_cif_timestamps",
     # SenseVoiceSmall, offline: CTC head over every frame, collapsed on the device
     "pfhip_is_ctc", "pfhip_svs_lid", "pfhip_svs_forward", "pfhip_svs_forward_s16",
+    # SenseVoiceSmall: CTC forced alignment of a token sequence against the last forward's rows
+    "pfhip_svs_align",
 ]
 
 
@@ -108,6 +110,11 @@ class _SvsOut(ctypes.Structure):
                 ("tok_frame", ctypes.POINTER(ctypes.c_int32)), ("tok_logp", ctypes.POINTER(ctypes.c_float)),
                 ("frame_ids", ctypes.POINTER(ctypes.c_int32)), ("frame_logp", ctypes.POINTER(ctypes.c_float)),
                 ("frame_len", ctypes.POINTER(ctypes.c_int32)), ("logp", ctypes.POINTER(ctypes.c_float)), ("logp_cap_floats", ctypes.c_size_t)]
+
+
+class _SvsAlignOut(ctypes.Structure):
+    _fields_ = [("tok_begin", ctypes.POINTER(ctypes.c_int32)), ("tok_end", ctypes.POINTER(ctypes.c_int32)),
+                ("tok_logp", ctypes.POINTER(ctypes.c_float)), ("score", ctypes.POINTER(ctypes.c_float)), ("max_tokens", ctypes.c_int)]
 
 
 class _StreamDetail(ctypes.Structure):
@@ -264,6 +271,8 @@ def load_lib() -> ctypes.CDLL:
         lib.pfhip_svs_forward.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ctypes.POINTER(ctypes.c_int32),
                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_SvsOut)]
         lib.pfhip_svs_forward_s16.argtypes = lib.pfhip_svs_forward.argtypes
+    if hasattr(lib, "pfhip_svs_align"):
+        lib.pfhip_svs_align.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ctypes.POINTER(_SvsAlignOut)]
     lib.pfhip_profile_enable.argtypes = [vp, ci]
     lib.pfhip_profile_read.argtypes = [vp, ctypes.POINTER(_Profile), ci]
     # 16-bit PCM in: the argument lists of the f32 siblings
@@ -959,6 +968,25 @@ class SenseVoiceHip:
         if want_logp:
             res["logp"] = cut(logp)
         return res
+
+    def align(self, tokens, max_tokens=None):
+        """pfhip_svs_align: CTC forced alignment of tokens[b] (ids after the four leading tags, e.g. forward()["ids"][b][4:]) against
+        the rows of this thread's last forward().  Returns dict(begin, end, logp: per-utterance arrays over its tokens — rows in
+        tok_frame's numbering, -1 where the utterance is too short for its tokens —, score: [B], -inf for such an utterance)."""
+        toks = [np.ascontiguousarray(t, dtype=np.int32) for t in tokens]
+        B = len(toks)
+        n = np.array([len(t) for t in toks], np.int32)
+        cap = max([int(x) for x in n] + [1]) if max_tokens is None else int(max_tokens)
+        begin = np.full((B, max(cap, 1)), -1, np.int32)
+        end = np.full((B, max(cap, 1)), -1, np.int32)
+        logp = np.full((B, max(cap, 1)), np.nan, np.float32)
+        score = np.full(max(B, 1), np.nan, np.float32)
+        ptrs = (ctypes.c_void_p * max(B, 1))(*[t.ctypes.data for t in toks])
+        i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        out = _SvsAlignOut(begin.ctypes.data_as(i32p), end.ctypes.data_as(i32p), logp.ctypes.data_as(f32p), score.ctypes.data_as(f32p), cap)
+        _check(self._lib, self._lib.pfhip_svs_align(self._h, ptrs, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, ctypes.byref(out)))
+        return dict(begin=[begin[b, :n[b]] for b in range(B)], end=[end[b, :n[b]] for b in range(B)],
+                    logp=[logp[b, :n[b]] for b in range(B)], score=score[:B])
 
     def get_tensor(self, name: str, cap_floats: int) -> np.ndarray:
         buf = np.zeros(max(cap_floats, 1), np.float32)

@@ -269,6 +269,23 @@ __global__ __launch_bounds__(256) void gather_best_kernel(const float* __restric
   if (r < M) best[r] = logp[(size_t)r * ld + ids[r]];
 }
 
+// lse[r] = log sum_c exp(logits[r][c]) of the unfused head's logits, one wave per row (max first, then the sum): what the fused head's
+// merge kernel writes as `lse`, kept for the aligner (ctc_align.hip).  A second pass over the chunk's logits, on the unfused route only.
+__global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ logits, int ld, int M, int V, float* __restrict__ lse) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const float* x = logits + (size_t)row * ld;
+  float m = -INFINITY;
+  for (int c = lane; c < V; c += 64) m = fmaxf(m, x[c]);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  float sum = 0.f;
+  for (int c = lane; c < V; c += 64) sum += x[c] == -INFINITY ? 0.f : expf(x[c] - m);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+  if (lane == 0) lse[row] = m + logf(sum);
+}
+
 }  // namespace
 
 void launch_svs_prompt_rows(const float* E, int D, const int* prompt, const int* row_off, const int* len, int B, float* feats, int ld,
@@ -277,6 +294,10 @@ void launch_svs_prompt_rows(const float* E, int D, const int* prompt, const int*
 }
 void launch_gather_best(const float* logp, int ld, const int32_t* ids, int M, float* best, hipStream_t s) {
   if (M > 0) hipLaunchKernelGGL(gather_best_kernel, dim3((M + 255) / 256), dim3(256), 0, s, logp, ld, ids, M, best);
+}
+
+void launch_row_lse(const float* logits, int ld, int M, int V, float* lse, hipStream_t s) {
+  if (M > 0) hipLaunchKernelGGL(row_lse_kernel, dim3((M + 3) / 4), dim3(256), 0, s, logits, ld, M, V, lse);
 }
 
 size_t ctc_head_workspace_bytes(int M, int V) {

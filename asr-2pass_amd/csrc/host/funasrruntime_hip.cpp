@@ -17,6 +17,8 @@
 #include "sensevoice_hip.h"
 #include "tpass_audio.h"
 
+#include <atomic>
+
 namespace {
 
 struct OfflineStreamHip {
@@ -24,6 +26,7 @@ struct OfflineStreamHip {
   std::unique_ptr<funasr::SenseVoiceSmallHip> svs;      // model type MODEL_SVS (offline-stream.cpp:50-56): `asr` stays unloaded
   std::unique_ptr<funasr::FsmnVadHip> vad;      // complete files only (InferFile): no per-file state, no lock
   std::unique_ptr<funasr::PuncModelHipBase> punc;      // OfflineStream::punc_handle (offline-stream.cpp:105-129)
+  std::atomic<bool> svs_ctc_stamps{false};      // FunOfflineSetCtcStamps: decided per call (a call with a decoder attached aligns nothing)
 };
 
 struct RecogResult {               // funasr::FUNASR_RECOG_RESULT (com-define.h)
@@ -193,10 +196,13 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
                                     const std::vector<std::vector<float>>& hw_emb, int sampling_rate, std::string wav_format,
                                     bool itn, int vad_tail_sil, int vad_max_len, FUNASR_DEC_HANDLE dec_handle, std::string svs_lang,
                                     bool svs_itn) {
-  (void)mode; (void)itn; (void)dec_handle;
+  (void)mode; (void)itn;
   OfflineStreamHip* os = static_cast<OfflineStreamHip*>(handle);
   if (!os || !sz_buf) return nullptr;
   funasr::SenseVoiceSmallHip* svs = os->svs.get();      // funasrruntime.cpp:265-266: the model type routes the Forward call
+  // FunOfflineSetCtcStamps: the spans of the greedy text's tokens.  With a decoder attached the text is a search's, which returns a
+  // string and no ids to align: the stamps stay empty
+  const bool svs_stamps = svs && os->svs_ctc_stamps.load() && !dec_handle;
   if (wav_format != "pcm" && wav_format != "PCM") return nullptr;      // the reference decodes other containers with ffmpeg
   // Audio::LoadPcmwav (audio.cpp:787-819); from here on samples, segments and stamps are at the model's rate (GetTimeLen
   // divides by dest_sample_rate, audio.cpp:254-257).
@@ -245,7 +251,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
     }
   }
   std::vector<std::string> msgs(index_vector.size());
-  std::vector<std::vector<float>> spans(index_vector.size()), conf(index_vector.size());
+  std::vector<std::vector<float>> spans(index_vector.size()), conf(index_vector.size()), svs_ms(index_vector.size());
   res->seg_ids.assign(index_vector.size(), {});
   size_t head = 0, msg_idx = 0;
   std::vector<int> batch;
@@ -269,7 +275,11 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
       const int seg = index_vector[msg_idx];
       msgs[seg] = msg_batch[k];
       res->seg_ids[seg] = svs ? svs->LastTokenIds()[k] : os->asr.LastTokenIds()[k];
-      if (svs) continue;                                          // no stamps; confidences stay with the adapter
+      if (svs) {                                                  // confidences stay with the adapter
+        if (svs_stamps && k == 0) svs->AlignGreedyTokens();       // once per batch, right behind its forward; refused: no stamps
+        if (svs_stamps && k < svs->LastTokenStampsMs().size()) svs_ms[seg] = svs->LastTokenStampsMs()[k];
+        continue;
+      }
       if (k < os->asr.LastTimestamps().size()) spans[seg] = os->asr.LastTimestamps()[k];
       if (k < os->asr.LastTokenConfidence().size()) conf[seg] = os->asr.LastTokenConfidence()[k];
     }
@@ -282,7 +292,11 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
     const float t0 = (float)res->segs[idx].first / (float)model_rate;                  // msg_stimes
     const size_t bar = msgs[idx].find(" | ");
     res->msg += msgs[idx].substr(0, bar);
-    if (bar != std::string::npos) {                 // "<text> | b0, e0,b1, e1": seconds relative to the segment
+    if (svs) {                                      // [begin_ms, end_ms] per text token from the forced alignment, the segment's offset added
+      const int t0_ms = (int)(1000 * t0);
+      for (size_t i = 0; i + 1 < svs_ms[idx].size(); i += 2)
+        cur_stamp += "[" + std::to_string((int)svs_ms[idx][i] + t0_ms) + "," + std::to_string((int)svs_ms[idx][i + 1] + t0_ms) + "],";
+    } else if (bar != std::string::npos) {                 // "<text> | b0, e0,b1, e1": seconds relative to the segment
       std::vector<float> v;
       std::stringstream ss(msgs[idx].substr(bar + 3));
       std::string item;
@@ -323,6 +337,10 @@ const std::vector<std::vector<int>>& FunASRGetSegmentIds(FUNASR_RESULT result) {
 const std::vector<std::pair<int, int>>& FunASRGetSegments(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->segs; }
 const std::vector<int>& FunASRGetOnlineIds(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_ids; }
 void FunOfflineSetNbest(FUNASR_HANDLE handle, int k) { if (handle) static_cast<OfflineStreamHip*>(handle)->asr.SetNbest(k); }
+void FunOfflineSetCtcStamps(FUNASR_HANDLE handle, int on) {
+  OfflineStreamHip* os = static_cast<OfflineStreamHip*>(handle);
+  if (os && os->svs) os->svs_ctc_stamps.store(on != 0);
+}
 void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode) { if (handle) static_cast<OfflineStreamHip*>(handle)->asr.SetCifTimestamps(mode); }
 const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->confidence; }
 const std::vector<float>& FunASRGetOnlineConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_conf; }

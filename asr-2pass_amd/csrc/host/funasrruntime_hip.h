@@ -126,6 +126,18 @@ const std::vector<int>& FunASRGetOnlineFireMs(FUNASR_RESULT result);
 // FunASRGetStamp in its usual "[[b,e],...]" form, one pair per character of the text, VAD segment offsets added; resolution is one
 // LFR row (60 ms), and they are not the head's stamps.  FunTpassSetCifStamps does the same for the offline pass of the 2-pass flow.
 void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode);
+// Time stamps for SenseVoiceSmall by CTC forced alignment (an extension: the reference's SenseVoiceSmall fills no stamps).
+// FunOfflineSetCtcStamps(h, on) switches what SenseVoiceSmallHip::SetCtcTimestamps switches, for every following FunOfflineInferBuffer
+// on the handle (nothing on a Paraformer handle); the switch is kept on the handle and applied call by call — the adapter's
+// AlignGreedyTokens right behind each batch's Forward — so that a call which gets no stamps pays for no alignment.  Off (default) the
+// adapter calls exactly what it always called; on, the tokens of the greedy text are aligned against the CTC rows (pfhip_svs_align) and
+// FunASRGetStamp holds "[[b,e],...]" in ms, one pair per text token (the kept ids behind the four tags), VAD segment offsets added;
+// resolution is one LFR row (60 ms).  A call with a decoder attached (dec_handle != nullptr) gets NO stamps and runs no alignment: a
+// search returns a string, not the ids an alignment needs.  Forward and alignment are two calls: when more threads call the handle
+// than it has execution contexts (PFHIP_INFLIGHT), another thread's forward can take the context in between; the alignment is then
+// refused (never run against foreign rows) and THAT batch's segments come back without stamps — under such load FunASRGetStamp of a
+// SenseVoice result may be empty or lack some segments' pairs.
+void FunOfflineSetCtcStamps(FUNASR_HANDLE handle, int on);
 void FunTpassSetCifStamps(FUNASR_HANDLE tpass_handle, int mode);
 // ... and the C-ABI handle of the offline acoustic model behind a FunOfflineInit handle (pfhip_inflight_stats in the harnesses)
 struct pfhip_model;

@@ -1,6 +1,7 @@
 // SenseVoiceSmallHip: see sensevoice_hip.h.
 #include "sensevoice_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +10,8 @@ namespace funasr {
 namespace {
 thread_local std::vector<std::vector<int>> tl_svs_ids, tl_svs_frames;
 thread_local std::vector<std::vector<float>> tl_svs_conf;
+thread_local std::vector<std::vector<int>> tl_svs_spans;
+thread_local std::vector<std::vector<float>> tl_svs_stamps;
 
 int Knob(const char* name, int dflt) {
   const char* e = std::getenv(name);
@@ -100,6 +103,8 @@ std::vector<std::string> SenseVoiceSmallHip::ForwardAny(const void* const* din, 
   tl_svs_ids.assign(results.size(), {});
   tl_svs_frames.assign(results.size(), {});
   tl_svs_conf.assign(results.size(), {});
+  tl_svs_spans.clear();
+  tl_svs_stamps.clear();
   if (batch_in <= 0 || !handle_) return results;
   const int B = batch_in, V = pfhip_vocab_size(handle_);
   Decoder* decoder = static_cast<Decoder*>(decoder_handle);
@@ -143,11 +148,55 @@ std::vector<std::string> SenseVoiceSmallHip::ForwardAny(const void* const* din, 
     }
     row0 += (size_t)frame_len[b];
   }
+  if (ctc_stamps_ && !decoder) AlignGreedyTokens();
   return results;
+}
+
+bool SenseVoiceSmallHip::AlignGreedyTokens() {                     // the greedy text's tokens: the kept ids behind the four tags
+  std::vector<std::vector<int>> toks(tl_svs_ids.size());
+  for (size_t b = 0; b < toks.size(); ++b)
+    if (tl_svs_ids[b].size() > 4) toks[b].assign(tl_svs_ids[b].begin() + 4, tl_svs_ids[b].end());
+  return AlignTokens(toks);
+}
+
+bool SenseVoiceSmallHip::AlignTokens(const std::vector<std::vector<int>>& ids) {
+  tl_svs_spans.clear();
+  tl_svs_stamps.clear();
+  const int B = (int)ids.size();
+  if (!handle_ || B == 0) return false;
+  int cap = 1;
+  std::vector<const int32_t*> ptr(B);
+  std::vector<int> n(B);
+  for (int b = 0; b < B; ++b) {
+    ptr[b] = ids[b].data(); n[b] = (int)ids[b].size();
+    cap = std::max(cap, n[b]);
+  }
+  std::vector<int32_t> begin((size_t)B * cap), end((size_t)B * cap);
+  std::vector<float> score(B);
+  pfhip_svs_align_out out{};
+  out.tok_begin = begin.data(); out.tok_end = end.data(); out.score = score.data(); out.max_tokens = cap;
+  if (pfhip_svs_align(handle_, ptr.data(), n.data(), B, &out) != PFHIP_OK) {
+    std::fprintf(stderr, "SenseVoiceSmallHip::AlignTokens: %s\n", pfhip_last_error());
+    return false;
+  }
+  const float F = (float)pfhip_lfr_frame_ms(handle_);
+  tl_svs_spans.assign(B, {});
+  tl_svs_stamps.assign(B, {});
+  for (int b = 0; b < B; ++b) {
+    if (!(score[b] > -INFINITY)) continue;                         // fewer rows than the tokens need: no spans for this utterance
+    for (int j = 0; j < n[b]; ++j) {
+      const int tb = begin[(size_t)b * cap + j], te = end[(size_t)b * cap + j];
+      tl_svs_spans[b].push_back(tb); tl_svs_spans[b].push_back(te);
+      tl_svs_stamps[b].push_back((float)(tb - 4) * F); tl_svs_stamps[b].push_back((float)(te - 4) * F);
+    }
+  }
+  return true;
 }
 
 const std::vector<std::vector<int>>& SenseVoiceSmallHip::LastTokenIds() const { return tl_svs_ids; }
 const std::vector<std::vector<int>>& SenseVoiceSmallHip::LastTokenFrames() const { return tl_svs_frames; }
 const std::vector<std::vector<float>>& SenseVoiceSmallHip::LastTokenConfidence() const { return tl_svs_conf; }
+const std::vector<std::vector<int>>& SenseVoiceSmallHip::LastTokenSpans() const { return tl_svs_spans; }
+const std::vector<std::vector<float>>& SenseVoiceSmallHip::LastTokenStampsMs() const { return tl_svs_stamps; }
 
 }  // namespace funasr

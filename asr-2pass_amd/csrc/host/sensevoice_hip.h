@@ -64,6 +64,27 @@ class SenseVoiceSmallHip : public ParaformerHipBase
   const std::vector<std::vector<int>>& LastTokenIds() const;
   const std::vector<std::vector<int>>& LastTokenFrames() const;
   const std::vector<std::vector<float>>& LastTokenConfidence() const;
+  // Token time spans by CTC forced alignment (pfhip_svs_align; an extension: the reference's SenseVoiceSmall returns no stamps).
+  // Off (the default), Forward calls exactly what it always called.  On, a Forward WITHOUT a decoder handle (the text is the greedy
+  // text) aligns the kept ids minus the four leading tags — the tokens of the text — right after the forward; with a decoder handle
+  // nothing is aligned, as the search returns a string and no ids.  ms rule (the project's own): speech row t = row - 4 covers
+  // [t F, (t + 1) F) with F = pfhip_lfr_frame_ms (60 ms), a token's span is [begin_t F, end_t F]; a caller that cut the audio into VAD
+  // segments adds the segment's offset, as for the CIF stamps.  Not virtual, like every method added here.
+  void SetCtcTimestamps(bool on) { ctc_stamps_ = on; }
+  bool GetCtcTimestamps() const { return ctc_stamps_; }
+  // Aligns ids of the caller's own (one list per utterance of the calling thread's last Forward, WITHOUT the four tags: a search
+  // result it has tokenised, a transcript) against that Forward's rows and replaces LastTokenSpans / LastTokenStampsMs; false (and
+  // both emptied) when the device call refuses them — bad ids, or another thread's Forward has taken the execution context since
+  // (possible with more calling threads than PFHIP_INFLIGHT contexts: the result then simply has no spans).
+  bool AlignTokens(const std::vector<std::vector<int>>& ids);
+  // AlignTokens on the text tokens of the calling thread's last Forward (its kept ids behind the four tags): what Forward itself
+  // does when the switch is on, for a caller that decides call by call (FunOfflineInferBuffer)
+  bool AlignGreedyTokens();
+  // of the last Forward (or AlignTokens) of the calling thread, per utterance: begin / end row pairs (rows of the T + 4 sequence like
+  // LastTokenFrames, end exclusive) and [begin_ms, end_ms] pairs, two entries per aligned token; empty while the switch is off, with
+  // a decoder handle, and for an utterance too short for its tokens
+  const std::vector<std::vector<int>>& LastTokenSpans() const;
+  const std::vector<std::vector<float>>& LastTokenStampsMs() const;
   void SetDevice(int device) { device_ = device; }
   pfhip_model* Handle() const { return handle_; }
   // CTCSearch's text step (:348-375) on kept ids; without a vocabulary the ids from the fifth on, space-separated
@@ -77,6 +98,7 @@ class SenseVoiceSmallHip : public ParaformerHipBase
   pfhip_model* handle_ = nullptr;
   HipVocab* vocab = nullptr;
   int asr_sample_rate_ = 16000, device_ = 0, batch_size_ = 1;
+  bool ctc_stamps_ = false;
 };
 
 }  // namespace funasr

@@ -5,6 +5,11 @@
 //                          <arg-max of each row>" — the Start / End / Finalize calls it saw, and the strings Forward returned
 //   svs_infer --handle-api <model_dir> <svs_lang> <svs_itn 0|1> <pcm_s16_file>      FunOfflineInit -> FunOfflineInferBuffer on the
 //                          directory (its name decides the model type); prints "seg <start> <end> : <ids>" and "text [<text>]"
+//   svs_infer --ctc-stamps ...       any of the three with token time spans by CTC forced alignment switched on (SetCtcTimestamps /
+//                          FunOfflineSetCtcStamps): the default form adds "utt <i> spans : <begin end>..." (rows) and "utt <i> stamps :
+//                          <begin_ms end_ms>..." per utterance, --decoder adds "utt <i> stamps <count>" (0: a search returns no ids),
+//                          --handle-api adds "handle stamp [<FunASRGetStamp>]"; --ctc-stamps --with-decoder --handle-api ... also
+//                          passes a decoder handle to FunOfflineInferBuffer (the stamp stays empty).  Without the flag nothing differs.
 // One packed ForwardPcm16 over all files, then Forward on the floats of the first file alone.  Prints per utterance
 // "utt <i> ids : ..." / "utt <i> frames : ..." / "utt <i> text [<text>]", then "alone ids : ..." for the float call.
 #include <cstdio>
@@ -18,6 +23,7 @@
 #include "sensevoice_hip.h"
 
 namespace {
+bool g_ctc_stamps = false, g_with_decoder = false;
 std::string dir_file(const std::string& model, const char* name) {      // <dir of am_model>/<name>, as the factory builds its paths
   const size_t slash = model.rfind('/');
   return (slash == std::string::npos ? std::string() : model.substr(0, slash + 1)) + name;
@@ -60,9 +66,13 @@ static int decoder_mode(int argc, char** argv) {
   std::vector<int> len;
   for (const auto& p : pcm) { ptr.push_back(p.data()); len.push_back((int)p.size()); }
   StubDecoder dec;
+  model.SetCtcTimestamps(g_ctc_stamps);
   for (int finished = 0; finished < 2; ++finished) {
     const std::vector<std::string> text = model.ForwardPcm16(ptr.data(), len.data(), finished != 0, "auto", false, &dec, (int)pcm.size());
     for (size_t i = 0; i < text.size(); ++i) std::printf("finished %d utt %zu text [%s]\n", finished, i, text[i].c_str());
+    if (g_ctc_stamps)
+      for (size_t i = 0; i < text.size(); ++i)
+        std::printf("utt %zu stamps %zu\n", i, i < model.LastTokenStampsMs().size() ? model.LastTokenStampsMs()[i].size() : (size_t)0);
   }
   std::printf("calls starts %d ends %d finals %d searches %d\n", dec.starts, dec.ends, dec.finals, dec.searches);
   return 0;
@@ -75,9 +85,11 @@ static int handle_api(int argc, char** argv) {
   std::ifstream f(argv[5], std::ios::binary);
   const std::vector<char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
   FUNASR_HANDLE h = FunOfflineInit(paths, 1, false, 1);
+  if (g_ctc_stamps) FunOfflineSetCtcStamps(h, 1);
   const std::vector<std::vector<float>> no_hw;
-  FUNASR_RESULT r = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, 16000, "pcm", true, 800, 60000, nullptr,
-                                          argv[3], std::atoi(argv[4]) != 0);
+  StubDecoder dec;
+  FUNASR_RESULT r = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, 16000, "pcm", true, 800, 60000,
+                                          g_with_decoder ? static_cast<FUNASR_DEC_HANDLE>(&dec) : nullptr, argv[3], std::atoi(argv[4]) != 0);
   if (!r) { std::fprintf(stderr, "inference failed\n"); return 1; }
   const auto& segs = FunASRGetSegments(r);
   const auto& ids = FunASRGetSegmentIds(r);
@@ -87,12 +99,18 @@ static int handle_api(int argc, char** argv) {
     std::printf("\n");
   }
   std::printf("handle text [%s]\n", FunASRGetResult(r, 0));
+  if (g_ctc_stamps) std::printf("handle stamp [%s]\n", FunASRGetStamp(r));
   FunASRFreeResult(r);
   FunOfflineUninit(h);
   return 0;
 }
 
 int main(int argc, char** argv) {
+  while (argc > 1 && (std::string(argv[1]) == "--ctc-stamps" || std::string(argv[1]) == "--with-decoder")) {      // leading switches
+    (std::string(argv[1]) == "--ctc-stamps" ? g_ctc_stamps : g_with_decoder) = true;
+    for (int i = 1; i + 1 < argc; ++i) argv[i] = argv[i + 1];
+    --argc;
+  }
   if (argc > 1 && std::string(argv[1]) == "--handle-api") return handle_api(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "--decoder") return decoder_mode(argc, argv);
   if (argc < 6) {
@@ -105,6 +123,7 @@ int main(int argc, char** argv) {
   funasr::SenseVoiceSmallHip model;
   model.SetBatchSize((int)pcm.size());
   model.InitAsr(argv[1], dir_file(argv[1], "am.mvn"), dir_file(argv[1], "config.yaml"), tokens, 1);
+  model.SetCtcTimestamps(g_ctc_stamps);
   std::vector<const int16_t*> ptr;
   std::vector<int> len;
   for (const auto& p : pcm) { ptr.push_back(p.data()); len.push_back((int)p.size()); }
@@ -116,6 +135,13 @@ int main(int argc, char** argv) {
     for (int fr : model.LastTokenFrames()[i]) std::printf(" %d", fr);
     std::printf("\nutt %zu confidence_ok %d\nutt %zu text [%s]\n", i, (int)(model.LastTokenConfidence()[i].size() == model.LastTokenIds()[i].size()), i,
                 text[i].c_str());
+    if (g_ctc_stamps) {
+      std::printf("utt %zu spans :", i);
+      if (i < model.LastTokenSpans().size()) for (int r : model.LastTokenSpans()[i]) std::printf(" %d", r);
+      std::printf("\nutt %zu stamps :", i);
+      if (i < model.LastTokenStampsMs().size()) for (float ms : model.LastTokenStampsMs()[i]) std::printf(" %d", (int)ms);
+      std::printf("\n");
+    }
   }
   std::vector<float> f32(pcm[0].size());
   for (size_t i = 0; i < f32.size(); ++i) f32[i] = (float)pcm[0][i] / 32768.f;

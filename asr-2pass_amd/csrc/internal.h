@@ -267,6 +267,12 @@ struct pfhip_model {
   float* svs_logp_host = nullptr;
   int debug_ctc_unfused = 0, svs_head_chunks = 0, svs_unfused_forwards = 0;
   Buf svs_ws, svs_frame, svs_logits, svs_logp;
+  // pfhip_svs_align: the log-sum-exp of every row of the last forward [M] (either head writes it), whether that forward completed,
+  // and the aligner's own buffers (metadata, emissions, back-pointers, results)
+  Buf svs_lse, al_meta, al_E, al_ws, al_out;
+  PinBuf al_host;
+  bool svs_fwd_ok = false;
+  uint64_t svs_serial = 0;       // counts this context's SenseVoice forwards: a thread's note of its last one is matched on it
   int *m_feat_off = nullptr, *m_prompt = nullptr;
   // device views into meta / dmeta
   int *m_frame_off = nullptr, *m_nframes = nullptr, *m_row_off = nullptr, *m_len = nullptr,

@@ -298,6 +298,8 @@ bool launch_ctc_head(const float* X, int ldx, const float* W, int ldw, const flo
 void launch_svs_prompt_rows(const float* E, int D, const int* prompt, const int* row_off, const int* len, int B, float* feats, int ld,
                             hipStream_t s);
 void launch_gather_best(const float* logp, int ld, const int32_t* ids, int M, float* best, hipStream_t s);
+// lse[r] = log-sum-exp of logits[r][0 .. V): what the unfused head keeps where the fused one's merge kernel writes `lse`
+void launch_row_lse(const float* logits, int ld, int M, int V, float* lse, hipStream_t s);
 // CTC collapse per utterance b over frames [row_off[b], row_off[b] + len[b]) (device arrays): a frame is kept when its id is not
 // `blank` and differs from the previous frame's.  ids / tok_frame / tok_logp [B][max_tokens] (the two last may be null): the kept
 // id, its 0-based frame inside the utterance and a copy of frame_logp there; token_num[b] = the number kept, also beyond max_tokens
@@ -305,6 +307,23 @@ void launch_gather_best(const float* logp, int ld, const int32_t* ids, int M, fl
 int ctc_collapse_chunk();
 bool launch_ctc_collapse(const int32_t* frame_ids, const float* frame_logp, const int* row_off, const int* len, int B, int blank,
                          int max_tokens, int32_t* ids, int32_t* tok_frame, float* tok_logp, int32_t* token_num, hipStream_t s);
+// ---- CTC forced alignment (ctc_align.hip) ---------------------------------------------------------------------------------------
+// Emissions of the labels asked for: utterance b owns rows [row_off[b], + len[b]) of X and labels[lab_off[b] .. + n_lab[b]) (device
+// arrays); E + e_off[b] is E_b [len[b]][n_lab[b] + 1] = x_t . W[id_j] + bias[id_j] - lse[row], column 0 the blank, column j label j.
+// fp32 FMA.  K % 32 == 0, row strides % 4 == 0.  Rows are clamped to the utterance, label ids to 0 .. V - 1.  false: nothing launched.
+bool launch_ctc_emissions(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* lse, const int* row_off,
+                          const int* len, const int* lab_off, const int* n_lab, const int32_t* labels, const long long* e_off, int B, int K,
+                          int V, int blank, float* E, hipStream_t s);
+// Viterbi over the CTC trellis of each utterance and the token spans (include/pfhip_ops.h states the recurrence).  e_floats: the floats
+// of E; workspace: ctc_align_workspace_bytes(e_floats) bytes of back-pointers.  tok_begin / tok_end / tok_logp [B][max_tokens] (tok_logp
+// may be null), score [B].  false (nothing launched) for max_tokens above ctc_align_max_tokens() (the two score rows of 2 L + 1 states
+// must fit 64 KB of LDS), a short workspace or a null buffer.  An utterance whose n_lab exceeds max_tokens or whose E_b leaves E is
+// answered as infeasible.
+size_t ctc_align_workspace_bytes(size_t e_floats);
+int ctc_align_max_tokens();
+bool launch_ctc_align(const float* E, const long long* e_off, size_t e_floats, const int* len, const int* n_lab, const int32_t* labels,
+                      const int* lab_off, int B, int max_tokens, int32_t* tok_begin, int32_t* tok_end, float* tok_logp, float* score,
+                      void* workspace, size_t workspace_bytes, hipStream_t s);
 // The same head with the k best columns of every row (topk.hip; 1 <= k <= kTopkMax <= V): topk_ids / topk_logp [ML][k], larger logit
 // first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry of its column bit for bit.  The
 // log-sum-exp is formed with logp null as well.  false (nothing launched) when the arguments are outside that.

@@ -364,6 +364,23 @@ int pfhip_op_ctc_collapse(const int32_t* frame_ids, const float* frame_logp, con
   return done();
 }
 int pfhip_op_ctc_collapse_chunk(void) { return pfhip::ctc_collapse_chunk(); }
+int pfhip_op_ctc_emissions(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* lse, const int* row_off,
+                           const int* len, const int* lab_off, const int* n_lab, const int32_t* labels, const long long* e_off, int B,
+                           int K, int V, int blank, float* E, void* stream) {
+  if (!pfhip::launch_ctc_emissions(X, ldx, W, ldw, bias, lse, row_off, len, lab_off, n_lab, labels, e_off, B, K, V, blank, E, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+size_t pfhip_op_ctc_align_workspace_bytes(size_t e_floats) { return pfhip::ctc_align_workspace_bytes(e_floats); }
+int pfhip_op_ctc_align_max_tokens(void) { return pfhip::ctc_align_max_tokens(); }
+int pfhip_op_ctc_align(const float* E, const long long* e_off, size_t e_floats, const int* len, const int* n_lab, const int32_t* labels,
+                       const int* lab_off, int B, int max_tokens, int32_t* tok_begin, int32_t* tok_end, float* tok_logp, float* score,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (!pfhip::launch_ctc_align(E, e_off, e_floats, len, n_lab, labels, lab_off, B, max_tokens, tok_begin, tok_end, tok_logp, score, workspace,
+                               workspace_bytes, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
 
 // ---- the scan, cache and row kernels (tests only: the descriptor-taking ones upload their descriptors synchronously) ----------------
 static int cif_stream_op(const float* enc, int lde, const float* alphas, const int* row_off, const int* n, const int* is_last,

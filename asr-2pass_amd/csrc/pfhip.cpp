@@ -989,6 +989,7 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
   int32_t *d_ids = dn + B, *d_frames = dn + B + bt, *d_fid = dn + B + 3 * bt;
   float *d_logp = reinterpret_cast<float*>(dn + B + 2 * bt), *d_flp = reinterpret_cast<float*>(d_fid + M);
   const float* X = m->x.f();
+  HIP_TRY(m->svs_lse.ensure((size_t)M * 4));                   // the rows' log-sum-exp, kept for pfhip_svs_align
   const bool unfused = pfhip::launch_ctx().exact || m->debug_ctc_unfused || m->svs_logp_host;
   m->debug_ctc_unfused = 0;
   m->svs_head_chunks = 0;
@@ -1004,6 +1005,7 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
         Scope sc(m, s, K_HEAD, 0, 12.0 * rows * V);
         pfhip::launch_logsoftmax_argmax(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_logp.f(), d_fid + r0, s, m->d_range_flag);
         pfhip::launch_gather_best(m->svs_logp.f(), V, d_fid + r0, rows, d_flp + r0, s);
+        pfhip::launch_row_lse(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_lse.f() + r0, s);
       }
       if (m->svs_logp_host)
         HIP_TRY(hipMemcpyAsync(m->svs_logp_host + (size_t)r0 * V, m->svs_logp.p, (size_t)rows * V * 4, hipMemcpyDeviceToHost, s));
@@ -1013,7 +1015,7 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
     const size_t ws = pfhip::ctc_head_workspace_bytes(M, V);
     HIP_TRY(m->svs_ws.ensure(ws));
     Scope sc(m, s, K_GEMM, 2.0 * M * (double)V * d, 4.0 * ((double)M * d + (double)V * d) + 12.0 * M * (w.vocab_pad / pfhip::kTileN));
-    if (!pfhip::launch_ctc_head(X, d, w.ctc.w, d, w.ctc.b, w.ctc.scale, M, V, d, d_fid, d_flp, nullptr, m->svs_ws.p, ws, s, m->d_range_flag))
+    if (!pfhip::launch_ctc_head(X, d, w.ctc.w, d, w.ctc.b, w.ctc.scale, M, V, d, d_fid, d_flp, m->svs_lse.f(), m->svs_ws.p, ws, s, m->d_range_flag))
       return fail(PFHIP_ERR_UNSUPPORTED, "CTC head: d_model must be a multiple of 32");
   }
   {
@@ -2187,6 +2189,12 @@ static void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all
 }
 
 namespace { thread_local pfhip_model* tl_last_replica = nullptr; }      // where this thread's last offline forward ran (debug getters)
+// pfhip_svs_align: per handle (its uid), where this thread's last pfhip_svs_forward on it ran — the context's uid and that context's
+// forward count then.  Handles come and go; the note is emptied when it has grown past 64 handles.
+namespace {
+struct SvsNote { uint64_t ctx_uid, serial; };
+thread_local std::map<uint64_t, SvsNote> tl_svs_notes;
+}
 
 // Callers of both sample formats share the queue; a packed forward holds ONE format, the leader's: pick takes the queued callers of
 // that format (in order) and leaves the others, in order, for the next leader.  Nothing is converted on the host, every caller gets
@@ -2695,6 +2703,8 @@ static pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n
   m->prof_stream = s;
   const int V = m->weights->cfg.vocab;
   m->nbest_k = 0; m->want_fires = false;
+  m->svs_fwd_ok = false;
+  ++m->svs_serial;
   m->svs_prompt.resize((size_t)4 * batch);
   for (int b = 0; b < batch; ++b) {      // sensevoice-small.cpp:607-640: language, then the two fixed rows 1 and 2, then text normalisation
     m->svs_prompt[4 * b] = lid[b]; m->svs_prompt[4 * b + 1] = 1; m->svs_prompt[4 * b + 2] = 2; m->svs_prompt[4 * b + 3] = textnorm[b];
@@ -2721,6 +2731,11 @@ static pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n
   }
   m->svs_logp_host = nullptr;
   if (st) return st;
+  m->svs_fwd_ok = true;                          // the rows and their log-sum-exp are what pfhip_svs_align reads ...
+  {                                              // ... for this thread, until this context runs another forward
+    if (tl_svs_notes.size() > 64) tl_svs_notes.clear();
+    tl_svs_notes[(m->group_head ? m->group_head : m)->uid] = SvsNote{m->uid, ++m->svs_serial};
+  }
   for (int b = 0; b < batch; ++b) {
     if (out->token_num) out->token_num[b] = m->M ? m->token_num[b] : 0;
     if (out->frame_len) out->frame_len[b] = m->T[b];
@@ -2764,6 +2779,97 @@ pfhip_status pfhip_svs_forward(pfhip_model* m, const float* const* pcm, const in
 pfhip_status pfhip_svs_forward_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                    const int32_t* textnorm, pfhip_svs_out* out) {
   return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out);
+}
+
+// CTC forced alignment of caller-given tokens against the rows of the calling thread's last pfhip_svs_forward (ctc_align.hip): the
+// emissions of blank | tokens[b] from the kept encoder rows and their log-sum-exp, the Viterbi pass, one copy back, one sync.
+pfhip_status pfhip_svs_align(pfhip_model* head, const int32_t* const* tokens, const int* n_tokens, int batch, pfhip_svs_align_out* out) {
+  g_err.clear();
+  if (!head || !tokens || !n_tokens || batch <= 0 || !out || !out->tok_begin || !out->tok_end) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!is_svs(head)) return fail(PFHIP_ERR_UNSUPPORTED, "not a SenseVoice (CTC) model: there are no CTC rows to align against");
+  // the context this thread's last forward ran on, looked up among this handle's own (matched on the uid: never a stale address)
+  pfhip_model* m = nullptr;
+  const auto note = tl_svs_notes.find(head->uid);
+  if (note != tl_svs_notes.end()) {
+    if (head->uid == note->second.ctx_uid) m = head;
+    for (pfhip_model* cx : head->contexts)
+      if (cx->uid == note->second.ctx_uid) m = cx;
+  }
+  if (!m) return fail(PFHIP_ERR_ARG, "this thread has run no pfhip_svs_forward on this handle");
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!m->svs_fwd_ok || m->svs_serial != note->second.serial)
+    return fail(PFHIP_ERR_ARG, "the rows of this thread's last pfhip_svs_forward are gone: its execution context has run another forward since");
+  if (batch != m->B) return fail(PFHIP_ERR_ARG, "batch differs from that of the last pfhip_svs_forward");
+  const ModelWeights& w = *m->weights;
+  const Config& c = w.cfg;
+  const int V = c.vocab, d = c.d_model, B = batch;
+  int longest = 0;
+  size_t n_labels = 0;
+  for (int b = 0; b < B; ++b) {
+    if (n_tokens[b] < 0 || (n_tokens[b] > 0 && !tokens[b])) return fail(PFHIP_ERR_ARG, "bad token list");
+    for (int j = 0; j < n_tokens[b]; ++j)
+      if (tokens[b][j] < 0 || tokens[b][j] >= V || tokens[b][j] == c.blank_id)
+        return fail(PFHIP_ERR_ARG, "a token outside 0 .. vocab - 1, or the blank");
+    longest = std::max(longest, n_tokens[b]);
+    n_labels += (size_t)n_tokens[b];
+  }
+  if (out->max_tokens < longest) return fail(PFHIP_ERR_CAPACITY, "max_tokens smaller than the longest token list");
+  if (longest > pfhip::ctc_align_max_tokens()) return fail(PFHIP_ERR_UNSUPPORTED, "more tokens than the trellis kernel's LDS rows hold");
+  const int maxL = std::max(longest, 1);
+  // host metadata: row_off, len, lab_off, n_lab [B] | labels | e_off [B] (int64, 8-byte aligned)
+  const size_t n_i32 = (4 * (size_t)B + std::max<size_t>(n_labels, 1) + 1) & ~(size_t)1;
+  HIP_TRY(hipSetDevice(m->device));
+  HIP_TRY(m->al_host.ensure(n_i32 * 4 + (size_t)B * 8));
+  HIP_TRY(m->al_meta.ensure(n_i32 * 4 + (size_t)B * 8));
+  int* hm = m->al_host.i();
+  long long* h_eoff = reinterpret_cast<long long*>(hm + n_i32);
+  size_t e_floats = 0, lo = 0;
+  for (int b = 0; b < B; ++b) {
+    const int N = m->T[b] > 4 ? m->T[b] - 4 : 0;                     // the speech rows: the four prompt rows are no CTC rows
+    hm[b] = m->row_off[b] + 4; hm[B + b] = N; hm[2 * B + b] = (int)lo; hm[3 * B + b] = n_tokens[b];
+    for (int j = 0; j < n_tokens[b]; ++j) hm[4 * B + lo + j] = tokens[b][j];
+    lo += (size_t)n_tokens[b];
+    h_eoff[b] = (long long)e_floats;
+    e_floats += (size_t)N * (n_tokens[b] + 1);
+  }
+  hipStream_t s = m->own_stream;
+  int* dm = m->al_meta.i();
+  const long long* d_eoff = reinterpret_cast<const long long*>(dm + n_i32);
+  const size_t bt = (size_t)B * maxL, n_out = 3 * bt + B;
+  const size_t ws = pfhip::ctc_align_workspace_bytes(e_floats);
+  HIP_TRY(m->al_E.ensure(std::max<size_t>(e_floats, 1) * 4));
+  HIP_TRY(m->al_ws.ensure(std::max<size_t>(ws, 1)));
+  HIP_TRY(m->al_out.ensure(n_out * 4));
+  std::vector<int32_t> res(n_out);
+  HIP_TRY(hipMemcpyAsync(dm, hm, n_i32 * 4 + (size_t)B * 8, hipMemcpyHostToDevice, s));
+  int32_t *d_begin = m->al_out.i(), *d_end = d_begin + bt;
+  float *d_logp = reinterpret_cast<float*>(d_end + bt), *d_score = d_logp + bt;
+  // (no profiling Scope: pfhip_profile_read stays the forward's own time)
+  if (m->M > 0) {
+    if (!pfhip::launch_ctc_emissions(m->x.f(), d, w.ctc.w, d, w.ctc.b, m->svs_lse.f(), dm, dm + B, dm + 2 * B, dm + 3 * B, dm + 4 * B, d_eoff, B,
+                                     d, V, c.blank_id, m->al_E.f(), s))
+      return fail(PFHIP_ERR_UNSUPPORTED, "CTC emissions: d_model must be a multiple of 32");
+  }
+  {
+    if (!pfhip::launch_ctc_align(m->al_E.f(), d_eoff, e_floats, dm + B, dm + 3 * B, dm + 4 * B, dm + 2 * B, B, maxL, d_begin, d_end, d_logp,
+                                 d_score, m->al_ws.p, ws, s))
+      return fail(PFHIP_ERR_ARG, "CTC alignment refused its arguments");
+  }
+  HIP_TRY(hipMemcpyAsync(res.data(), m->al_out.p, n_out * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  const float* r_logp = reinterpret_cast<const float*>(res.data() + 2 * bt);
+  for (int b = 0; b < B; ++b) {
+    const size_t dst = (size_t)b * out->max_tokens, src = (size_t)b * maxL;
+    for (int j = 0; j < n_tokens[b]; ++j) {        // tok_frame's numbering: the prompt rows counted
+      const int32_t tb = res[src + j], te = res[bt + src + j];
+      out->tok_begin[dst + j] = tb < 0 ? -1 : tb + 4;
+      out->tok_end[dst + j] = te < 0 ? -1 : te + 4;
+      if (out->tok_logp) out->tok_logp[dst + j] = r_logp[src + j];
+    }
+    if (out->score) out->score[b] = r_logp[bt + b];
+  }
+  return PFHIP_OK;
 }
 
 // One synthetic batch through every execution slot: the code objects are loaded, each context's workspace is sized for
@@ -2885,7 +2991,8 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   const int d = m->weights->cfg.d_model;
   if (nm == "feats") { src = m->feats.p; n = (size_t)m->M * m->weights->feat_dim; }
   else if (nm == "enc") { src = m->weights->cfg.svs ? m->x.p : m->enc.p; n = (size_t)m->M * d; }      // SenseVoice: the rows after tp.norm
-  else if (m->weights->cfg.svs) return fail(PFHIP_ERR_ARG, "a SenseVoice model has the tensors feats and enc, not " + nm);
+  else if (nm == "lse" && m->weights->cfg.svs) { src = m->svs_lse.p; n = (size_t)m->M; }             // the rows' log-sum-exp either CTC head kept
+  else if (m->weights->cfg.svs) return fail(PFHIP_ERR_ARG, "a SenseVoice model has the tensors feats, enc and lse, not " + nm);
   else if (nm == "alphas") { src = m->alphas.p; n = (size_t)m->M; }
   else if (nm == "emb") { src = m->emb.p; n = (size_t)m->ML * d; }
   else if (nm == "ts_up" && m->have_ts) { src = m->ts_up.p; n = (size_t)3 * m->M * d; }            // timestamp-head stages

@@ -44,6 +44,12 @@ def _lib():
             lib.pfhip_op_ctc_head_workspace_bytes.argtypes = [_ci, _ci]
             lib.pfhip_op_ctc_head.argtypes = [_vp, _ci, _vp, _ci, _vp, _cf, _ci, _ci, _ci, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
             lib.pfhip_op_ctc_collapse.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
+        if hasattr(lib, "pfhip_op_ctc_align"):
+            lib.pfhip_op_ctc_emissions.argtypes = [_vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
+            lib.pfhip_op_ctc_align_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_ctc_align_workspace_bytes.argtypes = [ctypes.c_size_t]
+            lib.pfhip_op_ctc_align.argtypes = [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp,
+                                               ctypes.c_size_t, _vp]
         _bound = True
     return lib
 
@@ -436,6 +442,69 @@ def ctc_collapse(frame_ids, frame_logp, row_off, length, max_tokens, blank=0, fi
     _ck(_lib().pfhip_op_ctc_collapse(_p(frame_ids), _p(frame_logp), _p(row_off), _p(length), B, int(blank), int(max_tokens), _p(ids),
                                      _p(tok_frame), _p(tok_logp), _p(token_num), _stream()), "ctc_collapse")
     return ids, tok_frame, tok_logp, token_num
+
+
+class CtcLabels:
+    """The labels of a batch as the alignment kernels take them: per-utterance label lists and frame counts on the host, and their
+    device arrays (labels packed, lab_off, n_lab, len int32; e_off int64 = the prefix sums of len * (n_lab + 1))."""
+
+    def __init__(self, labels, length, device="cuda"):
+        self.lists = [[int(x) for x in y] for y in labels]
+        self.length = [int(n) for n in length]
+        assert len(self.lists) == len(self.length)
+        self.B = len(self.lists)
+        self.n = [len(y) for y in self.lists]
+        self.lab_off_h = [sum(self.n[:b]) for b in range(self.B)]
+        sizes = [self.length[b] * (self.n[b] + 1) for b in range(self.B)]
+        self.e_off_h = [sum(sizes[:b]) for b in range(self.B)]
+        self.e_floats = sum(sizes)
+        i32 = lambda v: torch.tensor(list(v) or [0], dtype=torch.int32, device=device)
+        self.labels = i32([x for y in self.lists for x in y])
+        self.lab_off, self.n_lab, self.len = i32(self.lab_off_h), i32(self.n), i32(self.length)
+        self.e_off = torch.tensor(self.e_off_h or [0], dtype=torch.int64, device=device)
+
+    def cut(self, E, b):
+        """E_b [len, n_lab + 1] of a packed E (a host array or a tensor)."""
+        o, N, C = self.e_off_h[b], self.length[b], self.n[b] + 1
+        return E[o:o + N * C].reshape(N, C)
+
+
+def ctc_emissions(X, W, bias, lse, row_off, lab, blank=0, V=None, E=None, e_base=0):
+    """The emissions of the labels asked for (csrc/ctc_align.hip): packed E (float32, lab.e_floats) of X rows row_off[b] .. + lab.len[b]
+    against W rows blank | lab.lists[b], minus lse per row.  row_off: a device int32 tensor.  E / e_base: write into a caller's buffer
+    e_base floats in (tests put sentinels around it)."""
+    V = W.shape[0] if V is None else V
+    if E is None:
+        E = torch.empty(max(lab.e_floats, 1), dtype=torch.float32, device=X.device)
+    e_off = lab.e_off + int(e_base)
+    _ck(_lib().pfhip_op_ctc_emissions(_p(X), X.stride(0), _p(W), W.stride(0), _p(bias), _p(lse), _p(row_off), _p(lab.len), _p(lab.lab_off),
+                                      _p(lab.n_lab), _p(lab.labels), _p(e_off), lab.B, X.shape[1], V, int(blank), _p(E), _stream()),
+        "ctc_emissions")
+    return E
+
+
+def ctc_align_workspace_bytes(e_floats):
+    return int(_lib().pfhip_op_ctc_align_workspace_bytes(int(e_floats)))
+
+
+def ctc_align(E, lab, max_tokens=None, want_logp=True, workspace_bytes=None):
+    """Viterbi over the CTC trellis and the token spans (csrc/ctc_align.hip; include/pfhip_ops.h states the recurrence):
+    (tok_begin, tok_end [B, max_tokens] int32, tok_logp [B, max_tokens] or None, score [B]).  An n_lab above max_tokens is refused here,
+    before the launch (PfhipError), as the labels are the host's."""
+    lib = _lib()
+    max_tokens = max(lab.n + [0]) if max_tokens is None else int(max_tokens)
+    if any(n > max_tokens for n in lab.n):
+        raise PfhipError("ctc_align: an utterance has more labels than max_tokens")
+    dev = lab.len.device
+    tok_begin = torch.full((lab.B, max(max_tokens, 1)), -7, dtype=torch.int32, device=dev)
+    tok_end = torch.full((lab.B, max(max_tokens, 1)), -7, dtype=torch.int32, device=dev)
+    tok_logp = torch.full((lab.B, max(max_tokens, 1)), float("nan"), dtype=torch.float32, device=dev) if want_logp else None
+    score = torch.full((max(lab.B, 1),), float("nan"), dtype=torch.float32, device=dev)
+    nbytes = ctc_align_workspace_bytes(lab.e_floats) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _ck(lib.pfhip_op_ctc_align(_p(E), _p(lab.e_off), lab.e_floats, _p(lab.len), _p(lab.n_lab), _p(lab.labels), _p(lab.lab_off), lab.B,
+                               max_tokens, _p(tok_begin), _p(tok_end), _p(tok_logp), _p(score), _p(ws), nbytes, _stream()), "ctc_align")
+    return tok_begin[:, :max_tokens], tok_end[:, :max_tokens], None if tok_logp is None else tok_logp[:, :max_tokens], score[:lab.B]
 
 
 # ---- pre-split operands (csrc/gemm_p3.hip) ------------------------------------------------------------------------------------

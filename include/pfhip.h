@@ -669,13 +669,33 @@ pfhip_status pfhip_svs_forward(pfhip_model* m, const float* const* pcm, const in
                                const int32_t* textnorm, pfhip_svs_out* out);
 pfhip_status pfhip_svs_forward_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                    const int32_t* textnorm, pfhip_svs_out* out);
+/* CTC forced alignment: where each token of a given sequence begins and ends (upstream FunASR's output_timestamp for SenseVoice,
+ * recalled; nothing of it is in the reference tree).  tokens[b][0 .. n_tokens[b]) is aligned against the rows that the CALLING
+ * THREAD's last pfhip_svs_forward[_s16] on this handle left in its execution context — the lifetime rule of pfhip_get_tensor: valid
+ * until that context runs its next forward (a later forward of ANOTHER thread that landed on the same context included: the call then
+ * returns PFHIP_ERR_ARG instead of aligning against rows that are not the caller's, and the caller goes without spans or repeats
+ * the pair) — so `batch` must equal that forward's.  The frames are the speech rows only (the four
+ * prompt rows are no CTC rows), so tokens[b] are ids AFTER the four leading tags: ids[b][4:] of the forward for the greedy text, or
+ * any other sequence (a search result, a transcript the caller has).  The blank is the container's blank_id.  Emissions are
+ * x . ctc.w[id] + ctc.b[id] - log-sum-exp of the row, formed for the blank and the tokens asked for only (pfhip_op_ctc_emissions);
+ * the path is the Viterbi optimum of pfhip_op_ctc_align, whose comment states the recurrence and the tie rule.
+ * tok_begin / tok_end [batch][max_tokens]: the first row of token j on that path and one past its last, in tok_frame's numbering
+ * (rows of the utterance with the prompt rows counted, so >= 4); tok_logp (may be NULL): the token's emission at tok_begin;
+ * score [batch] (may be NULL): the path's log-probability.  An utterance too short for its tokens (rows < tokens + equal neighbours;
+ * an utterance of fewer than 400 samples has no rows) has score -inf and -1 in every span; the others are served.
+ * PFHIP_ERR_ARG, before any launch: a token outside 0 .. vocab - 1 or equal to the blank, a negative count, a batch mismatch, no
+ * previous forward of this thread on this handle.  PFHIP_ERR_UNSUPPORTED: a Paraformer handle.  PFHIP_ERR_CAPACITY: max_tokens below
+ * the longest n_tokens.  The forward itself is unchanged by this: it only keeps the row log-sum-exp both heads form anyway. */
+typedef struct pfhip_svs_align_out { int32_t* tok_begin; int32_t* tok_end; float* tok_logp; float* score; int max_tokens; } pfhip_svs_align_out;
+pfhip_status pfhip_svs_align(pfhip_model* m, const int32_t* const* tokens, const int* n_tokens, int batch, pfhip_svs_align_out* out);
 
 /* ---- inspection (parity tests) -----------------------------------------------------------------
  * Copies a named intermediate of the LAST forward to host: "feats" [M,560], "enc" [M,d],
  * "alphas" [M] (without the tail slot), "emb" [sum fires, d], "logp" [sum fires, vocab],
  * "fire_frame" [sum fires] (the fire frames of a forward that recorded them, as floats: the values are small integers).
  * Rows are utterance-major in batch order.  *n_out = floats written.  A SenseVoice handle has "feats" [M,560] (prompt rows
- * included, M = sum of T + 4) and "enc" [M,d] (the rows after tp.norm, which the CTC head reads). */
+ * included, M = sum of T + 4), "enc" [M,d] (the rows after tp.norm, which the CTC head reads) and "lse" [M] (the log-sum-exp of
+ * every row's logits as the CTC head that ran kept it: what pfhip_svs_align subtracts). */
 pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size_t cap_floats,
                               size_t* n_out);
 

@@ -161,6 +161,37 @@ int pfhip_op_ctc_collapse(const int32_t* frame_ids, const float* frame_logp, con
                           int max_tokens, int32_t* ids, int32_t* tok_frame, float* tok_logp, int32_t* token_num, void* stream);
 /* The number of frames one trip of the collapse kernel's scan covers (tests place lengths on both sides of it). */
 int pfhip_op_ctc_collapse_chunk(void);
+/* CTC forced alignment (ctc_align.hip), step 1: the emissions of the labels asked for, without the logits matrix.  Utterance b owns
+ * rows [row_off[b], row_off[b] + len[b]) of X [., K] and the labels labels[lab_off[b] .. + n_lab[b]) (DEVICE arrays; e_off is int64).
+ * E + e_off[b] is E_b [len[b]][n_lab[b] + 1], packed: E_b[t][j] = x_t . W[id_j] + bias[id_j] - lse[row_off[b] + t], where column 0 is
+ * the blank (id `blank`) and column j is label j (1-based; the same id may occur in several columns).  The caller computes e_off (the
+ * prefix sums of len * (n_lab + 1)) and the E_b must not overlap.  fp32 FMA arithmetic.  K % 32 == 0 and row strides % 4 == 0 as
+ * pfhip_op_ctc_head; W [V, K] has exactly V rows.  Nothing outside X's rows of the utterance, W, bias or E_b is read or written: rows
+ * are clamped to the utterance and a label outside 0 .. V - 1 is CLAMPED into it here (the model-level call refuses such a label on
+ * the host).  hipErrorInvalidValue, before anything is launched, for any other shape, a blank outside 0 .. V - 1 or a NULL buffer. */
+int pfhip_op_ctc_emissions(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* lse, const int* row_off,
+                           const int* len, const int* lab_off, const int* n_lab, const int32_t* labels, const long long* e_off, int B,
+                           int K, int V, int blank, float* E, void* stream);
+/* Step 2: the best path through the CTC trellis of each utterance and the spans of its labels.  E / e_off / len / n_lab / labels /
+ * lab_off as above (the label ids only decide which neighbours are the same label); e_floats = the floats of E.
+ *   N = len[b] frames, labels y_1 .. y_L, states s = 0 .. 2 L: s even is the blank (column 0), s odd is label (s + 1) / 2.
+ *   v_0[0] = E[0][0], v_0[1] = E[0][1] (L >= 1), every other state -inf.  For t >= 1: m = the largest of v_{t-1}[s], v_{t-1}[s-1]
+ *   (s >= 1) and v_{t-1}[s-2] (s odd, s >= 3 and y_{(s+1)/2} != y_{(s-1)/2}), a later candidate replacing the running best only when
+ *   strictly greater (stay, then 1, then 2); v_t[s] = m + E[t][column of s], one fp32 add.
+ *   End state 2 L if v_{N-1}[2 L] >= v_{N-1}[2 L - 1], else 2 L - 1 (L = 0: state 0); score[b] = that value.  N = 0: score 0 for
+ *   L = 0.  score -inf <=> infeasible (N < L + the number of equal neighbours; N = 0 with L > 0): every span of the utterance is
+ *   -1 and the other utterances are served.  -inf emissions are legal.
+ * tok_begin / tok_end / tok_logp [B][max_tokens] (tok_logp may be NULL): the first frame of the path in label j's state, one past the
+ * last, and E[tok_begin][j + 1]; slots from n_lab[b] on hold -1 / -1 / -inf.  workspace: pfhip_op_ctc_align_workspace_bytes(e_floats)
+ * bytes of device memory (one back-pointer byte per frame and state).  hipErrorInvalidValue, before anything is launched, for
+ * max_tokens above pfhip_op_ctc_align_max_tokens() (the two score rows of 2 L + 1 states live in 64 KB of LDS: 4095), a short
+ * workspace or a NULL buffer.  n_lab is device data: the caller, who wrote the labels, checks n_lab[b] <= max_tokens (ops.ctc_align
+ * and pfhip_svs_align do, before the launch); the kernel answers an utterance that breaks it, or whose E_b leaves E, as infeasible. */
+size_t pfhip_op_ctc_align_workspace_bytes(size_t e_floats);
+int pfhip_op_ctc_align_max_tokens(void);
+int pfhip_op_ctc_align(const float* E, const long long* e_off, size_t e_floats, const int* len, const int* n_lab, const int32_t* labels,
+                       const int* lab_off, int B, int max_tokens, int32_t* tok_begin, int32_t* tok_end, float* tok_logp, float* score,
+                       void* workspace, size_t workspace_bytes, void* stream);
 /* One streaming window (M <= 32 rows): LayerNormalization (g != NULL; width D <= K) -> MatMul/Gemm (+bias, +residual Adds, Relu)
  * (+ the SAN-M FSMN memory of fsmn_v over the M rows, k = 11) in ONE launch — stream_fused.hip. */
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
