@@ -1,4 +1,4 @@
-// Bookkeeping of the per-device hotword bank (pfhip.cpp): which hotword sets have their bias-decoder K/V rows resident in the
+// Bookkeeping of the per-device hotword bank (hotwords.cpp): which hotword sets have their bias-decoder K/V rows resident in the
 // device arena, where, and which of them may be overwritten.  Host code only — no HIP — so it is tested without a GPU
 // (host/hotword_bank_selftest.cpp).  The arena is a row-addressed array of `granule`-row granules; a set of H rows owns a
 // contiguous run of ceil(H / granule) granules (its slab), so a projection GEMM that pads its M to the granule writes only rows

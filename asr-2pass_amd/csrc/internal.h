@@ -1,4 +1,4 @@
-// Internal definitions shared by pfhip.cpp (offline forward) and stream.cpp (chunk-streaming forward).
+// Internal definitions shared by the offline path (pfhip.cpp and the files behind offline.h) and stream.cpp (chunk-streaming forward).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -106,7 +106,7 @@ struct PinBuf {
   int* i() const { return static_cast<int*>(p); }
 };
 
-pfhip_status build_frontend_tables(int n_mels, int sample_rate, FrontendTables* ft);   // pfhip.cpp
+pfhip_status build_frontend_tables(int n_mels, int sample_rate, FrontendTables* ft);   // model_build.cpp
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -193,14 +193,14 @@ struct pfhip_model {
   const uint64_t uid = pfhip_impl::next_model_uid();
   int device = 0;
   hipStream_t own_stream = nullptr;
-  // decoder K/V projections of a large batch run beside the (under-filled) token-side launches: pfhip.cpp enqueue_locked
+  // decoder K/V projections of a large batch run beside the (under-filled) token-side launches: forward.cpp enqueue_locked
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_enc_ready = nullptr;
   std::vector<hipEvent_t> ev_kv;
   std::mutex mu;
   // everything that is read-only after load, shared by the weight owner and its contexts (weights.h); the last of them frees it
   std::shared_ptr<const ModelWeights> weights;
-  // guard of the fp16 two-plane domain (pfhip.cpp fetch_locked): the forward's flag word (inside `meta`, cleared by the metadata
+  // guard of the fp16 two-plane domain (heads.cpp fetch_locked): the forward's flag word (inside `meta`, cleared by the metadata
   // upload), its pinned host mirror, what a re-run on the exact kernels needs, and the count of such re-runs
   int* d_range_flag = nullptr;
   PinBuf h_flag;

@@ -1,0 +1,89 @@
+// What the files of the offline path name across a file boundary: declarations and small shared structs, no data.
+#pragma once
+#include "internal.h"
+
+namespace pfhip_impl {
+
+// ---- model_build.cpp ----
+pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manifest_json, int device,
+                         pfhip_model** out);
+pfhip_status build_context(pfhip_model* owner, pfhip_model** out);
+pfhip_status read_file(const char* path, std::vector<char>& out);
+
+// ---- forward.cpp ----
+// Sets the calling thread's launch context (kernels.h) for the kernels of one forward of `m`: its range-flag word and whether this
+// is the re-run on the exact kernels.
+struct ForwardCtx {
+  pfhip::LaunchCtx saved;
+  explicit ForwardCtx(pfhip_model* m) : saved(pfhip::launch_ctx()) {
+    pfhip::launch_ctx().exact = m->exact_rerun || m->weights->always_exact;
+    pfhip::launch_ctx().range_flag = m->d_range_flag;
+  }
+  ~ForwardCtx() { pfhip::launch_ctx() = saved; }
+};
+pfhip_status enqueue_locked(pfhip_model* m, PcmView d_pcm, const int64_t* sample_off, const int* n_samples,
+                            int B, hipStream_t s, bool feats_only);
+
+// ---- heads.cpp ----
+struct SvsHost { const int32_t *num, *ids, *frames, *fid; const float *logp, *flp; };
+SvsHost svs_host(const pfhip_model* m);
+pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s);
+pfhip_status head_locked(pfhip_model* m, hipStream_t s, bool want_logp);
+pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_detail* dt = nullptr);
+void scatter_fires(const pfhip_model* m, int32_t* dst, int max_tokens);
+// the first k of the m->nbest_k candidates of every token row, utterance b at row b * max_tokens of the caller's buffers; staged
+// on the host like the ids (tok rows x k x 8 bytes)
+struct NbestStage {
+  std::vector<int32_t> ids; std::vector<float> logp;
+  pfhip_status start(pfhip_model* m, hipStream_t s) {
+    ids.resize((size_t)m->ML * m->nbest_k); logp.resize(ids.size());
+    HIP_TRY(hipMemcpyAsync(ids.data(), m->nb_ids.p, ids.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(logp.data(), m->nb_logp.p, logp.size() * 4, hipMemcpyDeviceToHost, s));
+    return PFHIP_OK;
+  }
+  void scatter(const pfhip_model* m, int k, int32_t* dst_ids, float* dst_logp, int max_tokens) const {      // after the synchronise
+    const int kc = m->nbest_k;
+    for (int b = 0; b < m->B; ++b)
+      for (int t = 0; t < m->n_fires[b]; ++t) {
+        const size_t src = ((size_t)m->tok_off[b] + t) * kc, dst = ((size_t)b * max_tokens + t) * k;
+        std::memcpy(dst_ids + dst, ids.data() + src, 4 * (size_t)k);
+        std::memcpy(dst_logp + dst, logp.data() + src, 4 * (size_t)k);
+      }
+  }
+};
+
+// ---- hotwords.cpp ----
+void release_hotwords(pfhip_model* m);
+struct HotwordPins {          // a forward's pins end with it, whichever way it ends (after its last synchronise)
+  pfhip_model* m;
+  ~HotwordPins() { release_hotwords(m); }
+};
+pfhip_status resolve_hotwords_locked(pfhip_model* m, const float* const* emb, const int* H, int n_sets, const int* set_of_utt, int B,
+                                     hipStream_t s);
+std::shared_ptr<const std::vector<float>> default_hotwords(pfhip_model* m);
+pfhip_status resolve_default_hotwords_locked(pfhip_model* m, int B, hipStream_t s);
+
+// ---- offline_api.cpp ----
+bool is_svs(const pfhip_model* m);
+pfhip_status refuse_svs();
+pfhip_status stage_pcm(pfhip_model* m, HostPcm pcm, const int* n_samples, int B, hipStream_t s,
+                       std::vector<int64_t>& off);
+pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, int B, int fs_in, hipStream_t s,
+                             std::vector<int64_t>& off, std::vector<int>& n_out);
+// hotword sets of a call: n_sets sets (emb[k]: [n[k], d]) and, per utterance, which one it attends to (of_utt == nullptr: all set 0)
+struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
+pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch,
+                            const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_detail* dt = nullptr);
+pfhip_model*& last_replica();       // the calling thread's tl_last_replica
+
+// ---- svs_api.cpp ----
+pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
+                                const int32_t* textnorm, pfhip_svs_out* out);
+
+// ---- pfhip.cpp: the execution slots ----
+void rebuild_slots_locked(pfhip_model* head);
+pfhip_model* acquire_slot(pfhip_model* head);
+void release_slot(pfhip_model* head, pfhip_model* slot);
+std::vector<pfhip_model*> all_slots(pfhip_model* head);
+
+}  // namespace pfhip_impl

@@ -342,7 +342,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
       continue;
     }
     // rounds of many connections (>= 1536 rows): the two LayerNorms of a layer folded into the GEMMs around them, as offline
-    // (pfhip.cpp forward_encoder: row statistics from the producing epilogue, algebraic normalisation in the consumer's)
+    // (forward.cpp forward_encoder: row statistics from the producing epilogue, algebraic normalisation in the consumer's)
     if (fuse_ln_s && !first)
       gemm_ln(L.qkv_f.folded, {.A = x, .C = m->qkv.f(), .ldc = 3 * d, .N = 3 * d, .K = d, .ln_colsum = L.qkv_f.colsum});
     else {

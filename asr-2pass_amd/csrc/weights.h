@@ -1,4 +1,4 @@
-// What a model holds that is read-only after load: one ModelWeights per device, built by build_model (pfhip.cpp), shared by the
+// What a model holds that is read-only after load: one ModelWeights per device, built by build_model (model_build.cpp), shared by the
 // weight owner and its execution contexts through a shared_ptr and freed by its destructor when the last of them goes.  Every
 // pointer a forward needs is a resolved field of the typed tables below; names and host pointers exist only inside the builder.
 #pragma once

@@ -157,7 +157,7 @@ def fused_ln_gemm(X, W, M, N, g=None, b=None, D=None, bias=None, R1=None, R2=Non
 
 def fold_layernorm(W, bias, g, b):
     """(W', b', colsum) for fused_gemv_1trip's algebraic LayerNorm: W' = W * g, b' = bias + W @ b, colsum = W'.sum(1) — in
-    double, rounded once, as the library does at load (pfhip.cpp)."""
+    double, rounded once, as the library does at load (model_build.cpp)."""
     Wd = W.double()
     Wf = (Wd * g.double()[None, :]).float()
     bf = ((bias.double() if bias is not None else 0.0) + Wd @ b.double()).float()

@@ -258,7 +258,7 @@ def test_full_size_batch_matches_oracle(pkg, weights_mod):
 
 @pytest.mark.parametrize("n_utts,check", [(36, (0, 13, 35)), (5, (0, 4)), (12, (0, 11))])
 def test_layernorm_folded_into_the_gemms_with_strong_gamma_beta(pkg, weights_mod, n_utts, check):
-    """Batches of >= 1536 rows take the fused encoder path (pfhip.cpp `fuse_ln`): the GEMMs that write the residual stream leave
+    """Batches of >= 1536 rows take the fused encoder path (forward.cpp `fuse_ln`): the GEMMs that write the residual stream leave
     per-tile row statistics, the GEMMs that read it normalise on load with gamma folded into their weights and beta into their
     bias.  Here gamma in [0.5, 1.5] and beta in [-0.5, 0.5] for every LayerNorm (the default synthetic weights keep them within
     5 % of 1 / 0), 36 x 30 s = 18000 encoder rows and > 4096 decoder rows (so the decoder's norm1 -> FFN1 and ffn_norm -> FFN2

@@ -209,7 +209,7 @@ def test_mixed_formats_in_the_merge_queue(pkg, plain):
 
     Every caller sends the same utterance u, so a merged forward is k copies of u in one format whatever the arrival order, and its
     per-utterance result is that of the unmerged call on [u] * k — the reference of the same batch composition, bit for bit (a
-    forward of another composition may differ in the last bits: pfhip.cpp, "cross-request batching").  k is not observable per caller:
+    forward of another composition may differ in the last bits: offline_api.cpp, "cross-request batching").  k is not observable per caller:
     each result must equal the reference of some k, the two formats' references are checked equal beforehand, and the lone two-thread
     case of the issue (k = 1: the unmerged call itself) is among them."""
     _, (man, blob) = plain

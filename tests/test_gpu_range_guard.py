@@ -1,4 +1,4 @@
-"""GPU: the guard of the fp16 two-plane domain (csrc/kernels.h LaunchCtx, pfhip.cpp fetch_locked).
+"""GPU: the guard of the fp16 two-plane domain (csrc/kernels.h LaunchCtx, heads.cpp fetch_locked).
 
 The default large-batch kernels stage their operands as two fp16 planes (gemm_x3.hip / gemm_p3.hip / attention_x3.hip): fp32-grade
 for values of ordinary magnitude, but |a| >= 65504 overflows and rows far below 1 lose relative precision.  The reference computes

@@ -3,7 +3,8 @@ The kernels are deterministic, so two builds of the library whose host code enqu
     python3 tools/forward_digest.py > new.txt;  PFHIP_LIB=build/ab/libpfhip_old.so python3 tools/forward_digest.py > old.txt;  diff old.txt new.txt
 Every case is one short forward in a fresh child process (the path knobs are read once per process, from its environment).
 Digested: token ids, token / fire / frame counts, log-probs, the `enc` and `alphas` tensors, and where the case has them the
-timestamp head's us_alphas / us_cif_peak, the N-best ids and values, the streaming tokens with their per-token detail.  The debug
+timestamp head's us_alphas / us_cif_peak, the N-best ids and values, the streaming tokens with their per-token detail; for SenseVoice
+everything pfhip_svs_forward returns from either CTC head, the rows' log-sum-exp and pfhip_svs_align on the returned tokens.  The debug
 read-outs that tell which path ran (plane / exact / context counters) are printed beside the digest and must match as well.
     python3 tools/forward_digest.py [case ...]      (no argument: all cases)"""
 import hashlib
@@ -32,6 +33,8 @@ CASES = {
     "small_paraformer": {},
     "second_context": {},
     "streaming": {},
+    "sensevoice": {},
+    "sensevoice_logp": {},
 }
 
 
@@ -125,6 +128,23 @@ def run_case(name):
                 add_detail(s, ids)
         for s in three:
             s.close()
+    elif name in ("sensevoice", "sensevoice_logp"):
+        model = pkg.SenseVoiceHip().InitAsr(W.synth_svs_weights(W.small_config_svs()))
+        # without log-prob rows the fused CTC head runs, with them the unfused one (GEMM + log-softmax over row chunks)
+        got = model.forward(secs(1, 2.5, 4), lid=[0, 3, 4], textnorm=[14, 15, 14], want_logp=name == "sensevoice_logp")
+        dg.add(got["token_num"], got["frame_len"])
+        for key in ("ids", "tok_frame", "tok_logp", "frame_ids", "frame_logp", "logp"):
+            for a in got.get(key) or []:
+                dg.add(a)
+        rows = int(np.sum(got["frame_len"]))
+        dg.add(model.get_tensor("enc", rows * 512), model.get_tensor("lse", rows))
+        al = model.align([ids[4:] for ids in got["ids"]])              # the returned tokens after the four leading tags
+        for key in ("begin", "end", "logp"):
+            for a in al[key]:
+                dg.add(a)
+        dg.add(al["score"])
+        for key in ("ctc_unfused_forwards", "ctc_head_chunks", "range_fallbacks", "plane_forwards"):
+            notes[key] = model.debug_poke(key)
     else:
         raise SystemExit(f"unknown case {name}")
     model.close()
