@@ -280,6 +280,14 @@ void launch_gather_rows(const int32_t* ids, const float* table, int D, float* ou
 void launch_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, int t, float* sel, int H, int D,
                       hipStream_t s);
 
+// ---- CT-Transformer helpers (punc.hip) ---------------------------------------------------------
+// out[row][0..D) = table[clamp(ids[row], 0, vocab - 1)] * scale + PE(pos + 1), pos = pos_of_row ? pos_of_row[row] : row; columns
+// D..Dout zeroed (Dout <= ldo)
+void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int D, int Dout, float* out, int ldo, int N,
+                         const float* inv_ts, float scale, const int* pos_of_row, hipStream_t s);
+// out[row] = the first maximum over columns [0, ncls) of the row (std::max_element, ct-transformer.cpp:193-196)
+void launch_argmax_first(const float* logits, int ldl, int N, int ncls, int32_t* out, hipStream_t s);
+
 // ---- head -----------------------------------------------------------------
 // per row: log-softmax over V logits, argmax (first max wins, util.cpp:63-74).  logp may be null.
 // range_flag (may be null): bit 0 is raised when a row's log-sum-exp is not finite (NaN / Inf reached the logits).
@@ -332,14 +340,11 @@ bool launch_logsoftmax_topk(const float* logits, int ldl, int ML, int V, int k, 
                             float* topk_logp, hipStream_t s, int* range_flag = nullptr);
 
 // ---- chunk-streaming pieces ----------------------------------------------
-// OnlineLfrCmvn + x*sqrt(d) + GetPosEmb (paraformer-online.cpp:196-238, 549-555, 240-268) for `n_rows`
-// LFR rows: row i = frames [6i, 6i+7) of fb (T frames incl. the splice cache), the tail replicated with
-// the last frame; out[i] = ((x + mean) * istd) * scale + PE(pos0 + i + 1).  out has row stride ldo.
-void launch_stream_lfr(const float* fb, int T, int n_rows, const float* mean, const float* istd, float scale,
-                       const float* inv_ts, int pos0, float* out, int ldo, hipStream_t s);
-// dst[r][0..ncols) = src[r][0..ncols) (or 0 when src == nullptr), columns ncols..ldd zeroed.
-void launch_rows_copy(float* dst, int ldd, const float* src, int lds_, int nrows, int ncols, hipStream_t s);
-// The same two for many connections in one launch: one descriptor per operation (arrays in HBM).
+// Per-connection operations of a streaming batch, many in one launch: one descriptor per operation (arrays in HBM).
+// rows_copy: dst[r][0..ncols) = src[r][0..ncols) (or 0 when src == nullptr), columns ncols..ldd zeroed.
+// stream_lfr: OnlineLfrCmvn + x*sqrt(d) + GetPosEmb (paraformer-online.cpp:196-238, 549-555, 240-268) for `n_rows` LFR rows: row i =
+// frames [6i, 6i+7) of fb (T frames incl. the splice cache), the tail replicated with the last frame;
+// out[i] = ((x + mean) * istd) * scale + PE(pos0 + i + 1).  out has row stride ldo.
 struct RowsCopyOp { float* dst; const float* src; int ldd, lds, nrows, ncols; };      // src == nullptr: zeros; lds == 0: row 0 repeated
 struct StreamLfrOp { const float* fb; float* out; int T, n_rows, pos0, pad_; };
 void launch_rows_copy_batch(const RowsCopyOp* ops, int n_ops, int max_rows, hipStream_t s);
@@ -410,10 +415,6 @@ LnGemmRoute fused_ln_gemm_route(int M, int N, int K, bool has_ln);
 // Generic LfrCmvn over raw fbank frames fb [F, n_mels] -> out [T = ceil(F/n), ldo] (columns >= m*n_mels zeroed).
 void launch_lfr_cmvn(const float* fb, int F, int T, int m, int n, int n_mels, const float* mean, const float* istd,
                      float* out, int ldo, hipStream_t s);
-// OnlineLfrCmvn form (fsmn-vad-online.cpp:90-133): row i = frames [i*n, i*n + m) of fb (which starts with the splice cache),
-// the tail replicated with the last frame; no left padding.
-void launch_lfr_cmvn_online(const float* fb, int F, int T, int m, int n, int n_mels, const float* mean, const float* istd,
-                            float* out, int ldo, hipStream_t s);
 // Memory block with left order 20: out = p + causal depthwise conv over [cache(19 rows); p]; cache_out (may be
 // null) receives the last 19 rows of [cache_in; p] and must not alias cache_in.
 // One connection's share of a packed FSMN-VAD forward: rows [row_off, row_off + T), network caches [layers][19][C]
@@ -422,6 +423,8 @@ struct VadSeg { const float* cache_in; float* cache_out; int row_off, T; };
 struct VadLfrOp { const float* fb; int Tin, n_out, row_off, pad_; };
 void launch_fsmn_causal20(const float* p, int ldp, const float* w, const VadSeg* segs, int B, int max_T, int layer, float* out,
                           int ldo, int C, hipStream_t s);
+// OnlineLfrCmvn (fsmn-vad-online.cpp:90-133) for many connections: row i of operation k = frames [i*n, i*n + m) of its fb (which starts
+// with the splice cache; Tin frames), the tail replicated with the last frame, no left padding; rows row_off .. + n_out of out.
 void launch_lfr_cmvn_online_batch(const VadLfrOp* ops, int n_ops, int max_rows, int m, int n, int n_mels, const float* mean,
                                   const float* istd, float* out, int ldo, hipStream_t s);
 void launch_softmax_rows(const float* x, int ldx, int M, int N, float* y, float* col0, hipStream_t s);

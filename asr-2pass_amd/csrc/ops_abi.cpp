@@ -1,7 +1,7 @@
 // Operator-level C ABI (include/pfhip_ops.h): thin wrappers over the kernel launchers.
 #include "../../include/pfhip_ops.h"
 
-#include "kernels.h"
+#include "internal.h"      // build_frontend_tables, DevMem; brings kernels.h
 
 #include <vector>
 
@@ -501,6 +501,207 @@ int pfhip_op_blstm(const float* gx, const float* whh, float* y, const int* off, 
 int pfhip_op_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, int t, float* sel, int H, int D, void* stream) {
   if (H < 0 || D <= 0 || !G || !c || !h || !lens || !sel) return (int)hipErrorInvalidValue;
   pfhip::launch_lstm_cell(G, c, h, lens, t, sel, H, D, S(stream));
+  return done();
+}
+
+}  // extern "C"
+
+// ---- the front-end kernels, the LFR/CMVN family, the PE kernels, the row gathers and small reductions (tests only) -------------------
+namespace {
+constexpr int kInvalid = (int)hipErrorInvalidValue;
+// launch, then wait: the entries below free what they uploaded when they return
+template <class Launch>
+int launch_and_drain(hipStream_t s, Launch launch) {
+  launch();
+  hipError_t e = hipGetLastError();
+  const hipError_t e2 = hipStreamSynchronize(s);
+  return (int)(e == hipSuccess ? e2 : e);
+}
+// The fbank kernel in either launch form from HOST index arrays.  Everything the kernel assumes is checked here: every frame it reads
+// lies inside pcm (pcm_samples samples), every row it writes inside feats (feats_rows rows of 560) or fb_out (total_frames rows of 80).
+template <typename Sample>
+int fbank_op(const Sample* pcm, long long pcm_samples, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+             int total_frames, float* fb_out, float* feats, long long feats_rows, const int* row_off, const float* cmvn_mean,
+             const float* cmvn_istd, void* stream) {
+  const bool raw = fb_out != nullptr;
+  if (!pcm || !sample_off || !frame_off || !nframes || B < 1 || total_frames < 0 || pcm_samples < 0 || raw == (feats != nullptr))
+    return kInvalid;
+  if (!raw && (!row_off || !cmvn_mean || !cmvn_istd || feats_rows < 0)) return kInvalid;
+  if (frame_off[0] != 0 || frame_off[B] != total_frames) return kInvalid;
+  for (int b = 0; b < B; ++b) {
+    const int nf = nframes[b];
+    if (nf < 0 || frame_off[b + 1] - frame_off[b] != nf) return kInvalid;
+    if (nf == 0) continue;
+    if (sample_off[b] < 0 || sample_off[b] + 400 + 160LL * (nf - 1) > pcm_samples) return kInvalid;
+    if (!raw && (row_off[b] < 0 || row_off[b] + (nf + 5) / 6 > feats_rows)) return kInvalid;
+  }
+  if (total_frames == 0) return 0;
+  pfhip_impl::FrontendTables ft;
+  if (pfhip_impl::build_frontend_tables(80, 16000, &ft) != PFHIP_OK) return (int)hipErrorUnknown;
+  pfhip_impl::DevMem d_so, d_fo, d_nf, d_ro;
+  hipError_t e = d_so.upload(sample_off, sizeof(int64_t) * B);
+  if (e == hipSuccess) e = d_fo.upload(frame_off, sizeof(int) * (B + 1));
+  if (e == hipSuccess) e = d_nf.upload(nframes, sizeof(int) * B);
+  if (e == hipSuccess && !raw) e = d_ro.upload(row_off, sizeof(int) * B);
+  if (e != hipSuccess) return (int)e;
+  const pfhip::FbankTables tb = ft.fbank(cmvn_mean, cmvn_istd);
+  return launch_and_drain(S(stream), [&] {
+    if (!raw)
+      pfhip::launch_fbank_lfr_cmvn(pcm, d_so.as<int64_t>(), d_fo.as<int>(), d_nf.as<int>(), d_ro.as<int>(), B, total_frames, tb, feats, S(stream));
+    else if (B == 1)
+      pfhip::launch_fbank_frames(pcm, d_so.as<int64_t>(), d_fo.as<int>(), d_nf.as<int>(), total_frames, tb, fb_out, S(stream));
+    else
+      pfhip::launch_fbank_frames_batch(pcm, d_so.as<int64_t>(), d_fo.as<int>(), d_nf.as<int>(), B, total_frames, tb, fb_out, S(stream));
+  });
+}
+inline bool lfr_shape_ok(int m, int n, int n_mels, int ldo) {
+  return m >= 1 && n >= 1 && n_mels >= 1 && (long long)m * n_mels <= ldo;
+}
+}  // namespace
+
+extern "C" {
+
+int pfhip_op_fbank(const float* pcm, long long pcm_samples, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                   int total_frames, float* fb_out, float* feats, long long feats_rows, const int* row_off, const float* cmvn_mean,
+                   const float* cmvn_istd, void* stream) {
+  return fbank_op(pcm, pcm_samples, sample_off, frame_off, nframes, B, total_frames, fb_out, feats, feats_rows, row_off, cmvn_mean, cmvn_istd,
+                  stream);
+}
+int pfhip_op_fbank_s16(const int16_t* pcm, long long pcm_samples, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                       int total_frames, float* fb_out, float* feats, long long feats_rows, const int* row_off, const float* cmvn_mean,
+                       const float* cmvn_istd, void* stream) {
+  return fbank_op(pcm, pcm_samples, sample_off, frame_off, nframes, B, total_frames, fb_out, feats, feats_rows, row_off, cmvn_mean, cmvn_istd,
+                  stream);
+}
+
+int pfhip_op_lfr_cmvn(const float* fb, int F, int m, int n, int n_mels, const float* mean, const float* istd, float* out, int ldo,
+                      void* stream) {
+  if (!fb || !mean || !istd || !out || F < 0 || !lfr_shape_ok(m, n, n_mels, ldo)) return kInvalid;
+  pfhip::launch_lfr_cmvn(fb, F, (F + n - 1) / n, m, n, n_mels, mean, istd, out, ldo, S(stream));
+  return done();
+}
+int pfhip_op_lfr_cmvn_packed(const float* fb, long long fb_frames, const int* frame_off, const int* nframes, const int* row_off, int B,
+                             int m, int n, int n_mels, const float* mean, const float* istd, float* out, int ldo, long long out_rows,
+                             void* stream) {
+  if (!fb || !frame_off || !nframes || !row_off || !mean || !istd || !out || B < 1 || fb_frames < 0 || out_rows < 0 ||
+      !lfr_shape_ok(m, n, n_mels, ldo))
+    return kInvalid;
+  int max_T = 0;
+  for (int b = 0; b < B; ++b) {
+    const int T = nframes[b] < 0 ? -1 : (nframes[b] + n - 1) / n;
+    if (T < 0 || frame_off[b] < 0 || (long long)frame_off[b] + nframes[b] > fb_frames || row_off[b] < 0 || (long long)row_off[b] + T > out_rows)
+      return kInvalid;
+    if (T > max_T) max_T = T;
+  }
+  pfhip_impl::DevMem d_fo, d_nf, d_ro;
+  hipError_t e = d_fo.upload(frame_off, sizeof(int) * B);
+  if (e == hipSuccess) e = d_nf.upload(nframes, sizeof(int) * B);
+  if (e == hipSuccess) e = d_ro.upload(row_off, sizeof(int) * B);
+  if (e != hipSuccess) return (int)e;
+  return launch_and_drain(S(stream), [&] {
+    pfhip::launch_lfr_cmvn_packed(fb, d_fo.as<int>(), d_nf.as<int>(), d_ro.as<int>(), B, max_T, m, n, n_mels, mean, istd, out, ldo, S(stream));
+  });
+}
+int pfhip_op_lfr_cmvn_online_batch(const float* fb, long long fb_frames, const int* fb_off, const int* Tin, const int* n_out,
+                                   const int* row_off, int n_ops, int m, int n, int n_mels, const float* mean, const float* istd,
+                                   float* out, int ldo, long long out_rows, void* stream) {
+  if (!fb || !fb_off || !Tin || !n_out || !row_off || !mean || !istd || !out || n_ops < 1 || fb_frames < 0 || out_rows < 0 ||
+      !lfr_shape_ok(m, n, n_mels, ldo))
+    return kInvalid;
+  std::vector<pfhip::VadLfrOp> ops((size_t)n_ops);
+  int max_rows = 0;
+  for (int k = 0; k < n_ops; ++k) {
+    // an operation with rows reads frame min(i n + j, Tin - 1): it needs one frame at least
+    if (n_out[k] < 0 || Tin[k] < 0 || (n_out[k] > 0 && Tin[k] < 1) || fb_off[k] < 0 || (long long)fb_off[k] + Tin[k] > fb_frames ||
+        row_off[k] < 0 || (long long)row_off[k] + n_out[k] > out_rows)
+      return kInvalid;
+    ops[k] = pfhip::VadLfrOp{fb + (size_t)fb_off[k] * n_mels, Tin[k], n_out[k], row_off[k], 0};
+    if (n_out[k] > max_rows) max_rows = n_out[k];
+  }
+  return with_device_segs(ops, S(stream), [&](const pfhip::VadLfrOp* d) {
+    pfhip::launch_lfr_cmvn_online_batch(d, n_ops, max_rows, m, n, n_mels, mean, istd, out, ldo, S(stream));
+  });
+}
+int pfhip_op_stream_lfr_batch(const float* fb, long long fb_frames, const int* fb_off, const int* T, const int* n_rows, const int* pos0,
+                              const int* row_off, int n_ops, const float* mean, const float* istd, float scale, const float* inv_ts,
+                              float* out, int ldo, long long out_rows, void* stream) {
+  if (!fb || !fb_off || !T || !n_rows || !pos0 || !row_off || !mean || !istd || !inv_ts || !out || n_ops < 1 || fb_frames < 0 ||
+      out_rows < 0 || ldo < 560)
+    return kInvalid;
+  std::vector<pfhip::StreamLfrOp> ops((size_t)n_ops);
+  int max_rows = 0;
+  for (int k = 0; k < n_ops; ++k) {
+    if (n_rows[k] < 0 || T[k] < 0 || (n_rows[k] > 0 && T[k] < 1) || fb_off[k] < 0 || (long long)fb_off[k] + T[k] > fb_frames ||
+        row_off[k] < 0 || (long long)row_off[k] + n_rows[k] > out_rows || pos0[k] < 0)
+      return kInvalid;
+    ops[k] = pfhip::StreamLfrOp{fb + (size_t)fb_off[k] * 80, out + (size_t)row_off[k] * ldo, T[k], n_rows[k], pos0[k], 0};
+    if (n_rows[k] > max_rows) max_rows = n_rows[k];
+  }
+  return with_device_segs(ops, S(stream), [&](const pfhip::StreamLfrOp* d) {
+    pfhip::launch_stream_lfr_batch(d, n_ops, max_rows, mean, istd, scale, inv_ts, ldo, S(stream));
+  });
+}
+int pfhip_op_rows_copy_batch(float* dst, long long dst_floats, const long long* dst_off, const float* src, long long src_floats,
+                             const long long* src_off, const int* ldd, const int* lds, const int* nrows, const int* ncols, int n_ops,
+                             void* stream) {
+  if (!dst || !dst_off || !src_off || !ldd || !lds || !nrows || !ncols || n_ops < 1 || dst_floats < 0 || src_floats < 0) return kInvalid;
+  std::vector<pfhip::RowsCopyOp> ops((size_t)n_ops);
+  int max_rows = 0;
+  for (int k = 0; k < n_ops; ++k) {
+    const bool has_src = src_off[k] >= 0;      // a negative source offset: no source, the rows are zeroed
+    if (nrows[k] < 0 || ldd[k] < 0 || ncols[k] < 0 || ncols[k] > ldd[k] || dst_off[k] < 0 ||
+        dst_off[k] + (long long)nrows[k] * ldd[k] > dst_floats)
+      return kInvalid;
+    if (has_src && nrows[k] > 0 &&
+        (!src || lds[k] < 0 || (lds[k] != 0 && lds[k] < ncols[k]) || src_off[k] + (long long)(nrows[k] - 1) * lds[k] + ncols[k] > src_floats))
+      return kInvalid;
+    ops[k] = pfhip::RowsCopyOp{dst + dst_off[k], has_src ? src + src_off[k] : nullptr, ldd[k], lds[k], nrows[k], ncols[k]};
+    if (nrows[k] > max_rows) max_rows = nrows[k];
+  }
+  return with_device_segs(ops, S(stream), [&](const pfhip::RowsCopyOp* d) { pfhip::launch_rows_copy_batch(d, n_ops, max_rows, S(stream)); });
+}
+
+int pfhip_op_embed(const float* feats, int D, float* x0, int ldx, const int* row_pos, int M, const float* inv_ts, float scale, void* stream) {
+  // inv_ts holds D / 2 entries: column c reads entry c or c - D / 2
+  if (!feats || !x0 || !row_pos || !inv_ts || M < 0 || D < 2 || D % 2 || ldx < D) return kInvalid;
+  pfhip::launch_embed(feats, D, x0, ldx, row_pos, M, inv_ts, scale, S(stream));
+  return done();
+}
+int pfhip_op_embed_gather(const int32_t* ids, const float* table, int vocab, int D, int Dout, float* out, int ldo, int N,
+                          const float* inv_ts, float scale, const int* pos_of_row, void* stream) {
+  if (!ids || !table || !out || !inv_ts || N < 0 || vocab < 1 || D < 2 || D % 2 || Dout < D || ldo < Dout) return kInvalid;
+  pfhip::launch_embed_gather(ids, table, vocab, D, Dout, out, ldo, N, inv_ts, scale, pos_of_row, S(stream));
+  return done();
+}
+int pfhip_op_argmax_first(const float* logits, int ldl, int N, int ncls, int32_t* out, void* stream) {
+  if (!logits || !out || N < 0 || ncls < 1 || ldl < ncls) return kInvalid;
+  pfhip::launch_argmax_first(logits, ldl, N, ncls, out, S(stream));
+  return done();
+}
+int pfhip_op_compact(const float* stage, float* emb, const int* tok_row_src, int ML, int D, void* stream) {
+  if (!stage || !emb || !tok_row_src || ML < 0 || D <= 0 || D % 4) return kInvalid;      // rows move as float4s
+  pfhip::launch_compact(stage, emb, tok_row_src, ML, D, S(stream));
+  return done();
+}
+int pfhip_op_gather_rows(const int32_t* ids, const float* table, int D, float* out, int R, void* stream) {
+  if (!ids || !table || !out || R < 0 || D <= 0 || D % 4) return kInvalid;               // rows move as float4s
+  pfhip::launch_gather_rows(ids, table, D, out, R, S(stream));
+  return done();
+}
+int pfhip_op_svs_prompt_rows(const float* E, int D, const int* prompt, const int* row_off, const int* len, int B, float* feats, int ld,
+                             void* stream) {
+  if (!E || !prompt || !row_off || !len || !feats || B < 0 || D <= 0 || D % 4 || ld < D) return kInvalid;
+  pfhip::launch_svs_prompt_rows(E, D, prompt, row_off, len, B, feats, ld, S(stream));
+  return done();
+}
+int pfhip_op_gather_best(const float* logp, int ld, const int32_t* ids, int M, float* best, void* stream) {
+  if (!logp || !ids || !best || M < 0 || ld < 1) return kInvalid;
+  pfhip::launch_gather_best(logp, ld, ids, M, best, S(stream));
+  return done();
+}
+int pfhip_op_row_lse(const float* logits, int ld, int M, int V, float* lse, void* stream) {
+  if (!logits || !lse || M < 0 || V < 1 || ld < V) return kInvalid;
+  pfhip::launch_row_lse(logits, ld, M, V, lse, S(stream));
   return done();
 }
 

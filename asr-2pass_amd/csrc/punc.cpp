@@ -19,12 +19,6 @@
 
 using namespace pfhip_impl;
 
-namespace pfhip {
-void launch_embed_gather(const int32_t* ids, const float* table, int vocab, int D, int Dout, float* out, int ldo, int N,
-                         const float* inv_ts, float scale, const int* pos_of_row, hipStream_t s);   // punc.hip
-void launch_argmax_first(const float* logits, int ldl, int N, int ncls, int32_t* out, hipStream_t s);
-}
-
 struct PuncReq : pfhip_impl::MergeReqBase {
   const int32_t* ids; int n; int vad_pos; int32_t* out;
   pfhip_status st = PFHIP_OK; std::string err;

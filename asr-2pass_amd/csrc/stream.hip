@@ -11,38 +11,6 @@ namespace {
 
 constexpr int kMels = 80, kLfrM = 7, kLfrN = 6, kFeat = kMels * kLfrM;
 
-__global__ __launch_bounds__(192) void stream_lfr_kernel(const float* __restrict__ fb, int T, int n_rows,
-                                                         const float* __restrict__ mean,
-                                                         const float* __restrict__ istd, float scale,
-                                                         const float* __restrict__ inv_ts, int pos0,
-                                                         float* __restrict__ out, int ldo) {
-  const int i = blockIdx.x;
-  if (i >= n_rows) return;
-  const float pos = (float)(pos0 + i + 1);
-  for (int c = threadIdx.x; c < kFeat; c += blockDim.x) {
-    const int j = c / kMels, bin = c - j * kMels;
-    int f = i * kLfrN + j;
-    if (f > T - 1) f = T - 1;                       // OnlineLfrCmvn :210-218: pad with the last frame
-    float x = fb[(size_t)f * kMels + bin];
-    x = (x + mean[c]) * istd[c];                    // :231-235
-    x = x * scale;                                  // Forward :549-553
-    const int half = kFeat / 2;
-    const int k = c < half ? c : c - half;
-    const float coe = inv_ts[k] * pos;              // GetPosEmb :251-259
-    x = x + (c < half ? sinf(coe) : cosf(coe));
-    out[(size_t)i * ldo + c] = x;
-  }
-}
-
-__global__ __launch_bounds__(256) void rows_copy_kernel(float* __restrict__ dst, int ldd,
-                                                        const float* __restrict__ src, int lds_, int nrows,
-                                                        int ncols) {
-  const int r = blockIdx.x;
-  if (r >= nrows) return;
-  for (int c = threadIdx.x; c < ldd; c += blockDim.x)
-    dst[(size_t)r * ldd + c] = (src && c < ncols) ? src[(size_t)r * lds_ + c] : 0.f;
-}
-
 // One block per connection of the batch (blockIdx.x): the window of stream b is rows [row_off, row_off + n) of the packed
 // encoder output, its fires go to emb_all[b * emb_rows ...], its carry lives in the stream's own buffer.
 // Batched forms for many connections: blockIdx.y = operation, each with its own pointers (descriptor array in HBM).
@@ -56,13 +24,13 @@ __global__ __launch_bounds__(192) void stream_lfr_batch_kernel(const StreamLfrOp
   for (int c = threadIdx.x; c < kFeat; c += blockDim.x) {
     const int j = c / kMels, bin = c - j * kMels;
     int f = i * kLfrN + j;
-    if (f > op.T - 1) f = op.T - 1;
+    if (f > op.T - 1) f = op.T - 1;                    // OnlineLfrCmvn :210-218: pad with the last frame
     float x = op.fb[(size_t)f * kMels + bin];
-    x = (x + mean[c]) * istd[c];
-    x = x * scale;
+    x = (x + mean[c]) * istd[c];                       // :231-235
+    x = x * scale;                                     // Forward :549-553
     const int half = kFeat / 2;
     const int k = c < half ? c : c - half;
-    const float coe = inv_ts[k] * pos;
+    const float coe = inv_ts[k] * pos;                 // GetPosEmb :251-259
     x = x + (c < half ? sinf(coe) : cosf(coe));
     op.out[(size_t)i * ldo + c] = x;
   }
@@ -198,18 +166,6 @@ __global__ __launch_bounds__(128) void fsmn_cached_kernel(const float* __restric
 }
 
 }  // namespace
-
-void launch_stream_lfr(const float* fb, int T, int n_rows, const float* mean, const float* istd, float scale,
-                       const float* inv_ts, int pos0, float* out, int ldo, hipStream_t s) {
-  if (n_rows <= 0) return;
-  hipLaunchKernelGGL(stream_lfr_kernel, dim3(n_rows), dim3(192), 0, s, fb, T, n_rows, mean, istd, scale, inv_ts,
-                     pos0, out, ldo);
-}
-
-void launch_rows_copy(float* dst, int ldd, const float* src, int lds_, int nrows, int ncols, hipStream_t s) {
-  if (nrows <= 0) return;
-  hipLaunchKernelGGL(rows_copy_kernel, dim3(nrows), dim3(256), 0, s, dst, ldd, src, lds_, nrows, ncols);
-}
 
 void launch_stream_lfr_batch(const StreamLfrOp* ops, int n_ops, int max_rows, const float* mean, const float* istd, float scale,
                              const float* inv_ts, int ldo, hipStream_t s) {

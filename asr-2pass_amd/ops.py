@@ -786,3 +786,149 @@ def frame_energy(pcm, sample_off, n_samples, flen=400, fshift=160):
     fn = lib.pfhip_op_frame_energy_s16 if pcm.dtype == torch.int16 else lib.pfhip_op_frame_energy
     _ck(fn(_p(pcm), _p(d_so), _p(d_fo), _p(d_nf), len(nf), fo[-1], int(flen), int(fshift), _p(e), _stream()), "frame_energy")
     return e[:fo[-1]], fo
+
+
+# ---- the front-end kernels, the LFR/CMVN family, the PE kernels, the gathers and small reductions ------------------------------------
+def _hl(values):
+    """_hi for int64 host arrays."""
+    import numpy as np
+    a = np.ascontiguousarray(values, np.int64)
+    return a, ctypes.c_void_p(a.ctypes.data)
+
+
+def fbank_entry(pcm, pcm_samples, sample_off, frame_off, nframes, B, total_frames, fb_out=None, feats=None, feats_rows=0, row_off=None,
+                cmvn_mean=None, cmvn_istd=None):
+    """pfhip_op_fbank / pfhip_op_fbank_s16 (by pcm's dtype, float32 or int16) as it is: nothing derived or checked here.  sample_off /
+    frame_off / nframes / row_off: host int sequences or None (= NULL)."""
+    lib = _lib()
+    lib.pfhip_op_fbank.argtypes = [_vp, _ll, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _ll, _vp, _vp, _vp, _vp]
+    lib.pfhip_op_fbank_s16.argtypes = lib.pfhip_op_fbank.argtypes
+    if pcm is not None and pcm.dtype not in (torch.float32, torch.int16):
+        raise PfhipError("fbank takes float32 or int16 samples")
+    fn = lib.pfhip_op_fbank_s16 if pcm is not None and pcm.dtype == torch.int16 else lib.pfhip_op_fbank
+    so = _hl(sample_off) if sample_off is not None else (None, None)
+    fo = _hi(frame_off) if frame_off is not None else (None, None)
+    nf = _hi(nframes) if nframes is not None else (None, None)
+    ro = _hi(row_off) if row_off is not None else (None, None)
+    _ck(fn(_p(pcm), int(pcm_samples), so[1], fo[1], nf[1], int(B), int(total_frames), _p(fb_out), _p(feats), int(feats_rows), ro[1],
+           _p(cmvn_mean), _p(cmvn_istd), _stream()), "fbank")
+
+
+def fbank_layout(n_samples, flen=400, fshift=160):
+    """(nframes, frame_off) of utterances of n_samples[b] samples: what the fbank entries take."""
+    nf = [0 if n < flen else 1 + (n - flen) // fshift for n in n_samples]
+    fo = [0]
+    for f in nf:
+        fo.append(fo[-1] + f)
+    return nf, fo
+
+
+def fbank_frames(pcm, sample_off, n_samples, out):
+    """Raw log-mel frames of the utterances packed in `pcm` (float32 or int16 device tensor; utterance b is n_samples[b] samples from
+    sample_off[b], host int sequences) into out [>= total frames, 80].  Returns frame_off."""
+    nf, fo = fbank_layout(n_samples)
+    fbank_entry(pcm, pcm.numel(), sample_off, fo, nf, len(nf), fo[-1], fb_out=out)
+    return fo
+
+
+def fbank_lfr_cmvn(pcm, sample_off, n_samples, row_off, cmvn_mean, cmvn_istd, feats):
+    """The fused form: LFR (7, 6) + CMVN rows of utterance b at row row_off[b] of feats [rows, 560]."""
+    nf, fo = fbank_layout(n_samples)
+    fbank_entry(pcm, pcm.numel(), sample_off, fo, nf, len(nf), fo[-1], feats=feats, feats_rows=feats.shape[0], row_off=row_off,
+                cmvn_mean=cmvn_mean, cmvn_istd=cmvn_istd)
+    return fo
+
+
+def lfr_cmvn(fb, F, m, n, n_mels, mean, istd, out):
+    """out [>= ceil(F / n), ldo] = LfrCmvn of fb [F, n_mels]; columns m * n_mels .. ldo zeroed."""
+    lib = _lib()
+    lib.pfhip_op_lfr_cmvn.argtypes = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp]
+    _ck(lib.pfhip_op_lfr_cmvn(_p(fb), int(F), int(m), int(n), int(n_mels), _p(mean), _p(istd), _p(out), out.stride(0), _stream()), "lfr_cmvn")
+
+
+def lfr_cmvn_packed(fb, frame_off, nframes, row_off, m, n, n_mels, mean, istd, out):
+    """LfrCmvn of the files packed in fb [frames, n_mels] (frame_off / nframes / row_off: host int sequences)."""
+    lib = _lib()
+    lib.pfhip_op_lfr_cmvn_packed.argtypes = [_vp, _ll, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ll, _vp]
+    fo, nf, ro = _hi(frame_off), _hi(nframes), _hi(row_off)
+    _ck(lib.pfhip_op_lfr_cmvn_packed(_p(fb), fb.shape[0], fo[1], nf[1], ro[1], len(nframes), int(m), int(n), int(n_mels), _p(mean), _p(istd),
+                                     _p(out), out.stride(0), out.shape[0], _stream()), "lfr_cmvn_packed")
+
+
+def lfr_cmvn_online_batch(fb, fb_off, Tin, n_out, row_off, m, n, n_mels, mean, istd, out):
+    """OnlineLfrCmvn rows of many connections (fb_off / Tin / n_out / row_off: host int sequences, in frames and rows)."""
+    lib = _lib()
+    lib.pfhip_op_lfr_cmvn_online_batch.argtypes = [_vp, _ll, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ll, _vp]
+    fo, ti, no, ro = _hi(fb_off), _hi(Tin), _hi(n_out), _hi(row_off)
+    _ck(lib.pfhip_op_lfr_cmvn_online_batch(_p(fb), fb.shape[0], fo[1], ti[1], no[1], ro[1], len(Tin), int(m), int(n), int(n_mels), _p(mean),
+                                           _p(istd), _p(out), out.stride(0), out.shape[0], _stream()), "lfr_cmvn_online_batch")
+
+
+def stream_lfr_batch(fb, fb_off, T, n_rows, pos0, row_off, mean, istd, scale, inv_ts, out):
+    """The streaming front end's LFR + CMVN + scale + PE rows of many connections into out [rows, ldo >= 560]."""
+    lib = _lib()
+    lib.pfhip_op_stream_lfr_batch.argtypes = [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _cf, _vp, _vp, _ci, _ll, _vp]
+    fo, tt, nr, p0, ro = _hi(fb_off), _hi(T), _hi(n_rows), _hi(pos0), _hi(row_off)
+    _ck(lib.pfhip_op_stream_lfr_batch(_p(fb), fb.shape[0], fo[1], tt[1], nr[1], p0[1], ro[1], len(T), _p(mean), _p(istd), float(scale),
+                                      _p(inv_ts), _p(out), out.stride(0), out.shape[0], _stream()), "stream_lfr_batch")
+
+
+def rows_copy_batch(dst, dst_off, src, src_off, ldd, lds, nrows, ncols):
+    """Many row copies in one launch over flat float32 tensors dst / src (src may be None); a negative src_off means zeros."""
+    lib = _lib()
+    lib.pfhip_op_rows_copy_batch.argtypes = [_vp, _ll, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ci, _vp]
+    do, so, a, b, c, d = _hl(dst_off), _hl(src_off), _hi(ldd), _hi(lds), _hi(nrows), _hi(ncols)
+    _ck(lib.pfhip_op_rows_copy_batch(_p(dst), dst.numel(), do[1], _p(src), src.numel() if src is not None else 0, so[1], a[1], b[1], c[1],
+                                     d[1], len(nrows), _stream()), "rows_copy_batch")
+
+
+def embed(feats, D, x0, row_pos, M, inv_ts, scale):
+    """x0 [>= M, ldx] = feats [M, D] * scale + PE(row_pos + 1); columns D .. ldx zeroed."""
+    lib = _lib()
+    lib.pfhip_op_embed.argtypes = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _cf, _vp]
+    _ck(lib.pfhip_op_embed(_p(feats), int(D), _p(x0), x0.stride(0), _p(row_pos), int(M), _p(inv_ts), float(scale), _stream()), "embed")
+
+
+def embed_gather(ids, table, D, Dout, out, N, inv_ts, scale, pos_of_row=None):
+    """out [>= N, ldo] = table[clamped id] * scale + PE; columns D .. Dout zeroed."""
+    lib = _lib()
+    lib.pfhip_op_embed_gather.argtypes = [_vp, _vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _cf, _vp, _vp]
+    _ck(lib.pfhip_op_embed_gather(_p(ids), _p(table), table.shape[0], int(D), int(Dout), _p(out), out.stride(0), int(N), _p(inv_ts),
+                                  float(scale), _p(pos_of_row), _stream()), "embed_gather")
+
+
+def argmax_first(logits, N, ncls, out):
+    lib = _lib()
+    lib.pfhip_op_argmax_first.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp]
+    _ck(lib.pfhip_op_argmax_first(_p(logits), logits.stride(0), int(N), int(ncls), _p(out), _stream()), "argmax_first")
+
+
+def compact(stage, emb, src_row, ML, D):
+    lib = _lib()
+    lib.pfhip_op_compact.argtypes = [_vp, _vp, _vp, _ci, _ci, _vp]
+    _ck(lib.pfhip_op_compact(_p(stage), _p(emb), _p(src_row), int(ML), int(D), _stream()), "compact")
+
+
+def gather_rows(ids, table, D, out, R):
+    lib = _lib()
+    lib.pfhip_op_gather_rows.argtypes = [_vp, _vp, _ci, _vp, _ci, _vp]
+    _ck(lib.pfhip_op_gather_rows(_p(ids), _p(table), int(D), _p(out), int(R), _stream()), "gather_rows")
+
+
+def svs_prompt_rows(E, D, prompt, row_off, length, B, feats):
+    lib = _lib()
+    lib.pfhip_op_svs_prompt_rows.argtypes = [_vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _vp]
+    _ck(lib.pfhip_op_svs_prompt_rows(_p(E), int(D), _p(prompt), _p(row_off), _p(length), int(B), _p(feats), feats.stride(0), _stream()),
+        "svs_prompt_rows")
+
+
+def gather_best(logp, ids, M, best):
+    lib = _lib()
+    lib.pfhip_op_gather_best.argtypes = [_vp, _ci, _vp, _ci, _vp, _vp]
+    _ck(lib.pfhip_op_gather_best(_p(logp), logp.stride(0), _p(ids), int(M), _p(best), _stream()), "gather_best")
+
+
+def row_lse(logits, M, V, lse):
+    lib = _lib()
+    lib.pfhip_op_row_lse.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp]
+    _ck(lib.pfhip_op_row_lse(_p(logits), logits.stride(0), int(M), int(V), _p(lse), _stream()), "row_lse")

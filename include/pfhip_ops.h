@@ -320,6 +320,75 @@ int pfhip_op_blstm(const float* gx, const float* whh, float* y, const int* off, 
  * lens[j] - 1 == t also copy h into sel[j]. */
 int pfhip_op_lstm_cell(const float* G, float* c, float* h, const int32_t* lens, int t, float* sel, int H, int D, void* stream);
 
+/* ---- The kernels that start every request, one entry each, for operator tests (no model path calls these entries).  Index arrays
+ * named HOST are plain host arrays: the entry checks them, uploads them (or the descriptors built from them) with a synchronous copy
+ * and returns after the stream has drained.  Every entry returns hipErrorInvalidValue before anything is launched for a NULL buffer
+ * and for what its kernel assumes. */
+/* The fused fbank kernel (csrc/fbank.hip; 16 kHz, 25-ms frames at a 10-ms shift, 80 mel bins, the tables of the model / VAD / stream
+ * loaders) on B >= 1 utterances packed in pcm (pcm_samples samples on the DEVICE; f32 in [-1, 1) or 16-bit PCM standing for
+ * s / 32768.f, the two bit for bit equal).  HOST arrays: sample_off [B] (in samples; odd offsets allowed for s16), frame_off [B + 1]
+ * (prefix sums of nframes, frame_off[B] == total_frames), nframes [B].  Exactly one of two outputs:
+ *   fb_out: raw log-mel frames [total_frames][80] (B == 1 by launch_fbank_frames, otherwise by launch_fbank_frames_batch);
+ *   feats (feats_rows rows of 560) with row_off [B] (HOST), cmvn_mean / cmvn_istd [560] (device): LFR (m = 7, n = 6) and
+ *   (x + mean) * istd fused, utterance b's ceil(nframes[b] / 6) rows at row row_off[b].
+ * Refused: B < 1, frame_off that is not the prefix sum of nframes or does not end at total_frames, a frame outside pcm, a row outside
+ * feats, both outputs or neither. */
+int pfhip_op_fbank(const float* pcm, long long pcm_samples, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                   int total_frames, float* fb_out, float* feats, long long feats_rows, const int* row_off, const float* cmvn_mean,
+                   const float* cmvn_istd, void* stream);
+int pfhip_op_fbank_s16(const int16_t* pcm, long long pcm_samples, const int64_t* sample_off, const int* frame_off, const int* nframes, int B,
+                       int total_frames, float* fb_out, float* feats, long long feats_rows, const int* row_off, const float* cmvn_mean,
+                       const float* cmvn_istd, void* stream);
+/* LfrCmvn (fsmn-vad.cpp:198-238 == paraformer.cpp:421-461) for any (m, n, n_mels): fb [F][n_mels] -> out [ceil(F / n)][ldo], row i =
+ * frames [i n - (m - 1) / 2, + m) with the first / last frame replicated, (x + mean) * istd, columns m * n_mels .. ldo zeroed. */
+int pfhip_op_lfr_cmvn(const float* fb, int F, int m, int n, int n_mels, const float* mean, const float* istd, float* out, int ldo,
+                      void* stream);
+/* The same for B files whose frames lie in fb (fb_frames frames): file b is frames [frame_off[b], + nframes[b]) (HOST arrays), padded
+ * at its own edges, its rows at row row_off[b] of out (out_rows rows).  A file without frames writes nothing. */
+int pfhip_op_lfr_cmvn_packed(const float* fb, long long fb_frames, const int* frame_off, const int* nframes, const int* row_off, int B,
+                             int m, int n, int n_mels, const float* mean, const float* istd, float* out, int ldo, long long out_rows,
+                             void* stream);
+/* OnlineLfrCmvn (fsmn-vad-online.cpp:90-133) for n_ops connections (HOST arrays): operation k reads Tin[k] frames from frame fb_off[k]
+ * of fb (the splice cache first) and writes n_out[k] rows from row row_off[k]: row i = frames [i n, i n + m), the tail replicated
+ * with the last frame, no left padding.  An operation with rows needs Tin >= 1. */
+int pfhip_op_lfr_cmvn_online_batch(const float* fb, long long fb_frames, const int* fb_off, const int* Tin, const int* n_out,
+                                   const int* row_off, int n_ops, int m, int n, int n_mels, const float* mean, const float* istd,
+                                   float* out, int ldo, long long out_rows, void* stream);
+/* The streaming front end's OnlineLfrCmvn + x * scale + GetPosEmb (paraformer-online.cpp:196-268, 549-555; m = 7, n = 6, 80 bins) for
+ * n_ops connections (HOST arrays): row i of operation k = frames [6 i, 6 i + 7) of its T[k] frames at fb_off[k], the tail replicated,
+ * out row row_off[k] + i columns [0, 560) = ((x + mean) * istd) * scale + PE(pos0[k] + i + 1); inv_ts [280].  Columns 560 .. ldo are
+ * not written. */
+int pfhip_op_stream_lfr_batch(const float* fb, long long fb_frames, const int* fb_off, const int* T, const int* n_rows, const int* pos0,
+                              const int* row_off, int n_ops, const float* mean, const float* istd, float scale, const float* inv_ts,
+                              float* out, int ldo, long long out_rows, void* stream);
+/* n_ops row copies in one launch (HOST arrays): operation k writes nrows[k] rows of ldd[k] floats at dst + dst_off[k]: columns
+ * [0, ncols[k]) from src + src_off[k] with row stride lds[k] (0: its row 0 repeated), or zeros where src_off[k] < 0; columns
+ * ncols[k] .. ldd[k] zeroed.  dst_floats / src_floats: the floats behind dst / src, which every operation must stay inside. */
+int pfhip_op_rows_copy_batch(float* dst, long long dst_floats, const long long* dst_off, const float* src, long long src_floats,
+                             const long long* src_off, const int* ldd, const int* lds, const int* nrows, const int* ncols, int n_ops,
+                             void* stream);
+/* x0[row][0 .. D) = feats[row] * scale + PE(row_pos[row] + 1) (sin in columns < D / 2, cos above; inv_ts [D / 2]); columns D .. ldx
+ * zeroed.  D even. */
+int pfhip_op_embed(const float* feats, int D, float* x0, int ldx, const int* row_pos, int M, const float* inv_ts, float scale, void* stream);
+/* out[row][0 .. D) = table[id] * scale + PE(pos + 1), id = ids[row] CLAMPED to [0, vocab - 1], pos = pos_of_row ? pos_of_row[row] : row;
+ * columns D .. Dout zeroed, columns Dout .. ldo not written.  D even. */
+int pfhip_op_embed_gather(const int32_t* ids, const float* table, int vocab, int D, int Dout, float* out, int ldo, int N,
+                          const float* inv_ts, float scale, const int* pos_of_row, void* stream);
+/* out[row] = the first maximum over columns [0, ncls) of logits[row] (std::max_element with operator<: a NaN never replaces the
+ * running maximum, a NaN in column 0 is never replaced). */
+int pfhip_op_argmax_first(const float* logits, int ldl, int N, int ncls, int32_t* out, void* stream);
+/* Row gathers; D % 4 == 0 (rows move as float4s).  compact: emb[r] = stage[tok_row_src[r]]; gather_rows: out[r] = table[ids[r]];
+ * svs_prompt_rows: rows row_off[b] .. + 3 of feats (row stride ld) = rows prompt[4 b .. 4 b + 3] of E, for every b with len[b] >= 4
+ * (an utterance with fewer rows is left untouched).  Index arrays on the device; the indices themselves are the caller's to keep
+ * inside the tables. */
+int pfhip_op_compact(const float* stage, float* emb, const int* tok_row_src, int ML, int D, void* stream);
+int pfhip_op_gather_rows(const int32_t* ids, const float* table, int D, float* out, int R, void* stream);
+int pfhip_op_svs_prompt_rows(const float* E, int D, const int* prompt, const int* row_off, const int* len, int B, float* feats, int ld,
+                             void* stream);
+/* best[r] = logp[r][ids[r]]; lse[r] = log sum_c exp(logits[r][c]), c < V (a row of -inf gives -inf). */
+int pfhip_op_gather_best(const float* logp, int ld, const int32_t* ids, int M, float* best, void* stream);
+int pfhip_op_row_lse(const float* logits, int ld, int M, int V, float* lse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
