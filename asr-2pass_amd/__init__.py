@@ -57,6 +57,10 @@ ABI_SYMBOLS = [
     "pfhip_is_ctc", "pfhip_svs_lid", "pfhip_svs_forward", "pfhip_svs_forward_s16",
     # SenseVoiceSmall: CTC forced alignment of a token sequence against the last forward's rows
     "pfhip_svs_align",
+    # SenseVoiceSmall: the forward with the spans of its greedy tokens in the same call
+    "pfhip_svs_forward_spans", "pfhip_svs_forward_spans_s16",
+    # SenseVoiceSmall: concurrent callers merged into packed forwards
+    "pfhip_svs_set_batching",
 ]
 
 
@@ -273,6 +277,11 @@ def load_lib() -> ctypes.CDLL:
         lib.pfhip_svs_forward_s16.argtypes = lib.pfhip_svs_forward.argtypes
     if hasattr(lib, "pfhip_svs_align"):
         lib.pfhip_svs_align.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ctypes.POINTER(_SvsAlignOut)]
+    if hasattr(lib, "pfhip_svs_forward_spans"):
+        lib.pfhip_svs_forward_spans.argtypes = lib.pfhip_svs_forward.argtypes + [ctypes.POINTER(_SvsAlignOut)]
+        lib.pfhip_svs_forward_spans_s16.argtypes = lib.pfhip_svs_forward_spans.argtypes
+    if hasattr(lib, "pfhip_svs_set_batching"):
+        lib.pfhip_svs_set_batching.argtypes = [vp, ci, ci]
     lib.pfhip_profile_enable.argtypes = [vp, ci]
     lib.pfhip_profile_read.argtypes = [vp, ctypes.POINTER(_Profile), ci]
     # 16-bit PCM in: the argument lists of the f32 siblings
@@ -919,6 +928,18 @@ class SenseVoiceHip:
     def set_inflight(self, n):
         _check(self._lib, self._lib.pfhip_set_inflight(self._h, int(n)))
 
+    def set_batching(self, wait_us, max_utterances=32):
+        """Merge concurrent forward() callers into one packed device batch (pfhip_svs_set_batching); wait_us = 0: off."""
+        _check(self._lib, self._lib.pfhip_svs_set_batching(self._h, int(wait_us), int(max_utterances)))
+
+    def inflight_stats(self):
+        """Per execution slot: dict(device, context, forwards, calls, utterances) (pfhip_inflight_stats)."""
+        arr = (_SlotStats * 64)()
+        n = ctypes.c_int(0)
+        _check(self._lib, self._lib.pfhip_inflight_stats(self._h, arr, 64, ctypes.byref(n)))
+        return [dict(device=a.device, context=a.context, forwards=a.forwards, calls=a.calls, utterances=a.utterances)
+                for a in arr[:n.value]]
+
     def warm_up(self, batch, n_samples):
         _check(self._lib, self._lib.pfhip_warm_up(self._h, int(batch), int(n_samples)))
 
@@ -928,8 +949,9 @@ class SenseVoiceHip:
         T = -(-frames // int(self.cfg.get("lfr_n", 6)))
         return T + 4 if T > 0 else 0
 
-    def forward(self, din, lang="auto", itn=True, lid=None, textnorm=None, want_logp=False):
-        """One packed forward.  lang / itn: a value for all utterances or one per utterance (svs_lang strings, booleans); lid /
+    def forward(self, din, lang="auto", itn=True, lid=None, textnorm=None, want_logp=False, want_spans=False, max_tokens=None):
+        """One packed forward.  want_spans: pfhip_svs_forward_spans — the result also holds span_begin / span_end / span_logp
+        (per-utterance arrays over the tokens behind the four tags, as align() returns them) and span_score [B].  lang / itn: a value for all utterances or one per utterance (svs_lang strings, booleans); lid /
         textnorm override them with prompt ids.  Returns dict(token_num [B], ids / tok_frame / tok_logp: per-utterance arrays (the four
         leading tag ids included), frame_len [B], frame_ids / frame_logp: per-utterance arrays over its rows, logp: per-utterance
         [rows, vocab] arrays when want_logp)."""
@@ -941,6 +963,8 @@ class SenseVoiceHip:
         ns = np.array([len(b) for b in bufs], np.int32)
         rows = [self.rows_of(int(n)) for n in ns]
         M, cap = int(sum(rows)), max(rows + [1])
+        if max_tokens is not None:
+            cap = int(max_tokens)                       # the caller's own bound: PFHIP_ERR_CAPACITY below the longest kept sequence
         V = int(self.cfg["vocab"])
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data for b in bufs])
         lid_a, tn_a = np.array(lid, np.int32), np.array(textnorm, np.int32)
@@ -956,9 +980,20 @@ class SenseVoiceHip:
         out = _SvsOut(ids.ctypes.data_as(i32p), token_num.ctypes.data_as(i32p), cap, tok_frame.ctypes.data_as(i32p),
                       tok_logp.ctypes.data_as(f32p), frame_ids.ctypes.data_as(i32p), frame_logp.ctypes.data_as(f32p),
                       frame_len.ctypes.data_as(i32p), logp.ctypes.data_as(f32p) if want_logp else None, logp.size if want_logp else 0)
-        fn = self._lib.pfhip_svs_forward_s16 if s16 else self._lib.pfhip_svs_forward
-        _check(self._lib, fn(self._h, ptrs, ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, lid_a.ctypes.data_as(i32p),
-                             tn_a.ctypes.data_as(i32p), ctypes.byref(out)))
+        args = [self._h, ptrs, ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, lid_a.ctypes.data_as(i32p), tn_a.ctypes.data_as(i32p),
+                ctypes.byref(out)]
+        if want_spans:
+            sp_begin = np.full((B, cap), -7, np.int32)
+            sp_end = np.full((B, cap), -7, np.int32)
+            sp_logp = np.full((B, cap), np.nan, np.float32)
+            sp_score = np.full(B, np.nan, np.float32)
+            sp = _SvsAlignOut(sp_begin.ctypes.data_as(i32p), sp_end.ctypes.data_as(i32p), sp_logp.ctypes.data_as(f32p),
+                              sp_score.ctypes.data_as(f32p), cap)
+            fn = self._lib.pfhip_svs_forward_spans_s16 if s16 else self._lib.pfhip_svs_forward_spans
+            args.append(ctypes.byref(sp))
+        else:
+            fn = self._lib.pfhip_svs_forward_s16 if s16 else self._lib.pfhip_svs_forward
+        _check(self._lib, fn(*args))
         assert frame_len.tolist() == rows, (frame_len.tolist(), rows)
         offs = np.concatenate([[0], np.cumsum(frame_len)]).astype(np.int64)
         cut = lambda a: [a[offs[b]:offs[b + 1]] for b in range(B)]
@@ -967,6 +1002,10 @@ class SenseVoiceHip:
                    frame_ids=cut(frame_ids), frame_logp=cut(frame_logp))
         if want_logp:
             res["logp"] = cut(logp)
+        if want_spans:
+            nt = [max(int(token_num[b]) - 4, 0) for b in range(B)]
+            res.update(span_begin=[sp_begin[b, :nt[b]] for b in range(B)], span_end=[sp_end[b, :nt[b]] for b in range(B)],
+                       span_logp=[sp_logp[b, :nt[b]] for b in range(B)], span_score=sp_score)
         return res
 
     def align(self, tokens, max_tokens=None):
@@ -995,7 +1034,8 @@ class SenseVoiceHip:
         return buf[:n.value]
 
     def debug_poke(self, what, value=0):
-        """pfhip_debug_poke: "ctc_unfused", "ctc_unfused_forwards", "ctc_head_chunks", "range_flag", "range_fallbacks", "plane_forwards"."""
+        """pfhip_debug_poke: "ctc_unfused", "ctc_unfused_forwards", "ctc_head_chunks", "range_flag", "range_fallbacks", "plane_forwards",
+        "svs_span_cap", "svs_unfused_rows", "svs_forward_calls"."""
         return int(self._lib.pfhip_debug_poke(self._h, what.encode(), int(value)))
 
 

@@ -22,6 +22,14 @@
 //     walks back over the N frames and writes the spans.  The recurrence (pfhip_ops.h states it in full): the largest of stay / step 1 /
 //     step 2 (step 2 only into a label state whose label differs from the previous label), a later candidate winning only when strictly
 //     greater, then ONE fp32 add of the emission (the file is built with -ffp-contract=off; __fadd_rn says it again).
+//
+// (c) ctc_greedy_plan_kernel.  What lets (a) and (b) run behind the collapse with no host round trip: from the collapse's token_num
+//     [B] (device) and the speech rows N_b (host-known, uploaded with the forward's metadata) it writes n_lab, lab_off — the labels are
+//     the collapse's own id buffer [B][maxT] behind the four tags, nothing is copied — and e_off, the exclusive int64 prefix sum of
+//     N_b (n_lab + 1).  ONE workgroup of 256 threads, b strided over it in chunks of 256: a Hillis-Steele scan of the chunk in LDS
+//     (8 steps, two barriers each) and a running carry every thread keeps in a register.  The trip counts depend on B alone: no
+//     spin-wait, no other workgroup, no atomics.  An utterance whose E_b would end beyond cap_floats (what the host allocated from the
+//     bound n_lab <= N_b) gets n_lab = -1, which (a) and (b) leave untouched and (b) answers as infeasible.
 #include "kernels.h"
 #include "launch_common.h"
 
@@ -35,6 +43,7 @@ constexpr int kEK = 32;                          // K-step
 constexpr int kEs = kET + 4;                     // padded LDS row (floats): 16-byte aligned float4 reads
 constexpr int kEmitBlocks = 16;                  // workgroups per utterance (32 x 30 s: 24 tiles each)
 constexpr int kVitThreads = 256;
+constexpr int kPlanThreads = 256;
 
 __device__ __forceinline__ int label_id(const int32_t* __restrict__ lab, int col, int L, int blank, int V) {
   // column 0: the blank; column j: label j.  Columns past the last are clamped onto it (their results are not stored).
@@ -48,16 +57,19 @@ __global__ __launch_bounds__(256) void ctc_emissions_kernel(const float* __restr
                                                             const int* __restrict__ row_off, const int* __restrict__ len,
                                                             const int* __restrict__ lab_off, const int* __restrict__ n_lab,
                                                             const int32_t* __restrict__ labels, const long long* __restrict__ e_off, int K, int V,
-                                                            int blank, float* __restrict__ E) {
+                                                            int blank, float* __restrict__ E, long long e_floats) {
   __shared__ __attribute__((aligned(16))) float Xs[kEK][kEs];
   __shared__ __attribute__((aligned(16))) float Ws[kEK][kEs];
   const int b = blockIdx.y;
   const int N = len[b], L = n_lab[b];
   if (N <= 0 || L < 0) return;                                       // uniform: the whole workgroup leaves
   const int C = L + 1;
+  const long long eo = e_off[b];
+  // e_floats >= 0 (sizes planned on the device, ctc_greedy_plan_kernel): an E_b that does not lie inside E is not written
+  if (e_floats >= 0 && (eo < 0 || eo + (long long)N * C > e_floats)) return;      // uniform
   const int32_t* lab = labels + lab_off[b];
   const int r0 = row_off[b];
-  float* Eb = E + e_off[b];
+  float* Eb = E + eo;
   const int tiles_n = (C + kET - 1) / kET, n_tiles = (N + kET - 1) / kET * tiles_n;
   const int tid = threadIdx.x;
   const int srow = tid >> 2, sq = tid & 3;                           // staging: operand row srow, k = 4 sq .. + 3 and 16 + 4 sq .. + 3
@@ -192,16 +204,67 @@ __global__ __launch_bounds__(kVitThreads) void ctc_viterbi_kernel(const float* _
   close();
 }
 
+
+__global__ __launch_bounds__(kPlanThreads) void ctc_greedy_plan_kernel(const int32_t* __restrict__ token_num, const int* __restrict__ speech_len,
+                                                                       int B, int maxT, long long cap_floats, int* __restrict__ n_lab,
+                                                                       int* __restrict__ lab_off, long long* __restrict__ e_off,
+                                                                       long long* __restrict__ total) {
+  __shared__ long long sh[kPlanThreads];
+  const int tid = threadIdx.x;
+  long long carry = 0;                                               // the floats of every utterance before this chunk
+  for (int b0 = 0; b0 < B; b0 += kPlanThreads) {                     // uniform trip count
+    const int b = b0 + tid;
+    int L = 0;
+    long long size = 0;
+    if (b < B) {
+      const int tn = token_num[b], N = speech_len[b];
+      L = tn > 4 ? tn - 4 : 0;
+      if (tn > maxT || N < 0) L = -1;                                // counts no collapse over maxT rows leaves: labels would lie outside ids[b]
+      else size = (long long)N * (L + 1);
+    }
+    sh[tid] = size;
+    __syncthreads();
+    for (int off = 1; off < kPlanThreads; off <<= 1) {               // inclusive scan of the chunk
+      const long long add = tid >= off ? sh[tid - off] : 0;
+      __syncthreads();
+      sh[tid] += add;
+      __syncthreads();
+    }
+    const long long incl = sh[tid], chunk = sh[kPlanThreads - 1];
+    if (b < B) {
+      const long long eo = carry + incl - size;
+      if (L >= 0 && (eo < 0 || eo + size < eo || eo + size > cap_floats)) L = -1;      // E_b would end beyond what is allocated
+      n_lab[b] = L;
+      lab_off[b] = b * maxT + 4;
+      e_off[b] = eo;
+    }
+    carry += chunk;
+    __syncthreads();                                                 // sh is rewritten by the next chunk
+  }
+  if (tid == 0 && total) *total = carry;
+}
+
 }  // namespace
 
 bool launch_ctc_emissions(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* lse, const int* row_off,
                           const int* len, const int* lab_off, const int* n_lab, const int32_t* labels, const long long* e_off, int B, int K,
-                          int V, int blank, float* E, hipStream_t s) {
+                          int V, int blank, float* E, hipStream_t s, long long e_floats) {
   if (B < 0 || B > 65535 || V <= 0 || K < 32 || K % 32 || ldx < K || ldx % 4 || ldw < K || ldw % 4 || blank < 0 || blank >= V) return false;
   if (B == 0) return true;
   if (!X || !W || !bias || !lse || !row_off || !len || !lab_off || !n_lab || !labels || !e_off || !E) return false;
   hipLaunchKernelGGL(ctc_emissions_kernel, dim3(kEmitBlocks, B), dim3(256), 0, s, X, ldx, W, ldw, bias, lse, row_off, len, lab_off, n_lab,
-                     labels, e_off, K, V, blank, E);
+                     labels, e_off, K, V, blank, E, e_floats);
+  return true;
+}
+
+bool launch_ctc_greedy_plan(const int32_t* token_num, const int* speech_len, int B, int maxT, long long cap_floats, int* n_lab, int* lab_off,
+                            long long* e_off, long long* total, hipStream_t s) {
+  // lab_off[b] = b maxT + 4 is an int: the id buffer [B][maxT] must be indexable by one
+  if (B < 0 || B > 65535 || maxT < 0 || cap_floats < 0 || (long long)B * maxT + 4 > 0x7fffffffLL) return false;
+  if (B == 0) return true;
+  if (!token_num || !speech_len || !n_lab || !lab_off || !e_off) return false;
+  hipLaunchKernelGGL(ctc_greedy_plan_kernel, dim3(1), dim3(kPlanThreads), 0, s, token_num, speech_len, B, maxT, cap_floats, n_lab, lab_off,
+                     e_off, total);
   return true;
 }
 

@@ -156,12 +156,20 @@ pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value) {
     for (pfhip_model* r : m->replicas) { visit(r, false); for (pfhip_model* cx : r->contexts) visit(cx, false); }
     return set ? PFHIP_OK : (pfhip_status)n;
   }
+  if (std::string(what) == "svs_span_cap") {          // pfhip_svs_forward_spans: a small stand-in for PFHIP_SVS_SPAN_MAX_FLOATS, on every context
+    m->debug_span_cap = value;
+    for (pfhip_model* cx : m->contexts) { std::lock_guard<std::mutex> xl(cx->mu); cx->debug_span_cap = value; }
+    return PFHIP_OK;
+  }
   if (std::string(what) == "ctc_head_chunks") {
     // (looked up among this handle's contexts, never dereferenced before it is found there: the note may be of a handle since destroyed)
     for (pfhip_model* cx : m->contexts)
       if (cx == last_replica()) return (pfhip_status)cx->svs_head_chunks;
     return (pfhip_status)m->svs_head_chunks;
   }
+  // the rows the unfused head chunks covered in the forward that served the calling thread's last pfhip_svs_forward (svs_api.cpp)
+  if (std::string(what) == "svs_unfused_rows") return (pfhip_status)svs_last_unfused_rows();
+  if (std::string(what) == "svs_forward_calls") return (pfhip_status)svs_last_forward_calls();      // ... and the callers that forward served
   if (std::string(what) == "range_flag") { m->debug_range_flag = value; return PFHIP_OK; }    // the next forward starts with its range flag raised
   if (std::string(what) == "range_fallbacks") {       // read-out: forwards redone on the exact kernels, over every context of the handle
     long long n = m->range_fallbacks;

@@ -49,7 +49,7 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
   // ---- metadata: one pinned staging buffer, one H2D copy ---------------------------------------------
   const bool svs = c.svs && !feats_only;
   if (svs && (int)m->svs_prompt.size() != 4 * B) return fail(PFHIP_ERR_ARG, "a SenseVoice model is run through pfhip_svs_forward");
-  const size_t n_ints = (size_t)2 * B /*sample_off as int64*/ + (B + 1) + 3 * (size_t)B + 2 * (size_t)M + 8 + (svs ? 5 * (size_t)B : 0);
+  const size_t n_ints = (size_t)2 * B /*sample_off as int64*/ + (B + 1) + 3 * (size_t)B + 2 * (size_t)M + 8 + (svs ? 6 * (size_t)B : 0);
   HIP_TRY(m->h_meta.ensure(n_ints * 4));
   HIP_TRY(m->meta.ensure(n_ints * 4));
   {
@@ -65,6 +65,10 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
       for (int b = 0; b < B; ++b) hm[o + b] = m->row_off[b] + 4;
       m->m_feat_off = dm + o; o += B;
       std::memcpy(hm + o, m->svs_prompt.data(), 4 * 4 * (size_t)B); m->m_prompt = dm + o; o += 4 * (size_t)B;
+      // the speech rows N_b the greedy tokens are aligned against (heads.cpp), 0 for an utterance nobody wants spans of
+      const bool spans = (int)m->svs_span_want.size() == B;
+      for (int b = 0; b < B; ++b) hm[o + b] = spans && m->svs_span_want[b] && m->T[b] > 4 ? m->T[b] - 4 : 0;
+      m->m_speech_len = dm + o; o += B;
     }
     if (o & 1) ++o;
     m->m_row_pos = dm + o;

@@ -229,7 +229,15 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
   const ModelWeights& w = *m->weights;
   const Config& c = w.cfg;
   const int d = c.d_model, B = m->B, M = m->M, V = c.vocab, maxT = m->maxT;
-  const size_t bt = (size_t)B * maxT, n_words = (size_t)B + 3 * bt + 2 * (size_t)M;
+  const size_t bt = (size_t)B * maxT, n_base = (size_t)B + 3 * bt + 2 * (size_t)M;
+  // pfhip_svs_forward_spans: the spans of the greedy tokens sit behind the forward's results, so they cross in the same copy.
+  // Slots per utterance: no utterance keeps more tokens behind its tags than it has speech rows, and the trellis kernel takes no more
+  // than its LDS rows hold (an utterance with more labels is answered as infeasible by the kernel's own check).
+  const bool spans = (int)m->svs_span_want.size() == B;
+  const int mt = spans ? std::min(maxT - 4, pfhip::ctc_align_max_tokens()) : 0;
+  const size_t sbt = (size_t)B * mt, n_words = n_base + (mt > 0 ? 3 * sbt + B : 0);
+  m->svs_span_mt = mt > 0 ? mt : 0;
+  m->svs_span_word = n_base;
   HIP_TRY(m->counts.ensure(n_words * 4));
   HIP_TRY(m->h_counts.ensure(n_words * 4));
   int32_t* dn = m->counts.i();
@@ -237,38 +245,98 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
   float *d_logp = reinterpret_cast<float*>(dn + B + 2 * bt), *d_flp = reinterpret_cast<float*>(d_fid + M);
   const float* X = m->x.f();
   HIP_TRY(m->svs_lse.ensure((size_t)M * 4));                   // the rows' log-sum-exp, kept for pfhip_svs_align
-  const bool unfused = pfhip::launch_ctx().exact || m->debug_ctc_unfused || m->svs_logp_host;
+  // merged callers (svs_api.cpp): per utterance the host buffer that takes its full log-prob rows, or null
+  const bool per_utt = (int)m->svs_logp_rows.size() == B;
+  const bool all_unfused = pfhip::launch_ctx().exact || m->debug_ctc_unfused || m->svs_logp_host;
   m->debug_ctc_unfused = 0;
   m->svs_head_chunks = 0;
-  if (unfused) {
-    ++m->svs_unfused_forwards;
-    const int rows_max = std::min(kSvsChunkRows, round_up(M, pfhip::kTileM));
-    HIP_TRY(m->svs_logits.ensure((size_t)rows_max * w.vocab_pad * 4));
-    HIP_TRY(m->svs_logp.ensure((size_t)rows_max * V * 4));
-    for (int r0 = 0; r0 < M; r0 += kSvsChunkRows) {
-      const int rows = std::min(kSvsChunkRows, M - r0);
-      gemm(m, s, X + (size_t)r0 * d, d, w.ctc, V, d, d, m->svs_logits.f(), w.vocab_pad, nullptr, 0, nullptr, 0, rows, false);
+  m->svs_unfused_rows = 0;
+  // GEMM + log-softmax + row log-sum-exp over rows [r0, r0 + n) in chunks of kSvsChunkRows; the rows' ids, best log-probs and
+  // log-sum-exp are (over)written, the full rows go to host_dst where one is given
+  // (their scratch is sized ONCE, before the first launch, for the longest range this head will run: no reallocation — a
+  // device-wide synchronise — between the launches of a merged batch)
+  {
+    int longest = 0;
+    if (all_unfused && !per_utt) longest = M;
+    for (int b = 0; per_utt && b < B; ++b)
+      if (all_unfused || m->svs_logp_rows[b]) longest = std::max(longest, m->T[b]);
+    if (longest > 0) {
+      const int rows_max = std::min(kSvsChunkRows, round_up(longest, pfhip::kTileM));
+      HIP_TRY(m->svs_logits.ensure((size_t)rows_max * w.vocab_pad * 4));
+      HIP_TRY(m->svs_logp.ensure((size_t)rows_max * V * 4));
+    }
+  }
+  auto unfused_rows = [&](int r0, int n, float* host_dst) -> pfhip_status {
+    for (int c0 = 0; c0 < n; c0 += kSvsChunkRows) {
+      const int rows = std::min(kSvsChunkRows, n - c0), q0 = r0 + c0;
+      gemm(m, s, X + (size_t)q0 * d, d, w.ctc, V, d, d, m->svs_logits.f(), w.vocab_pad, nullptr, 0, nullptr, 0, rows, false);
       {
         Scope sc(m, s, K_HEAD, 0, 12.0 * rows * V);
-        pfhip::launch_logsoftmax_argmax(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_logp.f(), d_fid + r0, s, m->d_range_flag);
-        pfhip::launch_gather_best(m->svs_logp.f(), V, d_fid + r0, rows, d_flp + r0, s);
-        pfhip::launch_row_lse(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_lse.f() + r0, s);
+        pfhip::launch_logsoftmax_argmax(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_logp.f(), d_fid + q0, s, m->d_range_flag);
+        pfhip::launch_gather_best(m->svs_logp.f(), V, d_fid + q0, rows, d_flp + q0, s);
+        pfhip::launch_row_lse(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_lse.f() + q0, s);
       }
-      if (m->svs_logp_host)
-        HIP_TRY(hipMemcpyAsync(m->svs_logp_host + (size_t)r0 * V, m->svs_logp.p, (size_t)rows * V * 4, hipMemcpyDeviceToHost, s));
+      if (host_dst) HIP_TRY(hipMemcpyAsync(host_dst + (size_t)c0 * V, m->svs_logp.p, (size_t)rows * V * 4, hipMemcpyDeviceToHost, s));
       ++m->svs_head_chunks;
+      m->svs_unfused_rows += rows;
     }
+    return PFHIP_OK;
+  };
+  if (all_unfused) ++m->svs_unfused_forwards;
+  if (all_unfused && !per_utt) {
+    const pfhip_status us = unfused_rows(0, M, m->svs_logp_host);
+    if (us) return us;
   } else {
-    const size_t ws = pfhip::ctc_head_workspace_bytes(M, V);
-    HIP_TRY(m->svs_ws.ensure(ws));
-    Scope sc(m, s, K_GEMM, 2.0 * M * (double)V * d, 4.0 * ((double)M * d + (double)V * d) + 12.0 * M * (w.vocab_pad / pfhip::kTileN));
-    if (!pfhip::launch_ctc_head(X, d, w.ctc.w, d, w.ctc.b, w.ctc.scale, M, V, d, d_fid, d_flp, m->svs_lse.f(), m->svs_ws.p, ws, s, m->d_range_flag))
-      return fail(PFHIP_ERR_UNSUPPORTED, "CTC head: d_model must be a multiple of 32");
+    if (!all_unfused) {
+      const size_t ws = pfhip::ctc_head_workspace_bytes(M, V);
+      HIP_TRY(m->svs_ws.ensure(ws));
+      Scope sc(m, s, K_GEMM, 2.0 * M * (double)V * d, 4.0 * ((double)M * d + (double)V * d) + 12.0 * M * (w.vocab_pad / pfhip::kTileN));
+      if (!pfhip::launch_ctc_head(X, d, w.ctc.w, d, w.ctc.b, w.ctc.scale, M, V, d, d_fid, d_flp, m->svs_lse.f(), m->svs_ws.p, ws, s, m->d_range_flag))
+        return fail(PFHIP_ERR_UNSUPPORTED, "CTC head: d_model must be a multiple of 32");
+    }
+    // A merged batch: the fused head has run over all rows; the unfused chunks run over the row ranges of the utterances whose
+    // caller asked for log-prob rows, and only those, so that each caller gets what it would get alone.  (The exact re-run and the
+    // debug switch keep sending every row through the unfused head.)
+    for (int b = 0; per_utt && b < B; ++b) {
+      if (m->T[b] == 0 || (!all_unfused && !m->svs_logp_rows[b])) continue;
+      const pfhip_status us = unfused_rows(m->row_off[b], m->T[b], m->svs_logp_rows[b]);
+      if (us) return us;
+    }
   }
   {
     Scope sc(m, s, K_CIF, 0, 20.0 * M);
     if (!pfhip::launch_ctc_collapse(d_fid, d_flp, m->m_row_off, m->m_len, B, c.blank_id, maxT, d_ids, d_frames, d_logp, dn, s))
       return fail(PFHIP_ERR_ARG, "CTC collapse refused its arguments");
+  }
+  if (mt > 0) {
+    // The greedy alignment behind the collapse, with no host round trip: the plan kernel turns the collapse's token_num into n_lab /
+    // lab_off / e_off on the device (the labels are d_ids behind the four tags), then the two kernels of pfhip_svs_align on the same
+    // rows.  E and the back-pointers are sized from what the host knows: n_lab[b] <= N_b, a kept token needs a frame, so
+    // sum_b N_b (N_b + 1) floats, capped; an utterance that would end beyond the cap is refused by the plan kernel (n_lab -1) and comes
+    // back with spans -1 and score -inf.  (No profiling Scope, as in pfhip_svs_align.)
+    long long cap = 0;
+    for (int b = 0; b < B; ++b) {
+      const long long N = m->svs_span_want[b] && m->T[b] > 4 ? m->T[b] - 4 : 0;
+      cap += N * (N + 1);
+    }
+    cap = std::min<long long>(cap, m->debug_span_cap > 0 ? m->debug_span_cap : (long long)PFHIP_SVS_SPAN_MAX_FLOATS);
+    const size_t ws = pfhip::ctc_align_workspace_bytes((size_t)cap);
+    HIP_TRY(m->al_E.ensure(std::max<size_t>((size_t)cap, 1) * 4));
+    HIP_TRY(m->al_ws.ensure(std::max<size_t>(ws, 1)));
+    const size_t plan_i32 = (2 * (size_t)B + 1) & ~(size_t)1;
+    HIP_TRY(m->al_plan.ensure(plan_i32 * 4 + ((size_t)B + 1) * 8));
+    int *d_nlab = m->al_plan.i(), *d_laboff = d_nlab + B;
+    long long* d_eoff = reinterpret_cast<long long*>(d_nlab + plan_i32);
+    int32_t *d_begin = dn + n_base, *d_end = d_begin + sbt;
+    float *d_slogp = reinterpret_cast<float*>(d_end + sbt), *d_score = d_slogp + sbt;
+    if (!pfhip::launch_ctc_greedy_plan(dn, m->m_speech_len, B, maxT, cap, d_nlab, d_laboff, d_eoff, d_eoff + B, s))
+      return fail(PFHIP_ERR_ARG, "CTC greedy plan refused its arguments");
+    if (!pfhip::launch_ctc_emissions(X, d, w.ctc.w, d, w.ctc.b, m->svs_lse.f(), m->m_feat_off, m->m_speech_len, d_laboff, d_nlab, d_ids, d_eoff,
+                                     B, d, V, c.blank_id, m->al_E.f(), s, cap))
+      return fail(PFHIP_ERR_UNSUPPORTED, "CTC emissions: d_model must be a multiple of 32");
+    if (!pfhip::launch_ctc_align(m->al_E.f(), d_eoff, (size_t)cap, m->m_speech_len, d_nlab, d_ids, d_laboff, B, mt, d_begin, d_end, d_slogp,
+                                 d_score, m->al_ws.p, ws, s))
+      return fail(PFHIP_ERR_ARG, "CTC alignment refused its arguments");
   }
   HIP_TRY(hipMemcpyAsync(m->h_counts.p, m->counts.p, n_words * 4, hipMemcpyDeviceToHost, s));
   {

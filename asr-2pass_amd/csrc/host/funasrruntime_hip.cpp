@@ -353,6 +353,8 @@ namespace {
 
 struct TpassStreamHip {               // funasr::TpassStream (tpass-stream.cpp): the shared models
   funasr::ParaformerHip asr;          // ONE object holds the offline session and the online encoder / decoder (paraformer.cpp:134-154)
+  std::unique_ptr<funasr::SenseVoiceSmallHip> svs;      // MODEL_DIR names MODEL_SVS (tpass-stream.cpp:44-50): this one holds both, `asr` stays unloaded
+  std::atomic<bool> svs_ctc_stamps{false};              // FunTpassSetCtcStamps
   int detail_k = 0;                   // FunTpassSetNbest: for the streams of later FunTpassOnlineInit calls
   std::unique_ptr<funasr::FsmnVadHip> vad;
   std::unique_ptr<funasr::PuncModelHipBase> punc_online;      // TpassStream::punc_online_handle (tpass-stream.cpp:100-135)
@@ -386,6 +388,15 @@ FUNASR_HANDLE FunTpassInit(std::map<std::string, std::string>& model_path, int t
   const std::string en_model_path = PathAppend(odir, q ? QUANT_ENCODER_NAME : ENCODER_NAME);
   const std::string de_model_path = PathAppend(odir, q ? QUANT_DECODER_NAME : DECODER_NAME);
   auto tokens_or_none = [](const std::string& p) { return FileExists(p) ? p : std::string(); };
+  if (mdir.find(MODEL_SVS) != std::string::npos) {                                                   // :44-50: the directory's name picks the class
+    ts->svs.reset(new funasr::SenseVoiceSmallHip());
+    ts->svs->InitAsr(am_model_path, en_model_path, de_model_path, PathAppend(odir, AM_CMVN_NAME), PathAppend(mdir, AM_CONFIG_NAME),
+                     tokens_or_none(PathAppend(mdir, TOKEN_PATH)), tokens_or_none(PathAppend(odir, TOKEN_PATH)), thread_num,
+                     PathAppend(odir, AM_CONFIG_NAME));                                              // :76-77, exits on failure
+    if (model_path.count(LM_DIR) && !model_path[LM_DIR].empty())                                     // :84-98: a call that returns
+      ts->svs->InitLm(PathAppend(model_path[LM_DIR], LM_FST_RES), PathAppend(model_path[LM_DIR], LM_CONFIG_NAME),
+                      PathAppend(model_path[LM_DIR], LEX_PATH), "");
+  } else
   ts->asr.InitAsr(am_model_path, en_model_path, de_model_path, PathAppend(odir, AM_CMVN_NAME), PathAppend(mdir, AM_CONFIG_NAME),
                   tokens_or_none(PathAppend(mdir, TOKEN_PATH)), tokens_or_none(PathAppend(odir, TOKEN_PATH)), thread_num,
                   PathAppend(odir, AM_CONFIG_NAME));                                                 // :76-77, exits on failure
@@ -412,7 +423,8 @@ FUNASR_HANDLE FunTpassOnlineInit(FUNASR_HANDLE tpass_handle, std::vector<int> ch
   auto os = std::make_unique<TpassOnlineStreamHip>();
   os->shared = ts;
   os->vad_online.reset(new funasr::FsmnVadOnlineHip(ts->vad.get()));
-  os->asr_online.reset(new funasr::ParaformerOnlineHip(&ts->asr, chunk_size));
+  if (ts->svs) os->asr_online.reset(new funasr::ParaformerOnlineHip(ts->svs.get(), chunk_size, MODEL_SVS));      // tpass-online-stream.cpp:14-15
+  else os->asr_online.reset(new funasr::ParaformerOnlineHip(&ts->asr, chunk_size));
   if (!os->asr_online->ok() || !os->vad_online->ok()) {
     std::fprintf(stderr, "FunTpassOnlineInit: %s\n", pfhip_last_error());
     return nullptr;
@@ -432,10 +444,15 @@ void FunTpassSetCifStamps(FUNASR_HANDLE tpass_handle, int mode) {
   if (tpass_handle) static_cast<TpassStreamHip*>(tpass_handle)->asr.SetCifTimestamps(mode);
 }
 
+void FunTpassSetCtcStamps(FUNASR_HANDLE tpass_handle, int on) {
+  TpassStreamHip* ts = static_cast<TpassStreamHip*>(tpass_handle);
+  if (ts && ts->svs) ts->svs_ctc_stamps.store(on != 0);
+}
+
 FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_handle, const char* sz_buf, int n_len,
                                   std::vector<std::vector<std::string>>& punc_cache, bool input_finished, int sampling_rate,
                                   std::string wav_format, ASR_TYPE mode, const std::vector<std::vector<float>>& hw_emb, bool itn,
-                                  int vad_tail_sil, int vad_max_len, FUNASR_DEC_HANDLE dec_handle) {
+                                  int vad_tail_sil, int vad_max_len, FUNASR_DEC_HANDLE dec_handle, std::string svs_lang, bool svs_itn) {
   (void)itn; (void)dec_handle;
   TpassStreamHip* ts = static_cast<TpassStreamHip*>(handle);
   TpassOnlineStreamHip* os = static_cast<TpassOnlineStreamHip*>(online_handle);
@@ -446,7 +463,7 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
     if (!os->audio.LoadPcmwavOnline(sz_buf, n_len)) return nullptr;
   } else {                  // LoadPcmwavOnline with WavResample of THIS buffer alone (audio.cpp:821-857): no state across calls
     std::vector<float> pcm;
-    if (!LoadPcm(ts->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
+    if (!LoadPcm(ts->svs ? ts->svs->Handle() : ts->asr.Handle(), sz_buf, n_len, sampling_rate, pcm)) {
       std::fprintf(stderr, "FunTpassInferBuffer: %s\n", pfhip_last_error());
       return nullptr;
     }
@@ -490,6 +507,29 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
     float* buff[1] = {frame.data.data()};
     int len[1] = {(int)frame.data.size()};
     const int16_t* buff16[1] = {frame.pcm16.data()};
+    if (ts->svs) {                               // funasrruntime.cpp:583-587, :609-631: the model type routes the second pass
+      funasr::SenseVoiceSmallHip* svs = ts->svs.get();
+      const std::vector<std::string> texts = frame.pcm16.size() == frame.data.size() && !frame.data.empty()
+                                                 ? svs->ForwardPcm16(buff16, len, true, svs_lang, svs_itn, nullptr, 1)
+                                                 : svs->Forward(buff, len, true, svs_lang, svs_itn, nullptr, 1);
+      const std::string text = texts.empty() ? "" : texts[0];
+      if (text.empty()) continue;
+      res->seg_ids.push_back(svs->LastTokenIds()[0]);
+      res->segs.emplace_back(frame.global_start, frame.global_end);      // ms on the connection's time axis
+      // FunTpassSetCtcStamps: the greedy tokens' spans (60-ms rows) plus the segment's start; a refused alignment leaves no pairs
+      if (ts->svs_ctc_stamps.load() && svs->AlignGreedyTokens() && !svs->LastTokenStampsMs().empty()) {
+        const std::vector<float>& ms = svs->LastTokenStampsMs()[0];
+        for (size_t i = 0; i + 1 < ms.size(); i += 2)
+          cur_stamp += "[" + std::to_string((int)ms[i] + frame.global_start) + "," + std::to_string((int)ms[i + 1] + frame.global_start) + "],";
+        if (cur_stamp != "[") {
+          cur_stamp.erase(cur_stamp.size() - 1);
+          res->stamp += cur_stamp + "]";
+          cur_stamp = "[";
+        }
+      }
+      res->tpass_msg = text;                     // no punctuation and no ITN for this model (:609-631)
+      continue;
+    }
     const std::vector<std::string> msgs = frame.pcm16.size() == frame.data.size() && !frame.data.empty()
                                               ? ts->asr.ForwardPcm16(buff16, len, true, hw_emb, nullptr, 1)
                                               : ts->asr.Forward(buff, len, true, hw_emb, nullptr, 1);

@@ -24,6 +24,10 @@
 #define ONLINE_MODEL_DIR "online-model-dir"
 #define VAD_DIR "vad-dir"
 #define PUNC_DIR "punc-dir"
+#define LM_DIR "lm-dir"                // com-define.h:18; its files: TLG.fst, config.yaml, lexicon.txt (:70, :86-87)
+#define LM_FST_RES "TLG.fst"
+#define LM_CONFIG_NAME "config.yaml"
+#define LEX_PATH "lexicon.txt"
 #define QUANTIZE "quantize"
 #define VAD_QUANT "vad-quant"
 #define PUNC_QUANT "punc-quant"
@@ -90,7 +94,8 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
                                   std::vector<std::vector<std::string>>& punc_cache, bool input_finished = true,
                                   int sampling_rate = 16000, std::string wav_format = "pcm", ASR_TYPE mode = ASR_TWO_PASS,
                                   const std::vector<std::vector<float>>& hw_emb = {{0.0f}}, bool itn = true, int vad_tail_sil = 800,
-                                  int vad_max_len = 60000, FUNASR_DEC_HANDLE dec_handle = nullptr);
+                                  int vad_max_len = 60000, FUNASR_DEC_HANDLE dec_handle = nullptr, std::string svs_lang = "auto",
+                                  bool svs_itn = true);
 const char* FunASRGetTpassResult(FUNASR_RESULT result, int n_index);
 void FunTpassOnlineUninit(FUNASR_HANDLE online_handle);
 void FunTpassUninit(FUNASR_HANDLE handle);
@@ -139,6 +144,12 @@ void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode);
 // SenseVoice result may be empty or lack some segments' pairs.
 void FunOfflineSetCtcStamps(FUNASR_HANDLE handle, int on);
 void FunTpassSetCifStamps(FUNASR_HANDLE tpass_handle, int mode);
+// The 2-pass sibling of FunOfflineSetCtcStamps, for a FunTpassInit handle whose MODEL_DIR names MODEL_SVS (the second pass is then a
+// SenseVoiceSmallHip: FunTpassInferBuffer's trailing svs_lang / svs_itn go to its Forward, tpass_msg is its text with no punctuation
+// and no ITN, funasrruntime.cpp:583-587, :609-631).  On: FunASRGetStamp of a result holds, per closed segment, "[[b,e],...]" — the
+// spans of the greedy tokens (one LFR row = 60 ms) plus the segment's global start.  FunASRGetSegmentIds / FunASRGetSegments of such
+// a result hold the second-pass ids and [start_ms, end_ms] of the segments closed in the call.
+void FunTpassSetCtcStamps(FUNASR_HANDLE tpass_handle, int on);
 // ... and the C-ABI handle of the offline acoustic model behind a FunOfflineInit handle (pfhip_inflight_stats in the harnesses)
 struct pfhip_model;
 pfhip_model* FunOfflineGetAsrHandle(FUNASR_HANDLE handle);

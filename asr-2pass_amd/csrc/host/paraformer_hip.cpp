@@ -124,18 +124,34 @@ void ParaformerHip::LoadOffline(const std::string& am_model, const std::string& 
     std::fprintf(stderr, "ParaformerHip::InitAsr: warm-up failed: %s\n", pfhip_last_error());
 }
 
+pfhip_model* LoadOnlineModelHip(const std::string& en_model, const std::string& de_model, const std::string& am_cmvn,
+                                const std::string& am_config, int device) {
+  // a container pair stands for both files of the online model
+  const bool container = en_model.size() > 10 && en_model.compare(en_model.size() - 10, 10, ".pfhip.bin") == 0;
+  pfhip_model* h = LoadModelFiles(en_model, container ? "" : de_model, "", am_cmvn, am_config, device, nullptr);
+  // One handler thread per connection in the server: their concurrent chunk calls are merged into batched passes; a leader
+  // stops waiting as soon as every open connection has queued, so a lone connection pays nothing.  0 switches the queue off.
+  pfhip_set_stream_batching(h, Knob("PFHIP_STREAM_WAIT_US", 3000), Knob("PFHIP_STREAM_MAX", 128));
+  return h;
+}
+HipVocab* LoadVocabHip(const std::string& token_file) { return LoadVocab(token_file); }
+std::string OnlineIdsToString(HipVocab* v, const std::vector<int>& ids) {
+  if (v) return v->Vector2StringV2(ids);                       // OnlineGreedySearch (paraformer.cpp:362-371): no language argument
+  std::string s;
+  for (size_t i = 0; i < ids.size(); ++i) {
+    if (i) s += ' ';
+    s += std::to_string(ids[i]);
+  }
+  return s;
+}
+
 void ParaformerHip::LoadOnline(const std::string& en_model, const std::string& de_model, const std::string& am_cmvn,
                                const std::string& am_config, const std::string& token_file) {
   if (online_handle_) { pfhip_destroy(online_handle_); online_handle_ = nullptr; }
-  // a container pair stands for both files of the online model
-  const bool container = en_model.size() > 10 && en_model.compare(en_model.size() - 10, 10, ".pfhip.bin") == 0;
-  online_handle_ = LoadModelFiles(en_model, container ? "" : de_model, "", am_cmvn, am_config, device_, nullptr);
+  online_handle_ = LoadOnlineModelHip(en_model, de_model, am_cmvn, am_config, device_);
   asr_sample_rate_ = pfhip_sample_rate(online_handle_);
   delete online_vocab;
   online_vocab = LoadVocab(token_file);                         // paraformer.cpp:117
-  // One handler thread per connection in the server: their concurrent chunk calls are merged into batched passes; a leader
-  // stops waiting as soon as every open connection has queued, so a lone connection pays nothing.  0 switches the queue off.
-  pfhip_set_stream_batching(online_handle_, Knob("PFHIP_STREAM_WAIT_US", 3000), Knob("PFHIP_STREAM_MAX", 128));
 }
 
 // offline (paraformer.cpp:21-53)
@@ -200,14 +216,7 @@ void ParaformerHip::InitLm(const std::string& lm_file, const std::string& lm_cfg
 int ParaformerHip::GetAsrSampleRate() { return asr_sample_rate_; }
 
 std::string ParaformerHip::OnlineTokensToString(const std::vector<int>& ids) {
-  HipVocab* v = online_vocab ? online_vocab : vocab;
-  if (v) return v->Vector2StringV2(ids);                       // OnlineGreedySearch (paraformer.cpp:362-371): no language argument
-  std::string s;
-  for (size_t i = 0; i < ids.size(); ++i) {
-    if (i) s += ' ';
-    s += std::to_string(ids[i]);
-  }
-  return s;
+  return OnlineIdsToString(online_vocab ? online_vocab : vocab, ids);
 }
 
 std::string ParaformerHip::Forward(float* din, int len, bool input_finished, const std::vector<std::vector<float>>& hw_emb,
@@ -449,18 +458,23 @@ bool ParaformerHip::InText(int id) const {
 namespace funasr {
 
 ParaformerOnlineHip::ParaformerOnlineHip(ParaformerHipBase* offline_handle, std::vector<int> chunk_size, std::string model_type) {
-  (void)model_type;                                             // MODEL_PARA only (SenseVoice is served offline, sensevoice_hip.h; its 2-pass seam is out of scope)
-  offline_handle_ = dynamic_cast<ParaformerHip*>(offline_handle);
-  if (!offline_handle_ || !offline_handle_->OnlineHandle() || chunk_size.size() != 3) {
+  // paraformer-online.cpp:37-59 casts the shared object to SenseVoiceSmall when model_type == MODEL_SVS and to Paraformer
+  // otherwise, and reads the online sessions off it; here both adapters own their online model behind one interface, so the
+  // object's own type decides and model_type is not needed to find it
+  (void)model_type;
+  offline_handle_ = offline_handle;
+  owner_ = dynamic_cast<OnlineModelOwner*>(offline_handle);
+  if (!owner_ || !owner_->OnlineHandle() || chunk_size.size() != 3) {
     std::fprintf(stderr, "ParaformerOnlineHip: the shared model holds no online encoder / decoder (InitAsr with en_model, de_model)\n");
+    owner_ = nullptr;
     return;
   }
-  if (pfhip_stream_create(offline_handle_->OnlineHandle(), chunk_size.data(), &stream_) != PFHIP_OK) {
+  if (pfhip_stream_create(owner_->OnlineHandle(), chunk_size.data(), &stream_) != PFHIP_OK) {
     std::fprintf(stderr, "ParaformerOnlineHip: %s\n", pfhip_last_error());
     stream_ = nullptr;
   }
   // chunk_len = chunk_size[1] * frame_shift (10 ms) * lfr_n (6) * 16 samples per ms (paraformer-online.cpp:40-43)
-  chunk_len = chunk_size[1] * 10 * 6 * (offline_handle_->GetAsrSampleRate() / 1000);
+  chunk_len = chunk_size[1] * 10 * 6 * (owner_->OnlineSampleRate() / 1000);
 }
 
 void ParaformerOnlineHip::SetDetail(int k, bool fires) {
@@ -525,7 +539,7 @@ std::string ParaformerOnlineHip::ForwardAny(const float* din, const int16_t* din
       std::fprintf(stderr, "ParaformerOnlineHip::Forward: no detail: %s\n", pfhip_last_error());
     }
   }
-  std::string result = offline_handle_->OnlineTokensToString(last_ids_);
+  std::string result = owner_->OnlineTokensToString(last_ids_);
   if (!result.empty() && pfhip_stream_last_path(stream_) == 2) result.push_back(' ');      // paraformer-online.cpp:585-587
   return result;
 }

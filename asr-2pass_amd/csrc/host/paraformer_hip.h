@@ -81,7 +81,24 @@ namespace funasr {
 
 class ParaformerOnlineHip;
 
-class ParaformerHip : public ParaformerHipBase
+// What ParaformerOnlineHip needs of the shared model object it is built from — the reference reads encoder_session_ /
+// decoder_session_ and the online vocabulary off a Paraformer or, with model_type == MODEL_SVS, off a SenseVoiceSmall
+// (paraformer-online.cpp:37-59).  Both adapters implement it; funasr::Model's own table is untouched.
+class OnlineModelOwner {
+ public:
+  virtual ~OnlineModelOwner() {}
+  virtual pfhip_model* OnlineHandle() const = 0;
+  virtual std::string OnlineTokensToString(const std::vector<int>& ids) = 0;      // online_vocab->Vector2StringV2 (paraformer.cpp:362-371)
+  virtual int OnlineSampleRate() const = 0;
+};
+// The online half of a 2-pass InitAsr (paraformer.cpp:56-131; sensevoice-small.cpp's nine-argument form does the same): the online
+// encoder and decoder into one Paraformer handle with stream batching on (PFHIP_STREAM_WAIT_US / PFHIP_STREAM_MAX).  Exits on failure.
+pfhip_model* LoadOnlineModelHip(const std::string& en_model, const std::string& de_model, const std::string& am_cmvn,
+                                const std::string& am_config, int device);
+HipVocab* LoadVocabHip(const std::string& token_file);              // tokens.json, or nullptr for an empty path / unreadable file
+std::string OnlineIdsToString(HipVocab* vocab, const std::vector<int>& ids);      // without a vocabulary: the ids, space separated
+
+class ParaformerHip : public ParaformerHipBase, public OnlineModelOwner
 #ifdef PFHIP_WITH_FUNASR
     , public WfstDecodable
 #endif
@@ -208,10 +225,11 @@ class ParaformerHip : public ParaformerHipBase
   // the C-ABI handles underneath — the offline model and, after a 2-pass / online InitAsr, the online model that
   // ParaformerOnlineHip streams are created from (the reference's encoder_session_ / decoder_session_) — and the text mappings
   pfhip_model* Handle() const { return handle_; }
-  pfhip_model* OnlineHandle() const { return online_handle_; }
+  pfhip_model* OnlineHandle() const override { return online_handle_; }
+  int OnlineSampleRate() const override { return asr_sample_rate_; }
   std::string TokensToString(const std::vector<int>& ids) { return IdsToString(ids); }
   // Paraformer::OnlineGreedySearch's text step: online_vocab->Vector2StringV2(hyps) (paraformer.cpp:362-371)
-  std::string OnlineTokensToString(const std::vector<int>& ids);
+  std::string OnlineTokensToString(const std::vector<int>& ids) override;
 
   std::string language = "zh-cn";          // paraformer.h:97
 
@@ -284,7 +302,8 @@ class ParaformerOnlineHip : public ParaformerHipBase {
 
  private:
   std::string ForwardAny(const float* f32, const int16_t* s16, int len, bool input_finished);
-  ParaformerHip* offline_handle_ = nullptr;
+  ParaformerHipBase* offline_handle_ = nullptr;      // the shared model object: a ParaformerHip, or (MODEL_SVS) a SenseVoiceSmallHip ...
+  OnlineModelOwner* owner_ = nullptr;                // ... as the owner of the online encoder / decoder
   pfhip_stream* stream_ = nullptr;
   std::vector<int> last_ids_;
   int detail_k_ = 0;                       // SetDetail

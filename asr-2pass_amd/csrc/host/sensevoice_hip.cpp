@@ -21,7 +21,32 @@ int Knob(const char* name, int dflt) {
 
 SenseVoiceSmallHip::~SenseVoiceSmallHip() {
   if (handle_) pfhip_destroy(handle_);
+  if (online_handle_) pfhip_destroy(online_handle_);
   delete vocab;
+  delete online_vocab_;
+}
+
+// 2pass: online first, then the offline model with the offline directory's config and tokens (the order of paraformer.cpp:134-154)
+void SenseVoiceSmallHip::InitAsr(const std::string& am_model, const std::string& en_model, const std::string& de_model,
+                                 const std::string& am_cmvn, const std::string& am_config, const std::string& token_file,
+                                 const std::string& online_token_file, int thread_num, const std::string& online_config_file) {
+  if (online_handle_) { pfhip_destroy(online_handle_); online_handle_ = nullptr; }
+  online_handle_ = LoadOnlineModelHip(en_model, de_model, am_cmvn, online_config_file, device_);
+  delete online_vocab_;
+  online_vocab_ = LoadVocabHip(online_token_file);
+  InitAsr(am_model, am_cmvn, am_config, token_file, thread_num);
+}
+void SenseVoiceSmallHip::InitAsr(const std::string& am_model, const std::string& en_model, const std::string& de_model,
+                                 const std::string& am_cmvn, const std::string& am_config, const std::string& token_file,
+                                 const std::string& online_token_file, int thread_num) {
+  InitAsr(am_model, en_model, de_model, am_cmvn, am_config, token_file, online_token_file, thread_num, am_config);
+}
+void SenseVoiceSmallHip::InitLm(const std::string& lm_file, const std::string& lm_config, const std::string& lex_file) {
+  InitLm(lm_file, lm_config, lex_file, "");
+}
+void SenseVoiceSmallHip::InitLm(const std::string& lm_file, const std::string&, const std::string&, const std::string&) {
+  std::fprintf(stderr, "SenseVoiceSmallHip::InitLm: %s is not loaded (no WFST / LM search for this model: the greedy text is served)\n",
+               lm_file.c_str());
 }
 
 void SenseVoiceSmallHip::InitAsr(const std::string& am_model, const std::string& am_cmvn, const std::string& am_config,

@@ -11,7 +11,7 @@
 
 namespace funasr {
 
-class SenseVoiceSmallHip : public ParaformerHipBase
+class SenseVoiceSmallHip : public ParaformerHipBase, public OnlineModelOwner
 #ifdef PFHIP_WITH_FUNASR
     , public WfstDecodable
 #endif
@@ -25,7 +25,24 @@ class SenseVoiceSmallHip : public ParaformerHipBase
   // beside the source, or a container x.pfhip.bin of kind "sensevoice".  Exits on failure like the reference's (:48-51).
   void InitAsr(const std::string& am_model, const std::string& am_cmvn, const std::string& am_config, const std::string& token_file,
                int thread_num) override;
-  using ParaformerHipBase::InitAsr;        // the online / 2-pass overloads stay visible (empty in the base: the 2-pass seam is out of scope)
+  // The 2-pass forms TpassStream calls on this model (tpass-stream.cpp:44-50, :76-77; sensevoice-small.cpp's nine-argument
+  // InitAsr): the online encoder and decoder (a small online Paraformer) into a handle of their own with stream batching on, as
+  // ParaformerHip's 2-pass InitAsr loads them, then the offline SenseVoice model with the offline directory's config and tokens.
+  // am_cmvn is the ONLINE directory's am.mvn and serves both, as tpass-stream.cpp:72 passes it.
+  void InitAsr(const std::string& am_model, const std::string& en_model, const std::string& de_model, const std::string& am_cmvn,
+               const std::string& am_config, const std::string& token_file, const std::string& online_token_file, int thread_num,
+               const std::string& online_config_file) override;
+  void InitAsr(const std::string& am_model, const std::string& en_model, const std::string& de_model, const std::string& am_cmvn,
+               const std::string& am_config, const std::string& token_file, const std::string& online_token_file, int thread_num) override;
+  using ParaformerHipBase::InitAsr;        // the six-argument online-only form stays visible (empty in the base)
+  // TpassStream calls InitLm when LM_DIR is set (tpass-stream.cpp:92-98): no search is built for this model, so the call returns
+  // having loaded nothing and says so once
+  void InitLm(const std::string& lm_file, const std::string& lm_config, const std::string& lex_file) override;
+  void InitLm(const std::string& lm_file, const std::string& lm_config, const std::string& lex_file, const std::string& lm_units_path) override;
+  // the online model ParaformerOnlineHip(this, chunk_size, MODEL_SVS) streams from
+  pfhip_model* OnlineHandle() const override { return online_handle_; }
+  std::string OnlineTokensToString(const std::vector<int>& ids) override { return OnlineIdsToString(online_vocab_, ids); }
+  int OnlineSampleRate() const override { return online_handle_ ? pfhip_sample_rate(online_handle_) : asr_sample_rate_; }
   // The overload of model.h:33-34 (sensevoice-small.cpp:575-690).  Returns batch_in strings; the reference refuses batch_in != 1
   // (:577-580), here the utterances are packed, all with the call's svs_lang / svs_itn.  decoder_handle == nullptr: the text of
   // CTCSearch (:323-377), made on the host from the ids the device collapsed.  With a decoder handle the full log-prob rows of every
@@ -96,6 +113,8 @@ class SenseVoiceSmallHip : public ParaformerHipBase
   std::vector<std::string> ForwardAny(const void* const* din, bool s16, const int* len, bool input_finished, const std::string& svs_lang,
                                       bool svs_itn, void* decoder_handle, int batch_in);
   pfhip_model* handle_ = nullptr;
+  pfhip_model* online_handle_ = nullptr;
+  HipVocab* online_vocab_ = nullptr;
   HipVocab* vocab = nullptr;
   int asr_sample_rate_ = 16000, device_ = 0, batch_size_ = 1;
   bool ctc_stamps_ = false;

@@ -6,6 +6,9 @@
 // nbest = 1..8 (FunTpassSetNbest, an extension) appends two fields to every line: " | online_detail <confidence>@<fire ms> ..." with one
 // entry per streamed token id of the call, and " | tpass_conf <confidence> ..." for the tokens of the second-pass text.
 // cif_stamps = 1 | 2 (FunTpassSetCifStamps, an extension): the stamp field of the second pass comes from the CIF scan's fire frames.
+// An offline_model_dir whose name contains "SenseVoiceSmall" makes the second pass a SenseVoiceSmallHip (tpass-stream.cpp:44-50); three
+// more arguments then apply: [svs_lang=auto] [svs_itn=1] [ctc_stamps=0] (FunTpassInferBuffer's trailing arguments, FunTpassSetCtcStamps),
+// and every line gets a field " | tpass_ids <second-pass ids of the segments closed in the call>".
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -30,6 +33,10 @@ int main(int argc, char** argv) {
   const int nbest = argc > 9 ? std::atoi(argv[9]) : 0;
   if (h && nbest > 0) FunTpassSetNbest(h, nbest);                  // before the connection's stream is made
   if (h && argc > 10) FunTpassSetCifStamps(h, std::atoi(argv[10]));      // the offline pass stamps from the CIF scan (an extension)
+  const bool svs = std::string(argv[1]).find(MODEL_SVS) != std::string::npos;
+  const std::string svs_lang = argc > 11 ? argv[11] : "auto";
+  const bool svs_itn = argc > 12 ? std::atoi(argv[12]) != 0 : true;
+  if (h && svs && argc > 13) FunTpassSetCtcStamps(h, std::atoi(argv[13]));
   FUNASR_HANDLE oh = FunTpassOnlineInit(h, {5, 10, 5});
   if (!h || !oh) return 1;
   std::vector<std::vector<std::string>> punc_cache(2);
@@ -38,7 +45,8 @@ int main(int argc, char** argv) {
   for (int off = 0; off < n_bytes; off += step_bytes, ++j) {
     const int nb = std::min(step_bytes, n_bytes - off);
     const bool last = off + step_bytes >= n_bytes;
-    FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, nb, punc_cache, last, audio_fs, "pcm", mode);
+    FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, nb, punc_cache, last, audio_fs, "pcm", mode, {{0.0f}}, true, 800, 60000,
+                                          nullptr, svs_lang, svs_itn);
     if (!r) { std::fprintf(stderr, "inference failed\n"); return 1; }
     std::printf("call %d | online %s | tpass %s | stamp %s", j, FunASRGetResult(r, 0), FunASRGetTpassResult(r, 0), FunASRGetStamp(r));
     if (nbest > 0) {
@@ -48,6 +56,10 @@ int main(int argc, char** argv) {
       for (size_t t = 0; t < conf.size() && t < ms.size(); ++t) std::printf(" %.9g@%d", conf[t], ms[t]);
       std::printf(" | tpass_conf");
       for (float c : FunASRGetTokenConfidence(r)) std::printf(" %.9g", c);
+    }
+    if (svs) {
+      std::printf(" | tpass_ids");
+      for (const std::vector<int>& seg : FunASRGetSegmentIds(r)) for (int id : seg) std::printf(" %d", id);
     }
     std::printf("\n");
     FunASRFreeResult(r);

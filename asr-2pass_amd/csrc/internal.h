@@ -266,6 +266,10 @@ struct pfhip_model {
   std::vector<int32_t> svs_prompt;
   float* svs_logp_host = nullptr;
   int debug_ctc_unfused = 0, svs_head_chunks = 0, svs_unfused_forwards = 0;
+  // a merged batch (svs_api.cpp): per utterance the host buffer for its full log-prob rows, or null (empty: a lone caller, who asks
+  // through svs_logp_host); the rows the unfused chunks of the last head covered (pfhip_debug_poke "svs_unfused_rows")
+  std::vector<float*> svs_logp_rows;
+  long long svs_unfused_rows = 0;
   Buf svs_ws, svs_frame, svs_logits, svs_logp;
   // pfhip_svs_align: the log-sum-exp of every row of the last forward [M] (either head writes it), whether that forward completed,
   // and the aligner's own buffers (metadata, emissions, back-pointers, results)
@@ -273,7 +277,17 @@ struct pfhip_model {
   PinBuf al_host;
   bool svs_fwd_ok = false;
   uint64_t svs_serial = 0;       // counts this context's SenseVoice forwards: a thread's note of its last one is matched on it
-  int *m_feat_off = nullptr, *m_prompt = nullptr;
+  // pfhip_svs_forward_spans: per utterance of the forward being run whether its greedy tokens are aligned inside the forward (empty:
+  // none are — pfhip_svs_forward; a range-guard re-run reads it again), the plan kernel's outputs (n_lab, lab_off [B] | e_off [B],
+  // total: int64), and of the last head: the token slots per utterance of the span results, their first word in counts / h_counts
+  // (tok_begin, tok_end, tok_logp [B][svs_span_mt] | score [B]; 0 slots = no spans were formed).  debug_span_cap: a test's
+  // stand-in for PFHIP_SVS_SPAN_MAX_FLOATS (pfhip_debug_poke "svs_span_cap", 0 = the constant).
+  std::vector<char> svs_span_want;
+  Buf al_plan;
+  int svs_span_mt = 0;
+  size_t svs_span_word = 0;
+  long long debug_span_cap = 0;
+  int *m_feat_off = nullptr, *m_prompt = nullptr, *m_speech_len = nullptr;
   // device views into meta / dmeta
   int *m_frame_off = nullptr, *m_nframes = nullptr, *m_row_off = nullptr, *m_len = nullptr,
       *m_row_pos = nullptr, *m_row_len = nullptr;

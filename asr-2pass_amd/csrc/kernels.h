@@ -319,9 +319,17 @@ bool launch_ctc_collapse(const int32_t* frame_ids, const float* frame_logp, cons
 // Emissions of the labels asked for: utterance b owns rows [row_off[b], + len[b]) of X and labels[lab_off[b] .. + n_lab[b]) (device
 // arrays); E + e_off[b] is E_b [len[b]][n_lab[b] + 1] = x_t . W[id_j] + bias[id_j] - lse[row], column 0 the blank, column j label j.
 // fp32 FMA.  K % 32 == 0, row strides % 4 == 0.  Rows are clamped to the utterance, label ids to 0 .. V - 1.  false: nothing launched.
+// e_floats >= 0: the floats of E, and an utterance whose E_b does not lie inside them is left unwritten (sizes planned on the device).
 bool launch_ctc_emissions(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* lse, const int* row_off,
                           const int* len, const int* lab_off, const int* n_lab, const int32_t* labels, const long long* e_off, int B, int K,
-                          int V, int blank, float* E, hipStream_t s);
+                          int V, int blank, float* E, hipStream_t s, long long e_floats = -1);
+// The step between the collapse and the two kernels above, on the device: from token_num [B] (the collapse's) and speech_len [B] (the
+// rows N_b the labels are aligned against) n_lab[b] = max(token_num[b] - 4, 0), lab_off[b] = b maxT + 4 (the labels are the collapse's
+// id buffer [B][maxT] behind the four tags), e_off[b] = the exclusive int64 prefix sum of N_b (n_lab[b] + 1), *total (may be null) =
+// the sum over all b.  n_lab[b] = -1 (both kernels then leave the utterance alone) where E_b would end beyond cap_floats, and — with
+// nothing added to the sum — where token_num[b] > maxT or N_b < 0.  One workgroup; B <= 65535.  false: nothing launched.
+bool launch_ctc_greedy_plan(const int32_t* token_num, const int* speech_len, int B, int maxT, long long cap_floats, int* n_lab, int* lab_off,
+                            long long* e_off, long long* total, hipStream_t s);
 // Viterbi over the CTC trellis of each utterance and the token spans (include/pfhip_ops.h states the recurrence).  e_floats: the floats
 // of E; workspace: ctc_align_workspace_bytes(e_floats) bytes of back-pointers.  tok_begin / tok_end / tok_logp [B][max_tokens] (tok_logp
 // may be null), score [B].  false (nothing launched) for max_tokens above ctc_align_max_tokens() (the two score rows of 2 L + 1 states

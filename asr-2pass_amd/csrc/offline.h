@@ -3,6 +3,31 @@
 #include "internal.h"
 
 namespace pfhip_impl {
+// hotword sets of a call: n_sets sets (emb[k]: [n[k], d]) and, per utterance, which one it attends to (of_utt == nullptr: all set 0)
+struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
+}  // namespace pfhip_impl
+
+// One caller in the cross-request queue of a handle (pfhip_model::bq; offline_api.cpp states the queue's rules).  A Paraformer handle
+// queues pfhip_offline_forward callers (out, hw, dt), a SenseVoice handle pfhip_svs_forward[_spans] callers (lid .. spans); a handle
+// is one or the other, so a queue never holds both.
+struct BatchReq : pfhip_impl::MergeReqBase {
+  pfhip_impl::HostPcm pcm{static_cast<const float* const*>(nullptr)}; const int* n; int batch; pfhip_out* out = nullptr;
+  pfhip_impl::HwSets hw{nullptr, nullptr, 0, nullptr};          // the caller's hotword sets (contextual models)
+  const pfhip_detail* dt = nullptr;                 // the caller's candidate / fire-frame buffers (pfhip_offline_forward_detail), or none
+  // SenseVoice: prompt ids per utterance, the caller's buffers, and — filled by the leader — where the packed forward ran: the
+  // context, its forward count then and the caller's first utterance in the packed batch (the note pfhip_svs_align matches)
+  const int32_t *lid = nullptr, *textnorm = nullptr;
+  pfhip_svs_out* sout = nullptr;
+  pfhip_svs_align_out* spans = nullptr;
+  pfhip_model* ran_on = nullptr;
+  uint64_t serial = 0;
+  int u0 = 0;
+  long long unfused_rows = 0;
+  int company = 0;                                  // the callers the packed forward served, this one included
+  pfhip_status st = PFHIP_OK; std::string err;
+};
+
+namespace pfhip_impl {
 
 // ---- model_build.cpp ----
 pfhip_status build_model(const void* blob, size_t blob_bytes, const char* manifest_json, int device,
@@ -70,15 +95,21 @@ pfhip_status stage_pcm(pfhip_model* m, HostPcm pcm, const int* n_samples, int B,
                        std::vector<int64_t>& off);
 pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, int B, int fs_in, hipStream_t s,
                              std::vector<int64_t>& off, std::vector<int>& n_out);
-// hotword sets of a call: n_sets sets (emb[k]: [n[k], d]) and, per utterance, which one it attends to (of_utt == nullptr: all set 0)
-struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
 pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch,
                             const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_detail* dt = nullptr);
 pfhip_model*& last_replica();       // the calling thread's tl_last_replica
+// the caller joins the handle's queue; `run` executes one packed forward for everybody taken.  The slot `me` led a batch on, or null
+pfhip_model* pool_submit(pfhip_model* head, BatchReq& me, void (*run)(pfhip_model*, const std::vector<BatchReq*>&));
 
 // ---- svs_api.cpp ----
+// a packed forward for merged callers: per utterance whether its greedy tokens are aligned (null: all, when there is a span buffer)
+// and the host buffer for its full log-prob rows (null: none); back come the context's forward count behind this forward and the
+// rows its unfused head chunks covered
+struct SvsMerge { const char* span_want = nullptr; float* const* logp_rows = nullptr; uint64_t serial = 0; long long unfused_rows = 0; };
+long long svs_last_unfused_rows();      // of the forward that served the calling thread's last pfhip_svs_forward
+int svs_last_forward_calls();           // the callers that forward served (1: a lone or direct call)
 pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
-                                const int32_t* textnorm, pfhip_svs_out* out);
+                                const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans = nullptr, SvsMerge* mg = nullptr);
 
 // ---- pfhip.cpp: the execution slots ----
 void rebuild_slots_locked(pfhip_model* head);

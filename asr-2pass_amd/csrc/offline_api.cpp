@@ -11,9 +11,7 @@
 
 #define g_err (pfhip_impl::last_error())
 
-// (BatchReq is the global type internal.h declares for pfhip_model::bq, so it stands outside the namespaces below)
-using pfhip_impl::HostPcm;
-using pfhip_impl::HwSets;
+// (BatchReq, the global type internal.h declares for pfhip_model::bq, is in offline.h: the SenseVoice forwards queue there too)
 
 // ---- cross-request batching ---------------------------------------------------------------------------------
 // The reference server runs `decoder-thread-num` threads that each call Forward on the shared handle with their own
@@ -25,13 +23,6 @@ using pfhip_impl::HwSets;
 // Results are those of separate calls up to the near-tie statement the tests make (packed layout, per-utterance masks:
 // tests/test_gpu_forward.py::test_batch_composition_invariance — a merged forward may run another kernel family than a lone one,
 // the same sums in another order, 1e-6 apart in the log-probabilities).
-struct BatchReq : pfhip_impl::MergeReqBase {
-  HostPcm pcm{static_cast<const float* const*>(nullptr)}; const int* n; int batch; pfhip_out* out;
-  HwSets hw{nullptr, nullptr, 0, nullptr};          // the caller's hotword sets (contextual models)
-  const pfhip_detail* dt = nullptr;                 // the caller's candidate / fire-frame buffers (pfhip_offline_forward_detail), or none
-  pfhip_status st = PFHIP_OK; std::string err;
-};
-
 namespace {
 using namespace pfhip_impl;
 
@@ -174,51 +165,11 @@ void run_batch_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken)
 
 thread_local pfhip_model* tl_last_replica = nullptr;      // where this thread's last offline forward ran (debug getters)
 
-// Callers of both sample formats share the queue; a packed forward holds ONE format, the leader's: pick takes the queued callers of
-// that format (in order) and leaves the others, in order, for the next leader.  Nothing is converted on the host, every caller gets
-// the results of a forward in its own format, which are those of the other format bit for bit.
 pfhip_status forward_batched(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch,
                                     const HwSets& hw, pfhip_out* out, const pfhip_detail* dt) {
   BatchReq me;
   me.pcm = pcm; me.n = n_samples; me.batch = batch; me.out = out; me.hw = hw; me.dt = dt;
-  int wait_us, max_utts;
-  { std::lock_guard<std::mutex> l(head->bq.mu); wait_us = head->batch_wait_us; max_utts = head->batch_max_utts; }
-  pfhip_model* ran_on = nullptr;
-  head->bq.submit(
-      me, wait_us,
-      // claim (under the queue lock): an idle slot, in the device-major order of `slots`
-      [&]() -> pfhip_model* {
-        if (head->slots.empty()) rebuild_slots_locked(head);
-        for (pfhip_model* r : head->slots)
-          if (r->inflight.load() == 0) { ++r->inflight; return r; }
-        return nullptr;
-      },
-      [&](pfhip_model* r) { --r->inflight; },
-      // gather: bounded by time and by utterance count
-      [&](const std::deque<BatchReq*>& q) { int u = 0; for (BatchReq* r : q) u += r->batch; return u >= max_utts; },
-      [&](std::deque<BatchReq*>& q, std::vector<BatchReq*>& take) {
-        int utts = 0;
-        const bool s16 = q.front()->pcm.s16;
-        std::deque<BatchReq*> other;                      // callers of the other sample format: they stay queued, in order
-        while (!q.empty() && (take.empty() || utts + q.front()->batch <= max_utts)) {
-          if (q.front()->pcm.s16 == s16) {
-            utts += q.front()->batch;
-            take.push_back(q.front());
-          } else {
-            other.push_back(q.front());
-          }
-          q.pop_front();
-        }
-        for (auto it = other.rbegin(); it != other.rend(); ++it) q.push_front(*it);
-        if (!other.empty()) ++head->format_splits;        // (pfhip_debug_poke "format_splits")
-      },
-      [&](pfhip_model* r, std::vector<BatchReq*>& take) {
-        ran_on = r;
-        int utts = 0;
-        for (BatchReq* q : take) utts += q->batch;
-        run_batch_requests(r, take);
-        ++r->served_forwards; r->served_calls += (int64_t)take.size(); r->served_utts += utts;
-      });
+  pfhip_model* ran_on = pool_submit(head, me, run_batch_requests);
   if (ran_on) tl_last_replica = ran_on;       // the leader's own slice ran there; followers ask the handle (pfhip_get_tensor: head)
   if (me.st != PFHIP_OK) g_err = me.err;
   return me.st;
@@ -427,6 +378,52 @@ pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, i
   st = head_locked(m, s, out->logp != nullptr);
   if (st) return st;
   return fetch_locked(m, out, s, dt);
+}
+
+// Callers of both sample formats share the queue; a packed forward holds ONE format, the leader's: pick takes the queued callers of
+// that format (in order) and leaves the others, in order, for the next leader.  Nothing is converted on the host, every caller gets
+// the results of a forward in its own format, which are those of the other format bit for bit.
+// Returns the slot the caller LED a batch on (null for a follower); `run` fills every taken request's result fields.
+pfhip_model* pool_submit(pfhip_model* head, BatchReq& me, void (*run)(pfhip_model*, const std::vector<BatchReq*>&)) {
+  int wait_us, max_utts;
+  { std::lock_guard<std::mutex> l(head->bq.mu); wait_us = head->batch_wait_us; max_utts = head->batch_max_utts; }
+  pfhip_model* ran_on = nullptr;
+  head->bq.submit(
+      me, wait_us,
+      // claim (under the queue lock): an idle slot, in the device-major order of `slots`
+      [&]() -> pfhip_model* {
+        if (head->slots.empty()) rebuild_slots_locked(head);
+        for (pfhip_model* r : head->slots)
+          if (r->inflight.load() == 0) { ++r->inflight; return r; }
+        return nullptr;
+      },
+      [&](pfhip_model* r) { --r->inflight; },
+      // gather: bounded by time and by utterance count
+      [&](const std::deque<BatchReq*>& q) { int u = 0; for (BatchReq* r : q) u += r->batch; return u >= max_utts; },
+      [&](std::deque<BatchReq*>& q, std::vector<BatchReq*>& take) {
+        int utts = 0;
+        const bool s16 = q.front()->pcm.s16;
+        std::deque<BatchReq*> other;                      // callers of the other sample format: they stay queued, in order
+        while (!q.empty() && (take.empty() || utts + q.front()->batch <= max_utts)) {
+          if (q.front()->pcm.s16 == s16) {
+            utts += q.front()->batch;
+            take.push_back(q.front());
+          } else {
+            other.push_back(q.front());
+          }
+          q.pop_front();
+        }
+        for (auto it = other.rbegin(); it != other.rend(); ++it) q.push_front(*it);
+        if (!other.empty()) ++head->format_splits;        // (pfhip_debug_poke "format_splits")
+      },
+      [&](pfhip_model* r, std::vector<BatchReq*>& take) {
+        ran_on = r;
+        int utts = 0;
+        for (BatchReq* q : take) utts += q->batch;
+        run(r, take);
+        ++r->served_forwards; r->served_calls += (int64_t)take.size(); r->served_utts += utts;
+      });
+  return ran_on;
 }
 
 pfhip_model*& last_replica() { return tl_last_replica; }

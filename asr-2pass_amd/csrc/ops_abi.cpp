@@ -371,6 +371,12 @@ int pfhip_op_ctc_emissions(const float* X, int ldx, const float* W, int ldw, con
     return (int)hipErrorInvalidValue;
   return done();
 }
+int pfhip_op_ctc_greedy_plan(const int32_t* token_num, const int* speech_len, int B, int maxT, long long cap_floats, int* n_lab, int* lab_off,
+                             long long* e_off, long long* total, void* stream) {
+  if (!pfhip::launch_ctc_greedy_plan(token_num, speech_len, B, maxT, cap_floats, n_lab, lab_off, e_off, total, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
 size_t pfhip_op_ctc_align_workspace_bytes(size_t e_floats) { return pfhip::ctc_align_workspace_bytes(e_floats); }
 int pfhip_op_ctc_align_max_tokens(void) { return pfhip::ctc_align_max_tokens(); }
 int pfhip_op_ctc_align(const float* E, const long long* e_off, size_t e_floats, const int* len, const int* n_lab, const int32_t* labels,

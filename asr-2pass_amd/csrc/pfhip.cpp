@@ -196,7 +196,7 @@ int pfhip_has_timestamp_head(const pfhip_model* m) { return m ? m->weights->cfg.
 pfhip_status pfhip_set_batching(pfhip_model* m, int wait_us, int max_utterances) {
   g_err.clear();
   if (!m || wait_us < 0 || max_utterances < 1) return fail(PFHIP_ERR_ARG, "bad argument");
-  if (is_svs(m)) return fail(PFHIP_ERR_UNSUPPORTED, "merging concurrent callers is not built for SenseVoice (CTC) models");
+  if (is_svs(m)) return fail(PFHIP_ERR_UNSUPPORTED, "a SenseVoice (CTC) handle merges its callers through pfhip_svs_set_batching");
   std::lock_guard<std::mutex> ql(m->bq.mu);
   m->batch_wait_us = wait_us;
   m->batch_max_utts = max_utterances;

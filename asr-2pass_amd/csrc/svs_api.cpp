@@ -1,5 +1,6 @@
 // SenseVoiceSmall, offline: the packed forward with its range-guard re-run, and CTC forced alignment against its rows.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -13,23 +14,159 @@ namespace {
 using namespace pfhip_impl;
 
 // pfhip_svs_align: per handle (its uid), where this thread's last pfhip_svs_forward on it ran — the context's uid and that context's
-// forward count then.  Handles come and go; the note is emptied when it has grown past 64 handles.
-struct SvsNote { uint64_t ctx_uid, serial; };
+// forward count then, and the caller's utterances within that forward: a lone caller's are all of them, a merged caller's the
+// sub-range [u0, u0 + batch) of the packed batch.  Handles come and go; the note is emptied when it has grown past 64 handles.
+struct SvsNote { uint64_t ctx_uid, serial; int u0, batch; };
 thread_local std::map<uint64_t, SvsNote> tl_svs_notes;
+// pfhip_debug_poke "svs_unfused_rows": the rows that went through the unfused head chunks in the forward which served the calling
+// thread's last pfhip_svs_forward — taken while that forward still held its context, so no later forward there changes it
+thread_local long long tl_unfused_rows = 0;
+thread_local int tl_forward_calls = 0;      // "svs_forward_calls": the callers that same forward served
+void keep_note(const pfhip_model* head, uint64_t ctx_uid, uint64_t serial, int u0, int batch) {
+  if (tl_svs_notes.size() > 64) tl_svs_notes.clear();
+  tl_svs_notes[head->uid] = SvsNote{ctx_uid, serial, u0, batch};
+}
+
+int rows_of(const pfhip_model* m, int n_samples) {      // forward_encoder's count: T + 4 prompt rows, or none at all
+  const int F = n_samples < 400 ? 0 : 1 + (n_samples - 400) / 160;
+  const int T = (F + m->weights->cfg.lfr_n - 1) / m->weights->cfg.lfr_n;
+  return T > 0 ? T + 4 : 0;
+}
+
+// One packed forward on `m` for everybody in `take` (one sample format: pool_submit's pick).  Every caller keeps its own lid /
+// textnorm per utterance and its own buffers; the forward's results are staged here and dealt out, a caller whose buffers are too
+// small fails alone.  Full log-prob rows go from the device straight into the buffer of the caller who asked (heads.cpp runs the
+// unfused chunks over those utterances' rows only); spans are formed for the utterances of the callers who brought a span buffer.
+void run_svs_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
+  const int V = m->weights->cfg.vocab;
+  std::vector<BatchReq*> take;
+  for (BatchReq* r : all_taken) {
+    r->ran_on = m;
+    r->company = 0;
+    if (r->sout->logp) {                              // known before anything is launched, as for a lone caller
+      size_t rows = 0;
+      for (int i = 0; i < r->batch; ++i) rows += (size_t)rows_of(m, r->n[i]);
+      if (rows * (size_t)V > r->sout->logp_cap_floats) {
+        r->st = PFHIP_ERR_CAPACITY; r->err = "logp_cap_floats smaller than rows x vocabulary"; continue;
+      }
+    }
+    take.push_back(r);
+  }
+  if (take.empty()) return;
+  for (BatchReq* r : take) r->company = (int)take.size();
+  if (take.size() == 1) {                             // nobody to share with: the caller's own buffers, as without the queue
+    BatchReq* r = take.front();
+    SvsMerge mg;
+    r->st = svs_forward_direct(m, r->pcm, r->n, r->batch, r->lid, r->textnorm, r->sout, r->spans, &mg);
+    r->err = g_err; r->serial = mg.serial; r->u0 = 0; r->unfused_rows = mg.unfused_rows;
+    return;
+  }
+  std::vector<const void*> ptrs; std::vector<int> lens, rows; std::vector<int32_t> lid, tn;
+  std::vector<char> span_want; std::vector<float*> logp_rows;
+  bool any_spans = false, any_logp = false;
+  int cap = 1; size_t M = 0;
+  for (BatchReq* r : take) {
+    r->u0 = (int)lens.size();
+    size_t row_in_req = 0;
+    for (int i = 0; i < r->batch; ++i) {
+      const int T = rows_of(m, r->n[i]);
+      ptrs.push_back(r->pcm.p[i]); lens.push_back(r->n[i]); rows.push_back(T); lid.push_back(r->lid[i]); tn.push_back(r->textnorm[i]);
+      span_want.push_back(r->spans ? 1 : 0);
+      logp_rows.push_back(r->sout->logp && T ? r->sout->logp + row_in_req * V : nullptr);
+      row_in_req += (size_t)T; M += (size_t)T; cap = std::max(cap, T);
+    }
+    any_spans = any_spans || r->spans; any_logp = any_logp || r->sout->logp;
+  }
+  const int utts = (int)lens.size();
+  std::vector<int32_t> ids((size_t)utts * cap), frames(ids.size()), num(utts), flen(utts), fid(std::max<size_t>(M, 1));
+  std::vector<float> tlogp(ids.size()), flp(fid.size());
+  pfhip_svs_out all{};
+  all.ids = ids.data(); all.token_num = num.data(); all.max_tokens = cap; all.tok_frame = frames.data(); all.tok_logp = tlogp.data();
+  all.frame_ids = fid.data(); all.frame_logp = flp.data(); all.frame_len = flen.data();
+  std::vector<int32_t> sb, se; std::vector<float> sl, ss;
+  pfhip_svs_align_out sp{};
+  if (any_spans) {
+    sb.assign(ids.size(), -1); se.assign(ids.size(), -1); sl.assign(ids.size(), -INFINITY); ss.assign(utts, 0.f);
+    sp.tok_begin = sb.data(); sp.tok_end = se.data(); sp.tok_logp = sl.data(); sp.score = ss.data(); sp.max_tokens = cap;
+  }
+  SvsMerge mg;
+  mg.span_want = any_spans ? span_want.data() : nullptr;
+  mg.logp_rows = any_logp ? logp_rows.data() : nullptr;
+  const pfhip_status st = svs_forward_direct(m, HostPcm(ptrs.data(), take.front()->pcm.s16), lens.data(), utts, lid.data(), tn.data(), &all,
+                                             any_spans ? &sp : nullptr, &mg);
+  const std::string err = g_err;
+  std::vector<size_t> row_off(utts + 1, 0);
+  for (int u = 0; u < utts; ++u) row_off[u + 1] = row_off[u] + (size_t)rows[u];
+  for (BatchReq* r : take) {
+    r->st = st; r->err = err; r->serial = mg.serial; r->unfused_rows = mg.unfused_rows;
+    if (st) continue;
+    pfhip_svs_out* o = r->sout;
+    int longest = 0;
+    for (int i = 0; i < r->batch; ++i) {
+      if (o->token_num) o->token_num[i] = num[r->u0 + i];
+      if (o->frame_len) o->frame_len[i] = flen[r->u0 + i];
+      longest = std::max(longest, num[r->u0 + i]);
+    }
+    if ((o->ids || o->tok_frame || o->tok_logp) && o->max_tokens < longest) {
+      r->st = PFHIP_ERR_CAPACITY; r->err = "max_tokens smaller than the longest token sequence"; continue;
+    }
+    if (r->spans && r->spans->max_tokens < longest - 4) {
+      r->st = PFHIP_ERR_CAPACITY; r->err = "spans: max_tokens smaller than the longest token list"; continue;
+    }
+    for (int i = 0; i < r->batch; ++i) {
+      const int u = r->u0 + i;
+      const size_t n = (size_t)num[u], src = (size_t)u * cap, dst = (size_t)i * o->max_tokens;
+      if (o->ids) std::memcpy(o->ids + dst, ids.data() + src, n * 4);
+      if (o->tok_frame) std::memcpy(o->tok_frame + dst, frames.data() + src, n * 4);
+      if (o->tok_logp) std::memcpy(o->tok_logp + dst, tlogp.data() + src, n * 4);
+      const size_t f0 = row_off[u] - row_off[r->u0];
+      if (o->frame_ids) std::memcpy(o->frame_ids + f0, fid.data() + row_off[u], (size_t)rows[u] * 4);
+      if (o->frame_logp) std::memcpy(o->frame_logp + f0, flp.data() + row_off[u], (size_t)rows[u] * 4);
+      if (r->spans) {
+        const size_t nt = n > 4 ? n - 4 : 0, sdst = (size_t)i * r->spans->max_tokens;
+        std::memcpy(r->spans->tok_begin + sdst, sb.data() + src, nt * 4);
+        std::memcpy(r->spans->tok_end + sdst, se.data() + src, nt * 4);
+        if (r->spans->tok_logp) std::memcpy(r->spans->tok_logp + sdst, sl.data() + src, nt * 4);
+        if (r->spans->score) r->spans->score[i] = ss[u];
+      }
+    }
+  }
+}
 
 pfhip_status svs_forward(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid, const int32_t* textnorm,
-                                pfhip_svs_out* out) {
+                                pfhip_svs_out* out, pfhip_svs_align_out* spans = nullptr) {
   g_err.clear();
   if (!head || !pcm.p || !n_samples || batch <= 0 || !lid || !textnorm || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (spans && (!spans->tok_begin || !spans->tok_end)) return fail(PFHIP_ERR_ARG, "bad argument");
   if (!is_svs(head)) return fail(PFHIP_ERR_UNSUPPORTED, "not a SenseVoice (CTC) model: a Paraformer is run through pfhip_offline_forward");
   if (!head->replicas.empty()) return fail(PFHIP_ERR_UNSUPPORTED, "multi-device groups are not built for SenseVoice (CTC) models");
   for (int b = 0; b < batch; ++b) {
     if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
     if (lid[b] < 0 || lid[b] > 15 || textnorm[b] < 0 || textnorm[b] > 15) return fail(PFHIP_ERR_ARG, "lid / textnorm outside 0..15");
   }
+  bool merge;
+  {
+    std::lock_guard<std::mutex> l(head->bq.mu);
+    merge = head->batch_wait_us > 0 && batch < head->batch_max_utts;
+  }
+  if (merge) {                                          // pfhip_svs_set_batching: merged with whoever else is calling (offline_api.cpp)
+    BatchReq me;
+    me.pcm = pcm; me.n = n_samples; me.batch = batch; me.lid = lid; me.textnorm = textnorm; me.sout = out; me.spans = spans;
+    pool_submit(head, me, run_svs_requests);
+    // leader or follower: where the forward ran, and which of its utterances are this caller's (pfhip_svs_align, the debug read-outs)
+    tl_unfused_rows = me.unfused_rows;
+    tl_forward_calls = me.company;
+    if (me.ran_on) {
+      last_replica() = me.ran_on;
+      if (me.serial) keep_note(head, me.ran_on->uid, me.serial, me.u0, batch);
+    }
+    if (me.st != PFHIP_OK) g_err = me.err;
+    return me.st;
+  }
   pfhip_model* m = acquire_slot(head);                  // the least-loaded execution context
   last_replica() = m;
-  const pfhip_status st = svs_forward_direct(m, pcm, n_samples, batch, lid, textnorm, out);
+  tl_forward_calls = 1;
+  const pfhip_status st = svs_forward_direct(m, pcm, n_samples, batch, lid, textnorm, out, spans);
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
   return st;
@@ -39,9 +176,12 @@ pfhip_status svs_forward(pfhip_model* head, HostPcm pcm, const int* n_samples, i
 
 namespace pfhip_impl {
 
+long long svs_last_unfused_rows() { return tl_unfused_rows; }
+int svs_last_forward_calls() { return tl_forward_calls; }
+
 // one packed forward on slot m, its range-guard re-run included, and the results into out
 pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
-                                       const int32_t* textnorm, pfhip_svs_out* out) {
+                                       const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans, SvsMerge* mg) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
@@ -67,6 +207,11 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
     if (rows * (size_t)V > out->logp_cap_floats) return fail(PFHIP_ERR_CAPACITY, "logp_cap_floats smaller than rows x vocabulary");
   }
   m->svs_logp_host = out->logp;
+  m->svs_span_want.assign(spans ? (size_t)batch : 0, 1);      // the head aligns the greedy tokens behind its collapse (heads.cpp)
+  if (spans && mg && mg->span_want) m->svs_span_want.assign(mg->span_want, mg->span_want + batch);
+  m->svs_logp_rows.clear();
+  if (mg && mg->logp_rows) m->svs_logp_rows.assign(mg->logp_rows, mg->logp_rows + batch);
+  m->svs_span_mt = 0;
   st = enqueue_locked(m, PcmView{m->pcm.p, pcm.s16}, off.data(), n_samples, batch, s, false);
   if (!st && m->M > 0 && m->range_hit && !m->weights->always_exact) {      // the guard of the fp16 two-plane domain: redone once, exact
     ++m->range_fallbacks;
@@ -75,17 +220,22 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
     m->exact_rerun = false;
   }
   m->svs_logp_host = nullptr;
+  m->svs_span_want.clear();
+  m->svs_logp_rows.clear();
+  (mg ? mg->unfused_rows : tl_unfused_rows) = st || m->M == 0 ? 0 : m->svs_unfused_rows;
   if (st) return st;
   m->svs_fwd_ok = true;                          // the rows and their log-sum-exp are what pfhip_svs_align reads ...
-  {                                              // ... for this thread, until this context runs another forward
-    if (tl_svs_notes.size() > 64) tl_svs_notes.clear();
-    tl_svs_notes[(m->group_head ? m->group_head : m)->uid] = SvsNote{m->uid, ++m->svs_serial};
-  }
+  ++m->svs_serial;                               // ... for this thread, until this context runs another forward
+  if (mg) mg->serial = m->svs_serial;            // (merged callers: each notes its own sub-range in its own thread)
+  else keep_note(m->group_head ? m->group_head : m, m->uid, m->svs_serial, 0, batch);
   for (int b = 0; b < batch; ++b) {
     if (out->token_num) out->token_num[b] = m->M ? m->token_num[b] : 0;
     if (out->frame_len) out->frame_len[b] = m->T[b];
   }
-  if (m->M == 0) return PFHIP_OK;
+  if (m->M == 0) {                                 // no rows at all: what pfhip_svs_align answers for no tokens against no rows
+    for (int b = 0; spans && spans->score && b < batch; ++b) spans->score[b] = 0.f;
+    return PFHIP_OK;
+  }
   if ((out->ids || out->tok_frame || out->tok_logp) && out->max_tokens < m->maxL)
     return fail(PFHIP_ERR_CAPACITY, "max_tokens smaller than the longest token sequence");
   const SvsHost h = svs_host(m);
@@ -97,6 +247,25 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
   }
   if (out->frame_ids) std::memcpy(out->frame_ids, h.fid, (size_t)m->M * 4);
   if (out->frame_logp) std::memcpy(out->frame_logp, h.flp, (size_t)m->M * 4);
+  if (spans) {                                     // they came in the forward's one copy, behind its results
+    const int mt = m->svs_span_mt;
+    const size_t sbt = (size_t)batch * mt;
+    const int32_t *s_begin = m->h_counts.i() + m->svs_span_word, *s_end = s_begin + sbt;
+    const float *s_logp = reinterpret_cast<const float*>(s_end + sbt), *s_score = s_logp + sbt;
+    for (int b = 0; b < batch; ++b)
+      if (spans->max_tokens < m->token_num[b] - 4) return fail(PFHIP_ERR_CAPACITY, "spans: max_tokens smaller than the longest token list");
+    for (int b = 0; b < batch; ++b) {
+      const int n = std::max(m->token_num[b] - 4, 0);
+      const size_t dst = (size_t)b * spans->max_tokens, src = (size_t)b * mt;
+      for (int j = 0; j < n; ++j) {                // tok_frame's numbering: the prompt rows counted; beyond the slots: refused by the kernel
+        const int32_t tb = j < mt ? s_begin[src + j] : -1, te = j < mt ? s_end[src + j] : -1;
+        spans->tok_begin[dst + j] = tb < 0 ? -1 : tb + 4;
+        spans->tok_end[dst + j] = te < 0 ? -1 : te + 4;
+        if (spans->tok_logp) spans->tok_logp[dst + j] = j < mt ? s_logp[src + j] : -INFINITY;
+      }
+      if (spans->score) spans->score[b] = s_score[b];
+    }
+  }
   return PFHIP_OK;
 }
 
@@ -115,6 +284,18 @@ int pfhip_svs_lid(const char* svs_lang) {
   return 0;
 }
 
+// pfhip_set_batching's sibling for a CTC handle: the same queue, the same two knobs
+pfhip_status pfhip_svs_set_batching(pfhip_model* m, int wait_us, int max_utterances) {
+  g_err.clear();
+  if (!m || wait_us < 0 || max_utterances < 1) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!is_svs(m)) return fail(PFHIP_ERR_UNSUPPORTED, "not a SenseVoice (CTC) model: a Paraformer handle takes pfhip_set_batching");
+  if (!m->replicas.empty()) return fail(PFHIP_ERR_UNSUPPORTED, "multi-device groups are not built for SenseVoice (CTC) models");
+  std::lock_guard<std::mutex> ql(m->bq.mu);
+  m->batch_wait_us = wait_us;
+  m->batch_max_utts = max_utterances;
+  return PFHIP_OK;
+}
+
 pfhip_status pfhip_svs_forward(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                const int32_t* textnorm, pfhip_svs_out* out) {
   return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out);
@@ -122,6 +303,15 @@ pfhip_status pfhip_svs_forward(pfhip_model* m, const float* const* pcm, const in
 pfhip_status pfhip_svs_forward_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                    const int32_t* textnorm, pfhip_svs_out* out) {
   return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out);
+}
+// the forward with the spans of its greedy tokens (ids[b][4:]) in the same stream work, copy and synchronise; spans == NULL: the above
+pfhip_status pfhip_svs_forward_spans(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                     const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans) {
+  return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out, spans);
+}
+pfhip_status pfhip_svs_forward_spans_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                         const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans) {
+  return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out, spans);
 }
 
 // CTC forced alignment of caller-given tokens against the rows of the calling thread's last pfhip_svs_forward (ctc_align.hip): the
@@ -142,7 +332,10 @@ pfhip_status pfhip_svs_align(pfhip_model* head, const int32_t* const* tokens, co
   std::lock_guard<std::mutex> lk(m->mu);
   if (!m->svs_fwd_ok || m->svs_serial != note->second.serial)
     return fail(PFHIP_ERR_ARG, "the rows of this thread's last pfhip_svs_forward are gone: its execution context has run another forward since");
-  if (batch != m->B) return fail(PFHIP_ERR_ARG, "batch differs from that of the last pfhip_svs_forward");
+  // the caller's utterances within that forward: all of a lone forward, its own sub-range of a merged one (never another caller's rows)
+  const int u0 = note->second.u0;
+  if (batch != note->second.batch || u0 < 0 || u0 + batch > m->B)
+    return fail(PFHIP_ERR_ARG, "batch differs from that of the last pfhip_svs_forward");
   const ModelWeights& w = *m->weights;
   const Config& c = w.cfg;
   const int V = c.vocab, d = c.d_model, B = batch;
@@ -168,8 +361,8 @@ pfhip_status pfhip_svs_align(pfhip_model* head, const int32_t* const* tokens, co
   long long* h_eoff = reinterpret_cast<long long*>(hm + n_i32);
   size_t e_floats = 0, lo = 0;
   for (int b = 0; b < B; ++b) {
-    const int N = m->T[b] > 4 ? m->T[b] - 4 : 0;                     // the speech rows: the four prompt rows are no CTC rows
-    hm[b] = m->row_off[b] + 4; hm[B + b] = N; hm[2 * B + b] = (int)lo; hm[3 * B + b] = n_tokens[b];
+    const int N = m->T[u0 + b] > 4 ? m->T[u0 + b] - 4 : 0;           // the speech rows: the four prompt rows are no CTC rows
+    hm[b] = m->row_off[u0 + b] + 4; hm[B + b] = N; hm[2 * B + b] = (int)lo; hm[3 * B + b] = n_tokens[b];
     for (int j = 0; j < n_tokens[b]; ++j) hm[4 * B + lo + j] = tokens[b][j];
     lo += (size_t)n_tokens[b];
     h_eoff[b] = (long long)e_floats;

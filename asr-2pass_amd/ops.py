@@ -46,6 +46,8 @@ def _lib():
             lib.pfhip_op_ctc_collapse.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp]
         if hasattr(lib, "pfhip_op_ctc_align"):
             lib.pfhip_op_ctc_emissions.argtypes = [_vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
+            if hasattr(lib, "pfhip_op_ctc_greedy_plan"):
+                lib.pfhip_op_ctc_greedy_plan.argtypes = [_vp, _vp, _ci, _ci, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp]
             lib.pfhip_op_ctc_align_workspace_bytes.restype = ctypes.c_size_t
             lib.pfhip_op_ctc_align_workspace_bytes.argtypes = [ctypes.c_size_t]
             lib.pfhip_op_ctc_align.argtypes = [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp,
@@ -481,6 +483,20 @@ def ctc_emissions(X, W, bias, lse, row_off, lab, blank=0, V=None, E=None, e_base
                                       _p(lab.n_lab), _p(lab.labels), _p(e_off), lab.B, X.shape[1], V, int(blank), _p(E), _stream()),
         "ctc_emissions")
     return E
+
+
+def ctc_greedy_plan(token_num, speech_len, maxT, cap_floats):
+    """The sizes of a greedy alignment from the collapse's counts, on the device (csrc/ctc_align.hip ctc_greedy_plan_kernel):
+    (n_lab, lab_off [B] int32, e_off [B] int64, total: int64 scalar tensor).  token_num / speech_len: device int32 tensors."""
+    B = token_num.numel()
+    dev = token_num.device
+    n_lab = torch.full((max(B, 1),), -77, dtype=torch.int32, device=dev)
+    lab_off = torch.full((max(B, 1),), -77, dtype=torch.int32, device=dev)
+    e_off = torch.full((max(B, 1),), -77, dtype=torch.int64, device=dev)
+    total = torch.full((1,), -77, dtype=torch.int64, device=dev)
+    _ck(_lib().pfhip_op_ctc_greedy_plan(_p(token_num), _p(speech_len), B, int(maxT), int(cap_floats), _p(n_lab), _p(lab_off), _p(e_off),
+                                        _p(total), _stream()), "ctc_greedy_plan")
+    return n_lab[:B], lab_off[:B], e_off[:B], total[0]
 
 
 def ctc_align_workspace_bytes(e_floats):

@@ -639,8 +639,15 @@ pfhip_status pfhip_punc_add_punc(pfhip_punc* p, const int32_t* ids, int n, int32
  * runs it one utterance at a time (sensevoice-small.cpp:575-690 refuses batch_in != 1); here utterances are packed as everywhere.
  * Model widths and wiring are recalled from upstream FunASR: no SenseVoice file was available when this was written.
  *   pfhip_is_ctc          1 for such a handle.  Every Paraformer forward, pfhip_stream_create and pfhip_set_batching return
- *                         PFHIP_ERR_UNSUPPORTED on it (merging concurrent callers is not built for this kind), and
- *                         pfhip_svs_forward does on a Paraformer handle.
+ *                         PFHIP_ERR_UNSUPPORTED on it, and pfhip_svs_forward does on a Paraformer handle.
+ *   pfhip_svs_set_batching   pfhip_set_batching for such a handle (which keeps refusing it; PFHIP_ERR_UNSUPPORTED here on a
+ *                         Paraformer handle and on a multi-device group): concurrent pfhip_svs_forward[_spans][_s16] callers
+ *                         are merged into packed forwards by the rules stated at pfhip_set_batching (a lone caller on an idle
+ *                         device runs at once, one sample format per packed forward, wait_us = 0: off), each with its own lid /
+ *                         textnorm per utterance, its own buffers and its own max_tokens (too small: that caller alone gets
+ *                         PFHIP_ERR_CAPACITY).  A caller asking for `logp` costs the others nothing: the fused head runs over all
+ *                         rows and the unfused chunks over that caller's rows only.  Results are those of separate calls up to
+ *                         the near-tie statement made for merged Paraformer callers (log-probs 1e-4).
  *   pfhip_svs_lid     <-> lid_map (sensevoice-small.h:121-129) with the look-up of sensevoice-small.cpp:597-602: "auto" 0, "zh" 3,
  *                         "en" 4, "yue" 7, "ja" 11, "ko" 12, "nospeech" 13; any other string (or NULL) 0.
  *   pfhip_svs_forward <-> SenseVoiceSmall::Forward (sensevoice-small.cpp:575-690): LfrCmvn features behind the four prompt rows
@@ -658,6 +665,7 @@ pfhip_status pfhip_punc_add_punc(pfhip_punc* p, const int32_t* ids, int n, int32
  * unfused head (GEMM + log-softmax over chunks of 2048 rows: at most 2 x 2048 x vocab floats of scratch, never rows x vocab). */
 int pfhip_is_ctc(const pfhip_model* m);
 int pfhip_svs_lid(const char* svs_lang);
+pfhip_status pfhip_svs_set_batching(pfhip_model* m, int wait_us, int max_utterances);
 typedef struct pfhip_svs_out {
   int32_t* ids; int32_t* token_num; int max_tokens;
   int32_t* tok_frame; float* tok_logp;
@@ -674,7 +682,8 @@ pfhip_status pfhip_svs_forward_s16(pfhip_model* m, const int16_t* const* pcm, co
  * THREAD's last pfhip_svs_forward[_s16] on this handle left in its execution context — the lifetime rule of pfhip_get_tensor: valid
  * until that context runs its next forward (a later forward of ANOTHER thread that landed on the same context included: the call then
  * returns PFHIP_ERR_ARG instead of aligning against rows that are not the caller's, and the caller goes without spans or repeats
- * the pair) — so `batch` must equal that forward's.  The frames are the speech rows only (the four
+ * the pair) — so `batch` must equal that forward's.  After a MERGED forward (pfhip_svs_set_batching) the rows are the caller's own
+ * sub-range of the packed batch, under the same lifetime rule; never another caller's.  The frames are the speech rows only (the four
  * prompt rows are no CTC rows), so tokens[b] are ids AFTER the four leading tags: ids[b][4:] of the forward for the greedy text, or
  * any other sequence (a search result, a transcript the caller has).  The blank is the container's blank_id.  Emissions are
  * x . ctc.w[id] + ctc.b[id] - log-sum-exp of the row, formed for the blank and the tokens asked for only (pfhip_op_ctc_emissions);
@@ -688,6 +697,23 @@ pfhip_status pfhip_svs_forward_s16(pfhip_model* m, const int16_t* const* pcm, co
  * the longest n_tokens.  The forward itself is unchanged by this: it only keeps the row log-sum-exp both heads form anyway. */
 typedef struct pfhip_svs_align_out { int32_t* tok_begin; int32_t* tok_end; float* tok_logp; float* score; int max_tokens; } pfhip_svs_align_out;
 pfhip_status pfhip_svs_align(pfhip_model* m, const int32_t* const* tokens, const int* n_tokens, int batch, pfhip_svs_align_out* out);
+/* pfhip_svs_forward[_s16] and the alignment of its own GREEDY tokens in ONE call: with spans != NULL each utterance's text tokens (its
+ * kept ids behind the four tags, ids[b][4:]) are aligned against its own speech rows inside the forward's stream work — a plan kernel
+ * turns the collapse's counts into the alignment's sizes on the device (pfhip_op_ctc_greedy_plan), then the two kernels of
+ * pfhip_svs_align — and the spans travel in the forward's one device-to-host copy, before its one synchronise: no second upload,
+ * copy or synchronise.  What comes back in `out` is that of pfhip_svs_forward bit for bit, and what comes back in `spans` is that of
+ * pfhip_svs_align(ids[b][4:]) after it bit for bit (same rows, same kernels); after a range-guard re-run both belong to the re-run.
+ * spans->max_tokens counts the tokens BEHIND the tags (PFHIP_ERR_CAPACITY below the longest token_num[b] - 4); tok_begin / tok_end are
+ * required, tok_logp / score may be NULL.  spans == NULL: pfhip_svs_forward itself, which launches what it always launched.
+ * The emissions and back-pointers are sized before the launch from n_lab[b] <= N_b (a kept token needs a frame): sum_b N_b (N_b + 1)
+ * floats over the batch's speech rows N_b, capped at PFHIP_SVS_SPAN_MAX_FLOATS (96 utterances of 30 s need 24 M; the back-pointers
+ * take two bytes per float on top).  An utterance whose emissions would end beyond the cap is answered as an infeasible one — spans
+ * -1, score -inf — and the others are served; align it with pfhip_svs_align, or in a smaller batch. */
+#define PFHIP_SVS_SPAN_MAX_FLOATS ((size_t)64 << 20)
+pfhip_status pfhip_svs_forward_spans(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                     const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans);
+pfhip_status pfhip_svs_forward_spans_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                         const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans);
 
 /* ---- inspection (parity tests) -----------------------------------------------------------------
  * Copies a named intermediate of the LAST forward to host: "feats" [M,560], "enc" [M,d],
@@ -738,7 +764,11 @@ pfhip_status pfhip_group_stats(pfhip_model* m, int* devices, int64_t* calls, int
  * "format_splits" how many merged batches (pfhip_set_batching) were cut short because f32 and s16 callers were queued together;
  * "ctc_unfused" (value != 0) sends the next pfhip_svs_forward of EVERY execution context of the handle through the unfused CTC head
  * (once each: with pfhip_set_inflight(1) that is the next forward); "ctc_unfused_forwards" returns how many forwards took that head,
- * summed over the contexts; "ctc_head_chunks" how many row chunks the unfused head of the calling thread's last forward ran. */
+ * summed over the contexts; "ctc_head_chunks" how many row chunks the unfused head of the calling thread's last forward ran;
+ * "svs_span_cap" (value floats, 0 = back to the constant) stands in for PFHIP_SVS_SPAN_MAX_FLOATS on every context of the handle;
+ * "svs_unfused_rows" how many rows went through the unfused head chunks in the forward — lone or merged — that served the calling
+ * thread's last pfhip_svs_forward[_spans] (a merged forward sends only the rows of the callers who asked for log-prob rows), and
+ * "svs_forward_calls" how many callers that forward served (1: a lone caller). */
 pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value);
 pfhip_status pfhip_profile_enable(pfhip_model* m, int on);
 pfhip_status pfhip_profile_read(pfhip_model* m, pfhip_profile* out, int reset);

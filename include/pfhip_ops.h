@@ -172,6 +172,17 @@ int pfhip_op_ctc_collapse_chunk(void);
 int pfhip_op_ctc_emissions(const float* X, int ldx, const float* W, int ldw, const float* bias, const float* lse, const int* row_off,
                            const int* len, const int* lab_off, const int* n_lab, const int32_t* labels, const long long* e_off, int B,
                            int K, int V, int blank, float* E, void* stream);
+/* The step between pfhip_op_ctc_collapse and the two alignment kernels when the GREEDY tokens are aligned with no host round trip
+ * (pfhip_svs_forward_spans): token_num [B] is the collapse's (device), speech_len [B] the rows N_b each utterance is aligned against
+ * (device; the host knows them before the forward).  n_lab[b] = max(token_num[b] - 4, 0) — the kept ids behind the four tags —,
+ * lab_off[b] = b * maxT + 4, so that `labels` is the collapse's own ids [B][maxT], e_off[b] = the exclusive int64 prefix sum of
+ * N_b * (n_lab[b] + 1), *total (may be NULL) = that sum over every b.  An utterance whose E_b would end beyond cap_floats gets
+ * n_lab[b] = -1 (its e_off and the total are the sums all the same); pfhip_op_ctc_emissions leaves such an utterance unwritten and
+ * pfhip_op_ctc_align answers it as infeasible.  token_num[b] > maxT or N_b < 0, which no collapse over maxT rows produces: n_lab -1 and
+ * nothing added to the sums.  One workgroup of 256 threads, a block scan through LDS.  hipErrorInvalidValue, before anything is
+ * launched, for B outside 0 .. 65535, maxT < 0, cap_floats < 0, B * maxT + 4 above INT_MAX or a NULL buffer other than total. */
+int pfhip_op_ctc_greedy_plan(const int32_t* token_num, const int* speech_len, int B, int maxT, long long cap_floats, int* n_lab, int* lab_off,
+                             long long* e_off, long long* total, void* stream);
 /* Step 2: the best path through the CTC trellis of each utterance and the spans of its labels.  E / e_off / len / n_lab / labels /
  * lab_off as above (the label ids only decide which neighbours are the same label); e_floats = the floats of E.
  *   N = len[b] frames, labels y_1 .. y_L, states s = 0 .. 2 L: s even is the blank (column 0), s odd is label (s + 1) / 2.

@@ -10,7 +10,10 @@ call's host work.  The two kernels are then timed on their own through the opera
 
 Prints one JSON line: medians, minima and maxima in ms, the rows / tokens / states of the batch and align_over_forward.
 
-  python tools/svs_align_bench.py [--batch 32] [--seconds 30] [--steps 10] [--warmup 3] [--reps 20]
+--in-forward adds the A/B of the one-call form: per step, interleaved, (A) forward + pfhip_svs_align on ids[b][4:] against (B)
+pfhip_svs_forward_spans, which forms the same spans inside the forward; "two_calls" / "one_call" in the JSON, wall clock.
+
+  python tools/svs_align_bench.py [--batch 32] [--seconds 30] [--steps 10] [--warmup 3] [--reps 20] [--in-forward]
 """
 import argparse
 import importlib
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--in-forward", action="store_true")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
@@ -78,6 +82,23 @@ def main():
            "rows": sum(rows), "speech_rows_max": max(rows) - 4, "tokens": sum(len(y) for y in tokens), "tokens_max": max(len(y) for y in tokens),
            "feasible": int(np.isfinite(al["score"]).sum()), "forward": stats(t_fwd), "align": stats(t_al)}
     res["align_over_forward"] = round(res["align"]["ms_median"] / res["forward"]["ms_median"], 4)
+
+    if args.in_forward:
+        t_two, t_one = [], []
+        for step in range(args.warmup + max(args.steps, 1)):
+            t0 = time.perf_counter()
+            got = model.forward(utts, lang="auto", itn=False)
+            al = model.align([ids[4:] for ids in got["ids"]])
+            t1 = time.perf_counter()
+            one = model.forward(utts, lang="auto", itn=False, want_spans=True)
+            t2 = time.perf_counter()
+            if step >= args.warmup:
+                t_two.append(1e3 * (t1 - t0))
+                t_one.append(1e3 * (t2 - t1))
+        res["two_calls"], res["one_call"] = stats(t_two), stats(t_one)
+        res["spans_equal"] = bool(all(np.array_equal(a, b) for a, b in zip(al["begin"], one["span_begin"])) and
+                                  all(np.array_equal(a, b) for a, b in zip(al["end"], one["span_end"])))
+        res["span_tokens"] = int(sum(len(x) for x in one["span_begin"]))
 
     # the two kernels alone, on the shapes and labels of that batch
     d, V = int(cfg["d_model"]), int(cfg["vocab"])
