@@ -61,6 +61,9 @@ ABI_SYMBOLS = [
     "pfhip_svs_forward_spans", "pfhip_svs_forward_spans_s16",
     # SenseVoiceSmall: concurrent callers merged into packed forwards
     "pfhip_svs_set_batching",
+    # speech quality: the DNSMOS networks
+    "pfhip_mos_create_from_files", "pfhip_mos_create_from_memory", "pfhip_mos_destroy", "pfhip_mos_set_workspace", "pfhip_mos_score",
+    "pfhip_mos_score_s16", "pfhip_mos_score_windows", "pfhip_mos_score_windows_s16",
 ]
 
 
@@ -1361,3 +1364,11 @@ def cif_timestamps(fire_frame, n_chars, n_frames, frame_ms=60.0, begin_time=0.0,
         raise err
     _check(lib, rc)
     return [(float(s[0]), float(s[1]), bool(s[2])) for s in spans[:n.value]]
+
+
+def __getattr__(name):
+    # DnsMosHip (dnsmos.py) runs on the operator bindings, which import torch: loaded on first use
+    if name == "DnsMosHip":
+        from .dnsmos import DnsMosHip
+        return DnsMosHip
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

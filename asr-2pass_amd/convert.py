@@ -390,3 +390,11 @@ def load_state_dict(path):
         if isinstance(obj, dict) and k in obj and isinstance(obj[k], dict):
             obj = obj[k]
     return obj
+
+
+def convert_dnsmos(primary, p808=None):
+    """The DNSMOS speech-quality networks (utils/DNSMOS/sig_bak_ovr.onnx or utils/pDNSMOS/sig_bak_ovr.onnx, and optionally
+    utils/DNSMOS/model_v8.onnx) -> (manifest, blob) of kind "dnsmos", the container pfhip_mos_create_from_memory takes: bit for bit
+    what the C++ reader (csrc/mos_files.cpp, pfhip_read_model_files("dnsmos", ...)) makes of the same files."""
+    from .dnsmos import container
+    return container(primary, p808)

@@ -465,4 +465,42 @@ void launch_resample(const float* in, const int64_t* in_off, const int* n_in, fl
 void launch_resample(const int16_t* in, const int64_t* in_off, const int* n_in, float* out, const int64_t* out_off, const int* n_out,
                      int B, const ResampleTable& t, hipStream_t s);
 
+// ---- the DNSMOS networks (conv3x3.hip, dnsmos.hip) ---------------------------------------------
+// 3x3 / pad 1 / stride 1 convolution + bias + ReLU on NHWC fp32 activations, x [N][H][W][Cin] -> y [N][H][W][Cout], or with `pool`
+// the 2x2 / stride 2 floor max-pool of that, y [N][H / 2][W / 2][Cout].  Every launcher returns false, having launched nothing, for
+// what its kernel does not take.
+// Cin 32 or a multiple of 64, Cout 32 or 64: implicit GEMM on two fp16 planes.  The weights are packed once (launch_conv3x3_pack: ONNX
+// [Cout][Cin][3][3] fp32 -> two plane images of conv3x3_plane_bytes(Cin, Cout) bytes each, times the power of two `scale` =
+// best_w_scale(max |w|)) and the same scale is passed to the convolution as w_scale.  N <= 65535.
+size_t conv3x3_plane_bytes(int Cin, int Cout);
+bool launch_conv3x3_pack(const float* w, int Cin, int Cout, float scale, void* hi, void* lo, hipStream_t s);
+bool launch_conv3x3_relu(const float* x, const void* whi, const void* wlo, float w_scale, const float* bias, float* y, int N, int H, int W,
+                         int Cin, int Cout, bool pool, hipStream_t s);
+// Cin == 1: x [N][H][W], w the ONNX [Cout][1][3][3]; nine FMAs in the order ky, kx ascending.
+bool launch_conv3x3_c1_relu(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cout, bool pool,
+                            hipStream_t s);
+// The primary net's front end: window i = the (n_frames + 1) * 160 samples at pcm + win_off[i] (device int64 array; n_win <= 65535),
+// frame f = samples [160 f, 160 f + 320); out [n_win][n_frames][161] = log(max(floor_v, sqrt(re^2 + im^2)^2)) / denom with re / im
+// against tab [320][2][kDnsmosBinStride], which dnsmos_stft_table builds on the host from the graph's two [161][320] STFT kernels.
+// s16: x = (float)s * (1 / 32768), bit for bit the f32 call.
+constexpr int kDnsmosBinStride = 168;
+constexpr int kDnsmosMelFrames = 900, kDnsmosMels = 120, kDnsmosFft = 321;
+void dnsmos_stft_table(const float* wr, const float* wi, float* tab);
+bool launch_dnsmos_logpow(const float* pcm, const int64_t* win_off, int n_win, const float* tab, int n_frames, float floor_v, float denom,
+                          float* out, hipStream_t s);
+bool launch_dnsmos_logpow(const int16_t* pcm, const int64_t* win_off, int n_win, const float* tab, int n_frames, float floor_v, float denom,
+                          float* out, hipStream_t s);
+// The P.808 net's input: out [n_win][900][120] = (power_to_db(melspectrogram(first 144000 samples of window i), ref = max) + 40) / 40,
+// transposed (dnsmos.hip's head says which settings are recalled).  dnsmos_mel_tables fills (host) tab [321][2][kDnsmosBinStride] and
+// melT [161][120]; wmax = n_win device words of scratch.
+void dnsmos_mel_tables(float* tab, float* melT);
+bool launch_dnsmos_melspec(const float* pcm, const int64_t* win_off, int n_win, const float* tab, const float* melT, float* out,
+                           unsigned* wmax, hipStream_t s);
+bool launch_dnsmos_melspec(const int16_t* pcm, const int64_t* win_off, int n_win, const float* tab, const float* melT, float* out,
+                           unsigned* wmax, hipStream_t s);
+// The head: max over the HW pixels of x [N][HW][C], then three dense layers y = x W + b with W [in][out] as the graph's MatMul holds
+// it, ReLU after the first two; out [N][D3].  C, D1, D2, D3 <= 256.
+bool launch_globalmax_mlp(const float* x, int N, int HW, int C, const float* w1, const float* b1, int D1, const float* w2, const float* b2,
+                          int D2, const float* w3, const float* b3, int D3, float* out, hipStream_t s);
+
 }  // namespace pfhip

@@ -169,11 +169,18 @@ void attribute(Span buf, Node& nd) {
   int64_t iv = 0;
   Fields it(buf);
   Field f;
+  std::vector<int64_t> list;
+  std::string sv;
+  bool has_s = false;
   while (it.next(f)) {
     if (f.no == 1 && f.wt == 2) name = text(f.s);
     else if (f.no == 3 && f.wt == 0) { iv = (int64_t)f.v; has_i = true; }
+    else if (f.no == 4 && f.wt == 2) { sv = text(f.s); has_s = true; }      // 4 s
+    else if (f.no == 8 && (f.wt == 0 || f.wt == 2)) ints(f, list);          // 8 ints
   }
   if (has_i) nd.int_attrs[name] = iv;
+  if (has_s) nd.str_attrs[name] = sv;
+  if (!list.empty()) nd.ints_attrs[name] = list;
 }
 
 // NodeProto: 1 input, 2 output, 3 name, 4 op_type, 5 attribute

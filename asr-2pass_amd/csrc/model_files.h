@@ -35,6 +35,8 @@ struct Node {
   std::string op_type, name;
   std::vector<std::string> inputs, outputs;
   std::map<std::string, int64_t> int_attrs;
+  std::map<std::string, std::vector<int64_t>> ints_attrs;      // pads, strides, kernel_shape, ... (the DNSMOS family check)
+  std::map<std::string, std::string> str_attrs;                // auto_pad
 };
 
 struct OnnxModel {
@@ -96,5 +98,11 @@ void load_asr(const std::string& model, const std::string& second, const std::st
               const std::string& config, Container& out);
 void load_vad(const std::string& model, const std::string& cmvn, const std::string& config, Container& out);
 void load_punc(const std::string& model, const std::string& config, Container& out);
+// The DNSMOS speech-quality networks (mos_files.cpp): utils/DNSMOS/sig_bak_ovr.onnx (or pDNSMOS/) and, optionally (""),
+// utils/DNSMOS/model_v8.onnx -> a container of kind "dnsmos".  The Conv / MaxPool / MatMul nodes are walked in graph order and every
+// kernel, bias and constant is taken from the file; a graph that is not of this family is refused with a FormatError naming the first
+// node that does not fit.  No cache is written.
+void load_dnsmos(const std::string& primary, const std::string& p808, Container& out);
+void load_dnsmos_bytes(const void* primary, size_t primary_bytes, const void* p808, size_t p808_bytes, Container& out);
 
 }  // namespace pfhip_files

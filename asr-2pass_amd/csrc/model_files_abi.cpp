@@ -28,7 +28,8 @@ pfhip_status read_files(const std::string& kind, const char* model, const char* 
     }
     else if (kind == "vad") pfhip_files::load_vad(nz(model), nz(cmvn), nz(config), c);
     else if (kind == "punc") pfhip_files::load_punc(nz(model), nz(config), c);
-    else return fail(PFHIP_ERR_ARG, "kind must be asr, sensevoice, vad or punc");
+    else if (kind == "dnsmos") pfhip_files::load_dnsmos(nz(model), nz(second), c);      // model = the primary net, second = model_v8.onnx
+    else return fail(PFHIP_ERR_ARG, "kind must be asr, sensevoice, vad, punc or dnsmos");
   } catch (const pfhip_files::FormatError& e) {
     return fail(PFHIP_ERR_FORMAT, e.what());
   } catch (const std::exception& e) {

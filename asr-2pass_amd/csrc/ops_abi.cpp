@@ -3,6 +3,8 @@
 
 #include "internal.h"      // build_frontend_tables, DevMem; brings kernels.h
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace {
@@ -708,6 +710,113 @@ int pfhip_op_gather_best(const float* logp, int ld, const int32_t* ids, int M, f
 int pfhip_op_row_lse(const float* logits, int ld, int M, int V, float* lse, void* stream) {
   if (!logits || !lse || M < 0 || V < 1 || ld < V) return kInvalid;
   pfhip::launch_row_lse(logits, ld, M, V, lse, S(stream));
+  return done();
+}
+
+}  // extern "C"
+
+// ---- the DNSMOS networks' kernels (conv3x3.hip, dnsmos.hip), one entry each ----------------------------------------------------------
+namespace {
+// window offsets from a HOST array: every window's samples must lie inside pcm
+bool windows_inside(const int64_t* win_off, int n_win, long long need, long long pcm_samples) {
+  for (int i = 0; i < n_win; ++i)
+    if (win_off[i] < 0 || win_off[i] + need > pcm_samples) return false;
+  return true;
+}
+template <typename Sample>
+int logpow_op(const Sample* pcm, long long pcm_samples, const int64_t* win_off, int n_win, int n_frames, const float* stft_real,
+              const float* stft_imag, float floor_v, float power, float denom, float* out, void* stream) {
+  // the graph's Pow exponent is the initialiser 2.0: the kernel squares
+  if (!pcm || !win_off || !stft_real || !stft_imag || !out || n_win < 0 || n_win > 65535 || n_frames < 1 || n_frames > 1 << 20 ||
+      power != 2.0f || !(denom != 0.f) || !windows_inside(win_off, n_win, 160LL * (n_frames + 1), pcm_samples))
+    return kInvalid;
+  if (n_win == 0) return 0;
+  std::vector<float> wr(161 * 320), wi(161 * 320), tab((size_t)320 * 2 * pfhip::kDnsmosBinStride);
+  hipError_t e = hipMemcpy(wr.data(), stft_real, wr.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(wi.data(), stft_imag, wi.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return (int)e;
+  pfhip::dnsmos_stft_table(wr.data(), wi.data(), tab.data());
+  pfhip_impl::DevMem d_tab, d_off;
+  e = d_tab.upload(tab);
+  if (e == hipSuccess) e = d_off.upload(win_off, sizeof(int64_t) * n_win);
+  if (e != hipSuccess) return (int)e;
+  bool ok = true;
+  const int rc = launch_and_drain(S(stream), [&] {
+    ok = pfhip::launch_dnsmos_logpow(pcm, d_off.as<int64_t>(), n_win, d_tab.f(), n_frames, floor_v, denom, out, S(stream));
+  });
+  return ok ? rc : kInvalid;
+}
+template <typename Sample>
+int melspec_op(const Sample* pcm, long long pcm_samples, const int64_t* win_off, int n_win, float* out, void* stream) {
+  if (!pcm || !win_off || !out || n_win < 0 || n_win > 65535 || !windows_inside(win_off, n_win, 144000, pcm_samples)) return kInvalid;
+  if (n_win == 0) return 0;
+  std::vector<float> tab((size_t)pfhip::kDnsmosFft * 2 * pfhip::kDnsmosBinStride), melT((size_t)161 * pfhip::kDnsmosMels);
+  pfhip::dnsmos_mel_tables(tab.data(), melT.data());
+  pfhip_impl::DevMem d_tab, d_mel, d_off, d_max;
+  hipError_t e = d_tab.upload(tab);
+  if (e == hipSuccess) e = d_mel.upload(melT);
+  if (e == hipSuccess) e = d_off.upload(win_off, sizeof(int64_t) * n_win);
+  if (e == hipSuccess) e = d_max.alloc(sizeof(unsigned) * n_win);
+  if (e != hipSuccess) return (int)e;
+  bool ok = true;
+  const int rc = launch_and_drain(S(stream), [&] {
+    ok = pfhip::launch_dnsmos_melspec(pcm, d_off.as<int64_t>(), n_win, d_tab.f(), d_mel.f(), out, d_max.as<unsigned>(), S(stream));
+  });
+  return ok ? rc : kInvalid;
+}
+}  // namespace
+
+extern "C" {
+
+int pfhip_op_conv3x3_relu(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int pool,
+                          void* stream) {
+  if (!x || !w || !bias || !y || N < 0 || H < 1 || W < 1) return kInvalid;
+  if (Cin == 1) {
+    if (!pfhip::launch_conv3x3_c1_relu(x, w, bias, y, N, H, W, Cout, pool != 0, S(stream))) return kInvalid;
+    return done();
+  }
+  if (!(Cin == 32 || (Cin >= 64 && Cin % 64 == 0 && Cin <= 4096)) || (Cout != 32 && Cout != 64)) return kInvalid;
+  // what a model does once at load: the weights' largest magnitude fixes the power-of-two scale of their plane images; a weight
+  // that is not finite has no place in the fp16 two-plane domain and is refused
+  std::vector<float> hw((size_t)Cout * Cin * 9);
+  hipError_t e = hipMemcpy(hw.data(), w, hw.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return (int)e;
+  float mx = 0.f;
+  for (float v : hw) {
+    if (!std::isfinite(v)) return kInvalid;
+    mx = std::max(mx, std::fabs(v));
+  }
+  const float scale = pfhip::best_w_scale(mx);
+  if (!(mx * scale <= 32768.0f)) return kInvalid;
+  pfhip_impl::DevMem hi, lo;
+  e = hi.alloc(pfhip::conv3x3_plane_bytes(Cin, Cout));
+  if (e == hipSuccess) e = lo.alloc(pfhip::conv3x3_plane_bytes(Cin, Cout));
+  if (e != hipSuccess) return (int)e;
+  bool ok = true;
+  const int rc = launch_and_drain(S(stream), [&] {
+    ok = pfhip::launch_conv3x3_pack(w, Cin, Cout, scale, hi.p, lo.p, S(stream)) &&
+         pfhip::launch_conv3x3_relu(x, hi.p, lo.p, scale, bias, y, N, H, W, Cin, Cout, pool != 0, S(stream));
+  });
+  return ok ? rc : kInvalid;
+}
+int pfhip_op_dnsmos_logpow(const float* pcm, long long pcm_samples, const int64_t* win_off, int n_win, int n_frames, const float* stft_real,
+                           const float* stft_imag, float floor_v, float power, float denom, float* out, void* stream) {
+  return logpow_op(pcm, pcm_samples, win_off, n_win, n_frames, stft_real, stft_imag, floor_v, power, denom, out, stream);
+}
+int pfhip_op_dnsmos_logpow_s16(const int16_t* pcm, long long pcm_samples, const int64_t* win_off, int n_win, int n_frames,
+                               const float* stft_real, const float* stft_imag, float floor_v, float power, float denom, float* out,
+                               void* stream) {
+  return logpow_op(pcm, pcm_samples, win_off, n_win, n_frames, stft_real, stft_imag, floor_v, power, denom, out, stream);
+}
+int pfhip_op_dnsmos_melspec(const float* pcm, long long pcm_samples, const int64_t* win_off, int n_win, float* out, void* stream) {
+  return melspec_op(pcm, pcm_samples, win_off, n_win, out, stream);
+}
+int pfhip_op_dnsmos_melspec_s16(const int16_t* pcm, long long pcm_samples, const int64_t* win_off, int n_win, float* out, void* stream) {
+  return melspec_op(pcm, pcm_samples, win_off, n_win, out, stream);
+}
+int pfhip_op_globalmax_mlp(const float* x, int N, int HW, int C, const float* w1, const float* b1, int D1, const float* w2, const float* b2,
+                           int D2, const float* w3, const float* b3, int D3, float* out, void* stream) {
+  if (!pfhip::launch_globalmax_mlp(x, N, HW, C, w1, b1, D1, w2, b2, D2, w3, b3, D3, out, S(stream))) return kInvalid;
   return done();
 }
 

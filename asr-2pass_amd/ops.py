@@ -948,3 +948,83 @@ def row_lse(logits, M, V, lse):
     lib = _lib()
     lib.pfhip_op_row_lse.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp]
     _ck(lib.pfhip_op_row_lse(_p(logits), logits.stride(0), int(M), int(V), _p(lse), _stream()), "row_lse")
+
+
+# ---- the DNSMOS networks' kernels (csrc/conv3x3.hip, csrc/dnsmos.hip) ----------------------------------------------------------------
+def conv3x3_relu(x, w, bias, pool=False, out=None):
+    """Conv 3x3 / pad 1 / stride 1 + bias + ReLU (+ the 2x2 floor max-pool) on NHWC float32: x [N, H, W, Cin] ([N, H, W] for Cin == 1),
+    w the ONNX [Cout, Cin, 3, 3], bias [Cout] -> [N, H, W, Cout], pooled [N, H // 2, W // 2, Cout].  `out`: a float32 device tensor
+    with room for the result (tests pass one with a canary behind it)."""
+    lib = _lib()
+    lib.pfhip_op_conv3x3_relu.argtypes = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp]
+    Cout, Cin = int(w.shape[0]), int(w.shape[1])
+    N, H, W = (int(v) for v in x.shape[:3])
+    if not (x.is_contiguous() and w.is_contiguous() and bias.is_contiguous()) or x.numel() != N * H * W * Cin:
+        raise PfhipError("conv3x3_relu takes contiguous NHWC activations and ONNX-layout weights")
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+    elif out.numel() < N * Ho * Wo * Cout:
+        raise PfhipError("conv3x3_relu: out is too small")
+    _ck(lib.pfhip_op_conv3x3_relu(_p(x), _p(w), _p(bias), _p(out), N, H, W, Cin, Cout, 1 if pool else 0, _stream()), "conv3x3_relu")
+    return out
+
+
+def dnsmos_logpow(pcm, win_off, stft_real, stft_imag, n_frames=900, floor=1e-12, power=2.0, denom=2.3025851, out=None):
+    """The primary DNSMOS net's front end: pcm a float32 or int16 device tensor (int16 means s / 32768), window i the 160 * (n_frames + 1)
+    samples from win_off[i] (host ints); stft_real / stft_imag the graph's kernels [161, 320(, 1)]; floor / power / denom its three
+    scalar initialisers.  Returns [n_win, n_frames, 161]."""
+    lib = _lib()
+    lib.pfhip_op_dnsmos_logpow.argtypes = [_vp, ctypes.c_longlong, _vp, _ci, _ci, _vp, _vp, _cf, _cf, _cf, _vp, _vp]
+    lib.pfhip_op_dnsmos_logpow_s16.argtypes = lib.pfhip_op_dnsmos_logpow.argtypes
+    if pcm.dtype not in (torch.float32, torch.int16):
+        raise PfhipError("dnsmos_logpow takes float32 or int16 samples")
+    if stft_real.numel() != 161 * 320 or stft_imag.numel() != 161 * 320:
+        raise PfhipError("dnsmos_logpow: the STFT kernels are [161, 320]")
+    off, off_p = _hl(win_off)
+    if out is None:
+        out = torch.empty((len(off), n_frames, 161), dtype=torch.float32, device=pcm.device)
+    elif out.numel() < len(off) * n_frames * 161:
+        raise PfhipError("dnsmos_logpow: out is too small")
+    fn = lib.pfhip_op_dnsmos_logpow_s16 if pcm.dtype == torch.int16 else lib.pfhip_op_dnsmos_logpow
+    _ck(fn(_p(pcm), pcm.numel(), off_p, len(off), int(n_frames), _p(stft_real), _p(stft_imag), float(floor), float(power), float(denom),
+           _p(out), _stream()), "dnsmos_logpow")
+    return out
+
+
+def dnsmos_melspec(pcm, win_off, out=None):
+    """The P.808 DNSMOS net's input (dnsmos_local.py's audio_melspec; librosa's defaults recalled, see pfhip_ops.h): window i the
+    144000 samples from win_off[i] of the float32 / int16 device tensor pcm.  Returns [n_win, 900, 120]."""
+    lib = _lib()
+    lib.pfhip_op_dnsmos_melspec.argtypes = [_vp, ctypes.c_longlong, _vp, _ci, _vp, _vp]
+    lib.pfhip_op_dnsmos_melspec_s16.argtypes = lib.pfhip_op_dnsmos_melspec.argtypes
+    if pcm.dtype not in (torch.float32, torch.int16):
+        raise PfhipError("dnsmos_melspec takes float32 or int16 samples")
+    off, off_p = _hl(win_off)
+    if out is None:
+        out = torch.empty((len(off), 900, 120), dtype=torch.float32, device=pcm.device)
+    elif out.numel() < len(off) * 900 * 120:
+        raise PfhipError("dnsmos_melspec: out is too small")
+    fn = lib.pfhip_op_dnsmos_melspec_s16 if pcm.dtype == torch.int16 else lib.pfhip_op_dnsmos_melspec
+    _ck(fn(_p(pcm), pcm.numel(), off_p, len(off), _p(out), _stream()), "dnsmos_melspec")
+    return out
+
+
+def globalmax_mlp(x, w1, b1, w2, b2, w3, b3, out=None):
+    """Global max over H and W of x [N, H, W, C], then three dense layers y = x @ w + b (w [in, out], as the graph's MatMul holds it)
+    with ReLU after the first two.  Returns [N, D3]."""
+    lib = _lib()
+    lib.pfhip_op_globalmax_mlp.argtypes = [_vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp]
+    N, H, W, C = (int(v) for v in x.shape)
+    if not all(t.is_contiguous() for t in (x, w1, b1, w2, b2, w3, b3)):
+        raise PfhipError("globalmax_mlp takes contiguous tensors")
+    if w1.shape[0] != C or w2.shape[0] != w1.shape[1] or w3.shape[0] != w2.shape[1]:
+        raise PfhipError("globalmax_mlp: the dense layers do not chain")
+    D1, D2, D3 = int(w1.shape[1]), int(w2.shape[1]), int(w3.shape[1])
+    if out is None:
+        out = torch.empty((N, D3), dtype=torch.float32, device=x.device)
+    elif out.numel() < N * D3:
+        raise PfhipError("globalmax_mlp: out is too small")
+    _ck(lib.pfhip_op_globalmax_mlp(_p(x), N, H * W, C, _p(w1), _p(b1), D1, _p(w2), _p(b2), D2, _p(w3), _p(b3), D3, _p(out), _stream()),
+        "globalmax_mlp")
+    return out

@@ -773,6 +773,45 @@ pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value);
 pfhip_status pfhip_profile_enable(pfhip_model* m, int on);
 pfhip_status pfhip_profile_read(pfhip_model* m, pfhip_profile* out, int reset);
 
+/* ---- Speech quality: the DNSMOS networks (utils/dnsmos_local.py; an extension of scope) ----
+ *   pfhip_mos_create_from_files  <-> ComputeScore.__init__ (dnsmos_local.py:25-27): primary_onnx = utils/DNSMOS/sig_bak_ovr.onnx or
+ *                                utils/pDNSMOS/sig_bak_ovr.onnx, p808_onnx_or_null = utils/DNSMOS/model_v8.onnx (NULL: the p808 fields
+ *                                are NaN).  The graphs are walked node by node and every kernel, bias and constant is taken from the
+ *                                file; a graph that is not of this family is PFHIP_ERR_FORMAT with pfhip_last_error naming the first
+ *                                node that does not fit (the sig.onnx / bak_ovr.onnx variants are refused so).
+ *   pfhip_mos_create_from_memory a container of kind "dnsmos" (convert.py convert_dnsmos, or pfhip_read_model_files(kind "dnsmos",
+ *                                model = primary, second = p808) — the same bytes).  Weights are packed once here; a convolution
+ *                                weight that is not finite or leaves the fp16 two-plane range is PFHIP_ERR_UNSUPPORTED.
+ *   pfhip_mos_score[_s16]        <-> ComputeScore.__call__ (dnsmos_local.py:51-104) for n_clips clips of 16 kHz audio (f32 in [-1, 1] or
+ *                                16-bit PCM standing for s / 32768.f, bit for bit equal): a clip shorter than 144160 samples is
+ *                                appended to itself until it is not; num_hops = int(floor(len / 16000) - 9.01) + 1; window idx is
+ *                                [int(idx * 16000), int((idx + 9.01) * 16000)) in double, skipped where that is shorter than 144160;
+ *                                the raw P.835 outputs go through get_polyfit_val (plain or personalized); everything is averaged over
+ *                                the scored windows, on the host in double.  An empty clip is PFHIP_ERR_ARG.  Other sample rates go
+ *                                through pfhip_resample first (Kaldi's resampler, where the script calls librosa's).
+ *   pfhip_mos_score_windows[_s16] the per-window raw outputs behind that: raw [n_windows][4] = (p808, sig, bak, ovr), clip after clip,
+ *                                num_hops / n_scored [n_clips]; *n_windows is always set, PFHIP_ERR_CAPACITY above cap_windows.
+ *   pfhip_mos_set_workspace      the cap in bytes on the activations of one slab of windows (default 2 GiB; one window always runs).
+ *                                Results do not depend on it, nor on what else a call holds.
+ * A handle serves one call at a time (calls on one handle are serialised); pfhip_mos_destroy waits for the device first. */
+typedef struct pfhip_mos pfhip_mos;
+typedef struct {
+  int32_t num_hops, n_scored;
+  double p808, sig_raw, bak_raw, ovr_raw, sig, bak, ovr;
+} pfhip_mos_result;
+pfhip_status pfhip_mos_create_from_files(const char* primary_onnx, const char* p808_onnx_or_null, int device, pfhip_mos** out);
+pfhip_status pfhip_mos_create_from_memory(const void* blob, size_t blob_bytes, const char* manifest_json, int device, pfhip_mos** out);
+void pfhip_mos_destroy(pfhip_mos* h);
+pfhip_status pfhip_mos_set_workspace(pfhip_mos* h, size_t bytes);
+pfhip_status pfhip_mos_score(pfhip_mos* h, const float* const* pcm, const int64_t* n_samples, int n_clips, int personalized,
+                             pfhip_mos_result* results);
+pfhip_status pfhip_mos_score_s16(pfhip_mos* h, const int16_t* const* pcm, const int64_t* n_samples, int n_clips, int personalized,
+                                 pfhip_mos_result* results);
+pfhip_status pfhip_mos_score_windows(pfhip_mos* h, const float* const* pcm, const int64_t* n_samples, int n_clips, int32_t* num_hops,
+                                     int32_t* n_scored, float* raw, size_t cap_windows, size_t* n_windows);
+pfhip_status pfhip_mos_score_windows_s16(pfhip_mos* h, const int16_t* const* pcm, const int64_t* n_samples, int n_clips, int32_t* num_hops,
+                                         int32_t* n_scored, float* raw, size_t cap_windows, size_t* n_windows);
+
 #ifdef __cplusplus
 }
 #endif

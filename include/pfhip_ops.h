@@ -400,6 +400,41 @@ int pfhip_op_svs_prompt_rows(const float* E, int D, const int* prompt, const int
 int pfhip_op_gather_best(const float* logp, int ld, const int32_t* ids, int M, float* best, void* stream);
 int pfhip_op_row_lse(const float* logits, int ld, int M, int V, float* lse, void* stream);
 
+/* ---- The kernels of the DNSMOS speech-quality networks (utils/dnsmos_local.py with utils/DNSMOS/sig_bak_ovr.onnx and model_v8.onnx;
+ * csrc/conv3x3.hip, csrc/dnsmos.hip), one entry each.  Arrays named HOST are plain host arrays; the entries that take one, and the
+ * convolution for Cin >= 32, upload what they build with a synchronous copy and return after the stream has drained.  Every entry
+ * returns hipErrorInvalidValue, before anything is launched, for a NULL buffer and for what its kernel does not take. */
+/* A Conv (kernel 3x3, pads 1, strides 1, with bias) + Relu, and with pool != 0 the MaxPool (kernel 2x2, strides 2, VALID: an odd last
+ * row or column is dropped) behind it — the graphs' nodes conv2d* / Relu* / *pooling* / MaxPool_*_conv —, on NHWC activations, which
+ * makes the graphs' Transposes around them empty: x [N][H][W][Cin] -> y [N][H][W][Cout], pooled [N][H / 2][W / 2][Cout]; w is the
+ * file's own [Cout][Cin][3][3], bias [Cout].  Cin == 1 (any Cout): nine fp32 FMAs per value, ky, kx ascending.  Cin 32 or a multiple of 64
+ * with Cout 32 or 64: an implicit GEMM on the fp16 matrix cores, two planes per operand and three products, fp32 accumulation — as
+ * close to fp64 as an fp32 chain; the weights must be finite and |x| < 65504; N <= 65535. */
+int pfhip_op_conv3x3_relu(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout, int pool,
+                          void* stream);
+/* The primary net from `input_1` to `mos_estimator_logpow/truediv:0` (Slice x 2, Reshape x 2, Concat, the two 1x1 Convs stft-real /
+ * stft-imag, Square, Square_1, Add, Sqrt, Pow, Max, Log, Div): window i = the 160 (n_frames + 1) samples at pcm + win_off[i] (HOST;
+ * pcm_samples samples on the device, f32 in [-1, 1] or 16-bit PCM standing for s / 32768.f, the two bit for bit equal), frame f its
+ * samples [160 f, 160 f + 320); stft_real / stft_imag the file's kernels [161][320] (device); floor_v, power, denom the initialisers
+ * Maximum/x, pow/y and truediv/y (1e-12, 2, 2.3025851; a power other than 2 is refused).  out [n_win][n_frames][161] =
+ * log(max(floor_v, sqrt(re^2 + im^2)^2)) / denom; fp32, four accumulators over k mod 4.  n_win <= 65535. */
+int pfhip_op_dnsmos_logpow(const float* pcm, long long pcm_samples, const int64_t* win_off, int n_win, int n_frames, const float* stft_real,
+                           const float* stft_imag, float floor_v, float power, float denom, float* out, void* stream);
+int pfhip_op_dnsmos_logpow_s16(const int16_t* pcm, long long pcm_samples, const int64_t* win_off, int n_win, int n_frames,
+                               const float* stft_real, const float* stft_imag, float floor_v, float power, float denom, float* out,
+                               void* stream);
+/* ComputeScore.audio_melspec (utils/dnsmos_local.py:29-33), the input of model_v8.onnx: out [n_win][900][120] = (power_to_db(
+ * melspectrogram(y = the first 144000 samples of window i, sr 16000, n_fft 321, hop 160, 120 mels), ref = max) + 40) / 40,
+ * transposed.  The library's defaults behind that line (periodic Hann window, centred frames padded with zeros, Slaney mel scale and
+ * normalisation over 0 .. 8000 Hz, amin 1e-10, top_db 80) are recalled from librosa 0.10.0, not read from a file. */
+int pfhip_op_dnsmos_melspec(const float* pcm, long long pcm_samples, const int64_t* win_off, int n_win, float* out, void* stream);
+int pfhip_op_dnsmos_melspec_s16(const int16_t* pcm, long long pcm_samples, const int64_t* win_off, int n_win, float* out, void* stream);
+/* ReduceMax over axes 1, 2 (global_max_pooling2d) and the three MatMul + Add (+ Relu after the first two) behind it: x [N][HW][C]
+ * (NHWC with H and W merged), w_i [in][out] as the graph's MatMul holds them, out [N][D3].  One workgroup per window, fp32, k
+ * ascending.  C, D1, D2, D3 in 1 .. 256. */
+int pfhip_op_globalmax_mlp(const float* x, int N, int HW, int C, const float* w1, const float* b1, int D1, const float* w2, const float* b2,
+                           int D2, const float* w3, const float* b3, int D3, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
