@@ -61,9 +61,6 @@ inline void pcm_to_f32(float* dst, PcmView src, size_t n) {
       return pfhip_impl::fail(PFHIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
-// bumped whenever a workspace buffer is (re)allocated or freed: cached hipGraphs hold raw pointers
-std::atomic<uint64_t>& buf_epoch();          // pfhip.cpp
-
 struct Buf {
   void* p = nullptr;
   size_t cap = 0;
@@ -75,14 +72,13 @@ struct Buf {
   ~Buf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    buf_epoch().fetch_add(1);
     if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
     bytes = (bytes + (1u << 20) - 1) & ~((size_t)(1u << 20) - 1);
     hipError_t e = hipMalloc(&p, bytes);
     if (e == hipSuccess) cap = bytes;
     return e;
   }
-  void release() { if (p) { (void)hipFree(p); buf_epoch().fetch_add(1); } p = nullptr; cap = 0; }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   float* f() const { return static_cast<float*>(p); }
   int* i() const { return static_cast<int*>(p); }
 };

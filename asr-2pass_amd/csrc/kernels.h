@@ -379,31 +379,47 @@ void launch_fsmn_cached(const float* t2, const float* w, const float* res, float
                         int C, hipStream_t s);
 
 // ---- fused kernels for ONE streaming window (stream_fused.hip): M <= 32 rows ---------------------------------------------
-// C[M,N] = act(LN?(X) W^T + bias) (+R1) (+R2) (+ FSMN memory of fsmn_v: v + depthwise conv k = 11 over the M rows).
-// g == nullptr: no LayerNorm; D = LN width (<= K; columns D..K of the normalised operand are 0).  One workgroup per 32 columns.
-void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
-                          float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
-                          const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K, bool relu, hipStream_t s);
-// Attention of ONE window (Lq, Lk <= 32 rows starting at the given pointers; d_k = 128; H heads): one small workgroup per head,
-// operands requested at kernel start (stream_fused.hip).  Returns false for shapes it does not take.
-// head_dim: 128 or 80 (any other: false).
-bool launch_window_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
-                             int H, float scale, hipStream_t s, int head_dim = kHeadDim);
-bool launch_window_attention_segments(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                                      const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
-                                      int max_q_len, int max_kv_len, float scale, hipStream_t s, const float* fsmn_w = nullptr,
-                                      float* mem = nullptr, int ldmem = 0, int head_dim = kHeadDim);
-// The window's attention AND the projection of its context by W [N, 512] (+bias, +R1, + the FSMN memory of fsmn_v) in one launch:
-// every workgroup redoes the attention and keeps the context in LDS (stream_fused.hip).  H = 4 heads of 128, Lq <= 20, Lk <= 32.
-bool launch_fused_att_out(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int Lq, int Lk, int H, float scale,
-                          const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* fsmn_v,
-                          int ldfv, const float* fsmn_w, int N, hipStream_t s);
-// the same operator with every operand requested in one trip and LayerNorm applied algebraically (stream_fused.hip): W / bias are
-// the gamma/beta-folded ones and ln_colsum their column sums when the LayerNorm is wanted.  Returns false for shapes it does not take.
-bool launch_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, float* C, int ldc, const float* bias, const float* ln_colsum,
-                             float eps, const float* R1, int ldr1, const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K,
-                             bool relu, hipStream_t s);
-// Which instantiation and launch geometry the two launchers above take for a shape: host arithmetic only (nothing is launched, no
+// Operands of C[M,N] = act(LN?(X) W^T + bias) (+R1) (+R2) (+ FSMN memory of fsmn_v) over the rows of one window; an absent field
+// is nullptr / 0 / false.  A launcher whose kernel has no parameter for a field that is set refuses the op (see each).
+struct WindowGemmOp {
+  const float* X = nullptr; int ldx = 0;
+  const float* W = nullptr; int ldw = 0;
+  float* C = nullptr; int ldc = 0;
+  int M = 0, N = 0, K = 0;
+  const float* bias = nullptr;
+  const float* R1 = nullptr; int ldr1 = 0;
+  const float* R2 = nullptr; int ldr2 = 0;
+  bool relu = false;
+  float eps = 1e-12f;
+  // the SAN-M memory term: + fsmn_v + depthwise conv k = 11 (taps fsmn_w) of fsmn_v over the M rows
+  const float* fsmn_v = nullptr; int ldv = 0; const float* fsmn_w = nullptr;
+  // LayerNorm of X in front, one form at most.  Explicit (launch_fused_ln_gemm): gamma ln_g, beta ln_b over columns [0, D), D <= K
+  // (columns D..K of the normalised operand are 0).  Algebraic (launch_fused_gemv_1trip): ln_colsum, the column sums of W, with W /
+  // bias the gamma/beta-folded ones; the LayerNorm is over exactly the K operand columns (D is 0 or K).
+  const float* ln_g = nullptr; const float* ln_b = nullptr; int D = 0;
+  const float* ln_colsum = nullptr;
+};
+// One workgroup per 32 columns or fewer (fused_ln_gemm_route).  Serves every field but ln_colsum: an op that carries it is a
+// programming error and aborts, as launch_gemm does for a fold that reaches the wrong kernel.
+void launch_fused_ln_gemm(const WindowGemmOp& op, hipStream_t s);
+// The same operator with every operand requested in one trip (fused_gemv_1trip_route).  Returns false, launching nothing, for the
+// shapes it does not take and for an op with R2 or ln_g (or a LayerNorm width D other than K): the caller falls back to
+// launch_fused_ln_gemm with the plain weights.
+bool launch_fused_gemv_1trip(const WindowGemmOp& op, hipStream_t s);
+// Attention of windows of at most 32 queries and 32 keys, d_k = 128 or 80: one small workgroup per head and window, operands
+// requested at kernel start.  max_kv_len: the host-side maximum of the key counts, as op.max_q_len is of the query counts.
+// op.q_off == nullptr: ONE window — max_q_len queries and max_kv_len keys starting at the pointers, grid (H), no segment array is
+// read (none may be set, nor fsmn_w / mem).  Otherwise B windows by the four segment arrays, grid (H, B); with fsmn_w
+// (self-attention: q segments == kv segments) the launch also writes the FSMN memory of V into mem, what launch_fsmn computes.
+// Returns false, launching nothing, for shapes it does not take and for an op with a field it does not serve (q_kv_limit,
+// mem_accumulate, plane images, K / V planes): the caller uses launch_attention.
+bool launch_window_attention(const AttnOp& op, int max_kv_len, hipStream_t s);
+// ONE window's attention (att, the one-window form above: 4 heads of 128, max_q_len <= 20, max_kv_len <= 32; att.O is not written)
+// AND the projection of its context by proj.W [N, 512] (+bias, +R1, + the FSMN memory) in one launch: every workgroup redoes the
+// attention and keeps the context in LDS, so proj.X and proj.M are unused (the rows are att.max_q_len).  False, launching nothing,
+// outside that and for a proj with R2, relu or a LayerNorm.
+bool launch_fused_att_out(const AttnOp& att, int max_kv_len, const WindowGemmOp& proj, hipStream_t s);
+// Which instantiation and launch geometry the two GEMM launchers above take for a shape: host arithmetic only (nothing is launched, no
 // device is needed), the environment knobs of this process included.  The launchers launch exactly what these return — the one
 // place the choice is made.
 struct Gemv1tRoute {        // fused_gemv1t_kernel<LN, FS, CW, CPL, 4, RPL, NF> on `waves` waves; ok == false: refused (all else 0)

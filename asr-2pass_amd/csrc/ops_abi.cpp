@@ -57,7 +57,9 @@ int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const
                            float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
                            const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K, int relu, void* stream) {
   if (!ln_gemm_shape_ok(M, K) || (g && (D % 4 || D > K || D > 2048))) return (int)hipErrorInvalidValue;
-  pfhip::launch_fused_ln_gemm(X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu != 0,
+  pfhip::launch_fused_ln_gemm({.X = X, .ldx = ldx, .W = W, .ldw = ldw, .C = C, .ldc = ldc, .M = M, .N = N, .K = K, .bias = bias, .R1 = R1,
+                               .ldr1 = ldr1, .R2 = R2, .ldr2 = ldr2, .relu = relu != 0, .eps = eps, .fsmn_v = fsmn_v, .ldv = ldv,
+                               .fsmn_w = fsmn_w, .ln_g = g, .ln_b = b, .D = D},
                               S(stream));
   return done();
 }
@@ -66,14 +68,18 @@ int pfhip_dev_fused_ln_gemm_bench(const float* X, int ldx, int D, const float* g
                                   size_t w_stride_floats, int n_copies, float* C, int ldc, const float* bias, const float* R1, int ldr1,
                                   int M, int N, int K, int relu, int n_launch, void* stream) {
   for (int i = 0; i < n_launch; ++i)
-    pfhip::launch_fused_ln_gemm(X, ldx, D, g, b, 1e-12f, W + (size_t)(i % n_copies) * w_stride_floats, ldw, C, ldc, bias, R1, ldr1, nullptr,
-                                0, nullptr, 0, nullptr, M, N, K, relu != 0, S(stream));
+    pfhip::launch_fused_ln_gemm({.X = X, .ldx = ldx, .W = W + (size_t)(i % n_copies) * w_stride_floats, .ldw = ldw, .C = C, .ldc = ldc,
+                                 .M = M, .N = N, .K = K, .bias = bias, .R1 = R1, .ldr1 = ldr1, .relu = relu != 0, .ln_g = g, .ln_b = b, .D = D},
+                                S(stream));
   return done();
 }
 int pfhip_op_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, float* C, int ldc, const float* bias,
                               const float* ln_colsum, float eps, const float* R1, int ldr1, const float* fsmn_v, int ldv,
                               const float* fsmn_w, int M, int N, int K, int relu, void* stream) {
-  if (!pfhip::launch_fused_gemv_1trip(X, ldx, W, ldw, C, ldc, bias, ln_colsum, eps, R1, ldr1, fsmn_v, ldv, fsmn_w, M, N, K, relu != 0, S(stream)))
+  if (!pfhip::launch_fused_gemv_1trip({.X = X, .ldx = ldx, .W = W, .ldw = ldw, .C = C, .ldc = ldc, .M = M, .N = N, .K = K, .bias = bias, .R1 = R1,
+                                       .ldr1 = ldr1, .relu = relu != 0, .eps = eps, .fsmn_v = fsmn_v, .ldv = ldv, .fsmn_w = fsmn_w,
+                                       .ln_colsum = ln_colsum},
+                                      S(stream)))
     return (int)hipErrorInvalidValue;
   return done();
 }
@@ -97,20 +103,23 @@ int pfhip_dev_fused_gemv_1trip_bench(const float* X, int ldx, const float* W, in
                                      const float* bias, const float* ln_colsum, const float* R1, int ldr1, int M, int N, int K, int relu,
                                      int n_launch, void* stream) {
   for (int i = 0; i < n_launch; ++i)
-    if (!pfhip::launch_fused_gemv_1trip(X, ldx, W + (size_t)(i % n_copies) * w_stride_floats, ldw, C, ldc, bias, ln_colsum, 1e-12f, R1, ldr1,
-                                        nullptr, 0, nullptr, M, N, K, relu != 0, S(stream)))
+    if (!pfhip::launch_fused_gemv_1trip({.X = X, .ldx = ldx, .W = W + (size_t)(i % n_copies) * w_stride_floats, .ldw = ldw, .C = C, .ldc = ldc,
+                                         .M = M, .N = N, .K = K, .bias = bias, .R1 = R1, .ldr1 = ldr1, .relu = relu != 0, .ln_colsum = ln_colsum},
+                                        S(stream)))
       return (int)hipErrorInvalidValue;
   return done();
 }
 int pfhip_op_window_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
                               int H, float scale, void* stream) {
-  if (!pfhip::launch_window_attention(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, H, scale, S(stream))) return (int)hipErrorInvalidValue;
-  return done();
+  return pfhip_op_window_attention_hd(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, H, scale, pfhip::kHeadDim, stream);
 }
 int pfhip_op_window_attention_hd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
                                  int H, float scale, int head_dim, void* stream) {
   if (head_dim != 128 && head_dim != 80) return (int)hipErrorInvalidValue;      // before anything is launched
-  if (!pfhip::launch_window_attention(Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk, H, scale, S(stream), head_dim)) return (int)hipErrorInvalidValue;
+  if (!pfhip::launch_window_attention({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .O = O, .ldo = ldo, .H = H, .max_q_len = Lq,
+                                       .scale = scale, .head_dim = head_dim},
+                                      Lk, S(stream)))
+    return (int)hipErrorInvalidValue;
   return done();
 }
 int pfhip_op_window_attention_segments(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
@@ -123,15 +132,20 @@ int pfhip_op_window_attention_segments(const float* Q, int ldq, const float* K, 
   const long long w = (long long)H * head_dim;
   if ((ldq | ldk | ldv | ldo) % 4 || ldq < w || ldk < w || ldv < w || ldo < w || (fsmn_w && (!mem || ldmem < w || ldmem % 4)))
     return (int)hipErrorInvalidValue;
-  if (!pfhip::launch_window_attention_segments(Q, ldq, K, ldk, V, ldv, O, ldo, q_off, q_len, kv_off, kv_len, B, H, max_q_len, max_kv_len, scale,
-                                               S(stream), fsmn_w, mem, ldmem, head_dim))
+  if (!pfhip::launch_window_attention({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .O = O, .ldo = ldo, .q_off = q_off, .q_len = q_len,
+                                       .kv_off = kv_off, .kv_len = kv_len, .B = B, .H = H, .max_q_len = max_q_len, .scale = scale,
+                                       .head_dim = head_dim, .fsmn_w = fsmn_w, .mem = mem, .ldmem = ldmem},
+                                      max_kv_len, S(stream)))
     return (int)hipErrorInvalidValue;
   return done();
 }
 int pfhip_op_fused_att_out(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int Lq, int Lk, int H, float scale,
                            const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* fsmn_v,
                            int ldfv, const float* fsmn_w, int N, void* stream) {
-  if (!pfhip::launch_fused_att_out(Q, ldq, K, ldk, V, ldv, Lq, Lk, H, scale, W, ldw, C, ldc, bias, R1, ldr1, fsmn_v, ldfv, fsmn_w, N, S(stream)))
+  if (!pfhip::launch_fused_att_out({.Q = Q, .ldq = ldq, .K = K, .ldk = ldk, .V = V, .ldv = ldv, .H = H, .max_q_len = Lq, .scale = scale}, Lk,
+                                   {.W = W, .ldw = ldw, .C = C, .ldc = ldc, .N = N, .bias = bias, .R1 = R1, .ldr1 = ldr1, .fsmn_v = fsmn_v,
+                                    .ldv = ldfv, .fsmn_w = fsmn_w},
+                                   S(stream)))
     return (int)hipErrorInvalidValue;
   return done();
 }

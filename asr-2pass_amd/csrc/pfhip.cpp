@@ -58,10 +58,6 @@ pfhip_status apply_env_inflight(pfhip_model** out) {
 
 namespace pfhip_impl {
 
-std::atomic<uint64_t>& buf_epoch() {
-  static std::atomic<uint64_t> e{1};
-  return e;
-}
 std::string& last_error() {
   thread_local std::string e;
   return e;

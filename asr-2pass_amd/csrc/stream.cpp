@@ -289,23 +289,25 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   static const bool fused_on = pfhip::env_on("PFHIP_STREAM_FUSED");
   const bool lean = fused_on && B == 1 && M <= 32;
   static const bool att_out_on = pfhip::env_is1("PFHIP_STREAM_ATT_OUT");
-  // LayerNorm `nm` (null: none) of X, then L
-  auto ln_gemm = [&](const float* X, int ldx, int D, const Norm* nm, const Linear& L, int ldw, float* Cd, int ldc,
-                     const float* R1, int ldr1, const float* R2, int ldr2, const float* fv, int ldv,
-                     const float* fw, int rows, int N, int K, bool relu) {
-    pfhip::launch_fused_ln_gemm(X, ldx, D, nm ? nm->g : nullptr, nm ? nm->b : nullptr, 1e-12f, L.w, ldw, Cd, ldc, L.b, R1, ldr1, R2, ldr2,
-                                fv, ldv, fw, rows, N, K, relu, st);
+  // `op` (X, C, the shape, the epilogue) on the dense weight L: W [N, K], bias
+  auto with_weight = [](const Linear& L, pfhip::WindowGemmOp op) { op.W = L.w; op.ldw = op.K; op.bias = L.b; return op; };
+  // A GEMM of the one window: op on L behind the LayerNorm `nm` (null: none; over op.D columns, K where that is 0); F (null: not
+  // built) is that LayerNorm folded into L at load.  The one-trip form first (stream_fused.hip: every operand requested at once) — on
+  // the folded weight with the LayerNorm applied algebraically, on L itself where there is no LayerNorm — and where it does not
+  // take the call, launch_fused_ln_gemm on L with the explicit LayerNorm.
+  auto window_gemm = [&](const Linear& L, const Norm* nm, const FoldLin* F, const pfhip::WindowGemmOp& op) {
+    const Linear* one = !nm ? &L : F ? &F->folded : nullptr;
+    if (one && one->w) {
+      pfhip::WindowGemmOp t = with_weight(*one, op);
+      if (nm) t.ln_colsum = F->colsum;
+      if (pfhip::launch_fused_gemv_1trip(t, st)) return;
+    }
+    pfhip::WindowGemmOp t = with_weight(L, op);
+    if (nm) { t.ln_g = nm->g; t.ln_b = nm->b; if (!t.D) t.D = t.K; }
+    pfhip::launch_fused_ln_gemm(t, st);
   };
-  // one-trip form of the same launches where the shape allows (stream_fused.hip: every operand requested at once, LayerNorm
-  // applied algebraically on the gamma/beta-folded weights built at load: colsum); false -> the caller uses ln_gemm
-  auto gemv1 = [&](const float* X, int ldx, const Linear& L, int ldw, float* Cd, int ldc, const float* colsum,
-                   const float* R1, int ldr1, const float* fv, int ldv, const float* fw, int rows, int N, int K, bool relu) {
-    return L.w && pfhip::launch_fused_gemv_1trip(X, ldx, L.w, ldw, Cd, ldc, L.b, colsum, 1e-12f, R1, ldr1, fv, ldv, fw, rows, N, K, relu, st);
-  };
-  // the same on a LayerNorm-folded weight; false too where the fold was not built
-  auto gemv1_ln = [&](const float* X, int ldx, const FoldLin& F, int ldw, float* Cd, int ldc, int rows, int N, int K, bool relu) {
-    return gemv1(X, ldx, F.folded, ldw, Cd, ldc, F.colsum, nullptr, 0, nullptr, 0, nullptr, rows, N, K, relu);
-  };
+  // a window attention's operands as the one-window form of launch_window_attention takes them: no segment array is read
+  auto one_window = [](pfhip::AttnOp op) { op.q_off = op.q_len = op.kv_off = op.kv_len = nullptr; return op; };
   const bool fuse_ln_s = !lean && w.enc_folded && pfhip::gemm_x6_ln_ok(M);
   if (fuse_ln_s) HIP_TRY(m->lnstats.ensure((size_t)(M + 256) * 4 * 2 * 4));
   auto gemm_ln = [&](const Linear& W, const pfhip::GemmOp& op) { split_gemm(st, W, op, M, d, m->lnstats.f()); };
@@ -321,24 +323,18 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     const int ldin = first ? FP : d, Din = first ? FD : d, Kp = first ? FP : d;
     if (lean) {
       // 5 launches: LN1+QKV | attention | out-projection + FSMN memory + residual | LN2+FFN1 | FFN2 + residual
-      if (!gemv1_ln(x, d, L.qkv_f, d, m->qkv.f(), 3 * d, M, 3 * d, d, false))      // (layer 0 has no folded qkv)
-        ln_gemm(xin, ldin, Din, &L.norm1, L.qkv, Kp, m->qkv.f(), 3 * d, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, 3 * d, Kp, false);
+      window_gemm(L.qkv, &L.norm1, first ? nullptr : &L.qkv_f,      // (layer 0 has no folded qkv, and reads the padded features)
+                  {.X = xin, .ldx = ldin, .C = m->qkv.f(), .ldc = 3 * d, .M = M, .N = 3 * d, .K = Kp, .D = Din});
+      const pfhip::WindowGemmOp out = {.X = m->ctx.f(), .ldx = d, .C = x, .ldc = d, .M = M, .N = d, .K = d, .R1 = first ? nullptr : x, .ldr1 = d,
+                                       .fsmn_v = m->qkv.f() + 2 * d, .ldv = 3 * d, .fsmn_w = L.fsmn_w};
       // attention + output projection + FSMN memory + residual as one launch (every workgroup redoes the attention) is opt-in:
       // measured slower than the two launches (stream_fused.hip, launch_fused_att_out)
-      if (!att_out_on || hd != pfhip::kHeadDim || !pfhip::launch_fused_att_out(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, M, M, c.n_head, att_scale,
-                                       L.out.w, d, x, d, L.out.b, first ? nullptr : x, d, m->qkv.f() + 2 * d,
-                                       3 * d, L.fsmn_w, d, st)) {
-        if (!pfhip::launch_window_attention(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, M, M,
-                                            c.n_head, att_scale, st, hd))
-          pfhip::launch_attention(self_att, st);
-        if (!gemv1(m->ctx.f(), d, L.out, d, x, d, nullptr, first ? nullptr : x, d, m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, M, d, d, false))
-          ln_gemm(m->ctx.f(), d, 0, nullptr, L.out, d, x, d, first ? nullptr : x, d, nullptr, 0,
-                  m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, M, d, d, false);
+      if (!att_out_on || hd != pfhip::kHeadDim || !pfhip::launch_fused_att_out(one_window(self_att), M, with_weight(L.out, out), st)) {
+        if (!pfhip::launch_window_attention(one_window(self_att), M, st)) pfhip::launch_attention(self_att, st);
+        window_gemm(L.out, nullptr, nullptr, out);
       }
-      if (!gemv1_ln(x, d, L.ffn1_f, d, m->hbuf.f(), c.ffn, M, c.ffn, d, true))
-        ln_gemm(x, d, d, &L.norm2, L.ffn1, d, m->hbuf.f(), c.ffn, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, c.ffn, d, true);
-      if (!gemv1(m->hbuf.f(), c.ffn, L.ffn2, c.ffn, x, d, nullptr, x, d, nullptr, 0, nullptr, M, d, c.ffn, false))
-        ln_gemm(m->hbuf.f(), c.ffn, 0, nullptr, L.ffn2, c.ffn, x, d, x, d, nullptr, 0, nullptr, 0, nullptr, M, d, c.ffn, false);
+      window_gemm(L.ffn1, &L.norm2, &L.ffn1_f, {.X = x, .ldx = d, .C = m->hbuf.f(), .ldc = c.ffn, .M = M, .N = c.ffn, .K = d, .relu = true});
+      window_gemm(L.ffn2, nullptr, nullptr, {.X = m->hbuf.f(), .ldx = c.ffn, .C = x, .ldc = d, .M = M, .N = d, .K = c.ffn, .R1 = x, .ldr1 = d});
       continue;
     }
     // rounds of many connections (>= 1536 rows): the two LayerNorms of a layer folded into the GEMMs around them, as offline
@@ -351,9 +347,9 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     }
     // windows of <= 32 rows: one small workgroup per (head, connection) instead of the long-sequence kernel, the FSMN memory of V
     // written by the same launch
-    if (!pfhip::launch_window_attention_segments(m->qkv.f(), 3 * d, m->qkv.f() + d, 3 * d, m->qkv.f() + 2 * d, 3 * d, m->ctx.f(), d, d_off,
-                                                 d_len, d_off, d_len, B, c.n_head, maxn, maxn, att_scale, st, L.fsmn_w,
-                                                 m->mem.f(), d, hd)) {
+    pfhip::AttnOp att_mem = self_att;
+    att_mem.fsmn_w = L.fsmn_w; att_mem.mem = m->mem.f(); att_mem.ldmem = d;
+    if (!pfhip::launch_window_attention(att_mem, maxn, st)) {
       pfhip::launch_fsmn(m->qkv.f() + 2 * d, 3 * d, L.fsmn_w, nullptr, 0, m->mem.f(), d, d_off, d_len, B, maxn, d, st);
       pfhip::launch_attention(self_att, st);
     }
@@ -374,8 +370,9 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   float* col = m->qkv.f();
   float* po = m->ctx.f();
   pfhip::launch_im2col3(m->enc.f(), d, col, 3 * d, d_row_pos, d_row_len, M, d, st);
-  if (!lean || !gemv1(col, 3 * d, w.pred.conv, 3 * d, po, d, nullptr, c.pred_residual ? m->enc.f() : nullptr, d,
-                      nullptr, 0, nullptr, M, d, 3 * d, true))
+  if (!lean || !pfhip::launch_fused_gemv_1trip(with_weight(w.pred.conv, {.X = col, .ldx = 3 * d, .C = po, .ldc = d, .M = M, .N = d, .K = 3 * d,
+                                                                         .R1 = c.pred_residual ? m->enc.f() : nullptr, .ldr1 = d, .relu = true}),
+                                               st))
     gemm(m, st, col, 3 * d, w.pred.conv, d, 3 * d, 3 * d, po, d, c.pred_residual ? m->enc.f() : nullptr, d, nullptr, 0, M, true);
   pfhip::launch_alpha(po, d, w.pred.out_w, w.pred.out_b, c.smooth_factor, c.noise_threshold, m->alphas.f(), M, d, st);
   // ---- CifSearch (:270-345), one block per connection ---------------------------------------------------
@@ -386,11 +383,9 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   const auto t_sync0 = std::chrono::steady_clock::now();
   HIP_TRY(hipStreamSynchronize(st));
   if (timing) {
-    static double wait_us = 0, enq_us = 0; static int n = 0;
-    static auto t_last = t_sync0;
+    static double wait_us = 0; static int n = 0;
     const auto t1 = std::chrono::steady_clock::now();
     wait_us += std::chrono::duration<double, std::micro>(t1 - t_sync0).count();
-    (void)enq_us; (void)t_last;
     if (++n % 50 == 0) { std::fprintf(stderr, "[stream timing] encoder: avg wait in sync %.1f us over %d chunks\n", wait_us / n, n); }
   }
   const int* fires = m->h_counts.i();
@@ -449,10 +444,8 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   auto dec_ffn = [&](const DecFfn& F, const float* xin, float* o) {
     if (lean_dec) {          // LN1+FFN1 | ffn_norm+FFN2
       const int f = c.dec_ffn;
-      if (!gemv1_ln(xin, d, F.ffn1_f, d, m->hd.f(), f, ML, f, d, true))
-        ln_gemm(xin, d, d, &F.norm1, F.ffn1, d, m->hd.f(), f, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, ML, f, d, true);
-      if (!gemv1_ln(m->hd.f(), f, F.ffn2_f, f, o, d, ML, d, f, false))
-        ln_gemm(m->hd.f(), f, f, &F.ffn_norm, F.ffn2, f, o, d, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, ML, d, f, false);
+      window_gemm(F.ffn1, &F.norm1, &F.ffn1_f, {.X = xin, .ldx = d, .C = m->hd.f(), .ldc = f, .M = ML, .N = f, .K = d, .relu = true});
+      window_gemm(F.ffn2, &F.ffn_norm, &F.ffn2_f, {.X = m->hd.f(), .ldx = f, .C = o, .ldc = d, .M = ML, .N = d, .K = f});
       return;
     }
     lnorm(m, st, xin, d, m->yd.f(), d, F.norm1, ML, d, d);
@@ -463,8 +456,7 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
   const int kv_ld = c.dec_layers * 2 * d;
   if (lean_dec) {            // the window is the same for every layer: all K/V projections in one launch
     HIP_TRY(m->kvall.ensure((size_t)32 * (kv_ld + pfhip::kTileN) * 4));
-    if (!gemv1(m->enc.f(), d, w.kv_all, d, m->kvall.f(), kv_ld, nullptr, nullptr, 0, nullptr, 0, nullptr, M, kv_ld, d, false))
-      ln_gemm(m->enc.f(), d, 0, nullptr, w.kv_all, d, m->kvall.f(), kv_ld, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, M, kv_ld, d, false);
+    window_gemm(w.kv_all, nullptr, nullptr, {.X = m->enc.f(), .ldx = d, .C = m->kvall.f(), .ldc = kv_ld, .M = M, .N = kv_ld, .K = d});
   }
   // the tokens' queries in qd against each stream's window in K | V (row stride ldkv), for the shapes the window kernels do not take
   auto cross_att = [&](const float* kv, int ldkv) {
@@ -479,30 +471,26 @@ pfhip_status forward_windows(pfhip_model* m, const std::vector<pfhip_stream*>& s
     lnorm(m, st, m->td.f(), d, m->t2.f(), d, L.norm2, ML, d, d);
     pfhip::launch_fsmn_cached(m->t2.f(), L.fsmn_w, xd, xd, d_segs, B, i, d, st);
     if (lean_dec) {
-      if (!gemv1_ln(xd, d, L.q_f, d, m->qd.f(), d, ML, d, d, false))
-        ln_gemm(xd, d, d, &L.norm3, L.q, d, m->qd.f(), d, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, ML, d, d, false);
-      const float* kvl = m->kvall.f() + (size_t)i * 2 * d;
-      if (att_out_on && hdd == pfhip::kHeadDim && pfhip::launch_fused_att_out(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, ML, M, c.dec_n_head, att_scale_d, L.out.w, d, xd, d,
-                                      L.out.b, xd, d, nullptr, 0, nullptr, d, st))
-        continue;
-      if (!pfhip::launch_window_attention(m->qd.f(), d, kvl, kv_ld, kvl + d, kv_ld, m->ctxd.f(), d, ML, M, c.dec_n_head, att_scale_d, st, hdd))
-        pfhip::launch_attention(cross_att(kvl, kv_ld), st);
-      if (!gemv1(m->ctxd.f(), d, L.out, d, xd, d, nullptr, xd, d, nullptr, 0, nullptr, ML, d, d, false))
-        ln_gemm(m->ctxd.f(), d, 0, nullptr, L.out, d, xd, d, xd, d, nullptr, 0, nullptr, 0, nullptr, ML, d, d, false);
+      window_gemm(L.q, &L.norm3, &L.q_f, {.X = xd, .ldx = d, .C = m->qd.f(), .ldc = d, .M = ML, .N = d, .K = d});
+      const pfhip::AttnOp att = cross_att(m->kvall.f() + (size_t)i * 2 * d, kv_ld);
+      const pfhip::WindowGemmOp out = {.X = m->ctxd.f(), .ldx = d, .C = xd, .ldc = d, .M = ML, .N = d, .K = d, .R1 = xd, .ldr1 = d};
+      if (att_out_on && hdd == pfhip::kHeadDim && pfhip::launch_fused_att_out(one_window(att), M, with_weight(L.out, out), st)) continue;
+      if (!pfhip::launch_window_attention(one_window(att), M, st)) pfhip::launch_attention(att, st);
+      window_gemm(L.out, nullptr, nullptr, out);
       continue;
     }
     lnorm(m, st, xd, d, m->yd.f(), d, L.norm3, ML, d, d);
     gemm(m, st, m->yd.f(), d, L.q, d, d, d, m->qd.f(), d, nullptr, 0, nullptr, 0, ML, false);
     gemm(m, st, m->enc.f(), d, L.kv, 2 * d, d, d, kvbuf, 2 * d, nullptr, 0, nullptr, 0, M, false);
-    if (!pfhip::launch_window_attention_segments(m->qd.f(), d, kvbuf, 2 * d, kvbuf + d, 2 * d, m->ctxd.f(), d, d_tok_off, d_tok_len, d_off,
-                                                 d_len, B, c.dec_n_head, maxN, maxn, att_scale_d, st, nullptr, nullptr, 0, hdd))
-      pfhip::launch_attention(cross_att(kvbuf, 2 * d), st);
+    const pfhip::AttnOp att = cross_att(kvbuf, 2 * d);
+    if (!pfhip::launch_window_attention(att, maxn, st)) pfhip::launch_attention(att, st);
     gemm(m, st, m->ctxd.f(), d, L.out, d, d, d, xd, d, xd, d, nullptr, 0, ML, false);
   }
   dec_ffn(w.dec3, xd, m->td.f());
   if (lean_dec) {
-    ln_gemm(m->td.f(), d, d, &w.dec_after, w.dec_out, d, m->logits.f(), w.vocab_pad, nullptr, 0,
-            nullptr, 0, nullptr, 0, nullptr, ML, c.vocab, d, false);
+    pfhip::launch_fused_ln_gemm(with_weight(w.dec_out, {.X = m->td.f(), .ldx = d, .C = m->logits.f(), .ldc = w.vocab_pad, .M = ML, .N = c.vocab,
+                                                        .K = d, .ln_g = w.dec_after.g, .ln_b = w.dec_after.b, .D = d}),
+                                st);
   } else {
     lnorm(m, st, m->td.f(), d, m->yd.f(), d, w.dec_after, ML, d, d);
     gemm(m, st, m->yd.f(), d, w.dec_out, c.vocab, d, d, m->logits.f(), w.vocab_pad, nullptr, 0, nullptr, 0, ML, false);

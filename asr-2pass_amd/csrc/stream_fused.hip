@@ -19,10 +19,10 @@
 #include "launch_common.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
-#include <atomic>
 
 namespace pfhip {
 namespace {
@@ -746,16 +746,18 @@ Gemv1tRoute fused_gemv_1trip_route(int M, int N, int K, bool has_ln, bool has_fs
   return {true, has_ln, has_fsmn, cw, cpl, M <= 8 ? 2 : 5, nf, K / ki};
 }
 
-void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
-                          float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* R2, int ldr2,
-                          const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K, bool relu, hipStream_t s) {
-  const LnGemmRoute r = fused_ln_gemm_route(M, N, K, g != nullptr);
+void launch_fused_ln_gemm(const WindowGemmOp& op, hipStream_t s) {
+  if (op.ln_colsum) {      // a programming error, as a fold that reaches the wrong GEMM kernel is (launch_gemm)
+    fprintf(stderr, "pfhip: the algebraic LayerNorm (ln_colsum) needs the one-trip window kernel\n");
+    abort();
+  }
+  const LnGemmRoute r = fused_ln_gemm_route(op.M, op.N, op.K, op.ln_g != nullptr);
   if (r.kernel == kLnGemmNone) return;
-  const dim3 grid((N + r.cw - 1) / r.cw), block(64 * r.waves);
+  const dim3 grid((op.N + r.cw - 1) / r.cw), block(64 * r.waves);
   if (r.kernel == kLnGemmVector) {
 #define PFHIP_LAUNCH(LN_, CW_, MR_)                                                                                                    \
-  hipLaunchKernelGGL((fused_ln_gemv_kernel<LN_, CW_, MR_>), grid, block, 0, s, X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, \
-                     ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu ? 1 : 0)
+  hipLaunchKernelGGL((fused_ln_gemv_kernel<LN_, CW_, MR_>), grid, block, 0, s, op.X, op.ldx, op.D, op.ln_g, op.ln_b, op.eps, op.W, op.ldw, \
+                     op.C, op.ldc, op.bias, op.R1, op.ldr1, op.R2, op.ldr2, op.fsmn_v, op.ldv, op.fsmn_w, op.M, op.N, op.K, op.relu ? 1 : 0)
 #define PFHIP_PICK_MR(LN_, CW_)                                                                     \
   do {                                                                                              \
     if (r.mr == 8) PFHIP_LAUNCH(LN_, CW_, 8); else if (r.mr == 16) PFHIP_LAUNCH(LN_, CW_, 16);      \
@@ -772,8 +774,8 @@ void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const 
     return;
   }
 #define PFHIP_LAUNCH(LN_, CW_)                                                                                                    \
-  hipLaunchKernelGGL((fused_ln_gemm_kernel<LN_, CW_>), grid, block, 0, s, X, ldx, D, g, b, eps, W, ldw, C, ldc, bias, R1, ldr1, R2, \
-                     ldr2, fsmn_v, ldv, fsmn_w, M, N, K, relu ? 1 : 0)
+  hipLaunchKernelGGL((fused_ln_gemm_kernel<LN_, CW_>), grid, block, 0, s, op.X, op.ldx, op.D, op.ln_g, op.ln_b, op.eps, op.W, op.ldw, \
+                     op.C, op.ldc, op.bias, op.R1, op.ldr1, op.R2, op.ldr2, op.fsmn_v, op.ldv, op.fsmn_w, op.M, op.N, op.K, op.relu ? 1 : 0)
   if (r.ln) {
     if (r.cw == 4) PFHIP_LAUNCH(true, 4); else if (r.cw == 8) PFHIP_LAUNCH(true, 8); else PFHIP_LAUNCH(true, 32);
   } else {
@@ -786,15 +788,14 @@ void launch_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const 
 // One-trip form (fused_gemv1t_kernel).  W / bias are the LayerNorm-folded ones when ln_colsum is given (the caller's LayerNorm is
 // over exactly the K operand columns).  False when the shape is outside what the kernel takes — the caller falls back to
 // launch_fused_ln_gemm with the plain weights.
-bool launch_fused_gemv_1trip(const float* X, int ldx, const float* W, int ldw, float* C, int ldc, const float* bias, const float* ln_colsum,
-                             float eps, const float* R1, int ldr1, const float* fsmn_v, int ldv, const float* fsmn_w, int M, int N, int K,
-                             bool relu, hipStream_t s) {
-  const Gemv1tRoute r = fused_gemv_1trip_route(M, N, K, ln_colsum != nullptr, fsmn_v != nullptr);
+bool launch_fused_gemv_1trip(const WindowGemmOp& op, hipStream_t s) {
+  if (op.R2 || op.ln_g || (op.D && op.D != op.K)) return false;      // the kernel has no parameter for these
+  const Gemv1tRoute r = fused_gemv_1trip_route(op.M, op.N, op.K, op.ln_colsum != nullptr, op.fsmn_v != nullptr);
   if (!r.ok) return false;
-  const dim3 grid(N / r.cw), block(64 * r.waves);
+  const dim3 grid(op.N / r.cw), block(64 * r.waves);
 #define PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, RPL_, NF_)                                                                                      \
-  hipLaunchKernelGGL((fused_gemv1t_kernel<LN_, FS_, CW_, CPL_, 4, RPL_, NF_>), grid, block, 0, s, X, ldx, W, ldw, C, ldc, bias, ln_colsum, eps, \
-                     R1, ldr1, fsmn_v, ldv, fsmn_w, M, N, K, relu ? 1 : 0)
+  hipLaunchKernelGGL((fused_gemv1t_kernel<LN_, FS_, CW_, CPL_, 4, RPL_, NF_>), grid, block, 0, s, op.X, op.ldx, op.W, op.ldw, op.C, op.ldc, op.bias, \
+                     op.ln_colsum, op.eps, op.R1, op.ldr1, op.fsmn_v, op.ldv, op.fsmn_w, op.M, op.N, op.K, op.relu ? 1 : 0)
 #define PFHIP_PICK_MR(LN_, FS_, CW_, CPL_, NF_)                                   \
   do { if (r.rpl == 2) PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, 2, NF_); else PFHIP_LAUNCH1T(LN_, FS_, CW_, CPL_, 5, NF_); } while (0)
 #define PFHIP_PICK_NF(LN_, FS_, CW_, CPL_)                                        \
@@ -821,32 +822,24 @@ static bool window_attention_on() {
   static const bool on = env_on("PFHIP_STREAM_WATT");
   return on;
 }
-bool launch_window_attention(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, int Lq, int Lk,
-                             int H, float scale, hipStream_t s, int head_dim) {
-  if (!window_attention_on() || Lq < 1 || Lq > 32 || Lk < 1 || Lk > 32 || H < 1 || (head_dim != 128 && head_dim != 80)) return false;
-  if (head_dim == 80)
-    hipLaunchKernelGGL(window_attention_kernel<80>, dim3(H), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk,
-                       scale * 1.4426950408889634f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-  else
-    hipLaunchKernelGGL(window_attention_kernel<128>, dim3(H), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, Lq, Lk,
-                       scale * 1.4426950408889634f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-  return true;
+// the AttnOp fields no window kernel has a parameter for
+static bool window_kernels_serve(const AttnOp& op) {
+  return !(op.q_kv_limit || op.mem_accumulate || op.planes_hi || op.planes_lo || op.kv_hi || op.kv_lo);
 }
-// B windows in one launch: segment arrays on the device, max_q_len / max_kv_len their host-side maxima (both <= 32 or false).
-// fsmn_w != nullptr (self-attention: q segments == kv segments, V = H * head_dim channels wide): the launch also writes the encoder
-// layer's FSMN memory of V into mem (what launch_fsmn computes) — one launch per layer less in a round of connections.
-bool launch_window_attention_segments(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo,
-                                      const int* q_off, const int* q_len, const int* kv_off, const int* kv_len, int B, int H,
-                                      int max_q_len, int max_kv_len, float scale, hipStream_t s, const float* fsmn_w, float* mem,
-                                      int ldmem, int head_dim) {
-  if (!window_attention_on() || B < 1 || H < 1 || max_q_len < 1 || max_q_len > 32 || max_kv_len < 1 || max_kv_len > 32 || (head_dim != 128 && head_dim != 80))
+// kernels.h states the two forms: one window at the pointers (q_off == nullptr, no segment array read), or B windows by the segment
+// arrays, with the FSMN memory of V written into mem where fsmn_w is given — one launch per layer less in a round of connections.
+bool launch_window_attention(const AttnOp& op, int max_kv_len, hipStream_t s) {
+  if (!window_attention_on() || op.H < 1 || op.max_q_len < 1 || op.max_q_len > 32 || max_kv_len < 1 || max_kv_len > 32 ||
+      (op.head_dim != 128 && op.head_dim != 80) || !window_kernels_serve(op))
     return false;
-  if (head_dim == 80)
-    hipLaunchKernelGGL(window_attention_kernel<80>, dim3(H, B), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, 0, 0,
-                       scale * 1.4426950408889634f, q_off, q_len, kv_off, kv_len, fsmn_w, mem, ldmem);
-  else
-    hipLaunchKernelGGL(window_attention_kernel<128>, dim3(H, B), dim3(256), 0, s, Q, ldq, K, ldk, V, ldv, O, ldo, 0, 0,
-                       scale * 1.4426950408889634f, q_off, q_len, kv_off, kv_len, fsmn_w, mem, ldmem);
+  const bool one = op.q_off == nullptr;
+  if (one && (op.q_len || op.kv_off || op.kv_len || op.fsmn_w || op.mem)) return false;
+  if (!one && (op.B < 1 || !op.q_len || !op.kv_off || !op.kv_len)) return false;
+  const dim3 grid = one ? dim3(op.H) : dim3(op.H, op.B);
+  const int Lq = one ? op.max_q_len : 0, Lk = one ? max_kv_len : 0;      // the segments form reads its lengths from the arrays
+  const auto kern = op.head_dim == 80 ? window_attention_kernel<80> : window_attention_kernel<128>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, op.Q, op.ldq, op.K, op.ldk, op.V, op.ldv, op.O, op.ldo, Lq, Lk,
+                     op.scale * 1.4426950408889634f, op.q_off, op.q_len, op.kv_off, op.kv_len, op.fsmn_w, op.mem, op.ldmem);
   return true;
 }
 
@@ -855,27 +848,19 @@ bool launch_window_attention_segments(const float* Q, int ldq, const float* K, i
 // path unless PFHIP_STREAM_ATT_OUT=1: measured, the fused launch costs ~17 us where window_attention_kernel (7.1) + boundary (1.5) +
 // projection (5.4) cost 14 — 128 workgroups x 16 waves each redoing 3 us of fp32 MFMA and 24 operand loads per lane is more than
 // the launch it saves (2.92 against 2.70 ms per chunk on the same box).  Kept, tested, as the record of that.
-bool launch_fused_att_out(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, int Lq, int Lk, int H, float scale,
-                          const float* W, int ldw, float* C, int ldc, const float* bias, const float* R1, int ldr1, const float* fsmn_v,
-                          int ldfv, const float* fsmn_w, int N, hipStream_t s) {
-  if (H != 4 || Lq < 1 || Lq > 20 || Lk < 1 || Lk > 32 || N < 4 || N % 4) return false;
-  const size_t lds = (size_t)4 * 4 * 32 * 33 * 4 + 4 * 32 * 33 * 4 + (size_t)kWaves * 20 * 4 * 4;       // 89,600 B
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr_done.load(std::memory_order_relaxed) >> (dev & 63) & 1ull)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_att_out_kernel<true, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_att_out_kernel<false, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_att_out_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_att_out_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  const float sl = scale * 1.4426950408889634f;
-  const dim3 grid(N / 4), block(1024);
-#define PFHIP_LAUNCH_AO(FS_, RPL_)                                                                                                    \
-  hipLaunchKernelGGL((fused_att_out_kernel<FS_, RPL_>), grid, block, lds, s, Q, ldq, K, ldk, V, ldv, Lq, Lk, sl, W, ldw, C, ldc, bias, R1, \
-                     ldr1, fsmn_v, ldfv, fsmn_w, N)
-  if (fsmn_v) { if (Lq <= 8) PFHIP_LAUNCH_AO(true, 2); else PFHIP_LAUNCH_AO(true, 5); }
+bool launch_fused_att_out(const AttnOp& att, int max_kv_len, const WindowGemmOp& proj, hipStream_t s) {
+  const int Lq = att.max_q_len, N = proj.N;
+  if (att.H != 4 || att.head_dim != 128 || Lq < 1 || Lq > 20 || max_kv_len < 1 || max_kv_len > 32 || N < 4 || N % 4) return false;
+  // one window only, and nothing either half of the kernel has no parameter for
+  if (att.q_off || att.q_len || att.kv_off || att.kv_len || att.fsmn_w || att.mem || !window_kernels_serve(att)) return false;
+  if (proj.R2 || proj.relu || proj.ln_g || proj.ln_colsum || (proj.K && proj.K != 512)) return false;
+  const int lds = 4 * 4 * 32 * 33 * 4 + 4 * 32 * 33 * 4 + kWaves * 20 * 4 * 4;       // 89,600 B
+  const dim3 grid(N / 4);
+#define PFHIP_LAUNCH_AO(FS_, RPL_)                                                                                                      \
+  launch_with_lds<fused_att_out_kernel<FS_, RPL_>, 1024>(grid, lds, s, att.Q, att.ldq, att.K, att.ldk, att.V, att.ldv, Lq, max_kv_len, \
+                                                         att.scale * 1.4426950408889634f, proj.W, proj.ldw, proj.C, proj.ldc, proj.bias, \
+                                                         proj.R1, proj.ldr1, proj.fsmn_v, proj.ldv, proj.fsmn_w, N)
+  if (proj.fsmn_v) { if (Lq <= 8) PFHIP_LAUNCH_AO(true, 2); else PFHIP_LAUNCH_AO(true, 5); }
   else { if (Lq <= 8) PFHIP_LAUNCH_AO(false, 2); else PFHIP_LAUNCH_AO(false, 5); }
 #undef PFHIP_LAUNCH_AO
   return true;
