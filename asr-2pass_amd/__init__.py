@@ -64,6 +64,10 @@ ABI_SYMBOLS = [
     # speech quality: the DNSMOS networks
     "pfhip_mos_create_from_files", "pfhip_mos_create_from_memory", "pfhip_mos_destroy", "pfhip_mos_set_workspace", "pfhip_mos_score",
     "pfhip_mos_score_s16", "pfhip_mos_score_windows", "pfhip_mos_score_windows_s16",
+    # SenseVoiceSmall: the forward with the CTC prefix beam search (and hotwords) on the device
+    "pfhip_svs_forward_beam", "pfhip_svs_forward_beam_s16",
+    # CTC prefix beam search: the hotword context graph (host only)
+    "pfhip_ctx_graph_create", "pfhip_ctx_graph_destroy", "pfhip_ctx_graph_vocab", "pfhip_ctx_graph_dump",
 ]
 
 
@@ -122,6 +126,16 @@ class _SvsOut(ctypes.Structure):
 class _SvsAlignOut(ctypes.Structure):
     _fields_ = [("tok_begin", ctypes.POINTER(ctypes.c_int32)), ("tok_end", ctypes.POINTER(ctypes.c_int32)),
                 ("tok_logp", ctypes.POINTER(ctypes.c_float)), ("score", ctypes.POINTER(ctypes.c_float)), ("max_tokens", ctypes.c_int)]
+
+
+class _SvsBeamOpts(ctypes.Structure):
+    _fields_ = [("first_beam", ctypes.c_int), ("second_beam", ctypes.c_int), ("nbest", ctypes.c_int), ("graph", ctypes.c_void_p)]
+
+
+class _SvsBeamOut(ctypes.Structure):
+    _fields_ = [("n_hyp", ctypes.POINTER(ctypes.c_int32)), ("ids", ctypes.POINTER(ctypes.c_int32)), ("n_tokens", ctypes.POINTER(ctypes.c_int32)),
+                ("score", ctypes.POINTER(ctypes.c_float)), ("ctc_score", ctypes.POINTER(ctypes.c_float)),
+                ("ctx_score", ctypes.POINTER(ctypes.c_float)), ("max_tokens", ctypes.c_int)]
 
 
 class _StreamDetail(ctypes.Structure):
@@ -285,6 +299,16 @@ def load_lib() -> ctypes.CDLL:
         lib.pfhip_svs_forward_spans_s16.argtypes = lib.pfhip_svs_forward_spans.argtypes
     if hasattr(lib, "pfhip_svs_set_batching"):
         lib.pfhip_svs_set_batching.argtypes = [vp, ci, ci]
+    if hasattr(lib, "pfhip_svs_forward_beam"):
+        lib.pfhip_svs_forward_beam.argtypes = lib.pfhip_svs_forward.argtypes + [ctypes.POINTER(_SvsBeamOpts), ctypes.POINTER(_SvsBeamOut)]
+        lib.pfhip_svs_forward_beam_s16.argtypes = lib.pfhip_svs_forward_beam.argtypes
+    if hasattr(lib, "pfhip_ctx_graph_create"):
+        i32p, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        lib.pfhip_ctx_graph_create.argtypes = [i32p, ctypes.POINTER(ci), fp, ci, ci, ctypes.POINTER(vp)]
+        lib.pfhip_ctx_graph_destroy.argtypes = [vp]
+        lib.pfhip_ctx_graph_destroy.restype = None
+        lib.pfhip_ctx_graph_vocab.argtypes = [vp]
+        lib.pfhip_ctx_graph_dump.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), i32p, fp, ci, i32p, i32p, fp, ci]
     lib.pfhip_profile_enable.argtypes = [vp, ci]
     lib.pfhip_profile_read.argtypes = [vp, ctypes.POINTER(_Profile), ci]
     # 16-bit PCM in: the argument lists of the f32 siblings
@@ -301,6 +325,60 @@ def _check(lib, st):
         e = PfhipError(f"pfhip status {st}: {lib.pfhip_last_error().decode()}")
         e.status = int(st)
         raise e
+
+
+class ContextGraph:
+    """The hotword context graph of the CTC prefix beam search (pfhip_ctx_graph_create, include/pfhip.h): words = token-id
+    sequences, weights = one weight per token (a sequence per word, or one number per word for every token of it).  Host only:
+    no device is needed.  handle: what ops.ctc_prefix_beam passes on; dump(): the CSR arrays."""
+
+    def __init__(self, words, weights, vocab):
+        lib = load_lib()
+        words = [[int(t) for t in w] for w in words]
+        wts = [[float(x)] * len(w) if np.isscalar(x) else [float(y) for y in x] for w, x in zip(words, weights)]
+        if len(wts) != len(words) or any(len(a) != len(b) for a, b in zip(words, wts)):
+            raise PfhipError("ContextGraph: one weight per token (or per word) is needed")
+        ids = np.asarray([t for w in words for t in w] or [0], np.int32)
+        tw = np.asarray([x for w in wts for x in w] or [0], np.float32)
+        n = np.asarray([len(w) for w in words] or [0], np.int32)
+        h = ctypes.c_void_p()
+        st = lib.pfhip_ctx_graph_create(ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                        tw.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(words), int(vocab), ctypes.byref(h))
+        if st != 0:
+            e = PfhipError(f"pfhip_ctx_graph_create: status {st} (an id outside 1 .. vocab - 1, an empty word or a non-finite weight)")
+            e.status = int(st)
+            raise e
+        self._lib, self.handle, self.vocab = lib, h, int(vocab)
+
+    def dump(self):
+        """dict(arc_begin [S + 1], escape [S], arc_label, arc_next, arc_weight [A])."""
+        lib = self._lib
+        ns, na = ctypes.c_int(), ctypes.c_int()
+        st = lib.pfhip_ctx_graph_dump(self.handle, ctypes.byref(ns), ctypes.byref(na), None, None, 0, None, None, None, 0)
+        assert st == 0
+        S, A = ns.value, na.value
+        out = dict(arc_begin=np.zeros(S + 1, np.int32), escape=np.zeros(S, np.float32), arc_label=np.zeros(max(A, 1), np.int32),
+                   arc_next=np.zeros(max(A, 1), np.int32), arc_weight=np.zeros(max(A, 1), np.float32))
+        i32p, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        st = lib.pfhip_ctx_graph_dump(self.handle, ctypes.byref(ns), ctypes.byref(na), out["arc_begin"].ctypes.data_as(i32p),
+                                      out["escape"].ctypes.data_as(fp), S, out["arc_label"].ctypes.data_as(i32p),
+                                      out["arc_next"].ctypes.data_as(i32p), out["arc_weight"].ctypes.data_as(fp), max(A, 1))
+        if st != 0:
+            raise PfhipError(f"pfhip_ctx_graph_dump: status {st}")
+        for key in ("arc_label", "arc_next", "arc_weight"):
+            out[key] = out[key][:A]
+        return out
+
+    def close(self):
+        if self.handle:
+            self._lib.pfhip_ctx_graph_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def read_model_files(kind, model, second=None, hotword=None, cmvn=None, config=None):
@@ -952,8 +1030,12 @@ class SenseVoiceHip:
         T = -(-frames // int(self.cfg.get("lfr_n", 6)))
         return T + 4 if T > 0 else 0
 
-    def forward(self, din, lang="auto", itn=True, lid=None, textnorm=None, want_logp=False, want_spans=False, max_tokens=None):
-        """One packed forward.  want_spans: pfhip_svs_forward_spans — the result also holds span_begin / span_end / span_logp
+    def forward(self, din, lang="auto", itn=True, lid=None, textnorm=None, want_logp=False, want_spans=False, max_tokens=None,
+                beam=None, nbest=None, graph=None, beam_max_tokens=None):
+        """One packed forward.  beam = (first_beam, second_beam): pfhip_svs_forward_beam — the CTC prefix beam search on the device,
+        with the hotwords of `graph` (a ContextGraph) — and the result also holds beam_n_hyp [B] and, per utterance, beam_ids (a list
+        of token arrays, best first; text tokens only), beam_score / beam_ctc_score / beam_ctx_score (arrays over its hypotheses);
+        nbest defaults to second_beam.  want_spans: pfhip_svs_forward_spans — the result also holds span_begin / span_end / span_logp
         (per-utterance arrays over the tokens behind the four tags, as align() returns them) and span_score [B].  lang / itn: a value for all utterances or one per utterance (svs_lang strings, booleans); lid /
         textnorm override them with prompt ids.  Returns dict(token_num [B], ids / tok_frame / tok_logp: per-utterance arrays (the four
         leading tag ids included), frame_len [B], frame_ids / frame_logp: per-utterance arrays over its rows, logp: per-utterance
@@ -985,7 +1067,24 @@ class SenseVoiceHip:
                       frame_len.ctypes.data_as(i32p), logp.ctypes.data_as(f32p) if want_logp else None, logp.size if want_logp else 0)
         args = [self._h, ptrs, ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, lid_a.ctypes.data_as(i32p), tn_a.ctypes.data_as(i32p),
                 ctypes.byref(out)]
-        if want_spans:
+        if beam is not None:
+            if want_spans:
+                raise PfhipError("forward: beam and want_spans are separate calls (align() the returned ids for spans)")
+            fbm, sbm = int(beam[0]), int(beam[1])
+            nb = sbm if nbest is None else int(nbest)
+            bmt = cap if beam_max_tokens is None else int(beam_max_tokens)
+            nbq = max(nb, 1)
+            b_nhyp = np.full(B, -7, np.int32)
+            b_ids = np.full((B, nbq, max(bmt, 1)), -1, np.int32)
+            b_ntok = np.full((B, nbq), -7, np.int32)
+            b_score, b_ctc, b_ctx = (np.full((B, nbq), np.nan, np.float32) for _ in range(3))
+            bopts = _SvsBeamOpts(fbm, sbm, nb, graph.handle if graph is not None else None)
+            bout = _SvsBeamOut(b_nhyp.ctypes.data_as(i32p), b_ids.ctypes.data_as(i32p), b_ntok.ctypes.data_as(i32p), b_score.ctypes.data_as(f32p),
+                               b_ctc.ctypes.data_as(f32p), b_ctx.ctypes.data_as(f32p), max(bmt, 1) if bmt > 0 else 0)
+            fn = self._lib.pfhip_svs_forward_beam_s16 if s16 else self._lib.pfhip_svs_forward_beam
+            args += [ctypes.byref(bopts), ctypes.byref(bout)]
+            self.last_beam_n_tokens = b_ntok          # also where the call ends in PFHIP_ERR_CAPACITY: the lengths needed
+        elif want_spans:
             sp_begin = np.full((B, cap), -7, np.int32)
             sp_end = np.full((B, cap), -7, np.int32)
             sp_logp = np.full((B, cap), np.nan, np.float32)
@@ -1005,6 +1104,11 @@ class SenseVoiceHip:
                    frame_ids=cut(frame_ids), frame_logp=cut(frame_logp))
         if want_logp:
             res["logp"] = cut(logp)
+        if beam is not None:
+            hyp = lambda a, b: a[b, :b_nhyp[b]]
+            res.update(beam_n_hyp=b_nhyp, beam_ids=[[b_ids[b, j, :b_ntok[b, j]] for j in range(b_nhyp[b])] for b in range(B)],
+                       beam_score=[hyp(b_score, b) for b in range(B)], beam_ctc_score=[hyp(b_ctc, b) for b in range(B)],
+                       beam_ctx_score=[hyp(b_ctx, b) for b in range(B)])
         if want_spans:
             nt = [max(int(token_num[b]) - 4, 0) for b in range(B)]
             res.update(span_begin=[sp_begin[b, :nt[b]] for b in range(B)], span_end=[sp_end[b, :nt[b]] for b in range(B)],

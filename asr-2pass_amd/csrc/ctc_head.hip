@@ -43,11 +43,15 @@ __device__ __forceinline__ void stage4(const float4& v, float scale, unsigned ch
   *reinterpret_cast<uint2*>(lo) = make_uint2(lo_pair(sub_lo(x0, h01), sub_hi(x1, h01)), lo_pair(sub_lo(x2, h23), sub_hi(x3, h23)));
 }
 
-// partials: [column tile][row] so that the merge kernel's threads (one per row) read consecutive words
-__global__ __launch_bounds__(256, 3) void ctc_head_tile_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ W, int ldw,
-                                                               const float* __restrict__ bias, float sw, int M, int V, int K, int tiles_n,
-                                                               int n_tiles, int gw, float* __restrict__ pmax, int* __restrict__ pidx,
-                                                               float* __restrict__ psum) {
+// partials: [column tile][row] so that the merge kernel's threads (one per row) read consecutive words.  The body of both tile
+// kernels below: TOPK = false is the greedy head; TOPK = true also leaves the tile's k best (value, column) pairs of every row in
+// pkv / pki [column tile][rank][row] (best first, equal values lower column first; a tile with fewer than k finite logits ends in
+// (-inf, INT_MAX) pairs).
+template <bool TOPK>
+__device__ __forceinline__ void ctc_head_tile(const float* __restrict__ X, int ldx, const float* __restrict__ W, int ldw,
+                                              const float* __restrict__ bias, float sw, int M, int V, int K, int tiles_n, int n_tiles, int gw,
+                                              float* __restrict__ pmax, int* __restrict__ pidx, float* __restrict__ psum, int k,
+                                              float* __restrict__ pkv, int* __restrict__ pki) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[kHeadLds];
 
   int tm, tn;
@@ -172,18 +176,55 @@ __global__ __launch_bounds__(256, 3) void ctc_head_tile_kernel(const float* __re
         const size_t o = (size_t)tn * M + grow;
         pmax[o] = best; pidx[o] = bidx; psum[o] = e;
       }
+      if constexpr (TOPK) {
+        // k rounds of the same (max, lowest column) pass: each round stores the winner and strikes it from the lane that holds it
+        for (int rank = 0; rank < k; ++rank) {                        // k is uniform: every lane reaches the shuffles
+          if (c4 == 0 && grow < M) {
+            const size_t o = ((size_t)tn * k + rank) * M + grow;
+            pkv[o] = best; pki[o] = bidx;
+          }
+          if (rank + 1 == k) break;
+          const int struck = bidx;
+          best = -INFINITY;
+          bidx = 0x7fffffff;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            if (gcol + q == struck) v[q] = -INFINITY;
+            if (v[q] > best) { best = v[q]; bidx = gcol + q; }
+          }
+#pragma unroll
+          for (int off = 16; off >= 1; off >>= 1) {
+            const float ob = __shfl_xor(best, off);
+            const int oi = __shfl_xor(bidx, off);
+            if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+          }
+        }
+      }
     }
     __syncthreads();
   }
 }
 
-// one thread per row walks the row's column tiles in ascending order with the running triple: a later tile replaces the maximum
+__global__ __launch_bounds__(256, 3) void ctc_head_tile_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ W, int ldw,
+                                                               const float* __restrict__ bias, float sw, int M, int V, int K, int tiles_n,
+                                                               int n_tiles, int gw, float* __restrict__ pmax, int* __restrict__ pidx,
+                                                               float* __restrict__ psum) {
+  ctc_head_tile<false>(X, ldx, W, ldw, bias, sw, M, V, K, tiles_n, n_tiles, gw, pmax, pidx, psum, 0, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256, 3) void ctc_head_tile_topk_kernel(const float* __restrict__ X, int ldx, const float* __restrict__ W, int ldw,
+                                                                    const float* __restrict__ bias, float sw, int M, int V, int K,
+                                                                    int tiles_n, int n_tiles, int gw, float* __restrict__ pmax,
+                                                                    int* __restrict__ pidx, float* __restrict__ psum, int k,
+                                                                    float* __restrict__ pkv, int* __restrict__ pki) {
+  ctc_head_tile<true>(X, ldx, W, ldw, bias, sw, M, V, K, tiles_n, n_tiles, gw, pmax, pidx, psum, k, pkv, pki);
+}
+
+// a row's column tiles in ascending order with the running triple: a later tile replaces the maximum
 // only when strictly larger (so among equal maxima the lowest column wins) and the sum is rescaled to the maximum it then has
-__global__ __launch_bounds__(256) void ctc_head_merge_kernel(const float* __restrict__ pmax, const int* __restrict__ pidx,
-                                                             const float* __restrict__ psum, int M, int tiles_n, int32_t* __restrict__ ids,
-                                                             float* __restrict__ logp_best, float* __restrict__ lse, int* range_flag) {
-  const int row = blockIdx.x * 256 + threadIdx.x;
-  if (row >= M) return;
+__device__ __forceinline__ void merge_row_triples(const float* __restrict__ pmax, const int* __restrict__ pidx, const float* __restrict__ psum,
+                                                  int M, int tiles_n, int row, int32_t* __restrict__ ids, float* __restrict__ logp_best,
+                                                  float* __restrict__ lse, int* range_flag, float* m_out, float* ls_out) {
   float m = -INFINITY, s = 0.f;
   int idx = 0x7fffffff;
   for (int t = 0; t < tiles_n; ++t) {
@@ -201,6 +242,66 @@ __global__ __launch_bounds__(256) void ctc_head_merge_kernel(const float* __rest
   logp_best[row] = -ls;                                              // best logit - (m + log s)
   if (lse) lse[row] = m + ls;
   if (range_flag && !(fabsf(m + ls) < INFINITY)) atomicOr(range_flag, 1);      // NaN / Inf reached the logits (as logsoftmax_argmax_kernel)
+  *m_out = m; *ls_out = ls;
+}
+
+// one thread per row
+__global__ __launch_bounds__(256) void ctc_head_merge_kernel(const float* __restrict__ pmax, const int* __restrict__ pidx,
+                                                             const float* __restrict__ psum, int M, int tiles_n, int32_t* __restrict__ ids,
+                                                             float* __restrict__ logp_best, float* __restrict__ lse, int* range_flag) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= M) return;
+  float m, ls;
+  merge_row_triples(pmax, pidx, psum, M, tiles_n, row, ids, logp_best, lse, range_flag, &m, &ls);
+}
+
+// The merge of the top-k head: the greedy outputs by the same walk, then the k best of the row's tiles x k pairs.  The running list
+// is 16 (value, column) pairs in registers of which the first k are used, kept sorted by an unrolled bubble insert (static indices
+// only: no scratch).  A tile's pairs are sorted, so the tile is left at its first pair that does not beat slot k - 1.
+__global__ __launch_bounds__(256) void ctc_head_merge_topk_kernel(const float* __restrict__ pmax, const int* __restrict__ pidx,
+                                                                  const float* __restrict__ psum, const float* __restrict__ pkv,
+                                                                  const int* __restrict__ pki, int M, int tiles_n, int k,
+                                                                  int32_t* __restrict__ ids, float* __restrict__ logp_best,
+                                                                  float* __restrict__ lse, int32_t* __restrict__ topk_ids,
+                                                                  float* __restrict__ topk_logp, int* range_flag) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= M) return;
+  float m, ls;
+  merge_row_triples(pmax, pidx, psum, M, tiles_n, row, ids, logp_best, lse, range_flag, &m, &ls);
+  float val[kCtcTopkMax];
+  int col[kCtcTopkMax];
+#pragma unroll
+  for (int j = 0; j < kCtcTopkMax; ++j) { val[j] = -INFINITY; col[j] = 0x7fffffff; }
+  for (int t = 0; t < tiles_n; ++t)
+    for (int rank = 0; rank < k; ++rank) {
+      const size_t o = ((size_t)t * k + rank) * M + row;
+      float cv = pkv[o];
+      int ci = pki[o];
+      float lv = val[0];                                             // the list's slot k - 1, picked with static indices
+      int lc = col[0];
+#pragma unroll
+      for (int j = 1; j < kCtcTopkMax; ++j)
+        if (j == k - 1) { lv = val[j]; lc = col[j]; }
+      if (!(cv > lv || (cv == lv && ci < lc))) break;                // it cannot be among the k best: nor can the tile's later pairs
+#pragma unroll
+      for (int j = 0; j < kCtcTopkMax; ++j) {
+        if (j >= k) break;                                           // slots from k on are never returned
+        const bool in = cv > val[j] || (cv == val[j] && ci < col[j]);
+        const float tv = in ? val[j] : cv;
+        const int ti = in ? col[j] : ci;
+        val[j] = in ? cv : val[j];
+        col[j] = in ? ci : col[j];
+        cv = tv; ci = ti;
+      }
+    }
+#pragma unroll
+  for (int j = 0; j < kCtcTopkMax; ++j)
+    if (j < k) {
+      const bool none = col[j] == 0x7fffffff;                        // fewer than k finite logits in the row
+      topk_ids[(size_t)row * k + j] = none ? -1 : col[j];
+      // (value - maximum) - log(sum) never increases along the row; rank 0 is logp_best's own -ls (0 - ls would lose the sign of -0)
+      topk_logp[(size_t)row * k + j] = none ? -INFINITY : (j == 0 ? -ls : (val[j] - m) - ls);
+    }
 }
 
 // ---- CTC collapse ---------------------------------------------------------------------------------------------------------------
@@ -286,7 +387,46 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
   if (lane == 0) lse[row] = m + logf(sum);
 }
 
+// The k best columns of a row of the unfused head's log-probs, one wave per row: round r takes the largest value that ranks behind
+// round r - 1's pick (smaller, or equal with a higher column), lowest column first — k passes over a row that sits in L2.
+__global__ __launch_bounds__(256) void row_topk_kernel(const float* __restrict__ logp, int ld, int rows, int V, int k,
+                                                       int32_t* __restrict__ topk_ids, float* __restrict__ topk_logp) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;                                           // whole waves leave: the shuffles below stay inside a wave
+  const float* x = logp + (size_t)row * ld;
+  float pv = INFINITY;
+  int pc = -1;
+  for (int r = 0; r < k; ++r) {
+    float best = -INFINITY;
+    int bc = 0x7fffffff;
+    for (int c = lane; c < V; c += 64) {
+      const float v = x[c];
+      const bool behind = v < pv || (v == pv && c > pc);
+      if (behind && (v > best || (v == best && c < bc))) { best = v; bc = c; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const float ob = __shfl_xor(best, off);
+      const int oc = __shfl_xor(bc, off);
+      if (ob > best || (ob == best && oc < bc)) { best = ob; bc = oc; }
+    }
+    if (lane == 0) {
+      topk_ids[(size_t)row * k + r] = bc == 0x7fffffff ? -1 : bc;
+      topk_logp[(size_t)row * k + r] = bc == 0x7fffffff ? -INFINITY : best;
+    }
+    pv = best; pc = bc;
+  }
+}
+
 }  // namespace
+
+bool launch_row_topk(const float* logp, int ld, int rows, int V, int k, int32_t* topk_ids, float* topk_logp, hipStream_t s) {
+  if (k < 1 || k > kCtcTopkMax || V < k || ld < V || rows < 0) return false;
+  if (rows == 0) return true;
+  if (!logp || !topk_ids || !topk_logp) return false;
+  hipLaunchKernelGGL(row_topk_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logp, ld, rows, V, k, topk_ids, topk_logp);
+  return true;
+}
 
 void launch_svs_prompt_rows(const float* E, int D, const int* prompt, const int* row_off, const int* len, int B, float* feats, int ld,
                             hipStream_t s) {
@@ -321,6 +461,36 @@ bool launch_ctc_head(const float* X, int ldx, const float* W, int ldw, const flo
   hipLaunchKernelGGL(ctc_head_tile_kernel, dim3(n_tiles), dim3(256), 0, s, X, ldx, W, ldw, bias, w_scale, M, V, K, tiles_n, n_tiles, gw, pmax,
                      pidx, psum);
   hipLaunchKernelGGL(ctc_head_merge_kernel, dim3((M + 255) / 256), dim3(256), 0, s, pmax, pidx, psum, M, tiles_n, ids, logp_best, lse, range_flag);
+  return true;
+}
+
+size_t ctc_head_topk_workspace_bytes(int M, int V, int k) {
+  const size_t tiles_n = (size_t)(V + kHT - 1) / kHT;
+  return ctc_head_workspace_bytes(M, V) + 2 * tiles_n * (size_t)k * (size_t)M * 4;
+}
+
+bool launch_ctc_head_topk(const float* X, int ldx, const float* W, int ldw, const float* bias, float w_scale, int M, int V, int K, int k,
+                          int32_t* ids, float* logp_best, float* lse, int32_t* topk_ids, float* topk_logp, void* workspace,
+                          size_t workspace_bytes, hipStream_t s, int* range_flag) {
+  if (k < 1 || k > kCtcTopkMax || V < k) return false;
+  if (M < 0 || V <= 0 || K < 32 || K % 32 || !W || !bias || ldw < K || ldw % 4 || !(w_scale > 0.f)) return false;
+  if (M == 0) return true;
+  if (!X || ldx < K || ldx % 4 || !ids || !logp_best || !topk_ids || !topk_logp || !workspace ||
+      workspace_bytes < ctc_head_topk_workspace_bytes(M, V, k))
+    return false;
+  const int tiles_m = (M + kHT - 1) / kHT, tiles_n = (V + kHT - 1) / kHT;
+  if ((long long)tiles_m * tiles_n > 0x7fffffffLL) return false;
+  const int n_tiles = tiles_m * tiles_n;
+  const int gw = std::max(1, std::min(tiles_n, (int)(2.0 * 1024 * 1024 / ((double)kHT * K * 4))));      // as launch_ctc_head
+  float* pmax = static_cast<float*>(workspace);
+  int* pidx = reinterpret_cast<int*>(pmax + (size_t)tiles_n * M);
+  float* psum = pmax + 2 * (size_t)tiles_n * M;
+  float* pkv = pmax + 3 * (size_t)tiles_n * M;
+  int* pki = reinterpret_cast<int*>(pkv + (size_t)tiles_n * k * M);
+  hipLaunchKernelGGL(ctc_head_tile_topk_kernel, dim3(n_tiles), dim3(256), 0, s, X, ldx, W, ldw, bias, w_scale, M, V, K, tiles_n, n_tiles, gw,
+                     pmax, pidx, psum, k, pkv, pki);
+  hipLaunchKernelGGL(ctc_head_merge_topk_kernel, dim3((M + 255) / 256), dim3(256), 0, s, pmax, pidx, psum, pkv, pki, M, tiles_n, k, ids,
+                     logp_best, lse, topk_ids, topk_logp, range_flag);
   return true;
 }
 

@@ -89,6 +89,9 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   if (nm == "feats") { src = m->feats.p; n = (size_t)m->M * m->weights->feat_dim; }
   else if (nm == "enc") { src = m->weights->cfg.svs ? m->x.p : m->enc.p; n = (size_t)m->M * d; }      // SenseVoice: the rows after tp.norm
   else if (nm == "lse" && m->weights->cfg.svs) { src = m->svs_lse.p; n = (size_t)m->M; }             // the rows' log-sum-exp either CTC head kept
+  // the k best columns of every row of the last pfhip_svs_forward_beam [M][first_beam]; the ids are int32 words in the float buffer
+  else if (nm == "ctc_topk_ids" && m->weights->cfg.svs && m->svs_topk_k) { src = m->svs_topk_ids.p; n = (size_t)m->M * m->svs_topk_k; }
+  else if (nm == "ctc_topk_logp" && m->weights->cfg.svs && m->svs_topk_k) { src = m->svs_topk_logp.p; n = (size_t)m->M * m->svs_topk_k; }
   else if (m->weights->cfg.svs) return fail(PFHIP_ERR_ARG, "a SenseVoice model has the tensors feats, enc and lse, not " + nm);
   else if (nm == "alphas") { src = m->alphas.p; n = (size_t)m->M; }
   else if (nm == "emb") { src = m->emb.p; n = (size_t)m->ML * d; }

@@ -65,9 +65,10 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
       for (int b = 0; b < B; ++b) hm[o + b] = m->row_off[b] + 4;
       m->m_feat_off = dm + o; o += B;
       std::memcpy(hm + o, m->svs_prompt.data(), 4 * 4 * (size_t)B); m->m_prompt = dm + o; o += 4 * (size_t)B;
-      // the speech rows N_b the greedy tokens are aligned against (heads.cpp), 0 for an utterance nobody wants spans of
-      const bool spans = (int)m->svs_span_want.size() == B;
-      for (int b = 0; b < B; ++b) hm[o + b] = spans && m->svs_span_want[b] && m->T[b] > 4 ? m->T[b] - 4 : 0;
+      // the speech rows N_b the greedy tokens are aligned against (heads.cpp), 0 for an utterance nobody wants spans of; a beam
+      // forward (pfhip_svs_forward_beam) searches the speech rows of every utterance
+      const bool spans = (int)m->svs_span_want.size() == B, beam = m->svs_beam_fb > 0;
+      for (int b = 0; b < B; ++b) hm[o + b] = ((spans && m->svs_span_want[b]) || beam) && m->T[b] > 4 ? m->T[b] - 4 : 0;
       m->m_speech_len = dm + o; o += B;
     }
     if (o & 1) ++o;

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "offline.h"
+#include "ctx_graph.h"
 #include "launch_common.h"
 
 namespace {
@@ -235,7 +236,18 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
   // than its LDS rows hold (an utterance with more labels is answered as infeasible by the kernel's own check).
   const bool spans = (int)m->svs_span_want.size() == B;
   const int mt = spans ? std::min(maxT - 4, pfhip::ctc_align_max_tokens()) : 0;
-  const size_t sbt = (size_t)B * mt, n_words = n_base + (mt > 0 ? 3 * sbt + B : 0);
+  const size_t sbt = (size_t)B * mt, n_span = n_base + (mt > 0 ? 3 * sbt + B : 0);
+  // pfhip_svs_forward_beam: the search's results behind those, in the same copy.  A hypothesis has no more tokens than speech rows.
+  const int fb = m->svs_beam_fb, sb = m->svs_beam_sb, nb = m->svs_beam_nbest;
+  const int bmt = fb ? std::max(maxT - 4, 0) : 0;
+  const size_t n_beam = fb ? (size_t)B + (size_t)B * nb * (4 + (size_t)bmt) : 0, n_words = n_span + n_beam;
+  m->svs_beam_mt = bmt;
+  m->svs_beam_word = n_span;
+  m->svs_topk_k = 0;
+  if (fb) {
+    HIP_TRY(m->svs_topk_ids.ensure((size_t)M * fb * 4));
+    HIP_TRY(m->svs_topk_logp.ensure((size_t)M * fb * 4));
+  }
   m->svs_span_mt = mt > 0 ? mt : 0;
   m->svs_span_word = n_base;
   HIP_TRY(m->counts.ensure(n_words * 4));
@@ -275,6 +287,9 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
         pfhip::launch_logsoftmax_argmax(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_logp.f(), d_fid + q0, s, m->d_range_flag);
         pfhip::launch_gather_best(m->svs_logp.f(), V, d_fid + q0, rows, d_flp + q0, s);
         pfhip::launch_row_lse(m->svs_logits.f(), w.vocab_pad, rows, V, m->svs_lse.f() + q0, s);
+        if (fb && !pfhip::launch_row_topk(m->svs_logp.f(), V, rows, V, fb, m->svs_topk_ids.i() + (size_t)q0 * fb,
+                                          m->svs_topk_logp.f() + (size_t)q0 * fb, s))
+          return fail(PFHIP_ERR_ARG, "beam search: first_beam larger than the vocabulary");
       }
       if (host_dst) HIP_TRY(hipMemcpyAsync(host_dst + (size_t)c0 * V, m->svs_logp.p, (size_t)rows * V * 4, hipMemcpyDeviceToHost, s));
       ++m->svs_head_chunks;
@@ -287,7 +302,15 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
     const pfhip_status us = unfused_rows(0, M, m->svs_logp_host);
     if (us) return us;
   } else {
-    if (!all_unfused) {
+    if (!all_unfused && fb) {                          // the head once, in its top-k form: ids / logp / lse are the greedy head's bit for bit
+      const size_t ws = pfhip::ctc_head_topk_workspace_bytes(M, V, fb);
+      HIP_TRY(m->svs_ws.ensure(ws));
+      Scope sc(m, s, K_GEMM, 2.0 * M * (double)V * d,
+               4.0 * ((double)M * d + (double)V * d) + (12.0 + 8.0 * fb) * M * (w.vocab_pad / pfhip::kTileN));
+      if (!pfhip::launch_ctc_head_topk(X, d, w.ctc.w, d, w.ctc.b, w.ctc.scale, M, V, d, fb, d_fid, d_flp, m->svs_lse.f(), m->svs_topk_ids.i(),
+                                       m->svs_topk_logp.f(), m->svs_ws.p, ws, s, m->d_range_flag))
+        return fail(PFHIP_ERR_UNSUPPORTED, "CTC head: d_model must be a multiple of 32 and first_beam at most the vocabulary");
+    } else if (!all_unfused) {
       const size_t ws = pfhip::ctc_head_workspace_bytes(M, V);
       HIP_TRY(m->svs_ws.ensure(ws));
       Scope sc(m, s, K_GEMM, 2.0 * M * (double)V * d, 4.0 * ((double)M * d + (double)V * d) + 12.0 * M * (w.vocab_pad / pfhip::kTileN));
@@ -337,6 +360,34 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
     if (!pfhip::launch_ctc_align(m->al_E.f(), d_eoff, (size_t)cap, m->m_speech_len, d_nlab, d_ids, d_laboff, B, mt, d_begin, d_end, d_slogp,
                                  d_score, m->al_ws.p, ws, s))
       return fail(PFHIP_ERR_ARG, "CTC alignment refused its arguments");
+  }
+  if (fb) {
+    // The prefix beam search over the speech rows (the four prompt rows are no CTC rows, sensevoice-small.cpp:422): one workgroup per
+    // utterance on the k best columns either head left.  The graph goes to the front of the search's workspace with this call.
+    const pfhip_ctx_graph* g = m->svs_beam_graph;
+    const size_t gbytes = g ? (g->packed.size() * 4 + 15) / 16 * 16 : 0;
+    const size_t nodes = pfhip::ctc_prefix_beam_workspace_bytes(M, B, sb);
+    HIP_TRY(m->svs_beam_ws.ensure(gbytes + nodes));
+    pfhip::CtxGraphDev dev;
+    if (g) {
+      HIP_TRY(hipMemcpyAsync(m->svs_beam_ws.p, g->packed.data(), g->packed.size() * 4, hipMemcpyHostToDevice, s));
+      const int S_ = g->n_states(), A = g->n_arcs();
+      const int32_t* gw = m->svs_beam_ws.i();
+      dev.n_states = S_; dev.n_arcs = A;
+      dev.arc_begin = gw;
+      dev.escape = reinterpret_cast<const float*>(gw + S_ + 1);
+      dev.arc_label = gw + 2 * S_ + 1;
+      dev.arc_next = gw + 2 * S_ + 1 + A;
+      dev.arc_weight = reinterpret_cast<const float*>(gw + 2 * S_ + 1 + 2 * A);
+    }
+    const size_t bn = (size_t)B * nb;
+    int32_t *b_nhyp = dn + n_span, *b_ntok = b_nhyp + B, *b_ids = b_ntok + bn;
+    float *b_score = reinterpret_cast<float*>(b_ids + bn * bmt), *b_ctc = b_score + bn, *b_ctx = b_ctc + bn;
+    if (!pfhip::launch_ctc_prefix_beam(m->svs_topk_ids.i(), m->svs_topk_logp.f(), fb, M, m->m_feat_off, m->m_speech_len, B, V, c.blank_id, fb, sb,
+                                       dev, nb, bmt, b_nhyp, b_ids, b_ntok, b_score, b_ctc, b_ctx,
+                                       static_cast<char*>(m->svs_beam_ws.p) + gbytes, nodes, s))
+      return fail(PFHIP_ERR_ARG, "CTC prefix beam search refused its arguments");
+    m->svs_topk_k = fb;
   }
   HIP_TRY(hipMemcpyAsync(m->h_counts.p, m->counts.p, n_words * 4, hipMemcpyDeviceToHost, s));
   {

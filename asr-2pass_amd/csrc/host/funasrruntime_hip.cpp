@@ -14,6 +14,7 @@
 #include "ct_transformer_hip.h"
 #include "fsmn_vad_hip.h"
 #include "paraformer_hip.h"
+#include "ctc_prefix_decoder_hip.h"
 #include "sensevoice_hip.h"
 #include "tpass_audio.h"
 
@@ -202,7 +203,10 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   funasr::SenseVoiceSmallHip* svs = os->svs.get();      // funasrruntime.cpp:265-266: the model type routes the Forward call
   // FunOfflineSetCtcStamps: the spans of the greedy text's tokens.  With a decoder attached the text is a search's, which returns a
   // string and no ids to align: the stamps stay empty
-  const bool svs_stamps = svs && os->svs_ctc_stamps.load() && !dec_handle;
+  // A CtcPrefixDecoderHip (FunASRCtcDecoderInit) selects the device search: its handle goes through to the adapter, and its best
+  // ids ARE there to align.  Any other decoder handle keeps what it had for this model: it is not passed on.
+  funasr::CtcPrefixDecoderHip* search = svs ? dynamic_cast<funasr::CtcPrefixDecoderHip*>(static_cast<funasr::Decoder*>(dec_handle)) : nullptr;
+  const bool svs_stamps = svs && os->svs_ctc_stamps.load() && (!dec_handle || search);
   if (wav_format != "pcm" && wav_format != "PCM") return nullptr;      // the reference decodes other containers with ffmpeg
   // Audio::LoadPcmwav (audio.cpp:787-819); from here on samples, segments and stamps are at the model's rate (GetTimeLen
   // divides by dest_sample_rate, audio.cpp:254-257).
@@ -267,8 +271,8 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
       len[k] = same_rate || !pcm16 ? res->segs[batch[k]].second - res->segs[batch[k]].first : n_in;
     }
     const std::vector<std::string> msg_batch =
-        svs ? (pcm16 ? svs->ForwardPcm16(buff16.data(), len.data(), true, svs_lang, svs_itn, nullptr, (int)batch.size())
-                     : svs->Forward(buff.data(), len.data(), true, svs_lang, svs_itn, nullptr, (int)batch.size())) :
+        svs ? (pcm16 ? svs->ForwardPcm16(buff16.data(), len.data(), true, svs_lang, svs_itn, search, (int)batch.size())
+                     : svs->Forward(buff.data(), len.data(), true, svs_lang, svs_itn, search, (int)batch.size())) :
         pcm16 ? os->asr.ForwardPcm16(buff16.data(), len.data(), true, hw_emb, nullptr, (int)batch.size(), same_rate ? 0 : sampling_rate)
               : os->asr.Forward(buff.data(), len.data(), true, hw_emb, nullptr, (int)batch.size());
     for (size_t k = 0; k < batch.size(); ++k, ++msg_idx) {        // funasrruntime.cpp:270-279
@@ -276,7 +280,7 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
       msgs[seg] = msg_batch[k];
       res->seg_ids[seg] = svs ? svs->LastTokenIds()[k] : os->asr.LastTokenIds()[k];
       if (svs) {                                                  // confidences stay with the adapter
-        if (svs_stamps && k == 0) svs->AlignGreedyTokens();       // once per batch, right behind its forward; refused: no stamps
+        if (svs_stamps && k == 0) search ? svs->AlignSearchTokens() : svs->AlignGreedyTokens();      // once per batch, right behind its forward; refused: no stamps
         if (svs_stamps && k < svs->LastTokenStampsMs().size()) svs_ms[seg] = svs->LastTokenStampsMs()[k];
         continue;
       }
@@ -449,11 +453,31 @@ void FunTpassSetCtcStamps(FUNASR_HANDLE tpass_handle, int on) {
   if (ts && ts->svs) ts->svs_ctc_stamps.store(on != 0);
 }
 
+// FunASRWfstDecoderInit's no-LM branch (funasrruntime.cpp:836-894): a CtcPrefixDecoder on the model's vocabulary
+FUNASR_DEC_HANDLE FunASRCtcDecoderInit(FUNASR_HANDLE handle, float glob_beam, float lat_beam, ASR_TYPE asr_type) {
+  if (!handle) return nullptr;
+  funasr::SenseVoiceSmallHip* svs = asr_type == ASR_OFFLINE ? static_cast<OfflineStreamHip*>(handle)->svs.get()
+                                                            : static_cast<TpassStreamHip*>(handle)->svs.get();
+  if (!svs) return nullptr;                                          // a Paraformer handle has no CTC rows to search
+  return static_cast<funasr::Decoder*>(new funasr::CtcPrefixDecoderHip(svs->GetHipVocab(), glob_beam, lat_beam));
+}
+static funasr::CtcPrefixDecoderHip* SearchOf(FUNASR_DEC_HANDLE dec) {
+  return dynamic_cast<funasr::CtcPrefixDecoderHip*>(static_cast<funasr::Decoder*>(dec));
+}
+int FunCtcDecoderLoadHwsRes(FUNASR_DEC_HANDLE dec, int inc_bias, std::unordered_map<std::string, int>& hws_map) {
+  funasr::CtcPrefixDecoderHip* d = dec ? SearchOf(dec) : nullptr;
+  return d ? d->LoadHwsRes(inc_bias, hws_map) : 0;
+}
+void FunCtcDecoderUnloadHwsRes(FUNASR_DEC_HANDLE dec) {
+  if (funasr::CtcPrefixDecoderHip* d = dec ? SearchOf(dec) : nullptr) d->UnloadHwsRes();
+}
+void FunCtcDecoderUninit(FUNASR_DEC_HANDLE dec) { delete static_cast<funasr::Decoder*>(dec); }
+
 FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_handle, const char* sz_buf, int n_len,
                                   std::vector<std::vector<std::string>>& punc_cache, bool input_finished, int sampling_rate,
                                   std::string wav_format, ASR_TYPE mode, const std::vector<std::vector<float>>& hw_emb, bool itn,
                                   int vad_tail_sil, int vad_max_len, FUNASR_DEC_HANDLE dec_handle, std::string svs_lang, bool svs_itn) {
-  (void)itn; (void)dec_handle;
+  (void)itn;
   TpassStreamHip* ts = static_cast<TpassStreamHip*>(handle);
   TpassOnlineStreamHip* os = static_cast<TpassOnlineStreamHip*>(online_handle);
   if (!ts || !os || !sz_buf) return nullptr;
@@ -509,15 +533,17 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
     const int16_t* buff16[1] = {frame.pcm16.data()};
     if (ts->svs) {                               // funasrruntime.cpp:583-587, :609-631: the model type routes the second pass
       funasr::SenseVoiceSmallHip* svs = ts->svs.get();
+      // a CtcPrefixDecoderHip selects the device search for the second pass; any other decoder handle is not passed on, as before
+      funasr::CtcPrefixDecoderHip* search = dynamic_cast<funasr::CtcPrefixDecoderHip*>(static_cast<funasr::Decoder*>(dec_handle));
       const std::vector<std::string> texts = frame.pcm16.size() == frame.data.size() && !frame.data.empty()
-                                                 ? svs->ForwardPcm16(buff16, len, true, svs_lang, svs_itn, nullptr, 1)
-                                                 : svs->Forward(buff, len, true, svs_lang, svs_itn, nullptr, 1);
+                                                 ? svs->ForwardPcm16(buff16, len, true, svs_lang, svs_itn, search, 1)
+                                                 : svs->Forward(buff, len, true, svs_lang, svs_itn, search, 1);
       const std::string text = texts.empty() ? "" : texts[0];
       if (text.empty()) continue;
       res->seg_ids.push_back(svs->LastTokenIds()[0]);
       res->segs.emplace_back(frame.global_start, frame.global_end);      // ms on the connection's time axis
       // FunTpassSetCtcStamps: the greedy tokens' spans (60-ms rows) plus the segment's start; a refused alignment leaves no pairs
-      if (ts->svs_ctc_stamps.load() && svs->AlignGreedyTokens() && !svs->LastTokenStampsMs().empty()) {
+      if (ts->svs_ctc_stamps.load() && (search ? svs->AlignSearchTokens() : svs->AlignGreedyTokens()) && !svs->LastTokenStampsMs().empty()) {
         const std::vector<float>& ms = svs->LastTokenStampsMs()[0];
         for (size_t i = 0; i + 1 < ms.size(); i += 2)
           cur_stamp += "[" + std::to_string((int)ms[i] + frame.global_start) + "," + std::to_string((int)ms[i + 1] + frame.global_start) + "],";

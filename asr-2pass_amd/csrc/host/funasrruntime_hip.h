@@ -16,6 +16,7 @@
 #pragma once
 #include <map>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #define MODEL_SVS "SenseVoiceSmall"    // com-define.h:41: a MODEL_DIR whose name contains it holds that model (offline-stream.cpp:50-56)
@@ -138,11 +139,25 @@ void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode);
 // adapter calls exactly what it always called; on, the tokens of the greedy text are aligned against the CTC rows (pfhip_svs_align) and
 // FunASRGetStamp holds "[[b,e],...]" in ms, one pair per text token (the kept ids behind the four tags), VAD segment offsets added;
 // resolution is one LFR row (60 ms).  A call with a decoder attached (dec_handle != nullptr) gets NO stamps and runs no alignment: a
-// search returns a string, not the ids an alignment needs.  Forward and alignment are two calls: when more threads call the handle
+// search returns a string, not the ids an alignment needs — except a CtcPrefixDecoderHip (FunASRCtcDecoderInit below), whose device
+// search returns ids: the stamps are then those of its best hypothesis.  Forward and alignment are two calls: when more threads call the handle
 // than it has execution contexts (PFHIP_INFLIGHT), another thread's forward can take the context in between; the alignment is then
 // refused (never run against foreign rows) and THAT batch's segments come back without stamps — under such load FunASRGetStamp of a
 // SenseVoice result may be empty or lack some segments' pairs.
 void FunOfflineSetCtcStamps(FUNASR_HANDLE handle, int on);
+// The per-connection decoder of a server without an LM (FunASRWfstDecoderInit's CtcPrefixDecoder branch, funasrruntime.cpp:836-894;
+// FunWfstDecoderLoadHwsRes / UnloadHwsRes / FunASRWfstDecoderUninit): FunASRCtcDecoderInit makes a CtcPrefixDecoderHip
+// (ctc_prefix_decoder_hip.h) on the vocabulary of the handle's SenseVoice model — nullptr for a Paraformer handle; asr_type says
+// whether `handle` is a FunOfflineInit or a FunTpassInit handle.  Passed as dec_handle to FunOfflineInferBuffer /
+// FunTpassInferBuffer it selects the CTC prefix beam search ON THE DEVICE, with first beam (int)glob_beam, second beam
+// (int)lat_beam (1..16 each) and the hotwords loaded into it; the text is the search's best hypothesis, and with
+// FunOfflineSetCtcStamps / FunTpassSetCtcStamps on, FunASRGetStamp holds the spans of ITS tokens.  Any other dec_handle is, for a
+// SenseVoice model, not passed on (as before).  FunCtcDecoderLoadHwsRes returns the hotwords that entered the graph (one with a
+// piece outside the vocabulary is skipped); an empty map changes nothing.
+FUNASR_DEC_HANDLE FunASRCtcDecoderInit(FUNASR_HANDLE handle, float glob_beam, float lat_beam, ASR_TYPE asr_type = ASR_OFFLINE);
+int FunCtcDecoderLoadHwsRes(FUNASR_DEC_HANDLE dec_handle, int inc_bias, std::unordered_map<std::string, int>& hws_map);
+void FunCtcDecoderUnloadHwsRes(FUNASR_DEC_HANDLE dec_handle);
+void FunCtcDecoderUninit(FUNASR_DEC_HANDLE dec_handle);
 void FunTpassSetCifStamps(FUNASR_HANDLE tpass_handle, int mode);
 // The 2-pass sibling of FunOfflineSetCtcStamps, for a FunTpassInit handle whose MODEL_DIR names MODEL_SVS (the second pass is then a
 // SenseVoiceSmallHip: FunTpassInferBuffer's trailing svs_lang / svs_itn go to its Forward, tpass_msg is its text with no punctuation

@@ -1,5 +1,8 @@
 // SenseVoiceSmallHip: see sensevoice_hip.h.
 #include "sensevoice_hip.h"
+#ifndef PFHIP_WITH_FUNASR
+#include "ctc_prefix_decoder_hip.h"
+#endif
 
 #include <algorithm>
 #include <cmath>
@@ -8,7 +11,7 @@
 
 namespace funasr {
 namespace {
-thread_local std::vector<std::vector<int>> tl_svs_ids, tl_svs_frames;
+thread_local std::vector<std::vector<int>> tl_svs_ids, tl_svs_frames, tl_svs_search;
 thread_local std::vector<std::vector<float>> tl_svs_conf;
 thread_local std::vector<std::vector<int>> tl_svs_spans;
 thread_local std::vector<std::vector<float>> tl_svs_stamps;
@@ -128,11 +131,18 @@ std::vector<std::string> SenseVoiceSmallHip::ForwardAny(const void* const* din, 
   tl_svs_ids.assign(results.size(), {});
   tl_svs_frames.assign(results.size(), {});
   tl_svs_conf.assign(results.size(), {});
+  tl_svs_search.assign(results.size(), {});
   tl_svs_spans.clear();
   tl_svs_stamps.clear();
   if (batch_in <= 0 || !handle_) return results;
   const int B = batch_in, V = pfhip_vocab_size(handle_);
   Decoder* decoder = static_cast<Decoder*>(decoder_handle);
+#ifndef PFHIP_WITH_FUNASR
+  CtcPrefixDecoderHip* search = dynamic_cast<CtcPrefixDecoderHip*>(decoder);      // the device search instead of the hand-off
+  if (search) decoder = nullptr;
+#else
+  void* search = nullptr;
+#endif
   // rows per utterance are known before the call: ceil(frames / 6) + 4 (sensevoice-small.cpp:520-560 is Paraformer's LfrCmvn)
   std::vector<int> rows(B);
   int max_rows = 1;
@@ -151,7 +161,21 @@ std::vector<std::string> SenseVoiceSmallHip::ForwardAny(const void* const* din, 
   out.ids = ids.data(); out.token_num = num.data(); out.max_tokens = max_rows;
   out.tok_frame = frames.data(); out.tok_logp = tok_logp.data(); out.frame_len = frame_len.data();
   if (decoder) { out.logp = logp.data(); out.logp_cap_floats = logp.size(); }
-  const pfhip_status st = s16 ? pfhip_svs_forward_s16(handle_, reinterpret_cast<const int16_t* const*>(din), len, B, lid.data(), textnorm.data(), &out)
+  std::vector<int32_t> frame_ids, b_nhyp, b_ids, b_ntok;
+  pfhip_status st;
+#ifndef PFHIP_WITH_FUNASR
+  if (search) {
+    frame_ids.assign(std::max<size_t>(total, 1), 0);
+    b_nhyp.assign(B, 0); b_ntok.assign(B, 0); b_ids.assign((size_t)B * max_rows, 0);
+    out.frame_ids = frame_ids.data();
+    const pfhip_svs_beam_opts opts{search->FirstBeam(), search->SecondBeam(), 1, search->Graph()};
+    pfhip_svs_beam_out bo{};
+    bo.n_hyp = b_nhyp.data(); bo.ids = b_ids.data(); bo.n_tokens = b_ntok.data(); bo.max_tokens = max_rows;
+    st = s16 ? pfhip_svs_forward_beam_s16(handle_, reinterpret_cast<const int16_t* const*>(din), len, B, lid.data(), textnorm.data(), &out, &opts, &bo)
+             : pfhip_svs_forward_beam(handle_, reinterpret_cast<const float* const*>(din), len, B, lid.data(), textnorm.data(), &out, &opts, &bo);
+  } else
+#endif
+  st = s16 ? pfhip_svs_forward_s16(handle_, reinterpret_cast<const int16_t* const*>(din), len, B, lid.data(), textnorm.data(), &out)
                               : pfhip_svs_forward(handle_, reinterpret_cast<const float* const*>(din), len, B, lid.data(), textnorm.data(), &out);
   if (st != PFHIP_OK) {                                          // the reference logs and returns "" (:664-667)
     std::fprintf(stderr, "SenseVoiceSmallHip::Forward: %s\n", pfhip_last_error());
@@ -164,6 +188,19 @@ std::vector<std::string> SenseVoiceSmallHip::ForwardAny(const void* const* din, 
     tl_svs_frames[b].assign(frames.begin() + at, frames.begin() + at + num[b]);
     for (int t = 0; t < num[b]; ++t) tl_svs_conf[b].push_back(std::exp(tok_logp[at + t]));
     if (frame_len[b] == 0) { results[b] = ""; continue; }        // :584-587
+#ifndef PFHIP_WITH_FUNASR
+    if (search) {                                                // CTCPrefixBeamSearch's text (:392-440) from the device's best ids
+      if (b_nhyp[b] > 0) tl_svs_search[b].assign(b_ids.begin() + at, b_ids.begin() + at + b_ntok[b]);
+      std::string text = search->IdsToText(tl_svs_search[b]);
+      const std::string lang = vocab ? vocab->Id2String(frame_ids[row0]) : "", itn = vocab ? vocab->Id2String(frame_ids[row0 + 3]) : "";
+      if (itn == "<|withitn|>") {
+        if (lang == "<|en|>") text += " ";
+      } else {
+        text += " ";
+      }
+      results[b] = text;
+    } else
+#endif
     if (decoder) {                                               // the caller's search gets the rows; between items it is restarted
       if (b > 0) { decoder->EndUtterance(); decoder->StartUtterance(); }
       results[b] = decoder->Search(logp.data() + row0 * (size_t)V, frame_len[b], V);
@@ -173,9 +210,12 @@ std::vector<std::string> SenseVoiceSmallHip::ForwardAny(const void* const* din, 
     }
     row0 += (size_t)frame_len[b];
   }
-  if (ctc_stamps_ && !decoder) AlignGreedyTokens();
+  if (ctc_stamps_ && search) AlignSearchTokens();
+  else if (ctc_stamps_ && !decoder) AlignGreedyTokens();
   return results;
 }
+
+bool SenseVoiceSmallHip::AlignSearchTokens() { return AlignTokens(std::vector<std::vector<int>>(tl_svs_search)); }
 
 bool SenseVoiceSmallHip::AlignGreedyTokens() {                     // the greedy text's tokens: the kept ids behind the four tags
   std::vector<std::vector<int>> toks(tl_svs_ids.size());
@@ -220,6 +260,7 @@ bool SenseVoiceSmallHip::AlignTokens(const std::vector<std::vector<int>>& ids) {
 
 const std::vector<std::vector<int>>& SenseVoiceSmallHip::LastTokenIds() const { return tl_svs_ids; }
 const std::vector<std::vector<int>>& SenseVoiceSmallHip::LastTokenFrames() const { return tl_svs_frames; }
+const std::vector<std::vector<int>>& SenseVoiceSmallHip::LastSearchIds() const { return tl_svs_search; }
 const std::vector<std::vector<float>>& SenseVoiceSmallHip::LastTokenConfidence() const { return tl_svs_conf; }
 const std::vector<std::vector<int>>& SenseVoiceSmallHip::LastTokenSpans() const { return tl_svs_spans; }
 const std::vector<std::vector<float>>& SenseVoiceSmallHip::LastTokenStampsMs() const { return tl_svs_stamps; }

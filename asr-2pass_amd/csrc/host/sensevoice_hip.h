@@ -48,6 +48,11 @@ class SenseVoiceSmallHip : public ParaformerHipBase, public OnlineModelOwner
   // CTCSearch (:323-377), made on the host from the ids the device collapsed.  With a decoder handle the full log-prob rows of every
   // utterance are handed to `((Decoder*)decoder_handle)->Search(rows, n_rows, vocab)` — the search itself (CTCPrefixBeamSearch /
   // BeamSearch, :651-662) is not part of this path — and, when input_finished, FinalizeDecode() gives the text.
+  // A decoder handle that is a CtcPrefixDecoderHip (ctc_prefix_decoder_hip.h; stand-alone build) is what the reference serves with
+  // CTCPrefixBeamSearch (:392-440, :651-657): the search then runs on the device with the decoder's beams and hotword graph
+  // (pfhip_svs_forward_beam), no log-prob row crosses to the host, and the text is made from the best ids — the pieces
+  // concatenated, "▁" to " " (CtcFinalizeDecode), then the trailing-space rule of :428-436 on the language and ITN tags, which
+  // are the arg-max of rows 0 and 3 (:413-420).  LastSearchIds() holds the best ids; with SetCtcTimestamps on they are aligned.
   // "" for an utterance without one full fbank window (:584-587) and for every item when the device call fails.
   std::vector<std::string> Forward(float** din, int* len, bool input_finished, std::string svs_lang = "auto", bool svs_itn = false,
                                    void* decoder_handle = nullptr, int batch_in = 1)
@@ -81,10 +86,17 @@ class SenseVoiceSmallHip : public ParaformerHipBase, public OnlineModelOwner
   const std::vector<std::vector<int>>& LastTokenIds() const;
   const std::vector<std::vector<int>>& LastTokenFrames() const;
   const std::vector<std::vector<float>>& LastTokenConfidence() const;
+  // per utterance the best token sequence of the device search of the calling thread's last Forward (text tokens only, no tags);
+  // empty lists when that Forward ran no device search
+  const std::vector<std::vector<int>>& LastSearchIds() const;
+  // AlignTokens on LastSearchIds(): what Forward does for a CtcPrefixDecoderHip call when the switch is on
+  bool AlignSearchTokens();
+  HipVocab* GetHipVocab() const { return vocab; }
   // Token time spans by CTC forced alignment (pfhip_svs_align; an extension: the reference's SenseVoiceSmall returns no stamps).
   // Off (the default), Forward calls exactly what it always called.  On, a Forward WITHOUT a decoder handle (the text is the greedy
-  // text) aligns the kept ids minus the four leading tags — the tokens of the text — right after the forward; with a decoder handle
-  // nothing is aligned, as the search returns a string and no ids.  ms rule (the project's own): speech row t = row - 4 covers
+  // text) aligns the kept ids minus the four leading tags — the tokens of the text — right after the forward; with a
+  // CtcPrefixDecoderHip the best ids of the device search are aligned; with any other decoder handle nothing is aligned, as that
+  // search returns a string and no ids.  ms rule (the project's own): speech row t = row - 4 covers
   // [t F, (t + 1) F) with F = pfhip_lfr_frame_ms (60 ms), a token's span is [begin_t F, end_t F]; a caller that cut the audio into VAD
   // segments adds the segment's offset, as for the CIF stamps.  Not virtual, like every method added here.
   void SetCtcTimestamps(bool on) { ctc_stamps_ = on; }

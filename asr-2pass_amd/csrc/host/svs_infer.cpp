@@ -10,6 +10,13 @@
 //                          <begin_ms end_ms>..." per utterance, --decoder adds "utt <i> stamps <count>" (0: a search returns no ids),
 //                          --handle-api adds "handle stamp [<FunASRGetStamp>]"; --ctc-stamps --with-decoder --handle-api ... also
 //                          passes a decoder handle to FunOfflineInferBuffer (the stamp stays empty).  Without the flag nothing differs.
+//   svs_infer --beam <am_model> <tokens.json|-> <svs_lang> <svs_itn 0|1> <glob_beam> <lat_beam> [--hotword <text> <score>]... <pcm_s16_file>...
+//                          the packed call with a CtcPrefixDecoderHip as decoder_handle (the device search): "hotwords loaded <n>",
+//                          per utterance "utt <i> search ids : ..." and "utt <i> text [<text>]" (with --ctc-stamps also "utt <i>
+//                          stamps : ..."), then the same after UnloadHwsRes as "unloaded utt <i> search ids : ..."
+//   svs_infer --beam-handle-api <model_dir> <svs_lang> <svs_itn 0|1> <glob_beam> <lat_beam> [--hotword <text> <score>]... <pcm_s16_file>
+//                          FunOfflineInit -> FunASRCtcDecoderInit -> FunCtcDecoderLoadHwsRes -> FunOfflineInferBuffer with that handle
+//                          -> FunCtcDecoderUninit; prints "hotwords loaded <n>", "handle text [<text>]", with --ctc-stamps "handle stamp [..]"
 // One packed ForwardPcm16 over all files, then Forward on the floats of the first file alone.  Prints per utterance
 // "utt <i> ids : ..." / "utt <i> frames : ..." / "utt <i> text [<text>]", then "alone ids : ..." for the float call.
 #include <cstdio>
@@ -19,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "ctc_prefix_decoder_hip.h"
 #include "funasrruntime_hip.h"
 #include "sensevoice_hip.h"
 
@@ -78,6 +86,74 @@ static int decoder_mode(int argc, char** argv) {
   return 0;
 }
 
+// the --hotword <text> <score> pairs from argv[at] on; returns the index behind them
+static int read_hotwords(int argc, char** argv, int at, std::unordered_map<std::string, int>& hws) {
+  while (at + 2 < argc && std::string(argv[at]) == "--hotword") { hws[argv[at + 1]] = std::atoi(argv[at + 2]); at += 3; }
+  return at;
+}
+
+static int beam_mode(int argc, char** argv) {
+  if (argc < 9) return 2;
+  const std::string tokens = std::string(argv[3]) == "-" ? "" : argv[3], lang = argv[4];
+  const bool itn = std::atoi(argv[5]) != 0;
+  std::unordered_map<std::string, int> hws;
+  const int first = read_hotwords(argc, argv, 8, hws);
+  const std::vector<std::vector<int16_t>> pcm = read_pcm(argc, argv, first);
+  funasr::SenseVoiceSmallHip model;
+  model.InitAsr(argv[2], dir_file(argv[2], "am.mvn"), dir_file(argv[2], "config.yaml"), tokens, 1);
+  model.SetCtcTimestamps(g_ctc_stamps);
+  funasr::CtcPrefixDecoderHip dec(model.GetHipVocab(), (float)std::atof(argv[6]), (float)std::atof(argv[7]));
+  std::printf("hotwords loaded %d\n", dec.LoadHwsRes(3, hws));
+  std::vector<const int16_t*> ptr;
+  std::vector<int> len;
+  for (const auto& p : pcm) { ptr.push_back(p.data()); len.push_back((int)p.size()); }
+  for (int pass = 0; pass < 2; ++pass) {
+    const char* tag = pass ? "unloaded " : "";
+    const std::vector<std::string> text = model.ForwardPcm16(ptr.data(), len.data(), true, lang, itn, &dec, (int)pcm.size());
+    for (size_t i = 0; i < text.size(); ++i) {
+      std::printf("%sutt %zu search ids :", tag, i);
+      for (int id : model.LastSearchIds()[i]) std::printf(" %d", id);
+      std::printf("\n%sutt %zu greedy ids :", tag, i);
+      for (int id : model.LastTokenIds()[i]) std::printf(" %d", id);
+      std::printf("\n%sutt %zu text [%s]\n", tag, i, text[i].c_str());
+      if (g_ctc_stamps) {
+        std::printf("%sutt %zu stamps :", tag, i);
+        if (i < model.LastTokenStampsMs().size()) for (float ms : model.LastTokenStampsMs()[i]) std::printf(" %d", (int)ms);
+        std::printf("\n");
+      }
+    }
+    dec.UnloadHwsRes();
+  }
+  return 0;
+}
+
+static int beam_handle_api(int argc, char** argv) {
+  if (argc < 8) return 2;
+  std::map<std::string, std::string> paths;
+  paths[MODEL_DIR] = argv[2];
+  std::unordered_map<std::string, int> hws;
+  const int first = read_hotwords(argc, argv, 7, hws);
+  if (first >= argc) return 2;
+  std::ifstream f(argv[first], std::ios::binary);
+  const std::vector<char> buf((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  FUNASR_HANDLE h = FunOfflineInit(paths, 1, false, 1);
+  if (g_ctc_stamps) FunOfflineSetCtcStamps(h, 1);
+  FUNASR_DEC_HANDLE dec = FunASRCtcDecoderInit(h, (float)std::atof(argv[5]), (float)std::atof(argv[6]));
+  if (!dec) { std::fprintf(stderr, "no decoder for this handle\n"); return 1; }
+  std::printf("hotwords loaded %d\n", FunCtcDecoderLoadHwsRes(dec, 3, hws));
+  const std::vector<std::vector<float>> no_hw;
+  FUNASR_RESULT r = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, 16000, "pcm", true, 800, 60000, dec, argv[3],
+                                          std::atoi(argv[4]) != 0);
+  if (!r) { std::fprintf(stderr, "inference failed\n"); return 1; }
+  std::printf("handle text [%s]\n", FunASRGetResult(r, 0));
+  if (g_ctc_stamps) std::printf("handle stamp [%s]\n", FunASRGetStamp(r));
+  FunASRFreeResult(r);
+  FunCtcDecoderUnloadHwsRes(dec);
+  FunCtcDecoderUninit(dec);
+  FunOfflineUninit(h);
+  return 0;
+}
+
 static int handle_api(int argc, char** argv) {
   if (argc < 6) return 2;
   std::map<std::string, std::string> paths;
@@ -111,6 +187,8 @@ int main(int argc, char** argv) {
     for (int i = 1; i + 1 < argc; ++i) argv[i] = argv[i + 1];
     --argc;
   }
+  if (argc > 1 && std::string(argv[1]) == "--beam") return beam_mode(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "--beam-handle-api") return beam_handle_api(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "--handle-api") return handle_api(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "--decoder") return decoder_mode(argc, argv);
   if (argc < 6) {

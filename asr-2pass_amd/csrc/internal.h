@@ -283,6 +283,14 @@ struct pfhip_model {
   int svs_span_mt = 0;
   size_t svs_span_word = 0;
   long long debug_span_cap = 0;
+  // pfhip_svs_forward_beam: the beams of the forward being run (svs_beam_fb == 0: no search; a range-guard re-run reads them again),
+  // its graph (the caller's, alive for the call), and of the last head: the k best columns of every row [M][svs_topk_k] (kept for
+  // pfhip_get_tensor "ctc_topk_*"), the token slots per hypothesis and the first word of the search's results in counts / h_counts
+  // (n_hyp [B] | n_tokens [B][nbest] | ids [B][nbest][svs_beam_mt] | score, ctc_score, ctx_score [B][nbest])
+  int svs_beam_fb = 0, svs_beam_sb = 0, svs_beam_nbest = 0, svs_topk_k = 0, svs_beam_mt = 0;
+  const pfhip_ctx_graph* svs_beam_graph = nullptr;
+  size_t svs_beam_word = 0;
+  Buf svs_topk_ids, svs_topk_logp, svs_beam_ws;
   int *m_feat_off = nullptr, *m_prompt = nullptr, *m_speech_len = nullptr;
   // device views into meta / dmeta
   int *m_frame_off = nullptr, *m_nframes = nullptr, *m_row_off = nullptr, *m_len = nullptr,

@@ -340,6 +340,39 @@ int ctc_align_max_tokens();
 bool launch_ctc_align(const float* E, const long long* e_off, size_t e_floats, const int* len, const int* n_lab, const int32_t* labels,
                       const int* lab_off, int B, int max_tokens, int32_t* tok_begin, int32_t* tok_end, float* tok_logp, float* score,
                       void* workspace, size_t workspace_bytes, hipStream_t s);
+// The fused CTC head with the k best columns of every row (ctc_head.hip; 1 <= k <= kCtcTopkMax, V >= k): ids / logp_best / lse are
+// launch_ctc_head's bit for bit (the same tile arithmetic; the greedy tile kernel is a separate instantiation that does not change);
+// topk_ids / topk_logp [M][k], larger logit first, equal logits smaller column first, value = (logit - row maximum) - log(sum): logit - lse, and logp_best at rank 0.
+// workspace: ctc_head_topk_workspace_bytes(M, V, k) bytes — per row and tile k (value, column) pairs on top of the greedy triple.
+constexpr int kCtcTopkMax = 16;
+size_t ctc_head_topk_workspace_bytes(int M, int V, int k);
+bool launch_ctc_head_topk(const float* X, int ldx, const float* W, int ldw, const float* bias, float w_scale, int M, int V, int K, int k,
+                          int32_t* ids, float* logp_best, float* lse, int32_t* topk_ids, float* topk_logp, void* workspace,
+                          size_t workspace_bytes, hipStream_t s, int* range_flag = nullptr);
+// The k best columns of every row of a log-prob matrix [rows][V] the unfused head formed (the exact re-run of the range guard, a caller
+// who wants full rows): topk_ids / topk_logp [rows][k], larger value first, equal values lower column first; 1 <= k <= kCtcTopkMax, V >= k.
+bool launch_row_topk(const float* logp, int ld, int rows, int V, int k, int32_t* topk_ids, float* topk_logp, hipStream_t s);
+// ---- CTC prefix beam search with hotwords (ctc_beam.hip) ------------------------------------------------------------------------
+// The context graph on the device (ctx_graph.h in CSR form; n_states == 0: no graph).  Indices are the host builder's, validated there.
+struct CtxGraphDev {
+  const int32_t* arc_begin = nullptr;            // [n_states + 1]
+  const float* escape = nullptr;                 // [n_states]
+  const int32_t* arc_label = nullptr;            // [n_arcs], sorted inside a state
+  const int32_t* arc_next = nullptr;
+  const float* arc_weight = nullptr;
+  int n_states = 0, n_arcs = 0;
+};
+// One workgroup per utterance walks rows [row_off[b], + len[b]) (device arrays) of topk_ids / topk_logp [rows][k] in order
+// (include/pfhip_ops.h states the recurrence and the tie rule).  1 <= first_beam <= k <= kBeamMax, 1 <= nbest <= second_beam <=
+// kBeamMax.  Out, per utterance: n_hyp [B]; ids [B][nbest][max_tokens]; n_tokens / score / ctc_score / ctx_score [B][nbest].
+// workspace: ctc_prefix_beam_workspace_bytes(rows, B, second_beam) bytes of trie nodes (the utterances' row ranges must not overlap:
+// an utterance's nodes live at its rows' positions).  false: nothing launched.
+constexpr int kBeamMax = 16;
+size_t ctc_prefix_beam_workspace_bytes(long long rows, int B, int second_beam);
+bool launch_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len, int B,
+                            int V, int blank, int first_beam, int second_beam, const CtxGraphDev& graph, int nbest, int max_tokens,
+                            int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score, float* ctx_score,
+                            void* workspace, size_t workspace_bytes, hipStream_t s);
 // The same head with the k best columns of every row (topk.hip; 1 <= k <= kTopkMax <= V): topk_ids / topk_logp [ML][k], larger logit
 // first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry of its column bit for bit.  The
 // log-sum-exp is formed with logp null as well.  false (nothing launched) when the arguments are outside that.

@@ -108,8 +108,11 @@ pfhip_model* pool_submit(pfhip_model* head, BatchReq& me, void (*run)(pfhip_mode
 struct SvsMerge { const char* span_want = nullptr; float* const* logp_rows = nullptr; uint64_t serial = 0; long long unfused_rows = 0; };
 long long svs_last_unfused_rows();      // of the forward that served the calling thread's last pfhip_svs_forward
 int svs_last_forward_calls();           // the callers that forward served (1: a lone or direct call)
+// pfhip_svs_forward_beam: the search's options and the caller's buffers (both set, or no search)
+struct SvsBeam { const pfhip_svs_beam_opts* opts = nullptr; pfhip_svs_beam_out* out = nullptr; };
 pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
-                                const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans = nullptr, SvsMerge* mg = nullptr);
+                                const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans = nullptr, SvsMerge* mg = nullptr,
+                                const SvsBeam* beam = nullptr);
 
 // ---- pfhip.cpp: the execution slots ----
 void rebuild_slots_locked(pfhip_model* head);

@@ -1,6 +1,7 @@
 // Operator-level C ABI (include/pfhip_ops.h): thin wrappers over the kernel launchers.
 #include "../../include/pfhip_ops.h"
 
+#include "ctx_graph.h"
 #include "internal.h"      // build_frontend_tables, DevMem; brings kernels.h
 
 #include <algorithm>
@@ -390,6 +391,62 @@ int pfhip_op_ctc_emissions(const float* X, int ldx, const float* W, int ldw, con
 int pfhip_op_ctc_greedy_plan(const int32_t* token_num, const int* speech_len, int B, int maxT, long long cap_floats, int* n_lab, int* lab_off,
                              long long* e_off, long long* total, void* stream) {
   if (!pfhip::launch_ctc_greedy_plan(token_num, speech_len, B, maxT, cap_floats, n_lab, lab_off, e_off, total, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+size_t pfhip_op_ctc_head_topk_workspace_bytes(int M, int V, int k) {
+  return M > 0 && V > 0 && k >= 1 && k <= pfhip::kCtcTopkMax ? pfhip::ctc_head_topk_workspace_bytes(M, V, k) : 0;
+}
+int pfhip_op_ctc_head_topk(const float* X, int ldx, const float* W, int ldw, const float* bias, float w_scale, int M, int V, int K, int k,
+                           int32_t* ids, float* logp_best, float* lse, int32_t* topk_ids, float* topk_logp, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  // the launcher checks k, V >= k, shapes, strides, buffers and the workspace size before it launches anything
+  if (!pfhip::launch_ctc_head_topk(X, ldx, W, ldw, bias, w_scale, M, V, K, k, ids, logp_best, lse, topk_ids, topk_logp, workspace,
+                                   workspace_bytes, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+// the graph's packed image goes in front of the trie nodes, 16-byte aligned
+static size_t beam_graph_bytes(const pfhip_ctx_graph* g) { return g ? (g->packed.size() * 4 + 15) / 16 * 16 : 0; }
+size_t pfhip_op_ctc_prefix_beam_workspace_bytes(long long rows, int B, int second_beam, const pfhip_ctx_graph* graph) {
+  const size_t nodes = pfhip::ctc_prefix_beam_workspace_bytes(rows, B, second_beam);
+  return nodes ? nodes + beam_graph_bytes(graph) : 0;
+}
+int pfhip_op_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len, int B,
+                             int V, int blank, int first_beam, int second_beam, const pfhip_ctx_graph* graph, int nbest, int max_tokens,
+                             int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score, float* ctx_score,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  const size_t gbytes = beam_graph_bytes(graph);
+  if ((graph && graph->vocab != V) || !workspace || workspace_bytes < gbytes) return (int)hipErrorInvalidValue;
+  pfhip::CtxGraphDev dev;
+  if (graph) {
+    const int S_ = graph->n_states(), A = graph->n_arcs();
+    const int32_t* w = static_cast<const int32_t*>(workspace);
+    dev.n_states = S_; dev.n_arcs = A;
+    dev.arc_begin = w;
+    dev.escape = reinterpret_cast<const float*>(w + S_ + 1);
+    dev.arc_label = w + 2 * S_ + 1;
+    dev.arc_next = w + 2 * S_ + 1 + A;
+    dev.arc_weight = reinterpret_cast<const float*>(w + 2 * S_ + 1 + 2 * A);
+  }
+  // nothing is copied for a call the launcher refuses: its checks first, on a launcher call that launches nothing (B = 0)
+  if (!pfhip::launch_ctc_prefix_beam(topk_ids, topk_logp, k, rows, row_off, len, 0, V, blank, first_beam, second_beam, dev, nbest, max_tokens,
+                                     n_hyp, ids, n_tokens, score, ctc_score, ctx_score, nullptr, 0, S(stream)))
+    return (int)hipErrorInvalidValue;
+  if (B < 0 || B > 65535 || workspace_bytes - gbytes < pfhip::ctc_prefix_beam_workspace_bytes(rows, B, second_beam))
+    return (int)hipErrorInvalidValue;
+  // ... and the buffers the launcher would refuse at B > 0, before the graph is copied
+  if (B > 0 && (!row_off || !len || !n_hyp || !n_tokens || !score || !ctc_score || !ctx_score || (max_tokens > 0 && !ids) ||
+                (rows > 0 && (!topk_ids || !topk_logp))))
+    return (int)hipErrorInvalidValue;
+  if (graph && B > 0) {
+    // the graph's memory is the handle's and pageable: the copy has left it when the call returns
+    const hipError_t e = hipMemcpyAsync(workspace, graph->packed.data(), graph->packed.size() * 4, hipMemcpyHostToDevice, S(stream));
+    if (e != hipSuccess) return (int)e;
+  }
+  if (!pfhip::launch_ctc_prefix_beam(topk_ids, topk_logp, k, rows, row_off, len, B, V, blank, first_beam, second_beam, dev, nbest, max_tokens,
+                                     n_hyp, ids, n_tokens, score, ctc_score, ctx_score, static_cast<char*>(workspace) + gbytes,
+                                     workspace_bytes - gbytes, S(stream)))
     return (int)hipErrorInvalidValue;
   return done();
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "offline.h"
+#include "ctx_graph.h"
 
 #define g_err (pfhip_impl::last_error())
 
@@ -181,7 +182,8 @@ int svs_last_forward_calls() { return tl_forward_calls; }
 
 // one packed forward on slot m, its range-guard re-run included, and the results into out
 pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
-                                       const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans, SvsMerge* mg) {
+                                       const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans, SvsMerge* mg,
+                                       const SvsBeam* beam) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
@@ -212,6 +214,11 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
   m->svs_logp_rows.clear();
   if (mg && mg->logp_rows) m->svs_logp_rows.assign(mg->logp_rows, mg->logp_rows + batch);
   m->svs_span_mt = 0;
+  // the search behind the head (heads.cpp); a range-guard re-run reads the same fields, so everything then belongs to the re-run
+  m->svs_beam_fb = beam ? beam->opts->first_beam : 0;
+  m->svs_beam_sb = beam ? beam->opts->second_beam : 0;
+  m->svs_beam_nbest = beam ? beam->opts->nbest : 0;
+  m->svs_beam_graph = beam ? beam->opts->graph : nullptr;
   st = enqueue_locked(m, PcmView{m->pcm.p, pcm.s16}, off.data(), n_samples, batch, s, false);
   if (!st && m->M > 0 && m->range_hit && !m->weights->always_exact) {      // the guard of the fp16 two-plane domain: redone once, exact
     ++m->range_fallbacks;
@@ -220,6 +227,8 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
     m->exact_rerun = false;
   }
   m->svs_logp_host = nullptr;
+  m->svs_beam_fb = m->svs_beam_sb = m->svs_beam_nbest = 0;
+  m->svs_beam_graph = nullptr;
   m->svs_span_want.clear();
   m->svs_logp_rows.clear();
   (mg ? mg->unfused_rows : tl_unfused_rows) = st || m->M == 0 ? 0 : m->svs_unfused_rows;
@@ -234,7 +243,32 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
   }
   if (m->M == 0) {                                 // no rows at all: what pfhip_svs_align answers for no tokens against no rows
     for (int b = 0; spans && spans->score && b < batch; ++b) spans->score[b] = 0.f;
+    for (int b = 0; beam && b < batch; ++b) beam->out->n_hyp[b] = 0;      // CtcSearch returns "" without searching
     return PFHIP_OK;
+  }
+  if (beam) {                                      // they came in the forward's one copy, behind the spans' words
+    pfhip_svs_beam_out* bo = beam->out;
+    const int nb = beam->opts->nbest, mt = m->svs_beam_mt;
+    const size_t bn = (size_t)batch * nb;
+    const int32_t *h_nhyp = m->h_counts.i() + m->svs_beam_word, *h_ntok = h_nhyp + batch, *h_ids = h_ntok + bn;
+    const float *h_score = reinterpret_cast<const float*>(h_ids + bn * mt), *h_ctc = h_score + bn, *h_ctx = h_ctc + bn;
+    int longest = 0;
+    for (int b = 0; b < batch; ++b) {
+      bo->n_hyp[b] = h_nhyp[b];
+      for (int j = 0; j < nb; ++j) {
+        const size_t o = (size_t)b * nb + j;
+        bo->n_tokens[o] = h_ntok[o];               // the true length: what max_tokens must hold where the call ends in PFHIP_ERR_CAPACITY
+        if (bo->score) bo->score[o] = h_score[o];
+        if (bo->ctc_score) bo->ctc_score[o] = h_ctc[o];
+        if (bo->ctx_score) bo->ctx_score[o] = h_ctx[o];
+        if (j < h_nhyp[b]) longest = std::max(longest, h_ntok[o]);
+      }
+    }
+    if (bo->max_tokens < longest) return fail(PFHIP_ERR_CAPACITY, "beam: max_tokens smaller than the longest hypothesis (n_tokens holds the lengths)");
+    for (size_t o = 0; o < bn; ++o) {
+      const int n = std::min(std::max(h_ntok[o], 0), mt);
+      std::memcpy(bo->ids + o * bo->max_tokens, h_ids + o * mt, (size_t)n * 4);
+    }
   }
   if ((out->ids || out->tok_frame || out->tok_logp) && out->max_tokens < m->maxL)
     return fail(PFHIP_ERR_CAPACITY, "max_tokens smaller than the longest token sequence");
@@ -312,6 +346,42 @@ pfhip_status pfhip_svs_forward_spans(pfhip_model* m, const float* const* pcm, co
 pfhip_status pfhip_svs_forward_spans_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                          const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans) {
   return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out, spans);
+}
+
+// The forward with the CTC prefix beam search (and hotwords) behind its head, in the same stream work, copy and synchronise.  The
+// merge queue of pfhip_svs_set_batching is passed by: a beam caller runs alone on a slot (merging them is not built).
+static pfhip_status svs_forward_beam(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid, const int32_t* textnorm,
+                                     pfhip_svs_out* out, const pfhip_svs_beam_opts* opts, pfhip_svs_beam_out* bo) {
+  g_err.clear();
+  if (!head || !pcm.p || !n_samples || batch <= 0 || !lid || !textnorm || !out || !opts || !bo) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!is_svs(head)) return fail(PFHIP_ERR_UNSUPPORTED, "not a SenseVoice (CTC) model: there are no CTC rows to search");
+  if (!head->replicas.empty()) return fail(PFHIP_ERR_UNSUPPORTED, "multi-device groups are not built for SenseVoice (CTC) models");
+  if (opts->first_beam < 1 || opts->first_beam > pfhip::kBeamMax || opts->second_beam < 1 || opts->second_beam > pfhip::kBeamMax)
+    return fail(PFHIP_ERR_ARG, "beam: first_beam and second_beam must lie in 1..16");
+  if (opts->nbest < 1 || opts->nbest > opts->second_beam) return fail(PFHIP_ERR_ARG, "beam: nbest must lie in 1..second_beam");
+  if (opts->first_beam > head->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "beam: first_beam larger than the vocabulary");
+  if (opts->graph && opts->graph->vocab != head->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "beam: the context graph was built for another vocabulary");
+  if (!bo->n_hyp || !bo->n_tokens || bo->max_tokens < 0 || (bo->max_tokens > 0 && !bo->ids)) return fail(PFHIP_ERR_ARG, "beam: a result buffer is missing");
+  for (int b = 0; b < batch; ++b) {
+    if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+    if (lid[b] < 0 || lid[b] > 15 || textnorm[b] < 0 || textnorm[b] > 15) return fail(PFHIP_ERR_ARG, "lid / textnorm outside 0..15");
+  }
+  pfhip_model* m = acquire_slot(head);
+  last_replica() = m;
+  tl_forward_calls = 1;
+  const SvsBeam beam{opts, bo};
+  const pfhip_status st = svs_forward_direct(m, pcm, n_samples, batch, lid, textnorm, out, nullptr, nullptr, &beam);
+  ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
+  release_slot(head, m);
+  return st;
+}
+pfhip_status pfhip_svs_forward_beam(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                    const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* opts, pfhip_svs_beam_out* beam) {
+  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, opts, beam);
+}
+pfhip_status pfhip_svs_forward_beam_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                        const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* opts, pfhip_svs_beam_out* beam) {
+  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, opts, beam);
 }
 
 // CTC forced alignment of caller-given tokens against the rows of the calling thread's last pfhip_svs_forward (ctc_align.hip): the

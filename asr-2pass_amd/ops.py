@@ -52,6 +52,15 @@ def _lib():
             lib.pfhip_op_ctc_align_workspace_bytes.argtypes = [ctypes.c_size_t]
             lib.pfhip_op_ctc_align.argtypes = [_vp, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp,
                                                ctypes.c_size_t, _vp]
+        if hasattr(lib, "pfhip_op_ctc_prefix_beam"):
+            lib.pfhip_op_ctc_head_topk_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_ctc_head_topk_workspace_bytes.argtypes = [_ci, _ci, _ci]
+            lib.pfhip_op_ctc_head_topk.argtypes = [_vp, _ci, _vp, _ci, _vp, _cf, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   ctypes.c_size_t, _vp]
+            lib.pfhip_op_ctc_prefix_beam_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_ctc_prefix_beam_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp]
+            lib.pfhip_op_ctc_prefix_beam.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci,
+                                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
         _bound = True
     return lib
 
@@ -426,6 +435,58 @@ def ctc_head(X, W, bias, w_scale="auto", M=None, V=None, want_lse=True):
     _ck(lib.pfhip_op_ctc_head(_p(X), X.stride(0), _p(W), W.stride(0), _p(bias), float(w_scale), M, V, K, _p(ids), _p(logp_best),
                               _p(lse), _p(ws), nbytes, _stream()), "ctc_head")
     return ids, logp_best, lse
+
+
+def ctc_head_topk(X, W, bias, k, w_scale="auto", M=None, V=None, workspace_bytes=None):
+    """The fused CTC head with the k best columns of every row (csrc/ctc_head.hip): (ids [M], logp_best [M], lse [M],
+    topk_ids [M, k] int32, topk_logp [M, k]); the first three are ctc_head's bit for bit.  1 <= k <= 16, V >= k."""
+    M = X.shape[0] if M is None else M
+    V = W.shape[0] if V is None else V
+    K = X.shape[1]
+    if w_scale == "auto":
+        w_scale = best_w_scale(float(W[:V].abs().max()))
+    lib = _lib()
+    dev = X.device
+    ids = torch.empty(M, dtype=torch.int32, device=dev)
+    logp_best = torch.empty(M, dtype=torch.float32, device=dev)
+    lse = torch.empty(M, dtype=torch.float32, device=dev)
+    kk = max(int(k), 1)
+    topk_ids = torch.full((M, kk), -7, dtype=torch.int32, device=dev)
+    topk_logp = torch.full((M, kk), float("nan"), dtype=torch.float32, device=dev)
+    nbytes = int(lib.pfhip_op_ctc_head_topk_workspace_bytes(M, V, int(k))) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=dev)
+    _ck(lib.pfhip_op_ctc_head_topk(_p(X), X.stride(0), _p(W), W.stride(0), _p(bias), float(w_scale), M, V, K, int(k), _p(ids),
+                                   _p(logp_best), _p(lse), _p(topk_ids), _p(topk_logp), _p(ws), nbytes, _stream()), "ctc_head_topk")
+    return ids, logp_best, lse, topk_ids, topk_logp
+
+
+def ctc_prefix_beam(topk_ids, topk_logp, row_off, length, vocab, first_beam, second_beam, nbest=None, max_tokens=None, blank=0,
+                    graph=None, workspace_bytes=None, rows=None):
+    """CTC prefix beam search with hotwords (csrc/ctc_beam.hip; include/pfhip_ops.h states the recurrence and the tie rule) over
+    topk_ids / topk_logp [rows, k]; row_off / length: int32 device tensors [B]; graph: a ContextGraph or None.  Returns
+    (n_hyp [B], ids [B, nbest, max_tokens], n_tokens [B, nbest], score, ctc_score, ctx_score [B, nbest]).  rows: the row count the
+    kernel is told (default: all of the tensors'; fewer leaves the rest as padding, and the workspace is sized for all)."""
+    lib = _lib()
+    all_rows, k = int(topk_ids.shape[0]), int(topk_ids.shape[1])
+    rows = all_rows if rows is None else min(int(rows), all_rows)
+    B = int(row_off.numel())
+    nbest = int(second_beam) if nbest is None else int(nbest)
+    max_tokens = rows if max_tokens is None else int(max_tokens)
+    dev = topk_ids.device
+    nb = max(nbest, 1)
+    n_hyp = torch.full((max(B, 1),), -7, dtype=torch.int32, device=dev)
+    ids = torch.full((max(B, 1), nb, max(max_tokens, 1)), -7, dtype=torch.int32, device=dev)
+    n_tokens = torch.full((max(B, 1), nb), -7, dtype=torch.int32, device=dev)
+    score, ctc_score, ctx_score = (torch.full((max(B, 1), nb), float("nan"), dtype=torch.float32, device=dev) for _ in range(3))
+    gh = graph.handle if graph is not None else None
+    nbytes = int(lib.pfhip_op_ctc_prefix_beam_workspace_bytes(all_rows, B, int(second_beam), gh)) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=dev)
+    if max_tokens != ids.shape[2]:                                   # max_tokens 0: the kernel gets a stride of 0 and no buffer use
+        ids = ids[:, :, :0]
+    _ck(lib.pfhip_op_ctc_prefix_beam(_p(topk_ids), _p(topk_logp), k, rows, _p(row_off), _p(length), B, int(vocab), int(blank),
+                                     int(first_beam), int(second_beam), gh, nbest, max_tokens, _p(n_hyp), _p(ids) if max_tokens else None,
+                                     _p(n_tokens), _p(score), _p(ctc_score), _p(ctx_score), _p(ws), nbytes, _stream()), "ctc_prefix_beam")
+    return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], ctc_score[:B], ctx_score[:B]
 
 
 def ctc_collapse_chunk():

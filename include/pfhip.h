@@ -715,6 +715,58 @@ pfhip_status pfhip_svs_forward_spans(pfhip_model* m, const float* const* pcm, co
 pfhip_status pfhip_svs_forward_spans_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                          const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans);
 
+/* ---- hotword context graph of the CTC prefix beam search (ctx_graph.cpp; host only, no device) ----
+ * What CtcPrefixDecoder::LoadHwsRes builds through ContextGraph::BuildContextGraph and walks with GetNextState
+ * (onnxruntime/src/context_graph.cpp:33-118), as a deterministic trie from state 0.  Hotword j is the token ids
+ * ids[sum n_ids[..j] .. + n_ids[j]) with one weight per token, tok_weight likewise packed (the reference's weight of a token is
+ * hotword score x UTF-8 length of its string, :76-77: the caller's product).  With minCum(node) = the least cumulative weight over
+ * the hotwords through a node:
+ *   - the arc into a node weighs minCum(node) - minCum(parent); the last token of a hotword leads back to state 0 and weighs the
+ *     hotword's cumulative weight - minCum(parent) (of duplicates the least);
+ *   - a token that matches no arc of an inner state scores the escape weight -minCum(state) and leads to state 0 — it is NOT tried
+ *     again from state 0 (reference behaviour); from state 0 a miss scores 0;
+ *   - a hotword that is a proper prefix of another: the node it ends on stays (the longer one goes on from it), is final, counts the
+ *     shorter word in its minCum, carries state 0's arcs as well (each heavier by the shorter word's cumulative weight - minCum; an
+ *     arc of its own with the same label wins) and keeps its escape weight, so a miss there takes the shorter word's bonus away.
+ * Arcs of a state are sorted by label.  PFHIP_ERR_ARG: an id outside 1 .. vocab - 1 (0 is the escape label), an empty word, a
+ * non-finite weight or cumulative weight, a NULL argument; pfhip_op_ctc_prefix_beam therefore only ever sees validated indices.
+ * pfhip_ctx_graph_dump (tests): *n_states / *n_arcs always; with every array given, the CSR form — arc_begin [cap_states + 1],
+ * escape [cap_states], arc_label / arc_next / arc_weight [cap_arcs] — or PFHIP_ERR_CAPACITY where a cap is too small.
+ * The reference's slip of the score index after a skipped over-long hotword (:56-61) has no counterpart: weights arrive per token. */
+typedef struct pfhip_ctx_graph pfhip_ctx_graph;
+pfhip_status pfhip_ctx_graph_create(const int32_t* ids, const int* n_ids, const float* tok_weight, int n_words, int vocab,
+                                    pfhip_ctx_graph** g);
+void pfhip_ctx_graph_destroy(pfhip_ctx_graph* g);
+int pfhip_ctx_graph_vocab(const pfhip_ctx_graph* g);
+pfhip_status pfhip_ctx_graph_dump(const pfhip_ctx_graph* g, int* n_states, int* n_arcs, int32_t* arc_begin, float* escape, int cap_states,
+                                  int32_t* arc_label, int32_t* arc_next, float* arc_weight, int cap_arcs);
+
+/* pfhip_svs_forward[_s16] with the CTC prefix beam search — and, through a context graph, hotwords — behind its head: what the
+ * reference's servers run for this model through a CtcPrefixDecoder per connection (funasrruntime.cpp:836-894,
+ * sensevoice-small.cpp:651-657, ctc-prefix-decoder.cpp:157-299).  The head runs ONCE, in its top-k form with k = first_beam
+ * (pfhip_op_ctc_head_topk: no logits matrix), the search (pfhip_op_ctc_prefix_beam, which states the recurrence and the tie rule)
+ * runs over the SPEECH rows of every utterance — the four prompt rows are no CTC rows (sensevoice-small.cpp:422) — and its results
+ * travel in the forward's one device-to-host copy, before its one synchronise.  `out` comes back as pfhip_svs_forward's bit for bit;
+ * pfhip_svs_align afterwards works against the same rows (e.g. on ids[b][0]); after a range-guard re-run everything belongs to the
+ * re-run, whose k best columns come from the unfused head's rows.
+ * opts: 1 <= first_beam, second_beam <= 16, 1 <= nbest <= second_beam, graph NULL or built for this model's vocabulary (it must
+ * stay alive for the call).  beam, caller-owned: n_hyp [batch]; ids [batch][nbest][max_tokens] (text tokens only, no tags; written
+ * up to n_tokens); n_tokens [batch][nbest] — the TRUE length; score / ctc_score / ctx_score [batch][nbest] (may be NULL).  An
+ * utterance without rows has n_hyp 0.  PFHIP_ERR_CAPACITY where max_tokens is below the longest returned hypothesis: n_hyp,
+ * n_tokens and the scores are written all the same, so n_tokens carries the length needed.  PFHIP_ERR_UNSUPPORTED: a Paraformer
+ * handle.  PFHIP_ERR_ARG: beams outside 1..16, nbest outside 1..second_beam, a graph of another vocabulary, a missing buffer.
+ * With pfhip_svs_set_batching on, the call is served alone, past the merge queue.  pfhip_get_tensor "ctc_topk_ids" (int32 words) /
+ * "ctc_topk_logp": the [M][first_beam] columns the search read, prompt rows included. */
+typedef struct pfhip_svs_beam_opts { int first_beam; int second_beam; int nbest; const pfhip_ctx_graph* graph; } pfhip_svs_beam_opts;
+typedef struct pfhip_svs_beam_out {
+  int32_t* n_hyp; int32_t* ids; int32_t* n_tokens; float* score; float* ctc_score; float* ctx_score; int max_tokens;
+} pfhip_svs_beam_out;
+pfhip_status pfhip_svs_forward_beam(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                    const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* opts, pfhip_svs_beam_out* beam);
+pfhip_status pfhip_svs_forward_beam_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                        const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* opts,
+                                        pfhip_svs_beam_out* beam);
+
 /* ---- inspection (parity tests) -----------------------------------------------------------------
  * Copies a named intermediate of the LAST forward to host: "feats" [M,560], "enc" [M,d],
  * "alphas" [M] (without the tail slot), "emb" [sum fires, d], "logp" [sum fires, vocab],

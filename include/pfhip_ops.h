@@ -203,6 +203,51 @@ int pfhip_op_ctc_align_max_tokens(void);
 int pfhip_op_ctc_align(const float* E, const long long* e_off, size_t e_floats, const int* len, const int* n_lab, const int32_t* labels,
                        const int* lab_off, int B, int max_tokens, int32_t* tok_begin, int32_t* tok_end, float* tok_logp, float* score,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* pfhip_op_ctc_head with the k best columns of every row (ctc_head.hip; what CtcPrefixDecoder::CtcSearch's first prune, TopK of
+ * onnxruntime/src/util.h:42-78, takes from a full log-softmax row — here without that row): 1 <= k <= 16, V >= k.  topk_ids /
+ * topk_logp [M][k]: larger logit first, equal logits smaller column first; a value is that column's logit minus the row's
+ * log-sum-exp.  ids, logp_best and lse are pfhip_op_ctc_head's on the same operands BIT FOR BIT (the same tile arithmetic; the
+ * greedy kernel is its own instantiation and is untouched), topk_ids[.., 0] == ids and topk_logp[.., 0] == logp_best: a value is
+ * formed as (logit - row maximum) - log(sum), which at rank 0 is logp_best's -log(sum) and never increases along a row.  Nothing of size [M][V] is written: per row and 128-column tile the
+ * epilogue leaves the tile's k best (value, column) pairs beside the greedy triple, and the merge kernel selects k of tiles x k.
+ * workspace: pfhip_op_ctc_head_topk_workspace_bytes(M, V, k).  hipErrorInvalidValue, before anything is launched, for k outside
+ * 1..16, V < k, any shape pfhip_op_ctc_head refuses, a NULL buffer (lse may be NULL) or a short workspace. */
+size_t pfhip_op_ctc_head_topk_workspace_bytes(int M, int V, int k);
+int pfhip_op_ctc_head_topk(const float* X, int ldx, const float* W, int ldw, const float* bias, float w_scale, int M, int V, int K, int k,
+                           int32_t* ids, float* logp_best, float* lse, int32_t* topk_ids, float* topk_logp, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* CTC prefix beam search with hotwords on the device (ctc_beam.hip): CtcPrefixDecoder::CtcSearch + CtcFinalizeDecode
+ * (onnxruntime/src/ctc-prefix-decoder.cpp:157-299, PrefixScore of ctc-prefix-decoder.h:64-110) over rows of k best columns.
+ * Utterance b owns rows [row_off[b], row_off[b] + len[b]) (DEVICE arrays; the ranges must not overlap) of topk_ids / topk_logp
+ * [rows][k], a row's first `first_beam` columns being its candidates (expected distinct).  1 <= first_beam <= k <= 16,
+ * 1 <= nbest <= second_beam <= 16, 0 <= blank < V.  graph: a pfhip_ctx_graph built for vocab == V, or NULL; the call copies it to
+ * the front of the workspace on `stream`.
+ *   A hypothesis is a token sequence with s (log-probability of the alignments ending in the blank), ns (of those ending in its
+ *   last token), a context score and a context state.  Start: the empty sequence with s = 0, ns = -FLT_MAX ("no path"; not -inf).
+ *   LogAdd(x, y) = the other operand where one is <= -FLT_MAX, else log(exp(x - m) + exp(y - m)) + m with m = max(x, y).
+ *   Per row, for every hypothesis h and candidate (tok, p):  blank: h unchanged receives s <- LogAdd(s, LogAdd(s_h, ns_h) + p);
+ *   tok == last token of h: h unchanged receives ns <- LogAdd(ns, ns_h + p), and h + tok receives ns <- LogAdd(ns, s_h + p);
+ *   any other tok: h + tok receives ns <- LogAdd(ns, LogAdd(s_h, ns_h) + p).  An unchanged hypothesis keeps its context; h + tok
+ *   has the state GetNextState(state_h, tok) and context_h + that arc's (or escape) weight.  total = LogAdd(s, ns) + context.  The
+ *   second_beam largest totals survive.  A sequence receives at most two terms per field and row, and two-term LogAdd is
+ *   commutative bit for bit, so the sums do not depend on the visiting order; the ORDER AMONG EQUAL TOTALS, which the reference
+ *   leaves open (nth_element over an unordered_map), is: unchanged hypotheses first, in beam order, then extensions,
+ *   hypothesis-major and candidate-minor (an extension that IS a live hypothesis counts as that unchanged hypothesis).
+ *   End: a hypothesis whose context state is not 0 receives that state's escape weight (the back-off of an unfinished match),
+ *   then the order by total, equal totals in beam order.  The Viterbi half and the boundary tags of the reference are not formed.
+ * Out per utterance: n_hyp [B] <= nbest; ids [B][nbest][max_tokens] (-1 behind the tokens); n_tokens [B][nbest] = the TRUE
+ * length, also above max_tokens (the surplus is not stored); score (total), ctc_score (LogAdd(s, ns)), ctx_score [B][nbest]
+ * (-inf / -inf / 0 behind n_hyp).  len[b] == 0 gives n_hyp 0, as CtcSearch returns "" without searching; so does an utterance
+ * whose rows leave [0, rows).  An id outside 0 .. V - 1 is CLAMPED into it; a log-probability that is NaN or below -FLT_MAX counts
+ * as -FLT_MAX.  workspace: pfhip_op_ctc_prefix_beam_workspace_bytes(rows, B, second_beam, graph) bytes of device memory (the
+ * graph, then a (parent, token) trie node per row and beam slot).  hipErrorInvalidValue, before anything is copied or launched,
+ * for anything outside the above, a graph of another vocab, a NULL buffer (ids with max_tokens 0 excepted) or a short workspace. */
+struct pfhip_ctx_graph;
+size_t pfhip_op_ctc_prefix_beam_workspace_bytes(long long rows, int B, int second_beam, const struct pfhip_ctx_graph* graph);
+int pfhip_op_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                             int B, int V, int blank, int first_beam, int second_beam, const struct pfhip_ctx_graph* graph, int nbest,
+                             int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score,
+                             float* ctx_score, void* workspace, size_t workspace_bytes, void* stream);
 /* One streaming window (M <= 32 rows): LayerNormalization (g != NULL; width D <= K) -> MatMul/Gemm (+bias, +residual Adds, Relu)
  * (+ the SAN-M FSMN memory of fsmn_v over the M rows, k = 11) in ONE launch — stream_fused.hip. */
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
