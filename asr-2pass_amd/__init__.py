@@ -68,6 +68,9 @@ ABI_SYMBOLS = [
     "pfhip_svs_forward_beam", "pfhip_svs_forward_beam_s16",
     # CTC prefix beam search: the hotword context graph (host only)
     "pfhip_ctx_graph_create", "pfhip_ctx_graph_destroy", "pfhip_ctx_graph_vocab", "pfhip_ctx_graph_dump",
+    # SenseVoiceSmall: a set of search options per utterance, beam callers in the merge queue, the graphs kept on the device
+    "pfhip_svs_forward_beam_sets", "pfhip_svs_forward_beam_sets_s16", "pfhip_svs_set_beam_merging", "pfhip_svs_set_graph_bank_bytes",
+    "pfhip_svs_graph_bank_stats",
 ]
 
 
@@ -151,6 +154,10 @@ class _SlotStats(ctypes.Structure):
 class _HwBankStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("hits", "misses", "evictions", "refused", "bytes_in_use", "bytes_capacity", "sets_resident",
                                               "forwards", "per_call_forwards", "sets_in_forwards", "max_sets_in_forward")]
+
+
+class _GraphBankStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("hits", "misses", "evictions", "refused", "bytes_in_use", "bytes_capacity", "graphs_resident")]
 
 
 class _Profile(ctypes.Structure):
@@ -302,6 +309,13 @@ def load_lib() -> ctypes.CDLL:
     if hasattr(lib, "pfhip_svs_forward_beam"):
         lib.pfhip_svs_forward_beam.argtypes = lib.pfhip_svs_forward.argtypes + [ctypes.POINTER(_SvsBeamOpts), ctypes.POINTER(_SvsBeamOut)]
         lib.pfhip_svs_forward_beam_s16.argtypes = lib.pfhip_svs_forward_beam.argtypes
+    if hasattr(lib, "pfhip_svs_forward_beam_sets"):
+        lib.pfhip_svs_forward_beam_sets.argtypes = lib.pfhip_svs_forward.argtypes + [ctypes.POINTER(_SvsBeamOpts), ci,
+                                                                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_SvsBeamOut)]
+        lib.pfhip_svs_forward_beam_sets_s16.argtypes = lib.pfhip_svs_forward_beam_sets.argtypes
+        lib.pfhip_svs_set_beam_merging.argtypes = [vp, ci]
+        lib.pfhip_svs_set_graph_bank_bytes.argtypes = [vp, ctypes.c_int64]
+        lib.pfhip_svs_graph_bank_stats.argtypes = [vp, ctypes.POINTER(_GraphBankStats)]
     if hasattr(lib, "pfhip_ctx_graph_create"):
         i32p, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
         lib.pfhip_ctx_graph_create.argtypes = [i32p, ctypes.POINTER(ci), fp, ci, ci, ctypes.POINTER(vp)]
@@ -1013,6 +1027,21 @@ class SenseVoiceHip:
         """Merge concurrent forward() callers into one packed device batch (pfhip_svs_set_batching); wait_us = 0: off."""
         _check(self._lib, self._lib.pfhip_svs_set_batching(self._h, int(wait_us), int(max_utterances)))
 
+    def set_beam_merging(self, on):
+        """With set_batching on: forward(beam=...) and forward(beam_sets=...) callers join the merge queue too
+        (pfhip_svs_set_beam_merging; off by default: every beam call is a forward of its own)."""
+        _check(self._lib, self._lib.pfhip_svs_set_beam_merging(self._h, 1 if on else 0))
+
+    def set_graph_bank_bytes(self, nbytes):
+        """The bound of the device's bank of context graphs (pfhip_svs_set_graph_bank_bytes); 0 banks nothing."""
+        _check(self._lib, self._lib.pfhip_svs_set_graph_bank_bytes(self._h, int(nbytes)))
+
+    def graph_bank_stats(self):
+        """dict(hits, misses, evictions, refused, bytes_in_use, bytes_capacity, graphs_resident) (pfhip_svs_graph_bank_stats)."""
+        st = _GraphBankStats()
+        _check(self._lib, self._lib.pfhip_svs_graph_bank_stats(self._h, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _GraphBankStats._fields_}
+
     def inflight_stats(self):
         """Per execution slot: dict(device, context, forwards, calls, utterances) (pfhip_inflight_stats)."""
         arr = (_SlotStats * 64)()
@@ -1031,8 +1060,11 @@ class SenseVoiceHip:
         return T + 4 if T > 0 else 0
 
     def forward(self, din, lang="auto", itn=True, lid=None, textnorm=None, want_logp=False, want_spans=False, max_tokens=None,
-                beam=None, nbest=None, graph=None, beam_max_tokens=None):
-        """One packed forward.  beam = (first_beam, second_beam): pfhip_svs_forward_beam — the CTC prefix beam search on the device,
+                beam=None, nbest=None, graph=None, beam_max_tokens=None, beam_sets=None):
+        """One packed forward.  beam_sets = [None | (first_beam, second_beam, nbest, graph), ...], one entry per utterance:
+        pfhip_svs_forward_beam_sets — every utterance searched with its own beams and ContextGraph (None: not searched, no
+        hypotheses), in one head launch and one search launch; the beam_* results are those of `beam`, the hypothesis stride being
+        the largest nbest among the entries.  beam = (first_beam, second_beam): pfhip_svs_forward_beam — the CTC prefix beam search on the device,
         with the hotwords of `graph` (a ContextGraph) — and the result also holds beam_n_hyp [B] and, per utterance, beam_ids (a list
         of token arrays, best first; text tokens only), beam_score / beam_ctc_score / beam_ctx_score (arrays over its hypotheses);
         nbest defaults to second_beam.  want_spans: pfhip_svs_forward_spans — the result also holds span_begin / span_end / span_logp
@@ -1067,22 +1099,43 @@ class SenseVoiceHip:
                       frame_len.ctypes.data_as(i32p), logp.ctypes.data_as(f32p) if want_logp else None, logp.size if want_logp else 0)
         args = [self._h, ptrs, ns.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), B, lid_a.ctypes.data_as(i32p), tn_a.ctypes.data_as(i32p),
                 ctypes.byref(out)]
+        if beam_sets is not None:
+            if want_spans or beam is not None:
+                raise PfhipError("forward: beam_sets goes without beam and want_spans")
+            if len(beam_sets) != B:
+                raise PfhipError("forward: beam_sets needs one entry per utterance")
+            beam = True                                # the results below are read as for `beam`
+            distinct, set_of = [], []
+            for e in beam_sets:                        # equal entries (the same graph object) share a set
+                key = None if e is None else (int(e[0]), int(e[1]), int(e[2]), e[3])
+                if key is not None and key not in distinct:
+                    distinct.append(key)
+                set_of.append(-1 if key is None else distinct.index(key))
+            sets_a = (_SvsBeamOpts * max(len(distinct), 1))(*[_SvsBeamOpts(f, s, n, g.handle if g is not None else None)
+                                                              for f, s, n, g in distinct])
+            set_of_a = np.array(set_of, np.int32)
+            nb = max([k[2] for k in distinct] + [1])
         if beam is not None:
             if want_spans:
                 raise PfhipError("forward: beam and want_spans are separate calls (align() the returned ids for spans)")
-            fbm, sbm = int(beam[0]), int(beam[1])
-            nb = sbm if nbest is None else int(nbest)
+            if beam_sets is None:
+                fbm, sbm = int(beam[0]), int(beam[1])
+                nb = sbm if nbest is None else int(nbest)
             bmt = cap if beam_max_tokens is None else int(beam_max_tokens)
             nbq = max(nb, 1)
             b_nhyp = np.full(B, -7, np.int32)
             b_ids = np.full((B, nbq, max(bmt, 1)), -1, np.int32)
             b_ntok = np.full((B, nbq), -7, np.int32)
             b_score, b_ctc, b_ctx = (np.full((B, nbq), np.nan, np.float32) for _ in range(3))
-            bopts = _SvsBeamOpts(fbm, sbm, nb, graph.handle if graph is not None else None)
             bout = _SvsBeamOut(b_nhyp.ctypes.data_as(i32p), b_ids.ctypes.data_as(i32p), b_ntok.ctypes.data_as(i32p), b_score.ctypes.data_as(f32p),
                                b_ctc.ctypes.data_as(f32p), b_ctx.ctypes.data_as(f32p), max(bmt, 1) if bmt > 0 else 0)
-            fn = self._lib.pfhip_svs_forward_beam_s16 if s16 else self._lib.pfhip_svs_forward_beam
-            args += [ctypes.byref(bopts), ctypes.byref(bout)]
+            if beam_sets is not None:
+                fn = self._lib.pfhip_svs_forward_beam_sets_s16 if s16 else self._lib.pfhip_svs_forward_beam_sets
+                args += [sets_a, max(len(distinct), 1), set_of_a.ctypes.data_as(i32p), ctypes.byref(bout)]
+            else:
+                bopts = _SvsBeamOpts(fbm, sbm, nb, graph.handle if graph is not None else None)
+                fn = self._lib.pfhip_svs_forward_beam_s16 if s16 else self._lib.pfhip_svs_forward_beam
+                args += [ctypes.byref(bopts), ctypes.byref(bout)]
             self.last_beam_n_tokens = b_ntok          # also where the call ends in PFHIP_ERR_CAPACITY: the lengths needed
         elif want_spans:
             sp_begin = np.full((B, cap), -7, np.int32)
@@ -1095,7 +1148,12 @@ class SenseVoiceHip:
             args.append(ctypes.byref(sp))
         else:
             fn = self._lib.pfhip_svs_forward_s16 if s16 else self._lib.pfhip_svs_forward
-        _check(self._lib, fn(*args))
+        try:
+            _check(self._lib, fn(*args))
+        except PfhipError as e:
+            if beam is not None:
+                e.beam_n_tokens = b_ntok              # this call's own (last_beam_n_tokens is the handle's last: shared among threads)
+            raise
         assert frame_len.tolist() == rows, (frame_len.tolist(), rows)
         offs = np.concatenate([[0], np.cumsum(frame_len)]).astype(np.int64)
         cut = lambda a: [a[offs[b]:offs[b + 1]] for b in range(B)]
@@ -1142,7 +1200,7 @@ class SenseVoiceHip:
 
     def debug_poke(self, what, value=0):
         """pfhip_debug_poke: "ctc_unfused", "ctc_unfused_forwards", "ctc_head_chunks", "range_flag", "range_fallbacks", "plane_forwards",
-        "svs_span_cap", "svs_unfused_rows", "svs_forward_calls"."""
+        "svs_span_cap", "svs_unfused_rows", "svs_forward_calls", "svs_topk_k"."""
         return int(self._lib.pfhip_debug_poke(self._h, what.encode(), int(value)))
 
 

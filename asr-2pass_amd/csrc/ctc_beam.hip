@@ -68,13 +68,19 @@ struct BeamState {                               // one buffer of the beam
   int state[kBM], node[kBM], par[kBM], tok[kBM], len[kBM];
 };
 
+// kPerUtt: workgroup b takes first_beam, second_beam, nbest and its graph from utt[b] (launch_ctc_prefix_beam_multi); the arguments
+// fb / sb / nbest are then the launch's strides only: sb the node stride of a row, nbest the hypothesis slots of an utterance (fb is
+// not read).  Everything read from utt[b] is uniform in the workgroup, so every barrier below still sits in uniform control flow.
+template <bool kPerUtt>
 __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __restrict__ topk_ids, const float* __restrict__ topk_logp, int k,
                                                               long long rows, const int* __restrict__ row_off, const int* __restrict__ len,
                                                               int V, int blank, int fb, int sb, CtxGraphDev g, int nbest, int max_tokens,
                                                               int32_t* __restrict__ n_hyp, int32_t* __restrict__ out_ids,
                                                               int32_t* __restrict__ n_tokens, float* __restrict__ score,
                                                               float* __restrict__ ctc_score, float* __restrict__ ctx_score,
-                                                              int32_t* __restrict__ node_parent, int32_t* __restrict__ node_token) {
+                                                              int32_t* __restrict__ node_parent, int32_t* __restrict__ node_token,
+                                                              const BeamUtt* __restrict__ utt, const CtxGraphDev* __restrict__ graphs,
+                                                              int n_graphs) {
   __shared__ BeamState beam[2];
   __shared__ int fr_id[2][kBM];
   __shared__ float fr_lp[2][kBM];
@@ -92,14 +98,28 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
   }
   for (size_t j = tid; j < (size_t)nbest * max_tokens; j += kBT) out_ids[o_h * max_tokens + j] = -1;
   // the rows must lie inside the arrays (row_off and len are device data the launcher could not see); T * sb + 1 stays below 2^31
-  const bool refused = T < 0 || r0 < 0 || r0 + T > rows;
+  bool refused = T < 0 || r0 < 0 || r0 + T > rows;
+  const int node_stride = sb;
+  if constexpr (kPerUtt) {
+    // the utterance's own beams: first_beam 0 is "no search"; one outside the launch's strides (k, sb, nbest) or naming no graph of
+    // the table has no hypothesis either.  Slots nbest[b] .. of the utterance keep the fill above.
+    const BeamUtt u = utt[b];
+    refused = refused || u.first_beam < 1 || u.first_beam > min(k, kBM) || u.second_beam < 1 || u.second_beam > min(sb, kBM) || u.nbest < 1 ||
+              u.nbest > min(u.second_beam, nbest) || u.graph < -1 || u.graph >= n_graphs;
+    if (!refused) {
+      fb = u.first_beam; sb = u.second_beam; nbest = u.nbest;
+      g = CtxGraphDev();
+      if (u.graph >= 0) g = graphs[u.graph];
+    }
+  }
   if (refused || T == 0) {                                           // uniform
     if (tid == 0) n_hyp[b] = 0;
     return;
   }
-  // utterance b's nodes 1 .. T * sb are stored at [r0 * sb, (r0 + T) * sb): node n at n - 1 (the root, node 0, is never read)
-  int32_t* const npar = node_parent + (size_t)r0 * sb;
-  int32_t* const ntok = node_token + (size_t)r0 * sb;
+  // utterance b's nodes 1 .. T * sb are stored from r0 * node_stride on, inside [r0, r0 + T) * node_stride (sb <= node_stride): node n
+  // at n - 1 (the root, node 0, is never read)
+  int32_t* const npar = node_parent + (size_t)r0 * node_stride;
+  int32_t* const ntok = node_token + (size_t)r0 * node_stride;
   const int32_t* const rid = topk_ids + (size_t)r0 * k;
   const float* const rlp = topk_logp + (size_t)r0 * k;
 
@@ -278,8 +298,44 @@ bool launch_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, int
     return false;
   int32_t* const node_parent = static_cast<int32_t*>(workspace);
   int32_t* const node_token = node_parent + std::max<size_t>((size_t)rows * second_beam, 1);
-  hipLaunchKernelGGL(ctc_prefix_beam_kernel, dim3(B), dim3(kBT), 0, s, topk_ids, topk_logp, k, rows, row_off, len, V, blank, first_beam,
-                     second_beam, graph, nbest, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, node_parent, node_token);
+  hipLaunchKernelGGL(ctc_prefix_beam_kernel<false>, dim3(B), dim3(kBT), 0, s, topk_ids, topk_logp, k, rows, row_off, len, V, blank, first_beam,
+                     second_beam, graph, nbest, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, node_parent, node_token,
+                     static_cast<const BeamUtt*>(nullptr), static_cast<const CtxGraphDev*>(nullptr), 0);
+  return true;
+}
+
+bool ctc_prefix_beam_multi_check(const BeamUtt* utt, int B, int k, int n_graphs, int* sb_max, int* nbest_max) {
+  if (B < 0 || B > 65535 || k < 1 || k > kBeamMax || n_graphs < 0 || (B > 0 && !utt)) return false;
+  int sm = 1, nm = 1;
+  for (int b = 0; b < B; ++b) {
+    const BeamUtt& u = utt[b];
+    if (u.first_beam < 0 || u.first_beam > k || u.second_beam < 0 || u.second_beam > kBeamMax || u.graph < -1 || u.graph >= n_graphs) return false;
+    if (u.first_beam == 0) continue;                                 // no search: second_beam and nbest are not read
+    if (u.nbest < 1 || u.nbest > u.second_beam) return false;
+    sm = std::max(sm, u.second_beam); nm = std::max(nm, u.nbest);
+  }
+  if (sb_max) *sb_max = sm;
+  if (nbest_max) *nbest_max = nm;
+  return true;
+}
+
+bool launch_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                                  int B, int V, int blank, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int sb_max,
+                                  int nbest_max, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
+                                  float* ctc_score, float* ctx_score, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  if (B < 0 || B > 65535 || rows < 0 || k < 1 || k > kBeamMax || sb_max < 1 || sb_max > kBeamMax || nbest_max < 1 || nbest_max > sb_max ||
+      n_graphs < 0 || V < 1 || blank < 0 || blank >= V || max_tokens < 0 || rows * sb_max + 1 > 0x7fffffffLL)
+    return false;
+  if (B == 0) return true;
+  if (!utt || (n_graphs > 0 && !graphs) || !row_off || !len || !n_hyp || !n_tokens || !score || !ctc_score || !ctx_score ||
+      (max_tokens > 0 && !ids) || (rows > 0 && (!topk_ids || !topk_logp)) || !workspace ||
+      workspace_bytes < ctc_prefix_beam_workspace_bytes(rows, B, sb_max))
+    return false;
+  int32_t* const node_parent = static_cast<int32_t*>(workspace);
+  int32_t* const node_token = node_parent + std::max<size_t>((size_t)rows * sb_max, 1);
+  hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(B), dim3(kBT), 0, s, topk_ids, topk_logp, k, rows, row_off, len, V, blank, 0, sb_max,
+                     CtxGraphDev(), nbest_max, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, node_parent, node_token, utt,
+                     graphs, n_graphs);
   return true;
 }
 

@@ -79,10 +79,17 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   if (!m || !name || !dst) return fail(PFHIP_ERR_ARG, "bad argument");
   // a group: the replica that served this thread's last offline forward holds the state being asked for
   if (!m->replicas.empty() && last_replica() && (last_replica() == m || last_replica()->group_head == m)) m = last_replica();
+  const std::string nm(name);
+  // the k best columns after a MERGED forward are the calling thread's own utterances' rows: its note says which context served it
+  // and which of that forward's utterances are its own (the rule of pfhip_svs_align); without a valid note: this handle's last forward
+  SvsNoteView own;
+  if (is_svs(m) && (nm == "ctc_topk_ids" || nm == "ctc_topk_logp")) {
+    own = svs_thread_note(m);
+    if (own.ctx) m = own.ctx;
+  }
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->prof_stream ? m->prof_stream : m->own_stream;
-  const std::string nm(name);
   const void* src = nullptr;
   size_t n = 0;
   const int d = m->weights->cfg.d_model;
@@ -90,8 +97,15 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   else if (nm == "enc") { src = m->weights->cfg.svs ? m->x.p : m->enc.p; n = (size_t)m->M * d; }      // SenseVoice: the rows after tp.norm
   else if (nm == "lse" && m->weights->cfg.svs) { src = m->svs_lse.p; n = (size_t)m->M; }             // the rows' log-sum-exp either CTC head kept
   // the k best columns of every row of the last pfhip_svs_forward_beam [M][first_beam]; the ids are int32 words in the float buffer
-  else if (nm == "ctc_topk_ids" && m->weights->cfg.svs && m->svs_topk_k) { src = m->svs_topk_ids.p; n = (size_t)m->M * m->svs_topk_k; }
-  else if (nm == "ctc_topk_logp" && m->weights->cfg.svs && m->svs_topk_k) { src = m->svs_topk_logp.p; n = (size_t)m->M * m->svs_topk_k; }
+  else if ((nm == "ctc_topk_ids" || nm == "ctc_topk_logp") && m->weights->cfg.svs && m->svs_topk_k) {
+    size_t r0 = 0, rows = (size_t)m->M;
+    if (own.ctx == m && m->svs_fwd_ok && m->svs_serial == own.serial && own.u0 >= 0 && own.batch > 0 && own.u0 + own.batch <= m->B) {
+      r0 = (size_t)m->row_off[own.u0];
+      rows = (size_t)m->row_off[own.u0 + own.batch - 1] + (size_t)m->T[own.u0 + own.batch - 1] - r0;
+    }
+    src = static_cast<const char*>(nm == "ctc_topk_ids" ? m->svs_topk_ids.p : m->svs_topk_logp.p) + r0 * m->svs_topk_k * 4;
+    n = rows * m->svs_topk_k;
+  }
   else if (m->weights->cfg.svs) return fail(PFHIP_ERR_ARG, "a SenseVoice model has the tensors feats, enc and lse, not " + nm);
   else if (nm == "alphas") { src = m->alphas.p; n = (size_t)m->M; }
   else if (nm == "emb") { src = m->emb.p; n = (size_t)m->ML * d; }
@@ -173,6 +187,7 @@ pfhip_status pfhip_debug_poke(pfhip_model* m, const char* what, int value) {
   // the rows the unfused head chunks covered in the forward that served the calling thread's last pfhip_svs_forward (svs_api.cpp)
   if (std::string(what) == "svs_unfused_rows") return (pfhip_status)svs_last_unfused_rows();
   if (std::string(what) == "svs_forward_calls") return (pfhip_status)svs_last_forward_calls();      // ... and the callers that forward served
+  if (std::string(what) == "svs_topk_k") return (pfhip_status)svs_last_topk_k();                    // ... and the stride of its k best columns
   if (std::string(what) == "range_flag") { m->debug_range_flag = value; return PFHIP_OK; }    // the next forward starts with its range flag raised
   if (std::string(what) == "range_fallbacks") {       // read-out: forwards redone on the exact kernels, over every context of the handle
     long long n = m->range_fallbacks;

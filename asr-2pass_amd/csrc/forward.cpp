@@ -66,8 +66,9 @@ pfhip_status forward_encoder(pfhip_model* m, PcmView d_pcm, const int64_t* sampl
       m->m_feat_off = dm + o; o += B;
       std::memcpy(hm + o, m->svs_prompt.data(), 4 * 4 * (size_t)B); m->m_prompt = dm + o; o += 4 * (size_t)B;
       // the speech rows N_b the greedy tokens are aligned against (heads.cpp), 0 for an utterance nobody wants spans of; a beam
-      // forward (pfhip_svs_forward_beam) searches the speech rows of every utterance
-      const bool spans = (int)m->svs_span_want.size() == B, beam = m->svs_beam_fb > 0;
+      // forward (pfhip_svs_forward_beam) searches the speech rows of every utterance (the sets form brings its own lengths with its
+      // descriptors — heads.cpp —, since there utterances with spans and utterances with a search share a forward)
+      const bool spans = (int)m->svs_span_want.size() == B, beam = m->svs_beam_fb > 0 && m->svs_beam_utt.empty();
       for (int b = 0; b < B; ++b) hm[o + b] = ((spans && m->svs_span_want[b]) || beam) && m->T[b] > 4 ? m->T[b] - 4 : 0;
       m->m_speech_len = dm + o; o += B;
     }

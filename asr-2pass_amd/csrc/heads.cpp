@@ -5,6 +5,7 @@
 
 #include "offline.h"
 #include "ctx_graph.h"
+#include "beam_front.h"
 #include "launch_common.h"
 
 namespace {
@@ -361,7 +362,34 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
                                  d_score, m->al_ws.p, ws, s))
       return fail(PFHIP_ERR_ARG, "CTC alignment refused its arguments");
   }
-  if (fb) {
+  if (fb && (int)m->svs_beam_utt.size() == B) {
+    // The search with every utterance on its own beams and graph (pfhip_svs_forward_beam_sets, merged beam callers): fb, sb and nb
+    // are the maxima — the columns' stride, the node stride and the hypothesis stride.  Descriptors, the graph table and the images
+    // of the graphs the device's bank does not hold go to the front of the search's workspace in one copy from pinned staging.
+    const int G = (int)m->svs_beam_graphs.size();
+    const pfhip_ctx_graph* const* graphs = m->svs_beam_graphs.data();
+    const void* const* resident = (int)m->svs_graph_dev.size() == G && G > 0 ? m->svs_graph_dev.data() : nullptr;
+    // Behind them, in the same copy, the speech rows of every utterance [B] (m_speech_len holds those of the span callers only).
+    const size_t lens = pfhip::beam_front_bytes(B, graphs, G, resident), front = lens + ((size_t)B * 4 + 15) / 16 * 16;
+    const size_t nodes = pfhip::ctc_prefix_beam_workspace_bytes(M, B, sb);
+    HIP_TRY(m->svs_beam_ws.ensure(front + nodes));
+    HIP_TRY(m->svs_beam_stage.ensure(front));
+    char* const dev = static_cast<char*>(m->svs_beam_ws.p);
+    char* const stage = static_cast<char*>(m->svs_beam_stage.p);
+    std::memset(stage, 0, front);
+    pfhip::beam_front_fill(stage, dev, m->svs_beam_utt.data(), B, graphs, G, resident);
+    for (int b = 0; b < B; ++b) reinterpret_cast<int*>(stage + lens)[b] = m->T[b] > 4 ? m->T[b] - 4 : 0;
+    HIP_TRY(hipMemcpyAsync(dev, stage, front, hipMemcpyHostToDevice, s));
+    const size_t bn = (size_t)B * nb;
+    int32_t *b_nhyp = dn + n_span, *b_ntok = b_nhyp + B, *b_ids = b_ntok + bn;
+    float *b_score = reinterpret_cast<float*>(b_ids + bn * bmt), *b_ctc = b_score + bn, *b_ctx = b_ctc + bn;
+    if (!pfhip::launch_ctc_prefix_beam_multi(m->svs_topk_ids.i(), m->svs_topk_logp.f(), fb, M, m->m_feat_off, reinterpret_cast<const int*>(dev + lens), B, V, c.blank_id,
+                                             reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                             reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), G, sb, nb, bmt,
+                                             b_nhyp, b_ids, b_ntok, b_score, b_ctc, b_ctx, dev + front, nodes, s))
+      return fail(PFHIP_ERR_ARG, "CTC prefix beam search refused its arguments");
+    m->svs_topk_k = fb;
+  } else if (fb) {
     // The prefix beam search over the speech rows (the four prompt rows are no CTC rows, sensevoice-small.cpp:422): one workgroup per
     // utterance on the k best columns either head left.  The graph goes to the front of the search's workspace with this call.
     const pfhip_ctx_graph* g = m->svs_beam_graph;

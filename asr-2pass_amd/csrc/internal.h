@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "weights.h"
 #include "hotword_bank.h"
+#include "graph_bank.h"
 #include "merge_queue.h"
 
 namespace pfhip_impl {
@@ -177,6 +178,16 @@ struct HwBankDev {
   int default_id = -1;                // the entry of the pfhip_set_hotwords set, pinned for as long as it is the default
   int64_t forwards = 0, sets_total = 0, sets_max = 0, percall_forwards = 0;
 };
+// The graph bank of one device (on the weight owner, shared by its contexts): packed images of hotword context graphs (ctx_graph.h)
+// in one arena, found again by content.  graph_bank.h keeps the books.  `mu` covers them AND the enqueue of a miss's fill + ready
+// event, so that whoever finds the entry afterwards finds its event recorded.
+struct GraphBankDev {
+  std::mutex mu;
+  HotwordBank bank;
+  char* arena = nullptr;
+  bool configured = false;
+  int64_t bound_bytes = -1;           // -1: PFHIP_CTX_GRAPH_BANK_MB (default 16) at first use
+};
 }  // namespace pfhip_impl
 
 namespace pfhip_impl {
@@ -291,6 +302,20 @@ struct pfhip_model {
   const pfhip_ctx_graph* svs_beam_graph = nullptr;
   size_t svs_beam_word = 0;
   Buf svs_topk_ids, svs_topk_logp, svs_beam_ws;
+  // pfhip_svs_forward_beam_sets and merged beam callers: every utterance on its own beams and graph.  svs_beam_utt [B] (empty: the
+  // one-set form above) with svs_beam_fb / _sb / _nbest the maxima over the searching utterances — the head's k, the node stride
+  // and the hypothesis stride of the results; svs_beam_graphs is the table the descriptors' graph indices name, svs_graph_dev per
+  // graph its image in the device's graph bank or null (then it goes up with the call, in front of the search's workspace),
+  // svs_graph_pins the bank entries the forward holds until after its last synchronise (graph_bank.cpp).  svs_beam_stage: the
+  // pinned staging of the copy that takes descriptors, table and unbanked images up (beam_front.h); svs_graph_stage / svs_graph_up:
+  // the pinned and the device staging of the ONE copy that takes a forward's bank misses up.
+  std::vector<pfhip::BeamUtt> svs_beam_utt;
+  std::vector<const pfhip_ctx_graph*> svs_beam_graphs;
+  std::vector<const void*> svs_graph_dev;
+  std::vector<int> svs_graph_pins;
+  PinBuf svs_beam_stage, svs_graph_stage;
+  Buf svs_graph_up;
+  std::unique_ptr<pfhip_impl::GraphBankDev> gbank{new pfhip_impl::GraphBankDev};      // on the weight owner
   int *m_feat_off = nullptr, *m_prompt = nullptr, *m_speech_len = nullptr;
   // device views into meta / dmeta
   int *m_frame_off = nullptr, *m_nframes = nullptr, *m_row_off = nullptr, *m_len = nullptr,
@@ -337,6 +362,7 @@ struct pfhip_model {
   // pfhip_offline_forward_resident); guarded by bq.mu
   std::shared_ptr<const std::vector<float>> hw_default;
   bool hw_merge = false;                    // on the head: contextual callers join the merge queue (pfhip_set_hotword_merging)
+  bool beam_merge = false;                  // on the head: SenseVoice beam callers join it (pfhip_svs_set_beam_merging); guarded by bq.mu
 
   // sets the device, waits for it, destroys contexts / replicas, events and streams; the members then free what they own
   ~pfhip_model();

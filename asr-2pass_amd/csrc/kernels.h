@@ -373,6 +373,19 @@ bool launch_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, int
                             int V, int blank, int first_beam, int second_beam, const CtxGraphDev& graph, int nbest, int max_tokens,
                             int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score, float* ctx_score,
                             void* workspace, size_t workspace_bytes, hipStream_t s);
+// The same search with every utterance on its own parameters: workgroup b reads utt[b] (a DEVICE array [B]) — first_beam 0: no search
+// for b (n_hyp 0); graph: an index into graphs (a DEVICE table [n_graphs]), -1: none.  The top-k rows have stride k and utterance b
+// reads their first first_beam[b] columns; trie nodes sit at the utterance's rows with stride sb_max (workspace:
+// ctc_prefix_beam_workspace_bytes(rows, B, sb_max)); outputs are [B][nbest_max]([max_tokens]), slots from nbest[b] on filled as the
+// slots behind n_hyp.  A descriptor outside the strides is answered as n_hyp 0 by the kernel; ctc_prefix_beam_multi_check is the
+// host's check of a HOST copy of the descriptors (beams 0..16, first_beam <= k, 1 <= nbest <= second_beam where first_beam > 0, graph
+// in -1 .. n_graphs - 1) and gives the two maxima (at least 1).
+struct BeamUtt { int first_beam, second_beam, nbest, graph; };
+bool ctc_prefix_beam_multi_check(const BeamUtt* utt, int B, int k, int n_graphs, int* sb_max, int* nbest_max);
+bool launch_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                                  int B, int V, int blank, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int sb_max,
+                                  int nbest_max, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
+                                  float* ctc_score, float* ctx_score, void* workspace, size_t workspace_bytes, hipStream_t s);
 // The same head with the k best columns of every row (topk.hip; 1 <= k <= kTopkMax <= V): topk_ids / topk_logp [ML][k], larger logit
 // first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry of its column bit for bit.  The
 // log-sum-exp is formed with logp null as well.  false (nothing launched) when the arguments are outside that.

@@ -627,6 +627,7 @@ pfhip_model::~pfhip_model() {
       if (D.bank.entry((int)i).ready) (void)hipEventDestroy(static_cast<hipEvent_t>(D.bank.entry((int)i).ready));
     if (D.arena) (void)hipFree(D.arena);
   }
+  pfhip_impl::destroy_graph_bank(this);      // the device's bank of context graphs (SenseVoice; unused on a context)
   for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
   if (own_stream) (void)hipStreamDestroy(own_stream);
   if (side_stream) (void)hipStreamDestroy(side_stream);

@@ -19,6 +19,11 @@ struct BatchReq : pfhip_impl::MergeReqBase {
   const int32_t *lid = nullptr, *textnorm = nullptr;
   pfhip_svs_out* sout = nullptr;
   pfhip_svs_align_out* spans = nullptr;
+  // a beam caller (pfhip_svs_set_beam_merging): its sets, per utterance the set it searches with (null: all set 0 — the
+  // pfhip_svs_forward_beam form) and its result buffers; topk_k comes back: the stride of the forward's k best columns
+  const pfhip_svs_beam_opts* sets = nullptr; int n_sets = 0; const int32_t* set_of = nullptr;
+  pfhip_svs_beam_out* bout = nullptr;
+  int topk_k = 0;
   pfhip_model* ran_on = nullptr;
   uint64_t serial = 0;
   int u0 = 0;
@@ -105,11 +110,27 @@ pfhip_model* pool_submit(pfhip_model* head, BatchReq& me, void (*run)(pfhip_mode
 // a packed forward for merged callers: per utterance whether its greedy tokens are aligned (null: all, when there is a span buffer)
 // and the host buffer for its full log-prob rows (null: none); back come the context's forward count behind this forward and the
 // rows its unfused head chunks covered
-struct SvsMerge { const char* span_want = nullptr; float* const* logp_rows = nullptr; uint64_t serial = 0; long long unfused_rows = 0; };
+struct SvsMerge { const char* span_want = nullptr; float* const* logp_rows = nullptr; uint64_t serial = 0; long long unfused_rows = 0; int topk_k = 0; };
+// the note of the calling thread's last forward on `head` (what pfhip_svs_align matches): the context it ran on — looked up among
+// the handle's own, null if there is none —, that context's forward count then and the caller's utterances within that forward
+struct SvsNoteView { pfhip_model* ctx = nullptr; uint64_t serial = 0; int u0 = 0, batch = 0; };
+SvsNoteView svs_thread_note(pfhip_model* head);
+int svs_last_topk_k();                  // the stride of the k best columns in the forward that served the calling thread (0: greedy)
+
+// ---- graph_bank.cpp ----
+pfhip_status svs_pin_graphs_locked(pfhip_model* m, hipStream_t s);
+void svs_release_graphs(pfhip_model* m);
+void destroy_graph_bank(pfhip_model* m);
 long long svs_last_unfused_rows();      // of the forward that served the calling thread's last pfhip_svs_forward
 int svs_last_forward_calls();           // the callers that forward served (1: a lone or direct call)
-// pfhip_svs_forward_beam: the search's options and the caller's buffers (both set, or no search)
-struct SvsBeam { const pfhip_svs_beam_opts* opts = nullptr; pfhip_svs_beam_out* out = nullptr; };
+// pfhip_svs_forward_beam: the search's options and the caller's buffers (both set, or no search).  The sets form
+// (pfhip_svs_forward_beam_sets, merged beam callers): utt [batch] gives every utterance its own beams and its graph as an index
+// into graphs (first_beam 0: no search; checked by the caller with ctc_prefix_beam_multi_check); opts is not read, and out's
+// hypothesis stride is the largest nbest among the searching utterances (1 if none).
+struct SvsBeam {
+  const pfhip_svs_beam_opts* opts = nullptr; pfhip_svs_beam_out* out = nullptr;
+  const pfhip::BeamUtt* utt = nullptr; const pfhip_ctx_graph* const* graphs = nullptr; int n_graphs = 0;
+};
 pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
                                 const int32_t* textnorm, pfhip_svs_out* out, pfhip_svs_align_out* spans = nullptr, SvsMerge* mg = nullptr,
                                 const SvsBeam* beam = nullptr);

@@ -3,6 +3,7 @@
 
 #include "ctx_graph.h"
 #include "internal.h"      // build_frontend_tables, DevMem; brings kernels.h
+#include "beam_front.h"
 
 #include <algorithm>
 #include <cmath>
@@ -447,6 +448,63 @@ int pfhip_op_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, in
   if (!pfhip::launch_ctc_prefix_beam(topk_ids, topk_logp, k, rows, row_off, len, B, V, blank, first_beam, second_beam, dev, nbest, max_tokens,
                                      n_hyp, ids, n_tokens, score, ctc_score, ctx_score, static_cast<char*>(workspace) + gbytes,
                                      workspace_bytes - gbytes, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+// every utterance on its own beams and graph: the descriptors are HOST arrays, checked here before anything is copied or launched,
+// then taken to the front of the workspace with the graphs' images in one copy (beam_front.h)
+static bool beam_multi_args(const int* first_beam, const int* second_beam, const int* nbest, const int* graph_of, int B, int k,
+                            const pfhip_ctx_graph* const* graphs, int n_graphs, int V, std::vector<pfhip::BeamUtt>* utt, int* sb_max, int* nb_max) {
+  if (B < 0 || B > 65535 || n_graphs < 0 || (n_graphs > 0 && !graphs) || (B > 0 && (!first_beam || !second_beam || !nbest || !graph_of)))
+    return false;
+  for (int g = 0; g < n_graphs; ++g)
+    if (!graphs[g] || graphs[g]->vocab != V) return false;
+  utt->resize((size_t)B);
+  for (int b = 0; b < B; ++b) (*utt)[b] = pfhip::BeamUtt{first_beam[b], second_beam[b], nbest[b], graph_of[b]};
+  return pfhip::ctc_prefix_beam_multi_check(utt->data(), B, k, n_graphs, sb_max, nb_max);
+}
+size_t pfhip_op_ctc_prefix_beam_multi_workspace_bytes(long long rows, int B, int k, const int* first_beam, const int* second_beam, const int* nbest,
+                                                      const int* graph_of, const pfhip_ctx_graph* const* graphs, int n_graphs) {
+  std::vector<pfhip::BeamUtt> utt;
+  int sb_max = 1, nb_max = 1;
+  if (n_graphs < 0 || (n_graphs > 0 && !graphs)) return 0;
+  for (int g = 0; g < n_graphs; ++g)
+    if (!graphs[g]) return 0;
+  if (!beam_multi_args(first_beam, second_beam, nbest, graph_of, B, k, graphs, n_graphs, n_graphs ? graphs[0]->vocab : 1, &utt, &sb_max, &nb_max))
+    return 0;
+  const size_t nodes = pfhip::ctc_prefix_beam_workspace_bytes(rows, B, sb_max);
+  return nodes ? nodes + pfhip::beam_front_bytes(B, graphs, n_graphs) : 0;
+}
+int pfhip_op_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                                   int B, int V, int blank, const int* first_beam, const int* second_beam, const int* nbest,
+                                   const int* graph_of, const pfhip_ctx_graph* const* graphs, int n_graphs, int max_tokens, int32_t* n_hyp,
+                                   int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score, float* ctx_score, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  std::vector<pfhip::BeamUtt> utt;
+  int sb_max = 1, nb_max = 1;
+  if (!beam_multi_args(first_beam, second_beam, nbest, graph_of, B, k, graphs, n_graphs, V, &utt, &sb_max, &nb_max)) return (int)hipErrorInvalidValue;
+  // the launcher's own checks, on a call that launches nothing (B = 0), then the buffers it would refuse at B > 0
+  if (!pfhip::launch_ctc_prefix_beam_multi(topk_ids, topk_logp, k, rows, row_off, len, 0, V, blank, nullptr, nullptr, n_graphs, sb_max, nb_max,
+                                           max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, nullptr, 0, S(stream)))
+    return (int)hipErrorInvalidValue;
+  const size_t front = pfhip::beam_front_bytes(B, graphs, n_graphs), nodes = pfhip::ctc_prefix_beam_workspace_bytes(rows, B, sb_max);
+  if (!workspace || workspace_bytes < front || workspace_bytes - front < nodes) return (int)hipErrorInvalidValue;
+  if (B > 0 && (!row_off || !len || !n_hyp || !n_tokens || !score || !ctc_score || !ctx_score || (max_tokens > 0 && !ids) ||
+                (rows > 0 && (!topk_ids || !topk_logp))))
+    return (int)hipErrorInvalidValue;
+  if (B == 0) return done();
+  char* const dev = static_cast<char*>(workspace);
+  std::vector<char> host(front, 0);
+  pfhip::beam_front_fill(host.data(), dev, utt.data(), B, graphs, n_graphs);
+  {
+    // pageable memory: the copy has left it when the call returns
+    const hipError_t e = hipMemcpyAsync(dev, host.data(), front, hipMemcpyHostToDevice, S(stream));
+    if (e != hipSuccess) return (int)e;
+  }
+  if (!pfhip::launch_ctc_prefix_beam_multi(topk_ids, topk_logp, k, rows, row_off, len, B, V, blank, reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                           reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), n_graphs, sb_max,
+                                           nb_max, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, dev + front,
+                                           workspace_bytes - front, S(stream)))
     return (int)hipErrorInvalidValue;
   return done();
 }

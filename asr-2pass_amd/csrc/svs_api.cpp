@@ -23,6 +23,7 @@ thread_local std::map<uint64_t, SvsNote> tl_svs_notes;
 // thread's last pfhip_svs_forward — taken while that forward still held its context, so no later forward there changes it
 thread_local long long tl_unfused_rows = 0;
 thread_local int tl_forward_calls = 0;      // "svs_forward_calls": the callers that same forward served
+thread_local int tl_topk_k = 0;             // "svs_topk_k": the stride of its k best columns (0: the greedy head)
 void keep_note(const pfhip_model* head, uint64_t ctx_uid, uint64_t serial, int u0, int batch) {
   if (tl_svs_notes.size() > 64) tl_svs_notes.clear();
   tl_svs_notes[head->uid] = SvsNote{ctx_uid, serial, u0, batch};
@@ -32,6 +33,53 @@ int rows_of(const pfhip_model* m, int n_samples) {      // forward_encoder's cou
   const int F = n_samples < 400 ? 0 : 1 + (n_samples - 400) / 160;
   const int T = (F + m->weights->cfg.lfr_n - 1) / m->weights->cfg.lfr_n;
   return T > 0 ? T + 4 : 0;
+}
+
+// The search's descriptors for a packed batch: per utterance its beams and the index of its graph in `graphs`, where a graph
+// appears once however many callers brought it — the same handle, or another handle with the same content.
+struct BeamPlan {
+  std::vector<pfhip::BeamUtt> utt;
+  std::vector<const pfhip_ctx_graph*> graphs;
+  int graph_index(const pfhip_ctx_graph* g) {
+    if (!g) return -1;
+    for (size_t i = 0; i < graphs.size(); ++i)
+      if (graphs[i] == g) return (int)i;
+    for (size_t i = 0; i < graphs.size(); ++i)
+      if (graphs[i]->vocab == g->vocab && graphs[i]->packed == g->packed) return (int)i;
+    graphs.push_back(g);
+    return (int)graphs.size() - 1;
+  }
+  // a caller's utterances: set_of == nullptr: all on sets[0]; sets == nullptr: a greedy caller, no search
+  void add(const pfhip_svs_beam_opts* sets, const int32_t* set_of, int batch) {
+    for (int b = 0; b < batch; ++b) {
+      const int k = !sets ? -1 : set_of ? set_of[b] : 0;
+      if (k < 0) { utt.push_back(pfhip::BeamUtt{0, 0, 0, -1}); continue; }
+      utt.push_back(pfhip::BeamUtt{sets[k].first_beam, sets[k].second_beam, sets[k].nbest, graph_index(sets[k].graph)});
+    }
+  }
+  // the hypothesis stride of utterances [u0, u0 + n): the largest nbest among those that search (1 if none)
+  int stride(int u0, int n) const {
+    int s = 1;
+    for (int u = u0; u < u0 + n; ++u)
+      if (utt[(size_t)u].first_beam > 0) s = std::max(s, utt[(size_t)u].nbest);
+    return s;
+  }
+};
+
+// a beam caller alone on slot m, with its own buffers: the one-set form as ever (its graph goes up with the call), the sets form
+// through the descriptors
+pfhip_status beam_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid, const int32_t* textnorm,
+                         pfhip_svs_out* out, const pfhip_svs_beam_opts* sets, const int32_t* set_of, pfhip_svs_beam_out* bo, SvsMerge* mg) {
+  SvsBeam beam;
+  beam.out = bo;
+  if (!set_of) {
+    beam.opts = sets;
+    return svs_forward_direct(m, pcm, n_samples, batch, lid, textnorm, out, nullptr, mg, &beam);
+  }
+  BeamPlan plan;
+  plan.add(sets, set_of, batch);
+  beam.utt = plan.utt.data(); beam.graphs = plan.graphs.data(); beam.n_graphs = (int)plan.graphs.size();
+  return svs_forward_direct(m, pcm, n_samples, batch, lid, textnorm, out, nullptr, mg, &beam);
 }
 
 // One packed forward on `m` for everybody in `take` (one sample format: pool_submit's pick).  Every caller keeps its own lid /
@@ -58,16 +106,20 @@ void run_svs_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
   if (take.size() == 1) {                             // nobody to share with: the caller's own buffers, as without the queue
     BatchReq* r = take.front();
     SvsMerge mg;
-    r->st = svs_forward_direct(m, r->pcm, r->n, r->batch, r->lid, r->textnorm, r->sout, r->spans, &mg);
-    r->err = g_err; r->serial = mg.serial; r->u0 = 0; r->unfused_rows = mg.unfused_rows;
+    r->st = r->bout ? beam_direct(m, r->pcm, r->n, r->batch, r->lid, r->textnorm, r->sout, r->sets, r->set_of, r->bout, &mg)
+                    : svs_forward_direct(m, r->pcm, r->n, r->batch, r->lid, r->textnorm, r->sout, r->spans, &mg);
+    r->err = g_err; r->serial = mg.serial; r->u0 = 0; r->unfused_rows = mg.unfused_rows; r->topk_k = mg.topk_k;
     return;
   }
   std::vector<const void*> ptrs; std::vector<int> lens, rows; std::vector<int32_t> lid, tn;
   std::vector<char> span_want; std::vector<float*> logp_rows;
-  bool any_spans = false, any_logp = false;
+  bool any_spans = false, any_logp = false, any_beam = false;
   int cap = 1; size_t M = 0;
+  BeamPlan plan;                                      // a greedy caller's utterances do not search
   for (BatchReq* r : take) {
     r->u0 = (int)lens.size();
+    plan.add(r->bout ? r->sets : nullptr, r->set_of, r->batch);
+    any_beam = any_beam || r->bout;
     size_t row_in_req = 0;
     for (int i = 0; i < r->batch; ++i) {
       const int T = rows_of(m, r->n[i]);
@@ -93,13 +145,28 @@ void run_svs_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
   SvsMerge mg;
   mg.span_want = any_spans ? span_want.data() : nullptr;
   mg.logp_rows = any_logp ? logp_rows.data() : nullptr;
+  // the beam callers' hypotheses, staged at the forward's own stride (the largest nbest among the searching utterances) with room
+  // for as many tokens as the longest utterance has rows; every caller is dealt its own at its own stride below
+  const int bstride = plan.stride(0, utts);
+  std::vector<int32_t> b_nhyp, b_ntok, b_ids;
+  std::vector<float> b_score, b_ctc, b_ctx;
+  pfhip_svs_beam_out ball{};
+  SvsBeam beam;
+  if (any_beam) {
+    const size_t bn = (size_t)utts * bstride;
+    b_nhyp.assign(utts, 0); b_ntok.assign(bn, 0); b_ids.assign(bn * cap, -1);
+    b_score.assign(bn, -INFINITY); b_ctc.assign(bn, -INFINITY); b_ctx.assign(bn, 0.f);
+    ball.n_hyp = b_nhyp.data(); ball.n_tokens = b_ntok.data(); ball.ids = b_ids.data(); ball.max_tokens = cap;
+    ball.score = b_score.data(); ball.ctc_score = b_ctc.data(); ball.ctx_score = b_ctx.data();
+    beam.out = &ball; beam.utt = plan.utt.data(); beam.graphs = plan.graphs.data(); beam.n_graphs = (int)plan.graphs.size();
+  }
   const pfhip_status st = svs_forward_direct(m, HostPcm(ptrs.data(), take.front()->pcm.s16), lens.data(), utts, lid.data(), tn.data(), &all,
-                                             any_spans ? &sp : nullptr, &mg);
+                                             any_spans ? &sp : nullptr, &mg, any_beam ? &beam : nullptr);
   const std::string err = g_err;
   std::vector<size_t> row_off(utts + 1, 0);
   for (int u = 0; u < utts; ++u) row_off[u + 1] = row_off[u] + (size_t)rows[u];
   for (BatchReq* r : take) {
-    r->st = st; r->err = err; r->serial = mg.serial; r->unfused_rows = mg.unfused_rows;
+    r->st = st; r->err = err; r->serial = mg.serial; r->unfused_rows = mg.unfused_rows; r->topk_k = mg.topk_k;
     if (st) continue;
     pfhip_svs_out* o = r->sout;
     int longest = 0;
@@ -107,6 +174,32 @@ void run_svs_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
       if (o->token_num) o->token_num[i] = num[r->u0 + i];
       if (o->frame_len) o->frame_len[i] = flen[r->u0 + i];
       longest = std::max(longest, num[r->u0 + i]);
+    }
+    if (r->bout) {                                    // n_hyp, the lengths and the scores also where max_tokens turns out too small
+      pfhip_svs_beam_out* bo = r->bout;
+      const int rs = plan.stride(r->u0, r->batch);
+      int longest_hyp = 0;
+      for (int i = 0; i < r->batch; ++i) {
+        const int u = r->u0 + i;
+        bo->n_hyp[i] = b_nhyp[u];
+        for (int j = 0; j < rs; ++j) {
+          const size_t src = (size_t)u * bstride + j, dst = (size_t)i * rs + j;
+          bo->n_tokens[dst] = b_ntok[src];
+          if (bo->score) bo->score[dst] = b_score[src];
+          if (bo->ctc_score) bo->ctc_score[dst] = b_ctc[src];
+          if (bo->ctx_score) bo->ctx_score[dst] = b_ctx[src];
+          if (j < b_nhyp[u]) longest_hyp = std::max(longest_hyp, b_ntok[src]);
+        }
+      }
+      if (bo->max_tokens < longest_hyp) {
+        r->st = PFHIP_ERR_CAPACITY; r->err = "beam: max_tokens smaller than the longest hypothesis (n_tokens holds the lengths)"; continue;
+      }
+      for (int i = 0; i < r->batch; ++i)
+        for (int j = 0; j < rs; ++j) {
+          const size_t src = (size_t)(r->u0 + i) * bstride + j, dst = (size_t)i * rs + j;
+          const int n = std::min(std::max(b_ntok[src], 0), cap);
+          std::memcpy(bo->ids + dst * bo->max_tokens, b_ids.data() + src * cap, (size_t)n * 4);
+        }
     }
     if ((o->ids || o->tok_frame || o->tok_logp) && o->max_tokens < longest) {
       r->st = PFHIP_ERR_CAPACITY; r->err = "max_tokens smaller than the longest token sequence"; continue;
@@ -134,6 +227,18 @@ void run_svs_requests(pfhip_model* m, const std::vector<BatchReq*>& all_taken) {
   }
 }
 
+// leader or follower, after the queue: where the forward ran, and which of its utterances are this caller's (pfhip_svs_align, the
+// debug read-outs)
+void note_merged(pfhip_model* head, const BatchReq& me, int batch) {
+  tl_unfused_rows = me.unfused_rows;
+  tl_forward_calls = me.company;
+  tl_topk_k = me.topk_k;
+  if (me.ran_on) {
+    last_replica() = me.ran_on;
+    if (me.serial) keep_note(head, me.ran_on->uid, me.serial, me.u0, batch);
+  }
+}
+
 pfhip_status svs_forward(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid, const int32_t* textnorm,
                                 pfhip_svs_out* out, pfhip_svs_align_out* spans = nullptr) {
   g_err.clear();
@@ -154,13 +259,7 @@ pfhip_status svs_forward(pfhip_model* head, HostPcm pcm, const int* n_samples, i
     BatchReq me;
     me.pcm = pcm; me.n = n_samples; me.batch = batch; me.lid = lid; me.textnorm = textnorm; me.sout = out; me.spans = spans;
     pool_submit(head, me, run_svs_requests);
-    // leader or follower: where the forward ran, and which of its utterances are this caller's (pfhip_svs_align, the debug read-outs)
-    tl_unfused_rows = me.unfused_rows;
-    tl_forward_calls = me.company;
-    if (me.ran_on) {
-      last_replica() = me.ran_on;
-      if (me.serial) keep_note(head, me.ran_on->uid, me.serial, me.u0, batch);
-    }
+    note_merged(head, me, batch);
     if (me.st != PFHIP_OK) g_err = me.err;
     return me.st;
   }
@@ -179,6 +278,17 @@ namespace pfhip_impl {
 
 long long svs_last_unfused_rows() { return tl_unfused_rows; }
 int svs_last_forward_calls() { return tl_forward_calls; }
+int svs_last_topk_k() { return tl_topk_k; }
+SvsNoteView svs_thread_note(pfhip_model* head) {
+  SvsNoteView v;
+  const auto note = tl_svs_notes.find(head->uid);
+  if (note == tl_svs_notes.end()) return v;
+  if (head->uid == note->second.ctx_uid) v.ctx = head;
+  for (pfhip_model* cx : head->contexts)
+    if (cx->uid == note->second.ctx_uid) v.ctx = cx;
+  v.serial = note->second.serial; v.u0 = note->second.u0; v.batch = note->second.batch;
+  return v;
+}
 
 // one packed forward on slot m, its range-guard re-run included, and the results into out
 pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid,
@@ -215,10 +325,30 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
   if (mg && mg->logp_rows) m->svs_logp_rows.assign(mg->logp_rows, mg->logp_rows + batch);
   m->svs_span_mt = 0;
   // the search behind the head (heads.cpp); a range-guard re-run reads the same fields, so everything then belongs to the re-run
-  m->svs_beam_fb = beam ? beam->opts->first_beam : 0;
-  m->svs_beam_sb = beam ? beam->opts->second_beam : 0;
-  m->svs_beam_nbest = beam ? beam->opts->nbest : 0;
-  m->svs_beam_graph = beam ? beam->opts->graph : nullptr;
+  const bool sets = beam && beam->utt;
+  m->svs_beam_fb = beam && !sets ? beam->opts->first_beam : 0;
+  m->svs_beam_sb = beam && !sets ? beam->opts->second_beam : 0;
+  m->svs_beam_nbest = beam && !sets ? beam->opts->nbest : 0;
+  m->svs_beam_graph = beam && !sets ? beam->opts->graph : nullptr;
+  m->svs_beam_utt.clear(); m->svs_beam_graphs.clear(); m->svs_graph_dev.clear();
+  struct GraphPins { pfhip_model* m; ~GraphPins() { svs_release_graphs(m); } } pins{m};      // let go after the forward's last synchronise
+  int beam_stride = beam && !sets ? beam->opts->nbest : 1;
+  if (sets) {
+    // every utterance on its own beams: the maxima are the head's k, the node stride and the hypothesis stride (no utterance
+    // searching: the greedy head, no search launch); the graphs are pinned in the device's bank before the first launch
+    int kmax = 0;
+    for (int b = 0; b < batch; ++b) kmax = std::max(kmax, beam->utt[b].first_beam);
+    if (kmax > 0) {
+      if (!pfhip::ctc_prefix_beam_multi_check(beam->utt, batch, kmax, beam->n_graphs, &m->svs_beam_sb, &m->svs_beam_nbest))
+        return fail(PFHIP_ERR_ARG, "beam: a set outside its bounds");
+      m->svs_beam_fb = kmax;
+      beam_stride = m->svs_beam_nbest;
+      m->svs_beam_utt.assign(beam->utt, beam->utt + batch);
+      m->svs_beam_graphs.assign(beam->graphs, beam->graphs + beam->n_graphs);
+      st = svs_pin_graphs_locked(m, s);
+      if (st) return st;
+    }
+  }
   st = enqueue_locked(m, PcmView{m->pcm.p, pcm.s16}, off.data(), n_samples, batch, s, false);
   if (!st && m->M > 0 && m->range_hit && !m->weights->always_exact) {      // the guard of the fp16 two-plane domain: redone once, exact
     ++m->range_fallbacks;
@@ -227,11 +357,14 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
     m->exact_rerun = false;
   }
   m->svs_logp_host = nullptr;
+  const bool searched = m->svs_beam_fb > 0;
   m->svs_beam_fb = m->svs_beam_sb = m->svs_beam_nbest = 0;
   m->svs_beam_graph = nullptr;
+  m->svs_beam_utt.clear(); m->svs_beam_graphs.clear(); m->svs_graph_dev.clear();
   m->svs_span_want.clear();
   m->svs_logp_rows.clear();
   (mg ? mg->unfused_rows : tl_unfused_rows) = st || m->M == 0 ? 0 : m->svs_unfused_rows;
+  (mg ? mg->topk_k : tl_topk_k) = st || m->M == 0 ? 0 : m->svs_topk_k;
   if (st) return st;
   m->svs_fwd_ok = true;                          // the rows and their log-sum-exp are what pfhip_svs_align reads ...
   ++m->svs_serial;                               // ... for this thread, until this context runs another forward
@@ -246,9 +379,17 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
     for (int b = 0; beam && b < batch; ++b) beam->out->n_hyp[b] = 0;      // CtcSearch returns "" without searching
     return PFHIP_OK;
   }
-  if (beam) {                                      // they came in the forward's one copy, behind the spans' words
+  if (beam && !searched) {                         // the sets form with no utterance searching: the greedy head ran, nothing was searched
     pfhip_svs_beam_out* bo = beam->out;
-    const int nb = beam->opts->nbest, mt = m->svs_beam_mt;
+    for (int b = 0; b < batch; ++b) {
+      bo->n_hyp[b] = 0; bo->n_tokens[b] = 0;
+      if (bo->score) bo->score[b] = -INFINITY;
+      if (bo->ctc_score) bo->ctc_score[b] = -INFINITY;
+      if (bo->ctx_score) bo->ctx_score[b] = 0.f;
+    }
+  } else if (beam) {                               // they came in the forward's one copy, behind the spans' words
+    pfhip_svs_beam_out* bo = beam->out;
+    const int nb = beam_stride, mt = m->svs_beam_mt;
     const size_t bn = (size_t)batch * nb;
     const int32_t *h_nhyp = m->h_counts.i() + m->svs_beam_word, *h_ntok = h_nhyp + batch, *h_ids = h_ntok + bn;
     const float *h_score = reinterpret_cast<const float*>(h_ids + bn * mt), *h_ctc = h_score + bn, *h_ctx = h_ctc + bn;
@@ -348,40 +489,85 @@ pfhip_status pfhip_svs_forward_spans_s16(pfhip_model* m, const int16_t* const* p
   return svs_forward(m, pcm, n_samples, batch, lid, textnorm, out, spans);
 }
 
-// The forward with the CTC prefix beam search (and hotwords) behind its head, in the same stream work, copy and synchronise.  The
-// merge queue of pfhip_svs_set_batching is passed by: a beam caller runs alone on a slot (merging them is not built).
+// The forward with the CTC prefix beam search (and hotwords) behind its head, in the same stream work, copy and synchronise: one set
+// of options for all utterances (set_of == nullptr: pfhip_svs_forward_beam) or a set per utterance (pfhip_svs_forward_beam_sets).
+// The merge queue of pfhip_svs_set_batching is passed by — the caller runs alone on a slot — unless pfhip_svs_set_beam_merging is on.
 static pfhip_status svs_forward_beam(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, const int32_t* lid, const int32_t* textnorm,
-                                     pfhip_svs_out* out, const pfhip_svs_beam_opts* opts, pfhip_svs_beam_out* bo) {
+                                     pfhip_svs_out* out, const pfhip_svs_beam_opts* sets, int n_sets, const int32_t* set_of,
+                                     pfhip_svs_beam_out* bo) {
   g_err.clear();
-  if (!head || !pcm.p || !n_samples || batch <= 0 || !lid || !textnorm || !out || !opts || !bo) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!head || !pcm.p || !n_samples || batch <= 0 || !lid || !textnorm || !out || !sets || n_sets < 1 || !bo) return fail(PFHIP_ERR_ARG, "bad argument");
   if (!is_svs(head)) return fail(PFHIP_ERR_UNSUPPORTED, "not a SenseVoice (CTC) model: there are no CTC rows to search");
   if (!head->replicas.empty()) return fail(PFHIP_ERR_UNSUPPORTED, "multi-device groups are not built for SenseVoice (CTC) models");
-  if (opts->first_beam < 1 || opts->first_beam > pfhip::kBeamMax || opts->second_beam < 1 || opts->second_beam > pfhip::kBeamMax)
-    return fail(PFHIP_ERR_ARG, "beam: first_beam and second_beam must lie in 1..16");
-  if (opts->nbest < 1 || opts->nbest > opts->second_beam) return fail(PFHIP_ERR_ARG, "beam: nbest must lie in 1..second_beam");
-  if (opts->first_beam > head->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "beam: first_beam larger than the vocabulary");
-  if (opts->graph && opts->graph->vocab != head->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "beam: the context graph was built for another vocabulary");
+  std::vector<char> used((size_t)n_sets, set_of ? 0 : 1);
+  for (int b = 0; set_of && b < batch; ++b) {
+    if (set_of[b] < -1 || set_of[b] >= n_sets) return fail(PFHIP_ERR_ARG, "beam: set_of names no set");
+    if (set_of[b] >= 0) used[(size_t)set_of[b]] = 1;
+  }
+  for (int k = 0; k < n_sets; ++k) {
+    const pfhip_svs_beam_opts* opts = sets + k;
+    if (!used[(size_t)k]) continue;
+    if (opts->first_beam < 1 || opts->first_beam > pfhip::kBeamMax || opts->second_beam < 1 || opts->second_beam > pfhip::kBeamMax)
+      return fail(PFHIP_ERR_ARG, "beam: first_beam and second_beam must lie in 1..16");
+    if (opts->nbest < 1 || opts->nbest > opts->second_beam) return fail(PFHIP_ERR_ARG, "beam: nbest must lie in 1..second_beam");
+    if (opts->first_beam > head->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "beam: first_beam larger than the vocabulary");
+    if (opts->graph && opts->graph->vocab != head->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "beam: the context graph was built for another vocabulary");
+  }
   if (!bo->n_hyp || !bo->n_tokens || bo->max_tokens < 0 || (bo->max_tokens > 0 && !bo->ids)) return fail(PFHIP_ERR_ARG, "beam: a result buffer is missing");
   for (int b = 0; b < batch; ++b) {
     if (n_samples[b] < 0 || (n_samples[b] > 0 && !pcm.p[b])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
     if (lid[b] < 0 || lid[b] > 15 || textnorm[b] < 0 || textnorm[b] > 15) return fail(PFHIP_ERR_ARG, "lid / textnorm outside 0..15");
   }
+  bool merge;
+  {
+    std::lock_guard<std::mutex> l(head->bq.mu);
+    merge = head->beam_merge && head->batch_wait_us > 0 && batch < head->batch_max_utts;
+  }
+  if (merge) {                                          // pfhip_svs_set_beam_merging: in the queue like a greedy caller
+    BatchReq me;
+    me.pcm = pcm; me.n = n_samples; me.batch = batch; me.lid = lid; me.textnorm = textnorm; me.sout = out;
+    me.sets = sets; me.n_sets = n_sets; me.set_of = set_of; me.bout = bo;
+    pool_submit(head, me, run_svs_requests);
+    note_merged(head, me, batch);
+    if (me.st != PFHIP_OK) g_err = me.err;
+    return me.st;
+  }
   pfhip_model* m = acquire_slot(head);
   last_replica() = m;
   tl_forward_calls = 1;
-  const SvsBeam beam{opts, bo};
-  const pfhip_status st = svs_forward_direct(m, pcm, n_samples, batch, lid, textnorm, out, nullptr, nullptr, &beam);
+  const pfhip_status st = beam_direct(m, pcm, n_samples, batch, lid, textnorm, out, sets, set_of, bo, nullptr);
   ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
   release_slot(head, m);
   return st;
 }
 pfhip_status pfhip_svs_forward_beam(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                     const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* opts, pfhip_svs_beam_out* beam) {
-  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, opts, beam);
+  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, opts, 1, nullptr, beam);
 }
 pfhip_status pfhip_svs_forward_beam_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                         const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* opts, pfhip_svs_beam_out* beam) {
-  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, opts, beam);
+  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, opts, 1, nullptr, beam);
+}
+pfhip_status pfhip_svs_forward_beam_sets(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                         const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* sets, int n_sets,
+                                         const int32_t* set_of, pfhip_svs_beam_out* beam) {
+  if (!set_of) return fail(PFHIP_ERR_ARG, "bad argument");
+  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, sets, n_sets, set_of, beam);
+}
+pfhip_status pfhip_svs_forward_beam_sets_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                             const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* sets, int n_sets,
+                                             const int32_t* set_of, pfhip_svs_beam_out* beam) {
+  if (!set_of) return fail(PFHIP_ERR_ARG, "bad argument");
+  return svs_forward_beam(m, pcm, n_samples, batch, lid, textnorm, out, sets, n_sets, set_of, beam);
+}
+// pfhip_set_hotword_merging's sibling: beam callers join the queue of pfhip_svs_set_batching
+pfhip_status pfhip_svs_set_beam_merging(pfhip_model* m, int on) {
+  g_err.clear();
+  if (!m) return fail(PFHIP_ERR_ARG, "null model");
+  if (!is_svs(m)) return fail(PFHIP_ERR_UNSUPPORTED, "not a SenseVoice (CTC) model: there is no search to merge");
+  std::lock_guard<std::mutex> l(m->bq.mu);
+  m->beam_merge = on != 0;
+  return PFHIP_OK;
 }
 
 // CTC forced alignment of caller-given tokens against the rows of the calling thread's last pfhip_svs_forward (ctc_align.hip): the

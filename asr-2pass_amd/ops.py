@@ -61,6 +61,11 @@ def _lib():
             lib.pfhip_op_ctc_prefix_beam_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp]
             lib.pfhip_op_ctc_prefix_beam.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _ci,
                                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+        if hasattr(lib, "pfhip_op_ctc_prefix_beam_multi"):
+            lib.pfhip_op_ctc_prefix_beam_multi_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_ctc_prefix_beam_multi_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci]
+            lib.pfhip_op_ctc_prefix_beam_multi.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp,
+                                                           _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
         _bound = True
     return lib
 
@@ -486,6 +491,46 @@ def ctc_prefix_beam(topk_ids, topk_logp, row_off, length, vocab, first_beam, sec
     _ck(lib.pfhip_op_ctc_prefix_beam(_p(topk_ids), _p(topk_logp), k, rows, _p(row_off), _p(length), B, int(vocab), int(blank),
                                      int(first_beam), int(second_beam), gh, nbest, max_tokens, _p(n_hyp), _p(ids) if max_tokens else None,
                                      _p(n_tokens), _p(score), _p(ctc_score), _p(ctx_score), _p(ws), nbytes, _stream()), "ctc_prefix_beam")
+    return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], ctc_score[:B], ctx_score[:B]
+
+
+def ctc_prefix_beam_multi(topk_ids, topk_logp, row_off, length, vocab, first_beam, second_beam, nbest, graph_of=None, graphs=(),
+                          max_tokens=None, blank=0, workspace_bytes=None, rows=None, out=None):
+    """ctc_prefix_beam with every utterance on its own parameters, in one launch (pfhip_op_ctc_prefix_beam_multi): first_beam,
+    second_beam, nbest and graph_of are host sequences [B] (first_beam 0: no search for that utterance; graph_of -1: no graph),
+    graphs a sequence of ContextGraph.  Utterance b reads the first first_beam[b] columns of its rows.  Returns ctc_prefix_beam's
+    tuple with nbest_max = the largest nbest among the searching utterances as the hypothesis stride.  out: that tuple to write
+    into instead of fresh tensors (a refusal must leave it as it was)."""
+    lib = _lib()
+    all_rows, k = int(topk_ids.shape[0]), int(topk_ids.shape[1])
+    rows = all_rows if rows is None else min(int(rows), all_rows)
+    B = int(row_off.numel())
+    arr = lambda v: (ctypes.c_int * max(B, 1))(*[int(x) for x in v])
+    graph_of = [-1] * B if graph_of is None else graph_of
+    if not (len(first_beam) == len(second_beam) == len(nbest) == len(graph_of) == B):
+        raise PfhipError("ctc_prefix_beam_multi: one first_beam, second_beam, nbest and graph_of per utterance")
+    fb, sb, nb, go = arr(first_beam), arr(second_beam), arr(nbest), arr(graph_of)
+    handles = (ctypes.c_void_p * max(len(graphs), 1))(*[g.handle for g in graphs])
+    nb_max = max([int(n) for f, n in zip(first_beam, nbest) if int(f) > 0] + [1])
+    max_tokens = rows if max_tokens is None else int(max_tokens)
+    dev = topk_ids.device
+    if out is None:
+        n_hyp = torch.full((max(B, 1),), -7, dtype=torch.int32, device=dev)
+        ids = torch.full((max(B, 1), nb_max, max(max_tokens, 1)), -7, dtype=torch.int32, device=dev)
+        n_tokens = torch.full((max(B, 1), nb_max), -7, dtype=torch.int32, device=dev)
+        score, ctc_score, ctx_score = (torch.full((max(B, 1), nb_max), float("nan"), dtype=torch.float32, device=dev) for _ in range(3))
+    else:
+        n_hyp, ids, n_tokens, score, ctc_score, ctx_score = out
+    if workspace_bytes is None:
+        nbytes = int(lib.pfhip_op_ctc_prefix_beam_multi_workspace_bytes(all_rows, B, k, fb, sb, nb, go, handles, len(graphs)))
+    else:
+        nbytes = int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    if max_tokens != ids.shape[2]:
+        ids = ids[:, :, :0]
+    _ck(lib.pfhip_op_ctc_prefix_beam_multi(_p(topk_ids), _p(topk_logp), k, rows, _p(row_off), _p(length), B, int(vocab), int(blank), fb, sb, nb,
+                                           go, handles, len(graphs), max_tokens, _p(n_hyp), _p(ids) if max_tokens else None, _p(n_tokens),
+                                           _p(score), _p(ctc_score), _p(ctx_score), _p(ws), nbytes, _stream()), "ctc_prefix_beam_multi")
     return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], ctc_score[:B], ctx_score[:B]
 
 

@@ -755,8 +755,9 @@ pfhip_status pfhip_ctx_graph_dump(const pfhip_ctx_graph* g, int* n_states, int* 
  * utterance without rows has n_hyp 0.  PFHIP_ERR_CAPACITY where max_tokens is below the longest returned hypothesis: n_hyp,
  * n_tokens and the scores are written all the same, so n_tokens carries the length needed.  PFHIP_ERR_UNSUPPORTED: a Paraformer
  * handle.  PFHIP_ERR_ARG: beams outside 1..16, nbest outside 1..second_beam, a graph of another vocabulary, a missing buffer.
- * With pfhip_svs_set_batching on, the call is served alone, past the merge queue.  pfhip_get_tensor "ctc_topk_ids" (int32 words) /
- * "ctc_topk_logp": the [M][first_beam] columns the search read, prompt rows included. */
+ * With pfhip_svs_set_batching on, the call is served alone, past the merge queue, unless pfhip_svs_set_beam_merging is on (below).
+ * pfhip_get_tensor "ctc_topk_ids" (int32 words) / "ctc_topk_logp": the [M][first_beam] columns the search read, prompt rows
+ * included. */
 typedef struct pfhip_svs_beam_opts { int first_beam; int second_beam; int nbest; const pfhip_ctx_graph* graph; } pfhip_svs_beam_opts;
 typedef struct pfhip_svs_beam_out {
   int32_t* n_hyp; int32_t* ids; int32_t* n_tokens; float* score; float* ctc_score; float* ctx_score; int max_tokens;
@@ -766,6 +767,47 @@ pfhip_status pfhip_svs_forward_beam(pfhip_model* m, const float* const* pcm, con
 pfhip_status pfhip_svs_forward_beam_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, const int32_t* lid,
                                         const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* opts,
                                         pfhip_svs_beam_out* beam);
+/* One call, several searches: pfhip_svs_forward_beam with every utterance on its own set of options — the sibling of
+ * pfhip_offline_forward_hwsets for the CTC model (one connection, one CtcPrefixDecoder with its own hotwords: websocket-server.cpp:173).
+ * sets [n_sets]; set_of [batch] names each utterance's set, -1: no search for it (n_hyp 0).  The head runs ONCE in its top-k form
+ * with k = the largest first_beam among the sets in use (no set in use: the greedy head of pfhip_svs_forward), and ONE search launch
+ * serves all utterances (pfhip_op_ctc_prefix_beam_multi): utterance b reads the first first_beam columns of its rows, which are the
+ * columns a head run at k = first_beam leaves, bit for bit (the value and order rules of pfhip_op_ctc_head_topk do not depend on
+ * k), so with every utterance on one set the call equals pfhip_svs_forward_beam bit for bit, and `out` is pfhip_svs_forward's.
+ * Results cross in the forward's one copy, before its one synchronise; a range-guard re-run redoes all of it.
+ * beam: as above with nbest stride = the largest nbest among the sets in use (1 if none): ids [batch][stride][max_tokens], the
+ * others [batch][stride]; slots from an utterance's own nbest on read as slots behind n_hyp.  Errors are pfhip_svs_forward_beam's,
+ * per set in use; PFHIP_ERR_ARG also for n_sets < 1 or a set_of outside -1 .. n_sets - 1.
+ * pfhip_get_tensor "ctc_topk_*" after it: [rows][k] with that k (pfhip_debug_poke "svs_topk_k").
+ * The graphs of this call and of merged beam callers stay on the device: a per-device bank of packed graph images shared by the
+ * execution contexts and found again by content (hash + byte compare).  A graph seen before costs no upload; all misses of a forward
+ * go up in one copy; least recently used graphs are evicted, never one a forward in flight uses; a graph the bank cannot take goes
+ * up with the call.  pfhip_svs_set_graph_bank_bytes bounds it (default PFHIP_CTX_GRAPH_BANK_MB = 16 per device; 0 banks nothing;
+ * set it while no forward is in flight, PFHIP_ERR_ARG otherwise).  Results do not depend on the bank.  pfhip_svs_forward_beam
+ * served alone keeps uploading its graph with the call. */
+pfhip_status pfhip_svs_forward_beam_sets(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, const int32_t* lid,
+                                         const int32_t* textnorm, pfhip_svs_out* out, const pfhip_svs_beam_opts* sets, int n_sets,
+                                         const int32_t* set_of, pfhip_svs_beam_out* beam);
+pfhip_status pfhip_svs_forward_beam_sets_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch,
+                                             const int32_t* lid, const int32_t* textnorm, pfhip_svs_out* out,
+                                             const pfhip_svs_beam_opts* sets, int n_sets, const int32_t* set_of, pfhip_svs_beam_out* beam);
+pfhip_status pfhip_svs_set_graph_bank_bytes(pfhip_model* m, int64_t bytes);
+/* Totals over the handle's device: graphs found resident, uploaded, dropped for room, refused (served from the call's workspace). */
+typedef struct pfhip_svs_graph_bank_stats_t {
+  int64_t hits, misses, evictions, refused;
+  int64_t bytes_in_use, bytes_capacity, graphs_resident;
+} pfhip_svs_graph_bank_stats_t;
+pfhip_status pfhip_svs_graph_bank_stats(pfhip_model* m, pfhip_svs_graph_bank_stats_t* out);
+/* Beam callers in the merge queue (pfhip_svs_set_batching): on != 0 lets concurrent pfhip_svs_forward_beam[_s16] and
+ * pfhip_svs_forward_beam_sets[_s16] callers share packed forwards with each other and with greedy callers of the same sample
+ * format: one head launch at the largest first_beam, one search launch with every utterance on its caller's beams and graph (graphs
+ * de-duplicated by pointer, then by content), each caller dealt its hypotheses at its own nbest stride and max_tokens.  A caller
+ * whose max_tokens is too small fails alone with PFHIP_ERR_CAPACITY, n_hyp / n_tokens / scores written as in the lone call.  Off
+ * (the default), every beam call is a forward of its own, as before.  Merged, `out` is that of a separate call as far as
+ * pfhip_svs_set_batching states it, and the hypotheses are the search's on the columns of the forward that served the caller:
+ * pfhip_get_tensor "ctc_topk_ids" / "ctc_topk_logp" then return the CALLING THREAD's own utterances' rows [own rows][k] (the
+ * lifetime rule of pfhip_svs_align), and pfhip_debug_poke "svs_topk_k" that forward's k. */
+pfhip_status pfhip_svs_set_beam_merging(pfhip_model* m, int on);
 
 /* ---- inspection (parity tests) -----------------------------------------------------------------
  * Copies a named intermediate of the LAST forward to host: "feats" [M,560], "enc" [M,d],

@@ -248,6 +248,27 @@ int pfhip_op_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, in
                              int B, int V, int blank, int first_beam, int second_beam, const struct pfhip_ctx_graph* graph, int nbest,
                              int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score,
                              float* ctx_score, void* workspace, size_t workspace_bytes, void* stream);
+/* The same search with every utterance on its own parameters, in one launch (the second instantiation of the kernel: the
+ * arithmetic, the tie rule and the sanitising are those above).  topk_ids / topk_logp [rows][k], row_off and len are DEVICE arrays
+ * as above; first_beam, second_beam, nbest and graph_of [B] are HOST arrays, and graphs is a HOST array of n_graphs handles.
+ * Utterance b reads the first first_beam[b] columns of its rows (the row stride stays k) and searches with second_beam[b], nbest[b]
+ * and graphs[graph_of[b]] (graph_of[b] == -1: no graph); first_beam[b] == 0: no search for b, n_hyp[b] = 0.  With nbest_max the
+ * largest nbest[b] among the searching utterances (1 if none): ids [B][nbest_max][max_tokens], n_tokens / score / ctc_score /
+ * ctx_score [B][nbest_max]; slots from nbest[b] on hold what slots behind n_hyp hold (-1 / 0 / -inf / -inf / 0).
+ * workspace: pfhip_op_ctc_prefix_beam_multi_workspace_bytes(...) bytes of device memory (0 for descriptors the entry refuses): the
+ * descriptors, a table of the graphs and their images, which the call copies there on `stream` in one copy, then a trie node per
+ * row and slot of the largest second_beam.  hipErrorInvalidValue, before anything is copied or launched, for: a beam outside
+ * 0..16, first_beam[b] > k, nbest[b] outside 1..second_beam[b] where first_beam[b] > 0, graph_of[b] outside -1 .. n_graphs - 1, a
+ * NULL graph or one built for another vocabulary than V, k outside 1..16, blank outside 0 .. V - 1, a NULL buffer (ids with
+ * max_tokens 0 excepted) or a short workspace. */
+size_t pfhip_op_ctc_prefix_beam_multi_workspace_bytes(long long rows, int B, int k, const int* first_beam, const int* second_beam,
+                                                      const int* nbest, const int* graph_of,
+                                                      const struct pfhip_ctx_graph* const* graphs, int n_graphs);
+int pfhip_op_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off,
+                                   const int* len, int B, int V, int blank, const int* first_beam, const int* second_beam,
+                                   const int* nbest, const int* graph_of, const struct pfhip_ctx_graph* const* graphs, int n_graphs,
+                                   int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score,
+                                   float* ctx_score, void* workspace, size_t workspace_bytes, void* stream);
 /* One streaming window (M <= 32 rows): LayerNormalization (g != NULL; width D <= K) -> MatMul/Gemm (+bias, +residual Adds, Relu)
  * (+ the SAN-M FSMN memory of fsmn_v over the M rows, k = 11) in ONE launch — stream_fused.hip. */
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
