@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     # SenseVoiceSmall: a set of search options per utterance, beam callers in the merge queue, the graphs kept on the device
     "pfhip_svs_forward_beam_sets", "pfhip_svs_forward_beam_sets_s16", "pfhip_svs_set_beam_merging", "pfhip_svs_set_graph_bank_bytes",
     "pfhip_svs_graph_bank_stats",
+    # hotwords for any Paraformer: the biased beam search over the head's candidates, behind the forward
+    "pfhip_offline_forward_bias", "pfhip_offline_forward_bias_s16",
 ]
 
 
@@ -138,6 +140,16 @@ class _SvsBeamOpts(ctypes.Structure):
 class _SvsBeamOut(ctypes.Structure):
     _fields_ = [("n_hyp", ctypes.POINTER(ctypes.c_int32)), ("ids", ctypes.POINTER(ctypes.c_int32)), ("n_tokens", ctypes.POINTER(ctypes.c_int32)),
                 ("score", ctypes.POINTER(ctypes.c_float)), ("ctc_score", ctypes.POINTER(ctypes.c_float)),
+                ("ctx_score", ctypes.POINTER(ctypes.c_float)), ("max_tokens", ctypes.c_int)]
+
+
+class _BiasOpts(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int), ("beam", ctypes.c_int), ("nbest", ctypes.c_int), ("graph", ctypes.c_void_p)]
+
+
+class _BiasOut(ctypes.Structure):
+    _fields_ = [("n_hyp", ctypes.POINTER(ctypes.c_int32)), ("ids", ctypes.POINTER(ctypes.c_int32)), ("n_tokens", ctypes.POINTER(ctypes.c_int32)),
+                ("score", ctypes.POINTER(ctypes.c_float)), ("am_score", ctypes.POINTER(ctypes.c_float)),
                 ("ctx_score", ctypes.POINTER(ctypes.c_float)), ("max_tokens", ctypes.c_int)]
 
 
@@ -248,6 +260,10 @@ def load_lib() -> ctypes.CDLL:
         lib.pfhip_offline_fetch_fire_frames.argtypes = [vp, vp]
         lib.pfhip_lfr_frame_ms.argtypes = [vp]
         lib.pfhip_cif_timestamps.argtypes = [vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, ci, ctypes.POINTER(ci)]
+    if hasattr(lib, "pfhip_offline_forward_bias"):
+        lib.pfhip_offline_forward_bias.argtypes = lib.pfhip_offline_forward_detail.argtypes + [ctypes.POINTER(_BiasOpts), ci, ctypes.POINTER(ctypes.c_int32),
+                                                                                               ctypes.POINTER(_BiasOut)]
+        lib.pfhip_offline_forward_bias_s16.argtypes = lib.pfhip_offline_forward_bias.argtypes
     lib.pfhip_stream_create.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(vp)]
     lib.pfhip_stream_destroy.argtypes = [vp]
     lib.pfhip_stream_destroy.restype = None
@@ -623,7 +639,7 @@ class ParaformerHip:
 
     def forward_ids(self, din: Sequence[np.ndarray], want_logp=False, max_tokens=None, hw_emb=None, want_timestamps=False,
                     sample_rate=None, hw_sets=None, set_of_utt=None, nbest=None, nbest_fill=0, nbest_s16=False,
-                    want_fire_frames=False, fire_fill=-1):
+                    want_fire_frames=False, fire_fill=-1, bias_sets=None, set_of=None, bias_max_tokens=None):
         """Batched forward.  Returns dict(token_num, n_fires, n_frames, ids=list of int arrays,
         logp=list of [n_fires, V] arrays or None[, us_alphas, us_peaks = lists of [3*T_b] arrays]).
         hw_emb: one hotword set [H, d] for the whole batch.  hw_sets + set_of_utt: a list of sets ([H_k, d] each) and, per
@@ -633,12 +649,18 @@ class ParaformerHip:
         log-probabilities (pfhip_offline_forward_nbest; rows >= n_fires keep nbest_fill); not together with sample_rate.
         nbest_s16: np.int16 utterances go to pfhip_offline_forward_nbest_s16 as they are instead of being converted here.
         want_fire_frames: also fire_frame [batch, max_tokens] int32, the LFR row each token row fired in (n_frames[b] = the tail slot;
-        rows >= n_fires keep fire_fill), through pfhip_offline_forward_detail — which takes nbest, hw_sets and sample_rate together."""
+        rows >= n_fires keep fire_fill), through pfhip_offline_forward_detail — which takes nbest, hw_sets and sample_rate together.
+        bias_sets: the same call plus the hotword-biased beam search over the head's candidates (pfhip_offline_forward_bias; an
+        extension that works on any Paraformer): a sequence of (width, beam, nbest, graph) with graph a ContextGraph or None, and
+        set_of: per utterance the index of its set, -1 for no search (default: every utterance on set 0).  The result then also holds
+        bias=dict(n_hyp [B], ids [B, stride, bias_max_tokens] (-1 where nothing was written), n_tokens, score, am_score, ctx_score
+        [B, stride]) with stride the largest nbest among the sets in use, and hyps: per utterance the list of (ids, score, am_score,
+        ctx_score).  np.int16 utterances go to the _s16 entry point as they are."""
         B = len(din)
         if B == 0:
             raise PfhipError("empty batch")
         # np.int16 utterances go to the *_s16 entry points as they are (with nbest only where nbest_s16 asks for it: floats otherwise)
-        bufs, s16 = _pcm_buffers(din) if nbest is None or nbest_s16 else ([_pcm_f32(x) for x in din], False)
+        bufs, s16 = _pcm_buffers(din) if nbest is None or nbest_s16 or bias_sets is not None else ([_pcm_f32(x) for x in din], False)
         sfx = "_s16" if s16 else ""
         lens = (ctypes.c_int * B)(*[int(b.shape[0]) for b in bufs])
         ptrs = (ctypes.c_void_p * B)(*[b.ctypes.data if b.shape[0] else None for b in bufs])
@@ -673,12 +695,14 @@ class ParaformerHip:
             out.max_us = max_us
         hw = np.ascontiguousarray(hw_emb, dtype=np.float32) if hw_emb is not None else None
         hw_ptr, n_hw = (hw.ctypes.data, int(hw.shape[0])) if hw is not None else (None, 0)
-        if want_fire_frames:
+        if want_fire_frames or bias_sets is not None:
             if hw_sets is not None and (hw_emb is not None or set_of_utt is None or len(set_of_utt) != B):
                 raise PfhipError("hw_sets needs set_of_utt [batch] and excludes hw_emb")
             k = int(nbest) if nbest is not None else 0
-            fire = np.full((B, max_tokens), fire_fill, np.int32)
-            det = _Detail(k, None, None, fire.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+            det = _Detail(k, None, None, None)
+            if want_fire_frames:
+                fire = np.full((B, max_tokens), fire_fill, np.int32)
+                det.fire_frame = fire.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
             if nbest is not None:
                 nb_ids = np.full((B, max_tokens, max(k, 1)), nbest_fill, np.int32)
                 nb_logp = np.full((B, max_tokens, max(k, 1)), nbest_fill, np.float32)
@@ -688,9 +712,33 @@ class ParaformerHip:
             sptr = (ctypes.c_void_p * max(len(sets), 1))(*[h.ctypes.data if h.size else None for h in sets])
             sn = (ctypes.c_int * max(len(sets), 1))(*[int(h.shape[0]) for h in sets])
             sof = (ctypes.c_int * B)(*[int(j) for j in (set_of_utt if hw_sets is not None else [0] * B)])
-            _check(self._lib, getattr(self._lib, "pfhip_offline_forward_detail" + sfx)(
-                self._h, ptrs, lens, B, int(sample_rate) if sample_rate is not None else 0, sptr, sn, len(sets), sof, ctypes.byref(out),
-                ctypes.byref(det)))
+            args = [self._h, ptrs, lens, B, int(sample_rate) if sample_rate is not None else 0, sptr, sn, len(sets), sof, ctypes.byref(out)]
+            if bias_sets is None:
+                _check(self._lib, getattr(self._lib, "pfhip_offline_forward_detail" + sfx)(*args, ctypes.byref(det)))
+            else:
+                i32p, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+                bias_sets = list(bias_sets)
+                bsets = (_BiasOpts * max(len(bias_sets), 1))(*[_BiasOpts(int(w), int(bm), int(n), g.handle if g is not None else None)
+                                                               for w, bm, n, g in bias_sets])
+                set_of = [0] * B if set_of is None else [int(j) for j in set_of]
+                if len(set_of) != B:
+                    raise PfhipError("set_of: one entry per utterance")
+                stride = max([int(bias_sets[j][2]) for j in set_of if 0 <= j < len(bias_sets)] + [1])
+                bmt = max_tokens if bias_max_tokens is None else int(bias_max_tokens)
+                b_nhyp = np.full(B, -7, np.int32)
+                b_ids = np.full((B, stride, max(bmt, 1)), -1, np.int32)
+                b_ntok = np.full((B, stride), -7, np.int32)
+                b_score, b_am, b_ctx = (np.full((B, stride), np.nan, np.float32) for _ in range(3))
+                bout = _BiasOut(b_nhyp.ctypes.data_as(i32p), b_ids.ctypes.data_as(i32p), b_ntok.ctypes.data_as(i32p), b_score.ctypes.data_as(fp),
+                                b_am.ctypes.data_as(fp), b_ctx.ctypes.data_as(fp), bmt)
+                bias = dict(n_hyp=b_nhyp, ids=b_ids, n_tokens=b_ntok, score=b_score, am_score=b_am, ctx_score=b_ctx)
+                try:
+                    _check(self._lib, getattr(self._lib, "pfhip_offline_forward_bias" + sfx)(
+                        *args, ctypes.byref(det) if (nbest is not None or want_fire_frames) else None, bsets, len(bias_sets),
+                        (ctypes.c_int32 * B)(*set_of), ctypes.byref(bout)))
+                except PfhipError as e:
+                    e.bias = bias                    # PFHIP_ERR_CAPACITY: n_hyp, n_tokens and the scores were written all the same
+                    raise
         elif nbest is not None:
             if sample_rate is not None or (hw_sets is not None and (hw_emb is not None or set_of_utt is None or len(set_of_utt) != B)):
                 raise PfhipError("nbest excludes sample_rate; hw_sets needs set_of_utt [batch] and excludes hw_emb")
@@ -728,7 +776,15 @@ class ParaformerHip:
             res["nbest_ids"], res["nbest_logp"] = nb_ids, nb_logp
         if want_fire_frames:
             res["fire_frame"] = fire
+        if bias_sets is not None:
+            res["bias"] = bias
+            res["hyps"] = [[(b_ids[b, j, :b_ntok[b, j]].copy(), float(b_score[b, j]), float(b_am[b, j]), float(b_ctx[b, j]))
+                            for j in range(int(b_nhyp[b]))] for b in range(B)]
         return res
+
+    def forward_bias(self, din: Sequence[np.ndarray], bias_sets, set_of=None, **kw):
+        """forward_ids(din, bias_sets=bias_sets, set_of=set_of, ...): the forward plus the hotword-biased beam search."""
+        return self.forward_ids(din, bias_sets=bias_sets, set_of=set_of, **kw)
 
     def Forward(self, din, len_=None, input_finished=True, hw_emb=None, decoder_handle=None, batch_in=1):
         """Same contract as Model::Forward: returns batch_in strings; an utterance that yields no

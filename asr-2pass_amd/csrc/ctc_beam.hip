@@ -20,6 +20,7 @@
 // NaN or below -FLT_MAX counts as -FLT_MAX, a NaN total ranks as -inf: whatever the rows hold, ranks stay unique, every beam slot
 // that is read was written, and every index stays inside its buffer.  Graph indices are the host builder's (ctx_graph.cpp).
 // The final walk from each surviving node to the root writes the ids; it reads nodes other threads wrote, behind a barrier.
+#include "ctx_step.h"
 #include "kernels.h"
 #include "launch_common.h"
 
@@ -42,25 +43,6 @@ __device__ __forceinline__ float log_add(float x, float y) {
   if (y <= -FLT_MAX) return x;
   const float m = fmaxf(x, y);
   return logf(expf(x - m) + expf(y - m)) + m;
-}
-
-// GetNextState (context_graph.cpp:95-118): the arc of `state` with label tok, else the state's escape weight and state 0
-__device__ __forceinline__ int ctx_step(const CtxGraphDev& g, int state, int tok, float* w) {
-  state = min(max(state, 0), g.n_states - 1);
-  int lo = g.arc_begin[state], hi = g.arc_begin[state + 1];
-  lo = min(max(lo, 0), g.n_arcs);
-  hi = min(max(hi, lo), g.n_arcs);
-  const int end = hi;
-  while (lo < hi) {                                                  // at most 31 trips
-    const int mid = lo + ((hi - lo) >> 1);
-    if (g.arc_label[mid] < tok) lo = mid + 1; else hi = mid;
-  }
-  if (lo < end && g.arc_label[lo] == tok) {
-    *w = g.arc_weight[lo];
-    return min(max(g.arc_next[lo], 0), g.n_states - 1);
-  }
-  *w = g.escape[state];
-  return 0;
 }
 
 struct BeamState {                               // one buffer of the beam

@@ -119,6 +119,65 @@ pfhip_status ts_head_locked(pfhip_model* m, hipStream_t s, bool stepwise_only = 
   return PFHIP_OK;
 }
 
+// ---- pfhip_offline_forward_bias: the search over the candidates the top-k head just left (nar_beam.hip) --------------------------
+// Rows: utterance b's token rows [tok_off[b], + min(n_fires[b], token_num[b])) of nb_ids / nb_logp [ML][nbest_k], all three read from
+// the device's own arrays (dmeta, and the CIF's counts).  Descriptors, the graph table and the graphs' images go to the front of the
+// search's workspace in one copy from pinned staging.  Results: bias_res, laid out as internal.h says.
+size_t bias_words(int B, int ns, int mt) { return (size_t)B + (size_t)B * ns * (4 + (size_t)mt); }
+pfhip_status bias_search_locked(pfhip_model* m, hipStream_t s) {
+  const NarBias& nb = *m->bias;
+  const int B = m->B, ML = m->ML, k = m->nbest_k, ns = nb.nbest_stride, mt = m->maxL;
+  const size_t front = pfhip::beam_front_bytes(B, nb.graphs, nb.n_graphs), nodes = pfhip::nbest_ctx_beam_workspace_bytes(ML, B, nb.beam_stride);
+  const size_t words = bias_words(B, ns, mt);
+  HIP_TRY(m->bias_ws.ensure(front + nodes));
+  HIP_TRY(m->bias_stage.ensure(front));
+  HIP_TRY(m->bias_res.ensure(words * 4));
+  HIP_TRY(m->h_bias.ensure(words * 4));
+  m->bias_mt = mt;
+  char* const dev = static_cast<char*>(m->bias_ws.p);
+  char* const stage = static_cast<char*>(m->bias_stage.p);
+  std::memset(stage, 0, front);
+  pfhip::beam_front_fill(stage, dev, nb.utt, B, nb.graphs, nb.n_graphs);
+  HIP_TRY(hipMemcpyAsync(dev, stage, front, hipMemcpyHostToDevice, s));
+  const size_t bn = (size_t)B * ns;
+  int32_t *r_nhyp = m->bias_res.i(), *r_ntok = r_nhyp + B, *r_ids = r_ntok + bn;
+  float *r_score = reinterpret_cast<float*>(r_ids + bn * mt), *r_am = r_score + bn, *r_ctx = r_am + bn;
+  Scope sc(m, s, K_HEAD, 0, 8.0 * ML * k + 8.0 * ML * nb.beam_stride);
+  if (!pfhip::launch_nbest_ctx_beam(m->nb_ids.i(), m->nb_logp.f(), k, ML, m->m_tok_off, m->m_tok_len, m->counts.i() + B, B, m->weights->cfg.vocab,
+                                    reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                    reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), nb.n_graphs,
+                                    nb.beam_stride, ns, mt, r_nhyp, r_ids, r_ntok, r_score, r_am, r_ctx, dev + front, nodes, s))
+    return fail(PFHIP_ERR_ARG, "hotword beam search refused its arguments");
+  return PFHIP_OK;
+}
+// after the synchronise behind the copy of bias_res: the caller's buffers.  n_hyp, the lengths and the scores also where max_tokens
+// turns out too small.
+pfhip_status scatter_bias(const pfhip_model* m) {
+  pfhip_bias_out* bo = m->bias->out;
+  const int B = m->B, ns = m->bias->nbest_stride, mt = m->bias_mt;
+  const size_t bn = (size_t)B * ns;
+  const int32_t *h_nhyp = m->h_bias.i(), *h_ntok = h_nhyp + B, *h_ids = h_ntok + bn;
+  const float *h_score = reinterpret_cast<const float*>(h_ids + bn * mt), *h_am = h_score + bn, *h_ctx = h_am + bn;
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    bo->n_hyp[b] = h_nhyp[b];
+    for (int j = 0; j < ns; ++j) {
+      const size_t o = (size_t)b * ns + j;
+      bo->n_tokens[o] = h_ntok[o];
+      if (bo->score) bo->score[o] = h_score[o];
+      if (bo->am_score) bo->am_score[o] = h_am[o];
+      if (bo->ctx_score) bo->ctx_score[o] = h_ctx[o];
+      if (j < h_nhyp[b]) longest = std::max(longest, h_ntok[o]);
+    }
+  }
+  if (bo->max_tokens < longest) return fail(PFHIP_ERR_CAPACITY, "bias: max_tokens smaller than the longest hypothesis (n_tokens holds the lengths)");
+  for (size_t o = 0; o < bn; ++o) {
+    const int n = std::min(std::max(h_ntok[o], 0), mt);
+    if (n) std::memcpy(bo->ids + o * bo->max_tokens, h_ids + o * mt, (size_t)n * 4);
+  }
+  return PFHIP_OK;
+}
+
 // the range flag of the forward crosses to the host with the results (one 4-byte copy in front of the sync that is there anyway)
 pfhip_status read_range_flag(pfhip_model* m, hipStream_t s, bool sync) {
   m->range_hit = 0;
@@ -191,6 +250,7 @@ pfhip_status fetch_once(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfh
   }
   NbestStage nbs;
   if (nk) { const pfhip_status ns = nbs.start(m, s); if (ns) return ns; }
+  if (m->bias) HIP_TRY(hipMemcpyAsync(m->h_bias.p, m->bias_res.p, bias_words(B, m->bias->nbest_stride, m->bias_mt) * 4, hipMemcpyDeviceToHost, s));
   const int V = m->weights->cfg.vocab;
   if (out->logp) {
     for (int b = 0; b < B; ++b)
@@ -441,11 +501,15 @@ pfhip_status head_locked(pfhip_model* m, hipStream_t s, bool want_logp) {
     const int k = m->nbest_k;
     HIP_TRY(m->nb_ids.ensure((size_t)m->ML * k * 4));
     HIP_TRY(m->nb_logp.ensure((size_t)m->ML * k * 4));
-    Scope sc(m, s, K_HEAD, 0, 4.0 * m->ML * V * (want_logp ? 3 : 2));
-    if (!pfhip::launch_logsoftmax_topk(m->logits.f(), m->weights->vocab_pad, m->ML, V, k, want_logp ? m->logp.f() : nullptr,
-                                       static_cast<int32_t*>(m->ids.p), static_cast<int32_t*>(m->nb_ids.p), m->nb_logp.f(), s,
-                                       m->d_range_flag))
-      return fail(PFHIP_ERR_ARG, "nbest k outside 1..8 or larger than the vocabulary");
+    {
+      Scope sc(m, s, K_HEAD, 0, 4.0 * m->ML * V * (want_logp ? 3 : 2));
+      if (!pfhip::launch_logsoftmax_topk(m->logits.f(), m->weights->vocab_pad, m->ML, V, k, want_logp ? m->logp.f() : nullptr,
+                                         static_cast<int32_t*>(m->ids.p), static_cast<int32_t*>(m->nb_ids.p), m->nb_logp.f(), s,
+                                         m->d_range_flag))
+        return fail(PFHIP_ERR_ARG, "nbest k outside 1..8 or larger than the vocabulary");
+    }
+    // behind the closed bracket of the top-k launch: the search has its own, so the head class counts each kernel once
+    if (m->bias) { const pfhip_status bs = bias_search_locked(m, s); if (bs) return bs; }
   } else {
     Scope sc(m, s, K_HEAD, 0, 4.0 * m->ML * V * (want_logp ? 3 : 2));
     pfhip::launch_logsoftmax_argmax(m->logits.f(), m->weights->vocab_pad, m->ML, V, want_logp ? m->logp.f() : nullptr,
@@ -466,7 +530,9 @@ pfhip_status head_locked(pfhip_model* m, hipStream_t s, bool want_logp) {
 // comes back belongs to the forward whose token_ids come back
 pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const pfhip_detail* dt) {
   pfhip_status st = fetch_once(m, out, s, dt);
-  if (st || !m->range_hit || m->exact_rerun || m->weights->always_exact || !m->last_pcm.p || m->last_feats_only) return st;
+  const bool bias = m->bias && m->ML > 0;                 // (no token row at all: the caller's buffers keep "no hypothesis")
+  if (st || !m->range_hit || m->exact_rerun || m->weights->always_exact || !m->last_pcm.p || m->last_feats_only)
+    return st || !bias ? st : scatter_bias(m);
   ++m->range_fallbacks;
   m->exact_rerun = true;
   const std::vector<int64_t> off = m->last_off;
@@ -475,6 +541,7 @@ pfhip_status fetch_locked(pfhip_model* m, pfhip_out* out, hipStream_t s, const p
   if (!st) st = head_locked(m, s, out->logp != nullptr);
   if (!st) st = fetch_once(m, out, s, dt);
   m->exact_rerun = false;
+  if (!st && m->bias && m->ML > 0) st = scatter_bias(m);
   return st;
 }
 

@@ -207,6 +207,8 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
   // ids ARE there to align.  Any other decoder handle keeps what it had for this model: it is not passed on.
   funasr::CtcPrefixDecoderHip* search = svs ? dynamic_cast<funasr::CtcPrefixDecoderHip*>(static_cast<funasr::Decoder*>(dec_handle)) : nullptr;
   const bool svs_stamps = svs && os->svs_ctc_stamps.load() && (!dec_handle || search);
+  // a Paraformer is handed such a handle too (hotwords for any Paraformer); any other decoder handle is not passed on, as before
+  funasr::Decoder* const bias_dec = svs ? nullptr : dynamic_cast<funasr::CtcPrefixDecoderHip*>(static_cast<funasr::Decoder*>(dec_handle));
   if (wav_format != "pcm" && wav_format != "PCM") return nullptr;      // the reference decodes other containers with ffmpeg
   // Audio::LoadPcmwav (audio.cpp:787-819); from here on samples, segments and stamps are at the model's rate (GetTimeLen
   // divides by dest_sample_rate, audio.cpp:254-257).
@@ -273,8 +275,8 @@ FUNASR_RESULT FunOfflineInferBuffer(FUNASR_HANDLE handle, const char* sz_buf, in
     const std::vector<std::string> msg_batch =
         svs ? (pcm16 ? svs->ForwardPcm16(buff16.data(), len.data(), true, svs_lang, svs_itn, search, (int)batch.size())
                      : svs->Forward(buff.data(), len.data(), true, svs_lang, svs_itn, search, (int)batch.size())) :
-        pcm16 ? os->asr.ForwardPcm16(buff16.data(), len.data(), true, hw_emb, nullptr, (int)batch.size(), same_rate ? 0 : sampling_rate)
-              : os->asr.Forward(buff.data(), len.data(), true, hw_emb, nullptr, (int)batch.size());
+        pcm16 ? os->asr.ForwardPcm16(buff16.data(), len.data(), true, hw_emb, bias_dec, (int)batch.size(), same_rate ? 0 : sampling_rate)
+              : os->asr.Forward(buff.data(), len.data(), true, hw_emb, bias_dec, (int)batch.size());
     for (size_t k = 0; k < batch.size(); ++k, ++msg_idx) {        // funasrruntime.cpp:270-279
       const int seg = index_vector[msg_idx];
       msgs[seg] = msg_batch[k];
@@ -458,8 +460,11 @@ FUNASR_DEC_HANDLE FunASRCtcDecoderInit(FUNASR_HANDLE handle, float glob_beam, fl
   if (!handle) return nullptr;
   funasr::SenseVoiceSmallHip* svs = asr_type == ASR_OFFLINE ? static_cast<OfflineStreamHip*>(handle)->svs.get()
                                                             : static_cast<TpassStreamHip*>(handle)->svs.get();
-  if (!svs) return nullptr;                                          // a Paraformer handle has no CTC rows to search
-  return static_cast<funasr::Decoder*>(new funasr::CtcPrefixDecoderHip(svs->GetHipVocab(), glob_beam, lat_beam));
+  // A Paraformer stream gets one on its own vocabulary: it has no CTC rows, but with hotwords loaded ParaformerHip runs the biased
+  // search over its head's candidates (an extension; the reference creates the decoder and then never looks at it, paraformer.cpp:563-579)
+  funasr::HipVocab* vocab = svs ? svs->GetHipVocab()
+                                : (asr_type == ASR_OFFLINE ? static_cast<OfflineStreamHip*>(handle)->asr : static_cast<TpassStreamHip*>(handle)->asr).GetHipVocab();
+  return static_cast<funasr::Decoder*>(new funasr::CtcPrefixDecoderHip(vocab, glob_beam, lat_beam));
 }
 static funasr::CtcPrefixDecoderHip* SearchOf(FUNASR_DEC_HANDLE dec) {
   return dynamic_cast<funasr::CtcPrefixDecoderHip*>(static_cast<funasr::Decoder*>(dec));
@@ -556,11 +561,14 @@ FUNASR_RESULT FunTpassInferBuffer(FUNASR_HANDLE handle, FUNASR_HANDLE online_han
       res->tpass_msg = text;                     // no punctuation and no ITN for this model (:609-631)
       continue;
     }
+    // a CtcPrefixDecoderHip goes through to the second pass (hotwords for any Paraformer); any other decoder handle does not, as before
+    funasr::Decoder* const bias_dec = dynamic_cast<funasr::CtcPrefixDecoderHip*>(static_cast<funasr::Decoder*>(dec_handle));
     const std::vector<std::string> msgs = frame.pcm16.size() == frame.data.size() && !frame.data.empty()
-                                              ? ts->asr.ForwardPcm16(buff16, len, true, hw_emb, nullptr, 1)
-                                              : ts->asr.Forward(buff, len, true, hw_emb, nullptr, 1);
+                                              ? ts->asr.ForwardPcm16(buff16, len, true, hw_emb, bias_dec, 1)
+                                              : ts->asr.Forward(buff, len, true, hw_emb, bias_dec, 1);
     std::string msg = msgs.empty() ? "" : msgs[0];
     if (msg.empty()) continue;
+    if (bias_dec) res->seg_ids.push_back(ts->asr.LastTokenIds()[0]);            // what FunASRGetSegmentIds returns for such a call
     if (!ts->asr.LastTokenConfidence().empty())                                     // FunTpassSetNbest: as FunOfflineInferBuffer
       res->confidence.insert(res->confidence.end(), ts->asr.LastTokenConfidence()[0].begin(), ts->asr.LastTokenConfidence()[0].end());
     const size_t bar = msg.find(" | ");

@@ -147,13 +147,18 @@ void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode);
 void FunOfflineSetCtcStamps(FUNASR_HANDLE handle, int on);
 // The per-connection decoder of a server without an LM (FunASRWfstDecoderInit's CtcPrefixDecoder branch, funasrruntime.cpp:836-894;
 // FunWfstDecoderLoadHwsRes / UnloadHwsRes / FunASRWfstDecoderUninit): FunASRCtcDecoderInit makes a CtcPrefixDecoderHip
-// (ctc_prefix_decoder_hip.h) on the vocabulary of the handle's SenseVoice model — nullptr for a Paraformer handle; asr_type says
+// (ctc_prefix_decoder_hip.h) on the vocabulary of the handle's SenseVoice model, or of its Paraformer; asr_type says
 // whether `handle` is a FunOfflineInit or a FunTpassInit handle.  Passed as dec_handle to FunOfflineInferBuffer /
 // FunTpassInferBuffer it selects the CTC prefix beam search ON THE DEVICE, with first beam (int)glob_beam, second beam
 // (int)lat_beam (1..16 each) and the hotwords loaded into it; the text is the search's best hypothesis, and with
 // FunOfflineSetCtcStamps / FunTpassSetCtcStamps on, FunASRGetStamp holds the spans of ITS tokens.  Any other dec_handle is, for a
 // SenseVoice model, not passed on (as before).  FunCtcDecoderLoadHwsRes returns the hotwords that entered the graph (one with a
 // piece outside the vocabulary is skipped); an empty map changes nothing.
+// A Paraformer (offline, or the 2-pass second pass) is handed such a handle too — an extension: the reference creates the decoder
+// and, without an LM, never looks at it (paraformer.cpp:563-579).  With hotwords loaded ParaformerHip runs
+// pfhip_offline_forward_bias (width min((int)glob_beam, 8), beam min((int)lat_beam, 16), n best 1): text, FunASRGetSegmentIds, stamps
+// and confidences are those of the search's best hypothesis, one token per row of the same forward.  With no hotword loaded, with an
+// LM, or with any other dec_handle the call is exactly what it is without a handle.
 FUNASR_DEC_HANDLE FunASRCtcDecoderInit(FUNASR_HANDLE handle, float glob_beam, float lat_beam, ASR_TYPE asr_type = ASR_OFFLINE);
 int FunCtcDecoderLoadHwsRes(FUNASR_DEC_HANDLE dec_handle, int inc_bias, std::unordered_map<std::string, int>& hws_map);
 void FunCtcDecoderUnloadHwsRes(FUNASR_DEC_HANDLE dec_handle);

@@ -1,6 +1,10 @@
 // Harness over the handle-API mirror (funasrruntime_hip.h) with the shape of the reference's offline client
 // (onnxruntime/bin/funasr-onnx-offline.cpp: FunOfflineInit -> FunOfflineInferBuffer per file -> FunASRGetResult):
 //   offline_infer <model_dir> <vad_dir|-> <pcm_s16_file> [batch=32] [threads=1] [repeat=1] [punc_dir|-] [audio_fs] [nbest=0] [cif_stamps=0]
+//                 [glob_beam lat_beam [hotword score]...]
+// With the two beams: one more pass through a decoder handle (FunASRCtcDecoderInit -> FunOfflineInferBuffer(dec_handle)) before any
+// hotword is loaded ("dec_seg ...", "dec_text", "dec_stamp"), then with the hotwords (FunCtcDecoderLoadHwsRes: "hw_loaded <n>",
+// "hw_seg ...", "hw_text", "hw_stamp", "hw_confidence ..."); nbest and cif_stamps, where given, stay on for both.
 // Prints one line per VAD segment, time order: "seg <start_sample> <end_sample> : <ids...>", then timing; with threads > 1
 // every thread transcribes the same buffer through the shared handle (the server's decoder threads).
 #include <atomic>
@@ -9,6 +13,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "funasrruntime_hip.h"
@@ -58,6 +63,33 @@ int main(int argc, char** argv) {
       if (!q) { std::fprintf(stderr, "inference failed\n"); return 1; }
       std::printf("cif_text %s\ncif_stamp %s\n", FunASRGetResult(q, 0), FunASRGetStamp(q));
       FunASRFreeResult(q);
+      FunOfflineSetCifStamps(h, 0);
+    }
+    if (argc > 12) {
+      if (nbest > 0) FunOfflineSetNbest(h, nbest);
+      if (cif_stamps > 0) FunOfflineSetCifStamps(h, cif_stamps);
+      FUNASR_DEC_HANDLE dec = FunASRCtcDecoderInit(h, (float)std::atof(argv[11]), (float)std::atof(argv[12]), ASR_OFFLINE);
+      std::printf("dec_handle %d\n", dec ? 1 : 0);
+      std::unordered_map<std::string, int> hws;
+      for (int a = 13; a + 1 < argc; a += 2) hws[argv[a]] = std::atoi(argv[a + 1]);
+      for (const char* tag : {"dec", "hw"}) {
+        if (std::string(tag) == "hw") std::printf("hw_loaded %d\n", FunCtcDecoderLoadHwsRes(dec, 0, hws));
+        FUNASR_RESULT q = FunOfflineInferBuffer(h, buf.data(), (int)buf.size(), RASR_NONE, nullptr, no_hw, audio_fs, "pcm", true, 800, 60000, dec);
+        if (!q) { std::fprintf(stderr, "inference failed\n"); return 1; }
+        const auto& qsegs = FunASRGetSegments(q);
+        const auto& qids = FunASRGetSegmentIds(q);
+        for (size_t i = 0; i < qsegs.size(); ++i) {
+          std::printf("%s_seg %d %d :", tag, qsegs[i].first, qsegs[i].second);
+          for (int id : qids[i]) std::printf(" %d", id);
+          std::printf("\n");
+        }
+        std::printf("%s_text %s\n%s_stamp %s\n%s_confidence", tag, FunASRGetResult(q, 0), tag, FunASRGetStamp(q), tag);
+        for (float c : FunASRGetTokenConfidence(q)) std::printf(" %.9g", c);
+        std::printf("\n");
+        FunASRFreeResult(q);
+      }
+      FunCtcDecoderUninit(dec);
+      FunOfflineSetNbest(h, 0);
       FunOfflineSetCifStamps(h, 0);
     }
     const std::string want_text = FunASRGetResult(r, 0), want_stamp = FunASRGetStamp(r);

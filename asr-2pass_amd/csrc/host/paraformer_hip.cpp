@@ -1,7 +1,11 @@
 #include "paraformer_hip.h"
+#ifndef PFHIP_WITH_FUNASR
+#include "ctc_prefix_decoder_hip.h"
+#endif
 
 #include "postprocess.h"
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -319,10 +323,36 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
   }
   // SetNbest: the same forward plus the k best columns of every token row (this caller's one hotword set as set 0)
   const int nk = nbest_k_;
-  std::vector<int32_t> nb_ids((size_t)(nk ? batch_in : 0) * max_tokens * nk);
+  // Hotwords for any Paraformer (an extension; pfhip_offline_forward_bias): no LM, the handle that came with the call is a
+  // CtcPrefixDecoderHip (FunASRCtcDecoderInit), it has hotwords loaded, and the model is no multi-device group.  Anything else —
+  // a decoder without hotwords, another decoder class, an LM — takes exactly the path it took before.
+  const pfhip_ctx_graph* bias_graph = nullptr;
+  pfhip_bias_opts bias_opts{1, 1, 1, nullptr};
+#ifndef PFHIP_WITH_FUNASR
+  if (!has_lm_ && wfst_decoder && pfhip_group_size(handle_) <= 1)
+    if (const CtcPrefixDecoderHip* bd = dynamic_cast<CtcPrefixDecoderHip*>(static_cast<Decoder*>(wfst_decoder))) {
+      bias_graph = bd->Graph();
+      bias_opts = pfhip_bias_opts{std::max(1, std::min({bd->FirstBeam(), 8, V})), std::max(1, std::min(bd->SecondBeam(), 16)), 1, bias_graph};
+    }
+#endif
+  // with the search on, a caller who asked for candidates gets rows wide enough to hold the chosen token: its confidence is read there
+  const int kk = bias_graph && nk ? std::max(nk, bias_opts.width) : nk;
+  std::vector<int32_t> nb_ids((size_t)(kk ? batch_in : 0) * max_tokens * kk);
   std::vector<float> nb_logp(nb_ids.size());
+  std::vector<int32_t> b_nhyp, b_ntok, b_ids;
   pfhip_status st;
-  if (cif_ts || (nk && sample_rate)) {            // one call carries the candidates, the fire frames and the rate of the audio
+  if (bias_graph) {                               // the detail call plus the search, one set for all utterances of this caller
+    b_nhyp.assign(batch_in, 0); b_ntok.assign(batch_in, 0); b_ids.assign((size_t)batch_in * max_tokens, 0);
+    pfhip_bias_out bout{b_nhyp.data(), b_ids.data(), b_ntok.data(), nullptr, nullptr, nullptr, max_tokens};
+    const pfhip_detail det{kk, kk ? nb_ids.data() : nullptr, kk ? nb_logp.data() : nullptr, cif_ts ? fire.data() : nullptr};
+    const float* sets[1] = {hw.data()};
+    const int set_rows[1] = {n_hw};
+    const std::vector<int> set_of_utt((size_t)batch_in, 0);
+    st = s16 ? pfhip_offline_forward_bias_s16(handle_, din16, len, batch_in, sample_rate, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(), &out,
+                                              &det, &bias_opts, 1, nullptr, &bout)
+             : pfhip_offline_forward_bias(handle_, din, len, batch_in, sample_rate, sets, set_rows, n_hw ? 1 : 0, set_of_utt.data(), &out, &det,
+                                          &bias_opts, 1, nullptr, &bout);
+  } else if (cif_ts || (nk && sample_rate)) {            // one call carries the candidates, the fire frames and the rate of the audio
     const pfhip_detail det{nk, nk ? nb_ids.data() : nullptr, nk ? nb_logp.data() : nullptr, cif_ts ? fire.data() : nullptr};
     const float* sets[1] = {hw.data()};
     const int set_rows[1] = {n_hw};
@@ -351,13 +381,22 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
   }
   for (int i = 0; i < batch_in; ++i) {
     const int n = tn[i] < nf[i] ? tn[i] : nf[i];
-    tl_last_ids[i].assign(ids.begin() + (size_t)i * max_tokens, ids.begin() + (size_t)i * max_tokens + n);
+    // the search's best hypothesis takes the place of the greedy ids: one token per row, so n, the fire frames and the head's traces
+    // stay those of the same rows
+    const bool biased = bias_graph && b_nhyp[i] > 0 && b_ntok[i] == n;
+    const int32_t* const best = biased ? b_ids.data() + (size_t)i * max_tokens : ids.data() + (size_t)i * max_tokens;
+    tl_last_ids[i].assign(best, best + n);
     if (nk) {
-      const size_t row0 = (size_t)i * max_tokens * nk;
-      tl_last_nbest_ids[i].assign(nb_ids.begin() + row0, nb_ids.begin() + row0 + (size_t)n * nk);
-      tl_last_nbest_logp[i].assign(nb_logp.begin() + row0, nb_logp.begin() + row0 + (size_t)n * nk);
-      for (int t = 0; t < n; ++t)
-        if (InText(tl_last_ids[i][t])) tl_last_conf[i].push_back(std::exp(nb_logp[row0 + (size_t)t * nk]));
+      const size_t row0 = (size_t)i * max_tokens * kk;
+      for (int t = 0; t < n; ++t) {
+        const size_t r = row0 + (size_t)t * kk;
+        tl_last_nbest_ids[i].insert(tl_last_nbest_ids[i].end(), nb_ids.begin() + r, nb_ids.begin() + r + nk);
+        tl_last_nbest_logp[i].insert(tl_last_nbest_logp[i].end(), nb_logp.begin() + r, nb_logp.begin() + r + nk);
+        if (!InText(tl_last_ids[i][t])) continue;
+        int c = 0;                                  // the chosen candidate's column: 0 without the search
+        while (biased && c + 1 < kk && nb_ids[r + c] != tl_last_ids[i][t]) ++c;
+        tl_last_conf[i].push_back(std::exp(nb_logp[r + c]));
+      }
     }
     if (decoder && fr[i] > 0) {                   // no feature frame: "" before any decoding (paraformer.cpp:477-480)
       // BeamSearch + FinalizeDecode (paraformer.cpp:410-419, 563-579; per item as paraformer-torch.cpp:431-466): `n` rows of V

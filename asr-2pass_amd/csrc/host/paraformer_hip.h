@@ -193,6 +193,7 @@ class ParaformerHip : public ParaformerHipBase, public OnlineModelOwner
   Vocab* GetLmVocab() override { return lm_vocab; }
 #endif
   bool HasLm() const { return has_lm_; }
+  HipVocab* GetHipVocab() const { return vocab; }      // tokens.json, or null: what a CtcPrefixDecoderHip of this model is built on
 
   // token ids of the last Forward, per utterance (what GreedySearch computed, paraformer.cpp:386-395)
   // (of the calling thread: Forward is re-entrant)

@@ -9,9 +9,14 @@
 // An offline_model_dir whose name contains "SenseVoiceSmall" makes the second pass a SenseVoiceSmallHip (tpass-stream.cpp:44-50); three
 // more arguments then apply: [svs_lang=auto] [svs_itn=1] [ctc_stamps=0] (FunTpassInferBuffer's trailing arguments, FunTpassSetCtcStamps),
 // and every line gets a field " | tpass_ids <second-pass ids of the segments closed in the call>".
+// Three or more further arguments, [glob_beam lat_beam [hotword score]...] behind those (use "auto 1 0" for the three before them): the
+// connection gets a decoder handle (FunASRCtcDecoderInit, FunCtcDecoderLoadHwsRes) that every FunTpassInferBuffer call passes on, and
+// every line gets the " | tpass_ids" field.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "funasrruntime_hip.h"
@@ -39,6 +44,13 @@ int main(int argc, char** argv) {
   if (h && svs && argc > 13) FunTpassSetCtcStamps(h, std::atoi(argv[13]));
   FUNASR_HANDLE oh = FunTpassOnlineInit(h, {5, 10, 5});
   if (!h || !oh) return 1;
+  FUNASR_DEC_HANDLE dec = nullptr;
+  if (argc > 15) {
+    dec = FunASRCtcDecoderInit(h, (float)std::atof(argv[14]), (float)std::atof(argv[15]), ASR_TWO_PASS);
+    std::unordered_map<std::string, int> hws;
+    for (int a = 16; a + 1 < argc; a += 2) hws[argv[a]] = std::atoi(argv[a + 1]);
+    std::printf("dec_handle %d hw_loaded %d\n", dec ? 1 : 0, FunCtcDecoderLoadHwsRes(dec, 0, hws));
+  }
   std::vector<std::vector<std::string>> punc_cache(2);
   const int n_bytes = (int)buf.size(), step_bytes = step * 2;
   int j = 0;
@@ -46,7 +58,7 @@ int main(int argc, char** argv) {
     const int nb = std::min(step_bytes, n_bytes - off);
     const bool last = off + step_bytes >= n_bytes;
     FUNASR_RESULT r = FunTpassInferBuffer(h, oh, buf.data() + off, nb, punc_cache, last, audio_fs, "pcm", mode, {{0.0f}}, true, 800, 60000,
-                                          nullptr, svs_lang, svs_itn);
+                                          dec, svs_lang, svs_itn);
     if (!r) { std::fprintf(stderr, "inference failed\n"); return 1; }
     std::printf("call %d | online %s | tpass %s | stamp %s", j, FunASRGetResult(r, 0), FunASRGetTpassResult(r, 0), FunASRGetStamp(r));
     if (nbest > 0) {
@@ -57,13 +69,14 @@ int main(int argc, char** argv) {
       std::printf(" | tpass_conf");
       for (float c : FunASRGetTokenConfidence(r)) std::printf(" %.9g", c);
     }
-    if (svs) {
+    if (svs || dec) {
       std::printf(" | tpass_ids");
       for (const std::vector<int>& seg : FunASRGetSegmentIds(r)) for (int id : seg) std::printf(" %d", id);
     }
     std::printf("\n");
     FunASRFreeResult(r);
   }
+  if (dec) FunCtcDecoderUninit(dec);
   FunTpassOnlineUninit(oh);
   FunTpassUninit(h);
   return 0;

@@ -163,6 +163,7 @@ using pfhip_impl::ProfRec;
 
 struct BatchReq;
 struct StreamReq;
+namespace pfhip_impl { struct NarBias; }
 
 namespace pfhip_impl {
 // The hotword bank of one device (on the weight owner; its contexts share it as they share the weights): the bias decoder's
@@ -260,6 +261,15 @@ struct pfhip_model {
   // value buffers the head fills, the k the device-pointer form asks for (pfhip_set_nbest) and the max_tokens of its last fetch
   int nbest_k = 0, nbest_enqueue_k = 0, nbest_fetch_max_tokens = 0;
   Buf nb_ids, nb_logp;
+  // pfhip_offline_forward_bias: the search of the forward being run over its candidates (null: none; set for the length of the call
+  // by forward_direct, so a range-guard re-run reads it again).  nbest_k is then at least the largest width in use.  bias_ws: the
+  // front block (beam_front.h) and the trie nodes; bias_stage: the pinned staging of the front block's one copy; bias_res / h_bias:
+  // the results on the device and on the host (n_hyp [B] | n_tokens [B][nb] | ids [B][nb][bias_mt] | score, am, ctx [B][nb]), which
+  // cross with the forward's other results in front of fetch_once's synchronise
+  const pfhip_impl::NarBias* bias = nullptr;
+  Buf bias_ws, bias_res;
+  PinBuf bias_stage, h_bias;
+  int bias_mt = 0;
   // Fire frames (cif.hip, the sibling kernel): whether the forward being run records them (a range-guard re-run reads it again), whether
   // the last forward did, and what the device-pointer forms ask for (pfhip_set_fire_frames; read on the handle the caller holds).  They
   // sit behind the token counts in `counts` — [2B | M + B], laid out like the CIF's staging rows: fire nf of utterance b at

@@ -386,6 +386,23 @@ bool launch_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_log
                                   int B, int V, int blank, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int sb_max,
                                   int nbest_max, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
                                   float* ctc_score, float* ctx_score, void* workspace, size_t workspace_bytes, hipStream_t s);
+// ---- hotword-biased beam search over a non-autoregressive head's candidates (nar_beam.hip) --------------------------------------
+// One workgroup per utterance walks rows [row_off[b], + len[b]) (device arrays) of cand_ids / cand_logp [rows][k] in order, one token
+// per row (include/pfhip_ops.h states the recurrence and the tie rule).  Workgroup b reads utt[b] (a DEVICE array [B]) with
+// first_beam as the WIDTH (the row's first `width` columns are its candidates), second_beam as the beam, nbest, and graph an index
+// into graphs (a DEVICE table [n_graphs]; -1: none): 1 <= width <= k <= kNarWidthMax, 1 <= nbest <= beam <= kBeamMax.  Trie nodes
+// sit at the utterance's rows with stride beam_stride (workspace: nbest_ctx_beam_workspace_bytes(rows, B, beam_stride); the row
+// ranges must not overlap); outputs are [B][nbest_stride]([max_tokens]).  A descriptor outside the strides (width 0 included: "no
+// search") is answered as n_hyp 0 by the kernel; nbest_ctx_beam_check is the host's check of a HOST copy of the descriptors
+// (allow_none: width 0 passes unread) and gives the two maxima (at least 1).  len_cap (a DEVICE array [B], or null): utterance b
+// walks min(len[b], len_cap[b]) rows.  false: nothing launched.
+constexpr int kNarWidthMax = 8;
+size_t nbest_ctx_beam_workspace_bytes(long long rows, int B, int beam_stride);
+bool nbest_ctx_beam_check(const BeamUtt* utt, int B, int k, int n_graphs, bool allow_none, int* beam_max, int* nbest_max);
+bool launch_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len,
+                           const int* len_cap, int B, int V, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int beam_stride, int nbest_stride,
+                           int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* am_score, float* ctx_score,
+                           void* workspace, size_t workspace_bytes, hipStream_t s);
 // The same head with the k best columns of every row (topk.hip; 1 <= k <= kTopkMax <= V): topk_ids / topk_logp [ML][k], larger logit
 // first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry of its column bit for bit.  The
 // log-sum-exp is formed with logp null as well.  false (nothing launched) when the arguments are outside that.

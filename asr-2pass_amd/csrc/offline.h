@@ -5,6 +5,12 @@
 namespace pfhip_impl {
 // hotword sets of a call: n_sets sets (emb[k]: [n[k], d]) and, per utterance, which one it attends to (of_utt == nullptr: all set 0)
 struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of_utt; };
+// pfhip_offline_forward_bias: per utterance the search's descriptor (first_beam = the width, 0: no search; graph: an index into
+// graphs), checked by the caller with nbest_ctx_beam_check, which also gave the strides; k: the head's candidate count, at least the
+// largest width; out: the caller's buffers
+struct NarBias {
+  const pfhip::BeamUtt* utt; const pfhip_ctx_graph* const* graphs; int n_graphs; int k, beam_stride, nbest_stride; pfhip_bias_out* out;
+};
 }  // namespace pfhip_impl
 
 // One caller in the cross-request queue of a handle (pfhip_model::bq; offline_api.cpp states the queue's rules).  A Paraformer handle
@@ -101,7 +107,7 @@ pfhip_status stage_pcm(pfhip_model* m, HostPcm pcm, const int* n_samples, int B,
 pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, int B, int fs_in, hipStream_t s,
                              std::vector<int64_t>& off, std::vector<int>& n_out);
 pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch,
-                            const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_detail* dt = nullptr);
+                            const HwSets& hw, pfhip_out* out, int fs_in = 0, const pfhip_detail* dt = nullptr, const NarBias* bias = nullptr);
 pfhip_model*& last_replica();       // the calling thread's tl_last_replica
 // the caller joins the handle's queue; `run` executes one packed forward for everybody taken.  The slot `me` led a batch on, or null
 pfhip_model* pool_submit(pfhip_model* head, BatchReq& me, void (*run)(pfhip_model*, const std::vector<BatchReq*>&));

@@ -1,5 +1,6 @@
 // The offline Paraformer entry points and the cross-request batching queue behind them.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <mutex>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "offline.h"
+#include "ctx_graph.h"
 
 #define g_err (pfhip_impl::last_error())
 
@@ -280,6 +282,72 @@ pfhip_status offline_forward_resident(pfhip_model* head, PcmView d_pcm, const in
   return st;
 }
 
+// pfhip_offline_forward_detail plus the hotword-biased search over the head's candidates (nar_beam.hip).  Served alone, past the
+// merge queue, on the least-loaded execution slot; every refusal comes before anything is staged.
+pfhip_status offline_forward_bias(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, int sample_rate,
+                                  const float* const* hw_emb, const int* n_hotwords, int n_hw_sets, const int* hw_set_of, pfhip_out* out,
+                                  const pfhip_detail* dt, const pfhip_bias_opts* sets, int n_sets, const int32_t* set_of, pfhip_bias_out* bo) {
+  g_err.clear();
+  if (is_svs(head)) return refuse_svs();
+  if (!head || !pcm.p || !n_samples || batch <= 0 || !out) return fail(PFHIP_ERR_ARG, "bad argument");
+  if (!head->replicas.empty()) return fail(PFHIP_ERR_UNSUPPORTED, "bias: not on a multi-device group");
+  if (!sets || n_sets < 1 || !bo || !bo->n_hyp || !bo->n_tokens || bo->max_tokens < 0 || (bo->max_tokens > 0 && !bo->ids))
+    return fail(PFHIP_ERR_ARG, "bias: sets and the n_hyp / ids / n_tokens buffers are needed");
+  if (dt && dt->nbest_k && (dt->nbest_k < 1 || dt->nbest_k > pfhip::kTopkMax || dt->nbest_k > head->weights->cfg.vocab || !dt->nbest_ids ||
+                            !dt->nbest_logp))
+    return fail(PFHIP_ERR_ARG, "nbest: k outside 1..8 (or above the vocabulary) or a null buffer");
+  const int V = head->weights->cfg.vocab;
+  std::vector<pfhip::BeamUtt> utt((size_t)batch, pfhip::BeamUtt{0, 0, 0, -1});
+  std::vector<const pfhip_ctx_graph*> graphs;
+  int kmax = 0;
+  for (int b = 0; b < batch; ++b) {
+    const int k = set_of ? set_of[b] : 0;
+    if (k < -1 || k >= n_sets) return fail(PFHIP_ERR_ARG, "bias: set_of outside -1 .. n_sets - 1");
+    if (k < 0) continue;
+    const pfhip_bias_opts& o = sets[k];
+    if (o.width < 1 || o.width > pfhip::kNarWidthMax || o.width > V || o.beam < 1 || o.beam > pfhip::kBeamMax || o.nbest < 1 || o.nbest > o.beam)
+      return fail(PFHIP_ERR_ARG, "bias: width outside 1..8 (or above the vocabulary), beam outside 1..16 or nbest outside 1..beam");
+    if (o.graph && o.graph->vocab != V) return fail(PFHIP_ERR_ARG, "bias: the graph was built for another vocabulary");
+    int gi = -1;
+    if (o.graph) {
+      gi = (int)(std::find(graphs.begin(), graphs.end(), o.graph) - graphs.begin());
+      if (gi == (int)graphs.size()) graphs.push_back(o.graph);
+    }
+    utt[b] = pfhip::BeamUtt{o.width, o.beam, o.nbest, gi};
+    kmax = std::max(kmax, o.width);
+  }
+  const int stride_k = std::max(kmax, dt ? (int)dt->nbest_k : 0);
+  NarBias nb{utt.data(), graphs.data(), (int)graphs.size(), stride_k, 1, 1, bo};
+  if (kmax && !pfhip::nbest_ctx_beam_check(utt.data(), batch, stride_k, nb.n_graphs, true, &nb.beam_stride, &nb.nbest_stride))
+    return fail(PFHIP_ERR_ARG, "bias: the search refused its descriptors");
+  HwSets hw;
+  if (const pfhip_status hs = hw_sets_of(head, hw_emb, n_hotwords, n_hw_sets, hw_set_of, &hw)) return hs;
+  for (int i = 0; i < batch; ++i)
+    if (n_samples[i] < 0 || (n_samples[i] > 0 && !pcm.p[i])) return fail(PFHIP_ERR_ARG, "bad pcm buffer");
+  const bool other_rate = sample_rate != 0 && sample_rate != head->weights->cfg.sample_rate;
+  if (other_rate) {
+    std::string why;
+    if (!pfhip_impl::resample_supported(sample_rate, head->weights->cfg.sample_rate, &why)) return fail(PFHIP_ERR_UNSUPPORTED, why);
+  }
+  // "no hypothesis" everywhere first: what an utterance without a search, without rows, or a batch without any token row keeps
+  for (int b = 0; b < batch; ++b) {
+    bo->n_hyp[b] = 0;
+    for (int j = 0; j < nb.nbest_stride; ++j) {
+      const size_t o = (size_t)b * nb.nbest_stride + j;
+      bo->n_tokens[o] = 0;
+      if (bo->score) bo->score[o] = -INFINITY;
+      if (bo->am_score) bo->am_score[o] = -INFINITY;
+      if (bo->ctx_score) bo->ctx_score[o] = 0.f;
+    }
+  }
+  pfhip_model* m = acquire_slot(head);
+  tl_last_replica = m;
+  const pfhip_status st = forward_direct(m, pcm, n_samples, batch, hw, out, other_rate ? sample_rate : 0, dt, kmax ? &nb : nullptr);
+  ++m->served_forwards; ++m->served_calls; m->served_utts += batch;
+  release_slot(head, m);
+  return st;
+}
+
 // pfhip_offline_forward at the caller's rate: resampled on the device into the slot's PCM workspace, then the same forward
 pfhip_status offline_forward_rate(pfhip_model* head, HostPcm pcm, const int* n_samples, int batch, int sample_rate,
                                          const float* hw_emb, int n_hotwords, pfhip_out* out) {
@@ -355,13 +423,18 @@ pfhip_status stage_resampled(pfhip_model* m, HostPcm pcm, const int* n_samples, 
 
 // fs_in: the rate of `pcm` when it is not the model's (resampled into the slot's PCM workspace first), else 0
 pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, int batch,
-                                   const HwSets& hw, pfhip_out* out, int fs_in, const pfhip_detail* dt) {
+                                   const HwSets& hw, pfhip_out* out, int fs_in, const pfhip_detail* dt, const NarBias* bias) {
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->own_stream;
   m->prof_stream = s;
   if (dt && dt->nbest_k > m->weights->cfg.vocab) return fail(PFHIP_ERR_ARG, "nbest k larger than the vocabulary");      // before any launch
   m->nbest_k = dt ? dt->nbest_k : 0;
+  // the search of pfhip_offline_forward_bias: the head computes the largest k anybody reads; the slot names the search for the
+  // length of this call only (a range-guard re-run inside fetch_locked reads it again)
+  struct BiasScope { pfhip_model* m; ~BiasScope() { m->bias = nullptr; } } bias_scope{m};
+  m->bias = bias;
+  if (bias) m->nbest_k = std::max(m->nbest_k, bias->k);
   m->want_fires = dt && dt->fire_frame;
   HotwordPins pins{m};              // held until the results (a range-guard re-run included) are back
   {
@@ -495,6 +568,21 @@ pfhip_status pfhip_offline_forward_nbest_s16(pfhip_model* head, const int16_t* c
                                              const float* const* hw_emb, const int* n_hotwords, int n_sets, const int* set_of_utt,
                                              pfhip_out* out, const pfhip_nbest* nb) {
   return offline_forward_nbest(head, pcm, n_samples, batch, hw_emb, n_hotwords, n_sets, set_of_utt, out, nb);
+}
+
+pfhip_status pfhip_offline_forward_bias(pfhip_model* head, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                        const float* const* hw_emb, const int* n_hotwords, int n_hw_sets, const int* hw_set_of,
+                                        pfhip_out* out, const pfhip_detail* det, const pfhip_bias_opts* sets, int n_sets,
+                                        const int32_t* set_of, pfhip_bias_out* bias_out) {
+  return offline_forward_bias(head, pcm, n_samples, batch, sample_rate, hw_emb, n_hotwords, n_hw_sets, hw_set_of, out, det, sets, n_sets,
+                              set_of, bias_out);
+}
+pfhip_status pfhip_offline_forward_bias_s16(pfhip_model* head, const int16_t* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                            const float* const* hw_emb, const int* n_hotwords, int n_hw_sets, const int* hw_set_of,
+                                            pfhip_out* out, const pfhip_detail* det, const pfhip_bias_opts* sets, int n_sets,
+                                            const int32_t* set_of, pfhip_bias_out* bias_out) {
+  return offline_forward_bias(head, pcm, n_samples, batch, sample_rate, hw_emb, n_hotwords, n_hw_sets, hw_set_of, out, det, sets, n_sets,
+                              set_of, bias_out);
 }
 
 // device-pointer form: k candidates for the following pfhip_offline_enqueue calls of this handle (context 0); 0 = off

@@ -508,6 +508,60 @@ int pfhip_op_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_lo
     return (int)hipErrorInvalidValue;
   return done();
 }
+// the search over a non-autoregressive head's candidates (nar_beam.hip): the same shape of entry, width >= 1 for every utterance
+static bool nar_beam_args(const int* width, const int* beam, const int* nbest, const int* graph_of, int B, int k,
+                          const pfhip_ctx_graph* const* graphs, int n_graphs, int V, std::vector<pfhip::BeamUtt>* utt, int* beam_max, int* nb_max) {
+  if (B < 0 || B > 65535 || n_graphs < 0 || (n_graphs > 0 && !graphs) || (B > 0 && (!width || !beam || !nbest || !graph_of))) return false;
+  for (int g = 0; g < n_graphs; ++g)
+    if (!graphs[g] || graphs[g]->vocab != V) return false;
+  utt->resize((size_t)B);
+  for (int b = 0; b < B; ++b) (*utt)[b] = pfhip::BeamUtt{width[b], beam[b], nbest[b], graph_of[b]};
+  return pfhip::nbest_ctx_beam_check(utt->data(), B, k, n_graphs, false, beam_max, nb_max);
+}
+size_t pfhip_op_nbest_ctx_beam_workspace_bytes(long long rows, int B, int k, const int* width, const int* beam, const int* nbest,
+                                               const int* graph_of, const pfhip_ctx_graph* const* graphs, int n_graphs) {
+  std::vector<pfhip::BeamUtt> utt;
+  int beam_max = 1, nb_max = 1;
+  if (n_graphs < 0 || (n_graphs > 0 && !graphs)) return 0;
+  for (int g = 0; g < n_graphs; ++g)
+    if (!graphs[g]) return 0;
+  if (!nar_beam_args(width, beam, nbest, graph_of, B, k, graphs, n_graphs, n_graphs ? graphs[0]->vocab : 1, &utt, &beam_max, &nb_max)) return 0;
+  const size_t nodes = pfhip::nbest_ctx_beam_workspace_bytes(rows, B, beam_max);
+  return nodes ? nodes + pfhip::beam_front_bytes(B, graphs, n_graphs) : 0;
+}
+int pfhip_op_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len, int B,
+                            int V, const int* width, const int* beam, const int* nbest, const int* graph_of,
+                            const pfhip_ctx_graph* const* graphs, int n_graphs, int max_tokens, int32_t* n_hyp, int32_t* ids,
+                            int32_t* n_tokens, float* score, float* am_score, float* ctx_score, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  std::vector<pfhip::BeamUtt> utt;
+  int beam_max = 1, nb_max = 1;
+  if (!nar_beam_args(width, beam, nbest, graph_of, B, k, graphs, n_graphs, V, &utt, &beam_max, &nb_max)) return (int)hipErrorInvalidValue;
+  // the launcher's own checks, on a call that launches nothing (B = 0), then the buffers it would refuse at B > 0
+  if (!pfhip::launch_nbest_ctx_beam(cand_ids, cand_logp, k, rows, row_off, len, nullptr, 0, V, nullptr, nullptr, n_graphs, beam_max, nb_max, max_tokens,
+                                    n_hyp, ids, n_tokens, score, am_score, ctx_score, nullptr, 0, S(stream)))
+    return (int)hipErrorInvalidValue;
+  const size_t front = pfhip::beam_front_bytes(B, graphs, n_graphs), nodes = pfhip::nbest_ctx_beam_workspace_bytes(rows, B, beam_max);
+  if (!workspace || workspace_bytes < front || workspace_bytes - front < nodes) return (int)hipErrorInvalidValue;
+  if (B > 0 && (!row_off || !len || !n_hyp || !n_tokens || !score || !am_score || !ctx_score || (max_tokens > 0 && !ids) ||
+                (rows > 0 && (!cand_ids || !cand_logp))))
+    return (int)hipErrorInvalidValue;
+  if (B == 0) return done();
+  char* const dev = static_cast<char*>(workspace);
+  std::vector<char> host(front, 0);
+  pfhip::beam_front_fill(host.data(), dev, utt.data(), B, graphs, n_graphs);
+  {
+    // pageable memory: the copy has left it when the call returns
+    const hipError_t e = hipMemcpyAsync(dev, host.data(), front, hipMemcpyHostToDevice, S(stream));
+    if (e != hipSuccess) return (int)e;
+  }
+  if (!pfhip::launch_nbest_ctx_beam(cand_ids, cand_logp, k, rows, row_off, len, nullptr, B, V, reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                    reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), n_graphs, beam_max,
+                                    nb_max, max_tokens, n_hyp, ids, n_tokens, score, am_score, ctx_score, dev + front,
+                                    workspace_bytes - front, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
 size_t pfhip_op_ctc_align_workspace_bytes(size_t e_floats) { return pfhip::ctc_align_workspace_bytes(e_floats); }
 int pfhip_op_ctc_align_max_tokens(void) { return pfhip::ctc_align_max_tokens(); }
 int pfhip_op_ctc_align(const float* E, const long long* e_off, size_t e_floats, const int* len, const int* n_lab, const int32_t* labels,

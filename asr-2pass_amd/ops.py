@@ -66,6 +66,11 @@ def _lib():
             lib.pfhip_op_ctc_prefix_beam_multi_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci]
             lib.pfhip_op_ctc_prefix_beam_multi.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp,
                                                            _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+        if hasattr(lib, "pfhip_op_nbest_ctx_beam"):
+            lib.pfhip_op_nbest_ctx_beam_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_nbest_ctx_beam_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci]
+            lib.pfhip_op_nbest_ctx_beam.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci,
+                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
         _bound = True
     return lib
 
@@ -532,6 +537,52 @@ def ctc_prefix_beam_multi(topk_ids, topk_logp, row_off, length, vocab, first_bea
                                            go, handles, len(graphs), max_tokens, _p(n_hyp), _p(ids) if max_tokens else None, _p(n_tokens),
                                            _p(score), _p(ctc_score), _p(ctx_score), _p(ws), nbytes, _stream()), "ctc_prefix_beam_multi")
     return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], ctc_score[:B], ctx_score[:B]
+
+
+def nbest_ctx_beam(cand_ids, cand_logp, row_off, length, vocab, width, beam, nbest, graph_of=None, graphs=(), max_tokens=None,
+                   workspace_bytes=None, rows=None, out=None):
+    """Hotword-biased beam search over a non-autoregressive head's candidates (csrc/nar_beam.hip; include/pfhip_ops.h states the
+    recurrence and the tie rule): cand_ids / cand_logp [rows, k <= 8] device tensors, row_off / length int32 device tensors [B];
+    width, beam, nbest and graph_of host sequences [B] (graph_of -1: no graph), graphs a sequence of ContextGraph.  Utterance b
+    reads the first width[b] columns of its rows and gives one token per row.  Returns (n_hyp [B], ids [B, nbest_max, max_tokens],
+    n_tokens [B, nbest_max], score, am_score, ctx_score [B, nbest_max]).  rows: the row count the kernel is told (default: all of the
+    tensors'; the workspace is sized for all).  out: that tuple to write into (a refusal must leave it as it was)."""
+    lib = _lib()
+    if not hasattr(lib, "pfhip_op_nbest_ctx_beam"):
+        raise PfhipError("nbest_ctx_beam: this libpfhip has no pfhip_op_nbest_ctx_beam")
+    all_rows, k = int(cand_ids.shape[0]), int(cand_ids.shape[1])
+    rows = all_rows if rows is None else min(int(rows), all_rows)
+    B = int(row_off.numel())
+    arr = lambda v: (ctypes.c_int * max(B, 1))(*[int(x) for x in v])
+    graph_of = [-1] * B if graph_of is None else graph_of
+    if not (len(width) == len(beam) == len(nbest) == len(graph_of) == B):
+        raise PfhipError("nbest_ctx_beam: one width, beam, nbest and graph_of per utterance")
+    wd, bm, nb, go = arr(width), arr(beam), arr(nbest), arr(graph_of)
+    handles = (ctypes.c_void_p * max(len(graphs), 1))(*[g.handle for g in graphs])
+    nb_max = max([int(n) for n in nbest] + [1])
+    max_tokens = rows if max_tokens is None else int(max_tokens)
+    dev = cand_ids.device
+    if out is None:
+        n_hyp = torch.full((max(B, 1),), -7, dtype=torch.int32, device=dev)
+        ids = torch.full((max(B, 1), nb_max, max(max_tokens, 1)), -7, dtype=torch.int32, device=dev)
+        n_tokens = torch.full((max(B, 1), nb_max), -7, dtype=torch.int32, device=dev)
+        score, am_score, ctx_score = (torch.full((max(B, 1), nb_max), float("nan"), dtype=torch.float32, device=dev) for _ in range(3))
+    else:
+        n_hyp, ids, n_tokens, score, am_score, ctx_score = out
+        if tuple(ids.shape) != (max(B, 1), nb_max, max(max_tokens, 1)) or any(tuple(t.shape) != (max(B, 1), nb_max)
+                                                                                for t in (n_tokens, score, am_score, ctx_score)):
+            raise PfhipError("nbest_ctx_beam: out must be shaped [B, nbest_max, max(max_tokens, 1)] and [B, nbest_max]")
+    if workspace_bytes is None:
+        nbytes = int(lib.pfhip_op_nbest_ctx_beam_workspace_bytes(all_rows, B, k, wd, bm, nb, go, handles, len(graphs)))
+    else:
+        nbytes = int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    if max_tokens == 0:                                              # the kernel gets a stride of 0 and no buffer
+        ids = ids[:, :, :0]
+    _ck(lib.pfhip_op_nbest_ctx_beam(_p(cand_ids), _p(cand_logp), k, rows, _p(row_off), _p(length), B, int(vocab), wd, bm, nb, go, handles,
+                                    len(graphs), max_tokens, _p(n_hyp), _p(ids) if max_tokens else None, _p(n_tokens), _p(score),
+                                    _p(am_score), _p(ctx_score), _p(ws), nbytes, _stream()), "nbest_ctx_beam")
+    return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], am_score[:B], ctx_score[:B]
 
 
 def ctc_collapse_chunk():

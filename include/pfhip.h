@@ -809,6 +809,44 @@ pfhip_status pfhip_svs_graph_bank_stats(pfhip_model* m, pfhip_svs_graph_bank_sta
  * lifetime rule of pfhip_svs_align), and pfhip_debug_poke "svs_topk_k" that forward's k. */
 pfhip_status pfhip_svs_set_beam_merging(pfhip_model* m, int on);
 
+/* ---- hotwords for any Paraformer: a biased beam search over the head's candidates (extension) --------
+ * The reference biases a Paraformer two ways: the contextual checkpoint (model_eb.onnx + bias decoder), and BiasLm inside the WFST
+ * search, which needs a TLG.fst.  Without an LM its Paraformer::Forward never looks at the connection's CtcPrefixDecoder
+ * (paraformer.cpp:563-579), so a client's hotwords are dropped.  This is NOT either of those paths: the head's k best columns of
+ * every token row (topk.hip) are searched on the device with a context graph (pfhip_op_nbest_ctx_beam, include/pfhip_ops.h, states
+ * the recurrence and the tie rule).  A Paraformer's token rows are independent positions, so the search replaces tokens position by
+ * position and never changes the token count: n_fires, token_num, fire frames and head timestamps of the same forward stay valid
+ * for the biased ids.  It works on any Paraformer (plain, small, contextual: both biases at once) and has not been evaluated on
+ * real speech.
+ * pfhip_offline_forward_bias[_s16] is pfhip_offline_forward_detail[_s16] plus the search: `out` and `det` (may be NULL) come back
+ * bit for bit as that call's with the same det.  sets [n_sets]: 1 <= width <= 8 (and <= vocab), 1 <= nbest <= beam <= 16, graph
+ * NULL or built for this model's vocabulary (alive for the call; it goes up with the call).  set_of [batch] names each utterance's
+ * set, -1: no search for it (n_hyp 0); NULL: every utterance on set 0.  The head runs ONCE in its top-k form at k = the largest of
+ * the widths in use and det->nbest_k; an utterance reads the first `width` columns of its rows (the value and order rules of the
+ * head do not depend on k).  The search covers min(token_num[b], n_fires[b]) rows, read from the device's own counts on the
+ * forward's stream, and its results cross before the forward's one synchronise; after a range-guard re-run everything belongs to
+ * the re-run; each execution context (pfhip_set_inflight) owns its buffers.  With pfhip_set_batching on the call is served alone,
+ * past the merge queue.
+ * bias_out, caller-owned, with stride = the largest nbest among the sets in use (1 if none): n_hyp [batch]; ids
+ * [batch][stride][max_tokens] (written up to n_tokens); n_tokens [batch][stride] = the searched row count for a live hypothesis;
+ * score (am + ctx) / am_score / ctx_score [batch][stride] (may be NULL; -inf / -inf / 0 behind n_hyp).  Without a graph hypothesis
+ * 0 is the greedy sequence.  PFHIP_ERR_UNSUPPORTED: a SenseVoice handle, a multi-device group.  PFHIP_ERR_CAPACITY where
+ * bias_out->max_tokens is below the longest returned hypothesis: n_hyp, n_tokens and the scores are written all the same.
+ * PFHIP_ERR_ARG: a limit broken in a set in use, n_sets < 1, a set_of outside -1 .. n_sets - 1, a missing buffer, a graph of
+ * another vocabulary. */
+typedef struct pfhip_bias_opts { int width; int beam; int nbest; const pfhip_ctx_graph* graph; } pfhip_bias_opts;
+typedef struct pfhip_bias_out {
+  int32_t* n_hyp; int32_t* ids; int32_t* n_tokens; float* score; float* am_score; float* ctx_score; int max_tokens;
+} pfhip_bias_out;
+pfhip_status pfhip_offline_forward_bias(pfhip_model* m, const float* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                        const float* const* hw_emb, const int* n_hotwords, int n_hw_sets, const int* hw_set_of,
+                                        pfhip_out* out, const pfhip_detail* det, const pfhip_bias_opts* sets, int n_sets,
+                                        const int32_t* set_of, pfhip_bias_out* bias_out);
+pfhip_status pfhip_offline_forward_bias_s16(pfhip_model* m, const int16_t* const* pcm, const int* n_samples, int batch, int sample_rate,
+                                            const float* const* hw_emb, const int* n_hotwords, int n_hw_sets, const int* hw_set_of,
+                                            pfhip_out* out, const pfhip_detail* det, const pfhip_bias_opts* sets, int n_sets,
+                                            const int32_t* set_of, pfhip_bias_out* bias_out);
+
 /* ---- inspection (parity tests) -----------------------------------------------------------------
  * Copies a named intermediate of the LAST forward to host: "feats" [M,560], "enc" [M,d],
  * "alphas" [M] (without the tail slot), "emb" [sum fires, d], "logp" [sum fires, vocab],

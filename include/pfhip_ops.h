@@ -269,6 +269,40 @@ int pfhip_op_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_lo
                                    const int* nbest, const int* graph_of, const struct pfhip_ctx_graph* const* graphs, int n_graphs,
                                    int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score,
                                    float* ctx_score, void* workspace, size_t workspace_bytes, void* stream);
+/* Hotword-biased beam search over the candidates of a NON-AUTOREGRESSIVE head (nar_beam.hip): a Paraformer's token rows are
+ * independent positions, so the search replaces tokens position by position and never changes the token count.  An EXTENSION: the
+ * reference biases a Paraformer only inside its WFST search (BiasLm); this is not that path.
+ * Utterance b owns rows [row_off[b], row_off[b] + len[b]) (DEVICE arrays; the ranges must not overlap) of cand_ids / cand_logp
+ * [rows][k].  Row t's candidates are its first width[b] columns (tok_c, p_c), descending and distinct as the top-k head leaves them.
+ * width, beam, nbest and graph_of [B] are HOST arrays and graphs a HOST array of n_graphs handles, each built for vocab == V
+ * (graph_of[b] == -1: no graph).  1 <= width[b] <= k <= 8, 1 <= nbest[b] <= beam[b] <= 16: at most 128 (hypothesis, candidate) pairs.
+ *   A hypothesis is (am, ctx, state, node).  Start: one hypothesis, am = 0, ctx = 0, state 0, the root node.
+ *   Row t, for every live hypothesis h (beam order) and candidate c < width:  am' = am_h + p_c (one fp32 add, left to right along
+ *   the sequence);  (state', w) = GetNextState(state_h, tok_c) of the graph (the arc's weight, else the state's escape weight and
+ *   state 0);  ctx' = ctx_h + w;  total' = am' + ctx'.  The `beam` largest totals survive; EQUAL totals order hypothesis-major,
+ *   candidate-minor.  Two extensions of a row differ in the parent or in the token, and the parents are distinct sequences of equal
+ *   length, so two extensions never name the same sequence: there is NO MERGE STEP, and nothing is summed over alignments.
+ *   End: a hypothesis whose state is not 0 receives escape[state] (the back-off of an unfinished match) into ctx, total is formed
+ *   again, and the order is by total, equal totals in beam order.
+ *   Without a graph w is 0 everywhere: hypothesis 0 is the greedy sequence (column 0 of every row) and its am the fp32
+ *   left-to-right sum of cand_logp[.., 0].  Every sum is a single fp32 add in the order written: results are reproducible bit for bit.
+ * Out per utterance, with nbest_stride the largest nbest[b]: n_hyp [B] <= nbest[b]; ids [B][nbest_stride][max_tokens] (-1 behind the
+ * tokens); n_tokens [B][nbest_stride] = len[b] for a live hypothesis, also above max_tokens (the surplus is not stored); score
+ * (total), am_score, ctx_score [B][nbest_stride] (-inf / -inf / 0 behind n_hyp and from nbest[b] on).  len[b] == 0 gives n_hyp 0; so
+ * does an utterance whose rows leave [0, rows): its own slots hold that fill (ids -1, n_tokens 0) and nothing else is written.  An id outside 0 .. V - 1 is CLAMPED into it; a
+ * log-probability that is NaN or below -FLT_MAX counts as -FLT_MAX; a NaN total ranks as -inf.
+ * workspace: pfhip_op_nbest_ctx_beam_workspace_bytes(...) bytes of device memory (0 for descriptors the entry refuses): the
+ * descriptors, a table of the graphs and their images, which the call copies there on `stream` in ONE copy, then a (parent, token)
+ * trie node per row and slot of the largest beam.  hipErrorInvalidValue, before anything is copied or launched, for anything outside
+ * the limits above, graph_of[b] outside -1 .. n_graphs - 1, a NULL graph or one built for another vocabulary than V, a NULL buffer
+ * (ids with max_tokens 0 excepted) or a short workspace. */
+size_t pfhip_op_nbest_ctx_beam_workspace_bytes(long long rows, int B, int k, const int* width, const int* beam, const int* nbest,
+                                               const int* graph_of, const struct pfhip_ctx_graph* const* graphs, int n_graphs);
+int pfhip_op_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len,
+                            int B, int V, const int* width, const int* beam, const int* nbest, const int* graph_of,
+                            const struct pfhip_ctx_graph* const* graphs, int n_graphs, int max_tokens, int32_t* n_hyp, int32_t* ids,
+                            int32_t* n_tokens, float* score, float* am_score, float* ctx_score, void* workspace,
+                            size_t workspace_bytes, void* stream);
 /* One streaming window (M <= 32 rows): LayerNormalization (g != NULL; width D <= K) -> MatMul/Gemm (+bias, +residual Adds, Relu)
  * (+ the SAN-M FSMN memory of fsmn_v over the M rows, k = 11) in ONE launch — stream_fused.hip. */
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
