@@ -73,6 +73,9 @@ ABI_SYMBOLS = [
     "pfhip_svs_graph_bank_stats",
     # hotwords for any Paraformer: the biased beam search over the head's candidates, behind the forward
     "pfhip_offline_forward_bias", "pfhip_offline_forward_bias_s16",
+    # token n-gram language model of the device searches (host only)
+    "pfhip_lm_graph_create", "pfhip_lm_graph_create_from_arpa", "pfhip_lm_graph_destroy", "pfhip_lm_graph_vocab", "pfhip_lm_graph_order",
+    "pfhip_lm_graph_dump", "pfhip_set_token_lm",
 ]
 
 
@@ -339,6 +342,19 @@ def load_lib() -> ctypes.CDLL:
         lib.pfhip_ctx_graph_destroy.restype = None
         lib.pfhip_ctx_graph_vocab.argtypes = [vp]
         lib.pfhip_ctx_graph_dump.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), i32p, fp, ci, i32p, i32p, fp, ci]
+    if hasattr(lib, "pfhip_lm_graph_create"):
+        i32p, fp, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)
+        cf = ctypes.c_float
+        lib.pfhip_lm_graph_create.argtypes = [ci, ctypes.POINTER(ci), i32p, dp, dp, ci, cf, cf, cf, ctypes.POINTER(vp)]
+        lib.pfhip_lm_graph_create_from_arpa.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ci, cf, cf, cf, ctypes.POINTER(vp),
+                                                        ctypes.POINTER(ctypes.c_longlong)]
+        lib.pfhip_lm_graph_destroy.argtypes = [vp]
+        lib.pfhip_lm_graph_destroy.restype = None
+        lib.pfhip_lm_graph_vocab.argtypes = [vp]
+        lib.pfhip_lm_graph_order.argtypes = [vp]
+        lib.pfhip_lm_graph_dump.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), fp, i32p, ci,
+                                            i32p, fp, i32p, ci, i32p, i32p, fp, ci]
+        lib.pfhip_set_token_lm.argtypes = [vp, vp]
     lib.pfhip_profile_enable.argtypes = [vp, ci]
     lib.pfhip_profile_read.argtypes = [vp, ctypes.POINTER(_Profile), ci]
     # 16-bit PCM in: the argument lists of the f32 siblings
@@ -402,6 +418,87 @@ class ContextGraph:
     def close(self):
         if self.handle:
             self._lib.pfhip_ctx_graph_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LmGraph:
+    """A token n-gram language model for the device searches and ops.lm_score (pfhip_lm_graph_*, include/pfhip.h states the
+    automaton and the weight rule).  Host only: no device is needed.  Labels: 0 .. vocab - 1 token ids, vocab </s>, vocab + 1 <s>,
+    vocab + 2 <unk>.  Build with from_ngrams or from_arpa.  handle: what the ops pass on; dump(): the arrays; n_skipped: the n-grams
+    from_arpa left out for an unknown word."""
+
+    def __init__(self, handle, vocab, n_skipped=0):
+        self._lib, self.handle, self.vocab, self.n_skipped = load_lib(), handle, int(vocab), int(n_skipped)
+        self.order = int(self._lib.pfhip_lm_graph_order(handle))
+
+    @classmethod
+    def from_ngrams(cls, ngrams, vocab, scale=1.0, token_bonus=0.0, oov_log10=-10.0, order=None):
+        """ngrams: a sequence of (labels, log10_prob, log10_backoff) in any sequence; order: the longest length (default: what
+        ngrams holds, at least 1)."""
+        lib = load_lib()
+        ngrams = [(tuple(int(t) for t in lab), float(p), float(b)) for lab, p, b in ngrams]
+        order = max([len(g[0]) for g in ngrams] + [1]) if order is None else int(order)
+        if any(len(g[0]) < 1 or len(g[0]) > order for g in ngrams):
+            raise PfhipError("LmGraph.from_ngrams: an n-gram without labels or longer than the order")
+        by_len = [[g for g in ngrams if len(g[0]) == n] for n in range(1, order + 1)]
+        flat = [g for part in by_len for g in part]
+        n = (ctypes.c_int * max(order, 1))(*[len(part) for part in by_len])
+        lab = np.asarray([t for g in flat for t in g[0]] or [0], np.int32)
+        p = np.asarray([g[1] for g in flat] or [0.0], np.float64)
+        b = np.asarray([g[2] for g in flat] or [0.0], np.float64)
+        h = ctypes.c_void_p()
+        dp = ctypes.POINTER(ctypes.c_double)
+        st = lib.pfhip_lm_graph_create(order, n, lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), p.ctypes.data_as(dp), b.ctypes.data_as(dp),
+                                       int(vocab), float(scale), float(token_bonus), float(oov_log10), ctypes.byref(h))
+        _check(lib, st)
+        return cls(h, vocab)
+
+    @classmethod
+    def from_arpa(cls, path, tokens, scale=1.0, token_bonus=0.0, oov_log10=-10.0):
+        """path: an ARPA file; tokens: the model's token strings (str or bytes), index = token id."""
+        lib = load_lib()
+        raw = [t if isinstance(t, bytes) else str(t).encode("utf-8") for t in tokens]
+        arr = (ctypes.c_char_p * max(len(raw), 1))(*raw)
+        h, skipped = ctypes.c_void_p(), ctypes.c_longlong(0)
+        st = lib.pfhip_lm_graph_create_from_arpa(os.fsencode(path), arr, len(raw), float(scale), float(token_bonus), float(oov_log10),
+                                                 ctypes.byref(h), ctypes.byref(skipped))
+        _check(lib, st)
+        return cls(h, len(raw), skipped.value)
+
+    def dump(self):
+        """dict(start, has_eos, uni_w / uni_next [vocab + 1], arc_begin [S + 1], backoff_w / backoff_state [S], arc_label / arc_next /
+        arc_weight [A])."""
+        lib = self._lib
+        ci = ctypes.c_int
+        ns, na, start, eos = ci(), ci(), ci(), ci()
+        st = lib.pfhip_lm_graph_dump(self.handle, ctypes.byref(ns), ctypes.byref(na), ctypes.byref(start), ctypes.byref(eos), None, None, 0,
+                                     None, None, None, 0, None, None, None, 0)
+        _check(lib, st)
+        S, A, U = ns.value, na.value, self.vocab + 1
+        out = dict(uni_w=np.zeros(U, np.float32), uni_next=np.zeros(U, np.int32), arc_begin=np.zeros(S + 1, np.int32),
+                   backoff_w=np.zeros(S, np.float32), backoff_state=np.zeros(S, np.int32), arc_label=np.zeros(max(A, 1), np.int32),
+                   arc_next=np.zeros(max(A, 1), np.int32), arc_weight=np.zeros(max(A, 1), np.float32))
+        i32p, fp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        ptr = lambda k: out[k].ctypes.data_as(fp if out[k].dtype == np.float32 else i32p)
+        st = lib.pfhip_lm_graph_dump(self.handle, ctypes.byref(ns), ctypes.byref(na), ctypes.byref(start), ctypes.byref(eos), ptr("uni_w"),
+                                     ptr("uni_next"), U, ptr("arc_begin"), ptr("backoff_w"), ptr("backoff_state"), S, ptr("arc_label"),
+                                     ptr("arc_next"), ptr("arc_weight"), max(A, 1))
+        if st != 0:
+            raise PfhipError(f"pfhip_lm_graph_dump: status {st}")
+        for key in ("arc_label", "arc_next", "arc_weight"):
+            out[key] = out[key][:A]
+        out["start"], out["has_eos"] = start.value, eos.value
+        return out
+
+    def close(self):
+        if self.handle:
+            self._lib.pfhip_lm_graph_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -782,6 +879,17 @@ class ParaformerHip:
                             for j in range(int(b_nhyp[b]))] for b in range(B)]
         return res
 
+    def set_token_lm(self, lm):
+        """pfhip_set_token_lm: lm (an LmGraph, or None to remove it) is walked by every search of this handle's forwards from now
+        on; its image is copied to the device, so the LmGraph may be closed afterwards.  The model's share of each hypothesis of
+        the last search: beam_lm_score()."""
+        _check(self._lib, self._lib.pfhip_set_token_lm(self._h, lm.handle if lm is not None else None))
+
+    def beam_lm_score(self, batch, stride):
+        """pfhip_get_tensor "beam_lm_score": [batch, stride] — the language model's share of the scores of this thread's last
+        searching forward, laid out as that call's score array."""
+        return self.get_tensor("beam_lm_score", int(batch) * int(stride)).reshape(int(batch), int(stride))
+
     def forward_bias(self, din: Sequence[np.ndarray], bias_sets, set_of=None, **kw):
         """forward_ids(din, bias_sets=bias_sets, set_of=set_of, ...): the forward plus the hotword-biased beam search."""
         return self.forward_ids(din, bias_sets=bias_sets, set_of=set_of, **kw)
@@ -1087,6 +1195,17 @@ class SenseVoiceHip:
         """With set_batching on: forward(beam=...) and forward(beam_sets=...) callers join the merge queue too
         (pfhip_svs_set_beam_merging; off by default: every beam call is a forward of its own)."""
         _check(self._lib, self._lib.pfhip_svs_set_beam_merging(self._h, 1 if on else 0))
+
+    def set_token_lm(self, lm):
+        """pfhip_set_token_lm: lm (an LmGraph, or None to remove it) is walked by every search of this handle's forwards from now
+        on; its image is copied to the device, so the LmGraph may be closed afterwards.  The model's share of each hypothesis of
+        the last search: beam_lm_score()."""
+        _check(self._lib, self._lib.pfhip_set_token_lm(self._h, lm.handle if lm is not None else None))
+
+    def beam_lm_score(self, batch, stride):
+        """pfhip_get_tensor "beam_lm_score": [batch, stride] — the language model's share of the scores of this thread's last
+        searching forward, laid out as that call's score array."""
+        return self.get_tensor("beam_lm_score", int(batch) * int(stride)).reshape(int(batch), int(stride))
 
     def set_graph_bank_bytes(self, nbytes):
         """The bound of the device's bank of context graphs (pfhip_svs_set_graph_bank_bytes); 0 banks nothing."""

@@ -8,6 +8,7 @@
 
 #include "ctx_graph.h"
 #include "kernels.h"
+#include "lm_graph.h"
 
 namespace pfhip {
 
@@ -25,6 +26,29 @@ inline CtxGraphDev ctx_graph_dev(const pfhip_ctx_graph* g, const void* image) {
   dev.arc_label = w + 2 * S_ + 1;
   dev.arc_next = w + 2 * S_ + 1 + A;
   dev.arc_weight = reinterpret_cast<const float*>(w + 2 * S_ + 1 + 2 * A);
+  return dev;
+}
+
+// the token n-gram language model the same way (lm_graph.h `packed`): its image follows the block above in the same copy
+inline size_t lm_graph_image_bytes(const pfhip_lm_graph* g) { return g ? (g->packed.size() * 4 + 15) / 16 * 16 : 0; }
+inline LmGraphDev lm_graph_dev(const pfhip_lm_graph* g, const void* image) {
+  LmGraphDev dev;
+  if (!g) return dev;
+  if (!image) {                                  // the counts alone: what a launcher's own checks read at B = 0
+    dev.n_states = g->n_states(); dev.n_arcs = g->n_arcs(); dev.vocab = g->vocab; dev.start = g->start; dev.has_eos = g->has_eos;
+    return dev;
+  }
+  const size_t U = (size_t)g->vocab + 1, S_ = (size_t)g->n_states(), A = (size_t)g->n_arcs();
+  const int32_t* w = static_cast<const int32_t*>(image);
+  dev.n_states = g->n_states(); dev.n_arcs = g->n_arcs(); dev.vocab = g->vocab; dev.start = g->start; dev.has_eos = g->has_eos;
+  dev.uni_w = reinterpret_cast<const float*>(w);
+  dev.uni_next = w + U;
+  dev.arc_begin = w + 2 * U;
+  dev.backoff_w = reinterpret_cast<const float*>(w + 2 * U + S_ + 1);
+  dev.backoff_state = w + 2 * U + 2 * S_ + 1;
+  dev.arc_label = w + 2 * U + 3 * S_ + 1;
+  dev.arc_next = w + 2 * U + 3 * S_ + 1 + A;
+  dev.arc_weight = reinterpret_cast<const float*>(w + 2 * U + 3 * S_ + 1 + 2 * A);
   return dev;
 }
 

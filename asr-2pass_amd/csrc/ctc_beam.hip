@@ -20,9 +20,17 @@
 // NaN or below -FLT_MAX counts as -FLT_MAX, a NaN total ranks as -inf: whatever the rows hold, ranks stay unique, every beam slot
 // that is read was written, and every index stays inside its buffer.  Graph indices are the host builder's (ctx_graph.cpp).
 // The final walk from each surviving node to the root writes the ids; it reads nodes other threads wrote, behind a barrier.
+//
+// kLm = true is the same search with a token n-gram language model (lm_step.h) walked beside the context graph.  The model's state and
+// score are a function of the prefix alone: an unchanged hypothesis keeps both, an extension h + tok takes lm_h + the weight of tok
+// after lm_state_h (a merged extension is the live hypothesis and keeps that one's, which are the same), every total takes lm as one
+// more fp32 add behind the sum it was, and at the end, where the model has </s>, every live hypothesis takes the weight of </s> (after
+// the context back-off, before the final order).  kLm = false compiles to what the kernel was before: the model's LDS arrays exist in
+// the kLm = true instantiation alone and the extra arguments are not read.
 #include "ctx_step.h"
 #include "kernels.h"
 #include "launch_common.h"
+#include "lm_step.h"
 
 #include <float.h>
 #include <math.h>
@@ -49,11 +57,28 @@ struct BeamState {                               // one buffer of the beam
   float s[kBM], ns[kBM], ctx[kBM];
   int state[kBM], node[kBM], par[kBM], tok[kBM], len[kBM];
 };
+struct BeamLm {                                  // the model's share of one buffer of the beam (kLm)
+  float lm[kBM];
+  int lm_state[kBM];
+};
+// The LDS of the model's state and score exists in the kLm = true instantiation alone: the arrays are function-local statics of the
+// specialisation that is only called there, so kLm = false keeps the LDS layout, and with it the code, it had before.
+template <bool kLm> struct LmLds;
+template <> struct LmLds<false> {
+  __device__ static __forceinline__ BeamLm* beam() { return nullptr; }
+  __device__ static __forceinline__ float* cand_lm() { return nullptr; }
+  __device__ static __forceinline__ int* cand_state() { return nullptr; }
+};
+template <> struct LmLds<true> {
+  __device__ static __forceinline__ BeamLm* beam() { __shared__ BeamLm b[2]; return b; }
+  __device__ static __forceinline__ float* cand_lm() { __shared__ float a[kSlots]; return a; }
+  __device__ static __forceinline__ int* cand_state() { __shared__ int a[kSlots]; return a; }
+};
 
 // kPerUtt: workgroup b takes first_beam, second_beam, nbest and its graph from utt[b] (launch_ctc_prefix_beam_multi); the arguments
 // fb / sb / nbest are then the launch's strides only: sb the node stride of a row, nbest the hypothesis slots of an utterance (fb is
 // not read).  Everything read from utt[b] is uniform in the workgroup, so every barrier below still sits in uniform control flow.
-template <bool kPerUtt>
+template <bool kPerUtt, bool kLm>
 __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __restrict__ topk_ids, const float* __restrict__ topk_logp, int k,
                                                               long long rows, const int* __restrict__ row_off, const int* __restrict__ len,
                                                               int V, int blank, int fb, int sb, CtxGraphDev g, int nbest, int max_tokens,
@@ -62,12 +87,15 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
                                                               float* __restrict__ ctc_score, float* __restrict__ ctx_score,
                                                               int32_t* __restrict__ node_parent, int32_t* __restrict__ node_token,
                                                               const BeamUtt* __restrict__ utt, const CtxGraphDev* __restrict__ graphs,
-                                                              int n_graphs) {
+                                                              int n_graphs, LmGraphDev lm, float* __restrict__ lm_score) {
   __shared__ BeamState beam[2];
   __shared__ int fr_id[2][kBM];
   __shared__ float fr_lp[2][kBM];
   __shared__ float c_tot[kSlots], c_s[kSlots], c_ns[kSlots], c_ctx[kSlots];
   __shared__ int c_state[kSlots], c_ok[kSlots];
+  BeamLm* const blm = LmLds<kLm>::beam();                            // null without a model, and then never read
+  float* const c_lm = LmLds<kLm>::cand_lm();
+  int* const c_lm_state = LmLds<kLm>::cand_state();
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int T = len[b];
@@ -77,6 +105,7 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
   for (int j = tid; j < nbest; j += kBT) {
     n_tokens[o_h + j] = 0;
     score[o_h + j] = -INFINITY; ctc_score[o_h + j] = -INFINITY; ctx_score[o_h + j] = 0.f;
+    if constexpr (kLm) lm_score[o_h + j] = 0.f;
   }
   for (size_t j = tid; j < (size_t)nbest * max_tokens; j += kBT) out_ids[o_h * max_tokens + j] = -1;
   // the rows must lie inside the arrays (row_off and len are device data the launcher could not see); T * sb + 1 stays below 2^31
@@ -118,6 +147,7 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
     BeamState& h = beam[0];
     h.s[0] = 0.f; h.ns[0] = -FLT_MAX; h.ctx[0] = 0.f;
     h.state[0] = 0; h.node[0] = 0; h.par[0] = -1; h.tok[0] = -1; h.len[0] = 0;
+    if constexpr (kLm) { blm[0].lm[0] = 0.f; blm[0].lm_state[0] = lm.start; }
   }
   fetch(0);
   __syncthreads();
@@ -151,6 +181,13 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
           cx = cx + w;
         }
         float tot = ens + cx;                                        // LogAdd(-FLT_MAX, ns) = ns
+        if constexpr (kLm) {
+          float w;
+          c_lm_state[slot] = lm_step(lm, blm[t & 1].lm_state[h], tok, &w);
+          const float l = blm[t & 1].lm[h] + w;
+          c_lm[slot] = l;
+          tot = tot + l;
+        }
         if (tot != tot) tot = -INFINITY;
         c_s[slot] = -FLT_MAX; c_ns[slot] = ens; c_ctx[slot] = cx; c_state[slot] = st; c_tot[slot] = tot;
       }
@@ -177,6 +214,7 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
           }
         if (ok) {
           float tot = log_add(us, uns) + cur.ctx[h];
+          if constexpr (kLm) tot = tot + blm[t & 1].lm[h];
           if (tot != tot) tot = -INFINITY;
           c_s[h] = us; c_ns[h] = uns; c_tot[h] = tot;
         }
@@ -207,6 +245,7 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
           nxt.s[rk] = c_s[i]; nxt.ns[rk] = c_ns[i]; nxt.ctx[rk] = cur.ctx[i];
           nxt.state[rk] = cur.state[i]; nxt.node[rk] = cur.node[i]; nxt.par[rk] = cur.par[i]; nxt.tok[rk] = cur.tok[i];
           nxt.len[rk] = cur.len[i];
+          if constexpr (kLm) { blm[(t + 1) & 1].lm[rk] = blm[t & 1].lm[i]; blm[(t + 1) & 1].lm_state[rk] = blm[t & 1].lm_state[i]; }
         } else {
           const int p = i - kBM, h = p / fb, c = p - h * fb;
           const int node = 1 + t * sb + rk;                          // <= T * sb
@@ -214,6 +253,7 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
           nxt.s[rk] = c_s[i]; nxt.ns[rk] = c_ns[i]; nxt.ctx[rk] = c_ctx[i];
           nxt.state[rk] = c_state[i]; nxt.node[rk] = node; nxt.par[rk] = cur.node[h]; nxt.tok[rk] = fid[c];
           nxt.len[rk] = cur.len[h] + 1;
+          if constexpr (kLm) { blm[(t + 1) & 1].lm[rk] = c_lm[i]; blm[(t + 1) & 1].lm_state[rk] = c_lm_state[i]; }
         }
       }
     }
@@ -232,6 +272,16 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
       if (g.n_states > 0 && st != 0) cx = cx + g.escape[min(max(st, 0), g.n_states - 1)];
       const float ctc = log_add(fin.s[tid], fin.ns[tid]);
       float tot = ctc + cx;
+      if constexpr (kLm) {
+        float l = blm[T & 1].lm[tid];
+        if (lm.has_eos) {
+          float w;
+          lm_step(lm, blm[T & 1].lm_state[tid], lm.vocab, &w);
+          l = l + w;
+        }
+        c_lm[tid] = l;
+        tot = tot + l;
+      }
       if (tot != tot) tot = -INFINITY;
       c_tot[tid] = tot; c_s[tid] = ctc; c_ctx[tid] = cx;
     }
@@ -246,6 +296,7 @@ __global__ __launch_bounds__(kBT) void ctc_prefix_beam_kernel(const int32_t* __r
   const int L = fin.len[tid];
   n_tokens[o_h + rk] = L;                                            // the true length, also above max_tokens
   score[o_h + rk] = c_tot[tid]; ctc_score[o_h + rk] = c_s[tid]; ctx_score[o_h + rk] = c_ctx[tid];
+  if constexpr (kLm) lm_score[o_h + rk] = c_lm[tid];
   int32_t* const dst = out_ids + (o_h + rk) * max_tokens;
   int node = fin.node[tid];
   const int cap = T * sb;                                            // the last node of this utterance
@@ -280,9 +331,9 @@ bool launch_ctc_prefix_beam(const int32_t* topk_ids, const float* topk_logp, int
     return false;
   int32_t* const node_parent = static_cast<int32_t*>(workspace);
   int32_t* const node_token = node_parent + std::max<size_t>((size_t)rows * second_beam, 1);
-  hipLaunchKernelGGL(ctc_prefix_beam_kernel<false>, dim3(B), dim3(kBT), 0, s, topk_ids, topk_logp, k, rows, row_off, len, V, blank, first_beam,
-                     second_beam, graph, nbest, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, node_parent, node_token,
-                     static_cast<const BeamUtt*>(nullptr), static_cast<const CtxGraphDev*>(nullptr), 0);
+  hipLaunchKernelGGL((ctc_prefix_beam_kernel<false, false>), dim3(B), dim3(kBT), 0, s, topk_ids, topk_logp, k, rows, row_off, len, V, blank,
+                     first_beam, second_beam, graph, nbest, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, node_parent, node_token,
+                     static_cast<const BeamUtt*>(nullptr), static_cast<const CtxGraphDev*>(nullptr), 0, LmGraphDev(), static_cast<float*>(nullptr));
   return true;
 }
 
@@ -301,10 +352,14 @@ bool ctc_prefix_beam_multi_check(const BeamUtt* utt, int B, int k, int n_graphs,
   return true;
 }
 
-bool launch_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
-                                  int B, int V, int blank, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int sb_max,
-                                  int nbest_max, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
-                                  float* ctc_score, float* ctx_score, void* workspace, size_t workspace_bytes, hipStream_t s) {
+namespace {
+
+template <bool kLm>
+bool launch_multi(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len, int B, int V, int blank,
+                  const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, const LmGraphDev& lm, int sb_max, int nbest_max, int max_tokens,
+                  int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score, float* ctx_score, float* lm_score, void* workspace,
+                  size_t workspace_bytes, hipStream_t s) {
+  if (kLm && (lm.n_states < 1 || lm.n_arcs < 0 || lm.vocab != V || lm.start < 0 || lm.start >= lm.n_states)) return false;
   if (B < 0 || B > 65535 || rows < 0 || k < 1 || k > kBeamMax || sb_max < 1 || sb_max > kBeamMax || nbest_max < 1 || nbest_max > sb_max ||
       n_graphs < 0 || V < 1 || blank < 0 || blank >= V || max_tokens < 0 || rows * sb_max + 1 > 0x7fffffffLL)
     return false;
@@ -313,12 +368,33 @@ bool launch_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_log
       (max_tokens > 0 && !ids) || (rows > 0 && (!topk_ids || !topk_logp)) || !workspace ||
       workspace_bytes < ctc_prefix_beam_workspace_bytes(rows, B, sb_max))
     return false;
+  if (kLm && (!lm_score || !lm.uni_w || !lm.uni_next || !lm.arc_begin || !lm.backoff_w || !lm.backoff_state ||
+              (lm.n_arcs > 0 && (!lm.arc_label || !lm.arc_next || !lm.arc_weight))))
+    return false;
   int32_t* const node_parent = static_cast<int32_t*>(workspace);
   int32_t* const node_token = node_parent + std::max<size_t>((size_t)rows * sb_max, 1);
-  hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(B), dim3(kBT), 0, s, topk_ids, topk_logp, k, rows, row_off, len, V, blank, 0, sb_max,
+  hipLaunchKernelGGL((ctc_prefix_beam_kernel<true, kLm>), dim3(B), dim3(kBT), 0, s, topk_ids, topk_logp, k, rows, row_off, len, V, blank, 0, sb_max,
                      CtxGraphDev(), nbest_max, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, node_parent, node_token, utt,
-                     graphs, n_graphs);
+                     graphs, n_graphs, lm, lm_score);
   return true;
+}
+
+}  // namespace
+
+bool launch_ctc_prefix_beam_multi(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                                  int B, int V, int blank, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int sb_max,
+                                  int nbest_max, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
+                                  float* ctc_score, float* ctx_score, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  return launch_multi<false>(topk_ids, topk_logp, k, rows, row_off, len, B, V, blank, utt, graphs, n_graphs, LmGraphDev(), sb_max, nbest_max,
+                             max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, nullptr, workspace, workspace_bytes, s);
+}
+
+bool launch_ctc_prefix_beam_multi_lm(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                                     int B, int V, int blank, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, const LmGraphDev& lm,
+                                     int sb_max, int nbest_max, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
+                                     float* ctc_score, float* ctx_score, float* lm_score, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  return launch_multi<true>(topk_ids, topk_logp, k, rows, row_off, len, B, V, blank, utt, graphs, n_graphs, lm, sb_max, nbest_max, max_tokens,
+                            n_hyp, ids, n_tokens, score, ctc_score, ctx_score, lm_score, workspace, workspace_bytes, s);
 }
 
 }  // namespace pfhip

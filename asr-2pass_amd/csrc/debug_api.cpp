@@ -83,16 +83,40 @@ pfhip_status pfhip_get_tensor(pfhip_model* m, const char* name, float* dst, size
   // the k best columns after a MERGED forward are the calling thread's own utterances' rows: its note says which context served it
   // and which of that forward's utterances are its own (the rule of pfhip_svs_align); without a valid note: this handle's last forward
   SvsNoteView own;
-  if (is_svs(m) && (nm == "ctc_topk_ids" || nm == "ctc_topk_logp")) {
+  if (is_svs(m) && (nm == "ctc_topk_ids" || nm == "ctc_topk_logp" || nm == "beam_lm_score")) {
     own = svs_thread_note(m);
     if (own.ctx) m = own.ctx;
   }
+  // a Paraformer's biased search ran on the slot that served this thread's last forward
+  if (!is_svs(m) && nm == "beam_lm_score" && last_replica() && last_replica()->group_head == m) m = last_replica();
   std::lock_guard<std::mutex> lk(m->mu);
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t s = m->prof_stream ? m->prof_stream : m->own_stream;
   const void* src = nullptr;
   size_t n = 0;
   const int d = m->weights->cfg.d_model;
+  // The language model's share of every hypothesis of the last search that walked one (pfhip_set_token_lm): [batch][stride] as the
+  // search's own outputs are laid out — after a merged forward the calling thread's own utterances, on their own stride
+  if (nm == "beam_lm_score") {
+    if (!m->beam_lm_stride || (int)m->beam_lm_nbest.size() != m->B)
+      return fail(PFHIP_ERR_ARG, "beam_lm_score: the last forward here searched without a token language model");
+    int u0 = 0, nu = m->B;
+    if (own.ctx == m && m->svs_fwd_ok && m->svs_serial == own.serial && own.u0 >= 0 && own.batch > 0 && own.u0 + own.batch <= m->B) {
+      u0 = own.u0; nu = own.batch;
+    }
+    int stride = 1;
+    for (int u = u0; u < u0 + nu; ++u) stride = std::max(stride, m->beam_lm_nbest[(size_t)u]);
+    n = (size_t)nu * stride;
+    if (n_out) *n_out = n;
+    if (n > cap_floats) return fail(PFHIP_ERR_CAPACITY, "dst too small");
+    const int fs = m->beam_lm_stride;
+    std::vector<float> all((size_t)m->B * fs);
+    HIP_TRY(hipMemcpyAsync(all.data(), m->beam_lm.p, all.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int u = 0; u < nu; ++u)
+      for (int j = 0; j < stride; ++j) dst[(size_t)u * stride + j] = j < fs ? all[(size_t)(u0 + u) * fs + j] : 0.f;
+    return PFHIP_OK;
+  }
   if (nm == "feats") { src = m->feats.p; n = (size_t)m->M * m->weights->feat_dim; }
   else if (nm == "enc") { src = m->weights->cfg.svs ? m->x.p : m->enc.p; n = (size_t)m->M * d; }      // SenseVoice: the rows after tp.norm
   else if (nm == "lse" && m->weights->cfg.svs) { src = m->svs_lse.p; n = (size_t)m->M; }             // the rows' log-sum-exp either CTC head kept

@@ -143,6 +143,22 @@ pfhip_status bias_search_locked(pfhip_model* m, hipStream_t s) {
   int32_t *r_nhyp = m->bias_res.i(), *r_ntok = r_nhyp + B, *r_ids = r_ntok + bn;
   float *r_score = reinterpret_cast<float*>(r_ids + bn * mt), *r_am = r_score + bn, *r_ctx = r_am + bn;
   Scope sc(m, s, K_HEAD, 0, 8.0 * ML * k + 8.0 * ML * nb.beam_stride);
+  m->beam_lm_stride = 0;
+  if (m->fw_lm) {
+    // pfhip_set_token_lm: the instantiation that walks the model, whose image lies on the device already; each hypothesis's share of
+    // the total stays on the device for pfhip_get_tensor "beam_lm_score"
+    HIP_TRY(m->beam_lm.ensure(std::max<size_t>(bn, 1) * 4));
+    if (!pfhip::launch_nbest_ctx_beam_lm(m->nb_ids.i(), m->nb_logp.f(), k, ML, m->m_tok_off, m->m_tok_len, m->counts.i() + B, B, m->weights->cfg.vocab,
+                                         reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                         reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), nb.n_graphs,
+                                         m->fw_lm->dev, nb.beam_stride, ns, mt, r_nhyp, r_ids, r_ntok, r_score, r_am, r_ctx, m->beam_lm.f(),
+                                         dev + front, nodes, s))
+      return fail(PFHIP_ERR_ARG, "hotword beam search with a language model refused its arguments");
+    m->beam_lm_stride = ns;
+    m->beam_lm_nbest.resize((size_t)B);
+    for (int b = 0; b < B; ++b) m->beam_lm_nbest[(size_t)b] = nb.utt[b].first_beam > 0 ? nb.utt[b].nbest : 0;
+    return PFHIP_OK;
+  }
   if (!pfhip::launch_nbest_ctx_beam(m->nb_ids.i(), m->nb_logp.f(), k, ML, m->m_tok_off, m->m_tok_len, m->counts.i() + B, B, m->weights->cfg.vocab,
                                     reinterpret_cast<const pfhip::BeamUtt*>(dev),
                                     reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), nb.n_graphs,
@@ -422,13 +438,21 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
                                  d_score, m->al_ws.p, ws, s))
       return fail(PFHIP_ERR_ARG, "CTC alignment refused its arguments");
   }
-  if (fb && (int)m->svs_beam_utt.size() == B) {
+  const bool per_utt_beams = (int)m->svs_beam_utt.size() == B;
+  m->beam_lm_stride = 0;                                             // "beam_lm_score" lives until the context's next forward, searching or not
+  if (fb && (per_utt_beams || m->fw_lm)) {
     // The search with every utterance on its own beams and graph (pfhip_svs_forward_beam_sets, merged beam callers): fb, sb and nb
     // are the maxima — the columns' stride, the node stride and the hypothesis stride.  Descriptors, the graph table and the images
     // of the graphs the device's bank does not hold go to the front of the search's workspace in one copy from pinned staging.
-    const int G = (int)m->svs_beam_graphs.size();
-    const pfhip_ctx_graph* const* graphs = m->svs_beam_graphs.data();
-    const void* const* resident = (int)m->svs_graph_dev.size() == G && G > 0 ? m->svs_graph_dev.data() : nullptr;
+    // With a token n-gram language model (pfhip_set_token_lm) the one-set form comes here too, as descriptors that all say the
+    // same: the model is walked by the per-utterance kernel's own instantiation.
+    std::vector<pfhip::BeamUtt> same;
+    const pfhip_ctx_graph* one_graph = m->svs_beam_graph;
+    if (!per_utt_beams) same.assign((size_t)B, pfhip::BeamUtt{fb, sb, nb, one_graph ? 0 : -1});
+    const pfhip::BeamUtt* const utts = per_utt_beams ? m->svs_beam_utt.data() : same.data();
+    const int G = per_utt_beams ? (int)m->svs_beam_graphs.size() : one_graph ? 1 : 0;
+    const pfhip_ctx_graph* const* graphs = per_utt_beams ? m->svs_beam_graphs.data() : &one_graph;
+    const void* const* resident = per_utt_beams && (int)m->svs_graph_dev.size() == G && G > 0 ? m->svs_graph_dev.data() : nullptr;
     // Behind them, in the same copy, the speech rows of every utterance [B] (m_speech_len holds those of the span callers only).
     const size_t lens = pfhip::beam_front_bytes(B, graphs, G, resident), front = lens + ((size_t)B * 4 + 15) / 16 * 16;
     const size_t nodes = pfhip::ctc_prefix_beam_workspace_bytes(M, B, sb);
@@ -437,12 +461,24 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
     char* const dev = static_cast<char*>(m->svs_beam_ws.p);
     char* const stage = static_cast<char*>(m->svs_beam_stage.p);
     std::memset(stage, 0, front);
-    pfhip::beam_front_fill(stage, dev, m->svs_beam_utt.data(), B, graphs, G, resident);
+    pfhip::beam_front_fill(stage, dev, utts, B, graphs, G, resident);
     for (int b = 0; b < B; ++b) reinterpret_cast<int*>(stage + lens)[b] = m->T[b] > 4 ? m->T[b] - 4 : 0;
     HIP_TRY(hipMemcpyAsync(dev, stage, front, hipMemcpyHostToDevice, s));
     const size_t bn = (size_t)B * nb;
     int32_t *b_nhyp = dn + n_span, *b_ntok = b_nhyp + B, *b_ids = b_ntok + bn;
     float *b_score = reinterpret_cast<float*>(b_ids + bn * bmt), *b_ctc = b_score + bn, *b_ctx = b_ctc + bn;
+    if (m->fw_lm) {
+      HIP_TRY(m->beam_lm.ensure(std::max<size_t>(bn, 1) * 4));
+      if (!pfhip::launch_ctc_prefix_beam_multi_lm(m->svs_topk_ids.i(), m->svs_topk_logp.f(), fb, M, m->m_feat_off, reinterpret_cast<const int*>(dev + lens),
+                                                  B, V, c.blank_id, reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                                  reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), G,
+                                                  m->fw_lm->dev, sb, nb, bmt, b_nhyp, b_ids, b_ntok, b_score, b_ctc, b_ctx, m->beam_lm.f(),
+                                                  dev + front, nodes, s))
+        return fail(PFHIP_ERR_ARG, "CTC prefix beam search with a language model refused its arguments");
+      m->beam_lm_stride = nb;
+      m->beam_lm_nbest.resize((size_t)B);
+      for (int b = 0; b < B; ++b) m->beam_lm_nbest[(size_t)b] = utts[b].first_beam > 0 ? utts[b].nbest : 0;
+    } else
     if (!pfhip::launch_ctc_prefix_beam_multi(m->svs_topk_ids.i(), m->svs_topk_logp.f(), fb, M, m->m_feat_off, reinterpret_cast<const int*>(dev + lens), B, V, c.blank_id,
                                              reinterpret_cast<const pfhip::BeamUtt*>(dev),
                                              reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), G, sb, nb, bmt,
@@ -494,6 +530,7 @@ pfhip_status svs_head_locked(pfhip_model* m, hipStream_t s) {
 }
 
 pfhip_status head_locked(pfhip_model* m, hipStream_t s, bool want_logp) {
+  m->beam_lm_stride = 0;                                             // "beam_lm_score" lives until the context's next forward, searching or not
   if (m->ML == 0) return PFHIP_OK;
   const int V = m->weights->cfg.vocab;
   if (want_logp) HIP_TRY(m->logp.ensure((size_t)m->ML * V * 4));

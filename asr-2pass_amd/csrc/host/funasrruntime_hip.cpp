@@ -347,6 +347,11 @@ void FunOfflineSetCtcStamps(FUNASR_HANDLE handle, int on) {
   OfflineStreamHip* os = static_cast<OfflineStreamHip*>(handle);
   if (os && os->svs) os->svs_ctc_stamps.store(on != 0);
 }
+int FunOfflineLoadTokenLm(FUNASR_HANDLE handle, const char* arpa_path, float scale, float token_bonus) {
+  OfflineStreamHip* os = static_cast<OfflineStreamHip*>(handle);
+  if (!os || !arpa_path) return 0;
+  return (os->svs ? os->svs->InitTokenLm(arpa_path, scale, token_bonus) : os->asr.InitTokenLm(arpa_path, scale, token_bonus)) ? 1 : 0;
+}
 void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode) { if (handle) static_cast<OfflineStreamHip*>(handle)->asr.SetCifTimestamps(mode); }
 const std::vector<float>& FunASRGetTokenConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->confidence; }
 const std::vector<float>& FunASRGetOnlineConfidence(FUNASR_RESULT result) { return static_cast<RecogResult*>(result)->online_conf; }
@@ -437,6 +442,12 @@ FUNASR_HANDLE FunTpassOnlineInit(FUNASR_HANDLE tpass_handle, std::vector<int> ch
   }
   if (ts->detail_k > 0) os->asr_online->SetDetail(ts->detail_k, true);      // FunTpassSetNbest
   return os.release();
+}
+
+int FunTpassLoadTokenLm(FUNASR_HANDLE tpass_handle, const char* arpa_path, float scale, float token_bonus) {
+  TpassStreamHip* ts = static_cast<TpassStreamHip*>(tpass_handle);
+  if (!ts || !arpa_path) return 0;
+  return (ts->svs ? ts->svs->InitTokenLm(arpa_path, scale, token_bonus) : ts->asr.InitTokenLm(arpa_path, scale, token_bonus)) ? 1 : 0;
 }
 
 void FunTpassSetNbest(FUNASR_HANDLE tpass_handle, int k) {

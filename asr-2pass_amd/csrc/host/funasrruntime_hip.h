@@ -132,6 +132,11 @@ const std::vector<int>& FunASRGetOnlineFireMs(FUNASR_RESULT result);
 // FunASRGetStamp in its usual "[[b,e],...]" form, one pair per character of the text, VAD segment offsets added; resolution is one
 // LFR row (60 ms), and they are not the head's stamps.  FunTpassSetCifStamps does the same for the offline pass of the 2-pass flow.
 void FunOfflineSetCifStamps(FUNASR_HANDLE handle, int mode);
+// A token n-gram language model for the handle's acoustic model (an extension; ParaformerHip::InitTokenLm /
+// SenseVoiceSmallHip::InitTokenLm): an ARPA file over the model's own tokens — not LM_DIR's TLG.fst, which is read (or not) as before.
+// From then on an inference call with a FunASRCtcDecoderInit handle searches with the model, hotwords or none.  1: loaded, 0: not.
+int FunOfflineLoadTokenLm(FUNASR_HANDLE handle, const char* arpa_path, float scale = 1.0f, float token_bonus = 0.0f);
+int FunTpassLoadTokenLm(FUNASR_HANDLE tpass_handle, const char* arpa_path, float scale = 1.0f, float token_bonus = 0.0f);
 // Time stamps for SenseVoiceSmall by CTC forced alignment (an extension: the reference's SenseVoiceSmall fills no stamps).
 // FunOfflineSetCtcStamps(h, on) switches what SenseVoiceSmallHip::SetCtcTimestamps switches, for every following FunOfflineInferBuffer
 // on the handle (nothing on a Paraformer handle); the switch is kept on the handle and applied call by call — the adapter's

@@ -5,6 +5,9 @@
 // With the two beams: one more pass through a decoder handle (FunASRCtcDecoderInit -> FunOfflineInferBuffer(dec_handle)) before any
 // hotword is loaded ("dec_seg ...", "dec_text", "dec_stamp"), then with the hotwords (FunCtcDecoderLoadHwsRes: "hw_loaded <n>",
 // "hw_seg ...", "hw_text", "hw_stamp", "hw_confidence ..."); nbest and cif_stamps, where given, stay on for both.
+// PFHIP_TOKEN_LM=<arpa file> (with PFHIP_TOKEN_LM_SCALE / PFHIP_TOKEN_LM_BONUS, defaults 1 / 0) in the environment: the file is
+// loaded with FunOfflineLoadTokenLm behind the passes without a decoder handle ("lm_loaded <0|1>"), so the "dec" pass — a decoder
+// handle, no hotwords — is the search with the model and the "hw" pass the search with both.
 // Prints one line per VAD segment, time order: "seg <start_sample> <end_sample> : <ids...>", then timing; with threads > 1
 // every thread transcribes the same buffer through the shared handle (the server's decoder threads).
 #include <atomic>
@@ -64,6 +67,10 @@ int main(int argc, char** argv) {
       std::printf("cif_text %s\ncif_stamp %s\n", FunASRGetResult(q, 0), FunASRGetStamp(q));
       FunASRFreeResult(q);
       FunOfflineSetCifStamps(h, 0);
+    }
+    if (const char* lm = std::getenv("PFHIP_TOKEN_LM")) {
+      const char *sc = std::getenv("PFHIP_TOKEN_LM_SCALE"), *bo = std::getenv("PFHIP_TOKEN_LM_BONUS");
+      std::printf("lm_loaded %d\n", FunOfflineLoadTokenLm(h, lm, sc ? (float)std::atof(sc) : 1.0f, bo ? (float)std::atof(bo) : 0.0f));
     }
     if (argc > 12) {
       if (nbest > 0) FunOfflineSetNbest(h, nbest);

@@ -139,6 +139,39 @@ pfhip_model* LoadOnlineModelHip(const std::string& en_model, const std::string& 
   return h;
 }
 HipVocab* LoadVocabHip(const std::string& token_file) { return LoadVocab(token_file); }
+
+bool LoadTokenLmHip(pfhip_model* handle, HipVocab* vocab, const std::string& arpa_path, float scale, float token_bonus) {
+#ifdef PFHIP_WITH_FUNASR
+  (void)handle; (void)vocab; (void)scale; (void)token_bonus;
+  std::fprintf(stderr, "InitTokenLm: %s is not loaded (the device search is not compiled into this build)\n", arpa_path.c_str());
+  return false;
+#else
+  if (!handle || !vocab || vocab->Size() != pfhip_vocab_size(handle)) {
+    std::fprintf(stderr, "InitTokenLm: %s is not loaded (it needs the model and its tokens.json, one string per token id)\n", arpa_path.c_str());
+    return false;
+  }
+  std::vector<std::string> words((size_t)vocab->Size());
+  std::vector<const char*> ptrs(words.size());
+  for (size_t i = 0; i < words.size(); ++i) { words[i] = vocab->Id2String((int)i); ptrs[i] = words[i].c_str(); }
+  pfhip_lm_graph* g = nullptr;
+  long long skipped = 0;
+  // a token the model does not list scores e^-23 (1e-10) before scaling, as an unseen word does in the reference's tools
+  if (pfhip_lm_graph_create_from_arpa(arpa_path.c_str(), ptrs.data(), (int)ptrs.size(), scale, token_bonus, -10.0f, &g, &skipped) != PFHIP_OK) {
+    std::fprintf(stderr, "InitTokenLm: %s\n", pfhip_last_error());
+    return false;
+  }
+  const pfhip_status st = pfhip_set_token_lm(handle, g);            // the image is on the device now: the host graph may go
+  if (st != PFHIP_OK) std::fprintf(stderr, "InitTokenLm: %s\n", pfhip_last_error());
+  else if (skipped) std::fprintf(stderr, "InitTokenLm: %lld n-grams of %s name words that are no tokens of this model\n", skipped, arpa_path.c_str());
+  pfhip_lm_graph_destroy(g);
+  return st == PFHIP_OK;
+#endif
+}
+
+bool ParaformerHip::InitTokenLm(const std::string& arpa_path, float scale, float token_bonus) {
+  has_token_lm_ = LoadTokenLmHip(handle_, vocab, arpa_path, scale, token_bonus);
+  return has_token_lm_;
+}
 std::string OnlineIdsToString(HipVocab* v, const std::vector<int>& ids) {
   if (v) return v->Vector2StringV2(ids);                       // OnlineGreedySearch (paraformer.cpp:362-371): no language argument
   std::string s;
@@ -326,22 +359,23 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
   // Hotwords for any Paraformer (an extension; pfhip_offline_forward_bias): no LM, the handle that came with the call is a
   // CtcPrefixDecoderHip (FunASRCtcDecoderInit), it has hotwords loaded, and the model is no multi-device group.  Anything else —
   // a decoder without hotwords, another decoder class, an LM — takes exactly the path it took before.
-  const pfhip_ctx_graph* bias_graph = nullptr;
+  // With a token LM (InitTokenLm) the search also runs for a handle that holds no hotwords: a graph-less set with the model.
+  bool bias_on = false;
   pfhip_bias_opts bias_opts{1, 1, 1, nullptr};
 #ifndef PFHIP_WITH_FUNASR
   if (!has_lm_ && wfst_decoder && pfhip_group_size(handle_) <= 1)
     if (const CtcPrefixDecoderHip* bd = dynamic_cast<CtcPrefixDecoderHip*>(static_cast<Decoder*>(wfst_decoder))) {
-      bias_graph = bd->Graph();
-      bias_opts = pfhip_bias_opts{std::max(1, std::min({bd->FirstBeam(), 8, V})), std::max(1, std::min(bd->SecondBeam(), 16)), 1, bias_graph};
+      bias_on = bd->Graph() != nullptr || has_token_lm_;
+      bias_opts = pfhip_bias_opts{std::max(1, std::min({bd->FirstBeam(), 8, V})), std::max(1, std::min(bd->SecondBeam(), 16)), 1, bd->Graph()};
     }
 #endif
   // with the search on, a caller who asked for candidates gets rows wide enough to hold the chosen token: its confidence is read there
-  const int kk = bias_graph && nk ? std::max(nk, bias_opts.width) : nk;
+  const int kk = bias_on && nk ? std::max(nk, bias_opts.width) : nk;
   std::vector<int32_t> nb_ids((size_t)(kk ? batch_in : 0) * max_tokens * kk);
   std::vector<float> nb_logp(nb_ids.size());
   std::vector<int32_t> b_nhyp, b_ntok, b_ids;
   pfhip_status st;
-  if (bias_graph) {                               // the detail call plus the search, one set for all utterances of this caller
+  if (bias_on) {                                  // the detail call plus the search, one set for all utterances of this caller
     b_nhyp.assign(batch_in, 0); b_ntok.assign(batch_in, 0); b_ids.assign((size_t)batch_in * max_tokens, 0);
     pfhip_bias_out bout{b_nhyp.data(), b_ids.data(), b_ntok.data(), nullptr, nullptr, nullptr, max_tokens};
     const pfhip_detail det{kk, kk ? nb_ids.data() : nullptr, kk ? nb_logp.data() : nullptr, cif_ts ? fire.data() : nullptr};
@@ -383,7 +417,7 @@ std::vector<std::string> ParaformerHip::ForwardAny(const void* const* din_any, b
     const int n = tn[i] < nf[i] ? tn[i] : nf[i];
     // the search's best hypothesis takes the place of the greedy ids: one token per row, so n, the fire frames and the head's traces
     // stay those of the same rows
-    const bool biased = bias_graph && b_nhyp[i] > 0 && b_ntok[i] == n;
+    const bool biased = bias_on && b_nhyp[i] > 0 && b_ntok[i] == n;
     const int32_t* const best = biased ? b_ids.data() + (size_t)i * max_tokens : ids.data() + (size_t)i * max_tokens;
     tl_last_ids[i].assign(best, best + n);
     if (nk) {

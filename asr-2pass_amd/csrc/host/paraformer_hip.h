@@ -95,6 +95,10 @@ class OnlineModelOwner {
 // encoder and decoder into one Paraformer handle with stream batching on (PFHIP_STREAM_WAIT_US / PFHIP_STREAM_MAX).  Exits on failure.
 pfhip_model* LoadOnlineModelHip(const std::string& en_model, const std::string& de_model, const std::string& am_cmvn,
                                 const std::string& am_config, int device);
+// A token n-gram language model for the device searches of `handle` (pfhip_set_token_lm): the ARPA file's words are matched to the
+// strings of `vocab` (index = token id).  false, with a line on stderr, for a missing vocabulary, an unreadable or damaged file, a
+// multi-device group — and inside the reference tree (PFHIP_WITH_FUNASR), where the search class is not compiled in.
+bool LoadTokenLmHip(pfhip_model* handle, HipVocab* vocab, const std::string& arpa_path, float scale, float token_bonus);
 HipVocab* LoadVocabHip(const std::string& token_file);              // tokens.json, or nullptr for an empty path / unreadable file
 std::string OnlineIdsToString(HipVocab* vocab, const std::vector<int>& ids);      // without a vocabulary: the ids, space separated
 
@@ -136,6 +140,13 @@ class ParaformerHip : public ParaformerHipBase, public OnlineModelOwner
   void InitLm(const std::string& lm_file, const std::string& lm_cfg_file, const std::string& lex_file) override;
   void InitLm(const std::string& lm_file, const std::string& lm_cfg_file, const std::string& lex_file,
               const std::string& lm_units_path) override;
+  // NOT InitLm and no TLG.fst: an ARPA n-gram over THIS MODEL'S TOKENS (tokens.json gives the strings), walked on the device by the
+  // search a CtcPrefixDecoderHip decoder handle stands for (pfhip_set_token_lm).  Once it is loaded, a Forward with such a handle
+  // runs that search even when the handle holds no hotwords (a graph-less set with the model) and its best hypothesis is the text;
+  // without a decoder handle, and without this call, nothing changes.  scale: the model's weight on the natural-log scale;
+  // token_bonus: added per token.  false: nothing was loaded (LoadTokenLmHip says why).
+  bool InitTokenLm(const std::string& arpa_path, float scale = 1.0f, float token_bonus = 0.0f);
+  bool HasTokenLm() const { return has_token_lm_; }
   // Returns batch_in strings.  "" for an utterance without one full fbank window (paraformer.cpp:477-480)
   // and for every item when the device call fails (the reference logs and returns "" too, :582-588).
   // Without an LM: GreedySearch on the device + Vocab::Vector2StringV2 (time-stamp models: Vector2String -> TimestampOnnx ->
@@ -251,6 +262,7 @@ class ParaformerHip : public ParaformerHipBase, public OnlineModelOwner
   int device_ = 0;
   int batch_size_ = 1;
   bool has_lm_ = false;
+  bool has_token_lm_ = false;               // InitTokenLm succeeded: a CtcPrefixDecoderHip handle searches without hotwords too
   int nbest_k_ = 0;                        // SetNbest
   int cif_ts_mode_ = 0;                    // SetCifTimestamps
   bool InText(int id) const;               // whether Vector2StringV2 / PostProcess keep the token of this id

@@ -52,6 +52,10 @@ void SenseVoiceSmallHip::InitLm(const std::string& lm_file, const std::string&, 
                lm_file.c_str());
 }
 
+bool SenseVoiceSmallHip::InitTokenLm(const std::string& arpa_path, float scale, float token_bonus) {
+  return LoadTokenLmHip(handle_, vocab, arpa_path, scale, token_bonus);
+}
+
 void SenseVoiceSmallHip::InitAsr(const std::string& am_model, const std::string& am_cmvn, const std::string& am_config,
                                  const std::string& token_file, int thread_num) {
   (void)thread_num;

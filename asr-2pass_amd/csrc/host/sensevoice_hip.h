@@ -39,6 +39,10 @@ class SenseVoiceSmallHip : public ParaformerHipBase, public OnlineModelOwner
   // having loaded nothing and says so once
   void InitLm(const std::string& lm_file, const std::string& lm_config, const std::string& lex_file) override;
   void InitLm(const std::string& lm_file, const std::string& lm_config, const std::string& lex_file, const std::string& lm_units_path) override;
+  // NOT InitLm and no TLG.fst: an ARPA n-gram over THIS MODEL'S TOKENS (tokens.json gives the strings) for the device search a
+  // CtcPrefixDecoderHip decoder handle stands for (pfhip_set_token_lm; ParaformerHip::InitTokenLm says the rest).  Calls without such a
+  // handle keep serving the greedy text.  false: nothing was loaded.
+  bool InitTokenLm(const std::string& arpa_path, float scale = 1.0f, float token_bonus = 0.0f);
   // the online model ParaformerOnlineHip(this, chunk_size, MODEL_SVS) streams from
   pfhip_model* OnlineHandle() const override { return online_handle_; }
   std::string OnlineTokensToString(const std::vector<int>& ids) override { return OnlineIdsToString(online_vocab_, ids); }

@@ -192,6 +192,15 @@ struct GraphBankDev {
 }  // namespace pfhip_impl
 
 namespace pfhip_impl {
+// The token n-gram language model of a handle (pfhip_set_token_lm): the packed image of an lm_graph.h automaton in device memory this
+// object owns, and the view the searches take (kernels.h).  Immutable once built; a forward holds a reference for its length.
+struct TokenLm {
+  DevMem image;
+  pfhip::LmGraphDev dev;
+};
+}  // namespace pfhip_impl
+
+namespace pfhip_impl {
 // a number no other handle of the process ever had: what a thread's note of "my last forward ran there" is matched on (an address
 // can be that of a handle destroyed since)
 inline uint64_t next_model_uid() { static std::atomic<uint64_t> n{0}; return ++n; }
@@ -267,6 +276,16 @@ struct pfhip_model {
   // the results on the device and on the host (n_hyp [B] | n_tokens [B][nb] | ids [B][nb][bias_mt] | score, am, ctx [B][nb]), which
   // cross with the forward's other results in front of fetch_once's synchronise
   const pfhip_impl::NarBias* bias = nullptr;
+  // pfhip_set_token_lm: on the handle the caller holds, the model every search of its forwards walks (null: none), under lm_mu; on
+  // the executing slot, fw_lm: the model of the forward being run (a range-guard re-run reads it again) and, of the last forward that
+  // searched with one, each hypothesis's share of the total [B][beam_lm_stride] on the device with every utterance's nbest (0: it did
+  // not search) — what pfhip_get_tensor "beam_lm_score" reads; beam_lm_stride 0: that forward had no model
+  std::mutex lm_mu;
+  std::shared_ptr<const pfhip_impl::TokenLm> token_lm;
+  const pfhip_impl::TokenLm* fw_lm = nullptr;
+  Buf beam_lm;
+  int beam_lm_stride = 0;
+  std::vector<int> beam_lm_nbest;
   Buf bias_ws, bias_res;
   PinBuf bias_stage, h_bias;
   int bias_mt = 0;

@@ -403,6 +403,37 @@ bool launch_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int 
                            const int* len_cap, int B, int V, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int beam_stride, int nbest_stride,
                            int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* am_score, float* ctx_score,
                            void* workspace, size_t workspace_bytes, hipStream_t s);
+// ---- token n-gram language model (lm_graph.h on the device; lm_step.h walks it, lm_score.hip scores sentences with it) ------------
+// n_states == 0: no model.  Indices are the host builder's, validated there; lm_step clamps them all the same.
+constexpr int kLmOrderMax = 6;
+struct LmGraphDev {
+  const float* uni_w = nullptr;                  // [vocab + 1]
+  const int32_t* uni_next = nullptr;             // [vocab + 1]
+  const int32_t* arc_begin = nullptr;            // [n_states + 1]
+  const float* backoff_w = nullptr;              // [n_states]
+  const int32_t* backoff_state = nullptr;        // [n_states]
+  const int32_t* arc_label = nullptr;            // [n_arcs], sorted inside a state
+  const int32_t* arc_next = nullptr;
+  const float* arc_weight = nullptr;
+  int n_states = 0, n_arcs = 0, vocab = 0, start = 0, has_eos = 0;
+};
+// One lane per sentence: sentence b is ids[b * max_len .. + len[b]) (device arrays; len clamped to 0 .. max_len, an id clamped to
+// 0 .. vocab - 1).  tok_w [B][max_len]: the weight of every token from the start state on (0 behind the sentence); eos_w [B]: the
+// weight of </s> behind the last token (0 without has_eos); total [B]: their fp32 sum, left to right.  false: nothing launched.
+bool launch_lm_score(const int32_t* ids, const int* len, int B, int max_len, const LmGraphDev& g, float* tok_w, float* eos_w, float* total,
+                     hipStream_t s);
+// The nar_beam.hip search with a language model walked beside the context graph (lm.n_states > 0; lm.vocab == V): every hypothesis
+// also carries the model's state and its score so far, which joins the total; lm_score [B][nbest_stride] is that share (0 behind
+// n_hyp).  Its own kernel instantiation: launch_nbest_ctx_beam runs what it ran before.
+bool launch_nbest_ctx_beam_lm(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len,
+                              const int* len_cap, int B, int V, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, const LmGraphDev& lm,
+                              int beam_stride, int nbest_stride, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
+                              float* am_score, float* ctx_score, float* lm_score, void* workspace, size_t workspace_bytes, hipStream_t s);
+// ... and launch_ctc_prefix_beam_multi the same way (ctc_beam.hip): a hypothesis's model state and score belong to its prefix.
+bool launch_ctc_prefix_beam_multi_lm(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                                     int B, int V, int blank, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, const LmGraphDev& lm,
+                                     int sb_max, int nbest_max, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
+                                     float* ctc_score, float* ctx_score, float* lm_score, void* workspace, size_t workspace_bytes, hipStream_t s);
 // The same head with the k best columns of every row (topk.hip; 1 <= k <= kTopkMax <= V): topk_ids / topk_logp [ML][k], larger logit
 // first, equal logits smaller column first, so topk_ids[.., 0] == ids; a value equals the logp entry of its column bit for bit.  The
 // log-sum-exp is formed with logp null as well.  false (nothing launched) when the arguments are outside that.

@@ -17,9 +17,16 @@
 // that is NaN or below -FLT_MAX counts as -FLT_MAX, a NaN total ranks as -inf: whatever the rows hold, ranks stay unique, every beam
 // slot that is read was written, and every index stays inside its buffer.  Graph indices are the host builder's (ctx_graph.cpp).
 // The final walk from each surviving node to the root writes the ids; it reads nodes other threads wrote, behind a barrier.
+//
+// kLm = true is the same search with a token n-gram language model (lm_step.h) walked beside the context graph: a hypothesis also
+// carries the model's state and its score so far, an extension adds the weight of its token to it, the total takes it as one more
+// fp32 add behind am + ctx, and at the end, where the model has </s>, every live hypothesis takes the weight of </s> (after the context
+// back-off, before the final order).  The model's state and score are a function of the token sequence alone.  kLm = false compiles to
+// what the kernel was before: the model's LDS arrays exist in the kLm = true instantiation alone, the extra arguments are not read.
 #include "ctx_step.h"
 #include "kernels.h"
 #include "launch_common.h"
+#include "lm_step.h"
 
 #include <float.h>
 #include <math.h>
@@ -38,7 +45,25 @@ struct NarBeam {                                 // one buffer of the beam
   float am[kBM], ctx[kBM];
   int state[kBM], node[kBM];
 };
+struct BeamLm {                                  // the model's share of one buffer of the beam (kLm)
+  float lm[kBM];
+  int lm_state[kBM];
+};
+// The LDS of the model's state and score exists in the kLm = true instantiation alone: the arrays are function-local statics of the
+// specialisation that is only called there, so kLm = false keeps the LDS layout, and with it the code, it had before.
+template <bool kLm> struct LmLds;
+template <> struct LmLds<false> {
+  __device__ static __forceinline__ BeamLm* beam() { return nullptr; }
+  __device__ static __forceinline__ float* cand_lm() { return nullptr; }
+  __device__ static __forceinline__ int* cand_state() { return nullptr; }
+};
+template <> struct LmLds<true> {
+  __device__ static __forceinline__ BeamLm* beam() { __shared__ BeamLm b[2]; return b; }
+  __device__ static __forceinline__ float* cand_lm() { __shared__ float a[kNT]; return a; }
+  __device__ static __forceinline__ int* cand_state() { __shared__ int a[kNT]; return a; }
+};
 
+template <bool kLm>
 __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __restrict__ cand_ids, const float* __restrict__ cand_logp, int k,
                                                              long long rows, const int* __restrict__ row_off, const int* __restrict__ len,
                                                              const int* __restrict__ len_cap, int V, int beam_stride, int nbest_stride, int max_tokens,
@@ -47,12 +72,15 @@ __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __re
                                                              float* __restrict__ am_score, float* __restrict__ ctx_score,
                                                              int32_t* __restrict__ node_parent, int32_t* __restrict__ node_token,
                                                              const BeamUtt* __restrict__ utt, const CtxGraphDev* __restrict__ graphs,
-                                                             int n_graphs) {
+                                                             int n_graphs, LmGraphDev lm, float* __restrict__ lm_score) {
   __shared__ NarBeam beam[2];
   __shared__ int fr_id[2][kWM];
   __shared__ float fr_lp[2][kWM];
   __shared__ float c_tot[kNT], c_am[kNT], c_ctx[kNT];
   __shared__ int c_state[kNT];
+  BeamLm* const blm = LmLds<kLm>::beam();                            // null without a model, and then never read
+  float* const c_lm = LmLds<kLm>::cand_lm();
+  int* const c_lm_state = LmLds<kLm>::cand_state();
 
   const int b = blockIdx.x, tid = threadIdx.x;
   const int T = len_cap ? min(len[b], len_cap[b]) : len[b];          // (the model's token rows: fires capped by the token count)
@@ -62,6 +90,7 @@ __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __re
   for (int j = tid; j < nbest_stride; j += kNT) {
     n_tokens[o_h + j] = 0;
     score[o_h + j] = -INFINITY; am_score[o_h + j] = -INFINITY; ctx_score[o_h + j] = 0.f;
+    if constexpr (kLm) lm_score[o_h + j] = 0.f;
   }
   for (size_t j = tid; j < (size_t)nbest_stride * max_tokens; j += kNT) out_ids[o_h * max_tokens + j] = -1;
   // the rows must lie inside the arrays (row_off and len are device data the launcher could not see), and the descriptor inside the
@@ -95,6 +124,7 @@ __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __re
   if (tid == 0) {
     NarBeam& h = beam[0];
     h.am[0] = 0.f; h.ctx[0] = 0.f; h.state[0] = 0; h.node[0] = 0;
+    if constexpr (kLm) { blm[0].lm[0] = 0.f; blm[0].lm_state[0] = lm.start; }
   }
   fetch(0);
   __syncthreads();
@@ -118,6 +148,13 @@ __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __re
         cx = cx + w;
       }
       float tot = am + cx;
+      if constexpr (kLm) {
+        float w;
+        c_lm_state[tid] = lm_step(lm, blm[t & 1].lm_state[h], fid[c], &w);
+        const float l = blm[t & 1].lm[h] + w;
+        c_lm[tid] = l;
+        tot = tot + l;
+      }
       if (tot != tot) tot = -INFINITY;
       c_am[tid] = am; c_ctx[tid] = cx; c_state[tid] = st; c_tot[tid] = tot;
     }
@@ -134,6 +171,7 @@ __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __re
         const int node = 1 + t * beam_stride + rk;                   // <= T * beam_stride
         npar[node - 1] = cur.node[h]; ntok[node - 1] = fid[c];
         nxt.am[rk] = c_am[tid]; nxt.ctx[rk] = c_ctx[tid]; nxt.state[rk] = c_state[tid]; nxt.node[rk] = node;
+        if constexpr (kLm) { blm[(t + 1) & 1].lm[rk] = c_lm[tid]; blm[(t + 1) & 1].lm_state[rk] = c_lm_state[tid]; }
       }
     }
     if (t + 1 < T) fetch(t + 1);                                     // buffer (t + 1) & 1: not the one this row reads
@@ -148,6 +186,16 @@ __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __re
     const int st = fin.state[tid];
     if (g.n_states > 0 && st != 0) cx = cx + g.escape[min(max(st, 0), g.n_states - 1)];
     float tot = fin.am[tid] + cx;
+    if constexpr (kLm) {
+      float l = blm[T & 1].lm[tid];
+      if (lm.has_eos) {
+        float w;
+        lm_step(lm, blm[T & 1].lm_state[tid], lm.vocab, &w);
+        l = l + w;
+      }
+      c_lm[tid] = l;
+      tot = tot + l;
+    }
     if (tot != tot) tot = -INFINITY;
     c_tot[tid] = tot; c_ctx[tid] = cx;
   }
@@ -159,6 +207,7 @@ __global__ __launch_bounds__(kNT) void nbest_ctx_beam_kernel(const int32_t* __re
   if (rk >= nbest) return;
   n_tokens[o_h + rk] = T;                                            // every row gave one token; the true count, also above max_tokens
   score[o_h + rk] = c_tot[tid]; am_score[o_h + rk] = fin.am[tid]; ctx_score[o_h + rk] = c_ctx[tid];
+  if constexpr (kLm) lm_score[o_h + rk] = c_lm[tid];
   int32_t* const dst = out_ids + (o_h + rk) * max_tokens;
   int node = fin.node[tid];
   const int cap = T * beam_stride;                                   // the last node of this utterance
@@ -192,10 +241,14 @@ bool nbest_ctx_beam_check(const BeamUtt* utt, int B, int k, int n_graphs, bool a
   return true;
 }
 
-bool launch_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len,
-                           const int* len_cap, int B, int V, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int beam_stride, int nbest_stride,
-                           int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* am_score, float* ctx_score,
-                           void* workspace, size_t workspace_bytes, hipStream_t s) {
+namespace {
+
+template <bool kLm>
+bool launch_nar(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len, const int* len_cap, int B,
+                int V, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, const LmGraphDev& lm, int beam_stride, int nbest_stride,
+                int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* am_score, float* ctx_score, float* lm_score,
+                void* workspace, size_t workspace_bytes, hipStream_t s) {
+  if (kLm && (lm.n_states < 1 || lm.n_arcs < 0 || lm.vocab != V || lm.start < 0 || lm.start >= lm.n_states)) return false;
   if (B < 0 || B > 65535 || rows < 0 || k < 1 || k > kNarWidthMax || beam_stride < 1 || beam_stride > kBeamMax || nbest_stride < 1 ||
       nbest_stride > beam_stride || n_graphs < 0 || V < 1 || max_tokens < 0 || rows * beam_stride + 1 > 0x7fffffffLL)
     return false;
@@ -204,11 +257,33 @@ bool launch_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int 
       (max_tokens > 0 && !ids) || (rows > 0 && (!cand_ids || !cand_logp)) || !workspace ||
       workspace_bytes < nbest_ctx_beam_workspace_bytes(rows, B, beam_stride))
     return false;
+  if (kLm && (!lm_score || !lm.uni_w || !lm.uni_next || !lm.arc_begin || !lm.backoff_w || !lm.backoff_state ||
+              (lm.n_arcs > 0 && (!lm.arc_label || !lm.arc_next || !lm.arc_weight))))
+    return false;
   int32_t* const node_parent = static_cast<int32_t*>(workspace);
   int32_t* const node_token = node_parent + std::max<size_t>((size_t)rows * beam_stride, 1);
-  hipLaunchKernelGGL(nbest_ctx_beam_kernel, dim3(B), dim3(kNT), 0, s, cand_ids, cand_logp, k, rows, row_off, len, len_cap, V, beam_stride, nbest_stride,
-                     max_tokens, n_hyp, ids, n_tokens, score, am_score, ctx_score, node_parent, node_token, utt, graphs, n_graphs);
+  hipLaunchKernelGGL(nbest_ctx_beam_kernel<kLm>, dim3(B), dim3(kNT), 0, s, cand_ids, cand_logp, k, rows, row_off, len, len_cap, V, beam_stride,
+                     nbest_stride, max_tokens, n_hyp, ids, n_tokens, score, am_score, ctx_score, node_parent, node_token, utt, graphs, n_graphs, lm,
+                     lm_score);
   return true;
+}
+
+}  // namespace
+
+bool launch_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len,
+                           const int* len_cap, int B, int V, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, int beam_stride, int nbest_stride,
+                           int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* am_score, float* ctx_score,
+                           void* workspace, size_t workspace_bytes, hipStream_t s) {
+  return launch_nar<false>(cand_ids, cand_logp, k, rows, row_off, len, len_cap, B, V, utt, graphs, n_graphs, LmGraphDev(), beam_stride, nbest_stride,
+                           max_tokens, n_hyp, ids, n_tokens, score, am_score, ctx_score, nullptr, workspace, workspace_bytes, s);
+}
+
+bool launch_nbest_ctx_beam_lm(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len,
+                              const int* len_cap, int B, int V, const BeamUtt* utt, const CtxGraphDev* graphs, int n_graphs, const LmGraphDev& lm,
+                              int beam_stride, int nbest_stride, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score,
+                              float* am_score, float* ctx_score, float* lm_score, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  return launch_nar<true>(cand_ids, cand_logp, k, rows, row_off, len, len_cap, B, V, utt, graphs, n_graphs, lm, beam_stride, nbest_stride, max_tokens,
+                          n_hyp, ids, n_tokens, score, am_score, ctx_score, lm_score, workspace, workspace_bytes, s);
 }
 
 }  // namespace pfhip

@@ -11,6 +11,8 @@ struct HwSets { const float* const* emb; const int* n; int n_sets; const int* of
 struct NarBias {
   const pfhip::BeamUtt* utt; const pfhip_ctx_graph* const* graphs; int n_graphs; int k, beam_stride, nbest_stride; pfhip_bias_out* out;
 };
+// the token n-gram language model of the handle the caller holds (pfhip_set_token_lm; token_lm.cpp), or null
+std::shared_ptr<const TokenLm> token_lm_of(pfhip_model* slot_or_head);
 }  // namespace pfhip_impl
 
 // One caller in the cross-request queue of a handle (pfhip_model::bq; offline_api.cpp states the queue's rules).  A Paraformer handle

@@ -432,8 +432,10 @@ pfhip_status forward_direct(pfhip_model* m, HostPcm pcm, const int* n_samples, i
   m->nbest_k = dt ? dt->nbest_k : 0;
   // the search of pfhip_offline_forward_bias: the head computes the largest k anybody reads; the slot names the search for the
   // length of this call only (a range-guard re-run inside fetch_locked reads it again)
-  struct BiasScope { pfhip_model* m; ~BiasScope() { m->bias = nullptr; } } bias_scope{m};
+  struct BiasScope { pfhip_model* m; ~BiasScope() { m->bias = nullptr; m->fw_lm = nullptr; } } bias_scope{m};
   m->bias = bias;
+  const std::shared_ptr<const TokenLm> lm = bias ? token_lm_of(m) : nullptr;      // pfhip_set_token_lm: the search walks it too
+  m->fw_lm = lm.get();
   if (bias) m->nbest_k = std::max(m->nbest_k, bias->k);
   m->want_fires = dt && dt->fire_frame;
   HotwordPins pins{m};              // held until the results (a range-guard re-run included) are back

@@ -2,6 +2,7 @@
 #include "../../include/pfhip_ops.h"
 
 #include "ctx_graph.h"
+#include "lm_graph.h"
 #include "internal.h"      // build_frontend_tables, DevMem; brings kernels.h
 #include "beam_front.h"
 
@@ -559,6 +560,137 @@ int pfhip_op_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int
                                     reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), n_graphs, beam_max,
                                     nb_max, max_tokens, n_hyp, ids, n_tokens, score, am_score, ctx_score, dev + front,
                                     workspace_bytes - front, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+// the CTC search with a token n-gram language model: its image follows the front block in the call's one copy.  lm == NULL is the
+// sibling entry, argument for argument.
+size_t pfhip_op_ctc_prefix_beam_multi_lm_workspace_bytes(long long rows, int B, int k, const int* first_beam, const int* second_beam,
+                                                         const int* nbest, const int* graph_of, const pfhip_ctx_graph* const* graphs,
+                                                         int n_graphs, const pfhip_lm_graph* lm) {
+  const size_t plain = pfhip_op_ctc_prefix_beam_multi_workspace_bytes(rows, B, k, first_beam, second_beam, nbest, graph_of, graphs, n_graphs);
+  return plain ? plain + pfhip::lm_graph_image_bytes(lm) : 0;
+}
+int pfhip_op_ctc_prefix_beam_multi_lm(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off, const int* len,
+                                      int B, int V, int blank, const int* first_beam, const int* second_beam, const int* nbest,
+                                      const int* graph_of, const pfhip_ctx_graph* const* graphs, int n_graphs, const pfhip_lm_graph* lm,
+                                      int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* ctc_score,
+                                      float* ctx_score, float* lm_score, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!lm_score) return (int)hipErrorInvalidValue;
+  std::vector<pfhip::BeamUtt> utt;
+  int sb_max = 1, nb_max = 1;
+  if (!lm) {
+    const int e = pfhip_op_ctc_prefix_beam_multi(topk_ids, topk_logp, k, rows, row_off, len, B, V, blank, first_beam, second_beam, nbest, graph_of,
+                                                 graphs, n_graphs, max_tokens, n_hyp, ids, n_tokens, score, ctc_score, ctx_score, workspace,
+                                                 workspace_bytes, stream);
+    if (e != 0 || B == 0) return e;
+    beam_multi_args(first_beam, second_beam, nbest, graph_of, B, k, graphs, n_graphs, V, &utt, &sb_max, &nb_max);      // passed above
+    const hipError_t z = hipMemsetAsync(lm_score, 0, sizeof(float) * (size_t)B * nb_max, S(stream));
+    return z != hipSuccess ? (int)z : done();
+  }
+  if (lm->vocab != V) return (int)hipErrorInvalidValue;
+  if (!beam_multi_args(first_beam, second_beam, nbest, graph_of, B, k, graphs, n_graphs, V, &utt, &sb_max, &nb_max)) return (int)hipErrorInvalidValue;
+  // the launcher's own checks, on a call that launches nothing (B = 0), then the buffers it would refuse at B > 0
+  if (!pfhip::launch_ctc_prefix_beam_multi_lm(topk_ids, topk_logp, k, rows, row_off, len, 0, V, blank, nullptr, nullptr, n_graphs,
+                                              pfhip::lm_graph_dev(lm, nullptr), sb_max, nb_max, max_tokens, n_hyp, ids, n_tokens, score,
+                                              ctc_score, ctx_score, lm_score, nullptr, 0, S(stream)))
+    return (int)hipErrorInvalidValue;
+  const size_t front = pfhip::beam_front_bytes(B, graphs, n_graphs), image = pfhip::lm_graph_image_bytes(lm),
+               nodes = pfhip::ctc_prefix_beam_workspace_bytes(rows, B, sb_max);
+  if (!workspace || workspace_bytes < front + image || workspace_bytes - front - image < nodes) return (int)hipErrorInvalidValue;
+  if (B > 0 && (!row_off || !len || !n_hyp || !n_tokens || !score || !ctc_score || !ctx_score || (max_tokens > 0 && !ids) ||
+                (rows > 0 && (!topk_ids || !topk_logp))))
+    return (int)hipErrorInvalidValue;
+  if (B == 0) return done();
+  char* const dev = static_cast<char*>(workspace);
+  std::vector<char> host(front + image, 0);
+  pfhip::beam_front_fill(host.data(), dev, utt.data(), B, graphs, n_graphs);
+  std::memcpy(host.data() + front, lm->packed.data(), lm->packed.size() * 4);
+  {
+    // pageable memory: the copy has left it when the call returns
+    const hipError_t e = hipMemcpyAsync(dev, host.data(), front + image, hipMemcpyHostToDevice, S(stream));
+    if (e != hipSuccess) return (int)e;
+  }
+  if (!pfhip::launch_ctc_prefix_beam_multi_lm(topk_ids, topk_logp, k, rows, row_off, len, B, V, blank, reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                              reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), n_graphs,
+                                              pfhip::lm_graph_dev(lm, dev + front), sb_max, nb_max, max_tokens, n_hyp, ids, n_tokens, score,
+                                              ctc_score, ctx_score, lm_score, dev + front + image, workspace_bytes - front - image, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+// the search over a non-autoregressive head's candidates the same way
+size_t pfhip_op_nbest_ctx_beam_lm_workspace_bytes(long long rows, int B, int k, const int* width, const int* beam, const int* nbest,
+                                                  const int* graph_of, const pfhip_ctx_graph* const* graphs, int n_graphs,
+                                                  const pfhip_lm_graph* lm) {
+  const size_t plain = pfhip_op_nbest_ctx_beam_workspace_bytes(rows, B, k, width, beam, nbest, graph_of, graphs, n_graphs);
+  return plain ? plain + pfhip::lm_graph_image_bytes(lm) : 0;
+}
+int pfhip_op_nbest_ctx_beam_lm(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off, const int* len, int B,
+                               int V, const int* width, const int* beam, const int* nbest, const int* graph_of,
+                               const pfhip_ctx_graph* const* graphs, int n_graphs, const pfhip_lm_graph* lm, int max_tokens, int32_t* n_hyp,
+                               int32_t* ids, int32_t* n_tokens, float* score, float* am_score, float* ctx_score, float* lm_score,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (!lm_score) return (int)hipErrorInvalidValue;
+  if (!lm) {
+    const int e = pfhip_op_nbest_ctx_beam(cand_ids, cand_logp, k, rows, row_off, len, B, V, width, beam, nbest, graph_of, graphs, n_graphs,
+                                          max_tokens, n_hyp, ids, n_tokens, score, am_score, ctx_score, workspace, workspace_bytes, stream);
+    if (e != 0 || B == 0) return e;
+    int nb_max = 1;
+    for (int b = 0; b < B; ++b) nb_max = std::max(nb_max, nbest[b]);
+    const hipError_t z = hipMemsetAsync(lm_score, 0, sizeof(float) * (size_t)B * nb_max, S(stream));
+    return z != hipSuccess ? (int)z : done();
+  }
+  if (lm->vocab != V) return (int)hipErrorInvalidValue;
+  std::vector<pfhip::BeamUtt> utt;
+  int beam_max = 1, nb_max = 1;
+  if (!nar_beam_args(width, beam, nbest, graph_of, B, k, graphs, n_graphs, V, &utt, &beam_max, &nb_max)) return (int)hipErrorInvalidValue;
+  // the launcher's own checks, on a call that launches nothing (B = 0), then the buffers it would refuse at B > 0
+  const pfhip::LmGraphDev probe = pfhip::lm_graph_dev(lm, nullptr);
+  if (!pfhip::launch_nbest_ctx_beam_lm(cand_ids, cand_logp, k, rows, row_off, len, nullptr, 0, V, nullptr, nullptr, n_graphs, probe, beam_max, nb_max,
+                                       max_tokens, n_hyp, ids, n_tokens, score, am_score, ctx_score, lm_score, nullptr, 0, S(stream)))
+    return (int)hipErrorInvalidValue;
+  const size_t front = pfhip::beam_front_bytes(B, graphs, n_graphs), image = pfhip::lm_graph_image_bytes(lm),
+               nodes = pfhip::nbest_ctx_beam_workspace_bytes(rows, B, beam_max);
+  if (!workspace || workspace_bytes < front + image || workspace_bytes - front - image < nodes) return (int)hipErrorInvalidValue;
+  if (B > 0 && (!row_off || !len || !n_hyp || !n_tokens || !score || !am_score || !ctx_score || (max_tokens > 0 && !ids) ||
+                (rows > 0 && (!cand_ids || !cand_logp))))
+    return (int)hipErrorInvalidValue;
+  if (B == 0) return done();
+  char* const dev = static_cast<char*>(workspace);
+  std::vector<char> host(front + image, 0);
+  pfhip::beam_front_fill(host.data(), dev, utt.data(), B, graphs, n_graphs);
+  std::memcpy(host.data() + front, lm->packed.data(), lm->packed.size() * 4);
+  {
+    // pageable memory: the copy has left it when the call returns
+    const hipError_t e = hipMemcpyAsync(dev, host.data(), front + image, hipMemcpyHostToDevice, S(stream));
+    if (e != hipSuccess) return (int)e;
+  }
+  if (!pfhip::launch_nbest_ctx_beam_lm(cand_ids, cand_logp, k, rows, row_off, len, nullptr, B, V, reinterpret_cast<const pfhip::BeamUtt*>(dev),
+                                       reinterpret_cast<const pfhip::CtxGraphDev*>(dev + pfhip::beam_front_table_off(B)), n_graphs,
+                                       pfhip::lm_graph_dev(lm, dev + front), beam_max, nb_max, max_tokens, n_hyp, ids, n_tokens, score, am_score,
+                                       ctx_score, lm_score, dev + front + image, workspace_bytes - front - image, S(stream)))
+    return (int)hipErrorInvalidValue;
+  return done();
+}
+// sentences scored by the model (lm_score.hip): the image goes to the workspace first
+size_t pfhip_op_lm_score_workspace_bytes(const pfhip_lm_graph* lm) { return pfhip::lm_graph_image_bytes(lm); }
+int pfhip_op_lm_score(const int32_t* ids, const int* len, int B, int max_len, const pfhip_lm_graph* lm, float* tok_w, float* eos_w, float* total,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  static_assert(pfhip::kLmOrderMax == PFHIP_LM_ORDER_MAX, "one cap for the builder and the device loop");
+  if (!lm || B < 0 || max_len < 0) return (int)hipErrorInvalidValue;
+  const size_t image = pfhip::lm_graph_image_bytes(lm);
+  if (!workspace || workspace_bytes < image) return (int)hipErrorInvalidValue;
+  if (!pfhip::launch_lm_score(ids, len, 0, max_len, pfhip::lm_graph_dev(lm, nullptr), tok_w, eos_w, total, S(stream)) ||
+      (long long)B * max_len > 0x7fffffffLL)
+    return (int)hipErrorInvalidValue;
+  if (B > 0 && (!len || !eos_w || !total || (max_len > 0 && (!ids || !tok_w)))) return (int)hipErrorInvalidValue;
+  if (B == 0) return done();
+  {
+    // the graph's memory is the handle's and pageable: the copy has left it when the call returns
+    const hipError_t e = hipMemcpyAsync(workspace, lm->packed.data(), lm->packed.size() * 4, hipMemcpyHostToDevice, S(stream));
+    if (e != hipSuccess) return (int)e;
+  }
+  if (!pfhip::launch_lm_score(ids, len, B, max_len, pfhip::lm_graph_dev(lm, workspace), tok_w, eos_w, total, S(stream)))
     return (int)hipErrorInvalidValue;
   return done();
 }

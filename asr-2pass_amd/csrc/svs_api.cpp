@@ -331,7 +331,9 @@ pfhip_status svs_forward_direct(pfhip_model* m, HostPcm pcm, const int* n_sample
   m->svs_beam_nbest = beam && !sets ? beam->opts->nbest : 0;
   m->svs_beam_graph = beam && !sets ? beam->opts->graph : nullptr;
   m->svs_beam_utt.clear(); m->svs_beam_graphs.clear(); m->svs_graph_dev.clear();
-  struct GraphPins { pfhip_model* m; ~GraphPins() { svs_release_graphs(m); } } pins{m};      // let go after the forward's last synchronise
+  struct GraphPins { pfhip_model* m; ~GraphPins() { svs_release_graphs(m); m->fw_lm = nullptr; } } pins{m};      // let go after the forward's last synchronise
+  const std::shared_ptr<const TokenLm> lm = beam ? token_lm_of(m) : nullptr;      // pfhip_set_token_lm: the search walks it too
+  m->fw_lm = lm.get();
   int beam_stride = beam && !sets ? beam->opts->nbest : 1;
   if (sets) {
     // every utterance on its own beams: the maxima are the head's k, the node stride and the hypothesis stride (no utterance

@@ -71,6 +71,18 @@ def _lib():
             lib.pfhip_op_nbest_ctx_beam_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci]
             lib.pfhip_op_nbest_ctx_beam.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci,
                                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+        if hasattr(lib, "pfhip_op_lm_score"):
+            lib.pfhip_op_lm_score_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_lm_score_workspace_bytes.argtypes = [_vp]
+            lib.pfhip_op_lm_score.argtypes = [_vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+            lib.pfhip_op_nbest_ctx_beam_lm_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_nbest_ctx_beam_lm_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]
+            lib.pfhip_op_nbest_ctx_beam_lm.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp,
+                                                       _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+            lib.pfhip_op_ctc_prefix_beam_multi_lm_workspace_bytes.restype = ctypes.c_size_t
+            lib.pfhip_op_ctc_prefix_beam_multi_lm_workspace_bytes.argtypes = [ctypes.c_longlong, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp]
+            lib.pfhip_op_ctc_prefix_beam_multi_lm.argtypes = [_vp, _vp, _ci, ctypes.c_longlong, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp,
+                                                              _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
         _bound = True
     return lib
 
@@ -583,6 +595,98 @@ def nbest_ctx_beam(cand_ids, cand_logp, row_off, length, vocab, width, beam, nbe
                                     len(graphs), max_tokens, _p(n_hyp), _p(ids) if max_tokens else None, _p(n_tokens), _p(score),
                                     _p(am_score), _p(ctx_score), _p(ws), nbytes, _stream()), "nbest_ctx_beam")
     return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], am_score[:B], ctx_score[:B]
+
+
+def ctc_prefix_beam_multi_lm(topk_ids, topk_logp, row_off, length, vocab, first_beam, second_beam, nbest, lm, graph_of=None, graphs=(),
+                             max_tokens=None, blank=0, workspace_bytes=None, rows=None):
+    """ctc_prefix_beam_multi with a token n-gram language model fused in (pfhip_op_ctc_prefix_beam_multi_lm): lm an LmGraph, or None
+    for the sibling's launch.  Returns ctc_prefix_beam_multi's tuple and lm_score [B, nbest_max] behind it; score includes lm_score."""
+    lib = _lib()
+    if not hasattr(lib, "pfhip_op_ctc_prefix_beam_multi_lm"):
+        raise PfhipError("ctc_prefix_beam_multi_lm: this libpfhip has no pfhip_op_ctc_prefix_beam_multi_lm")
+    all_rows, k = int(topk_ids.shape[0]), int(topk_ids.shape[1])
+    rows = all_rows if rows is None else min(int(rows), all_rows)
+    B = int(row_off.numel())
+    arr = lambda v: (ctypes.c_int * max(B, 1))(*[int(x) for x in v])
+    graph_of = [-1] * B if graph_of is None else graph_of
+    if not (len(first_beam) == len(second_beam) == len(nbest) == len(graph_of) == B):
+        raise PfhipError("ctc_prefix_beam_multi_lm: one first_beam, second_beam, nbest and graph_of per utterance")
+    fb, sb, nb, go = arr(first_beam), arr(second_beam), arr(nbest), arr(graph_of)
+    handles = (ctypes.c_void_p * max(len(graphs), 1))(*[g.handle for g in graphs])
+    lmh = lm.handle if lm is not None else None
+    nb_max = max([int(n) for f, n in zip(first_beam, nbest) if int(f) > 0] + [1])
+    max_tokens = rows if max_tokens is None else int(max_tokens)
+    dev = topk_ids.device
+    n_hyp = torch.full((max(B, 1),), -7, dtype=torch.int32, device=dev)
+    ids = torch.full((max(B, 1), nb_max, max(max_tokens, 1)), -7, dtype=torch.int32, device=dev)
+    n_tokens = torch.full((max(B, 1), nb_max), -7, dtype=torch.int32, device=dev)
+    score, ctc_score, ctx_score, lm_score = (torch.full((max(B, 1), nb_max), float("nan"), dtype=torch.float32, device=dev) for _ in range(4))
+    if workspace_bytes is None:
+        nbytes = int(lib.pfhip_op_ctc_prefix_beam_multi_lm_workspace_bytes(all_rows, B, k, fb, sb, nb, go, handles, len(graphs), lmh))
+    else:
+        nbytes = int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    if max_tokens != ids.shape[2]:
+        ids = ids[:, :, :0]
+    _ck(lib.pfhip_op_ctc_prefix_beam_multi_lm(_p(topk_ids), _p(topk_logp), k, rows, _p(row_off), _p(length), B, int(vocab), int(blank), fb, sb,
+                                              nb, go, handles, len(graphs), lmh, max_tokens, _p(n_hyp), _p(ids) if max_tokens else None,
+                                              _p(n_tokens), _p(score), _p(ctc_score), _p(ctx_score), _p(lm_score), _p(ws), nbytes, _stream()),
+        "ctc_prefix_beam_multi_lm")
+    return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], ctc_score[:B], ctx_score[:B], lm_score[:B]
+
+
+def nbest_ctx_beam_lm(cand_ids, cand_logp, row_off, length, vocab, width, beam, nbest, lm, graph_of=None, graphs=(), max_tokens=None,
+                      workspace_bytes=None, rows=None):
+    """nbest_ctx_beam with a token n-gram language model fused in (pfhip_op_nbest_ctx_beam_lm): lm an LmGraph, or None for the
+    sibling's launch.  Returns nbest_ctx_beam's tuple and lm_score [B, nbest_max] behind it; score includes lm_score."""
+    lib = _lib()
+    if not hasattr(lib, "pfhip_op_nbest_ctx_beam_lm"):
+        raise PfhipError("nbest_ctx_beam_lm: this libpfhip has no pfhip_op_nbest_ctx_beam_lm")
+    all_rows, k = int(cand_ids.shape[0]), int(cand_ids.shape[1])
+    rows = all_rows if rows is None else min(int(rows), all_rows)
+    B = int(row_off.numel())
+    arr = lambda v: (ctypes.c_int * max(B, 1))(*[int(x) for x in v])
+    graph_of = [-1] * B if graph_of is None else graph_of
+    if not (len(width) == len(beam) == len(nbest) == len(graph_of) == B):
+        raise PfhipError("nbest_ctx_beam_lm: one width, beam, nbest and graph_of per utterance")
+    wd, bm, nb, go = arr(width), arr(beam), arr(nbest), arr(graph_of)
+    handles = (ctypes.c_void_p * max(len(graphs), 1))(*[g.handle for g in graphs])
+    lmh = lm.handle if lm is not None else None
+    nb_max = max([int(n) for n in nbest] + [1])
+    max_tokens = rows if max_tokens is None else int(max_tokens)
+    dev = cand_ids.device
+    n_hyp = torch.full((max(B, 1),), -7, dtype=torch.int32, device=dev)
+    ids = torch.full((max(B, 1), nb_max, max(max_tokens, 1)), -7, dtype=torch.int32, device=dev)
+    n_tokens = torch.full((max(B, 1), nb_max), -7, dtype=torch.int32, device=dev)
+    score, am_score, ctx_score, lm_score = (torch.full((max(B, 1), nb_max), float("nan"), dtype=torch.float32, device=dev) for _ in range(4))
+    if workspace_bytes is None:
+        nbytes = int(lib.pfhip_op_nbest_ctx_beam_lm_workspace_bytes(all_rows, B, k, wd, bm, nb, go, handles, len(graphs), lmh))
+    else:
+        nbytes = int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    if max_tokens == 0:                                              # the kernel gets a stride of 0 and no buffer
+        ids = ids[:, :, :0]
+    _ck(lib.pfhip_op_nbest_ctx_beam_lm(_p(cand_ids), _p(cand_logp), k, rows, _p(row_off), _p(length), B, int(vocab), wd, bm, nb, go, handles,
+                                       len(graphs), lmh, max_tokens, _p(n_hyp), _p(ids) if max_tokens else None, _p(n_tokens), _p(score),
+                                       _p(am_score), _p(ctx_score), _p(lm_score), _p(ws), nbytes, _stream()), "nbest_ctx_beam_lm")
+    return n_hyp[:B], ids[:B], n_tokens[:B], score[:B], am_score[:B], ctx_score[:B], lm_score[:B]
+
+
+def lm_score(ids, length, lm):
+    """Sentences scored by a token n-gram language model (csrc/lm_score.hip; pfhip_op_lm_score in include/pfhip_ops.h): ids int32
+    [B, max_len] and length int32 [B] device tensors, lm an LmGraph.  Returns (tok_w [B, max_len], eos_w [B], total [B])."""
+    lib = _lib()
+    if not hasattr(lib, "pfhip_op_lm_score"):
+        raise PfhipError("lm_score: this libpfhip has no pfhip_op_lm_score")
+    B, max_len = int(ids.shape[0]), int(ids.shape[1])
+    dev = ids.device
+    tok_w = torch.full((max(B, 1), max(max_len, 1)), float("nan"), dtype=torch.float32, device=dev)[:, :max_len].contiguous()
+    eos_w, total = (torch.full((max(B, 1),), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
+    nbytes = int(lib.pfhip_op_lm_score_workspace_bytes(lm.handle))
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    _ck(lib.pfhip_op_lm_score(_p(ids) if max_len else None, _p(length), B, max_len, lm.handle, _p(tok_w) if max_len else None, _p(eos_w),
+                              _p(total), _p(ws), nbytes, _stream()), "lm_score")
+    return tok_w[:B], eos_w[:B], total[:B]
 
 
 def ctc_collapse_chunk():

@@ -741,6 +741,69 @@ int pfhip_ctx_graph_vocab(const pfhip_ctx_graph* g);
 pfhip_status pfhip_ctx_graph_dump(const pfhip_ctx_graph* g, int* n_states, int* n_arcs, int32_t* arc_begin, float* escape, int cap_states,
                                   int32_t* arc_label, int32_t* arc_next, float* arc_weight, int cap_arcs);
 
+/* ---- token n-gram language model of the device searches (lm_graph.cpp; host only, no device) ----
+ * A back-off n-gram model over the MODEL'S OWN TOKENS (characters or BPE pieces), as SRILM writes it in ARPA form, for shallow
+ * fusion inside the device searches and for rescoring (pfhip_op_lm_score, pfhip_ops.h).  It is NOT the reference's TLG.fst route
+ * (InitLm): a word-level model needs a lexicon transducer, and BiasLm walks that same WFST; both stay outside this library.
+ * Labels: 0 .. vocab - 1 are token ids, vocab is </s>, vocab + 1 is <s>, vocab + 2 is <unk>.  <s> appears inside histories only: an
+ * n-gram of length >= 2 that predicts <s> is dropped, the unigram <s> gives the state of the history (<s>) and no arc.  <unk> may
+ * only be a unigram (PFHIP_ERR_ARG above order 1) and gives no state.  An n-gram of length >= 2 whose history (its first n - 1
+ * labels) is not itself a kept n-gram is dropped.
+ * pfhip_lm_graph_create: n-grams of length n = 1 .. order (order <= PFHIP_LM_ORDER_MAX), n_grams[n - 1] of each, packed by
+ * length: labels holds n labels per n-gram (oldest first, the predicted label last), log10_prob / log10_backoff one value per
+ * n-gram in the same sequence (back-off 0 where ARPA gives none; the back-off of a highest-order n-gram is not read).
+ * The automaton:
+ *   - state 0 is the empty history; every kept n-gram of length 1 .. order - 1 is a state; states are numbered by history length,
+ *     then lexicographically by labels, oldest label first;
+ *   - state h has one arc per kept n-gram (h, w), sorted by label w; the arc's next state is the longest suffix of (h, w) that is a
+ *     state (0 if none);
+ *   - each state has a back-off weight and a back-off state: the longest PROPER suffix of h that is a state (0 if none), always a
+ *     strictly shorter history, so a chain of back-offs ends in state 0 after at most order - 1 steps;
+ *   - state 0 is direct-indexed by label: uni_w / uni_next [vocab + 1].  A token without a unigram scores <unk>'s unigram where
+ *     there is one, else oov_log10, and leads to state 0.  uni_w[vocab] is only meaningful when has_eos (</s> has a unigram);
+ *   - the start state is the state of the history (<s>) if it exists, else 0.
+ * A step from state s by label w: in state 0 add uni_w[w] and go to uni_next[w]; elsewhere take the arc of s with label w (add its
+ * weight, go to its next state), or add the back-off weight, fall to the back-off state and try again.
+ * Weights are natural logarithms with the scale and the bonus baked in, so that a search only ever adds: an arc (and a uni_w entry)
+ * is fl32((p10 * ln10) * scale + token_bonus), without the bonus where the label is </s>; a back-off weight is
+ * fl32((b10 * ln10) * scale); ln10 = 2.302585092994046, every operation an IEEE double operation on its own, one rounding to float.
+ * PFHIP_ERR_ARG with a pfhip_last_error text: order outside 1 .. PFHIP_LM_ORDER_MAX, a negative count, sizes beyond int32 indices,
+ * a label outside 0 .. vocab + 2, an n-gram listed twice, a non-finite number or a weight that is not finite in fp32.
+ * pfhip_lm_graph_create_from_arpa reads an ARPA file and feeds the entry above.  tokens [vocab]: the model's token strings, UTF-8; a
+ * word is the token id whose string it equals byte for byte (the lowest id among duplicates); <s>, </s> and <unk> are recognised by
+ * name first.  An n-gram with any other unknown word, or with <unk> above order 1, is skipped and counted in *n_skipped (optional).
+ * Numbers are read with strtod.  PFHIP_ERR_ARG with a text: the file cannot be read, no \data\ or \end\ line, a section missing or
+ * out of turn, a count that disagrees with its section, a line with the wrong number of fields, a non-finite or malformed number,
+ * an order above the cap, counts beyond int32 indices.
+ * pfhip_lm_graph_dump (tests): the four counts always; with every array given — uni_w / uni_next [cap_uni >= vocab + 1], arc_begin
+ * [cap_states + 1] (arc_begin[0] == arc_begin[1] == 0: state 0 keeps its arcs in uni_*), backoff_w / backoff_state [cap_states],
+ * arc_label / arc_next / arc_weight [cap_arcs] — the arrays, or PFHIP_ERR_CAPACITY where a cap is too small. */
+#define PFHIP_LM_ORDER_MAX 6
+typedef struct pfhip_lm_graph pfhip_lm_graph;
+/* pfhip_set_token_lm: the model every SEARCH of this handle's forwards walks from now on (shallow fusion; pfhip_ops.h states the
+ * recurrences): pfhip_svs_forward_beam[_s16], pfhip_svs_forward_beam_sets[_s16], merged beam callers (pfhip_svs_set_beam_merging)
+ * and pfhip_offline_forward_bias[_s16] then run the searches' model-walking instantiations.  `score` is the total including the
+ * model's share, ctc_score / am_score and ctx_score keep their meaning, and the share itself is read with pfhip_get_tensor
+ * "beam_lm_score": [batch][stride] laid out as the call's own score array (0 behind n_hyp), the calling thread's last searching
+ * forward, with the lifetime rule of "ctc_topk_*" (until the execution context runs another forward).  `out`, the detail buffers
+ * and the spans stay bit for bit the plain call's; a range-guard re-run redoes the search with the model.  Greedy calls do not read
+ * the model.  The packed image is copied to the handle's device once, into memory the handle owns: the host graph may be destroyed
+ * afterwards.  NULL removes the model; with none set every call launches exactly what it launched before.
+ * PFHIP_ERR_ARG: a graph of another vocabulary, a forward in flight, a handle that is not the one pfhip_create returned.
+ * PFHIP_ERR_UNSUPPORTED: a multi-device group.  This is not InitLm: a TLG.fst is still not read (see above). */
+pfhip_status pfhip_set_token_lm(pfhip_model* m, const pfhip_lm_graph* lm);
+pfhip_status pfhip_lm_graph_create(int order, const int* n_grams, const int32_t* labels, const double* log10_prob,
+                                   const double* log10_backoff, int vocab, float scale, float token_bonus, float oov_log10,
+                                   pfhip_lm_graph** g);
+pfhip_status pfhip_lm_graph_create_from_arpa(const char* path, const char* const* tokens, int vocab, float scale, float token_bonus,
+                                             float oov_log10, pfhip_lm_graph** g, long long* n_skipped);
+void pfhip_lm_graph_destroy(pfhip_lm_graph* g);
+int pfhip_lm_graph_vocab(const pfhip_lm_graph* g);
+int pfhip_lm_graph_order(const pfhip_lm_graph* g);
+pfhip_status pfhip_lm_graph_dump(const pfhip_lm_graph* g, int* n_states, int* n_arcs, int* start, int* has_eos, float* uni_w,
+                                 int32_t* uni_next, int cap_uni, int32_t* arc_begin, float* backoff_w, int32_t* backoff_state,
+                                 int cap_states, int32_t* arc_label, int32_t* arc_next, float* arc_weight, int cap_arcs);
+
 /* pfhip_svs_forward[_s16] with the CTC prefix beam search — and, through a context graph, hotwords — behind its head: what the
  * reference's servers run for this model through a CtcPrefixDecoder per connection (funasrruntime.cpp:836-894,
  * sensevoice-small.cpp:651-657, ctc-prefix-decoder.cpp:157-299).  The head runs ONCE, in its top-k form with k = first_beam

@@ -303,6 +303,56 @@ int pfhip_op_nbest_ctx_beam(const int32_t* cand_ids, const float* cand_logp, int
                             const struct pfhip_ctx_graph* const* graphs, int n_graphs, int max_tokens, int32_t* n_hyp, int32_t* ids,
                             int32_t* n_tokens, float* score, float* am_score, float* ctx_score, void* workspace,
                             size_t workspace_bytes, void* stream);
+/* The token n-gram language model of pfhip.h (pfhip_lm_graph_*) on the device.  lm_step(state, label) is the step pfhip.h states:
+ * acc = 0; in state 0: acc += uni_w[label], next = uni_next[label]; elsewhere a binary search over the state's arcs — found: acc +=
+ * weight, next = the arc's; not found: acc += backoff_w[state], state = backoff_state[state], again (at most PFHIP_LM_ORDER_MAX
+ * trips, then state 0).  Every addition is a single fp32 add in that order; every index is clamped into its array.
+ * pfhip_op_lm_score (lm_score.hip) — N-best rescoring and perplexity: sentence b is ids[b][0 .. len[b]) of ids [B][max_len]
+ * (DEVICE arrays; len clamped to 0 .. max_len, an id outside 0 .. vocab - 1 CLAMPED into it), walked from the start state, one
+ * lane per sentence.  tok_w [B][max_len]: acc of every token (0 behind the sentence); eos_w [B]: acc of </s> behind the last
+ * token, 0 where the model has no </s>; total [B]: the fp32 sum of the sentence's tok_w left to right, then + eos_w.  All natural
+ * logarithms with the graph's scale and bonus baked in.  workspace: pfhip_op_lm_score_workspace_bytes(lm) bytes of device memory,
+ * where the call copies the graph's image on `stream`.  hipErrorInvalidValue, before anything is copied or launched: a NULL graph or
+ * buffer (ids / tok_w with max_len 0 excepted), a negative size, B * max_len above 2^31 - 1, a short workspace. */
+struct pfhip_lm_graph;
+size_t pfhip_op_lm_score_workspace_bytes(const struct pfhip_lm_graph* lm);
+int pfhip_op_lm_score(const int32_t* ids, const int* len, int B, int max_len, const struct pfhip_lm_graph* lm, float* tok_w, float* eos_w,
+                      float* total, void* workspace, size_t workspace_bytes, void* stream);
+/* pfhip_op_nbest_ctx_beam with that model fused in shallowly (its own kernel instantiation; one model serves every utterance of the
+ * launch, lm built for vocab == V).  A hypothesis also carries (lm, lm_state): start lm = 0, lm_state = the model's start state.
+ * An extension by tok_c: lm' = lm_h + acc(lm_step(lm_state_h, tok_c)), and total' = (am' + ctx') + lm', one more fp32 add.  End:
+ * behind the context back-off, where the model has </s>, lm += acc(lm_step(lm_state, vocab)); total is formed again the same way
+ * and the order is by total.  lm_score [B][nbest_stride] is the hypothesis's lm (0 behind n_hyp); score includes it, am_score and
+ * ctx_score keep their meaning.  Tie rules, sanitising and the node layout are the sibling's.  lm == NULL: the sibling's launch and
+ * outputs bit for bit, lm_score 0.  The workspace holds the model's image behind the graphs' (one copy for all of it):
+ * pfhip_op_nbest_ctx_beam_lm_workspace_bytes.  Refusals as the sibling's, and a NULL lm_score or a model of another vocabulary. */
+size_t pfhip_op_nbest_ctx_beam_lm_workspace_bytes(long long rows, int B, int k, const int* width, const int* beam, const int* nbest,
+                                                  const int* graph_of, const struct pfhip_ctx_graph* const* graphs, int n_graphs,
+                                                  const struct pfhip_lm_graph* lm);
+int pfhip_op_nbest_ctx_beam_lm(const int32_t* cand_ids, const float* cand_logp, int k, long long rows, const int* row_off,
+                               const int* len, int B, int V, const int* width, const int* beam, const int* nbest, const int* graph_of,
+                               const struct pfhip_ctx_graph* const* graphs, int n_graphs, const struct pfhip_lm_graph* lm,
+                               int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens, float* score, float* am_score,
+                               float* ctx_score, float* lm_score, void* workspace, size_t workspace_bytes, void* stream);
+/* pfhip_op_ctc_prefix_beam_multi with the model fused in shallowly (its own kernel instantiation; one model serves every searching
+ * utterance of the launch, lm built for vocab == V).  A hypothesis also carries (lm, lm_state), a function of its PREFIX alone:
+ * start lm = 0, lm_state = the model's start state; an unchanged hypothesis keeps both; a new extension h + tok gets lm' = lm_h +
+ * acc(lm_step(lm_state_h, tok)); an extension that names a live hypothesis is that hypothesis and keeps that one's (the same
+ * values).  total = (LogAdd(s, ns) + ctx) + lm, one more fp32 add.  End: behind the context back-off, where the model has </s>,
+ * lm += acc(lm_step(lm_state, vocab)); total again, then the order.  lm_score [B][nbest_max] is the hypothesis's lm (0 behind
+ * n_hyp); score includes it, ctc_score and ctx_score keep their meaning.  Everything else is the sibling's.  lm == NULL: the
+ * sibling's launch and outputs bit for bit, lm_score 0.  Workspace: pfhip_op_ctc_prefix_beam_multi_lm_workspace_bytes (the model's
+ * image behind the graphs', one copy for all of it).  Refusals as the sibling's, and a NULL lm_score or a model of another vocabulary. */
+size_t pfhip_op_ctc_prefix_beam_multi_lm_workspace_bytes(long long rows, int B, int k, const int* first_beam, const int* second_beam,
+                                                         const int* nbest, const int* graph_of,
+                                                         const struct pfhip_ctx_graph* const* graphs, int n_graphs,
+                                                         const struct pfhip_lm_graph* lm);
+int pfhip_op_ctc_prefix_beam_multi_lm(const int32_t* topk_ids, const float* topk_logp, int k, long long rows, const int* row_off,
+                                      const int* len, int B, int V, int blank, const int* first_beam, const int* second_beam,
+                                      const int* nbest, const int* graph_of, const struct pfhip_ctx_graph* const* graphs, int n_graphs,
+                                      const struct pfhip_lm_graph* lm, int max_tokens, int32_t* n_hyp, int32_t* ids, int32_t* n_tokens,
+                                      float* score, float* ctc_score, float* ctx_score, float* lm_score, void* workspace,
+                                      size_t workspace_bytes, void* stream);
 /* One streaming window (M <= 32 rows): LayerNormalization (g != NULL; width D <= K) -> MatMul/Gemm (+bias, +residual Adds, Relu)
  * (+ the SAN-M FSMN memory of fsmn_v over the M rows, k = 11) in ONE launch — stream_fused.hip. */
 int pfhip_op_fused_ln_gemm(const float* X, int ldx, int D, const float* g, const float* b, float eps, const float* W, int ldw,
